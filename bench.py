@@ -309,6 +309,38 @@ def timed_region(step, steps: int, warmup: int, sync, lib, profile: bool = True)
     return elapsed, prof, out
 
 
+DUMP_BYTES = 32 << 20
+DUMP_WINDOW = 4096
+
+
+def dump_outputs(y: torch.Tensor, out_dir: str, name: str = "y") -> dict:
+    """--dump-outputs: `y` (what the last timed step returned to its caller) as out_dir/<name>.npy in float32 (float64 when it
+    is float64), so two builds fed the same seeded input can be compared value for value.  Up to DUMP_BYTES it is written whole;
+    a larger output (the default chain returns 7.4 GB) is sampled as rows of DUMP_WINDOW consecutive samples: the head of every
+    signal row (the filters' start-up), then windows at positions drawn from a fixed seed -- the same positions for the same shape."""
+    y = y if y.dtype == torch.float64 else y.float()
+    info = {"file": f"{name}.npy", "output_shape": list(y.shape), "dtype": str(y.dtype).replace("torch.", "")}
+    if y.numel() * y.element_size() <= DUMP_BYTES:
+        arr = y.detach().cpu().numpy()
+        info["sampled"] = False
+    else:
+        T = y.shape[-1]
+        rows = y.numel() // T
+        L = min(T, DUMP_WINDOW)
+        n = DUMP_BYTES // (L * y.element_size())
+        heads = min(rows, n // 2)
+        g = np.random.default_rng(0)
+        r = np.concatenate([np.arange(heads), g.integers(0, rows, n - heads)])
+        s = np.concatenate([np.zeros(heads, np.int64), g.integers(0, T - L + 1, n - heads)])
+        rr = torch.from_numpy(r[:, None]).to(y.device)
+        cc = torch.from_numpy(s[:, None] + np.arange(L)).to(y.device)
+        arr = y.reshape(rows, T)[rr, cc].cpu().numpy()        # (n, L): window i = output row r[i], samples s[i] .. s[i] + L - 1
+        info.update(sampled=True, windows=int(n), window=int(L), seed=0)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, info["file"]), np.ascontiguousarray(arr))
+    return info
+
+
 def group_stats(groups: list[float]) -> dict:
     """min / median / max of the per-step times of the timed groups.  A FIRST group slower than 1.5 x the median of all groups
     (clock ramp after the idle gap, a one-off allocator stall) is dropped and reported as dropped; nothing else is."""
@@ -490,23 +522,29 @@ def main() -> None:
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
                     help="only warm-up + timed steps (for rocprofv3 runs: no stage / variant / single-stream passes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/y.npy (rank 0; a seeded sample when above 32 MB)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        # plain `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU, rendezvous on 127.0.0.1) by
-        # replacing this process with torch.distributed.run on the same command line; rank 0 prints the one JSON line
+        # plain `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU, rendezvous on 127.0.0.1): this
+        # process becomes torch.distributed.run on the same command line; rank 0 prints the one JSON line
         import socket
+
+        from torch.distributed import run as launcher
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
         os.environ.setdefault("OMP_NUM_THREADS", "8")
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-               "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        launcher.main(["--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1", "--master-port", str(port),
+                       os.path.abspath(__file__), *sys.argv[1:]])
+        return
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus} "
                          "(or run plain `python bench.py --gpus N`, which starts the ranks itself)")
@@ -563,6 +601,7 @@ def main() -> None:
 
     elapsed, _, out = timed_region(step, args.steps, args.warmup, sync, lib, profile=False)      # THE timed region: wall clock only
     first_call_ms = timed_region.first_ms
+    dumped = dump_outputs(out, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     out = None
     elapsed_prof, prof, out = timed_region(step, args.steps, 0, sync, lib, profile=True)       # same steps again, with per-kernel events
     # what the process group itself says about its size (an all-reduce of ones over RCCL / gloo), and which device
@@ -914,6 +953,8 @@ def main() -> None:
             line["stages"] = stages
         if variants:
             line["variants"] = variants
+        if dumped:
+            line["dump_outputs"] = dumped
         if gather_ms is not None:
             line["gather_ms"] = round(gather_ms, 2)
             line["value_with_gather"] = round(total_rows * T / (elapsed / args.steps + gather_ms * 1e-3) / 1e6, 1)

@@ -70,3 +70,33 @@ def test_traffic_file_is_consistent():
     pairs4 = round(slab4 * 1e9 / (256 * 4096 * 8))
     extra4 = (mp["measured_read"] - slab4) / (256 * 4096 * 8 / 1e9)
     assert pairs4 == 8 and 0.95 <= extra4 <= 2.4, (pairs4, extra4)
+
+
+def test_timed_steps_and_dumped_outputs(tmp_path, monkeypatch):
+    """--steps K runs exactly K timed steps after W warm-up ones; --dump-outputs writes the last step's output whole when it
+    fits the budget, else a seeded sample of windows (every row's head first) that is the same for the same shape."""
+    import torch
+    import bench
+
+    calls = []
+    el, prof, out = bench.timed_region(lambda: len(calls.append(1) or calls), 5, 2, lambda: None, None, profile=False)
+    assert len(calls) == 7 and out == 7 and el >= 0 and prof == {}
+
+    y = torch.randn(3, 1000, generator=torch.Generator().manual_seed(0))
+    info = bench.dump_outputs(y, str(tmp_path / "whole"))
+    got = np.load(tmp_path / "whole" / "y.npy")
+    assert info["sampled"] is False and got.dtype == np.float32 and np.array_equal(got, y.numpy())
+    assert bench.dump_outputs(y.double(), str(tmp_path / "f64"))["dtype"] == "float64"
+    assert np.load(tmp_path / "f64" / "y.npy").dtype == np.float64
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 16)
+    monkeypatch.setattr(bench, "DUMP_WINDOW", 256)
+    y = torch.randn(4, 50_000, generator=torch.Generator().manual_seed(1))
+    info = bench.dump_outputs(y, str(tmp_path / "a"))
+    a = np.load(tmp_path / "a" / "y.npy")
+    assert info["sampled"] is True and a.shape == (64, 256) and a.nbytes <= 1 << 16 and a.dtype == np.float32
+    assert np.array_equal(a[:4], y[:, :256].numpy())                                      # row heads
+    flat = y.numpy()
+    assert all(any(np.array_equal(w, flat[r, s:s + 256]) for r in range(4) for s in np.flatnonzero(flat[r] == w[0])) for w in a)
+    bench.dump_outputs(y.clone(), str(tmp_path / "b"))
+    assert np.array_equal(np.load(tmp_path / "b" / "y.npy"), a)                            # same positions run to run
