@@ -283,8 +283,6 @@ fir_direct_simple_kernel(const T *__restrict__ x, T *__restrict__ y, const T *__
     }
 }
 
-static int64_t envi_fir(const char *name, int64_t dflt) { return env_i64(name, dflt); }      // read once per process (common.h)
-
 // The last H samples of the logical signal [hist | x] (what the next chunk needs as its history).
 template <typename T>
 __global__ void __launch_bounds__(256)
@@ -331,10 +329,10 @@ void fir_direct_forward(const void *x, void *y, int dtype, int64_t C, int64_t T,
     // ... and so does any job whose 1024-sample tiles are all resident at once (8 workgroups per CU): one round of
     // the plain kernel costs ~40 clocks per tap, one MFMA workgroup walks its 16384-sample tile for ~128 clocks per
     // tap -- the MFMA kernel wins on throughput (2.5 x), not on latency (streaming chunks, 64 x 4096 and the like)
-    const bool few_tiles = C * ceil_div(T, (int64_t)1024) <= envi_fir("TFX_FIR_ONE_ROUND_TILES", 2048);   // 0: MFMA whenever T allows (tests)
-    const bool short_rows = dtype == TFX_F32 && (T < envi_fir("TFX_FIR_MFMA_MIN_T", FIR_NOUT / 4) || few_tiles);
+    const bool few_tiles = C * ceil_div(T, (int64_t)1024) <= env_i64("TFX_FIR_ONE_ROUND_TILES", 2048);   // 0: MFMA whenever T allows (tests)
+    const bool short_rows = dtype == TFX_F32 && (T < env_i64("TFX_FIR_MFMA_MIN_T", FIR_NOUT / 4) || few_tiles);
     if (dtype == TFX_F32 && !short_rows) {
-        const int njv = (int)envi_fir("TFX_FIR_NJ", 1);
+        const int njv = (int)env_i64("TFX_FIR_NJ", 1);
         const int nj = (njv == 2 || njv == 4) ? njv : 1;
         const int nout = 4 * nj * 1024;
         const int64_t tiles = ceil_div(T, nout);
@@ -347,7 +345,7 @@ void fir_direct_forward(const void *x, void *y, int dtype, int64_t C, int64_t T,
             if (best < 0 || cost < best) best = cost, kc = cand;
         }
         {
-            const int v = (int)envi_fir("TFX_FIR_KC", 0);
+            const int v = (int)env_i64("TFX_FIR_KC", 0);
             if (v == 128 || v == 512 || v == 1024) kc = v;
         }
         const int nchunks = (int)ceil_div(K, kc);

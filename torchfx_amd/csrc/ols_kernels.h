@@ -71,111 +71,63 @@ constexpr int OLS_CB = 32;      // columns per workgroup in the column passes
 __device__ __forceinline__ int pad16(int p) { return p + (p >> 4); }
 __device__ __forceinline__ int row_shift(const OlsGeom &g, int64_t c) { return g.sh_on ? (int)(((int64_t)g.sh_base + c * g.Tn) & 31) : 0; }
 
-template <bool INV>
-__device__ __forceinline__ void dft16(cpx (&v)[16])
-{
-    // t = t1 + 4 t2, k = 4 k1 + k2:  W16^(tk) = W4^(t1 k1) W16^(t1 k2) W4^(t2 k2)
-    constexpr float C1 = 0.92387953251128674f, S1 = 0.38268343236508977f, R2 = 0.70710678118654752f;
-#pragma unroll
-    for (int t1 = 0; t1 < 4; ++t1) dft4<INV>(v[t1], v[t1 + 4], v[t1 + 8], v[t1 + 12]);
-    // v[t1 + 4 k2] *= W16^(t1 k2)   (forward: exp(-i pi n/8); inverse: conjugate)
-    auto tw = [&](cpx &x, float c, float sn) {           // multiply by (c - i sn) forward, (c + i sn) inverse
-        const float s_ = INV ? -sn : sn;
-        x = make_float2(x.x * c + x.y * s_, x.y * c - x.x * s_);
-    };
-    tw(v[1 + 4], C1, S1);  tw(v[1 + 8], R2, R2);  tw(v[1 + 12], S1, C1);      // n = 1, 2, 3
-    tw(v[2 + 4], R2, R2);  tw(v[2 + 8], 0.f, 1.f); tw(v[2 + 12], -R2, R2);    // n = 2, 4, 6
-    tw(v[3 + 4], S1, C1);  tw(v[3 + 8], -R2, R2); tw(v[3 + 12], -C1, -S1);    // n = 3, 6, 9
-#pragma unroll
-    for (int k2 = 0; k2 < 4; ++k2) dft4<INV>(v[4 * k2], v[4 * k2 + 1], v[4 * k2 + 2], v[4 * k2 + 3]);
-    // X[k] now sits at v[4 (k % 4) + k / 4]
-}
-#define DFT16_AT(k) (4 * ((k) & 3) + ((k) >> 2))
-
 
 // ---------------------------------------------------------------------------------------------
-// Column pass (A: forward from the signal, C: inverse to the output), radix (16, 16).  256 threads:
-// thread (col = tid & 31, q = tid >> 5) owns butterflies j = q + 8 i (i < 2) of its column, 16 rows
-// each (rows j + 16 t).  LDS: one [256][32] complex buffer (64 KB), one exchange per direction.
+// Column pass (A: forward from the signal, C: inverse to the output), radix (16, 16).  512 / NBF threads:
+// thread (col = tid & 31, q = tid >> 5) owns butterflies j = q + (16 / NBF) i (i < NBF) of its column, 16 rows
+// each (rows j + 16 t).  LDS: one [256][32] complex buffer (64 KB), one exchange per direction.  The butterflies are
+// packed arithmetic (fftpk.h: a 16-point DFT in 80 vector instructions instead of ~160, a twiddle product in 2 instead of 4).
+// NBF = butterflies per thread.  Only NBF = 1 (512 threads, 16 waves per CU) is instantiated; the parameter and its
+// one-trip loops stay because flattening them changes the compiler's address arithmetic in these kernels.
 // ---------------------------------------------------------------------------------------------
-// PK: the butterflies in packed arithmetic (fftpk.h: a 16-point DFT in 80 vector instructions instead of ~160, a twiddle
-// product in 2 instead of 4); the exchange and its addresses are the same.  TFX_OLS_PK=0 selects the compiler-scheduled form.
-template <bool INV, int NBF, bool PK, bool LEAN = false>
+template <bool INV, int NBF, bool LEAN = false>
 __device__ __forceinline__ void col_stages16(cpx (&v)[NBF][16], cpx *lds, const cpx *tw256, int col, int q)
 {
     constexpr int QS = 16 / NBF;               // butterfly j = q + QS * i
-    if (PK) {
-        using pk::v2f;
-        const v2f Wc = {0.92387953251128675613f, 0.38268343236508977173f}, Wr = {0.70710678118654752440f, 0.70710678118654752440f};
-        v2f *L = (v2f *)lds;
-        const v2f *TW = (const v2f *)tw256;
-#pragma unroll
-        for (int i = 0; i < NBF; ++i) {
-            v2f u[16];
-#pragma unroll
-            for (int t = 0; t < 16; ++t) u[t] = __builtin_bit_cast(v2f, v[i][t]);
-            pk::pk_dft16<INV>(u, Wc, Wr);
-            const int j = q + QS * i;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) L[(16 * j + k) * OLS_CB + col] = u[PK_DFT16_AT(k)];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < NBF; ++i) {
-            const int j = q + QS * i;
-            v2f d[16], w[16];
-#pragma unroll
-            for (int t = 0; t < 16; ++t) d[t] = L[(j + 16 * t) * OLS_CB + col];
-            if (LEAN) {                                  // twiddles in four batches: 24 registers less at the peak
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) if (4 * b + t > 0) w[t] = TW[((4 * b + t) * j) & 255];
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) if (4 * b + t > 0) d[4 * b + t] = pk::pk_cmul<INV>(d[4 * b + t], w[t]);
-                }
-            } else {
-#pragma unroll
-            for (int t = 1; t < 16; ++t) w[t] = TW[(t * j) & 255];
-            __builtin_amdgcn_sched_barrier(0);       // all reads are issued before the first product (asm consumers: the scheduler would sink them)
-#pragma unroll
-            for (int t = 1; t < 16; ++t) d[t] = pk::pk_cmul<INV>(d[t], w[t]);
-            }
-            pk::pk_dft16<INV>(d, Wc, Wr);          // natural-order output row j + 16 k sits at d[PK_DFT16_AT(k)]
-#pragma unroll
-            for (int t = 0; t < 16; ++t) v[i][t] = __builtin_bit_cast(cpx, d[t]);
-        }
-        return;
-    }
+    using pk::v2f;
+    const v2f Wc = {0.92387953251128675613f, 0.38268343236508977173f}, Wr = {0.70710678118654752440f, 0.70710678118654752440f};
+    v2f *L = (v2f *)lds;
+    const v2f *TW = (const v2f *)tw256;
 #pragma unroll
     for (int i = 0; i < NBF; ++i) {
-        dft16<INV>(v[i]);
+        v2f u[16];
+#pragma unroll
+        for (int t = 0; t < 16; ++t) u[t] = __builtin_bit_cast(v2f, v[i][t]);
+        pk::pk_dft16<INV>(u, Wc, Wr);
         const int j = q + QS * i;
 #pragma unroll
-        for (int k = 0; k < 16; ++k) lds[(16 * j + k) * OLS_CB + col] = v[i][DFT16_AT(k)];
+        for (int k = 0; k < 16; ++k) L[(16 * j + k) * OLS_CB + col] = u[PK_DFT16_AT(k)];
     }
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < NBF; ++i) {
         const int j = q + QS * i;
+        v2f d[16], w[16];
 #pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            cpx x = lds[(j + 16 * t) * OLS_CB + col];
-            if (t > 0) {
-                const cpx w = tw256[(t * j) & 255];
-                x = INV ? cmulc(x, w) : cmul(x, w);
+        for (int t = 0; t < 16; ++t) d[t] = L[(j + 16 * t) * OLS_CB + col];
+        if (LEAN) {                                  // twiddles in four batches: 24 registers less at the peak
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) if (4 * b + t > 0) w[t] = TW[((4 * b + t) * j) & 255];
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) if (4 * b + t > 0) d[4 * b + t] = pk::pk_cmul<INV>(d[4 * b + t], w[t]);
             }
-            v[i][t] = x;
+        } else {
+#pragma unroll
+            for (int t = 1; t < 16; ++t) w[t] = TW[(t * j) & 255];
+            __builtin_amdgcn_sched_barrier(0);   // all reads are issued before the first product (asm consumers: the scheduler would sink them)
+#pragma unroll
+            for (int t = 1; t < 16; ++t) d[t] = pk::pk_cmul<INV>(d[t], w[t]);
         }
-        dft16<INV>(v[i]);          // natural-order output row j + 16 k sits at v[i][DFT16_AT(k)]
+        pk::pk_dft16<INV>(d, Wc, Wr);          // natural-order output row j + 16 k sits at d[PK_DFT16_AT(k)]
+#pragma unroll
+        for (int t = 0; t < 16; ++t) v[i][t] = __builtin_bit_cast(cpx, d[t]);
     }
 }
 
-// NBF = butterflies per thread: 2 -> 256 threads (8 waves per CU at 2 workgroups), 1 -> 512 threads
-// (16 waves per CU, half the registers per thread).  PROBE (development, tools/archive/ols_knobs.py):
-// 1 = no FFT (load -> store), 2 = loads only, 3 = stores only.
-template <int NBF, int PROBE>
+template <int NBF>
 __global__ void __launch_bounds__(512 / NBF, 2)
 ols_col_fwd16_kernel(const float *__restrict__ x, cpx *__restrict__ T, const cpx *__restrict__ tw256g,
                      OlsGeom g, int64_t frame0)
@@ -199,12 +151,7 @@ ols_col_fwd16_kernel(const float *__restrict__ x, cpx *__restrict__ T, const cpx
     // interior frames (the common case) need no bounds checks
     const int64_t span = (int64_t)OLS_N1 * g.N2;
     const bool inner = ia0 >= 0 && ia0 + span <= g.Tn && has_b && ib0 >= 0 && ib0 + span <= g.Tn;
-    if (PROBE == 3) {
-#pragma unroll
-        for (int i = 0; i < NBF; ++i)
-#pragma unroll
-            for (int t = 0; t < 16; ++t) v[i][t] = make_float2((float)t, (float)col);
-    } else if (inner && (g.nt & 1)) {          // the signal is read once: streaming loads
+    if (inner && (g.nt & 1)) {          // the signal is read once: streaming loads
 #pragma unroll
         for (int i = 0; i < NBF; ++i)
 #pragma unroll
@@ -250,25 +197,16 @@ ols_col_fwd16_kernel(const float *__restrict__ x, cpx *__restrict__ T, const cpx
         if (bad) g.nf_pair[cb_] = 1;
     }
     __syncthreads();
-    if (PROBE == 0 || PROBE == 4) col_stages16<false, NBF, PROBE == 0>(v, lds, tw256, col, q);
+    col_stages16<false, NBF>(v, lds, tw256, col, q);
     cpx *Tp = T + pair * ((int64_t)OLS_N1 * g.P2);
-    if (PROBE == 2) {
-        float acc = 0.f;
-#pragma unroll
-        for (int i = 0; i < NBF; ++i)
-#pragma unroll
-            for (int k = 0; k < 16; ++k) acc += v[i][k].x + v[i][k].y;
-        if (acc == 1.2345e30f) Tp[n2] = make_float2(acc, acc);
-        return;
-    }
 #pragma unroll
     for (int i = 0; i < NBF; ++i)
 #pragma unroll
         for (int k = 0; k < 16; ++k)
-            Tp[(int64_t)(q + QS * i + 16 * k) * g.P2 + n2] = v[i][DFT16_AT(k)];
+            Tp[(int64_t)(q + QS * i + 16 * k) * g.P2 + n2] = v[i][PK_DFT16_AT(k)];
 }
 
-template <int NBF, int PROBE>
+template <int NBF>
 __global__ void __launch_bounds__(512 / NBF, 2)
 ols_col_inv16_kernel(const cpx *__restrict__ T, float *__restrict__ y, const cpx *__restrict__ tw256g,
                      OlsGeom g, int64_t frame0)
@@ -285,34 +223,18 @@ ols_col_inv16_kernel(const cpx *__restrict__ T, float *__restrict__ y, const cpx
     const int n2 = cb * OLS_CB + col;
     const cpx *Tp = T + pair * ((int64_t)OLS_N1 * g.P2);
     cpx v[NBF][16];
-    if (PROBE == 3) {
 #pragma unroll
-        for (int i = 0; i < NBF; ++i)
+    for (int i = 0; i < NBF; ++i)
 #pragma unroll
-            for (int t = 0; t < 16; ++t) v[i][t] = make_float2((float)t, (float)col);
-    } else {
-#pragma unroll
-        for (int i = 0; i < NBF; ++i)
-#pragma unroll
-            for (int t = 0; t < 16; ++t) v[i][t] = Tp[(int64_t)(q + QS * i + 16 * t) * g.P2 + n2];
-    }
+        for (int t = 0; t < 16; ++t) v[i][t] = Tp[(int64_t)(q + QS * i + 16 * t) * g.P2 + n2];
     __syncthreads();
-    if (PROBE == 0 || PROBE == 4) col_stages16<true, NBF, PROBE == 0>(v, lds, tw256, col, q);
+    col_stages16<true, NBF>(v, lds, tw256, col, q);
 
     const int64_t fa = frame0 + 2 * pair, fb = fa + 1;
     const int64_t ca = fa / g.F, oa0 = (fa % g.F) * g.S;
     const bool has_b = fb < g.nframes;
     const int64_t cb_ = has_b ? fb / g.F : 0, ob0 = has_b ? (fb % g.F) * g.S : 0;
     float *ya = y + ca * g.Tout, *yb = y + cb_ * g.Tout;
-    if (PROBE == 2) {
-        float acc = 0.f;
-#pragma unroll
-        for (int i = 0; i < NBF; ++i)
-#pragma unroll
-            for (int k = 0; k < 16; ++k) acc += v[i][k].x + v[i][k].y;
-        if (acc == 1.2345e30f) ya[oa0] = acc;
-        return;
-    }
     const int64_t sha = g.out_shift + row_shift(g, ca), shb = g.out_shift + row_shift(g, cb_);
     const bool epi = g.ep_scale | g.ep_clamp | (g.ep_stat >= 0);
     double acc_a = 0.0, acc_b = 0.0;
@@ -322,7 +244,7 @@ ols_col_inv16_kernel(const cpx *__restrict__ T, float *__restrict__ y, const cpx
         for (int k = 0; k < 16; ++k) {
             const int64_t n = (int64_t)(q + QS * i + 16 * k) * g.N2 + n2;
             if (n < g.S) {                                   // valid part of the block
-                cpx o = v[i][DFT16_AT(k)];
+                cpx o = v[i][PK_DFT16_AT(k)];
                 const int64_t oa = oa0 + n - sha, ob = ob0 + n - shb;
                 const bool wa = oa >= 0 && oa < g.Tout, wb = has_b && ob >= 0 && ob < g.Tout;
                 if (epi) {                                   // Gain / clamp / statistic on the stored values
@@ -403,7 +325,7 @@ struct SosFuse {                                 // by value in the kernel argum
     double co[SOSF_MAXK][5];                     // b0, b1, b2, -a1, -a2 of each section; unit-b0 form: b0_0 ... b0_s, b1 / b0, b2 / b0, -a1, -a2
     double *sections;                            // optional [K, C, T] float64: every section's output (parity tests), or null
     int warm_blocks;                             // warm-up of a row in 32-sample blocks
-    int prio;                                    // the transform / memory phases issue ahead of the recursion (TFX_OLS_SOS_PRIO)
+    int prio;                                    // the transform / memory phases issue ahead of the recursion (olsnative_forward: always 1)
 };
 
 template <int KS, bool TAPS, bool UNIT>
@@ -551,13 +473,13 @@ ols_col_fwd16_sos_kernel(const float *__restrict__ x, cpx *__restrict__ T, const
 #pragma unroll
         for (int t = 0; t < 16; ++t) v[0][t] = make_float2(S[(q + 16 * t) * SOSF_LS + col], S[(256 + q + 16 * t) * SOSF_LS + col]);
         __syncthreads();                                      // the exchange overwrites the stage
-        col_stages16<false, 1, true, true>(v, lds, tw256, col, q);
+        col_stages16<false, 1, true>(v, lds, tw256, col, q);
         char *Tb = (char *)(Tp + blk * OLS_CB);               // wave-uniform base, 32-bit lane offsets (a pair's workspace is 8 MB)
         unsigned off = (unsigned)(q * g.P2 + col) * (unsigned)sizeof(cpx);
         asm volatile("" : "+v"(off));
         const unsigned ostep = 16u * (unsigned)g.P2 * (unsigned)sizeof(cpx);
 #pragma unroll
-        for (int k = 0; k < 16; ++k) { *(cpx *)(Tb + off) = v[0][DFT16_AT(k)]; off += ostep; }
+        for (int k = 0; k < 16; ++k) { *(cpx *)(Tb + off) = v[0][PK_DFT16_AT(k)]; off += ostep; }
         __syncthreads();                                      // exchange read: the stage may be refilled
     }
     // Non-finite values never leave a recursion (iir_cpu.cpp:132-147: once in the state, every later output of the row carries
@@ -799,53 +721,7 @@ ols_row256pk_kernel(cpx *__restrict__ T, const cpx *__restrict__ Hp, const cpx *
 // direction needs only two LDS exchanges (the radix-4 version above needs four).  LDS positions
 // are padded by one element per 16 so the stride-16 writes of the first stage are conflict-free.
 // ---------------------------------------------------------------------------------------------
-// in: v[t] = element at position lane + 64 t (natural order).  out: same arrangement, transformed.
-template <bool INV>
-__device__ __forceinline__ void row_fft1024(cpx (&v)[16], cpx *lds, const cpx *twr, int lane)
-{
-    // stage A: radix 16, Ns = 1
-    dft16<INV>(v);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) lds[pad16(16 * lane + k)] = v[DFT16_AT(k)];
-    wave_sync2();
-    // stage B: radix 16, Ns = 16: inputs lane + 64 t, twiddle W256^(t k), k = lane % 16
-    const int kb = lane & 15;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-        cpx x = lds[pad16(lane + 64 * t)];
-        if (t > 0) {
-            const cpx w = twr[(4 * t * kb) & 1023];
-            x = INV ? cmulc(x, w) : cmul(x, w);
-        }
-        v[t] = x;
-        if ((t & 3) == 3) __builtin_amdgcn_sched_barrier(0);    // bound the number of loads in flight
-    }
-    wave_sync2();
-    dft16<INV>(v);
-    const int j0 = (lane >> 4) * 256 + kb;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) lds[pad16(j0 + 16 * k)] = v[DFT16_AT(k)];
-    wave_sync2();
-    // stage C: radix 4, Ns = 256: butterflies j = lane + 64 i, inputs j + 256 r, twiddle W1024^(r j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int j = lane + 64 * i;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            cpx x = lds[pad16(j + 256 * r)];
-            if (r > 0) {
-                const cpx w = twr[(r * j) & 1023];
-                x = INV ? cmulc(x, w) : cmul(x, w);
-            }
-            v[i + 4 * r] = x;
-        }
-        dft4<INV>(v[i], v[i + 4], v[i + 8], v[i + 12]);     // outputs j + 256 r  ->  t = i + 4 r
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    wave_sync2();
-}
-
-// the same wavefront transform in packed arithmetic (fftpk.h): in: v[t] = element lane + 64 t, out: the same arrangement
+// in packed arithmetic (fftpk.h).  in: v[t] = element at position lane + 64 t (natural order).  out: same arrangement, transformed.
 template <bool INV>
 __device__ __forceinline__ void row_fft1024_pk(pk::v2f (&v)[16], pk::v2f *lds, const pk::v2f *twr, int lane, pk::v2f Wc, pk::v2f Wr)
 {
@@ -894,7 +770,6 @@ __device__ __forceinline__ void row_fft1024_pk(pk::v2f (&v)[16], pk::v2f *lds, c
     wave_sync2();
 }
 
-template <bool PK>
 __global__ void __launch_bounds__(256, 3)
 ols_row1024_kernel(cpx *__restrict__ T, const cpx *__restrict__ Hp, const cpx *__restrict__ twrg,
                    const cpx *__restrict__ tlo, const cpx *__restrict__ thi, const cpx *__restrict__ tu,
@@ -919,170 +794,46 @@ ols_row1024_kernel(cpx *__restrict__ T, const cpx *__restrict__ Hp, const cpx *_
     // W_N^(k1 n2), n2 = lane + 64 t  =  W_N^(k1 lane) * W_N^(64 k1 t)
     const unsigned ml = (unsigned)(k1 * lane);
     const cpx wl = cmul(tlo[ml & 511], thi[ml >> 9]);
-    if (PK) {
-        using pk::v2f;
-        const v2f Wc = {0.92387953251128675613f, 0.38268343236508977173f}, Wr = {0.70710678118654752440f, 0.70710678118654752440f};
-        v2f u[16], h[16];
+    using pk::v2f;
+    const v2f Wc = {0.92387953251128675613f, 0.38268343236508977173f}, Wr = {0.70710678118654752440f, 0.70710678118654752440f};
+    v2f u[16], h[16];
 #pragma unroll
-        for (int t = 0; t < 16; ++t) h[t] = ((const v2f *)base)[lane + 64 * t];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const unsigned iu = 2u * ((unsigned)(k1 * t) & (unsigned)(Nmask >> 6));
-            const cpx w = cmul(wl, make_float2(tuc[iu], tuc[iu + 1]));
-            u[t] = pk::pk_cmul<false>(h[t], __builtin_bit_cast(v2f, w));
-        }
-        row_fft1024_pk<false>(u, (v2f *)lds, (const v2f *)twr, lane, Wc, Wr);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int t = 0; t < 16; ++t) h[t] = ((const v2f *)hrow)[lane + 64 * t];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int t = 0; t < 16; ++t) u[t] = pk::pk_cmul<false>(u[t], h[t]);
-        __builtin_amdgcn_sched_barrier(0);
-        row_fft1024_pk<true>(u, (v2f *)lds, (const v2f *)twr, lane, Wc, Wr);
-        float wlx = wl.x, wly = wl.y;
-        asm volatile("" : "+v"(wlx), "+v"(wly));
-        const cpx wl2 = make_float2(wlx, wly);
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const unsigned iu = 2u * ((unsigned)(k1 * t) & (unsigned)(Nmask >> 6));
-            const cpx w = cmul(wl2, make_float2(tuc[iu], tuc[iu + 1]));
-            ((v2f *)base)[lane + 64 * t] = pk::pk_cmul<true>(u[t], __builtin_bit_cast(v2f, w));
-        }
-        return;
-    }
-    cpx v[16];
+    for (int t = 0; t < 16; ++t) h[t] = ((const v2f *)base)[lane + 64 * t];
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < 16; ++t) {
         const unsigned iu = 2u * ((unsigned)(k1 * t) & (unsigned)(Nmask >> 6));
-        const cpx ut = make_float2(tuc[iu], tuc[iu + 1]);
-        v[t] = cmul(base[lane + 64 * t], cmul(wl, ut));
+        const cpx w = cmul(wl, make_float2(tuc[iu], tuc[iu + 1]));
+        u[t] = pk::pk_cmul<false>(h[t], __builtin_bit_cast(v2f, w));
     }
+    row_fft1024_pk<false>(u, (v2f *)lds, (const v2f *)twr, lane, Wc, Wr);
     __builtin_amdgcn_sched_barrier(0);
-    row_fft1024<false>(v, lds, twr, lane);
-    __builtin_amdgcn_sched_barrier(0);      // keep the spectrum loads from being hoisted over the FFT
 #pragma unroll
-    for (int t = 0; t < 16; ++t) v[t] = cmul(v[t], hrow[lane + 64 * t]);
+    for (int t = 0; t < 16; ++t) h[t] = ((const v2f *)hrow)[lane + 64 * t];
     __builtin_amdgcn_sched_barrier(0);
-    row_fft1024<true>(v, lds, twr, lane);
+#pragma unroll
+    for (int t = 0; t < 16; ++t) u[t] = pk::pk_cmul<false>(u[t], h[t]);
     __builtin_amdgcn_sched_barrier(0);
-    // recompute the row twiddles instead of keeping 16 of them live across both FFTs: the empty
-    // asm hides wl from common-subexpression elimination
+    row_fft1024_pk<true>(u, (v2f *)lds, (const v2f *)twr, lane, Wc, Wr);
     float wlx = wl.x, wly = wl.y;
-    asm volatile("" : "+v"(wlx), "+v"(wly));
+    asm volatile("" : "+v"(wlx), "+v"(wly));     // recompute the row twiddles, do not keep 16 of them live across both FFTs
     const cpx wl2 = make_float2(wlx, wly);
 #pragma unroll
     for (int t = 0; t < 16; ++t) {
         const unsigned iu = 2u * ((unsigned)(k1 * t) & (unsigned)(Nmask >> 6));
-        const cpx ut = make_float2(tuc[iu], tuc[iu + 1]);
-        base[lane + 64 * t] = cmulc(v[t], cmul(wl2, ut));
+        const cpx w = cmul(wl2, make_float2(tuc[iu], tuc[iu + 1]));
+        ((v2f *)base)[lane + 64 * t] = pk::pk_cmul<true>(u[t], __builtin_bit_cast(v2f, w));
     }
 }
 
 // ---------------------------------------------------------------------------------------------
 // Row pass B, N2 = 4096 (N = 2^20: 93.6 % of every block is valid output at K = 65536 instead of
 // 74.6 % at N = 2^18).  One workgroup per row, thread j owns elements n2 = j + 256 t: radix
-// (16, 16, 16) Stockham, three register stages and two LDS exchanges per direction.
+// (16, 16, 16) Stockham, three register stages and two LDS exchanges per direction (pk::fft4096_pk).  The exchanges
+// write contiguous and read strided: stage-1 output k of thread j goes to j + j/16 + 272 k, stage 2 reads two runs of
+// 16 slots 272 apart, stage 3 reads 17 j + t -- conflict-free on both sides.  Butterflies and products are packed
+// arithmetic (fftpk.h): ~900 instead of 1420 vector instructions per wave and row.
 // ---------------------------------------------------------------------------------------------
-// Exchange layout XCH (physical LDS position of logical p is p + p/16 in both):
-//   0  "write strided, read contiguous" (textbook Stockham): stage-1 butterfly j scatters output k to 16 j + k,
-//      stage 2 gathers j + 256 t.  The ds_write_b64 groups (16 contiguous lanes, banks mod 32 dwords) are
-//      conflict-free, but a ds_read_b64 group is 32 lanes and the 32 positions j + j/16 straddle one pad slot:
-//      lanes 0 and 31 of every group meet on one bank -> every read of stages 2 and 3 takes two LDS cycles per
-//      group instead of one (PMC round 2: SQ_LDS_BANK_CONFLICT = 54 % of the LDS-active cycles).
-//   1  "write contiguous, read strided": with digits n = n0 + 16 n1 + 256 n2, k = k0 + 16 k1 + 256 k2
-//        stage 1  thread j = n0 + 16 n1 : DFT over n2 -> A[k0] stored at  j + 256 k0
-//        stage 2  thread j = n0 + 16 k0 : reads (n0 + 256 k0) + 16 n1, * W256^(n1 k0), DFT over n1 -> B[k1] at j + 256 k1
-//        stage 3  thread j = k0 + 16 k1 : reads 16 j + n0 (its own 16 consecutive slots), * W4096^(n0 j), DFT over n0
-//      -> X[j + 256 k2], the same ownership as the input.  Physical addresses stay base + immediate:
-//      j + j/16 + 272 k (stores: 16 contiguous lanes -> 16 contiguous slots), (j & 15) + 272 (j >> 4) + 17 t
-//      (stage-2 loads: two runs of 16 slots 272 = 16 (mod 32) apart) and 17 j + t (stage-3 loads: 17 is odd, so 32
-//      consecutive j hit 32 different slots mod 32) -- no conflicts on either side.
-//   2  layout 1 with the sixteen loads of a stage issued as single ds_read_b64 from one asm statement (default): the
-//      compiler pairs them into ds_read2_b64, which the LDS serves at half the bytes per clock.
-// Measured on cfg 4 (one stream, same box, profiles/r03_experiments.txt): 4.01 / 3.73 / 3.69 ms for XCH 0 / 1 / 2.
-// Sixteen ds_read_b64 at base + t * STRIDE_B that the load/store optimiser cannot pair into ds_read2_b64 (two
-// 16-lane-group accesses with 32-dword banking at half the bytes per clock, MI355X_MICROARCH.md LDS table): the
-// reads are issued from one asm statement, which also waits for them (the compiler does not track asm loads).
-template <int STRIDE_B>
-__device__ __forceinline__ void lds_read16_b64(cpx (&v)[16], const cpx *p)
-{
-    typedef const char __attribute__((address_space(3))) *lds_ptr;
-    const unsigned a = (unsigned)(uintptr_t)(lds_ptr)(const char *)p;
-    double d[16];
-    asm volatile(
-        "ds_read_b64 %0, %16 offset:%17\n\tds_read_b64 %1, %16 offset:%18\n\tds_read_b64 %2, %16 offset:%19\n\t"
-        "ds_read_b64 %3, %16 offset:%20\n\tds_read_b64 %4, %16 offset:%21\n\tds_read_b64 %5, %16 offset:%22\n\t"
-        "ds_read_b64 %6, %16 offset:%23\n\tds_read_b64 %7, %16 offset:%24\n\tds_read_b64 %8, %16 offset:%25\n\t"
-        "ds_read_b64 %9, %16 offset:%26\n\tds_read_b64 %10, %16 offset:%27\n\tds_read_b64 %11, %16 offset:%28\n\t"
-        "ds_read_b64 %12, %16 offset:%29\n\tds_read_b64 %13, %16 offset:%30\n\tds_read_b64 %14, %16 offset:%31\n\t"
-        "ds_read_b64 %15, %16 offset:%32\n\ts_waitcnt lgkmcnt(0)"
-        : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]), "=&v"(d[4]), "=&v"(d[5]), "=&v"(d[6]), "=&v"(d[7]),
-          "=&v"(d[8]), "=&v"(d[9]), "=&v"(d[10]), "=&v"(d[11]), "=&v"(d[12]), "=&v"(d[13]), "=&v"(d[14]), "=&v"(d[15])
-        : "v"(a), "n"(0 * STRIDE_B), "n"(1 * STRIDE_B), "n"(2 * STRIDE_B), "n"(3 * STRIDE_B), "n"(4 * STRIDE_B),
-          "n"(5 * STRIDE_B), "n"(6 * STRIDE_B), "n"(7 * STRIDE_B), "n"(8 * STRIDE_B), "n"(9 * STRIDE_B), "n"(10 * STRIDE_B),
-          "n"(11 * STRIDE_B), "n"(12 * STRIDE_B), "n"(13 * STRIDE_B), "n"(14 * STRIDE_B), "n"(15 * STRIDE_B)
-        : "memory");
-#pragma unroll
-    for (int t = 0; t < 16; ++t) v[t] = __builtin_bit_cast(cpx, d[t]);
-}
-
-template <bool INV, int XCH>
-__device__ __forceinline__ void row_fft4096(cpx (&v)[16], cpx *lds, const cpx *twB, const cpx *twA, int j)
-{
-    dft16<INV>(v);                                             // stage 1
-    const int kb = j & 15, jh = j >> 4;
-    if (XCH == 0) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) lds[pad16(16 * j + k)] = v[DFT16_AT(k)];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) lds[j + jh + 272 * k] = v[DFT16_AT(k)];
-    }
-    __syncthreads();
-    if (XCH == 2) lds_read16_b64<17 * 8>(v, lds + kb + 272 * jh);
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {                             // stage 2: twiddle W256^(t k0)
-        cpx x = XCH == 0 ? lds[pad16(j + 256 * t)] : (XCH == 2 ? v[t] : lds[kb + 272 * jh + 17 * t]);
-        if (t > 0) {
-            const cpx w = twB[16 * t + (XCH == 0 ? kb : jh)];    // [t][k0]: broadcast within a group
-            x = INV ? cmulc(x, w) : cmul(x, w);
-        }
-        v[t] = x;
-    }
-    __syncthreads();
-    dft16<INV>(v);
-    if (XCH == 0) {
-        const int j0 = jh * 256 + kb;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) lds[pad16(j0 + 16 * k)] = v[DFT16_AT(k)];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) lds[j + jh + 272 * k] = v[DFT16_AT(k)];
-    }
-    __syncthreads();
-    if (XCH == 2) lds_read16_b64<8>(v, lds + 17 * j);
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {                             // stage 3: twiddle W4096^(t j)
-        cpx x = XCH == 0 ? lds[pad16(j + 256 * t)] : (XCH == 2 ? v[t] : lds[17 * j + t]);
-        if (t > 0) {
-            // W4096^(t j) = W4096^(t (j & 15)) * W256^(t (j >> 4)): two [t][.] tables, conflict-free
-            const cpx w = cmul(twA[16 * t + kb], twB[16 * t + jh]);
-            x = INV ? cmulc(x, w) : cmul(x, w);
-        }
-        v[t] = x;
-    }
-    __syncthreads();
-    dft16<INV>(v);
-    // natural order: X[j + 256 k] = v[DFT16_AT(k)]
-    cpx o[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) o[k] = v[DFT16_AT(k)];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) v[k] = o[k];
-}
-
 // Row -> workgroup mapping (MAP):
 //   0  row = blockIdx (pair-major, as stored)
 //   1  XCD-aware: workgroup b runs on XCD b % 8 (observed dispatch order, MI355X_MICROARCH.md; only speed
@@ -1092,7 +843,7 @@ __device__ __forceinline__ void row_fft4096(cpx (&v)[16], cpx *lds, const cpx *t
 //      hit in that XCD's L2 by the other np - 1 rows (was: re-fetched for about every second pair,
 //      +25 % read traffic of this pass).
 // (Keeping Hp[k1] in registers and looping a workgroup over the pairs needs 168 VGPRs -> spills at 3 waves/SIMD.)
-template <int MAP, int XCH>
+template <int MAP>
 __global__ void __launch_bounds__(256, 4)
 ols_row4096_kernel(cpx *__restrict__ T, const cpx *__restrict__ Hp, const cpx *__restrict__ tw256g,
                    const cpx *__restrict__ t4log, const cpx *__restrict__ t4hig,
@@ -1124,65 +875,36 @@ ols_row4096_kernel(cpx *__restrict__ T, const cpx *__restrict__ Hp, const cpx *_
     const cpx *hrow = Hp + (int64_t)k1 * N2;
     const unsigned ml = (unsigned)(k1 * j);
     const cpx wl = cmul(tlo[ml & 511], thi[ml >> 9]);
-    {
-        cpx *base = T + (p * OLS_N1 + k1) * P2;
-        if (XCH == 3) {
-            // packed arithmetic (fftpk.h): same exchange layout as XCH 1 / 2, the butterflies and products as v_pk_* with operand
-            // selectors: ~900 instead of 1420 vector instructions per wave and row
-            using pk::v2f;
-            const v2f Wc = {0.92387953251128675613f, 0.38268343236508977173f}, Wr = {0.70710678118654752440f, 0.70710678118654752440f};
-            v2f u[16], h[16];
+    cpx *base = T + (p * OLS_N1 + k1) * P2;
+    using pk::v2f;
+    const v2f Wc = {0.92387953251128675613f, 0.38268343236508977173f}, Wr = {0.70710678118654752440f, 0.70710678118654752440f};
+    v2f u[16], h[16];
 #pragma unroll
-            for (int t = 0; t < 16; ++t) h[t] = ((const v2f *)base)[j + 256 * t];
-            __builtin_amdgcn_sched_barrier(0);
+    for (int t = 0; t < 16; ++t) h[t] = ((const v2f *)base)[j + 256 * t];
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                const unsigned iu = 2u * ((unsigned)(k1 * t) & umask);
-                const cpx w = cmul(wl, make_float2(tuc[iu], tuc[iu + 1]));          // W_N^(k1 (j + 256 t))
-                u[t] = pk::pk_cmul<false>(h[t], __builtin_bit_cast(v2f, w));
-            }
-            pk::fft4096_pk<false>(u, (v2f *)lds, (const v2f *)twB, (const v2f *)twA, j, Wc, Wr);
-            __builtin_amdgcn_sched_barrier(0);
+    for (int t = 0; t < 16; ++t) {
+        const unsigned iu = 2u * ((unsigned)(k1 * t) & umask);
+        const cpx w = cmul(wl, make_float2(tuc[iu], tuc[iu + 1]));          // W_N^(k1 (j + 256 t))
+        u[t] = pk::pk_cmul<false>(h[t], __builtin_bit_cast(v2f, w));
+    }
+    pk::fft4096_pk<false>(u, (v2f *)lds, (const v2f *)twB, (const v2f *)twA, j, Wc, Wr);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int t = 0; t < 16; ++t) h[t] = ((const v2f *)hrow)[j + 256 * t];
-            __builtin_amdgcn_sched_barrier(0);
+    for (int t = 0; t < 16; ++t) h[t] = ((const v2f *)hrow)[j + 256 * t];
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int t = 0; t < 16; ++t) u[t] = pk::pk_cmul<false>(u[t], h[t]);
-            __builtin_amdgcn_sched_barrier(0);
-            pk::fft4096_pk<true>(u, (v2f *)lds, (const v2f *)twB, (const v2f *)twA, j, Wc, Wr);
-            float wlx = wl.x, wly = wl.y;
-            asm volatile("" : "+v"(wlx), "+v"(wly));
-            const cpx wl2 = make_float2(wlx, wly);
+    for (int t = 0; t < 16; ++t) u[t] = pk::pk_cmul<false>(u[t], h[t]);
+    __builtin_amdgcn_sched_barrier(0);
+    pk::fft4096_pk<true>(u, (v2f *)lds, (const v2f *)twB, (const v2f *)twA, j, Wc, Wr);
+    float wlx = wl.x, wly = wl.y;
+    asm volatile("" : "+v"(wlx), "+v"(wly));     // recompute, do not keep 16 twiddles live (see row1024)
+    const cpx wl2 = make_float2(wlx, wly);
 #pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                const unsigned iu = 2u * ((unsigned)(k1 * t) & umask);
-                const cpx w = cmul(wl2, make_float2(tuc[iu], tuc[iu + 1]));
-                ((v2f *)base)[j + 256 * t] = pk::pk_cmul<true>(u[t], __builtin_bit_cast(v2f, w));
-            }
-            return;
-        }
-        cpx v[16];
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const unsigned iu = 2u * ((unsigned)(k1 * t) & umask);
-            const cpx ut = make_float2(tuc[iu], tuc[iu + 1]);
-            v[t] = cmul(base[j + 256 * t], cmul(wl, ut));
-        }
-        row_fft4096<false, XCH == 3 ? 2 : XCH>(v, lds, twB, twA, j);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int t = 0; t < 16; ++t) v[t] = cmul(v[t], hrow[j + 256 * t]);
-        __builtin_amdgcn_sched_barrier(0);
-        row_fft4096<true, XCH == 3 ? 2 : XCH>(v, lds, twB, twA, j);
-        float wlx = wl.x, wly = wl.y;
-        asm volatile("" : "+v"(wlx), "+v"(wly));     // recompute, do not keep 16 twiddles live (see row1024)
-        const cpx wl2 = make_float2(wlx, wly);
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const unsigned iu = 2u * ((unsigned)(k1 * t) & umask);
-            const cpx ut = make_float2(tuc[iu], tuc[iu + 1]);
-            base[j + 256 * t] = cmulc(v[t], cmul(wl2, ut));
-        }
+    for (int t = 0; t < 16; ++t) {
+        const unsigned iu = 2u * ((unsigned)(k1 * t) & umask);
+        const cpx w = cmul(wl2, make_float2(tuc[iu], tuc[iu + 1]));
+        ((v2f *)base)[j + 256 * t] = pk::pk_cmul<true>(u[t], __builtin_bit_cast(v2f, w));
     }
 }
 

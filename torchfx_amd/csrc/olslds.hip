@@ -210,7 +210,6 @@ __device__ __forceinline__ void transform_pair(cx<R> (&v)[16], cx<R> *lds, const
     __builtin_amdgcn_sched_barrier(0);
     fft4096<R, true>(v, lds, twB, twA, j);
 }
-#ifndef TFX_LDS_NO_PK
 template <>
 __device__ __forceinline__ void transform_pair<float>(cx<float> (&v)[16], cx<float> *lds, const cx<float> *twB, const cx<float> *twA,
                                                       const cx<float> *__restrict__ Hs, int j)
@@ -235,7 +234,6 @@ __device__ __forceinline__ void transform_pair<float>(cx<float> (&v)[16], cx<flo
 #pragma unroll
     for (int t = 0; t < 16; ++t) v[t] = __builtin_bit_cast(cx<float>, u[t]);
 }
-#endif
 
 // Pair -> workgroup: workgroups are dealt to the eight XCDs round robin (observed, MI355X_MICROARCH.md; only speed depends on
 // it).  XCD b % 8 owns the pairs [xcd * per_xcd, (xcd + 1) * per_xcd) and its workgroups (local index m = b / 8) take them in
@@ -383,94 +381,17 @@ ols_lds8192_kernel(const R *__restrict__ x, R *__restrict__ y, const cx<R> *__re
     store_pair<R, LDS8K, 32>(v, y, g, p, j, smem);
 }
 
-// ---- 16 384 points in the same 256-thread workgroup (float32; 4096 < K <= 8192 on long rows) --------------------------------
-// The same construction one level up: a radix-4 step in registers around FOUR 4096-point transforms (thread j holds
-// z[j + 256 t], t < 64: u_r = sum_q z[n + 4096 q] W4^(q r), times W16384^(n r), FFT_4096(u_r) = the bins 4 m + r).
-// W16384^((j + 256 t) r) = W16384^(j r) W64^(t r): three table entries per thread times W256^(4 t r) = twB[16 t + 4 r] from LDS.
-// 128 VGPRs of data, 198 in all: two workgroups per CU instead of four, still well ahead of the three-pass pipeline
-// (64 x 2.88 M: 4097 / 5000 / 6000 / 8192 taps 0.50 / 0.52 / 0.56 / 0.67 ms against 0.84 / 0.85 / 0.89 / 0.91).
-// Spectrum: [r][the pair-interleaved order of the 4096-point kernel over m].
-__device__ __forceinline__ void transform_pair16k_r4(cx<float> (&v)[64], cx<float> *lds, const cx<float> *twB_, const cx<float> *twA_,
-                                                     const v4f *__restrict__ Hq, const v2f *__restrict__ w16kg, int j)
-{
-    const v2f Wc = {0.92387953251128675613f, 0.38268343236508977173f}, Wr = {0.70710678118654752440f, 0.70710678118654752440f};
-    const v2f *twB = (const v2f *)twB_, *twA = (const v2f *)twA_;
-    v2f u[4][16];
-    {
-        const v2f w1 = w16kg[j], w2 = w16kg[512 + j], w3 = w16kg[1024 + j];
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            v2f a0 = __builtin_bit_cast(v2f, v[t]), a1 = __builtin_bit_cast(v2f, v[t + 16]);
-            v2f a2 = __builtin_bit_cast(v2f, v[t + 32]), a3 = __builtin_bit_cast(v2f, v[t + 48]);
-            pk::pk_dft4<false, false>(a0, a1, a2, a3);
-            u[0][t] = a0;
-            u[1][t] = pk::pk_cmul<false>(a1, t ? pk::pk_cmul<false>(w1, twB[16 * t + 4]) : w1);
-            u[2][t] = pk::pk_cmul<false>(a2, t ? pk::pk_cmul<false>(w2, twB[16 * t + 8]) : w2);
-            u[3][t] = pk::pk_cmul<false>(a3, t ? pk::pk_cmul<false>(w3, twB[16 * t + 12]) : w3);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        pk::fft4096_pk<false>(u[r], (v2f *)lds, twB, twA, j, Wc, Wr);
-        v4f q[8];
-#pragma unroll
-        for (int m = 0; m < 8; ++m) q[m] = Hq[(8 * r + m) * 256 + j];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            u[r][2 * m] = pk::pk_cmul<false>(u[r][2 * m], v2f{q[m].x, q[m].y});
-            u[r][2 * m + 1] = pk::pk_cmul<false>(u[r][2 * m + 1], v2f{q[m].z, q[m].w});
-        }
-        pk::fft4096_pk<true>(u[r], (v2f *)lds, twB, twA, j, Wc, Wr);
-    }
-    {
-        const v2f w1 = w16kg[j], w2 = w16kg[512 + j], w3 = w16kg[1024 + j];
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            v2f a0 = u[0][t];
-            v2f a1 = pk::pk_cmul<true>(u[1][t], t ? pk::pk_cmul<false>(w1, twB[16 * t + 4]) : w1);
-            v2f a2 = pk::pk_cmul<true>(u[2][t], t ? pk::pk_cmul<false>(w2, twB[16 * t + 8]) : w2);
-            v2f a3 = pk::pk_cmul<true>(u[3][t], t ? pk::pk_cmul<false>(w3, twB[16 * t + 12]) : w3);
-            pk::pk_dft4<true, false>(a0, a1, a2, a3);
-            v[t] = __builtin_bit_cast(cx<float>, a0);
-            v[t + 16] = __builtin_bit_cast(cx<float>, a1);
-            v[t + 32] = __builtin_bit_cast(cx<float>, a2);
-            v[t + 48] = __builtin_bit_cast(cx<float>, a3);
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256, 2)          // 198 VGPRs; at three workgroups per CU (168) it spills and runs 5-8 % slower
-ols_lds16k_r4_kernel(const float *__restrict__ x, float *__restrict__ y, const v4f *__restrict__ Hq, const cx<float> *__restrict__ tw256g,
-                     const cx<float> *__restrict__ t4log, const v2f *__restrict__ w16kg, Geom<float> g, int64_t npairs, int64_t per_xcd)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    cx<float> *lds = (cx<float> *)smem;
-    cx<float> *twB = lds + LDS_N + LDS_N / 16;
-    cx<float> *twA = twB + 256;
-    const int j = threadIdx.x;
-    twB[j] = tw256g[((j >> 4) * (j & 15)) & 255];
-    twA[j] = t4log[j];
-    const int64_t pair = (int64_t)(blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
-    if ((int64_t)(blockIdx.x >> 3) >= per_xcd || pair >= npairs) return;
-    __syncthreads();
-    cx<float> v[64];
-    const PairAt<float> p(pair, g);
-    fetch_pair<float, 16384, 64>(v, x, g, p, j);
-    const bool nan_b = sanitize_partner<float, 64>(v, p);
-    transform_pair16k_r4(v, lds, twB, twA, Hq, w16kg, j);
-    poison_partner<float, 64>(v, nan_b);
-    store_pair<float, 16384, 64>(v, y, g, p, j, smem);
-}
-
-// ---- 16 384 points in a 512-thread workgroup (round 6): the radix-4 construction with HALF the registers per thread --------------
-// ols_lds16k_r4_kernel holds 64 complex values per thread (198 VGPRs: two workgroups = 8 wavefronts per CU).  Here thread j of 512
-// holds z[j + 512 t], t < 32 -- the footprint of the 8192-point kernel, so 16 wavefronts per CU fit -- and the two halves of the
-// workgroup run two of the four 4096-point transforms AT THE SAME TIME, each through its own exchange buffer:
+// ---- 16 384 points in a 512-thread workgroup (float32; 4096 < K <= 8192 on long rows) ------------------------------------------
+// The construction of the 8192-point kernel one level up: a radix-4 step in registers around FOUR 4096-point transforms
+// (u_r = sum_q z[n + 4096 q] W4^(q r), times W16384^(n r), FFT_4096(u_r) = the bins 4 m + r).  Thread j of 512 holds z[j + 512 t],
+// t < 32 -- the footprint of the 8192-point kernel, so 16 wavefronts per CU fit (one 256-thread workgroup holding all 64 values
+// per thread needs 198 VGPRs: 8 wavefronts) -- and the two halves of the workgroup run two of the four 4096-point transforms AT
+// THE SAME TIME, each through its own exchange buffer:
 //   radix-4 step in registers (n, n + 4096 q are t0 + 8 q of one thread), times W16384^(n r) = W16384^(j r) W256^(8 r t0)
 //   -> u_r[j + 512 t0];  half h transforms r = 2 h and 2 h + 1 and needs u_r[jj + 256 t'] (jj = j & 255): the even t' of half 0 and
 //   the odd t' of half 1 are its own, the others sit in thread j ^ 256 -- one exchange of 16 values per thread through the (still
-//   free) transform buffers, and the mirror image on the way back.  Spectrum and tables: those of the 256-thread radix-4 kernel.
+//   free) transform buffers, and the mirror image on the way back.
+// Spectrum: [r][the pair-interleaved order of the 4096-point kernel over m]; tables: W256, the W4096 table, W16384^(r j).
 __device__ __forceinline__ void transform_pair16k_w8(cx<float> (&v)[32], v2f *lbuf, const cx<float> *twB_, const cx<float> *twA_,
                                                      const v4f *__restrict__ Hq, const v2f *__restrict__ w16kg, int j)
 {
@@ -786,7 +707,7 @@ template <typename R> static Plan get_plan(const R *kf, int64_t K, int64_t lead,
                 for (int i = 0; i < 256; ++i) hs.push_back(W(i, 8192));
             if (kind == 3)
                 for (int r = 1; r < 4; ++r)
-                    for (int i = 0; i < 512; ++i) hs.push_back(W(r * i, 16384));      // [r - 1][i]: the 256-thread kernel reads i < 256, the 512-thread one all
+                    for (int i = 0; i < 512; ++i) hs.push_back(W(r * i, 16384));      // [r - 1][j]: W16384^(r j) of thread j
             p.Hs = upload<R>(hs);
             p.owner = std::shared_ptr<void>(p.Hs, [](void *q) { (void)hipFree(q); });
             p.tw256 = (char *)p.Hs + (size_t)N * sizeof(cx<R>);
@@ -800,8 +721,6 @@ template <typename R> static Plan get_plan(const R *kf, int64_t K, int64_t lead,
     g_last[dev] = &it->second;
     return it->second;
 }
-
-static int64_t envi(const char *name, int64_t dflt) { return env_i64(name, dflt); }      // read once per process (common.h)
 
 }  // namespace ldsfft
 
@@ -821,27 +740,27 @@ void olslds_clear()
 // TFX_OLS_LDS16K_R4=0 hand them back to the three-pass pipeline / rocFFT)
 bool olslds_supported(int64_t K, int dtype, int64_t L, int64_t *N_out)
 {
-    if (ldsfft::envi("TFX_OLS_LDS", 1) == 0 || ldsfft::envi("TFX_OLS_NATIVE", 1) == 0) return false;
-    const int64_t lg = ldsfft::envi("TFX_FFT_LOG2N", 0);
+    if (env_i64("TFX_OLS_LDS", 1) == 0 || env_i64("TFX_OLS_NATIVE", 1) == 0) return false;
+    const int64_t lg = env_i64("TFX_FFT_LOG2N", 0);
     if (lg != 0 && lg != 12 && lg != 13 && lg != 14) return false;         // a forced block size of another path
     int64_t N = 0;
-    const int64_t use16k = ldsfft::envi("TFX_OLS_LDS16K", 1);                // 0 never, 1 where the three-pass pipeline does not reach, 2 always
+    const int64_t use16k = env_i64("TFX_OLS_LDS16K", 1);                // 0 never, 1 where the three-pass pipeline does not reach, 2 always
     // taps from which the 8192-point block pays (0: never): measured equal at 512 taps in float32 and in float64
-    const int64_t min8k = ldsfft::envi("TFX_OLS_LDS8K_MINK", dtype == TFX_F32 ? 640 : 700);
+    const int64_t min8k = env_i64("TFX_OLS_LDS8K_MINK", dtype == TFX_F32 ? 640 : 700);
     const bool can8k = K >= 1 && K <= ldsfft::LDS8K / 2 && min8k > 0 && (lg == 0 || lg == 13);
     // rows shorter than 65 536 samples are a handful of workgroups that all run at once: the call takes as long as ONE workgroup,
     // so the smallest block that fits wins there ([2, 44100], 1500 taps: 8 us at 4096 points, 15 us at 8192)
     // from ~3300 taps the radix-4 kernel at 16 384 points overtakes it on long rows (4096 taps: 0.47 against 0.53 ms, 3000 taps:
     // 0.45 against 0.44) although it runs two workgroups per CU instead of four
-    const int64_t min16k = ldsfft::envi("TFX_OLS_LDS16K_MINK", 3400);
-    const bool r4_long = dtype == TFX_F32 && lg == 0 && L >= 65536 && use16k == 1 && ldsfft::envi("TFX_OLS_LDS16K_R4", 1) >= 1 &&
+    const int64_t min16k = env_i64("TFX_OLS_LDS16K_MINK", 3400);
+    const bool r4_long = dtype == TFX_F32 && lg == 0 && L >= 65536 && use16k == 1 && env_i64("TFX_OLS_LDS16K_R4", 1) >= 1 &&
                          min16k > 0 && K >= min16k && K <= ldsfft::LDS16K / 2;
     if (r4_long) N = ldsfft::LDS16K;
     else if (can8k && (lg == 13 || (K >= min8k && (L >= 65536 || K > ldsfft::LDS_N / 2)))) N = ldsfft::LDS8K;
     else if (K >= 1 && K <= ldsfft::LDS_N / 2 && lg != 14 && lg != 13) N = ldsfft::LDS_N;
     else if (K >= 1 && K <= ldsfft::LDS16K / 2 && dtype == TFX_F32 && (lg == 0 || lg == 14) &&
-             (use16k >= 2 || lg == 14 || (use16k == 1 && (L < 65536 || ldsfft::envi("TFX_OLS_LDS16K_R4", 1) >= 1)) ||
-              ldsfft::envi("TFX_OLS_LDS16K_R4", 1) >= 2))
+             (use16k >= 2 || lg == 14 || (use16k == 1 && (L < 65536 || env_i64("TFX_OLS_LDS16K_R4", 1) >= 1)) ||
+              env_i64("TFX_OLS_LDS16K_R4", 1) >= 2))
         N = ldsfft::LDS16K;
     if (!N) return false;
     if (N_out) *N_out = N;
@@ -854,7 +773,7 @@ void olslds_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int elem_byt
 {
     const int64_t line = 128 / elem_bytes;
     const int64_t Tout = Tn + pl + pr - K + 1;
-    const bool align = (Tn % line == 0) && (Tout % line == 0) && ldsfft::envi("TFX_OLS_ALIGN", 1) != 0;
+    const bool align = (Tn % line == 0) && (Tout % line == 0) && env_i64("TFX_OLS_ALIGN", 1) != 0;
     const int64_t lead = align ? (line - (pl % line)) % line : 0;
     int64_t S = N - (K + lead) + 1;
     if (align && S > 2 * line) S -= S % line;
@@ -873,7 +792,7 @@ static void olslds_typed(const R *x, R *y, int64_t C, int64_t Tn, const R *kf_ho
     g.hist = hist; g.H = hist ? H : 0;
     g.ep_gain = ep ? (R)ep->gain : (R)1; g.ep_scale = ep ? ep->scale : 0; g.ep_clamp = ep ? ep->clamp : 0;
     g.ep_stat = ep ? ep->stat_mode : -1; g.ep_partial = nullptr;
-    g.nt = (int)envi("TFX_OLS_LDS_NT", 2);
+    g.nt = (int)env_i64("TFX_OLS_LDS_NT", 2);
     int64_t lead = 0, N = 0;
     TFX_CHECK(olslds_supported(K, sizeof(R) == 4 ? TFX_F32 : TFX_F64, Tn + pl + pr, &N), "olslds_forward: %lld taps are not for this path", (long long)K);
     olslds_geometry(K, Tn, pl, pr, (int)sizeof(R), N, &lead, &g.S);
@@ -881,9 +800,9 @@ static void olslds_typed(const R *x, R *y, int64_t C, int64_t Tn, const R *kf_ho
     g.F = ceil_div(g.Tout, g.S);
     g.nframes = C * g.F;
     // 16 384 points: the 1024-thread workgroup on rows the three-pass pipeline does not reach (few pairs: the sixteen wavefronts
-    // of one pair run side by side), four 4096-point transforms in a 256-thread workgroup on long rows (TFX_OLS_LDS16K_R4: 0 never, 2 always)
-    const int64_t r4 = envi("TFX_OLS_LDS16K_R4", 1);
-    const bool use_r4 = N == LDS16K && sizeof(R) == 4 && (r4 >= 2 || (r4 == 1 && L >= 65536 && envi("TFX_OLS_LDS16K", 1) < 2));
+    // of one pair run side by side), four 4096-point transforms in a 512-thread workgroup on long rows (TFX_OLS_LDS16K_R4: 0 never, 2 always)
+    const int64_t r4 = env_i64("TFX_OLS_LDS16K_R4", 1);
+    const bool use_r4 = N == LDS16K && sizeof(R) == 4 && (r4 >= 2 || (r4 == 1 && L >= 65536 && env_i64("TFX_OLS_LDS16K", 1) < 2));
     const int kind = N == LDS_N ? 0 : N == LDS8K ? 1 : use_r4 ? 3 : 2;
     const Plan plan = get_plan<R>(kf_host, K, lead, (int)N, kind, stream);      // holds its buffer until this function has enqueued its launch
     const int64_t npairs = ceil_div(g.nframes, 2);
@@ -904,14 +823,8 @@ static void olslds_typed(const R *x, R *y, int64_t C, int64_t Tn, const R *kf_ho
     static bool ready[4][TFX_MAX_DEVICES] = {};            // per kernel kind of this instantiation
     bool done = false;
     if constexpr (sizeof(R) == 4) {
-        if (kind == 3 && envi("TFX_OLS_LDS16K_W8", 1) != 0) {
-            static bool ready_w8[TFX_MAX_DEVICES] = {};
-            launch(ols_lds16k_w8_kernel, ready_w8[dev], "ols_lds16k_w8_kernel", lds16k_w8_bytes(), per_xcd * 8, 512,
-                   (const float *)x, (float *)y, (const v4f *)plan.Hs, (const cx<float> *)plan.tw256, (const cx<float> *)plan.t4lo,
-                   (const v2f *)plan.w8k, g, npairs, per_xcd);
-            done = true;
-        } else if (kind == 3) {
-            launch(ols_lds16k_r4_kernel, ready[3][dev], "ols_lds16k_r4_kernel", lds_bytes<float>(), per_xcd * 8, 256,
+        if (kind == 3) {
+            launch(ols_lds16k_w8_kernel, ready[3][dev], "ols_lds16k_w8_kernel", lds16k_w8_bytes(), per_xcd * 8, 512,
                    (const float *)x, (float *)y, (const v4f *)plan.Hs, (const cx<float> *)plan.tw256, (const cx<float> *)plan.t4lo,
                    (const v2f *)plan.w8k, g, npairs, per_xcd);
             done = true;
@@ -922,7 +835,7 @@ static void olslds_typed(const R *x, R *y, int64_t C, int64_t Tn, const R *kf_ho
                 TFX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
                 cus_tab[dev] = std::max(8, cus / 8 * 8);      // one 1024-thread workgroup per CU
             }
-            const int64_t grid = std::max<int64_t>(8, std::min<int64_t>(envi("TFX_OLS_LDS16K_GRID", cus_tab[dev]) / 8 * 8, per_xcd * 8));
+            const int64_t grid = std::max<int64_t>(8, std::min<int64_t>(env_i64("TFX_OLS_LDS16K_GRID", cus_tab[dev]) / 8 * 8, per_xcd * 8));
             launch(ols_lds16k_kernel, ready[2][dev], "ols_lds16k_kernel", lds16k_bytes(), grid, 1024,
                    (const float *)x, (float *)y, (const v4f *)plan.Hs, (const v2f *)plan.tw256, g, npairs, per_xcd);
             done = true;

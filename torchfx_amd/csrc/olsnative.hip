@@ -185,23 +185,12 @@ static std::vector<cpx> twiddles(int64_t n, int64_t count, int64_t step)   // W_
     return t;
 }
 
-static int64_t envi(const char *name, int64_t dflt) { return env_i64(name, dflt); }      // read once per process (common.h)
-
 // ---- per-device one-time set-up: kernel attributes (the first touch of a kernel loads the library's code object: 10-25 ms)
 // and the internal streams with their fork / join events (the first stream of a process costs ~5 ms each).  The first call
 // on a device runs this on a helper thread WHILE the calling thread computes the filter's spectrum on the host.
-typedef void (*colf_t)(const float *, cpx *, const cpx *, OlsGeom, int64_t);
-typedef void (*coli_t)(const cpx *, float *, const cpx *, OlsGeom, int64_t);
 typedef void (*row_t)(cpx *, const cpx *, const cpx *, const cpx *, const cpx *, const cpx *, const cpx *, const cpx *,
                       int64_t, int, int64_t);
-static const colf_t colf_tab[2][5] = {
-    {ols_col_fwd16_kernel<2, 0>, ols_col_fwd16_kernel<2, 1>, ols_col_fwd16_kernel<2, 2>, ols_col_fwd16_kernel<2, 3>, ols_col_fwd16_kernel<2, 4>},
-    {ols_col_fwd16_kernel<1, 0>, ols_col_fwd16_kernel<1, 1>, ols_col_fwd16_kernel<1, 2>, ols_col_fwd16_kernel<1, 3>, ols_col_fwd16_kernel<1, 4>}};
-static const coli_t coli_tab[2][5] = {
-    {ols_col_inv16_kernel<2, 0>, ols_col_inv16_kernel<2, 1>, ols_col_inv16_kernel<2, 2>, ols_col_inv16_kernel<2, 3>, ols_col_inv16_kernel<2, 4>},
-    {ols_col_inv16_kernel<1, 0>, ols_col_inv16_kernel<1, 1>, ols_col_inv16_kernel<1, 2>, ols_col_inv16_kernel<1, 3>, ols_col_inv16_kernel<1, 4>}};
-static const row_t row_tab[8] = {ols_row4096_kernel<0, 0>, ols_row4096_kernel<1, 0>, ols_row4096_kernel<0, 1>, ols_row4096_kernel<1, 1>,
-                                 ols_row4096_kernel<0, 2>, ols_row4096_kernel<1, 2>, ols_row4096_kernel<0, 3>, ols_row4096_kernel<1, 3>};
+static const row_t row_tab[2] = {ols_row4096_kernel<0>, ols_row4096_kernel<1>};
 typedef void (*colsos_t)(const float *, cpx *, const cpx *, OlsGeom, int64_t, SosFuse);
 #define TFX_SOSF_ROW(TAPS_, UNIT_) {ols_col_fwd16_sos_kernel<1, TAPS_, UNIT_>, ols_col_fwd16_sos_kernel<2, TAPS_, UNIT_>, ols_col_fwd16_sos_kernel<3, TAPS_, UNIT_>, \
                                     ols_col_fwd16_sos_kernel<4, TAPS_, UNIT_>, ols_col_fwd16_sos_kernel<5, TAPS_, UNIT_>, ols_col_fwd16_sos_kernel<6, TAPS_, UNIT_>, \
@@ -226,20 +215,17 @@ static void ols_set_attributes(int dev)
 {
     std::lock_guard<std::mutex> lk(g_attr_mu);            // not the plan lock: this runs beside the spectrum computation
     if (attr_tab[dev]) return;
-    for (int a = 0; a < 8; ++a)
+    for (int a = 0; a < 2; ++a)
         TFX_HIP(hipFuncSetAttribute((const void *)row_tab[a], hipFuncAttributeMaxDynamicSharedMemorySize, (int)((4096 + 256 + 512) * sizeof(cpx))));
     TFX_HIP(hipFuncSetAttribute((const void *)ols_row8192_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((4096 + 256 + 512) * sizeof(cpx))));
     TFX_HIP(hipFuncSetAttribute((const void *)ols_row8192_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((4096 + 256 + 512) * sizeof(cpx))));
     TFX_HIP(hipFuncSetAttribute((const void *)ols_rowspec8192_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((4096 + 256 + 512) * sizeof(cpx))));
     TFX_HIP(hipFuncSetAttribute((const void *)ols_rowspec4096_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((4096 + 256 + 512) * sizeof(cpx))));
-    for (int a = 0; a < 2; ++a)
-        for (int b = 0; b < 5; ++b) {
-            TFX_HIP(hipFuncSetAttribute((const void *)colf_tab[a][b], hipFuncAttributeMaxDynamicSharedMemorySize, (int)OLS_SHM_COL));
-            TFX_HIP(hipFuncSetAttribute((const void *)coli_tab[a][b], hipFuncAttributeMaxDynamicSharedMemorySize, (int)OLS_SHM_COL));
-        }
+    TFX_HIP(hipFuncSetAttribute((const void *)ols_col_fwd16_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OLS_SHM_COL));
+    TFX_HIP(hipFuncSetAttribute((const void *)ols_col_inv16_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OLS_SHM_COL));
     for (int a = 0; a < 4; ++a)
         for (int b = 0; b < SOSF_MAXK; ++b)
-            TFX_HIP(hipFuncSetAttribute((const void *)colsos_tab[a][b], hipFuncAttributeMaxDynamicSharedMemorySize, (int)OLS_SHM_SOSF + 16384));
+            TFX_HIP(hipFuncSetAttribute((const void *)colsos_tab[a][b], hipFuncAttributeMaxDynamicSharedMemorySize, (int)OLS_SHM_SOSF));
     attr_tab[dev] = true;
 }
 static void ols_make_lanes(int dev, int nlanes)           // lanes are created when first used
@@ -261,7 +247,7 @@ void olsnative_prewarm()
     const int dev = current_device();
     // the lanes of both pipelines (plain: 2; recursion in pass A: 3) -- a stream created later, behind gigabytes of workspace
     // allocations, cost 64 ms in the first call (profiles/r05_experiments.txt section 9)
-    const int want_lanes = (int)std::min<int64_t>(MAXL, std::max<int64_t>(1, std::max(envi("TFX_OLS_STREAMS", 2), envi("TFX_OLS_SOS_STREAMS", 3))));
+    const int want_lanes = (int)std::min<int64_t>(MAXL, std::max<int64_t>(1, std::max(env_i64("TFX_OLS_STREAMS", 2), env_i64("TFX_OLS_SOS_STREAMS", 3))));
     std::lock_guard<std::mutex> lk(g_warm_mu);
     if (g_warm[dev].valid()) return;                         // started before (its result, or error, is kept)
     if (attr_tab[dev] && (want_lanes <= 1 || lanes_tab[dev].stream[want_lanes - 1])) return;
@@ -304,7 +290,7 @@ void olsnative_wait_warm()
 struct HostTrace {
     bool on;
     std::chrono::steady_clock::time_point t0;
-    HostTrace() : on(envi("TFX_OLS_TRACE", 0) != 0), t0(std::chrono::steady_clock::now()) {}
+    HostTrace() : on(env_i64("TFX_OLS_TRACE", 0) != 0), t0(std::chrono::steady_clock::now()) {}
     void mark(const char *what)
     {
         if (!on) return;
@@ -349,7 +335,7 @@ static NativePlanPtr get_native_plan(const float *kf, int64_t K, int64_t N, int6
     pl->N = N; pl->K = K; pl->N2 = (int)(N / OLS_N1);
     HostTrace tr;
     const int N2 = pl->N2;
-    const bool dev_spectrum = (N2 == 4096 || N2 == 8192) && envi("TFX_OLS_GPU_SPECTRUM", 1) != 0;
+    const bool dev_spectrum = (N2 == 4096 || N2 == 8192) && env_i64("TFX_OLS_GPU_SPECTRUM", 1) != 0;
     if (!dev_spectrum) {
         // spectrum in float64 on the host: conj(FFT(kf zero-padded)) / N   (_fftconv.py:123-124,131 + irfft scaling)
         std::vector<double> re((size_t)N, 0.0), im((size_t)N, 0.0);
@@ -418,7 +404,7 @@ static NativePlanPtr get_native_plan(const float *kf, int64_t K, int64_t N, int6
         g.Tn = K; g.Tout = K; g.F = 1; g.S = N; g.pad_left = lead; g.out_shift = 0; g.nframes = 1;
         g.hist = nullptr; g.H = 0; g.ep_gain = 1.0f; g.ep_scale = 0; g.ep_clamp = 0; g.ep_stat = -1; g.ep_partial = nullptr;
         g.N2 = N2; g.P2 = N2; g.nt = 0;
-        hipLaunchKernelGGL(colf_tab[1][0], dim3((unsigned)(N2 / OLS_CB)), dim3(512), OLS_SHM_COL, stream,
+        hipLaunchKernelGGL(ols_col_fwd16_kernel<1>, dim3((unsigned)(N2 / OLS_CB)), dim3(512), OLS_SHM_COL, stream,
                            (const float *)pl->taps_dev, pl->Hp, pl->tw256, g, (int64_t)0);
         TFX_HIP(hipGetLastError());
         if (N2 == 4096)
@@ -453,12 +439,12 @@ void olsnative_clear()
 // block sizes this path implements: N = 256 * N2, N2 in {256, 1024, 4096, 8192}
 bool olsnative_supported(int64_t K, int64_t L, int64_t *N_out)
 {
-    if (envi("TFX_OLS_NATIVE", 1) == 0) return false;
+    if (env_i64("TFX_OLS_NATIVE", 1) == 0) return false;
     int64_t N = 0;
-    const int64_t lg = envi("TFX_FFT_LOG2N", 0);
+    const int64_t lg = env_i64("TFX_FFT_LOG2N", 0);
     if (lg == 16 || lg == 18 || lg == 20 || lg == 21) N = (int64_t)1 << lg;
     else if (lg != 0) return false;
-    else if (K < envi("TFX_OLS_NATIVE_MIN_K", 16)) return false;   // a handful of taps: use the direct kernel / rocFFT
+    else if (K < env_i64("TFX_OLS_NATIVE_MIN_K", 16)) return false;   // a handful of taps: use the direct kernel / rocFFT
     else if (4 * K <= (1 << 16)) {
         // 8193 ... 16 384 taps (below that the one-launch kernels serve): 2^16 points waste 12-25 % of a block on the overlap.  Rows of
         // 4 M samples and more take the 2^20-point block (16 x 28.8 M: 16 384 taps 2.20 -> 1.93 ms, 12 288: 2.07 -> 1.93, 8193: 1.98
@@ -466,16 +452,16 @@ bool olsnative_supported(int64_t K, int64_t L, int64_t *N_out)
         // 0.831, 9000: 0.850 -> 0.827); shorter rows are a handful of workgroups either way (profiles/r06_experiments.txt section 9)
         N = 1 << 16;
         if (K > 8192 && L >= 4 * ((int64_t)1 << 20)) N = (int64_t)1 << 20;
-        else if (K >= envi("TFX_OLS_N18_MINK", 9000) && L >= ((int64_t)1 << 21)) N = 1 << 18;
+        else if (K >= env_i64("TFX_OLS_N18_MINK", 9000) && L >= ((int64_t)1 << 21)) N = 1 << 18;
     }
     // rows shorter than 4 M samples: 2^18 points -- but from ~22 K taps the 2^20-point block wins there too once a row holds two
     // of them (64 x 2.88 M: 65 536 taps 1.01-1.07 -> 0.86 ms, 32 768 taps 0.92 -> 0.85, 23 000 taps 0.897 -> 0.852; at 22 000 taps
     // 0.820 against 0.855; r05 experiments section 11, r06 section 9)
-    else if (2 * K <= (1 << 18) && L < 4 * ((int64_t)1 << 20)) N = (K > envi("TFX_OLS_N20_MINK", 22528) && L >= ((int64_t)1 << 21)) ? ((int64_t)1 << 20) : (1 << 18);
+    else if (2 * K <= (1 << 18) && L < 4 * ((int64_t)1 << 20)) N = (K > env_i64("TFX_OLS_N20_MINK", 22528) && L >= ((int64_t)1 << 21)) ? ((int64_t)1 << 20) : (1 << 18);
     else if (2 * K <= (1 << 20)) {
         N = (int64_t)1 << 20;                            // long signals: 4x fewer blocks, less overlap
         // 2^21 = 256 x 8192 on signals of at least four such blocks: half the overlap again (TFX_OLS_N21: 0 never)
-        if (envi("TFX_OLS_N21", 0) != 0 && K > 16384 && L >= ((int64_t)1 << 23)) N = (int64_t)1 << 21;
+        if (env_i64("TFX_OLS_N21", 0) != 0 && K > 16384 && L >= ((int64_t)1 << 23)) N = (int64_t)1 << 21;
     }
     else return false;
     if (N < 2 * K) return false;
@@ -495,22 +481,19 @@ bool sos_unit_rows(const double *sos_host, int64_t K, double (*rows)[5]);     //
 
 bool olsnative_sos_supported(int64_t Ksos, int64_t warm, int64_t K, int64_t Tn, int64_t pl, int64_t pr, int force, int64_t *N_out)
 {
-    if (envi("TFX_OLS_SOS", 1) == 0) return false;
-    if (Ksos < 1 || Ksos > SOSF_MAXK || warm < 0 || warm > envi("TFX_OLS_SOS_MAXWARM", 4096)) return false;
+    if (env_i64("TFX_OLS_SOS", 1) == 0) return false;
+    if (Ksos < 1 || Ksos > SOSF_MAXK || warm < 0 || warm > env_i64("TFX_OLS_SOS_MAXWARM", 4096)) return false;
     const int64_t L = Tn + pl + pr;
-    if (L < K || envi("TFX_OLS_ALIGN", 1) == 0) return false;
+    if (L < K || env_i64("TFX_OLS_ALIGN", 1) == 0) return false;
     int64_t N = (int64_t)1 << (force == 2 ? 21 : 20);       // force: 1 = the 2^20-point block, 2 = the 2^21-point block, whatever the row length
     if (force) { if (N < 2 * (K + 32)) return false; }
     else {
         if (!olsnative_supported(K, L, &N) || (N != ((int64_t)1 << 20) && N != ((int64_t)1 << 21))) return false;
         // rows of 8192 samples (N = 2^21) halve the warm-up share of the recursion pass: 9.7 against 10.1 ms on the cfg-5 chain
         // (the plain pipeline is 5 % slower at 2^21 and stays at 2^20; profiles/r05_experiments.txt section 8)
-        if (N == ((int64_t)1 << 20) && envi("TFX_OLS_SOS_N21", 1) != 0 && L >= ((int64_t)1 << 23) && 2 * (K + 32) <= ((int64_t)1 << 21))
+        if (N == ((int64_t)1 << 20) && env_i64("TFX_OLS_SOS_N21", 1) != 0 && L >= ((int64_t)1 << 23) && 2 * (K + 32) <= ((int64_t)1 << 21))
             N = (int64_t)1 << 21;
     }
-    // development (profiles/r06_experiments.txt): TFX_OLS_SOS_PROBE_A = 1 runs the recursion pass alone (passes B and C skipped, wrong
-    // output), = 22 also takes rows of 16 384 samples (N = 2^22) -- what the warm-up share of such rows would buy pass A'
-    if (envi("TFX_OLS_SOS_PROBE_A", 0) == 22 && !force) N = (int64_t)1 << 22;
     if (N_out) *N_out = N;
     return true;
 }
@@ -520,7 +503,7 @@ void olsnative_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int64_t N
 {
     const int64_t L = Tn + pl + pr, Tout = L - K + 1;
     (void)Tout;
-    const bool align = envi("TFX_OLS_ALIGN", 1) != 0;
+    const bool align = env_i64("TFX_OLS_ALIGN", 1) != 0;
     const int64_t lead = align ? (32 - (pl % 32)) % 32 : 0;
     int64_t S = N - (K + lead) + 1;
     if (align && S > 64) S -= S % 32;
@@ -552,7 +535,7 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
     // sh(c) samples (row_shift) so that its frames start on lines of MEMORY; the column passes address the same way, only the
     // first and the last line of a row are partial.
     int64_t lead = 0;
-    const bool align = envi("TFX_OLS_ALIGN", 1) != 0;
+    const bool align = env_i64("TFX_OLS_ALIGN", 1) != 0;
     if (align) lead = (32 - (pl % 32)) % 32;
     g.sh_base = (int)(((uintptr_t)x >> 2) & 31);
     g.sh_on = (align && (Tn % 32 != 0 || g.sh_base != 0)) ? 1 : 0;
@@ -593,8 +576,8 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
     tr.mark("plan (spectrum, tables)");
     g.F = ceil_div(g.Tout + g.out_shift + (g.sh_on ? 31 : 0), g.S);
     g.nframes = C * g.F; g.N2 = plan->N2;
-    g.P2 = g.N2 + (int)envi("TFX_OLS_PITCH_PAD", 0);
-    g.nt = (int)envi("TFX_OLS_NT", 3);
+    g.P2 = g.N2;
+    g.nt = (int)env_i64("TFX_OLS_NT", 3);
     const int64_t npairs = ceil_div(g.nframes, 2);
     if (!sosf && C > 1 && (g.F & 1)) {     // some pair straddles two signal rows: see ols_col_fwd16_kernel
         g.nf_pair = (int *)scratch("olsn_nf_pair", (size_t)C * sizeof(int), stream);
@@ -611,15 +594,15 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
     // Cascade in pass A: one workgroup per frame pair lives for a whole frame (190-320 column blocks), so a launch needs
     // hundreds of pairs to fill the chip -- slabs of 320 pairs (2.5 GB; N = 2^21: 240 pairs, 3.75 GB) on three lanes
     // (profiles/r05_experiments.txt).
-    int nlanes = (int)(sosf ? envi("TFX_OLS_SOS_STREAMS", 3) : envi("TFX_OLS_STREAMS", 2));
+    int nlanes = (int)(sosf ? env_i64("TFX_OLS_SOS_STREAMS", 3) : env_i64("TFX_OLS_STREAMS", 2));
     if (nlanes < 1) nlanes = 1;
     if (nlanes > MAXL) nlanes = MAXL;
     const int64_t pair_bytes = (int64_t)OLS_N1 * g.P2 * (int64_t)sizeof(cpx);
-    int64_t slab = sosf ? envi("TFX_OLS_SOS_PAIRS", 0) : envi("TFX_OLS_PAIRS_PER_SLAB", 0);
+    int64_t slab = sosf ? env_i64("TFX_OLS_SOS_PAIRS", 0) : env_i64("TFX_OLS_PAIRS_PER_SLAB", 0);
     if (slab <= 0) {
         // The workspace lives outside PyTorch's caching allocator and is kept between calls (scratch(), released by
         // tfx_clear_caches); TFX_OLS_SLAB_MB bounds a lane's share, never more than 1/8 of the free memory over all lanes.
-        int64_t slab_mb = sosf ? envi("TFX_OLS_SOS_SLAB_MB", N == ((int64_t)1 << 21) ? 3840 : 2560) : envi("TFX_OLS_SLAB_MB", 64);
+        int64_t slab_mb = sosf ? env_i64("TFX_OLS_SOS_SLAB_MB", N == ((int64_t)1 << 21) ? 3840 : 2560) : env_i64("TFX_OLS_SLAB_MB", 64);
         {
             // the cap follows the memory free when the device is first used (and again after tfx_clear_caches), not at every call:
             // a driver query per step costs tens of microseconds, is not allowed while a stream is capturing, and would make the
@@ -658,37 +641,30 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
         if (slab <= 8) { (void)scratch(lane_tags[got], bytes, stream); break; }          // throws with the allocator's name in the message
         slab = std::max<int64_t>(8, slab / 2);
     }
-    cpx *T = Tlane[0];
     tr.mark("workspaces");
     const size_t shm_col = OLS_SHM_COL;
     const size_t shm_row = (size_t)(g.N2 * 5) * sizeof(cpx);
-    const int probe = (int)envi("TFX_OLS_PROBE", 0);           // development only (tools/archive/ols_knobs.py)
-    const int nbf = envi("TFX_OLS_COL_THREADS", 512) == 512 ? 1 : 2;
     // XCD-aware row map (1) pays when a slab holds many pairs per spectrum row; with cache-sized slabs the plain map is faster
-    const int rowmap = (int)envi("TFX_OLS_ROWMAP", slab >= 32 ? 1 : 0);
-    const int colv = (probe & 3) ? (probe & 3) : (envi("TFX_OLS_PK", 1) ? 0 : 4);     // 4 = compiler-scheduled butterflies
-    const colf_t colf = colf_tab[nbf == 1][colv];
-    const coli_t coli = coli_tab[nbf == 1][colv];
-    const int xch = (int)envi("TFX_OLS_ROW_XCH", envi("TFX_OLS_PK", 1) ? 3 : 2);
-    const row_t rowk = row_tab[(rowmap == 0 ? 0 : 1) + 2 * (xch < 0 || xch > 3 ? 3 : xch)];
+    const int rowmap = (int)env_i64("TFX_OLS_ROWMAP", slab >= 32 ? 1 : 0);
+    const row_t rowk = row_tab[rowmap == 0 ? 0 : 1];
+    const bool row_r4 = env_i64("TFX_OLS_ROW_R4", 0) != 0;        // radix-4 row passes for N2 = 256 / 1024 (cross-check)
     ols_set_attributes(dev);
     tr.mark("function attributes");
     const int ncb = g.N2 / OLS_CB;
     SosFuse sosk{};
     bool sos_unit = false;
     if (sosf) {
-        TFX_CHECK((g.N2 == 4096 || g.N2 == 8192 || envi("TFX_OLS_SOS_PROBE_A", 0) == 22) && align && !hist && sosf->K >= 1 && sosf->K <= SOSF_MAXK && sosf->warm >= 0,
+        TFX_CHECK((g.N2 == 4096 || g.N2 == 8192) && align && !hist && sosf->K >= 1 && sosf->K <= SOSF_MAXK && sosf->warm >= 0,
                   "olsnative_forward: the cascade cannot run inside the column pass here (olsnative_sos_supported)");
         g.nf_flag = (int *)scratch("olsn_nf_flag", (size_t)g.nframes * sizeof(int), stream);
-        sos_unit = envi("TFX_OLS_SOS_UNIT_B0", 1) != 0 && sos_unit_rows(sosf->sos, sosf->K, sosk.co);
+        sos_unit = env_i64("TFX_OLS_SOS_UNIT_B0", 1) != 0 && sos_unit_rows(sosf->sos, sosf->K, sosk.co);
         for (int64_t s = 0; s < sosf->K && !sos_unit; ++s) {
             const double *co = sosf->sos + 6 * s;                 // b0 b1 b2 a0 a1 a2; a0 is not used (iir_cpu.cpp:86)
             sosk.co[s][0] = co[0]; sosk.co[s][1] = co[1]; sosk.co[s][2] = co[2]; sosk.co[s][3] = -co[4]; sosk.co[s][4] = -co[5];
         }
         sosk.sections = sosf->sections;
-        sosk.prio = (int)envi("TFX_OLS_SOS_PRIO", 1);
-        const int64_t warm_dev = envi("TFX_OLS_SOS_WARM", -1);            // development: probe builds of the experiments log (wrong results)
-        sosk.warm_blocks = (int)ceil_div(warm_dev >= 0 ? warm_dev : sosf->warm, OLS_CB);
+        sosk.prio = 1;
+        sosk.warm_blocks = (int)ceil_div(sosf->warm, OLS_CB);
     }
     // Internal streams (TFX_OLS_STREAMS, default 2), slabs rotate over them: while one slab drains the tail of a pass
     // (the last, partially filled round of workgroups) the other slab's pass fills the idle CUs.
@@ -708,72 +684,42 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
     }
     tr.mark("lanes, workspaces, fork");
     int64_t slab_idx = 0;
-    // Cascade in pass A: the lanes would otherwise march in step (all in pass A', then all in B, then all in C) -- the first
-    // slab of lane i is cut to (i + 1) / nlanes of a slab so that the three kinds of pass meet on the chip
-    // development: extra dynamic LDS for the recursion pass = one workgroup per CU, the rest of the CU stays free for passes B / C
-    const size_t sos_lds_pad = sosf ? (size_t)envi("TFX_OLS_SOS_LDS_PAD", 0) : 0;
-    const int64_t sos_sub = sosf ? envi("TFX_OLS_SOS_SUB_PAIRS", 0) : 0;
-    const int stagger = sosf ? (int)envi("TFX_OLS_SOS_STAGGER", 0) : 0;
-    for (int64_t p0 = 0, step_pairs = slab; p0 < npairs; p0 += step_pairs, ++slab_idx) {
-        step_pairs = (stagger && nlanes > 1 && slab_idx < nlanes) ? std::max<int64_t>(1, slab * (slab_idx + 1) / nlanes) : slab;
-        const int64_t np = (npairs - p0 < step_pairs) ? (npairs - p0) : step_pairs;
+    for (int64_t p0 = 0; p0 < npairs; p0 += slab, ++slab_idx) {
+        const int64_t np = (npairs - p0 < slab) ? (npairs - p0) : slab;
         const int ln = nlanes > 1 ? (int)(slab_idx % nlanes) : 0;
         hipStream_t stream = nlanes > 1 ? lane_stream[ln] : user_stream;   // shadows the parameter
         cpx *T = Tlane[ln];
         if (sosf) {
             ProfScope ps("ols_col_fwd16_sos_kernel", stream);
-            hipLaunchKernelGGL(colsos_tab[(sosf->sections ? 1 : 0) + (sos_unit ? 2 : 0)][sosf->K - 1], dim3((unsigned)np), dim3(512), OLS_SHM_SOSF + sos_lds_pad, stream,
+            hipLaunchKernelGGL(colsos_tab[(sosf->sections ? 1 : 0) + (sos_unit ? 2 : 0)][sosf->K - 1], dim3((unsigned)np), dim3(512), OLS_SHM_SOSF, stream,
                                x, T, plan->tw256, g, 2 * p0, sosk);
             TFX_HIP(hipGetLastError());
         } else {
             ProfScope ps("ols_col_fwd16_kernel", stream);
-            hipLaunchKernelGGL(colf, dim3((unsigned)(np * ncb)), dim3(512 / nbf), shm_col, stream,
+            hipLaunchKernelGGL(ols_col_fwd16_kernel<1>, dim3((unsigned)(np * ncb)), dim3(512), shm_col, stream,
                                x, T, plan->tw256, g, 2 * p0);
             TFX_HIP(hipGetLastError());
         }
-        if (sosf && envi("TFX_OLS_SOS_PROBE_A", 0) != 0) continue;          // development: pass A' alone
-        if (sosf && probe == 0 && sos_sub > 0 && sos_sub < np && g.N2 == 4096) {
-            // behind the one wide launch of the recursion pass, passes B and C walk the slab in cache-sized pieces so that pass C
-            // finds what pass B just wrote in the Infinity Cache (the regime of the plain pipeline's 64 MB slabs).  Measured
-            // slower (10.4-10.5 against 9.7-10.2 ms, profiles/r05_experiments.txt): off by default (TFX_OLS_SOS_SUB_PAIRS)
-            for (int64_t q0 = 0; q0 < np; q0 += sos_sub) {
-                const int64_t nq = std::min(sos_sub, np - q0);
-                cpx *Tq = T + q0 * ((int64_t)OLS_N1 * g.P2);
-                {
-                    ProfScope ps("ols_row4096_kernel", stream);
-                    hipLaunchKernelGGL(row_tab[2 * (xch < 0 || xch > 3 ? 3 : xch)], dim3((unsigned)(nq * OLS_N1)), dim3(256), (size_t)(4096 + 256 + 512) * sizeof(cpx), stream,
-                                       Tq, plan->Hp, plan->tw256, plan->t4lo, plan->t4hi, plan->tlo, plan->thi, plan->tu, N - 1, g.P2, nq);
-                    TFX_HIP(hipGetLastError());
-                }
-                {
-                    ProfScope ps("ols_col_inv16_kernel", stream);
-                    hipLaunchKernelGGL(coli, dim3((unsigned)(nq * ncb)), dim3(512 / nbf), shm_col, stream, Tq, y, plan->tw256, g, 2 * (p0 + q0));
-                    TFX_HIP(hipGetLastError());
-                }
-            }
-            continue;
-        }
         {
             const int64_t nrows = np * OLS_N1;
-            ProfScope ps(g.N2 == 4096 ? "ols_row4096_kernel" : g.N2 == 8192 ? "ols_row8192_kernel" : (g.N2 == 1024 && envi("TFX_OLS_ROW_R4", 0) == 0 ? "ols_row1024_kernel" : "ols_row_kernel"), stream);
-            if (g.N2 == 4096 && probe == 0) {
+            ProfScope ps(g.N2 == 4096 ? "ols_row4096_kernel" : g.N2 == 8192 ? "ols_row8192_kernel" : (g.N2 == 1024 && !row_r4 ? "ols_row1024_kernel" : "ols_row_kernel"), stream);
+            if (g.N2 == 4096) {
                 hipLaunchKernelGGL(rowk, dim3((unsigned)nrows), dim3(256), (size_t)(4096 + 256 + 512) * sizeof(cpx), stream,
                                    T, plan->Hp, plan->tw256, plan->t4lo, plan->t4hi, plan->tlo, plan->thi, plan->tu,
                                    N - 1, g.P2, np);
-            } else if (g.N2 == 4096) {
             } else if (g.N2 == 8192) {
                 hipLaunchKernelGGL(rowmap == 0 ? ols_row8192_kernel<0> : ols_row8192_kernel<1>, dim3((unsigned)nrows), dim3(256),
                                    (size_t)(4096 + 256 + 512) * sizeof(cpx), stream,
                                    T, plan->Hp, plan->tw256, plan->t4lo, plan->tlo, plan->thi, plan->tu, plan->w8k, N - 1, g.P2, np);
             }
-            else if (g.N2 == 1024 && envi("TFX_OLS_ROW_R4", 0) == 0)
-                hipLaunchKernelGGL(envi("TFX_OLS_PK", 1) ? ols_row1024_kernel<true> : ols_row1024_kernel<false>, dim3((unsigned)ceil_div(nrows, 4)), dim3(256),
+            else if (g.N2 == 1024 && !row_r4)
+                hipLaunchKernelGGL(ols_row1024_kernel, dim3((unsigned)ceil_div(nrows, 4)), dim3(256),
                                    (size_t)(1024 + 4 * (1024 + 64)) * sizeof(cpx), stream,
                                    T, plan->Hp, plan->twr, plan->tlo, plan->thi, plan->tu, nrows, N - 1, g.P2);
             else if (g.N2 == 1024)
                 hipLaunchKernelGGL(ols_row_kernel<5>, dim3((unsigned)ceil_div(nrows, 4)), dim3(256), shm_row, stream,
                                    T, plan->Hp, plan->twr, plan->tlo, plan->thi, nrows, g.P2);
-            else if (envi("TFX_OLS_PK", 1) != 0 && envi("TFX_OLS_ROW_R4", 0) == 0) {
+            else if (!row_r4) {
                 const int64_t groups = ceil_div(nrows, 16);
                 const int64_t cap = 8 * 256 * 3;                 // a few rounds of resident workgroups: the lane twiddles are loaded once per workgroup
                 hipLaunchKernelGGL(ols_row256pk_kernel, dim3((unsigned)std::min(groups, cap)), dim3(256), (size_t)16 * 272 * sizeof(cpx), stream,
@@ -785,7 +731,7 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
         }
         {
             ProfScope ps("ols_col_inv16_kernel", stream);
-            hipLaunchKernelGGL(coli, dim3((unsigned)(np * ncb)), dim3(512 / nbf), shm_col, stream,
+            hipLaunchKernelGGL(ols_col_inv16_kernel<1>, dim3((unsigned)(np * ncb)), dim3(512), shm_col, stream,
                                T, y, plan->tw256, g, 2 * p0);
             TFX_HIP(hipGetLastError());
         }

@@ -951,8 +951,6 @@ void sos_clear_plans()
     g_plans.clear();
 }
 
-static int env_int(const char *name, int dflt) { return (int)env_i64(name, dflt); }      // read once per process (common.h)
-
 static int g_cus[TFX_MAX_DEVICES] = {0};
 static int device_cus()
 {
@@ -974,15 +972,15 @@ static void plan_segments(SosParams &p, int64_t plan_warm, int TILE, int residen
 {
     const int64_t tiles_total = ceil_div(p.T, TILE);
     int64_t nseg = 1, seg_len = tiles_total * TILE, warm = 0;
-    const int force_nseg = env_int("TFX_SOS_NSEG", 0);
+    const int force_nseg = (int)env_i64("TFX_SOS_NSEG", 0);
     if (plan_warm >= 0) {
         {
             // halo rounded to 1 KB of float32: streams start on cache-line boundaries; 256 measured 1.5-4 % faster
             // than 32 on the float64 kernel (64 x 2.88 M / 10 M / 28.8 M), no difference beyond
-            const int64_t q = env_int("TFX_SOS_WARM_ROUND", 256);         // samples; power of two >= 32
+            const int64_t q = env_i64("TFX_SOS_WARM_ROUND", 256);         // samples; power of two >= 32
             warm = (plan_warm + q - 1) & ~(q - 1);
         }
-        const int wpc = env_int("TFX_SOS_WAVES_PER_CU", 0);
+        const int wpc = (int)env_i64("TFX_SOS_WAVES_PER_CU", 0);
         const int64_t capacity = (int64_t)device_cus() * (wpc > 0 ? wpc : resident_waves_per_cu);
         int64_t nseg_target = force_nseg > 0 ? force_nseg : capacity / p.C;      // floor: one round
         if (nseg_target < 1) nseg_target = 1;
@@ -992,7 +990,7 @@ static void plan_segments(SosParams &p, int64_t plan_warm, int TILE, int residen
             // costing every stream an extra, mostly discarded tile (+4 % at 64 x 2.88 M with 4096-sample tiles).
             int64_t seg_tiles = ceil_div(ceil_div(p.T - warm, nseg_target) + warm, TILE);
             if (force_nseg <= 0) {
-                const int64_t min_tiles = ceil_div(env_int("TFX_SOS_MIN_SEG_OVER_WARM", 8) * warm, TILE);
+                const int64_t min_tiles = ceil_div(env_i64("TFX_SOS_MIN_SEG_OVER_WARM", 8) * warm, TILE);
                 if (seg_tiles < min_tiles) seg_tiles = min_tiles;
             }
             if (seg_tiles < 1) seg_tiles = 1;
@@ -1167,7 +1165,7 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in,
     // float32 arithmetic: LC = 32 + register prefetch (4 waves per SIMD); float64: LC = 64 -- the kernel is bound by VALU
     // issue (1440 instructions per 2048-sample tile, ~100 % busy at 3 waves per SIMD), and 64 samples per lane halve the
     // scan's share per sample (0.352 vs 0.38-0.42 ms at cfg 2 on the same box)
-    int variant = (rare || sum_bands) ? 1 : env_int("TFX_SOS_VARIANT", -1);
+    int variant = (rare || sum_bands) ? 1 : (int)env_i64("TFX_SOS_VARIANT", -1);
     if (variant < 0) variant = (prec == TFX_PREC_F32) ? 2 : 4;
     {
         const int xs_ = x_dtype == TFX_F32 ? 4 : 8, ys_ = y_dtype == TFX_F32 ? 4 : 8;
@@ -1185,8 +1183,8 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in,
     p.x = x; p.y = y; p.taps = y_sections;
     p.sx_in = sx_in; p.sy_in = sy_in; p.sx_out = sx_out; p.sy_out = sy_out;
     p.C = C; p.C_in = C_in; p.T = T; p.K = (int)K; p.x_pitch = T;
-    p.nt = env_int("TFX_SOS_NT", 1);
-    p.fair = env_int("TFX_SOS_FAIR", 15);
+    p.nt = (int)env_i64("TFX_SOS_NT", 1);
+    p.fair = (int)env_i64("TFX_SOS_FAIR", 15);
     p.nsum = sum_bands ? (int)NB : 0;
     p.ep_gain = ep->gain; p.ep_scale = ep->scale; p.ep_clamp = ep->clamp; p.ep_stat = ep->stat_mode;
     p.ep_partial = nullptr; p.ep_host = ep;
@@ -1208,7 +1206,7 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in,
     } else {
         // the shipping float32-in / float32-out geometry (LC = 64, aligned rows, no section taps) runs the unit-b0 form when the
         // cascade has one (TFX_SOS_UNIT_B0=0: plain form)
-        if (LC == 64 && variant == 4 && vec && !p.taps && !sum_bands && x_dtype == TFX_F32 && y_dtype == TFX_F32 && env_int("TFX_SOS_UNIT_B0", 1) != 0) {
+        if (LC == 64 && variant == 4 && vec && !p.taps && !sum_bands && x_dtype == TFX_F32 && y_dtype == TFX_F32 && env_i64("TFX_SOS_UNIT_B0", 1) != 0) {
             if (pl->unit_ok < 0) {
                 bool ok = true;
                 for (int b = 0; b < pl->NB && ok; ++b)
