@@ -5,6 +5,7 @@ import os
 import re
 import subprocess
 
+import numpy as np
 import pytest
 
 from tests.conftest import ROOT
@@ -239,3 +240,57 @@ def test_tuning_knobs_are_read_once_per_process_and_reloadable():
     assert a == 1 << 20 and b == 1 << 20          # the second lookup comes from the table, not from the environment
     assert c == 1 << 18                           # ... until the host asks for a reload
     assert d0 == 1 << 18 and d1 == 1 << 18        # the dynamic switch itself is read at reload; then every lookup is fresh
+
+
+def _plan_info(lib, sos):
+    a = np.ascontiguousarray(sos, dtype=np.float64)
+    prec, warm, bound = ctypes.c_int(), ctypes.c_int64(), ctypes.c_double()
+    assert lib.tfx_sos_plan_info(a.ctypes.data, a.shape[0], ctypes.byref(prec), ctypes.byref(warm), ctypes.byref(bound)) == 0
+    return prec.value, warm.value, bound.value
+
+
+def _fused_warmup(lib, sos):
+    a = np.ascontiguousarray(sos, dtype=np.float64)
+    return lib.tfx_sos_fft_conv_warmup(a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), a.shape[0])
+
+
+def test_nan_coefficient_does_not_share_a_cache_entry_with_the_valid_cascade():
+    """The host caches key on the coefficients' bytes: a cascade queried after its NaN twin (same coefficients but one
+    NaN) keeps its own answers, and the NaN twin gets its own, whichever of the two comes first."""
+    from torchfx_amd import _lib
+    lib = _lib.load()
+    good = np.array([[0.2, 0.4, 0.2, 1, -0.5, 0.2]])
+    nan = good.copy()
+    nan[0, 4] = np.nan
+    assert lib.tfx_clear_caches() == 0
+    alone = _plan_info(lib, good)
+    assert alone[0] == 1 and alone[1] > 0 and np.isfinite(alone[2])      # TFX_PREC_F32, decays, finite bound
+    assert lib.tfx_clear_caches() == 0
+    assert _plan_info(lib, nan)[1] == -1
+    assert _plan_info(lib, good) == alone
+
+    good = np.array([[0.3, 0.1, 0.3, 1, -0.6, 0.25]])
+    nan = good.copy()
+    nan[0, 4] = np.nan
+    assert lib.tfx_clear_caches() == 0
+    w = _fused_warmup(lib, good)
+    assert w > 0
+    assert _fused_warmup(lib, nan) == -1
+    assert lib.tfx_clear_caches() == 0
+    assert _fused_warmup(lib, nan) == -1
+    assert _fused_warmup(lib, good) == w
+
+
+def test_plan_info_is_the_same_when_more_cascades_than_the_cache_holds_come_in_another_order():
+    """300 distinct cascades (the SOS plan cache holds 256) queried forwards, then backwards: evicted plans are rebuilt with
+    the same answers."""
+    from torchfx_amd import _lib
+    lib = _lib.load()
+    g = np.random.default_rng(7)
+    cascades = []
+    for _ in range(300):
+        r, th = g.uniform(0.3, 0.95), g.uniform(0.05, 3.0)
+        cascades.append(np.array([[*g.uniform(-1, 1, 3), 1.0, -2 * r * np.cos(th), r * r]]))
+    first = [_plan_info(lib, s) for s in cascades]
+    second = [_plan_info(lib, s) for s in reversed(cascades)][::-1]
+    assert first == second

@@ -99,9 +99,6 @@ struct SosFuseHost {
     double *sections;       // optional DEVICE [K, C, T] float64: every section's output, or null
 };
 
-// fir.hip: device copy of a host tap vector, cached by content and device (uploaded, blocking, the first time a filter is seen)
-const void *cached_taps(const void *host, size_t bytes, size_t padded);
-
 // Every device-side cache (plans, taps, spectra, scratch, internal streams, occupancy answers) is
 // keyed by the ordinal of the device that is current at the call: one process may drive several GPUs
 // (the Python layer wraps each op in torch.cuda.device(x.device)).

@@ -13,6 +13,7 @@
 //   Z = rfft(fr) ;  Z *= conj(rfft(kf_pad)) / N ;  o = irfft(Z) ;  y[c, f*S + i] = o[i], i < S
 #include "common.h"
 #include "epilogue.h"
+#include "plan_cache.h"
 #include "../../include/torchfx_hip.h"
 
 #include <rocfft/rocfft.h>
@@ -124,25 +125,12 @@ struct FftPlan {
     rocfft_plan fwd = nullptr, inv = nullptr;
     size_t work_bytes = 0;
 };
-struct SpecKey {
-    int dev, dtype;
-    int64_t N;
-    std::vector<char> taps;
-    bool operator<(const SpecKey &o) const
-    {
-        if (dev != o.dev) return dev < o.dev;
-        if (dtype != o.dtype) return dtype < o.dtype;
-        if (N != o.N) return N < o.N;
-        return taps < o.taps;
-    }
-};
 
 static std::mutex g_fft_mu;
 static bool g_rocfft_up = false;
 static std::map<FftKey, FftPlan> g_fft_plans;
-static std::map<SpecKey, void *> g_specs;
-static const SpecKey *g_spec_last_key[TFX_MAX_DEVICES] = {};      // per device: the entry used last (std::map nodes are stable)
-static void *g_spec_last[TFX_MAX_DEVICES] = {};
+static PlanCache<DeviceBuffer, 2> g_specs(64);                   // tail: dtype, N
+static PlanCache<int64_t, 1> g_warmups(256);                     // fused_warmup; tail: bits
 
 static FftPlan &get_fft_plan(int dtype, int64_t N, int64_t batch)
 {
@@ -180,62 +168,33 @@ static void exec_fft(rocfft_plan plan, void *in, void *out, void *work, size_t w
 }
 
 template <typename T, typename T2>
-static void *get_spectrum(int dtype, const void *kernel_host, int64_t K, int64_t N, hipStream_t stream)
+static std::shared_ptr<DeviceBuffer> get_spectrum(int dtype, const void *kernel_host, int64_t K, int64_t N, hipStream_t stream)
 {
-    // steady state: the spectrum used last on this device, recognised by one memcmp (no key, no allocation per call)
-    const SpecKey **last_key = g_spec_last_key;
-    void **last_spec = g_spec_last;
-    const int dev_ = current_device();
-    if (const SpecKey *lk_ = last_key[dev_]) {
-        if (lk_->dtype == dtype && lk_->N == N && lk_->taps.size() == (size_t)K * sizeof(T) &&
-            memcmp(lk_->taps.data(), kernel_host, lk_->taps.size()) == 0)
-            return last_spec[dev_];
-    }
-    SpecKey key{dev_, dtype, N, std::vector<char>((const char *)kernel_host, (const char *)kernel_host + K * sizeof(T))};
-    auto it = g_specs.find(key);
-    if (it != g_specs.end()) {
-        last_key[dev_] = &it->first;
-        last_spec[dev_] = it->second;
-        return it->second;
-    }
-    if (g_specs.size() > 64) {
-        for (auto &kv : g_specs) (void)hipFree(kv.second);
-        g_specs.clear();
-    }
-    for (int d2 = 0; d2 < TFX_MAX_DEVICES; ++d2) { last_key[d2] = nullptr; last_spec[d2] = nullptr; }   // nodes may go / move
-    // one-time per (filter, N): pad taps, forward transform, conjugate + scale.  Blocking.
-    const int64_t bins = N / 2 + 1;
-    std::vector<T> hp((size_t)N, (T)0);
-    memcpy(hp.data(), kernel_host, (size_t)K * sizeof(T));
-    T *dpad = nullptr;
-    T2 *dspec = nullptr;
-    TFX_HIP(hipMalloc((void **)&dpad, (size_t)N * sizeof(T)));
-    TFX_HIP(hipMalloc((void **)&dspec, (size_t)bins * sizeof(T2)));
-    TFX_HIP(hipMemcpy(dpad, hp.data(), (size_t)N * sizeof(T), hipMemcpyHostToDevice));
-    FftPlan &p1 = get_fft_plan(dtype, N, 1);
-    void *work = nullptr;
-    if (p1.work_bytes) TFX_HIP(hipMalloc(&work, p1.work_bytes));
-    exec_fft(p1.fwd, dpad, dspec, work, p1.work_bytes, stream);
-    TFX_HIP(hipStreamSynchronize(stream));
-    std::vector<T2> hs((size_t)bins);
-    TFX_HIP(hipMemcpy(hs.data(), dspec, (size_t)bins * sizeof(T2), hipMemcpyDeviceToHost));
-    const T sc = (T)1 / (T)N;
-    for (auto &v : hs) { v.x = v.x * sc; v.y = -v.y * sc; }        // conj(.)/N  (_fftconv.py:131)
-    TFX_HIP(hipMemcpy(dspec, hs.data(), (size_t)bins * sizeof(T2), hipMemcpyHostToDevice));
-    (void)hipFree(dpad);
-    if (work) (void)hipFree(work);
-    auto ins = g_specs.emplace(std::move(key), (void *)dspec).first;
-    last_key[dev_] = &ins->first;
-    last_spec[dev_] = dspec;
-    return dspec;
+    return g_specs.get(kernel_host, (size_t)K * sizeof(T), {dtype, N}, stream, [&] {
+        // one-time per (filter, N): pad taps, forward transform, conjugate + scale.  Blocking.
+        const int64_t bins = N / 2 + 1;
+        std::vector<T> hp((size_t)N, (T)0);
+        memcpy(hp.data(), kernel_host, (size_t)K * sizeof(T));
+        const DeviceBuffer dpad(hp);
+        auto dspec = std::make_shared<DeviceBuffer>(nullptr, (size_t)bins * sizeof(T2));
+        FftPlan &p1 = get_fft_plan(dtype, N, 1);
+        const DeviceBuffer work(nullptr, p1.work_bytes);
+        exec_fft(p1.fwd, dpad.p, dspec->p, work.p, p1.work_bytes, stream);
+        TFX_HIP(hipStreamSynchronize(stream));
+        std::vector<T2> hs((size_t)bins);
+        TFX_HIP(hipMemcpy(hs.data(), dspec->p, (size_t)bins * sizeof(T2), hipMemcpyDeviceToHost));
+        const T sc = (T)1 / (T)N;
+        for (auto &v : hs) { v.x = v.x * sc; v.y = -v.y * sc; }        // conj(.)/N  (_fftconv.py:131)
+        TFX_HIP(hipMemcpy(dspec->p, hs.data(), (size_t)bins * sizeof(T2), hipMemcpyHostToDevice));
+        return dspec;
+    });
 }
 
 void fftconv_clear()
 {
-    std::lock_guard<std::mutex> lk(g_fft_mu);
-    for (auto &kv : g_specs) (void)hipFree(kv.second);
     g_specs.clear();
-    for (int d = 0; d < TFX_MAX_DEVICES; ++d) { g_spec_last_key[d] = nullptr; g_spec_last[d] = nullptr; }
+    g_warmups.clear();
+    std::lock_guard<std::mutex> lk(g_fft_mu);
     for (auto &kv : g_fft_plans) {
         if (kv.second.fwd) rocfft_plan_destroy(kv.second.fwd);
         if (kv.second.inv) rocfft_plan_destroy(kv.second.inv);
@@ -271,7 +230,8 @@ static void fft_conv_typed(const T *x, T *y, int dtype, int64_t C, int64_t Tn, c
     const int64_t bins = N / 2 + 1;
 
     std::lock_guard<std::mutex> lk(g_fft_mu);
-    const T2 *H = (const T2 *)get_spectrum<T, T2>(dtype, kernel_host, K, N, stream);
+    const std::shared_ptr<DeviceBuffer> spec = get_spectrum<T, T2>(dtype, kernel_host, K, N, stream);
+    const T2 *H = (const T2 *)spec->p;
 
     // channel slab so that frames + spectra stay within the workspace budget
     const int64_t ws_mb = env_i64("TFX_FFT_WS_MB", 2048);
@@ -376,16 +336,9 @@ void fft_conv_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, c
 // long-double matrix products.
 static int64_t fused_warmup(const double *sos_host, int64_t Ksos)
 {
-    static std::mutex mu;
-    static std::map<std::vector<double>, int64_t> memo;
     const int bits = (int)std::max<int64_t>(20, std::min<int64_t>(60, env_i64("TFX_OLS_SOS_HALO_BITS", 40)));
-    std::vector<double> key(sos_host, sos_host + 6 * Ksos);
-    key.push_back((double)bits);
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = memo.find(key);
-    if (it != memo.end()) return it->second;
-    if (memo.size() > 256) memo.clear();
-    return memo[key] = sos_warmup_bits(sos_host, Ksos, bits);
+    return *g_warmups.get(sos_host, (size_t)(6 * Ksos) * sizeof(double), {bits}, nullptr,
+                          [&] { return std::make_shared<int64_t>(sos_warmup_bits(sos_host, Ksos, bits)); });
 }
 
 int64_t sos_fft_conv_warmup(const double *sos_host, int64_t Ksos) { return (Ksos >= 1 && Ksos <= 8) ? fused_warmup(sos_host, Ksos) : -1; }

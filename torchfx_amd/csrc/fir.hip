@@ -19,65 +19,27 @@
 // float64 signals (the reference computes conv1d in the input dtype) use a plain LDS-tiled
 // vector kernel: rare path, correctness first.
 #include "common.h"
+#include "plan_cache.h"
 #include "../../include/torchfx_hip.h"
 
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <vector>
 
 namespace tfx {
 
-// device copies of tap vectors, keyed by content: uploaded (blocking) the first time a filter
-// is seen, then reused -- no host sync on the steady-state path.
-static std::mutex g_taps_mu;
-static std::map<std::vector<char>, void *> g_taps;
-static const std::vector<char> *g_taps_last_key[TFX_MAX_DEVICES] = {};   // per device: the entry used last
-static const void *g_taps_last[TFX_MAX_DEVICES] = {};
-const void *cached_taps(const void *host, size_t bytes, size_t padded)
+// device copies of tap vectors, keyed by content and padded size: uploaded (blocking) the first time a filter is seen, then
+// reused -- no host sync on the steady-state path
+static PlanCache<DeviceBuffer, 1> g_taps(128);
+std::shared_ptr<DeviceBuffer> cached_taps(const void *host, size_t bytes, size_t padded)
 {
-    const int dev = current_device();
-    std::lock_guard<std::mutex> lk(g_taps_mu);
-    // steady state (the same filter call after call): one memcmp, no key construction -- a long tap vector would
-    // otherwise cost a heap allocation of its size per call
-    if (const std::vector<char> *lk_ = g_taps_last_key[dev]) {
-        if (lk_->size() == bytes + 2 && memcmp(lk_->data(), host, bytes) == 0 && (*lk_)[bytes] == (char)(padded & 0xff))
-            return g_taps_last[dev];
-    }
-    std::vector<char> key((const char *)host, (const char *)host + bytes);
-    key.push_back((char)(padded & 0xff));
-    key.push_back((char)dev);
-    auto it = g_taps.find(key);
-    if (it != g_taps.end()) {
-        g_taps_last_key[dev] = &it->first;
-        g_taps_last[dev] = it->second;
-        return it->second;
-    }
-    if (g_taps.size() > 128) {
-        (void)hipDeviceSynchronize();
-        for (auto &kv : g_taps) (void)hipFree(kv.second);
-        g_taps.clear();
-        for (int d2 = 0; d2 < TFX_MAX_DEVICES; ++d2) { g_taps_last_key[d2] = nullptr; g_taps_last[d2] = nullptr; }
-    }
-    std::vector<char> h(padded, 0);
-    memcpy(h.data(), host, bytes);
-    void *d = nullptr;
-    TFX_HIP(hipMalloc(&d, padded));
-    TFX_HIP(hipMemcpy(d, h.data(), padded, hipMemcpyHostToDevice));
-    auto ins = g_taps.emplace(std::move(key), d).first;
-    g_taps_last_key[dev] = &ins->first;                 // std::map nodes are stable
-    g_taps_last[dev] = d;
-    return d;
+    return g_taps.get(host, bytes, {(int64_t)padded}, nullptr, [&] {
+        std::vector<char> h(padded, 0);
+        memcpy(h.data(), host, bytes);
+        return std::make_shared<DeviceBuffer>(h);
+    });
 }
-void fir_clear()
-{
-    std::lock_guard<std::mutex> lk(g_taps_mu);
-    (void)hipDeviceSynchronize();
-    for (auto &kv : g_taps) (void)hipFree(kv.second);
-    g_taps.clear();
-    for (int d = 0; d < TFX_MAX_DEVICES; ++d) { g_taps_last_key[d] = nullptr; g_taps_last[d] = nullptr; }
-}
+void fir_clear() { g_taps.clear(); }
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
@@ -323,7 +285,8 @@ void fir_direct_forward(const void *x, void *y, int dtype, int64_t C, int64_t T,
     TFX_CHECK(C > 0 && T > 0, "fir_direct_forward: negative size");
     const size_t esz = dtype == TFX_F32 ? 4 : 8;
     const int64_t Kpad = ceil_div(K, FIR_KC_MAX) * FIR_KC_MAX;
-    const void *kdev = cached_taps(kernel_host, (size_t)K * esz, (size_t)Kpad * esz);
+    const std::shared_ptr<DeviceBuffer> taps = cached_taps(kernel_host, (size_t)K * esz, (size_t)Kpad * esz);   // held until launched
+    const void *kdev = taps->p;
     // rows much shorter than one 16384-sample MFMA tile (streaming chunks): the plain LDS-tiled kernel
     // has 1024-sample tiles and finishes in a few microseconds instead of a full tile's ~60
     // ... and so does any job whose 1024-sample tiles are all resident at once (8 workgroups per CU): one round of

@@ -26,14 +26,13 @@
 #include "fftpk.h"
 #include "fftpk16k.h"
 #include "ldsfft.h"
+#include "plan_cache.h"
 #include "../../include/torchfx_hip.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <memory>
-#include <mutex>
 #include <vector>
 
 namespace tfx {
@@ -588,61 +587,20 @@ ols_lds16k_kernel(const float *__restrict__ x, float *__restrict__ y, const v4f 
 }
 
 // ---- host: per-filter tables ---------------------------------------------------------------------
-// A plan's device buffer (spectrum | tables, one allocation) is OWNED by the plan objects that point into it: get_plan hands
-// out a copy, so a caller keeps the buffer alive until its launches are enqueued, whatever another host thread evicts in
-// the meantime; the last owner's hipFree synchronises the device, i.e. runs behind those launches (round 4 returned a
-// plain copy and freed every spectrum when the 66th filter arrived: a launch on a freed buffer).
+// A plan's device buffer holds spectrum | tables in one allocation; the plan is shared-owned (PlanCache), so a caller keeps
+// the buffer alive until its launches are enqueued (round 4 returned a plain copy and freed every spectrum when the 66th
+// filter arrived: a launch on a freed buffer).
 struct Plan {
-    void *Hs = nullptr, *tw256 = nullptr, *t4lo = nullptr, *w8k = nullptr;
-    std::shared_ptr<void> owner;
+    DeviceBuffer buf;                                   // the spectrum, then the tables
+    void *tw256 = nullptr, *t4lo = nullptr, *w8k = nullptr;     // into buf
+    template <typename T> explicit Plan(const std::vector<T> &h) : buf(h) {}
 };
-static std::mutex g_mu;
-static std::map<std::vector<char>, Plan> g_plans;
-static std::map<std::vector<char>, uint64_t> g_used;                     // last use of a key (eviction: least recently used first)
-static uint64_t g_tick = 0;
-static const std::vector<char> *g_last_key[TFX_MAX_DEVICES] = {};       // std::map nodes are stable
-static const Plan *g_last[TFX_MAX_DEVICES] = {};
-constexpr size_t LDS_PLAN_CAP = 64;
-
-template <typename R> static void *upload(const std::vector<cx<R>> &h)
-{
-    void *d = nullptr;
-    TFX_HIP(hipMalloc(&d, h.size() * sizeof(cx<R>)));
-    TFX_HIP(hipMemcpy(d, h.data(), h.size() * sizeof(cx<R>), hipMemcpyHostToDevice));
-    return d;
-}
+static PlanCache<Plan, 3> g_plans(64, "overlap-save");  // tail: sizeof(R), kind, lead
 
 // kind: 0 = 4096 points, 1 = 8192 (radix 2 around 4096), 2 = 16 384 in a 1024-thread workgroup, 3 = 16 384 as radix 4 around 4096
-template <typename R> static Plan get_plan(const R *kf, int64_t K, int64_t lead, int N, int kind, hipStream_t stream)
+template <typename R> static std::shared_ptr<Plan> get_plan(const R *kf, int64_t K, int64_t lead, int N, int kind, hipStream_t stream)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
-    const int dev = current_device();
-    const size_t nb = (size_t)K * sizeof(R);
-    const char tail[3] = {(char)(sizeof(R) + 16 * kind), (char)lead, (char)dev};
-    if (const std::vector<char> *lk_ = g_last_key[dev]) {       // steady state: one memcmp, no key construction
-        if (lk_->size() == nb + 3 && memcmp(lk_->data(), kf, nb) == 0 && memcmp(lk_->data() + nb, tail, 3) == 0) {
-            g_used[*lk_] = ++g_tick;
-            return *g_last[dev];
-        }
-    }
-    std::vector<char> key((const char *)kf, (const char *)kf + nb);
-    key.insert(key.end(), tail, tail + 3);
-    auto it = g_plans.find(key);
-    if (it == g_plans.end()) {
-        // a new filter costs a device allocation and a blocking upload: not inside a stream capture
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        TFX_CHECK(!(hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone),
-                  "overlap-save: first use of this filter (%lld taps) inside a stream capture -- run it once before capturing "
-                  "(its spectrum is uploaded with a blocking copy)", (long long)K);
-        while (g_plans.size() >= LDS_PLAN_CAP) {              // least recently used entry goes; its buffer lives on with whoever still holds it
-            auto victim = g_used.begin();
-            for (auto u = g_used.begin(); u != g_used.end(); ++u)
-                if (u->second < victim->second) victim = u;
-            for (int d = 0; d < TFX_MAX_DEVICES; ++d)
-                if (g_last_key[d] && *g_last_key[d] == victim->first) { g_last_key[d] = nullptr; g_last[d] = nullptr; }
-            g_plans.erase(victim->first);
-            g_used.erase(victim);
-        }
+    return g_plans.get(kf, (size_t)K * sizeof(R), {(int64_t)sizeof(R), kind, lead}, stream, [&] {
         // conj(FFT(taps behind `lead` zeros, zero padded to N)) / N in float64  (_fftconv.py:123-124,131 + irfft scaling)
         std::vector<double> re((size_t)N, 0.0), im((size_t)N, 0.0);
         for (int64_t i = 0; i < K; ++i) re[(size_t)(lead + i)] = (double)kf[i];
@@ -653,7 +611,6 @@ template <typename R> static Plan get_plan(const R *kf, int64_t K, int64_t lead,
             cx<R> w; w.x = (R)cos(a); w.y = (R)sin(a);
             return w;
         };
-        Plan p;
         if (kind == 2) {
             // spectral ownership of fftpk16k.h: thread r, register s <-> bin (r & 255) + 256 (4 (r >> 8) + s / 4) + 4096 (s % 4);
             // registers (2 m, 2 m + 1) of a thread sit next to each other: one 16-byte load
@@ -671,10 +628,6 @@ template <typename R> static Plan get_plan(const R *kf, int64_t K, int64_t lead,
                     tab[512 + 16 * d + b] = W(d * b, 16384); tab[576 + 16 * d + b] = W(d * b, 1024); tab[640 + 16 * d + b] = W(d * b, 64);
                 }
             hs.insert(hs.end(), tab.begin(), tab.end());
-            p.Hs = upload<R>(hs);                             // one allocation, one copy: spectrum | tables
-            p.owner = std::shared_ptr<void>(p.Hs, [](void *q) { (void)hipFree(q); });
-            p.tw256 = (char *)p.Hs + (size_t)N * sizeof(cx<R>);
-            p.t4lo = nullptr;
         } else {
             std::vector<cx<R>> t256(256), t4(256);
             if (kind == 3) {
@@ -708,30 +661,20 @@ template <typename R> static Plan get_plan(const R *kf, int64_t K, int64_t lead,
             if (kind == 3)
                 for (int r = 1; r < 4; ++r)
                     for (int i = 0; i < 512; ++i) hs.push_back(W(r * i, 16384));      // [r - 1][j]: W16384^(r j) of thread j
-            p.Hs = upload<R>(hs);
-            p.owner = std::shared_ptr<void>(p.Hs, [](void *q) { (void)hipFree(q); });
-            p.tw256 = (char *)p.Hs + (size_t)N * sizeof(cx<R>);
-            p.t4lo = (char *)p.tw256 + 256 * sizeof(cx<R>);
-            p.w8k = (char *)p.t4lo + 256 * sizeof(cx<R>);
         }
-        it = g_plans.emplace(std::move(key), p).first;
-    }
-    g_used[it->first] = ++g_tick;
-    g_last_key[dev] = &it->first;
-    g_last[dev] = &it->second;
-    return it->second;
+        auto p = std::make_shared<Plan>(hs);                  // one allocation, one copy: spectrum | tables
+        p->tw256 = (char *)p->buf.p + (size_t)N * sizeof(cx<R>);
+        if (kind != 2) {
+            p->t4lo = (char *)p->tw256 + 256 * sizeof(cx<R>);
+            p->w8k = (char *)p->t4lo + 256 * sizeof(cx<R>);
+        }
+        return p;
+    });
 }
 
 }  // namespace ldsfft
 
-void olslds_clear()
-{
-    using namespace ldsfft;
-    std::lock_guard<std::mutex> lk(g_mu);
-    g_plans.clear();                        // the owners free their buffers (hipFree waits for the device)
-    g_used.clear();
-    for (int d = 0; d < TFX_MAX_DEVICES; ++d) { g_last_key[d] = nullptr; g_last[d] = nullptr; }
-}
+void olslds_clear() { ldsfft::g_plans.clear(); }
 
 // taps this path takes: at least half of every block must be valid output -- 4096 points for K < 640 (float32; measured
 // equal to the 8192-point block at 512 taps, faster below) and K < 700 (float64), 8192 points above that up to 4096 taps
@@ -804,7 +747,7 @@ static void olslds_typed(const R *x, R *y, int64_t C, int64_t Tn, const R *kf_ho
     const int64_t r4 = env_i64("TFX_OLS_LDS16K_R4", 1);
     const bool use_r4 = N == LDS16K && sizeof(R) == 4 && (r4 >= 2 || (r4 == 1 && L >= 65536 && env_i64("TFX_OLS_LDS16K", 1) < 2));
     const int kind = N == LDS_N ? 0 : N == LDS8K ? 1 : use_r4 ? 3 : 2;
-    const Plan plan = get_plan<R>(kf_host, K, lead, (int)N, kind, stream);      // holds its buffer until this function has enqueued its launch
+    const std::shared_ptr<Plan> plan = get_plan<R>(kf_host, K, lead, (int)N, kind, stream);      // holds its buffer until this function has enqueued its launch
     const int64_t npairs = ceil_div(g.nframes, 2);
     if (g.ep_stat >= 0) g.ep_partial = (double *)scratch("olslds_ep_partial", (size_t)g.nframes * sizeof(double), stream);
     const int dev = current_device();
@@ -825,8 +768,8 @@ static void olslds_typed(const R *x, R *y, int64_t C, int64_t Tn, const R *kf_ho
     if constexpr (sizeof(R) == 4) {
         if (kind == 3) {
             launch(ols_lds16k_w8_kernel, ready[3][dev], "ols_lds16k_w8_kernel", lds16k_w8_bytes(), per_xcd * 8, 512,
-                   (const float *)x, (float *)y, (const v4f *)plan.Hs, (const cx<float> *)plan.tw256, (const cx<float> *)plan.t4lo,
-                   (const v2f *)plan.w8k, g, npairs, per_xcd);
+                   (const float *)x, (float *)y, (const v4f *)plan->buf.p, (const cx<float> *)plan->tw256, (const cx<float> *)plan->t4lo,
+                   (const v2f *)plan->w8k, g, npairs, per_xcd);
             done = true;
         } else if (kind == 2) {
             static int cus_tab[TFX_MAX_DEVICES] = {};
@@ -837,16 +780,16 @@ static void olslds_typed(const R *x, R *y, int64_t C, int64_t Tn, const R *kf_ho
             }
             const int64_t grid = std::max<int64_t>(8, std::min<int64_t>(env_i64("TFX_OLS_LDS16K_GRID", cus_tab[dev]) / 8 * 8, per_xcd * 8));
             launch(ols_lds16k_kernel, ready[2][dev], "ols_lds16k_kernel", lds16k_bytes(), grid, 1024,
-                   (const float *)x, (float *)y, (const v4f *)plan.Hs, (const v2f *)plan.tw256, g, npairs, per_xcd);
+                   (const float *)x, (float *)y, (const v4f *)plan->buf.p, (const v2f *)plan->tw256, g, npairs, per_xcd);
             done = true;
         }
     }
     if (!done && kind == 1)
         launch(ols_lds8192_kernel<R>, ready[1][dev], "ols_lds8192_kernel", lds_bytes<R>(), per_xcd * 8, 256,
-               x, y, (const cx<R> *)plan.Hs, (const cx<R> *)plan.tw256, (const cx<R> *)plan.t4lo, (const cx<R> *)plan.w8k, g, npairs, per_xcd);
+               x, y, (const cx<R> *)plan->buf.p, (const cx<R> *)plan->tw256, (const cx<R> *)plan->t4lo, (const cx<R> *)plan->w8k, g, npairs, per_xcd);
     else if (!done)
         launch(ols_lds4096_kernel<R>, ready[0][dev], "ols_lds4096_kernel", lds_bytes<R>(), per_xcd * 8, 256,
-               x, y, (const cx<R> *)plan.Hs, (const cx<R> *)plan.tw256, (const cx<R> *)plan.t4lo, g, npairs, per_xcd);
+               x, y, (const cx<R> *)plan->buf.p, (const cx<R> *)plan->tw256, (const cx<R> *)plan->t4lo, g, npairs, per_xcd);
     if (g.ep_stat >= 0)
         stat_finish(g.ep_partial, ep->per_row ? C : 1, ep->per_row ? g.F : g.nframes, g.ep_stat, ep->stat_out, stream);
 }

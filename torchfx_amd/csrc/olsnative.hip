@@ -32,6 +32,7 @@
 #include "epilogue.h"
 #include "fftpk.h"
 #include "ols_kernels.h"
+#include "plan_cache.h"
 #include "../../include/torchfx_hip.h"
 
 #include <algorithm>
@@ -39,7 +40,7 @@
 #include <cmath>
 #include <cstring>
 #include <future>
-#include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -51,32 +52,23 @@ namespace tfx {
 // ---------------------------------------------------------------------------------------------
 // Host: plan (tables + permuted spectrum) cache and orchestration
 // ---------------------------------------------------------------------------------------------
+// A plan owns its device buffers; olsnative_forward holds its plan until its launches are enqueued, whatever another host
+// thread evicts meanwhile (round 4 handed out raw pointers and freed every plan when the 18th filter arrived).
 struct NativePlan {
     int64_t N = 0, K = 0;
     int N2 = 0;
     cpx *Hp = nullptr, *tw256 = nullptr, *twr = nullptr, *tlo = nullptr, *thi = nullptr, *tu = nullptr, *t4lo = nullptr, *t4hi = nullptr, *w8k = nullptr;
-    float *taps_dev = nullptr;      // device copy of the taps while the spectrum kernels may still read it (N = 2^20)
-    cpx *tables = nullptr;          // the one allocation tw256 ... t4hi point into
+    std::unique_ptr<DeviceBuffer> spectrum;   // Hp
+    std::unique_ptr<DeviceBuffer> tables;     // the one allocation tw256 ... w8k point into
+    std::unique_ptr<DeviceBuffer> taps_dev;   // device copy of the taps while the spectrum kernels may still read it (N = 2^20)
     hipEvent_t ready = nullptr;     // recorded behind the spectrum kernels: other streams wait for it before they read Hp
     hipStream_t ready_stream = nullptr;
-    NativePlan() = default;
-    NativePlan(const NativePlan &) = delete;
-    NativePlan &operator=(const NativePlan &) = delete;
-    ~NativePlan()                   // the last owner frees: hipFree waits for the device, i.e. runs behind every launch that used the plan
-    {
-        for (cpx *q : {Hp, tables}) if (q) (void)hipFree(q);
-        if (taps_dev) (void)hipFree(taps_dev);
-        if (ready) (void)hipEventDestroy(ready);
-    }
+    ~NativePlan() { if (ready) (void)hipEventDestroy(ready); }
 };
-// Plans are shared_ptr-owned: olsnative_forward keeps its plan alive until its launches are enqueued, whatever another host
-// thread evicts meanwhile (round 4 handed out raw pointers and freed every plan when the 18th filter arrived).
 typedef std::shared_ptr<NativePlan> NativePlanPtr;
-static std::mutex g_np_mu;
-static std::map<std::vector<char>, NativePlanPtr> g_nplans;
+static PlanCache<NativePlan, 2> g_nplans(16, "overlap-save");      // tail: N, lead
+static std::mutex g_np_mu;                                         // guards g_free_mb
 static int64_t g_free_mb[TFX_MAX_DEVICES] = {};                  // per device: free memory (MB) seen at first use, 0 = not asked yet
-static NativePlanPtr g_last_plan[TFX_MAX_DEVICES];             // per device: the plan used last and its key
-static std::vector<char> g_last_key[TFX_MAX_DEVICES];
 
 // Forward FFT in float64 of a real sequence of L samples zero-padded to n = 2^m points (the spectrum of the taps, once per
 // filter; it sits in the latency of the first call with a new filter).  One decimation-in-frequency step of radix R = 16
@@ -168,13 +160,6 @@ static void host_fft(std::vector<double> &re, std::vector<double> &im)
 
 void host_fft_f64(std::vector<double> &re, std::vector<double> &im) { host_fft(re, im); }     // olslds.hip's spectra
 
-static cpx *upload_cpx(const std::vector<cpx> &h)
-{
-    cpx *d = nullptr;
-    TFX_HIP(hipMalloc((void **)&d, h.size() * sizeof(cpx)));
-    TFX_HIP(hipMemcpy(d, h.data(), h.size() * sizeof(cpx), hipMemcpyHostToDevice));
-    return d;
-}
 static std::vector<cpx> twiddles(int64_t n, int64_t count, int64_t step)   // W_n^(step*i), i < count
 {
     std::vector<cpx> t((size_t)count);
@@ -300,37 +285,9 @@ struct HostTrace {
     }
 };
 
-static NativePlanPtr get_native_plan(const float *kf, int64_t K, int64_t N, int64_t lead, hipStream_t stream)
+// a new filter costs device allocations, blocking uploads (and, for N = 2^20, two launches on `stream`)
+static NativePlanPtr build_native_plan(const float *kf, int64_t K, int64_t N, int64_t lead, hipStream_t stream)
 {
-    // steady state (the same filter call after call, e.g. streaming chunks): one memcmp against the plan
-    // used last, no key construction
-    NativePlanPtr *last = g_last_plan;
-    std::vector<char> *last_key = g_last_key;
-    const int dev_ = current_device();
-    {
-        const std::vector<char> &lk = last_key[dev_];
-        const size_t nb = (size_t)K * sizeof(float);
-        if (last[dev_] && lk.size() == nb + 2 * sizeof(int64_t) + 1 && memcmp(lk.data(), kf, nb) == 0 &&
-            memcmp(lk.data() + nb, &N, sizeof(N)) == 0 && memcmp(lk.data() + nb + sizeof(N), &lead, sizeof(lead)) == 0)
-            return last[dev_];
-    }
-    std::vector<char> key((const char *)kf, (const char *)kf + K * sizeof(float));
-    key.insert(key.end(), (const char *)&N, (const char *)&N + sizeof(N));
-    key.insert(key.end(), (const char *)&lead, (const char *)&lead + sizeof(lead));
-    key.push_back((char)current_device());
-    auto it = g_nplans.find(key);
-    if (it != g_nplans.end()) { last[dev_] = it->second; last_key[dev_] = key; return it->second; }
-    {
-        // a new filter costs device allocations, blocking uploads (and, for N = 2^20, two launches): not inside a stream capture
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        TFX_CHECK(!(hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone),
-                  "overlap-save: first use of this filter (%lld taps) inside a stream capture -- run it once before capturing "
-                  "(its spectrum and tables are uploaded with blocking copies)", (long long)K);
-    }
-    if (g_nplans.size() > 16) {            // the map lets go; a plan lives on with whoever still holds it
-        for (int d = 0; d < TFX_MAX_DEVICES; ++d) last[d].reset();
-        g_nplans.clear();
-    }
     NativePlanPtr pl = std::make_shared<NativePlan>();
     pl->N = N; pl->K = K; pl->N2 = (int)(N / OLS_N1);
     HostTrace tr;
@@ -366,7 +323,8 @@ static NativePlanPtr get_native_plan(const float *kf, int64_t K, int64_t N, int6
             }
         }
         tr.mark("  spectrum: permute");
-        pl->Hp = upload_cpx(hp);
+        pl->spectrum = std::make_unique<DeviceBuffer>(hp);
+        pl->Hp = (cpx *)pl->spectrum->p;
         tr.mark("  spectrum: upload");
     }
     {
@@ -389,23 +347,22 @@ static NativePlanPtr get_native_plan(const float *kf, int64_t K, int64_t N, int6
             all.insert(all.end(), parts[i].begin(), parts[i].end());
             all.resize((all.size() + 31) & ~(size_t)31);          // 256-byte aligned sub-tables
         }
-        cpx *basep = upload_cpx(all);
-        for (int i = 0; i < 8; ++i) *slots[i] = basep + off[i];
-        pl->tables = basep;
+        pl->tables = std::make_unique<DeviceBuffer>(all);
+        for (int i = 0; i < 8; ++i) *slots[i] = (cpx *)pl->tables->p + off[i];
     }
     tr.mark("  twiddle tables");
     if (dev_spectrum) {
         // N = 2^20: the spectrum is computed by the pipeline's own kernels on the caller's stream (see ols_rowspec4096_kernel)
-        TFX_HIP(hipMalloc((void **)&pl->taps_dev, (size_t)K * sizeof(float)));
-        TFX_HIP(hipMemcpy(pl->taps_dev, kf, (size_t)K * sizeof(float), hipMemcpyHostToDevice));
-        TFX_HIP(hipMalloc((void **)&pl->Hp, (size_t)N * sizeof(cpx)));
+        pl->taps_dev = std::make_unique<DeviceBuffer>(kf, (size_t)K * sizeof(float));
+        pl->spectrum = std::make_unique<DeviceBuffer>(nullptr, (size_t)N * sizeof(cpx));
+        pl->Hp = (cpx *)pl->spectrum->p;
         ols_set_attributes(current_device());                 // the column pass needs more than 64 KB of dynamic LDS
         OlsGeom g{};
         g.Tn = K; g.Tout = K; g.F = 1; g.S = N; g.pad_left = lead; g.out_shift = 0; g.nframes = 1;
         g.hist = nullptr; g.H = 0; g.ep_gain = 1.0f; g.ep_scale = 0; g.ep_clamp = 0; g.ep_stat = -1; g.ep_partial = nullptr;
         g.N2 = N2; g.P2 = N2; g.nt = 0;
         hipLaunchKernelGGL(ols_col_fwd16_kernel<1>, dim3((unsigned)(N2 / OLS_CB)), dim3(512), OLS_SHM_COL, stream,
-                           (const float *)pl->taps_dev, pl->Hp, pl->tw256, g, (int64_t)0);
+                           (const float *)pl->taps_dev->p, pl->Hp, pl->tw256, g, (int64_t)0);
         TFX_HIP(hipGetLastError());
         if (N2 == 4096)
             hipLaunchKernelGGL(ols_rowspec4096_kernel, dim3(OLS_N1), dim3(256), (size_t)(4096 + 256 + 512) * sizeof(cpx), stream,
@@ -419,17 +376,15 @@ static NativePlanPtr get_native_plan(const float *kf, int64_t K, int64_t N, int6
         pl->ready_stream = stream;
         tr.mark("  spectrum: device (2 launches)");
     }
-    g_nplans[key] = pl;
-    last[dev_] = pl; last_key[dev_] = key;
     return pl;
 }
 
 void olsnative_clear()
 {
+    g_nplans.clear();
     {
         std::lock_guard<std::mutex> lk(g_np_mu);
-        g_nplans.clear();
-        for (int d = 0; d < TFX_MAX_DEVICES; ++d) { g_last_plan[d].reset(); g_free_mb[d] = 0; }
+        for (int d = 0; d < TFX_MAX_DEVICES; ++d) g_free_mb[d] = 0;
     }
     std::lock_guard<std::mutex> lk(g_warm_mu);          // a failed helper is not remembered beyond a clear
     for (int d = 0; d < TFX_MAX_DEVICES; ++d) g_warm[d] = std::shared_future<void>();
@@ -517,9 +472,9 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
                        const SosFuseHost *sosf)
 {
     HostTrace tr;
-    // g_np_mu guards the plan cache, the one-time function attributes and the creation of the internal streams (the three
-    // short sections below); the launches themselves are not serialised, so two host threads that drive two streams overlap
-    // (each stream has its own scratch slabs; the internal lanes are shared and ordered by the fork / join events)
+    // the plan cache, the one-time function attributes and the creation of the internal streams each take a lock of their own;
+    // the launches themselves are not serialised, so two host threads that drive two streams overlap (each stream has its own
+    // scratch slabs; the internal lanes are shared and ordered by the fork / join events)
     OlsGeom g;
     const int64_t L = Tn + pl + pr;
     g.Tn = Tn; g.Tout = L - K + 1; g.pad_left = pl; g.out_shift = 0;
@@ -552,8 +507,8 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
     NativePlanPtr plan;
     std::exception_ptr plan_err;
     try {
-        std::lock_guard<std::mutex> lk(g_np_mu);
-        plan = get_native_plan(kf_host, K, N, lead, stream);
+        plan = g_nplans.get(kf_host, (size_t)K * sizeof(float), {N, lead}, stream,
+                            [&] { return build_native_plan(kf_host, K, N, lead, stream); });
     } catch (...) { plan_err = std::current_exception(); }
     {
         std::shared_future<void> w;
@@ -607,8 +562,7 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
             // the cap follows the memory free when the device is first used (and again after tfx_clear_caches), not at every call:
             // a driver query per step costs tens of microseconds, is not allowed while a stream is capturing, and would make the
             // slab geometry depend on the allocator's state of the moment (advisor, round 3)
-            static std::mutex cap_mu;
-            std::lock_guard<std::mutex> cl(cap_mu);
+            std::lock_guard<std::mutex> cl(g_np_mu);
             int64_t &cap_free_mb = g_free_mb[current_device()];
             if (cap_free_mb == 0) {
                 size_t free_b = 0, total_b = 0;

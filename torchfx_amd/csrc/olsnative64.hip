@@ -14,12 +14,12 @@
 #include "common.h"
 #include "epilogue.h"
 #include "ldsfft.h"
+#include "plan_cache.h"
 #include "../../include/torchfx_hip.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <vector>
@@ -187,11 +187,12 @@ ols64_row_kernel(cpd *__restrict__ T, const cpd *__restrict__ Hp, const cpd *__r
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
 struct Plan {
-    cpd *Hp = nullptr, *tw256 = nullptr, *t4lo = nullptr, *tlo = nullptr, *thi = nullptr, *tu = nullptr;
-    std::shared_ptr<void> owner;                     // one device allocation: spectrum | tables
+    DeviceBuffer buf;                                // one device allocation: spectrum | tables
+    cpd *Hp, *tw256, *t4lo, *tlo, *thi, *tu;        // into buf
+    explicit Plan(const std::vector<cpd> &all) : buf(all) {}
 };
-static std::mutex g_mu;
-static std::map<std::vector<char>, Plan> g_plans;
+static PlanCache<Plan, 1> g_plans(8, "overlap-save");    // 16 MB of spectrum each; tail: lead
+static std::mutex g_mu;                                  // guards g_attr
 static bool g_attr[TFX_MAX_DEVICES] = {};
 
 static cpd W(long double num, long double den)
@@ -201,19 +202,8 @@ static cpd W(long double num, long double den)
     return w;
 }
 
-static Plan get_plan(const double *kf, int64_t K, int64_t lead, hipStream_t stream)
+static std::shared_ptr<Plan> build_plan(const double *kf, int64_t K, int64_t lead)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
-    std::vector<char> key((const char *)kf, (const char *)kf + K * sizeof(double));
-    key.push_back((char)lead);
-    key.push_back((char)current_device());
-    auto it = g_plans.find(key);
-    if (it != g_plans.end()) return it->second;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    TFX_CHECK(!(hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone),
-              "overlap-save: first use of this filter (%lld taps) inside a stream capture -- run it once before capturing "
-              "(its spectrum and tables are uploaded with blocking copies)", (long long)K);
-    if (g_plans.size() >= 8) g_plans.clear();        // 16 MB of spectrum each; a plan lives on with whoever still holds it
     // conj(FFT(taps behind `lead` zeros, zero padded to N)) / N   (_fftconv.py:123-124,131 + irfft scaling), row k1 = k % 256
     std::vector<double> re((size_t)NPTS, 0.0), im((size_t)NPTS, 0.0);
     for (int64_t i = 0; i < K; ++i) re[(size_t)(lead + i)] = kf[i];
@@ -237,24 +227,15 @@ static Plan get_plan(const double *kf, int64_t K, int64_t lead, hipStream_t stre
     for (int i = 0; i < 128; ++i) all[o++] = W(512.0L * i, (long double)NPTS);
     const size_t ou = o;
     for (int i = 0; i < 4096; ++i) all[o++] = W(i, 4096);
-    void *d = nullptr;
-    TFX_HIP(hipMalloc(&d, all.size() * sizeof(cpd)));
-    TFX_HIP(hipMemcpy(d, all.data(), all.size() * sizeof(cpd), hipMemcpyHostToDevice));
-    Plan p;
-    p.owner = std::shared_ptr<void>(d, [](void *q) { (void)hipFree(q); });
-    p.Hp = (cpd *)d;
-    p.tw256 = p.Hp + o256; p.t4lo = p.Hp + o4; p.tlo = p.Hp + olo; p.thi = p.Hp + ohi; p.tu = p.Hp + ou;
-    g_plans[key] = p;
+    auto p = std::make_shared<Plan>(all);
+    p->Hp = (cpd *)p->buf.p;
+    p->tw256 = p->Hp + o256; p->t4lo = p->Hp + o4; p->tlo = p->Hp + olo; p->thi = p->Hp + ohi; p->tu = p->Hp + ou;
     return p;
 }
 
 }  // namespace ols64
 
-void olsnative64_clear()
-{
-    std::lock_guard<std::mutex> lk(ols64::g_mu);
-    ols64::g_plans.clear();
-}
+void olsnative64_clear() { ols64::g_plans.clear(); }
 
 // float64 signals, taps beyond the one-launch kernels' 4096, a signal of at least one 2^20-point block, no streaming history
 bool olsnative64_supported(int64_t K, int64_t L, bool has_hist)
@@ -293,7 +274,8 @@ void olsnative64_forward(const double *x, double *y, int64_t C, int64_t Tn, cons
         g.nf_pair = (int *)scratch("olsn64_nf_pair", (size_t)C * sizeof(int), stream);
         TFX_HIP(hipMemsetAsync(g.nf_pair, 0, (size_t)C * sizeof(int), stream));
     }
-    const Plan plan = get_plan(kf_host, K, lead, stream);
+    const std::shared_ptr<Plan> plan =              // held until the launches are enqueued
+        g_plans.get(kf_host, (size_t)K * sizeof(double), {lead}, stream, [&] { return build_plan(kf_host, K, lead); });
     const int dev = current_device();
     constexpr size_t shm_col = (size_t)(N1 * CB + 256) * sizeof(cpd);
     constexpr size_t shm_row = (size_t)(N2 + N2 / 16 + 512) * sizeof(cpd);
@@ -321,18 +303,18 @@ void olsnative64_forward(const double *x, double *y, int64_t C, int64_t Tn, cons
         const int64_t np = std::min(slab, npairs - p0);
         {
             ProfScope ps("ols64_col_fwd_kernel", stream);
-            hipLaunchKernelGGL(ols64_col_fwd_kernel, dim3((unsigned)(np * ncb)), dim3(256), shm_col, stream, x, T, plan.tw256, g, 2 * p0);
+            hipLaunchKernelGGL(ols64_col_fwd_kernel, dim3((unsigned)(np * ncb)), dim3(256), shm_col, stream, x, T, plan->tw256, g, 2 * p0);
             TFX_HIP(hipGetLastError());
         }
         {
             ProfScope ps("ols64_row_kernel", stream);
-            hipLaunchKernelGGL(ols64_row_kernel, dim3((unsigned)(np * N1)), dim3(256), shm_row, stream, T, plan.Hp, plan.tw256, plan.t4lo,
-                               plan.tlo, plan.thi, plan.tu);
+            hipLaunchKernelGGL(ols64_row_kernel, dim3((unsigned)(np * N1)), dim3(256), shm_row, stream, T, plan->Hp, plan->tw256, plan->t4lo,
+                               plan->tlo, plan->thi, plan->tu);
             TFX_HIP(hipGetLastError());
         }
         {
             ProfScope ps("ols64_col_inv_kernel", stream);
-            hipLaunchKernelGGL(ols64_col_inv_kernel, dim3((unsigned)(np * ncb)), dim3(256), shm_col, stream, T, y, plan.tw256, g, 2 * p0);
+            hipLaunchKernelGGL(ols64_col_inv_kernel, dim3((unsigned)(np * ncb)), dim3(256), shm_col, stream, T, y, plan->tw256, g, 2 * p0);
             TFX_HIP(hipGetLastError());
         }
     }

@@ -28,11 +28,12 @@
 //     (_ops.py:149) -- or float32 (TFX_PREC_F32).
 #include "common.h"
 #include "epilogue.h"
+#include "plan_cache.h"
 #include "../../include/torchfx_hip.h"
 
 #include <cmath>
 #include <cstring>
-#include <map>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -604,19 +605,14 @@ struct SosPlan {
     int nsteps32 = 6, nsteps16 = 6, nsteps64 = 6;
     int64_t warm = -1;            // samples; -1 = too long / not decaying
     double err_bound_f32 = -1.0;  // worst-case |err| of f32 arithmetic for |x| <= 1 (lazy)
-    void *tab_f64_lc32 = nullptr; // device
-    void *tab_f32_lc32 = nullptr;
-    void *tab_f64_lc16 = nullptr;
-    void *tab_f32_lc16 = nullptr;
-    void *tab_f64_lc64 = nullptr;
-    void *tab_f32_lc64 = nullptr;
-    void *tab_f64_lc64_unit = nullptr;   // unit-b0 form (fill_tables)
+    std::unique_ptr<DeviceBuffer> tab_f64_lc32, tab_f32_lc32, tab_f64_lc16, tab_f32_lc16, tab_f64_lc64, tab_f32_lc64;   // lazy
+    std::unique_ptr<DeviceBuffer> tab_f64_lc64_unit;     // unit-b0 form (fill_tables)
     int unit_ok = -1;                    // the cascade has a unit-b0 form (lazy)
     std::vector<double> sos;
 };
 
-static std::mutex g_plan_mu;
-static std::map<std::vector<double>, SosPlan *> g_plans;
+static PlanCache<SosPlan, 1> g_plans(256);     // tail: the number of bands (a bank of NB x K sections is not a cascade of NB*K)
+static std::mutex g_plan_mu;                   // the lazy members of a plan
 
 // one zero-input step of the whole cascade on state w = [x1,x2, y1_1,y1_2, ..., yK_1,yK_2]
 static void cascade_step(const std::vector<double> &sos, int K, std::vector<ld> &w)
@@ -867,12 +863,6 @@ static double f32_error_bound(const std::vector<double> &sos, int K)
     return 2.5 * worst / scale;
 }
 
-static void free_plan(SosPlan *pl)
-{
-    void *t[7] = {pl->tab_f64_lc32, pl->tab_f32_lc32, pl->tab_f64_lc16, pl->tab_f32_lc16, pl->tab_f64_lc64, pl->tab_f32_lc64, pl->tab_f64_lc64_unit};
-    for (void *q : t) if (q) (void)hipFree(q);
-    delete pl;
-}
 static double plan_err_bound(SosPlan *pl)
 {
     std::lock_guard<std::mutex> lk(g_plan_mu);
@@ -894,35 +884,26 @@ static double auto_bound()
     return (e && *e) ? atof(e) : 2e-5;
 }
 
-static SosPlan *get_plan(const double *sos_host, int64_t K, hipStream_t stream, int64_t NB = 1)
+static std::shared_ptr<SosPlan> get_plan(const double *sos_host, int64_t K, hipStream_t stream, int64_t NB = 1)
 {
-    std::vector<double> key(sos_host, sos_host + NB * K * 6);
-    key.push_back((double)NB);             // a bank of NB x K sections is not a cascade of NB*K
-    key.push_back((double)current_device());   // the tables live on one device
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    auto it = g_plans.find(key);
-    if (it != g_plans.end()) return it->second;
-    if (g_plans.size() > 256) {   // bound the cache
-        for (auto &kv : g_plans) free_plan(kv.second);
-        g_plans.clear();
-    }
-    SosPlan *pl = new SosPlan();
-    pl->K = (int)K;
-    pl->NB = (int)NB;
-    pl->sos.assign(sos_host, sos_host + NB * K * 6);
-    pl->warm = 0;
-    for (int64_t b = 0; b < NB; ++b) {     // every band must have forgotten its start state
-        std::vector<double> one(sos_host + b * K * 6, sos_host + (b + 1) * K * 6);
-        const int64_t w = warmup_length(one, (int)K);
-        if (w < 0) { pl->warm = -1; break; }
-        if (w > pl->warm) pl->warm = w;
-    }
-    g_plans[key] = pl;
-    return pl;
+    return g_plans.get(sos_host, (size_t)(NB * K * 6) * sizeof(double), {NB}, stream, [&] {
+        auto pl = std::make_shared<SosPlan>();
+        pl->K = (int)K;
+        pl->NB = (int)NB;
+        pl->sos.assign(sos_host, sos_host + NB * K * 6);
+        pl->warm = 0;
+        for (int64_t b = 0; b < NB; ++b) {     // every band must have forgotten its start state
+            std::vector<double> one(sos_host + b * K * 6, sos_host + (b + 1) * K * 6);
+            const int64_t w = warmup_length(one, (int)K);
+            if (w < 0) { pl->warm = -1; break; }
+            if (w > pl->warm) pl->warm = w;
+        }
+        return pl;
+    });
 }
 
 template <typename TC>
-static void *ensure_table(SosPlan *pl, void **slot, int LC, int *nsteps, hipStream_t stream, bool unit = false)
+static void *ensure_table(SosPlan *pl, std::unique_ptr<DeviceBuffer> *slot, int LC, int *nsteps, hipStream_t stream, bool unit = false)
 {
     std::lock_guard<std::mutex> lk(g_plan_mu);
     if (!*slot) {
@@ -933,23 +914,12 @@ static void *ensure_table(SosPlan *pl, void **slot, int LC, int *nsteps, hipStre
             fill_tables<TC>(one, pl->K, LC, hb, *nsteps, unit);
             h.insert(h.end(), hb.begin(), hb.end());
         }
-        void *d = nullptr;
-        TFX_HIP(hipMalloc(&d, h.size() * sizeof(TC)));
-        // synchronous copy from a temporary: happens once per distinct filter
-        TFX_HIP(hipMemcpy(d, h.data(), h.size() * sizeof(TC), hipMemcpyHostToDevice));
-        *slot = d;
+        *slot = std::make_unique<DeviceBuffer>(h);      // synchronous copy from a temporary: once per distinct filter
     }
-    return *slot;
+    return (*slot)->p;
 }
 
-void sos_clear_plans()
-{
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    for (auto &kv : g_plans) {
-        free_plan(kv.second);
-    }
-    g_plans.clear();
-}
+void sos_clear_plans() { g_plans.clear(); }
 
 static int g_cus[TFX_MAX_DEVICES] = {0};
 static int device_cus()
@@ -1156,7 +1126,8 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in,
     for (int64_t i = 0; i < NB * K * 6; ++i)
         TFX_CHECK(std::isfinite(sos_host[i]), "sos_forward: non-finite SOS coefficient");
 
-    SosPlan *pl = get_plan(sos_host, K, stream, NB);
+    const std::shared_ptr<SosPlan> plan = get_plan(sos_host, K, stream, NB);     // held until the launches are enqueued
+    SosPlan *pl = plan.get();
     int prec = precision;
     if (prec == TFX_PREC_AUTO) prec = (plan_err_bound(pl) <= auto_bound()) ? TFX_PREC_F32 : TFX_PREC_F64;
     if (x_dtype == TFX_F64 || y_dtype == TFX_F64) prec = TFX_PREC_F64;   // f64 signals: always f64 math
@@ -1347,9 +1318,12 @@ void chunk_forward(const float *x, int64_t x_pitch, float *y, int64_t C, int64_t
     p.nseg = 1; p.warm = 0; p.seg_len = ceil_div(T, 1024) * 1024; p.nsum = 0;
     p.ep_stat = -1; p.nf_flag = nullptr;
     int prec = precision;
+    std::shared_ptr<SosPlan> plan;                 // the plan and the taps are held until the launch is enqueued
+    std::shared_ptr<DeviceBuffer> taps;
     if (K > 0) {
         for (int64_t i = 0; i < K * 6; ++i) TFX_CHECK(std::isfinite(sos_host[i]), "chunk_forward: non-finite SOS coefficient");
-        SosPlan *pl = get_plan(sos_host, K, stream, 1);
+        plan = get_plan(sos_host, K, stream, 1);
+        SosPlan *pl = plan.get();
         if (prec == TFX_PREC_AUTO) prec = (plan_err_bound(pl) <= auto_bound()) ? TFX_PREC_F32 : TFX_PREC_F64;
         if (prec == TFX_PREC_F32) {
             p.tab = ensure_table<float>(pl, &pl->tab_f32_lc16, 16, &pl->nsteps16, stream);
@@ -1363,7 +1337,8 @@ void chunk_forward(const float *x, int64_t x_pitch, float *y, int64_t C, int64_t
         // the flipped taps, zeros up to Kp; cached by content like every other tap vector
         std::vector<float> lay((size_t)Kp, 0.0f);
         memcpy(lay.data() + (Hpad - H), taps_host, (size_t)Kf * 4);
-        q.taps = (const float *)cached_taps(lay.data(), (size_t)Kp * 4, (size_t)Kp * 4);
+        taps = cached_taps(lay.data(), (size_t)Kp * 4, (size_t)Kp * 4);
+        q.taps = (const float *)taps->p;
     }
     q.hist_in = Kf > 1 ? hist_in : nullptr; q.hist_out = Kf > 1 ? hist_out : nullptr; q.y = y; q.Kf = (int)Kf;
     q.Tpad = (int)((T + 3) & ~3);
@@ -1413,7 +1388,8 @@ bool sos_unit_rows(const double *sos_host, int64_t K, double (*rows)[5])
 
 void sos_plan_info(const double *sos_host, int64_t K, int *precision, int64_t *warmup, double *err_bound)
 {
-    SosPlan *pl = get_plan(sos_host, K, nullptr, 1);
+    const std::shared_ptr<SosPlan> plan = get_plan(sos_host, K, nullptr, 1);
+    SosPlan *pl = plan.get();
     const double eb = plan_err_bound(pl);
     if (precision) *precision = (eb <= auto_bound()) ? TFX_PREC_F32 : TFX_PREC_F64;
     if (warmup) *warmup = pl->warm;
