@@ -318,6 +318,24 @@ int tfx_delay_line_forward(const void *x, void *y, int dtype, int64_t C, int64_t
                            int64_t delay, double decay, double mix, tfx_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * tfx_delay_forward -- the BPM-synced multi-tap Delay (src/torchfx/effect.py:934-1538: MonoDelayStrategy,
+ * PingPongDelayStrategy and the torch.lerp dry/wet mix of Delay.forward) in ONE launch:
+ *   wet[n] = sum_{i=1..taps} amps[i-1] * src[n - i*delay]   (positions outside [0, T) skipped, tap order, +0.0 start)
+ *   y[n]   = lerp(n < T ? x[n] : 0, wet[n], mix)            n in [0, T + taps*delay)
+ * x DEVICE [rows, T] of dtype; y DEVICE [rows, T + taps*delay]; amps_host HOST float64 [taps] (the reference's
+ * feedback ** (i-1), amps[0] = 1).  pingpong != 0: rows are consecutive (left, right) pairs (rows even); odd taps of the
+ * left row feed the right one, even taps of the right row the left one; else every row delays itself.  Same arithmetic
+ * as the composition on the device (bit-identical).  The epilogue works as for the filters above.  Arguments are
+ * checked before the device is touched (null pointers, taps < 1, delay < 0, odd rows with ping-pong, bad dtype).
+ * ------------------------------------------------------------------------- */
+int tfx_delay_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
+                      const double *amps_host, double mix, int pingpong, const tfx_epilogue *epilogue,
+                      tfx_stream_t stream);
+/* the kernel tfx_delay_forward picks (host-only): 0 = span (taps*delay + tile staged in LDS), 1 = lattice (long delay,
+ * taps <= 8, residue classes with a register ring), 2 = gather (anything else, every tap a global load) */
+int tfx_delay_plan_info(int64_t delay, int64_t taps, int dtype, int pingpong, int *regime);
+
+/* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of
  * ParallelFilterCombination.forward, src/torchfx/filter/__base.py:1019-1026).
  * xs_host: HOST array of n DEVICE pointers, each [numel] of dtype.

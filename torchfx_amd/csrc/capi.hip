@@ -62,6 +62,13 @@ void normalize_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, 
 void sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, hipStream_t stream);
 void delay_line_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int64_t delay, double coeff,
                         hipStream_t stream);
+// delay.hip
+void delay_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
+                 const double *amps_host, double mix, int pingpong, const Epilogue *ep);
+void delay_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
+                   const double *amps_host, double mix, int pingpong, const Epilogue *ep, hipStream_t stream);
+int delay_regime(int64_t D, int64_t taps, int esz, int pingpong);
+void delay_clear();
 // layout.hip
 void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, int64_t C, int64_t ld_out, int64_t f_base,
                           double scale, hipStream_t stream);
@@ -562,6 +569,26 @@ int tfx_delay_line_forward(const void *x, void *y, int dtype, int64_t C, int64_t
     TFX_API_END
 }
 
+int tfx_delay_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
+                      const double *amps_host, double mix, int pingpong, const tfx_epilogue *epilogue, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    const Epilogue ep = to_epilogue(epilogue);
+    delay_check(x, y, dtype, rows, T, delay, taps, amps_host, mix, pingpong, &ep);     // before anything touches the device
+    delay_forward(x, y, dtype, rows, T, delay, taps, amps_host, mix, pingpong, &ep, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_delay_plan_info(int64_t delay, int64_t taps, int dtype, int pingpong, int *regime)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(regime, "delay_plan_info: null output");
+    TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "delay_plan_info: bad dtype %d", dtype);
+    TFX_CHECK(taps >= 1 && delay >= 0 && (delay == 0 || taps <= (INT64_MAX / 2) / delay), "delay_plan_info: bad delay or taps");
+    *regime = delay_regime(delay, taps, dtype == TFX_F32 ? 4 : 8, pingpong != 0);
+    TFX_API_END
+}
+
 int tfx_sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, tfx_stream_t stream)
 {
     TFX_API_BEGIN
@@ -667,6 +694,7 @@ int tfx_clear_caches(void)
     olsnative_clear();
     olsnative64_clear();
     olslds_clear();
+    delay_clear();
     scratch_clear();
     TFX_API_END
 }

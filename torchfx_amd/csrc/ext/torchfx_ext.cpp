@@ -285,6 +285,47 @@ Tensor delay_line_op(const Tensor &x, int64_t delay_samples, double decay, doubl
     return y;
 }
 
+// BPM-synced multi-tap Delay (effect.py:934-1538): x [..., T] -> [..., T + taps*D], leading dimensions flattened into rows;
+// ping-pong when the second-to-last dimension holds a stereo pair, as PingPongDelayStrategy decides
+std::vector<int64_t> delay_shape(const Tensor &x, int64_t delay_samples, int64_t taps)
+{
+    TORCH_CHECK(x.dim() >= 1, "delay_forward: x must have a time dimension");
+    TORCH_CHECK(taps >= 1, "delay_forward: at least one tap");
+    TORCH_CHECK(delay_samples >= 0, "delay_forward: negative delay");
+    std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
+    shape.back() += taps * delay_samples;
+    return shape;
+}
+
+std::tuple<Tensor, Tensor> delay_impl(const Tensor &x_in, int64_t delay_samples, at::ArrayRef<double> amps, double mix, bool pingpong,
+                                      double gain, bool clamp, int64_t stat_mode, bool per_row)
+{
+    need_device(x_in, "x");
+    const int64_t taps = (int64_t)amps.size();
+    const std::vector<int64_t> shape = delay_shape(x_in, delay_samples, taps);
+    const Tensor x = x_in.contiguous();
+    const int64_t T = x.size(-1), rows = T > 0 ? x.numel() / T : c10::multiply_integers(x.sizes().begin(), x.sizes().end() - 1);
+    const bool pp = pingpong && x.dim() >= 2 && x.size(-2) == 2;
+    Tensor y = at::empty(shape, x.options()), stat;
+    const tfx_epilogue ep = make_epilogue(gain, clamp, stat_mode, per_row, stat, x, rows);
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_delay_forward(x.data_ptr(), y.data_ptr(), dtype_code(x, "delay_forward"), rows, T, delay_samples, taps, amps.data(), mix,
+                               pp ? 1 : 0, &ep, stream_of(x)),
+             "delay_forward");
+    return {y, stat};
+}
+
+std::tuple<Tensor, Tensor> delay_ep_op(const Tensor &x, int64_t delay_samples, at::ArrayRef<double> amps, double mix, bool pingpong,
+                                       double gain, bool clamp, int64_t stat_mode, bool per_row)
+{
+    return delay_impl(x, delay_samples, amps, mix, pingpong, gain, clamp, stat_mode, per_row);
+}
+
+Tensor delay_op(const Tensor &x, int64_t delay_samples, at::ArrayRef<double> amps, double mix, bool pingpong)
+{
+    return std::get<0>(delay_impl(x, delay_samples, amps, mix, pingpong, 1.0, false, -1, false));
+}
+
 // ---------------------------------------------------------------------------------------------------
 // FIR (fir.py:556-568) and overlap-save FFT convolution (_fftconv.py:70-141)
 // ---------------------------------------------------------------------------------------------------
@@ -600,6 +641,17 @@ std::tuple<Tensor, Tensor, Tensor> biquad_meta(const Tensor &x, const Tensor &, 
     Tensor st = at::empty({x.size(0), 2}, x.options().dtype(at::kDouble));
     return {at::empty(x.sizes(), x.options().dtype(out_type(x, out_dtype))), st, at::empty_like(st)};
 }
+Tensor delay_meta(const Tensor &x, int64_t delay_samples, at::ArrayRef<double> amps, double, bool)
+{
+    return at::empty(delay_shape(x, delay_samples, (int64_t)amps.size()), x.options());
+}
+std::tuple<Tensor, Tensor> delay_ep_meta(const Tensor &x, int64_t delay_samples, at::ArrayRef<double> amps, double, bool, double, bool,
+                                         int64_t stat_mode, bool per_row)
+{
+    const int64_t T = x.dim() ? x.size(-1) : 1, rows = T > 0 ? x.numel() / T : 0;
+    return {at::empty(delay_shape(x, delay_samples, (int64_t)amps.size()), x.options()),
+            at::empty({stat_mode >= 0 ? (per_row ? rows : 1) : 0}, x.options().dtype(at::kDouble))};
+}
 Tensor fft_conv_meta(const Tensor &x, const Tensor &kernel, int64_t pad_left, int64_t pad_right)
 {
     const int64_t tout = x.size(1) + pad_left + pad_right - kernel.numel() + 1;
@@ -623,6 +675,9 @@ TORCH_LIBRARY(torchfx_hip, m)
     m.def("biquad_forward(Tensor x, Tensor b, float a1, float a2, Tensor? state_x=None, Tensor? state_y=None, *, "
           "ScalarType? out_dtype=None, int precision=-1) -> (Tensor, Tensor, Tensor)");
     m.def("delay_line_forward(Tensor(a) x, int delay_samples, float decay, float mix) -> Tensor(a)");
+    m.def("delay_forward(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong) -> Tensor");
+    m.def("delay_forward_ep(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong, float gain, bool clamp, int stat_mode, "
+          "bool per_row) -> (Tensor, Tensor)");
     m.def("fir_direct_forward(Tensor x, Tensor kernel) -> Tensor");
     m.def("fft_conv_forward(Tensor x, Tensor kernel, int pad_left, int pad_right) -> Tensor");
     m.def("fir_stream_forward(Tensor x, Tensor kernel, Tensor? hist, bool direct) -> (Tensor, Tensor)");
@@ -653,6 +708,8 @@ TORCH_LIBRARY_IMPL(torchfx_hip, CUDA, m)          // "CUDA" is the dispatch key 
     m.impl("sos_bank_sum_forward", bank_sum_op);
     m.impl("biquad_forward", biquad_op);
     m.impl("delay_line_forward", delay_line_op);
+    m.impl("delay_forward", delay_op);
+    m.impl("delay_forward_ep", delay_ep_op);
     m.impl("fir_direct_forward", fir_direct_op);
     m.impl("fft_conv_forward", fft_conv_op);
     m.impl("fir_stream_forward", fir_stream_op);
@@ -680,6 +737,8 @@ TORCH_LIBRARY_IMPL(torchfx_hip, Meta, m)
     m.impl("biquad_forward", biquad_meta);
     m.impl("fir_direct_forward", [](const Tensor &x, const Tensor &) { return at::empty_like(x); });
     m.impl("fft_conv_forward", fft_conv_meta);
+    m.impl("delay_forward", delay_meta);
+    m.impl("delay_forward_ep", delay_ep_meta);
     m.impl("fir_stream_forward", [](const Tensor &x, const Tensor &kernel, const OptTensor &, bool) {
         return std::make_tuple(at::empty_like(x), at::empty({x.size(0), kernel.numel() - 1}, x.options()));
     });
@@ -697,7 +756,7 @@ static void no_cpu_boxed(const c10::OperatorHandle &op, c10::DispatchKeySet, tor
 TORCH_LIBRARY_IMPL(torchfx_hip, CPU, m)
 {
     for (const char *name : {"sos_forward", "sos_forward_sections", "sos_bank_forward", "sos_bank_sum_forward", "biquad_forward",
-                             "delay_line_forward", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
+                             "delay_line_forward", "delay_forward", "delay_forward_ep", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
                              "fft_conv_forward_ep", "sos_fft_conv_forward", "normalize_apply", "sum_forward", "gain_forward", "quantile_abs", "stat_forward",
                              "normalize_forward", "deinterleave_forward", "deinterleave_into", "interleave_forward"})
         m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());

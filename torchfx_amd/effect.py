@@ -5,8 +5,10 @@ Reference: ``src/torchfx/effect.py`` -- ``FX.__or__`` (:253-258, builds a ``Filt
 SURVEY.md 8f rank 3: they are not filters, but a ``wave | iir | gain | fir`` pipeline passes through
 them, so they run as streaming HIP passes (``csrc/effects.hip``) and a clamp-free ``Gain`` can be
 folded into a neighbouring filter's coefficients by the ``Wave`` planner (opt-in, ``fuse_gain``).
-``Reverb`` is the reference's one-tap feed-forward comb over ``delay_line_forward``; the BPM-synced
-multi-tap ``Delay`` remains out of scope.
+``Reverb`` is the reference's one-tap feed-forward comb over ``delay_line_forward``.  ``Delay`` is the reference's
+BPM-synced multi-tap delay (``effect.py:934-1538``) with its mono and ping-pong strategies: on device float32 / float64
+signals one HIP launch (``csrc/delay.hip``) replaces the strategy's ``2 * taps`` passes, the zero-pad copy and the
+``torch.lerp``; CPU tensors, other dtypes and custom strategies run the reference's torch composition.
 """
 from __future__ import annotations
 
@@ -215,3 +217,138 @@ class Reverb(FX):
         from torchfx_amd._ops import delay_line_forward
 
         return delay_line_forward(waveform, self.delay, self.decay, self.mix)
+
+
+# ------------------------------------------------------------------------------- Delay
+class DelayStrategy(abc.ABC):
+    """How the delayed copies are laid out (``effect.py:934-1023``): ``apply_delay(waveform, delay_samples, taps, feedback)``
+    returns the wet signal, ``delay_samples * taps`` samples longer than the input, tap ``i`` delayed by ``i * delay_samples``
+    with gain ``feedback ** (i - 1)``."""
+
+    @abc.abstractmethod
+    def apply_delay(self, waveform: Tensor, delay_samples: int, taps: int, feedback: float) -> Tensor: ...
+
+
+def _tap_sum(dst: Tensor, src: Tensor, delay_samples: int, taps: int, feedback: float, tap_filter=None) -> None:
+    """``dst[..., i*D : i*D + T] += src * feedback ** (i - 1)`` for the taps ``tap_filter`` accepts, in tap order -- one
+    multiply and one add per tap, as the reference's strategies do."""
+    T = src.size(-1)
+    for i in range(1, taps + 1):
+        if tap_filter is not None and not tap_filter(i):
+            continue
+        start = delay_samples * i
+        n = min(T, dst.size(-1) - start)
+        if n > 0:
+            dst[..., start:start + n] += src[..., :n] * (1.0 if i == 1 else feedback ** (i - 1))
+
+
+class MonoDelayStrategy(DelayStrategy):
+    """Every channel delays itself (``effect.py:1026-1151``), any shape ``(..., time)``."""
+
+    def apply_delay(self, waveform: Tensor, delay_samples: int, taps: int, feedback: float) -> Tensor:
+        shape = list(waveform.shape)
+        shape[-1] += delay_samples * taps
+        delayed = torch.zeros(shape, dtype=waveform.dtype, device=waveform.device)
+        _tap_sum(delayed, waveform, delay_samples, taps, feedback)
+        return delayed
+
+
+class PingPongDelayStrategy(DelayStrategy):
+    """Echoes bounce between the channels of a stereo pair (``effect.py:1154-1305``): odd taps carry the left channel into
+    the right one, even taps the right into the left.  Input that is not ``(..., 2, time)`` is delayed as mono."""
+
+    def apply_delay(self, waveform: Tensor, delay_samples: int, taps: int, feedback: float) -> Tensor:
+        if waveform.ndim < 2 or waveform.size(-2) != 2:
+            return MonoDelayStrategy().apply_delay(waveform, delay_samples, taps, feedback)
+        shape = list(waveform.shape)
+        shape[-1] += delay_samples * taps
+        delayed = torch.zeros(shape, dtype=waveform.dtype, device=waveform.device)
+        _tap_sum(delayed[..., 1, :], waveform[..., 0, :], delay_samples, taps, feedback, lambda i: i % 2 == 1)
+        _tap_sum(delayed[..., 0, :], waveform[..., 1, :], delay_samples, taps, feedback, lambda i: i % 2 == 0)
+        return delayed
+
+
+class Delay(FX):
+    """Multi-tap delay with a dry/wet mix (``effect.py:1308-1538``)::
+
+        delayed[n] = sum_{i=1..taps} feedback^(i-1) * x[n - i * delay_samples]
+        y = torch.lerp(x zero-padded to the delayed length, delayed, mix)
+
+    ``delay_samples`` directly, or ``bpm`` + ``delay_time`` (a :class:`~torchfx_amd.typing.MusicalTime` string such as
+    ``"1/8"``, ``"1/4d"``, ``"1/8t"``) at ``fs``; with ``fs=None`` the rate comes from the ``Wave`` the effect is piped
+    into and the delay is worked out at the first ``forward``.  The output is ``taps * delay_samples`` samples longer
+    than the input.
+
+    Device float32 / float64 signals with the stock strategies run one HIP launch (:func:`torchfx_ext.delay_forward`,
+    bit-identical to the composition on the device); CPU tensors, other dtypes and custom strategies run the reference's
+    torch composition (``strategy.apply_delay`` then ``torch.lerp``)."""
+
+    def __init__(self, delay_samples: int | None = None, bpm: float | None = None, delay_time: str = "1/8",
+                 fs: int | None = None, feedback: float = 0.3, mix: float = 0.2, taps: int = 3,
+                 strategy: DelayStrategy | None = None) -> None:
+        super().__init__()
+        self.fs, self.bpm, self.delay_time = fs, bpm, delay_time
+        if delay_samples is not None:
+            assert delay_samples > 0, "Delay samples must be positive."
+            self.delay_samples = delay_samples
+            self._needs_calculation = False
+        else:
+            assert bpm is not None, "BPM must be provided if delay_samples is not set."
+            assert bpm > 0, "BPM must be positive."
+            if fs is not None:
+                assert fs > 0, "Sample rate (fs) must be positive."
+                self.delay_samples = self._calculate_delay_samples(bpm, delay_time, fs)
+                self._needs_calculation = False
+            else:
+                self.delay_samples = None      # worked out at the first forward, once a Wave has set fs
+                self._needs_calculation = True
+        assert 0 <= feedback <= 0.95, "Feedback must be between 0 and 0.95."
+        assert 0 <= mix <= 1, "Mix must be between 0 and 1."
+        assert taps >= 1, "Taps must be at least 1."
+        self.feedback, self.mix, self.taps = feedback, mix, taps
+        self.strategy = strategy or MonoDelayStrategy()
+
+    @staticmethod
+    def _calculate_delay_samples(bpm: float, delay_time: str, fs: int) -> int:
+        from torchfx_amd.typing import MusicalTime
+
+        return int(MusicalTime.from_string(delay_time).duration_seconds(bpm) * fs)
+
+    def _resolve(self) -> None:
+        if self._needs_calculation:
+            assert self.fs is not None, ("Sample rate (fs) is required for BPM-synced delay."
+                                         "Either provide fs parameter or use with Wave pipeline (wave | delay).")
+            assert self.fs > 0, "Sample rate (fs) must be positive."
+            assert self.bpm is not None, "BPM must be set for BPM-synced delay."
+            self.delay_samples = self._calculate_delay_samples(self.bpm, self.delay_time, self.fs)
+            self._needs_calculation = False
+
+    def native_refusal(self, x: Tensor) -> str | None:
+        """None when ``x`` runs the HIP kernel, else why it takes the torch composition."""
+        if type(self.strategy) not in (MonoDelayStrategy, PingPongDelayStrategy):
+            return f"custom strategy {type(self.strategy).__name__}"
+        if not x.is_cuda:
+            return f"{x.device.type} tensor"
+        if x.dtype not in (torch.float32, torch.float64):
+            return f"{x.dtype} signal"
+        if x.dim() == 0:
+            return "0-d tensor"
+        return None
+
+    def pingpong(self, x: Tensor) -> bool:
+        return isinstance(self.strategy, PingPongDelayStrategy) and x.dim() >= 2 and x.size(-2) == 2
+
+    @torch.no_grad()
+    def forward(self, waveform: Tensor, epilogue=None) -> Tensor:
+        self._resolve()
+        if self.native_refusal(waveform) is None:
+            return _ext().delay_forward(waveform, self.delay_samples, self.taps, self.feedback, self.mix,
+                                        self.pingpong(waveform), epilogue=epilogue)
+        if epilogue is not None:
+            raise RuntimeError(f"Delay: no fused epilogue on the torch composition ({self.native_refusal(waveform)})")
+        delayed = self.strategy.apply_delay(waveform, self.delay_samples, self.taps, self.feedback)
+        if waveform.size(-1) < delayed.size(-1):
+            padded = torch.zeros(*waveform.shape[:-1], delayed.size(-1), dtype=waveform.dtype, device=waveform.device)
+            padded[..., :waveform.size(-1)] = waveform
+            waveform = padded
+        return torch.lerp(waveform, delayed, self.mix)

@@ -32,7 +32,8 @@ from torchfx_amd import _lib as L
 from torchfx_amd import native
 
 __all__ = [
-    "biquad_forward", "sos_forward", "sos_bank_forward", "sos_bank_sum_forward", "delay_line_forward",
+    "biquad_forward", "sos_forward", "sos_bank_forward", "sos_bank_sum_forward", "delay_line_forward", "delay_forward",
+    "delay_amplitudes", "delay_regime",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
 ]
@@ -119,6 +120,37 @@ def delay_line_forward(x: Tensor, delay_samples: int, decay: float, mix: float) 
     """``binding.cpp:68-81`` / ``delay_cpu.cpp:43-85``.  Like the reference, returns the input tensor itself
     when the signal is not longer than the delay."""
     return native.ops().delay_line_forward(x, int(delay_samples), float(decay), float(mix))
+
+
+def delay_amplitudes(taps: int, feedback: float) -> list[float]:
+    """The tap gains of the reference's delay strategies (``effect.py:1118-1121``): 1.0, then ``feedback ** (i - 1)`` as
+    Python computes it."""
+    return [1.0 if i == 1 else float(feedback ** (i - 1)) for i in range(1, int(taps) + 1)]
+
+
+def delay_forward(x: Tensor, delay_samples: int, taps: int, feedback: float, mix: float, pingpong: bool = False,
+                  epilogue: Epilogue | None = None) -> Tensor:
+    """The BPM-synced multi-tap ``Delay`` in one launch: ``torch.lerp(pad(x), strategy.apply_delay(x, D, taps, feedback),
+    mix)`` of ``effect.py:1447-1538`` with the mono or (``pingpong`` and ``x.size(-2) == 2``) ping-pong strategy.
+    ``x [..., T]`` -> ``[..., T + taps * delay_samples]``, bit-identical to that composition on the device."""
+    amps = delay_amplitudes(taps, feedback)
+    if epilogue is not None:
+        y, epilogue.stat_value = native.ops().delay_forward_ep(x, int(delay_samples), amps, float(mix), bool(pingpong), epilogue.gain,
+                                                               epilogue.clamp, epilogue.stat_mode, epilogue.per_row)
+        return y
+    return native.ops().delay_forward(x, int(delay_samples), amps, float(mix), bool(pingpong))
+
+
+DELAY_REGIMES = ("span", "lattice", "gather")
+
+
+def delay_regime(delay_samples: int, taps: int, dtype: torch.dtype = torch.float32, pingpong: bool = False) -> str:
+    """Which kernel :func:`delay_forward` runs (``tfx_delay_plan_info``; host-only): "span" (the taps' span staged in LDS),
+    "lattice" (long delay, residue classes with the last taps in registers) or "gather"."""
+    r = ctypes.c_int(0)
+    L.check(L.load().tfx_delay_plan_info(int(delay_samples), int(taps), L.TFX_F64 if dtype == torch.float64 else L.TFX_F32,
+                                         int(bool(pingpong)), ctypes.byref(r)))
+    return DELAY_REGIMES[r.value]
 
 
 _TAPS_HOST: dict = {}        # (id(base tensor), offset, numel, dtype wanted) -> (weakref to base, version, host tensor)

@@ -210,7 +210,7 @@ def plan_cache_clear() -> None:
 
 
 def _member_key(m: nn.Module, guard: list) -> tuple:
-    from torchfx_amd.effect import Gain, Normalize
+    from torchfx_amd.effect import Delay, Gain, Normalize
 
     guard.append(m)
     k: tuple = (id(m),)
@@ -227,6 +227,9 @@ def _member_key(m: nn.Module, guard: list) -> tuple:
     elif isinstance(m, Normalize):
         guard.append(m.strategy)
         k += (id(m.strategy),)
+    elif isinstance(m, Delay):
+        guard.append(m.strategy)
+        k += (m.delay_samples, m.taps, m.feedback, m.mix, type(m.strategy), getattr(m, "fs", None))
     return k
 
 
@@ -387,16 +390,17 @@ class Wave:
         if getattr(self, "fuse_recursive", False):
             plan = self._recursive_plan(plan, length, dtype)
         if getattr(self, "fuse_epilogue", False):
-            plan = self._epilogue_plan(plan)
+            plan = self._epilogue_plan(plan, dtype)
         return plan
 
     @staticmethod
-    def _epilogue_plan(plan: list[nn.Module]) -> list[nn.Module]:
+    def _epilogue_plan(plan: list[nn.Module], dtype: torch.dtype = torch.float32) -> list[nn.Module]:
         """``fuse_epilogue``: ``filter | Gain`` , ``filter | Normalize`` and ``filter | Gain | Normalize`` run as
         the filter's kernel with an epilogue (``effect.Epilogued``) when the filter is an SOS module / cascade or
         an FFT-mode FIR and the normalisation strategy is one with a streaming reduction (peak, RMS, per
-        channel)."""
-        from torchfx_amd.effect import Epilogued, Gain, Normalize
+        channel).  A ``Delay`` with a stock strategy on a float32 / float64 signal is such a producer too (its one
+        launch stores every output sample once); a custom strategy runs the torch composition and stays staged."""
+        from torchfx_amd.effect import Delay, Epilogued, Gain, MonoDelayStrategy, Normalize, PingPongDelayStrategy
         from torchfx_amd.filter.biquad import Biquad
         from torchfx_amd.filter.fir import FIR
         from torchfx_amd.filter.fused import CascadeFIR, FusedSOSCascade
@@ -406,7 +410,9 @@ class Wave:
         i = 0
         while i < len(plan):
             m = plan[i]
-            producer = isinstance(m, (IIR, Biquad, FusedSOSCascade, CascadeFIR)) or (_plain_fir(m) and m._conv_mode != "direct")
+            producer = isinstance(m, (IIR, Biquad, FusedSOSCascade, CascadeFIR)) or (_plain_fir(m) and m._conv_mode != "direct") or (
+                type(m) is Delay and type(m.strategy) in (MonoDelayStrategy, PingPongDelayStrategy)
+                and dtype in (torch.float32, torch.float64))
             gain = norm = None
             j = i + 1
             if producer and j < len(plan) and isinstance(plan[j], Gain):
@@ -533,7 +539,7 @@ class Wave:
     def explain(self) -> list[str]:
         """One line per step of :meth:`plan` for THIS tensor: the step, the route it will take (``CascadeFIR``: the fused
         recursion-in-pass-A pipeline or the staged pair of launches) and why."""
-        from torchfx_amd.effect import Epilogued
+        from torchfx_amd.effect import Delay, Epilogued
         from torchfx_amd.filter.fused import CascadeFIR, FusedSOSCascade
 
         lines = []
@@ -548,8 +554,24 @@ class Wave:
                     line += f": staged -- {inner.recursive_refused}"
                 elif getattr(inner, "fold_refused", None) is not None:
                     line += f": staged -- spectral fold refused (error estimate {inner.fold_refused:.1e})"
+            elif isinstance(inner, Delay):
+                line += ": " + Wave._delay_route(inner, self._ys, self.fs)
             lines.append(line)
         return lines
+
+    @staticmethod
+    def _delay_route(d, x: Tensor, fs) -> str:
+        """``native (<regime>)`` or ``torch composition -- <reason>`` for a Delay step on ``x`` (the input of the pipeline:
+        every step before a Delay keeps the dtype and device)."""
+        from torchfx_amd import torchfx_ext
+
+        why = d.native_refusal(x)
+        if why is not None:
+            return f"torch composition -- {why}"
+        D = d.delay_samples
+        if D is None:                       # BPM-synced and not run yet: the delay the first forward will use
+            D = d._calculate_delay_samples(d.bpm, d.delay_time, d.fs if d.fs is not None else fs)
+        return f"native ({torchfx_ext.delay_regime(D, d.taps, x.dtype, d.pingpong(x))})"
 
     def _materialize(self) -> None:
         if not self._pipeline:
