@@ -242,6 +242,42 @@ def test_tuning_knobs_are_read_once_per_process_and_reloadable():
     assert d0 == 1 << 18 and d1 == 1 << 18        # the dynamic switch itself is read at reload; then every lookup is fresh
 
 
+# switches retired in favour of the constant they defaulted to: no source may read or offer them again
+RETIRED_KNOBS = (
+    "TFX_SOS_NT", "TFX_SOS_FAIR", "TFX_SOS_WAVES_PER_CU", "TFX_SOS_WARM_ROUND", "TFX_SOS_MIN_SEG_OVER_WARM", "TFX_SOS_UNIT_B0",
+    "TFX_FIR_NJ", "TFX_OLS_NT", "TFX_OLS_LDS_NT", "TFX_OLS_ROWMAP", "TFX_OLS_ALIGN", "TFX_OLS_NATIVE_MIN_K",
+    "TFX_OLS_N18_MINK", "TFX_OLS_N20_MINK", "TFX_OLS_N21", "TFX_OLS_SOS", "TFX_OLS_SOS_MAXWARM", "TFX_OLS_SOS_N21",
+    "TFX_OLS_SOS_HALO_BITS", "TFX_OLS_SOS_UNIT_B0", "TFX_OLS_GPU_SPECTRUM", "TFX_OLS_TRACE", "TFX_OLS_LDS16K_MINK",
+    "TFX_OLS_LDS16K_GRID",
+)
+
+
+def test_every_environment_knob_the_library_reads_is_documented():
+    """The TFX_* variables the native library reads (env_i64 / getenv under torchfx_amd/csrc) are exactly the ones
+    INTEGRATION.md section 5 names, and no retired switch is left anywhere in the library's sources or header."""
+    read = set()
+    for dirpath, _, files in os.walk(os.path.join(ROOT, "torchfx_amd", "csrc")):
+        for f in files:
+            if f.endswith((".hip", ".h", ".cpp")):
+                src = open(os.path.join(dirpath, f)).read()
+                read |= set(re.findall(r'\b(?:env_i64|getenv)\s*\(\s*"(TFX_[A-Z0-9_]+)"', src))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = re.search(r"^## 5\..*?(?=^## |\Z)", doc, flags=re.M | re.S).group(0)
+    documented = set(re.findall(r"\b(TFX_[A-Z0-9_]+)", section))
+    assert len(read) > 10, sorted(read)
+    assert read == documented, f"read, not documented: {sorted(read - documented)}; documented, not read: {sorted(documented - read)}"
+    pattern = re.compile(r"\b(%s)\b" % "|".join(RETIRED_KNOBS))
+    left = []
+    for top in ("torchfx_amd", "include"):
+        for dirpath, dirs, files in os.walk(os.path.join(ROOT, top)):
+            dirs[:] = [d for d in dirs if d not in ("build", "__pycache__")]
+            for f in files:
+                if f.endswith((".hip", ".h", ".cpp", ".py", ".md", ".txt")):
+                    path = os.path.join(dirpath, f)
+                    left += ["%s: %s" % (os.path.relpath(path, ROOT), m) for m in pattern.findall(open(path).read())]
+    assert not left, left
+
+
 def _plan_info(lib, sos):
     a = np.ascontiguousarray(sos, dtype=np.float64)
     prec, warm, bound = ctypes.c_int(), ctypes.c_int64(), ctypes.c_double()

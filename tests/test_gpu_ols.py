@@ -46,7 +46,7 @@ def test_native_ols_vs_rocfft_and_f64(C, T, K, monkeypatch):
     """The hand-written four-step pipeline (two frames per complex FFT) against the rocFFT path
     and against a float64 FFT convolution; odd frame counts leave an unpaired frame.  The last case (140 000 taps) takes
     the 2^20-point block on its own -- whose filter spectrum is computed ON THE DEVICE in float32 by the pipeline's forward
-    kernels (olsnative.hip, `TFX_OLS_GPU_SPECTRUM`), like the reference's own float32 `rfft` of the kernel
+    kernels (olsnative.hip, ols_rowspec4096_kernel), like the reference's own float32 `rfft` of the kernel
     (_fftconv.py:123-124): same 4e-6 of the float64 convolution as the host-float64 spectra of the smaller blocks."""
     from scipy.signal import fftconvolve
     rng = np.random.default_rng(K + T)

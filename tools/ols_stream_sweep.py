@@ -31,7 +31,6 @@ for slab in [int(v) for v in os.environ.get('SWEEP_SLABS', '8,16,32,64,128,256,1
     row = []
     for streams in [int(v) for v in os.environ.get('SWEEP_STREAMS', '2,3,4,6,8').split(',')]:
         os.environ["TFX_OLS_SLAB_MB"] = str(slab)
-        os.environ["TFX_OLS_SLAB_MIN_MB"] = str(min(slab, 64))
         os.environ["TFX_OLS_PAIRS_PER_SLAB"] = str(max(1, slab // 8))
         os.environ["TFX_OLS_STREAMS"] = str(streams)
         row.append(f"{streams} streams {wall():6.3f}")

@@ -45,14 +45,12 @@ def main():
         print("plan", E.sos_plan_info(sos))
         for prec in ("f64", "f32"):
             for var in (0, 1, 2, 3, 4, 5):
-                for wpc in (0, 8):
-                    os.environ["TFX_SOS_VARIANT"] = str(var)
-                    os.environ["TFX_SOS_WAVES_PER_CU"] = str(wpc)
-                    wall, prof = timed(lambda: E.sos_forward(x, None, sos_t, None, None, precision=prec))
-                    ms = list(prof.values())[0]
-                    print(f"sos {prec} var={var} waves/cu={wpc:2d}: kernel {ms:7.3f} ms  wall {wall:7.3f} ms  "
-                          f"{C * T / ms / 1e3:9.1f} Msamp/s  {8 * C * T / ms / 1e9:6.2f} TB/s ({8 * C * T / ms / 1e9 / 8 * 100:5.1f}% of 8 TB/s)",
-                          flush=True)
+                os.environ["TFX_SOS_VARIANT"] = str(var)
+                wall, prof = timed(lambda: E.sos_forward(x, None, sos_t, None, None, precision=prec))
+                ms = list(prof.values())[0]
+                print(f"sos {prec} var={var}: kernel {ms:7.3f} ms  wall {wall:7.3f} ms  "
+                      f"{C * T / ms / 1e3:9.1f} Msamp/s  {8 * C * T / ms / 1e9:6.2f} TB/s ({8 * C * T / ms / 1e9 / 8 * 100:5.1f}% of 8 TB/s)",
+                      flush=True)
         del x
     if "fir" in which:
         C, T = 64, 2_880_000

@@ -1,11 +1,13 @@
 // Where does the direct-FIR kernel's time go?  Runs the library's own kernel (included from
-// torchfx_amd/csrc/fir.hip) with the output stores and/or the global loads compiled out.
+// torchfx_amd/csrc/fir.hip) in the shape the library launches (NJ = FIR_NJ, grid rounded to the eight XCDs) with the
+// output stores and/or the global loads compiled out.
 #include "../../torchfx_amd/csrc/fir.hip"
 namespace tfx {
 void set_last_error(const std::string &) {}
 bool prof_on() { return false; }
 void prof_begin(const char *, hipStream_t) {}
 void prof_end(hipStream_t) {}
+int64_t env_i64(const char *, int64_t dflt) { return dflt; }
 }  // namespace tfx
 using namespace tfx;
 
@@ -17,14 +19,15 @@ static void run(const char *name, const float *x, float *y, const float *k, int6
     const size_t shmem = (((XW_PAD + 3) & ~3) + 31 + FIR_KC + 33) * sizeof(float);
     hipFuncSetAttribute((const void *)fir_direct_mfma_kernel<FIR_KC, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     const int64_t tiles = (T + FIR_NOUT - 1) / FIR_NOUT;
+    const unsigned grid = (unsigned)((C * tiles + 7) / 8 * 8);
     hipEvent_t a, b;
     hipEventCreate(&a);
     hipEventCreate(&b);
     float best = 1e9;
     for (int rep = 0; rep < 6; ++rep) {
         hipEventRecord(a);
-        hipLaunchKernelGGL((fir_direct_mfma_kernel<FIR_KC, DBG>), dim3((unsigned)(C * tiles)), dim3(256), shmem, 0, x, y, k, C, T, K,
-                           (K + FIR_KC - 1) / FIR_KC, tiles);
+        hipLaunchKernelGGL((fir_direct_mfma_kernel<FIR_KC, DBG>), dim3(grid), dim3(256), shmem, 0, x, y, k, C, T, K,
+                           (K + FIR_KC - 1) / FIR_KC, tiles, (const float *)nullptr, 0);
         hipEventRecord(b);
         hipEventSynchronize(b);
         float ms;

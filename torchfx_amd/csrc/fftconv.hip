@@ -329,14 +329,14 @@ void fft_conv_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, c
 // (_ops.py:119-176 with state None -> iir_cpu.cpp:64-159), its result rounded to float32 (iir.py:84-184, the downcast), then
 // fft_conv1d (_fftconv.py:70-141) -- the cascade runs inside the forward column pass (olsnative.hip), no pass of its own.
 // Warm-up of a row's recursion inside the column pass: the state a row starts from is the true one to 2^-bits of the
-// state's scale (TFX_OLS_SOS_HALO_BITS, default 40 = 9e-13: 1/20 of the 2e-11 the section-by-section parity tests state
+// state's scale (40 bits = 9e-13: 1/20 of the 2e-11 the section-by-section parity tests state
 // (tests/gpu_common.py TOL_IIR_F64OUT) and 5 orders below the float32 rounding the samples get next; round 5 ran 48, 3.6e-15:
 // +0.15 ms per chain step for digits no test can read, profiles/r05_experiments.txt section 6; the stand-alone cascade kernel
 // uses 60).  Cached by coefficient content: the analysis is a few dozen
 // long-double matrix products.
 static int64_t fused_warmup(const double *sos_host, int64_t Ksos)
 {
-    const int bits = (int)std::max<int64_t>(20, std::min<int64_t>(60, env_i64("TFX_OLS_SOS_HALO_BITS", 40)));
+    constexpr int bits = 40;
     return *g_warmups.get(sos_host, (size_t)(6 * Ksos) * sizeof(double), {bits}, nullptr,
                           [&] { return std::make_shared<int64_t>(sos_warmup_bits(sos_host, Ksos, bits)); });
 }

@@ -12,9 +12,9 @@
 //     out(i,j) = y[nb + 32 i + j] = sum_s  A[i][s] * B[s][j]
 //     A[i][s] = xw[32 i + s]          (signal window, LDS, rows padded 32->33 floats)
 //     B[s][j] = kpad[s - j + 31]      (taps, Toeplitz, LDS, 31 zeros in front)
-// Each wave owns NJ = 4 output tiles of 32x32 = 1024 consecutive samples and re-uses every B
-// fragment across them; a workgroup (4 waves) covers 16384 outputs of one channel per pass and
-// walks the taps in chunks of <= 1024 so the LDS window stays bounded for any K.
+// Each wave owns NJ output tiles of 32x32 = 1024 consecutive samples and re-uses every B fragment
+// across them; a workgroup (4 waves) covers 4 x NJ x 1024 outputs of one channel per pass and walks
+// the taps in chunks of <= 1024 so the LDS window stays bounded for any K.
 //
 // float64 signals (the reference computes conv1d in the input dtype) use a plain LDS-tiled
 // vector kernel: rare path, correctness first.
@@ -43,21 +43,21 @@ void fir_clear() { g_taps.clear(); }
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
-constexpr int FIR_NJ = 4;                       // 32x32 tiles per wave
-constexpr int FIR_WOUT = FIR_NJ * 1024;         // outputs per wave
-constexpr int FIR_NOUT = 4 * FIR_WOUT;          // outputs per workgroup
+constexpr int FIR_NJ = 1;                       // 32x32 tiles per wave
+constexpr int FIR_NOUT = 4 * FIR_NJ * 1024;     // outputs per workgroup
 constexpr int FIR_KC_MAX = 1024;                // largest tap chunk (taps are zero-padded to it)
+constexpr int64_t FIR_MFMA_MIN_T = 4096;        // float32 rows shorter than this run the plain kernel
 
 __device__ __forceinline__ int xpad33(int m) { return m + (m >> 5); }
 
 // kf_dev: [Kpad] flipped taps on device, zero-padded to a multiple of FIR_KC_MAX
 // FIR_KC: taps per chunk (128 / 512 / 1024 -- short filters do not pay for 1024-tap chunks).
 // DBG (tools/ubench/fir_probe.hip only): bit 0 drops the output stores, bit 1 the global loads.
-// NJ = 32x32 output tiles per wave (TFX_FIR_NJ): 4 = 16384 outputs and a 76 KB window per workgroup, two workgroups per
-// CU (rounds 1-2); 2 = 8192 outputs, 43 KB, three per CU; 1 = 4096 outputs, 26 KB, five per CU (default).  With two
-// workgroups per CU, both fill their window, multiply and store in lockstep, so the matrix pipe idles during every fill
-// and store; more, smaller workgroups interleave those phases: cfg 3 2.86 / 2.77 / 2.73 ms for NJ = 4 / 2 / 1 on one box
-// (profiles/r03_fir.txt; NJ = 1 at six waves per SIMD spills 36 B and is back to 2.78).
+// NJ = 32x32 output tiles per wave; the library launches NJ = FIR_NJ = 1: 4096 outputs and a 26 KB window per workgroup,
+// five per CU.  NJ = 4 (16384 outputs, 76 KB, two per CU; rounds 1-2) and NJ = 2 (8192 outputs, 43 KB, three per CU) were
+// slower: with two workgroups per CU, both fill their window, multiply and store in lockstep, so the matrix pipe idles
+// during every fill and store; more, smaller workgroups interleave those phases: cfg 3 2.86 / 2.77 / 2.73 ms for
+// NJ = 4 / 2 / 1 on one box (profiles/r03_fir.txt; NJ = 1 at six waves per SIMD spills 36 B and is back to 2.78).
 template <int FIR_KC, int DBG = 0, int NJ = FIR_NJ>
 __global__ void __launch_bounds__(256, NJ == 4 ? 2 : (NJ == 2 ? 3 : 5))
 fir_direct_mfma_kernel(const float *__restrict__ x, float *__restrict__ y,
@@ -287,18 +287,15 @@ void fir_direct_forward(const void *x, void *y, int dtype, int64_t C, int64_t T,
     const int64_t Kpad = ceil_div(K, FIR_KC_MAX) * FIR_KC_MAX;
     const std::shared_ptr<DeviceBuffer> taps = cached_taps(kernel_host, (size_t)K * esz, (size_t)Kpad * esz);   // held until launched
     const void *kdev = taps->p;
-    // rows much shorter than one 16384-sample MFMA tile (streaming chunks): the plain LDS-tiled kernel
-    // has 1024-sample tiles and finishes in a few microseconds instead of a full tile's ~60
+    // rows shorter than FIR_MFMA_MIN_T (streaming chunks; measured when an MFMA tile was 16384 samples, NJ = 4): the plain
+    // LDS-tiled kernel has 1024-sample tiles and finishes in a few microseconds instead of a full tile's ~60
     // ... and so does any job whose 1024-sample tiles are all resident at once (8 workgroups per CU): one round of
-    // the plain kernel costs ~40 clocks per tap, one MFMA workgroup walks its 16384-sample tile for ~128 clocks per
+    // the plain kernel costs ~40 clocks per tap, one NJ = 4 MFMA workgroup walked its 16384-sample tile for ~128 clocks per
     // tap -- the MFMA kernel wins on throughput (2.5 x), not on latency (streaming chunks, 64 x 4096 and the like)
     const bool few_tiles = C * ceil_div(T, (int64_t)1024) <= env_i64("TFX_FIR_ONE_ROUND_TILES", 2048);   // 0: MFMA whenever T allows (tests)
-    const bool short_rows = dtype == TFX_F32 && (T < env_i64("TFX_FIR_MFMA_MIN_T", FIR_NOUT / 4) || few_tiles);
+    const bool short_rows = dtype == TFX_F32 && (T < env_i64("TFX_FIR_MFMA_MIN_T", FIR_MFMA_MIN_T) || few_tiles);
     if (dtype == TFX_F32 && !short_rows) {
-        const int njv = (int)env_i64("TFX_FIR_NJ", 1);
-        const int nj = (njv == 2 || njv == 4) ? njv : 1;
-        const int nout = 4 * nj * 1024;
-        const int64_t tiles = ceil_div(T, nout);
+        const int64_t tiles = ceil_div(T, FIR_NOUT);
         TFX_CHECK(C * tiles < (1ll << 31), "fir_direct_forward: grid too large");
         // chunk size: cost per chunk ~ (KC+32)/32 contraction blocks + ~4 blocks' worth of refill
         int kc = 1024;
@@ -313,11 +310,11 @@ void fir_direct_forward(const void *x, void *y, int dtype, int64_t C, int64_t T,
         }
         const int nchunks = (int)ceil_div(K, kc);
         auto launch = [&](auto kern, int KC) {
-            const int XW = nout + KC + 32;
+            const int XW = FIR_NOUT + KC + 32;
             const int XW_PAD = XW + (XW >> 5) + 1;
             const size_t shmem = (((XW_PAD + 3) & ~3) + 31 + KC + 33) * sizeof(float);
-            static bool attr_done[TFX_MAX_DEVICES][9] = {};
-            bool &done = attr_done[current_device()][(KC == 128 ? 0 : (KC == 512 ? 1 : 2)) + (nj == 2 ? 3 : (nj == 1 ? 6 : 0))];
+            static bool attr_done[TFX_MAX_DEVICES][3] = {};
+            bool &done = attr_done[current_device()][KC == 128 ? 0 : (KC == 512 ? 1 : 2)];
             if (!done) {
                 TFX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
                 done = true;
@@ -327,17 +324,9 @@ void fir_direct_forward(const void *x, void *y, int dtype, int64_t C, int64_t T,
                                (float *)y, (const float *)kdev, C, T, (int)K, nchunks, tiles, (const float *)hist, (int)H);
             TFX_HIP(hipGetLastError());
         };
-        if (nj == 1) {
-            if (kc == 128) launch(fir_direct_mfma_kernel<128, 0, 1>, 128);
-            else if (kc == 512) launch(fir_direct_mfma_kernel<512, 0, 1>, 512);
-            else launch(fir_direct_mfma_kernel<1024, 0, 1>, 1024);
-        } else if (nj == 2) {
-            if (kc == 128) launch(fir_direct_mfma_kernel<128, 0, 2>, 128);
-            else if (kc == 512) launch(fir_direct_mfma_kernel<512, 0, 2>, 512);
-            else launch(fir_direct_mfma_kernel<1024, 0, 2>, 1024);
-        } else if (kc == 128) launch(fir_direct_mfma_kernel<128, 0>, 128);
-        else if (kc == 512) launch(fir_direct_mfma_kernel<512, 0>, 512);
-        else launch(fir_direct_mfma_kernel<1024, 0>, 1024);
+        if (kc == 128) launch(fir_direct_mfma_kernel<128>, 128);
+        else if (kc == 512) launch(fir_direct_mfma_kernel<512>, 512);
+        else launch(fir_direct_mfma_kernel<1024>, 1024);
     } else {
         const int64_t tiles = ceil_div(T, 1024);
         TFX_CHECK(C * tiles < (1ll << 31), "fir_direct_forward: grid too large");

@@ -56,7 +56,7 @@ struct OlsGeom {
     int *nf_flag;      // cascade in pass A: [nframes], 1 = the recursion of this frame met a non-finite value (every slot written)
     int *nf_pair;      // plain pass A: [C] zeroed per call, or null: row c's first frame shares its transform with row c - 1's last and
                        // held a non-finite sample (only when a row has an odd number of frames)
-    int nt;            // nontemporal hints (TFX_OLS_NT, default 3): 1 = signal loads of pass A, 2 = signal stores of pass C -- the signal
+    int nt;            // nontemporal hints (the host passes 3): 1 = signal loads of pass A, 2 = signal stores of pass C -- the signal
                        // is read once and written once; chain step 7.98 -> 7.87 ms.  (The same hint on the workspace loads of
                        // passes B and C, their last use, changes nothing.)
 };

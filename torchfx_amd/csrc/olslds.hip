@@ -54,7 +54,7 @@ template <typename R> struct Geom {
     R ep_gain;
     int ep_scale, ep_clamp, ep_stat;
     double *ep_partial;   // [nframes]: one partial per frame
-    int nt;               // TFX_OLS_LDS_NT (default 2): 2 = the output is stored with the nontemporal hint (written once: 2-3 % on every
+    int nt;               // nontemporal hints (the host passes 2): 2 = the output is stored with the nontemporal hint (written once: 2-3 % on every
                           // block size; the same hint on the signal loads, whose overlap the XCD's L2 serves, changes nothing)
 };
 
@@ -695,9 +695,8 @@ bool olslds_supported(int64_t K, int dtype, int64_t L, int64_t *N_out)
     // so the smallest block that fits wins there ([2, 44100], 1500 taps: 8 us at 4096 points, 15 us at 8192)
     // from ~3300 taps the radix-4 kernel at 16 384 points overtakes it on long rows (4096 taps: 0.47 against 0.53 ms, 3000 taps:
     // 0.45 against 0.44) although it runs two workgroups per CU instead of four
-    const int64_t min16k = env_i64("TFX_OLS_LDS16K_MINK", 3400);
     const bool r4_long = dtype == TFX_F32 && lg == 0 && L >= 65536 && use16k == 1 && env_i64("TFX_OLS_LDS16K_R4", 1) >= 1 &&
-                         min16k > 0 && K >= min16k && K <= ldsfft::LDS16K / 2;
+                         K >= 3400 && K <= ldsfft::LDS16K / 2;
     if (r4_long) N = ldsfft::LDS16K;
     else if (can8k && (lg == 13 || (K >= min8k && (L >= 65536 || K > ldsfft::LDS_N / 2)))) N = ldsfft::LDS8K;
     else if (K >= 1 && K <= ldsfft::LDS_N / 2 && lg != 14 && lg != 13) N = ldsfft::LDS_N;
@@ -716,7 +715,7 @@ void olslds_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int elem_byt
 {
     const int64_t line = 128 / elem_bytes;
     const int64_t Tout = Tn + pl + pr - K + 1;
-    const bool align = (Tn % line == 0) && (Tout % line == 0) && env_i64("TFX_OLS_ALIGN", 1) != 0;
+    const bool align = (Tn % line == 0) && (Tout % line == 0);
     const int64_t lead = align ? (line - (pl % line)) % line : 0;
     int64_t S = N - (K + lead) + 1;
     if (align && S > 2 * line) S -= S % line;
@@ -735,7 +734,7 @@ static void olslds_typed(const R *x, R *y, int64_t C, int64_t Tn, const R *kf_ho
     g.hist = hist; g.H = hist ? H : 0;
     g.ep_gain = ep ? (R)ep->gain : (R)1; g.ep_scale = ep ? ep->scale : 0; g.ep_clamp = ep ? ep->clamp : 0;
     g.ep_stat = ep ? ep->stat_mode : -1; g.ep_partial = nullptr;
-    g.nt = (int)env_i64("TFX_OLS_LDS_NT", 2);
+    g.nt = 2;
     int64_t lead = 0, N = 0;
     TFX_CHECK(olslds_supported(K, sizeof(R) == 4 ? TFX_F32 : TFX_F64, Tn + pl + pr, &N), "olslds_forward: %lld taps are not for this path", (long long)K);
     olslds_geometry(K, Tn, pl, pr, (int)sizeof(R), N, &lead, &g.S);
@@ -778,7 +777,7 @@ static void olslds_typed(const R *x, R *y, int64_t C, int64_t Tn, const R *kf_ho
                 TFX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
                 cus_tab[dev] = std::max(8, cus / 8 * 8);      // one 1024-thread workgroup per CU
             }
-            const int64_t grid = std::max<int64_t>(8, std::min<int64_t>(env_i64("TFX_OLS_LDS16K_GRID", cus_tab[dev]) / 8 * 8, per_xcd * 8));
+            const int64_t grid = std::max<int64_t>(8, std::min<int64_t>(cus_tab[dev], per_xcd * 8));
             launch(ols_lds16k_kernel, ready[2][dev], "ols_lds16k_kernel", lds16k_bytes(), grid, 1024,
                    (const float *)x, (float *)y, (const v4f *)plan->buf.p, (const v2f *)plan->tw256, g, npairs, per_xcd);
             done = true;

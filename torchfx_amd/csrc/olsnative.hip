@@ -18,7 +18,7 @@
 //          frame_b's, only the first S = N-K+1 (valid) samples are stored      -> y
 //     Hp[k1][k2] = conj(FFT(kf_pad))[k1 + N1 k2] / N is precomputed once per filter: on the host in float64 for
 //     N = 2^16 / 2^18, ON THE DEVICE in float32 by this pipeline's own forward kernels for N = 2^20 / 2^21 (ols_rowspec4096_kernel, ols_rowspec8192_kernel;
-//     the reference's rfft of the kernel is float32 too, _fftconv.py:123-124; TFX_OLS_GPU_SPECTRUM=0: host float64).
+//     the reference's rfft of the kernel is float32 too, _fftconv.py:123-124).
 //   * every FFT is a Stockham autosort in registers + LDS -- radix 16 x 16 in the column passes (one
 //     LDS exchange), radix 16 x 16 x 4 / 16 x 16 x 16 in the row passes (two exchanges per direction),
 //     radix 4 for N2 = 256; layouts are chosen so all LDS accesses of the column passes are
@@ -36,7 +36,6 @@
 #include "../../include/torchfx_hip.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <future>
@@ -241,7 +240,7 @@ void olsnative_prewarm()
         ols_set_attributes(dev);
         if (want_lanes > 1) ols_make_lanes(dev, want_lanes);
         // the first raw hipMalloc + pageable host-to-device copy of a process set up the runtime's staging path (7-36 ms on the
-        // boxes of round 4, TFX_OLS_TRACE): done here once so that the first plan's table upload does not pay for it
+        // boxes of round 4): done here once so that the first plan's table upload does not pay for it
         void *p = nullptr;
         std::vector<char> h((size_t)1 << 20, 0);
         if (hipMalloc(&p, h.size()) == hipSuccess) {
@@ -271,28 +270,13 @@ void olsnative_wait_warm()
     }
 }
 
-// TFX_OLS_TRACE=1: host milliseconds of the set-up phases of a call on stderr (where the first call of a process goes)
-struct HostTrace {
-    bool on;
-    std::chrono::steady_clock::time_point t0;
-    HostTrace() : on(env_i64("TFX_OLS_TRACE", 0) != 0), t0(std::chrono::steady_clock::now()) {}
-    void mark(const char *what)
-    {
-        if (!on) return;
-        const auto t1 = std::chrono::steady_clock::now();
-        fprintf(stderr, "[tfx ols] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-        t0 = t1;
-    }
-};
-
 // a new filter costs device allocations, blocking uploads (and, for N = 2^20, two launches on `stream`)
 static NativePlanPtr build_native_plan(const float *kf, int64_t K, int64_t N, int64_t lead, hipStream_t stream)
 {
     NativePlanPtr pl = std::make_shared<NativePlan>();
     pl->N = N; pl->K = K; pl->N2 = (int)(N / OLS_N1);
-    HostTrace tr;
     const int N2 = pl->N2;
-    const bool dev_spectrum = (N2 == 4096 || N2 == 8192) && env_i64("TFX_OLS_GPU_SPECTRUM", 1) != 0;
+    const bool dev_spectrum = N2 == 4096 || N2 == 8192;
     if (!dev_spectrum) {
         // spectrum in float64 on the host: conj(FFT(kf zero-padded)) / N   (_fftconv.py:123-124,131 + irfft scaling)
         std::vector<double> re((size_t)N, 0.0), im((size_t)N, 0.0);
@@ -301,7 +285,6 @@ static NativePlanPtr build_native_plan(const float *kf, int64_t K, int64_t N, in
         // on 128-byte boundaries while the outputs stay unshifted
         for (int64_t i = 0; i < K; ++i) re[(size_t)(lead + i)] = (double)kf[i];
         host_fft(re, im);
-        tr.mark("  spectrum: host FFT");
         std::vector<cpx> hp((size_t)N);
         {
             const double inv_n = 1.0 / (double)N;                  // exact: N is a power of two
@@ -322,10 +305,8 @@ static NativePlanPtr build_native_plan(const float *kf, int64_t K, int64_t N, in
                 for (auto &t : th) t.join();
             }
         }
-        tr.mark("  spectrum: permute");
         pl->spectrum = std::make_unique<DeviceBuffer>(hp);
         pl->Hp = (cpx *)pl->spectrum->p;
-        tr.mark("  spectrum: upload");
     }
     {
         // all twiddle tables in ONE allocation and ONE copy (eight hipMalloc + hipMemcpy pairs cost 7-9 ms of the first call)
@@ -350,7 +331,6 @@ static NativePlanPtr build_native_plan(const float *kf, int64_t K, int64_t N, in
         pl->tables = std::make_unique<DeviceBuffer>(all);
         for (int i = 0; i < 8; ++i) *slots[i] = (cpx *)pl->tables->p + off[i];
     }
-    tr.mark("  twiddle tables");
     if (dev_spectrum) {
         // N = 2^20: the spectrum is computed by the pipeline's own kernels on the caller's stream (see ols_rowspec4096_kernel)
         pl->taps_dev = std::make_unique<DeviceBuffer>(kf, (size_t)K * sizeof(float));
@@ -374,7 +354,6 @@ static NativePlanPtr build_native_plan(const float *kf, int64_t K, int64_t N, in
         TFX_HIP(hipEventCreateWithFlags(&pl->ready, hipEventDisableTiming));
         TFX_HIP(hipEventRecord(pl->ready, stream));
         pl->ready_stream = stream;
-        tr.mark("  spectrum: device (2 launches)");
     }
     return pl;
 }
@@ -399,7 +378,7 @@ bool olsnative_supported(int64_t K, int64_t L, int64_t *N_out)
     const int64_t lg = env_i64("TFX_FFT_LOG2N", 0);
     if (lg == 16 || lg == 18 || lg == 20 || lg == 21) N = (int64_t)1 << lg;
     else if (lg != 0) return false;
-    else if (K < env_i64("TFX_OLS_NATIVE_MIN_K", 16)) return false;   // a handful of taps: use the direct kernel / rocFFT
+    else if (K < 16) return false;   // a handful of taps: use the direct kernel / rocFFT
     else if (4 * K <= (1 << 16)) {
         // 8193 ... 16 384 taps (below that the one-launch kernels serve): 2^16 points waste 12-25 % of a block on the overlap.  Rows of
         // 4 M samples and more take the 2^20-point block (16 x 28.8 M: 16 384 taps 2.20 -> 1.93 ms, 12 288: 2.07 -> 1.93, 8193: 1.98
@@ -407,17 +386,13 @@ bool olsnative_supported(int64_t K, int64_t L, int64_t *N_out)
         // 0.831, 9000: 0.850 -> 0.827); shorter rows are a handful of workgroups either way (profiles/r06_experiments.txt section 9)
         N = 1 << 16;
         if (K > 8192 && L >= 4 * ((int64_t)1 << 20)) N = (int64_t)1 << 20;
-        else if (K >= env_i64("TFX_OLS_N18_MINK", 9000) && L >= ((int64_t)1 << 21)) N = 1 << 18;
+        else if (K >= 9000 && L >= ((int64_t)1 << 21)) N = 1 << 18;
     }
     // rows shorter than 4 M samples: 2^18 points -- but from ~22 K taps the 2^20-point block wins there too once a row holds two
     // of them (64 x 2.88 M: 65 536 taps 1.01-1.07 -> 0.86 ms, 32 768 taps 0.92 -> 0.85, 23 000 taps 0.897 -> 0.852; at 22 000 taps
     // 0.820 against 0.855; r05 experiments section 11, r06 section 9)
-    else if (2 * K <= (1 << 18) && L < 4 * ((int64_t)1 << 20)) N = (K > env_i64("TFX_OLS_N20_MINK", 22528) && L >= ((int64_t)1 << 21)) ? ((int64_t)1 << 20) : (1 << 18);
-    else if (2 * K <= (1 << 20)) {
-        N = (int64_t)1 << 20;                            // long signals: 4x fewer blocks, less overlap
-        // 2^21 = 256 x 8192 on signals of at least four such blocks: half the overlap again (TFX_OLS_N21: 0 never)
-        if (env_i64("TFX_OLS_N21", 0) != 0 && K > 16384 && L >= ((int64_t)1 << 23)) N = (int64_t)1 << 21;
-    }
+    else if (2 * K <= (1 << 18) && L < 4 * ((int64_t)1 << 20)) N = (K > 22528 && L >= ((int64_t)1 << 21)) ? ((int64_t)1 << 20) : (1 << 18);
+    else if (2 * K <= (1 << 20)) N = (int64_t)1 << 20;   // long signals: 4x fewer blocks, less overlap
     else return false;
     if (N < 2 * K) return false;
     if (L < N) {                                        // signal shorter than one block
@@ -436,17 +411,16 @@ bool sos_unit_rows(const double *sos_host, int64_t K, double (*rows)[5]);     //
 
 bool olsnative_sos_supported(int64_t Ksos, int64_t warm, int64_t K, int64_t Tn, int64_t pl, int64_t pr, int force, int64_t *N_out)
 {
-    if (env_i64("TFX_OLS_SOS", 1) == 0) return false;
-    if (Ksos < 1 || Ksos > SOSF_MAXK || warm < 0 || warm > env_i64("TFX_OLS_SOS_MAXWARM", 4096)) return false;
+    if (Ksos < 1 || Ksos > SOSF_MAXK || warm < 0 || warm > 4096) return false;
     const int64_t L = Tn + pl + pr;
-    if (L < K || env_i64("TFX_OLS_ALIGN", 1) == 0) return false;
+    if (L < K) return false;
     int64_t N = (int64_t)1 << (force == 2 ? 21 : 20);       // force: 1 = the 2^20-point block, 2 = the 2^21-point block, whatever the row length
     if (force) { if (N < 2 * (K + 32)) return false; }
     else {
         if (!olsnative_supported(K, L, &N) || (N != ((int64_t)1 << 20) && N != ((int64_t)1 << 21))) return false;
         // rows of 8192 samples (N = 2^21) halve the warm-up share of the recursion pass: 9.7 against 10.1 ms on the cfg-5 chain
         // (the plain pipeline is 5 % slower at 2^21 and stays at 2^20; profiles/r05_experiments.txt section 8)
-        if (N == ((int64_t)1 << 20) && env_i64("TFX_OLS_SOS_N21", 1) != 0 && L >= ((int64_t)1 << 23) && 2 * (K + 32) <= ((int64_t)1 << 21))
+        if (N == ((int64_t)1 << 20) && L >= ((int64_t)1 << 23) && 2 * (K + 32) <= ((int64_t)1 << 21))
             N = (int64_t)1 << 21;
     }
     if (N_out) *N_out = N;
@@ -458,20 +432,18 @@ void olsnative_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int64_t N
 {
     const int64_t L = Tn + pl + pr, Tout = L - K + 1;
     (void)Tout;
-    const bool align = env_i64("TFX_OLS_ALIGN", 1) != 0;
-    const int64_t lead = align ? (32 - (pl % 32)) % 32 : 0;
+    const int64_t lead = (32 - (pl % 32)) % 32;
     int64_t S = N - (K + lead) + 1;
-    if (align && S > 64) S -= S % 32;
+    if (S > 64) S -= S % 32;
     if (S_out) *S_out = S;
     // rows that are not whole 128-byte lines shift their frame grid by up to 31 samples (row_shift): one more frame at most
-    if (F_out) *F_out = ceil_div(Tout + ((align && (Tn % 32 != 0)) ? 31 : 0), S);
+    if (F_out) *F_out = ceil_div(Tout + (Tn % 32 != 0 ? 31 : 0), S);
 }
 
 void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const float *kf_host, int64_t K,
                        int64_t pl, int64_t pr, int64_t N, hipStream_t stream, const float *hist, int64_t H, const Epilogue *ep,
                        const SosFuseHost *sosf)
 {
-    HostTrace tr;
     // the plan cache, the one-time function attributes and the creation of the internal streams each take a lock of their own;
     // the launches themselves are not serialised, so two host threads that drive two streams overlap (each stream has its own
     // scratch slabs; the internal lanes are shared and ordered by the fork / join events)
@@ -489,16 +461,14 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
     // Rows that are not whole lines (Tn % 32 != 0, or x starting inside a line) keep this: row c's frame grid is moved left by
     // sh(c) samples (row_shift) so that its frames start on lines of MEMORY; the column passes address the same way, only the
     // first and the last line of a row are partial.
-    int64_t lead = 0;
-    const bool align = env_i64("TFX_OLS_ALIGN", 1) != 0;
-    if (align) lead = (32 - (pl % 32)) % 32;
+    const int64_t lead = (32 - (pl % 32)) % 32;
     g.sh_base = (int)(((uintptr_t)x >> 2) & 31);
-    g.sh_on = (align && (Tn % 32 != 0 || g.sh_base != 0)) ? 1 : 0;
+    g.sh_on = (Tn % 32 != 0 || g.sh_base != 0) ? 1 : 0;
     g.nf_flag = nullptr;
     g.nf_pair = nullptr;
     g.pad_left = pl + lead;
     g.S = N - (K + lead) + 1;
-    if (align && g.S > 64) g.S -= g.S % 32;
+    if (g.S > 64) g.S -= g.S % 32;
     const int dev = current_device();
     // first call on this device: kernel attributes (code-object load) and the internal streams are set up on a helper thread
     // while this thread computes the spectrum (both are tens of milliseconds, one bound by the driver, one by the host's cores);
@@ -528,11 +498,10 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
     }
     if (plan_err) std::rethrow_exception(plan_err);
     if (plan->ready && plan->ready_stream != stream) TFX_HIP(hipStreamWaitEvent(stream, plan->ready, 0));   // spectrum computed on another stream
-    tr.mark("plan (spectrum, tables)");
     g.F = ceil_div(g.Tout + g.out_shift + (g.sh_on ? 31 : 0), g.S);
     g.nframes = C * g.F; g.N2 = plan->N2;
     g.P2 = g.N2;
-    g.nt = (int)env_i64("TFX_OLS_NT", 3);
+    g.nt = 3;
     const int64_t npairs = ceil_div(g.nframes, 2);
     if (!sosf && C > 1 && (g.F & 1)) {     // some pair straddles two signal rows: see ols_col_fwd16_kernel
         g.nf_pair = (int *)scratch("olsn_nf_pair", (size_t)C * sizeof(int), stream);
@@ -595,23 +564,21 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
         if (slab <= 8) { (void)scratch(lane_tags[got], bytes, stream); break; }          // throws with the allocator's name in the message
         slab = std::max<int64_t>(8, slab / 2);
     }
-    tr.mark("workspaces");
     const size_t shm_col = OLS_SHM_COL;
     const size_t shm_row = (size_t)(g.N2 * 5) * sizeof(cpx);
     // XCD-aware row map (1) pays when a slab holds many pairs per spectrum row; with cache-sized slabs the plain map is faster
-    const int rowmap = (int)env_i64("TFX_OLS_ROWMAP", slab >= 32 ? 1 : 0);
-    const row_t rowk = row_tab[rowmap == 0 ? 0 : 1];
+    const int rowmap = slab >= 32 ? 1 : 0;
+    const row_t rowk = row_tab[rowmap];
     const bool row_r4 = env_i64("TFX_OLS_ROW_R4", 0) != 0;        // radix-4 row passes for N2 = 256 / 1024 (cross-check)
     ols_set_attributes(dev);
-    tr.mark("function attributes");
     const int ncb = g.N2 / OLS_CB;
     SosFuse sosk{};
     bool sos_unit = false;
     if (sosf) {
-        TFX_CHECK((g.N2 == 4096 || g.N2 == 8192) && align && !hist && sosf->K >= 1 && sosf->K <= SOSF_MAXK && sosf->warm >= 0,
+        TFX_CHECK((g.N2 == 4096 || g.N2 == 8192) && !hist && sosf->K >= 1 && sosf->K <= SOSF_MAXK && sosf->warm >= 0,
                   "olsnative_forward: the cascade cannot run inside the column pass here (olsnative_sos_supported)");
         g.nf_flag = (int *)scratch("olsn_nf_flag", (size_t)g.nframes * sizeof(int), stream);
-        sos_unit = env_i64("TFX_OLS_SOS_UNIT_B0", 1) != 0 && sos_unit_rows(sosf->sos, sosf->K, sosk.co);
+        sos_unit = sos_unit_rows(sosf->sos, sosf->K, sosk.co);
         for (int64_t s = 0; s < sosf->K && !sos_unit; ++s) {
             const double *co = sosf->sos + 6 * s;                 // b0 b1 b2 a0 a1 a2; a0 is not used (iir_cpu.cpp:86)
             sosk.co[s][0] = co[0]; sosk.co[s][1] = co[1]; sosk.co[s][2] = co[2]; sosk.co[s][3] = -co[4]; sosk.co[s][4] = -co[5];
@@ -631,12 +598,10 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
     hipStream_t user_stream = stream;
     if (nlanes > 1) {
         ols_make_lanes(dev, nlanes);
-        tr.mark("  lane streams / events");
         std::lock_guard<std::mutex> fl(lane_mu);
         TFX_HIP(hipEventRecord(ev_fork, user_stream));
         for (int i = 0; i < nlanes; ++i) TFX_HIP(hipStreamWaitEvent(lane_stream[i], ev_fork, 0));
     }
-    tr.mark("lanes, workspaces, fork");
     int64_t slab_idx = 0;
     for (int64_t p0 = 0; p0 < npairs; p0 += slab, ++slab_idx) {
         const int64_t np = (npairs - p0 < slab) ? (npairs - p0) : slab;
@@ -690,7 +655,6 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
             TFX_HIP(hipGetLastError());
         }
     }
-    tr.mark("launches");
     if (nlanes > 1) {
         std::lock_guard<std::mutex> jl(lane_mu);
         for (int i = 0; i < nlanes; ++i) {

@@ -936,22 +936,17 @@ static int device_cus()
 // Time segmentation.  Streams are persistent (one wavefront walks its whole segment), so the
 // launch should be exactly ONE resident round: nstreams <= CUs x resident waves, otherwise the
 // second round doubles the time.  `resident_waves_per_cu` comes from the occupancy query of the
-// kernel actually launched.  Segments shorter than TFX_SOS_MIN_SEG_OVER_WARM x warm-up are not
-// worth their halo.
+// kernel actually launched.  Segments shorter than 8 x warm-up are not worth their halo.
 static void plan_segments(SosParams &p, int64_t plan_warm, int TILE, int resident_waves_per_cu)
 {
     const int64_t tiles_total = ceil_div(p.T, TILE);
     int64_t nseg = 1, seg_len = tiles_total * TILE, warm = 0;
     const int force_nseg = (int)env_i64("TFX_SOS_NSEG", 0);
     if (plan_warm >= 0) {
-        {
-            // halo rounded to 1 KB of float32: streams start on cache-line boundaries; 256 measured 1.5-4 % faster
-            // than 32 on the float64 kernel (64 x 2.88 M / 10 M / 28.8 M), no difference beyond
-            const int64_t q = env_i64("TFX_SOS_WARM_ROUND", 256);         // samples; power of two >= 32
-            warm = (plan_warm + q - 1) & ~(q - 1);
-        }
-        const int wpc = (int)env_i64("TFX_SOS_WAVES_PER_CU", 0);
-        const int64_t capacity = (int64_t)device_cus() * (wpc > 0 ? wpc : resident_waves_per_cu);
+        // halo rounded to 1 KB of float32: streams start on cache-line boundaries; 256 measured 1.5-4 % faster
+        // than 32 on the float64 kernel (64 x 2.88 M / 10 M / 28.8 M), no difference beyond
+        warm = (plan_warm + 255) & ~(int64_t)255;
+        const int64_t capacity = (int64_t)device_cus() * resident_waves_per_cu;
         int64_t nseg_target = force_nseg > 0 ? force_nseg : capacity / p.C;      // floor: one round
         if (nseg_target < 1) nseg_target = 1;
         if (nseg_target > 1 && p.T > warm) {
@@ -960,7 +955,7 @@ static void plan_segments(SosParams &p, int64_t plan_warm, int TILE, int residen
             // costing every stream an extra, mostly discarded tile (+4 % at 64 x 2.88 M with 4096-sample tiles).
             int64_t seg_tiles = ceil_div(ceil_div(p.T - warm, nseg_target) + warm, TILE);
             if (force_nseg <= 0) {
-                const int64_t min_tiles = ceil_div(env_i64("TFX_SOS_MIN_SEG_OVER_WARM", 8) * warm, TILE);
+                const int64_t min_tiles = ceil_div(8 * warm, TILE);
                 if (seg_tiles < min_tiles) seg_tiles = min_tiles;
             }
             if (seg_tiles < 1) seg_tiles = 1;
@@ -1154,8 +1149,8 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in,
     p.x = x; p.y = y; p.taps = y_sections;
     p.sx_in = sx_in; p.sy_in = sy_in; p.sx_out = sx_out; p.sy_out = sy_out;
     p.C = C; p.C_in = C_in; p.T = T; p.K = (int)K; p.x_pitch = T;
-    p.nt = (int)env_i64("TFX_SOS_NT", 1);
-    p.fair = (int)env_i64("TFX_SOS_FAIR", 15);
+    p.nt = 1;
+    p.fair = 15;
     p.nsum = sum_bands ? (int)NB : 0;
     p.ep_gain = ep->gain; p.ep_scale = ep->scale; p.ep_clamp = ep->clamp; p.ep_stat = ep->stat_mode;
     p.ep_partial = nullptr; p.ep_host = ep;
@@ -1176,8 +1171,8 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in,
         else launch_main<float, float, float>(p, vec, variant, nstreams, stream);
     } else {
         // the shipping float32-in / float32-out geometry (LC = 64, aligned rows, no section taps) runs the unit-b0 form when the
-        // cascade has one (TFX_SOS_UNIT_B0=0: plain form)
-        if (LC == 64 && variant == 4 && vec && !p.taps && !sum_bands && x_dtype == TFX_F32 && y_dtype == TFX_F32 && env_i64("TFX_SOS_UNIT_B0", 1) != 0) {
+        // cascade has one (unit_form_ok); other cascades run the plain form
+        if (LC == 64 && variant == 4 && vec && !p.taps && !sum_bands && x_dtype == TFX_F32 && y_dtype == TFX_F32) {
             if (pl->unit_ok < 0) {
                 bool ok = true;
                 for (int b = 0; b < pl->NB && ok; ++b)
