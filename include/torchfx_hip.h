@@ -331,6 +331,36 @@ int tfx_delay_line_forward(const void *x, void *y, int dtype, int64_t C, int64_t
 int tfx_delay_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
                       const double *amps_host, double mix, int pingpong, const tfx_epilogue *epilogue,
                       tfx_stream_t stream);
+/* ---------------------------------------------------------------------------
+ * tfx_delay_stream_forward -- one chunk of a stateful (streaming) Delay, StatefulDelay in torchfx_amd/realtime.py.
+ * Each row's chunk continues the last H = taps*delay input samples of that row (hist_in):
+ *   v = [hist_in[r] | x[r]],  wet[n] = sum_{i=1..taps} amps[i-1] * src_v[H + n - i*delay]   (tap order, +0.0 start)
+ *   y[n] = lerp(x[n], wet[n], mix)   n in [0, T);   hist_out[r] = the newest H samples of v
+ * x DEVICE [rows, T] of dtype; y DEVICE [rows, T]; hist_in DEVICE [rows, H] or NULL (= silence: the first chunk);
+ * hist_out DEVICE [rows, H] (may be NULL only when rows*H = 0); neither y nor hist_out may overlap x, hist_in or each
+ * other (checked: the kernel reads the inputs and writes the outputs from different workgroups); amps and
+ * pingpong as for tfx_delay_forward (ping-pong rows read the partner row's history).  The outputs of consecutive chunks,
+ * followed by those of H zero samples (the ring-out), are bit-identical to tfx_delay_forward on the whole signal.
+ * T = 0 leaves y empty and copies the history.  One launch.  Arguments are checked before the device is touched (null
+ * pointers, taps < 1, delay < 0, negative sizes, odd rows with ping-pong, bad dtype, overlapping buffers, overflow of
+ * taps*delay).
+ * ------------------------------------------------------------------------- */
+int tfx_delay_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
+                             const double *amps_host, double mix, int pingpong, const void *hist_in, void *hist_out,
+                             tfx_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * tfx_delay_line_stream_forward -- one chunk of tfx_delay_line_forward over a continuous stream (StatefulReverb):
+ *   v = [hist_in[c] | x[c]],  y[c,n] = x[c,n] + (mix*decay) * v[c, n]   (v indexed from the start of hist_in),
+ *   hist_out[c] = the newest `delay` samples of v.
+ * x, y DEVICE [C, T]; hist_in DEVICE [C, delay] or NULL (= silence: the first `delay` outputs copy x, as the one-shot
+ * call leaves them); hist_out DEVICE [C, delay].  Neither y nor hist_out may overlap x, hist_in or each other (checked).
+ * Same arithmetic as tfx_delay_line_forward.
+ * One launch; arguments are checked before the device is touched.
+ * ------------------------------------------------------------------------- */
+int tfx_delay_line_stream_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int64_t delay, double decay,
+                                  double mix, const void *hist_in, void *hist_out, tfx_stream_t stream);
+
 /* the kernel tfx_delay_forward picks (host-only): 0 = span (taps*delay + tile staged in LDS), 1 = lattice (long delay,
  * taps <= 8, residue classes with a register ring), 2 = gather (anything else, every tap a global load) */
 int tfx_delay_plan_info(int64_t delay, int64_t taps, int dtype, int pingpong, int *regime);

@@ -59,6 +59,8 @@ SIGNATURES = {
     "tfx_env_reload": (_int, []),
     "tfx_delay_line_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _dbl, _dbl, _vp]),
     "tfx_delay_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _vp, _dbl, _int, _vp, _vp]),
+    "tfx_delay_stream_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _vp, _dbl, _int, _vp, _vp, _vp]),
+    "tfx_delay_line_stream_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _dbl, _dbl, _vp, _vp, _vp]),
     "tfx_delay_plan_info": (_int, [_i64, _i64, _int, _int, ctypes.POINTER(_int)]),
     "tfx_sum_forward": (_int, [_vp, _int, _vp, _int, _i64, _vp]),
     "tfx_gain_forward": (_int, [_vp, _vp, _int, _i64, _dbl, _int, _vp]),

@@ -62,11 +62,19 @@ void normalize_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, 
 void sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, hipStream_t stream);
 void delay_line_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int64_t delay, double coeff,
                         hipStream_t stream);
+void delay_line_stream_check(const void *x, const void *y, int dtype, int64_t C, int64_t T, int64_t delay, const void *hist_in,
+                             const void *hist_out);
+void delay_line_stream_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int64_t delay, double coeff,
+                               const void *hist_in, void *hist_out, hipStream_t stream);
 // delay.hip
 void delay_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
                  const double *amps_host, double mix, int pingpong, const Epilogue *ep);
 void delay_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
                    const double *amps_host, double mix, int pingpong, const Epilogue *ep, hipStream_t stream);
+void delay_stream_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
+                        const double *amps_host, double mix, int pingpong, const void *hist_in, const void *hist_out);
+void delay_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
+                          const double *amps_host, double mix, int pingpong, const void *hist_in, void *hist_out, hipStream_t stream);
 int delay_regime(int64_t D, int64_t taps, int esz, int pingpong);
 void delay_clear();
 // layout.hip
@@ -576,6 +584,26 @@ int tfx_delay_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T
     const Epilogue ep = to_epilogue(epilogue);
     delay_check(x, y, dtype, rows, T, delay, taps, amps_host, mix, pingpong, &ep);     // before anything touches the device
     delay_forward(x, y, dtype, rows, T, delay, taps, amps_host, mix, pingpong, &ep, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_delay_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
+                             const double *amps_host, double mix, int pingpong, const void *hist_in, void *hist_out,
+                             tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    // checked before anything touches the device
+    delay_stream_check(x, y, dtype, rows, T, delay, taps, amps_host, mix, pingpong, hist_in, hist_out);
+    delay_stream_forward(x, y, dtype, rows, T, delay, taps, amps_host, mix, pingpong, hist_in, hist_out, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_delay_line_stream_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int64_t delay, double decay,
+                                  double mix, const void *hist_in, void *hist_out, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    delay_line_stream_check(x, y, dtype, C, T, delay, hist_in, hist_out);        // before anything touches the device
+    delay_line_stream_forward(x, y, dtype, C, T, delay, mix * decay, hist_in, hist_out, (hipStream_t)stream);
     TFX_API_END
 }
 

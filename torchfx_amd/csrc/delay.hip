@@ -372,6 +372,144 @@ void delay_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, i
     else delay_launch<double>(x, y, rows, T, delay, taps, amps_host, mix, pingpong, e, stream);
 }
 
+// ---- streaming (StatefulDelay) ----------------------------------------------------------------------------------------
+// One chunk of a continuous stream.  The chunk's rows sit behind the last H = taps*D input samples of each row (hist_in,
+// null = silence); on that virtual row v = [hist_in | x] the chunk's outputs are the one-shot kernels' outputs at the
+// chunk's positions, and flushing H zero samples gives the tail:
+//   wet[n] = sum_{i=1..taps} a_i * src(n - i*D),  src(m) = m >= 0 ? x[m] : hist_in[H + m]   (n in [0, T), tap order)
+//   y[n]   = lerp(x[n], wet[n], w);   hist_out = the newest H samples of v
+// Exactness against the one-shot call on the whole signal: the wet sum starts at +0.0, and a history sample that stands for
+// "before the signal" (silence at the start of the stream, or the zero chunk of a flush) adds fl(+0.0 * a_i) = +0.0 (a_i >= 0);
+// a sum that starts at +0.0 is never -0.0 under round-to-nearest, and v + (+0.0) = v for every other v (NaN and Inf
+// included), so those terms leave the bits of the sum where the one-shot kernel, which skips them, leaves them.  Every
+// other term, the product rounding (contract(off) above) and lerp_mix are the one-shot kernels'.
+// Regime: one coalesced gather kernel for every chunk size.  In the real-time regime (T <= D) each tap's sources are one
+// contiguous run of the history, so reading taps*T samples and writing T is the floor; for T >> D the re-reads of a
+// tap (taps*D samples behind) are served by L2, because the tiles of a row run in order on one XCD (xcd_contiguous, applied
+// to the output tiles alone so that all eight XCDs share them however large the history is).
+// The launch carries a second role: the workgroups past the output tiles write hist_out (no second launch).
+constexpr int DLY_STR_E = 4;                               // history elements per thread
+constexpr int64_t DLY_STR_OTILE = DLY_THREADS, DLY_STR_HTILE = (int64_t)DLY_THREADS * DLY_STR_E;
+
+template <typename T> struct DelayStreamArgs {
+    const T *x, *hist_in;       // [rows, T], [rows, H] or null
+    T *y, *hist_out;            // [rows, T], [rows, H]
+    int64_t T_, H, D;
+    int taps;
+    T w;
+    int64_t otiles, htiles;     // output / history tiles per row
+    int64_t rows, nwg;
+    const double *a_dev;
+    double a[DLY_ARG_AMPS];
+};
+
+template <typename T> __device__ __forceinline__ T amp(const DelayStreamArgs<T> &p, int i)
+{
+    return (T)(p.a_dev ? p.a_dev[i - 1] : p.a[i - 1]);
+}
+
+template <typename T, bool PP>
+__global__ void __launch_bounds__(DLY_THREADS) delay_stream_kernel(const DelayStreamArgs<T> p)
+{
+    const int64_t n_out = p.rows * p.otiles;
+    if ((int64_t)blockIdx.x < n_out) {
+        // the output tiles are the first n_out blocks, remapped among themselves: every XCD gets a contiguous run of them
+        const int64_t lid = xcd_contiguous(blockIdx.x, n_out);
+        const int64_t row = lid / p.otiles, tile = lid % p.otiles;
+        const int c = PP ? (int)(row & 1) : 0;
+        const int64_t srow = PP ? (row ^ 1) : row;             // ping-pong: the partner row feeds this one
+        const T *src = p.x + srow * p.T_;
+        const T *hsrc = p.hist_in ? p.hist_in + srow * p.H + p.H : nullptr;     // hsrc[m], m in [-H, 0)
+        const int64_t n = tile * DLY_STR_OTILE + threadIdx.x;
+        if (n >= p.T_) return;
+        T wet = (T)0;
+        for (int i = 1; i <= p.taps; ++i) {
+            if (PP && ((i & 1) != c)) continue;                  // odd taps -> row 1, even taps -> row 0
+            const int64_t m = n - (int64_t)i * p.D;
+            if (m >= 0) wet = wet + src[m] * amp(p, i);
+            else if (hsrc) wet = wet + hsrc[m] * amp(p, i);
+        }
+        p.y[row * p.T_ + n] = lerp_mix(p.x[row * p.T_ + n], wet, p.w);
+        return;
+    }
+    // second role: hist_out[row, j] = v[T + j], v = [hist_in | x] of the row
+    const int64_t g = (int64_t)blockIdx.x - n_out, row = g / p.htiles, tile = g % p.htiles;
+    const T *xr = p.x + row * p.T_;
+    const T *hr = p.hist_in ? p.hist_in + row * p.H : nullptr;
+    T *ho = p.hist_out + row * p.H;
+#pragma unroll
+    for (int e = 0; e < DLY_STR_E; ++e) {
+        const int64_t j = tile * DLY_STR_HTILE + e * DLY_THREADS + threadIdx.x;
+        if (j >= p.H) break;
+        const int64_t v = p.T_ + j;
+        ho[j] = v >= p.H ? xr[v - p.H] : (hr ? hr[v] : (T)0);
+    }
+}
+
+// [a, a + na) and [b, b + nb) share no byte (null pointers and empty ranges share none)
+static bool stream_disjoint(const void *a, size_t na, const void *b, size_t nb)
+{
+    if (!a || !b || !na || !nb) return true;
+    const char *p = (const char *)a, *q = (const char *)b;
+    return p + na <= q || q + nb <= p;
+}
+
+void delay_stream_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
+                        const double *amps_host, double mix, int pingpong, const void *hist_in, const void *hist_out)
+{
+    TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "delay_stream_forward: bad dtype %d", dtype);
+    TFX_CHECK(taps >= 1, "delay_stream_forward: taps must be at least 1, got %lld", (long long)taps);
+    TFX_CHECK(delay >= 0, "delay_stream_forward: negative delay %lld", (long long)delay);
+    TFX_CHECK(rows >= 0 && T >= 0, "delay_stream_forward: negative size");
+    TFX_CHECK(!pingpong || rows % 2 == 0, "delay_stream_forward: ping-pong needs an even number of rows, got %lld", (long long)rows);
+    TFX_CHECK(amps_host, "delay_stream_forward: null amplitudes");
+    TFX_CHECK(delay == 0 || taps <= (INT64_MAX / 4) / delay, "delay_stream_forward: taps*delay overflows");
+    TFX_CHECK(mix == mix, "delay_stream_forward: NaN mix");
+    const int64_t H = taps * delay;
+    TFX_CHECK(rows == 0 || (T <= INT64_MAX / 4 / rows && H <= INT64_MAX / 4 / rows), "delay_stream_forward: size overflows");
+    TFX_CHECK((x || rows * T == 0) && (y || rows * T == 0) && (hist_out || rows * H == 0), "delay_stream_forward: null pointer");
+    const size_t esz = dtype == TFX_F32 ? 4 : 8, xb = (size_t)(rows * T) * esz, hb = (size_t)(rows * H) * esz;
+    TFX_CHECK(stream_disjoint(hist_in, hb, hist_out, hb), "delay_stream_forward: the new history needs its own buffer");
+    TFX_CHECK(stream_disjoint(y, xb, x, xb) && stream_disjoint(y, xb, hist_in, hb) && stream_disjoint(hist_out, hb, x, xb) &&
+                  stream_disjoint(y, xb, hist_out, hb),
+              "delay_stream_forward: y and hist_out may not overlap x, hist_in or each other");
+}
+
+template <typename T>
+static void delay_stream_launch(const void *x, void *y, int64_t rows, int64_t T_, int64_t D, int64_t taps, const double *amps_host,
+                                double mix, int pingpong, const void *hist_in, void *hist_out, hipStream_t stream)
+{
+    DelayStreamArgs<T> p{};
+    p.x = (const T *)x; p.y = (T *)y; p.hist_in = (const T *)hist_in; p.hist_out = (T *)hist_out;
+    p.T_ = T_; p.D = D; p.taps = (int)taps; p.H = taps * D; p.w = (T)mix; p.rows = rows;
+    std::shared_ptr<DeviceBuffer> amps_dev;
+    if (taps > DLY_ARG_AMPS) {
+        const int64_t tail[1] = {taps};
+        amps_dev = g_amps.get(amps_host, (size_t)taps * sizeof(double), tail, stream,
+                              [&] { return std::make_shared<DeviceBuffer>(amps_host, (size_t)taps * sizeof(double)); });
+        p.a_dev = (const double *)amps_dev->p;
+    } else {
+        for (int64_t i = 0; i < taps; ++i) p.a[i] = amps_host[i];
+    }
+    p.otiles = ceil_div(T_, DLY_STR_OTILE);
+    p.htiles = ceil_div(p.H, DLY_STR_HTILE);
+    p.nwg = rows * (p.otiles + p.htiles);
+    if (p.nwg == 0) return;
+    TFX_CHECK(p.nwg < (1ll << 31), "delay_stream_forward: grid too large");
+    ProfScope ps("delay_stream_kernel", stream);
+    if (pingpong) hipLaunchKernelGGL((delay_stream_kernel<T, true>), dim3((unsigned)p.nwg), dim3(DLY_THREADS), 0, stream, p);
+    else hipLaunchKernelGGL((delay_stream_kernel<T, false>), dim3((unsigned)p.nwg), dim3(DLY_THREADS), 0, stream, p);
+    TFX_HIP(hipGetLastError());
+}
+
+void delay_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
+                          const double *amps_host, double mix, int pingpong, const void *hist_in, void *hist_out, hipStream_t stream)
+{
+    delay_stream_check(x, y, dtype, rows, T, delay, taps, amps_host, mix, pingpong, hist_in, hist_out);
+    if (dtype == TFX_F32) delay_stream_launch<float>(x, y, rows, T, delay, taps, amps_host, mix, pingpong, hist_in, hist_out, stream);
+    else delay_stream_launch<double>(x, y, rows, T, delay, taps, amps_host, mix, pingpong, hist_in, hist_out, stream);
+}
+
 void delay_clear() { g_amps.clear(); }
 
 }  // namespace tfx

@@ -292,6 +292,91 @@ void delay_line_forward(const void *x, void *y, int dtype, int64_t C, int64_t T,
     TFX_HIP(hipGetLastError());
 }
 
+// ---- delay line, streaming (StatefulReverb) ---------------------------------------------------------------------------
+// One chunk of a continuous stream: the D samples of each row that precede the chunk come from hist_in (null = silence),
+//   y[n] = x[n] + coeff * v[n - D],  v = [hist_in | x];   hist_out = the newest D samples of v.
+// Same expression as delay_line_kernel, in this file and under the same contraction setting, so a chunk's samples are the
+// one-shot kernel's bits; with hist_in null the first D outputs are copies of x, as the one-shot kernel leaves them.  The
+// workgroups past the output tiles write hist_out (one launch per chunk).  Scalar loads: rows of any alignment.
+constexpr int EFX_STR_E = 4;                               // samples per thread
+constexpr int64_t EFX_STR_TILE = (int64_t)EFX_THREADS * EFX_STR_E;
+
+template <typename T>
+__global__ void __launch_bounds__(EFX_THREADS)
+delay_line_stream_kernel(const T *__restrict__ x, const T *__restrict__ hist_in, T *__restrict__ y, T *__restrict__ hist_out,
+                         int64_t rows, int64_t T_, int64_t D, int64_t otiles, int64_t htiles, T coeff)
+{
+    const int64_t n_out = rows * otiles;
+    const int64_t id = blockIdx.x;
+    if (id < n_out) {
+        const int64_t row = id / otiles, tile = id % otiles;
+        const T *xr = x + row * T_;
+        const T *hr = hist_in ? hist_in + row * D : nullptr;
+        T *yr = y + row * T_;
+#pragma unroll
+        for (int e = 0; e < EFX_STR_E; ++e) {
+            const int64_t n = tile * EFX_STR_TILE + e * EFX_THREADS + threadIdx.x;
+            if (n >= T_) break;
+            T v = xr[n];
+            if (n >= D) v += coeff * xr[n - D];
+            else if (hr) v += coeff * hr[n];
+            yr[n] = v;
+        }
+        return;
+    }
+    const int64_t g = id - n_out, row = g / htiles, tile = g % htiles;
+    const T *xr = x + row * T_;
+    const T *hr = hist_in ? hist_in + row * D : nullptr;
+    T *ho = hist_out + row * D;
+#pragma unroll
+    for (int e = 0; e < EFX_STR_E; ++e) {
+        const int64_t j = tile * EFX_STR_TILE + e * EFX_THREADS + threadIdx.x;
+        if (j >= D) break;
+        const int64_t v = T_ + j;
+        ho[j] = v >= D ? xr[v - D] : (hr ? hr[v] : (T)0);
+    }
+}
+
+// [a, a + na) and [b, b + nb) share no byte (null pointers and empty ranges share none)
+static bool stream_disjoint(const void *a, size_t na, const void *b, size_t nb)
+{
+    if (!a || !b || !na || !nb) return true;
+    const char *p = (const char *)a, *q = (const char *)b;
+    return p + na <= q || q + nb <= p;
+}
+
+void delay_line_stream_check(const void *x, const void *y, int dtype, int64_t C, int64_t T, int64_t delay, const void *hist_in,
+                             const void *hist_out)
+{
+    TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "delay_line_stream_forward: bad dtype %d", dtype);
+    TFX_CHECK(delay >= 0, "delay_line_stream_forward: negative delay %lld", (long long)delay);
+    TFX_CHECK(C >= 0 && T >= 0, "delay_line_stream_forward: negative size");
+    TFX_CHECK(C == 0 || (T <= INT64_MAX / 4 / C && delay <= INT64_MAX / 4 / C), "delay_line_stream_forward: size overflows");
+    TFX_CHECK((x || C * T == 0) && (y || C * T == 0) && (hist_out || C * delay == 0), "delay_line_stream_forward: null pointer");
+    const size_t esz = dtype == TFX_F32 ? 4 : 8, xb = (size_t)(C * T) * esz, hb = (size_t)(C * delay) * esz;
+    TFX_CHECK(stream_disjoint(hist_in, hb, hist_out, hb), "delay_line_stream_forward: the new history needs its own buffer");
+    TFX_CHECK(stream_disjoint(y, xb, x, xb) && stream_disjoint(y, xb, hist_in, hb) && stream_disjoint(hist_out, hb, x, xb) &&
+                  stream_disjoint(y, xb, hist_out, hb),
+              "delay_line_stream_forward: y and hist_out may not overlap x, hist_in or each other");
+}
+
+void delay_line_stream_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int64_t delay, double coeff,
+                               const void *hist_in, void *hist_out, hipStream_t stream)
+{
+    delay_line_stream_check(x, y, dtype, C, T, delay, hist_in, hist_out);
+    const int64_t otiles = ceil_div(T, EFX_STR_TILE), htiles = ceil_div(delay, EFX_STR_TILE), nwg = C * (otiles + htiles);
+    if (nwg == 0) return;
+    TFX_CHECK(nwg < (1ll << 31), "delay_line_stream_forward: grid too large");
+    ProfScope ps("delay_line_stream_kernel", stream);
+    if (dtype == TFX_F32)
+        hipLaunchKernelGGL(delay_line_stream_kernel<float>, dim3((unsigned)nwg), dim3(EFX_THREADS), 0, stream, (const float *)x,
+                           (const float *)hist_in, (float *)y, (float *)hist_out, C, T, delay, otiles, htiles, (float)coeff);
+    else
+        hipLaunchKernelGGL(delay_line_stream_kernel<double>, dim3((unsigned)nwg), dim3(EFX_THREADS), 0, stream, (const double *)x,
+                           (const double *)hist_in, (double *)y, (double *)hist_out, C, T, delay, otiles, htiles, coeff);
+    TFX_HIP(hipGetLastError());
+}
+
 // ---- host ---------------------------------------------------------------------------------------
 static inline int64_t efx_tiles(int64_t T, int esz) { return ceil_div(T, (int64_t)EFX_U * EFX_THREADS * (16 / esz)); }
 

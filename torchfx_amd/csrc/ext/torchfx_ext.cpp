@@ -326,6 +326,58 @@ Tensor delay_op(const Tensor &x, int64_t delay_samples, at::ArrayRef<double> amp
     return std::get<0>(delay_impl(x, delay_samples, amps, mix, pingpong, 1.0, false, -1, false));
 }
 
+// one chunk of a streaming Delay / delay line (StatefulDelay, StatefulReverb): x [..., T] -> (y [..., T], new history [rows, H]).
+// The history of the previous chunk (None = silence) and the chunk are read from their two buffers; the new history is a fresh
+// tensor every call (the graph replay of realtime.py copies it into its persistent home).
+Tensor stream_hist_in(const OptTensor &hist, const Tensor &x, int64_t rows, int64_t H, const char *what)
+{
+    if (!hist.has_value() || !hist->defined() || rows * H == 0) return Tensor();
+    TORCH_CHECK(hist->dim() == 2 && hist->size(0) == rows && hist->size(1) == H, what, ": history must be [rows, H] = [", rows, ", ", H,
+                "], got ", hist->sizes());
+    return hist->to(x.device(), x.scalar_type()).contiguous();
+}
+
+int64_t stream_rows(const Tensor &x)
+{
+    TORCH_CHECK(x.dim() >= 1, "stream: x must have a time dimension");
+    return c10::multiply_integers(x.sizes().begin(), x.sizes().end() - 1);
+}
+
+std::tuple<Tensor, Tensor> delay_stream_op(const Tensor &x_in, const OptTensor &hist, int64_t delay_samples, at::ArrayRef<double> amps,
+                                           double mix, bool pingpong)
+{
+    need_device(x_in, "x");
+    const int64_t taps = (int64_t)amps.size();
+    TORCH_CHECK(taps >= 1, "delay_stream_forward: at least one tap");
+    TORCH_CHECK(delay_samples >= 0, "delay_stream_forward: negative delay");
+    const Tensor x = x_in.contiguous();
+    const int64_t T = x.size(-1), rows = stream_rows(x), H = taps * delay_samples;
+    const bool pp = pingpong && x.dim() >= 2 && x.size(-2) == 2;
+    const Tensor hin = stream_hist_in(hist, x, rows, H, "delay_stream_forward");
+    Tensor y = at::empty_like(x), hout = at::empty({rows, H}, x.options());
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_delay_stream_forward(x.data_ptr(), y.data_ptr(), dtype_code(x, "delay_stream_forward"), rows, T, delay_samples, taps,
+                                      amps.data(), mix, pp ? 1 : 0, hin.defined() ? hin.data_ptr() : nullptr, hout.data_ptr(),
+                                      stream_of(x)),
+             "delay_stream_forward");
+    return {y, hout};
+}
+
+std::tuple<Tensor, Tensor> delay_line_stream_op(const Tensor &x_in, const OptTensor &hist, int64_t delay_samples, double decay, double mix)
+{
+    need_device(x_in, "x");
+    TORCH_CHECK(delay_samples >= 0, "delay_line_stream_forward: negative delay");
+    const Tensor x = x_in.contiguous();
+    const int64_t T = x.size(-1), rows = stream_rows(x);
+    const Tensor hin = stream_hist_in(hist, x, rows, delay_samples, "delay_line_stream_forward");
+    Tensor y = at::empty_like(x), hout = at::empty({rows, delay_samples}, x.options());
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_delay_line_stream_forward(x.data_ptr(), y.data_ptr(), dtype_code(x, "delay_line_stream_forward"), rows, T, delay_samples,
+                                           decay, mix, hin.defined() ? hin.data_ptr() : nullptr, hout.data_ptr(), stream_of(x)),
+             "delay_line_stream_forward");
+    return {y, hout};
+}
+
 // ---------------------------------------------------------------------------------------------------
 // FIR (fir.py:556-568) and overlap-save FFT convolution (_fftconv.py:70-141)
 // ---------------------------------------------------------------------------------------------------
@@ -652,6 +704,17 @@ std::tuple<Tensor, Tensor> delay_ep_meta(const Tensor &x, int64_t delay_samples,
     return {at::empty(delay_shape(x, delay_samples, (int64_t)amps.size()), x.options()),
             at::empty({stat_mode >= 0 ? (per_row ? rows : 1) : 0}, x.options().dtype(at::kDouble))};
 }
+std::tuple<Tensor, Tensor> delay_stream_meta(const Tensor &x, const OptTensor &, int64_t delay_samples, at::ArrayRef<double> amps,
+                                             double, bool)
+{
+    TORCH_CHECK(!amps.empty() && delay_samples >= 0, "delay_stream_forward: bad delay or taps");
+    return {at::empty_like(x), at::empty({stream_rows(x), (int64_t)amps.size() * delay_samples}, x.options())};
+}
+std::tuple<Tensor, Tensor> delay_line_stream_meta(const Tensor &x, const OptTensor &, int64_t delay_samples, double, double)
+{
+    TORCH_CHECK(delay_samples >= 0, "delay_line_stream_forward: negative delay");
+    return {at::empty_like(x), at::empty({stream_rows(x), delay_samples}, x.options())};
+}
 Tensor fft_conv_meta(const Tensor &x, const Tensor &kernel, int64_t pad_left, int64_t pad_right)
 {
     const int64_t tout = x.size(1) + pad_left + pad_right - kernel.numel() + 1;
@@ -678,6 +741,8 @@ TORCH_LIBRARY(torchfx_hip, m)
     m.def("delay_forward(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong) -> Tensor");
     m.def("delay_forward_ep(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong, float gain, bool clamp, int stat_mode, "
           "bool per_row) -> (Tensor, Tensor)");
+    m.def("delay_stream_forward(Tensor x, Tensor? hist, int delay_samples, float[] amps, float mix, bool pingpong) -> (Tensor, Tensor)");
+    m.def("delay_line_stream_forward(Tensor x, Tensor? hist, int delay_samples, float decay, float mix) -> (Tensor, Tensor)");
     m.def("fir_direct_forward(Tensor x, Tensor kernel) -> Tensor");
     m.def("fft_conv_forward(Tensor x, Tensor kernel, int pad_left, int pad_right) -> Tensor");
     m.def("fir_stream_forward(Tensor x, Tensor kernel, Tensor? hist, bool direct) -> (Tensor, Tensor)");
@@ -710,6 +775,8 @@ TORCH_LIBRARY_IMPL(torchfx_hip, CUDA, m)          // "CUDA" is the dispatch key 
     m.impl("delay_line_forward", delay_line_op);
     m.impl("delay_forward", delay_op);
     m.impl("delay_forward_ep", delay_ep_op);
+    m.impl("delay_stream_forward", delay_stream_op);
+    m.impl("delay_line_stream_forward", delay_line_stream_op);
     m.impl("fir_direct_forward", fir_direct_op);
     m.impl("fft_conv_forward", fft_conv_op);
     m.impl("fir_stream_forward", fir_stream_op);
@@ -739,6 +806,8 @@ TORCH_LIBRARY_IMPL(torchfx_hip, Meta, m)
     m.impl("fft_conv_forward", fft_conv_meta);
     m.impl("delay_forward", delay_meta);
     m.impl("delay_forward_ep", delay_ep_meta);
+    m.impl("delay_stream_forward", delay_stream_meta);
+    m.impl("delay_line_stream_forward", delay_line_stream_meta);
     m.impl("fir_stream_forward", [](const Tensor &x, const Tensor &kernel, const OptTensor &, bool) {
         return std::make_tuple(at::empty_like(x), at::empty({x.size(0), kernel.numel() - 1}, x.options()));
     });
@@ -756,7 +825,7 @@ static void no_cpu_boxed(const c10::OperatorHandle &op, c10::DispatchKeySet, tor
 TORCH_LIBRARY_IMPL(torchfx_hip, CPU, m)
 {
     for (const char *name : {"sos_forward", "sos_forward_sections", "sos_bank_forward", "sos_bank_sum_forward", "biquad_forward",
-                             "delay_line_forward", "delay_forward", "delay_forward_ep", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
+                             "delay_line_forward", "delay_forward", "delay_forward_ep", "delay_stream_forward", "delay_line_stream_forward", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
                              "fft_conv_forward_ep", "sos_fft_conv_forward", "normalize_apply", "sum_forward", "gain_forward", "quantile_abs", "stat_forward",
                              "normalize_forward", "deinterleave_forward", "deinterleave_into", "interleave_forward"})
         m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());

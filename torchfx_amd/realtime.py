@@ -10,7 +10,10 @@ goes to the device interleaved -- pinned staging, de-interleave kernel, ``torchf
 back interleaved, so the host never transposes), plus what the reference lacks: :class:`StatefulFIR`,
 an FIR that carries its last K-1 input samples so that ``overlap = 0`` streaming is exact for FIR
 stages too; its kernels read the history and the chunk from two buffers (``tfx_fir_stream_forward``),
-there is no concatenated copy of the chunk.
+there is no concatenated copy of the chunk.  :class:`StatefulDelay` and :class:`StatefulReverb` do the same for the two
+time-based effects: they carry the last ``taps * delay_samples`` (``delay``) input samples of every row, return chunks of the
+chunk's shape, and one launch per chunk (``tfx_delay_stream_forward`` / ``tfx_delay_line_stream_forward``) gives the
+one-shot effect's bits.
 
 Small chunks are launch-bound (a 2 x 4096 step is ~60 us of host + launch overhead for a few us of
 GPU work), so ``StreamProcessor(..., use_graph=True)`` captures one full-size chunk step -- every
@@ -22,6 +25,7 @@ from __future__ import annotations
 import abc
 import dataclasses
 import enum
+import math
 import os
 import threading
 from collections.abc import Generator, Sequence
@@ -29,7 +33,7 @@ from collections.abc import Generator, Sequence
 import torch
 from torch import Tensor, nn
 
-from torchfx_amd.effect import FX
+from torchfx_amd.effect import FX, Delay, MonoDelayStrategy, PingPongDelayStrategy, Reverb, _ext
 from torchfx_amd.filter._base import AbstractFilter
 from torchfx_amd.filter.fir import FIR
 
@@ -68,6 +72,144 @@ class StatefulFIR(FIR):
         direct = self._conv_mode == "direct" or rows.shape[0] * rows.shape[1] * k <= self.DIRECT_BELOW_MACS
         y, self._hist = torchfx_ext.fir_stream_forward(rows, taps, h, direct)
         return y.reshape(shape)
+
+
+def _rows(x: Tensor) -> int:
+    if x.ndim not in (1, 2, 3):
+        raise ValueError("Input must be of shape [T], [C, T], or [B, C, T]")
+    return math.prod(x.shape[:-1])
+
+
+def _carried(hist: Tensor | None, rows: int, H: int, x: Tensor) -> Tensor | None:
+    """The history a delay effect carries into this chunk: None (silence) when there is none or the row count, dtype or
+    device changed; when only its length ``H`` changed, the newest ``min(H_old, H)`` samples, zero-filled at the front."""
+    if hist is None or hist.shape[0] != rows or hist.dtype != x.dtype or hist.device != x.device:
+        return None
+    old = hist.shape[1]
+    if old == H:
+        return hist
+    out = torch.zeros(rows, H, dtype=x.dtype, device=x.device)
+    k = min(old, H)
+    if k:
+        out[:, H - k:] = hist[:, old - k:]
+    return out
+
+
+def _native_stream(x: Tensor) -> bool:
+    return x.is_cuda and x.dtype in (torch.float32, torch.float64)
+
+
+class StatefulDelay(Delay):
+    """:class:`~torchfx_amd.effect.Delay` over a continuous stream: every chunk's output has the chunk's shape, the last
+    ``H = taps * delay_samples`` input samples of every row are carried in ``_hist`` (``[rows, H]``) and :meth:`flush`
+    returns the ring-out (``[..., H]``).  The chunks' outputs followed by the ring-out are bit-identical to ``Delay`` on
+    the whole signal, on the same device and in the same dtype, whatever the chunk sizes (``csrc/delay.hip``).
+
+    Device float32 / float64 chunks run one launch each (:func:`torchfx_ext.delay_stream_forward`); other chunks run the
+    one-shot effect on ``[history | chunk]`` and keep the chunk's part.  The history restarts from silence when the row
+    count, dtype or device changes; when ``H`` changes between chunks (``delay_samples``, ``taps``, or ``bpm`` /
+    ``delay_time`` / ``fs`` of a BPM-synced instance) the newest samples are kept.  Only the stock strategies stream."""
+
+    def __init__(self, delay_samples: int | None = None, bpm: float | None = None, delay_time: str = "1/8",
+                 fs: int | None = None, feedback: float = 0.3, mix: float = 0.2, taps: int = 3,
+                 strategy=None) -> None:
+        super().__init__(delay_samples, bpm, delay_time, fs, feedback, mix, taps, strategy)
+        if type(self.strategy) not in (MonoDelayStrategy, PingPongDelayStrategy):
+            raise TypeError(f"StatefulDelay streams MonoDelayStrategy and PingPongDelayStrategy only, got {type(self.strategy).__name__}")
+        self._bpm_synced = delay_samples is None
+        self._bpm_key = (bpm, delay_time, fs) if self.delay_samples is not None else None
+        self._hist: Tensor | None = None
+        self._last: tuple | None = None             # (leading shape, dtype, device) of the last chunk, for flush()
+
+    def reset_state(self) -> None:
+        self._hist = None
+        self._last = None
+
+    def _delay(self) -> int:
+        """The delay of this chunk: a BPM-synced instance follows ``bpm``, ``delay_time`` and ``fs``."""
+        if self._bpm_synced and (self.bpm, self.delay_time, self.fs) != self._bpm_key:
+            self._needs_calculation = True
+            self._resolve()
+            self._bpm_key = (self.bpm, self.delay_time, self.fs)
+        self._resolve()
+        return int(self.delay_samples)
+
+    def _capture_key(self) -> tuple:
+        """What a captured HIP graph of this effect bakes in (``StreamProcessor._graph_step`` recaptures when it changes)."""
+        return self._delay(), int(self.taps), float(self.feedback), float(self.mix), type(self.strategy)
+
+    def _sync_history(self) -> None:
+        """Bring the carried history to the current ``H`` (newest samples kept) before a capture takes it as a home."""
+        if self._hist is not None:
+            self._hist = _carried(self._hist, self._hist.shape[0], int(self.taps) * self._delay(), self._hist)
+
+    @torch.no_grad()
+    def forward(self, x: Tensor) -> Tensor:
+        rows = _rows(x)
+        D = self._delay()
+        taps = int(self.taps)
+        H, T = taps * D, x.shape[-1]
+        h = _carried(self._hist, rows, H, x)
+        self._last = (tuple(x.shape[:-1]), x.dtype, x.device)
+        if _native_stream(x):
+            y, self._hist = _ext().delay_stream_forward(x, h, D, taps, self.feedback, self.mix, self.pingpong(x))
+            return y
+        if h is None:
+            h = torch.zeros(rows, H, dtype=x.dtype, device=x.device)
+        v = torch.cat([h, x.reshape(rows, T)], dim=-1)
+        self._hist = v[:, T:].clone()
+        return Delay.forward(self, v.reshape(*x.shape[:-1], H + T))[..., H:H + T]
+
+    @torch.no_grad()
+    def flush(self) -> Tensor:
+        """The ring-out of the stream (the last ``taps * delay_samples`` samples of the one-shot output), shaped like the
+        last chunk; then the state is reset.  Without a chunk since the last reset: an empty tensor."""
+        if self._last is None:
+            return torch.zeros(0)
+        lead, dtype, device = self._last
+        tail = self.forward(torch.zeros(*lead, int(self.taps) * self._delay(), dtype=dtype, device=device))
+        self.reset_state()
+        return tail
+
+
+class StatefulReverb(Reverb):
+    """:class:`~torchfx_amd.effect.Reverb` (``y[n] = x[n] + mix * decay * x[n - delay]``) over a continuous stream: the last
+    ``delay`` input samples of every row are carried in ``_hist``, so a chunk's first ``delay`` outputs get the previous
+    chunk's echo and chunks shorter than the delay are not passed through unchanged.  Output has the chunk's shape (no
+    tail).  Chunked output equals ``Reverb`` on the whole signal (``torch.equal``).  Device float32 / float64 chunks run
+    one launch each (:func:`torchfx_ext.delay_line_stream_forward`); other chunks run the one-shot effect on
+    ``[history | chunk]`` -- which, like ``Reverb`` itself, needs a device: the library's delay line has no CPU path, so a CPU
+    chunk longer than the history raises as ``Reverb`` does on a CPU signal longer than the delay."""
+
+    def __init__(self, delay: int = 4410, decay: float = 0.5, mix: float = 0.5) -> None:
+        super().__init__(delay, decay, mix)
+        self._hist: Tensor | None = None
+
+    def reset_state(self) -> None:
+        self._hist = None
+
+    def _capture_key(self) -> tuple:
+        return int(self.delay), float(self.decay), float(self.mix)
+
+    def _sync_history(self) -> None:
+        if self._hist is not None:
+            self._hist = _carried(self._hist, self._hist.shape[0], int(self.delay), self._hist)
+
+    @torch.no_grad()
+    def forward(self, x: Tensor) -> Tensor:
+        rows = _rows(x)
+        D, T = int(self.delay), x.shape[-1]
+        h = _carried(self._hist, rows, D, x)
+        if _native_stream(x):
+            y, self._hist = _ext().delay_line_stream_forward(x, h, D, self.decay, self.mix)
+            return y
+        xr = x.reshape(rows, T)
+        if h is None:                                   # the stream starts here: the one-shot effect on the chunk itself
+            self._hist = torch.cat([torch.zeros(rows, D, dtype=x.dtype, device=x.device), xr], dim=-1)[:, T:].clone()
+            return Reverb.forward(self, x)
+        v = torch.cat([h, xr], dim=-1)
+        self._hist = v[:, T:].clone()
+        return Reverb.forward(self, v.reshape(*x.shape[:-1], D + T))[..., D:]
 
 
 class _ChunkRun:
@@ -270,9 +412,18 @@ class StreamProcessor:
             w = e(w)
         return w
 
+    def _capture_members(self) -> list:
+        """Members whose parameters a captured step bakes in and whose carried state can change length (StatefulDelay,
+        StatefulReverb): they name their parameters in ``_capture_key`` and resize their history in ``_sync_history``."""
+        return [m for e in self._effects for m in (e.modules() if isinstance(e, nn.Module) else [e]) if hasattr(m, "_capture_key")]
+
     def _graph_step(self, w: Tensor) -> Tensor:
         """Replay the captured step on ``w`` (capturing it first; the carried states must exist)."""
-        sig = (tuple(w.shape), w.dtype, tuple(tuple(getattr(m, a).shape) for m, a in self._stateful_slots()))
+        members = self._capture_members()
+        for m in members:                             # a parameter change since the last chunk: history at its new length
+            m._sync_history()
+        sig = (tuple(w.shape), w.dtype, tuple(tuple(getattr(m, a).shape) for m, a in self._stateful_slots()),
+               tuple(m._capture_key() for m in members))
         if self._graph is None or self._graph[4] != sig:
             dev = w.device
             slots = self._stateful_slots()

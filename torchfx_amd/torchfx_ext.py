@@ -33,7 +33,7 @@ from torchfx_amd import native
 
 __all__ = [
     "biquad_forward", "sos_forward", "sos_bank_forward", "sos_bank_sum_forward", "delay_line_forward", "delay_forward",
-    "delay_amplitudes", "delay_regime",
+    "delay_amplitudes", "delay_regime", "delay_stream_forward", "delay_line_stream_forward",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
 ]
@@ -142,6 +142,22 @@ def delay_forward(x: Tensor, delay_samples: int, taps: int, feedback: float, mix
 
 
 DELAY_REGIMES = ("span", "lattice", "gather")
+
+
+def delay_stream_forward(x: Tensor, hist: Tensor | None, delay_samples: int, taps: int, feedback: float, mix: float,
+                         pingpong: bool = False) -> tuple[Tensor, Tensor]:
+    """One chunk of a streaming ``Delay`` in one launch: ``x [..., T]`` continues the last ``H = taps * delay_samples`` input
+    samples of every row (``hist [rows, H]``, None = silence).  Returns ``(y [..., T], new history [rows, H])``; the chunks'
+    outputs followed by those of ``H`` zero samples are bit-identical to :func:`delay_forward` on the whole signal."""
+    return native.ops().delay_stream_forward(x, hist, int(delay_samples), delay_amplitudes(taps, feedback), float(mix),
+                                             bool(pingpong))
+
+
+def delay_line_stream_forward(x: Tensor, hist: Tensor | None, delay_samples: int, decay: float,
+                              mix: float) -> tuple[Tensor, Tensor]:
+    """One chunk of :func:`delay_line_forward` over a continuous stream: the ``delay_samples`` samples of every row before
+    ``x [..., T]`` come from ``hist [rows, delay_samples]`` (None = silence).  Returns ``(y [..., T], new history)``."""
+    return native.ops().delay_line_stream_forward(x, hist, int(delay_samples), float(decay), float(mix))
 
 
 def delay_regime(delay_samples: int, taps: int, dtype: torch.dtype = torch.float32, pingpong: bool = False) -> str:

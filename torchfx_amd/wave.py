@@ -541,6 +541,7 @@ class Wave:
         recursion-in-pass-A pipeline or the staged pair of launches) and why."""
         from torchfx_amd.effect import Delay, Epilogued
         from torchfx_amd.filter.fused import CascadeFIR, FusedSOSCascade
+        from torchfx_amd.realtime import StatefulDelay, _native_stream
 
         lines = []
         for m in self.plan():
@@ -554,6 +555,9 @@ class Wave:
                     line += f": staged -- {inner.recursive_refused}"
                 elif getattr(inner, "fold_refused", None) is not None:
                     line += f": staged -- spectral fold refused (error estimate {inner.fold_refused:.1e})"
+            elif isinstance(inner, StatefulDelay):
+                line += ": " + ("native stream (delay_stream_kernel)" if _native_stream(self._ys)
+                                else f"torch composition -- {self._ys.device.type} {self._ys.dtype} signal")
             elif isinstance(inner, Delay):
                 line += ": " + Wave._delay_route(inner, self._ys, self.fs)
             lines.append(line)
