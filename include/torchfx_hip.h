@@ -366,6 +366,25 @@ int tfx_delay_line_stream_forward(const void *x, void *y, int dtype, int64_t C, 
 int tfx_delay_plan_info(int64_t delay, int64_t taps, int dtype, int pingpong, int *regime);
 
 /* ---------------------------------------------------------------------------
+ * tfx_resample_forward -- polyphase rational resampling along each row, scipy.signal.resample_poly(x, up, down, axis=-1,
+ * padtype="constant") with the caller's filter, in ONE launch:
+ *   up, down reduced by their gcd; up == down: y = x (a copy);  n_out = ceil(T * up / down);
+ *   h_padded = [0 * n_pre_pad | taps | 0 * n_post_pad] with SciPy's n_pre_pad, n_post_pad and n_pre_remove (worked out here
+ *   from nh, up and down, half_len = (nh - 1) / 2), zero padded to Lp * up taps;
+ *   y[m] = sum_{j < Lp} h_padded[n mod up + j*up] * x[n / up - j],  n = (m + n_pre_remove) * down,  x = 0 outside [0, T).
+ * x DEVICE [rows, T] of dtype (float32 / float64); y DEVICE [rows, n_out] of dtype; taps_host HOST [nh] of dtype, already
+ * scaled by up (resample_poly's `h *= up`).  The polyphase table is cached by the taps' bytes, up, down and dtype, so once a
+ * filter has run the call can be captured into a HIP graph.  Arguments are checked before the device is touched.
+ * ------------------------------------------------------------------------- */
+int tfx_resample_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
+                         const void *taps_host, int64_t nh, tfx_stream_t stream);
+/* what tfx_resample_forward does for rows of T samples (host-only): n_out, n_pre_remove, the padded filter length
+ * (nh + n_pre_pad + n_post_pad), taps per phase Lp, the kernel (0 = window in LDS and taps in registers, 1 = window in LDS and
+ * taps through the cache, 2 = gather: the window does not fit in LDS, 3 = copy: up == down) and its LDS bytes per workgroup */
+int tfx_resample_plan_info(int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int64_t *n_out, int64_t *n_pre_remove,
+                           int64_t *padded, int64_t *Lp, int *kernel, int64_t *lds_bytes);
+
+/* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of
  * ParallelFilterCombination.forward, src/torchfx/filter/__base.py:1019-1026).
  * xs_host: HOST array of n DEVICE pointers, each [numel] of dtype.

@@ -77,6 +77,14 @@ void delay_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64
                           const double *amps_host, double mix, int pingpong, const void *hist_in, void *hist_out, hipStream_t stream);
 int delay_regime(int64_t D, int64_t taps, int esz, int pingpong);
 void delay_clear();
+// resample.hip
+void resample_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
+                    const void *taps_host, int64_t nh);
+void resample_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down, const void *taps_host,
+                      int64_t nh, hipStream_t stream);
+void resample_plan_info(int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int64_t *n_out, int64_t *pre_remove,
+                        int64_t *padded, int64_t *Lp, int *kernel, int64_t *lds_bytes);
+void resample_clear();
 // layout.hip
 void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, int64_t C, int64_t ld_out, int64_t f_base,
                           double scale, hipStream_t stream);
@@ -617,6 +625,24 @@ int tfx_delay_plan_info(int64_t delay, int64_t taps, int dtype, int pingpong, in
     TFX_API_END
 }
 
+int tfx_resample_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
+                         const void *taps_host, int64_t nh, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    resample_check(x, y, dtype, rows, T, up, down, taps_host, nh);        // before anything touches the device
+    resample_forward(x, y, dtype, rows, T, up, down, taps_host, nh, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_resample_plan_info(int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int64_t *n_out, int64_t *n_pre_remove,
+                           int64_t *padded, int64_t *Lp, int *kernel, int64_t *lds_bytes)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(n_out && n_pre_remove && padded && Lp && kernel && lds_bytes, "resample_plan_info: null output");
+    resample_plan_info(T, up, down, nh, dtype, n_out, n_pre_remove, padded, Lp, kernel, lds_bytes);
+    TFX_API_END
+}
+
 int tfx_sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, tfx_stream_t stream)
 {
     TFX_API_BEGIN
@@ -723,6 +749,7 @@ int tfx_clear_caches(void)
     olsnative64_clear();
     olslds_clear();
     delay_clear();
+    resample_clear();
     scratch_clear();
     TFX_API_END
 }

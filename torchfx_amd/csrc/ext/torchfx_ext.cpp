@@ -378,6 +378,35 @@ std::tuple<Tensor, Tensor> delay_line_stream_op(const Tensor &x_in, const OptTen
     return {y, hout};
 }
 
+// Polyphase resampling (scipy.signal.resample_poly, padtype "constant"): x [..., T] -> [..., ceil(T * up / down)], leading
+// dimensions flattened into rows; h HOST [nh] in x's dtype, the designed filter already scaled by up
+std::vector<int64_t> resample_shape(const Tensor &x, int64_t up, int64_t down)
+{
+    TORCH_CHECK(x.dim() >= 1, "resample_forward: x must have a time dimension");
+    TORCH_CHECK(up >= 1 && down >= 1, "resample_forward: up and down must be >= 1");
+    std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
+    TORCH_CHECK(shape.back() <= INT64_MAX / up, "resample_forward: T * up overflows");
+    shape.back() = (shape.back() * up + down - 1) / down;
+    return shape;
+}
+
+Tensor resample_op(const Tensor &x_in, int64_t up, int64_t down, const Tensor &h)
+{
+    need_device(x_in, "x");
+    const std::vector<int64_t> shape = resample_shape(x_in, up, down);
+    TORCH_CHECK(!h.is_cuda() && h.dim() == 1 && h.numel() >= 1, "resample_forward: h must be a non-empty 1-D host tensor");
+    TORCH_CHECK(h.scalar_type() == x_in.scalar_type(), "resample_forward: h must have x's dtype (", x_in.scalar_type(), "), got ",
+                h.scalar_type());
+    const Tensor x = x_in.contiguous(), hc = h.contiguous();
+    const int64_t T = x.size(-1), rows = T > 0 ? x.numel() / T : c10::multiply_integers(x.sizes().begin(), x.sizes().end() - 1);
+    Tensor y = at::empty(shape, x.options());
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_resample_forward(x.data_ptr(), y.data_ptr(), dtype_code(x, "resample_forward"), rows, T, up, down, hc.data_ptr(),
+                                  hc.numel(), stream_of(x)),
+             "resample_forward");
+    return y;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // FIR (fir.py:556-568) and overlap-save FFT convolution (_fftconv.py:70-141)
 // ---------------------------------------------------------------------------------------------------
@@ -693,6 +722,10 @@ std::tuple<Tensor, Tensor, Tensor> biquad_meta(const Tensor &x, const Tensor &, 
     Tensor st = at::empty({x.size(0), 2}, x.options().dtype(at::kDouble));
     return {at::empty(x.sizes(), x.options().dtype(out_type(x, out_dtype))), st, at::empty_like(st)};
 }
+Tensor resample_meta(const Tensor &x, int64_t up, int64_t down, const Tensor &)
+{
+    return at::empty(resample_shape(x, up, down), x.options());
+}
 Tensor delay_meta(const Tensor &x, int64_t delay_samples, at::ArrayRef<double> amps, double, bool)
 {
     return at::empty(delay_shape(x, delay_samples, (int64_t)amps.size()), x.options());
@@ -739,6 +772,7 @@ TORCH_LIBRARY(torchfx_hip, m)
           "ScalarType? out_dtype=None, int precision=-1) -> (Tensor, Tensor, Tensor)");
     m.def("delay_line_forward(Tensor(a) x, int delay_samples, float decay, float mix) -> Tensor(a)");
     m.def("delay_forward(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong) -> Tensor");
+    m.def("resample_forward(Tensor x, int up, int down, Tensor h) -> Tensor");
     m.def("delay_forward_ep(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong, float gain, bool clamp, int stat_mode, "
           "bool per_row) -> (Tensor, Tensor)");
     m.def("delay_stream_forward(Tensor x, Tensor? hist, int delay_samples, float[] amps, float mix, bool pingpong) -> (Tensor, Tensor)");
@@ -774,6 +808,7 @@ TORCH_LIBRARY_IMPL(torchfx_hip, CUDA, m)          // "CUDA" is the dispatch key 
     m.impl("biquad_forward", biquad_op);
     m.impl("delay_line_forward", delay_line_op);
     m.impl("delay_forward", delay_op);
+    m.impl("resample_forward", resample_op);
     m.impl("delay_forward_ep", delay_ep_op);
     m.impl("delay_stream_forward", delay_stream_op);
     m.impl("delay_line_stream_forward", delay_line_stream_op);
@@ -805,6 +840,7 @@ TORCH_LIBRARY_IMPL(torchfx_hip, Meta, m)
     m.impl("fir_direct_forward", [](const Tensor &x, const Tensor &) { return at::empty_like(x); });
     m.impl("fft_conv_forward", fft_conv_meta);
     m.impl("delay_forward", delay_meta);
+    m.impl("resample_forward", resample_meta);
     m.impl("delay_forward_ep", delay_ep_meta);
     m.impl("delay_stream_forward", delay_stream_meta);
     m.impl("delay_line_stream_forward", delay_line_stream_meta);
@@ -825,7 +861,7 @@ static void no_cpu_boxed(const c10::OperatorHandle &op, c10::DispatchKeySet, tor
 TORCH_LIBRARY_IMPL(torchfx_hip, CPU, m)
 {
     for (const char *name : {"sos_forward", "sos_forward_sections", "sos_bank_forward", "sos_bank_sum_forward", "biquad_forward",
-                             "delay_line_forward", "delay_forward", "delay_forward_ep", "delay_stream_forward", "delay_line_stream_forward", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
+                             "delay_line_forward", "delay_forward", "delay_forward_ep", "delay_stream_forward", "delay_line_stream_forward", "resample_forward", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
                              "fft_conv_forward_ep", "sos_fft_conv_forward", "normalize_apply", "sum_forward", "gain_forward", "quantile_abs", "stat_forward",
                              "normalize_forward", "deinterleave_forward", "deinterleave_into", "interleave_forward"})
         m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());

@@ -36,6 +36,7 @@ from torch import Tensor, nn
 from torchfx_amd.effect import FX, Delay, MonoDelayStrategy, PingPongDelayStrategy, Reverb, _ext
 from torchfx_amd.filter._base import AbstractFilter
 from torchfx_amd.filter.fir import FIR
+from torchfx_amd.resample import Resample
 
 
 class StatefulFIR(FIR):
@@ -351,6 +352,9 @@ class StreamProcessor:
         for e in self._effects:
             if not isinstance(e, FX):
                 raise TypeError("All effects must inherit from FX when used in StreamProcessor")
+            if any(isinstance(m, Resample) for m in e.modules()):
+                raise TypeError("Resample cannot run in StreamProcessor: resampling each chunk on its own leaves a seam at "
+                                "every chunk boundary; resample the whole signal (Wave.resample) before or after streaming")
         self._chunk_size, self._overlap, self._device = chunk_size, overlap, device
         self._use_graph = use_graph
         self._graph = None            # (CUDAGraph, static in, static out, stream, signature, state slots, homes)

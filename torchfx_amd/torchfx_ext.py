@@ -33,7 +33,8 @@ from torchfx_amd import native
 
 __all__ = [
     "biquad_forward", "sos_forward", "sos_bank_forward", "sos_bank_sum_forward", "delay_line_forward", "delay_forward",
-    "delay_amplitudes", "delay_regime", "delay_stream_forward", "delay_line_stream_forward",
+    "delay_amplitudes", "delay_regime", "delay_stream_forward", "delay_line_stream_forward", "resample_forward",
+    "resample_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
 ]
@@ -167,6 +168,27 @@ def delay_regime(delay_samples: int, taps: int, dtype: torch.dtype = torch.float
     L.check(L.load().tfx_delay_plan_info(int(delay_samples), int(taps), L.TFX_F64 if dtype == torch.float64 else L.TFX_F32,
                                          int(bool(pingpong)), ctypes.byref(r)))
     return DELAY_REGIMES[r.value]
+
+
+def resample_forward(x: Tensor, up: int, down: int, h: Tensor) -> Tensor:
+    """``scipy.signal.resample_poly(x, up, down, axis=-1, padtype="constant")`` with the filter ``h`` (a 1-D host tensor in
+    ``x``'s dtype, already scaled by ``up``) in one launch: ``x [..., T]`` -> ``[..., ceil(T * up / down)]``."""
+    return native.ops().resample_forward(x.contiguous(), int(up), int(down), h)
+
+
+RESAMPLE_KERNELS = ("resample_reg_kernel", "resample_lds_kernel", "resample_gather_kernel", "copy")
+
+
+def resample_plan_info(length: int, up: int, down: int, taps: int, dtype: torch.dtype = torch.float32) -> dict:
+    """What :func:`resample_forward` does for rows of ``length`` samples and a filter of ``taps`` taps (``tfx_resample_plan_info``;
+    host-only): ``n_out``, ``n_pre_remove``, ``padded`` (the filter length with SciPy's zero padding), ``Lp`` (taps per
+    phase), ``kernel`` and ``lds_bytes`` per workgroup."""
+    o = [ctypes.c_int64(0) for _ in range(4)]
+    k, lds = ctypes.c_int(0), ctypes.c_int64(0)
+    L.check(L.load().tfx_resample_plan_info(int(length), int(up), int(down), int(taps), L.TFX_F64 if dtype == torch.float64 else L.TFX_F32,
+                                            *[ctypes.byref(v) for v in o], ctypes.byref(k), ctypes.byref(lds)))
+    return {"n_out": o[0].value, "n_pre_remove": o[1].value, "padded": o[2].value, "Lp": o[3].value,
+            "kernel": RESAMPLE_KERNELS[k.value], "lds_bytes": lds.value}
 
 
 _TAPS_HOST: dict = {}        # (id(base tensor), offset, numel, dtype wanted) -> (weakref to base, version, host tensor)

@@ -211,6 +211,7 @@ def plan_cache_clear() -> None:
 
 def _member_key(m: nn.Module, guard: list) -> tuple:
     from torchfx_amd.effect import Delay, Gain, Normalize
+    from torchfx_amd.resample import Resample, window_key
 
     guard.append(m)
     k: tuple = (id(m),)
@@ -230,6 +231,8 @@ def _member_key(m: nn.Module, guard: list) -> tuple:
     elif isinstance(m, Delay):
         guard.append(m.strategy)
         k += (m.delay_samples, m.taps, m.feedback, m.mix, type(m.strategy), getattr(m, "fs", None))
+    elif isinstance(m, Resample):
+        k += (m.new_fs, m.fs, window_key(m.window))
     return k
 
 
@@ -317,6 +320,23 @@ class Wave:
         return _instantiate(built)
 
     def _build_plan(self, length: int, dtype: torch.dtype = torch.float32) -> list[nn.Module]:
+        """A ``Resample`` is a barrier: the steps between two of them are planned on their own, at the row length they see,
+        and nothing merges, folds or attaches an epilogue across one."""
+        from torchfx_amd.resample import Resample
+
+        plan: list[nn.Module] = []
+        segment: list[nn.Module] = []
+        for m in self._pipeline:
+            if isinstance(m, Resample):
+                plan += self._build_segment(segment, length, dtype)
+                plan.append(m)
+                segment = []
+                length = m.output_length(length)
+            else:
+                segment.append(m)
+        return plan + self._build_segment(segment, length, dtype)
+
+    def _build_segment(self, pipeline: list[nn.Module], length: int, dtype: torch.dtype = torch.float32) -> list[nn.Module]:
         from torchfx_amd.filter.biquad import Biquad
         from torchfx_amd.filter.fir import FIR
         from torchfx_amd.filter._sos import CascadeTable
@@ -365,7 +385,7 @@ class Wave:
                     plan.append(_merge_fir_run(mem) if len(mem) >= 2 else mem[0])
             items, kind = [], None
 
-        for m in self._pipeline:
+        for m in pipeline:
             if fold and isinstance(m, Gain) and not m.clamp:
                 (items if kind is not None else lead).append(m)
                 continue
@@ -542,8 +562,10 @@ class Wave:
         from torchfx_amd.effect import Delay, Epilogued
         from torchfx_amd.filter.fused import CascadeFIR, FusedSOSCascade
         from torchfx_amd.realtime import StatefulDelay, _native_stream
+        from torchfx_amd.resample import Resample
 
         lines = []
+        length = int(self._ys.shape[-1]) if self._ys.dim() else 0
         for m in self.plan():
             inner = m.producer if isinstance(m, Epilogued) else m
             line = type(m).__name__ + (f"[{type(inner).__name__}]" if inner is not m else "")
@@ -560,6 +582,9 @@ class Wave:
                                 else f"torch composition -- {self._ys.device.type} {self._ys.dtype} signal")
             elif isinstance(inner, Delay):
                 line += ": " + Wave._delay_route(inner, self._ys, self.fs)
+            elif isinstance(inner, Resample):
+                line += ": " + inner.route(self._ys, length)
+                length = inner.output_length(length)
             lines.append(line)
         return lines
 
@@ -617,17 +642,39 @@ class Wave:
     def __or__(self, f: nn.Module) -> "Wave":
         if not isinstance(f, nn.Module):
             raise TypeError(f"Expected nn.Module, but got {type(f).__name__} instead.")
-        for m in f.modules():                       # includes f itself and nested containers
-            if isinstance(m, FX):
-                if getattr(m, "fs", 0) is None:
-                    m.fs = self.fs
-                if isinstance(m, AbstractFilter) and not m._has_computed_coeff:
-                    m.compute_coefficients()
+        fs = Wave._bind_fs(f, self.fs)
         steps = list(f.children()) if isinstance(f, nn.Sequential) else [f]
-        return Wave._deferred(self._ys, self.fs, self._device, self.metadata,
+        return Wave._deferred(self._ys, fs, self._device, self.metadata,
                               self._pipeline + steps, self.fuse_fir, getattr(self, "fuse_spectral", False),
                               getattr(self, "fuse_gain", False), getattr(self, "fuse_epilogue", False),
                               getattr(self, "fuse_recursive", False))
+
+    @staticmethod
+    def _bind_fs(f: nn.Module, fs):
+        """Give every effect in ``f`` without a rate the rate of the signal it will see and design the filters that have no
+        coefficients yet.  Steps of a sequential container are walked in order: after a ``Resample`` the rate is its
+        ``new_fs``.  Returns the rate of ``f``'s output."""
+        from torchfx_amd.resample import Resample
+
+        if isinstance(f, nn.Sequential):
+            if isinstance(f, FX) and getattr(f, "fs", 0) is None:
+                f.fs = fs
+            for step in f.children():
+                fs = Wave._bind_fs(step, fs)
+            return fs
+        for m in f.modules():                       # includes f itself and nested containers
+            if isinstance(m, FX):
+                if getattr(m, "fs", 0) is None:
+                    m.fs = fs
+                if isinstance(m, AbstractFilter) and not m._has_computed_coeff:
+                    m.compute_coefficients()
+        return f.new_fs if isinstance(f, Resample) else fs
+
+    def resample(self, new_fs: int, window=("kaiser", 5.0)) -> "Wave":
+        """``self | Resample(new_fs, window=window)``: the signal at ``new_fs`` (``scipy.signal.resample_poly`` semantics)."""
+        from torchfx_amd.resample import Resample
+
+        return self | Resample(new_fs, window=window)
 
     # ------------------------------------------------------------------ files
     _SUBTYPE_BY_ENCODING = {"PCM_S": lambda b: f"PCM_{b}", "PCM_U": lambda b: "PCM_U8" if b == 8 else f"PCM_{b}",
