@@ -383,6 +383,27 @@ int tfx_resample_forward(const void *x, void *y, int dtype, int64_t rows, int64_
  * taps through the cache, 2 = gather: the window does not fit in LDS, 3 = copy: up == down) and its LDS bytes per workgroup */
 int tfx_resample_plan_info(int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int64_t *n_out, int64_t *n_pre_remove,
                            int64_t *padded, int64_t *Lp, int *kernel, int64_t *lds_bytes);
+/* ---------------------------------------------------------------------------
+ * tfx_resample_stream_forward -- one chunk of tfx_resample_forward over a continuous stream, in ONE launch.  The stream fixes
+ * (up, down reduced by their gcd) n_pre_pad and n_pre_remove as above and Lp_s = ceil((nh + n_pre_pad) / up) taps per phase.
+ * After `consumed` = N input samples per row it has emitted M(N) = max(0, ceil(N*up/down) - n_pre_remove) outputs; a chunk of
+ * T samples emits outputs [M(N), M(N + T)) of the whole signal's, each final (it reads no input past N + T - 1).  Every row
+ * carries the last H = Lp_s - 1 input samples: hist_in DEVICE [rows, H] holds inputs [N - H, N) (zeros before 0; NULL =
+ * silence), hist_out DEVICE [rows, H] receives [N + T - H, N + T).  The remaining ceil(N*up/down) - M(N) outputs come from
+ * feeding zeros.  For finite inputs, the chunks' outputs equal tfx_resample_forward on the whole signal bit for bit (up to the
+ * sign of a zero): each output is the same fma chain.  up == down: y = x and H = 0.
+ * x DEVICE [rows, T], y DEVICE [rows, M(N + T) - M(N)], taps_host as for tfx_resample_forward.  y and hist_out may not overlap
+ * x, hist_in or each other.  Arguments are checked before the device is touched.
+ * ------------------------------------------------------------------------- */
+int tfx_resample_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
+                                const void *taps_host, int64_t nh, int64_t consumed, const void *hist_in, void *hist_out,
+                                tfx_stream_t stream);
+/* what tfx_resample_stream_forward does with a chunk of T samples after `consumed` (host-only): the outputs [out_begin, out_end)
+ * it emits, the history length H, n_pre_remove (the outputs a stream holds back), Lp_s, the kernel (as tfx_resample_plan_info)
+ * and its largest LDS bytes per workgroup (a chunk with few tiles per launch takes smaller tiles, to fill the device) */
+int tfx_resample_stream_plan_info(int64_t consumed, int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int64_t *out_begin,
+                                  int64_t *out_end, int64_t *hist_len, int64_t *n_pre_remove, int64_t *Lp, int *kernel,
+                                  int64_t *lds_bytes);
 
 /* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of

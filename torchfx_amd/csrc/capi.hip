@@ -84,6 +84,14 @@ void resample_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T
                       int64_t nh, hipStream_t stream);
 void resample_plan_info(int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int64_t *n_out, int64_t *pre_remove,
                         int64_t *padded, int64_t *Lp, int *kernel, int64_t *lds_bytes);
+void resample_stream_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
+                           const void *taps_host, int64_t nh, int64_t consumed, const void *hist_in, const void *hist_out);
+void resample_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
+                             const void *taps_host, int64_t nh, int64_t consumed, const void *hist_in, void *hist_out,
+                             hipStream_t stream);
+void resample_stream_plan_info(int64_t consumed, int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int64_t *out_begin,
+                               int64_t *out_end, int64_t *hist_len, int64_t *pre_remove, int64_t *Lp, int *kernel,
+                               int64_t *lds_bytes);
 void resample_clear();
 // layout.hip
 void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, int64_t C, int64_t ld_out, int64_t f_base,
@@ -640,6 +648,27 @@ int tfx_resample_plan_info(int64_t T, int64_t up, int64_t down, int64_t nh, int 
     TFX_API_BEGIN
     TFX_CHECK(n_out && n_pre_remove && padded && Lp && kernel && lds_bytes, "resample_plan_info: null output");
     resample_plan_info(T, up, down, nh, dtype, n_out, n_pre_remove, padded, Lp, kernel, lds_bytes);
+    TFX_API_END
+}
+
+int tfx_resample_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
+                                const void *taps_host, int64_t nh, int64_t consumed, const void *hist_in, void *hist_out,
+                                tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    // checked before anything touches the device
+    resample_stream_check(x, y, dtype, rows, T, up, down, taps_host, nh, consumed, hist_in, hist_out);
+    resample_stream_forward(x, y, dtype, rows, T, up, down, taps_host, nh, consumed, hist_in, hist_out, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_resample_stream_plan_info(int64_t consumed, int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int64_t *out_begin,
+                                  int64_t *out_end, int64_t *hist_len, int64_t *n_pre_remove, int64_t *Lp, int *kernel,
+                                  int64_t *lds_bytes)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(out_begin && out_end && hist_len && n_pre_remove && Lp && kernel && lds_bytes, "resample_stream_plan_info: null output");
+    resample_stream_plan_info(consumed, T, up, down, nh, dtype, out_begin, out_end, hist_len, n_pre_remove, Lp, kernel, lds_bytes);
     TFX_API_END
 }
 

@@ -407,6 +407,47 @@ Tensor resample_op(const Tensor &x_in, int64_t up, int64_t down, const Tensor &h
     return y;
 }
 
+// One chunk of a resampling stream (tfx_resample_stream_forward): x [..., T] after `consumed` samples per row, h as for
+// resample_forward, hist [rows, H] (None = silence) -> (y [..., M(consumed + T) - M(consumed)], new history [rows, H])
+struct ResampleStreamPlan {
+    int64_t begin, end, H, pre, Lp, lds;
+    int kernel;
+};
+
+ResampleStreamPlan resample_stream_plan(const Tensor &x, const Tensor &h, int64_t up, int64_t down, int64_t consumed)
+{
+    TORCH_CHECK(x.dim() >= 1, "resample_stream_forward: x must have a time dimension");
+    TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kDouble, "resample_stream_forward: float32 or float64 only, got ",
+                x.scalar_type());
+    ResampleStreamPlan p{};
+    check_rc(tfx_resample_stream_plan_info(consumed, x.size(-1), up, down, h.numel(), x.scalar_type() == at::kFloat ? TFX_F32 : TFX_F64,
+                                           &p.begin, &p.end, &p.H, &p.pre, &p.Lp, &p.kernel, &p.lds),
+             "resample_stream_forward");
+    return p;
+}
+
+std::tuple<Tensor, Tensor> resample_stream_op(const Tensor &x_in, const Tensor &h, const OptTensor &hist, int64_t up, int64_t down,
+                                              int64_t consumed)
+{
+    need_device(x_in, "x");
+    TORCH_CHECK(!h.is_cuda() && h.dim() == 1 && h.numel() >= 1, "resample_stream_forward: h must be a non-empty 1-D host tensor");
+    TORCH_CHECK(h.scalar_type() == x_in.scalar_type(), "resample_stream_forward: h must have x's dtype (", x_in.scalar_type(),
+                "), got ", h.scalar_type());
+    const ResampleStreamPlan pl = resample_stream_plan(x_in, h, up, down, consumed);
+    const Tensor x = x_in.contiguous(), hc = h.contiguous();
+    const int64_t T = x.size(-1), rows = stream_rows(x);
+    const Tensor hin = stream_hist_in(hist, x, rows, pl.H, "resample_stream_forward");
+    std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
+    shape.back() = pl.end - pl.begin;
+    Tensor y = at::empty(shape, x.options()), hout = at::empty({rows, pl.H}, x.options());
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_resample_stream_forward(x.data_ptr(), y.data_ptr(), dtype_code(x, "resample_stream_forward"), rows, T, up, down,
+                                         hc.data_ptr(), hc.numel(), consumed, hin.defined() ? hin.data_ptr() : nullptr,
+                                         hout.data_ptr(), stream_of(x)),
+             "resample_stream_forward");
+    return {y, hout};
+}
+
 // ---------------------------------------------------------------------------------------------------
 // FIR (fir.py:556-568) and overlap-save FFT convolution (_fftconv.py:70-141)
 // ---------------------------------------------------------------------------------------------------
@@ -726,6 +767,14 @@ Tensor resample_meta(const Tensor &x, int64_t up, int64_t down, const Tensor &)
 {
     return at::empty(resample_shape(x, up, down), x.options());
 }
+std::tuple<Tensor, Tensor> resample_stream_meta(const Tensor &x, const Tensor &h, const OptTensor &, int64_t up, int64_t down,
+                                                int64_t consumed)
+{
+    const ResampleStreamPlan pl = resample_stream_plan(x, h, up, down, consumed);
+    std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
+    shape.back() = pl.end - pl.begin;
+    return {at::empty(shape, x.options()), at::empty({stream_rows(x), pl.H}, x.options())};
+}
 Tensor delay_meta(const Tensor &x, int64_t delay_samples, at::ArrayRef<double> amps, double, bool)
 {
     return at::empty(delay_shape(x, delay_samples, (int64_t)amps.size()), x.options());
@@ -773,6 +822,7 @@ TORCH_LIBRARY(torchfx_hip, m)
     m.def("delay_line_forward(Tensor(a) x, int delay_samples, float decay, float mix) -> Tensor(a)");
     m.def("delay_forward(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong) -> Tensor");
     m.def("resample_forward(Tensor x, int up, int down, Tensor h) -> Tensor");
+    m.def("resample_stream_forward(Tensor x, Tensor h, Tensor? hist, int up, int down, int consumed) -> (Tensor, Tensor)");
     m.def("delay_forward_ep(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong, float gain, bool clamp, int stat_mode, "
           "bool per_row) -> (Tensor, Tensor)");
     m.def("delay_stream_forward(Tensor x, Tensor? hist, int delay_samples, float[] amps, float mix, bool pingpong) -> (Tensor, Tensor)");
@@ -809,6 +859,7 @@ TORCH_LIBRARY_IMPL(torchfx_hip, CUDA, m)          // "CUDA" is the dispatch key 
     m.impl("delay_line_forward", delay_line_op);
     m.impl("delay_forward", delay_op);
     m.impl("resample_forward", resample_op);
+    m.impl("resample_stream_forward", resample_stream_op);
     m.impl("delay_forward_ep", delay_ep_op);
     m.impl("delay_stream_forward", delay_stream_op);
     m.impl("delay_line_stream_forward", delay_line_stream_op);
@@ -841,6 +892,7 @@ TORCH_LIBRARY_IMPL(torchfx_hip, Meta, m)
     m.impl("fft_conv_forward", fft_conv_meta);
     m.impl("delay_forward", delay_meta);
     m.impl("resample_forward", resample_meta);
+    m.impl("resample_stream_forward", resample_stream_meta);
     m.impl("delay_forward_ep", delay_ep_meta);
     m.impl("delay_stream_forward", delay_stream_meta);
     m.impl("delay_line_stream_forward", delay_line_stream_meta);
@@ -861,7 +913,7 @@ static void no_cpu_boxed(const c10::OperatorHandle &op, c10::DispatchKeySet, tor
 TORCH_LIBRARY_IMPL(torchfx_hip, CPU, m)
 {
     for (const char *name : {"sos_forward", "sos_forward_sections", "sos_bank_forward", "sos_bank_sum_forward", "biquad_forward",
-                             "delay_line_forward", "delay_forward", "delay_forward_ep", "delay_stream_forward", "delay_line_stream_forward", "resample_forward", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
+                             "delay_line_forward", "delay_forward", "delay_forward_ep", "delay_stream_forward", "delay_line_stream_forward", "resample_forward", "resample_stream_forward", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
                              "fft_conv_forward_ep", "sos_fft_conv_forward", "normalize_apply", "sum_forward", "gain_forward", "quantile_abs", "stat_forward",
                              "normalize_forward", "deinterleave_forward", "deinterleave_into", "interleave_forward"})
         m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());

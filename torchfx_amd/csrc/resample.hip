@@ -99,12 +99,17 @@ static ResampleTiling resample_tiling(int64_t up, int64_t down, int64_t pre, int
 
 template <typename T> struct ResampleArgs {
     const T *x;                 // [rows, T_]
-    T *y;                       // [rows, n_out]
+    T *y;                       // [rows, n_out - m_begin]
     const T *hp;                // [up, Lp]
     int64_t T_, n_out, tiles;
     int64_t up, down, pre, pre_div, Lp;
     int64_t halo;               // window inputs behind x[n / up] of the tile's first output: LP - 1 (>= Lp - 1)
     int64_t G, E, span, tile_out;
+    // stream only: x holds the absolute inputs [N, N + T_), hist the H before them (null: zeros); the launch computes outputs
+    // [m_begin, n_out) in tiles from m_base = m_begin rounded down to a multiple of up, and writes the new history to hist_out
+    const T *hist;              // [rows, H]
+    T *hist_out;                // [rows, H]
+    int64_t N, H, m_begin, m_base;
 };
 
 constexpr int RS_STAGE_BATCH = 8;                         // staging loads in flight per thread
@@ -113,15 +118,39 @@ constexpr int RS_STAGE_BATCH = 8;                         // staging loads in fl
 // Register taps run LP terms per output: the extra ones are 0 * x[n / up - j] for j >= Lp, exact (+0 or -0 added) while the
 // window is finite.  A workgroup whose window holds a NaN or an Inf sums exactly the Lp terms SciPy sums instead, so the
 // non-finite samples poison the same outputs.
-template <typename T, int LP, bool STAGE>
+// STREAM: one chunk of a stream (tfx_resample_stream_forward).  Inputs come from the history and the chunk by absolute index,
+// zeros before the history and past the chunk; the per-output sum (order, taps, start from +0) is the one-shot kernel's, so a
+// finite stream gives its bits.  Tile 0 of every row also writes the row's new history.
+template <typename T, bool STREAM>
+__device__ __forceinline__ T rs_load(const ResampleArgs<T> &p, const T *xr, const T *hr, int64_t i)
+{
+    if (!STREAM) return (i >= 0 && i < p.T_) ? xr[i] : (T)0;
+    const int64_t k = i - p.N;
+    if (k >= 0) return k < p.T_ ? xr[k] : (T)0;
+    return (hr && k >= -p.H) ? hr[k + p.H] : (T)0;
+}
+
+template <typename T, int LP, bool STAGE, bool STREAM>
 __global__ void __launch_bounds__(RS_THREADS) resample_kernel(const ResampleArgs<T> p)
 {
     extern __shared__ unsigned char rs_lds_raw[];
     T *win = (T *)rs_lds_raw;
     const int64_t row = blockIdx.x / p.tiles, tile = blockIdx.x % p.tiles;
     const T *xr = p.x + row * p.T_;
-    T *yr = p.y + row * p.n_out;
-    const int64_t m0 = tile * p.tile_out;                          // a multiple of up
+    const T *hr = STREAM && p.hist ? p.hist + row * p.H : nullptr;
+    const int64_t mb = STREAM ? p.m_begin : 0;
+    T *yr = p.y + row * (p.n_out - mb);
+    if (STREAM) {
+        if (tile == 0) {                                            // new history: the last H of [hist | chunk]
+            T *ho = p.hist_out + row * p.H;
+            for (int64_t k = threadIdx.x; k < p.H; k += RS_THREADS) {
+                const int64_t v = k + p.T_;
+                ho[k] = v >= p.H ? xr[v - p.H] : (hr ? hr[v] : (T)0);
+            }
+        }
+        if (p.n_out <= mb) return;                                  // a chunk that completes no output (uniform per launch)
+    }
+    const int64_t m0 = (STREAM ? p.m_base : 0) + tile * p.tile_out;     // a multiple of up
     const int64_t s0 = (m0 / p.up) * p.down + p.pre_div - p.halo;    // first input of the window
     bool finite = true;
     if (STAGE) {
@@ -132,8 +161,7 @@ __global__ void __launch_bounds__(RS_THREADS) resample_kernel(const ResampleArgs
 #pragma unroll
             for (int u = 0; u < RS_STAGE_BATCH; ++u) {
                 const int j = j0 + u * RS_THREADS + (int)threadIdx.x;
-                const int64_t i = s0 + j;
-                v[u] = (j < span && i >= 0 && i < p.T_) ? xr[i] : (T)0;
+                v[u] = j < span ? rs_load<T, STREAM>(p, xr, hr, s0 + j) : (T)0;
             }
 #pragma unroll
             for (int u = 0; u < RS_STAGE_BATCH; ++u) {
@@ -159,28 +187,32 @@ __global__ void __launch_bounds__(RS_THREADS) resample_kernel(const ResampleArgs
             for (int64_t e = 0; e < p.E; ++e) {
                 const int64_t m = m0 + q + step * e;
                 if (m >= p.n_out) break;
+                if (STREAM && m < mb) continue;
                 const T *w = win + ((int)last + wstep * (int)e);
                 T acc = (T)0;
 #pragma unroll
                 for (int j = (LP > 0 ? LP : 1) - 1; j >= 0; --j) acc = fma(tap[j], w[-j], acc);
-                yr[m] = acc;
+                yr[m - mb] = acc;
             }
             continue;
         }
         for (int64_t e = 0; e < p.E; ++e) {
             const int64_t m = m0 + q + step * e;
             if (m >= p.n_out) break;
+            if (STREAM && m < mb) continue;
             const int64_t li = last + (int64_t)wstep * e;
             T acc = (T)0;
             if (STAGE) {
                 const T *w = win + li;
                 for (int64_t j = p.Lp - 1; j >= 0; --j) acc = fma(h[j], w[-j], acc);
             } else {
-                const int64_t i = s0 + li;                          // x[i - j], j < Lp, inside [0, T)
-                const int64_t j_lo = i - p.T_ + 1 > 0 ? i - p.T_ + 1 : 0, j_hi = i < p.Lp - 1 ? i : p.Lp - 1;
-                for (int64_t j = j_hi; j >= j_lo; --j) acc = fma(h[j], xr[i - j], acc);
+                // x[i - j], j < Lp, inside the inputs there are: [0, T) (stream: [max(0, N - H), N + T))
+                const int64_t i = s0 + li;
+                const int64_t lo = STREAM ? (p.N - p.H > 0 ? p.N - p.H : 0) : 0, hi = (STREAM ? p.N : 0) + p.T_ - 1;
+                const int64_t j_lo = i - hi > 0 ? i - hi : 0, j_hi = i - lo < p.Lp - 1 ? i - lo : p.Lp - 1;
+                for (int64_t j = j_hi; j >= j_lo; --j) acc = fma(h[j], STREAM ? rs_load<T, true>(p, xr, hr, i - j) : xr[i - j], acc);
             }
-            yr[m] = acc;
+            yr[m - mb] = acc;
         }
     }
 }
@@ -235,49 +267,64 @@ void resample_plan_info(int64_t T, int64_t up, int64_t down, int64_t nh, int dty
     *lds_bytes = t.lds;
 }
 
-// polyphase tables by content: the taps' bytes plus (up, down, dtype, n_pre_pad, Lp)
+// polyphase tables by content: the taps' bytes plus (up, down, dtype, n_pre_pad, Lp).  A stream's table has Lp_s taps per phase,
+// a one-shot call's SciPy's Lp >= Lp_s: the two share an entry wherever the geometry agrees.
 static PlanCache<DeviceBuffer, 5> g_tables(32, "resample_forward");
+
+template <typename T>
+static const T *resample_table(const void *taps_host, int64_t nh, int64_t up, int64_t down, int64_t pre_pad, int64_t Lp,
+                               hipStream_t stream, std::shared_ptr<DeviceBuffer> *keep)
+{
+    const int64_t tail[5] = {up, down, (int64_t)sizeof(T), pre_pad, Lp};
+    *keep = g_tables.get(taps_host, (size_t)nh * sizeof(T), tail, stream, [&] {
+        std::vector<T> hp((size_t)(up * Lp), (T)0);
+        const T *h = (const T *)taps_host;
+        for (int64_t k = 0; k < nh; ++k) {                       // h_padded[pre_pad + k] = h[k] -> hp[p][j], p + j*up
+            const int64_t s = pre_pad + k;
+            hp[(size_t)((s % up) * Lp + s / up)] = h[k];
+        }
+        return std::make_shared<DeviceBuffer>(hp);
+    });
+    return (const T *)(*keep)->p;
+}
+
+template <typename T, bool STREAM>
+static void resample_dispatch(const ResampleArgs<T> &p, int64_t rows, const ResampleTiling &t, hipStream_t stream)
+{
+    static const char *const names[2][3] = {{"resample_reg_kernel", "resample_lds_kernel", "resample_gather_kernel"},
+                                            {"resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel"}};
+    const int64_t nwg = rows * p.tiles;
+    TFX_CHECK(nwg < (1ll << 31), "resample_forward: grid too large");
+    const dim3 grid((unsigned)nwg), block(RS_THREADS);
+    ProfScope ps(names[STREAM][t.kernel], stream);
+    if (t.kernel == RS_REG) {
+        switch (t.LP) {
+        case 8: hipLaunchKernelGGL((resample_kernel<T, 8, true, STREAM>), grid, block, (size_t)t.lds, stream, p); break;
+        case 16: hipLaunchKernelGGL((resample_kernel<T, 16, true, STREAM>), grid, block, (size_t)t.lds, stream, p); break;
+        case 24: hipLaunchKernelGGL((resample_kernel<T, 24, true, STREAM>), grid, block, (size_t)t.lds, stream, p); break;
+        case 32: hipLaunchKernelGGL((resample_kernel<T, 32, true, STREAM>), grid, block, (size_t)t.lds, stream, p); break;
+        case 48: hipLaunchKernelGGL((resample_kernel<T, 48, true, STREAM>), grid, block, (size_t)t.lds, stream, p); break;
+        default: hipLaunchKernelGGL((resample_kernel<T, 64, true, STREAM>), grid, block, (size_t)t.lds, stream, p); break;
+        }
+    } else if (t.kernel == RS_LDS) {
+        hipLaunchKernelGGL((resample_kernel<T, 0, true, STREAM>), grid, block, (size_t)t.lds, stream, p);
+    } else {
+        hipLaunchKernelGGL((resample_kernel<T, 0, false, STREAM>), grid, block, 0, stream, p);
+    }
+    TFX_HIP(hipGetLastError());
+}
 
 template <typename T>
 static void resample_launch(const void *x, void *y, int64_t rows, int64_t T_, int64_t up, int64_t down, const void *taps_host,
                             int64_t nh, const ResampleGeom &g, const ResampleTiling &t, hipStream_t stream)
 {
-    const int64_t tail[5] = {up, down, (int64_t)sizeof(T), g.pre_pad, g.Lp};
-    std::shared_ptr<DeviceBuffer> table = g_tables.get(taps_host, (size_t)nh * sizeof(T), tail, stream, [&] {
-        std::vector<T> hp((size_t)(up * g.Lp), (T)0);
-        const T *h = (const T *)taps_host;
-        for (int64_t k = 0; k < nh; ++k) {                       // h_padded[g.pre_pad + k] = h[k] -> hp[p][j], p + j*up
-            const int64_t s = g.pre_pad + k;
-            hp[(size_t)((s % up) * g.Lp + s / up)] = h[k];
-        }
-        return std::make_shared<DeviceBuffer>(hp);
-    });
+    std::shared_ptr<DeviceBuffer> table;
     ResampleArgs<T> p{};
-    p.x = (const T *)x; p.y = (T *)y; p.hp = (const T *)table->p;
+    p.x = (const T *)x; p.y = (T *)y; p.hp = resample_table<T>(taps_host, nh, up, down, g.pre_pad, g.Lp, stream, &table);
     p.T_ = T_; p.n_out = g.n_out; p.up = up; p.down = down; p.pre = g.pre_remove; p.pre_div = g.pre_remove * down / up; p.Lp = g.Lp;
     p.G = t.G; p.E = t.E; p.span = t.span; p.tile_out = t.tile_out; p.halo = t.LP - 1;
     p.tiles = ceil_div(g.n_out, t.tile_out);
-    const int64_t nwg = rows * p.tiles;
-    TFX_CHECK(nwg < (1ll << 31), "resample_forward: grid too large");
-    const dim3 grid((unsigned)nwg), block(RS_THREADS);
-    if (t.kernel == RS_REG) {
-        ProfScope ps("resample_reg_kernel", stream);
-        switch (t.LP) {
-        case 8: hipLaunchKernelGGL((resample_kernel<T, 8, true>), grid, block, (size_t)t.lds, stream, p); break;
-        case 16: hipLaunchKernelGGL((resample_kernel<T, 16, true>), grid, block, (size_t)t.lds, stream, p); break;
-        case 24: hipLaunchKernelGGL((resample_kernel<T, 24, true>), grid, block, (size_t)t.lds, stream, p); break;
-        case 32: hipLaunchKernelGGL((resample_kernel<T, 32, true>), grid, block, (size_t)t.lds, stream, p); break;
-        case 48: hipLaunchKernelGGL((resample_kernel<T, 48, true>), grid, block, (size_t)t.lds, stream, p); break;
-        default: hipLaunchKernelGGL((resample_kernel<T, 64, true>), grid, block, (size_t)t.lds, stream, p); break;
-        }
-    } else if (t.kernel == RS_LDS) {
-        ProfScope ps("resample_lds_kernel", stream);
-        hipLaunchKernelGGL((resample_kernel<T, 0, true>), grid, block, (size_t)t.lds, stream, p);
-    } else {
-        ProfScope ps("resample_gather_kernel", stream);
-        hipLaunchKernelGGL((resample_kernel<T, 0, false>), grid, block, 0, stream, p);
-    }
-    TFX_HIP(hipGetLastError());
+    resample_dispatch<T, false>(p, rows, t, stream);
 }
 
 void resample_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down, const void *taps_host,
@@ -298,6 +345,160 @@ void resample_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T
     if (rows == 0 || g.n_out == 0) return;
     if (dtype == TFX_F32) resample_launch<float>(x, y, rows, T, up, down, taps_host, nh, g, t, stream);
     else resample_launch<double>(x, y, rows, T, up, down, taps_host, nh, g, t, stream);
+}
+
+// ---- streams: one chunk per launch --------------------------------------------------------------------------------------
+// The geometry a stream fixes up front (up, down reduced): SciPy's n_pre_pad and n_pre_remove, Lp_s = ceil((nh + n_pre_pad) / up)
+// taps per phase (no length-dependent post-padding) and the H = Lp_s - 1 inputs each row carries.  After N inputs the stream
+// has emitted M(N) = max(0, ceil(N*up/down) - n_pre_remove) outputs: output m reads inputs up to (m + n_pre_remove)*down/up,
+// which is < N for every m < M(N), and none older than N - H for m >= M(N).
+struct ResampleStreamGeom {
+    int64_t pre_pad, pre_remove, Lp, H, m_begin, m_end;
+};
+
+static int64_t stream_emitted(int64_t N, int64_t up, int64_t down, int64_t pre)
+{
+    const int64_t m = ceil_div(N * up, down) - pre;
+    return m > 0 ? m : 0;
+}
+
+static ResampleStreamGeom resample_stream_geometry(int64_t N, int64_t T, int64_t up, int64_t down, int64_t nh)
+{
+    ResampleStreamGeom g{};
+    if (up == down) {                                           // a copy: nothing held back, nothing carried
+        g.m_begin = N;
+        g.m_end = N + T;
+        return g;
+    }
+    const int64_t half_len = (nh - 1) / 2;
+    g.pre_pad = down - half_len % down;
+    g.pre_remove = (half_len + g.pre_pad) / down;
+    g.Lp = ceil_div(nh + g.pre_pad, up);
+    g.H = g.Lp - 1;
+    g.m_begin = stream_emitted(N, up, down, g.pre_remove);
+    g.m_end = stream_emitted(N + T, up, down, g.pre_remove);
+    return g;
+}
+
+static void resample_stream_plan(int64_t N, int64_t T, int64_t *up, int64_t *down, int64_t nh, int esz, ResampleStreamGeom *g,
+                                 ResampleTiling *t)
+{
+    const int64_t d = gcd64(*up, *down);
+    *up /= d;
+    *down /= d;
+    *g = resample_stream_geometry(N, T, *up, *down, nh);
+    *t = resample_tiling(*up, *down, g->pre_remove, g->Lp, esz);
+}
+
+// [a, a + na) and [b, b + nb) share no byte (null pointers and empty ranges share none)
+static bool rs_disjoint(const void *a, size_t na, const void *b, size_t nb)
+{
+    if (!a || !b || !na || !nb) return true;
+    const char *p = (const char *)a, *q = (const char *)b;
+    return p + na <= q || q + nb <= p;
+}
+
+void resample_stream_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
+                           const void *taps_host, int64_t nh, int64_t consumed, const void *hist_in, const void *hist_out)
+{
+    TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "resample_stream_forward: bad dtype %d", dtype);
+    TFX_CHECK(up >= 1 && down >= 1, "resample_stream_forward: up and down must be >= 1, got %lld / %lld", (long long)up,
+              (long long)down);
+    TFX_CHECK(rows >= 0 && T >= 0 && consumed >= 0, "resample_stream_forward: negative size or consumed count");
+    TFX_CHECK(nh >= 1 && taps_host, "resample_stream_forward: no taps");
+    TFX_CHECK(up <= (1ll << 24) && down <= (1ll << 24) && nh <= (1ll << 30), "resample_stream_forward: up, down or taps too large");
+    TFX_CHECK(T <= INT64_MAX / 8 - consumed && consumed + T <= (INT64_MAX / 4) / (up * down),
+              "resample_stream_forward: (consumed + T) * up * down overflows");
+    const int esz = dtype == TFX_F32 ? 4 : 8;
+    ResampleStreamGeom g;
+    ResampleTiling t;
+    resample_stream_plan(consumed, T, &up, &down, nh, esz, &g, &t);
+    const int64_t n_y = g.m_end - g.m_begin;
+    TFX_CHECK(rows == 0 || (T <= INT64_MAX / 16 / rows && n_y <= INT64_MAX / 16 / rows && g.H <= INT64_MAX / 16 / rows),
+              "resample_stream_forward: size overflows");
+    TFX_CHECK((x || rows * T == 0) && (y || rows * n_y == 0) && (hist_out || rows * g.H == 0), "resample_stream_forward: null pointer");
+    const size_t xb = (size_t)(rows * T) * esz, yb = (size_t)(rows * n_y) * esz, hb = (size_t)(rows * g.H) * esz;
+    TFX_CHECK(rs_disjoint(hist_in, hb, hist_out, hb), "resample_stream_forward: the new history needs its own buffer");
+    TFX_CHECK(rs_disjoint(y, yb, x, xb) && rs_disjoint(y, yb, hist_in, hb) && rs_disjoint(hist_out, hb, x, xb) &&
+                  rs_disjoint(y, yb, hist_out, hb),
+              "resample_stream_forward: y and hist_out may not overlap x, hist_in or each other");
+}
+
+// host-only: what resample_stream_forward does with a chunk of T samples after `consumed` (arguments as resample_stream_check's)
+void resample_stream_plan_info(int64_t consumed, int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int64_t *out_begin,
+                               int64_t *out_end, int64_t *hist_len, int64_t *pre_remove, int64_t *Lp, int *kernel,
+                               int64_t *lds_bytes)
+{
+    const int one = 1;
+    resample_stream_check(&one, &one, dtype, 0, T, up, down, &one, nh, consumed, nullptr, nullptr);
+    ResampleStreamGeom g;
+    ResampleTiling t;
+    resample_stream_plan(consumed, T, &up, &down, nh, dtype == TFX_F32 ? 4 : 8, &g, &t);
+    *out_begin = g.m_begin;
+    *out_end = g.m_end;
+    *hist_len = g.H;
+    *pre_remove = g.pre_remove;
+    *Lp = g.Lp;
+    *kernel = t.kernel;
+    *lds_bytes = t.lds;
+}
+
+constexpr int64_t RS_STREAM_MIN_WG = 256;                // one workgroup per CU
+
+// A chunk can be short next to a whole signal (2 x 512 in real time is a tile or two): halve the outputs per thread until the
+// launch has RS_STREAM_MIN_WG workgroups (or E = 1).  Not further: below ~8 outputs per thread the register taps are loaded for
+// too few outputs (a 1536-workgroup target made 64 x 65536-sample chunks at 160/147 1.6x slower).  The sum each output gets
+// does not depend on the tiling.
+static ResampleTiling stream_tiling(ResampleTiling t, int64_t rows, int64_t up, int64_t down, int64_t pre, int64_t n_tile_out,
+                                    int esz)
+{
+    while (t.E > 1 && rows * ceil_div(n_tile_out, t.tile_out) < RS_STREAM_MIN_WG) {
+        t.E = (t.E + 1) / 2;
+        t.tile_out = up * t.G * t.E;
+        if (t.kernel != RS_GATHER) {
+            t.span = window_span(up, down, pre, t.LP, t.G, t.E);
+            t.lds = t.span * esz;
+        }
+    }
+    return t;
+}
+
+template <typename T>
+static void resample_stream_launch(const void *x, void *y, int64_t rows, int64_t T_, int64_t up, int64_t down,
+                                   const void *taps_host, int64_t nh, int64_t N, const void *hist_in, void *hist_out,
+                                   const ResampleStreamGeom &g, const ResampleTiling &t0, hipStream_t stream)
+{
+    const int64_t m_base = g.m_begin / up * up;
+    const ResampleTiling t = stream_tiling(t0, rows, up, down, g.pre_remove, g.m_end - m_base, (int)sizeof(T));
+    std::shared_ptr<DeviceBuffer> table;
+    ResampleArgs<T> p{};
+    p.x = (const T *)x; p.y = (T *)y; p.hp = resample_table<T>(taps_host, nh, up, down, g.pre_pad, g.Lp, stream, &table);
+    p.T_ = T_; p.n_out = g.m_end; p.up = up; p.down = down; p.pre = g.pre_remove; p.pre_div = g.pre_remove * down / up; p.Lp = g.Lp;
+    p.G = t.G; p.E = t.E; p.span = t.span; p.tile_out = t.tile_out; p.halo = t.LP - 1;
+    p.hist = (const T *)hist_in; p.hist_out = (T *)hist_out; p.N = N; p.H = g.H;
+    p.m_begin = g.m_begin; p.m_base = m_base;
+    // at least one tile per row: tile 0 writes the new history even when the chunk completes no output
+    p.tiles = std::max<int64_t>(1, ceil_div(g.m_end - p.m_base, t.tile_out));
+    resample_dispatch<T, true>(p, rows, t, stream);
+}
+
+void resample_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
+                             const void *taps_host, int64_t nh, int64_t consumed, const void *hist_in, void *hist_out,
+                             hipStream_t stream)
+{
+    resample_stream_check(x, y, dtype, rows, T, up, down, taps_host, nh, consumed, hist_in, hist_out);
+    const int esz = dtype == TFX_F32 ? 4 : 8;
+    ResampleStreamGeom g;
+    ResampleTiling t;
+    resample_stream_plan(consumed, T, &up, &down, nh, esz, &g, &t);
+    if (rows == 0) return;
+    if (t.kernel == RS_COPY) {                                  // up == down: y = x, no history
+        if (T) TFX_HIP(hipMemcpyAsync(y, x, (size_t)(rows * T * esz), hipMemcpyDeviceToDevice, stream));
+        return;
+    }
+    if (g.m_end == g.m_begin && g.H == 0) return;               // nothing to emit and nothing to carry
+    if (dtype == TFX_F32) resample_stream_launch<float>(x, y, rows, T, up, down, taps_host, nh, consumed, hist_in, hist_out, g, t, stream);
+    else resample_stream_launch<double>(x, y, rows, T, up, down, taps_host, nh, consumed, hist_in, hist_out, g, t, stream);
 }
 
 void resample_clear() { g_tables.clear(); }

@@ -13,7 +13,9 @@ stages too; its kernels read the history and the chunk from two buffers (``tfx_f
 there is no concatenated copy of the chunk.  :class:`StatefulDelay` and :class:`StatefulReverb` do the same for the two
 time-based effects: they carry the last ``taps * delay_samples`` (``delay``) input samples of every row, return chunks of the
 chunk's shape, and one launch per chunk (``tfx_delay_stream_forward`` / ``tfx_delay_line_stream_forward``) gives the
-one-shot effect's bits.
+one-shot effect's bits.  :class:`StatefulResample` converts the rate of a stream: it carries the last ``Lp_s - 1`` inputs of
+every row, returns the outputs each chunk completes (``tfx_resample_stream_forward``), and its chunks plus ``flush()`` are
+``resample_poly`` on the whole signal.
 
 Small chunks are launch-bound (a 2 x 4096 step is ~60 us of host + launch overhead for a few us of
 GPU work), so ``StreamProcessor(..., use_graph=True)`` captures one full-size chunk step -- every
@@ -36,7 +38,7 @@ from torch import Tensor, nn
 from torchfx_amd.effect import FX, Delay, MonoDelayStrategy, PingPongDelayStrategy, Reverb, _ext
 from torchfx_amd.filter._base import AbstractFilter
 from torchfx_amd.filter.fir import FIR
-from torchfx_amd.resample import Resample
+from torchfx_amd.resample import Resample, design_taps, window_key
 
 
 class StatefulFIR(FIR):
@@ -213,6 +215,150 @@ class StatefulReverb(Reverb):
         return Reverb.forward(self, v.reshape(*x.shape[:-1], D + T))[..., D:]
 
 
+class StatefulResample(Resample):
+    """:class:`~torchfx_amd.resample.Resample` over a continuous stream: chunks go in, the converted signal comes out in
+    pieces with no seam.  After chunks of ``N`` input samples per row in all the stream has returned exactly
+    ``M(N) = max(0, ceil(N * up / down) - latency)`` outputs, each final; :meth:`flush` returns the ``latency`` (at most)
+    outputs still held back.  All chunk outputs followed by ``flush()`` are :func:`~torchfx_amd.resample.resample_poly` on the
+    whole signal, ``ceil(N * up / down)`` samples: on the device ``torch.equal`` to it for finite float32 / float64 input,
+    whatever the chunk sizes.  A chunk may return zero samples.
+
+    Every row carries its last ``history_length`` input samples in ``_hist``, and the stream two host integers: the inputs
+    consumed and the outputs emitted (so no chunk waits on the device).  Device float32 / float64 chunks run one launch each
+    (:func:`torchfx_ext.resample_stream_forward`); CPU chunks run ``scipy.signal.upfirdn`` on ``[history | chunk]``.  The
+    stream restarts from silence when the row count, dtype or device changes, and when ``new_fs``, ``fs`` or ``window``
+    changes between chunks -- the outputs still held back are then dropped.  A ``Wave`` is a whole signal: pipe it through
+    ``Resample`` or use ``Wave.resample`` instead."""
+
+    def __init__(self, new_fs: int, fs: int | None = None, window=("kaiser", 5.0)) -> None:
+        super().__init__(new_fs, fs, window)
+        self.reset_state()
+
+    def reset_state(self) -> None:
+        self._hist: Tensor | None = None
+        self._consumed = 0                          # N: input samples per row so far
+        self._emitted = 0                           # M(N): output samples per row so far
+        self._key: tuple | None = None              # (rows, dtype, device, new_fs, fs, window) of the running stream
+        self._geo: tuple[int, int] = (0, 0)         # its (n_pre_remove, history length)
+        self._last: tuple | None = None             # (leading shape, dtype, device) of the last chunk, for flush()
+
+    def _geometry(self, up: int, down: int) -> tuple[int, int]:
+        """``(n_pre_remove, Lp_s - 1)`` of the designed filter: the outputs held back and the history length."""
+        if up == down:
+            return 0, 0
+        nh = int(design_taps(up, down, self.window, torch.float32).numel())
+        half_len = (nh - 1) // 2
+        pre_pad = down - half_len % down
+        return (half_len + pre_pad) // down, -(-(nh + pre_pad) // up) - 1
+
+    @property
+    def latency(self) -> int:
+        """The outputs a stream holds back (``n_pre_remove``): what :meth:`flush` returns at most."""
+        return self._geometry(*self._ratio())[0]
+
+    @property
+    def history_length(self) -> int:
+        """The input samples every row carries between chunks (``Lp_s - 1``)."""
+        return self._geometry(*self._ratio())[1]
+
+    def route(self, x: Tensor, length: int | None = None) -> str:
+        """``native (<kernel>)`` for the next chunk of ``x`` (``length`` samples, default x's), or the host / refusal route."""
+        if not x.is_cuda or x.dtype not in (torch.float32, torch.float64):
+            return super().route(x, length)
+        from torchfx_amd import torchfx_ext
+
+        up, down = self._ratio()
+        if up == down:
+            return "native (copy)"
+        n = int(x.shape[-1]) if length is None else int(length)
+        taps = int(design_taps(up, down, self.window, x.dtype).numel())
+        return f"native ({torchfx_ext.resample_stream_plan_info(self._consumed, n, up, down, taps, x.dtype)['kernel']})"
+
+    def _emit_count(self, n: int, up: int, down: int, pre: int) -> int:
+        return max(0, -(-n * up // down) - pre)
+
+    @torch.no_grad()
+    def forward(self, x: Tensor) -> Tensor:
+        rows = _rows(x)
+        if x.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"StatefulResample: float32 or float64 signals only, got {x.dtype}")
+        up, down = self._ratio()
+        key = (rows, x.dtype, x.device, self.new_fs, self.fs, window_key(self.window))
+        if key != self._key:                        # a new stream: from silence
+            self.reset_state()
+            self._key, self._geo = key, self._geometry(up, down)
+        self._last = (tuple(x.shape[:-1]), x.dtype, x.device)
+        T = x.shape[-1]
+        if up == down:
+            y = x.clone()
+        else:
+            h = design_taps(up, down, self.window, x.dtype)
+            if x.is_cuda:
+                from torchfx_amd import torchfx_ext
+
+                with torch.cuda.device(x.device):
+                    y, self._hist = torchfx_ext.resample_stream_forward(x, h, self._hist, up, down, self._consumed)
+            else:
+                y = self._host_chunk(x, rows, up, down, h)
+        self._consumed += T
+        self._emitted = self._consumed if up == down else self._emit_count(self._consumed, up, down, self._geo[0])
+        return y
+
+    def _host_chunk(self, x: Tensor, rows: int, up: int, down: int, h: Tensor) -> Tensor:
+        """One chunk on the host: ``scipy.signal.upfirdn`` over ``[history | chunk]``, from a window start that is a multiple
+        of ``down`` so the phases are the whole signal's."""
+        import numpy as np
+        from scipy.signal import upfirdn
+
+        pre, H = self._geo
+        N, T = self._consumed, x.shape[-1]
+        xr = x.detach().reshape(rows, T)
+        hist = self._hist if self._hist is not None else torch.zeros(rows, H, dtype=x.dtype)
+        v = torch.cat([hist, xr], dim=-1)                   # absolute inputs [N - H, N + T), zeros before 0
+        self._hist = v[:, v.shape[-1] - H:].clone()
+        m0, m1 = self._emit_count(N, up, down, pre), self._emit_count(N + T, up, down, pre)
+        lead = tuple(x.shape[:-1])
+        if m1 == m0:
+            return torch.zeros(*lead, 0, dtype=x.dtype)
+        s = (N - H) // down * down                           # window start, <= N - H; inputs before N - H meet no tap
+        hn = h.numpy()
+        half_len = (hn.size - 1) // 2
+        hp = np.concatenate([np.zeros(down - half_len % down, dtype=hn.dtype), hn])
+        vv = np.concatenate([np.zeros((rows, N - H - s), dtype=hn.dtype), v.numpy()], axis=-1)
+        yu = upfirdn(hp, vv, up, down, axis=-1)
+        r0 = m0 + pre - up * (s // down)                      # upfirdn output r is output r + up*s/down - pre of the whole
+        out = np.zeros((rows, m1 - m0), dtype=yu.dtype)
+        got = yu[:, r0:r0 + m1 - m0]
+        out[:, :got.shape[-1]] = got
+        return torch.from_numpy(out.astype(hn.dtype, copy=False)).reshape(*lead, m1 - m0)
+
+    @torch.no_grad()
+    def flush(self) -> Tensor:
+        """The outputs still held back (``ceil(N * up / down) - M(N)``, at most :attr:`latency`), computed with zeros past
+        the end and shaped like the last chunk; then the state is reset.  Without a chunk since the last reset: an empty
+        tensor."""
+        if self._last is None:
+            return torch.zeros(0)
+        lead, dtype, device = self._last
+        up, down = self._ratio()
+        pre = self._geometry(up, down)[0]
+        N = self._consumed
+        rem = -(-N * up // down) - self._emitted
+        if rem <= 0:
+            tail = torch.zeros(*lead, 0, dtype=dtype, device=device)
+        else:
+            Z = -(-pre * down // up)                       # zeros that complete every held-back output
+            while self._emit_count(N + Z, up, down, pre) - self._emitted < rem:
+                Z += 1
+            tail = self.forward(torch.zeros(*lead, Z, dtype=dtype, device=device))[..., :rem].contiguous()
+        self.reset_state()
+        return tail
+
+
+def _has_stateful_resample(e) -> bool:
+    return any(isinstance(m, StatefulResample) for m in (e.modules() if isinstance(e, nn.Module) else [e]))
+
+
 class _ChunkRun:
     """``IIR ... | StatefulFIR | Gain`` (any non-empty sub-pattern of at least two effects) as ONE launch per small chunk
     (``torchfx_ext.chunk_forward``): the chain of a 2 x 512 block is launch-bound, not arithmetic-bound.  Consecutive
@@ -352,9 +498,14 @@ class StreamProcessor:
         for e in self._effects:
             if not isinstance(e, FX):
                 raise TypeError("All effects must inherit from FX when used in StreamProcessor")
-            if any(isinstance(m, Resample) for m in e.modules()):
+            if not isinstance(e, StatefulResample) and any(isinstance(m, Resample) for m in e.modules()):
                 raise TypeError("Resample cannot run in StreamProcessor: resampling each chunk on its own leaves a seam at "
-                                "every chunk boundary; resample the whole signal (Wave.resample) before or after streaming")
+                                "every chunk boundary; use StatefulResample as a top-level effect of the chain, or resample "
+                                "the whole signal (Wave.resample) before or after streaming")
+        self._resamplers = [e for e in self._effects if isinstance(e, StatefulResample)]
+        if self._resamplers and overlap != 0:
+            raise ValueError(f"A chain with a StatefulResample needs overlap = 0, got {overlap}: dropped overlap samples "
+                             "have no counterpart in the resampled output")
         self._chunk_size, self._overlap, self._device = chunk_size, overlap, device
         self._use_graph = use_graph
         self._graph = None            # (CUDAGraph, static in, static out, stream, signature, state slots, homes)
@@ -372,9 +523,10 @@ class StreamProcessor:
         return None
 
     def _configure_effects(self, fs: int) -> None:
-        """fs propagation, redesign on change, Nyquist check (``stream.py:119-162``)."""
-        nyquist = fs / 2.0
+        """fs propagation, redesign on change, Nyquist check (``stream.py:119-162``).  The effects are walked in order with
+        a running rate: a ``StatefulResample`` gets the rate it receives and the effects after it get its ``new_fs``."""
         for e in self._effects:
+            nyquist = fs / 2.0
             cutoff = getattr(e, "cutoff", None)
             if isinstance(e, AbstractFilter) and isinstance(cutoff, (int, float)) and cutoff >= nyquist:
                 raise ValueError(
@@ -388,6 +540,14 @@ class StreamProcessor:
                         e.reset_state()
             if isinstance(e, AbstractFilter) and not e._has_computed_coeff:
                 e.compute_coefficients()
+            if isinstance(e, StatefulResample):
+                fs = e.new_fs
+
+    def output_rate(self, fs: int) -> int:
+        """The sample rate of the chain's output for an input at ``fs``."""
+        for e in self._resamplers:
+            fs = e.new_fs
+        return fs
 
     # ---- HIP-graph replay of the per-chunk step ------------------------------------------------
     _STATE_ATTRS = ("_state_x", "_state_y", "_hist")
@@ -411,10 +571,24 @@ class StreamProcessor:
         the copy-in / replay / copy-out of a graph step)."""
         return len(self._segments) == 1 and isinstance(self._segments[0], _ChunkRun) and self._segments[0].fuses(w)
 
-    def _run(self, w: Tensor) -> Tensor:
-        for e in self._segments:
+    def _run(self, w: Tensor, start: int = 0) -> Tensor | None:
+        """The chain from segment ``start`` on; None when a resampler completes no output for this chunk (the effects
+        after it are not called)."""
+        for e in self._segments[start:]:
             w = e(w)
+            if isinstance(e, StatefulResample) and w.shape[-1] == 0:
+                return None
         return w
+
+    def _tails(self) -> Generator[Tensor, None, None]:
+        """The end of the stream: every resampler's held-back outputs, left to right, through the effects after it."""
+        for i, e in enumerate(self._segments):
+            if isinstance(e, StatefulResample):
+                t = e.flush()
+                if t.dim() > 0 and t.shape[-1] > 0:
+                    t = self._run(t, i + 1)
+                    if t is not None:
+                        yield t
 
     def _capture_members(self) -> list:
         """Members whose parameters a captured step bakes in and whose carried state can change length (StatefulDelay,
@@ -481,16 +655,19 @@ class StreamProcessor:
         while offset < n:
             w = x[..., offset:offset + self._chunk_size].to(self._device)
             full = w.shape[-1] == self._chunk_size
-            if self._use_graph and full and primed and w.is_cuda and not self._fused(w):
+            if self._use_graph and full and primed and w.is_cuda and not self._fused(w) and not self._resamplers:
                 w = self._graph_step(w)
             else:
                 w = self._run(w)            # first chunk creates the states; ragged tail runs eagerly
                 primed = True
-            yield w[..., self._overlap:] if (self._overlap > 0 and offset > 0) else w
+            if w is not None:
+                yield w[..., self._overlap:] if (self._overlap > 0 and offset > 0) else w
             offset += hop
+        yield from self._tails()
 
     @torch.no_grad()
     def process_tensor(self, x: Tensor, fs: int) -> Tensor:
+        """The whole processed signal; after a ``StatefulResample`` at the chain's output rate (:meth:`output_rate`)."""
         return torch.cat(list(self.process_chunks(x, fs)), dim=-1)
 
     # ---- files (``stream.py:164-347``) -------------------------------------------------------------
@@ -512,13 +689,17 @@ class StreamProcessor:
             frames, _ = sf.read(str(input_path), start=offset, stop=offset + n, dtype="float32", always_2d=True)
             # interleaved [n, C] -> planar [C, n] on the device (reference: data_np.T.copy() on the host)
             w = _io.upload_interleaved(frames, self._device) if on_gpu else torch.from_numpy(frames.T.copy())
-            if self._use_graph and on_gpu and primed and w.shape[-1] == self._chunk_size and not self._fused(w):
+            if (self._use_graph and on_gpu and primed and w.shape[-1] == self._chunk_size and not self._fused(w)
+                    and not self._resamplers):
                 w = self._graph_step(w)
             else:
                 w = self._run(w)
                 primed = True
-            yield (w[..., self._overlap:] if (self._overlap > 0 and offset > 0) else w), fs
+            if w is not None:
+                yield (w[..., self._overlap:] if (self._overlap > 0 and offset > 0) else w), fs
             offset += hop
+        for w in self._tails():
+            yield w, fs
 
     @torch.no_grad()
     def process_file_chunks(self, input_path) -> Generator[Tensor, None, None]:
@@ -532,7 +713,8 @@ class StreamProcessor:
                      subtype: str | None = None) -> None:
         """Process an audio file chunk by chunk into ``output_path`` (``stream.py:164-276``): output format
         from the extension (WAV when unknown), subtype FLOAT for WAV unless given, parent directories
-        created.  Chunks travel interleaved in both directions; the transposes run on the GPU."""
+        created.  Chunks travel interleaved in both directions; the transposes run on the GPU.  The file is written at
+        the chain's output rate (:meth:`output_rate`)."""
         import pathlib
 
         import soundfile as sf
@@ -546,7 +728,7 @@ class StreamProcessor:
             format = {".wav": "WAV", ".flac": "FLAC", ".ogg": "OGG"}.get(out.suffix.lower(), "WAV")  # noqa: A001
         if subtype is None:
             subtype = "FLOAT" if format == "WAV" else None
-        with sf.SoundFile(str(out), mode="w", samplerate=info.samplerate, channels=info.channels, format=format,
+        with sf.SoundFile(str(out), mode="w", samplerate=self.output_rate(info.samplerate), channels=info.channels, format=format,
                           subtype=subtype) as sink:
             hostbuf = None                                            # one host buffer for every chunk on its way out
             for w, _ in self._file_steps(input_path):
@@ -641,6 +823,9 @@ class RealtimeProcessor:
         for e in modules:
             if not isinstance(e, FX):
                 raise TypeError("All effects must inherit from FX when used in RealtimeProcessor")
+            if _has_stateful_resample(e):
+                raise TypeError("StatefulResample cannot run in RealtimeProcessor: a sound card's output block has the input "
+                                "block's length and sample rate; resample with StreamProcessor or Wave.resample instead")
         self._runner = StreamProcessor(modules, chunk_size=config.buffer_size, overlap=0, device=device, use_graph=use_graph)
         self._backend, self._config, self._running = backend, config, False
         self._buffer_capacity = buffer_capacity

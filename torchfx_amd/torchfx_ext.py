@@ -34,7 +34,7 @@ from torchfx_amd import native
 __all__ = [
     "biquad_forward", "sos_forward", "sos_bank_forward", "sos_bank_sum_forward", "delay_line_forward", "delay_forward",
     "delay_amplitudes", "delay_regime", "delay_stream_forward", "delay_line_stream_forward", "resample_forward",
-    "resample_plan_info",
+    "resample_plan_info", "resample_stream_forward", "resample_stream_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
 ]
@@ -189,6 +189,32 @@ def resample_plan_info(length: int, up: int, down: int, taps: int, dtype: torch.
                                             *[ctypes.byref(v) for v in o], ctypes.byref(k), ctypes.byref(lds)))
     return {"n_out": o[0].value, "n_pre_remove": o[1].value, "padded": o[2].value, "Lp": o[3].value,
             "kernel": RESAMPLE_KERNELS[k.value], "lds_bytes": lds.value}
+
+
+def resample_stream_forward(x: Tensor, h: Tensor, hist: Tensor | None, up: int, down: int,
+                            consumed: int) -> tuple[Tensor, Tensor]:
+    """One chunk of a resampling stream in one launch: ``x [..., T]`` follows ``consumed`` input samples per row, whose last
+    ``H`` are ``hist [rows, H]`` (None = silence).  Returns ``(y [..., M(consumed + T) - M(consumed)], new history [rows, H])``
+    with ``M(N) = max(0, ceil(N * up / down) - n_pre_remove)``: the outputs of :func:`resample_forward` on the whole signal
+    that these inputs complete (``tfx_resample_stream_forward``)."""
+    return native.ops().resample_stream_forward(x.contiguous(), h, hist, int(up), int(down), int(consumed))
+
+
+RESAMPLE_STREAM_KERNELS = ("resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel", "copy")
+
+
+def resample_stream_plan_info(consumed: int, length: int, up: int, down: int, taps: int,
+                              dtype: torch.dtype = torch.float32) -> dict:
+    """What :func:`resample_stream_forward` does with a chunk of ``length`` samples after ``consumed`` (host-only):
+    the outputs ``[out_begin, out_end)`` it emits, ``hist_len`` (H), ``n_pre_remove`` (outputs held back), ``Lp`` (taps per
+    phase), ``kernel`` and ``lds_bytes`` per workgroup."""
+    o = [ctypes.c_int64(0) for _ in range(5)]
+    k, lds = ctypes.c_int(0), ctypes.c_int64(0)
+    L.check(L.load().tfx_resample_stream_plan_info(int(consumed), int(length), int(up), int(down), int(taps),
+                                                   L.TFX_F64 if dtype == torch.float64 else L.TFX_F32,
+                                                   *[ctypes.byref(v) for v in o], ctypes.byref(k), ctypes.byref(lds)))
+    return {"out_begin": o[0].value, "out_end": o[1].value, "hist_len": o[2].value, "n_pre_remove": o[3].value,
+            "Lp": o[4].value, "kernel": RESAMPLE_STREAM_KERNELS[k.value], "lds_bytes": lds.value}
 
 
 _TAPS_HOST: dict = {}        # (id(base tensor), offset, numel, dtype wanted) -> (weakref to base, version, host tensor)
