@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
-"""bench.py -- the driver's benchmark contract for the torchfx.filter hot path on MI355X.
+"""bench.py -- the benchmark contract for the torchfx.filter hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: launched by torch.distributed.run, one rank per GPU)
+
+A plain run does only what the headline needs: it sets up, runs W warm-up and K timed steps, writes --dump-outputs and prints
+the line (metric, value, ms_per_step, dtype, config, device records, end_to_end).  ``--full`` adds everything else described
+below: the per-kernel table and roofline (the K steps once more with the library's HIP events), and at N = 1 the single-stream
+pass, ``variants``, ``stages``, the reference's published shapes, cfg 5 on one GPU and ``cpu_baseline``.
 
 A "step" is one pass of the hot path over one batch of synthetic audio already resident in HBM.
 Default workload = the configuration BASELINE.json's metric is quoted on: the fused pipe chain
@@ -11,13 +16,13 @@ GPU (configs[4] is 512 channels over 8 GPUs = 64 per GPU), executed THROUGH THE 
 step is ``(Wave(x) | f1 | f2 | fir | rev).ys`` -- pipe operators, plan lookup (plan cache) and the planned
 modules (default fusion policy) are all inside the timed region; ``end_to_end`` reports the first call
 (planning included) beside the steady state.
-At N = 1 the line also carries the driver-timed stage figures of configs[1..3] (``stages``) and two
-untimed variants of the chain (``variants``).  Channels shard across ranks with no data-path
+At N = 1 a --full line also carries the stage figures of configs[1..3] timed in this process (``stages``) and
+three variants of the chain (``variants``).  Channels shard across ranks with no data-path
 collective: ``--scaling weak`` (default) keeps 64 channels per GPU, ``--scaling strong
 --total-channels 512`` splits a fixed batch; ``--gather`` adds the final RCCL gather to rank 0 and
 reports ``value_with_gather`` beside ``value``.
 
-Prints ONE JSON line on rank 0.  ``roofline`` follows SURVEY.md 8(d): algorithmic bytes are 8 B per
+Prints ONE JSON line on rank 0.  ``roofline`` (--full) follows SURVEY.md 8(d): algorithmic bytes are 8 B per
 sample-channel (4 B read + 4 B written) for every stage and for the fused chain.  ``cpu_baseline``
 times the oracle (our CPU restatement of the reference path, pinned by golden vectors) on a bounded
 sample of the same workload -- a reported baseline, never a target.
@@ -519,9 +524,14 @@ def main() -> None:
     ap.add_argument("--total-channels", type=int, default=512, help="fixed batch of --scaling strong (cfg 5)")
     ap.add_argument("--seconds", type=float, default=None, help="signal length (default: 600 chain/fftconv, 60 sos/fir)")
     ap.add_argument("--gather", action="store_true", help="also time the final RCCL gather to rank 0")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel table and roofline (the timed steps once more "
+                         "with HIP events) and, at N = 1, the single-stream pass, variants, stages, published shapes, cfg 5 on one "
+                         "GPU and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only warm-up + timed steps (for rocprofv3 runs: no stage / variant / single-stream passes)")
+                    help="with --full: per-kernel table and roofline only (for rocprofv3 runs: no stage / variant / single-stream "
+                         "passes)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step returned as DIR/y.npy (rank 0; a seeded sample when above 32 MB)")
     args = ap.parse_args()
@@ -602,8 +612,10 @@ def main() -> None:
     elapsed, _, out = timed_region(step, args.steps, args.warmup, sync, lib, profile=False)      # THE timed region: wall clock only
     first_call_ms = timed_region.first_ms
     dumped = dump_outputs(out, args.dump_outputs) if args.dump_outputs and rank == 0 else None
-    out = None
-    elapsed_prof, prof, out = timed_region(step, args.steps, 0, sync, lib, profile=True)       # same steps again, with per-kernel events
+    elapsed_prof = prof = None
+    if args.full:
+        out = None
+        elapsed_prof, prof, out = timed_region(step, args.steps, 0, sync, lib, profile=True)   # same steps again, with per-kernel events
     # what the process group itself says about its size (an all-reduce of ones over RCCL / gloo), and which device
     # every rank drives -- WORLD_SIZE is only what the launcher claimed
     from torchfx_amd.distributed import ranks_seen as _ranks_seen
@@ -620,7 +632,7 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    extras = rank == 0 and world == 1 and not args.no_extras
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras
     # per-kernel durations without overlap: the overlap-save passes of consecutive slabs run on internal
     # streams in the timed region, which inflates each kernel's elapsed time; one extra, untimed pass on a
     # single stream gives the clean per-kernel numbers
@@ -739,14 +751,11 @@ def main() -> None:
         ms_step = elapsed / args.steps * 1e3
         samples = C * T
         value = total_rows * T / (elapsed / args.steps) / 1e6             # whole-job Msamples/s (all ranks' rows / slowest rank's time)
-        kernels = kernel_table(prof, args.steps)
-        # per-kernel HBM model: the bytes each launch group must move by design (not the 8 B/sample
-        # algorithmic figure) -> achieved GB/s of that kernel; PMC-measured traffic agrees within a few %
+        kernels = kernel_table(prof, args.steps) if args.full else {}
+        # the overlap-save pass's block, hop and blocks per row (config.overlap_save): host-side plan queries only
         line_ols = None
         try:
             from torchfx_amd import torchfx_ext as E
-            model = {"sos_stream_kernel<f64>": 8.0 * samples, "sos_stream_kernel<f32>": 8.0 * samples,
-                     "ols_lds4096_kernel": 8.0 * samples, "ols_lds8192_kernel": 8.0 * samples, "ols_lds16k_r4_kernel": 8.0 * samples}
             if ols_taps:
                 kk = ols_taps
                 info = E.ols_plan_info(kk, T, (kk - 1, 0))
@@ -755,151 +764,159 @@ def main() -> None:
                 fused = E.sos_fft_conv_plan_info(T, _sos, kk, (kk - 1, 0)) if args.workload == "chain" else None
                 if fused and "CascadeFIR" in desc:      # the recursion-in-pass-A pipeline picks its own block (2^21 on long rows)
                     info = dict(info, N=fused["N"], S=fused["S"], F=fused["F"])
-                frames = C * info["F"]
-                pairs = (frames + 1) // 2
                 n = info["N"]
-                model["ols_col_fwd16_kernel"] = frames * n * 4.0 + pairs * n * 8.0
-                # the recursion's column pass also reads every row's warm-up (64 of 256 blocks for the cfg-2 cascade at 2^-48, round 5; fewer at round 6's 2^-40)
-                wb = -(-max(0, E.sos_fft_conv_warmup(_sos)) // 32)
-                rows_blk = n // 256 // 32                               # column blocks per row: 128 (4096-sample rows) or 256 (8192)
-                model["ols_col_fwd16_sos_kernel"] = frames * n * 4.0 * (1.0 + min(wb, rows_blk) / rows_blk) + pairs * n * 8.0
-                model["ols_row8192_kernel"] = pairs * n * 16.0
-                model["ols_col_inv16_kernel"] = pairs * n * 8.0 + 4.0 * samples
-                for nm in ("ols_row_kernel", "ols_row1024_kernel", "ols_row4096_kernel"):
-                    model[nm] = pairs * n * 16.0
                 line_ols = {"taps": kk, "fft_block": n, "hop": info["S"], "blocks_per_row": info["F"],
                             "native_lds_fft": info["native"], "model_bytes_per_sample": round((20.0 * n / info["S"]) + 4.0, 2)}
-            for name, k in kernels.items():
-                if name in model and k["ms_per_step"] > 0:
-                    k["model_GB_per_step"] = round(model[name] / 1e9, 3)
-                    k["GBps"] = round(model[name] / 1e9 / (k["ms_per_step"] * 1e-3), 1)
-                    k["frac_of_8TBps"] = round(k["GBps"] / HBM_PEAK_GBS, 4)
         except Exception:
             pass
-        kernels_serial = None
-        if prof_serial:
-            kernels_serial = {}
-            for name, v in prof_serial.items():
-                ms = v["total_ms"] / 2
-                kernels_serial[name] = {"ms_per_step": round(ms, 4), "avg_ms_per_launch": round(v["total_ms"] / v["calls"], 4)}
-                if name in kernels and "model_GB_per_step" in kernels[name]:
-                    kernels_serial[name]["GBps"] = round(kernels[name]["model_GB_per_step"] / (ms * 1e-3), 1)
-        dom = max(kernels, key=lambda n: kernels[n]["ms_per_step"]) if kernels else None
-        gpu_ms = sum(k["ms_per_step"] for k in kernels.values())
-        # per-GPU algorithmic bytes of one step: 8 B per sample-channel
-        alg_gb = 8.0 * samples / 1e9
-        # roofline object = the DOMINANT kernel: algorithmic work of one launch / its average
-        # duration in the timed region (HIP events on the launch stream).  The whole-step figure
-        # (all passes of the step share the one 8 B/sample) is reported beside it as step_*.
-        if args.workload == "fir":
-            step_ach = 2.0 * 1024 * samples / (ms_step * 1e-3) / 1e12
-            roof = {"bound": "mfma", "peak": FP32_PEAK_TF, "unit": "TFLOP/s", "traffic": None,
-                    "note": "2*1024 flop/sample on exact-f32 MFMA (v_mfma_f32_32x32x2_f32); HBM roof unreachable (SURVEY 7.3-3)"}
-            unit_work = 2.0 * 1024 / 1e12                                  # TFLOP per sample
-        else:
-            step_ach = alg_gb / (ms_step * 1e-3)
-            roof = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": None,
-                    "note": "achieved = 8 B/sample-channel x samples one launch of the dominant kernel covers / its "
-                            "average duration; step_achieved = 8 B x samples of the step / step time (all passes)"}
-            unit_work = 8.0 / 1e9                                          # GB per sample
-        if dom:
-            per_launch = samples / max(kernels[dom]["launches_per_step"], 1e-9)
-            ach = unit_work * per_launch / (kernels[dom]["avg_ms_per_launch"] * 1e-3)
-        else:
-            ach = step_ach
-        multi_pass = chainlike and ols_taps is not None
-        if multi_pass:
-            # overlap-save steps: three kernels of comparable weight overlap on internal streams, so "the dominant
-            # kernel" flips between runs and its elapsed time is stretched by its neighbours.  The roofline figure
-            # is therefore the STEP: algorithmic bytes of the step / step time; the per-kernel view sits beside it.
-            roof["achieved"] = round(step_ach, 2)
-            roof["frac"] = round(step_ach / roof["peak"], 4)
-            roof["frac_is"] = "whole step (all passes share the one 8 B/sample-channel)"
-            roof["dominant_kernel_in_timed_region"] = {"achieved": round(ach, 2), "frac": round(ach / roof["peak"], 4),
-                                                       "note": "three passes overlap: per-kernel elapsed times include contention"}
-        else:
-            roof["achieved"] = round(ach, 2)
-            roof["frac"] = round(ach / roof["peak"], 4)
-            roof["frac_is"] = "dominant kernel: algorithmic work of one launch / its average duration (HIP events)"
-        roof["step_achieved"] = round(step_ach, 2)
-        roof["step_frac"] = round(step_ach / roof["peak"], 4)
-        if multi_pass and line_ols:
-            # what THIS design can reach at best: a transform longer than LDS is three passes over a complex workspace, i.e.
-            # model bytes per sample (20 N / S + 4, + the warm-up re-reads of the recursion's column pass) moved at the rate a
-            # plain device copy sustains on this part (MI355X_MICROARCH.md: 6.29 TB/s) -- read `frac` against this, not 1.0
-            mb = float(line_ols["model_bytes_per_sample"])
-            if "ols_col_fwd16_sos_kernel" in kernels:
-                mb += 4.0 * min(wb, rows_blk) / rows_blk * line_ols["fft_block"] / line_ols["hop"]
-            roof["design_ceiling"] = {"frac": round(8.0 / mb * COPY_RATE_GBS / HBM_PEAK_GBS, 4), "model_bytes_per_sample": round(mb, 2),
-                                      "copy_rate_GBps": COPY_RATE_GBS,
-                                      "what": "8 B/sample / (model bytes per sample of the three-pass overlap-save) x the device's sustained copy rate / peak"}
-        if args.workload == "chain" and "ols_col_fwd16_sos_kernel" in kernels:
-            # the default plan IS the reference's arithmetic: float64 recursion (inside the forward column pass), float32 overlap-save
-            roof["step_frac_reference_arithmetic"] = roof["step_frac"]
-            roof["reference_arithmetic_means"] = ("float64 DF1 recursion, one rounding to float32, float32 FFT convolution -- the reference's "
-                                                  "operations, not its bits: a row of the transform restarts from a warm-up (state true to 2^-40), "
-                                                  "FMA contraction and the unit-b0 form reassociate the numerator; parity bars: every section "
-                                                  "2e-11 in float64, the float32 cascade output 1 ulp, the chain 1e-5 (tests/gpu_common.py)")
-        if variants and "ms_per_step" in variants.get("chain_fold", {}):
-            roof["step_frac_spectral_fold"] = variants["chain_fold"]["frac_of_8TBps_at_8B_per_sample"]
-        if variants and "ms_per_step" in variants.get("chain_iir_kernel", {}):
-            roof["step_frac_iir_as_its_own_pass"] = variants["chain_iir_kernel"]["frac_of_8TBps_at_8B_per_sample"]
-        if variants and "ms_per_step" in variants.get("chain_reference_staging", {}):
-            roof["step_frac_reference_staging"] = variants["chain_reference_staging"]["frac_of_8TBps_at_8B_per_sample"]
-        if dom and prof_serial and dom in prof_serial:
-            # the same kernel with nothing else on the chip (the untimed single-stream pass): in the timed region the
-            # three overlap-save passes of different slabs run concurrently, so every kernel's elapsed time there is
-            # stretched by its neighbours -- the wall clock gains, the per-kernel figure does not show the kernel alone
-            alone_ms = prof_serial[dom]["total_ms"] / prof_serial[dom]["calls"]
-            per_launch_alone = samples / max(prof_serial[dom]["calls"] / 2.0, 1e-9)
-            a1 = unit_work * per_launch_alone / (alone_ms * 1e-3)
-            roof["alone"] = {"avg_ms_per_launch": round(alone_ms, 4), "achieved": round(a1, 2), "frac": round(a1 / roof["peak"], 4),
-                             "what": "the dominant kernel on one internal stream, untimed extra pass (no concurrent kernels)"}
-        # HBM bytes from rocprofv3 PMC passes of this same command (tools/profile_gpu.sh -> profiles/):
-        # counters cannot be read from inside the process, so the file written by the last profiling
-        # session is reported together with the digest of the HIP sources it was taken from
-        try:
-            tr = json.load(open(os.path.join(ROOT, TRAFFIC_FILE)))
-            ent = tr.get(args.workload)
-            if ent and C == 64 and seconds == ent.get("seconds", 600.0):
-                roof["step_traffic"] = ent["bytes_per_step"]
-                pk = ent.get("per_kernel_GB_per_launch", {}).get(dom)
-                if multi_pass:
-                    roof["traffic"] = ent["bytes_per_step"]                       # per step, like `achieved`
-                elif pk:
-                    lps = pk.get("launches_per_step")
-                    scale = (lps / kernels[dom]["launches_per_step"]) if lps else 1.0   # same bytes, other slab count
-                    roof["traffic"] = round((pk["read"] + pk["write"]) * 1e9 * scale)
-                roof["traffic_source"] = (f"{TRAFFIC_FILE} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes of this command): L2-miss "
-                                          "traffic; the overlap-save workspace share of it is served by the Infinity Cache (64 MB slabs), not HBM")
-                roof["traffic_from_this_build"] = tr.get("source_digest") == source_digest()
-        except Exception:
-            pass
-        roof["dominant_kernel"] = dom
-        if dom:
-            roof["dominant_kernel_avg_ms"] = kernels[dom]["avg_ms_per_launch"]
-            roof["dominant_kernel_ms_per_step"] = kernels[dom]["ms_per_step"]
-        for kn in ("sos_stream_kernel<f64>", "sos_stream_kernel<f32>"):
-            if kn in kernels:
-                a = alg_gb / (kernels[kn]["ms_per_step"] * 1e-3)
-                roof["iir_kernel"] = {"name": kn, "achieved": round(a, 1), "unit": "GB/s", "frac": round(a / HBM_PEAK_GBS, 4)}
         dtype = {"chain": "f64 (IIR) + f32 (FFT); f32 I/O", "chain_fold": "f32 (overlap-save FFT arithmetic for the whole folded chain); f32 I/O",
                  "chain_iir_kernel": "f64 (IIR) + f32 (FFT); f32 I/O", "chain_reference_staging": "f64 (IIR) + f32 (FFT); f32 I/O",
                  "sos": "f64; f32 I/O", "fir": "f32", "fir_fft": "f32", "fftconv": "f32"}[args.workload]
-        if args.workload == "chain" and "sos_stream_kernel<f64>" in kernels:
-            dtype = "f64 (IIR) + f32 (FFT); f32 I/O"
-        iir_knob = os.environ.get("TORCHFX_AMD_IIR_PRECISION", "f64")
-        if "ols_col_fwd16_sos_kernel" in kernels:
-            iir_how = ("float64 DF1 recursion (iir_cpu.cpp:132-147) in registers inside the overlap-save pipeline's forward column pass "
-                       "(ols_col_fwd16_sos_kernel: one thread per 4096-sample row, warm-up to 2^-40 from zero state), rounded once to float32; "
-                       "every section's output readable through y_sections (tests/test_gpu_sos_ols.py)")
-        elif args.workload.startswith("chain") and not any(n.startswith("sos_stream_kernel") for n in kernels):
-            iir_how = ("folded into the f32 overlap-save pass (fuse_spectral, opt-in: the cascade's impulse response joins the FIR run; "
-                       "no recursive kernel runs)")
-        elif args.workload in ("fir", "fir_fft", "fftconv"):
-            iir_how = "n/a (no IIR stage)"
-        else:
-            iir_how = f"{iir_knob} recursion in sos_stream_kernel (TORCHFX_AMD_IIR_PRECISION)"
+        if args.full:                                     # per-kernel table, roofline: figures of the event-profiled run
+            # per-kernel HBM model: the bytes each launch group must move by design (not the 8 B/sample
+            # algorithmic figure) -> achieved GB/s of that kernel; PMC-measured traffic agrees within a few %
+            try:
+                model = {"sos_stream_kernel<f64>": 8.0 * samples, "sos_stream_kernel<f32>": 8.0 * samples,
+                         "ols_lds4096_kernel": 8.0 * samples, "ols_lds8192_kernel": 8.0 * samples, "ols_lds16k_r4_kernel": 8.0 * samples}
+                if line_ols:
+                    n = line_ols["fft_block"]
+                    frames = C * line_ols["blocks_per_row"]
+                    pairs = (frames + 1) // 2
+                    model["ols_col_fwd16_kernel"] = frames * n * 4.0 + pairs * n * 8.0
+                    # the recursion's column pass also reads every row's warm-up (64 of 256 blocks for the cfg-2 cascade at 2^-48, round 5; fewer at round 6's 2^-40)
+                    wb = -(-max(0, E.sos_fft_conv_warmup(_sos)) // 32)
+                    rows_blk = n // 256 // 32                               # column blocks per row: 128 (4096-sample rows) or 256 (8192)
+                    model["ols_col_fwd16_sos_kernel"] = frames * n * 4.0 * (1.0 + min(wb, rows_blk) / rows_blk) + pairs * n * 8.0
+                    model["ols_row8192_kernel"] = pairs * n * 16.0
+                    model["ols_col_inv16_kernel"] = pairs * n * 8.0 + 4.0 * samples
+                    for nm in ("ols_row_kernel", "ols_row1024_kernel", "ols_row4096_kernel"):
+                        model[nm] = pairs * n * 16.0
+                for name, k in kernels.items():
+                    if name in model and k["ms_per_step"] > 0:
+                        k["model_GB_per_step"] = round(model[name] / 1e9, 3)
+                        k["GBps"] = round(model[name] / 1e9 / (k["ms_per_step"] * 1e-3), 1)
+                        k["frac_of_8TBps"] = round(k["GBps"] / HBM_PEAK_GBS, 4)
+            except Exception:
+                pass
+            kernels_serial = None
+            if prof_serial:
+                kernels_serial = {}
+                for name, v in prof_serial.items():
+                    ms = v["total_ms"] / 2
+                    kernels_serial[name] = {"ms_per_step": round(ms, 4), "avg_ms_per_launch": round(v["total_ms"] / v["calls"], 4)}
+                    if name in kernels and "model_GB_per_step" in kernels[name]:
+                        kernels_serial[name]["GBps"] = round(kernels[name]["model_GB_per_step"] / (ms * 1e-3), 1)
+            dom = max(kernels, key=lambda n: kernels[n]["ms_per_step"]) if kernels else None
+            gpu_ms = sum(k["ms_per_step"] for k in kernels.values())
+            # per-GPU algorithmic bytes of one step: 8 B per sample-channel
+            alg_gb = 8.0 * samples / 1e9
+            # roofline object = the DOMINANT kernel: algorithmic work of one launch / its average
+            # duration in the timed region (HIP events on the launch stream).  The whole-step figure
+            # (all passes of the step share the one 8 B/sample) is reported beside it as step_*.
+            if args.workload == "fir":
+                step_ach = 2.0 * 1024 * samples / (ms_step * 1e-3) / 1e12
+                roof = {"bound": "mfma", "peak": FP32_PEAK_TF, "unit": "TFLOP/s", "traffic": None,
+                        "note": "2*1024 flop/sample on exact-f32 MFMA (v_mfma_f32_32x32x2_f32); HBM roof unreachable (SURVEY 7.3-3)"}
+                unit_work = 2.0 * 1024 / 1e12                                  # TFLOP per sample
+            else:
+                step_ach = alg_gb / (ms_step * 1e-3)
+                roof = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": None,
+                        "note": "achieved = 8 B/sample-channel x samples one launch of the dominant kernel covers / its "
+                                "average duration; step_achieved = 8 B x samples of the step / step time (all passes)"}
+                unit_work = 8.0 / 1e9                                          # GB per sample
+            if dom:
+                per_launch = samples / max(kernels[dom]["launches_per_step"], 1e-9)
+                ach = unit_work * per_launch / (kernels[dom]["avg_ms_per_launch"] * 1e-3)
+            else:
+                ach = step_ach
+            multi_pass = chainlike and ols_taps is not None
+            if multi_pass:
+                # overlap-save steps: three kernels of comparable weight overlap on internal streams, so "the dominant
+                # kernel" flips between runs and its elapsed time is stretched by its neighbours.  The roofline figure
+                # is therefore the STEP: algorithmic bytes of the step / step time; the per-kernel view sits beside it.
+                roof["achieved"] = round(step_ach, 2)
+                roof["frac"] = round(step_ach / roof["peak"], 4)
+                roof["frac_is"] = "whole step (all passes share the one 8 B/sample-channel)"
+                roof["dominant_kernel_in_timed_region"] = {"achieved": round(ach, 2), "frac": round(ach / roof["peak"], 4),
+                                                           "note": "three passes overlap: per-kernel elapsed times include contention"}
+            else:
+                roof["achieved"] = round(ach, 2)
+                roof["frac"] = round(ach / roof["peak"], 4)
+                roof["frac_is"] = "dominant kernel: algorithmic work of one launch / its average duration (HIP events)"
+            roof["step_achieved"] = round(step_ach, 2)
+            roof["step_frac"] = round(step_ach / roof["peak"], 4)
+            if multi_pass and line_ols:
+                # what THIS design can reach at best: a transform longer than LDS is three passes over a complex workspace, i.e.
+                # model bytes per sample (20 N / S + 4, + the warm-up re-reads of the recursion's column pass) moved at the rate a
+                # plain device copy sustains on this part (COPY_RATE_GBS, 6.29 TB/s) -- read `frac` against this, not 1.0
+                mb = float(line_ols["model_bytes_per_sample"])
+                if "ols_col_fwd16_sos_kernel" in kernels:
+                    mb += 4.0 * min(wb, rows_blk) / rows_blk * line_ols["fft_block"] / line_ols["hop"]
+                roof["design_ceiling"] = {"frac": round(8.0 / mb * COPY_RATE_GBS / HBM_PEAK_GBS, 4), "model_bytes_per_sample": round(mb, 2),
+                                          "copy_rate_GBps": COPY_RATE_GBS,
+                                          "what": "8 B/sample / (model bytes per sample of the three-pass overlap-save) x the device's sustained copy rate / peak"}
+            if args.workload == "chain" and "ols_col_fwd16_sos_kernel" in kernels:
+                # the default plan IS the reference's arithmetic: float64 recursion (inside the forward column pass), float32 overlap-save
+                roof["step_frac_reference_arithmetic"] = roof["step_frac"]
+                roof["reference_arithmetic_means"] = ("float64 DF1 recursion, one rounding to float32, float32 FFT convolution -- the reference's "
+                                                      "operations, not its bits: a row of the transform restarts from a warm-up (state true to 2^-40), "
+                                                      "FMA contraction and the unit-b0 form reassociate the numerator; parity bars: every section "
+                                                      "2e-11 in float64, the float32 cascade output 1 ulp, the chain 1e-5 (tests/gpu_common.py)")
+            if variants and "ms_per_step" in variants.get("chain_fold", {}):
+                roof["step_frac_spectral_fold"] = variants["chain_fold"]["frac_of_8TBps_at_8B_per_sample"]
+            if variants and "ms_per_step" in variants.get("chain_iir_kernel", {}):
+                roof["step_frac_iir_as_its_own_pass"] = variants["chain_iir_kernel"]["frac_of_8TBps_at_8B_per_sample"]
+            if variants and "ms_per_step" in variants.get("chain_reference_staging", {}):
+                roof["step_frac_reference_staging"] = variants["chain_reference_staging"]["frac_of_8TBps_at_8B_per_sample"]
+            if dom and prof_serial and dom in prof_serial:
+                # the same kernel with nothing else on the chip (the untimed single-stream pass): in the timed region the
+                # three overlap-save passes of different slabs run concurrently, so every kernel's elapsed time there is
+                # stretched by its neighbours -- the wall clock gains, the per-kernel figure does not show the kernel alone
+                alone_ms = prof_serial[dom]["total_ms"] / prof_serial[dom]["calls"]
+                per_launch_alone = samples / max(prof_serial[dom]["calls"] / 2.0, 1e-9)
+                a1 = unit_work * per_launch_alone / (alone_ms * 1e-3)
+                roof["alone"] = {"avg_ms_per_launch": round(alone_ms, 4), "achieved": round(a1, 2), "frac": round(a1 / roof["peak"], 4),
+                                 "what": "the dominant kernel on one internal stream, untimed extra pass (no concurrent kernels)"}
+            # HBM bytes from rocprofv3 PMC passes of this same command (tools/profile_gpu.sh -> profiles/):
+            # counters cannot be read from inside the process, so the file written by the last profiling
+            # session is reported together with the digest of the HIP sources it was taken from
+            try:
+                tr = json.load(open(os.path.join(ROOT, TRAFFIC_FILE)))
+                ent = tr.get(args.workload)
+                if ent and C == 64 and seconds == ent.get("seconds", 600.0):
+                    roof["step_traffic"] = ent["bytes_per_step"]
+                    pk = ent.get("per_kernel_GB_per_launch", {}).get(dom)
+                    if multi_pass:
+                        roof["traffic"] = ent["bytes_per_step"]                       # per step, like `achieved`
+                    elif pk:
+                        lps = pk.get("launches_per_step")
+                        scale = (lps / kernels[dom]["launches_per_step"]) if lps else 1.0   # same bytes, other slab count
+                        roof["traffic"] = round((pk["read"] + pk["write"]) * 1e9 * scale)
+                    roof["traffic_source"] = (f"{TRAFFIC_FILE} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes of this command): L2-miss "
+                                              "traffic; the overlap-save workspace share of it is served by the Infinity Cache (64 MB slabs), not HBM")
+                    roof["traffic_from_this_build"] = tr.get("source_digest") == source_digest()
+            except Exception:
+                pass
+            roof["dominant_kernel"] = dom
+            if dom:
+                roof["dominant_kernel_avg_ms"] = kernels[dom]["avg_ms_per_launch"]
+                roof["dominant_kernel_ms_per_step"] = kernels[dom]["ms_per_step"]
+            for kn in ("sos_stream_kernel<f64>", "sos_stream_kernel<f32>"):
+                if kn in kernels:
+                    a = alg_gb / (kernels[kn]["ms_per_step"] * 1e-3)
+                    roof["iir_kernel"] = {"name": kn, "achieved": round(a, 1), "unit": "GB/s", "frac": round(a / HBM_PEAK_GBS, 4)}
+            iir_knob = os.environ.get("TORCHFX_AMD_IIR_PRECISION", "f64")
+            if "ols_col_fwd16_sos_kernel" in kernels:
+                iir_how = ("the reference's float64 DF1 recursion in registers inside the overlap-save pipeline's forward column pass "
+                           "(ols_col_fwd16_sos_kernel: one thread per 4096-sample row, warm-up to 2^-40 from zero state), rounded once to float32; "
+                           "every section's output readable through y_sections (tests/test_gpu_sos_ols.py)")
+            elif args.workload.startswith("chain") and not any(n.startswith("sos_stream_kernel") for n in kernels):
+                iir_how = ("folded into the f32 overlap-save pass (fuse_spectral, opt-in: the cascade's impulse response joins the FIR run; "
+                           "no recursive kernel runs)")
+            elif args.workload in ("fir", "fir_fft", "fftconv"):
+                iir_how = "n/a (no IIR stage)"
+            else:
+                iir_how = f"{iir_knob} recursion in sos_stream_kernel (TORCHFX_AMD_IIR_PRECISION)"
         line = {
             # BASELINE.json's metric string; `value` is the whole-job aggregate, `per_gpu_value` the per-GPU rate
             "metric": "Msamples/s/GPU (64-ch fused biquad→FIR→FFT-conv chain); % HBM roofline"
@@ -912,17 +929,20 @@ def main() -> None:
             "config": {"workload": desc, "channels_per_gpu": C, "total_channels": total_rows, "seconds": seconds, "fs": FS,
                        "samples_per_gpu": samples, "parallelism": f"channel-shard x{world}, no data-path collective",
                        "fusion_policy": os.environ.get("TORCHFX_AMD_FUSION", "auto"),
-                       "iir_precision": iir_how,
                        "source_digest": source_digest()},
-            "roofline": roof,
-            "kernels": kernels, "gpu_ms_per_step_sum_of_kernels": round(gpu_ms, 4),
-            "kernels_from": "an identical region of the same steps run right after the timed one WITH the library's per-kernel HIP "
-                            "events (the timed region itself runs without them: two event records per launch)",
-            "ms_per_step_with_event_profiling": round(elapsed_prof / args.steps * 1e3, 4),
-            "kernels_note": "timed region: overlap-save passes of different slabs overlap on internal streams, so "
-                            "per-kernel times there include contention; kernels_single_stream = same kernels, one stream, untimed pass",
-            "kernels_single_stream": kernels_serial,
         }
+        if args.full:
+            line["config"]["iir_precision"] = iir_how
+            line.update({
+                "roofline": roof,
+                "kernels": kernels, "gpu_ms_per_step_sum_of_kernels": round(gpu_ms, 4),
+                "kernels_from": "an identical region of the same steps run right after the timed one WITH the library's per-kernel HIP "
+                                "events (the timed region itself runs without them: two event records per launch)",
+                "ms_per_step_with_event_profiling": round(elapsed_prof / args.steps * 1e3, 4),
+                "kernels_note": "timed region: overlap-save passes of different slabs overlap on internal streams, so "
+                                "per-kernel times there include contention; kernels_single_stream = same kernels, one stream, untimed pass",
+                "kernels_single_stream": kernels_serial,
+            })
         line["ranks_seen"] = seen                         # all-reduce of ones on the process group (RCCL at N > 1)
         line["devices"] = devices
         line["distinct_device_uuids"] = len(set(uuids))
@@ -958,7 +978,7 @@ def main() -> None:
         if gather_ms is not None:
             line["gather_ms"] = round(gather_ms, 2)
             line["value_with_gather"] = round(total_rows * T / (elapsed / args.steps + gather_ms * 1e-3) / 1e6, 1)
-        if not args.no_cpu_baseline and world == 1:      # rank 0 at N=1 only (contract)
+        if args.full and not args.no_cpu_baseline and world == 1:      # rank 0 at N=1 only (contract)
             try:
                 base_wl = "chain" if args.workload.startswith("chain") else args.workload
                 base_wl = "fir" if base_wl == "fir_fft" else base_wl

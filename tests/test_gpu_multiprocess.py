@@ -189,6 +189,48 @@ def test_bench_two_ranks_on_one_device(tmp_path):
         assert "cpu_baseline" not in line and "stages" not in line          # rank 0 at N = 1 only
 
 
+def test_bench_plain_line_and_full_line(tmp_path):
+    """A plain `python bench.py --gpus 1` prints the headline and nothing that needs runs of its own; --full adds the per-kernel
+    table, the roofline and the N = 1 extras (the CPU baseline leg has its own test in test_bench_contract.py).  The output of
+    the last timed step is the same either way."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--seconds", "2",
+                            "--channels", "2", "--dump-outputs", str(tmp_path / name)] + extra,
+                           env=env, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines[name] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in plain and k in full
+        if k not in ("value", "ms_per_step"):
+            assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["steps"] == 2 and plain["warmup"] == 1 and plain["dump_outputs"]["file"] == "y.npy"
+    moved = {"roofline", "kernels", "kernels_single_stream", "ms_per_step_with_event_profiling", "variants", "stages",
+             "published_context", "cfg5_512ch_on_one_gpu", "cpu_baseline"}
+    assert not moved & set(plain), moved & set(plain)
+    assert moved - {"cpu_baseline"} <= set(full), moved - set(full)
+    assert full["kernels"] and "iir_precision" in full["config"] and "cpu_baseline" not in full
+    # every leg of --full ran: a leg that raises leaves an {"error": ...} entry (or a "skipped" one) instead of its figures
+    legs = {"cfg5_512ch_on_one_gpu": full["cfg5_512ch_on_one_gpu"], **{f"published.{k}": v for k, v in full["published_context"]["cases"].items()},
+            **{f"variants.{k}": v for k, v in full["variants"].items()},
+            **{f"stages.{k}": v for k, v in full["stages"].items() if isinstance(v, dict)}}
+    assert len(full["variants"]) == 3 and len(full["published_context"]["cases"]) == 7
+    failed = {k: v for k, v in legs.items() if "error" in v or "skipped" in v}
+    assert not failed, failed
+    assert all("ms_per_step" in v for k, v in legs.items() if k.startswith(("variants.", "stages."))), legs
+    assert full["cfg5_512ch_on_one_gpu"]["ms_per_step"] > 0 and full["roofline"]["step_frac"] > 0
+    assert np.array_equal(np.load(tmp_path / "plain" / "y.npy"), np.load(tmp_path / "full" / "y.npy"))
+
+
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher in front (the shape of the command the driver uses at N = 1): bench.py
     re-executes itself under torch.distributed.run, one rank per GPU; rank 0 prints ONE JSON line with ranks_seen == 2.

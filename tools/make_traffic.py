@@ -8,8 +8,9 @@ Bytes: FETCH_SIZE and WRITE_SIZE are reported in KiB by rocprofv3.  On gfx950 FE
 128-B request for wide coalesced streams (MI355X_MICROARCH.md, HBM section), so read bytes = 2 x FETCH_SIZE;
 WRITE_SIZE is taken at face value.  Both factors are validated here against bytes that are known by
 construction: the row pass reads and writes its workspace slab exactly once (model_check below).
-The profiled command runs W warm-up steps, K timed steps and (since round 3) the same K steps once more with the library's
-per-kernel events -- all of them seen by rocprofv3: per-step = totals / (W + 2 K), read from the bench line of the run."""
+The profiled command runs W warm-up steps, K timed steps and, with --full, the same K steps once more with the library's
+per-kernel events -- all of them seen by rocprofv3: per-step = totals / (W + K), or (W + 2 K) for a --full line, read from the
+bench line of the run."""
 import json
 import os
 import re
@@ -34,7 +35,7 @@ def main() -> None:
     src = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles")
     import bench
 
-    out = {"_comment": "HBM bytes per bench step from rocprofv3 PMC passes of `bench.py --workload W --no-extras` (FETCH_SIZE and "
+    out = {"_comment": "HBM bytes per bench step from rocprofv3 PMC passes of `bench.py --workload W` (FETCH_SIZE and "
                        "WRITE_SIZE in separate runs, tools/profile_gpu.sh). read = 2 x FETCH_SIZE (gfx950 tallies 64 B per 128-B request "
                        "for coalesced streams), write = WRITE_SIZE. Sources: profiles/%s_<workload>.{txt,json}." % tag,
            "source_digest": bench.source_digest()}

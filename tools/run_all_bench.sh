@@ -1,17 +1,18 @@
 #!/bin/bash
-# run every bench workload on the GPU box and print the one-line summaries (+ wall seconds)
-R=${GRAFT_REPO_ROOT:-$(pwd)}; mkdir -p $R/gpurun_out
+# run every bench workload with --full and print the one-line summaries (+ wall seconds)
+# usage: tools/run_all_bench.sh <output dir>      (bench_<workload>.json / .err land there)
+R=$(cd "$(dirname "$0")/.." && pwd); OUT=${1:?usage: run_all_bench.sh <output dir>}; mkdir -p "$OUT"
 for w in chain sos fir fftconv; do
   s=$SECONDS
-  python $R/bench.py --workload $w > $R/gpurun_out/bench_$w.json 2> $R/gpurun_out/bench_$w.err
+  python $R/bench.py --workload $w --full > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
   echo "$w wall $((SECONDS-s)) s"
 done
-python - <<'PY'
-import json, os
-R = os.environ.get("GRAFT_REPO_ROOT", ".")
+python - "$OUT" <<'PY'
+import json, sys
+out = sys.argv[1]
 for w in ("chain", "sos", "fir", "fftconv"):
     try:
-        d = json.loads(open(f"{R}/gpurun_out/bench_{w}.json").read().strip().splitlines()[-1])
+        d = json.loads(open(f"{out}/bench_{w}.json").read().strip().splitlines()[-1])
         print(w, d["value"], d["ms_per_step"], d["roofline"]["frac"], d["roofline"].get("step_frac"), json.dumps(d["cpu_baseline"])[:420])
     except Exception as e:
         print(w, "FAILED", e)
