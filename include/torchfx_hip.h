@@ -222,7 +222,8 @@ int tfx_fft_conv_forward_ep(const void *x, void *y, int dtype, int64_t C, int64_
 int tfx_sos_fft_conv_supported(int64_t T, const double *sos_host, int64_t K, int64_t taps,
                                int64_t pad_left, int64_t pad_right, int force_block);
 /* 1 + the geometry the fused pipeline would use (*N block length: 2^20, or 2^21 = 256 rows of 8192 samples on rows of at
- * least 2^23 samples; *S hop; *F frames per row; *warmup samples), 0 when tfx_sos_fft_conv_supported would say no.  Host-only. */
+ * least 2^23 samples; *S hop; *F frames per row for x on a 128-byte line -- a view that starts inside one can take one
+ * frame more; *warmup samples), 0 when tfx_sos_fft_conv_supported would say no.  Host-only. */
 int tfx_sos_fft_conv_plan_info(int64_t T, const double *sos_host, int64_t K, int64_t taps,
                                int64_t pad_left, int64_t pad_right, int force_block,
                                int64_t *N, int64_t *S, int64_t *F, int64_t *warmup);
@@ -294,7 +295,9 @@ int tfx_ols_plan_info(int64_t K, int64_t T, int64_t pad_left, int64_t pad_right,
 /* The same for a signal of `dtype` (tfx_ols_plan_info answers for float32).  *path = 2: one launch, the
  * whole transform of a block in LDS and registers (*N = 4096, 8192 or 16384: K <= 8192 in float32, K <= 4096 in
  * float64; e N/S + e bytes of HBM traffic per output sample, e = element size); 1: the three-pass four-step
- * pipeline (float32, 20 N/S + 4); 0: rocFFT (~95, float64 ~190). */
+ * pipeline (float32, 20 N/S + 4); 0: rocFFT (~95, float64 ~190).  The answer is what tfx_fft_conv_forward does for a
+ * signal whose base pointer sits on a 128-byte line: *F is that signal's frame count, and on path 1 a view that starts
+ * inside a line can take one frame more. */
 int tfx_ols_plan_info2(int64_t K, int64_t T, int64_t pad_left, int64_t pad_right, int dtype,
                        int64_t *N, int64_t *S, int64_t *F, int *path);
 

@@ -3,6 +3,7 @@
 // (the elementwise kernels live in effects.hip).
 #include "common.h"
 #include "epilogue.h"
+#include "ols_route.h"
 #include "../../include/torchfx_hip.h"
 
 #include <atomic>
@@ -13,7 +14,7 @@
 
 namespace tfx {
 
-// implemented in sos.hip / fir.hip / fftconv.hip
+// implemented in sos.hip / fir.hip (the overlap-save entry points: ols_route.h)
 void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C, int64_t T,
                  const double *sos_host, int64_t K, const double *sx_in, const double *sy_in,
                  double *sx_out, double *sy_out, void *y_sections, int precision, hipStream_t stream, int64_t NB = 1,
@@ -31,29 +32,8 @@ void chunk_forward(const float *x, int64_t x_pitch, float *y, int64_t C, int64_t
 void fir_hist_update(const void *x, const void *hist_in, void *hist_out, int dtype, int64_t C, int64_t T, int64_t H,
                      hipStream_t stream);
 void fir_clear();
-void fft_conv_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, const void *kernel_host,
-                      int64_t K, int64_t pad_left, int64_t pad_right, hipStream_t stream, const void *hist = nullptr,
-                      int64_t H = 0, const Epilogue *ep = nullptr);
-bool sos_fft_conv_supported(int64_t T, const double *sos_host, int64_t Ksos, int64_t K, int64_t pad_left, int64_t pad_right, int force);
-int64_t sos_fft_conv_warmup(const double *sos_host, int64_t Ksos);
-bool sos_fft_conv_plan(int64_t T, const double *sos_host, int64_t Ksos, int64_t K, int64_t pad_left, int64_t pad_right, int force,
-                       int64_t *N_out, int64_t *S_out, int64_t *F_out, int64_t *warm_out);
-void sos_fft_conv_forward(const float *x, float *y, int64_t C, int64_t T, const double *sos_host, int64_t Ksos,
-                          const float *kernel_host, int64_t K, int64_t pad_left, int64_t pad_right, double *sections, int force,
-                          const Epilogue *ep, hipStream_t stream);
 void normalize_apply_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int mode, int per_row, double peak,
                              const double *stat, hipStream_t stream);
-void fftconv_clear();
-void olsnative_clear();
-bool olsnative_supported(int64_t K, int64_t L, int64_t *N_out);
-void olsnative_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int64_t N, int64_t *S_out, int64_t *F_out);
-void olsnative64_clear();
-bool olsnative64_supported(int64_t K, int64_t L, bool has_hist);
-void olsnative64_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int64_t *S_out, int64_t *F_out);
-void olslds_clear();
-void olsnative_prewarm();
-bool olslds_supported(int64_t K, int dtype, int64_t L, int64_t *N_out);
-void olslds_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int elem_bytes, int64_t N, int64_t *lead_out, int64_t *S_out);
 // effects.hip
 void gain_forward(const void *x, void *y, int dtype, int64_t n, double gain, int clamp, hipStream_t stream);
 void stat_forward(const void *x, int dtype, int64_t C, int64_t T, int mode, int per_row, double *out_dev, hipStream_t stream);
@@ -98,7 +78,6 @@ void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, in
                           double scale, hipStream_t stream);
 void interleave_forward(const float *in, float *out, int64_t F, int64_t C, int64_t ld_in, int64_t f_base,
                         hipStream_t stream);
-int64_t fftconv_block_size(int64_t K, int64_t L);
 
 // ---- environment knobs, read once --------------------------------------------------------------
 namespace {
@@ -381,7 +360,8 @@ int tfx_sos_fft_conv_supported(int64_t T, const double *sos_host, int64_t K, int
                                int force_block)
 {
     try {
-        return (sos_host && sos_fft_conv_supported(T, sos_host, K, taps, pad_left, pad_right, force_block)) ? 1 : 0;
+        return (sos_host && sos_fft_conv_plan(T, sos_host, K, taps, pad_left, pad_right, force_block, nullptr, nullptr, nullptr,
+                                              nullptr)) ? 1 : 0;
     } catch (...) {
         return 0;
     }
@@ -522,33 +502,18 @@ int tfx_chunk_forward(const float *x, int64_t x_pitch, float *y, int64_t C, int6
     TFX_API_END
 }
 
+// what fft_conv_forward would do without a streaming history, for a base pointer on a 128-byte line (ols_route.h)
 static void ols_plan(int64_t K, int64_t T, int64_t pad_left, int64_t pad_right, int dtype, int64_t *N, int64_t *S,
                      int64_t *F, int *path)
 {
     const int64_t L = T + pad_left + pad_right;
     TFX_CHECK(K >= 1 && L >= K, "ols_plan_info: kernel size %lld larger than the padded signal %lld", (long long)K, (long long)L);
     TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "ols_plan_info: bad dtype %d", dtype);
-    int64_t n = 0, hop = 0, frames = 0;
-    int p = 0;
-    if (olslds_supported(K, dtype, L, &n)) {
-        int64_t lead = 0;
-        olslds_geometry(K, T, pad_left, pad_right, dtype == TFX_F32 ? 4 : 8, n, &lead, &hop);
-        p = 2;
-    } else if (dtype == TFX_F32 && olsnative_supported(K, L, &n)) {
-        olsnative_geometry(K, T, pad_left, pad_right, n, &hop, &frames);
-        p = 1;
-    } else if (dtype == TFX_F64 && olsnative64_supported(K, L, false)) {
-        n = (int64_t)1 << 20;
-        olsnative64_geometry(K, T, pad_left, pad_right, &hop, &frames);
-        p = 1;
-    } else {
-        n = fftconv_block_size(K, L);
-        hop = n - K + 1;
-    }
-    if (N) *N = n;
-    if (S) *S = hop;
-    if (F) *F = frames > 0 ? frames : ceil_div(L - K + 1, hop);
-    if (path) *path = p;
+    const OlsRoute r = ols_route(K, T, pad_left, pad_right, dtype, false, 0);
+    if (N) *N = r.N;
+    if (S) *S = r.S;
+    if (F) *F = r.F;
+    if (path) *path = r.path;
 }
 
 int tfx_ols_plan_info(int64_t K, int64_t T, int64_t pad_left, int64_t pad_right, int64_t *N, int64_t *S,

@@ -13,6 +13,7 @@
 //   Z = rfft(fr) ;  Z *= conj(rfft(kf_pad)) / N ;  o = irfft(Z) ;  y[c, f*S + i] = o[i], i < S
 #include "common.h"
 #include "epilogue.h"
+#include "ols_route.h"
 #include "plan_cache.h"
 #include "../../include/torchfx_hip.h"
 
@@ -28,24 +29,7 @@
 
 namespace tfx {
 
-// olsnative.hip: hand-written LDS FFT passes for the long-kernel float32 case
-bool olsnative_supported(int64_t K, int64_t L, int64_t *N_out);
-void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const float *kf_host, int64_t K,
-                       int64_t pl, int64_t pr, int64_t N, hipStream_t stream, const float *hist, int64_t H, const Epilogue *ep,
-                       const SosFuseHost *sosf = nullptr);
-void olsnative_wait_warm();
-void olsnative_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int64_t N, int64_t *S_out, int64_t *F_out);
-bool olsnative64_supported(int64_t K, int64_t L, bool has_hist);                          // olsnative64.hip
-void olsnative64_forward(const double *x, double *y, int64_t C, int64_t Tn, const double *kf_host, int64_t K, int64_t pl, int64_t pr,
-                         hipStream_t stream);
-bool olsnative_sos_supported(int64_t Ksos, int64_t warm, int64_t K, int64_t Tn, int64_t pl, int64_t pr, int force, int64_t *N_out);
-void sos_plan_info(const double *sos_host, int64_t K, int *precision, int64_t *warmup, double *err_bound);
-int64_t sos_warmup_bits(const double *sos_host, int64_t K, int bits);
-
-// olslds.hip: one launch, the whole 4096-point transform in LDS (K <= 2048 taps, float32 and float64, rows of any length)
-bool olslds_supported(int64_t K, int dtype, int64_t L, int64_t *N_out);
-void olslds_forward(const void *x, void *y, int dtype, int64_t C, int64_t Tn, const void *kf_host, int64_t K,
-                    int64_t pl, int64_t pr, hipStream_t stream, const void *hist, int64_t H, const Epilogue *ep);
+int64_t sos_warmup_bits(const double *sos_host, int64_t K, int bits);      // sos.hip
 
 #define TFX_ROCFFT(expr)                                                                     \
     do {                                                                                     \
@@ -220,13 +204,10 @@ int64_t fftconv_block_size(int64_t K, int64_t L)
 
 template <typename T, typename T2>
 static void fft_conv_typed(const T *x, T *y, int dtype, int64_t C, int64_t Tn, const void *kernel_host,
-                           int64_t K, int64_t pl, int64_t pr, hipStream_t stream, const T *hist, int64_t Hlen)
+                           int64_t K, int64_t pl, int64_t pr, const OlsRoute &r, hipStream_t stream, const T *hist, int64_t Hlen)
 {
-    const int64_t L = Tn + pl + pr;
-    const int64_t Tout = L - K + 1;
-    const int64_t N = fftconv_block_size(K, L);
-    const int64_t S = N - K + 1;
-    const int64_t F = ceil_div(Tout, S);
+    const int64_t Tout = Tn + pl + pr - K + 1;
+    const int64_t N = r.N, S = r.S, F = r.F;
     const int64_t bins = N / 2 + 1;
 
     std::lock_guard<std::mutex> lk(g_fft_mu);
@@ -298,31 +279,43 @@ void fft_conv_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, c
     TFX_CHECK(C > 0 && T >= 0, "fft_conv_forward: negative size");
     TFX_CHECK(y && kernel_host && (x || T == 0), "fft_conv_forward: null pointer");
     olsnative_wait_warm();               // a set-up helper started by tfx_prewarm finishes before anything here is enqueued
-    int64_t Nn = 0;
-    if (olslds_supported(K, dtype, L, &Nn)) {
-        // kernels that fit on chip: no workspace, epilogue in the store of the inverse transform
-        olslds_forward(x, y, dtype, C, T, kernel_host, K, pad_left, pad_right, stream, hist, H, (ep && ep->any()) ? ep : nullptr);
-        return;
-    }
-    if (dtype == TFX_F32 && olsnative_supported(K, L, &Nn)) {
-        // the LDS-resident path applies the epilogue in its last pass (the store of the inverse column FFT)
-        olsnative_forward((const float *)x, (float *)y, C, T, (const float *)kernel_host, K, pad_left, pad_right, Nn, stream,
-                          (const float *)hist, H, (ep && ep->any()) ? ep : nullptr);
-        return;
-    }
-    if (dtype == TFX_F64 && olsnative64_supported(K, L, hist != nullptr)) {
-        // float64 beyond the one-launch kernels' 4096 taps: the three-pass pipeline in float64 (olsnative64.hip)
-        olsnative64_forward((const double *)x, (double *)y, C, T, (const double *)kernel_host, K, pad_left, pad_right, stream);
-        if (ep && ep->any()) epilogue_as_passes(y, dtype, C, L - K + 1, *ep, stream);
-        return;
-    }
-    if (dtype == TFX_F32)
-        fft_conv_typed<float, float2>((const float *)x, (float *)y, dtype, C, T, kernel_host, K, pad_left, pad_right, stream,
+    const OlsRoute r = ols_route(K, T, pad_left, pad_right, dtype, hist != nullptr, ols_sh_base(x, dtype == TFX_F32 ? 4 : 8));
+    const Epilogue *fused_ep = (ep && ep->any()) ? ep : nullptr;
+    if (r.path == OLS_PATH_LDS)          // kernels that fit on chip: no workspace, epilogue in the store of the inverse transform
+        return olslds_forward(x, y, dtype, C, T, kernel_host, K, pad_left, pad_right, r, stream, hist, H, fused_ep);
+    if (r.path == OLS_PATH_PASSES && dtype == TFX_F32)     // the epilogue in the last pass (the store of the inverse column FFT)
+        return olsnative_forward((const float *)x, (float *)y, C, T, (const float *)kernel_host, K, pad_left, pad_right, r, stream,
+                                 (const float *)hist, H, fused_ep);
+    if (r.path == OLS_PATH_PASSES)       // float64 beyond the one-launch kernels' 4096 taps (olsnative64.hip)
+        olsnative64_forward((const double *)x, (double *)y, C, T, (const double *)kernel_host, K, pad_left, pad_right, r, stream);
+    else if (dtype == TFX_F32)
+        fft_conv_typed<float, float2>((const float *)x, (float *)y, dtype, C, T, kernel_host, K, pad_left, pad_right, r, stream,
                                       (const float *)hist, H);
     else
-        fft_conv_typed<double, double2>((const double *)x, (double *)y, dtype, C, T, kernel_host, K, pad_left, pad_right, stream,
+        fft_conv_typed<double, double2>((const double *)x, (double *)y, dtype, C, T, kernel_host, K, pad_left, pad_right, r, stream,
                                         (const double *)hist, H);
-    if (ep && ep->any()) epilogue_as_passes(y, dtype, C, L - K + 1, *ep, stream);     // rocFFT path: separate passes
+    if (fused_ep) epilogue_as_passes(y, dtype, C, L - K + 1, *ep, stream);     // float64 three-pass and rocFFT: separate passes
+}
+
+OlsRoute ols_route(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int dtype, bool has_hist, int sh_base)
+{
+    const int64_t L = Tn + pl + pr;
+    OlsRoute r;
+    if (olslds_supported(K, dtype, L, &r.N, &r.lds_kind)) {
+        r.path = OLS_PATH_LDS;
+        olslds_geometry(K, Tn, pl, pr, dtype, r);
+    } else if (dtype == TFX_F32 && olsnative_supported(K, L, &r.N)) {
+        r.path = OLS_PATH_PASSES;
+        olsnative_geometry(K, Tn, pl, pr, sh_base, r);
+    } else if (dtype == TFX_F64 && olsnative64_supported(K, L, has_hist, &r.N)) {
+        r.path = OLS_PATH_PASSES;
+        olsnative64_geometry(K, Tn, pl, pr, sh_base, r);
+    } else {
+        r.N = fftconv_block_size(K, L);
+        r.S = r.N - K + 1;
+        r.F = ceil_div(L - K + 1, r.S);
+    }
+    return r;
 }
 
 // `iir-cascade | FIR` as ONE overlap-save pipeline in the reference's arithmetic: the zero-state float64 cascade
@@ -341,25 +334,43 @@ static int64_t fused_warmup(const double *sos_host, int64_t Ksos)
                           [&] { return std::make_shared<int64_t>(sos_warmup_bits(sos_host, Ksos, bits)); });
 }
 
-int64_t sos_fft_conv_warmup(const double *sos_host, int64_t Ksos) { return (Ksos >= 1 && Ksos <= 8) ? fused_warmup(sos_host, Ksos) : -1; }
+int64_t sos_fft_conv_warmup(const double *sos_host, int64_t Ksos) { return (Ksos >= 1 && Ksos <= OLS_SOS_MAXK) ? fused_warmup(sos_host, Ksos) : -1; }
 
-bool sos_fft_conv_supported(int64_t T, const double *sos_host, int64_t Ksos, int64_t K, int64_t pad_left, int64_t pad_right, int force)
+// The cascade-in-pass-A route: 4096- or 8192-point rows of the three-pass pipeline, a cascade of at most OLS_SOS_MAXK
+// sections whose warm-up fits a row.  `force`: 1 / 2 = the 2^20 / 2^21-point block even for rows shorter than one block
+// (tests at fixture size; a one-frame launch).  False when this form does not serve the call, else its route and warm-up.
+static bool sos_fft_conv_route(int64_t T, const double *sos_host, int64_t Ksos, int64_t K, int64_t pl, int64_t pr, int force,
+                               int sh_base, OlsRoute &r, int64_t &warm)
 {
-    if (Ksos < 1 || T <= 0 || K < 1) return false;
-    int64_t N = 0;
-    return Ksos <= 8 && olsnative_sos_supported(Ksos, fused_warmup(sos_host, Ksos), K, T, pad_left, pad_right, force, &N);
+    if (Ksos < 1 || Ksos > OLS_SOS_MAXK || T <= 0 || K < 1) return false;
+    warm = fused_warmup(sos_host, Ksos);
+    const int64_t L = T + pl + pr;
+    if (warm < 0 || warm > 4096 || L < K) return false;
+    r.N = (int64_t)1 << (force == 2 ? 21 : 20);
+    if (force) { if (r.N < 2 * (K + 32)) return false; }
+    else {
+        if (!olsnative_supported(K, L, &r.N) || (r.N != ((int64_t)1 << 20) && r.N != ((int64_t)1 << 21))) return false;
+        // rows of 8192 samples (N = 2^21) halve the warm-up share of the recursion pass: 9.7 against 10.1 ms on the cfg-5 chain
+        // (the plain pipeline is 5 % slower at 2^21 and stays at 2^20; profiles/r05_experiments.txt section 8)
+        if (r.N == ((int64_t)1 << 20) && L >= ((int64_t)1 << 23) && 2 * (K + 32) <= ((int64_t)1 << 21))
+            r.N = (int64_t)1 << 21;
+    }
+    r.path = OLS_PATH_PASSES;
+    olsnative_geometry(K, T, pl, pr, sh_base, r);
+    return true;
 }
 
-// block length, hop, frames per row and warm-up samples the fused pipeline would use; false when it does not serve the geometry
+// block length, hop, frames per row and warm-up samples the fused pipeline would use for x on a 128-byte line; false when it
+// does not serve the geometry
 bool sos_fft_conv_plan(int64_t T, const double *sos_host, int64_t Ksos, int64_t K, int64_t pad_left, int64_t pad_right, int force,
                        int64_t *N_out, int64_t *S_out, int64_t *F_out, int64_t *warm_out)
 {
-    if (Ksos < 1 || Ksos > 8 || T <= 0 || K < 1) return false;
-    const int64_t warm = fused_warmup(sos_host, Ksos);
-    int64_t N = 0;
-    if (!olsnative_sos_supported(Ksos, warm, K, T, pad_left, pad_right, force, &N)) return false;
-    olsnative_geometry(K, T, pad_left, pad_right, N, S_out, F_out);
-    if (N_out) *N_out = N;
+    OlsRoute r;
+    int64_t warm = 0;
+    if (!sos_fft_conv_route(T, sos_host, Ksos, K, pad_left, pad_right, force, 0, r, warm)) return false;
+    if (N_out) *N_out = r.N;
+    if (S_out) *S_out = r.S;
+    if (F_out) *F_out = r.F;
     if (warm_out) *warm_out = warm;
     return true;
 }
@@ -378,13 +389,13 @@ void sos_fft_conv_forward(const float *x, float *y, int64_t C, int64_t T, const 
     TFX_CHECK(x && y && kernel_host && sos_host, "sos_fft_conv_forward: null pointer");
     TFX_CHECK(((uintptr_t)x & 3) == 0 && ((uintptr_t)y & 3) == 0, "sos_fft_conv_forward: x and y must be float-aligned");
     olsnative_wait_warm();               // a set-up helper started by tfx_prewarm finishes before anything here is enqueued
-    int64_t N = 0;
-    const int64_t warm = Ksos <= 8 ? fused_warmup(sos_host, Ksos) : -1;
-    TFX_CHECK(olsnative_sos_supported(Ksos, warm, K, T, pad_left, pad_right, force, &N),
+    OlsRoute r;
+    int64_t warm = -1;
+    TFX_CHECK(sos_fft_conv_route(T, sos_host, Ksos, K, pad_left, pad_right, force, ols_sh_base(x, 4), r, warm),
               "sos_fft_conv_forward: unsupported here (at most 8 sections whose memory fades within 4096 samples, taps that take "
               "the 2^20-point block) -- ask tfx_sos_fft_conv_supported first");
     const SosFuseHost sf{sos_host, Ksos, warm, sections};
-    olsnative_forward(x, y, C, T, kernel_host, K, pad_left, pad_right, N, stream, nullptr, 0, (ep && ep->any()) ? ep : nullptr, &sf);
+    olsnative_forward(x, y, C, T, kernel_host, K, pad_left, pad_right, r, stream, nullptr, 0, (ep && ep->any()) ? ep : nullptr, &sf);
 }
 
 }  // namespace tfx

@@ -26,6 +26,7 @@
 #include "fftpk.h"
 #include "fftpk16k.h"
 #include "ldsfft.h"
+#include "ols_route.h"
 #include "plan_cache.h"
 #include "../../include/torchfx_hip.h"
 
@@ -680,8 +681,8 @@ void olslds_clear() { ldsfft::g_plans.clear(); }
 // equal to the 8192-point block at 512 taps, faster below) and K < 700 (float64), 8192 points above that up to 4096 taps
 // (float32, 64 x 2.88 M: 1024 taps 0.36 -> 0.34 ms, 2048 taps 0.49 -> 0.39, 4096 taps 0.85 (three passes) -> 0.52; float64, 32 x 2.88 M: 2048 taps
 // 0.60 -> 0.44, 4096 taps 3.0 (rocFFT) -> 0.62), 16 384 points for 4096 < K <= 8192 (float32; TFX_OLS_LDS16K=0 and
-// TFX_OLS_LDS16K_R4=0 hand them back to the three-pass pipeline / rocFFT)
-bool olslds_supported(int64_t K, int dtype, int64_t L, int64_t *N_out)
+// TFX_OLS_LDS16K_R4=0 hand them back to the three-pass pipeline / rocFFT).  *kind_out: the kernel (OlsRoute::lds_kind)
+bool olslds_supported(int64_t K, int dtype, int64_t L, int64_t *N_out, int *kind_out)
 {
     if (env_i64("TFX_OLS_LDS", 1) == 0 || env_i64("TFX_OLS_NATIVE", 1) == 0) return false;
     const int64_t lg = env_i64("TFX_FFT_LOG2N", 0);
@@ -695,58 +696,51 @@ bool olslds_supported(int64_t K, int dtype, int64_t L, int64_t *N_out)
     // so the smallest block that fits wins there ([2, 44100], 1500 taps: 8 us at 4096 points, 15 us at 8192)
     // from ~3300 taps the radix-4 kernel at 16 384 points overtakes it on long rows (4096 taps: 0.47 against 0.53 ms, 3000 taps:
     // 0.45 against 0.44) although it runs two workgroups per CU instead of four
-    const bool r4_long = dtype == TFX_F32 && lg == 0 && L >= 65536 && use16k == 1 && env_i64("TFX_OLS_LDS16K_R4", 1) >= 1 &&
-                         K >= 3400 && K <= ldsfft::LDS16K / 2;
+    const int64_t r4 = env_i64("TFX_OLS_LDS16K_R4", 1);
+    const bool r4_long = dtype == TFX_F32 && lg == 0 && L >= 65536 && use16k == 1 && r4 >= 1 && K >= 3400 && K <= ldsfft::LDS16K / 2;
     if (r4_long) N = ldsfft::LDS16K;
     else if (can8k && (lg == 13 || (K >= min8k && (L >= 65536 || K > ldsfft::LDS_N / 2)))) N = ldsfft::LDS8K;
     else if (K >= 1 && K <= ldsfft::LDS_N / 2 && lg != 14 && lg != 13) N = ldsfft::LDS_N;
     else if (K >= 1 && K <= ldsfft::LDS16K / 2 && dtype == TFX_F32 && (lg == 0 || lg == 14) &&
-             (use16k >= 2 || lg == 14 || (use16k == 1 && (L < 65536 || env_i64("TFX_OLS_LDS16K_R4", 1) >= 1)) ||
-              env_i64("TFX_OLS_LDS16K_R4", 1) >= 2))
+             (use16k >= 2 || lg == 14 || (use16k == 1 && (L < 65536 || r4 >= 1)) || r4 >= 2))
         N = ldsfft::LDS16K;
     if (!N) return false;
-    if (N_out) *N_out = N;
+    // 16 384 points (float32 only): the 1024-thread workgroup on rows the three-pass pipeline does not reach (few pairs: the
+    // sixteen wavefronts of one pair run side by side), four 4096-point transforms in a 512-thread workgroup on long rows
+    // (TFX_OLS_LDS16K_R4: 0 never, 2 always)
+    const bool use_r4 = r4 >= 2 || (r4 == 1 && L >= 65536 && use16k < 2);
+    *N_out = N;
+    *kind_out = N == ldsfft::LDS_N ? 0 : N == ldsfft::LDS8K ? 1 : use_r4 ? 3 : 2;
     return true;
 }
 
-// frame geometry shared with tfx_ols_plan_info: `lead` zero taps in front of the flipped kernel move the frame starts
-// onto 128-byte lines when the rows themselves are aligned, and the hop is rounded down to whole lines
-void olslds_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int elem_bytes, int64_t N, int64_t *lead_out, int64_t *S_out)
+// `lead` zero taps in front of the flipped kernel move the frame starts onto 128-byte lines when the rows themselves are
+// aligned, and the hop is rounded down to whole lines
+void olslds_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int dtype, OlsRoute &r)
 {
-    const int64_t line = 128 / elem_bytes;
+    const int64_t line = dtype == TFX_F32 ? 32 : 16;
     const int64_t Tout = Tn + pl + pr - K + 1;
     const bool align = (Tn % line == 0) && (Tout % line == 0);
-    const int64_t lead = align ? (line - (pl % line)) % line : 0;
-    int64_t S = N - (K + lead) + 1;
-    if (align && S > 2 * line) S -= S % line;
-    *lead_out = lead;
-    *S_out = S;
+    r.lead = align ? (line - (pl % line)) % line : 0;
+    r.S = r.N - (K + r.lead) + 1;
+    if (align && r.S > 2 * line) r.S -= r.S % line;
+    r.F = ceil_div(Tout, r.S);
 }
 
 template <typename R>
 static void olslds_typed(const R *x, R *y, int64_t C, int64_t Tn, const R *kf_host, int64_t K, int64_t pl, int64_t pr,
-                         hipStream_t stream, const R *hist, int64_t H, const Epilogue *ep)
+                         const OlsRoute &r, hipStream_t stream, const R *hist, int64_t H, const Epilogue *ep)
 {
     using namespace ldsfft;
-    Geom<R> g;
-    const int64_t L = Tn + pl + pr;
-    g.Tn = Tn; g.Tout = L - K + 1;
+    Geom<R> g;                           // block, kernel and frame geometry: olslds_supported / olslds_geometry
+    g.Tn = Tn; g.Tout = Tn + pl + pr - K + 1;
     g.hist = hist; g.H = hist ? H : 0;
     g.ep_gain = ep ? (R)ep->gain : (R)1; g.ep_scale = ep ? ep->scale : 0; g.ep_clamp = ep ? ep->clamp : 0;
     g.ep_stat = ep ? ep->stat_mode : -1; g.ep_partial = nullptr;
     g.nt = 2;
-    int64_t lead = 0, N = 0;
-    TFX_CHECK(olslds_supported(K, sizeof(R) == 4 ? TFX_F32 : TFX_F64, Tn + pl + pr, &N), "olslds_forward: %lld taps are not for this path", (long long)K);
-    olslds_geometry(K, Tn, pl, pr, (int)sizeof(R), N, &lead, &g.S);
-    g.pad_left = pl + lead;
-    g.F = ceil_div(g.Tout, g.S);
-    g.nframes = C * g.F;
-    // 16 384 points: the 1024-thread workgroup on rows the three-pass pipeline does not reach (few pairs: the sixteen wavefronts
-    // of one pair run side by side), four 4096-point transforms in a 512-thread workgroup on long rows (TFX_OLS_LDS16K_R4: 0 never, 2 always)
-    const int64_t r4 = env_i64("TFX_OLS_LDS16K_R4", 1);
-    const bool use_r4 = N == LDS16K && sizeof(R) == 4 && (r4 >= 2 || (r4 == 1 && L >= 65536 && env_i64("TFX_OLS_LDS16K", 1) < 2));
-    const int kind = N == LDS_N ? 0 : N == LDS8K ? 1 : use_r4 ? 3 : 2;
-    const std::shared_ptr<Plan> plan = get_plan<R>(kf_host, K, lead, (int)N, kind, stream);      // holds its buffer until this function has enqueued its launch
+    g.S = r.S; g.pad_left = pl + r.lead; g.F = r.F; g.nframes = C * g.F;
+    const int kind = r.lds_kind;
+    const std::shared_ptr<Plan> plan = get_plan<R>(kf_host, K, r.lead, (int)r.N, kind, stream);      // holds its buffer until this function has enqueued its launch
     const int64_t npairs = ceil_div(g.nframes, 2);
     if (g.ep_stat >= 0) g.ep_partial = (double *)scratch("olslds_ep_partial", (size_t)g.nframes * sizeof(double), stream);
     const int dev = current_device();
@@ -794,12 +788,12 @@ static void olslds_typed(const R *x, R *y, int64_t C, int64_t Tn, const R *kf_ho
 }
 
 void olslds_forward(const void *x, void *y, int dtype, int64_t C, int64_t Tn, const void *kf_host, int64_t K,
-                    int64_t pl, int64_t pr, hipStream_t stream, const void *hist, int64_t H, const Epilogue *ep)
+                    int64_t pl, int64_t pr, const OlsRoute &r, hipStream_t stream, const void *hist, int64_t H, const Epilogue *ep)
 {
     if (dtype == TFX_F32)
-        olslds_typed<float>((const float *)x, (float *)y, C, Tn, (const float *)kf_host, K, pl, pr, stream, (const float *)hist, H, ep);
+        olslds_typed<float>((const float *)x, (float *)y, C, Tn, (const float *)kf_host, K, pl, pr, r, stream, (const float *)hist, H, ep);
     else
-        olslds_typed<double>((const double *)x, (double *)y, C, Tn, (const double *)kf_host, K, pl, pr, stream, (const double *)hist, H, ep);
+        olslds_typed<double>((const double *)x, (double *)y, C, Tn, (const double *)kf_host, K, pl, pr, r, stream, (const double *)hist, H, ep);
 }
 
 }  // namespace tfx

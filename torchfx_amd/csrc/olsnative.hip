@@ -32,6 +32,7 @@
 #include "epilogue.h"
 #include "fftpk.h"
 #include "ols_kernels.h"
+#include "ols_route.h"
 #include "plan_cache.h"
 #include "../../include/torchfx_hip.h"
 
@@ -404,71 +405,41 @@ bool olsnative_supported(int64_t K, int64_t L, int64_t *N_out)
     return true;
 }
 
-// The cascade-in-pass-A form (ols_col_fwd16_sos_kernel): 4096-point rows, aligned frames, a cascade of at most SOSF_MAXK
-// sections whose warm-up fits a row.  `force`: take the 2^20-point block even for rows shorter than one block (tests at
-// fixture size; a one-frame launch).
 bool sos_unit_rows(const double *sos_host, int64_t K, double (*rows)[5]);     // sos.hip
+static_assert(SOSF_MAXK == OLS_SOS_MAXK, "the cascade route (fftconv.hip) admits the sections the column pass holds");
 
-bool olsnative_sos_supported(int64_t Ksos, int64_t warm, int64_t K, int64_t Tn, int64_t pl, int64_t pr, int force, int64_t *N_out)
+// 128-byte aligned frames (rows themselves aligned): prepend `lead` zeros to the flipped taps so that the left padding
+// becomes a multiple of 32 samples, and round the hop down to a multiple of 32: every 32-column segment the column passes
+// read or write is then exactly one cache line (misaligned segments straddle two lines: +8 % time on the forward pass,
+// +26 % on the inverse pass, measured).
+// Rows that are not whole lines (Tn % 32 != 0, or x starting inside a line) keep this: row c's frame grid is moved left by
+// sh(c) samples (row_shift) so that its frames start on lines of MEMORY -- one more frame at most; the column passes address
+// the same way, only the first and the last line of a row are partial.
+void olsnative_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int sh_base, OlsRoute &r)
 {
-    if (Ksos < 1 || Ksos > SOSF_MAXK || warm < 0 || warm > 4096) return false;
-    const int64_t L = Tn + pl + pr;
-    if (L < K) return false;
-    int64_t N = (int64_t)1 << (force == 2 ? 21 : 20);       // force: 1 = the 2^20-point block, 2 = the 2^21-point block, whatever the row length
-    if (force) { if (N < 2 * (K + 32)) return false; }
-    else {
-        if (!olsnative_supported(K, L, &N) || (N != ((int64_t)1 << 20) && N != ((int64_t)1 << 21))) return false;
-        // rows of 8192 samples (N = 2^21) halve the warm-up share of the recursion pass: 9.7 against 10.1 ms on the cfg-5 chain
-        // (the plain pipeline is 5 % slower at 2^21 and stays at 2^20; profiles/r05_experiments.txt section 8)
-        if (N == ((int64_t)1 << 20) && L >= ((int64_t)1 << 23) && 2 * (K + 32) <= ((int64_t)1 << 21))
-            N = (int64_t)1 << 21;
-    }
-    if (N_out) *N_out = N;
-    return true;
+    const int64_t Tout = Tn + pl + pr - K + 1;
+    r.lead = (32 - (pl % 32)) % 32;
+    r.S = r.N - (K + r.lead) + 1;
+    if (r.S > 64) r.S -= r.S % 32;
+    r.sh_base = sh_base;
+    r.sh_on = (Tn % 32 != 0 || sh_base != 0) ? 1 : 0;
+    r.F = ceil_div(Tout + (r.sh_on ? 31 : 0), r.S);
 }
 
-// hop and frames per row of a block size on this path (what olsnative_forward computes for itself below)
-void olsnative_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int64_t N, int64_t *S_out, int64_t *F_out)
-{
-    const int64_t L = Tn + pl + pr, Tout = L - K + 1;
-    (void)Tout;
-    const int64_t lead = (32 - (pl % 32)) % 32;
-    int64_t S = N - (K + lead) + 1;
-    if (S > 64) S -= S % 32;
-    if (S_out) *S_out = S;
-    // rows that are not whole 128-byte lines shift their frame grid by up to 31 samples (row_shift): one more frame at most
-    if (F_out) *F_out = ceil_div(Tout + (Tn % 32 != 0 ? 31 : 0), S);
-}
-
-void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const float *kf_host, int64_t K,
-                       int64_t pl, int64_t pr, int64_t N, hipStream_t stream, const float *hist, int64_t H, const Epilogue *ep,
-                       const SosFuseHost *sosf)
+void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const float *kf_host, int64_t K, int64_t pl, int64_t pr,
+                       const OlsRoute &r, hipStream_t stream, const float *hist, int64_t H, const Epilogue *ep, const SosFuseHost *sosf)
 {
     // the plan cache, the one-time function attributes and the creation of the internal streams each take a lock of their own;
     // the launches themselves are not serialised, so two host threads that drive two streams overlap (each stream has its own
     // scratch slabs; the internal lanes are shared and ordered by the fork / join events)
+    const int64_t N = r.N, lead = r.lead;           // block and frame geometry: olsnative_geometry
     OlsGeom g;
-    const int64_t L = Tn + pl + pr;
-    g.Tn = Tn; g.Tout = L - K + 1; g.pad_left = pl; g.out_shift = 0;
+    g.Tn = Tn; g.Tout = Tn + pl + pr - K + 1; g.pad_left = pl + lead; g.out_shift = 0;
+    g.S = r.S; g.F = r.F; g.sh_on = r.sh_on; g.sh_base = r.sh_base;
     g.hist = hist; g.H = hist ? H : 0;
     g.ep_gain = ep ? (float)ep->gain : 1.0f; g.ep_scale = ep ? ep->scale : 0; g.ep_clamp = ep ? ep->clamp : 0;
     g.ep_stat = ep ? ep->stat_mode : -1; g.ep_partial = nullptr;
-    // 128-byte aligned frames (rows themselves aligned): prepend `lead` zeros to the flipped taps so
-    // that the left padding becomes a multiple of 32 samples, and round the hop down to a multiple
-    // of 32: every 32-column segment the column passes read or write is then exactly one cache
-    // line (misaligned segments straddle two lines: +8 % time on the forward pass, +26 % on the
-    // inverse pass, measured)
-    // Rows that are not whole lines (Tn % 32 != 0, or x starting inside a line) keep this: row c's frame grid is moved left by
-    // sh(c) samples (row_shift) so that its frames start on lines of MEMORY; the column passes address the same way, only the
-    // first and the last line of a row are partial.
-    const int64_t lead = (32 - (pl % 32)) % 32;
-    g.sh_base = (int)(((uintptr_t)x >> 2) & 31);
-    g.sh_on = (Tn % 32 != 0 || g.sh_base != 0) ? 1 : 0;
-    g.nf_flag = nullptr;
-    g.nf_pair = nullptr;
-    g.pad_left = pl + lead;
-    g.S = N - (K + lead) + 1;
-    if (g.S > 64) g.S -= g.S % 32;
+    g.nf_flag = nullptr; g.nf_pair = nullptr;
     const int dev = current_device();
     // first call on this device: kernel attributes (code-object load) and the internal streams are set up on a helper thread
     // while this thread computes the spectrum (both are tens of milliseconds, one bound by the driver, one by the host's cores);
@@ -498,7 +469,6 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
     }
     if (plan_err) std::rethrow_exception(plan_err);
     if (plan->ready && plan->ready_stream != stream) TFX_HIP(hipStreamWaitEvent(stream, plan->ready, 0));   // spectrum computed on another stream
-    g.F = ceil_div(g.Tout + g.out_shift + (g.sh_on ? 31 : 0), g.S);
     g.nframes = C * g.F; g.N2 = plan->N2;
     g.P2 = g.N2;
     g.nt = 3;

@@ -14,6 +14,7 @@
 #include "common.h"
 #include "epilogue.h"
 #include "ldsfft.h"
+#include "ols_route.h"
 #include "plan_cache.h"
 #include "../../include/torchfx_hip.h"
 
@@ -238,36 +239,32 @@ static std::shared_ptr<Plan> build_plan(const double *kf, int64_t K, int64_t lea
 void olsnative64_clear() { ols64::g_plans.clear(); }
 
 // float64 signals, taps beyond the one-launch kernels' 4096, a signal of at least one 2^20-point block, no streaming history
-bool olsnative64_supported(int64_t K, int64_t L, bool has_hist)
+bool olsnative64_supported(int64_t K, int64_t L, bool has_hist, int64_t *N_out)
 {
     if (env_i64("TFX_OLS_NATIVE", 1) == 0 || env_i64("TFX_OLS_NATIVE64", 1) == 0 || env_i64("TFX_FFT_LOG2N", 0) != 0) return false;
+    *N_out = ols64::NPTS;
     return !has_hist && K > 4096 && 2 * (K + 16) <= ols64::NPTS && L >= ols64::NPTS;
 }
 
-void olsnative64_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int64_t *S_out, int64_t *F_out)
+// frames on 128-byte lines, as in olsnative_geometry (olsnative.hip) with 16-sample lines and no short-hop exception
+void olsnative64_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int sh_base, OlsRoute &r)
 {
     const int64_t Tout = Tn + pl + pr - K + 1;
-    const int64_t lead = (16 - (pl % 16)) % 16;
-    int64_t S = ols64::NPTS - (K + lead) + 1;
-    S -= S % 16;
-    if (S_out) *S_out = S;
-    if (F_out) *F_out = ceil_div(Tout + ((Tn % 16 != 0) ? 15 : 0), S);
+    r.lead = (16 - (pl % 16)) % 16;
+    r.S = r.N - (K + r.lead) + 1;
+    r.S -= r.S % 16;
+    r.sh_base = sh_base;
+    r.sh_on = (Tn % 16 != 0 || sh_base != 0) ? 1 : 0;
+    r.F = ceil_div(Tout + (r.sh_on ? 15 : 0), r.S);
 }
 
 void olsnative64_forward(const double *x, double *y, int64_t C, int64_t Tn, const double *kf_host, int64_t K, int64_t pl, int64_t pr,
-                         hipStream_t stream)
+                         const OlsRoute &r, hipStream_t stream)
 {
     using namespace ols64;
-    Geom g;
-    const int64_t L = Tn + pl + pr;
-    g.Tn = Tn; g.Tout = L - K + 1;
-    const int64_t lead = (16 - (pl % 16)) % 16;      // frames start on 128-byte lines: `lead` zero taps in front of the flipped kernel
-    g.pad_left = pl + lead;
-    g.S = NPTS - (K + lead) + 1;
-    g.S -= g.S % 16;
-    g.sh_base = (int)(((uintptr_t)x >> 3) & 15);
-    g.sh_on = (Tn % 16 != 0 || g.sh_base != 0) ? 1 : 0;
-    g.F = ceil_div(g.Tout + (g.sh_on ? 15 : 0), g.S);
+    Geom g;                                          // block and frame geometry: olsnative64_geometry
+    g.Tn = Tn; g.Tout = Tn + pl + pr - K + 1; g.pad_left = pl + r.lead;
+    g.S = r.S; g.F = r.F; g.sh_on = r.sh_on; g.sh_base = r.sh_base;
     g.nframes = C * g.F;
     g.nf_pair = nullptr;
     if (C > 1 && (g.F & 1)) {
@@ -275,7 +272,7 @@ void olsnative64_forward(const double *x, double *y, int64_t C, int64_t Tn, cons
         TFX_HIP(hipMemsetAsync(g.nf_pair, 0, (size_t)C * sizeof(int), stream));
     }
     const std::shared_ptr<Plan> plan =              // held until the launches are enqueued
-        g_plans.get(kf_host, (size_t)K * sizeof(double), {lead}, stream, [&] { return build_plan(kf_host, K, lead); });
+        g_plans.get(kf_host, (size_t)K * sizeof(double), {r.lead}, stream, [&] { return build_plan(kf_host, K, r.lead); });
     const int dev = current_device();
     constexpr size_t shm_col = (size_t)(N1 * CB + 256) * sizeof(cpd);
     constexpr size_t shm_row = (size_t)(N2 + N2 / 16 + 512) * sizeof(cpd);
