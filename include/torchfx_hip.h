@@ -241,6 +241,18 @@ int tfx_normalize_apply(const void *x, void *y, int dtype, int64_t C, int64_t T,
                         double peak, const double *stat_dev, tfx_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Stream history -- the contract of every streaming entry point (tfx_fir_stream_forward, tfx_chunk_forward,
+ * tfx_delay_stream_forward, tfx_delay_line_stream_forward, tfx_resample_stream_forward).  A chunk continues the last H input
+ * samples of each of its rows (H is the entry's: K-1, Kf-1, taps*delay, delay, Lp_s-1):
+ *   hist_in  DEVICE [rows, H] of the entry's dtype: the H samples before the chunk, oldest first; NULL = silence (the first
+ *            chunk of a stream).
+ *   hist_out DEVICE [rows, H]: receives the newest H samples of [hist_in | x] (x: what the entry filters, the cascade output
+ *            for tfx_chunk_forward), the next chunk's hist_in.  NULL only where the entry allows it, or when rows*H = 0.
+ * hist_out needs its own buffer, and neither y nor hist_out may overlap x, hist_in or each other.  The entries check this
+ * rule and their other arguments before they touch the device; a refused call returns non-zero.
+ * ------------------------------------------------------------------------- */
+
+/* ---------------------------------------------------------------------------
  * tfx_fir_stream_forward -- one chunk of a stateful FIR (streaming).
  * The reference's FIR is stateless (src/torchfx/filter/fir.py:526-579: every call left-pads with K-1
  * zeros), so StreamProcessor (src/torchfx/realtime/stream.py:164-347) is only seamless for FIR stages
@@ -248,8 +260,8 @@ int tfx_normalize_apply(const void *x, void *y, int dtype, int64_t C, int64_t T,
  *   y[c,n] = sum_{j<K} kernel[j] * xv[c, n+j],   xv = [hist_in[c, 0..K-2] | x[c, 0..T-1]],
  * the kernels read the K-1 history samples and the chunk from their two buffers (no concatenated copy),
  * and hist_out receives the last K-1 samples of xv for the next call.
- *   hist_in  DEVICE [C, K-1] of `dtype` or NULL (= zeros: first chunk);  hist_out DEVICE [C, K-1] or NULL,
- *   a different buffer than hist_in;  direct != 0: time-domain kernels, else overlap-save.
+ *   History as in "Stream history" with H = K-1; hist_out NULL: no history out.  direct != 0: time-domain kernels, else
+ *   overlap-save.
  * ------------------------------------------------------------------------- */
 int tfx_fir_stream_forward(const void *x, void *y, int dtype, int64_t C, int64_t T,
                            const void *kernel_host, int64_t K, int direct,
@@ -275,7 +287,8 @@ int tfx_quantile_abs(const float *x, int64_t n, double q, double *out_dev, tfx_s
  *   Limits (tfx_chunk_supported): T <= 4096, K <= 64, Kf <= 4096, T * Kf <= 2^22 -- a latency path, not a throughput one.
  *   x_pitch: elements between consecutive rows of x (a chunk is usually a column window of a longer [C, T_total] buffer:
  *   no contiguous copy needed); 0 = T.  y is contiguous [C, T].
- *   state pointers: DEVICE float64 [K, C, 2] (in: NULL = zeros);  hist: DEVICE float32 [C, Kf-1], in and out distinct;
+ *   state pointers: DEVICE float64 [K, C, 2] (in: NULL = zeros);  history as in "Stream history", float32 with H = Kf-1 (its
+ *   overlap rule takes x as (C-1)*x_pitch + T floats); hist_out NULL: no history out;
  *   sos_host [K, 6] HOST float64;  taps_host HOST float32 (flipped, like the module's kernel buffer).
  * ------------------------------------------------------------------------- */
 int tfx_chunk_supported(int64_t C, int64_t T, int64_t K, int64_t Kf);
@@ -339,14 +352,12 @@ int tfx_delay_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T
  * Each row's chunk continues the last H = taps*delay input samples of that row (hist_in):
  *   v = [hist_in[r] | x[r]],  wet[n] = sum_{i=1..taps} amps[i-1] * src_v[H + n - i*delay]   (tap order, +0.0 start)
  *   y[n] = lerp(x[n], wet[n], mix)   n in [0, T);   hist_out[r] = the newest H samples of v
- * x DEVICE [rows, T] of dtype; y DEVICE [rows, T]; hist_in DEVICE [rows, H] or NULL (= silence: the first chunk);
- * hist_out DEVICE [rows, H] (may be NULL only when rows*H = 0); neither y nor hist_out may overlap x, hist_in or each
- * other (checked: the kernel reads the inputs and writes the outputs from different workgroups); amps and
- * pingpong as for tfx_delay_forward (ping-pong rows read the partner row's history).  The outputs of consecutive chunks,
+ * x DEVICE [rows, T] of dtype; y DEVICE [rows, T]; history as in "Stream history" (the kernel reads the inputs and
+ * writes the outputs from different workgroups); amps and pingpong as for tfx_delay_forward (ping-pong rows read the partner row's
+ * history).  The outputs of consecutive chunks,
  * followed by those of H zero samples (the ring-out), are bit-identical to tfx_delay_forward on the whole signal.
- * T = 0 leaves y empty and copies the history.  One launch.  Arguments are checked before the device is touched (null
- * pointers, taps < 1, delay < 0, negative sizes, odd rows with ping-pong, bad dtype, overlapping buffers, overflow of
- * taps*delay).
+ * T = 0 leaves y empty and copies the history.  One launch.  Refused: null pointers, taps < 1, delay < 0, negative sizes,
+ * odd rows with ping-pong, bad dtype, overflow of taps*delay.
  * ------------------------------------------------------------------------- */
 int tfx_delay_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
                              const double *amps_host, double mix, int pingpong, const void *hist_in, void *hist_out,
@@ -356,10 +367,8 @@ int tfx_delay_stream_forward(const void *x, void *y, int dtype, int64_t rows, in
  * tfx_delay_line_stream_forward -- one chunk of tfx_delay_line_forward over a continuous stream (StatefulReverb):
  *   v = [hist_in[c] | x[c]],  y[c,n] = x[c,n] + (mix*decay) * v[c, n]   (v indexed from the start of hist_in),
  *   hist_out[c] = the newest `delay` samples of v.
- * x, y DEVICE [C, T]; hist_in DEVICE [C, delay] or NULL (= silence: the first `delay` outputs copy x, as the one-shot
- * call leaves them); hist_out DEVICE [C, delay].  Neither y nor hist_out may overlap x, hist_in or each other (checked).
- * Same arithmetic as tfx_delay_line_forward.
- * One launch; arguments are checked before the device is touched.
+ * x, y DEVICE [C, T]; history as in "Stream history" with H = delay (silence: the first `delay` outputs copy x, as the
+ * one-shot call leaves them).  Same arithmetic as tfx_delay_line_forward.  One launch.
  * ------------------------------------------------------------------------- */
 int tfx_delay_line_stream_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int64_t delay, double decay,
                                   double mix, const void *hist_in, void *hist_out, tfx_stream_t stream);
@@ -391,12 +400,11 @@ int tfx_resample_plan_info(int64_t T, int64_t up, int64_t down, int64_t nh, int 
  * (up, down reduced by their gcd) n_pre_pad and n_pre_remove as above and Lp_s = ceil((nh + n_pre_pad) / up) taps per phase.
  * After `consumed` = N input samples per row it has emitted M(N) = max(0, ceil(N*up/down) - n_pre_remove) outputs; a chunk of
  * T samples emits outputs [M(N), M(N + T)) of the whole signal's, each final (it reads no input past N + T - 1).  Every row
- * carries the last H = Lp_s - 1 input samples: hist_in DEVICE [rows, H] holds inputs [N - H, N) (zeros before 0; NULL =
- * silence), hist_out DEVICE [rows, H] receives [N + T - H, N + T).  The remaining ceil(N*up/down) - M(N) outputs come from
+ * carries the last H = Lp_s - 1 input samples ("Stream history"): hist_in holds inputs [N - H, N) (zeros before 0), hist_out
+ * receives [N + T - H, N + T).  The remaining ceil(N*up/down) - M(N) outputs come from
  * feeding zeros.  For finite inputs, the chunks' outputs equal tfx_resample_forward on the whole signal bit for bit (up to the
  * sign of a zero): each output is the same fma chain.  up == down: y = x and H = 0.
- * x DEVICE [rows, T], y DEVICE [rows, M(N + T) - M(N)], taps_host as for tfx_resample_forward.  y and hist_out may not overlap
- * x, hist_in or each other.  Arguments are checked before the device is touched.
+ * x DEVICE [rows, T], y DEVICE [rows, M(N + T) - M(N)], taps_host as for tfx_resample_forward.
  * ------------------------------------------------------------------------- */
 int tfx_resample_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
                                 const void *taps_host, int64_t nh, int64_t consumed, const void *hist_in, void *hist_out,

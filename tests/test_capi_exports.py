@@ -155,6 +155,36 @@ def _build_c_host(tmp_path, with_hip=False):
     return exe
 
 
+def test_fir_and_chunk_streams_refuse_overlapping_buffers_before_the_device():
+    """The stream-history buffer rule (torchfx_hip.h, "Stream history") holds for tfx_fir_stream_forward and
+    tfx_chunk_forward as for the other streams: refused before any launch, so no device is needed to see it."""
+    from torchfx_amd import _lib
+    lib = _lib.load()
+    buf = (ctypes.c_float * 512)()
+    at = lambda k: ctypes.c_void_p(ctypes.addressof(buf) + 4 * k)    # noqa: E731
+    taps = (ctypes.c_float * 33)(*([1.0 / 33] * 33))
+    # C = 2 rows; (T, taps, x, y, hist_in, hist_out, x_pitch), offsets in floats; H = taps - 1
+    cases = {
+        "aliased histories": (8, 5, 0, 16, 32, 32, 0),                   # x [0, 16), y [16, 32), hist_in [32, 40)
+        "overlapping histories": (8, 5, 0, 16, 32, 36, 0),
+        "hist_out inside y": (8, 5, 0, 16, 32, 20, 0),
+        "y inside hist_in": (8, 33, 0, 20, 16, 100, 0),                  # hist_in [16, 80), y [20, 36)
+        "y = x": (8, 5, 0, 0, 32, 40, 0),
+        "hist_out overlaps x": (8, 5, 0, 16, 32, 8, 0),
+        "y overlaps the pitched x": (8, 5, 0, 20, 40, 50, 20),          # x rows [0, 8) and [20, 28)
+    }
+    for what, (T, K, x, y, hin, hout, pitch) in cases.items():
+        own = "own buffer" if "histories" in what else "may not overlap"
+        if not pitch:
+            assert lib.tfx_fir_stream_forward(at(x), at(y), 0, 2, T, taps, K, 1, at(hin), at(hout), None) != 0, what
+            err = lib.tfx_last_error()
+            assert b"fir_stream_forward" in err and own.encode() in err, (what, err)
+        assert lib.tfx_chunk_forward(at(x), pitch, at(y), 2, T, None, 0, None, None, None, None, taps, K, at(hin), at(hout),
+                                     1.0, 0, 0, 0, None) != 0, what
+        err = lib.tfx_last_error()
+        assert b"chunk_forward" in err and own.encode() in err, (what, err)
+
+
 def test_plain_c_host_builds_and_runs_without_a_gpu(tmp_path):
     exe = _build_c_host(tmp_path)
     out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout

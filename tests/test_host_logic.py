@@ -856,3 +856,29 @@ def test_stream_processor_fuses_small_chunks_and_keeps_member_state(oracle_backe
     big.process_tensor(torch.zeros(2, 8192), fs)
     assert [c[0] for c in oracle_backend.calls] == ["sos_forward", "gain_forward"]
     assert not any(isinstance(s, _ChunkRun) for s in StreamProcessor([F.LoButterworth(3000, order=4, fs=fs)], 512, device="cpu")._segments)
+
+
+def test_stateful_fir_keeps_its_newest_history_when_the_tap_count_changes(oracle_backend):
+    """A StatefulFIR whose tap count changes mid-stream carries the newest samples of its history (zeros in front when
+    it grows), as StatefulDelay does when its history length changes -- alone and inside a fused chunk run."""
+    from torchfx_amd.effect import Gain
+    from torchfx_amd.realtime import StatefulFIR, _ChunkRun
+    x = torch.from_numpy(np.random.default_rng(5).standard_normal((2, 300))).float()
+    long_taps, short_taps = np.hanning(9) / np.hanning(9).sum(), [0.5, 0.3, 0.2]
+
+    def fresh(taps, v):
+        return StatefulFIR(taps, conv_mode="direct")(v)
+
+    for make in (lambda f: f, lambda f: _ChunkRun([], f, Gain(1.0))):
+        fir = StatefulFIR(long_taps, conv_mode="direct")
+        run = make(fir)
+        run(x[:, :100])
+        assert torch.equal(fir._hist, x[:, 92:100])
+        fir.kernel = StatefulFIR(short_taps).kernel                   # 9 -> 3 taps: the newest 2 samples carry over
+        y = run(x[:, 100:200])
+        assert fir._hist.shape == (2, 2)
+        close(y, fresh(short_taps, x[:, 98:200])[:, 2:].numpy(), 1e-6)
+        fir.kernel = StatefulFIR(long_taps).kernel                    # 3 -> 9 taps: [0 * 6 | newest 2]
+        y = run(x[:, 200:])
+        v = torch.cat([torch.zeros(2, 6), x[:, 198:]], dim=-1)
+        close(y, fresh(long_taps, v)[:, 8:].numpy(), 1e-6)

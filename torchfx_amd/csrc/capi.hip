@@ -470,15 +470,17 @@ int tfx_fir_stream_forward(const void *x, void *y, int dtype, int64_t C, int64_t
 {
     TFX_API_BEGIN
     TFX_CHECK(K >= 1, "fir_stream_forward: empty kernel");
+    TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "fir_stream_forward: bad dtype %d", dtype);
+    TFX_CHECK(C >= 0 && T >= 0 && (C == 0 || (T <= INT64_MAX / 16 / C && K <= INT64_MAX / 16 / C)),
+              "fir_stream_forward: negative size or size overflows");
+    TFX_CHECK(C == 0 || T == 0 || x, "fir_stream_forward: null signal");
     const int64_t H = K - 1;
+    check_stream_buffers("fir_stream_forward", dtype == TFX_F32 ? 4 : 8, x, C * T, y, C * T, hist_in, hist_out, C * H);
     if (C > 0 && T > 0) {
         if (direct) fir_direct_forward(x, y, dtype, C, T, kernel_host, K, (hipStream_t)stream, H ? hist_in : nullptr, hist_in ? H : 0);
         else fft_conv_forward(x, y, dtype, C, T, kernel_host, K, H, 0, (hipStream_t)stream, H ? hist_in : nullptr, hist_in ? H : 0);
     }
-    if (hist_out && C > 0) {
-        TFX_CHECK(T == 0 || x, "fir_stream_forward: null signal");
-        fir_hist_update(x, hist_in, hist_out, dtype, C, T, H, (hipStream_t)stream);
-    }
+    if (hist_out && C > 0) fir_hist_update(x, hist_in, hist_out, dtype, C, T, H, (hipStream_t)stream);
     TFX_API_END
 }
 

@@ -66,6 +66,32 @@ void scratch_clear();
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// ---- stream history (include/torchfx_hip.h, "Stream history") ------------------------------------------------------------
+// The buffer rule of every streaming entry point, checked before the device is touched: hist_out gets its own buffer, and
+// neither y nor hist_out may overlap x, hist_in or each other.  Extents count elements of esz bytes (the caller has ruled out
+// overflow); a null pointer or an empty extent overlaps nothing.  Messages start with `what`, the entry point's name.
+inline void check_stream_buffers(const char *what, size_t esz, const void *x, int64_t xn, const void *y, int64_t yn,
+                                 const void *hist_in, const void *hist_out, int64_t hn)
+{
+    const auto apart = [esz](const void *a, int64_t na, const void *b, int64_t nb) {
+        if (!a || !b || na <= 0 || nb <= 0) return true;
+        const char *p = (const char *)a, *q = (const char *)b;
+        return p + (size_t)na * esz <= q || q + (size_t)nb * esz <= p;
+    };
+    TFX_CHECK(apart(hist_in, hn, hist_out, hn), "%s: the new history needs its own buffer", what);
+    TFX_CHECK(apart(y, yn, x, xn) && apart(y, yn, hist_in, hn) && apart(hist_out, hn, x, xn) && apart(y, yn, hist_out, hn),
+              "%s: y and hist_out may not overlap x, hist_in or each other", what);
+}
+
+// Sample T_ + j of a row's [hr (H samples) | xr (T_ samples)], zero where there is no history (hr null): element j of the
+// history the next chunk gets.
+template <typename T>
+__device__ __forceinline__ T stream_hist_at(const T *xr, const T *hr, int64_t T_, int64_t H, int64_t j)
+{
+    const int64_t v = T_ + j;
+    return v >= H ? xr[v - H] : (hr ? hr[v] : (T)0);
+}
+
 // ---- tuning knobs from the environment (TFX_*) --------------------------------------------------
 // Read ONCE per process and name (capi.hip): a dispatch asks for about ten of them and a short-row call lasts 8-30 us.
 // The table is keyed by the knob's text (a per-thread, pointer-keyed shortcut in front of it is checked against the text, so

@@ -441,17 +441,8 @@ __global__ void __launch_bounds__(DLY_THREADS) delay_stream_kernel(const DelaySt
     for (int e = 0; e < DLY_STR_E; ++e) {
         const int64_t j = tile * DLY_STR_HTILE + e * DLY_THREADS + threadIdx.x;
         if (j >= p.H) break;
-        const int64_t v = p.T_ + j;
-        ho[j] = v >= p.H ? xr[v - p.H] : (hr ? hr[v] : (T)0);
+        ho[j] = stream_hist_at(xr, hr, p.T_, p.H, j);
     }
-}
-
-// [a, a + na) and [b, b + nb) share no byte (null pointers and empty ranges share none)
-static bool stream_disjoint(const void *a, size_t na, const void *b, size_t nb)
-{
-    if (!a || !b || !na || !nb) return true;
-    const char *p = (const char *)a, *q = (const char *)b;
-    return p + na <= q || q + nb <= p;
 }
 
 void delay_stream_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
@@ -468,11 +459,7 @@ void delay_stream_check(const void *x, const void *y, int dtype, int64_t rows, i
     const int64_t H = taps * delay;
     TFX_CHECK(rows == 0 || (T <= INT64_MAX / 4 / rows && H <= INT64_MAX / 4 / rows), "delay_stream_forward: size overflows");
     TFX_CHECK((x || rows * T == 0) && (y || rows * T == 0) && (hist_out || rows * H == 0), "delay_stream_forward: null pointer");
-    const size_t esz = dtype == TFX_F32 ? 4 : 8, xb = (size_t)(rows * T) * esz, hb = (size_t)(rows * H) * esz;
-    TFX_CHECK(stream_disjoint(hist_in, hb, hist_out, hb), "delay_stream_forward: the new history needs its own buffer");
-    TFX_CHECK(stream_disjoint(y, xb, x, xb) && stream_disjoint(y, xb, hist_in, hb) && stream_disjoint(hist_out, hb, x, xb) &&
-                  stream_disjoint(y, xb, hist_out, hb),
-              "delay_stream_forward: y and hist_out may not overlap x, hist_in or each other");
+    check_stream_buffers("delay_stream_forward", dtype == TFX_F32 ? 4 : 8, x, rows * T, y, rows * T, hist_in, hist_out, rows * H);
 }
 
 template <typename T>

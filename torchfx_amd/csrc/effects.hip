@@ -332,17 +332,8 @@ delay_line_stream_kernel(const T *__restrict__ x, const T *__restrict__ hist_in,
     for (int e = 0; e < EFX_STR_E; ++e) {
         const int64_t j = tile * EFX_STR_TILE + e * EFX_THREADS + threadIdx.x;
         if (j >= D) break;
-        const int64_t v = T_ + j;
-        ho[j] = v >= D ? xr[v - D] : (hr ? hr[v] : (T)0);
+        ho[j] = stream_hist_at(xr, hr, T_, D, j);
     }
-}
-
-// [a, a + na) and [b, b + nb) share no byte (null pointers and empty ranges share none)
-static bool stream_disjoint(const void *a, size_t na, const void *b, size_t nb)
-{
-    if (!a || !b || !na || !nb) return true;
-    const char *p = (const char *)a, *q = (const char *)b;
-    return p + na <= q || q + nb <= p;
 }
 
 void delay_line_stream_check(const void *x, const void *y, int dtype, int64_t C, int64_t T, int64_t delay, const void *hist_in,
@@ -353,11 +344,7 @@ void delay_line_stream_check(const void *x, const void *y, int dtype, int64_t C,
     TFX_CHECK(C >= 0 && T >= 0, "delay_line_stream_forward: negative size");
     TFX_CHECK(C == 0 || (T <= INT64_MAX / 4 / C && delay <= INT64_MAX / 4 / C), "delay_line_stream_forward: size overflows");
     TFX_CHECK((x || C * T == 0) && (y || C * T == 0) && (hist_out || C * delay == 0), "delay_line_stream_forward: null pointer");
-    const size_t esz = dtype == TFX_F32 ? 4 : 8, xb = (size_t)(C * T) * esz, hb = (size_t)(C * delay) * esz;
-    TFX_CHECK(stream_disjoint(hist_in, hb, hist_out, hb), "delay_line_stream_forward: the new history needs its own buffer");
-    TFX_CHECK(stream_disjoint(y, xb, x, xb) && stream_disjoint(y, xb, hist_in, hb) && stream_disjoint(hist_out, hb, x, xb) &&
-                  stream_disjoint(y, xb, hist_out, hb),
-              "delay_line_stream_forward: y and hist_out may not overlap x, hist_in or each other");
+    check_stream_buffers("delay_line_stream_forward", dtype == TFX_F32 ? 4 : 8, x, C * T, y, C * T, hist_in, hist_out, C * delay);
 }
 
 void delay_line_stream_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int64_t delay, double coeff,

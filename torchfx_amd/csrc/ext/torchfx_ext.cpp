@@ -285,6 +285,23 @@ Tensor delay_line_op(const Tensor &x, int64_t delay_samples, double decay, doubl
     return y;
 }
 
+// The streaming ops' history (include/torchfx_hip.h, "Stream history"): the previous chunk's [rows, H] on x's device and in
+// x's dtype, or undefined (= silence: None, or nothing to carry)
+Tensor stream_hist_in(const OptTensor &hist, const Tensor &x, int64_t rows, int64_t H, const char *what)
+{
+    if (!hist.has_value() || !hist->defined() || rows * H == 0) return Tensor();
+    TORCH_CHECK(hist->dim() == 2 && hist->size(0) == rows && hist->size(1) == H, what, ": history must be [rows, H] = [", rows, ", ", H,
+                "], got ", hist->sizes());
+    return hist->to(x.device(), x.scalar_type()).contiguous();
+}
+
+// rows of x [..., T]: the leading dimensions flattened (also for T = 0)
+int64_t stream_rows(const Tensor &x)
+{
+    TORCH_CHECK(x.dim() >= 1, "stream: x must have a time dimension");
+    return c10::multiply_integers(x.sizes().begin(), x.sizes().end() - 1);
+}
+
 // BPM-synced multi-tap Delay (effect.py:934-1538): x [..., T] -> [..., T + taps*D], leading dimensions flattened into rows;
 // ping-pong when the second-to-last dimension holds a stereo pair, as PingPongDelayStrategy decides
 std::vector<int64_t> delay_shape(const Tensor &x, int64_t delay_samples, int64_t taps)
@@ -304,7 +321,7 @@ std::tuple<Tensor, Tensor> delay_impl(const Tensor &x_in, int64_t delay_samples,
     const int64_t taps = (int64_t)amps.size();
     const std::vector<int64_t> shape = delay_shape(x_in, delay_samples, taps);
     const Tensor x = x_in.contiguous();
-    const int64_t T = x.size(-1), rows = T > 0 ? x.numel() / T : c10::multiply_integers(x.sizes().begin(), x.sizes().end() - 1);
+    const int64_t T = x.size(-1), rows = stream_rows(x);
     const bool pp = pingpong && x.dim() >= 2 && x.size(-2) == 2;
     Tensor y = at::empty(shape, x.options()), stat;
     const tfx_epilogue ep = make_epilogue(gain, clamp, stat_mode, per_row, stat, x, rows);
@@ -329,20 +346,6 @@ Tensor delay_op(const Tensor &x, int64_t delay_samples, at::ArrayRef<double> amp
 // one chunk of a streaming Delay / delay line (StatefulDelay, StatefulReverb): x [..., T] -> (y [..., T], new history [rows, H]).
 // The history of the previous chunk (None = silence) and the chunk are read from their two buffers; the new history is a fresh
 // tensor every call (the graph replay of realtime.py copies it into its persistent home).
-Tensor stream_hist_in(const OptTensor &hist, const Tensor &x, int64_t rows, int64_t H, const char *what)
-{
-    if (!hist.has_value() || !hist->defined() || rows * H == 0) return Tensor();
-    TORCH_CHECK(hist->dim() == 2 && hist->size(0) == rows && hist->size(1) == H, what, ": history must be [rows, H] = [", rows, ", ", H,
-                "], got ", hist->sizes());
-    return hist->to(x.device(), x.scalar_type()).contiguous();
-}
-
-int64_t stream_rows(const Tensor &x)
-{
-    TORCH_CHECK(x.dim() >= 1, "stream: x must have a time dimension");
-    return c10::multiply_integers(x.sizes().begin(), x.sizes().end() - 1);
-}
-
 std::tuple<Tensor, Tensor> delay_stream_op(const Tensor &x_in, const OptTensor &hist, int64_t delay_samples, at::ArrayRef<double> amps,
                                            double mix, bool pingpong)
 {
@@ -398,7 +401,7 @@ Tensor resample_op(const Tensor &x_in, int64_t up, int64_t down, const Tensor &h
     TORCH_CHECK(h.scalar_type() == x_in.scalar_type(), "resample_forward: h must have x's dtype (", x_in.scalar_type(), "), got ",
                 h.scalar_type());
     const Tensor x = x_in.contiguous(), hc = h.contiguous();
-    const int64_t T = x.size(-1), rows = T > 0 ? x.numel() / T : c10::multiply_integers(x.sizes().begin(), x.sizes().end() - 1);
+    const int64_t T = x.size(-1), rows = stream_rows(x);
     Tensor y = at::empty(shape, x.options());
     c10::hip::HIPGuard guard(x.get_device());
     check_rc(tfx_resample_forward(x.data_ptr(), y.data_ptr(), dtype_code(x, "resample_forward"), rows, T, up, down, hc.data_ptr(),
@@ -557,19 +560,13 @@ std::tuple<Tensor, Tensor> fir_stream_op(const Tensor &x_in, const Tensor &kerne
     const Tensor k = taps_host(kernel, x);
     const int64_t C = x.size(0), T = x.size(1), K = k.numel();
     TORCH_CHECK(K >= 1, "fir_stream_forward: empty kernel");
-    Tensor hin;
-    const void *hp = nullptr;
-    if (hist.has_value() && hist->defined() && K > 1) {
-        TORCH_CHECK(hist->dim() == 2 && hist->size(0) == C && hist->size(1) == K - 1, "fir_stream_forward: history must be [C, K-1] = [",
-                    C, ", ", K - 1, "], got ", hist->sizes());
-        hin = hist->to(x.device(), x.scalar_type()).contiguous();
-        hp = hin.data_ptr();
-    }
+    const Tensor hin = stream_hist_in(hist, x, C, K - 1, "fir_stream_forward");
     Tensor y = at::empty_like(x);
     Tensor hout = at::empty({C, K - 1}, x.options());
     c10::hip::HIPGuard guard(x.get_device());
     check_rc(tfx_fir_stream_forward(x.data_ptr(), y.data_ptr(), dtype_code(x, "fir_stream_forward"), C, T, k.data_ptr(), K,
-                                    direct ? 1 : 0, hp, K > 1 ? hout.data_ptr() : nullptr, stream_of(x)),
+                                    direct ? 1 : 0, hin.defined() ? hin.data_ptr() : nullptr, K > 1 ? hout.data_ptr() : nullptr,
+                                    stream_of(x)),
              "fir_stream_forward");
     return {y, hout};
 }
@@ -589,16 +586,10 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> chunk_op(const Tensor &x_in, const Te
     const Tensor k = taps_host(kernel, x);
     const int64_t C = x.size(0), T = x.size(1), K = sos.size(0), Kf = k.numel();
     TORCH_CHECK(tfx_chunk_supported(C, T, K, Kf), "chunk_forward: unsupported geometry C=", C, " T=", T, " K=", K, " taps=", Kf);
-    Tensor kx, ky, hin;
+    Tensor kx, ky;
     const double *sx = K ? state_ptr(state_x, {K, C, 2}, x, "state_x", kx) : nullptr;
     const double *sy = K ? state_ptr(state_y, {K, C, 2}, x, "state_y", ky) : nullptr;
-    const float *hp = nullptr;
-    if (hist.has_value() && hist->defined() && Kf > 1) {
-        TORCH_CHECK(hist->dim() == 2 && hist->size(0) == C && hist->size(1) == Kf - 1, "chunk_forward: history must be [C, K-1] = [",
-                    C, ", ", Kf - 1, "], got ", hist->sizes());
-        hin = hist->to(x.device(), at::kFloat).contiguous();
-        hp = hin.data_ptr<float>();
-    }
+    const Tensor hin = stream_hist_in(hist, x, C, Kf - 1, "chunk_forward");
     Tensor y = at::empty({C, T}, x.options());
     Tensor nsx = at::empty({K, C, 2}, x.options().dtype(at::kDouble));
     Tensor nsy = at::empty({K, C, 2}, x.options().dtype(at::kDouble));
@@ -606,8 +597,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> chunk_op(const Tensor &x_in, const Te
     c10::hip::HIPGuard guard(x.get_device());
     check_rc(tfx_chunk_forward(x.data_ptr<float>(), C > 1 ? x.stride(0) : T, y.data_ptr<float>(), C, T, K ? sos.data_ptr<double>() : nullptr, K, sx, sy,
                                K ? nsx.data_ptr<double>() : nullptr, K ? nsy.data_ptr<double>() : nullptr, k.data_ptr<float>(), Kf,
-                               hp, Kf > 1 ? hout.data_ptr<float>() : nullptr, gain, scale ? 1 : 0, clamp ? 1 : 0,
-                               precision_or_default(precision), stream_of(x)),
+                               hin.defined() ? hin.data_ptr<float>() : nullptr, Kf > 1 ? hout.data_ptr<float>() : nullptr, gain,
+                               scale ? 1 : 0, clamp ? 1 : 0, precision_or_default(precision), stream_of(x)),
              "chunk_forward");
     return {y, nsx, nsy, hout};
 }

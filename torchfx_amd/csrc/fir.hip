@@ -253,16 +253,14 @@ fir_hist_update_kernel(const T *__restrict__ x, const T *__restrict__ hist_in, T
 {
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (g >= C * H) return;
-    const int64_t c = g / H, i = g - c * H;
-    const int64_t j = Tn - H + i;                 // index into x; negative -> older history
-    hist_out[g] = j >= 0 ? x[c * Tn + j] : (hist_in ? hist_in[c * H + H + j] : (T)0);
+    const int64_t c = g / H;
+    hist_out[g] = stream_hist_at(x + c * Tn, hist_in ? hist_in + c * H : nullptr, Tn, H, g - c * H);
 }
 
 void fir_hist_update(const void *x, const void *hist_in, void *hist_out, int dtype, int64_t C, int64_t T, int64_t H,
                      hipStream_t stream)
 {
     if (C * H == 0) return;
-    TFX_CHECK(hist_out && hist_out != hist_in, "fir_stream_forward: the new history needs its own buffer");
     const unsigned grid = (unsigned)ceil_div(C * H, 256);
     if (dtype == TFX_F32)
         hipLaunchKernelGGL(fir_hist_update_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float *)x,

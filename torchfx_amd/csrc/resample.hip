@@ -143,10 +143,7 @@ __global__ void __launch_bounds__(RS_THREADS) resample_kernel(const ResampleArgs
     if (STREAM) {
         if (tile == 0) {                                            // new history: the last H of [hist | chunk]
             T *ho = p.hist_out + row * p.H;
-            for (int64_t k = threadIdx.x; k < p.H; k += RS_THREADS) {
-                const int64_t v = k + p.T_;
-                ho[k] = v >= p.H ? xr[v - p.H] : (hr ? hr[v] : (T)0);
-            }
+            for (int64_t k = threadIdx.x; k < p.H; k += RS_THREADS) ho[k] = stream_hist_at(xr, hr, p.T_, p.H, k);
         }
         if (p.n_out <= mb) return;                                  // a chunk that completes no output (uniform per launch)
     }
@@ -390,14 +387,6 @@ static void resample_stream_plan(int64_t N, int64_t T, int64_t *up, int64_t *dow
     *t = resample_tiling(*up, *down, g->pre_remove, g->Lp, esz);
 }
 
-// [a, a + na) and [b, b + nb) share no byte (null pointers and empty ranges share none)
-static bool rs_disjoint(const void *a, size_t na, const void *b, size_t nb)
-{
-    if (!a || !b || !na || !nb) return true;
-    const char *p = (const char *)a, *q = (const char *)b;
-    return p + na <= q || q + nb <= p;
-}
-
 void resample_stream_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
                            const void *taps_host, int64_t nh, int64_t consumed, const void *hist_in, const void *hist_out)
 {
@@ -417,11 +406,7 @@ void resample_stream_check(const void *x, const void *y, int dtype, int64_t rows
     TFX_CHECK(rows == 0 || (T <= INT64_MAX / 16 / rows && n_y <= INT64_MAX / 16 / rows && g.H <= INT64_MAX / 16 / rows),
               "resample_stream_forward: size overflows");
     TFX_CHECK((x || rows * T == 0) && (y || rows * n_y == 0) && (hist_out || rows * g.H == 0), "resample_stream_forward: null pointer");
-    const size_t xb = (size_t)(rows * T) * esz, yb = (size_t)(rows * n_y) * esz, hb = (size_t)(rows * g.H) * esz;
-    TFX_CHECK(rs_disjoint(hist_in, hb, hist_out, hb), "resample_stream_forward: the new history needs its own buffer");
-    TFX_CHECK(rs_disjoint(y, yb, x, xb) && rs_disjoint(y, yb, hist_in, hb) && rs_disjoint(hist_out, hb, x, xb) &&
-                  rs_disjoint(y, yb, hist_out, hb),
-              "resample_stream_forward: y and hist_out may not overlap x, hist_in or each other");
+    check_stream_buffers("resample_stream_forward", esz, x, rows * T, y, rows * n_y, hist_in, hist_out, rows * g.H);
 }
 
 // host-only: what resample_stream_forward does with a chunk of T samples after `consumed` (arguments as resample_stream_check's)

@@ -1302,13 +1302,14 @@ void chunk_forward(const float *x, int64_t x_pitch, float *y, int64_t C, int64_t
     TFX_CHECK(chunk_supported(C, T, K, Kf), "chunk_forward: unsupported geometry C=%lld T=%lld K=%lld taps=%lld "
               "(T <= 4096, K <= 64, T * taps <= 2^22)", (long long)C, (long long)T, (long long)K, (long long)Kf);
     TFX_CHECK(x && y && taps_host && (K == 0 || sos_host), "chunk_forward: null pointer");
-    TFX_CHECK(hist_out == nullptr || hist_out != hist_in, "chunk_forward: the new history needs its own buffer");   // NULL = silence in / no history out
+    if (x_pitch <= 0) x_pitch = T;
+    TFX_CHECK(x_pitch >= T, "chunk_forward: row pitch %lld smaller than the row length %lld", (long long)x_pitch, (long long)T);
+    TFX_CHECK(x_pitch <= INT64_MAX / 8 / C, "chunk_forward: row pitch %lld overflows", (long long)x_pitch);
+    check_stream_buffers("chunk_forward", 4, x, (C - 1) * x_pitch + T, y, C * T, hist_in, hist_out, C * (Kf - 1));
     ChunkParams q{};
     SosParams &p = q.sos;
     p.x = x; p.y = nullptr; p.taps = nullptr;
     p.sx_in = sx_in; p.sy_in = sy_in; p.sx_out = sx_out; p.sy_out = sy_out;
-    if (x_pitch <= 0) x_pitch = T;
-    TFX_CHECK(x_pitch >= T, "chunk_forward: row pitch %lld smaller than the row length %lld", (long long)x_pitch, (long long)T);
     p.C = C; p.C_in = C; p.T = T; p.K = (int)K; p.x_pitch = x_pitch;
     p.nseg = 1; p.warm = 0; p.seg_len = ceil_div(T, 1024) * 1024; p.nsum = 0;
     p.ep_stat = -1; p.nf_flag = nullptr;

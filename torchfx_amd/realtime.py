@@ -41,6 +41,12 @@ from torchfx_amd.filter.fir import FIR
 from torchfx_amd.resample import Resample, design_taps, window_key
 
 
+def _rows(x: Tensor) -> int:
+    if x.ndim not in (1, 2, 3):
+        raise ValueError("Input must be of shape [T], [C, T], or [B, C, T]")
+    return math.prod(x.shape[:-1])
+
+
 class StatefulFIR(FIR):
     """FIR whose K-1 sample input history survives between calls (``reset_state()`` clears it):
     filtering a signal chunk by chunk equals filtering it in one piece."""
@@ -58,33 +64,22 @@ class StatefulFIR(FIR):
     def forward(self, x: Tensor) -> Tensor:
         from torchfx_amd import torchfx_ext
 
-        if x.ndim not in (1, 2, 3):
-            raise ValueError("Input must be of shape [T], [C, T], or [B, C, T]")
-        shape = x.shape
-        rows = x.reshape(-1, shape[-1])
+        rows = _rows(x)
+        xr = x.reshape(-1, x.shape[-1])
         taps = self.kernel.reshape(-1)
         k = taps.numel()
         if k == 1:
             return super().forward(x)
-        h = self._hist
-        if h is not None and (h.shape[0] != rows.shape[0] or h.dtype != rows.dtype or h.device != rows.device):
-            h = None                                          # row count / dtype / device changed: start from silence
         # history and chunk stay in their own buffers (tfx_fir_stream_forward reads both); no torch.cat.
         # Small chunks take the one-launch direct kernel whatever the mode (a 2 x 512 chunk through the FFT path is
         # half a dozen launches for a microsecond of arithmetic); both paths meet the same 1e-5 bar.
-        direct = self._conv_mode == "direct" or rows.shape[0] * rows.shape[1] * k <= self.DIRECT_BELOW_MACS
-        y, self._hist = torchfx_ext.fir_stream_forward(rows, taps, h, direct)
-        return y.reshape(shape)
-
-
-def _rows(x: Tensor) -> int:
-    if x.ndim not in (1, 2, 3):
-        raise ValueError("Input must be of shape [T], [C, T], or [B, C, T]")
-    return math.prod(x.shape[:-1])
+        direct = self._conv_mode == "direct" or x.numel() * k <= self.DIRECT_BELOW_MACS
+        y, self._hist = torchfx_ext.fir_stream_forward(xr, taps, _carried(self._hist, rows, k - 1, x), direct)
+        return y.reshape(x.shape)
 
 
 def _carried(hist: Tensor | None, rows: int, H: int, x: Tensor) -> Tensor | None:
-    """The history a delay effect carries into this chunk: None (silence) when there is none or the row count, dtype or
+    """The history a stateful effect carries into this chunk: None (silence) when there is none or the row count, dtype or
     device changed; when only its length ``H`` changed, the newest ``min(H_old, H)`` samples, zero-filled at the front."""
     if hist is None or hist.shape[0] != rows or hist.dtype != x.dtype or hist.device != x.device:
         return None
@@ -102,7 +97,19 @@ def _native_stream(x: Tensor) -> bool:
     return x.is_cuda and x.dtype in (torch.float32, torch.float64)
 
 
-class StatefulDelay(Delay):
+class _RingOut:
+    """The stream's last chunk as ``flush()`` needs it: ``_note(x)`` keeps its leading shape, dtype and device in ``_last``
+    (``reset_state`` sets it to None) and ``_zeros(n)`` is a chunk of ``n`` zero samples shaped like it."""
+
+    def _note(self, x: Tensor) -> None:
+        self._last = (tuple(x.shape[:-1]), x.dtype, x.device)
+
+    def _zeros(self, n: int) -> Tensor:
+        lead, dtype, device = self._last
+        return torch.zeros(*lead, n, dtype=dtype, device=device)
+
+
+class StatefulDelay(_RingOut, Delay):
     """:class:`~torchfx_amd.effect.Delay` over a continuous stream: every chunk's output has the chunk's shape, the last
     ``H = taps * delay_samples`` input samples of every row are carried in ``_hist`` (``[rows, H]``) and :meth:`flush`
     returns the ring-out (``[..., H]``).  The chunks' outputs followed by the ring-out are bit-identical to ``Delay`` on
@@ -121,12 +128,11 @@ class StatefulDelay(Delay):
             raise TypeError(f"StatefulDelay streams MonoDelayStrategy and PingPongDelayStrategy only, got {type(self.strategy).__name__}")
         self._bpm_synced = delay_samples is None
         self._bpm_key = (bpm, delay_time, fs) if self.delay_samples is not None else None
-        self._hist: Tensor | None = None
-        self._last: tuple | None = None             # (leading shape, dtype, device) of the last chunk, for flush()
+        self.reset_state()
 
     def reset_state(self) -> None:
-        self._hist = None
-        self._last = None
+        self._hist: Tensor | None = None
+        self._last: tuple | None = None
 
     def _delay(self) -> int:
         """The delay of this chunk: a BPM-synced instance follows ``bpm``, ``delay_time`` and ``fs``."""
@@ -153,7 +159,7 @@ class StatefulDelay(Delay):
         taps = int(self.taps)
         H, T = taps * D, x.shape[-1]
         h = _carried(self._hist, rows, H, x)
-        self._last = (tuple(x.shape[:-1]), x.dtype, x.device)
+        self._note(x)
         if _native_stream(x):
             y, self._hist = _ext().delay_stream_forward(x, h, D, taps, self.feedback, self.mix, self.pingpong(x))
             return y
@@ -169,8 +175,7 @@ class StatefulDelay(Delay):
         last chunk; then the state is reset.  Without a chunk since the last reset: an empty tensor."""
         if self._last is None:
             return torch.zeros(0)
-        lead, dtype, device = self._last
-        tail = self.forward(torch.zeros(*lead, int(self.taps) * self._delay(), dtype=dtype, device=device))
+        tail = self.forward(self._zeros(int(self.taps) * self._delay()))
         self.reset_state()
         return tail
 
@@ -215,7 +220,7 @@ class StatefulReverb(Reverb):
         return Reverb.forward(self, v.reshape(*x.shape[:-1], D + T))[..., D:]
 
 
-class StatefulResample(Resample):
+class StatefulResample(_RingOut, Resample):
     """:class:`~torchfx_amd.resample.Resample` over a continuous stream: chunks go in, the converted signal comes out in
     pieces with no seam.  After chunks of ``N`` input samples per row in all the stream has returned exactly
     ``M(N) = max(0, ceil(N * up / down) - latency)`` outputs, each final; :meth:`flush` returns the ``latency`` (at most)
@@ -240,7 +245,7 @@ class StatefulResample(Resample):
         self._emitted = 0                           # M(N): output samples per row so far
         self._key: tuple | None = None              # (rows, dtype, device, new_fs, fs, window) of the running stream
         self._geo: tuple[int, int] = (0, 0)         # its (n_pre_remove, history length)
-        self._last: tuple | None = None             # (leading shape, dtype, device) of the last chunk, for flush()
+        self._last: tuple | None = None
 
     def _geometry(self, up: int, down: int) -> tuple[int, int]:
         """``(n_pre_remove, Lp_s - 1)`` of the designed filter: the outputs held back and the history length."""
@@ -287,7 +292,7 @@ class StatefulResample(Resample):
         if key != self._key:                        # a new stream: from silence
             self.reset_state()
             self._key, self._geo = key, self._geometry(up, down)
-        self._last = (tuple(x.shape[:-1]), x.dtype, x.device)
+        self._note(x)
         T = x.shape[-1]
         if up == down:
             y = x.clone()
@@ -339,18 +344,17 @@ class StatefulResample(Resample):
         tensor."""
         if self._last is None:
             return torch.zeros(0)
-        lead, dtype, device = self._last
         up, down = self._ratio()
         pre = self._geometry(up, down)[0]
         N = self._consumed
         rem = -(-N * up // down) - self._emitted
         if rem <= 0:
-            tail = torch.zeros(*lead, 0, dtype=dtype, device=device)
+            tail = self._zeros(0)
         else:
             Z = -(-pre * down // up)                       # zeros that complete every held-back output
             while self._emit_count(N + Z, up, down, pre) - self._emitted < rem:
                 Z += 1
-            tail = self.forward(torch.zeros(*lead, Z, dtype=dtype, device=device))[..., :rem].contiguous()
+            tail = self.forward(self._zeros(Z))[..., :rem].contiguous()
         self.reset_state()
         return tail
 
@@ -435,9 +439,7 @@ class _ChunkRun:
             return w
         rows = w.shape[0]
         sx, sy = self._states(rows, w.device)
-        hist = self.fir._hist if self.fir is not None else None
-        if hist is not None and (hist.shape[0] != rows or hist.dtype != w.dtype or hist.device != w.device):
-            hist = None
+        hist = _carried(self.fir._hist, rows, taps.numel() - 1, w) if self.fir is not None else None
         g = self.gain.linear_gain() if self.gain is not None else None
         y, nsx, nsy, nh = torchfx_ext.chunk_forward(w, sos, sx, sy, taps, hist, g,
                                                     bool(self.gain is not None and self.gain.clamp))
@@ -643,27 +645,27 @@ class StreamProcessor:
         graph.replay()
         return static_out.clone()
 
-    @torch.no_grad()
-    def process_chunks(self, x: Tensor, fs: int) -> Generator[Tensor, None, None]:
-        """Yield processed chunks; with overlap the first ``overlap`` samples of every chunk but the
-        first are dropped (``stream.py:327-331``)."""
-        self._configure_effects(fs)
-        n = x.shape[-1]
-        hop = self._chunk_size - self._overlap
-        offset = 0
+    def _steps(self, chunks) -> Generator[Tensor, None, None]:
+        """The chain over ``(offset, device chunk)`` pairs, then the resamplers' tails; with overlap the first ``overlap``
+        samples of every chunk but the first are dropped (``stream.py:327-331``)."""
         primed = False
-        while offset < n:
-            w = x[..., offset:offset + self._chunk_size].to(self._device)
-            full = w.shape[-1] == self._chunk_size
-            if self._use_graph and full and primed and w.is_cuda and not self._fused(w) and not self._resamplers:
+        for offset, w in chunks:
+            if (self._use_graph and primed and w.is_cuda and w.shape[-1] == self._chunk_size and not self._fused(w)
+                    and not self._resamplers):
                 w = self._graph_step(w)
             else:
                 w = self._run(w)            # first chunk creates the states; ragged tail runs eagerly
                 primed = True
             if w is not None:
                 yield w[..., self._overlap:] if (self._overlap > 0 and offset > 0) else w
-            offset += hop
         yield from self._tails()
+
+    @torch.no_grad()
+    def process_chunks(self, x: Tensor, fs: int) -> Generator[Tensor, None, None]:
+        """Yield processed chunks of ``x`` (see :meth:`_steps`)."""
+        self._configure_effects(fs)
+        hop = self._chunk_size - self._overlap
+        yield from self._steps((o, x[..., o:o + self._chunk_size].to(self._device)) for o in range(0, x.shape[-1], hop))
 
     @torch.no_grad()
     def process_tensor(self, x: Tensor, fs: int) -> Tensor:
@@ -671,41 +673,26 @@ class StreamProcessor:
         return torch.cat(list(self.process_chunks(x, fs)), dim=-1)
 
     # ---- files (``stream.py:164-347``) -------------------------------------------------------------
-    def _file_steps(self, input_path) -> Generator[tuple[Tensor, bool], None, None]:
-        """Decode ``chunk_size`` frames at a time, run the effects on the device, yield the planar
-        ``[C, n]`` result (device tensor) with the overlap already dropped."""
+    def _file_chunks(self, input_path) -> Generator[tuple[int, Tensor], None, None]:
+        """Decode ``chunk_size`` frames at a time and yield ``(offset, planar [C, n] chunk on the device)``."""
         import soundfile as sf
 
         from torchfx_amd import io as _io
 
         info = sf.info(str(input_path))
-        fs, num_frames = info.samplerate, info.frames
-        self._configure_effects(fs)
-        hop = self._chunk_size - self._overlap
+        self._configure_effects(info.samplerate)
         on_gpu = torch.device(self._device).type == "cuda"
-        offset, primed = 0, False
-        while offset < num_frames:
-            n = min(self._chunk_size, num_frames - offset)
+        for offset in range(0, info.frames, self._chunk_size - self._overlap):
+            n = min(self._chunk_size, info.frames - offset)
             frames, _ = sf.read(str(input_path), start=offset, stop=offset + n, dtype="float32", always_2d=True)
             # interleaved [n, C] -> planar [C, n] on the device (reference: data_np.T.copy() on the host)
-            w = _io.upload_interleaved(frames, self._device) if on_gpu else torch.from_numpy(frames.T.copy())
-            if (self._use_graph and on_gpu and primed and w.shape[-1] == self._chunk_size and not self._fused(w)
-                    and not self._resamplers):
-                w = self._graph_step(w)
-            else:
-                w = self._run(w)
-                primed = True
-            if w is not None:
-                yield (w[..., self._overlap:] if (self._overlap > 0 and offset > 0) else w), fs
-            offset += hop
-        for w in self._tails():
-            yield w, fs
+            yield offset, (_io.upload_interleaved(frames, self._device) if on_gpu else torch.from_numpy(frames.T.copy()))
 
     @torch.no_grad()
     def process_file_chunks(self, input_path) -> Generator[Tensor, None, None]:
         """Generator over processed chunks of a file, as host tensors ``[channels, frames]`` like the
         reference's ``process_chunks(path)`` (``stream.py:278-347``)."""
-        for w, _ in self._file_steps(input_path):
+        for w in self._steps(self._file_chunks(input_path)):
             yield w.cpu()
 
     @torch.no_grad()
@@ -731,7 +718,7 @@ class StreamProcessor:
         with sf.SoundFile(str(out), mode="w", samplerate=self.output_rate(info.samplerate), channels=info.channels, format=format,
                           subtype=subtype) as sink:
             hostbuf = None                                            # one host buffer for every chunk on its way out
-            for w, _ in self._file_steps(input_path):
+            for w in self._steps(self._file_chunks(input_path)):
                 if w.is_cuda and w.dim() == 2 and w.dtype == torch.float32:
                     if hostbuf is None or hostbuf.shape[0] < w.shape[1] or hostbuf.shape[1] != w.shape[0]:
                         import numpy as np
