@@ -5,8 +5,8 @@
 //     y[c,n] = sum_{t<K} kf[t] * xp[c, n+t],   xp[m] = x[m-(K-1)]  (zero for m < K-1)
 //
 // float32: 2K flop/sample (2048 at K=1024) makes this FP32-rate bound, not HBM bound.  gfx950 has
-// an exact-f32 matrix instruction, v_mfma_f32_32x32x2_f32 (bitwise an fmaf chain, same peak as
-// the vector ALU but one instruction per 4096 flop), so the convolution is phrased as a
+// an exact-f32 matrix instruction, v_mfma_f32_32x32x2_f32 (on finite data bitwise an fmaf chain, same
+// peak as the vector ALU but one instruction per 4096 flop), so the convolution is phrased as a
 // Toeplitz product on the matrix pipe -- NOT to "reach MFMA" with reduced precision, the
 // arithmetic is plain f32 FMA:
 //     out(i,j) = y[nb + 32 i + j] = sum_s  A[i][s] * B[s][j]
@@ -15,6 +15,15 @@
 // Each wave owns NJ output tiles of 32x32 = 1024 consecutive samples and re-uses every B fragment
 // across them; a workgroup (4 waves) covers 4 x NJ x 1024 outputs of one channel per pass and walks
 // the taps in chunks of <= 1024 so the LDS window stays bounded for any K.
+//
+// Non-finite samples.  The Toeplitz array multiplies its zero padding (31 in front, 33 behind, K rounded up to
+// the chunk) with real samples, and 0 * NaN = 0 * Inf = NaN: left alone, a bad sample at p would reach outputs
+// before p and after p + K - 1, and an Inf inside its reach would come out as NaN.  But the padded sum touches a
+// superset of the reference's samples and NaN / Inf never leave an accumulator, so a FINITE result has met no
+// bad sample and stands; a thread forms each of its non-finite results again after the tap loop as a plain
+// fmaf chain over the K real taps -- the terms of the reference, no others; zero-VALUED taps are multiplied
+// like any other.  A bad sample at p reaches exactly y[p .. p + K - 1] of its row ("Non-finite
+// samples in the direct FIR"; tests/test_gpu_fir_edges.py); finite data never takes the branch and keeps its bits.
 //
 // float64 signals (the reference computes conv1d in the input dtype) use a plain LDS-tiled
 // vector kernel: rare path, correctness first.
@@ -47,6 +56,8 @@ constexpr int FIR_NJ = 1;                       // 32x32 tiles per wave
 constexpr int FIR_NOUT = 4 * FIR_NJ * 1024;     // outputs per workgroup
 constexpr int FIR_KC_MAX = 1024;                // largest tap chunk (taps are zero-padded to it)
 constexpr int64_t FIR_MFMA_MIN_T = 4096;        // float32 rows shorter than this run the plain kernel
+
+constexpr int FIR_CLASS_NONFINITE = 0x207;      // v_cmp_class mask: signalling NaN | quiet NaN | -Inf | +Inf
 
 __device__ __forceinline__ int xpad33(int m) { return m + (m >> 5); }
 
@@ -196,6 +207,8 @@ fir_direct_mfma_kernel(const float *__restrict__ x, float *__restrict__ y,
     // keeping `li` / `kk` alive through the contraction cost the 96-VGPR kernel its one spilled register.
     const int lane_e = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     const int li_e = lane_e & 31, kk_e = lane_e >> 5;
+    static_assert(NJ * 16 <= 32, "one bit of `redo` per accumulator");
+    unsigned redo = 0;                                      // accumulators that came out NaN / Inf
 #pragma unroll
     for (int t = 0; t < NJ; ++t) {
         const int64_t nb = n0 + wave * WOUT + t * 1024;
@@ -204,6 +217,26 @@ fir_direct_mfma_kernel(const float *__restrict__ x, float *__restrict__ y,
             const int i = 8 * (r >> 2) + 4 * kk_e + (r & 3);
             const int64_t n = nb + 32 * i + li_e;
             if ((DBG & 1) ? (acc[t][r] == 1234.5f) : (n < T)) yrow[n] = acc[t][r];
+            redo |= (unsigned)__builtin_amdgcn_classf(acc[t][r], FIR_CLASS_NONFINITE) << (16 * t + r);
+        }
+    }
+    // rare: non-finite results (see the header).  Each again from the definition: the K real taps in tap order, the sum
+    // fir_direct_simple_kernel forms, samples straight from memory.  Here, after the stores, the accumulators are dead: the
+    // branch costs the steady-state kernel no register (inside the tap loop it cost 13 and a wave of occupancy).
+    if (DBG == 0 && redo) {
+        const int nl0 = wave * WOUT + 128 * kk_e + li_e;
+#pragma unroll 1
+        for (int q = 0; q < NJ * 16; ++q) {
+            const int64_t n = n0 + nl0 + (q >> 4) * 1024 + 32 * (8 * ((q & 15) >> 2) + (q & 3));
+            if (!((redo >> q) & 1u) || n >= T) continue;
+            float a = 0.0f;
+#pragma unroll 1
+            for (int u = 0; u < K; ++u) {
+                const int64_t g = n + u - (int64_t)(K - 1);          // <= n < T
+                const float v = g >= 0 ? xrow[g] : ((hist && g >= -(int64_t)H) ? hist[c * H + H + g] : 0.0f);
+                a = fmaf(kf_dev[u], v, a);
+            }
+            yrow[n] = a;
         }
     }
 }

@@ -1212,6 +1212,7 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in,
 struct ChunkParams {
     SosParams sos;           // x = the chunk [C, T] with row pitch sos.x_pitch; y is replaced by the LDS buffer inside the kernel
     const float *taps;       // device: [Hpad - H zeros | flipped taps (Kf) | zeros up to Hpad + 4]   (cached_taps)
+                             // (the zeros only fill the float4 groups: the kernel never multiplies them)
     const float *hist_in;    // [C, Kf - 1] or null (= silence)
     float *hist_out;         // [C, Kf - 1] or null
     float *y;                // [C, T]
@@ -1260,19 +1261,27 @@ __global__ void __launch_bounds__(1024) chunk_iir_fir_kernel(const ChunkParams q
     for (int n0 = 4 * tid; n0 < T; n0 += 4 * nthr) {
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         float4 a = ub4[n0 >> 2];
-        for (int k = 0; k < Kp; k += 4) {
+        // taps [jlo, jhi) of the group at k; the sample window slides on by four either way
+        const auto group = [&](int k, int jlo, int jhi) {
             const float4 b = ub4[((n0 + k) >> 2) + 1];
             const float4 h = kp4[k >> 2];
             const float win[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                acc[r] = fmaf(h.x, win[r], acc[r]);
-                acc[r] = fmaf(h.y, win[r + 1], acc[r]);
-                acc[r] = fmaf(h.z, win[r + 2], acc[r]);
-                acc[r] = fmaf(h.w, win[r + 3], acc[r]);
+                if (jlo <= 0 && 0 < jhi) acc[r] = fmaf(h.x, win[r], acc[r]);
+                if (jlo <= 1 && 1 < jhi) acc[r] = fmaf(h.y, win[r + 1], acc[r]);
+                if (jlo <= 2 && 2 < jhi) acc[r] = fmaf(h.z, win[r + 2], acc[r]);
+                if (jlo <= 3 && 3 < jhi) acc[r] = fmaf(h.w, win[r + 3], acc[r]);
             }
             a = b;
-        }
+        };
+        // The padding taps are never multiplied: 0 * NaN = 0 * Inf = NaN would carry a non-finite sample to outputs outside
+        // its K-sample reach (the trailing zeros meet the three samples AFTER the output, the leading ones older history).
+        // First group: its Hpad - H leading zeros are skipped; last group: the last real tap and three zeros.  Real taps are
+        // multiplied whatever their value, in the same order as before: finite data keeps its bits.
+        group(0, Hpad - H, Kp == 4 ? 1 : 4);
+        for (int k = 4; k < Kp - 4; k += 4) group(k, 0, 4);
+        if (Kp > 4) group(Kp - 4, 0, 1);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int n = n0 + r;
