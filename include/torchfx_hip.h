@@ -123,6 +123,33 @@ int tfx_sos_plan_info(const double *sos_host, int64_t K,
                       int *precision, int64_t *warmup, double *err_bound);
 
 /* ---------------------------------------------------------------------------
+ * tfx_sos_filtfilt_forward -- zero-phase (forward-backward) filtering along each row with the semantics of
+ * scipy.signal.sosfiltfilt(sos, x, axis=-1, padtype, padlen) (SciPy 1.15); the reference has no counterpart.
+ * The cascade runs over the row extended by `padlen` samples at each end, then backward over its own output, each
+ * pass started from the cascade's steady state for its first sample (sosfilt_zi), in float64 DF1 arithmetic.  Two
+ * cascade launches around one float64 intermediate: the extension and the time reversal are index arithmetic, the
+ * signal is read once and written once (24 B per float32 sample).  A row with a NaN comes back all NaN, a row
+ * with an Inf all non-finite.
+ *   x        DEVICE [C,T] of x_dtype;  y DEVICE [C,T] of y_dtype (written)
+ *   sos_host HOST   [K,6] float64, a0 = 1; a section with a pole at z = 1 (a0 + a1 + a2 = 0) is an error
+ *   padtype  enum tfx_padtype;  padlen >= 0, or -1 for SciPy's default (tfx_sos_filtfilt_plan_info reports it);
+ *            T <= padlen is an error
+ *   work     DEVICE float64 [C * (T + 2 * padlen)], provided by the caller (the intermediate); contents on
+ *            return are unspecified
+ * ------------------------------------------------------------------------- */
+enum tfx_padtype { TFX_PAD_ODD = 0, TFX_PAD_EVEN = 1, TFX_PAD_CONSTANT = 2, TFX_PAD_NONE = 3 };
+int tfx_sos_filtfilt_forward(const void *x, int x_dtype, void *y, int y_dtype,
+                             int64_t C, int64_t T,
+                             const double *sos_host, int64_t K,
+                             int padtype, int64_t padlen, double *work, tfx_stream_t stream);
+/* What tfx_sos_filtfilt_forward does for [C,T] rows (host-only; same argument checks): SciPy's default padlen for
+ * this cascade, the padlen in force, the elements of `work`, the warm-up halo of a time segment (-1 = one segment
+ * per row) and the segments per row of the forward and of the reverse pass.  Any output may be NULL. */
+int tfx_sos_filtfilt_plan_info(int64_t C, int64_t T, const double *sos_host, int64_t K, int padtype, int64_t padlen,
+                               int64_t *default_padlen, int64_t *padlen_used, int64_t *work_elems, int64_t *warmup,
+                               int *nseg_forward, int *nseg_reverse);
+
+/* ---------------------------------------------------------------------------
  * tfx_biquad_forward -- single DF1 biquad.
  * Replaces  torchfx_ext.biquad_forward(x, b, a1, a2, state_x, state_y)
  *           binding.cpp:30-50,84-87 -> biquad_forward_cpu iir_cpu.cpp:10-62 /

@@ -20,6 +20,11 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C, in
                  double *sx_out, double *sy_out, void *y_sections, int precision, hipStream_t stream, int64_t NB = 1,
                  bool sum_bands = false, const Epilogue *ep = nullptr);
 void sos_plan_info(const double *sos_host, int64_t K, int *precision, int64_t *warmup, double *err_bound);
+void sos_filtfilt_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C, int64_t T, const double *sos_host, int64_t K,
+                          int padtype, int64_t padlen, double *work, hipStream_t stream);
+void sos_filtfilt_plan_info(int64_t C, int64_t T, const double *sos_host, int64_t K, int padtype, int64_t padlen,
+                            int64_t *default_padlen, int64_t *padlen_used, int64_t *work_elems, int64_t *warmup,
+                            int *nseg_forward, int *nseg_reverse);
 void sos_clear_plans();
 void fir_direct_forward(const void *x, void *y, int dtype, int64_t C, int64_t T,
                         const void *kernel_host, int64_t K, hipStream_t stream, const void *hist = nullptr, int64_t H = 0);
@@ -424,6 +429,23 @@ int tfx_sos_bank_sum_forward(const void *x, int x_dtype, void *y, int y_dtype, i
     TFX_API_BEGIN
     sos_forward(x, x_dtype, y, y_dtype, C, T, sos_host, K, state_x_in, state_y_in, state_x_out, state_y_out,
                 nullptr, precision, (hipStream_t)stream, n_bands, true);
+    TFX_API_END
+}
+
+int tfx_sos_filtfilt_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C, int64_t T,
+                             const double *sos_host, int64_t K, int padtype, int64_t padlen, double *work, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    sos_filtfilt_forward(x, x_dtype, y, y_dtype, C, T, sos_host, K, padtype, padlen, work, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_sos_filtfilt_plan_info(int64_t C, int64_t T, const double *sos_host, int64_t K, int padtype, int64_t padlen,
+                               int64_t *default_padlen, int64_t *padlen_used, int64_t *work_elems, int64_t *warmup,
+                               int *nseg_forward, int *nseg_reverse)
+{
+    TFX_API_BEGIN
+    sos_filtfilt_plan_info(C, T, sos_host, K, padtype, padlen, default_padlen, padlen_used, work_elems, warmup, nseg_forward, nseg_reverse);
     TFX_API_END
 }
 

@@ -410,6 +410,32 @@ Tensor resample_op(const Tensor &x_in, int64_t up, int64_t down, const Tensor &h
     return y;
 }
 
+// Zero-phase filtering (scipy.signal.sosfiltfilt along the last axis): x [..., T] -> [..., T] of x's dtype, leading dimensions
+// flattened into rows; sos HOST [K, 6]; padtype as enum tfx_padtype, padlen -1 = SciPy's default.  The float64 intermediate
+// [rows, T + 2 padlen] is a temporary tensor of PyTorch's allocator, released when the op returns (stream-ordered reuse).
+Tensor sos_filtfilt_op(const Tensor &x_in, const Tensor &sos_cpu, int64_t padtype, int64_t padlen)
+{
+    need_device(x_in, "x");
+    TORCH_CHECK(x_in.dim() >= 1, "sos_filtfilt: x must have a time dimension");
+    const Tensor sos = host_f64(sos_cpu, 6, "sos_filtfilt");
+    TORCH_CHECK(sos.dim() == 2, "sos_filtfilt: sos must be [K, 6]");
+    const Tensor x = x_in.contiguous();
+    const int64_t T = x.size(-1), rows = stream_rows(x), K = sos.size(0);
+    const int dt = dtype_code(x, "sos_filtfilt");
+    int64_t work_elems = 0;
+    check_rc(tfx_sos_filtfilt_plan_info(rows, T, sos.data_ptr<double>(), K, (int)padtype, padlen, nullptr, nullptr, &work_elems,
+                                        nullptr, nullptr, nullptr),
+             "sos_filtfilt");
+    Tensor y = at::empty_like(x);
+    if (rows == 0) return y;
+    Tensor work = at::empty({work_elems}, x.options().dtype(at::kDouble));
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_sos_filtfilt_forward(x.data_ptr(), dt, y.data_ptr(), dt, rows, T, sos.data_ptr<double>(), K, (int)padtype, padlen,
+                                      work.data_ptr<double>(), stream_of(x)),
+             "sos_filtfilt");
+    return y;
+}
+
 // One chunk of a resampling stream (tfx_resample_stream_forward): x [..., T] after `consumed` samples per row, h as for
 // resample_forward, hist [rows, H] (None = silence) -> (y [..., M(consumed + T) - M(consumed)], new history [rows, H])
 struct ResampleStreamPlan {
@@ -813,6 +839,7 @@ TORCH_LIBRARY(torchfx_hip, m)
     m.def("delay_line_forward(Tensor(a) x, int delay_samples, float decay, float mix) -> Tensor(a)");
     m.def("delay_forward(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong) -> Tensor");
     m.def("resample_forward(Tensor x, int up, int down, Tensor h) -> Tensor");
+    m.def("sos_filtfilt(Tensor x, Tensor sos_cpu, int padtype=0, int padlen=-1) -> Tensor");
     m.def("resample_stream_forward(Tensor x, Tensor h, Tensor? hist, int up, int down, int consumed) -> (Tensor, Tensor)");
     m.def("delay_forward_ep(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong, float gain, bool clamp, int stat_mode, "
           "bool per_row) -> (Tensor, Tensor)");
@@ -850,6 +877,7 @@ TORCH_LIBRARY_IMPL(torchfx_hip, CUDA, m)          // "CUDA" is the dispatch key 
     m.impl("delay_line_forward", delay_line_op);
     m.impl("delay_forward", delay_op);
     m.impl("resample_forward", resample_op);
+    m.impl("sos_filtfilt", sos_filtfilt_op);
     m.impl("resample_stream_forward", resample_stream_op);
     m.impl("delay_forward_ep", delay_ep_op);
     m.impl("delay_stream_forward", delay_stream_op);
@@ -883,6 +911,7 @@ TORCH_LIBRARY_IMPL(torchfx_hip, Meta, m)
     m.impl("fft_conv_forward", fft_conv_meta);
     m.impl("delay_forward", delay_meta);
     m.impl("resample_forward", resample_meta);
+    m.impl("sos_filtfilt", [](const Tensor &x, const Tensor &, int64_t, int64_t) { return at::empty_like(x); });
     m.impl("resample_stream_forward", resample_stream_meta);
     m.impl("delay_forward_ep", delay_ep_meta);
     m.impl("delay_stream_forward", delay_stream_meta);
@@ -904,7 +933,7 @@ static void no_cpu_boxed(const c10::OperatorHandle &op, c10::DispatchKeySet, tor
 TORCH_LIBRARY_IMPL(torchfx_hip, CPU, m)
 {
     for (const char *name : {"sos_forward", "sos_forward_sections", "sos_bank_forward", "sos_bank_sum_forward", "biquad_forward",
-                             "delay_line_forward", "delay_forward", "delay_forward_ep", "delay_stream_forward", "delay_line_stream_forward", "resample_forward", "resample_stream_forward", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
+                             "delay_line_forward", "delay_forward", "delay_forward_ep", "delay_stream_forward", "delay_line_stream_forward", "resample_forward", "sos_filtfilt", "resample_stream_forward", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
                              "fft_conv_forward_ep", "sos_fft_conv_forward", "normalize_apply", "sum_forward", "gain_forward", "quantile_abs", "stat_forward",
                              "normalize_forward", "deinterleave_forward", "deinterleave_into", "interleave_forward"})
         m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());

@@ -35,6 +35,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 namespace tfx {
@@ -81,7 +82,27 @@ struct SosParams {
     int fair;            // > 0: waves that share a SIMD alternate their issue priority every 2^fair clocks
     int fair_nw;         // waves per SIMD of this launch (the priority levels that rotate): 2 ... 4
     int unit;            // host side only: `tab` holds the unit-b0 form (UNIT kernels)
+    // zero-phase passes (FF kernels, sos_filtfilt_forward): T above is the length of the edge-extended row, ff_T + 2 * ff_pad
+    int ff;              // 1 = forward pass over the virtual extension of x, 2 = reverse-time pass over the intermediate
+    int ff_padtype;      // TFX_PAD_ODD / EVEN / CONSTANT (NONE arrives as ff_pad = 0)
+    int64_t ff_T;        // samples per row of the signal itself
+    int64_t ff_pad;      // samples the row is extended by at each end
+    const double *ff_gain;   // device [K + 1]: G_(s-1) at [s], the DC gain of the sections in front of section s (G_(-1) = 1)
 };
+
+// Sample i of the row x[0 .. T) extended by `pad` samples at each end (scipy.signal's odd_ext / even_ext / const_ext), i counted
+// from the start of the extension; pad < T.
+template <typename TIn>
+__device__ __forceinline__ double ff_ext_sample(const TIn *__restrict__ x, int64_t T, int64_t pad, int padtype, int64_t i)
+{
+    const int64_t j = i - pad;
+    if (j >= 0 && j < T) return (double)x[j];
+    const int64_t edge = j < 0 ? 0 : T - 1;
+    const int64_t mirror = j < 0 ? -j : 2 * (T - 1) - j;
+    if (padtype == TFX_PAD_CONSTANT) return (double)x[edge];
+    if (padtype == TFX_PAD_EVEN) return (double)x[mirror];
+    return 2.0 * (double)x[edge] - (double)x[mirror];
+}
 
 __device__ __forceinline__ void wave_sync()
 {
@@ -141,14 +162,22 @@ template <typename T> struct U16 {               // 16 bytes of T
 //      zeros_like + in-place adds -- so N branches cost 8 B/sample instead of N x 8 + (N + 1) x 4
 // EPI  epilogue on the stored samples (epilogue.h); a separate instantiation so that the plain kernel keeps
 //      its register budget (the statistic accumulator and the extra selects cost ~30 VGPRs = one wave per SIMD)
+// FF   zero-phase pass (SosParams::ff): 1 reads the virtual edge extension of x, 2 walks the float64 intermediate from its
+//      end and stores the signal's own samples at their reversed places; both start from the cascade's steady state for
+//      the row's first sample (scipy.signal.sosfilt_zi * x[0]).  Scalar (!VEC) path only; FF = 0 compiles to the code
+//      it was before
+// FFR  the zero-phase passes of a float64 result refine the scan's start states once (see the scan below)
 // The stream body: one wavefront walks stream `sid` = (row, segment) with `stage` as its private LDS (transposition
 // stage + carry).  Shared by the cascade kernel below and by the fused per-chunk kernel (chunk_iir_fir_kernel), whose
 // output pointer is an LDS buffer.
-template <typename TIn, typename TOut, typename TC, int LC, bool VEC, bool TAPS, bool PF, bool SUMB, bool EPI, bool UNIT = false>
+template <typename TIn, typename TOut, typename TC, int LC, bool VEC, bool TAPS, bool PF, bool SUMB, bool EPI, bool UNIT = false, int FF = 0, bool FFR = false>
 __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_t sid, char *const stage, const int lane)
 {
     static_assert(!(TAPS && SUMB), "section taps are not available in sum mode");
     static_assert(!(UNIT && (TAPS || SUMB)), "the unit-b0 form serves the plain cascade only");
+    static_assert(FF == 0 || !(VEC || TAPS || PF || SUMB || EPI || UNIT), "the zero-phase passes run the plain scalar path");
+    // what the LDS stage holds on the way in: the odd extension 2 x[0] - x[i] of a float32 row is not a float32 value
+    typedef typename std::conditional<FF == 1, TC, TIn>::type TSt;
     constexpr int IOB = sizeof(TIn) > sizeof(TOut) ? sizeof(TIn) : sizeof(TOut);
     constexpr int CHUNK_B = LC * IOB + 16;   // per-lane chunk, padded: conflict-free b128 access
     constexpr int STAGE_B = 64 * CHUNK_B;
@@ -158,7 +187,7 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
 #define TFX_SB 4
 #endif
     constexpr int SB = TFX_SB;          // scheduling-barrier period (samples)
-    constexpr int EI = 16 / sizeof(TIn), NUI = LC / EI;   // elems per 16 B, units per lane (in)
+    constexpr int EI = 16 / sizeof(TSt), NUI = LC / EI;   // elems per 16 B, units per lane (in)
     constexpr int EO = 16 / sizeof(TOut), NUO = LC / EO;  // (out)
 
     const int K = p.K;
@@ -179,7 +208,7 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
     const int64_t band = SUMB ? 0 : c / p.C_in;
     const int64_t st_rows = SUMB ? p.C_in * nbl : p.C;     // rows of the [K, rows, 2] state tensors
     const TIn *__restrict__ xrow = (const TIn *)p.x + (c - band * p.C_in) * p.x_pitch;
-    TOut *__restrict__ yrow = (TOut *)p.y + c * T;
+    TOut *__restrict__ yrow = (TOut *)p.y + c * (FF == 2 ? p.ff_T : T);
     // Coefficient tables live in the CONSTANT address space: wave-uniform indices then lower to
     // s_load (scalar cache, SGPR operands) instead of per-lane vector loads.
     typedef const TC __attribute__((address_space(4))) *ctab_t;
@@ -204,9 +233,16 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
         const int s = rem >> 2, f = rem & 3;
         TC v = (TC)0;
         if (start == 0) {
-            const double *src = (f < 2) ? p.sx_in : p.sy_in;
-            if (src) v = (TC)src[((int64_t)s * st_rows + (SUMB ? b * p.C_in + c : c)) * 2 + (f & 1)];
-            if (UNIT) v *= ((const TC *)p.tab)[(band * K + s) * TS + (f < 2 ? 160 : 161)];      // into the section's scale
+            if constexpr (FF != 0) {
+                // steady state of the cascade for a constant input v0 = the first sample of the pass: section s has seen
+                // v0 G_(s-1) for ever and answered v0 G_s
+                const double v0 = FF == 1 ? ff_ext_sample(xrow, p.ff_T, p.ff_pad, p.ff_padtype, 0) : (double)xrow[T - 1];
+                v = (TC)(v0 * p.ff_gain[s + (f >> 1)]);
+            } else {
+                const double *src = (f < 2) ? p.sx_in : p.sy_in;
+                if (src) v = (TC)src[((int64_t)s * st_rows + (SUMB ? b * p.C_in + c : c)) * 2 + (f & 1)];
+                if (UNIT) v *= ((const TC *)p.tab)[(band * K + s) * TS + (f < 2 ? 160 : 161)];      // into the section's scale
+            }
         }
         carry[i] = v;
     }
@@ -215,7 +251,7 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
     // ---- global -> registers (coalesced).  Per-lane pointer + immediate offsets; the common
     //      full-tile case is branch-free, a partial tile (signal tail) is predicated.
     uint4 rawv[VEC ? NUI : 1];
-    TIn raws[VEC ? 1 : LC];
+    TSt raws[VEC ? 1 : LC];
     auto load_tile = [&](int64_t ts) {
         const int64_t left = T - ts;
         if constexpr (VEC) {
@@ -228,6 +264,31 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
 #pragma unroll
                 for (int i = 0; i < NUI; ++i)
                     rawv[i] = (i * 64 + lane < nv) ? xl[i * 64] : make_uint4(0, 0, 0, 0);
+            }
+        } else if constexpr (FF == 1) {
+            // element e of the tile is sample ts + e of the extended row; tiles inside the signal load it as it lies
+            const int64_t j0 = ts - p.ff_pad;
+            if (j0 >= 0 && j0 + TILE <= p.ff_T) {
+                const TIn *__restrict__ xl = xrow + j0 + lane;
+#pragma unroll
+                for (int i = 0; i < LC; ++i) raws[i] = (TSt)xl[i * 64];
+            } else {
+#pragma unroll
+                for (int i = 0; i < LC; ++i) {
+                    const int64_t n = ts + i * 64 + lane;
+                    raws[i] = n < T ? (TSt)ff_ext_sample(xrow, p.ff_T, p.ff_pad, p.ff_padtype, n) : (TSt)0;
+                }
+            }
+        } else if constexpr (FF == 2) {
+            // element e of the tile is sample T - 1 - (ts + e) of the intermediate: the row is walked from its end
+            const TIn *__restrict__ xl = xrow + (T - 1 - ts - lane);
+            if (left >= TILE) {
+#pragma unroll
+                for (int i = 0; i < LC; ++i) raws[i] = xl[-(i * 64)];
+            } else {
+                const int nv = (int)left;
+#pragma unroll
+                for (int i = 0; i < LC; ++i) raws[i] = (i * 64 + lane < nv) ? xl[-(i * 64)] : (TIn)0;
             }
         } else {
             const TIn *__restrict__ xl = xrow + ts + lane;
@@ -244,7 +305,7 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
     // LDS stage addresses: unit q = i*64 + lane lives at chunk q/NU, slot q%NU; 64 % NU == 0
     char *const st_in_v = stage + (lane / NUI) * CHUNK_B + (lane % NUI) * 16;
     char *const st_out_v = stage + (lane / NUO) * CHUNK_B + (lane % NUO) * 16;
-    char *const st_in_s = stage + (lane / LC) * CHUNK_B + (lane % LC) * (int)sizeof(TIn);     // LC | 64
+    char *const st_in_s = stage + (lane / LC) * CHUNK_B + (lane % LC) * (int)sizeof(TSt);     // LC | 64
     char *const st_out_s = stage + (lane / LC) * CHUNK_B + (lane % LC) * (int)sizeof(TOut);
     char *const st_own = stage + lane * CHUNK_B;
 
@@ -260,13 +321,13 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
             for (int i = 0; i < NUI; ++i) *(uint4 *)(st_in_v + i * (64 / NUI) * CHUNK_B) = rawv[i];
         } else {
 #pragma unroll
-            for (int i = 0; i < LC; ++i) *(TIn *)(st_in_s + i * (64 / LC) * CHUNK_B) = raws[i];
+            for (int i = 0; i < LC; ++i) *(TSt *)(st_in_s + i * (64 / LC) * CHUNK_B) = raws[i];
         }
         wave_sync();
         auto read_own = [&]() {
 #pragma unroll
             for (int i = 0; i < NUI; ++i) {
-                U16<TIn> v;
+                U16<TSt> v;
                 v.u = *(const uint4 *)(st_own + i * 16);
 #pragma unroll
                 for (int e = 0; e < EI; ++e) d[i * EI + e] = (TC)v.e[e];
@@ -377,24 +438,47 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
                 s0 += fma(pm[4 * K_ + 0], t0, pm[4 * K_ + 1] * t1);                       \
                 s1 += fma(pm[4 * K_ + 2], t0, pm[4 * K_ + 3] * t1);                       \
             }
-            TFX_KS_STEP(0, 0x111)   // row_shr:1
-            TFX_KS_STEP(1, 0x112)   // row_shr:2
-            TFX_KS_STEP(2, 0x114)   // row_shr:4
-            TFX_KS_STEP(3, 0x118)   // row_shr:8
-#undef TFX_KS_STEP
-            {
-                // b. rows 1 and 3 take in the aggregate of the row before them (row_bcast:15),
-                //    then rows 2 and 3 the inclusive value of lane 31 (row_bcast:31): two DPP
-                //    steps with per-lane matrices instead of readlanes + a select tree
-                const TC a0 = dpp_bcast<0x142, 0xA>(s0), a1 = dpp_bcast<0x142, 0xA>(s1);
-                s0 += fma(mqa[0], a0, mqa[1] * a1);
-                s1 += fma(mqa[2], a0, mqa[3] * a1);
-                const TC c0 = dpp_bcast<0x143, 0xC>(s0), c1 = dpp_bcast<0x143, 0xC>(s1);
-                s0 += fma(mqb[0], c0, mqb[1] * c1);
-                s1 += fma(mqb[2], c0, mqb[3] * c1);
+            // b. rows 1 and 3 take in the aggregate of the row before them (row_bcast:15),
+            //    then rows 2 and 3 the inclusive value of lane 31 (row_bcast:31): two DPP
+            //    steps with per-lane matrices instead of readlanes + a select tree
+#define TFX_LANE_SCAN()                                                                   \
+            TFX_KS_STEP(0, 0x111)   /* row_shr:1 */                                       \
+            TFX_KS_STEP(1, 0x112)   /* row_shr:2 */                                       \
+            TFX_KS_STEP(2, 0x114)   /* row_shr:4 */                                       \
+            TFX_KS_STEP(3, 0x118)   /* row_shr:8 */                                       \
+            {                                                                             \
+                const TC a0 = dpp_bcast<0x142, 0xA>(s0), a1 = dpp_bcast<0x142, 0xA>(s1);  \
+                s0 += fma(mqa[0], a0, mqa[1] * a1);                                       \
+                s1 += fma(mqa[2], a0, mqa[3] * a1);                                       \
+                const TC c0 = dpp_bcast<0x143, 0xC>(s0), c1 = dpp_bcast<0x143, 0xC>(s1);  \
+                s0 += fma(mqb[0], c0, mqb[1] * c1);                                       \
+                s1 += fma(mqb[2], c0, mqb[3] * c1);                                       \
             }
+            TFX_LANE_SCAN()
             TC h1 = dpp_shift<0x138>(s0), h2 = dpp_shift<0x138>(s1);     // wave_shr:1: state at chunk start
             if (lane == 0) { h1 = cy1; h2 = cy2; }                       // lane 0: the carried true state
+            if constexpr (FFR) {
+                // One step of iterative refinement of the start states.  The scan adds zero-state chunk responses that are
+                // hundreds of times larger than the state they cancel to when the poles lie next to z = 1 and the output
+                // is rough (high-pass, notch): 2e-9 of the output scale on HiButterworth(20) in float64, which the forward
+                // cascade's float32 results never see but a float64 zero-phase result does.  So: run the recursion once
+                // more from the start states just found; where chunk j - 1 ends and where chunk j was told to start differ
+                // by a residual of that size, and the same scan over the residuals (e_j = r_j + P e_(j-1), e_0 = 0) gives
+                // the correction with a relative error of its own.  What is left is the rounding of a sequential recursion.
+                TC w1 = h1, w2 = h2;
+#pragma unroll
+                for (int n = 0; n < LC; ++n) {
+                    const TC w = fma(na1, w1, fma(na2, w2, d[n]));
+                    w2 = w1;   w1 = w;
+                }
+                s0 = dpp_shift<0x138>(w1) - h1;
+                s1 = dpp_shift<0x138>(w2) - h2;
+                if (lane == 0) { s0 = (TC)0; s1 = (TC)0; }
+                TFX_LANE_SCAN()
+                h1 += s0;   h2 += s1;
+            }
+#undef TFX_LANE_SCAN
+#undef TFX_KS_STEP
 
             // (3) the recursion proper from the TRUE start state over the stored f[n]: 2 flop/sample,
             //     writes the section output in place.  (Cheaper than correcting the zero-state output
@@ -500,6 +584,19 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
                         if (q >= lo && q < hi) yl[i * 64] = v;
                     }
                 }
+            } else if constexpr (FF == 2) {
+                // sample n of this pass is sample T - 1 - ff_pad - n of the result; the extension's samples are not stored
+                const int64_t lo_s = p.ff_pad - ts, hi_s = p.ff_pad + p.ff_T - ts;
+                const int64_t lo2 = lo64 > lo_s ? lo64 : lo_s, hi2 = hi64 < hi_s ? hi64 : hi_s;
+                const int lo = lo2 > 0 ? (int)(lo2 < TILE ? lo2 : TILE) : 0;
+                const int hi = hi2 < TILE ? (int)(hi2 > 0 ? hi2 : 0) : TILE;
+                TOut *__restrict__ yl = yrow + (T - 1 - p.ff_pad - ts - lane);
+#pragma unroll
+                for (int i = 0; i < LC; ++i) {
+                    const int e = i * 64 + lane;
+                    const TOut v = *(const TOut *)(st_out_s + i * (64 / LC) * CHUNK_B);
+                    if (e >= lo && e < hi) yl[-(i * 64)] = v;
+                }
             } else {
                 TOut *__restrict__ yl = yrow + ts + lane;
                 const int lo = lo64 > 0 ? (int)lo64 : 0;
@@ -541,14 +638,14 @@ template <typename TC, int LC> __host__ __device__ inline int sos_carry_bytes(in
     return (((nbl * K * 4 + 2 * LC) * (int)sizeof(TC)) + 15) & ~15;
 }
 
-template <typename TIn, typename TOut, typename TC, int LC, bool VEC, bool TAPS, bool PF, int MINW, bool SUMB = false, bool EPI = false, bool UNIT = false>
+template <typename TIn, typename TOut, typename TC, int LC, bool VEC, bool TAPS, bool PF, int MINW, bool SUMB = false, bool EPI = false, bool UNIT = false, int FF = 0, bool FFR = false>
 __global__ void __launch_bounds__(256, MINW) sos_stream_kernel(const SosParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // provably wave-uniform -> SGPR addressing
     const int per_wave = sos_stage_bytes<TIn, TOut, TC, LC>() + sos_carry_bytes<TC, LC>(SUMB ? p.nsum : 1, p.K);
-    sos_stream_body<TIn, TOut, TC, LC, VEC, TAPS, PF, SUMB, EPI, UNIT>(p, (int64_t)blockIdx.x * 4 + wave, smem + wave * per_wave, lane);
+    sos_stream_body<TIn, TOut, TC, LC, VEC, TAPS, PF, SUMB, EPI, UNIT, FF, FFR>(p, (int64_t)blockIdx.x * 4 + wave, smem + wave * per_wave, lane);
 }
 
 // Non-finite samples and time segmentation.  In the sequential recursion a NaN / Inf never leaves: once the
@@ -580,6 +677,11 @@ __global__ void __launch_bounds__(256) sos_nonfinite_fix_kernel(const SosParams 
     if (begin >= T) return;
     TOut *y = (TOut *)p.y, *taps = (TOut *)p.taps;
     const TOut nanv = (TOut)__builtin_nan("");
+    if (p.ff == 2) {      // reverse-time pass: sample n of the pass lies at T - 1 - ff_pad - n of the result row (sos_stream_body)
+        const int64_t lo = begin > p.ff_pad ? begin : p.ff_pad, hi = p.ff_pad + p.ff_T;
+        for (int64_t n = lo + tid; n < hi; n += nthr) y[row * p.ff_T + (T - 1 - p.ff_pad - n)] = nanv;
+        return;
+    }
     for (int64_t n = begin + tid; n < T; n += nthr) y[row * T + n] = nanv;
     if (taps)
         for (int sct = 0; sct < p.K; ++sct)
@@ -607,6 +709,7 @@ struct SosPlan {
     double err_bound_f32 = -1.0;  // worst-case |err| of f32 arithmetic for |x| <= 1 (lazy)
     std::unique_ptr<DeviceBuffer> tab_f64_lc32, tab_f32_lc32, tab_f64_lc16, tab_f32_lc16, tab_f64_lc64, tab_f32_lc64;   // lazy
     std::unique_ptr<DeviceBuffer> tab_f64_lc64_unit;     // unit-b0 form (fill_tables)
+    std::unique_ptr<DeviceBuffer> ff_gain;               // zero-phase passes: the K + 1 cumulative DC gains (filtfilt_gains), lazy
     int unit_ok = -1;                    // the cascade has a unit-b0 form (lazy)
     std::vector<double> sos;
 };
@@ -970,7 +1073,17 @@ static void plan_segments(SosParams &p, int64_t plan_warm, int TILE, int residen
     p.nseg = (int)nseg; p.seg_len = seg_len; p.warm = warm;
 }
 
-template <typename TIn, typename TOut, typename TC, int LC, bool VEC, bool TAPS, bool PF, int MINW, bool SUMB = false, bool EPI = false, bool UNIT = false>
+// Zero-phase passes: the segmentation must not depend on an occupancy query, because tfx_sos_filtfilt_plan_info reports it
+// without a device.  The FF kernels run LC = 32 at two workgroups per CU (launch bounds; 72 KB of LDS each at K = 4) unless
+// the carry of a long cascade leaves room for one only.
+constexpr int FF_LC = 32;
+static size_t ff_shmem(int K)
+{
+    return 4 * (size_t)(sos_stage_bytes<double, double, double, FF_LC>() + sos_carry_bytes<double, FF_LC>(1, K));
+}
+static int ff_blocks_per_cu(int K) { return 2 * ff_shmem(K) <= 160 * 1024 ? 2 : 1; }
+
+template <typename TIn, typename TOut, typename TC, int LC, bool VEC, bool TAPS, bool PF, int MINW, bool SUMB = false, bool EPI = false, bool UNIT = false, int FF = 0, bool FFR = false>
 static void launch_one(SosParams p, int64_t plan_warm, hipStream_t stream)
 {
     constexpr int IOB = sizeof(TIn) > sizeof(TOut) ? sizeof(TIn) : sizeof(TOut);
@@ -979,7 +1092,7 @@ static void launch_one(SosParams p, int64_t plan_warm, hipStream_t stream)
     const int carry_b = (((nbl * p.K * 4 + 2 * LC) * (int)sizeof(TC)) + 15) & ~15;
     const size_t shmem = 4 * (size_t)(STAGE_B + carry_b);
     TFX_CHECK(shmem <= 160 * 1024, "sos_forward: %d band(s) x K=%d need %zu B of LDS (max 163840)", nbl, p.K, shmem);
-    auto kern = sos_stream_kernel<TIn, TOut, TC, LC, VEC, TAPS, PF, MINW, SUMB, EPI, UNIT>;
+    auto kern = sos_stream_kernel<TIn, TOut, TC, LC, VEC, TAPS, PF, MINW, SUMB, EPI, UNIT, FF, FFR>;
     if (!EPI) p.ep_stat = -1;                      // the plain instantiation has no epilogue code
     if (shmem > 64 * 1024)
         TFX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
@@ -988,7 +1101,17 @@ static void launch_one(SosParams p, int64_t plan_warm, hipStream_t stream)
     const int dev = current_device();
     int &blocks_per_cu = blocks_per_cu_tab[dev];
     size_t &blocks_shmem = blocks_shmem_tab[dev];
-    if (!blocks_per_cu || blocks_shmem != shmem) {
+    if constexpr (FF != 0) {
+        // the plan query's assumption, checked once per instance, device and LDS size against what the runtime can hold
+        if (!blocks_per_cu || blocks_shmem != shmem) {
+            int nb = 0;
+            TFX_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, 256, shmem) == hipSuccess &&
+                      nb >= ff_blocks_per_cu(p.K), "sos_filtfilt: %d workgroup(s) per CU fit, the segment plan counts on %d", nb,
+                      ff_blocks_per_cu(p.K));
+            blocks_shmem = shmem;
+        }
+        blocks_per_cu = ff_blocks_per_cu(p.K);
+    } else if (!blocks_per_cu || blocks_shmem != shmem) {
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, 256, shmem) != hipSuccess || nb < 1) nb = 1;
         blocks_per_cu = nb;
@@ -1007,13 +1130,20 @@ static void launch_one(SosParams p, int64_t plan_warm, hipStream_t stream)
     if (p.nseg > 1)                        // see sos_nonfinite_fix_kernel: every stream writes its slot, no memset needed
         p.nf_flag = (int *)scratch("sos_nf_flag", (size_t)nstreams * sizeof(int), stream);
     {
-        ProfScope ps(sizeof(TC) == 8 ? "sos_stream_kernel<f64>" : "sos_stream_kernel<f32>", stream);
+        ProfScope ps(FF == 1 ? "sos_filtfilt_forward_kernel" : FF == 2 ? "sos_filtfilt_reverse_kernel"
+                     : sizeof(TC) == 8 ? "sos_stream_kernel<f64>" : "sos_stream_kernel<f32>", stream);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shmem, stream, p);
         TFX_HIP(hipGetLastError());
     }
     if (p.nseg > 1) {                      // ~2 us on cfg 2 (measured by leaving it out)
-        hipLaunchKernelGGL(sos_nonfinite_fix_kernel<TOut>, dim3((unsigned)p.C), dim3(256), 0, stream, p, nbl, SUMB ? p.C_in * nbl : p.C);
-        TFX_HIP(hipGetLastError());
+        const auto fix = [&] {
+            hipLaunchKernelGGL(sos_nonfinite_fix_kernel<TOut>, dim3((unsigned)p.C), dim3(256), 0, stream, p, nbl, SUMB ? p.C_in * nbl : p.C);
+            TFX_HIP(hipGetLastError());
+        };
+        if constexpr (FF != 0) {           // the zero-phase profile names every launch of the call
+            ProfScope ps("sos_nonfinite_fix_kernel", stream);
+            fix();
+        } else fix();
     }
     if (p.ep_stat >= 0) {
         const Epilogue *ep = (const Epilogue *)p.ep_host;
@@ -1197,6 +1327,119 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in,
         else launch_rare<double, double, double>(p, vec, nstreams, stream);
     }
     if (ep->any() && !ep_fused) epilogue_as_passes(y, y_dtype, C, T, *ep, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// Zero-phase filtering, scipy.signal.sosfiltfilt along each row: the cascade runs forward over the edge-extended row and then
+// backward over its own output, each pass from the cascade's steady state for the first sample it sees, and the extension is
+// dropped.  Two launches of the cascade kernel (FF = 1, 2) around ONE float64 intermediate [C, T + 2 padlen]: the extension is
+// index arithmetic in the first pass's loads, the time reversal is the second pass's load and store addressing -- no padded,
+// flipped or widened copy of the signal exists.  24 B per sample of float32 signal (4 + 8 + 8 + 4).  Both passes are cut into
+// time segments exactly like the forward cascade (same warm-up bound, same repair of non-finite rows); in the reverse pass a
+// segment's halo lies at LATER samples of the row.
+// ------------------------------------------------------------------------------------------
+int64_t sos_filtfilt_default_padlen(const double *sos_host, int64_t K)
+{
+    int64_t zb = 0, za = 0;
+    for (int64_t s = 0; s < K; ++s) { zb += sos_host[s * 6 + 2] == 0.0; za += sos_host[s * 6 + 5] == 0.0; }
+    return 3 * (2 * K + 1 - (zb < za ? zb : za));
+}
+
+// G_(s-1) at [s], s = 0 ... K: the DC gain of the first s sections, prod sum(b_j) / sum(a_j).  A pole at z = 1 has none.
+static std::vector<double> filtfilt_gains(const double *sos_host, int64_t K)
+{
+    std::vector<double> g((size_t)K + 1);
+    ld acc = 1.0L;
+    g[0] = 1.0;
+    for (int64_t s = 0; s < K; ++s) {
+        const double *co = sos_host + s * 6;
+        const ld den = (ld)co[3] + (ld)co[4] + (ld)co[5];
+        TFX_CHECK(den != 0.0L, "sos_filtfilt: section %lld has a pole at z = 1: the cascade has no steady state to start from", (long long)s);
+        acc *= ((ld)co[0] + (ld)co[1] + (ld)co[2]) / den;
+        g[(size_t)s + 1] = (double)acc;
+    }
+    return g;
+}
+
+// the checks shared by the call and its plan query; returns the padlen in force
+static int64_t filtfilt_check(int64_t C, int64_t T, const double *sos_host, int64_t K, int padtype, int64_t padlen)
+{
+    TFX_CHECK(C >= 0 && T >= 0, "sos_filtfilt: negative size");
+    TFX_CHECK(sos_host && K >= 1 && K <= 512, "sos_filtfilt: null coefficients or bad section count %lld (1 ... 512)", (long long)K);
+    TFX_CHECK(padtype >= TFX_PAD_ODD && padtype <= TFX_PAD_NONE, "sos_filtfilt: bad padtype %d", padtype);
+    TFX_CHECK(padlen >= -1, "sos_filtfilt: negative padlen %lld (-1 = the default)", (long long)padlen);
+    for (int64_t i = 0; i < K * 6; ++i) TFX_CHECK(std::isfinite(sos_host[i]), "sos_filtfilt: non-finite SOS coefficient");
+    for (int64_t s = 0; s < K; ++s) TFX_CHECK(sos_host[s * 6 + 3] == 1.0, "sos_filtfilt: sos[%lld, 3] (a0) must be 1", (long long)s);
+    int64_t pad = padlen < 0 ? sos_filtfilt_default_padlen(sos_host, K) : padlen;
+    if (padtype == TFX_PAD_NONE) pad = 0;
+    TFX_CHECK(T > pad, "The length of the input vector x must be greater than padlen, which is %lld.", (long long)pad);
+    TFX_CHECK(T <= (INT64_MAX / 64 - 2 * pad) / (C > 0 ? C : 1), "sos_filtfilt: size overflows");
+    return pad;
+}
+
+static SosParams filtfilt_params(int pass, int64_t C, int64_t T, int64_t K, int padtype, int64_t pad)
+{
+    SosParams p{};
+    p.C = C; p.C_in = C; p.T = T + 2 * pad; p.K = (int)K;
+    p.x_pitch = pass == 1 ? T : p.T;
+    p.fair = 15;
+    p.ep_stat = -1;
+    p.ff = pass; p.ff_padtype = padtype; p.ff_T = T; p.ff_pad = pad;
+    return p;
+}
+
+void sos_filtfilt_plan_info(int64_t C, int64_t T, const double *sos_host, int64_t K, int padtype, int64_t padlen,
+                            int64_t *default_padlen, int64_t *padlen_used, int64_t *work_elems, int64_t *warmup,
+                            int *nseg_forward, int *nseg_reverse)
+{
+    const int64_t pad = filtfilt_check(C, T, sos_host, K, padtype, padlen);
+    (void)filtfilt_gains(sos_host, K);
+    const std::shared_ptr<SosPlan> plan = get_plan(sos_host, K, nullptr, 1);
+    SosParams p = filtfilt_params(1, C > 0 ? C : 1, T, K, padtype, pad);
+    plan_segments(p, plan->warm, 64 * FF_LC, ff_blocks_per_cu((int)K) * 4);      // both passes walk rows of T + 2 pad samples
+    if (default_padlen) *default_padlen = sos_filtfilt_default_padlen(sos_host, K);
+    if (padlen_used) *padlen_used = pad;
+    if (work_elems) *work_elems = C * (T + 2 * pad);
+    if (warmup) *warmup = plan->warm;
+    if (nseg_forward) *nseg_forward = p.nseg;
+    if (nseg_reverse) *nseg_reverse = p.nseg;
+}
+
+template <typename TIn, typename TOut, int FF, bool FFR>
+static void filtfilt_launch(const SosParams &p, int64_t plan_warm, hipStream_t stream)
+{
+    launch_one<TIn, TOut, double, FF_LC, false, false, false, 2, false, false, false, FF, FFR>(p, plan_warm, stream);
+}
+
+void sos_filtfilt_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C, int64_t T, const double *sos_host, int64_t K,
+                          int padtype, int64_t padlen, double *work, hipStream_t stream)
+{
+    TFX_CHECK(x_dtype == TFX_F32 || x_dtype == TFX_F64, "sos_filtfilt: bad x dtype %d", x_dtype);
+    TFX_CHECK(y_dtype == TFX_F32 || y_dtype == TFX_F64, "sos_filtfilt: bad y dtype %d", y_dtype);
+    const int64_t pad = filtfilt_check(C, T, sos_host, K, padtype, padlen);
+    const std::vector<double> gains = filtfilt_gains(sos_host, K);
+    if (C == 0) return;
+    TFX_CHECK(x && y && work, "sos_filtfilt: null signal, result or workspace pointer");
+
+    const std::shared_ptr<SosPlan> plan = get_plan(sos_host, K, stream, 1);      // held until the launches are enqueued
+    SosPlan *pl = plan.get();
+    const void *tab = ensure_table<double>(pl, &pl->tab_f64_lc32, FF_LC, &pl->nsteps32, stream);
+    {
+        std::lock_guard<std::mutex> lk(g_plan_mu);
+        if (!pl->ff_gain) pl->ff_gain = std::make_unique<DeviceBuffer>(gains);
+    }
+    SosParams p = filtfilt_params(1, C, T, K, padtype, pad);
+    p.tab = tab; p.nsteps = pl->nsteps32; p.ff_gain = (const double *)pl->ff_gain->p;
+    p.x = x; p.y = work;
+    // a float64 result takes the refined start states in both passes; a float32 result is 20 times inside its bar without
+    const bool refine = y_dtype == TFX_F64;
+    if (x_dtype == TFX_F32 && !refine) filtfilt_launch<float, double, 1, false>(p, pl->warm, stream);
+    else if (x_dtype == TFX_F32) filtfilt_launch<float, double, 1, true>(p, pl->warm, stream);
+    else if (!refine) filtfilt_launch<double, double, 1, false>(p, pl->warm, stream);
+    else filtfilt_launch<double, double, 1, true>(p, pl->warm, stream);
+    p.ff = 2; p.x = work; p.y = y; p.x_pitch = p.T;
+    if (y_dtype == TFX_F32) filtfilt_launch<double, float, 2, false>(p, pl->warm, stream);
+    else filtfilt_launch<double, double, 2, true>(p, pl->warm, stream);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@ from torchfx_amd.filter.iir import (
     LoChebyshev1, LoChebyshev2, LoElliptic, LoLinkwitzRiley, LoShelving, Notch, ParametricEQ,
     Peaking, Shelving,
 )
+from torchfx_amd.filter.zerophase import ZeroPhase
 
 __all__ = [
     "AbstractFilter", "ParallelFilterCombination",
@@ -21,5 +22,5 @@ __all__ = [
     "FusedSOSCascade", "HiButterworth", "HiChebyshev1", "HiChebyshev2", "HiElliptic",
     "HiLinkwitzRiley", "HiShelving", "IIR", "LinkwitzRiley", "LoButterworth", "LoChebyshev1",
     "LoChebyshev2", "LoElliptic", "LoLinkwitzRiley", "LoShelving", "LogFilterBank", "Notch", "ParametricEQ",
-    "Peaking", "Shelving",
+    "Peaking", "Shelving", "ZeroPhase",
 ]

@@ -363,6 +363,15 @@ def _has_stateful_resample(e) -> bool:
     return any(isinstance(m, StatefulResample) for m in (e.modules() if isinstance(e, nn.Module) else [e]))
 
 
+def _refuse_zero_phase(e, who: str) -> None:
+    from torchfx_amd.filter.zerophase import ZeroPhase
+
+    if any(isinstance(m, ZeroPhase) for m in (e.modules() if isinstance(e, nn.Module) else [e])):
+        raise TypeError(f"ZeroPhase cannot run in {who}: zero-phase filtering is non-causal -- its backward pass starts at the "
+                        "end of the signal, which a chunked stream has not seen yet; filter the whole signal "
+                        "(wave | ZeroPhase(...) or sosfiltfilt) before or after streaming")
+
+
 class _ChunkRun:
     """``IIR ... | StatefulFIR | Gain`` (any non-empty sub-pattern of at least two effects) as ONE launch per small chunk
     (``torchfx_ext.chunk_forward``): the chain of a 2 x 512 block is launch-bound, not arithmetic-bound.  Consecutive
@@ -500,6 +509,7 @@ class StreamProcessor:
         for e in self._effects:
             if not isinstance(e, FX):
                 raise TypeError("All effects must inherit from FX when used in StreamProcessor")
+            _refuse_zero_phase(e, "StreamProcessor")
             if not isinstance(e, StatefulResample) and any(isinstance(m, Resample) for m in e.modules()):
                 raise TypeError("Resample cannot run in StreamProcessor: resampling each chunk on its own leaves a seam at "
                                 "every chunk boundary; use StatefulResample as a top-level effect of the chain, or resample "
@@ -810,6 +820,7 @@ class RealtimeProcessor:
         for e in modules:
             if not isinstance(e, FX):
                 raise TypeError("All effects must inherit from FX when used in RealtimeProcessor")
+            _refuse_zero_phase(e, "RealtimeProcessor")
             if _has_stateful_resample(e):
                 raise TypeError("StatefulResample cannot run in RealtimeProcessor: a sound card's output block has the input "
                                 "block's length and sample rate; resample with StreamProcessor or Wave.resample instead")

@@ -34,7 +34,7 @@ from torchfx_amd import native
 __all__ = [
     "biquad_forward", "sos_forward", "sos_bank_forward", "sos_bank_sum_forward", "delay_line_forward", "delay_forward",
     "delay_amplitudes", "delay_regime", "delay_stream_forward", "delay_line_stream_forward", "resample_forward",
-    "resample_plan_info", "resample_stream_forward", "resample_stream_plan_info",
+    "resample_plan_info", "resample_stream_forward", "resample_stream_plan_info", "sos_filtfilt", "sos_filtfilt_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
 ]
@@ -198,6 +198,40 @@ def resample_stream_forward(x: Tensor, h: Tensor, hist: Tensor | None, up: int, 
     with ``M(N) = max(0, ceil(N * up / down) - n_pre_remove)``: the outputs of :func:`resample_forward` on the whole signal
     that these inputs complete (``tfx_resample_stream_forward``)."""
     return native.ops().resample_stream_forward(x.contiguous(), h, hist, int(up), int(down), int(consumed))
+
+
+PADTYPES = {"odd": 0, "even": 1, "constant": 2, None: 3}           # enum tfx_padtype
+
+
+def sos_array(sos) -> np.ndarray:
+    """``sos`` (tensor / array / nested list) as a host float64 ``[K, 6]`` array."""
+    a = sos.detach().cpu().numpy() if isinstance(sos, Tensor) else np.asarray(sos)
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 6:
+        raise ValueError(f"sos array must be shape (n_sections, 6), got {a.shape}")
+    return a
+
+
+def sos_filtfilt(x: Tensor, sos, padtype="odd", padlen: int | None = None) -> Tensor:
+    """``scipy.signal.sosfiltfilt(sos, x, axis=-1, padtype=padtype, padlen=padlen)`` on a device tensor ``x [..., T]``
+    (float32 / float64; the result has its dtype): two cascade launches around one float64 intermediate
+    (``tfx_sos_filtfilt_forward``).  ``sos [K,6]`` on the host; ``padlen`` None = SciPy's default."""
+    return native.ops().sos_filtfilt(x.contiguous(), _coeff(sos), PADTYPES[padtype], -1 if padlen is None else int(padlen))
+
+
+def sos_filtfilt_plan_info(sos, rows: int, length: int, padtype="odd", padlen: int | None = None) -> dict:
+    """What :func:`sos_filtfilt` does for ``rows`` rows of ``length`` samples (``tfx_sos_filtfilt_plan_info``; host-only, same
+    argument checks): ``default_padlen`` (SciPy's), ``padlen`` in force, ``work_elems`` (float64 elements of the
+    intermediate), ``warmup`` (halo of a time segment, -1 = one segment per row) and the segments per row of the two passes,
+    ``nseg_forward`` / ``nseg_reverse``."""
+    a = sos_array(sos)
+    o = [ctypes.c_int64(0) for _ in range(4)]
+    nf, nr = ctypes.c_int(0), ctypes.c_int(0)
+    L.check(L.load().tfx_sos_filtfilt_plan_info(int(rows), int(length), a.ctypes.data, a.shape[0], PADTYPES[padtype],
+                                                -1 if padlen is None else int(padlen), *[ctypes.byref(v) for v in o],
+                                                ctypes.byref(nf), ctypes.byref(nr)))
+    return {"default_padlen": o[0].value, "padlen": o[1].value, "work_elems": o[2].value, "warmup": o[3].value,
+            "nseg_forward": nf.value, "nseg_reverse": nr.value}
 
 
 RESAMPLE_STREAM_KERNELS = ("resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel", "copy")

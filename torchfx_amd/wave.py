@@ -211,6 +211,7 @@ def plan_cache_clear() -> None:
 
 def _member_key(m: nn.Module, guard: list) -> tuple:
     from torchfx_amd.effect import Delay, Gain, Normalize
+    from torchfx_amd.filter.zerophase import ZeroPhase
     from torchfx_amd.resample import Resample, window_key
 
     guard.append(m)
@@ -233,6 +234,8 @@ def _member_key(m: nn.Module, guard: list) -> tuple:
         k += (m.delay_samples, m.taps, m.feedback, m.mix, type(m.strategy), getattr(m, "fs", None))
     elif isinstance(m, Resample):
         k += (m.new_fs, m.fs, window_key(m.window))
+    elif isinstance(m, ZeroPhase):
+        k += (m.padtype, m.padlen)
     return k
 
 
@@ -321,17 +324,20 @@ class Wave:
 
     def _build_plan(self, length: int, dtype: torch.dtype = torch.float32) -> list[nn.Module]:
         """A ``Resample`` is a barrier: the steps between two of them are planned on their own, at the row length they see,
-        and nothing merges, folds or attaches an epilogue across one."""
+        and nothing merges, folds or attaches an epilogue across one.  So is a ``ZeroPhase`` (its two passes are one step;
+        the row length stays)."""
+        from torchfx_amd.filter.zerophase import ZeroPhase
         from torchfx_amd.resample import Resample
 
         plan: list[nn.Module] = []
         segment: list[nn.Module] = []
         for m in self._pipeline:
-            if isinstance(m, Resample):
+            if isinstance(m, (Resample, ZeroPhase)):
                 plan += self._build_segment(segment, length, dtype)
                 plan.append(m)
                 segment = []
-                length = m.output_length(length)
+                if isinstance(m, Resample):
+                    length = m.output_length(length)
             else:
                 segment.append(m)
         return plan + self._build_segment(segment, length, dtype)
@@ -561,6 +567,7 @@ class Wave:
         recursion-in-pass-A pipeline or the staged pair of launches) and why."""
         from torchfx_amd.effect import Delay, Epilogued
         from torchfx_amd.filter.fused import CascadeFIR, FusedSOSCascade
+        from torchfx_amd.filter.zerophase import ZeroPhase
         from torchfx_amd.realtime import StatefulDelay, _native_stream
         from torchfx_amd.resample import Resample
 
@@ -585,6 +592,8 @@ class Wave:
             elif isinstance(inner, Resample):
                 line += ": " + inner.route(self._ys, length)
                 length = inner.output_length(length)
+            elif isinstance(inner, ZeroPhase):
+                line += ": " + inner.route(self._ys, length)
             lines.append(line)
         return lines
 
