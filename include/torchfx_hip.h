@@ -150,6 +150,29 @@ int tfx_sos_filtfilt_plan_info(int64_t C, int64_t T, const double *sos_host, int
                                int *nseg_forward, int *nseg_reverse);
 
 /* ---------------------------------------------------------------------------
+ * tfx_sos_block_energy_forward -- the cascade and the energy of its output per block of samples in ONE launch; the
+ * filtered signal is never stored.  With y = the float64 DF1 cascade of row r from zero state,
+ *   s[r, i] = sum of y[r, n]^2 over n in [e_i, e_(i+1)),   e_i = (i * num) / den (integer division),
+ * for i < nblk = (T * den) / num; samples from e_nblk on belong to no block.  The measurement under a BS.1770 loudness
+ * meter (K-weighting, num / den = fs / 10); the reference has no counterpart.  Deterministic: every s[r, i] has one
+ * writer, and how a row is cut into time segments depends on T, the cascade and num / den alone, so a row's result
+ * does not depend on the other rows.  A NaN / Inf sample makes its block and every later block of its row non-finite.
+ *   x        DEVICE [C,T] of x_dtype (float32 or float64);  s DEVICE float64 [C, nblk] (written)
+ *   sos_host HOST   [K,6] float64, a0 = 1
+ *   num, den >= 1 with num >= 64 * den (blocks of at least 64 samples)
+ * ------------------------------------------------------------------------- */
+int tfx_sos_block_energy_forward(const void *x, int x_dtype, double *s,
+                                 int64_t C, int64_t T,
+                                 const double *sos_host, int64_t K,
+                                 int64_t num, int64_t den, tfx_stream_t stream);
+/* What tfx_sos_block_energy_forward does for [C,T] rows (host-only; same argument checks): the blocks per row, the time
+ * segments per row and the warm-up halo of a segment (0 with one segment).  A cascade that does not decay
+ * (tfx_sos_plan_info: warmup -1) runs one segment per row and is refused for rows above 2^24 samples.  Any output may
+ * be NULL. */
+int tfx_sos_block_energy_plan_info(int64_t C, int64_t T, const double *sos_host, int64_t K, int64_t num, int64_t den,
+                                   int64_t *nblk, int *nseg, int64_t *warm);
+
+/* ---------------------------------------------------------------------------
  * tfx_biquad_forward -- single DF1 biquad.
  * Replaces  torchfx_ext.biquad_forward(x, b, a1, a2, state_x, state_y)
  *           binding.cpp:30-50,84-87 -> biquad_forward_cpu iir_cpu.cpp:10-62 /

@@ -39,6 +39,9 @@ SIGNATURES = {
     "tfx_sos_filtfilt_forward": (_int, [_vp, _int, _vp, _int, _i64, _i64, _vp, _i64, _int, _i64, _vp, _vp]),
     "tfx_sos_filtfilt_plan_info": (_int, [_i64, _i64, _vp, _i64, _int, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                           ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tfx_sos_block_energy_forward": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
+    "tfx_sos_block_energy_plan_info": (_int, [_i64, _i64, _vp, _i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_int),
+                                              ctypes.POINTER(_i64)]),
     "tfx_biquad_forward": (_int, [_vp, _int, _vp, _int, _i64, _i64, _vp, _dbl, _dbl, _vp, _vp, _vp, _vp, _int, _vp]),
     "tfx_fir_direct_forward": (_int, [_vp, _vp, _int, _i64, _i64, _vp, _i64, _vp]),
     "tfx_fft_conv_forward": (_int, [_vp, _vp, _int, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),

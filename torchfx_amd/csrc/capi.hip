@@ -25,6 +25,10 @@ void sos_filtfilt_forward(const void *x, int x_dtype, void *y, int y_dtype, int6
 void sos_filtfilt_plan_info(int64_t C, int64_t T, const double *sos_host, int64_t K, int padtype, int64_t padlen,
                             int64_t *default_padlen, int64_t *padlen_used, int64_t *work_elems, int64_t *warmup,
                             int *nseg_forward, int *nseg_reverse);
+void sos_block_energy_forward(const void *x, int x_dtype, double *s, int64_t C, int64_t T, const double *sos_host, int64_t K,
+                              int64_t num, int64_t den, hipStream_t stream);
+void sos_block_energy_plan_info(int64_t C, int64_t T, const double *sos_host, int64_t K, int64_t num, int64_t den,
+                                int64_t *nblk, int *nseg, int64_t *warm);
 void sos_clear_plans();
 void fir_direct_forward(const void *x, void *y, int dtype, int64_t C, int64_t T,
                         const void *kernel_host, int64_t K, hipStream_t stream, const void *hist = nullptr, int64_t H = 0);
@@ -446,6 +450,22 @@ int tfx_sos_filtfilt_plan_info(int64_t C, int64_t T, const double *sos_host, int
 {
     TFX_API_BEGIN
     sos_filtfilt_plan_info(C, T, sos_host, K, padtype, padlen, default_padlen, padlen_used, work_elems, warmup, nseg_forward, nseg_reverse);
+    TFX_API_END
+}
+
+int tfx_sos_block_energy_forward(const void *x, int x_dtype, double *s, int64_t C, int64_t T, const double *sos_host, int64_t K,
+                                 int64_t num, int64_t den, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    sos_block_energy_forward(x, x_dtype, s, C, T, sos_host, K, num, den, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_sos_block_energy_plan_info(int64_t C, int64_t T, const double *sos_host, int64_t K, int64_t num, int64_t den,
+                                   int64_t *nblk, int *nseg, int64_t *warm)
+{
+    TFX_API_BEGIN
+    sos_block_energy_plan_info(C, T, sos_host, K, num, den, nblk, nseg, warm);
     TFX_API_END
 }
 

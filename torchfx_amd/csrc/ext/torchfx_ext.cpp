@@ -436,6 +436,40 @@ Tensor sos_filtfilt_op(const Tensor &x_in, const Tensor &sos_cpu, int64_t padtyp
     return y;
 }
 
+// The cascade and the energy of its output per block of samples (tfx_sos_block_energy_forward): x [..., T] -> float64 [..., nblk],
+// leading dimensions flattened into rows; sos HOST [K, 6]; blocks [(i num) / den, ((i + 1) num) / den), nblk = (T den) / num
+std::vector<int64_t> sos_block_energy_shape(const Tensor &x, const Tensor &sos, int64_t num, int64_t den)
+{
+    TORCH_CHECK(x.dim() >= 1, "sos_block_energy: x must have a time dimension");
+    TORCH_CHECK(sos.dim() == 2 && sos.size(1) == 6, "sos_block_energy: sos must be [K, 6]");
+    TORCH_CHECK(num >= 1 && den >= 1 && num / 64 >= den, "sos_block_energy: blocks of num / den = ", num, " / ", den,
+                " samples are shorter than 64");
+    std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
+    TORCH_CHECK(shape.back() <= (int64_t(1) << 61) / den, "sos_block_energy: T * den overflows");
+    shape.back() = shape.back() * den / num;
+    return shape;
+}
+
+Tensor sos_block_energy_op(const Tensor &x_in, const Tensor &sos_cpu, int64_t num, int64_t den)
+{
+    need_device(x_in, "x");
+    const Tensor sos = host_f64(sos_cpu, 6, "sos_block_energy");
+    const std::vector<int64_t> shape = sos_block_energy_shape(x_in, sos, num, den);
+    const Tensor x = x_in.contiguous();
+    const int64_t T = x.size(-1), rows = stream_rows(x), K = sos.size(0);
+    const int dt = dtype_code(x, "sos_block_energy");
+    int64_t nblk = 0;
+    check_rc(tfx_sos_block_energy_plan_info(rows, T, sos.data_ptr<double>(), K, num, den, &nblk, nullptr, nullptr), "sos_block_energy");
+    TORCH_CHECK(nblk == shape.back(), "sos_block_energy: the library plans ", nblk, " blocks, the shape has ", shape.back());
+    Tensor s = at::empty(shape, x.options().dtype(at::kDouble));
+    if (s.numel() == 0) return s;
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_sos_block_energy_forward(x.data_ptr(), dt, s.data_ptr<double>(), rows, T, sos.data_ptr<double>(), K, num, den,
+                                          stream_of(x)),
+             "sos_block_energy");
+    return s;
+}
+
 // One chunk of a resampling stream (tfx_resample_stream_forward): x [..., T] after `consumed` samples per row, h as for
 // resample_forward, hist [rows, H] (None = silence) -> (y [..., M(consumed + T) - M(consumed)], new history [rows, H])
 struct ResampleStreamPlan {
@@ -840,6 +874,7 @@ TORCH_LIBRARY(torchfx_hip, m)
     m.def("delay_forward(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong) -> Tensor");
     m.def("resample_forward(Tensor x, int up, int down, Tensor h) -> Tensor");
     m.def("sos_filtfilt(Tensor x, Tensor sos_cpu, int padtype=0, int padlen=-1) -> Tensor");
+    m.def("sos_block_energy(Tensor x, Tensor sos_cpu, int num, int den=1) -> Tensor");
     m.def("resample_stream_forward(Tensor x, Tensor h, Tensor? hist, int up, int down, int consumed) -> (Tensor, Tensor)");
     m.def("delay_forward_ep(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong, float gain, bool clamp, int stat_mode, "
           "bool per_row) -> (Tensor, Tensor)");
@@ -878,6 +913,7 @@ TORCH_LIBRARY_IMPL(torchfx_hip, CUDA, m)          // "CUDA" is the dispatch key 
     m.impl("delay_forward", delay_op);
     m.impl("resample_forward", resample_op);
     m.impl("sos_filtfilt", sos_filtfilt_op);
+    m.impl("sos_block_energy", sos_block_energy_op);
     m.impl("resample_stream_forward", resample_stream_op);
     m.impl("delay_forward_ep", delay_ep_op);
     m.impl("delay_stream_forward", delay_stream_op);
@@ -912,6 +948,9 @@ TORCH_LIBRARY_IMPL(torchfx_hip, Meta, m)
     m.impl("delay_forward", delay_meta);
     m.impl("resample_forward", resample_meta);
     m.impl("sos_filtfilt", [](const Tensor &x, const Tensor &, int64_t, int64_t) { return at::empty_like(x); });
+    m.impl("sos_block_energy", [](const Tensor &x, const Tensor &sos, int64_t num, int64_t den) {
+        return at::empty(sos_block_energy_shape(x, sos, num, den), x.options().dtype(at::kDouble));
+    });
     m.impl("resample_stream_forward", resample_stream_meta);
     m.impl("delay_forward_ep", delay_ep_meta);
     m.impl("delay_stream_forward", delay_stream_meta);
@@ -933,7 +972,7 @@ static void no_cpu_boxed(const c10::OperatorHandle &op, c10::DispatchKeySet, tor
 TORCH_LIBRARY_IMPL(torchfx_hip, CPU, m)
 {
     for (const char *name : {"sos_forward", "sos_forward_sections", "sos_bank_forward", "sos_bank_sum_forward", "biquad_forward",
-                             "delay_line_forward", "delay_forward", "delay_forward_ep", "delay_stream_forward", "delay_line_stream_forward", "resample_forward", "sos_filtfilt", "resample_stream_forward", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
+                             "delay_line_forward", "delay_forward", "delay_forward_ep", "delay_stream_forward", "delay_line_stream_forward", "resample_forward", "sos_filtfilt", "sos_block_energy", "resample_stream_forward", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
                              "fft_conv_forward_ep", "sos_fft_conv_forward", "normalize_apply", "sum_forward", "gain_forward", "quantile_abs", "stat_forward",
                              "normalize_forward", "deinterleave_forward", "deinterleave_into", "interleave_forward"})
         m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());

@@ -88,6 +88,9 @@ struct SosParams {
     int64_t ff_T;        // samples per row of the signal itself
     int64_t ff_pad;      // samples the row is extended by at each end
     const double *ff_gain;   // device [K + 1]: G_(s-1) at [s], the DC gain of the sections in front of section s (G_(-1) = 1)
+    // measuring pass (MEAS kernels, sos_block_energy_forward): y is the float64 [C, ms_nblk] array of block energies; block i
+    // holds the samples [e_i, e_(i+1)), e_i = (i * ms_num) / ms_den, and segment g owns the blocks [g * ms_bps, (g + 1) * ms_bps)
+    int64_t ms_num, ms_den, ms_nblk, ms_bps;
 };
 
 // Sample i of the row x[0 .. T) extended by `pad` samples at each end (scipy.signal's odd_ext / even_ext / const_ext), i counted
@@ -167,15 +170,20 @@ template <typename T> struct U16 {               // 16 bytes of T
 //      the row's first sample (scipy.signal.sosfilt_zi * x[0]).  Scalar (!VEC) path only; FF = 0 compiles to the code
 //      it was before
 // FFR  the zero-phase passes of a float64 result refine the scan's start states once (see the scan below)
+// MEAS measuring pass (SosParams::ms_*): the cascade's output is not stored; the stream keeps the sum of its squares over each
+//      block of samples it owns.  Segments start on block edges (their halo in front), so every block has one writer.  Scalar
+//      (!VEC) path only, TOut = TIn (the stage holds the input alone); MEAS = false compiles to the code it was before
 // The stream body: one wavefront walks stream `sid` = (row, segment) with `stage` as its private LDS (transposition
 // stage + carry).  Shared by the cascade kernel below and by the fused per-chunk kernel (chunk_iir_fir_kernel), whose
 // output pointer is an LDS buffer.
-template <typename TIn, typename TOut, typename TC, int LC, bool VEC, bool TAPS, bool PF, bool SUMB, bool EPI, bool UNIT = false, int FF = 0, bool FFR = false>
+template <typename TIn, typename TOut, typename TC, int LC, bool VEC, bool TAPS, bool PF, bool SUMB, bool EPI, bool UNIT = false, int FF = 0, bool FFR = false, bool MEAS = false>
 __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_t sid, char *const stage, const int lane)
 {
     static_assert(!(TAPS && SUMB), "section taps are not available in sum mode");
     static_assert(!(UNIT && (TAPS || SUMB)), "the unit-b0 form serves the plain cascade only");
     static_assert(FF == 0 || !(VEC || TAPS || PF || SUMB || EPI || UNIT), "the zero-phase passes run the plain scalar path");
+    static_assert(!MEAS || !(VEC || TAPS || PF || SUMB || EPI || UNIT || FF != 0), "the measuring pass runs the plain scalar path");
+    static_assert(!MEAS || (std::is_same<TC, double>::value && LC <= 64), "block energies: float64 sums, at most one block edge per lane");
     // what the LDS stage holds on the way in: the odd extension 2 x[0] - x[i] of a float32 row is not a float32 value
     typedef typename std::conditional<FF == 1, TC, TIn>::type TSt;
     constexpr int IOB = sizeof(TIn) > sizeof(TOut) ? sizeof(TIn) : sizeof(TOut);
@@ -216,15 +224,23 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
 
     // stream g reads [g * seg_len, (g + 1) * seg_len + warm): exactly seg_tiles full tiles for every stream, the
     // first `warm` samples of a stream g > 0 being its halo (plan_segments)
-    const int64_t start = (int64_t)g * p.seg_len;
-    const int64_t out_begin = g ? start + p.warm : 0;
+    int64_t start = (int64_t)g * p.seg_len;
+    int64_t out_begin = g ? start + p.warm : 0;
+    int64_t ms_kb = 0, ms_ke = 0;                          // measuring pass: this stream owns the blocks [ms_kb, ms_ke)
+    if constexpr (MEAS) {
+        ms_kb = (int64_t)g * p.ms_bps;
+        ms_ke = ms_kb + p.ms_bps < p.ms_nblk ? ms_kb + p.ms_bps : p.ms_nblk;
+        out_begin = ms_kb * p.ms_num / p.ms_den;           // e_kb >= warm for g > 0 (block_energy_plan)
+        start = g ? out_begin - p.warm : 0;
+    }
     if (out_begin >= T) {
         if (p.nf_flag && lane == 0) p.nf_flag[sid] = 0;
         return;
     }
     int64_t out_end = start + p.seg_len + p.warm;
     if (out_end > T || g == p.nseg - 1) out_end = T;
-    const bool last_seg = (out_end == T);
+    if constexpr (MEAS) out_end = ms_ke * p.ms_num / p.ms_den;      // e_ke <= T: samples from e_nblk on belong to no block
+    const bool last_seg = !MEAS && (out_end == T);         // (the measuring pass returns no state)
 
     // ---- initial carry: the caller's state for the stream that starts at n = 0, zeros for a
     //      warm-up start.  Layout of state tensors: [K, C, 2] (iir_cpu.cpp:125-130).
@@ -311,6 +327,8 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
 
     if constexpr (PF) load_tile(start);
     double ep_acc = 0.0;                   // this lane's share of the stream's statistic (0 is neutral for both modes)
+    double ms_carry = 0.0;                 // measuring pass: the sum so far of the block that is open at the tile's first sample
+    int ms_bad = 0;                        // ... and whether this lane has written a non-finite block
 
     for (int64_t ts = start; ts < out_end; ts += TILE) {
         TC d[LC];
@@ -527,8 +545,66 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
         }
 
 
+        // ---- measuring pass: nothing is stored but the energy of the blocks that end in this tile
+        if constexpr (MEAS) {
+            if (ts + TILE > out_begin) {
+                // Sample n lies in block floor(((n + 1) den - 1) / num).  For this lane's chunk [a, a + LC): qm = the block of
+                // sample a - 1 (-1 in front of the row), rm the remainder of that division; sample a + k is in block
+                // qm + floor((rm + (k + 1) den) / num), so the chunk's only edge (blocks are at least 64 >= LC samples long) is
+                // at k = ke = floor((num - rm - 1) / den), if that is below LC.  The two quotients come from a float64
+                // estimate corrected by one step of integer arithmetic (T den < 2^61: the estimate is off by at most one).
+                const int64_t w = (ts + (int64_t)lane * LC) * p.ms_den - 1;
+                int64_t qm = (int64_t)floor((double)w / (double)p.ms_num);
+                int64_t rm = w - qm * p.ms_num;
+                if (rm < 0) { qm -= 1; rm += p.ms_num; }
+                else if (rm >= p.ms_num) { qm += 1; rm -= p.ms_num; }
+                const int64_t gap = p.ms_num - rm - 1;
+                int ke = LC;
+                if (gap < (int64_t)LC * p.ms_den) {
+                    ke = (int)((double)gap / (double)p.ms_den);
+                    if ((int64_t)ke * p.ms_den > gap) --ke;
+                    else if ((int64_t)(ke + 1) * p.ms_den <= gap) ++ke;
+                }
+                const bool edge = ke < LC;
+                // this lane's samples in sequence: sa belongs to the block open at its first sample, sb to the one that starts at ke
+                TC sa = (TC)0, sb = (TC)0;
+#pragma unroll
+                for (int n = 0; n < LC; ++n) sa = fma(d[n], d[n], sa);
+                if (edge) {                        // rare: one lane in num / den / LC
+                    sa = (TC)0;
+#pragma unroll
+                    for (int n = 0; n < LC; ++n) {
+                        const TC t = d[n] * d[n];
+                        if (n < ke) sa += t; else sb += t;
+                    }
+                }
+                // segmented inclusive scan over the lanes (Kogge-Stone, fixed tree): v = the open block's sum at the END of the
+                // lane's chunk, counted from the last edge at or before it -- or, with no edge yet (f = 0), from the tile's start
+                TC v = edge ? sb : sa;
+                int f = edge ? 1 : 0;
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {
+                    const TC vp = __shfl_up(v, off);
+                    const int fp = __shfl_up(f, off);
+                    if (lane >= off) {
+                        if (!f) v = vp + v;
+                        f |= fp;
+                    }
+                }
+                if (!f) v = ms_carry + v;
+                TC before = __shfl_up(v, 1);       // the open block's sum in front of this lane's chunk
+                if (lane == 0) before = ms_carry;
+                if (edge && qm >= ms_kb && qm < ms_ke) {       // block qm ends inside this chunk: its one writer
+                    const TC tot = before + sa;
+                    ((double *)p.y)[c * p.ms_nblk + qm] = tot;
+                    ms_bad |= !(fabs(tot) <= 1.79e308);
+                }
+                ms_carry = __shfl(v, 63);
+            }
+        }
+
         // ---- store (skipped entirely while still inside the warm-up halo)
-        if (ts + TILE > out_begin) {
+        if (!MEAS && ts + TILE > out_begin) {
             const int64_t lo64 = out_begin - ts, hi64 = out_end - ts;
             const bool full = (lo64 <= 0) && (hi64 >= TILE);
             if constexpr (UNIT) {                       // the product of all b0, once, on the way out
@@ -611,6 +687,19 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
             wave_sync();
         }
     }
+    if constexpr (MEAS) {
+        // the stream's last block ends with its last tile when e_ke is a multiple of the tile away from `start`: no lane saw that edge
+        if (lane == 0 && (out_end - start) % TILE == 0) {
+            ((double *)p.y)[c * p.ms_nblk + ms_ke - 1] = ms_carry;
+            ms_bad |= !(fabs(ms_carry) <= 1.79e308);
+        }
+        // a non-finite block = a non-finite output sample of the cascade among the stream's own: the recursion keeps it to the end
+        // of the row, which the segments after this one cannot know (sos_block_energy_fix_kernel).  Not the carried state: the last
+        // tile runs on into the next segment's samples.
+        const int anyb = __any(ms_bad) ? 1 : 0;
+        if (p.nf_flag && lane == 0) p.nf_flag[sid] = anyb;
+        return;
+    }
     if (p.nf_flag) {
         // the carried state at the end of the stream (every band, every section: last two inputs and outputs);
         // non-finite there = non-finite from some sample of this stream to the end of the row (iir_cpu.cpp:132-147),
@@ -638,14 +727,14 @@ template <typename TC, int LC> __host__ __device__ inline int sos_carry_bytes(in
     return (((nbl * K * 4 + 2 * LC) * (int)sizeof(TC)) + 15) & ~15;
 }
 
-template <typename TIn, typename TOut, typename TC, int LC, bool VEC, bool TAPS, bool PF, int MINW, bool SUMB = false, bool EPI = false, bool UNIT = false, int FF = 0, bool FFR = false>
+template <typename TIn, typename TOut, typename TC, int LC, bool VEC, bool TAPS, bool PF, int MINW, bool SUMB = false, bool EPI = false, bool UNIT = false, int FF = 0, bool FFR = false, bool MEAS = false>
 __global__ void __launch_bounds__(256, MINW) sos_stream_kernel(const SosParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // provably wave-uniform -> SGPR addressing
     const int per_wave = sos_stage_bytes<TIn, TOut, TC, LC>() + sos_carry_bytes<TC, LC>(SUMB ? p.nsum : 1, p.K);
-    sos_stream_body<TIn, TOut, TC, LC, VEC, TAPS, PF, SUMB, EPI, UNIT, FF, FFR>(p, (int64_t)blockIdx.x * 4 + wave, smem + wave * per_wave, lane);
+    sos_stream_body<TIn, TOut, TC, LC, VEC, TAPS, PF, SUMB, EPI, UNIT, FF, FFR, MEAS>(p, (int64_t)blockIdx.x * 4 + wave, smem + wave * per_wave, lane);
 }
 
 // Non-finite samples and time segmentation.  In the sequential recursion a NaN / Inf never leaves: once the
@@ -694,6 +783,23 @@ __global__ void __launch_bounds__(256) sos_nonfinite_fix_kernel(const SosParams 
         if (p.sx_out && sct > 0) p.sx_out[o] = __builtin_nan("");   // section 0's input history is the signal itself: already exact
         if (p.sy_out) p.sy_out[o] = __builtin_nan("");
     }
+}
+
+// The same repair for the measuring pass: the blocks of the segments after the row's first flagged one become NaN.
+__global__ void __launch_bounds__(256) sos_block_energy_fix_kernel(const SosParams p)
+{
+    __shared__ int sh_first;
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int64_t row = blockIdx.x;
+    if (tid == 0) sh_first = p.nseg;
+    __syncthreads();
+    for (int q = tid; q < p.nseg; q += nthr)
+        if (p.nf_flag[row * p.nseg + q]) atomicMin(&sh_first, q);
+    __syncthreads();
+    const int g0 = sh_first;
+    if (g0 >= p.nseg - 1) return;
+    double *s = (double *)p.y + row * p.ms_nblk;
+    for (int64_t b = (int64_t)(g0 + 1) * p.ms_bps + tid; b < p.ms_nblk; b += nthr) s[b] = __builtin_nan("");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1440,6 +1546,109 @@ void sos_filtfilt_forward(const void *x, int x_dtype, void *y, int y_dtype, int6
     p.ff = 2; p.x = work; p.y = y; p.x_pitch = p.T;
     if (y_dtype == TFX_F32) filtfilt_launch<double, float, 2, false>(p, pl->warm, stream);
     else filtfilt_launch<double, double, 2, true>(p, pl->warm, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// Block energies: S[r, i] = sum of y[r, n]^2 over n in [e_i, e_(i+1)), e_i = (i num) / den, y = the float64 cascade of row r from
+// zero state -- the measurement under a loudness meter (K-weighting, 100 ms blocks).  One launch of the cascade kernel (MEAS)
+// that reads the signal once and writes nblk values per row; the filtered signal exists in registers only.
+//
+// Rows are cut into time segments like the forward cascade (same warm-up bound, same TFX_SOS_NSEG), with two differences.
+// A segment owns whole blocks: it starts `warm` samples in front of a block edge, so every S[r, i] has one writer and no
+// partial sums cross streams.  And the cut depends on the row length, the cascade and num / den alone -- not on the number of
+// rows, not on the device: a row's bits are the same in every batch, and the plan query needs no GPU.  The target is one
+// segment per wave slot of the part (256 CUs x 2 workgroups x 4 waves), and segments of at least 4 x warm-up: 2 rows x 28.8 M
+// samples ran 0.191 / 0.140 / 0.119 ms with segments of 8 / 4 / 2 x warm-up, 8 x 2.88 M 0.181 / 0.106 / 0.071, but 64 x 2.88 M,
+// which fills the part either way, 0.258 / 0.242 / 0.28: 4 x is the shortest that costs the full part nothing.
+// ------------------------------------------------------------------------------------------
+constexpr int MS_LC = 32;
+constexpr int64_t MS_STREAMS = 2048;
+constexpr int64_t MS_SEQ_MAX = (int64_t)1 << 24;       // longest row one wavefront is asked to walk alone
+
+struct BlockEnergyPlan { int64_t nblk, bps, warm; int nseg; };
+
+static BlockEnergyPlan block_energy_plan(int64_t C, int64_t T, const double *sos_host, int64_t K, int64_t num, int64_t den)
+{
+    TFX_CHECK(C >= 0 && T >= 0, "sos_block_energy: negative size");
+    TFX_CHECK(sos_host && K >= 1 && K <= 512, "sos_block_energy: null coefficients or bad section count %lld (1 ... 512)", (long long)K);
+    TFX_CHECK(num >= 1 && den >= 1, "sos_block_energy: block length num / den needs num >= 1 and den >= 1");
+    TFX_CHECK(num / 64 >= den, "sos_block_energy: blocks of num / den = %lld / %lld samples are shorter than 64", (long long)num, (long long)den);
+    TFX_CHECK(T <= ((int64_t)1 << 61) / den && C <= INT32_MAX, "sos_block_energy: size overflows");
+    for (int64_t i = 0; i < K * 6; ++i) TFX_CHECK(std::isfinite(sos_host[i]), "sos_block_energy: non-finite SOS coefficient");
+    for (int64_t s = 0; s < K; ++s) TFX_CHECK(sos_host[s * 6 + 3] == 1.0, "sos_block_energy: sos[%lld, 3] (a0) must be 1", (long long)s);
+    const std::shared_ptr<SosPlan> plan = get_plan(sos_host, K, nullptr, 1);
+    BlockEnergyPlan bp;
+    bp.nblk = T * den / num;
+    bp.bps = bp.nblk; bp.warm = 0; bp.nseg = 1;
+    TFX_CHECK(plan->warm >= 0 || T <= MS_SEQ_MAX, "sos_block_energy: the cascade does not decay (no warm-up length), so rows cannot be cut into "
+              "segments, and %lld samples are too many for one wavefront per row (max %lld)", (long long)T, (long long)MS_SEQ_MAX);
+    if (plan->warm >= 0 && bp.nblk > 1) {
+        const int64_t warm = (plan->warm + 255) & ~(int64_t)255;
+        const int64_t force_nseg = env_i64("TFX_SOS_NSEG", 0);
+        const int64_t covered = bp.nblk * num / den;                       // e_nblk
+        int64_t len = ceil_div(covered, force_nseg > 0 ? force_nseg : MS_STREAMS);
+        if (force_nseg <= 0 && len < 4 * warm) len = 4 * warm;
+        if (len < warm) len = warm;
+        if (len < 1) len = 1;
+        const int64_t b = ceil_div(len * den, num);                        // e_b >= len >= warm: the halo of segment 1 starts inside the row
+        if (b >= 1 && b < bp.nblk) { bp.bps = b; bp.nseg = (int)ceil_div(bp.nblk, b); bp.warm = warm; }
+    }
+    return bp;
+}
+
+void sos_block_energy_plan_info(int64_t C, int64_t T, const double *sos_host, int64_t K, int64_t num, int64_t den,
+                                int64_t *nblk, int *nseg, int64_t *warm)
+{
+    const BlockEnergyPlan bp = block_energy_plan(C, T, sos_host, K, num, den);
+    if (nblk) *nblk = bp.nblk;
+    if (nseg) *nseg = bp.nseg;
+    if (warm) *warm = bp.warm;
+}
+
+template <typename TIn>
+static void block_energy_launch(SosParams p, hipStream_t stream)
+{
+    const size_t shmem = 4 * (size_t)(sos_stage_bytes<TIn, TIn, double, MS_LC>() + sos_carry_bytes<double, MS_LC>(1, p.K));
+    TFX_CHECK(shmem <= 160 * 1024, "sos_block_energy: K=%d needs %zu B of LDS (max 163840)", p.K, shmem);
+    auto kern = sos_stream_kernel<TIn, TIn, double, MS_LC, false, false, false, 2, false, false, false, 0, false, true>;
+    if (shmem > 64 * 1024)
+        TFX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    const int64_t nstreams = p.C * p.nseg;
+    TFX_CHECK(nstreams <= INT32_MAX, "sos_block_energy: %lld streams are too many for one launch", (long long)nstreams);
+    p.nf_flag = nullptr;
+    if (p.nseg > 1) p.nf_flag = (int *)scratch("sos_nf_flag", (size_t)nstreams * sizeof(int), stream);
+    {
+        ProfScope ps("sos_block_energy_kernel", stream);
+        hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(nstreams, 4)), dim3(256), shmem, stream, p);
+        TFX_HIP(hipGetLastError());
+    }
+    if (p.nseg > 1) {
+        ProfScope ps("sos_block_energy_fix_kernel", stream);
+        hipLaunchKernelGGL(sos_block_energy_fix_kernel, dim3((unsigned)p.C), dim3(256), 0, stream, p);
+        TFX_HIP(hipGetLastError());
+    }
+}
+
+void sos_block_energy_forward(const void *x, int x_dtype, double *s, int64_t C, int64_t T, const double *sos_host, int64_t K,
+                              int64_t num, int64_t den, hipStream_t stream)
+{
+    TFX_CHECK(x_dtype == TFX_F32 || x_dtype == TFX_F64, "sos_block_energy: bad x dtype %d", x_dtype);
+    const BlockEnergyPlan bp = block_energy_plan(C, T, sos_host, K, num, den);
+    if (C == 0 || bp.nblk == 0) return;
+    TFX_CHECK(x && s, "sos_block_energy: null signal or result pointer");
+    const std::shared_ptr<SosPlan> plan = get_plan(sos_host, K, stream, 1);      // held until the launches are enqueued
+    SosPlan *pl = plan.get();
+    SosParams p{};
+    p.tab = ensure_table<double>(pl, &pl->tab_f64_lc32, MS_LC, &pl->nsteps32, stream);
+    p.nsteps = pl->nsteps32;
+    p.x = x; p.y = s;
+    p.C = C; p.C_in = C; p.T = T; p.K = (int)K; p.x_pitch = T;
+    p.nseg = bp.nseg; p.warm = bp.warm;
+    p.fair = 15; p.fair_nw = 2;
+    p.ep_stat = -1;
+    p.ms_num = num; p.ms_den = den; p.ms_nblk = bp.nblk; p.ms_bps = bp.bps;
+    if (x_dtype == TFX_F32) block_energy_launch<float>(p, stream);
+    else block_energy_launch<double>(p, stream);
 }
 
 // ------------------------------------------------------------------------------------------

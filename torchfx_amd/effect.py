@@ -157,6 +157,57 @@ class Normalize(FX):
         return self.strategy(waveform, self.peak)
 
 
+class LoudnessNormalize(FX):
+    """Normalise to a programme loudness: measure the integrated loudness ``L`` of the signal (ITU-R BS.1770-4 / EBU R128,
+    :func:`torchfx_amd.loudness.integrated_loudness`) and multiply by ``10 ** ((target - L) / 20)``.
+
+    ``target`` in LUFS (-23 = EBU R128 delivery, -14 / -16 = streaming services); ``channel_weights`` as for the measurement
+    (default 1.0 per channel).  One measurement per ``[C, T]`` signal, one per batch item of ``[B, C, T]``, mono for ``[T]``.
+    The gain stays on the signal's device: nothing is read back between measuring and applying.  A signal that measures
+    ``-inf`` (silence, or shorter than 400 ms) is left unchanged, as ``Normalize`` leaves an all-zero signal; a NaN measurement
+    gives NaN samples.  ``fs`` comes from the ``Wave`` the effect is piped into when it is None.  A whole-signal measurement:
+    it is a step of its own in ``Wave.plan()`` and cannot run in a chunked stream."""
+
+    def __init__(self, target: float = -23.0, channel_weights: tp.Sequence[float] | None = None, fs: int | None = None) -> None:
+        super().__init__()
+        if not math.isfinite(target):
+            raise ValueError(f"target must be a finite loudness in LUFS, got {target!r}")
+        self.target = float(target)
+        self.channel_weights = None if channel_weights is None else tuple(float(w) for w in channel_weights)
+        self.fs = fs
+
+    def route(self, x: Tensor, length: int | None = None) -> str:
+        """``native (...)`` or ``scipy on host -- <reason>`` for the measurement of ``x`` (rows of ``length`` samples, default x's)."""
+        if not x.is_cuda:
+            return f"scipy on host -- {x.device.type} tensor"
+        if x.dtype not in (torch.float32, torch.float64):
+            return f"refused -- {x.dtype} signal (float32 / float64 only)"
+        from torchfx_amd.loudness import kweighting_sos
+
+        n = int(x.shape[-1]) if length is None else int(length)
+        rows = max(1, x.numel() // max(1, int(x.shape[-1]))) if x.dim() else 1
+        try:
+            info = _ext().sos_block_energy_plan_info(kweighting_sos(self.fs), rows, n, self.fs, 10)
+        except (RuntimeError, ValueError) as e:
+            return f"refused -- {e}"
+        return (f"native (sos_block_energy_kernel, {info['nblk']} sub-blocks of 100 ms, {info['nseg']} segment(s) per row; "
+                "gating and gain on the device)")
+
+    @torch.no_grad()
+    def forward(self, waveform: Tensor) -> Tensor:
+        if self.fs is None:
+            raise ValueError("LoudnessNormalize needs the sample rate: pass fs or pipe a Wave into it (wave | LoudnessNormalize())")
+        from torchfx_amd.loudness import integrated_loudness
+
+        loud = integrated_loudness(waveform, self.fs, self.channel_weights)
+        gain = torch.pow(10.0, (self.target - loud) / 20.0)
+        gain = torch.where(torch.isneginf(loud), torch.ones_like(gain), gain).to(waveform.dtype)
+        return waveform * (gain.view(-1, 1, 1) if gain.dim() else gain)
+
+    def extra_repr(self) -> str:
+        return f"target={self.target}, channel_weights={self.channel_weights}, fs={self.fs}"
+
+
 class Epilogued(FX):
     """Planner product (``Wave.plan()``, ``fuse_epilogue``): a filter followed by ``Gain`` and / or ``Normalize``
     whose elementwise work rides on the filter's own kernel.  ``producer`` is an SOS filter / cascade or an

@@ -372,6 +372,15 @@ def _refuse_zero_phase(e, who: str) -> None:
                         "(wave | ZeroPhase(...) or sosfiltfilt) before or after streaming")
 
 
+def _refuse_loudness(e, who: str) -> None:
+    from torchfx_amd.effect import LoudnessNormalize
+
+    if any(isinstance(m, LoudnessNormalize) for m in (e.modules() if isinstance(e, nn.Module) else [e])):
+        raise TypeError(f"LoudnessNormalize cannot run in {who}: integrated loudness is a measurement of the whole signal "
+                        "(its relative gate depends on every block), which a chunked stream has not seen yet; normalise the "
+                        "whole signal (wave | LoudnessNormalize(...)) before or after streaming")
+
+
 class _ChunkRun:
     """``IIR ... | StatefulFIR | Gain`` (any non-empty sub-pattern of at least two effects) as ONE launch per small chunk
     (``torchfx_ext.chunk_forward``): the chain of a 2 x 512 block is launch-bound, not arithmetic-bound.  Consecutive
@@ -510,6 +519,7 @@ class StreamProcessor:
             if not isinstance(e, FX):
                 raise TypeError("All effects must inherit from FX when used in StreamProcessor")
             _refuse_zero_phase(e, "StreamProcessor")
+            _refuse_loudness(e, "StreamProcessor")
             if not isinstance(e, StatefulResample) and any(isinstance(m, Resample) for m in e.modules()):
                 raise TypeError("Resample cannot run in StreamProcessor: resampling each chunk on its own leaves a seam at "
                                 "every chunk boundary; use StatefulResample as a top-level effect of the chain, or resample "
@@ -821,6 +831,7 @@ class RealtimeProcessor:
             if not isinstance(e, FX):
                 raise TypeError("All effects must inherit from FX when used in RealtimeProcessor")
             _refuse_zero_phase(e, "RealtimeProcessor")
+            _refuse_loudness(e, "RealtimeProcessor")
             if _has_stateful_resample(e):
                 raise TypeError("StatefulResample cannot run in RealtimeProcessor: a sound card's output block has the input "
                                 "block's length and sample rate; resample with StreamProcessor or Wave.resample instead")

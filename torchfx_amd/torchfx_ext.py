@@ -35,6 +35,7 @@ __all__ = [
     "biquad_forward", "sos_forward", "sos_bank_forward", "sos_bank_sum_forward", "delay_line_forward", "delay_forward",
     "delay_amplitudes", "delay_regime", "delay_stream_forward", "delay_line_stream_forward", "resample_forward",
     "resample_plan_info", "resample_stream_forward", "resample_stream_plan_info", "sos_filtfilt", "sos_filtfilt_plan_info",
+    "sos_block_energy", "sos_block_energy_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
 ]
@@ -232,6 +233,25 @@ def sos_filtfilt_plan_info(sos, rows: int, length: int, padtype="odd", padlen: i
                                                 ctypes.byref(nf), ctypes.byref(nr)))
     return {"default_padlen": o[0].value, "padlen": o[1].value, "work_elems": o[2].value, "warmup": o[3].value,
             "nseg_forward": nf.value, "nseg_reverse": nr.value}
+
+
+def sos_block_energy(x: Tensor, sos, num: int, den: int = 1) -> Tensor:
+    """The cascade and the energy of its output per block of samples in one launch (``tfx_sos_block_energy_forward``); the
+    filtered signal is never stored.  ``x [..., T]`` on the device (float32 / float64, contiguous rows), ``sos [K,6]`` on the
+    host, used from zero state in float64 -> float64 ``[..., nblk]`` with ``S[r, i] = sum(y[r, e_i : e_(i+1)] ** 2)``,
+    ``e_i = (i * num) // den``, ``nblk = (T * den) // num`` (possibly 0); ``num / den >= 64``."""
+    return native.ops().sos_block_energy(x.contiguous(), _coeff(sos), int(num), int(den))
+
+
+def sos_block_energy_plan_info(sos, rows: int, length: int, num: int, den: int = 1) -> dict:
+    """What :func:`sos_block_energy` does for ``rows`` rows of ``length`` samples (``tfx_sos_block_energy_plan_info``;
+    host-only, same argument checks): ``nblk`` blocks per row, ``nseg`` time segments per row and ``warm``, the halo of a
+    segment (0 with one segment).  The cut depends on ``length``, the cascade and ``num / den`` alone."""
+    a = sos_array(sos)
+    nblk, warm, nseg = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0)
+    L.check(L.load().tfx_sos_block_energy_plan_info(int(rows), int(length), a.ctypes.data, a.shape[0], int(num), int(den),
+                                                    ctypes.byref(nblk), ctypes.byref(nseg), ctypes.byref(warm)))
+    return {"nblk": nblk.value, "nseg": nseg.value, "warm": warm.value}
 
 
 RESAMPLE_STREAM_KERNELS = ("resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel", "copy")
