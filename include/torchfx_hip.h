@@ -277,6 +277,12 @@ int tfx_sos_fft_conv_supported(int64_t T, const double *sos_host, int64_t K, int
 int tfx_sos_fft_conv_plan_info(int64_t T, const double *sos_host, int64_t K, int64_t taps,
                                int64_t pad_left, int64_t pad_right, int force_block,
                                int64_t *N, int64_t *S, int64_t *F, int64_t *warmup);
+/* The same, plus the tail geometry: at N = 2^21, where what a row's last frame has to deliver fits the hop of a 2^20-point
+ * frame, that frame runs at *tail_N = 2^20 points with hop *tail_S, from sample (*F - 1) * *S of the output row on; the
+ * *F - 1 frames before it run at *N.  *tail_N = *tail_S = 0: all *F frames run at *N.  Any output may be NULL. */
+int tfx_sos_fft_conv_plan_info2(int64_t T, const double *sos_host, int64_t K, int64_t taps,
+                                int64_t pad_left, int64_t pad_right, int force_block,
+                                int64_t *N, int64_t *S, int64_t *F, int64_t *warmup, int64_t *tail_N, int64_t *tail_S);
 /* samples a row's recursion starts early from zero state inside the column pass (-1: more than 8 sections / no decay) */
 int64_t tfx_sos_fft_conv_warmup(const double *sos_host, int64_t K);
 int tfx_sos_fft_conv_forward(const float *x, float *y, int64_t C, int64_t T,

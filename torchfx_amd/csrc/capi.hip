@@ -386,6 +386,16 @@ int tfx_sos_fft_conv_plan_info(int64_t T, const double *sos_host, int64_t K, int
     }
 }
 
+int tfx_sos_fft_conv_plan_info2(int64_t T, const double *sos_host, int64_t K, int64_t taps, int64_t pad_left, int64_t pad_right,
+                                int force_block, int64_t *N, int64_t *S, int64_t *F, int64_t *warmup, int64_t *tail_N, int64_t *tail_S)
+{
+    try {
+        return (sos_host && sos_fft_conv_plan(T, sos_host, K, taps, pad_left, pad_right, force_block, N, S, F, warmup, tail_N, tail_S)) ? 1 : 0;
+    } catch (...) {
+        return 0;
+    }
+}
+
 int64_t tfx_sos_fft_conv_warmup(const double *sos_host, int64_t K)
 {
     try {

@@ -339,6 +339,7 @@ int64_t sos_fft_conv_warmup(const double *sos_host, int64_t Ksos) { return (Ksos
 // The cascade-in-pass-A route: 4096- or 8192-point rows of the three-pass pipeline, a cascade of at most OLS_SOS_MAXK
 // sections whose warm-up fits a row.  `force`: 1 / 2 = the 2^20 / 2^21-point block even for rows shorter than one block
 // (tests at fixture size; a one-frame launch).  False when this form does not serve the call, else its route and warm-up.
+// At 2^21 points the route carries a tail geometry where a row's last frame fits a 2^20-point block (olsnative_tail_geometry).
 static bool sos_fft_conv_route(int64_t T, const double *sos_host, int64_t Ksos, int64_t K, int64_t pl, int64_t pr, int force,
                                int sh_base, OlsRoute &r, int64_t &warm)
 {
@@ -357,13 +358,14 @@ static bool sos_fft_conv_route(int64_t T, const double *sos_host, int64_t Ksos, 
     }
     r.path = OLS_PATH_PASSES;
     olsnative_geometry(K, T, pl, pr, sh_base, r);
+    olsnative_tail_geometry(K, T, pl, pr, r);
     return true;
 }
 
-// block length, hop, frames per row and warm-up samples the fused pipeline would use for x on a 128-byte line; false when it
-// does not serve the geometry
+// block length, hop, frames per row, warm-up samples and the tail geometry's block and hop (0: none) the fused pipeline would
+// use for x on a 128-byte line; false when it does not serve the geometry
 bool sos_fft_conv_plan(int64_t T, const double *sos_host, int64_t Ksos, int64_t K, int64_t pad_left, int64_t pad_right, int force,
-                       int64_t *N_out, int64_t *S_out, int64_t *F_out, int64_t *warm_out)
+                       int64_t *N_out, int64_t *S_out, int64_t *F_out, int64_t *warm_out, int64_t *tail_N_out, int64_t *tail_S_out)
 {
     OlsRoute r;
     int64_t warm = 0;
@@ -372,6 +374,8 @@ bool sos_fft_conv_plan(int64_t T, const double *sos_host, int64_t Ksos, int64_t 
     if (S_out) *S_out = r.S;
     if (F_out) *F_out = r.F;
     if (warm_out) *warm_out = warm;
+    if (tail_N_out) *tail_N_out = r.tail_N;
+    if (tail_S_out) *tail_S_out = r.tail_S;
     return true;
 }
 

@@ -39,6 +39,9 @@ struct OlsGeom {
     int64_t Tout;      // output row length
     int64_t F;         // frames per channel
     int64_t S;         // hop = valid outputs per frame
+    int64_t t0;        // time origin of frame 0 of every row: 0, or (tail geometry, olsnative_forward) the sample behind the
+                       // main geometry's last frame.  x, Tn and the validity bounds [0, Tn) stay the row's own, so a tail
+                       // frame's FIR history and warm-up read the real samples in front of t0
     int64_t pad_left;  // left zero padding of the framed signal (>= the caller's; rounded up for alignment)
     int64_t out_shift; // = pad_left - caller's pad_left: block output i is y[i - out_shift]
     int64_t nframes;   // C * F
@@ -47,7 +50,8 @@ struct OlsGeom {
     // epilogue of the inverse column pass on the stored samples (epilogue.h)
     float ep_gain;
     int ep_scale, ep_clamp, ep_stat;
-    double *ep_partial;   // [nframes][N2 / 32]: one partial per (frame, column block); row c owns F * N2/32 consecutive ones
+    double *ep_partial;   // one partial per (frame, column block): frame f of row c owns the N2/32 slots from c * ep_row + f * N2/32
+    int64_t ep_row;       // slots between two rows: F * N2/32, or more where a row's tail frame keeps its partials behind them
     int N2;            // row length (N = 256 * N2)
     int P2;            // row pitch of the workspace T in elements (N2 + pad: breaks the power-of-two stride)
     int sh_on, sh_base; // rows that are not whole 128-byte lines (T % 32 != 0, or a base pointer inside a line): row c's frame grid
@@ -143,9 +147,9 @@ ols_col_fwd16_kernel(const float *__restrict__ x, cpx *__restrict__ T, const cpx
     const int cb = blockIdx.x % ncb;
     const int n2 = cb * OLS_CB + col;
     const int64_t fa = frame0 + 2 * pair, fb = fa + 1;
-    const int64_t ca = fa / g.F, ia0 = (fa % g.F) * g.S - g.pad_left - row_shift(g, ca);
+    const int64_t ca = fa / g.F, ia0 = g.t0 + (fa % g.F) * g.S - g.pad_left - row_shift(g, ca);
     const bool has_b = fb < g.nframes;
-    const int64_t cb_ = has_b ? fb / g.F : 0, ib0 = has_b ? (fb % g.F) * g.S - g.pad_left - row_shift(g, cb_) : 0;
+    const int64_t cb_ = has_b ? fb / g.F : 0, ib0 = has_b ? g.t0 + (fb % g.F) * g.S - g.pad_left - row_shift(g, cb_) : 0;
     const float *xa = x + ca * g.Tn, *xb = x + cb_ * g.Tn;
     cpx v[NBF][16];
     // interior frames (the common case) need no bounds checks
@@ -231,9 +235,9 @@ ols_col_inv16_kernel(const cpx *__restrict__ T, float *__restrict__ y, const cpx
     col_stages16<true, NBF>(v, lds, tw256, col, q);
 
     const int64_t fa = frame0 + 2 * pair, fb = fa + 1;
-    const int64_t ca = fa / g.F, oa0 = (fa % g.F) * g.S;
+    const int64_t ca = fa / g.F, oa0 = g.t0 + (fa % g.F) * g.S;
     const bool has_b = fb < g.nframes;
-    const int64_t cb_ = has_b ? fb / g.F : 0, ob0 = has_b ? (fb % g.F) * g.S : 0;
+    const int64_t cb_ = has_b ? fb / g.F : 0, ob0 = has_b ? g.t0 + (fb % g.F) * g.S : 0;
     float *ya = y + ca * g.Tout, *yb = y + cb_ * g.Tout;
     const int64_t sha = g.out_shift + row_shift(g, ca), shb = g.out_shift + row_shift(g, cb_);
     const bool epi = g.ep_scale | g.ep_clamp | (g.ep_stat >= 0);
@@ -278,8 +282,8 @@ ols_col_inv16_kernel(const cpx *__restrict__ T, float *__restrict__ y, const cpx
         if (tid == 0) {
             double ra = red[0], rb = red[nw];
             for (int u = 1; u < nw; ++u) { ra = red_comb_rt(g.ep_stat, ra, red[u]); rb = red_comb_rt(g.ep_stat, rb, red[nw + u]); }
-            g.ep_partial[fa * ncb + cb] = ra;
-            if (has_b) g.ep_partial[fb * ncb + cb] = rb;
+            g.ep_partial[ca * g.ep_row + (fa % g.F) * ncb + cb] = ra;
+            if (has_b) g.ep_partial[cb_ * g.ep_row + (fb % g.F) * ncb + cb] = rb;
         }
     }
 }
@@ -290,9 +294,9 @@ __global__ void __launch_bounds__(256) ols_straddle_fix_kernel(float *__restrict
 {
     const int64_t c = blockIdx.x;
     if (!g.nf_pair[c]) return;
-    if (blockIdx.y == 0 && threadIdx.x == 0 && g.ep_stat >= 0) g.ep_partial[(c * g.F) * (g.N2 / OLS_CB)] = __builtin_nan("");
-    const int64_t hi = min(g.Tout, g.S - g.out_shift - row_shift(g, c));
-    for (int64_t t = (int64_t)blockIdx.y * 256 + threadIdx.x; t < hi; t += (int64_t)gridDim.y * 256) y[c * g.Tout + t] = __builtin_nanf("");
+    if (blockIdx.y == 0 && threadIdx.x == 0 && g.ep_stat >= 0) g.ep_partial[c * g.ep_row] = __builtin_nan("");
+    const int64_t lo = max((int64_t)0, g.t0 - g.out_shift - row_shift(g, c)), hi = min(g.Tout, g.t0 + g.S - g.out_shift - row_shift(g, c));
+    for (int64_t t = lo + (int64_t)blockIdx.y * 256 + threadIdx.x; t < hi; t += (int64_t)gridDim.y * 256) y[c * g.Tout + t] = __builtin_nanf("");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -315,6 +319,9 @@ __global__ void __launch_bounds__(256) ols_straddle_fix_kernel(float *__restrict
 // float32 samples back IN PLACE -> the stage is the column transform's input z = a + i b -> radix-16 x 16 transform through
 // the same LDS bytes -> workspace.  Samples outside [0, T) enter the recursion as zeros and leave it as zeros (the
 // reference filters T samples and the FIR pads afterwards).
+// Tail geometry (OlsGeom::t0 != 0, one frame per row): the same walk over the row's LAST frame at a smaller block -- the clocks
+// start at t0 - pad_left - row_shift instead of 0 - ..., everything else (x, Tn, the validity bounds, the warm-up, which reads
+// the real samples in front of t0) is the row's own.  t0 is wave-uniform and lives in the two scalar clocks only.
 // ---------------------------------------------------------------------------------------------
 constexpr int SOSF_MAXK = 8;
 constexpr int SOSF_K4W = 4;                      // up to this many sections the kernel fits 128 registers: two workgroups per CU
@@ -341,9 +348,9 @@ ols_col_fwd16_sos_kernel(const float *__restrict__ x, cpx *__restrict__ T, const
     if (tid < 256) tw256[tid] = tw256g[tid];
     const int64_t pair = blockIdx.x;
     const int64_t fa = frame0 + 2 * pair, fb = fa + 1;
-    const int64_t ca = fa / g.F, ia0 = (fa % g.F) * g.S - g.pad_left - row_shift(g, ca);
+    const int64_t ca = fa / g.F, ia0 = g.t0 + (fa % g.F) * g.S - g.pad_left - row_shift(g, ca);
     const bool has_b = fb < g.nframes;
-    const int64_t cb_ = has_b ? fb / g.F : 0, ib0 = has_b ? (fb % g.F) * g.S - g.pad_left - row_shift(g, cb_) : 0;
+    const int64_t cb_ = has_b ? fb / g.F : 0, ib0 = has_b ? g.t0 + (fb % g.F) * g.S - g.pad_left - row_shift(g, cb_) : 0;
     const float *xa = x + ca * g.Tn, *xb = x + cb_ * g.Tn;
     const int nblk = g.N2 / OLS_CB;
     // Wave-uniform clock of the walk: `ta` / `tb` = time (sample index in its row) of row 0's first sample of the block being
@@ -357,8 +364,10 @@ ols_col_fwd16_sos_kernel(const float *__restrict__ x, cpx *__restrict__ T, const
     const bool mine_b = tid >= 256;
     const int rel_l = (tid & 255) * g.N2;
     // section taps: a sample lies in the windows of two consecutive frames (they overlap by K - 1 samples); the frame whose LAST
-    // S window samples hold it stores it (frame 0 of a row: its whole window) -- one writer per address
-    const int own_lo = TAPS ? (((mine_b ? fb : fa) % g.F) == 0 ? 0 : OLS_N1 * g.N2 - (int)g.S) : 0;
+    // S window samples hold it stores it (the frame whose window starts at the row's start: its whole window) -- one writer per
+    // address.  N - S is the same for the main and the tail geometry (both blocks are whole lines), so the tail frame's
+    // samples begin where the last main frame's end
+    const int own_lo = TAPS ? ((((mine_b ? fb : fa) % g.F) == 0 && g.t0 == 0) ? 0 : OLS_N1 * g.N2 - (int)g.S) : 0;
     double h1[KS + 1], h2[KS + 1];             // h[0]: input history; h[s + 1]: output history of section s (iir_cpu.cpp:125-130)
 #pragma unroll
     for (int s = 0; s <= KS; ++s) { h1[s] = 0.0; h2[s] = 0.0; }
@@ -506,8 +515,11 @@ ols_col_fwd16_sos_kernel(const float *__restrict__ x, cpx *__restrict__ T, const
 // flagged frames entered the transform as zeros from the bad sample on, so the frame that shares a transform with one (even a
 // frame of the neighbouring signal row) keeps its own finite output.  z = s + 1 (section taps, parity tests): section s is exact up to its first non-finite sample, which
 // lies in the flagged frame's window or its warm-up; everything behind that sample becomes NaN (iir_cpu.cpp:132-147).
+// `gt`: the tail geometry (one frame per row behind the main frames, flags and partials of its own) when has_tail: a row's
+// frames in time order are the main ones, then its tail frame -- a flagged main frame makes the row NaN through the tail, a
+// flagged tail frame from gt.t0 on.
 __global__ void __launch_bounds__(256)
-ols_sos_nonfinite_fix_kernel(float *__restrict__ y, double *__restrict__ sections, OlsGeom g, int warm_blocks)
+ols_sos_nonfinite_fix_kernel(float *__restrict__ y, double *__restrict__ sections, OlsGeom g, int warm_blocks, OlsGeom gt, int has_tail)
 {
     __shared__ int s_first;
     __shared__ long long s_n;
@@ -518,14 +530,18 @@ ols_sos_nonfinite_fix_kernel(float *__restrict__ y, double *__restrict__ section
     for (int64_t f = tid; f < g.F; f += 256)
         if (g.nf_flag[c * g.F + f]) atomicMin(&s_first, (int)f);
     __syncthreads();
-    const int64_t first = s_first;
-    if (first == 0x7fffffff) return;
+    int64_t first = s_first;
+    if (first == 0x7fffffff) {
+        if (!has_tail || !gt.nf_flag[c]) return;
+        g = gt;                                   // the tail frame is the row's first flagged one: frame 0 of its geometry
+        first = 0;
+    }
     const int sh = row_shift(g, c);
     const float nanf_ = __builtin_nanf("");
     if (blockIdx.z == 0) {
         // the statistic of an epilogue saw the flagged frames' stand-in samples: a NaN partial wins both reductions (epilogue.h)
-        if (blockIdx.y == 0 && tid == 0 && g.ep_stat >= 0) g.ep_partial[(c * g.F + first) * (g.N2 / OLS_CB)] = __builtin_nan("");
-        const int64_t t0 = max((int64_t)0, first * g.S - g.out_shift - sh);
+        if (blockIdx.y == 0 && tid == 0 && g.ep_stat >= 0) g.ep_partial[c * g.ep_row + first * (g.N2 / OLS_CB)] = __builtin_nan("");
+        const int64_t t0 = max((int64_t)0, g.t0 + first * g.S - g.out_shift - sh);
         const int64_t len = g.Tout - t0, per = (len + gridDim.y - 1) / gridDim.y;
         const int64_t lo = t0 + per * blockIdx.y, hi = min(g.Tout, lo + per);
         for (int64_t t = lo + tid; t < hi; t += 256) y[c * g.Tout + t] = nanf_;
@@ -533,7 +549,7 @@ ols_sos_nonfinite_fix_kernel(float *__restrict__ y, double *__restrict__ section
     }
     if (!sections || blockIdx.y != 0) return;
     double *row = sections + ((int64_t)(blockIdx.z - 1) * (g.nframes / g.F) + c) * g.Tn;
-    const int64_t start = max((int64_t)0, first * g.S - g.pad_left - sh - (int64_t)OLS_CB * warm_blocks);
+    const int64_t start = max((int64_t)0, g.t0 + first * g.S - g.pad_left - sh - (int64_t)OLS_CB * warm_blocks);
     for (int64_t t0 = start; t0 < g.Tn; t0 += 4096) {         // first non-finite sample of this section, 4096 samples at a time
         for (int64_t t = t0 + tid; t < min(g.Tn, t0 + 4096); t += 256)
             if (!(__builtin_fabs(row[t]) <= 1.7976931348623157e308)) { atomicMin(&s_n, (long long)t); break; }

@@ -16,6 +16,8 @@ struct OlsRoute {
     int lds_kind = -1;          // one-launch kernel: 0 = 4096 points, 1 = 8192, 2 = 16 384 (1024-thread), 3 = 16 384 (w8)
     int64_t N = 0, lead = 0, S = 0, F = 0;
     int sh_base = 0, sh_on = 0; // three-pass: element offset of x in its 128-byte line; row frame grids shifted
+    int64_t tail_N = 0, tail_S = 0;   // cascade route: block and hop of the tail geometry (the last of a row's F frames runs at this
+                                      // smaller block, the F - 1 before it at N), or 0: all F frames at N  (olsnative_tail_geometry)
 };
 
 inline int ols_sh_base(const void *x, int elem_bytes) { return (int)(((uintptr_t)x & 127) / elem_bytes); }
@@ -30,7 +32,8 @@ void fftconv_clear();
 constexpr int OLS_SOS_MAXK = 8;                              // cascade sections the column pass holds (SOSF_MAXK)
 int64_t sos_fft_conv_warmup(const double *sos_host, int64_t Ksos);
 bool sos_fft_conv_plan(int64_t T, const double *sos_host, int64_t Ksos, int64_t K, int64_t pad_left, int64_t pad_right, int force,
-                       int64_t *N_out, int64_t *S_out, int64_t *F_out, int64_t *warm_out);
+                       int64_t *N_out, int64_t *S_out, int64_t *F_out, int64_t *warm_out, int64_t *tail_N_out = nullptr,
+                       int64_t *tail_S_out = nullptr);
 void sos_fft_conv_forward(const float *x, float *y, int64_t C, int64_t T, const double *sos_host, int64_t Ksos,
                           const float *kernel_host, int64_t K, int64_t pad_left, int64_t pad_right, double *sections, int force,
                           const Epilogue *ep, hipStream_t stream);
@@ -45,6 +48,7 @@ void olslds_clear();
 // olsnative.hip: the three-pass pipeline in float32
 bool olsnative_supported(int64_t K, int64_t L, int64_t *N_out);
 void olsnative_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int sh_base, OlsRoute &r);
+void olsnative_tail_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, OlsRoute &r);   // after olsnative_geometry: fills tail_N, tail_S
 void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const float *kf_host, int64_t K, int64_t pl, int64_t pr,
                        const OlsRoute &r, hipStream_t stream, const float *hist, int64_t H, const Epilogue *ep,
                        const SosFuseHost *sosf = nullptr);

@@ -63,10 +63,11 @@ struct NativePlan {
     std::unique_ptr<DeviceBuffer> taps_dev;   // device copy of the taps while the spectrum kernels may still read it (N = 2^20)
     hipEvent_t ready = nullptr;     // recorded behind the spectrum kernels: other streams wait for it before they read Hp
     hipStream_t ready_stream = nullptr;
+    std::shared_ptr<NativePlan> tail;   // the 2^20-point plan of the same taps for the rows' short last frames (OlsRoute::tail_N), or null
     ~NativePlan() { if (ready) (void)hipEventDestroy(ready); }
 };
 typedef std::shared_ptr<NativePlan> NativePlanPtr;
-static PlanCache<NativePlan, 2> g_nplans(16, "overlap-save");      // tail: N, lead
+static PlanCache<NativePlan, 3> g_nplans(16, "overlap-save");      // tail: N, lead, block of the tail frames (0: none)
 static std::mutex g_np_mu;                                         // guards g_free_mb
 static int64_t g_free_mb[TFX_MAX_DEVICES] = {};                  // per device: free memory (MB) seen at first use, 0 = not asked yet
 
@@ -340,7 +341,7 @@ static NativePlanPtr build_native_plan(const float *kf, int64_t K, int64_t N, in
         ols_set_attributes(current_device());                 // the column pass needs more than 64 KB of dynamic LDS
         OlsGeom g{};
         g.Tn = K; g.Tout = K; g.F = 1; g.S = N; g.pad_left = lead; g.out_shift = 0; g.nframes = 1;
-        g.hist = nullptr; g.H = 0; g.ep_gain = 1.0f; g.ep_scale = 0; g.ep_clamp = 0; g.ep_stat = -1; g.ep_partial = nullptr;
+        g.hist = nullptr; g.H = 0; g.ep_gain = 1.0f; g.ep_scale = 0; g.ep_clamp = 0; g.ep_stat = -1; g.ep_partial = nullptr; g.ep_row = 0;
         g.N2 = N2; g.P2 = N2; g.nt = 0;
         hipLaunchKernelGGL(ols_col_fwd16_kernel<1>, dim3((unsigned)(N2 / OLS_CB)), dim3(512), OLS_SHM_COL, stream,
                            (const float *)pl->taps_dev->p, pl->Hp, pl->tw256, g, (int64_t)0);
@@ -426,6 +427,24 @@ void olsnative_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, int sh_ba
     r.F = ceil_div(Tout + (r.sh_on ? 31 : 0), r.S);
 }
 
+// The last frame of a row holds half a frame of useful samples on average and goes through all three passes at full size.
+// Where the block is 2^21 points and what the last frame has to deliver fits the hop of a 2^20-point frame (admissible for
+// the tap count), the route carries a second geometry: F - 1 main frames per row, then ONE 2^20-point tail frame per row
+// whose time origin is t0 = (F - 1) * S -- half the workspace traffic and transform work for that frame.  `lead` is the
+// same for both blocks, so N - S is too and t0 is a whole line: the tail frames start on 128-byte lines like the others.
+// r.F stays the row's frame count (main + tail).
+void olsnative_tail_geometry(int64_t K, int64_t Tn, int64_t pl, int64_t pr, OlsRoute &r)
+{
+    r.tail_N = r.tail_S = 0;
+    const int64_t Nt = (int64_t)1 << 20;
+    if (r.N != ((int64_t)1 << 21) || r.F < 2 || Nt < 2 * (K + 32)) return;
+    int64_t St = Nt - (K + r.lead) + 1;
+    if (St > 64) St -= St % 32;
+    const int64_t Tout = Tn + pl + pr - K + 1;
+    if (Tout + (r.sh_on ? 31 : 0) - (r.F - 1) * r.S > St) return;
+    r.tail_N = Nt; r.tail_S = St;
+}
+
 void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const float *kf_host, int64_t K, int64_t pl, int64_t pr,
                        const OlsRoute &r, hipStream_t stream, const float *hist, int64_t H, const Epilogue *ep, const SosFuseHost *sosf)
 {
@@ -434,12 +453,14 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
     // scratch slabs; the internal lanes are shared and ordered by the fork / join events)
     const int64_t N = r.N, lead = r.lead;           // block and frame geometry: olsnative_geometry
     OlsGeom g;
-    g.Tn = Tn; g.Tout = Tn + pl + pr - K + 1; g.pad_left = pl + lead; g.out_shift = 0;
-    g.S = r.S; g.F = r.F; g.sh_on = r.sh_on; g.sh_base = r.sh_base;
+    g.Tn = Tn; g.Tout = Tn + pl + pr - K + 1; g.pad_left = pl + lead; g.out_shift = 0; g.t0 = 0;
+    const bool tail = r.tail_N != 0;                // the rows' last frames run at 2^20 points: olsnative_tail_geometry
+    g.S = r.S; g.F = tail ? r.F - 1 : r.F; g.sh_on = r.sh_on; g.sh_base = r.sh_base;
     g.hist = hist; g.H = hist ? H : 0;
     g.ep_gain = ep ? (float)ep->gain : 1.0f; g.ep_scale = ep ? ep->scale : 0; g.ep_clamp = ep ? ep->clamp : 0;
-    g.ep_stat = ep ? ep->stat_mode : -1; g.ep_partial = nullptr;
+    g.ep_stat = ep ? ep->stat_mode : -1; g.ep_partial = nullptr; g.ep_row = 0;
     g.nf_flag = nullptr; g.nf_pair = nullptr;
+    TFX_CHECK(!tail || (sosf && g.F >= 1), "olsnative_forward: tail frames are the cascade route's");
     const int dev = current_device();
     // first call on this device: kernel attributes (code-object load) and the internal streams are set up on a helper thread
     // while this thread computes the spectrum (both are tens of milliseconds, one bound by the driver, one by the host's cores);
@@ -448,8 +469,11 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
     NativePlanPtr plan;
     std::exception_ptr plan_err;
     try {
-        plan = g_nplans.get(kf_host, (size_t)K * sizeof(float), {N, lead}, stream,
-                            [&] { return build_native_plan(kf_host, K, N, lead, stream); });
+        plan = g_nplans.get(kf_host, (size_t)K * sizeof(float), {N, lead, r.tail_N}, stream, [&] {
+            NativePlanPtr p = build_native_plan(kf_host, K, N, lead, stream);
+            if (tail) p->tail = build_native_plan(kf_host, K, r.tail_N, lead, stream);
+            return p;
+        });
     } catch (...) { plan_err = std::current_exception(); }
     {
         std::shared_future<void> w;
@@ -469,6 +493,7 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
     }
     if (plan_err) std::rethrow_exception(plan_err);
     if (plan->ready && plan->ready_stream != stream) TFX_HIP(hipStreamWaitEvent(stream, plan->ready, 0));   // spectrum computed on another stream
+    if (tail && plan->tail->ready && plan->tail->ready_stream != stream) TFX_HIP(hipStreamWaitEvent(stream, plan->tail->ready, 0));
     g.nframes = C * g.F; g.N2 = plan->N2;
     g.P2 = g.N2;
     g.nt = 3;
@@ -477,8 +502,19 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
         g.nf_pair = (int *)scratch("olsn_nf_pair", (size_t)C * sizeof(int), stream);
         TFX_HIP(hipMemsetAsync(g.nf_pair, 0, (size_t)C * sizeof(int), stream));
     }
-    if (g.ep_stat >= 0)                   // every (frame, column block) slot is written by exactly one workgroup
-        g.ep_partial = (double *)scratch("olsn_ep_partial", (size_t)(g.nframes * (g.N2 / OLS_CB)) * sizeof(double), stream);
+    // tail geometry: one frame per row from t0 on; tail frames of neighbouring rows pair up, the cascade pass keeps the two
+    // rows of such a pair apart like it does for any pair that straddles rows
+    OlsGeom gt = g;
+    if (tail) {
+        gt.t0 = g.F * g.S; gt.S = r.tail_S; gt.F = 1; gt.nframes = C; gt.N2 = plan->tail->N2; gt.P2 = gt.N2;
+    }
+    const int64_t npairs_t = tail ? ceil_div(C, 2) : 0;
+    g.ep_row = g.F * (g.N2 / OLS_CB) + (tail ? gt.N2 / OLS_CB : 0);
+    gt.ep_row = g.ep_row;
+    if (g.ep_stat >= 0) {                 // every (frame, column block) slot is written by exactly one workgroup
+        g.ep_partial = (double *)scratch("olsn_ep_partial", (size_t)(C * g.ep_row) * sizeof(double), stream);
+        gt.ep_partial = g.ep_partial + g.F * (g.N2 / OLS_CB);       // a row's tail partials sit behind its main frames'
+    }
     // Slab = the frame pairs one A / B / C launch triple covers; slabs rotate over `nlanes` internal streams, each with its own
     // workspace.  Rounds 1-2 sized slabs for launch efficiency (1 GB: few, large launches).  Round 3 measured the other
     // regime: when the LIVE workspace (slab x lanes) fits the 256 MB Infinity Cache with room for the streaming signal, passes
@@ -534,20 +570,20 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
         if (slab <= 8) { (void)scratch(lane_tags[got], bytes, stream); break; }          // throws with the allocator's name in the message
         slab = std::max<int64_t>(8, slab / 2);
     }
+    cpx *Ttail = tail ? (cpx *)scratch("olsn_Ttail", (size_t)npairs_t * OLS_N1 * (size_t)gt.P2 * sizeof(cpx), stream) : nullptr;   // a slab of its own
     const size_t shm_col = OLS_SHM_COL;
     const size_t shm_row = (size_t)(g.N2 * 5) * sizeof(cpx);
     // XCD-aware row map (1) pays when a slab holds many pairs per spectrum row; with cache-sized slabs the plain map is faster
     const int rowmap = slab >= 32 ? 1 : 0;
-    const row_t rowk = row_tab[rowmap];
     const bool row_r4 = env_i64("TFX_OLS_ROW_R4", 0) != 0;        // radix-4 row passes for N2 = 256 / 1024 (cross-check)
     ols_set_attributes(dev);
-    const int ncb = g.N2 / OLS_CB;
     SosFuse sosk{};
     bool sos_unit = false;
     if (sosf) {
         TFX_CHECK((g.N2 == 4096 || g.N2 == 8192) && !hist && sosf->K >= 1 && sosf->K <= SOSF_MAXK && sosf->warm >= 0,
                   "olsnative_forward: the cascade cannot run inside the column pass here (olsnative_sos_supported)");
-        g.nf_flag = (int *)scratch("olsn_nf_flag", (size_t)g.nframes * sizeof(int), stream);
+        g.nf_flag = (int *)scratch("olsn_nf_flag", (size_t)(g.nframes + (tail ? C : 0)) * sizeof(int), stream);
+        gt.nf_flag = g.nf_flag + g.nframes;
         sos_unit = sos_unit_rows(sosf->sos, sosf->K, sosk.co);
         for (int64_t s = 0; s < sosf->K && !sos_unit; ++s) {
             const double *co = sosf->sos + 6 * s;                 // b0 b1 b2 a0 a1 a2; a0 is not used (iir_cpu.cpp:86)
@@ -572,12 +608,10 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
         TFX_HIP(hipEventRecord(ev_fork, user_stream));
         for (int i = 0; i < nlanes; ++i) TFX_HIP(hipStreamWaitEvent(lane_stream[i], ev_fork, 0));
     }
-    int64_t slab_idx = 0;
-    for (int64_t p0 = 0; p0 < npairs; p0 += slab, ++slab_idx) {
-        const int64_t np = (npairs - p0 < slab) ? (npairs - p0) : slab;
-        const int ln = nlanes > 1 ? (int)(slab_idx % nlanes) : 0;
-        hipStream_t stream = nlanes > 1 ? lane_stream[ln] : user_stream;   // shadows the parameter
-        cpx *T = Tlane[ln];
+    // the A / B / C launch triple of frame pairs [p0, p0 + np) of one geometry
+    auto launch_slab = [&](const OlsGeom &g, const NativePlan *plan, cpx *T, int64_t p0, int64_t np, int rowmap, hipStream_t stream) {
+        const int64_t N = plan->N;
+        const int ncb = g.N2 / OLS_CB;
         if (sosf) {
             ProfScope ps("ols_col_fwd16_sos_kernel", stream);
             hipLaunchKernelGGL(colsos_tab[(sosf->sections ? 1 : 0) + (sos_unit ? 2 : 0)][sosf->K - 1], dim3((unsigned)np), dim3(512), OLS_SHM_SOSF, stream,
@@ -593,7 +627,7 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
             const int64_t nrows = np * OLS_N1;
             ProfScope ps(g.N2 == 4096 ? "ols_row4096_kernel" : g.N2 == 8192 ? "ols_row8192_kernel" : (g.N2 == 1024 && !row_r4 ? "ols_row1024_kernel" : "ols_row_kernel"), stream);
             if (g.N2 == 4096) {
-                hipLaunchKernelGGL(rowk, dim3((unsigned)nrows), dim3(256), (size_t)(4096 + 256 + 512) * sizeof(cpx), stream,
+                hipLaunchKernelGGL(row_tab[rowmap], dim3((unsigned)nrows), dim3(256), (size_t)(4096 + 256 + 512) * sizeof(cpx), stream,
                                    T, plan->Hp, plan->tw256, plan->t4lo, plan->t4hi, plan->tlo, plan->thi, plan->tu,
                                    N - 1, g.P2, np);
             } else if (g.N2 == 8192) {
@@ -624,6 +658,15 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
                                T, y, plan->tw256, g, 2 * p0);
             TFX_HIP(hipGetLastError());
         }
+    };
+    // The tail frames go first, on the CALLER'S stream, which idles between the fork and the join (a fourth lane would be a
+    // fifth hardware queue): their few pass-A workgroups are resident together with the main geometry's (64 x 15 frames: 32 +
+    // 448 of 512 slots, one round as before), half as long, and their B and C run beside the lanes' pass A.
+    if (tail) launch_slab(gt, plan->tail.get(), Ttail, 0, npairs_t, npairs_t >= 32 ? 1 : 0, user_stream);
+    int64_t slab_idx = 0;
+    for (int64_t p0 = 0; p0 < npairs; p0 += slab, ++slab_idx) {
+        const int ln = nlanes > 1 ? (int)(slab_idx % nlanes) : 0;
+        launch_slab(g, plan.get(), Tlane[ln], p0, std::min(npairs - p0, slab), rowmap, nlanes > 1 ? lane_stream[ln] : user_stream);
     }
     if (nlanes > 1) {
         std::lock_guard<std::mutex> jl(lane_mu);
@@ -635,7 +678,7 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
     if (sosf) {                           // non-finite values stay in a recursion: see ols_sos_nonfinite_fix_kernel
         const unsigned chunks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, g.Tout >> 16));
         hipLaunchKernelGGL(ols_sos_nonfinite_fix_kernel, dim3((unsigned)C, chunks, (unsigned)(1 + (sosf->sections ? sosf->K : 0))), dim3(256), 0,
-                           user_stream, y, sosf->sections, g, sosk.warm_blocks);
+                           user_stream, y, sosf->sections, g, sosk.warm_blocks, gt, tail ? 1 : 0);
         TFX_HIP(hipGetLastError());
     }
     if (g.nf_pair) {
@@ -644,8 +687,7 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
         TFX_HIP(hipGetLastError());
     }
     if (g.ep_stat >= 0)                   // after the join: all partials are in
-        stat_finish(g.ep_partial, ep->per_row ? C : 1, (ep->per_row ? g.F : g.nframes) * (g.N2 / OLS_CB), g.ep_stat,
-                    ep->stat_out, user_stream);
+        stat_finish(g.ep_partial, ep->per_row ? C : 1, (ep->per_row ? 1 : C) * g.ep_row, g.ep_stat, ep->stat_out, user_stream);
 }
 
 }  // namespace tfx

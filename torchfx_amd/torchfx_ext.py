@@ -329,14 +329,16 @@ def sos_fft_conv_supported(T: int, sos, taps: int, padding: tuple[int, int] = (0
 
 def sos_fft_conv_plan_info(T: int, sos, taps: int, padding: tuple[int, int] = (0, 0), force_block: int = 0) -> dict | None:
     """Block length ``N``, hop ``S``, frames per row ``F`` and warm-up samples of :func:`sos_fft_conv_forward` for rows of
-    ``T`` samples, or None where it does not serve the geometry (``tfx_sos_fft_conv_plan_info``; host-only)."""
+    ``T`` samples, or None where it does not serve the geometry (``tfx_sos_fft_conv_plan_info2``; host-only).  ``tail_N`` /
+    ``tail_S``: block and hop of the row's last frame where it runs at a smaller block than the ``F - 1`` before it, else 0."""
     s = np.ascontiguousarray(_coeff(sos).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 6)
-    n, h, f, w = (ctypes.c_int64(0) for _ in range(4))
-    ok = L.load().tfx_sos_fft_conv_plan_info(ctypes.c_int64(int(T)), s.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+    n, h, f, w, tn, ts = (ctypes.c_int64(0) for _ in range(6))
+    ok = L.load().tfx_sos_fft_conv_plan_info2(ctypes.c_int64(int(T)), s.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                                              ctypes.c_int64(s.shape[0]), ctypes.c_int64(int(taps)), ctypes.c_int64(int(padding[0])),
                                              ctypes.c_int64(int(padding[1])), ctypes.c_int(int(force_block)), ctypes.byref(n),
-                                             ctypes.byref(h), ctypes.byref(f), ctypes.byref(w))
-    return {"N": n.value, "S": h.value, "F": f.value, "warmup": w.value, "workspace_bytes_held": workspace_bytes()} if ok else None
+                                             ctypes.byref(h), ctypes.byref(f), ctypes.byref(w), ctypes.byref(tn), ctypes.byref(ts))
+    return {"N": n.value, "S": h.value, "F": f.value, "warmup": w.value, "tail_N": tn.value, "tail_S": ts.value,
+            "workspace_bytes_held": workspace_bytes()} if ok else None
 
 
 def clear_caches() -> None:
