@@ -61,6 +61,14 @@ def rnd(shape, seed, dtype=np.float32):
     return (x / np.abs(x).max()).astype(dtype)
 
 
+def allpass_sos(K, seed=5):
+    """K all-pass sections (|H| = 1: nothing decays, so the host finds no warm-up length and rows run as one segment)."""
+    rng = np.random.default_rng(seed)
+    r, th = rng.uniform(0.3, 0.9, K), rng.uniform(0.2, 2.9, K)
+    a1, a2 = -2 * r * np.cos(th), r * r
+    return np.stack([a2, a1, np.ones(K), np.ones(K), a1, a2], axis=1)
+
+
 def reverb_ir(K=65536):
     ir = np.random.default_rng(0).standard_normal(K) * np.exp(-np.arange(K) / 8000.0)
     return (ir / np.abs(ir).sum()).astype(np.float32)

@@ -8,7 +8,7 @@ import pytest
 import scipy.signal as ss
 import torch
 
-from tests.gpu_common import DEV, TOL_IIR_F32OUT, TOL_IIR_F64OUT, close, dev
+from tests.gpu_common import DEV, TOL_IIR_F32OUT, TOL_IIR_F64OUT, allpass_sos, close, dev, rnd
 
 pytestmark = pytest.mark.gpu
 
@@ -56,7 +56,7 @@ def ref(sos, x, **kw):
 
 
 def check(name, x, what, **kw):
-    sos = sos_of(name)
+    sos = sos_of(name) if isinstance(name, str) else name          # a filter of the grid, or the coefficients themselves
     y = fx().sosfiltfilt(dev(x), sos, **kw)
     assert y.is_cuda and y.shape == x.shape and y.dtype == dev(x).dtype
     exp = ref(sos, x, **kw)
@@ -107,6 +107,17 @@ def test_dc_offset_pins_the_start_states(dtype):
     for shape in [(2, 20_000), (4, 600_000)]:
         x = (0.8 + 0.01 * np.random.default_rng(3).standard_normal(shape)).astype(dtype)
         check("lo_butter40_o8", x, f"dc offset {shape} {dtype.__name__}")
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_a_long_cascade_leaves_room_for_one_workgroup_per_cu(dtype):
+    """100 all-pass sections: from 81 sections on the carry takes so much LDS that one workgroup fits a CU instead of two,
+    and the segment plan and the launch both count on one."""
+    from torchfx_amd import torchfx_ext
+    sos = allpass_sos(100)
+    info = torchfx_ext.sos_filtfilt_plan_info(sos, 2, 20_000)
+    assert info["warmup"] == -1 and info["nseg_forward"] == info["nseg_reverse"] == 1, info
+    check(sos, rnd((2, 20_000), 9, dtype), f"100 all-pass sections {dtype.__name__}")
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])

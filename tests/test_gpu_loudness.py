@@ -21,7 +21,7 @@ import pytest
 import torch
 
 from tests import loudness_reference as R
-from tests.gpu_common import DEV, TOL_IIR_F64OUT
+from tests.gpu_common import DEV, TOL_IIR_F64OUT, allpass_sos, rnd
 
 pytestmark = pytest.mark.gpu
 
@@ -220,6 +220,19 @@ def test_a_general_cascade_and_block_length(refs, dtype, monkeypatch):
     check_energy(ext().sos_block_energy(dev(ref.x), sos, 1000, 3), s_ref, bar, "butter8, 1000/3, forced segments")
     with pytest.raises(RuntimeError, match="shorter than 64"):
         ext().sos_block_energy(dev(ref.x), sos, 191, 3)
+
+
+def test_a_cascade_whose_carry_needs_more_than_64_kb_of_lds():
+    """256 all-pass sections on a float32 signal, blocks of 1000 / 3 samples: from 209 sections on the launch asks for more
+    dynamic LDS than a kernel gets without raising its limit first."""
+    sos = allpass_sos(256)
+    x = rnd((2, 20_000), 9, np.float32)
+    assert ext().sos_block_energy_plan_info(sos, 2, x.shape[-1], 1000, 3)["nseg"] == 1          # nothing decays: no segments
+    y = R.filtered(x, sos)
+    e = R.edges(x.shape[-1], 1000, 3)
+    s_ref = R.block_energy(x, sos, 1000, 3, y=y)
+    assert s_ref.shape == (2, 60) and np.isfinite(s_ref).all()
+    check_energy(ext().sos_block_energy(dev(x), sos, 1000, 3), s_ref, energy_bar(y, s_ref, e), "256 all-pass sections, 1000/3")
 
 
 def test_deterministic_and_independent_of_the_other_rows(refs, monkeypatch):

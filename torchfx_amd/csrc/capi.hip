@@ -4,6 +4,7 @@
 #include "common.h"
 #include "epilogue.h"
 #include "ols_route.h"
+#include "sos.h"
 #include "../../include/torchfx_hip.h"
 
 #include <atomic>
@@ -14,30 +15,10 @@
 
 namespace tfx {
 
-// implemented in sos.hip / fir.hip (the overlap-save entry points: ols_route.h)
-void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C, int64_t T,
-                 const double *sos_host, int64_t K, const double *sx_in, const double *sy_in,
-                 double *sx_out, double *sy_out, void *y_sections, int precision, hipStream_t stream, int64_t NB = 1,
-                 bool sum_bands = false, const Epilogue *ep = nullptr);
-void sos_plan_info(const double *sos_host, int64_t K, int *precision, int64_t *warmup, double *err_bound);
-void sos_filtfilt_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C, int64_t T, const double *sos_host, int64_t K,
-                          int padtype, int64_t padlen, double *work, hipStream_t stream);
-void sos_filtfilt_plan_info(int64_t C, int64_t T, const double *sos_host, int64_t K, int padtype, int64_t padlen,
-                            int64_t *default_padlen, int64_t *padlen_used, int64_t *work_elems, int64_t *warmup,
-                            int *nseg_forward, int *nseg_reverse);
-void sos_block_energy_forward(const void *x, int x_dtype, double *s, int64_t C, int64_t T, const double *sos_host, int64_t K,
-                              int64_t num, int64_t den, hipStream_t stream);
-void sos_block_energy_plan_info(int64_t C, int64_t T, const double *sos_host, int64_t K, int64_t num, int64_t den,
-                                int64_t *nblk, int *nseg, int64_t *warm);
-void sos_clear_plans();
+// implemented in fir.hip (the cascade's entry points: sos.h; the overlap-save entry points: ols_route.h)
 void fir_direct_forward(const void *x, void *y, int dtype, int64_t C, int64_t T,
                         const void *kernel_host, int64_t K, hipStream_t stream, const void *hist = nullptr, int64_t H = 0);
 void quantile_abs_forward(const float *x, int64_t n, double q, double *out_dev, hipStream_t stream);
-bool chunk_supported(int64_t C, int64_t T, int64_t K, int64_t Kf);
-void chunk_forward(const float *x, int64_t x_pitch, float *y, int64_t C, int64_t T, const double *sos_host, int64_t K,
-                   const double *sx_in, const double *sy_in, double *sx_out, double *sy_out,
-                   const float *taps_host, int64_t Kf, const float *hist_in, float *hist_out,
-                   double gain, int scale, int clamp, int precision, hipStream_t stream);
 void fir_hist_update(const void *x, const void *hist_in, void *hist_out, int dtype, int64_t C, int64_t T, int64_t H,
                      hipStream_t stream);
 void fir_clear();

@@ -15,6 +15,7 @@
 #include "epilogue.h"
 #include "ols_route.h"
 #include "plan_cache.h"
+#include "sos.h"
 #include "../../include/torchfx_hip.h"
 
 #include <rocfft/rocfft.h>
@@ -28,8 +29,6 @@
 #include <vector>
 
 namespace tfx {
-
-int64_t sos_warmup_bits(const double *sos_host, int64_t K, int bits);      // sos.hip
 
 #define TFX_ROCFFT(expr)                                                                     \
     do {                                                                                     \

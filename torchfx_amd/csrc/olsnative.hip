@@ -34,6 +34,7 @@
 #include "ols_kernels.h"
 #include "ols_route.h"
 #include "plan_cache.h"
+#include "sos.h"
 #include "../../include/torchfx_hip.h"
 
 #include <algorithm>
@@ -406,7 +407,6 @@ bool olsnative_supported(int64_t K, int64_t L, int64_t *N_out)
     return true;
 }
 
-bool sos_unit_rows(const double *sos_host, int64_t K, double (*rows)[5]);     // sos.hip
 static_assert(SOSF_MAXK == OLS_SOS_MAXK, "the cascade route (fftconv.hip) admits the sections the column pass holds");
 
 // 128-byte aligned frames (rows themselves aligned): prepend `lead` zeros to the flipped taps so that the left padding

@@ -29,6 +29,7 @@
 #include "common.h"
 #include "epilogue.h"
 #include "plan_cache.h"
+#include "sos.h"
 #include "../../include/torchfx_hip.h"
 
 #include <cmath>
@@ -191,10 +192,7 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
     constexpr int STAGE_B = 64 * CHUNK_B;
     constexpr int TILE = 64 * LC;
     constexpr int TS = tab_stride(LC);
-#ifndef TFX_SB
-#define TFX_SB 4
-#endif
-    constexpr int SB = TFX_SB;          // scheduling-barrier period (samples)
+    constexpr int SB = 4;               // scheduling-barrier period (samples)
     constexpr int EI = 16 / sizeof(TSt), NUI = LC / EI;   // elems per 16 B, units per lane (in)
     constexpr int EO = 16 / sizeof(TOut), NUO = LC / EO;  // (out)
 
@@ -716,15 +714,15 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
     }
 }
 
-// bytes of LDS one stream needs: the transposition stage plus the carry (4 values per band and section, 2 x LC capture scratch)
+// Bytes of LDS one stream (wavefront) needs, as sos_stream_body lays them out: the transposition stage (64 padded per-lane chunks
+// of the wider of the two signal types) plus the carry (4 values per band and section, 2 x LC capture scratch), rounded to 16.
+// Every launch sizes its dynamic LDS with this and the kernels place wave w at w times it: if the two disagreed, the carry of
+// one wave would overwrite the stage of the next.
 template <typename TIn, typename TOut, typename TC, int LC>
-__host__ __device__ constexpr int sos_stage_bytes()
+__host__ __device__ constexpr int sos_wave_lds_bytes(int nbl, int K)
 {
-    return 64 * (LC * (int)(sizeof(TIn) > sizeof(TOut) ? sizeof(TIn) : sizeof(TOut)) + 16);
-}
-template <typename TC, int LC> __host__ __device__ inline int sos_carry_bytes(int nbl, int K)
-{
-    return (((nbl * K * 4 + 2 * LC) * (int)sizeof(TC)) + 15) & ~15;
+    return 64 * (LC * (int)(sizeof(TIn) > sizeof(TOut) ? sizeof(TIn) : sizeof(TOut)) + 16) +
+           ((((nbl * K * 4 + 2 * LC) * (int)sizeof(TC)) + 15) & ~15);
 }
 
 template <typename TIn, typename TOut, typename TC, int LC, bool VEC, bool TAPS, bool PF, int MINW, bool SUMB = false, bool EPI = false, bool UNIT = false, int FF = 0, bool FFR = false, bool MEAS = false>
@@ -733,7 +731,7 @@ __global__ void __launch_bounds__(256, MINW) sos_stream_kernel(const SosParams p
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // provably wave-uniform -> SGPR addressing
-    const int per_wave = sos_stage_bytes<TIn, TOut, TC, LC>() + sos_carry_bytes<TC, LC>(SUMB ? p.nsum : 1, p.K);
+    const int per_wave = sos_wave_lds_bytes<TIn, TOut, TC, LC>(SUMB ? p.nsum : 1, p.K);
     sos_stream_body<TIn, TOut, TC, LC, VEC, TAPS, PF, SUMB, EPI, UNIT, FF, FFR, MEAS>(p, (int64_t)blockIdx.x * 4 + wave, smem + wave * per_wave, lane);
 }
 
@@ -749,18 +747,24 @@ __global__ void __launch_bounds__(256, MINW) sos_stream_kernel(const SosParams p
 // and exit.  (Folding this into the main launch -- last workgroup to finish, device-scope fences -- was measured:
 // the per-workgroup release fence writes back the XCD's L2 and the cfg-2 kernel went from 0.29-0.33 to 0.46-0.52 ms.)
 //   y rows = C (output rows); state rows = st_rows with row c owning {b * C_in + c} for b < nbl in sum mode.
+// The first segment of `row` whose stream left its flag set, p.nseg if none did.  Called by every thread of the workgroup.
+__device__ __forceinline__ int first_flagged_segment(const SosParams &p, int64_t row)
+{
+    __shared__ int sh_first;
+    if (threadIdx.x == 0) sh_first = p.nseg;
+    __syncthreads();
+    for (int q = threadIdx.x; q < p.nseg; q += blockDim.x)
+        if (p.nf_flag[row * p.nseg + q]) atomicMin(&sh_first, q);
+    __syncthreads();
+    return sh_first;
+}
+
 template <typename TOut>
 __global__ void __launch_bounds__(256) sos_nonfinite_fix_kernel(const SosParams p, int nbl, int64_t st_rows)
 {
-    __shared__ int sh_first;
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int64_t T = p.T, row = blockIdx.x;
-    if (tid == 0) sh_first = p.nseg;
-    __syncthreads();
-    for (int q = tid; q < p.nseg; q += nthr)
-        if (p.nf_flag[row * p.nseg + q]) atomicMin(&sh_first, q);
-    __syncthreads();
-    const int g0 = sh_first;
+    const int g0 = first_flagged_segment(p, row);
     if (g0 >= p.nseg - 1) return;                                // clean row, or only the last segment is bad (it poisons itself)
     const int64_t begin = (int64_t)(g0 + 1) * p.seg_len + p.warm;   // first sample segment g0 + 1 stores
     if (begin >= T) return;
@@ -788,15 +792,9 @@ __global__ void __launch_bounds__(256) sos_nonfinite_fix_kernel(const SosParams 
 // The same repair for the measuring pass: the blocks of the segments after the row's first flagged one become NaN.
 __global__ void __launch_bounds__(256) sos_block_energy_fix_kernel(const SosParams p)
 {
-    __shared__ int sh_first;
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int64_t row = blockIdx.x;
-    if (tid == 0) sh_first = p.nseg;
-    __syncthreads();
-    for (int q = tid; q < p.nseg; q += nthr)
-        if (p.nf_flag[row * p.nseg + q]) atomicMin(&sh_first, q);
-    __syncthreads();
-    const int g0 = sh_first;
+    const int g0 = first_flagged_segment(p, row);
     if (g0 >= p.nseg - 1) return;
     double *s = (double *)p.y + row * p.ms_nblk;
     for (int64_t b = (int64_t)(g0 + 1) * p.ms_bps + tid; b < p.ms_nblk; b += nthr) s[b] = __builtin_nan("");
@@ -810,11 +808,10 @@ typedef long double ld;
 struct SosPlan {
     int K = 0;          // sections per band
     int NB = 1;         // bands (filter-bank mode: independent SOS sets sharing the input)
-    int nsteps32 = 6, nsteps16 = 6, nsteps64 = 6;
     int64_t warm = -1;            // samples; -1 = too long / not decaying
     double err_bound_f32 = -1.0;  // worst-case |err| of f32 arithmetic for |x| <= 1 (lazy)
-    std::unique_ptr<DeviceBuffer> tab_f64_lc32, tab_f32_lc32, tab_f64_lc16, tab_f32_lc16, tab_f64_lc64, tab_f32_lc64;   // lazy
-    std::unique_ptr<DeviceBuffer> tab_f64_lc64_unit;     // unit-b0 form (fill_tables)
+    struct Table { std::unique_ptr<DeviceBuffer> buf; int nsteps = 6; };
+    Table tab[2][3][2];           // [float32 / float64][LC = 16 / 32 / 64][plain / unit-b0 form (fill_tables)], lazy: table_for
     std::unique_ptr<DeviceBuffer> ff_gain;               // zero-phase passes: the K + 1 cumulative DC gains (filtfilt_gains), lazy
     int unit_ok = -1;                    // the cascade has a unit-b0 form (lazy)
     std::vector<double> sos;
@@ -972,8 +969,6 @@ static void fill_tables(const std::vector<double> &sos, int K, int LC, std::vect
 // samples per cascade (a millisecond, once per plan) against the sequential float64 recursion, and the
 // largest difference is scaled by 2.5 (device runs of 4.6e7 samples per cascade measure 0.54 .. 1.02 of twice the
 // replayed error over five orders of magnitude of it, tools/iir_f32_calibrate.py).
-template <typename TC> static void fill_tables(const std::vector<double> &sos, int K, int LC, std::vector<TC> &out, int &nsteps, bool unit);
-
 static double f32_error_bound(const std::vector<double> &sos, int K)
 {
     constexpr int LC = 32, TILE = 64 * LC;
@@ -1111,21 +1106,40 @@ static std::shared_ptr<SosPlan> get_plan(const double *sos_host, int64_t K, hipS
     });
 }
 
-template <typename TC>
-static void *ensure_table(SosPlan *pl, std::unique_ptr<DeviceBuffer> *slot, int LC, int *nsteps, hipStream_t stream, bool unit = false)
+static bool plan_unit_ok(SosPlan *pl)
 {
     std::lock_guard<std::mutex> lk(g_plan_mu);
-    if (!*slot) {
-        std::vector<TC> h;
-        for (int b = 0; b < pl->NB; ++b) {
-            std::vector<double> one(pl->sos.begin() + (size_t)b * pl->K * 6, pl->sos.begin() + (size_t)(b + 1) * pl->K * 6);
-            std::vector<TC> hb;
-            fill_tables<TC>(one, pl->K, LC, hb, *nsteps, unit);
-            h.insert(h.end(), hb.begin(), hb.end());
-        }
-        *slot = std::make_unique<DeviceBuffer>(h);      // synchronous copy from a temporary: once per distinct filter
+    if (pl->unit_ok < 0) {
+        bool ok = true;
+        for (int b = 0; b < pl->NB && ok; ++b)
+            ok = unit_form_ok(std::vector<double>(pl->sos.begin() + (size_t)b * pl->K * 6, pl->sos.begin() + (size_t)(b + 1) * pl->K * 6), pl->K);
+        pl->unit_ok = ok ? 1 : 0;
     }
-    return (*slot)->p;
+    return pl->unit_ok != 0;
+}
+
+template <typename TC> static void build_table(SosPlan *pl, int LC, bool unit, SosPlan::Table &t)
+{
+    std::vector<TC> h;
+    for (int b = 0; b < pl->NB; ++b) {
+        std::vector<double> one(pl->sos.begin() + (size_t)b * pl->K * 6, pl->sos.begin() + (size_t)(b + 1) * pl->K * 6);
+        std::vector<TC> hb;
+        fill_tables<TC>(one, pl->K, LC, hb, t.nsteps, unit);
+        h.insert(h.end(), hb.begin(), hb.end());
+    }
+    t.buf = std::make_unique<DeviceBuffer>(h);          // synchronous copy from a temporary: once per distinct filter
+}
+// The one way to a plan's device tables: sets p.tab / p.nsteps / p.unit for the arithmetic type, the tile size LC (16, 32, 64)
+// and the form, building the table on first use.  Every (type, LC, form) has a table of its own.
+static void table_for(SosParams &p, SosPlan *pl, bool f32, int LC, bool unit = false)
+{
+    std::lock_guard<std::mutex> lk(g_plan_mu);
+    SosPlan::Table &t = pl->tab[f32 ? 0 : 1][LC == 16 ? 0 : (LC == 32 ? 1 : 2)][unit ? 1 : 0];
+    if (!t.buf) {
+        if (f32) build_table<float>(pl, LC, unit, t);
+        else build_table<double>(pl, LC, unit, t);
+    }
+    p.tab = t.buf->p; p.nsteps = t.nsteps; p.unit = unit ? 1 : 0;
 }
 
 void sos_clear_plans() { g_plans.clear(); }
@@ -1185,48 +1199,52 @@ static void plan_segments(SosParams &p, int64_t plan_warm, int TILE, int residen
 constexpr int FF_LC = 32;
 static size_t ff_shmem(int K)
 {
-    return 4 * (size_t)(sos_stage_bytes<double, double, double, FF_LC>() + sos_carry_bytes<double, FF_LC>(1, K));
+    return 4 * (size_t)sos_wave_lds_bytes<double, double, double, FF_LC>(1, K);      // float32 at either end: the same, the stage holds the wider type
 }
 static int ff_blocks_per_cu(int K) { return 2 * ff_shmem(K) <= 160 * 1024 ? 2 : 1; }
 
-template <typename TIn, typename TOut, typename TC, int LC, bool VEC, bool TAPS, bool PF, int MINW, bool SUMB = false, bool EPI = false, bool UNIT = false, int FF = 0, bool FFR = false>
+// The one launch of the cascade kernel: LDS size, segmentation, flag scratch, the launch and the repair launch behind it.
+// MEAS: the measuring pass arrives with its segmentation decided (block_energy_plan: nseg, warm, ms_bps; fair_nw = 2), so the
+// occupancy query and plan_segments are not for it.
+template <typename TIn, typename TOut, typename TC, int LC, bool VEC, bool TAPS, bool PF, int MINW, bool SUMB = false, bool EPI = false, bool UNIT = false, int FF = 0, bool FFR = false, bool MEAS = false>
 static void launch_one(SosParams p, int64_t plan_warm, hipStream_t stream)
 {
-    constexpr int IOB = sizeof(TIn) > sizeof(TOut) ? sizeof(TIn) : sizeof(TOut);
-    constexpr int STAGE_B = 64 * (LC * IOB + 16);
     const int nbl = SUMB ? p.nsum : 1;
-    const int carry_b = (((nbl * p.K * 4 + 2 * LC) * (int)sizeof(TC)) + 15) & ~15;
-    const size_t shmem = 4 * (size_t)(STAGE_B + carry_b);
-    TFX_CHECK(shmem <= 160 * 1024, "sos_forward: %d band(s) x K=%d need %zu B of LDS (max 163840)", nbl, p.K, shmem);
-    auto kern = sos_stream_kernel<TIn, TOut, TC, LC, VEC, TAPS, PF, MINW, SUMB, EPI, UNIT, FF, FFR>;
+    const size_t shmem = 4 * (size_t)sos_wave_lds_bytes<TIn, TOut, TC, LC>(nbl, p.K);
+    if constexpr (MEAS) TFX_CHECK(shmem <= 160 * 1024, "sos_block_energy: K=%d needs %zu B of LDS (max 163840)", p.K, shmem);
+    else TFX_CHECK(shmem <= 160 * 1024, "sos_forward: %d band(s) x K=%d need %zu B of LDS (max 163840)", nbl, p.K, shmem);
+    auto kern = sos_stream_kernel<TIn, TOut, TC, LC, VEC, TAPS, PF, MINW, SUMB, EPI, UNIT, FF, FFR, MEAS>;
     if (!EPI) p.ep_stat = -1;                      // the plain instantiation has no epilogue code
     if (shmem > 64 * 1024)
         TFX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    static int blocks_per_cu_tab[TFX_MAX_DEVICES] = {0};     // per template instance and device
-    static size_t blocks_shmem_tab[TFX_MAX_DEVICES] = {0};
-    const int dev = current_device();
-    int &blocks_per_cu = blocks_per_cu_tab[dev];
-    size_t &blocks_shmem = blocks_shmem_tab[dev];
-    if constexpr (FF != 0) {
-        // the plan query's assumption, checked once per instance, device and LDS size against what the runtime can hold
-        if (!blocks_per_cu || blocks_shmem != shmem) {
+    if constexpr (!MEAS) {
+        static int blocks_per_cu_tab[TFX_MAX_DEVICES] = {0};     // per template instance and device
+        static size_t blocks_shmem_tab[TFX_MAX_DEVICES] = {0};
+        const int dev = current_device();
+        int &blocks_per_cu = blocks_per_cu_tab[dev];
+        size_t &blocks_shmem = blocks_shmem_tab[dev];
+        if constexpr (FF != 0) {
+            // the plan query's assumption, checked once per instance, device and LDS size against what the runtime can hold
+            if (!blocks_per_cu || blocks_shmem != shmem) {
+                int nb = 0;
+                TFX_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, 256, shmem) == hipSuccess &&
+                          nb >= ff_blocks_per_cu(p.K), "sos_filtfilt: %d workgroup(s) per CU fit, the segment plan counts on %d", nb,
+                          ff_blocks_per_cu(p.K));
+                blocks_shmem = shmem;
+            }
+            blocks_per_cu = ff_blocks_per_cu(p.K);
+        } else if (!blocks_per_cu || blocks_shmem != shmem) {
             int nb = 0;
-            TFX_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, 256, shmem) == hipSuccess &&
-                      nb >= ff_blocks_per_cu(p.K), "sos_filtfilt: %d workgroup(s) per CU fit, the segment plan counts on %d", nb,
-                      ff_blocks_per_cu(p.K));
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, 256, shmem) != hipSuccess || nb < 1) nb = 1;
+            blocks_per_cu = nb;
             blocks_shmem = shmem;
         }
-        blocks_per_cu = ff_blocks_per_cu(p.K);
-    } else if (!blocks_per_cu || blocks_shmem != shmem) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, 256, shmem) != hipSuccess || nb < 1) nb = 1;
-        blocks_per_cu = nb;
-        blocks_shmem = shmem;
+        plan_segments(p, plan_warm, 64 * LC, blocks_per_cu * 4);
+        p.fair_nw = blocks_per_cu < 2 ? 1 : (blocks_per_cu > 4 ? 4 : blocks_per_cu);      // one wave of every resident workgroup per SIMD
+        if (p.fair_nw < 2) p.fair = 0;
     }
-    plan_segments(p, plan_warm, 64 * LC, blocks_per_cu * 4);
-    p.fair_nw = blocks_per_cu < 2 ? 1 : (blocks_per_cu > 4 ? 4 : blocks_per_cu);      // one wave of every resident workgroup per SIMD
-    if (p.fair_nw < 2) p.fair = 0;
     const int64_t nstreams = p.C * p.nseg;
+    if constexpr (MEAS) TFX_CHECK(nstreams <= INT32_MAX, "sos_block_energy: %lld streams are too many for one launch", (long long)nstreams);
     const unsigned grid = (unsigned)ceil_div(nstreams, 4);
     if (p.ep_stat >= 0) {                  // streams that have nothing to store leave their (zeroed) slot alone
         p.ep_partial = (double *)scratch("sos_ep_partial", (size_t)nstreams * sizeof(double), stream);
@@ -1236,18 +1254,19 @@ static void launch_one(SosParams p, int64_t plan_warm, hipStream_t stream)
     if (p.nseg > 1)                        // see sos_nonfinite_fix_kernel: every stream writes its slot, no memset needed
         p.nf_flag = (int *)scratch("sos_nf_flag", (size_t)nstreams * sizeof(int), stream);
     {
-        ProfScope ps(FF == 1 ? "sos_filtfilt_forward_kernel" : FF == 2 ? "sos_filtfilt_reverse_kernel"
+        ProfScope ps(MEAS ? "sos_block_energy_kernel" : FF == 1 ? "sos_filtfilt_forward_kernel" : FF == 2 ? "sos_filtfilt_reverse_kernel"
                      : sizeof(TC) == 8 ? "sos_stream_kernel<f64>" : "sos_stream_kernel<f32>", stream);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shmem, stream, p);
         TFX_HIP(hipGetLastError());
     }
     if (p.nseg > 1) {                      // ~2 us on cfg 2 (measured by leaving it out)
         const auto fix = [&] {
-            hipLaunchKernelGGL(sos_nonfinite_fix_kernel<TOut>, dim3((unsigned)p.C), dim3(256), 0, stream, p, nbl, SUMB ? p.C_in * nbl : p.C);
+            if constexpr (MEAS) hipLaunchKernelGGL(sos_block_energy_fix_kernel, dim3((unsigned)p.C), dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL(sos_nonfinite_fix_kernel<TOut>, dim3((unsigned)p.C), dim3(256), 0, stream, p, nbl, SUMB ? p.C_in * nbl : p.C);
             TFX_HIP(hipGetLastError());
         };
-        if constexpr (FF != 0) {           // the zero-phase profile names every launch of the call
-            ProfScope ps("sos_nonfinite_fix_kernel", stream);
+        if constexpr (MEAS || FF != 0) {   // the zero-phase and measuring profiles name every launch of the call
+            ProfScope ps(MEAS ? "sos_block_energy_fix_kernel" : "sos_nonfinite_fix_kernel", stream);
             fix();
         } else fix();
     }
@@ -1260,51 +1279,51 @@ static void launch_one(SosParams p, int64_t plan_warm, hipStream_t stream)
 // Variants (TFX_SOS_VARIANT): 0 = LC32, 1 = LC16, 2 = LC32 + register prefetch, 3 = LC16 + prefetch.
 // Register budgets (waves/SIMD) were chosen from -Rpass-analysis so that nothing spills.
 template <typename TIn, typename TOut, typename TC>
-static void launch_main(const SosParams &p, bool vec, int variant, int64_t nstreams, hipStream_t stream)   // nstreams = plan warm-up
+static void launch_main(const SosParams &p, bool vec, int variant, int64_t plan_warm, hipStream_t stream)
 {
     constexpr bool F32 = sizeof(TC) == 4;
     if (p.taps && vec && variant >= 4) {   // the shipping LC = 64 geometry with every section's output tapped (parity tests)
-        launch_one<TIn, TOut, TC, 64, true, true, false, F32 ? 3 : 2>(p, nstreams, stream);
+        launch_one<TIn, TOut, TC, 64, true, true, false, F32 ? 3 : 2>(p, plan_warm, stream);
         return;
     }
     if (p.taps || !vec) {     // debug taps / unaligned rows: plain dword path
         if (variant & 1) {
-            if (p.taps) launch_one<TIn, TOut, TC, 16, false, true, false, F32 ? 5 : 3>(p, nstreams, stream);
-            else launch_one<TIn, TOut, TC, 16, false, false, false, F32 ? 5 : 3>(p, nstreams, stream);
+            if (p.taps) launch_one<TIn, TOut, TC, 16, false, true, false, F32 ? 5 : 3>(p, plan_warm, stream);
+            else launch_one<TIn, TOut, TC, 16, false, false, false, F32 ? 5 : 3>(p, plan_warm, stream);
         } else {
-            if (p.taps) launch_one<TIn, TOut, TC, 32, false, true, false, F32 ? 3 : 2>(p, nstreams, stream);
-            else launch_one<TIn, TOut, TC, 32, false, false, false, F32 ? 3 : 2>(p, nstreams, stream);
+            if (p.taps) launch_one<TIn, TOut, TC, 32, false, true, false, F32 ? 3 : 2>(p, plan_warm, stream);
+            else launch_one<TIn, TOut, TC, 32, false, false, false, F32 ? 3 : 2>(p, plan_warm, stream);
         }
         return;
     }
     if constexpr (!F32) {
         if (p.unit) {          // unit-b0 form of the shipping geometry, plain and with the epilogue (same cascade arithmetic in both)
-            if (p.ep_fused) launch_one<TIn, TOut, TC, 64, true, false, false, 2, false, true, true>(p, nstreams, stream);
-            else launch_one<TIn, TOut, TC, 64, true, false, false, 2, false, false, true>(p, nstreams, stream);
+            if (p.ep_fused) launch_one<TIn, TOut, TC, 64, true, false, false, 2, false, true, true>(p, plan_warm, stream);
+            else launch_one<TIn, TOut, TC, 64, true, false, false, 2, false, false, true>(p, plan_warm, stream);
             return;
         }
     }
     if (p.ep_fused) {          // epilogue instantiation: same tile geometry as the plain kernel (bit-identical cascade output)
-        if (variant >= 4) launch_one<TIn, TOut, TC, 64, true, false, false, F32 ? 3 : 2, false, true>(p, nstreams, stream);
-        else launch_one<TIn, TOut, TC, 32, true, false, true, 2, false, true>(p, nstreams, stream);
+        if (variant >= 4) launch_one<TIn, TOut, TC, 64, true, false, false, F32 ? 3 : 2, false, true>(p, plan_warm, stream);
+        else launch_one<TIn, TOut, TC, 32, true, false, true, 2, false, true>(p, plan_warm, stream);
         return;
     }
     switch (variant) {
-    case 1: launch_one<TIn, TOut, TC, 16, true, false, false, F32 ? 8 : 5>(p, nstreams, stream); break;
-    case 2: launch_one<TIn, TOut, TC, 32, true, false, true, F32 ? 4 : 2>(p, nstreams, stream); break;
-    case 3: launch_one<TIn, TOut, TC, 16, true, false, true, F32 ? 6 : 4>(p, nstreams, stream); break;
-    case 4: launch_one<TIn, TOut, TC, 64, true, false, false, F32 ? 3 : 2>(p, nstreams, stream); break;   // 64 samples per lane: half the scan per sample
-    case 5: launch_one<TIn, TOut, TC, 64, true, false, true, F32 ? 3 : 1>(p, nstreams, stream); break;
-    default: launch_one<TIn, TOut, TC, 32, true, false, false, F32 ? 5 : 3>(p, nstreams, stream); break;
+    case 1: launch_one<TIn, TOut, TC, 16, true, false, false, F32 ? 8 : 5>(p, plan_warm, stream); break;
+    case 2: launch_one<TIn, TOut, TC, 32, true, false, true, F32 ? 4 : 2>(p, plan_warm, stream); break;
+    case 3: launch_one<TIn, TOut, TC, 16, true, false, true, F32 ? 6 : 4>(p, plan_warm, stream); break;
+    case 4: launch_one<TIn, TOut, TC, 64, true, false, false, F32 ? 3 : 2>(p, plan_warm, stream); break;   // 64 samples per lane: half the scan per sample
+    case 5: launch_one<TIn, TOut, TC, 64, true, false, true, F32 ? 3 : 1>(p, plan_warm, stream); break;
+    default: launch_one<TIn, TOut, TC, 32, true, false, false, F32 ? 5 : 3>(p, plan_warm, stream); break;
     }
 }
 // rarely used dtype mixes: one configuration only
 template <typename TIn, typename TOut, typename TC>
-static void launch_rare(const SosParams &p, bool vec, int64_t nstreams, hipStream_t stream)   // nstreams = plan warm-up
+static void launch_rare(const SosParams &p, bool vec, int64_t plan_warm, hipStream_t stream)
 {
-    if (p.taps) launch_one<TIn, TOut, TC, 16, false, true, false, 3>(p, nstreams, stream);
-    else if (vec) launch_one<TIn, TOut, TC, 16, true, false, false, 4>(p, nstreams, stream);
-    else launch_one<TIn, TOut, TC, 16, false, false, false, 3>(p, nstreams, stream);
+    if (p.taps) launch_one<TIn, TOut, TC, 16, false, true, false, 3>(p, plan_warm, stream);
+    else if (vec) launch_one<TIn, TOut, TC, 16, true, false, false, 4>(p, plan_warm, stream);
+    else launch_one<TIn, TOut, TC, 16, false, false, false, 3>(p, plan_warm, stream);
 }
 
 // sum mode: one configuration per dtype mix (LC = 16: the accumulator costs registers)
@@ -1313,6 +1332,31 @@ static void launch_sum(const SosParams &p, bool vec, int64_t plan_warm, hipStrea
 {
     if (vec) launch_one<TIn, TOut, TC, 16, true, false, false, 3, true>(p, plan_warm, stream);
     else launch_one<TIn, TOut, TC, 16, false, false, false, 3, true>(p, plan_warm, stream);
+}
+
+// The tile variant of a call (the list at launch_main), and with it the tile size LC of kernel and table.  `env` is
+// TFX_SOS_VARIANT (negative = unset), `vec` the aligned 16-byte path, `ep` a requested epilogue (fused where vec holds).
+static int resolve_variant(bool rare, bool sum, int prec, bool vec, bool ep, int env)
+{
+    if (rare || sum) return 1;                     // one configuration only (launch_rare, launch_sum)
+    // float32 arithmetic: LC = 32 + register prefetch (4 waves per SIMD); float64: LC = 64 -- the kernel is bound by VALU
+    // issue (1440 instructions per 2048-sample tile, ~100 % busy at 3 waves per SIMD), and 64 samples per lane halve the
+    // scan's share per sample (0.352 vs 0.38-0.42 ms at cfg 2 on the same box)
+    int variant = env >= 0 ? env : (prec == TFX_PREC_F32 ? 2 : 4);
+    if (variant >= 4 && !vec) variant = 2;         // LC = 64 exists for the aligned (16-byte) path only
+    if (variant >= 4 && ep) variant = 4;           // (its epilogue instantiation: no register prefetch)
+    if (variant < 4 && ep && vec) variant = 2;     // the epilogue kernel exists for LC = 32 and LC = 64: table and kernel must agree
+    return variant;
+}
+
+// The coefficient checks every entry point shares: K sections per band in 1 ... 512 (the per-wave carry, 4 values per section,
+// lives in LDS next to the transposition stage), finite values, and -- where the caller's contract says so -- a0 = 1.
+static void check_sos(const char *op, const double *sos_host, int64_t K, bool require_a0_one, int64_t NB = 1)
+{
+    TFX_CHECK(sos_host && K >= 1 && K <= 512, "%s: null coefficients or bad section count %lld (1 ... 512)", op, (long long)K);
+    for (int64_t i = 0; i < NB * K * 6; ++i) TFX_CHECK(std::isfinite(sos_host[i]), "%s: non-finite SOS coefficient", op);
+    if (require_a0_one)
+        for (int64_t s = 0; s < NB * K; ++s) TFX_CHECK(sos_host[s * 6 + 3] == 1.0, "%s: sos[%lld, 3] (a0) must be 1", op, (long long)s);
 }
 
 // NB > 1 = filter-bank mode: NB independent K-section cascades applied to the same C_in input
@@ -1354,33 +1398,26 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in,
         if (ep->any()) epilogue_as_passes(y, y_dtype, C, K == 0 ? T : 0, *ep, stream);
         return;
     }
-    for (int64_t i = 0; i < NB * K * 6; ++i)
-        TFX_CHECK(std::isfinite(sos_host[i]), "sos_forward: non-finite SOS coefficient");
+    check_sos("sos_forward", sos_host, K, false, NB);
 
     const std::shared_ptr<SosPlan> plan = get_plan(sos_host, K, stream, NB);     // held until the launches are enqueued
     SosPlan *pl = plan.get();
     int prec = precision;
     if (prec == TFX_PREC_AUTO) prec = (plan_err_bound(pl) <= auto_bound()) ? TFX_PREC_F32 : TFX_PREC_F64;
     if (x_dtype == TFX_F64 || y_dtype == TFX_F64) prec = TFX_PREC_F64;   // f64 signals: always f64 math
+    const bool f32 = prec == TFX_PREC_F32;
     const bool rare = !(x_dtype == TFX_F32 && y_dtype == TFX_F32);
-
-    // float32 arithmetic: LC = 32 + register prefetch (4 waves per SIMD); float64: LC = 64 -- the kernel is bound by VALU
-    // issue (1440 instructions per 2048-sample tile, ~100 % busy at 3 waves per SIMD), and 64 samples per lane halve the
-    // scan's share per sample (0.352 vs 0.38-0.42 ms at cfg 2 on the same box)
-    int variant = (rare || sum_bands) ? 1 : (int)env_i64("TFX_SOS_VARIANT", -1);
-    if (variant < 0) variant = (prec == TFX_PREC_F32) ? 2 : 4;
-    {
-        const int xs_ = x_dtype == TFX_F32 ? 4 : 8, ys_ = y_dtype == TFX_F32 ? 4 : 8;
-        const bool vec_ = (((uintptr_t)x & 15) == 0) && (((uintptr_t)y & 15) == 0) && ((T * xs_) % 16 == 0) && ((T * ys_) % 16 == 0);
-        if (variant >= 4 && !vec_) variant = 2;                               // LC = 64 exists for the aligned (16-byte) path only
-        if (variant >= 4 && ep->any()) variant = 4;                           // (its epilogue instantiation: no register prefetch)
-    }
+    const int xsz = x_dtype == TFX_F32 ? 4 : 8, ysz = y_dtype == TFX_F32 ? 4 : 8;
+    const bool vec = (((uintptr_t)x & 15) == 0) && (((uintptr_t)y & 15) == 0) && ((T * xsz) % 16 == 0) && ((T * ysz) % 16 == 0);
+    const int variant = resolve_variant(rare, sum_bands, prec, vec, ep->any(), (int)env_i64("TFX_SOS_VARIANT", -1));
+    const int LC = variant >= 4 ? 64 : ((variant & 1) ? 16 : 32);
     // fused into the kernel on the main path (float32 I/O, aligned rows, no taps, single cascade); everything
     // else runs the plain kernel and the same arithmetic as separate passes over y
-    const bool ep_fused = ep->any() && x_dtype == TFX_F32 && y_dtype == TFX_F32 && !sum_bands && !y_sections &&
-                          (((uintptr_t)x & 15) == 0) && (((uintptr_t)y & 15) == 0) && ((T * 4) % 16 == 0);
-    if (ep_fused && variant < 4) variant = 2;      // the epilogue kernel exists for LC = 32 and LC = 64: table and kernel must agree
-    const int LC = variant >= 4 ? 64 : ((variant & 1) ? 16 : 32);
+    const bool ep_fused = ep->any() && !rare && !sum_bands && !y_sections && vec;
+    // the shipping float32-in / float32-out geometry (float64 arithmetic, LC = 64, aligned rows, no section taps) runs the
+    // unit-b0 form when the cascade has one (unit_form_ok); other cascades run the plain form
+    const bool unit = !f32 && variant == 4 && vec && !y_sections && !sum_bands && !rare && plan_unit_ok(pl);
+
     SosParams p{};
     p.x = x; p.y = y; p.taps = y_sections;
     p.sx_in = sx_in; p.sy_in = sy_in; p.sx_out = sx_out; p.sy_out = sy_out;
@@ -1392,46 +1429,20 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in,
     p.ep_partial = nullptr; p.ep_host = ep;
     p.ep_fused = ep_fused ? 1 : 0;
     if (!ep_fused) { p.ep_scale = p.ep_clamp = 0; p.ep_stat = -1; }
+    table_for(p, pl, f32, LC, unit);
 
-    const int64_t nstreams = pl->warm;     // segmentation is decided per kernel instance (launch_one)
-
-    const int xsz = x_dtype == TFX_F32 ? 4 : 8, ysz = y_dtype == TFX_F32 ? 4 : 8;
-    const bool vec = (((uintptr_t)x & 15) == 0) && (((uintptr_t)y & 15) == 0) &&
-                     ((T * xsz) % 16 == 0) && ((T * ysz) % 16 == 0);
-
-    if (prec == TFX_PREC_F32) {
-        p.tab = ensure_table<float>(pl, LC == 64 ? &pl->tab_f32_lc64 : (LC == 32 ? &pl->tab_f32_lc32 : &pl->tab_f32_lc16), LC,
-                                    LC == 64 ? &pl->nsteps64 : (LC == 32 ? &pl->nsteps32 : &pl->nsteps16), stream);
-        p.nsteps = LC == 64 ? pl->nsteps64 : (LC == 32 ? pl->nsteps32 : pl->nsteps16);
-        if (sum_bands) launch_sum<float, float, float>(p, vec, nstreams, stream);
-        else launch_main<float, float, float>(p, vec, variant, nstreams, stream);
-    } else {
-        // the shipping float32-in / float32-out geometry (LC = 64, aligned rows, no section taps) runs the unit-b0 form when the
-        // cascade has one (unit_form_ok); other cascades run the plain form
-        if (LC == 64 && variant == 4 && vec && !p.taps && !sum_bands && x_dtype == TFX_F32 && y_dtype == TFX_F32) {
-            if (pl->unit_ok < 0) {
-                bool ok = true;
-                for (int b = 0; b < pl->NB && ok; ++b)
-                    ok = unit_form_ok(std::vector<double>(pl->sos.begin() + (size_t)b * pl->K * 6, pl->sos.begin() + (size_t)(b + 1) * pl->K * 6), pl->K);
-                pl->unit_ok = ok ? 1 : 0;
-            }
-            p.unit = pl->unit_ok;
-        }
-        if (p.unit)
-            p.tab = ensure_table<double>(pl, &pl->tab_f64_lc64_unit, 64, &pl->nsteps64, stream, true);
-        else
-        p.tab = ensure_table<double>(pl, LC == 64 ? &pl->tab_f64_lc64 : (LC == 32 ? &pl->tab_f64_lc32 : &pl->tab_f64_lc16), LC,
-                                     LC == 64 ? &pl->nsteps64 : (LC == 32 ? &pl->nsteps32 : &pl->nsteps16), stream);
-        p.nsteps = LC == 64 ? pl->nsteps64 : (LC == 32 ? pl->nsteps32 : pl->nsteps16);
-        if (sum_bands) {
-            if (x_dtype == TFX_F32 && y_dtype == TFX_F32) launch_sum<float, float, double>(p, vec, nstreams, stream);
-            else if (x_dtype == TFX_F64 && y_dtype == TFX_F64) launch_sum<double, double, double>(p, vec, nstreams, stream);
-            else TFX_CHECK(false, "sos_forward: sum mode needs equal input and output dtypes");
-        } else if (x_dtype == TFX_F32 && y_dtype == TFX_F32) launch_main<float, float, double>(p, vec, variant, nstreams, stream);
-        else if (x_dtype == TFX_F32) launch_rare<float, double, double>(p, vec, nstreams, stream);
-        else if (y_dtype == TFX_F32) launch_rare<double, float, double>(p, vec, nstreams, stream);
-        else launch_rare<double, double, double>(p, vec, nstreams, stream);
-    }
+    const int64_t warm = pl->warm;         // segmentation is decided per kernel instance (launch_one)
+    if (f32) {
+        if (sum_bands) launch_sum<float, float, float>(p, vec, warm, stream);
+        else launch_main<float, float, float>(p, vec, variant, warm, stream);
+    } else if (sum_bands) {
+        if (x_dtype == TFX_F32 && y_dtype == TFX_F32) launch_sum<float, float, double>(p, vec, warm, stream);
+        else if (x_dtype == TFX_F64 && y_dtype == TFX_F64) launch_sum<double, double, double>(p, vec, warm, stream);
+        else TFX_CHECK(false, "sos_forward: sum mode needs equal input and output dtypes");
+    } else if (!rare) launch_main<float, float, double>(p, vec, variant, warm, stream);
+    else if (x_dtype == TFX_F32) launch_rare<float, double, double>(p, vec, warm, stream);
+    else if (y_dtype == TFX_F32) launch_rare<double, float, double>(p, vec, warm, stream);
+    else launch_rare<double, double, double>(p, vec, warm, stream);
     if (ep->any() && !ep_fused) epilogue_as_passes(y, y_dtype, C, T, *ep, stream);
 }
 
@@ -1471,11 +1482,9 @@ static std::vector<double> filtfilt_gains(const double *sos_host, int64_t K)
 static int64_t filtfilt_check(int64_t C, int64_t T, const double *sos_host, int64_t K, int padtype, int64_t padlen)
 {
     TFX_CHECK(C >= 0 && T >= 0, "sos_filtfilt: negative size");
-    TFX_CHECK(sos_host && K >= 1 && K <= 512, "sos_filtfilt: null coefficients or bad section count %lld (1 ... 512)", (long long)K);
+    check_sos("sos_filtfilt", sos_host, K, true);
     TFX_CHECK(padtype >= TFX_PAD_ODD && padtype <= TFX_PAD_NONE, "sos_filtfilt: bad padtype %d", padtype);
     TFX_CHECK(padlen >= -1, "sos_filtfilt: negative padlen %lld (-1 = the default)", (long long)padlen);
-    for (int64_t i = 0; i < K * 6; ++i) TFX_CHECK(std::isfinite(sos_host[i]), "sos_filtfilt: non-finite SOS coefficient");
-    for (int64_t s = 0; s < K; ++s) TFX_CHECK(sos_host[s * 6 + 3] == 1.0, "sos_filtfilt: sos[%lld, 3] (a0) must be 1", (long long)s);
     int64_t pad = padlen < 0 ? sos_filtfilt_default_padlen(sos_host, K) : padlen;
     if (padtype == TFX_PAD_NONE) pad = 0;
     TFX_CHECK(T > pad, "The length of the input vector x must be greater than padlen, which is %lld.", (long long)pad);
@@ -1529,13 +1538,13 @@ void sos_filtfilt_forward(const void *x, int x_dtype, void *y, int y_dtype, int6
 
     const std::shared_ptr<SosPlan> plan = get_plan(sos_host, K, stream, 1);      // held until the launches are enqueued
     SosPlan *pl = plan.get();
-    const void *tab = ensure_table<double>(pl, &pl->tab_f64_lc32, FF_LC, &pl->nsteps32, stream);
     {
         std::lock_guard<std::mutex> lk(g_plan_mu);
         if (!pl->ff_gain) pl->ff_gain = std::make_unique<DeviceBuffer>(gains);
     }
     SosParams p = filtfilt_params(1, C, T, K, padtype, pad);
-    p.tab = tab; p.nsteps = pl->nsteps32; p.ff_gain = (const double *)pl->ff_gain->p;
+    table_for(p, pl, false, FF_LC);
+    p.ff_gain = (const double *)pl->ff_gain->p;
     p.x = x; p.y = work;
     // a float64 result takes the refined start states in both passes; a float32 result is 20 times inside its bar without
     const bool refine = y_dtype == TFX_F64;
@@ -1570,12 +1579,10 @@ struct BlockEnergyPlan { int64_t nblk, bps, warm; int nseg; };
 static BlockEnergyPlan block_energy_plan(int64_t C, int64_t T, const double *sos_host, int64_t K, int64_t num, int64_t den)
 {
     TFX_CHECK(C >= 0 && T >= 0, "sos_block_energy: negative size");
-    TFX_CHECK(sos_host && K >= 1 && K <= 512, "sos_block_energy: null coefficients or bad section count %lld (1 ... 512)", (long long)K);
+    check_sos("sos_block_energy", sos_host, K, true);
     TFX_CHECK(num >= 1 && den >= 1, "sos_block_energy: block length num / den needs num >= 1 and den >= 1");
     TFX_CHECK(num / 64 >= den, "sos_block_energy: blocks of num / den = %lld / %lld samples are shorter than 64", (long long)num, (long long)den);
     TFX_CHECK(T <= ((int64_t)1 << 61) / den && C <= INT32_MAX, "sos_block_energy: size overflows");
-    for (int64_t i = 0; i < K * 6; ++i) TFX_CHECK(std::isfinite(sos_host[i]), "sos_block_energy: non-finite SOS coefficient");
-    for (int64_t s = 0; s < K; ++s) TFX_CHECK(sos_host[s * 6 + 3] == 1.0, "sos_block_energy: sos[%lld, 3] (a0) must be 1", (long long)s);
     const std::shared_ptr<SosPlan> plan = get_plan(sos_host, K, nullptr, 1);
     BlockEnergyPlan bp;
     bp.nblk = T * den / num;
@@ -1605,30 +1612,6 @@ void sos_block_energy_plan_info(int64_t C, int64_t T, const double *sos_host, in
     if (warm) *warm = bp.warm;
 }
 
-template <typename TIn>
-static void block_energy_launch(SosParams p, hipStream_t stream)
-{
-    const size_t shmem = 4 * (size_t)(sos_stage_bytes<TIn, TIn, double, MS_LC>() + sos_carry_bytes<double, MS_LC>(1, p.K));
-    TFX_CHECK(shmem <= 160 * 1024, "sos_block_energy: K=%d needs %zu B of LDS (max 163840)", p.K, shmem);
-    auto kern = sos_stream_kernel<TIn, TIn, double, MS_LC, false, false, false, 2, false, false, false, 0, false, true>;
-    if (shmem > 64 * 1024)
-        TFX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    const int64_t nstreams = p.C * p.nseg;
-    TFX_CHECK(nstreams <= INT32_MAX, "sos_block_energy: %lld streams are too many for one launch", (long long)nstreams);
-    p.nf_flag = nullptr;
-    if (p.nseg > 1) p.nf_flag = (int *)scratch("sos_nf_flag", (size_t)nstreams * sizeof(int), stream);
-    {
-        ProfScope ps("sos_block_energy_kernel", stream);
-        hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(nstreams, 4)), dim3(256), shmem, stream, p);
-        TFX_HIP(hipGetLastError());
-    }
-    if (p.nseg > 1) {
-        ProfScope ps("sos_block_energy_fix_kernel", stream);
-        hipLaunchKernelGGL(sos_block_energy_fix_kernel, dim3((unsigned)p.C), dim3(256), 0, stream, p);
-        TFX_HIP(hipGetLastError());
-    }
-}
-
 void sos_block_energy_forward(const void *x, int x_dtype, double *s, int64_t C, int64_t T, const double *sos_host, int64_t K,
                               int64_t num, int64_t den, hipStream_t stream)
 {
@@ -1639,16 +1622,16 @@ void sos_block_energy_forward(const void *x, int x_dtype, double *s, int64_t C, 
     const std::shared_ptr<SosPlan> plan = get_plan(sos_host, K, stream, 1);      // held until the launches are enqueued
     SosPlan *pl = plan.get();
     SosParams p{};
-    p.tab = ensure_table<double>(pl, &pl->tab_f64_lc32, MS_LC, &pl->nsteps32, stream);
-    p.nsteps = pl->nsteps32;
+    table_for(p, pl, false, MS_LC);
     p.x = x; p.y = s;
     p.C = C; p.C_in = C; p.T = T; p.K = (int)K; p.x_pitch = T;
     p.nseg = bp.nseg; p.warm = bp.warm;
     p.fair = 15; p.fair_nw = 2;
     p.ep_stat = -1;
     p.ms_num = num; p.ms_den = den; p.ms_nblk = bp.nblk; p.ms_bps = bp.bps;
-    if (x_dtype == TFX_F32) block_energy_launch<float>(p, stream);
-    else block_energy_launch<double>(p, stream);
+    // the segmentation above is final (block_energy_plan): launch_one takes it as it is
+    if (x_dtype == TFX_F32) launch_one<float, float, double, MS_LC, false, false, false, 2, false, false, false, 0, false, true>(p, pl->warm, stream);
+    else launch_one<double, double, double, MS_LC, false, false, false, 2, false, false, false, 0, false, true>(p, pl->warm, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1778,16 +1761,11 @@ void chunk_forward(const float *x, int64_t x_pitch, float *y, int64_t C, int64_t
     std::shared_ptr<SosPlan> plan;                 // the plan and the taps are held until the launch is enqueued
     std::shared_ptr<DeviceBuffer> taps;
     if (K > 0) {
-        for (int64_t i = 0; i < K * 6; ++i) TFX_CHECK(std::isfinite(sos_host[i]), "chunk_forward: non-finite SOS coefficient");
+        check_sos("chunk_forward", sos_host, K, false);
         plan = get_plan(sos_host, K, stream, 1);
         SosPlan *pl = plan.get();
         if (prec == TFX_PREC_AUTO) prec = (plan_err_bound(pl) <= auto_bound()) ? TFX_PREC_F32 : TFX_PREC_F64;
-        if (prec == TFX_PREC_F32) {
-            p.tab = ensure_table<float>(pl, &pl->tab_f32_lc16, 16, &pl->nsteps16, stream);
-        } else {
-            p.tab = ensure_table<double>(pl, &pl->tab_f64_lc16, 16, &pl->nsteps16, stream);
-        }
-        p.nsteps = pl->nsteps16;
+        table_for(p, pl, prec == TFX_PREC_F32, 16);
     }
     const int H = (int)Kf - 1, Hpad = (H + 3) & ~3, Kp = Hpad + 4;
     {   // device taps in the kernel's layout: Hpad - H leading zeros (they meet the zero-filled front of the LDS buffer),
@@ -1802,7 +1780,7 @@ void chunk_forward(const float *x, int64_t x_pitch, float *y, int64_t C, int64_t
     q.gain = (float)gain; q.scale = scale; q.clamp = clamp;
     const bool vec = (((uintptr_t)x & 15) == 0) && (T % 4 == 0) && (x_pitch % 4 == 0);
     const bool f32 = prec == TFX_PREC_F32;
-    const size_t stage_b = K > 0 ? (size_t)(sos_stage_bytes<float, float, double, 16>() + (f32 ? sos_carry_bytes<float, 16>(1, (int)K) : sos_carry_bytes<double, 16>(1, (int)K))) : 0;
+    const size_t stage_b = K == 0 ? 0 : (size_t)(f32 ? sos_wave_lds_bytes<float, float, float, 16>(1, (int)K) : sos_wave_lds_bytes<float, float, double, 16>(1, (int)K));
     const size_t shmem = (size_t)(Hpad + q.Tpad + 8 + Kp) * 4 + stage_b;
     TFX_CHECK(shmem <= 64 * 1024, "chunk_forward: needs %zu B of LDS", shmem);
     // the cascade is one wavefront's work; the FIR phase scales with the threads: 4 outputs each
