@@ -122,6 +122,17 @@ int tfx_sos_bank_sum_forward(const void *x, int x_dtype, void *y, int y_dtype,
 int tfx_sos_plan_info(const double *sos_host, int64_t K,
                       int *precision, int64_t *warmup, double *err_bound);
 
+/* The float64-arithmetic facts of a cascade (host only, any output may be NULL): *unit_form = 1 when float32 signals on
+ * aligned rows run it in the unit-b0 form (K >= 2, sane b0); *refine_f32 / *refine_f64 = 1 when launches with a float32 /
+ * float64 result take the kernels that refine the lane scan's start states once per section and tile.  The rule is
+ * measured per cascade: the unrefined kernel's float64 arithmetic and the sequential float64 recursion are replayed on the
+ * host against a long double recursion; errs[4] = {blocked, sequential} error as shares of the output scale at 64 samples
+ * per lane (float32 signals), then at 16 (float64 results).  A float32 result refines when blocked > 1e-10, a float64
+ * result when blocked > 2 max(sequential, 2^-50).  Cascades with poles next to z = 1 under a rough output (20 Hz
+ * high-pass, notch, low peaking EQ) refine; ordinary ones run the kernels they always did. */
+int tfx_sos_refine_info(const double *sos_host, int64_t K,
+                        int *unit_form, int *refine_f32, int *refine_f64, double *errs);
+
 /* ---------------------------------------------------------------------------
  * tfx_sos_filtfilt_forward -- zero-phase (forward-backward) filtering along each row with the semantics of
  * scipy.signal.sosfiltfilt(sos, x, axis=-1, padtype, padlen) (SciPy 1.15); the reference has no counterpart.

@@ -15,6 +15,7 @@
  * Plain C11, no dependencies.  Arithmetic order follows the cited reference
  * lines; citations are relative to /root/reference/.
  */
+#include <float.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -85,6 +86,72 @@ void oracle_sos_df1_f64(const double *x, double *y, int64_t C, int64_t T,
             state_x[(s * C + c) * 2 + 1] = sx1[s];
             state_y[(s * C + c) * 2 + 0] = sy0[s];
             state_y[(s * C + c) * 2 + 1] = sy1[s];
+        }
+        free(sx0);
+    }
+}
+
+/* ---------------------------------------------------------------------------
+ * The same cascade in a wide type: the truth the float64 results are judged by.
+ * Same signature and layout as oracle_sos_df1_f64.  Inputs and coefficients are
+ * the given doubles; every product, sum and state is a __float128 (113 mantissa
+ * bits, gcc on x86-64; long double where the type is missing); outputs, section
+ * outputs and final states are rounded once to double.  A product of two doubles
+ * is exact in 113 bits, so one output costs five roundings at 2^-113.  Only
+ * + - * and conversions: libgcc's soft-float routines, no libquadmath.
+ * ------------------------------------------------------------------------- */
+#if defined(__SIZEOF_FLOAT128__) && !defined(ORACLE_NO_FLOAT128)
+typedef __float128 wide_t;
+#define ORACLE_WIDE_MANT_DIG 113
+#else
+typedef long double wide_t;
+#define ORACLE_WIDE_MANT_DIG LDBL_MANT_DIG
+#endif
+
+int oracle_wide_mant_dig(void) { return ORACLE_WIDE_MANT_DIG; }
+
+void oracle_sos_df1_wide(const double *x, double *y, int64_t C, int64_t T,
+                         const double *sos, int64_t K,
+                         double *state_x, double *state_y,
+                         double *y_sections)
+{
+#pragma omp parallel for schedule(static) if (C > 1)
+    for (int64_t c = 0; c < C; ++c) {
+        wide_t *sx0 = (wide_t *)malloc(sizeof(wide_t) * 9 * (size_t)(K > 0 ? K : 1));
+        wide_t *sx1 = sx0 + K, *sy0 = sx1 + K, *sy1 = sy0 + K, *co = sy1 + K;
+        for (int64_t s = 0; s < K; ++s) {
+            sx0[s] = state_x[(s * C + c) * 2 + 0];
+            sx1[s] = state_x[(s * C + c) * 2 + 1];
+            sy0[s] = state_y[(s * C + c) * 2 + 0];
+            sy1[s] = state_y[(s * C + c) * 2 + 1];
+            co[s * 5 + 0] = sos[s * 6 + 0];
+            co[s * 5 + 1] = sos[s * 6 + 1];
+            co[s * 5 + 2] = sos[s * 6 + 2];
+            co[s * 5 + 3] = sos[s * 6 + 4];
+            co[s * 5 + 4] = sos[s * 6 + 5];
+        }
+        const double *xc = x + c * T;
+        double *yc = y + c * T;
+        for (int64_t n = 0; n < T; ++n) {
+            wide_t val = xc[n];
+            for (int64_t s = 0; s < K; ++s) {
+                const wide_t *q = co + s * 5;
+                wide_t yn = q[0] * val + q[1] * sx0[s] + q[2] * sx1[s]
+                          - q[3] * sy0[s] - q[4] * sy1[s];
+                sx1[s] = sx0[s];
+                sx0[s] = val;
+                sy1[s] = sy0[s];
+                sy0[s] = yn;
+                val = yn;
+                if (y_sections) y_sections[(s * C + c) * T + n] = (double)yn;
+            }
+            yc[n] = (double)val;
+        }
+        for (int64_t s = 0; s < K; ++s) {
+            state_x[(s * C + c) * 2 + 0] = (double)sx0[s];
+            state_x[(s * C + c) * 2 + 1] = (double)sx1[s];
+            state_y[(s * C + c) * 2 + 0] = (double)sy0[s];
+            state_y[(s * C + c) * 2 + 1] = (double)sy1[s];
         }
         free(sx0);
     }

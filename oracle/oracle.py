@@ -72,6 +72,42 @@ def sos_forward(x, sos, state_x=None, state_y=None, sections=False):
     return (y, sx, sy, ysec) if sections else (y, sx, sy)
 
 
+def _wide_symbol(name):
+    lib = _lib()
+    if not hasattr(lib, name):
+        raise RuntimeError(f"oracle/liboracle.so has no {name}: it was built from an older oracle.c; "
+                           "rebuild it with `make -C oracle oracle`")
+    return getattr(lib, name)
+
+
+def wide_mant_dig() -> int:
+    """Mantissa bits of the type ``sos_forward_wide`` computes in: 113 (``__float128``), or ``LDBL_MANT_DIG`` where the
+    compiler has no such type."""
+    f = _wide_symbol("oracle_wide_mant_dig")
+    f.restype = ctypes.c_int
+    return int(f())
+
+
+def sos_forward_wide(x, sos, state_x=None, state_y=None, sections=False):
+    """The recursion of :func:`sos_forward` with every product, sum and state in ``__float128``; inputs and coefficients are
+    the given values as doubles, outputs, section outputs and final states are rounded once to double.  Returns what
+    :func:`sos_forward` returns.  Not the reference's arithmetic: the truth a float64 result is judged by."""
+    f = _wide_symbol("oracle_sos_df1_wide")
+    x = np.ascontiguousarray(x)
+    assert x.ndim == 2
+    C, T = x.shape
+    sos = np.ascontiguousarray(sos, dtype=np.float64)
+    K = sos.shape[0]
+    sx = np.zeros((K, C, 2)) if state_x is None else np.array(state_x, dtype=np.float64, copy=True)
+    sy = np.zeros((K, C, 2)) if state_y is None else np.array(state_y, dtype=np.float64, copy=True)
+    xd = x.astype(np.float64)
+    y = np.empty_like(xd)
+    ysec = np.empty((K, C, T)) if sections else None
+    f.restype = None
+    f(_p(xd), _p(y), _i64(C), _i64(T), _p(sos), _i64(K), _p(sx), _p(sy), _p(ysec))
+    return (y, sx, sy, ysec) if sections else (y, sx, sy)
+
+
 def biquad_forward(x, b, a1, a2, state_x=None, state_y=None):
     """``biquad_forward_cpu`` (``iir_cpu.cpp:10-62``); states ``[C,2]``."""
     x = np.ascontiguousarray(x, dtype=np.float64)

@@ -73,7 +73,7 @@ def test_chunked_state_carry_golden(golden, sos_variant):
 def test_ill_conditioned_golden(golden, name, sos_variant):
     g = golden("iir_hard")
     y, sx, sy = ext().sos_forward(dev(g["x"]), None, torch.from_numpy(g[name + "_sos"]), None, None)
-    close(y, g[name + "_y"], 2.5e-7, name)      # pole radius ~0.999: allow 2 ulp
+    close(y, g[name + "_y"], TOL_IIR_F32OUT, name)      # pole radius ~0.999; measured 3.8e-9 at most with the refined start states
     close(sy, g[name + "_sy"], 1e-8, name + " sy")
 
 

@@ -1,14 +1,19 @@
-"""Float64 emulation of the cascade kernel's blocked arithmetic (LC = 32 samples per lane, 64 lanes per tile) with and without
-the refinement step the zero-phase passes of a float64 result take (csrc/sos.hip, FFR), against a long-double sequential
-recursion.  Host only; prints, per filter, the largest error of the blocked form, of the refined form and of a sequential
-float64 recursion.  The lane scan is summed lane by lane here (the kernel's tree order differs; the magnitudes do not).
+"""Float64 emulation of the cascade kernel's blocked arithmetic (LC = 16 / 32 / 64 samples per lane, 64 lanes per tile) with and
+without the refinement step (csrc/sos.hip, FFR: the zero-phase passes of a float64 result, and the forward cascade and the
+measuring pass for the cascades the library's rule picks), against a long-double sequential recursion.  Host
+only; prints, per filter, rate and LC, the largest error of the blocked form, of the refined form and of a sequential float64
+recursion.  The lane scan is summed lane by lane here (the kernel's tree order differs; the magnitudes do not); the library's
+own decision replays the kernel's tree in C++ (tfx_sos_refine_info) and lands on the same figures.
 
-    python tools/filtfilt_refine_emulation.py
+    python tools/filtfilt_refine_emulation.py                       # the 48 kHz table of DESIGN.md 4.8, LC = 32
+    python tools/filtfilt_refine_emulation.py --fs 96000 192000 --lc 16 64
 """
 from __future__ import annotations
 
 import numpy as np
 import scipy.signal as ss
+
+import argparse
 
 LC, NL = 32, 64
 TILE = LC * NL
@@ -86,11 +91,15 @@ def section_long_double(b, a, x):
     return y
 
 
-def main() -> None:
-    x = np.random.default_rng(0).uniform(-1, 1, TILE * 16)
-    filters = {"HiButterworth(20, order=5) @ 48 kHz": ss.butter(5, 20, "highpass", fs=48000, output="sos"),
-               "Notch(60, q=30) @ 48 kHz": ss.tf2sos(*ss.iirnotch(60, 30, fs=48000)),
-               "LoButterworth(40, order=8) @ 48 kHz": ss.butter(8, 40, fs=48000, output="sos")}
+def run(fs: int, lc: int) -> None:
+    global LC, TILE
+    LC, TILE = lc, lc * NL
+    x = np.random.default_rng(0).uniform(-1, 1, max(TILE * 16, 65536))
+    filters = {f"HiButterworth(20, order=5) @ {fs} Hz, LC {lc}": ss.butter(5, 20, "highpass", fs=fs, output="sos"),
+               f"HiButterworth(20, order=4) @ {fs} Hz, LC {lc}": ss.butter(4, 20, "highpass", fs=fs, output="sos"),
+               f"Notch(60, q=30) @ {fs} Hz, LC {lc}": ss.tf2sos(*ss.iirnotch(60, 30, fs=fs)),
+               f"LoButterworth(40, order=8) @ {fs} Hz, LC {lc}": ss.butter(8, 40, fs=fs, output="sos"),
+               f"LoButterworth(2000, order=4) @ {fs} Hz, LC {lc}": ss.butter(4, 2000, fs=fs, output="sos")}
     for name, sos in filters.items():
         blocked, refined, seq, ref = x.copy(), x.copy(), x.copy(), x.astype(np.longdouble)
         for s in sos:
@@ -101,6 +110,16 @@ def main() -> None:
         scale = max(1.0, float(np.abs(ref).max()))
         print(f"{name}: blocked {float(np.abs(blocked - ref).max()) / scale:.2e}   refined {float(np.abs(refined - ref).max()) / scale:.2e}   "
               f"sequential float64 {float(np.abs(seq - ref).max()) / scale:.2e}   (of max(1, max|y|) = {scale:.2f})")
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--fs", type=int, nargs="+", default=[48000])
+    ap.add_argument("--lc", type=int, nargs="+", default=[32], choices=[16, 32, 64])
+    args = ap.parse_args()
+    for fs in args.fs:
+        for lc in args.lc:
+            run(fs, lc)
 
 
 if __name__ == "__main__":

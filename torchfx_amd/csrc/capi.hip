@@ -468,6 +468,14 @@ int tfx_sos_plan_info(const double *sos_host, int64_t K, int *precision, int64_t
     TFX_API_END
 }
 
+int tfx_sos_refine_info(const double *sos_host, int64_t K, int *unit_form, int *refine_f32, int *refine_f64, double *errs)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(sos_host && K >= 1 && K <= 512, "sos_refine_info: null coefficients or bad section count %lld", (long long)K);
+    sos_refine_info(sos_host, K, unit_form, refine_f32, refine_f64, errs);
+    TFX_API_END
+}
+
 int tfx_biquad_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C, int64_t T,
                        const double *b_host, double a1, double a2, const double *state_x_in,
                        const double *state_y_in, double *state_x_out, double *state_y_out, int precision,

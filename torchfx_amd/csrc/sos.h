@@ -13,6 +13,7 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C, in
                  double *sx_out, double *sy_out, void *y_sections, int precision, hipStream_t stream, int64_t NB = 1,
                  bool sum_bands = false, const Epilogue *ep = nullptr);
 void sos_plan_info(const double *sos_host, int64_t K, int *precision, int64_t *warmup, double *err_bound);
+void sos_refine_info(const double *sos_host, int64_t K, int *unit_form, int *refine_f32, int *refine_f64, double *errs);
 void sos_clear_plans();
 
 // zero-phase filtering (scipy.signal.sosfiltfilt along each row)

@@ -83,6 +83,7 @@ struct SosParams {
     int fair;            // > 0: waves that share a SIMD alternate their issue priority every 2^fair clocks
     int fair_nw;         // waves per SIMD of this launch (the priority levels that rotate): 2 ... 4
     int unit;            // host side only: `tab` holds the unit-b0 form (UNIT kernels)
+    int refine;          // host side only: the launch takes the kernels that refine the scan's start states (FFR; plan_refine)
     // zero-phase passes (FF kernels, sos_filtfilt_forward): T above is the length of the edge-extended row, ff_T + 2 * ff_pad
     int ff;              // 1 = forward pass over the virtual extension of x, 2 = reverse-time pass over the intermediate
     int ff_padtype;      // TFX_PAD_ODD / EVEN / CONSTANT (NONE arrives as ff_pad = 0)
@@ -170,7 +171,8 @@ template <typename T> struct U16 {               // 16 bytes of T
 //      end and stores the signal's own samples at their reversed places; both start from the cascade's steady state for
 //      the row's first sample (scipy.signal.sosfilt_zi * x[0]).  Scalar (!VEC) path only; FF = 0 compiles to the code
 //      it was before
-// FFR  the zero-phase passes of a float64 result refine the scan's start states once (see the scan below)
+// FFR  refine the scan's start states once (see the scan below): the zero-phase passes of a float64 result, and the forward
+//      cascade and the measuring pass for the cascades whose plan asks for it (plan_refine)
 // MEAS measuring pass (SosParams::ms_*): the cascade's output is not stored; the stream keeps the sum of its squares over each
 //      block of samples it owns.  Segments start on block edges (their halo in front), so every block has one writer.  Scalar
 //      (!VEC) path only, TOut = TIn (the stage holds the input alone); MEAS = false compiles to the code it was before
@@ -476,9 +478,8 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
             if constexpr (FFR) {
                 // One step of iterative refinement of the start states.  The scan adds zero-state chunk responses that are
                 // hundreds of times larger than the state they cancel to when the poles lie next to z = 1 and the output
-                // is rough (high-pass, notch): 2e-9 of the output scale on HiButterworth(20) in float64, which the forward
-                // cascade's float32 results never see but a float64 zero-phase result does.  So: run the recursion once
-                // more from the start states just found; where chunk j - 1 ends and where chunk j was told to start differ
+                // is rough (high-pass, notch): 2e-9 of the output scale on HiButterworth(20) at 48 kHz in float64, and 1e-7
+                // at 192 kHz.  So: run the recursion once more from the start states just found; where chunk j - 1 ends and where chunk j was told to start differ
                 // by a residual of that size, and the same scan over the residuals (e_j = r_j + P e_(j-1), e_0 = 0) gives
                 // the correction with a relative error of its own.  What is left is the rounding of a sequential recursion.
                 TC w1 = h1, w2 = h2;
@@ -814,6 +815,8 @@ struct SosPlan {
     Table tab[2][3][2];           // [float32 / float64][LC = 16 / 32 / 64][plain / unit-b0 form (fill_tables)], lazy: table_for
     std::unique_ptr<DeviceBuffer> ff_gain;               // zero-phase passes: the K + 1 cumulative DC gains (filtfilt_gains), lazy
     int unit_ok = -1;                    // the cascade has a unit-b0 form (lazy)
+    int blocked_known[3] = {0, 0, 0};    // per LC = 16 / 32 / 64: the measured error of the unrefined float64 kernel and of the
+    double blocked[3][3] = {};           // sequential float64 recursion, shares of the output scale (plan_blocked_error, lazy)
     std::vector<double> sos;
 };
 
@@ -1067,6 +1070,173 @@ static double f32_error_bound(const std::vector<double> &sos, int K)
     return 2.5 * worst / scale;
 }
 
+// Whether a cascade needs the refined start states (FFR kernels).  The lane scan rebuilds every lane's start state from
+// zero-state pieces that are far larger than the state they cancel to when the poles sit next to z = 1 and the section's
+// output is rough (20 Hz high-pass, notch, low peaking EQ, the K-weighting high-pass): the float64 kernel then loses
+// 5e-9 of the output scale at 48 kHz and 1e-7 at 192 kHz on a plain DC-blocking high-pass, where a sequential float64
+// recursion loses 2e-12 and 2e-11.  No closed form of the pole positions predicts that across numerators
+// (a low-pass with the same poles is fine), so -- like the float32 estimate above -- it is MEASURED, once per plan and
+// tile size: the kernel's float64 arithmetic without the refinement (same tile / lane structure, same tables, same scan
+// tree) and the sequential float64 recursion are both replayed on 2^16 pseudo-random samples against a long double
+// recursion.  `blocked` and `seq` are the two largest errors as shares of max(1, max|y|).  The rule:
+//   float64 result (and the block energies):  refine when blocked > 2 max(seq, 2^-50) -- the blocking costs more than the
+//                                             float64 recursion itself does;
+//   float32 result:                           refine when blocked > 1e-10.  An error e flips the float32 rounding of about
+//                                             (e / 2^-23) log2(2^-23 / e) of the outputs (one binade after the other, each
+//                                             with its own ulp); at a typical error of a third of the largest that is
+//                                             0.3 % at 1e-10, and 6 % at the 5e-9 of the 48 kHz high-pass.
+template <typename TR>
+static std::vector<TR> replay_sequential(const std::vector<double> &sos, int K, const std::vector<float> &x)
+{
+    std::vector<TR> ref(x.begin(), x.end());
+    for (int s = 0; s < K; ++s) {
+        const double *co = &sos[s * 6];
+        const TR b0 = co[0], b1 = co[1], b2 = co[2], a1 = co[4], a2 = co[5];
+        TR x1 = 0, x2 = 0, y1 = 0, y2 = 0;
+        for (size_t n = 0; n < ref.size(); ++n) {
+            const TR v = ref[n];
+            const TR y = b0 * v + b1 * x1 + b2 * x2 - a1 * y1 - a2 * y2;
+            x2 = x1; x1 = v; y2 = y1; y1 = y;
+            ref[n] = y;
+        }
+    }
+    return ref;
+}
+
+struct BlockedError { double blocked = 0.0, seq = 0.0, blocked_max = 0.0; };      // blocked_max: over the bands of a bank
+
+static BlockedError f64_blocked_error(const std::vector<double> &sos, int K, int LC)
+{
+    const int TILE = 64 * LC, TS = tab_stride(LC);
+    const int64_t N = 1 << 16;
+    BlockedError out;
+    std::vector<double> tab;
+    int nsteps = 0;
+    fill_tables<double>(sos, K, LC, tab, nsteps, false);
+    for (double v : tab) if (!std::isfinite(v)) { out.blocked = out.seq = INFINITY; return out; }
+    std::vector<float> x((size_t)N);
+    uint64_t st = 0x9E3779B97F4A7C15ull;
+    for (auto &v : x) { st = st * 6364136223846793005ull + 1442695040888963407ull; v = (float)((double)(st >> 11) / 9007199254740992.0 * 2.0 - 1.0); }
+    const std::vector<ld> ref = replay_sequential<ld>(sos, K, x);
+    const std::vector<double> seq = replay_sequential<double>(sos, K, x);
+    // float64 replay of sos_stream_kernel without FFR (one stream, no time segmentation): the float32 replay above in double
+    std::vector<double> cur(x.begin(), x.end());
+    std::vector<double> carry((size_t)K * 4, 0.0);
+    std::vector<double> pv1(64), pv2(64), s0(64), s1(64), t0(64), t1(64);
+    for (int64_t ts = 0; ts < N; ts += TILE) {
+        double *d = &cur[(size_t)ts];
+        for (int s = 0; s < K; ++s) {
+            const double *tb = &tab[(size_t)s * TS];
+            const double b0 = tb[0], b1 = tb[1], b2 = tb[2], na1 = tb[3], na2 = tb[4];
+            double *cs = &carry[(size_t)s * 4];
+            for (int l = 0; l < 64; ++l) {
+                pv1[l] = l ? d[(l - 1) * LC + LC - 1] : cs[0];
+                pv2[l] = l ? d[(l - 1) * LC + LC - 2] : cs[1];
+            }
+            cs[0] = d[63 * LC + LC - 1]; cs[1] = d[63 * LC + LC - 2];
+            for (int l = 0; l < 64; ++l) {
+                double *c = d + l * LC;
+                for (int n = LC - 1; n >= 0; --n) {
+                    const double x1 = n >= 1 ? c[n - 1] : pv1[l];
+                    const double x2 = n >= 2 ? c[n - 2] : (n == 1 ? pv1[l] : pv2[l]);
+                    c[n] = fma(b2, x2, fma(b1, x1, b0 * c[n]));
+                }
+                double u1 = l ? 0.0 : cs[2], u2 = l ? 0.0 : cs[3];
+                for (int n = 0; n < LC; ++n) { const double u = fma(na1, u1, fma(na2, u2, c[n])); u2 = u1; u1 = u; }
+                s0[l] = u1; s1[l] = u2;
+            }
+            const double *pm = tb + 8;
+            for (int k = 0; k < 4; ++k) {
+                for (int l = 0; l < 64; ++l) { const bool src = (l & 15) >= (1 << k); t0[l] = src ? s0[l - (1 << k)] : 0.0; t1[l] = src ? s1[l - (1 << k)] : 0.0; }
+                for (int l = 0; l < 64; ++l) {
+                    s0[l] += fma(pm[4 * k + 0], t0[l], pm[4 * k + 1] * t1[l]);
+                    s1[l] += fma(pm[4 * k + 2], t0[l], pm[4 * k + 3] * t1[l]);
+                }
+            }
+            {
+                const double *mp = tb + 32;
+                for (int l = 0; l < 64; ++l) { const bool on = (l >> 4) & 1; t0[l] = on ? s0[(l & ~15) - 1] : 0.0; t1[l] = on ? s1[(l & ~15) - 1] : 0.0; }
+                for (int l = 0; l < 64; ++l) {
+                    const double *m = mp + 4 * (l & 15);
+                    s0[l] += fma(m[0], t0[l], m[1] * t1[l]);
+                    s1[l] += fma(m[2], t0[l], m[3] * t1[l]);
+                }
+                const double c0 = s0[31], c1 = s1[31];
+                for (int l = 32; l < 64; ++l) {
+                    const double *m = mp + 4 * (l & 31);
+                    const double n0 = s0[l] + fma(m[0], c0, m[1] * c1), n1 = s1[l] + fma(m[2], c0, m[3] * c1);
+                    s0[l] = n0; s1[l] = n1;
+                }
+            }
+            const double cy1 = cs[2], cy2 = cs[3];
+            for (int l = 0; l < 64; ++l) {
+                double h1 = l ? s0[l - 1] : cy1, h2 = l ? s1[l - 1] : cy2;
+                double *c = d + l * LC;
+                for (int n = 0; n < LC; ++n) {
+                    const double yv = fma(na1, h1, fma(na2, h2, c[n]));
+                    c[n] = yv; h2 = h1; h1 = yv;
+                }
+            }
+            cs[2] = d[63 * LC + LC - 1]; cs[3] = d[63 * LC + LC - 2];
+        }
+    }
+    ld scale = 1.0L, wb = 0.0L, wq = 0.0L;
+    for (size_t i = 0; i < (size_t)N; ++i) {
+        const ld eb = fabsl((ld)cur[i] - ref[i]), eq = fabsl((ld)seq[i] - ref[i]);
+        if (!(eb <= wb)) wb = eb;                             // NaN-propagating
+        if (!(eq <= wq)) wq = eq;
+        scale = fmaxl(scale, fabsl(ref[i]));
+    }
+    out.blocked = (double)(wb / scale);
+    out.seq = (double)(wq / scale);
+    return out;
+}
+
+constexpr double REFINE_F32_RESULT = 1e-10;       // largest blocked error a float32 result is left with
+constexpr double REFINE_F64_FACTOR = 2.0;         // ... and a float64 result, as a multiple of the sequential recursion's own
+constexpr double REFINE_F64_FLOOR = 0x1p-50;
+
+static int lc_index(int LC) { return LC == 16 ? 0 : (LC == 32 ? 1 : 2); }
+
+// the measured errors of the plan's worst band at tile size LC (lazy)
+static BlockedError plan_blocked_error(SosPlan *pl, int LC)
+{
+    const int i = lc_index(LC);
+    bool known;
+    {
+        std::lock_guard<std::mutex> lk(g_plan_mu);
+        known = pl->blocked_known[i] != 0;
+    }
+    if (!known) {
+        // The replay runs OUTSIDE the lock (about 10 ms for four sections, a second for 512): the plan's coefficients never
+        // change, two threads that race here compute the same numbers, and nobody else's plan lookup waits for them.
+        BlockedError worst;
+        double bmax = 0.0;
+        for (int b = 0; b < pl->NB; ++b) {
+            std::vector<double> one(pl->sos.begin() + (size_t)b * pl->K * 6, pl->sos.begin() + (size_t)(b + 1) * pl->K * 6);
+            const BlockedError e = f64_blocked_error(one, pl->K, LC);
+            // a float64 result: the band furthest past its own bar decides; a float32 result: the largest error of any band
+            if (b == 0 || !(e.blocked / fmax(e.seq, REFINE_F64_FLOOR) <= worst.blocked / fmax(worst.seq, REFINE_F64_FLOOR))) worst = e;
+            if (!(e.blocked <= bmax)) bmax = e.blocked;
+        }
+        std::lock_guard<std::mutex> lk(g_plan_mu);
+        pl->blocked[i][0] = worst.blocked; pl->blocked[i][1] = worst.seq; pl->blocked[i][2] = bmax;
+        pl->blocked_known[i] = 1;
+    }
+    std::lock_guard<std::mutex> lk(g_plan_mu);
+    BlockedError e;
+    e.blocked = pl->blocked[i][0]; e.seq = pl->blocked[i][1]; e.blocked_max = pl->blocked[i][2];
+    return e;
+}
+// The decision, per cascade, tile size and result dtype (float64 arithmetic only).  Non-finite estimates (an unstable
+// cascade) refine nothing: there is no accuracy to keep.
+static bool plan_refine(SosPlan *pl, int LC, bool f64_result)
+{
+    const BlockedError e = plan_blocked_error(pl, LC);
+    if (!std::isfinite(e.blocked) || !std::isfinite(e.seq) || !std::isfinite(e.blocked_max)) return false;
+    return f64_result ? e.blocked > REFINE_F64_FACTOR * fmax(e.seq, REFINE_F64_FLOOR) : e.blocked_max > REFINE_F32_RESULT;
+}
+
 static double plan_err_bound(SosPlan *pl)
 {
     std::lock_guard<std::mutex> lk(g_plan_mu);
@@ -1282,6 +1452,25 @@ template <typename TIn, typename TOut, typename TC>
 static void launch_main(const SosParams &p, bool vec, int variant, int64_t plan_warm, hipStream_t stream)
 {
     constexpr bool F32 = sizeof(TC) == 4;
+    if constexpr (!F32) {
+        if (p.refine) {
+            // refined start states (plan_refine): the shipping geometry only -- LC = 64 on aligned rows in both forms, with and
+            // without the epilogue, LC = 32 on the dword path, and the two with section taps (sos_forward sends every
+            // refined launch here, whatever TFX_SOS_VARIANT says)
+            if (p.taps) {
+                if (vec) launch_one<TIn, TOut, TC, 64, true, true, false, 2, false, false, false, 0, true>(p, plan_warm, stream);
+                else launch_one<TIn, TOut, TC, 32, false, true, false, 2, false, false, false, 0, true>(p, plan_warm, stream);
+            } else if (!vec) launch_one<TIn, TOut, TC, 32, false, false, false, 2, false, false, false, 0, true>(p, plan_warm, stream);
+            else if (p.unit) {
+                if (p.ep_fused) launch_one<TIn, TOut, TC, 64, true, false, false, 2, false, true, true, 0, true>(p, plan_warm, stream);
+                else launch_one<TIn, TOut, TC, 64, true, false, false, 2, false, false, true, 0, true>(p, plan_warm, stream);
+            } else {
+                if (p.ep_fused) launch_one<TIn, TOut, TC, 64, true, false, false, 2, false, true, false, 0, true>(p, plan_warm, stream);
+                else launch_one<TIn, TOut, TC, 64, true, false, false, 2, false, false, false, 0, true>(p, plan_warm, stream);
+            }
+            return;
+        }
+    }
     if (p.taps && vec && variant >= 4) {   // the shipping LC = 64 geometry with every section's output tapped (parity tests)
         launch_one<TIn, TOut, TC, 64, true, true, false, F32 ? 3 : 2>(p, plan_warm, stream);
         return;
@@ -1321,6 +1510,12 @@ static void launch_main(const SosParams &p, bool vec, int variant, int64_t plan_
 template <typename TIn, typename TOut, typename TC>
 static void launch_rare(const SosParams &p, bool vec, int64_t plan_warm, hipStream_t stream)
 {
+    if (p.refine) {           // the same three with refined start states (plan_refine)
+        if (p.taps) launch_one<TIn, TOut, TC, 16, false, true, false, 3, false, false, false, 0, true>(p, plan_warm, stream);
+        else if (vec) launch_one<TIn, TOut, TC, 16, true, false, false, 4, false, false, false, 0, true>(p, plan_warm, stream);
+        else launch_one<TIn, TOut, TC, 16, false, false, false, 3, false, false, false, 0, true>(p, plan_warm, stream);
+        return;
+    }
     if (p.taps) launch_one<TIn, TOut, TC, 16, false, true, false, 3>(p, plan_warm, stream);
     else if (vec) launch_one<TIn, TOut, TC, 16, true, false, false, 4>(p, plan_warm, stream);
     else launch_one<TIn, TOut, TC, 16, false, false, false, 3>(p, plan_warm, stream);
@@ -1330,6 +1525,13 @@ static void launch_rare(const SosParams &p, bool vec, int64_t plan_warm, hipStre
 template <typename TIn, typename TOut, typename TC>
 static void launch_sum(const SosParams &p, bool vec, int64_t plan_warm, hipStream_t stream)
 {
+    if constexpr (sizeof(TC) == 8) {
+        if (p.refine) {       // refined start states (plan_refine)
+            if (vec) launch_one<TIn, TOut, TC, 16, true, false, false, 3, true, false, false, 0, true>(p, plan_warm, stream);
+            else launch_one<TIn, TOut, TC, 16, false, false, false, 3, true, false, false, 0, true>(p, plan_warm, stream);
+            return;
+        }
+    }
     if (vec) launch_one<TIn, TOut, TC, 16, true, false, false, 3, true>(p, plan_warm, stream);
     else launch_one<TIn, TOut, TC, 16, false, false, false, 3, true>(p, plan_warm, stream);
 }
@@ -1409,8 +1611,16 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in,
     const bool rare = !(x_dtype == TFX_F32 && y_dtype == TFX_F32);
     const int xsz = x_dtype == TFX_F32 ? 4 : 8, ysz = y_dtype == TFX_F32 ? 4 : 8;
     const bool vec = (((uintptr_t)x & 15) == 0) && (((uintptr_t)y & 15) == 0) && ((T * xsz) % 16 == 0) && ((T * ysz) % 16 == 0);
-    const int variant = resolve_variant(rare, sum_bands, prec, vec, ep->any(), (int)env_i64("TFX_SOS_VARIANT", -1));
-    const int LC = variant >= 4 ? 64 : ((variant & 1) ? 16 : 32);
+    int variant = resolve_variant(rare, sum_bands, prec, vec, ep->any(), (int)env_i64("TFX_SOS_VARIANT", -1));
+    int LC = variant >= 4 ? 64 : ((variant & 1) ? 16 : 32);
+    // Cascades whose lane scan costs the result accuracy (poles next to z = 1 under a rough output; plan_refine, decided per
+    // cascade and for the dtype of the result) take the refined kernels.  Those exist for the shipping geometry only: LC = 64
+    // on aligned rows, LC = 32 on the dword path; LC = 16 for the rare dtype mixes and the sum mode as before.  The decision
+    // is made at the tile size of that geometry -- the one the refined launch runs -- whatever TFX_SOS_VARIANT asks for: a
+    // variant with fewer samples per lane is never left unrefined where the shipping one is refined.  Every other cascade runs the kernel, and computes the bits, it did without this rule.
+    const int lc_rule = (rare || sum_bands) ? LC : (vec ? 64 : 32);
+    const bool refine = !f32 && plan_refine(pl, lc_rule, y_dtype == TFX_F64);
+    if (refine && !rare && !sum_bands) { variant = vec ? 4 : 0; LC = lc_rule; }
     // fused into the kernel on the main path (float32 I/O, aligned rows, no taps, single cascade); everything
     // else runs the plain kernel and the same arithmetic as separate passes over y
     const bool ep_fused = ep->any() && !rare && !sum_bands && !y_sections && vec;
@@ -1429,6 +1639,7 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in,
     p.ep_partial = nullptr; p.ep_host = ep;
     p.ep_fused = ep_fused ? 1 : 0;
     if (!ep_fused) { p.ep_scale = p.ep_clamp = 0; p.ep_stat = -1; }
+    p.refine = refine ? 1 : 0;
     table_for(p, pl, f32, LC, unit);
 
     const int64_t warm = pl->warm;         // segmentation is decided per kernel instance (launch_one)
@@ -1630,7 +1841,11 @@ void sos_block_energy_forward(const void *x, int x_dtype, double *s, int64_t C, 
     p.ep_stat = -1;
     p.ms_num = num; p.ms_den = den; p.ms_nblk = bp.nblk; p.ms_bps = bp.bps;
     // the segmentation above is final (block_energy_plan): launch_one takes it as it is
-    if (x_dtype == TFX_F32) launch_one<float, float, double, MS_LC, false, false, false, 2, false, false, false, 0, false, true>(p, pl->warm, stream);
+    // the energies are float64 results: a cascade whose lane scan costs more than the float64 recursion itself refines it
+    if (plan_refine(pl, MS_LC, true)) {
+        if (x_dtype == TFX_F32) launch_one<float, float, double, MS_LC, false, false, false, 2, false, false, false, 0, true, true>(p, pl->warm, stream);
+        else launch_one<double, double, double, MS_LC, false, false, false, 2, false, false, false, 0, true, true>(p, pl->warm, stream);
+    } else if (x_dtype == TFX_F32) launch_one<float, float, double, MS_LC, false, false, false, 2, false, false, false, 0, false, true>(p, pl->warm, stream);
     else launch_one<double, double, double, MS_LC, false, false, false, 2, false, false, false, 0, false, true>(p, pl->warm, stream);
 }
 
@@ -1829,6 +2044,22 @@ void sos_plan_info(const double *sos_host, int64_t K, int *precision, int64_t *w
     if (precision) *precision = (eb <= auto_bound()) ? TFX_PREC_F32 : TFX_PREC_F64;
     if (warmup) *warmup = pl->warm;
     if (err_bound) *err_bound = eb;
+}
+
+// The float64-arithmetic facts of a cascade: whether it runs the unit-b0 form on the shipping geometry, and the refinement
+// rule (plan_refine) with what it was decided on, at the two tile sizes that matter: LC = 64 (float32 signals, aligned rows)
+// and LC = 16 (float64 results: the other dtype mixes, banks, the sum mode).  errs = {blocked, seq} at LC = 64, then at LC = 16.
+void sos_refine_info(const double *sos_host, int64_t K, int *unit_form, int *refine_f32, int *refine_f64, double *errs)
+{
+    const std::shared_ptr<SosPlan> plan = get_plan(sos_host, K, nullptr, 1);
+    SosPlan *pl = plan.get();
+    if (unit_form) *unit_form = plan_unit_ok(pl) ? 1 : 0;
+    if (refine_f32) *refine_f32 = plan_refine(pl, 64, false) ? 1 : 0;
+    if (refine_f64) *refine_f64 = plan_refine(pl, 16, true) ? 1 : 0;
+    if (errs) {
+        const BlockedError a = plan_blocked_error(pl, 64), b = plan_blocked_error(pl, 16);
+        errs[0] = a.blocked; errs[1] = a.seq; errs[2] = b.blocked; errs[3] = b.seq;
+    }
 }
 
 }  // namespace tfx

@@ -458,9 +458,13 @@ def interleave_forward(x: Tensor, frame_base: int = 0, frames: int | None = None
 
 
 # ---- host-only planning queries (no tensors, no GPU needed): ctypes over the C ABI --------------------
-def sos_plan_info(sos) -> dict:
+def sos_plan_info(sos, refine: bool = True) -> dict:
     """Host-side plan facts for an SOS matrix: warm-up halo length, the float32 error estimate and what
-    ``precision='auto'`` would choose."""
+    ``precision='auto'`` would choose; ``unit_form`` (float32 signals on aligned rows run the unit-b0 form) and the
+    refinement rule of the float64 arithmetic (``tfx_sos_refine_info``): ``refine_f32`` / ``refine_f64`` = launches with a
+    float32 / float64 result take the kernels with refined start states, decided on ``blocked_error`` against
+    ``sequential_error`` (each at 64 and at 16 samples per lane).  ``refine=False`` leaves those five out and with them the
+    host replay they rest on (about 10 ms for four sections, once per plan and tile size)."""
     lib = L.load()
     s = np.ascontiguousarray(sos.detach().cpu().numpy() if isinstance(sos, Tensor) else sos, dtype=np.float64)
     if s.ndim != 2 or s.shape[-1] != 6:
@@ -468,8 +472,16 @@ def sos_plan_info(sos) -> dict:
     prec, warm, eb = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_double(0.0)
     L.check(lib.tfx_sos_plan_info(s.ctypes.data_as(ctypes.c_void_p), s.shape[0],
                                   ctypes.byref(prec), ctypes.byref(warm), ctypes.byref(eb)))
+    if not refine:          # the warm-up and the float32 estimate alone: no replay of the float64 kernel (about 10 ms per plan)
+        return {"auto_precision": "f32" if prec.value == L.PREC_F32 else "f64",
+                "warmup": warm.value, "f32_error_bound": eb.value}
+    unit, r32, r64, errs = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), (ctypes.c_double * 4)()
+    L.check(lib.tfx_sos_refine_info(s.ctypes.data_as(ctypes.c_void_p), s.shape[0], ctypes.byref(unit), ctypes.byref(r32),
+                                    ctypes.byref(r64), errs))
     return {"auto_precision": "f32" if prec.value == L.PREC_F32 else "f64",
-            "warmup": warm.value, "f32_error_bound": eb.value}
+            "warmup": warm.value, "f32_error_bound": eb.value,
+            "unit_form": bool(unit.value), "refine_f32": bool(r32.value), "refine_f64": bool(r64.value),
+            "blocked_error": (errs[0], errs[2]), "sequential_error": (errs[1], errs[3])}
 
 
 def env_reload() -> None:

@@ -176,7 +176,7 @@ def _iir_as_fir(sos_t: Tensor, max_taps: int = 1 << 17) -> nn.Module | None:
         if key in _IIR_FIR:
             _IIR_FIR.move_to_end(key)
             return _IIR_FIR[key]
-    w = torchfx_ext.sos_plan_info(sos)["warmup"]
+    w = torchfx_ext.sos_plan_info(sos, refine=False)["warmup"]
     fir = None
     if 0 <= w <= max_taps:
         imp = np.zeros(int(w) + 1)
