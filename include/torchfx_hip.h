@@ -484,6 +484,25 @@ int tfx_resample_stream_plan_info(int64_t consumed, int64_t T, int64_t up, int64
                                   int64_t *lds_bytes);
 
 /* ---------------------------------------------------------------------------
+ * tfx_true_peak_forward -- the true-peak reading of ITU-R BS.1770-4 Annex 2 per row: peak[r] = max_m |y[r, m]| over the
+ * T * up outputs y = tfx_resample_forward(x, up, down = 1) with the caller's interpolation filter, the up-sampled signal never
+ * stored.  Every y[m] is tfx_resample_forward's fma chain, so a finite row gives the bits of max |.| over that call's output.
+ * A row with a NaN sample reads NaN, a row with an Inf sample NaN or +Inf; other rows are unaffected.
+ * x DEVICE [rows, T] of dtype (float32 / float64); peak DEVICE [rows] of dtype (linear, not dB); up 2, 4 or 8; taps_host HOST
+ * [nh] of dtype, already scaled by up, nh <= 64 * up (the taps of a phase are held in registers); work DEVICE [work_elems] of
+ * dtype (tfx_true_peak_plan_info), the per-tile maxima, the caller's to reuse once the call has run.  Two launches, no atomics;
+ * the tiling depends on T, up and nh alone, so a row's bits do not depend on the batch.  The polyphase table is the one
+ * tfx_resample_forward caches.  Arguments are checked before the device is touched.  rows * T == 0 writes nothing (a row of no
+ * samples has peak 0: the caller's to set).
+ * ------------------------------------------------------------------------- */
+int tfx_true_peak_forward(const void *x, int dtype, void *peak, int64_t rows, int64_t T, int64_t up,
+                          const void *taps_host, int64_t nh, void *work, tfx_stream_t stream);
+/* what tfx_true_peak_forward does for rows of T samples (host-only, same checks): taps per phase Lp, the input positions per
+ * workgroup tile_in, the tiles per row and the elements of `work` (rows * tiles) */
+int tfx_true_peak_plan_info(int64_t rows, int64_t T, int64_t up, int64_t nh, int dtype,
+                            int64_t *Lp, int64_t *tile_in, int64_t *tiles, int64_t *work_elems);
+
+/* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of
  * ParallelFilterCombination.forward, src/torchfx/filter/__base.py:1019-1026).
  * xs_host: HOST array of n DEVICE pointers, each [numel] of dtype.

@@ -77,6 +77,9 @@ SIGNATURES = {
     "tfx_resample_stream_plan_info": (_int, [_i64, _i64, _i64, _i64, _i64, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                              ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                              ctypes.POINTER(_int), ctypes.POINTER(_i64)]),
+    "tfx_true_peak_forward": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "tfx_true_peak_plan_info": (_int, [_i64, _i64, _i64, _i64, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                       ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "tfx_sum_forward": (_int, [_vp, _int, _vp, _int, _i64, _vp]),
     "tfx_gain_forward": (_int, [_vp, _vp, _int, _i64, _dbl, _int, _vp]),
     "tfx_stat_forward": (_int, [_vp, _int, _i64, _i64, _int, _int, _vp, _vp]),

@@ -63,6 +63,12 @@ void resample_stream_plan_info(int64_t consumed, int64_t T, int64_t up, int64_t 
                                int64_t *out_end, int64_t *hist_len, int64_t *pre_remove, int64_t *Lp, int *kernel,
                                int64_t *lds_bytes);
 void resample_clear();
+void true_peak_check(const void *x, int dtype, const void *peak, int64_t rows, int64_t T, int64_t up, const void *taps_host,
+                     int64_t nh, const void *work);
+void true_peak_forward(const void *x, int dtype, void *peak, int64_t rows, int64_t T, int64_t up, const void *taps_host, int64_t nh,
+                       void *work, hipStream_t stream);
+void true_peak_plan_info(int64_t rows, int64_t T, int64_t up, int64_t nh, int dtype, int64_t *Lp, int64_t *tile_in, int64_t *tiles,
+                         int64_t *work_elems);
 // layout.hip
 void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, int64_t C, int64_t ld_out, int64_t f_base,
                           double scale, hipStream_t stream);
@@ -677,6 +683,24 @@ int tfx_resample_stream_plan_info(int64_t consumed, int64_t T, int64_t up, int64
     TFX_API_BEGIN
     TFX_CHECK(out_begin && out_end && hist_len && n_pre_remove && Lp && kernel && lds_bytes, "resample_stream_plan_info: null output");
     resample_stream_plan_info(consumed, T, up, down, nh, dtype, out_begin, out_end, hist_len, n_pre_remove, Lp, kernel, lds_bytes);
+    TFX_API_END
+}
+
+int tfx_true_peak_forward(const void *x, int dtype, void *peak, int64_t rows, int64_t T, int64_t up, const void *taps_host,
+                          int64_t nh, void *work, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    true_peak_check(x, dtype, peak, rows, T, up, taps_host, nh, work);    // before anything touches the device
+    true_peak_forward(x, dtype, peak, rows, T, up, taps_host, nh, work, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_true_peak_plan_info(int64_t rows, int64_t T, int64_t up, int64_t nh, int dtype, int64_t *Lp, int64_t *tile_in,
+                            int64_t *tiles, int64_t *work_elems)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(Lp && tile_in && tiles && work_elems, "true_peak_plan_info: null output");
+    true_peak_plan_info(rows, T, up, nh, dtype, Lp, tile_in, tiles, work_elems);
     TFX_API_END
 }
 

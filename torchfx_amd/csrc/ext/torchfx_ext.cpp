@@ -470,6 +470,36 @@ Tensor sos_block_energy_op(const Tensor &x_in, const Tensor &sos_cpu, int64_t nu
     return s;
 }
 
+// True peak per row (tfx_true_peak_forward): x [..., T] -> [...] of x's dtype, the linear max |.| over the T * up outputs of
+// resample_forward(x, up, 1, taps); taps HOST [nh] in x's dtype, already scaled by up.  The per-tile maxima are a temporary
+// tensor of PyTorch's allocator.  A row of no samples has peak 0.
+std::vector<int64_t> true_peak_shape(const Tensor &x)
+{
+    TORCH_CHECK(x.dim() >= 1, "true_peak: x must have a time dimension");
+    return std::vector<int64_t>(x.sizes().begin(), x.sizes().end() - 1);
+}
+
+Tensor true_peak_op(const Tensor &x_in, const Tensor &taps, int64_t up)
+{
+    need_device(x_in, "x");
+    const std::vector<int64_t> shape = true_peak_shape(x_in);
+    TORCH_CHECK(!taps.is_cuda() && taps.dim() == 1 && taps.numel() >= 1, "true_peak: taps must be a non-empty 1-D host tensor");
+    TORCH_CHECK(taps.scalar_type() == x_in.scalar_type(), "true_peak: taps must have x's dtype (", x_in.scalar_type(), "), got ",
+                taps.scalar_type());
+    const Tensor x = x_in.contiguous(), hc = taps.contiguous();
+    const int64_t T = x.size(-1), rows = stream_rows(x);
+    const int dt = dtype_code(x, "true_peak");
+    int64_t Lp = 0, tile_in = 0, tiles = 0, work_elems = 0;
+    check_rc(tfx_true_peak_plan_info(rows, T, up, hc.numel(), dt, &Lp, &tile_in, &tiles, &work_elems), "true_peak");
+    if (rows * T == 0) return at::zeros(shape, x.options());
+    Tensor peak = at::empty(shape, x.options()), work = at::empty({work_elems}, x.options());
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_true_peak_forward(x.data_ptr(), dt, peak.data_ptr(), rows, T, up, hc.data_ptr(), hc.numel(), work.data_ptr(),
+                                   stream_of(x)),
+             "true_peak");
+    return peak;
+}
+
 // One chunk of a resampling stream (tfx_resample_stream_forward): x [..., T] after `consumed` samples per row, h as for
 // resample_forward, hist [rows, H] (None = silence) -> (y [..., M(consumed + T) - M(consumed)], new history [rows, H])
 struct ResampleStreamPlan {
@@ -875,6 +905,7 @@ TORCH_LIBRARY(torchfx_hip, m)
     m.def("resample_forward(Tensor x, int up, int down, Tensor h) -> Tensor");
     m.def("sos_filtfilt(Tensor x, Tensor sos_cpu, int padtype=0, int padlen=-1) -> Tensor");
     m.def("sos_block_energy(Tensor x, Tensor sos_cpu, int num, int den=1) -> Tensor");
+    m.def("true_peak(Tensor x, Tensor taps_cpu, int up) -> Tensor");
     m.def("resample_stream_forward(Tensor x, Tensor h, Tensor? hist, int up, int down, int consumed) -> (Tensor, Tensor)");
     m.def("delay_forward_ep(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong, float gain, bool clamp, int stat_mode, "
           "bool per_row) -> (Tensor, Tensor)");
@@ -914,6 +945,7 @@ TORCH_LIBRARY_IMPL(torchfx_hip, CUDA, m)          // "CUDA" is the dispatch key 
     m.impl("resample_forward", resample_op);
     m.impl("sos_filtfilt", sos_filtfilt_op);
     m.impl("sos_block_energy", sos_block_energy_op);
+    m.impl("true_peak", true_peak_op);
     m.impl("resample_stream_forward", resample_stream_op);
     m.impl("delay_forward_ep", delay_ep_op);
     m.impl("delay_stream_forward", delay_stream_op);
@@ -951,6 +983,7 @@ TORCH_LIBRARY_IMPL(torchfx_hip, Meta, m)
     m.impl("sos_block_energy", [](const Tensor &x, const Tensor &sos, int64_t num, int64_t den) {
         return at::empty(sos_block_energy_shape(x, sos, num, den), x.options().dtype(at::kDouble));
     });
+    m.impl("true_peak", [](const Tensor &x, const Tensor &, int64_t) { return at::empty(true_peak_shape(x), x.options()); });
     m.impl("resample_stream_forward", resample_stream_meta);
     m.impl("delay_forward_ep", delay_ep_meta);
     m.impl("delay_stream_forward", delay_stream_meta);
@@ -972,7 +1005,7 @@ static void no_cpu_boxed(const c10::OperatorHandle &op, c10::DispatchKeySet, tor
 TORCH_LIBRARY_IMPL(torchfx_hip, CPU, m)
 {
     for (const char *name : {"sos_forward", "sos_forward_sections", "sos_bank_forward", "sos_bank_sum_forward", "biquad_forward",
-                             "delay_line_forward", "delay_forward", "delay_forward_ep", "delay_stream_forward", "delay_line_stream_forward", "resample_forward", "sos_filtfilt", "sos_block_energy", "resample_stream_forward", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
+                             "delay_line_forward", "delay_forward", "delay_forward_ep", "delay_stream_forward", "delay_line_stream_forward", "resample_forward", "sos_filtfilt", "sos_block_energy", "true_peak", "resample_stream_forward", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
                              "fft_conv_forward_ep", "sos_fft_conv_forward", "normalize_apply", "sum_forward", "gain_forward", "quantile_abs", "stat_forward",
                              "normalize_forward", "deinterleave_forward", "deinterleave_into", "interleave_forward"})
         m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());

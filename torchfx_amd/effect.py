@@ -166,12 +166,21 @@ class LoudnessNormalize(FX):
     The gain stays on the signal's device: nothing is read back between measuring and applying.  A signal that measures
     ``-inf`` (silence, or shorter than 400 ms) is left unchanged, as ``Normalize`` leaves an all-zero signal; a NaN measurement
     gives NaN samples.  ``fs`` comes from the ``Wave`` the effect is piped into when it is None.  A whole-signal measurement:
-    it is a step of its own in ``Wave.plan()`` and cannot run in a chunked stream."""
+    it is a step of its own in ``Wave.plan()`` and cannot run in a chunked stream.
 
-    def __init__(self, target: float = -23.0, channel_weights: tp.Sequence[float] | None = None, fs: int | None = None) -> None:
+    ``max_true_peak`` (dBTP, default None = no ceiling) caps the gain so that the programme true peak ``TP`` of the result
+    -- the largest channel's reading of the ``[C, T]`` signal or batch item, :func:`torchfx_amd.loudness.true_peak` on the
+    same input -- does not pass it: the gain in dB is ``min(target - L, max_true_peak - TP)``.  The ceiling only lowers
+    the gain; it does not limit."""
+
+    def __init__(self, target: float = -23.0, channel_weights: tp.Sequence[float] | None = None, fs: int | None = None,
+                 max_true_peak: float | None = None) -> None:
         super().__init__()
         if not math.isfinite(target):
             raise ValueError(f"target must be a finite loudness in LUFS, got {target!r}")
+        if max_true_peak is not None and not math.isfinite(max_true_peak):
+            raise ValueError(f"max_true_peak must be None or a finite level in dBTP, got {max_true_peak!r}")
+        self.max_true_peak = None if max_true_peak is None else float(max_true_peak)
         self.target = float(target)
         self.channel_weights = None if channel_weights is None else tuple(float(w) for w in channel_weights)
         self.fs = fs
@@ -190,8 +199,21 @@ class LoudnessNormalize(FX):
             info = _ext().sos_block_energy_plan_info(kweighting_sos(self.fs), rows, n, self.fs, 10)
         except (RuntimeError, ValueError) as e:
             return f"refused -- {e}"
-        return (f"native (sos_block_energy_kernel, {info['nblk']} sub-blocks of 100 ms, {info['nseg']} segment(s) per row; "
+        text = (f"native (sos_block_energy_kernel, {info['nblk']} sub-blocks of 100 ms, {info['nseg']} segment(s) per row; "
                 "gating and gain on the device)")
+        if self.max_true_peak is None:
+            return text
+        from torchfx_amd.loudness import default_oversample
+        from torchfx_amd.resample import design_taps
+
+        up = default_oversample(self.fs)
+        if up == 1:
+            return text + " + native (stat_forward, sample peak per row)"
+        try:
+            tp_info = _ext().true_peak_plan_info(rows, n, up, int(design_taps(up, 1, dtype=x.dtype).numel()), x.dtype)
+        except (RuntimeError, ValueError) as e:
+            return f"refused -- {e}"
+        return text + f" + native (true_peak_kernel, {up}x oversampled, {tp_info['tiles']} tile(s) per row)"
 
     @torch.no_grad()
     def forward(self, waveform: Tensor) -> Tensor:
@@ -200,12 +222,19 @@ class LoudnessNormalize(FX):
         from torchfx_amd.loudness import integrated_loudness
 
         loud = integrated_loudness(waveform, self.fs, self.channel_weights)
-        gain = torch.pow(10.0, (self.target - loud) / 20.0)
+        gain_db = self.target - loud
+        if self.max_true_peak is not None:
+            from torchfx_amd.loudness import true_peak
+
+            peak = true_peak(waveform, self.fs)
+            gain_db = torch.minimum(gain_db, self.max_true_peak - (peak.amax(-1) if peak.dim() else peak))
+        gain = torch.pow(10.0, gain_db / 20.0)
         gain = torch.where(torch.isneginf(loud), torch.ones_like(gain), gain).to(waveform.dtype)
         return waveform * (gain.view(-1, 1, 1) if gain.dim() else gain)
 
     def extra_repr(self) -> str:
-        return f"target={self.target}, channel_weights={self.channel_weights}, fs={self.fs}"
+        ceiling = "" if self.max_true_peak is None else f", max_true_peak={self.max_true_peak}"
+        return f"target={self.target}, channel_weights={self.channel_weights}, fs={self.fs}{ceiling}"
 
 
 class Epilogued(FX):

@@ -1,5 +1,6 @@
 """Programme loudness after ITU-R BS.1770-4 / EBU R128: :func:`integrated_loudness` (LUFS, two-stage gating),
-:func:`momentary_loudness`, :func:`short_term_loudness` and the measurement under them, :func:`block_energy`.
+:func:`momentary_loudness`, :func:`short_term_loudness`, :func:`loudness_range` (LU, EBU Tech 3342) and the measurement under
+them, :func:`block_energy`; and the true peak of BS.1770-4 Annex 2, :func:`true_peak` (dBTP) / :func:`true_peak_linear`.
 
 Everything is built on ONE array per signal: the energy of the K-weighted signal in consecutive 100 ms sub-blocks,
 ``S[.., c, i] = sum(y[c, e_i : e_(i+1)] ** 2)`` with ``e_i = (i * fs) // 10`` and ``y`` the float64 K-weighting cascade of
@@ -7,7 +8,12 @@ channel ``c`` from zero state.  A 400 ms gating block with 75 % overlap is four 
 window thirty.  On ROCm device float32 / float64 tensors one HIP launch computes ``S`` (``csrc/sos.hip``,
 :func:`torchfx_ext.sos_block_energy`): it reads the signal once and never stores the filtered one.  CPU tensors run SciPy's
 ``sosfilt`` and NumPy in float64.  The gating is a few torch ops on the ``[.., nblk]`` array, on the signal's device, with
-no host synchronisation.  True peak, loudness range and a streaming meter are not provided.
+no host synchronisation.
+
+The true peak is the largest magnitude of the signal oversampled to at least 192 kHz with the library's own interpolator
+(:func:`torchfx_amd.resample.resample_poly`).  On device tensors two HIP launches compute it per row (``csrc/resample.hip``,
+:func:`torchfx_ext.true_peak`): they read the signal once and never store the oversampled one.  CPU tensors run SciPy's
+``resample_poly``.  A streaming meter is not provided.
 """
 from __future__ import annotations
 
@@ -20,6 +26,10 @@ from torch import Tensor
 
 ABSOLUTE_GATE = -70.0          # LUFS
 RELATIVE_GATE = -10.0          # LU under the mean of the absolutely gated blocks
+LRA_RELATIVE_GATE = -20.0      # Tech 3342: LU under the mean of the absolutely gated short-term windows
+LRA_LOW, LRA_HIGH = 10, 95     # Tech 3342: the percentiles whose spread is the loudness range
+OVERSAMPLE_FACTORS = (1, 2, 4, 8)
+MAX_TAPS_PER_PHASE = 64        # the native kernel holds a phase's taps in registers
 OFFSET = -0.691                # BS.1770: L = -0.691 + 10 log10(sum_c w_c z_c)
 
 
@@ -157,3 +167,103 @@ def integrated_loudness(x: Tensor, fs: int, channel_weights=None) -> Tensor:
     out = _lufs(torch.where(both, p, zero).sum(-1) / both.sum(-1))
     out = torch.where(n_abs > 0, out, torch.full_like(out, -math.inf))
     return torch.where(torch.isnan(p).any(-1), torch.full_like(out, math.nan), out)
+
+
+@torch.no_grad()
+def loudness_range(x: Tensor, fs: int, channel_weights=None) -> Tensor:
+    """Loudness range (LRA) in LU after EBU Tech 3342: float64 on ``x``'s device, 0-d for ``[T]`` and ``[C, T]``, ``[B]`` for
+    ``[B, C, T]``.
+
+    The short-term values ``l_j`` (3 s windows, 100 ms hop) with ``l_j > -70`` pass the absolute gate; the relative gate
+    lies 20 LU under the loudness of their mean power; of the ``n`` values that pass both, sorted, the range is
+    ``v[(95 (n - 1) + 50) // 100] - v[(10 (n - 1) + 50) // 100]`` -- Tech 3342's nearest-rank percentiles, halves rounded up.
+    ``0.0`` when no window passes or the signal is shorter than 3 s; NaN when any window is NaN.  No host synchronisation:
+    the values that fail are masked to ``+inf`` before the sort and the two ranks are gathered on the device."""
+    p, count = _window_power(x, fs, channel_weights, 30)
+    if count == 0:
+        return torch.zeros(p.shape[:-1], dtype=torch.float64, device=p.device)
+    lj = _lufs(p)
+    zero = torch.zeros((), dtype=torch.float64, device=p.device)
+    above = lj > ABSOLUTE_GATE
+    gate = _lufs(torch.where(above, p, zero).sum(-1) / above.sum(-1)) + LRA_RELATIVE_GATE
+    both = above & (lj > gate.unsqueeze(-1))
+    n = both.sum(-1, keepdim=True)
+    v = torch.sort(torch.where(both, lj, torch.full_like(lj, math.inf)), dim=-1).values
+    last = (n - 1).clamp(min=0)
+    low = torch.div(LRA_LOW * last + 50, 100, rounding_mode="floor")
+    high = torch.div(LRA_HIGH * last + 50, 100, rounding_mode="floor")
+    out = (v.gather(-1, high) - v.gather(-1, low)).squeeze(-1)
+    out = torch.where(n.squeeze(-1) > 0, out, torch.zeros_like(out))
+    return torch.where(torch.isnan(p).any(-1), torch.full_like(out, math.nan), out)
+
+
+def default_oversample(fs: int) -> int:
+    """BS.1770-4 Annex 2 oversamples to at least 192 kHz: 4 below 96 kHz, 2 below 192 kHz, 1 (the sample peak) from there."""
+    return 4 if fs < 96000 else 2 if fs < 192000 else 1
+
+
+def _interpolator(taps, oversample: int, dtype: torch.dtype):
+    """The caller's interpolation filter (already scaled by ``oversample``) as a 1-D host tensor of ``dtype``; None = the
+    library's own design."""
+    if taps is None:
+        return None
+    a = taps.detach().cpu().numpy() if isinstance(taps, Tensor) else np.asarray(taps)
+    if a.ndim != 1 or a.size == 0:
+        raise ValueError(f"true_peak: taps must be a non-empty 1-D array, got shape {a.shape}")
+    if a.size > MAX_TAPS_PER_PHASE * oversample:
+        raise ValueError(f"true_peak: {a.size} taps, at most {MAX_TAPS_PER_PHASE} * oversample = "
+                         f"{MAX_TAPS_PER_PHASE * oversample} are supported")
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64 if dtype == torch.float64 else np.float32))
+
+
+@torch.no_grad()
+def true_peak_linear(x: Tensor, fs: int, oversample: int | None = None, taps=None) -> Tensor:
+    """:func:`true_peak` as a linear magnitude in the signal's dtype (same shapes): ``max |resample_poly(row, L, 1)|`` over
+    that function's ``T * L`` outputs, ``0`` for a row of no samples."""
+    _check_signal(x, "true_peak")
+    fs = _check_fs(fs)
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"true_peak: float32 or float64 signals only, got {x.dtype}")
+    if oversample is None:
+        oversample = default_oversample(fs)
+    if isinstance(oversample, bool) or oversample not in OVERSAMPLE_FACTORS:
+        raise ValueError(f"true_peak: oversample must be one of {OVERSAMPLE_FACTORS}, got {oversample!r}")
+    up = int(oversample)
+    h = _interpolator(taps, up, x.dtype)
+    if x.shape[-1] == 0:
+        return torch.zeros(x.shape[:-1], dtype=x.dtype, device=x.device)
+    if not x.is_cuda:
+        if up == 1:
+            return x.abs().amax(-1)
+        from torchfx_amd.resample import resample_poly
+
+        # resample_poly takes the filter before its `h *= up`; up is a power of two, so the division is exact
+        window = ("kaiser", 5.0) if h is None else (h / up).numpy()
+        return resample_poly(x, up, 1, window=window).abs().amax(-1)
+    from torchfx_amd import torchfx_ext
+
+    with torch.cuda.device(x.device):
+        if up == 1:
+            return torchfx_ext.stat_forward(x, torchfx_ext.STAT_ABSMAX, per_row=True).reshape(x.shape[:-1]).to(x.dtype)
+        if h is None:
+            from torchfx_amd.resample import design_taps
+
+            h = design_taps(up, 1, ("kaiser", 5.0), x.dtype)
+        return torchfx_ext.true_peak(x, h, up)
+
+
+@torch.no_grad()
+def true_peak(x: Tensor, fs: int, oversample: int | None = None, taps=None) -> Tensor:
+    """True peak in dBTP per channel after ITU-R BS.1770-4 Annex 2: ``x [T]``, ``[C, T]`` or ``[B, C, T]`` (float32 /
+    float64) -> float64 on ``x``'s device, 0-d for ``[T]``, ``[C]`` for ``[C, T]``, ``[B, C]`` for ``[B, C, T]``.  The
+    programme figure is the largest channel's, ``true_peak(x, fs).amax(-1)``.
+
+    The reading of a row is ``20 log10 max |resample_poly(row, L, 1, window=("kaiser", 5.0))|`` over exactly that function's
+    ``T * L`` outputs.  ``oversample`` = ``L`` is 1, 2, 4 or 8; None picks 4 below 96 kHz, 2 below 192 kHz and 1 from there
+    (Annex 2: oversample to at least 192 kHz); ``L = 1`` is the sample peak.  The interpolator is
+    :func:`torchfx_amd.resample.design_taps` ``(L, 1)`` (``firwin``, ``20 L + 1`` taps, scaled by ``L``); ``taps`` replaces
+    it with the caller's own 1-D filter, already scaled by ``L`` and at most ``64 L`` long (the table in Annex 2 is one such
+    filter).  Silence reads ``-inf``; a row with a NaN sample reads NaN, a row with an Inf sample NaN or ``+inf``; other rows
+    are unaffected.  Device tensors run the HIP kernel, CPU tensors SciPy's ``resample_poly`` in the signal's dtype; no
+    host synchronisation."""
+    return 20.0 * torch.log10(true_peak_linear(x, fs, oversample, taps).to(torch.float64))

@@ -35,7 +35,7 @@ __all__ = [
     "biquad_forward", "sos_forward", "sos_bank_forward", "sos_bank_sum_forward", "delay_line_forward", "delay_forward",
     "delay_amplitudes", "delay_regime", "delay_stream_forward", "delay_line_stream_forward", "resample_forward",
     "resample_plan_info", "resample_stream_forward", "resample_stream_plan_info", "sos_filtfilt", "sos_filtfilt_plan_info",
-    "sos_block_energy", "sos_block_energy_plan_info",
+    "sos_block_energy", "sos_block_energy_plan_info", "true_peak", "true_peak_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
 ]
@@ -252,6 +252,24 @@ def sos_block_energy_plan_info(sos, rows: int, length: int, num: int, den: int =
     L.check(L.load().tfx_sos_block_energy_plan_info(int(rows), int(length), a.ctypes.data, a.shape[0], int(num), int(den),
                                                     ctypes.byref(nblk), ctypes.byref(nseg), ctypes.byref(warm)))
     return {"nblk": nblk.value, "nseg": nseg.value, "warm": warm.value}
+
+
+def true_peak(x: Tensor, taps: Tensor, up: int) -> Tensor:
+    """The linear true peak per row in two launches (``tfx_true_peak_forward``): ``max |resample_forward(x, up, 1, taps)|``
+    over the last axis, bit for bit on finite rows, without storing the up-sampled signal.  ``x [..., T]`` on the device
+    (float32 / float64) -> ``[...]`` of its dtype; ``taps`` a 1-D host tensor in ``x``'s dtype, already scaled by ``up``
+    (2, 4 or 8), at most ``64 * up`` long.  A row with a NaN sample reads NaN."""
+    return native.ops().true_peak(x.contiguous(), taps, int(up))
+
+
+def true_peak_plan_info(rows: int, length: int, up: int, taps: int, dtype: torch.dtype = torch.float32) -> dict:
+    """What :func:`true_peak` does for ``rows`` rows of ``length`` samples and a filter of ``taps`` taps
+    (``tfx_true_peak_plan_info``; host-only, same argument checks): ``Lp`` (taps per phase), ``tile_in`` (input positions per
+    workgroup), ``tiles`` per row and ``work_elems`` (the per-tile maxima).  The tiling does not depend on ``rows``."""
+    o = [ctypes.c_int64(0) for _ in range(4)]
+    L.check(L.load().tfx_true_peak_plan_info(int(rows), int(length), int(up), int(taps),
+                                             L.TFX_F64 if dtype == torch.float64 else L.TFX_F32, *[ctypes.byref(v) for v in o]))
+    return {"Lp": o[0].value, "tile_in": o[1].value, "tiles": o[2].value, "work_elems": o[3].value}
 
 
 RESAMPLE_STREAM_KERNELS = ("resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel", "copy")

@@ -694,6 +694,20 @@ class Wave:
 
         return float(integrated_loudness(self.ys, self.fs, channel_weights))
 
+    def true_peak(self, oversample: int | None = None) -> float:
+        """True peak of the (materialised) programme in dBTP -- the largest channel's reading (ITU-R BS.1770-4 Annex 2,
+        :func:`torchfx_amd.loudness.true_peak`); ``-inf`` for silence."""
+        from torchfx_amd.loudness import true_peak
+
+        return float(true_peak(self.ys, self.fs, oversample).max())
+
+    def loudness_range(self, channel_weights=None) -> float:
+        """Loudness range of the (materialised) signal in LU (EBU Tech 3342,
+        :func:`torchfx_amd.loudness.loudness_range`); ``0.0`` for silence or less than 3 s."""
+        from torchfx_amd.loudness import loudness_range
+
+        return float(loudness_range(self.ys, self.fs, channel_weights))
+
     def resample(self, new_fs: int, window=("kaiser", 5.0)) -> "Wave":
         """``self | Resample(new_fs, window=window)``: the signal at ``new_fs`` (``scipy.signal.resample_poly`` semantics)."""
         from torchfx_amd.resample import Resample
