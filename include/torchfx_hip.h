@@ -503,6 +503,37 @@ int tfx_true_peak_plan_info(int64_t rows, int64_t T, int64_t up, int64_t nh, int
                             int64_t *Lp, int64_t *tile_in, int64_t *tiles, int64_t *work_elems);
 
 /* ---------------------------------------------------------------------------
+ * tfx_limiter_forward -- look-ahead true-peak limiter in ONE launch.  x is [groups, channels, T]; the `channels` rows of a
+ * group share one gain curve.  All arithmetic in dtype, for a group and sample positions n, i, k:
+ *   1. q[ch,i] = max_{ph<up} |v[ch, i*up + ph]|, v = tfx_resample_forward(x[ch], up, down = 1) with taps_host (that call's fma
+ *      chain, as tfx_true_peak_forward); q[ch,-1] = 0
+ *   2. p[i] = max_ch max(|x[ch,i]|, q[ch,i], q[ch,i-1]);  up == 1 (the sample peak, taps ignored): p[i] = max_ch |x[ch,i]|
+ *   3. r[i] = p[i] > c ? c / p[i] : 1 (correctly rounded), r = 1 outside [0, T)
+ *   4. m[k] = min r[k-H+1 .. k+A-1]
+ *   5. s[n]: acc = +0, then for j = A-1 down to 0: acc = fma(w[j], 1 - m[n-j], acc)
+ *   6. g[n] = min(max(1 - s[n], 0), r[n])
+ *   7. y[ch,n] = g[n] * x[ch,n]
+ * x, y DEVICE [groups, channels, T] of dtype (y may not alias x: tiles read their neighbours' inputs); gain DEVICE [groups, T]
+ * of dtype or null (g, the gain-reduction meter); c the linear ceiling (> 0, already rounded to dtype); A in [1, 512] and H in
+ * [1, 4096] samples; window_host HOST [A] of dtype, non-negative and finite (the caller normalises it to sum 1); up 1, 2, 4 or 8;
+ * taps_host HOST [nh] of dtype as for tfx_true_peak_forward (nh <= 64 * up; ignored for up == 1).
+ * No recursion: a workgroup computes `tile` consecutive outputs of one group from a bounded window, so a group's bits do not
+ * depend on the batch.  A tile whose staged window holds a NaN or an Inf in any channel writes NaN to all its outputs in every
+ * channel of the group (and to gain); other tiles and other groups are unaffected.  No atomics, no workspace.  The tap table
+ * and the padded window are cached by content, so once they have run the call can be captured into a HIP graph.  Arguments are
+ * checked before the device is touched.  groups * T == 0 writes nothing.
+ * ------------------------------------------------------------------------- */
+int tfx_limiter_forward(const void *x, void *y, void *gain_or_null, int dtype, int64_t groups, int64_t channels, int64_t T,
+                        double c, int64_t A, int64_t H, const void *window_host, int64_t up, const void *taps_host, int64_t nh,
+                        tfx_stream_t stream);
+/* what tfx_limiter_forward does (host-only, same checks on the sizes): outputs per workgroup `tile` (8193 - 2A - H), tiles per
+ * group, the input samples a tile reads behind its first and past its last output (halo_left, halo_right), taps per phase Lp
+ * (0 for up == 1) and the LDS bytes per workgroup.  The tiling depends on T, A, H, up, nh and dtype alone. */
+int tfx_limiter_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh, int dtype,
+                          int64_t *tile, int64_t *tiles, int64_t *halo_left, int64_t *halo_right, int64_t *Lp,
+                          int64_t *lds_bytes);
+
+/* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of
  * ParallelFilterCombination.forward, src/torchfx/filter/__base.py:1019-1026).
  * xs_host: HOST array of n DEVICE pointers, each [numel] of dtype.

@@ -69,6 +69,15 @@ void true_peak_forward(const void *x, int dtype, void *peak, int64_t rows, int64
                        void *work, hipStream_t stream);
 void true_peak_plan_info(int64_t rows, int64_t T, int64_t up, int64_t nh, int dtype, int64_t *Lp, int64_t *tile_in, int64_t *tiles,
                          int64_t *work_elems);
+// limiter.hip
+void limiter_check(const void *x, const void *y, int dtype, int64_t groups, int64_t channels, int64_t T, double c, int64_t A,
+                   int64_t H, const void *window_host, int64_t up, const void *taps_host, int64_t nh);
+void limiter_forward(const void *x, void *y, void *gain, int dtype, int64_t groups, int64_t channels, int64_t T, double c,
+                     int64_t A, int64_t H, const void *window_host, int64_t up, const void *taps_host, int64_t nh,
+                     hipStream_t stream);
+void limiter_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh, int dtype,
+                       int64_t *tile, int64_t *tiles, int64_t *halo_left, int64_t *halo_right, int64_t *Lp, int64_t *lds_bytes);
+void limiter_clear();
 // layout.hip
 void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, int64_t C, int64_t ld_out, int64_t f_base,
                           double scale, hipStream_t stream);
@@ -704,6 +713,26 @@ int tfx_true_peak_plan_info(int64_t rows, int64_t T, int64_t up, int64_t nh, int
     TFX_API_END
 }
 
+int tfx_limiter_forward(const void *x, void *y, void *gain_or_null, int dtype, int64_t groups, int64_t channels, int64_t T,
+                        double c, int64_t A, int64_t H, const void *window_host, int64_t up, const void *taps_host, int64_t nh,
+                        tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    limiter_check(x, y, dtype, groups, channels, T, c, A, H, window_host, up, taps_host, nh);    // before anything touches the device
+    limiter_forward(x, y, gain_or_null, dtype, groups, channels, T, c, A, H, window_host, up, taps_host, nh, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_limiter_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh, int dtype,
+                          int64_t *tile, int64_t *tiles, int64_t *halo_left, int64_t *halo_right, int64_t *Lp,
+                          int64_t *lds_bytes)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(tile && tiles && halo_left && halo_right && Lp && lds_bytes, "limiter_plan_info: null output");
+    limiter_plan_info(groups, channels, T, A, H, up, nh, dtype, tile, tiles, halo_left, halo_right, Lp, lds_bytes);
+    TFX_API_END
+}
+
 int tfx_sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, tfx_stream_t stream)
 {
     TFX_API_BEGIN
@@ -811,6 +840,7 @@ int tfx_clear_caches(void)
     olslds_clear();
     delay_clear();
     resample_clear();
+    limiter_clear();
     scratch_clear();
     TFX_API_END
 }

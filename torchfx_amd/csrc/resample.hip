@@ -16,6 +16,7 @@
 // All indices are 64-bit: (m + n_pre_remove) * down passes 2^31 on long rows.
 #include "common.h"
 #include "plan_cache.h"
+#include "polyphase.h"
 #include "../../include/torchfx_hip.h"
 
 #include <vector>
@@ -27,44 +28,12 @@ constexpr int64_t RS_LDS_BYTES = 49152;                  // three workgroups of 
 constexpr int64_t RS_EMAX = 64;                           // outputs per thread and tile
 enum { RS_REG = 0, RS_LDS = 1, RS_GATHER = 2, RS_COPY = 3 };
 
-// scipy.signal.resample_poly's arithmetic for a filter of nh taps (up, down already reduced)
-struct ResampleGeom {
-    int64_t n_out, pre_pad, post_pad, pre_remove, padded, Lp;
-};
-
-static int64_t floor_div(int64_t a, int64_t b) { return a / b - ((a % b != 0) && ((a < 0) != (b < 0))); }
-
-static ResampleGeom resample_geometry(int64_t T, int64_t up, int64_t down, int64_t nh)
-{
-    ResampleGeom g{};
-    g.n_out = ceil_div(T * up, down);
-    const int64_t half_len = (nh - 1) / 2;
-    g.pre_pad = down - half_len % down;
-    g.pre_remove = (half_len + g.pre_pad) / down;
-    // SciPy increments n_post_pad while _output_len(len, T, up, down) = ((T-1)*up + len - 1) // down + 1 < n_out + pre_remove;
-    // the least such pad in closed form (floor division: T = 0 gives a negative numerator)
-    const int64_t len0 = nh + g.pre_pad, need = g.n_out + g.pre_remove;
-    const int64_t have = floor_div((T - 1) * up + len0 - 1, down) + 1;
-    g.post_pad = have >= need ? 0 : down * (need - 1) - (T - 1) * up - len0 + 1;
-    g.padded = len0 + g.post_pad;
-    g.Lp = ceil_div(g.padded, up);
-    return g;
-}
-
 // workgroup geometry: G phase groups of `up` threads, E outputs per thread, `span` inputs in the tile's window
 struct ResampleTiling {
     int kernel;
     int64_t G, E, span, tile_out, lds;
     int64_t LP;                 // REG: taps held in registers (Lp rounded up to a bucket), else Lp
 };
-
-// register-tap buckets: each is one instantiation of the kernel
-static int64_t reg_bucket(int64_t Lp)
-{
-    for (int64_t b : {8, 16, 24, 32, 48, 64})
-        if (Lp <= b) return b;
-    return 0;
-}
 
 static int64_t window_span(int64_t up, int64_t down, int64_t pre, int64_t Lp, int64_t G, int64_t E)
 {
@@ -111,8 +80,6 @@ template <typename T> struct ResampleArgs {
     T *hist_out;                // [rows, H]
     int64_t N, H, m_begin, m_base;
 };
-
-constexpr int RS_STAGE_BATCH = 8;                         // staging loads in flight per thread
 
 // LP > 0: taps in registers, zero past Lp (LP >= Lp);  LP == 0: taps through the cache.  STAGE: inputs from the LDS window.
 // Register taps run LP terms per output: the extra ones are 0 * x[n / up - j] for j >= Lp, exact (+0 or -0 added) while the
@@ -269,7 +236,7 @@ void resample_plan_info(int64_t T, int64_t up, int64_t down, int64_t nh, int dty
 static PlanCache<DeviceBuffer, 5> g_tables(32, "resample_forward");
 
 template <typename T>
-static const T *resample_table(const void *taps_host, int64_t nh, int64_t up, int64_t down, int64_t pre_pad, int64_t Lp,
+const T *resample_table(const void *taps_host, int64_t nh, int64_t up, int64_t down, int64_t pre_pad, int64_t Lp,
                                hipStream_t stream, std::shared_ptr<DeviceBuffer> *keep)
 {
     const int64_t tail[5] = {up, down, (int64_t)sizeof(T), pre_pad, Lp};
@@ -284,6 +251,10 @@ static const T *resample_table(const void *taps_host, int64_t nh, int64_t up, in
     });
     return (const T *)(*keep)->p;
 }
+template const float *resample_table<float>(const void *, int64_t, int64_t, int64_t, int64_t, int64_t, hipStream_t,
+                                             std::shared_ptr<DeviceBuffer> *);
+template const double *resample_table<double>(const void *, int64_t, int64_t, int64_t, int64_t, int64_t, hipStream_t,
+                                               std::shared_ptr<DeviceBuffer> *);
 
 template <typename T, bool STREAM>
 static void resample_dispatch(const ResampleArgs<T> &p, int64_t rows, const ResampleTiling &t, hipStream_t stream)
@@ -503,11 +474,6 @@ void resample_stream_forward(const void *x, void *y, int dtype, int64_t rows, in
 //             true_peak_fold_kernel (one workgroup per row) folds work[row, :] into peak[row].  No atomics.
 //   non-finite  a tile whose window holds a NaN or an Inf writes NaN (the row's reading is NaN; other rows are untouched)
 // The tiling is fixed (it does not depend on rows), so a row's bits do not depend on the batch.
-constexpr int TP_THREADS = 256;
-constexpr int TP_R = 16;                                  // consecutive input positions per thread
-constexpr int64_t TP_TILE = (int64_t)TP_THREADS * TP_R;   // positions per workgroup
-constexpr int64_t TP_LP_MAX = 72;                         // nh <= 64 * up gives Lp <= 65
-
 template <typename T> struct TruePeakArgs {
     const T *x;                 // [rows, T_]
     T *work;                    // [rows, tiles]
@@ -516,33 +482,6 @@ template <typename T> struct TruePeakArgs {
     int64_t i_lo;               // pre / up: the input position of the row's first output
     int64_t n_lo, n_hi;         // n = i*up + phase is an output for n in [pre, pre + T_*up)
 };
-
-template <typename T> using tp_const_ptr = const T __attribute__((address_space(4))) *;
-
-// acc = fma(tap, x, acc); tp_fma0 starts a chain from +0.  The f32 forms are single instructions by hand: left to itself the
-// compiler packs neighbouring chains into v_pk_fma_f32 and pays a register copy for every odd-aligned pair of inputs (238
-// v_mov per 384 fma and 234 VGPRs).  The tap is asked for in a vector register: one v_mov per tap and phase, and the fma
-// measured 18 % faster than with the tap as its scalar operand.
-__device__ __forceinline__ float tp_fma(float tap, float x, float acc)
-{
-    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(tap), "v"(x));
-    return acc;
-}
-__device__ __forceinline__ float tp_fma0(float tap, float x)
-{
-    float acc;
-    asm("v_fma_f32 %0, %1, %2, 0" : "=v"(acc) : "v"(tap), "v"(x));
-    return acc;
-}
-__device__ __forceinline__ double tp_fma(double tap, double x, double acc) { return fma(tap, x, acc); }
-__device__ __forceinline__ double tp_fma0(double tap, double x) { return fma(tap, x, 0.0); }
-
-template <typename T> __device__ __forceinline__ T tp_max(T m, T a) { return (a > m || a != a) ? a : m; }
-
-// window line stride: 256 columns + up to ceil(71 / 16) = 5 of halo; f32 S = 2 (mod 32), f64 S = 1 (mod 16)
-template <typename T> constexpr int tp_stride() { return sizeof(T) == 4 ? 290 : 273; }
-
-static int64_t tp_bucket(int64_t Lp) { return reg_bucket(Lp) ? reg_bucket(Lp) : TP_LP_MAX; }
 
 template <typename T> __device__ __forceinline__ T tp_block_max(T m, T *part)
 {

@@ -237,6 +237,66 @@ class LoudnessNormalize(FX):
         return f"target={self.target}, channel_weights={self.channel_weights}, fs={self.fs}{ceiling}"
 
 
+class Limiter(FX):
+    """Look-ahead true-peak limiter: :func:`torchfx_amd.limiter.limit` with the same parameters -- ``ceiling_db`` (dBTP for
+    ``detector="true_peak"``, dBFS for ``"sample"``), ``lookahead`` and ``hold`` in seconds, ``link`` (one gain curve per
+    ``[C, T]`` signal or batch item), ``oversample``, ``taps`` and ``window``.  ``wave | LoudnessNormalize(-14) | Limiter(-1.0)``
+    brings a programme to its target loudness and takes down the peaks that pass the ceiling.
+
+    The sample ceiling ``|y| <= c (1 + u)^2`` always holds; the true peak of the result is measured, not guaranteed (within
+    0.001 dB of the ceiling at the default 1.5 ms look-ahead on the material measured, more with a shorter one -- see
+    :func:`~torchfx_amd.limiter.limit`).  ``fs`` comes from the ``Wave`` the effect is piped into when it is None.  The gain
+    looks ``A - 1`` samples ahead: the limiter is a step of its own in ``Wave.plan()`` and cannot run in a chunked stream."""
+
+    def __init__(self, ceiling_db: float = -1.0, lookahead: float = 1.5e-3, hold: float = 10e-3, detector: str = "true_peak",
+                 link: bool = True, oversample: int | None = None, taps=None, window=None, fs: int | None = None) -> None:
+        super().__init__()
+        from torchfx_amd.limiter import LimiterParams
+
+        LimiterParams(48000 if fs is None else fs, torch.float32, ceiling_db, 0.0, 0.0, detector, oversample)   # argument errors now
+        for name, v in (("lookahead", lookahead), ("hold", hold)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+                raise ValueError(f"limit: {name} must be a finite time >= 0 in seconds, got {v!r}")
+        self.ceiling_db, self.lookahead, self.hold = float(ceiling_db), float(lookahead), float(hold)
+        self.detector, self.link, self.oversample, self.taps, self.window, self.fs = detector, bool(link), oversample, taps, window, fs
+
+    def params(self, dtype: torch.dtype):
+        """The call's :class:`torchfx_amd.limiter.LimiterParams` for a signal of ``dtype`` at ``self.fs``."""
+        if self.fs is None:
+            raise ValueError("Limiter needs the sample rate: pass fs or pipe a Wave into it (wave | Limiter())")
+        from torchfx_amd.limiter import LimiterParams
+
+        return LimiterParams(self.fs, dtype, self.ceiling_db, self.lookahead, self.hold, self.detector, self.oversample, self.taps,
+                             self.window)
+
+    def route(self, x: Tensor, length: int | None = None) -> str:
+        """``native (...)`` or ``numpy on host -- <reason>`` for ``x`` (rows of ``length`` samples, default x's)."""
+        if not x.is_cuda:
+            return f"numpy on host -- {x.device.type} tensor"
+        try:
+            P = self.params(x.dtype)
+            n = int(x.shape[-1]) if length is None else int(length)
+            info = _ext().limiter_plan_info(n, P.A, P.H, P.up, 0 if P.taps is None else int(P.taps.numel()), x.dtype)
+        except (RuntimeError, ValueError, TypeError) as e:
+            return f"refused -- {e}"
+        det = f"{P.up}x oversampled detector" if P.up > 1 else "sample-peak detector"
+        return (f"native (limiter_kernel, {det}, look-ahead {P.A} / hold {P.H} samples, {info['tiles']} tile(s) of {info['tile']} "
+                "per group; one launch)")
+
+    @torch.no_grad()
+    def forward(self, waveform: Tensor) -> Tensor:
+        if self.fs is None:
+            raise ValueError("Limiter needs the sample rate: pass fs or pipe a Wave into it (wave | Limiter())")
+        from torchfx_amd.limiter import limit
+
+        return limit(waveform, self.fs, self.ceiling_db, self.lookahead, self.hold, self.detector, self.link, self.oversample,
+                     self.taps, self.window)
+
+    def extra_repr(self) -> str:
+        return (f"ceiling_db={self.ceiling_db}, lookahead={self.lookahead}, hold={self.hold}, detector={self.detector!r}, "
+                f"link={self.link}, fs={self.fs}")
+
+
 class Epilogued(FX):
     """Planner product (``Wave.plan()``, ``fuse_epilogue``): a filter followed by ``Gain`` and / or ``Normalize``
     whose elementwise work rides on the filter's own kernel.  ``producer`` is an SOS filter / cascade or an

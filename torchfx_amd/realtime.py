@@ -381,6 +381,15 @@ def _refuse_loudness(e, who: str) -> None:
                         "whole signal (wave | LoudnessNormalize(...)) before or after streaming")
 
 
+def _refuse_limiter(e, who: str) -> None:
+    from torchfx_amd.effect import Limiter
+
+    if any(isinstance(m, Limiter) for m in (e.modules() if isinstance(e, nn.Module) else [e])):
+        raise TypeError(f"Limiter cannot run in {who}: its gain looks A - 1 samples ahead (the look-ahead), which a chunked stream "
+                        "has not seen yet, and a streaming limiter that carries that history is not provided; limit the whole "
+                        "signal (wave | Limiter(...)) before or after streaming")
+
+
 class _ChunkRun:
     """``IIR ... | StatefulFIR | Gain`` (any non-empty sub-pattern of at least two effects) as ONE launch per small chunk
     (``torchfx_ext.chunk_forward``): the chain of a 2 x 512 block is launch-bound, not arithmetic-bound.  Consecutive
@@ -520,6 +529,7 @@ class StreamProcessor:
                 raise TypeError("All effects must inherit from FX when used in StreamProcessor")
             _refuse_zero_phase(e, "StreamProcessor")
             _refuse_loudness(e, "StreamProcessor")
+            _refuse_limiter(e, "StreamProcessor")
             if not isinstance(e, StatefulResample) and any(isinstance(m, Resample) for m in e.modules()):
                 raise TypeError("Resample cannot run in StreamProcessor: resampling each chunk on its own leaves a seam at "
                                 "every chunk boundary; use StatefulResample as a top-level effect of the chain, or resample "
@@ -832,6 +842,7 @@ class RealtimeProcessor:
                 raise TypeError("All effects must inherit from FX when used in RealtimeProcessor")
             _refuse_zero_phase(e, "RealtimeProcessor")
             _refuse_loudness(e, "RealtimeProcessor")
+            _refuse_limiter(e, "RealtimeProcessor")
             if _has_stateful_resample(e):
                 raise TypeError("StatefulResample cannot run in RealtimeProcessor: a sound card's output block has the input "
                                 "block's length and sample rate; resample with StreamProcessor or Wave.resample instead")

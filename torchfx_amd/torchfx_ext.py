@@ -35,7 +35,7 @@ __all__ = [
     "biquad_forward", "sos_forward", "sos_bank_forward", "sos_bank_sum_forward", "delay_line_forward", "delay_forward",
     "delay_amplitudes", "delay_regime", "delay_stream_forward", "delay_line_stream_forward", "resample_forward",
     "resample_plan_info", "resample_stream_forward", "resample_stream_plan_info", "sos_filtfilt", "sos_filtfilt_plan_info",
-    "sos_block_energy", "sos_block_energy_plan_info", "true_peak", "true_peak_plan_info",
+    "sos_block_energy", "sos_block_energy_plan_info", "true_peak", "true_peak_plan_info", "limiter_forward", "limiter_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
 ]
@@ -270,6 +270,29 @@ def true_peak_plan_info(rows: int, length: int, up: int, taps: int, dtype: torch
     L.check(L.load().tfx_true_peak_plan_info(int(rows), int(length), int(up), int(taps),
                                              L.TFX_F64 if dtype == torch.float64 else L.TFX_F32, *[ctypes.byref(v) for v in o]))
     return {"Lp": o[0].value, "tile_in": o[1].value, "tiles": o[2].value, "work_elems": o[3].value}
+
+
+def limiter_forward(x: Tensor, c: float, A: int, H: int, window: Tensor, up: int = 1, taps: Tensor | None = None,
+                    channels: int = 1, return_gain: bool = False) -> tuple[Tensor, Tensor]:
+    """The look-ahead limiter in one launch (``tfx_limiter_forward``; the definition is :func:`torchfx_amd.limiter.limit`'s), in
+    samples: ``x [..., T]`` on the device (float32 / float64), its rows in groups of ``channels`` consecutive rows that share
+    one gain curve; ``c`` the linear ceiling already rounded to ``x``'s dtype, ``A <= 512`` look-ahead and ``H <= 4096`` hold
+    samples, ``window`` the ``A`` smoothing weights and ``taps`` the interpolator (``up`` 2, 4 or 8; None for ``up == 1``) as
+    1-D host tensors of ``x``'s dtype.  Returns ``(y, g)`` with ``g [groups, T]`` the gain curve, empty without ``return_gain``."""
+    return native.ops().limiter_forward(x.contiguous(), float(c), int(A), int(H), window, int(up), taps, int(channels),
+                                        bool(return_gain))
+
+
+def limiter_plan_info(length: int, A: int, H: int, up: int = 1, taps: int = 0, dtype: torch.dtype = torch.float32,
+                      groups: int = 1, channels: int = 1) -> dict:
+    """What :func:`limiter_forward` does for groups of rows of ``length`` samples (``tfx_limiter_plan_info``; host-only, same
+    checks on the sizes): ``tile`` (outputs per workgroup), ``tiles`` per group, ``halo_left`` / ``halo_right`` (input samples
+    a tile reads behind its first and past its last output), ``Lp`` (taps per phase, 0 for ``up == 1``) and ``lds_bytes``.
+    The tiling does not depend on ``groups`` or ``channels``."""
+    o = [ctypes.c_int64(0) for _ in range(6)]
+    L.check(L.load().tfx_limiter_plan_info(int(groups), int(channels), int(length), int(A), int(H), int(up), int(taps),
+                                           L.TFX_F64 if dtype == torch.float64 else L.TFX_F32, *[ctypes.byref(v) for v in o]))
+    return dict(zip(("tile", "tiles", "halo_left", "halo_right", "Lp", "lds_bytes"), (v.value for v in o)))
 
 
 RESAMPLE_STREAM_KERNELS = ("resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel", "copy")

@@ -210,7 +210,7 @@ def plan_cache_clear() -> None:
 
 
 def _member_key(m: nn.Module, guard: list) -> tuple:
-    from torchfx_amd.effect import Delay, Gain, LoudnessNormalize, Normalize
+    from torchfx_amd.effect import Delay, Gain, Limiter, LoudnessNormalize, Normalize
     from torchfx_amd.filter.zerophase import ZeroPhase
     from torchfx_amd.resample import Resample, window_key
 
@@ -238,6 +238,8 @@ def _member_key(m: nn.Module, guard: list) -> tuple:
         k += (m.padtype, m.padlen)
     elif isinstance(m, LoudnessNormalize):
         k += (m.target, m.channel_weights, m.fs)
+    elif isinstance(m, Limiter):
+        k += (m.ceiling_db, m.lookahead, m.hold, m.detector, m.link, m.oversample, id(m.taps), id(m.window), m.fs)
     return k
 
 
@@ -327,15 +329,16 @@ class Wave:
     def _build_plan(self, length: int, dtype: torch.dtype = torch.float32) -> list[nn.Module]:
         """A ``Resample`` is a barrier: the steps between two of them are planned on their own, at the row length they see,
         and nothing merges, folds or attaches an epilogue across one.  So is a ``ZeroPhase`` (its two passes are one step;
-        the row length stays) and a ``LoudnessNormalize`` (it measures exactly the signal the steps before it produce)."""
-        from torchfx_amd.effect import LoudnessNormalize
+        the row length stays), a ``LoudnessNormalize`` (it measures exactly the signal the steps before it produce) and a
+        ``Limiter`` (its detector reads the samples the steps before it store)."""
+        from torchfx_amd.effect import Limiter, LoudnessNormalize
         from torchfx_amd.filter.zerophase import ZeroPhase
         from torchfx_amd.resample import Resample
 
         plan: list[nn.Module] = []
         segment: list[nn.Module] = []
         for m in self._pipeline:
-            if isinstance(m, (Resample, ZeroPhase, LoudnessNormalize)):
+            if isinstance(m, (Resample, ZeroPhase, LoudnessNormalize, Limiter)):
                 plan += self._build_segment(segment, length, dtype)
                 plan.append(m)
                 segment = []
@@ -568,7 +571,7 @@ class Wave:
     def explain(self) -> list[str]:
         """One line per step of :meth:`plan` for THIS tensor: the step, the route it will take (``CascadeFIR``: the fused
         recursion-in-pass-A pipeline or the staged pair of launches) and why."""
-        from torchfx_amd.effect import Delay, Epilogued, LoudnessNormalize
+        from torchfx_amd.effect import Delay, Epilogued, Limiter, LoudnessNormalize
         from torchfx_amd.filter.fused import CascadeFIR, FusedSOSCascade
         from torchfx_amd.filter.zerophase import ZeroPhase
         from torchfx_amd.realtime import StatefulDelay, _native_stream
@@ -595,7 +598,7 @@ class Wave:
             elif isinstance(inner, Resample):
                 line += ": " + inner.route(self._ys, length)
                 length = inner.output_length(length)
-            elif isinstance(inner, (ZeroPhase, LoudnessNormalize)):
+            elif isinstance(inner, (ZeroPhase, LoudnessNormalize, Limiter)):
                 line += ": " + inner.route(self._ys, length)
             lines.append(line)
         return lines
