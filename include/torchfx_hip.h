@@ -309,8 +309,8 @@ int tfx_normalize_apply(const void *x, void *y, int dtype, int64_t C, int64_t T,
 
 /* ---------------------------------------------------------------------------
  * Stream history -- the contract of every streaming entry point (tfx_fir_stream_forward, tfx_chunk_forward,
- * tfx_delay_stream_forward, tfx_delay_line_stream_forward, tfx_resample_stream_forward).  A chunk continues the last H input
- * samples of each of its rows (H is the entry's: K-1, Kf-1, taps*delay, delay, Lp_s-1):
+ * tfx_delay_stream_forward, tfx_delay_line_stream_forward, tfx_resample_stream_forward, tfx_limiter_stream_forward).  A chunk
+ * continues the last H input samples of each of its rows (H is the entry's: K-1, Kf-1, taps*delay, delay, Lp_s-1, Hs):
  *   hist_in  DEVICE [rows, H] of the entry's dtype: the H samples before the chunk, oldest first; NULL = silence (the first
  *            chunk of a stream).
  *   hist_out DEVICE [rows, H]: receives the newest H samples of [hist_in | x] (x: what the entry filters, the cascade output
@@ -532,6 +532,40 @@ int tfx_limiter_forward(const void *x, void *y, void *gain_or_null, int dtype, i
 int tfx_limiter_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh, int dtype,
                           int64_t *tile, int64_t *tiles, int64_t *halo_left, int64_t *halo_right, int64_t *Lp,
                           int64_t *lds_bytes);
+
+/* ---------------------------------------------------------------------------
+ * tfx_limiter_stream_forward -- one chunk of tfx_limiter_forward over a continuous stream, in ONE launch.  With Y the one-shot
+ * result of the whole stream (past and to come), the chunk of T samples that follows `consumed` = N inputs per row writes
+ *   y[., t] = Y[N - D + t], 0 where N - D + t < 0        (gain[., t] = g[N - D + t], 1 there)
+ * and each sample is final.  (A, H, up, nh) fix the stream's geometry, with n_pre_remove and Lp as tfx_resample_plan_info gives
+ * them for (up, down = 1, nh), i_lo = n_pre_remove / up and rem = n_pre_remove mod up:
+ *   latency D  = A - 1 + i_lo (+ 1 when rem >= 2; an odd-length filter has rem = 1): output n needs input n + D and no later one;
+ *                up == 1: A - 1
+ *   history Hs = D + A + H - 2 + max(1, Lp - i_lo) (up == 1: D + A + H - 2): the inputs before the chunk its outputs read
+ * History as in "Stream history" with H = Hs: hist_in holds inputs [N - Hs, N) (zeros before 0).  The kernel reads [hist_in | x]
+ * from the two buffers and knows where the stream began: positions before 0 have r = 1 and q[-1] = 0 although the interpolator
+ * rings into them.  n_in <= T is the number of real inputs in x: n_in < T says that the stream ends after them -- x[., n_in:] is
+ * never read, r = 1 from N + n_in on and the interpolated signal is cut there, exactly as tfx_limiter_forward treats its end --
+ * and hist_out then receives the newest Hs samples of [hist_in | x[., :n_in]].  The last min(N, D) outputs of a stream of N
+ * inputs are the end of a chunk with T = D, n_in = 0.  `consumed` matters only up to Hs + D and is clamped there.
+ * Every output is tfx_limiter_forward's arithmetic (the same fma chains, rounded division and exact minimum), so the chunks'
+ * outputs equal the one-shot call on the whole signal bit for bit, whatever the chunk sizes.  A workgroup computes up to `tile`
+ * outputs and sweeps only the T' + 2A + H - 2 positions of p / r they depend on.  A tile whose [hist_in | x] window holds a NaN
+ * or an Inf in any channel writes NaN to all its outputs (at positions >= 0) in every channel of the group; once the sample has
+ * left the history the outputs are the clean stream's again.
+ * x, y DEVICE [groups, channels, T], gain DEVICE [groups, T] or null, hist_out DEVICE [groups, channels, Hs] or null (no history
+ * out); gain may not overlap x, y, hist_in or hist_out either; the other arguments as for tfx_limiter_forward.  T == 0 copies
+ * hist_in to hist_out.
+ * ------------------------------------------------------------------------- */
+int tfx_limiter_stream_forward(const void *x, void *y, void *gain_or_null, int dtype, int64_t groups, int64_t channels, int64_t T,
+                               int64_t n_in, int64_t consumed, double c, int64_t A, int64_t H, const void *window_host, int64_t up,
+                               const void *taps_host, int64_t nh, const void *hist_in, void *hist_out, tfx_stream_t stream);
+/* what tfx_limiter_stream_forward does with a chunk of T samples (host-only, same checks on the sizes): the stream's latency D
+ * and history length Hs, outputs per workgroup `tile` (8193 - 2A - H), tiles per group, the positions of p / r the first
+ * workgroup sweeps (min(T, tile) + 2A + H - 2, of 8192) and the LDS bytes per workgroup */
+int tfx_limiter_stream_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh,
+                                 int dtype, int64_t *latency, int64_t *history, int64_t *tile, int64_t *tiles, int64_t *positions,
+                                 int64_t *lds_bytes);
 
 /* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of

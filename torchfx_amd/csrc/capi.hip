@@ -77,6 +77,15 @@ void limiter_forward(const void *x, void *y, void *gain, int dtype, int64_t grou
                      hipStream_t stream);
 void limiter_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh, int dtype,
                        int64_t *tile, int64_t *tiles, int64_t *halo_left, int64_t *halo_right, int64_t *Lp, int64_t *lds_bytes);
+void limiter_stream_check(const void *x, const void *y, const void *gain, int dtype, int64_t groups, int64_t channels, int64_t T,
+                          int64_t n_in, int64_t consumed, double c, int64_t A, int64_t H, const void *window_host, int64_t up,
+                          const void *taps_host, int64_t nh, const void *hist_in, const void *hist_out);
+void limiter_stream_forward(const void *x, void *y, void *gain, int dtype, int64_t groups, int64_t channels, int64_t T, int64_t n_in,
+                            int64_t consumed, double c, int64_t A, int64_t H, const void *window_host, int64_t up,
+                            const void *taps_host, int64_t nh, const void *hist_in, void *hist_out, hipStream_t stream);
+void limiter_stream_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh, int dtype,
+                              int64_t *latency, int64_t *history, int64_t *tile, int64_t *tiles, int64_t *positions,
+                              int64_t *lds_bytes);
 void limiter_clear();
 // layout.hip
 void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, int64_t C, int64_t ld_out, int64_t f_base,
@@ -730,6 +739,29 @@ int tfx_limiter_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A
     TFX_API_BEGIN
     TFX_CHECK(tile && tiles && halo_left && halo_right && Lp && lds_bytes, "limiter_plan_info: null output");
     limiter_plan_info(groups, channels, T, A, H, up, nh, dtype, tile, tiles, halo_left, halo_right, Lp, lds_bytes);
+    TFX_API_END
+}
+
+int tfx_limiter_stream_forward(const void *x, void *y, void *gain_or_null, int dtype, int64_t groups, int64_t channels, int64_t T,
+                               int64_t n_in, int64_t consumed, double c, int64_t A, int64_t H, const void *window_host, int64_t up,
+                               const void *taps_host, int64_t nh, const void *hist_in, void *hist_out, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    // checked before anything touches the device
+    limiter_stream_check(x, y, gain_or_null, dtype, groups, channels, T, n_in, consumed, c, A, H, window_host, up, taps_host, nh,
+                         hist_in, hist_out);
+    limiter_stream_forward(x, y, gain_or_null, dtype, groups, channels, T, n_in, consumed, c, A, H, window_host, up, taps_host, nh,
+                           hist_in, hist_out, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_limiter_stream_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh,
+                                 int dtype, int64_t *latency, int64_t *history, int64_t *tile, int64_t *tiles, int64_t *positions,
+                                 int64_t *lds_bytes)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(latency && history && tile && tiles && positions && lds_bytes, "limiter_stream_plan_info: null output");
+    limiter_stream_plan_info(groups, channels, T, A, H, up, nh, dtype, latency, history, tile, tiles, positions, lds_bytes);
     TFX_API_END
 }
 

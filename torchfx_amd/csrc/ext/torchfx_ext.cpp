@@ -537,6 +537,47 @@ std::tuple<Tensor, Tensor> limiter_op(const Tensor &x_in, double c, int64_t A, i
     return std::make_tuple(y, gain);
 }
 
+// One chunk of a limiter stream (tfx_limiter_stream_forward): x [..., T] after `consumed` samples per row, hist [rows, Hs] (None =
+// silence), n_in real inputs in x (-1: all T; fewer: the stream ends after them) -> (y like x: the one-shot result from position
+// consumed - D on, gain [groups, T] or an empty tensor, new history [rows, Hs]).  The other arguments as limiter_op's.
+std::tuple<Tensor, Tensor, Tensor> limiter_stream_op(const Tensor &x_in, const OptTensor &hist, int64_t consumed, double c, int64_t A,
+                                                     int64_t H, const Tensor &window, int64_t up, const OptTensor &taps,
+                                                     int64_t channels, bool return_gain, int64_t n_in)
+{
+    const char *what = "limiter_stream_forward";
+    need_device(x_in, "x");
+    TORCH_CHECK(x_in.dim() >= 1, what, ": x must have a time dimension");
+    TORCH_CHECK(!window.is_cuda() && window.dim() == 1 && window.numel() == A, what, ": window must be a 1-D host tensor of ", A, " values");
+    TORCH_CHECK(window.scalar_type() == x_in.scalar_type(), what, ": window must have x's dtype (", x_in.scalar_type(), "), got ",
+                window.scalar_type());
+    const bool has_taps = taps.has_value() && taps->defined();
+    TORCH_CHECK(up == 1 || has_taps, what, ": up > 1 needs taps");
+    if (has_taps) {
+        TORCH_CHECK(!taps->is_cuda() && taps->dim() == 1 && taps->numel() >= 1, what, ": taps must be a non-empty 1-D host tensor");
+        TORCH_CHECK(taps->scalar_type() == x_in.scalar_type(), what, ": taps must have x's dtype (", x_in.scalar_type(), "), got ",
+                    taps->scalar_type());
+    }
+    const Tensor x = x_in.contiguous(), wc = window.contiguous();
+    const Tensor hc = has_taps ? taps->contiguous() : Tensor();
+    const int64_t T = x.size(-1), rows = stream_rows(x);
+    TORCH_CHECK(channels >= 1 && rows % channels == 0, what, ": ", rows, " rows do not split into groups of ", channels);
+    const int64_t groups = rows / channels, nh = has_taps && up > 1 ? hc.numel() : 0;
+    const int dt = dtype_code(x, what);
+    int64_t info[6];
+    check_rc(tfx_limiter_stream_plan_info(groups, channels, T, A, H, up, nh, dt, info, info + 1, info + 2, info + 3, info + 4, info + 5),
+             what);
+    const int64_t Hs = info[1];
+    const Tensor hin = stream_hist_in(hist, x, rows, Hs, what);
+    Tensor y = at::empty_like(x), hout = at::empty({rows, Hs}, x.options());
+    Tensor gain = return_gain ? at::empty({groups, T}, x.options()) : at::empty({0}, x.options());
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_limiter_stream_forward(x.data_ptr(), y.data_ptr(), return_gain ? gain.data_ptr() : nullptr, dt, groups, channels, T,
+                                        n_in < 0 ? T : n_in, consumed, c, A, H, wc.data_ptr(), up, nh ? hc.data_ptr() : nullptr, nh,
+                                        hin.defined() ? hin.data_ptr() : nullptr, hout.data_ptr(), stream_of(x)),
+             what);
+    return std::make_tuple(y, gain, hout);
+}
+
 // One chunk of a resampling stream (tfx_resample_stream_forward): x [..., T] after `consumed` samples per row, h as for
 // resample_forward, hist [rows, H] (None = silence) -> (y [..., M(consumed + T) - M(consumed)], new history [rows, H])
 struct ResampleStreamPlan {
@@ -945,6 +986,8 @@ TORCH_LIBRARY(torchfx_hip, m)
     m.def("true_peak(Tensor x, Tensor taps_cpu, int up) -> Tensor");
     m.def("limiter_forward(Tensor x, float c, int A, int H, Tensor window_cpu, int up, Tensor? taps_cpu, int channels, "
           "bool return_gain) -> (Tensor, Tensor)");
+    m.def("limiter_stream_forward(Tensor x, Tensor? hist, int consumed, float c, int A, int H, Tensor window_cpu, int up, "
+          "Tensor? taps_cpu, int channels, bool return_gain, int n_in=-1) -> (Tensor, Tensor, Tensor)");
     m.def("resample_stream_forward(Tensor x, Tensor h, Tensor? hist, int up, int down, int consumed) -> (Tensor, Tensor)");
     m.def("delay_forward_ep(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong, float gain, bool clamp, int stat_mode, "
           "bool per_row) -> (Tensor, Tensor)");
@@ -986,6 +1029,7 @@ TORCH_LIBRARY_IMPL(torchfx_hip, CUDA, m)          // "CUDA" is the dispatch key 
     m.impl("sos_block_energy", sos_block_energy_op);
     m.impl("true_peak", true_peak_op);
     m.impl("limiter_forward", limiter_op);
+    m.impl("limiter_stream_forward", limiter_stream_op);
     m.impl("resample_stream_forward", resample_stream_op);
     m.impl("delay_forward_ep", delay_ep_op);
     m.impl("delay_stream_forward", delay_stream_op);
@@ -1045,7 +1089,7 @@ static void no_cpu_boxed(const c10::OperatorHandle &op, c10::DispatchKeySet, tor
 TORCH_LIBRARY_IMPL(torchfx_hip, CPU, m)
 {
     for (const char *name : {"sos_forward", "sos_forward_sections", "sos_bank_forward", "sos_bank_sum_forward", "biquad_forward",
-                             "delay_line_forward", "delay_forward", "delay_forward_ep", "delay_stream_forward", "delay_line_stream_forward", "resample_forward", "sos_filtfilt", "sos_block_energy", "true_peak", "limiter_forward", "resample_stream_forward", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
+                             "delay_line_forward", "delay_forward", "delay_forward_ep", "delay_stream_forward", "delay_line_stream_forward", "resample_forward", "sos_filtfilt", "sos_block_energy", "true_peak", "limiter_forward", "limiter_stream_forward", "resample_stream_forward", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
                              "fft_conv_forward_ep", "sos_fft_conv_forward", "normalize_apply", "sum_forward", "gain_forward", "quantile_abs", "stat_forward",
                              "normalize_forward", "deinterleave_forward", "deinterleave_into", "interleave_forward"})
         m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());

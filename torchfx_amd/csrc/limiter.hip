@@ -26,11 +26,16 @@
 // p / r live at index a + a/16 (a thread's 16 consecutive words and a wave's strided sweep both spread over the banks).
 // LDS: (8704 + 8736) elements = 69 760 B float32 (two workgroups per CU), 139 520 B float64 (one).
 // Non-finite: a tile whose staged windows hold a NaN or an Inf in any channel writes NaN to all its outputs of the group.
+//
+// Stream form (tfx_limiter_stream_forward, limiter_kernel<T, LP, true>): the same kernel on [hist | x], a row's carried history
+// and its chunk in their two buffers.  A chunk's outputs trail its inputs by the latency D, a tile sweeps only the positions its
+// outputs depend on, and the launch also writes the next chunk's history (LimiterStreamPlan below has the geometry).
 #include "common.h"
 #include "plan_cache.h"
 #include "polyphase.h"
 #include "../../include/torchfx_hip.h"
 
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -57,6 +62,39 @@ template <typename T> struct LimiterArgs {
     int rem;                    // n_pre_remove mod up
     int xoff;                   // LP - 1 - i_lo: window offset of a position's own sample
     T c;
+    // stream form only (tfx_limiter_stream_forward): a row is [hist | x], T_ = N + n_in is where the stream ends so far
+    const T *hist;              // [groups, channels, Hs] or null (silence)
+    T *hist_out;                // [groups, channels, Hs] or null
+    int64_t Tc, N, Hs, n_in;    // chunk length (pitch of x, y and gain), inputs before the chunk (clamped), history, real inputs
+    int D;                      // latency: output t of the chunk is stream position N - D + t
+};
+
+// A row by sample position.  One-shot: x[row] over [0, T_).  Stream: positions [N - Hs, N) come from hist (zeros when null),
+// [N, T_) from x; nothing exists before 0 or from T_ on.
+template <typename T, bool STREAM> struct LmRow {
+    const T *xr, *hr;
+    int64_t N, h0, end;
+    __device__ __forceinline__ LmRow(const LimiterArgs<T> &p, int64_t row) : xr(nullptr), hr(nullptr), N(0), h0(0), end(p.T_)
+    {
+        if constexpr (STREAM) {
+            xr = p.x + row * p.Tc;
+            hr = p.hist ? p.hist + row * p.Hs : nullptr;
+            N = p.N;
+            h0 = p.N - p.Hs;
+        } else {
+            xr = p.x + row * p.T_;
+        }
+    }
+    __device__ __forceinline__ T at(int64_t i) const
+    {
+        if constexpr (STREAM) {
+            if (i < 0 || i >= end) return (T)0;
+            if (i >= N) return xr[i - N];
+            return (hr && i >= h0) ? hr[i - h0] : (T)0;
+        } else {
+            return (i >= 0 && i < end) ? xr[i] : (T)0;
+        }
+    }
 };
 
 __device__ __forceinline__ int lm_idx(int a) { return a + (a >> 4); }
@@ -76,8 +114,12 @@ template <bool SCALAR> __device__ __forceinline__ double lm_fma(double tap, doub
 __device__ __forceinline__ float lm_div(float a, float b) { return __fdiv_rn(a, b); }
 __device__ __forceinline__ double lm_div(double a, double b) { return a / b; }
 
-// LP > 0: `up`x interpolator with LP taps per phase in registers;  LP == 0: up = 1, the sample peak
-template <typename T, int LP>
+// LP > 0: `up`x interpolator with LP taps per phase in registers;  LP == 0: up = 1, the sample peak.
+// STREAM: one chunk of a stream.  Output o of tile k is chunk sample t = k * tile + o at stream position N - D + t (0 is written
+// where that is negative); the tile's `nout` outputs depend on positions a < np = nout + 2A + H - 2 of p / r only, and every
+// phase below sweeps those alone (a 512-sample block: about 1100 of the 8192).  The arithmetic per output is the one-shot
+// form's, so the bits agree.  The blocks of a group also copy the newest Hs samples of [hist | x[:n_in]] to hist_out.
+template <typename T, int LP, bool STREAM>
 __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T> p)
 {
     constexpr int S = tp_stride<T>(), NW = TP_R + (LP > 0 ? LP : 1) - 1, SPAN = (int)TP_TILE + (LP > 0 ? LP : 1) - 1;
@@ -87,40 +129,56 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
     T *reg = rr + LM_PAD;                                        // LM_REGION
     const int t = (int)threadIdx.x;
     const int64_t grp = blockIdx.x / p.tiles, tile = blockIdx.x % p.tiles;
-    const int64_t n0 = tile * p.tile;
+    const int64_t n0 = tile * p.tile - (STREAM ? p.D - p.N : 0);  // position of the tile's first output
     const int64_t rb = n0 - (p.A + p.H - 1);                     // sample of position a = 0
-    const T *xg = p.x + grp * p.channels * p.T_;
-    for (int a = t; a < LM_NR; a += LM_THREADS) rr[lm_idx(a)] = (T)0;
+    const int64_t left = (STREAM ? p.Tc : p.T_) - tile * p.tile;
+    const int nout = left < p.tile ? (int)left : p.tile;         // the tile's outputs
+    const int np = STREAM ? nout + 2 * p.A + p.H - 2 : LM_NR;    // positions of p / r they depend on (a = 0 is spare)
+    if constexpr (STREAM) {
+        if (p.hist_out)
+            for (int ch = 0; ch < p.channels; ++ch) {
+                const int64_t row = grp * p.channels + ch;
+                const T *hr = p.hist ? p.hist + row * p.Hs : nullptr;
+                for (int64_t j = tile * LM_THREADS + t; j < p.Hs; j += p.tiles * LM_THREADS)
+                    p.hist_out[row * p.Hs + j] = stream_hist_at(p.x + row * p.Tc, hr, p.n_in, p.Hs, j);
+            }
+    }
+    {
+        const int nz = (STREAM && np + 2 * TP_R < LM_NR) ? np + 2 * TP_R : LM_NR;
+        for (int a = t; a < nz; a += LM_THREADS) rr[lm_idx(a)] = (T)0;
+    }
     bool bad = false;
     if constexpr (LP == 0) {
         for (int ch = 0; ch < p.channels; ++ch) {
-            const T *xr = xg + (int64_t)ch * p.T_;
-            for (int a = t; a < LM_NR; a += LM_THREADS) {        // a thread's own words only: no barrier
-                const int64_t i = rb + a;
-                const T v = (i >= 0 && i < p.T_) ? xr[i] : (T)0;
+            const LmRow<T, STREAM> xr(p, grp * p.channels + ch);
+            for (int a = t; a < np; a += LM_THREADS) {           // a thread's own words only: no barrier
+                const T v = xr.at(rb + a);
                 bad |= !isfinite(v);
                 rr[lm_idx(a)] = lm_max(rr[lm_idx(a)], (T)fabs(v));
             }
         }
     } else {
         const int up = (int)p.up;
+        // positions 0 .. np feed p[a], a < np (p[a] takes a term from a + 1): the passes and the threads of a pass that hold one
+        const int passes = (STREAM && np < (int)TP_TILE) ? 1 : LM_NR / (int)TP_TILE;
         for (int ch = 0; ch < p.channels; ++ch) {
-            const T *xr = xg + (int64_t)ch * p.T_;
-            for (int ps = 0; ps < LM_NR / (int)TP_TILE; ++ps) {
+            const LmRow<T, STREAM> xr(p, grp * p.channels + ch);
+            for (int ps = 0; ps < passes; ++ps) {
                 const int a0 = ps * (int)TP_TILE + t * TP_R;     // the thread's first position
+                const bool live = !STREAM || a0 <= np;
+                const int span = STREAM ? min(SPAN, (np - ps * (int)TP_TILE) / TP_R * TP_R + NW) : SPAN;
                 const int64_t s0 = p.i_lo + rb + ps * TP_TILE - (LP - 1);       // first input of the window
-                for (int j0 = 0; j0 < SPAN; j0 += LM_THREADS * RS_STAGE_BATCH) {
+                for (int j0 = 0; j0 < span; j0 += LM_THREADS * RS_STAGE_BATCH) {
                     T v[RS_STAGE_BATCH];
 #pragma unroll
                     for (int u = 0; u < RS_STAGE_BATCH; ++u) {
                         const int j = j0 + u * LM_THREADS + t;
-                        const int64_t i = s0 + j;
-                        v[u] = (j < SPAN && i >= 0 && i < p.T_) ? xr[i] : (T)0;
+                        v[u] = j < span ? xr.at(s0 + j) : (T)0;
                     }
 #pragma unroll
                     for (int u = 0; u < RS_STAGE_BATCH; ++u) {
                         const int j = j0 + u * LM_THREADS + t;
-                        if (j < SPAN) reg[(j % TP_R) * S + j / TP_R] = v[u];
+                        if (j < span) reg[(j % TP_R) * S + j / TP_R] = v[u];
                         bad |= !isfinite(v[u]);
                     }
                 }
@@ -129,7 +187,9 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
 #pragma unroll
                 for (int r = 0; r < TP_R; ++r) hi[r] = lo[r] = (T)0;
                 const int64_t nf = (p.i_lo + rb + a0) * p.up;    // n of the thread's first position, phase 0
-                if (nf >= p.n_lo && nf + (int64_t)TP_R * up <= p.n_hi) {
+                if (!live) {
+                    // nothing of this thread's 16 positions is needed
+                } else if (nf >= p.n_lo && nf + (int64_t)TP_R * up <= p.n_hi) {
                     T xw[NW];
 #pragma unroll
                     for (int k = 0; k < NW; ++k) xw[k] = reg[(k % TP_R) * S + t + k / TP_R];
@@ -177,7 +237,7 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
                 }
                 // step 1: a thread's own 16 positions
 #pragma unroll
-                for (int r = 0; r < TP_R; ++r) {
+                for (int r = 0; r < TP_R && live; ++r) {
                     const int k = r + p.xoff;
                     T v = lm_max(lm_max(hi[r], lo[r]), (T)fabs(reg[(k % TP_R) * S + t + k / TP_R]));
                     if (r + 1 < TP_R) v = lm_max(v, lo[r + 1 < TP_R ? r + 1 : r]);
@@ -187,23 +247,24 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
                 }
                 __syncthreads();                                 // also: every read of the window is done
                 // step 2: the two terms that belong to a neighbour's position
-                if (a0 > 0) rr[lm_idx(a0 - 1)] = lm_max(rr[lm_idx(a0 - 1)], lo[0]);
-                if (a0 + TP_R < LM_NR) rr[lm_idx(a0 + TP_R)] = lm_max(rr[lm_idx(a0 + TP_R)], hi[TP_R - 1]);
+                if (live && a0 > 0) rr[lm_idx(a0 - 1)] = lm_max(rr[lm_idx(a0 - 1)], lo[0]);
+                if (live && a0 + TP_R < LM_NR) rr[lm_idx(a0 + TP_R)] = lm_max(rr[lm_idx(a0 + TP_R)], hi[TP_R - 1]);
             }
         }
     }
+    const int64_t pitch = STREAM ? p.Tc : p.T_, y0 = tile * p.tile;    // rows of y / gain, the tile's first sample in them
     if (__syncthreads_or(bad)) {
         const T nan = (T)NAN;
         for (int ch = 0; ch < p.channels; ++ch) {
-            T *yr = p.y + (grp * p.channels + ch) * p.T_;
-            for (int o = t; o < p.tile && n0 + o < p.T_; o += LM_THREADS) yr[n0 + o] = nan;
+            T *yr = p.y + (grp * p.channels + ch) * pitch + y0;
+            for (int o = t; o < nout; o += LM_THREADS) yr[o] = (STREAM && n0 + o < 0) ? (T)0 : nan;
         }
         if (p.gain)
-            for (int o = t; o < p.tile && n0 + o < p.T_; o += LM_THREADS) p.gain[grp * p.T_ + n0 + o] = nan;
+            for (int o = t; o < nout; o += LM_THREADS) p.gain[grp * pitch + y0 + o] = (STREAM && n0 + o < 0) ? (T)1 : nan;
         return;
     }
     // r, and its copy the sliding minimum starts from
-    for (int a = t; a < LM_NR; a += LM_THREADS) {
+    for (int a = t; a < np; a += LM_THREADS) {
         const int64_t i = rb + a;
         const T pv = rr[lm_idx(a)];
         const T rv = (i >= 0 && i < p.T_ && pv > p.c) ? lm_div(p.c, pv) : (T)1;
@@ -218,12 +279,16 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
         T v[LM_EPT];
 #pragma unroll
         for (int e = 0; e < LM_EPT; ++e) {
-            const int a = e * LM_THREADS + t, b = a + w < LM_NR ? a + w : a;
-            v[e] = lm_min(reg[a], reg[b]);
+            if (STREAM && e * LM_THREADS >= np) break;
+            const int a = e * LM_THREADS + t, b = a + w < np ? a + w : a;
+            v[e] = (!STREAM || a < np) ? lm_min(reg[a], reg[b]) : (T)1;
         }
         __syncthreads();
 #pragma unroll
-        for (int e = 0; e < LM_EPT; ++e) reg[e * LM_THREADS + t] = v[e];
+        for (int e = 0; e < LM_EPT; ++e) {
+            if (STREAM && e * LM_THREADS >= np) break;
+            reg[e * LM_THREADS + t] = v[e];
+        }
         __syncthreads();
         w *= 2;
     }
@@ -231,27 +296,30 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
     // of w; transposed in place through registers.  Entries in front of n0 - A + 1 meet zero weights only: 0.
     {
         const int shift = p.Apad - p.A;
+        const int nd = STREAM ? (nout + TP_R - 1) / TP_R * TP_R + p.Apad : LM_DE * LM_THREADS;    // entries the sweeps read
         T d[LM_DE];
 #pragma unroll
         for (int e = 0; e < LM_DE; ++e) {
+            if (STREAM && e * LM_THREADS >= nd) break;
             const int a = e * LM_THREADS + t + 1 - shift;
-            d[e] = (a >= 1 && a + W - 1 < LM_NR) ? (T)1 - lm_min(reg[a], reg[a + W - w]) : (T)0;
+            d[e] = (a >= 1 && a + W - 1 < np) ? (T)1 - lm_min(reg[a], reg[a + W - w]) : (T)0;
         }
         __syncthreads();
 #pragma unroll
         for (int e = 0; e < LM_DE; ++e) {
+            if (STREAM && e * LM_THREADS >= nd) break;
             const int dl = e * LM_THREADS + t;
             reg[(dl % TP_R) * LM_SD + dl / TP_R] = d[e];
         }
         __syncthreads();
     }
     // s and g: 16 consecutive outputs per thread and sweep
-    for (int sw = 0; sw * (int)TP_TILE < p.tile; ++sw) {
+    for (int sw = 0; sw * (int)TP_TILE < nout; ++sw) {
         const int o0 = sw * (int)TP_TILE + t * TP_R;
         T acc[TP_R];
 #pragma unroll
         for (int e = 0; e < TP_R; ++e) acc[e] = (T)0;
-        if (o0 < p.tile) {
+        if (o0 < nout) {
 #pragma unroll 1
             for (int jb = p.Apad - TP_R; jb >= 0; jb -= TP_R) {
                 // weights j = jb + jj; output e reads d at o0 + cb + e + 15 - jj, cb = Apad - 16 - jb
@@ -269,7 +337,7 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
             }
 #pragma unroll
             for (int e = 0; e < TP_R; ++e) {
-                if (o0 + e < p.tile) {
+                if (o0 + e < nout) {
                     const int ix = lm_idx(o0 + e + p.A + p.H - 1);
                     T g = (T)1 - acc[e];
                     g = g > (T)0 ? g : (T)0;
@@ -280,12 +348,16 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
     }
     __syncthreads();
     for (int ch = 0; ch < p.channels; ++ch) {
-        const T *xr = xg + (int64_t)ch * p.T_;
-        T *yr = p.y + (grp * p.channels + ch) * p.T_;
-        for (int o = t; o < p.tile && n0 + o < p.T_; o += LM_THREADS) yr[n0 + o] = rr[lm_idx(o + p.A + p.H - 1)] * xr[n0 + o];
+        const LmRow<T, STREAM> xr(p, grp * p.channels + ch);
+        T *yr = p.y + (grp * p.channels + ch) * pitch + y0;
+        for (int o = t; o < nout; o += LM_THREADS) {
+            if constexpr (STREAM) yr[o] = n0 + o < 0 ? (T)0 : rr[lm_idx(o + p.A + p.H - 1)] * xr.at(n0 + o);
+            else yr[o] = rr[lm_idx(o + p.A + p.H - 1)] * xr.xr[n0 + o];
+        }
     }
     if (p.gain)
-        for (int o = t; o < p.tile && n0 + o < p.T_; o += LM_THREADS) p.gain[grp * p.T_ + n0 + o] = rr[lm_idx(o + p.A + p.H - 1)];
+        for (int o = t; o < nout; o += LM_THREADS)
+            p.gain[grp * pitch + y0 + o] = (STREAM && n0 + o < 0) ? (T)1 : rr[lm_idx(o + p.A + p.H - 1)];
 }
 
 struct LimiterPlan {
@@ -294,27 +366,27 @@ struct LimiterPlan {
 };
 
 // everything but the pointers and the values of c and the window (host-only)
-static LimiterPlan limiter_plan(int dtype, int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh)
+static LimiterPlan limiter_plan(const char *what, int dtype, int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh)
 {
-    TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "limiter_forward: bad dtype %d", dtype);
-    TFX_CHECK(up == 1 || up == 2 || up == 4 || up == 8, "limiter_forward: up must be 1, 2, 4 or 8, got %lld", (long long)up);
-    TFX_CHECK(groups >= 0 && T >= 0, "limiter_forward: negative size");
-    TFX_CHECK(channels >= 1 && channels <= (1 << 20), "limiter_forward: channels must be in [1, 2^20], got %lld", (long long)channels);
-    TFX_CHECK(A >= 1 && A <= LM_A_MAX, "limiter_forward: look-ahead of %lld samples, the limit is 1 ... %lld", (long long)A,
+    TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "%s: bad dtype %d", what, dtype);
+    TFX_CHECK(up == 1 || up == 2 || up == 4 || up == 8, "%s: up must be 1, 2, 4 or 8, got %lld", what, (long long)up);
+    TFX_CHECK(groups >= 0 && T >= 0, "%s: negative size", what);
+    TFX_CHECK(channels >= 1 && channels <= (1 << 20), "%s: channels must be in [1, 2^20], got %lld", what, (long long)channels);
+    TFX_CHECK(A >= 1 && A <= LM_A_MAX, "%s: look-ahead of %lld samples, the limit is 1 ... %lld", what, (long long)A,
               (long long)LM_A_MAX);
-    TFX_CHECK(H >= 1 && H <= LM_H_MAX, "limiter_forward: hold of %lld samples, the limit is 1 ... %lld", (long long)H,
+    TFX_CHECK(H >= 1 && H <= LM_H_MAX, "%s: hold of %lld samples, the limit is 1 ... %lld", what, (long long)H,
               (long long)LM_H_MAX);
-    TFX_CHECK(T <= (INT64_MAX / 64) / up, "limiter_forward: T * up overflows");
+    TFX_CHECK(T <= (INT64_MAX / 64) / up, "%s: T * up overflows", what);
     LimiterPlan pl{};
     if (up > 1) {
-        TFX_CHECK(nh >= 1, "limiter_forward: no taps");
-        TFX_CHECK(nh <= 64 * up, "limiter_forward: %lld taps, at most 64 * up = %lld are held in registers", (long long)nh,
+        TFX_CHECK(nh >= 1, "%s: no taps", what);
+        TFX_CHECK(nh <= 64 * up, "%s: %lld taps, at most 64 * up = %lld are held in registers", what, (long long)nh,
                   (long long)(64 * up));
         pl.g = resample_geometry(T, up, 1, nh);
-        TFX_CHECK(pl.g.Lp <= TP_LP_MAX, "limiter_forward: %lld taps per phase", (long long)pl.g.Lp);
+        TFX_CHECK(pl.g.Lp <= TP_LP_MAX, "%s: %lld taps per phase", what, (long long)pl.g.Lp);
         pl.LP = tp_bucket(pl.g.Lp);
         pl.i_lo = pl.g.pre_remove / up;
-        TFX_CHECK(pl.i_lo <= pl.LP - 1, "limiter_forward: the filter's delay exceeds its taps per phase");
+        TFX_CHECK(pl.i_lo <= pl.LP - 1, "%s: the filter's delay exceeds its taps per phase", what);
     }
     pl.tile = LM_NR + 1 - 2 * A - H;
     pl.tiles = ceil_div(T, pl.tile);
@@ -322,28 +394,35 @@ static LimiterPlan limiter_plan(int dtype, int64_t groups, int64_t channels, int
     pl.halo_right = A + pl.i_lo;
     pl.lds = (int64_t)(LM_PAD + LM_REGION) * (dtype == TFX_F32 ? 4 : 8);
     TFX_CHECK(groups == 0 || (T <= INT64_MAX / 16 / groups / channels && pl.tiles < (1ll << 31) / groups),
-              "limiter_forward: size overflows");
+              "%s: size overflows", what);
     return pl;
+}
+
+static void limiter_check_values(const char *what, int dtype, double c, int64_t A, const void *window_host, int64_t up,
+                                 const void *taps_host)
+{
+    TFX_CHECK(std::isfinite(c) && c > 0.0, "%s: the ceiling must be a finite linear value > 0, got %g", what, c);
+    TFX_CHECK(window_host, "%s: no window", what);
+    TFX_CHECK(up == 1 || taps_host, "%s: no taps", what);
+    for (int64_t j = 0; j < A; ++j) {
+        const double v = dtype == TFX_F32 ? (double)((const float *)window_host)[j] : ((const double *)window_host)[j];
+        TFX_CHECK(std::isfinite(v) && v >= 0.0, "%s: window[%lld] = %g is negative or not finite", what, (long long)j, v);
+    }
 }
 
 void limiter_check(const void *x, const void *y, int dtype, int64_t groups, int64_t channels, int64_t T, double c, int64_t A,
                    int64_t H, const void *window_host, int64_t up, const void *taps_host, int64_t nh)
 {
-    (void)limiter_plan(dtype, groups, channels, T, A, H, up, nh);
-    TFX_CHECK(std::isfinite(c) && c > 0.0, "limiter_forward: the ceiling must be a finite linear value > 0, got %g", c);
-    TFX_CHECK(window_host, "limiter_forward: no window");
-    TFX_CHECK(up == 1 || taps_host, "limiter_forward: no taps");
-    for (int64_t j = 0; j < A; ++j) {
-        const double v = dtype == TFX_F32 ? (double)((const float *)window_host)[j] : ((const double *)window_host)[j];
-        TFX_CHECK(std::isfinite(v) && v >= 0.0, "limiter_forward: window[%lld] = %g is negative or not finite", (long long)j, v);
-    }
-    TFX_CHECK(groups * T == 0 || (x && y), "limiter_forward: null pointer");
+    const char *what = "limiter_forward";
+    (void)limiter_plan(what, dtype, groups, channels, T, A, H, up, nh);
+    limiter_check_values(what, dtype, c, A, window_host, up, taps_host);
+    TFX_CHECK(groups * T == 0 || (x && y), "%s: null pointer", what);
 }
 
 void limiter_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh, int dtype,
                        int64_t *tile, int64_t *tiles, int64_t *halo_left, int64_t *halo_right, int64_t *Lp, int64_t *lds_bytes)
 {
-    const LimiterPlan pl = limiter_plan(dtype, groups, channels, T, A, H, up, nh);
+    const LimiterPlan pl = limiter_plan("limiter_forward", dtype, groups, channels, T, A, H, up, nh);
     *tile = pl.tile;
     *tiles = pl.tiles;
     *halo_left = pl.halo_left;
@@ -355,23 +434,31 @@ void limiter_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, i
 // the smoothing weights zero padded to a multiple of 16, by content
 static PlanCache<DeviceBuffer, 2> g_windows(32, "limiter_forward");
 
-template <typename T, int LP> static void limiter_launch_lp(const LimiterArgs<T> &p, int64_t groups, size_t lds, hipStream_t stream)
+template <typename T, int LP, bool STREAM>
+static void limiter_launch_lp(const LimiterArgs<T> &p, int64_t groups, size_t lds, hipStream_t stream)
 {
     static bool attr_done[TFX_MAX_DEVICES] = {};
     bool &done = attr_done[current_device()];
     if (!done) {
-        TFX_HIP(hipFuncSetAttribute((const void *)limiter_kernel<T, LP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        TFX_HIP(hipFuncSetAttribute((const void *)limiter_kernel<T, LP, STREAM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         done = true;
     }
-    ProfScope ps("limiter_kernel", stream);
-    hipLaunchKernelGGL((limiter_kernel<T, LP>), dim3((unsigned)(groups * p.tiles)), dim3(LM_THREADS), lds, stream, p);
+    ProfScope ps(STREAM ? "limiter_stream_kernel" : "limiter_kernel", stream);
+    hipLaunchKernelGGL((limiter_kernel<T, LP, STREAM>), dim3((unsigned)(groups * p.tiles)), dim3(LM_THREADS), lds, stream, p);
     TFX_HIP(hipGetLastError());
 }
+
+// the stream form's extra arguments (tfx_limiter_stream_forward); N is `consumed` after the clamp
+struct LimiterStreamArgs {
+    const void *hist_in;
+    void *hist_out;
+    int64_t n_in, N, D, Hs;
+};
 
 template <typename T>
 static void limiter_launch(const void *x, void *y, void *gain, int64_t groups, int64_t channels, int64_t T_, double c, int64_t A,
                            int64_t H, const void *window_host, int64_t up, const void *taps_host, int64_t nh,
-                           const LimiterPlan &pl, hipStream_t stream)
+                           const LimiterPlan &pl, hipStream_t stream, const LimiterStreamArgs *st = nullptr)
 {
     std::shared_ptr<DeviceBuffer> table, window;
     LimiterArgs<T> p{};
@@ -385,22 +472,32 @@ static void limiter_launch(const void *x, void *y, void *gain, int64_t groups, i
     p.x = (const T *)x; p.y = (T *)y; p.gain = (T *)gain; p.w = (const T *)window->p;
     p.T_ = T_; p.tiles = pl.tiles; p.up = up; p.channels = (int)channels; p.A = (int)A; p.Apad = (int)Apad; p.H = (int)H;
     p.tile = (int)pl.tile; p.c = (T)c;
+    if (st) {                                   // T_ is the chunk's length; the kernel's T_ is where the stream ends so far
+        p.hist = (const T *)st->hist_in; p.hist_out = (T *)st->hist_out;
+        p.Tc = T_; p.N = st->N; p.Hs = st->Hs; p.n_in = st->n_in; p.D = (int)st->D;
+        T_ = p.T_ = st->N + st->n_in;
+    }
     if (up > 1) {
         p.hp = resample_table<T>(taps_host, nh, up, 1, pl.g.pre_pad, pl.LP, stream, &table);
         p.i_lo = pl.i_lo; p.n_lo = pl.g.pre_remove; p.n_hi = pl.g.pre_remove + T_ * up;
         p.rem = (int)(pl.g.pre_remove % up); p.xoff = (int)(pl.LP - 1 - pl.i_lo);
     }
     const size_t lds = (size_t)pl.lds;
+#define TFX_LM_CASE(LP_) \
+    if (st) limiter_launch_lp<T, LP_, true>(p, groups, lds, stream); \
+    else limiter_launch_lp<T, LP_, false>(p, groups, lds, stream); \
+    break
     switch (up > 1 ? pl.LP : 0) {
-    case 0: limiter_launch_lp<T, 0>(p, groups, lds, stream); break;
-    case 8: limiter_launch_lp<T, 8>(p, groups, lds, stream); break;
-    case 16: limiter_launch_lp<T, 16>(p, groups, lds, stream); break;
-    case 24: limiter_launch_lp<T, 24>(p, groups, lds, stream); break;
-    case 32: limiter_launch_lp<T, 32>(p, groups, lds, stream); break;
-    case 48: limiter_launch_lp<T, 48>(p, groups, lds, stream); break;
-    case 64: limiter_launch_lp<T, 64>(p, groups, lds, stream); break;
-    default: limiter_launch_lp<T, (int)TP_LP_MAX>(p, groups, lds, stream); break;
+    case 0: TFX_LM_CASE(0);
+    case 8: TFX_LM_CASE(8);
+    case 16: TFX_LM_CASE(16);
+    case 24: TFX_LM_CASE(24);
+    case 32: TFX_LM_CASE(32);
+    case 48: TFX_LM_CASE(48);
+    case 64: TFX_LM_CASE(64);
+    default: TFX_LM_CASE((int)TP_LP_MAX);
     }
+#undef TFX_LM_CASE
 }
 
 void limiter_forward(const void *x, void *y, void *gain, int dtype, int64_t groups, int64_t channels, int64_t T, double c,
@@ -409,9 +506,90 @@ void limiter_forward(const void *x, void *y, void *gain, int dtype, int64_t grou
 {
     limiter_check(x, y, dtype, groups, channels, T, c, A, H, window_host, up, taps_host, nh);
     if (groups * T == 0) return;
-    const LimiterPlan pl = limiter_plan(dtype, groups, channels, T, A, H, up, nh);
+    const LimiterPlan pl = limiter_plan("limiter_forward", dtype, groups, channels, T, A, H, up, nh);
     if (dtype == TFX_F32) limiter_launch<float>(x, y, gain, groups, channels, T, c, A, H, window_host, up, taps_host, nh, pl, stream);
     else limiter_launch<double>(x, y, gain, groups, channels, T, c, A, H, window_host, up, taps_host, nh, pl, stream);
+}
+
+// ---- the stream form ------------------------------------------------------------------------------------------------------
+// Geometry of a stream (A, H, up, nh alone).  p[i] takes the interpolator's outputs of positions i - 1, i and i + 1's phases
+// below rem: the newest input any of them reads is i + i_lo -- i + i_lo + 1 when rem >= 2 (with rem == 1 the one tap that
+// meets it is the zero SciPy pads in front; with an odd-length design rem is 1) -- and the oldest i - 1 + i_lo - (Lp - 1).
+// g[n] reads r over [n - A - H + 2, n + A - 1].  So output n is final once input n + D is in, D = A - 1 + forward reach, and
+// the chunk that starts with output N - D reads back to N - D - (A + H - 2) - (Lp - i_lo).
+struct LimiterStreamPlan {
+    LimiterPlan pl;
+    int64_t D, Hs, positions;
+};
+
+static LimiterStreamPlan limiter_stream_plan(int dtype, int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H,
+                                             int64_t up, int64_t nh)
+{
+    LimiterStreamPlan sp{};
+    sp.pl = limiter_plan("limiter_stream_forward", dtype, groups, channels, T, A, H, up, nh);
+    const int64_t rem = up > 1 ? sp.pl.g.pre_remove % up : 0;
+    const int64_t back = up > 1 ? std::max<int64_t>(1, sp.pl.g.Lp - sp.pl.i_lo) : 0;
+    sp.D = A - 1 + sp.pl.i_lo + (rem >= 2 ? 1 : 0);
+    sp.Hs = sp.D + A + H - 2 + back;
+    sp.positions = std::min(T, sp.pl.tile) + 2 * A + H - 2;
+    return sp;
+}
+
+void limiter_stream_check(const void *x, const void *y, const void *gain, int dtype, int64_t groups, int64_t channels, int64_t T,
+                          int64_t n_in, int64_t consumed, double c, int64_t A, int64_t H, const void *window_host, int64_t up,
+                          const void *taps_host, int64_t nh, const void *hist_in, const void *hist_out)
+{
+    const char *what = "limiter_stream_forward";
+    const LimiterStreamPlan sp = limiter_stream_plan(dtype, groups, channels, T, A, H, up, nh);
+    limiter_check_values(what, dtype, c, A, window_host, up, taps_host);
+    TFX_CHECK(n_in >= 0 && n_in <= T, "%s: n_in = %lld is not in [0, T = %lld]", what, (long long)n_in, (long long)T);
+    TFX_CHECK(consumed >= 0, "%s: negative stream position %lld", what, (long long)consumed);
+    const int64_t rows = groups * channels;
+    TFX_CHECK(rows * T == 0 || y, "%s: null pointer", what);
+    TFX_CHECK(rows * n_in == 0 || x, "%s: null pointer", what);
+    const size_t esz = dtype == TFX_F32 ? 4 : 8;
+    check_stream_buffers(what, esz, x, rows * T, y, rows * T, hist_in, hist_out, rows * sp.Hs);
+    check_stream_buffers(what, esz, x, rows * T, gain, groups * T, hist_in, hist_out, rows * sp.Hs);
+    check_stream_buffers(what, esz, y, rows * T, gain, groups * T, nullptr, nullptr, 0);
+}
+
+void limiter_stream_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh, int dtype,
+                              int64_t *latency, int64_t *history, int64_t *tile, int64_t *tiles, int64_t *positions,
+                              int64_t *lds_bytes)
+{
+    const LimiterStreamPlan sp = limiter_stream_plan(dtype, groups, channels, T, A, H, up, nh);
+    *latency = sp.D;
+    *history = sp.Hs;
+    *tile = sp.pl.tile;
+    *tiles = sp.pl.tiles;
+    *positions = sp.positions;
+    *lds_bytes = sp.pl.lds;
+}
+
+void limiter_stream_forward(const void *x, void *y, void *gain, int dtype, int64_t groups, int64_t channels, int64_t T, int64_t n_in,
+                            int64_t consumed, double c, int64_t A, int64_t H, const void *window_host, int64_t up,
+                            const void *taps_host, int64_t nh, const void *hist_in, void *hist_out, hipStream_t stream)
+{
+    limiter_stream_check(x, y, gain, dtype, groups, channels, T, n_in, consumed, c, A, H, window_host, up, taps_host, nh, hist_in,
+                         hist_out);
+    const LimiterStreamPlan sp = limiter_stream_plan(dtype, groups, channels, T, A, H, up, nh);
+    const int64_t rows = groups * channels;
+    if (rows == 0) return;
+    if (T == 0) {                                // nothing in, nothing out: the history moves on unchanged
+        const size_t bytes = (size_t)(rows * sp.Hs) * (dtype == TFX_F32 ? 4 : 8);
+        if (hist_out && bytes) {
+            if (hist_in) TFX_HIP(hipMemcpyAsync(hist_out, hist_in, bytes, hipMemcpyDeviceToDevice, stream));
+            else TFX_HIP(hipMemsetAsync(hist_out, 0, bytes, stream));
+        }
+        return;
+    }
+    // positions before N - Hs are never read and position 0 matters only while it lies in [N - Hs, N + T): past Hs + D every N
+    // gives the same chunk
+    const LimiterStreamArgs st{hist_in, hist_out, n_in, std::min(consumed, sp.Hs + sp.D), sp.D, sp.Hs};
+    if (dtype == TFX_F32)
+        limiter_launch<float>(x, y, gain, groups, channels, T, c, A, H, window_host, up, taps_host, nh, sp.pl, stream, &st);
+    else
+        limiter_launch<double>(x, y, gain, groups, channels, T, c, A, H, window_host, up, taps_host, nh, sp.pl, stream, &st);
 }
 
 void limiter_clear() { g_windows.clear(); }

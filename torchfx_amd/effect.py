@@ -246,7 +246,8 @@ class Limiter(FX):
     The sample ceiling ``|y| <= c (1 + u)^2`` always holds; the true peak of the result is measured, not guaranteed (within
     0.001 dB of the ceiling at the default 1.5 ms look-ahead on the material measured, more with a shorter one -- see
     :func:`~torchfx_amd.limiter.limit`).  ``fs`` comes from the ``Wave`` the effect is piped into when it is None.  The gain
-    looks ``A - 1`` samples ahead: the limiter is a step of its own in ``Wave.plan()`` and cannot run in a chunked stream."""
+    looks ``A - 1`` samples ahead: the limiter is a step of its own in ``Wave.plan()`` and cannot run in a chunked stream --
+    :class:`torchfx_amd.realtime.StatefulLimiter` is the effect for that."""
 
     def __init__(self, ceiling_db: float = -1.0, lookahead: float = 1.5e-3, hold: float = 10e-3, detector: str = "true_peak",
                  link: bool = True, oversample: int | None = None, taps=None, window=None, fs: int | None = None) -> None:

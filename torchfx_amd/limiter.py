@@ -5,7 +5,9 @@ can only lower the whole programme's gain, the limiter takes down the peaks alon
 followed by a short FIR -- no recursion -- so every output depends on a bounded window of inputs.  On ROCm device float32 /
 float64 tensors ONE HIP launch (``csrc/limiter.hip``, :func:`torchfx_ext.limiter_forward`) reads the signal once and writes
 it once: the detector's oversampled signal, the gain curve and its intermediates never leave the chip.  CPU tensors run
-NumPy / SciPy with the same definition in the signal's dtype.  A streaming limiter is not provided.
+NumPy / SciPy with the same definition in the signal's dtype.  For a chunked stream the bounded window is what makes
+:class:`torchfx_amd.realtime.StatefulLimiter` possible: it carries a fixed input history per row and its chunks plus ``flush()``
+are this function's result on the whole signal, bit for bit.
 """
 from __future__ import annotations
 

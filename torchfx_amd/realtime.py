@@ -15,7 +15,10 @@ time-based effects: they carry the last ``taps * delay_samples`` (``delay``) inp
 chunk's shape, and one launch per chunk (``tfx_delay_stream_forward`` / ``tfx_delay_line_stream_forward``) gives the
 one-shot effect's bits.  :class:`StatefulResample` converts the rate of a stream: it carries the last ``Lp_s - 1`` inputs of
 every row, returns the outputs each chunk completes (``tfx_resample_stream_forward``), and its chunks plus ``flush()`` are
-``resample_poly`` on the whole signal.
+``resample_poly`` on the whole signal.  :class:`StatefulLimiter` is the look-ahead limiter of a stream: it carries the last
+``D + A + H - 2`` (+ the detector interpolator's reach) inputs of every row, holds the last ``D = A - 1 + i_lo`` outputs back
+(``tfx_limiter_stream_forward``, one launch per chunk), and its chunks plus ``flush()`` are ``limit`` on the whole signal;
+``aligned=False`` gives the constant-latency form a sound card needs.
 
 Small chunks are launch-bound (a 2 x 4096 step is ~60 us of host + launch overhead for a few us of
 GPU work), so ``StreamProcessor(..., use_graph=True)`` captures one full-size chunk step -- every
@@ -35,7 +38,7 @@ from collections.abc import Generator, Sequence
 import torch
 from torch import Tensor, nn
 
-from torchfx_amd.effect import FX, Delay, MonoDelayStrategy, PingPongDelayStrategy, Reverb, _ext
+from torchfx_amd.effect import FX, Delay, Limiter, MonoDelayStrategy, PingPongDelayStrategy, Reverb, _ext
 from torchfx_amd.filter._base import AbstractFilter
 from torchfx_amd.filter.fir import FIR
 from torchfx_amd.resample import Resample, design_taps, window_key
@@ -359,6 +362,187 @@ class StatefulResample(_RingOut, Resample):
         return tail
 
 
+class StatefulLimiter(_RingOut, Limiter):
+    """:class:`~torchfx_amd.effect.Limiter` over a continuous stream: chunks go in, the limited signal comes out with no seam.
+    The gain at a sample reads ``latency`` = ``D = A - 1 + i_lo`` samples ahead (``A`` the look-ahead in samples, ``i_lo`` the
+    detector interpolator's forward reach: 0 for ``detector="sample"``, 10 for the library's filters), so after ``N`` input
+    samples per row the stream has returned the first ``max(0, N - D)`` samples of :func:`~torchfx_amd.limiter.limit` on the
+    whole signal, each final, and :meth:`flush` returns the remaining ``min(N, D)``, computed with the stream ending at ``N``.
+
+    * ``aligned=True``: a chunk returns the outputs it completes -- ``max(0, N + T - D) - max(0, N - D)`` samples, possibly
+      none.  All chunk outputs followed by ``flush()`` are ``limit`` on the whole signal: ``torch.equal``, on the same device
+      and in the same dtype, whatever the chunk sizes.
+    * ``aligned=False`` (constant latency, what a sound card needs): every chunk returns the chunk's shape, the one-shot result
+      delayed by ``D`` samples with zeros first; ``flush()`` still returns the last ``min(N, D)``.
+
+    Every row carries its last ``history_length`` input samples in ``_hist`` (``[rows, Hs]``) and the stream one host integer,
+    ``min(N, Hs + D)``: no chunk waits on the device.  Device float32 / float64 chunks run one launch each
+    (:func:`torchfx_ext.limiter_stream_forward`, which reads the history and the chunk from their two buffers and sweeps only the
+    positions the chunk's outputs depend on); CPU chunks run the host definition on ``[history | chunk]``.  The stream restarts
+    from silence -- and what is held back is dropped -- when the row count, dtype, device or ``link`` grouping changes and when
+    ``lookahead``, ``hold``, ``detector``, ``oversample``, ``taps`` or ``fs`` changes.  A changed ``ceiling_db`` or ``window`` (of
+    the same length) applies from the next chunk on without a restart; such a run equals no one-shot call.  A NaN or Inf makes
+    the outputs of the chunks whose ``[history | chunk]`` still holds it NaN (all channels of the group); after that the stream
+    is the clean stream's again, bit for bit.  A ``Wave`` is a whole signal: pipe it through ``Limiter`` instead."""
+
+    def __init__(self, ceiling_db: float = -1.0, lookahead: float = 1.5e-3, hold: float = 10e-3, detector: str = "true_peak",
+                 link: bool = True, oversample: int | None = None, taps=None, window=None, fs: int | None = None,
+                 aligned: bool = True) -> None:
+        super().__init__(ceiling_db, lookahead, hold, detector, link, oversample, taps, window, fs)
+        self.aligned = bool(aligned)
+        self._pcache: tuple | None = None
+        self._geos: dict = {}
+        self.reset_state()
+
+    def reset_state(self) -> None:
+        self._hist: Tensor | None = None
+        self._pos = 0                               # min(N, Hs + D): input samples per row so far, as far as it matters
+        self._key: tuple | None = None              # what the running stream is bound to (see _stream)
+        self._geo: tuple[int, int] = (0, 0)         # its (D, Hs)
+        self._last: tuple | None = None
+
+    def _params(self, dtype: torch.dtype):
+        """``self.params(dtype)``, kept while the attributes it is made from stay what they were."""
+        ver = tuple((id(v), getattr(v, "_version", None)) for v in (self.taps, self.window))
+        key = (dtype, self.fs, self.ceiling_db, self.lookahead, self.hold, self.detector, self.oversample, ver)
+        if self._pcache is None or self._pcache[0] != key:
+            self._pcache = (key, self.params(dtype), (self.taps, self.window))
+        return self._pcache[1]
+
+    def _geometry(self, P) -> tuple[int, int]:
+        """``(D, Hs)`` of the stream: ``tfx_limiter_stream_plan_info``'s latency and history (host-only)."""
+        key = (P.A, P.H, P.up, 0 if P.taps is None else int(P.taps.numel()))
+        geo = self._geos.get(key)
+        if geo is None:
+            info = _ext().limiter_stream_plan_info(0, *key)
+            geo = self._geos[key] = (info["latency"], info["history"])
+        return geo
+
+    @property
+    def latency(self) -> int:
+        """The samples the stream holds back (``D``): what :meth:`flush` returns at most, and the delay of ``aligned=False``."""
+        return self._geometry(self._params(torch.float32))[0]
+
+    @property
+    def history_length(self) -> int:
+        """The input samples every row carries between chunks (``Hs = D + A + H - 2`` plus the interpolator's backward reach)."""
+        return self._geometry(self._params(torch.float32))[1]
+
+    def _stream(self, lead: tuple, dtype: torch.dtype, device) -> tuple:
+        """``(P, groups, channels, key, (D, Hs))`` for chunks of leading shape ``lead``: a stream lives while ``key`` stays."""
+        P = self._params(dtype)
+        channels = int(lead[-1]) if (self.link and lead) else 1        # limiter._grouping, from the leading shape
+        groups = math.prod(lead) // channels if channels else 0
+        key = (groups, channels, dtype, device, P.A, P.H, P.up, None if P.taps is None else P.taps.numpy().tobytes())
+        return P, groups, channels, key, self._geometry(P)
+
+    def route(self, x: Tensor, length: int | None = None) -> str:
+        """``native (limiter_stream_kernel, ...)`` for the next chunk of ``x``, or the host / refusal route."""
+        if not _native_stream(x):
+            return super().route(x, length)
+        try:
+            P = self.params(x.dtype)
+            n = int(x.shape[-1]) if length is None else int(length)
+            info = _ext().limiter_stream_plan_info(n, P.A, P.H, P.up, 0 if P.taps is None else int(P.taps.numel()), x.dtype)
+        except (RuntimeError, ValueError, TypeError) as e:
+            return f"refused -- {e}"
+        det = f"{P.up}x oversampled detector" if P.up > 1 else "sample-peak detector"
+        return (f"native (limiter_stream_kernel, {det}, look-ahead {P.A} / hold {P.H} samples, latency {info['latency']}, history "
+                f"{info['history']}, {info['tiles']} tile(s), {info['positions']} of 8192 positions swept; one launch)")
+
+    def _capture_key(self) -> tuple:
+        """What a captured HIP graph of this effect bakes in (the ceiling and the window among it)."""
+        dtype = self._last[1] if self._last is not None else torch.float32
+        return self._params(dtype).key(), self.link, self.aligned
+
+    def _sync_history(self) -> None:
+        """Nothing to resize: a parameter that changes the history's length restarts the stream (``_graph_ready``)."""
+
+    def _graph_ready(self, x: Tensor) -> bool:
+        """A replay skips :meth:`forward`: it leaves nothing stale once the position counter has saturated, for the stream
+        that is running."""
+        if self._key is None or self._pos != sum(self._geo):
+            return False
+        return self._stream(tuple(x.shape[:-1]), x.dtype, x.device)[3] == self._key
+
+    @torch.no_grad()
+    def forward(self, x: Tensor) -> Tensor:
+        _rows(x)
+        P, groups, channels, key, geo = self._stream(tuple(x.shape[:-1]), x.dtype, x.device)
+        if key != self._key:                        # a new stream: from silence
+            self.reset_state()
+            self._key, self._geo = key, geo
+        self._note(x)
+        (D, Hs), N, T = geo, self._pos, x.shape[-1]
+        if T == 0:
+            return torch.zeros_like(x)
+        if _native_stream(x):
+            with torch.cuda.device(x.device):
+                y, _, self._hist = _ext().limiter_stream_forward(x, self._hist, N, P.c, P.A, P.H, torch.from_numpy(P.w), P.up,
+                                                                 P.taps, channels, False)
+        else:
+            y = self._host_chunk(x, P, groups, channels)
+        self._pos = min(N + T, Hs + D)
+        k = min(T, max(0, D - N)) if self.aligned else 0         # outputs in front of position 0
+        return y[..., k:] if k else y
+
+    def _window(self, rows: int, dtype: torch.dtype) -> tuple[Tensor, Tensor]:
+        """``(history [rows, Hs], its valid part)``: the part starts at position 0 while the stream is younger than ``Hs``."""
+        Hs = self._geo[1]
+        hist = self._hist.cpu() if self._hist is not None else torch.zeros(rows, Hs, dtype=dtype)
+        return hist, hist[:, Hs - min(self._pos, Hs):]
+
+    def _host_chunk(self, x: Tensor, P, groups: int, channels: int) -> Tensor:
+        """One chunk on the host: the one-shot definition on ``[history | chunk]`` -- its start is position 0 or a sample no
+        output of the chunk reads behind, its end a sample none reads past -- and the chunk's outputs cut from it."""
+        from torchfx_amd.limiter import _limit_host
+
+        (D, Hs), N, T = self._geo, self._pos, x.shape[-1]
+        rows = groups * channels
+        hist, valid = self._window(rows, x.dtype)
+        xr = x.detach().reshape(rows, T).cpu()
+        v = torch.cat([valid, xr], dim=-1)                   # positions [N - valid, N + T)
+        self._hist = torch.cat([hist, xr], dim=-1)[:, T:].to(x.device)
+        out = torch.zeros(rows, T, dtype=x.dtype)
+        lo = max(0, N - D)
+        n = N + T - D - lo
+        if n > 0:
+            s = lo - (N - valid.shape[-1])
+            out[:, T - n:] = _limit_host(v, P, groups, channels)[0][:, s:s + n]
+        return out.reshape(x.shape).to(x.device)
+
+    @torch.no_grad()
+    def flush(self) -> Tensor:
+        """The outputs still held back (the last ``min(N, latency)`` samples of the one-shot result), computed with the stream
+        ending here and shaped like the last chunk; then the state is reset.  Without a chunk since the last reset, or after a
+        parameter change that restarts the stream: an empty tensor."""
+        if self._last is None:
+            return torch.zeros(0)
+        lead, dtype, device = self._last
+        P, groups, channels, key, _ = self._stream(lead, dtype, device)
+        D, N = self._geo[0], self._pos
+        n = min(N, D) if key == self._key else 0
+        if n == 0:
+            tail = self._zeros(0)
+        elif device.type == "cuda":
+            with torch.cuda.device(device):           # a chunk of D samples with no input in it: the stream ends at N
+                y = _ext().limiter_stream_forward(self._zeros(D), self._hist, N, P.c, P.A, P.H, torch.from_numpy(P.w), P.up,
+                                                  P.taps, channels, False, 0)[0]
+            tail = y[..., D - n:].contiguous()
+        else:
+            from torchfx_amd.limiter import _limit_host
+
+            v = self._window(groups * channels, dtype)[1]
+            tail = _limit_host(v, P, groups, channels)[0][:, v.shape[-1] - n:].reshape(*lead, n).to(device)
+        self.reset_state()
+        return tail
+
+
+def _holds_back(e) -> bool:
+    """Effects whose chunks may return fewer samples than they take and that hand the rest out in ``flush()``."""
+    return isinstance(e, (StatefulResample, StatefulLimiter))
+
+
 def _has_stateful_resample(e) -> bool:
     return any(isinstance(m, StatefulResample) for m in (e.modules() if isinstance(e, nn.Module) else [e]))
 
@@ -382,12 +566,15 @@ def _refuse_loudness(e, who: str) -> None:
 
 
 def _refuse_limiter(e, who: str) -> None:
-    from torchfx_amd.effect import Limiter
-
-    if any(isinstance(m, Limiter) for m in (e.modules() if isinstance(e, nn.Module) else [e])):
+    members = list(e.modules() if isinstance(e, nn.Module) else [e])
+    if any(isinstance(m, Limiter) and not isinstance(m, StatefulLimiter) for m in members):
         raise TypeError(f"Limiter cannot run in {who}: its gain looks A - 1 samples ahead (the look-ahead), which a chunked stream "
-                        "has not seen yet, and a streaming limiter that carries that history is not provided; limit the whole "
-                        "signal (wave | Limiter(...)) before or after streaming")
+                        "has not seen yet; a streaming limiter that carries that history is not provided by Limiter itself -- use "
+                        "StatefulLimiter(...) in its place, or limit the whole signal (wave | Limiter(...)) before or after "
+                        "streaming")
+    if not isinstance(e, StatefulLimiter) and any(isinstance(m, StatefulLimiter) for m in members):
+        raise TypeError(f"StatefulLimiter must be a top-level effect of the chain in {who}: the processor flushes what it holds "
+                        "back at the end of the stream")
 
 
 class _ChunkRun:
@@ -535,9 +722,11 @@ class StreamProcessor:
                                 "every chunk boundary; use StatefulResample as a top-level effect of the chain, or resample "
                                 "the whole signal (Wave.resample) before or after streaming")
         self._resamplers = [e for e in self._effects if isinstance(e, StatefulResample)]
-        if self._resamplers and overlap != 0:
-            raise ValueError(f"A chain with a StatefulResample needs overlap = 0, got {overlap}: dropped overlap samples "
-                             "have no counterpart in the resampled output")
+        self._limiters = [e for e in self._effects if isinstance(e, StatefulLimiter)]
+        if (self._resamplers or self._limiters) and overlap != 0:
+            who = "StatefulResample" if self._resamplers else "StatefulLimiter"
+            raise ValueError(f"A chain with a {who} needs overlap = 0, got {overlap}: the effect holds outputs back, so a chunk's "
+                             "dropped overlap samples have no counterpart in its output")
         self._chunk_size, self._overlap, self._device = chunk_size, overlap, device
         self._use_graph = use_graph
         self._graph = None            # (CUDAGraph, static in, static out, stream, signature, state slots, homes)
@@ -604,23 +793,29 @@ class StreamProcessor:
         return len(self._segments) == 1 and isinstance(self._segments[0], _ChunkRun) and self._segments[0].fuses(w)
 
     def _run(self, w: Tensor, start: int = 0) -> Tensor | None:
-        """The chain from segment ``start`` on; None when a resampler completes no output for this chunk (the effects
-        after it are not called)."""
+        """The chain from segment ``start`` on; None when an effect that holds outputs back (``StatefulResample``,
+        ``StatefulLimiter``) completes no output for this chunk (the effects after it are not called)."""
         for e in self._segments[start:]:
             w = e(w)
-            if isinstance(e, StatefulResample) and w.shape[-1] == 0:
+            if _holds_back(e) and w.shape[-1] == 0:
                 return None
         return w
 
     def _tails(self) -> Generator[Tensor, None, None]:
-        """The end of the stream: every resampler's held-back outputs, left to right, through the effects after it."""
+        """The end of the stream: the held-back outputs of every resampler and limiter, left to right, each through the effects
+        after it (so a limiter behind a resampler limits the resampler's tail before it hands out its own)."""
         for i, e in enumerate(self._segments):
-            if isinstance(e, StatefulResample):
+            if _holds_back(e):
                 t = e.flush()
                 if t.dim() > 0 and t.shape[-1] > 0:
                     t = self._run(t, i + 1)
                     if t is not None:
                         yield t
+
+    def _graphable(self, w: Tensor) -> bool:
+        """Whether a replayed step leaves the host side of every effect right: a resampler counts samples per chunk (never),
+        a limiter only until its position counter has saturated (chunks run eagerly until then)."""
+        return not self._resamplers and all(m._graph_ready(w) for m in self._limiters)
 
     def _capture_members(self) -> list:
         """Members whose parameters a captured step bakes in and whose carried state can change length (StatefulDelay,
@@ -681,7 +876,7 @@ class StreamProcessor:
         primed = False
         for offset, w in chunks:
             if (self._use_graph and primed and w.is_cuda and w.shape[-1] == self._chunk_size and not self._fused(w)
-                    and not self._resamplers):
+                    and self._graphable(w)):
                 w = self._graph_step(w)
             else:
                 w = self._run(w)            # first chunk creates the states; ragged tail runs eagerly
@@ -846,6 +1041,11 @@ class RealtimeProcessor:
             if _has_stateful_resample(e):
                 raise TypeError("StatefulResample cannot run in RealtimeProcessor: a sound card's output block has the input "
                                 "block's length and sample rate; resample with StreamProcessor or Wave.resample instead")
+            if isinstance(e, StatefulLimiter) and e.aligned:
+                raise TypeError("StatefulLimiter(aligned=True) cannot run in RealtimeProcessor: it returns the outputs a block "
+                                "completes, none for the first blocks, and a sound card's output block has the input block's "
+                                "length; construct it with aligned=False (constant latency: the result delayed by "
+                                "StatefulLimiter.latency samples)")
         self._runner = StreamProcessor(modules, chunk_size=config.buffer_size, overlap=0, device=device, use_graph=use_graph)
         self._backend, self._config, self._running = backend, config, False
         self._buffer_capacity = buffer_capacity
@@ -920,7 +1120,8 @@ class RealtimeProcessor:
 
     def _chain(self, w: Tensor) -> Tensor:
         full = w.shape[-1] == self._config.buffer_size
-        if self._runner._use_graph and w.is_cuda and full and self._primed and not self._runner._fused(w):
+        if (self._runner._use_graph and w.is_cuda and full and self._primed and not self._runner._fused(w)
+                and self._runner._graphable(w)):
             return self._runner._graph_step(w)
         y = self._runner._run(w)             # the first block creates the carried states; ragged blocks run eagerly
         self._primed = self._primed or full
@@ -964,6 +1165,12 @@ class RealtimeProcessor:
         self._primed = False
 
     latency_ms = property(lambda self: self._config.latency_ms)
+
+    @property
+    def chain_latency_samples(self) -> int:
+        """The delay the effects add on top of the buffer's: the sum of their ``latency`` (``StatefulLimiter``'s ``D``)."""
+        return sum(int(getattr(e, "latency", 0) or 0) for e in self._runner.effects)
+
     is_running = property(lambda self: self._running)
     effects = property(lambda self: self._runner.effects)
     config = property(lambda self: self._config)

@@ -36,6 +36,7 @@ __all__ = [
     "delay_amplitudes", "delay_regime", "delay_stream_forward", "delay_line_stream_forward", "resample_forward",
     "resample_plan_info", "resample_stream_forward", "resample_stream_plan_info", "sos_filtfilt", "sos_filtfilt_plan_info",
     "sos_block_energy", "sos_block_energy_plan_info", "true_peak", "true_peak_plan_info", "limiter_forward", "limiter_plan_info",
+    "limiter_stream_forward", "limiter_stream_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
 ]
@@ -293,6 +294,33 @@ def limiter_plan_info(length: int, A: int, H: int, up: int = 1, taps: int = 0, d
     L.check(L.load().tfx_limiter_plan_info(int(groups), int(channels), int(length), int(A), int(H), int(up), int(taps),
                                            L.TFX_F64 if dtype == torch.float64 else L.TFX_F32, *[ctypes.byref(v) for v in o]))
     return dict(zip(("tile", "tiles", "halo_left", "halo_right", "Lp", "lds_bytes"), (v.value for v in o)))
+
+
+def limiter_stream_forward(x: Tensor, hist: Tensor | None, consumed: int, c: float, A: int, H: int, window: Tensor, up: int = 1,
+                           taps: Tensor | None = None, channels: int = 1, return_gain: bool = False,
+                           n_in: int | None = None) -> tuple[Tensor, Tensor | None, Tensor]:
+    """One chunk of a limiter stream in one launch (``tfx_limiter_stream_forward``): ``x [..., T]`` follows ``consumed`` input
+    samples per row, whose last ``Hs`` are ``hist [rows, Hs]`` (None = silence).  Returns ``(y, gain | None, new history)``:
+    ``y[..., t]`` is sample ``consumed - D + t`` of :func:`limiter_forward` on the whole stream (0 where that is negative),
+    ``gain [groups, T]`` the gain curve there (1 where negative) with ``return_gain``.  ``n_in`` (default: all ``T``) is the
+    number of real inputs in ``x``; fewer says that the stream ends after them (the tail of a stream: ``T = D``, ``n_in = 0``).
+    ``D`` and ``Hs`` are :func:`limiter_stream_plan_info`'s ``latency`` and ``history``; the other arguments are
+    :func:`limiter_forward`'s."""
+    y, g, h = native.ops().limiter_stream_forward(x.contiguous(), hist, int(consumed), float(c), int(A), int(H), window, int(up), taps,
+                                                  int(channels), bool(return_gain), -1 if n_in is None else int(n_in))
+    return y, (g if return_gain else None), h
+
+
+def limiter_stream_plan_info(length: int, A: int, H: int, up: int = 1, taps: int = 0, dtype: torch.dtype = torch.float32,
+                             groups: int = 1, channels: int = 1) -> dict:
+    """What :func:`limiter_stream_forward` does with a chunk of ``length`` samples (``tfx_limiter_stream_plan_info``; host-only,
+    same checks on the sizes): the stream's ``latency`` (D) and ``history`` (Hs) -- fixed by ``A``, ``H``, ``up`` and ``taps``
+    alone --, ``tile`` (outputs per workgroup), ``tiles`` per group, ``positions`` (of the 8192 positions of the detector, the
+    division and the sliding minimum, those the first workgroup sweeps) and ``lds_bytes``."""
+    o = [ctypes.c_int64(0) for _ in range(6)]
+    L.check(L.load().tfx_limiter_stream_plan_info(int(groups), int(channels), int(length), int(A), int(H), int(up), int(taps),
+                                                  L.TFX_F64 if dtype == torch.float64 else L.TFX_F32, *[ctypes.byref(v) for v in o]))
+    return dict(zip(("latency", "history", "tile", "tiles", "positions", "lds_bytes"), (v.value for v in o)))
 
 
 RESAMPLE_STREAM_KERNELS = ("resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel", "copy")
