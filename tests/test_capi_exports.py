@@ -82,6 +82,33 @@ def test_custom_ops_registered_with_meta_and_no_cpu_kernel():
         torch.ops.torchfx_hip.fir_direct_forward(torch.zeros(1, 8), torch.ones(3))
 
 
+TORCH_OPS = {
+    "sos_forward", "sos_forward_sections", "sos_bank_forward", "sos_bank_sum_forward", "biquad_forward", "delay_line_forward",
+    "delay_forward", "resample_forward", "sos_filtfilt", "sos_block_energy", "true_peak", "limiter_forward",
+    "limiter_stream_forward", "resample_stream_forward", "delay_forward_ep", "delay_stream_forward", "delay_line_stream_forward",
+    "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep", "fft_conv_forward_ep",
+    "sos_fft_conv_forward", "normalize_apply", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
+    "deinterleave_forward", "deinterleave_into", "interleave_forward",
+}
+
+
+def test_every_op_of_the_namespace_has_a_device_kernel_and_a_cpu_refusal():
+    """The 33 ops of ``torchfx_hip`` and nothing else; each one is registered for the CUDA key (its kernel) and for the CPU key
+    (the "no CPU path" error), so no op can be defined without either."""
+    import torch
+    import torchfx_amd.ops  # noqa: F401
+    names = {s.name for s in torch._C._jit_get_all_schemas() if s.name.startswith("torchfx_hip::")}
+    assert len(TORCH_OPS) == 33
+    assert names == {"torchfx_hip::" + n for n in TORCH_OPS}
+    for name in sorted(names):
+        assert torch._C._dispatch_has_kernel_for_dispatch_key(name, "CUDA"), name
+        assert torch._C._dispatch_has_kernel_for_dispatch_key(name, "CPU"), name
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        torch.ops.torchfx_hip.interleave_forward(torch.zeros(2, 8))
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        torch.ops.torchfx_hip.resample_forward(torch.zeros(1, 8), 2, 1, torch.ones(5))
+
+
 def test_compiled_module_has_the_reference_surface():
     """`torchfx_ext` (pybind) exposes exactly the names of src/torchfx/_csrc/binding.cpp:83-96 with the same
     argument lists (tests/test_ops_dispatch.py:29-35 of the reference asserts the three attributes)."""

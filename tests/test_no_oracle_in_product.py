@@ -42,9 +42,10 @@ def test_no_cpu_fallback_branches():
     for fn in ops:
         assert "native.ops()" in ast.unparse(fn), fn.name
     cpp = open(os.path.join(ROOT, "torchfx_amd", "csrc", "ext", "torchfx_ext.cpp")).read()
-    cuda_block = cpp[cpp.index("TORCH_LIBRARY_IMPL(torchfx_hip, CUDA, m)"):cpp.index("TORCH_LIBRARY_IMPL(torchfx_hip, Meta, m)")]
-    impls = re.findall(r'm\.impl\("(\w+)", (\w+)\)', cuda_block)
-    assert len(impls) >= 14
+    # one reg_op line per op: its schema and the function registered for the CUDA key (the CPU key gets the refusal)
+    ops_block = cpp[cpp.index("TORCH_LIBRARY(torchfx_hip, m)"):cpp.index("TORCH_LIBRARY_IMPL(torchfx_hip, Meta, m)")]
+    impls = re.findall(r'reg_op\(m,\s*"(\w+)\(.*?,\s*(\w+)\);', ops_block, re.S)
+    assert len(impls) == ops_block.count("reg_op(") == 33 and "m.impl(" not in ops_block and "m.def(" not in ops_block
     for name, fn in impls:
         body = cpp[cpp.index(" " + fn + "("):]
         body = body[:body.index("\n}\n")]

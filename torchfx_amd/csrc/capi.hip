@@ -1,10 +1,12 @@
 // capi.hip -- extern "C" surface of libtorchfx_hip.so (see include/torchfx_hip.h) plus the
-// small shared services: thread-local error text, per-kernel HIP-event timing, device scratch,
-// (the elementwise kernels live in effects.hip).
+// small shared services: thread-local error text, per-kernel HIP-event timing, device scratch.
+// An entry point is one call of the op's host function (sos.h, ols_route.h, timedomain.h), which
+// checks its arguments before anything touches the device.
 #include "common.h"
 #include "epilogue.h"
 #include "ols_route.h"
 #include "sos.h"
+#include "timedomain.h"
 #include "../../include/torchfx_hip.h"
 
 #include <atomic>
@@ -14,84 +16,6 @@
 #include <vector>
 
 namespace tfx {
-
-// implemented in fir.hip (the cascade's entry points: sos.h; the overlap-save entry points: ols_route.h)
-void fir_direct_forward(const void *x, void *y, int dtype, int64_t C, int64_t T,
-                        const void *kernel_host, int64_t K, hipStream_t stream, const void *hist = nullptr, int64_t H = 0);
-void quantile_abs_forward(const float *x, int64_t n, double q, double *out_dev, hipStream_t stream);
-void fir_hist_update(const void *x, const void *hist_in, void *hist_out, int dtype, int64_t C, int64_t T, int64_t H,
-                     hipStream_t stream);
-void fir_clear();
-void normalize_apply_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int mode, int per_row, double peak,
-                             const double *stat, hipStream_t stream);
-// effects.hip
-void gain_forward(const void *x, void *y, int dtype, int64_t n, double gain, int clamp, hipStream_t stream);
-void stat_forward(const void *x, int dtype, int64_t C, int64_t T, int mode, int per_row, double *out_dev, hipStream_t stream);
-void normalize_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int mode, int per_row, double peak,
-                       hipStream_t stream);
-void sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, hipStream_t stream);
-void delay_line_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int64_t delay, double coeff,
-                        hipStream_t stream);
-void delay_line_stream_check(const void *x, const void *y, int dtype, int64_t C, int64_t T, int64_t delay, const void *hist_in,
-                             const void *hist_out);
-void delay_line_stream_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int64_t delay, double coeff,
-                               const void *hist_in, void *hist_out, hipStream_t stream);
-// delay.hip
-void delay_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
-                 const double *amps_host, double mix, int pingpong, const Epilogue *ep);
-void delay_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
-                   const double *amps_host, double mix, int pingpong, const Epilogue *ep, hipStream_t stream);
-void delay_stream_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
-                        const double *amps_host, double mix, int pingpong, const void *hist_in, const void *hist_out);
-void delay_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
-                          const double *amps_host, double mix, int pingpong, const void *hist_in, void *hist_out, hipStream_t stream);
-int delay_regime(int64_t D, int64_t taps, int esz, int pingpong);
-void delay_clear();
-// resample.hip
-void resample_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
-                    const void *taps_host, int64_t nh);
-void resample_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down, const void *taps_host,
-                      int64_t nh, hipStream_t stream);
-void resample_plan_info(int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int64_t *n_out, int64_t *pre_remove,
-                        int64_t *padded, int64_t *Lp, int *kernel, int64_t *lds_bytes);
-void resample_stream_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
-                           const void *taps_host, int64_t nh, int64_t consumed, const void *hist_in, const void *hist_out);
-void resample_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
-                             const void *taps_host, int64_t nh, int64_t consumed, const void *hist_in, void *hist_out,
-                             hipStream_t stream);
-void resample_stream_plan_info(int64_t consumed, int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int64_t *out_begin,
-                               int64_t *out_end, int64_t *hist_len, int64_t *pre_remove, int64_t *Lp, int *kernel,
-                               int64_t *lds_bytes);
-void resample_clear();
-void true_peak_check(const void *x, int dtype, const void *peak, int64_t rows, int64_t T, int64_t up, const void *taps_host,
-                     int64_t nh, const void *work);
-void true_peak_forward(const void *x, int dtype, void *peak, int64_t rows, int64_t T, int64_t up, const void *taps_host, int64_t nh,
-                       void *work, hipStream_t stream);
-void true_peak_plan_info(int64_t rows, int64_t T, int64_t up, int64_t nh, int dtype, int64_t *Lp, int64_t *tile_in, int64_t *tiles,
-                         int64_t *work_elems);
-// limiter.hip
-void limiter_check(const void *x, const void *y, int dtype, int64_t groups, int64_t channels, int64_t T, double c, int64_t A,
-                   int64_t H, const void *window_host, int64_t up, const void *taps_host, int64_t nh);
-void limiter_forward(const void *x, void *y, void *gain, int dtype, int64_t groups, int64_t channels, int64_t T, double c,
-                     int64_t A, int64_t H, const void *window_host, int64_t up, const void *taps_host, int64_t nh,
-                     hipStream_t stream);
-void limiter_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh, int dtype,
-                       int64_t *tile, int64_t *tiles, int64_t *halo_left, int64_t *halo_right, int64_t *Lp, int64_t *lds_bytes);
-void limiter_stream_check(const void *x, const void *y, const void *gain, int dtype, int64_t groups, int64_t channels, int64_t T,
-                          int64_t n_in, int64_t consumed, double c, int64_t A, int64_t H, const void *window_host, int64_t up,
-                          const void *taps_host, int64_t nh, const void *hist_in, const void *hist_out);
-void limiter_stream_forward(const void *x, void *y, void *gain, int dtype, int64_t groups, int64_t channels, int64_t T, int64_t n_in,
-                            int64_t consumed, double c, int64_t A, int64_t H, const void *window_host, int64_t up,
-                            const void *taps_host, int64_t nh, const void *hist_in, void *hist_out, hipStream_t stream);
-void limiter_stream_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh, int dtype,
-                              int64_t *latency, int64_t *history, int64_t *tile, int64_t *tiles, int64_t *positions,
-                              int64_t *lds_bytes);
-void limiter_clear();
-// layout.hip
-void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, int64_t C, int64_t ld_out, int64_t f_base,
-                          double scale, hipStream_t stream);
-void interleave_forward(const float *in, float *out, int64_t F, int64_t C, int64_t ld_in, int64_t f_base,
-                        hipStream_t stream);
 
 // ---- environment knobs, read once --------------------------------------------------------------
 namespace {
@@ -294,7 +218,6 @@ void scratch_set_allocator(tfx_alloc_fn a, tfx_free_fn f, void *ctx)
     g_alloc_fn = a; g_free_fn = f; g_alloc_ctx = ctx;
 }
 
-// ---- elementwise kernels ----------------------------------------------------------------------------
 }  // namespace tfx
 
 using namespace tfx;
@@ -534,18 +457,7 @@ int tfx_fir_stream_forward(const void *x, void *y, int dtype, int64_t C, int64_t
                            int direct, const void *hist_in, void *hist_out, tfx_stream_t stream)
 {
     TFX_API_BEGIN
-    TFX_CHECK(K >= 1, "fir_stream_forward: empty kernel");
-    TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "fir_stream_forward: bad dtype %d", dtype);
-    TFX_CHECK(C >= 0 && T >= 0 && (C == 0 || (T <= INT64_MAX / 16 / C && K <= INT64_MAX / 16 / C)),
-              "fir_stream_forward: negative size or size overflows");
-    TFX_CHECK(C == 0 || T == 0 || x, "fir_stream_forward: null signal");
-    const int64_t H = K - 1;
-    check_stream_buffers("fir_stream_forward", dtype == TFX_F32 ? 4 : 8, x, C * T, y, C * T, hist_in, hist_out, C * H);
-    if (C > 0 && T > 0) {
-        if (direct) fir_direct_forward(x, y, dtype, C, T, kernel_host, K, (hipStream_t)stream, H ? hist_in : nullptr, hist_in ? H : 0);
-        else fft_conv_forward(x, y, dtype, C, T, kernel_host, K, H, 0, (hipStream_t)stream, H ? hist_in : nullptr, hist_in ? H : 0);
-    }
-    if (hist_out && C > 0) fir_hist_update(x, hist_in, hist_out, dtype, C, T, H, (hipStream_t)stream);
+    fir_stream_forward(x, y, dtype, C, T, kernel_host, K, direct, hist_in, hist_out, (hipStream_t)stream);
     TFX_API_END
 }
 
@@ -630,7 +542,6 @@ int tfx_delay_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T
 {
     TFX_API_BEGIN
     const Epilogue ep = to_epilogue(epilogue);
-    delay_check(x, y, dtype, rows, T, delay, taps, amps_host, mix, pingpong, &ep);     // before anything touches the device
     delay_forward(x, y, dtype, rows, T, delay, taps, amps_host, mix, pingpong, &ep, (hipStream_t)stream);
     TFX_API_END
 }
@@ -640,8 +551,6 @@ int tfx_delay_stream_forward(const void *x, void *y, int dtype, int64_t rows, in
                              tfx_stream_t stream)
 {
     TFX_API_BEGIN
-    // checked before anything touches the device
-    delay_stream_check(x, y, dtype, rows, T, delay, taps, amps_host, mix, pingpong, hist_in, hist_out);
     delay_stream_forward(x, y, dtype, rows, T, delay, taps, amps_host, mix, pingpong, hist_in, hist_out, (hipStream_t)stream);
     TFX_API_END
 }
@@ -650,7 +559,6 @@ int tfx_delay_line_stream_forward(const void *x, void *y, int dtype, int64_t C, 
                                   double mix, const void *hist_in, void *hist_out, tfx_stream_t stream)
 {
     TFX_API_BEGIN
-    delay_line_stream_check(x, y, dtype, C, T, delay, hist_in, hist_out);        // before anything touches the device
     delay_line_stream_forward(x, y, dtype, C, T, delay, mix * decay, hist_in, hist_out, (hipStream_t)stream);
     TFX_API_END
 }
@@ -669,7 +577,6 @@ int tfx_resample_forward(const void *x, void *y, int dtype, int64_t rows, int64_
                          const void *taps_host, int64_t nh, tfx_stream_t stream)
 {
     TFX_API_BEGIN
-    resample_check(x, y, dtype, rows, T, up, down, taps_host, nh);        // before anything touches the device
     resample_forward(x, y, dtype, rows, T, up, down, taps_host, nh, (hipStream_t)stream);
     TFX_API_END
 }
@@ -688,8 +595,6 @@ int tfx_resample_stream_forward(const void *x, void *y, int dtype, int64_t rows,
                                 tfx_stream_t stream)
 {
     TFX_API_BEGIN
-    // checked before anything touches the device
-    resample_stream_check(x, y, dtype, rows, T, up, down, taps_host, nh, consumed, hist_in, hist_out);
     resample_stream_forward(x, y, dtype, rows, T, up, down, taps_host, nh, consumed, hist_in, hist_out, (hipStream_t)stream);
     TFX_API_END
 }
@@ -708,7 +613,6 @@ int tfx_true_peak_forward(const void *x, int dtype, void *peak, int64_t rows, in
                           int64_t nh, void *work, tfx_stream_t stream)
 {
     TFX_API_BEGIN
-    true_peak_check(x, dtype, peak, rows, T, up, taps_host, nh, work);    // before anything touches the device
     true_peak_forward(x, dtype, peak, rows, T, up, taps_host, nh, work, (hipStream_t)stream);
     TFX_API_END
 }
@@ -727,7 +631,6 @@ int tfx_limiter_forward(const void *x, void *y, void *gain_or_null, int dtype, i
                         tfx_stream_t stream)
 {
     TFX_API_BEGIN
-    limiter_check(x, y, dtype, groups, channels, T, c, A, H, window_host, up, taps_host, nh);    // before anything touches the device
     limiter_forward(x, y, gain_or_null, dtype, groups, channels, T, c, A, H, window_host, up, taps_host, nh, (hipStream_t)stream);
     TFX_API_END
 }
@@ -747,9 +650,6 @@ int tfx_limiter_stream_forward(const void *x, void *y, void *gain_or_null, int d
                                const void *taps_host, int64_t nh, const void *hist_in, void *hist_out, tfx_stream_t stream)
 {
     TFX_API_BEGIN
-    // checked before anything touches the device
-    limiter_stream_check(x, y, gain_or_null, dtype, groups, channels, T, n_in, consumed, c, A, H, window_host, up, taps_host, nh,
-                         hist_in, hist_out);
     limiter_stream_forward(x, y, gain_or_null, dtype, groups, channels, T, n_in, consumed, c, A, H, window_host, up, taps_host, nh,
                            hist_in, hist_out, (hipStream_t)stream);
     TFX_API_END

@@ -22,6 +22,7 @@
 #include "common.h"
 #include "epilogue.h"
 #include "plan_cache.h"
+#include "timedomain.h"
 #include "../../include/torchfx_hip.h"
 
 #pragma clang fp contract(off)
@@ -277,8 +278,8 @@ int delay_regime(int64_t D, int64_t taps, int esz, int pingpong)
     return fits ? DLY_SPAN : DLY_GATHER;
 }
 
-void delay_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
-                 const double *amps_host, double mix, int pingpong, const Epilogue *ep)
+static void delay_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
+                        const double *amps_host, double mix, int pingpong, const Epilogue *ep)
 {
     TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "delay_forward: bad dtype %d", dtype);
     TFX_CHECK(taps >= 1, "delay_forward: taps must be at least 1, got %lld", (long long)taps);
@@ -445,8 +446,8 @@ __global__ void __launch_bounds__(DLY_THREADS) delay_stream_kernel(const DelaySt
     }
 }
 
-void delay_stream_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
-                        const double *amps_host, double mix, int pingpong, const void *hist_in, const void *hist_out)
+static void delay_stream_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
+                               const double *amps_host, double mix, int pingpong, const void *hist_in, const void *hist_out)
 {
     TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "delay_stream_forward: bad dtype %d", dtype);
     TFX_CHECK(taps >= 1, "delay_stream_forward: taps must be at least 1, got %lld", (long long)taps);

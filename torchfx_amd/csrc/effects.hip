@@ -11,6 +11,7 @@
 // .item()); the apply kernel reads them and handles the all-zero case itself.
 #include "common.h"
 #include "epilogue.h"
+#include "timedomain.h"
 #include "../../include/torchfx_hip.h"
 
 namespace tfx {
@@ -336,8 +337,8 @@ delay_line_stream_kernel(const T *__restrict__ x, const T *__restrict__ hist_in,
     }
 }
 
-void delay_line_stream_check(const void *x, const void *y, int dtype, int64_t C, int64_t T, int64_t delay, const void *hist_in,
-                             const void *hist_out)
+static void delay_line_stream_check(const void *x, const void *y, int dtype, int64_t C, int64_t T, int64_t delay,
+                                    const void *hist_in, const void *hist_out)
 {
     TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "delay_line_stream_forward: bad dtype %d", dtype);
     TFX_CHECK(delay >= 0, "delay_line_stream_forward: negative delay %lld", (long long)delay);
@@ -461,9 +462,6 @@ void epilogue_as_passes(void *y, int dtype, int64_t C, int64_t T, const Epilogue
         stat_launch(y, dtype, ep.per_row ? C : 1, ep.per_row ? T : C * T, ep.stat_mode, ep.stat_out, stream);
     }
 }
-
-void normalize_apply_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int mode, int per_row, double peak,
-                             const double *stat, hipStream_t stream);
 
 void normalize_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int mode, int per_row, double peak,
                        hipStream_t stream)

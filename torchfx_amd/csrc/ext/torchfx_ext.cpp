@@ -113,6 +113,19 @@ const double *state_ptr(const OptTensor &s, at::IntArrayRef shape, const Tensor 
     return keep.data_ptr<double>();
 }
 
+// a filter or window handed over as it is: a 1-D host tensor in x's dtype, non-empty (or of exactly `numel` values), made contiguous
+Tensor host_vector(const Tensor &t, const Tensor &x, const char *what, const char *name, int64_t numel = -1)
+{
+    if (numel < 0) {
+        TORCH_CHECK(!t.is_cuda() && t.dim() == 1 && t.numel() >= 1, what, ": ", name, " must be a non-empty 1-D host tensor");
+    } else {
+        TORCH_CHECK(!t.is_cuda() && t.dim() == 1 && t.numel() == numel, what, ": ", name, " must be a 1-D host tensor of ", numel, " values");
+    }
+    TORCH_CHECK(t.scalar_type() == x.scalar_type(), what, ": ", name, " must have x's dtype (", x.scalar_type(), "), got ",
+                t.scalar_type());
+    return t.contiguous();
+}
+
 int precision_or_default(int64_t precision)
 {
     if (precision >= 0) return (int)precision;
@@ -133,30 +146,56 @@ at::ScalarType out_type(const Tensor &x, const std::optional<at::ScalarType> &ou
 // ---------------------------------------------------------------------------------------------------
 // SOS cascade (binding.cpp:52-66) and its filter-bank / sum forms
 // ---------------------------------------------------------------------------------------------------
+// the epilogue arguments of the *_ep ops; absent = the plain op and its C entry
+struct EpilogueArgs {
+    double gain;
+    bool clamp;
+    int64_t stat_mode;
+    bool per_row;
+};
+
+// cascade + epilogue (Gain / clamp / statistic for Normalize applied by the producing kernel, include/torchfx_hip.h)
+tfx_epilogue make_epilogue(const EpilogueArgs &a, Tensor &stat, const Tensor &like, int64_t rows)
+{
+    TORCH_CHECK(a.stat_mode >= -1 && a.stat_mode <= 1, "epilogue: stat_mode must be -1 (none), 0 (max|y|) or 1 (sum y^2)");
+    stat = at::empty({a.stat_mode >= 0 ? (a.per_row ? rows : 1) : 0}, like.options().dtype(at::kDouble));
+    tfx_epilogue ep;
+    ep.gain = a.gain; ep.clamp = a.clamp ? 1 : 0; ep.stat_mode = (int)a.stat_mode; ep.stat_per_row = a.per_row ? 1 : 0;
+    ep.stat_out = a.stat_mode >= 0 ? stat.data_ptr<double>() : nullptr;
+    return ep;
+}
+
+// sos_forward / sos_forward_sections (tfx_sos_forward) and, with `epa`, sos_forward_ep (tfx_sos_forward_ep): the fourth tensor is
+// every section's output (empty without `sections`) or the epilogue's statistic
 std::tuple<Tensor, Tensor, Tensor, Tensor> sos_impl(const Tensor &x_in, const Tensor &sos_cpu, const OptTensor &state_x,
                                                     const OptTensor &state_y, std::optional<at::ScalarType> out_dtype,
-                                                    int64_t precision, bool sections)
+                                                    int64_t precision, bool sections, const EpilogueArgs *epa = nullptr)
 {
-    TORCH_CHECK(x_in.dim() == 2, "sos_forward: x must be [C, T], got ", x_in.sizes());
+    const char *what = epa ? "sos_forward_ep" : "sos_forward";
+    TORCH_CHECK(x_in.dim() == 2, what, ": x must be [C, T], got ", x_in.sizes());
     need_device(x_in, "x");
     const Tensor x = x_in.contiguous();
-    const Tensor sos = host_f64(sos_cpu, 6, "sos_forward");
-    TORCH_CHECK(sos.dim() == 2, "sos_forward: sos must be [K, 6]");
+    const Tensor sos = host_f64(sos_cpu, 6, what);
+    TORCH_CHECK(sos.dim() == 2, what, ": sos must be [K, 6]");
     const int64_t C = x.size(0), T = x.size(1), K = sos.size(0);
-    Tensor kx, ky;
+    Tensor kx, ky, fourth;
     const double *sx = state_ptr(state_x, {K, C, 2}, x, "state_x", kx);
     const double *sy = state_ptr(state_y, {K, C, 2}, x, "state_y", ky);
     const auto odt = out_type(x, out_dtype);
     Tensor y = at::empty({C, T}, x.options().dtype(odt));
     Tensor nsx = at::empty({K, C, 2}, x.options().dtype(at::kDouble));
     Tensor nsy = at::empty({K, C, 2}, x.options().dtype(at::kDouble));
-    Tensor sec = sections ? at::empty({K, C, T}, x.options().dtype(odt)) : at::empty({0}, x.options().dtype(odt));
+    tfx_epilogue ep{};
+    if (epa) ep = make_epilogue(*epa, fourth, x, C);
+    else fourth = sections ? at::empty({K, C, T}, x.options().dtype(odt)) : at::empty({0}, x.options().dtype(odt));
+    const int xdt = dtype_code(x, what), ydt = dtype_code(y, what), prec = precision_or_default(precision);
     c10::hip::HIPGuard guard(x.get_device());
-    check_rc(tfx_sos_forward(x.data_ptr(), dtype_code(x, "sos_forward"), y.data_ptr(), dtype_code(y, "sos_forward"), C, T,
-                             sos.data_ptr<double>(), K, sx, sy, nsx.data_ptr<double>(), nsy.data_ptr<double>(),
-                             sections ? sec.data_ptr() : nullptr, precision_or_default(precision), stream_of(x)),
-             "sos_forward");
-    return {y, nsx, nsy, sec};
+    check_rc(epa ? tfx_sos_forward_ep(x.data_ptr(), xdt, y.data_ptr(), ydt, C, T, sos.data_ptr<double>(), K, sx, sy, nsx.data_ptr<double>(),
+                                      nsy.data_ptr<double>(), prec, &ep, stream_of(x))
+                 : tfx_sos_forward(x.data_ptr(), xdt, y.data_ptr(), ydt, C, T, sos.data_ptr<double>(), K, sx, sy, nsx.data_ptr<double>(),
+                                   nsy.data_ptr<double>(), sections ? fourth.data_ptr() : nullptr, prec, stream_of(x)),
+             what);
+    return {y, nsx, nsy, fourth};
 }
 
 std::tuple<Tensor, Tensor, Tensor> sos_op(const Tensor &x, const Tensor &sos_cpu, const OptTensor &sx, const OptTensor &sy,
@@ -171,6 +210,14 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> sos_sections_op(const Tensor &x, cons
                                                            int64_t precision)
 {
     return sos_impl(x, sos_cpu, sx, sy, out_dtype, precision, true);
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> sos_ep_op(const Tensor &x, const Tensor &sos_cpu, const OptTensor &sx, const OptTensor &sy,
+                                                     double gain, bool clamp, int64_t stat_mode, bool per_row,
+                                                     std::optional<at::ScalarType> out_dtype, int64_t precision)
+{
+    const EpilogueArgs epa{gain, clamp, stat_mode, per_row};
+    return sos_impl(x, sos_cpu, sx, sy, out_dtype, precision, false, &epa);
 }
 
 std::tuple<Tensor, Tensor, Tensor> bank_impl(const Tensor &x_in, const Tensor &banks_cpu, const OptTensor &state_x,
@@ -208,42 +255,6 @@ std::tuple<Tensor, Tensor, Tensor> bank_sum_op(const Tensor &x, const Tensor &ba
                                                int64_t precision)
 {
     return bank_impl(x, banks, sx, sy, std::nullopt, precision, true);
-}
-
-// cascade + epilogue (Gain / clamp / statistic for Normalize applied by the producing kernel, include/torchfx_hip.h)
-tfx_epilogue make_epilogue(double gain, bool clamp, int64_t stat_mode, bool per_row, Tensor &stat, const Tensor &like, int64_t rows)
-{
-    TORCH_CHECK(stat_mode >= -1 && stat_mode <= 1, "epilogue: stat_mode must be -1 (none), 0 (max|y|) or 1 (sum y^2)");
-    stat = at::empty({stat_mode >= 0 ? (per_row ? rows : 1) : 0}, like.options().dtype(at::kDouble));
-    tfx_epilogue ep;
-    ep.gain = gain; ep.clamp = clamp ? 1 : 0; ep.stat_mode = (int)stat_mode; ep.stat_per_row = per_row ? 1 : 0;
-    ep.stat_out = stat_mode >= 0 ? stat.data_ptr<double>() : nullptr;
-    return ep;
-}
-
-std::tuple<Tensor, Tensor, Tensor, Tensor> sos_ep_op(const Tensor &x_in, const Tensor &sos_cpu, const OptTensor &state_x,
-                                                     const OptTensor &state_y, double gain, bool clamp, int64_t stat_mode,
-                                                     bool per_row, std::optional<at::ScalarType> out_dtype, int64_t precision)
-{
-    TORCH_CHECK(x_in.dim() == 2, "sos_forward_ep: x must be [C, T], got ", x_in.sizes());
-    need_device(x_in, "x");
-    const Tensor x = x_in.contiguous();
-    const Tensor sos = host_f64(sos_cpu, 6, "sos_forward_ep");
-    TORCH_CHECK(sos.dim() == 2, "sos_forward_ep: sos must be [K, 6]");
-    const int64_t C = x.size(0), T = x.size(1), K = sos.size(0);
-    Tensor kx, ky, stat;
-    const double *sx = state_ptr(state_x, {K, C, 2}, x, "state_x", kx);
-    const double *sy = state_ptr(state_y, {K, C, 2}, x, "state_y", ky);
-    Tensor y = at::empty({C, T}, x.options().dtype(out_type(x, out_dtype)));
-    Tensor nsx = at::empty({K, C, 2}, x.options().dtype(at::kDouble));
-    Tensor nsy = at::empty({K, C, 2}, x.options().dtype(at::kDouble));
-    const tfx_epilogue ep = make_epilogue(gain, clamp, stat_mode, per_row, stat, x, C);
-    c10::hip::HIPGuard guard(x.get_device());
-    check_rc(tfx_sos_forward_ep(x.data_ptr(), dtype_code(x, "sos_forward_ep"), y.data_ptr(), dtype_code(y, "sos_forward_ep"), C, T,
-                                sos.data_ptr<double>(), K, sx, sy, nsx.data_ptr<double>(), nsy.data_ptr<double>(),
-                                precision_or_default(precision), &ep, stream_of(x)),
-             "sos_forward_ep");
-    return {y, nsx, nsy, stat};
 }
 
 // single biquad (binding.cpp:30-50): b [3] tensor, a1 / a2 scalars, states [C, 2]
@@ -315,7 +326,7 @@ std::vector<int64_t> delay_shape(const Tensor &x, int64_t delay_samples, int64_t
 }
 
 std::tuple<Tensor, Tensor> delay_impl(const Tensor &x_in, int64_t delay_samples, at::ArrayRef<double> amps, double mix, bool pingpong,
-                                      double gain, bool clamp, int64_t stat_mode, bool per_row)
+                                      const EpilogueArgs &epa)
 {
     need_device(x_in, "x");
     const int64_t taps = (int64_t)amps.size();
@@ -324,7 +335,7 @@ std::tuple<Tensor, Tensor> delay_impl(const Tensor &x_in, int64_t delay_samples,
     const int64_t T = x.size(-1), rows = stream_rows(x);
     const bool pp = pingpong && x.dim() >= 2 && x.size(-2) == 2;
     Tensor y = at::empty(shape, x.options()), stat;
-    const tfx_epilogue ep = make_epilogue(gain, clamp, stat_mode, per_row, stat, x, rows);
+    const tfx_epilogue ep = make_epilogue(epa, stat, x, rows);
     c10::hip::HIPGuard guard(x.get_device());
     check_rc(tfx_delay_forward(x.data_ptr(), y.data_ptr(), dtype_code(x, "delay_forward"), rows, T, delay_samples, taps, amps.data(), mix,
                                pp ? 1 : 0, &ep, stream_of(x)),
@@ -335,12 +346,12 @@ std::tuple<Tensor, Tensor> delay_impl(const Tensor &x_in, int64_t delay_samples,
 std::tuple<Tensor, Tensor> delay_ep_op(const Tensor &x, int64_t delay_samples, at::ArrayRef<double> amps, double mix, bool pingpong,
                                        double gain, bool clamp, int64_t stat_mode, bool per_row)
 {
-    return delay_impl(x, delay_samples, amps, mix, pingpong, gain, clamp, stat_mode, per_row);
+    return delay_impl(x, delay_samples, amps, mix, pingpong, {gain, clamp, stat_mode, per_row});
 }
 
 Tensor delay_op(const Tensor &x, int64_t delay_samples, at::ArrayRef<double> amps, double mix, bool pingpong)
 {
-    return std::get<0>(delay_impl(x, delay_samples, amps, mix, pingpong, 1.0, false, -1, false));
+    return std::get<0>(delay_impl(x, delay_samples, amps, mix, pingpong, {1.0, false, -1, false}));      // the neutral epilogue
 }
 
 // one chunk of a streaming Delay / delay line (StatefulDelay, StatefulReverb): x [..., T] -> (y [..., T], new history [rows, H]).
@@ -397,10 +408,7 @@ Tensor resample_op(const Tensor &x_in, int64_t up, int64_t down, const Tensor &h
 {
     need_device(x_in, "x");
     const std::vector<int64_t> shape = resample_shape(x_in, up, down);
-    TORCH_CHECK(!h.is_cuda() && h.dim() == 1 && h.numel() >= 1, "resample_forward: h must be a non-empty 1-D host tensor");
-    TORCH_CHECK(h.scalar_type() == x_in.scalar_type(), "resample_forward: h must have x's dtype (", x_in.scalar_type(), "), got ",
-                h.scalar_type());
-    const Tensor x = x_in.contiguous(), hc = h.contiguous();
+    const Tensor hc = host_vector(h, x_in, "resample_forward", "h"), x = x_in.contiguous();
     const int64_t T = x.size(-1), rows = stream_rows(x);
     Tensor y = at::empty(shape, x.options());
     c10::hip::HIPGuard guard(x.get_device());
@@ -483,10 +491,7 @@ Tensor true_peak_op(const Tensor &x_in, const Tensor &taps, int64_t up)
 {
     need_device(x_in, "x");
     const std::vector<int64_t> shape = true_peak_shape(x_in);
-    TORCH_CHECK(!taps.is_cuda() && taps.dim() == 1 && taps.numel() >= 1, "true_peak: taps must be a non-empty 1-D host tensor");
-    TORCH_CHECK(taps.scalar_type() == x_in.scalar_type(), "true_peak: taps must have x's dtype (", x_in.scalar_type(), "), got ",
-                taps.scalar_type());
-    const Tensor x = x_in.contiguous(), hc = taps.contiguous();
+    const Tensor hc = host_vector(taps, x_in, "true_peak", "taps"), x = x_in.contiguous();
     const int64_t T = x.size(-1), rows = stream_rows(x);
     const int dt = dtype_code(x, "true_peak");
     int64_t Lp = 0, tile_in = 0, tiles = 0, work_elems = 0;
@@ -503,37 +508,50 @@ Tensor true_peak_op(const Tensor &x_in, const Tensor &taps, int64_t up)
 // Look-ahead limiter (tfx_limiter_forward): x [..., T], its rows in groups of `channels` consecutive rows that share one gain
 // curve -> (y like x, gain [groups, T] or an empty tensor).  c the linear ceiling already rounded to x's dtype, A / H in samples,
 // window HOST [A] and taps HOST [nh] (None for up == 1) in x's dtype.
+// what both limiter ops do between the device check and the plan query: the checks, the contiguous tensors and the sizes the C entries take
+struct LimiterInputs {
+    Tensor x, window, taps;              // contiguous; taps undefined without an interpolator
+    int64_t T, rows, groups, nh;         // nh = 0 for up == 1
+    int dt;
+    const void *taps_ptr() const { return nh ? taps.data_ptr() : nullptr; }
+};
+
+LimiterInputs limiter_inputs(const char *what, const Tensor &x_in, int64_t A, const Tensor &window, int64_t up, const OptTensor &taps,
+                             int64_t channels)
+{
+    TORCH_CHECK(x_in.dim() >= 1, what, ": x must have a time dimension");
+    LimiterInputs in;
+    in.window = host_vector(window, x_in, what, "window", A);
+    const bool has_taps = taps.has_value() && taps->defined();
+    TORCH_CHECK(up == 1 || has_taps, what, ": up > 1 needs taps");
+    if (has_taps) in.taps = host_vector(*taps, x_in, what, "taps");
+    in.x = x_in.contiguous();
+    in.T = in.x.size(-1);
+    in.rows = stream_rows(in.x);
+    TORCH_CHECK(channels >= 1 && in.rows % channels == 0, what, ": ", in.rows, " rows do not split into groups of ", channels);
+    in.groups = in.rows / channels;
+    in.nh = has_taps && up > 1 ? in.taps.numel() : 0;
+    in.dt = dtype_code(in.x, what);
+    return in;
+}
+
 std::tuple<Tensor, Tensor> limiter_op(const Tensor &x_in, double c, int64_t A, int64_t H, const Tensor &window, int64_t up,
                                       const OptTensor &taps, int64_t channels, bool return_gain)
 {
+    const char *what = "limiter_forward";
     need_device(x_in, "x");
-    TORCH_CHECK(x_in.dim() >= 1, "limiter_forward: x must have a time dimension");
-    TORCH_CHECK(!window.is_cuda() && window.dim() == 1 && window.numel() == A, "limiter_forward: window must be a 1-D host tensor of ",
-                A, " values");
-    TORCH_CHECK(window.scalar_type() == x_in.scalar_type(), "limiter_forward: window must have x's dtype (", x_in.scalar_type(),
-                "), got ", window.scalar_type());
-    const bool has_taps = taps.has_value() && taps->defined();
-    TORCH_CHECK(up == 1 || has_taps, "limiter_forward: up > 1 needs taps");
-    if (has_taps) {
-        TORCH_CHECK(!taps->is_cuda() && taps->dim() == 1 && taps->numel() >= 1, "limiter_forward: taps must be a non-empty 1-D host tensor");
-        TORCH_CHECK(taps->scalar_type() == x_in.scalar_type(), "limiter_forward: taps must have x's dtype (", x_in.scalar_type(),
-                    "), got ", taps->scalar_type());
-    }
-    const Tensor x = x_in.contiguous(), wc = window.contiguous();
-    const Tensor hc = has_taps ? taps->contiguous() : Tensor();
-    const int64_t T = x.size(-1), rows = stream_rows(x);
-    TORCH_CHECK(channels >= 1 && rows % channels == 0, "limiter_forward: ", rows, " rows do not split into groups of ", channels);
-    const int64_t groups = rows / channels, nh = has_taps && up > 1 ? hc.numel() : 0;
-    const int dt = dtype_code(x, "limiter_forward");
+    const LimiterInputs in = limiter_inputs(what, x_in, A, window, up, taps, channels);
+    const Tensor &x = in.x;
     int64_t info[6];
-    check_rc(tfx_limiter_plan_info(groups, channels, T, A, H, up, nh, dt, info, info + 1, info + 2, info + 3, info + 4, info + 5),
-             "limiter_forward");
+    check_rc(tfx_limiter_plan_info(in.groups, channels, in.T, A, H, up, in.nh, in.dt, info, info + 1, info + 2, info + 3, info + 4,
+                                   info + 5),
+             what);
     Tensor y = at::empty_like(x);
-    Tensor gain = return_gain ? at::empty({groups, T}, x.options()) : at::empty({0}, x.options());
+    Tensor gain = return_gain ? at::empty({in.groups, in.T}, x.options()) : at::empty({0}, x.options());
     c10::hip::HIPGuard guard(x.get_device());
-    check_rc(tfx_limiter_forward(x.data_ptr(), y.data_ptr(), return_gain ? gain.data_ptr() : nullptr, dt, groups, channels, T, c, A, H,
-                                 wc.data_ptr(), up, nh ? hc.data_ptr() : nullptr, nh, stream_of(x)),
-             "limiter_forward");
+    check_rc(tfx_limiter_forward(x.data_ptr(), y.data_ptr(), return_gain ? gain.data_ptr() : nullptr, in.dt, in.groups, channels, in.T, c,
+                                 A, H, in.window.data_ptr(), up, in.taps_ptr(), in.nh, stream_of(x)),
+             what);
     return std::make_tuple(y, gain);
 }
 
@@ -546,33 +564,19 @@ std::tuple<Tensor, Tensor, Tensor> limiter_stream_op(const Tensor &x_in, const O
 {
     const char *what = "limiter_stream_forward";
     need_device(x_in, "x");
-    TORCH_CHECK(x_in.dim() >= 1, what, ": x must have a time dimension");
-    TORCH_CHECK(!window.is_cuda() && window.dim() == 1 && window.numel() == A, what, ": window must be a 1-D host tensor of ", A, " values");
-    TORCH_CHECK(window.scalar_type() == x_in.scalar_type(), what, ": window must have x's dtype (", x_in.scalar_type(), "), got ",
-                window.scalar_type());
-    const bool has_taps = taps.has_value() && taps->defined();
-    TORCH_CHECK(up == 1 || has_taps, what, ": up > 1 needs taps");
-    if (has_taps) {
-        TORCH_CHECK(!taps->is_cuda() && taps->dim() == 1 && taps->numel() >= 1, what, ": taps must be a non-empty 1-D host tensor");
-        TORCH_CHECK(taps->scalar_type() == x_in.scalar_type(), what, ": taps must have x's dtype (", x_in.scalar_type(), "), got ",
-                    taps->scalar_type());
-    }
-    const Tensor x = x_in.contiguous(), wc = window.contiguous();
-    const Tensor hc = has_taps ? taps->contiguous() : Tensor();
-    const int64_t T = x.size(-1), rows = stream_rows(x);
-    TORCH_CHECK(channels >= 1 && rows % channels == 0, what, ": ", rows, " rows do not split into groups of ", channels);
-    const int64_t groups = rows / channels, nh = has_taps && up > 1 ? hc.numel() : 0;
-    const int dt = dtype_code(x, what);
+    const LimiterInputs in = limiter_inputs(what, x_in, A, window, up, taps, channels);
+    const Tensor &x = in.x;
     int64_t info[6];
-    check_rc(tfx_limiter_stream_plan_info(groups, channels, T, A, H, up, nh, dt, info, info + 1, info + 2, info + 3, info + 4, info + 5),
+    check_rc(tfx_limiter_stream_plan_info(in.groups, channels, in.T, A, H, up, in.nh, in.dt, info, info + 1, info + 2, info + 3, info + 4,
+                                          info + 5),
              what);
     const int64_t Hs = info[1];
-    const Tensor hin = stream_hist_in(hist, x, rows, Hs, what);
-    Tensor y = at::empty_like(x), hout = at::empty({rows, Hs}, x.options());
-    Tensor gain = return_gain ? at::empty({groups, T}, x.options()) : at::empty({0}, x.options());
+    const Tensor hin = stream_hist_in(hist, x, in.rows, Hs, what);
+    Tensor y = at::empty_like(x), hout = at::empty({in.rows, Hs}, x.options());
+    Tensor gain = return_gain ? at::empty({in.groups, in.T}, x.options()) : at::empty({0}, x.options());
     c10::hip::HIPGuard guard(x.get_device());
-    check_rc(tfx_limiter_stream_forward(x.data_ptr(), y.data_ptr(), return_gain ? gain.data_ptr() : nullptr, dt, groups, channels, T,
-                                        n_in < 0 ? T : n_in, consumed, c, A, H, wc.data_ptr(), up, nh ? hc.data_ptr() : nullptr, nh,
+    check_rc(tfx_limiter_stream_forward(x.data_ptr(), y.data_ptr(), return_gain ? gain.data_ptr() : nullptr, in.dt, in.groups, channels,
+                                        in.T, n_in < 0 ? in.T : n_in, consumed, c, A, H, in.window.data_ptr(), up, in.taps_ptr(), in.nh,
                                         hin.defined() ? hin.data_ptr() : nullptr, hout.data_ptr(), stream_of(x)),
              what);
     return std::make_tuple(y, gain, hout);
@@ -601,11 +605,9 @@ std::tuple<Tensor, Tensor> resample_stream_op(const Tensor &x_in, const Tensor &
                                               int64_t consumed)
 {
     need_device(x_in, "x");
-    TORCH_CHECK(!h.is_cuda() && h.dim() == 1 && h.numel() >= 1, "resample_stream_forward: h must be a non-empty 1-D host tensor");
-    TORCH_CHECK(h.scalar_type() == x_in.scalar_type(), "resample_stream_forward: h must have x's dtype (", x_in.scalar_type(),
-                "), got ", h.scalar_type());
-    const ResampleStreamPlan pl = resample_stream_plan(x_in, h, up, down, consumed);
-    const Tensor x = x_in.contiguous(), hc = h.contiguous();
+    const Tensor hc = host_vector(h, x_in, "resample_stream_forward", "h");
+    const ResampleStreamPlan pl = resample_stream_plan(x_in, hc, up, down, consumed);
+    const Tensor x = x_in.contiguous();
     const int64_t T = x.size(-1), rows = stream_rows(x);
     const Tensor hin = stream_hist_in(hist, x, rows, pl.H, "resample_stream_forward");
     std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
@@ -641,38 +643,39 @@ Tensor fir_direct_op(const Tensor &x_in, const Tensor &kernel)
     return y;
 }
 
-Tensor fft_conv_op(const Tensor &x_in, const Tensor &kernel, int64_t pad_left, int64_t pad_right)
+// fft_conv_forward (tfx_fft_conv_forward) and, with `epa`, fft_conv_forward_ep (tfx_fft_conv_forward_ep): y and the epilogue's
+// statistic (undefined without one)
+std::tuple<Tensor, Tensor> fft_conv_impl(const Tensor &x_in, const Tensor &kernel, int64_t pad_left, int64_t pad_right,
+                                         const EpilogueArgs *epa)
 {
-    TORCH_CHECK(x_in.dim() == 2, "fft_conv_forward: x must be [C, T], got ", x_in.sizes());
-    need_device(x_in, "x");
-    const Tensor x = x_in.contiguous();
-    const Tensor k = taps_host(kernel, x);
-    const int64_t C = x.size(0), T = x.size(1), K = k.numel();
-    const int64_t tout = T + pad_left + pad_right - K + 1;
-    Tensor y = at::empty({C, tout > 0 ? tout : 0}, x.options());
-    c10::hip::HIPGuard guard(x.get_device());
-    check_rc(tfx_fft_conv_forward(x.data_ptr(), y.data_ptr(), dtype_code(x, "fft_conv_forward"), C, T, k.data_ptr(), K, pad_left,
-                                  pad_right, stream_of(x)),
-             "fft_conv_forward");
-    return y;
-}
-
-std::tuple<Tensor, Tensor> fft_conv_ep_op(const Tensor &x_in, const Tensor &kernel, int64_t pad_left, int64_t pad_right, double gain,
-                                          bool clamp, int64_t stat_mode, bool per_row)
-{
-    TORCH_CHECK(x_in.dim() == 2, "fft_conv_forward_ep: x must be [C, T], got ", x_in.sizes());
+    const char *what = epa ? "fft_conv_forward_ep" : "fft_conv_forward";
+    TORCH_CHECK(x_in.dim() == 2, what, ": x must be [C, T], got ", x_in.sizes());
     need_device(x_in, "x");
     const Tensor x = x_in.contiguous();
     const Tensor k = taps_host(kernel, x);
     const int64_t C = x.size(0), T = x.size(1), K = k.numel();
     const int64_t tout = T + pad_left + pad_right - K + 1;
     Tensor y = at::empty({C, tout > 0 ? tout : 0}, x.options()), stat;
-    const tfx_epilogue ep = make_epilogue(gain, clamp, stat_mode, per_row, stat, x, C);
+    tfx_epilogue ep{};
+    if (epa) ep = make_epilogue(*epa, stat, x, C);
+    const int dt = dtype_code(x, what);
     c10::hip::HIPGuard guard(x.get_device());
-    check_rc(tfx_fft_conv_forward_ep(x.data_ptr(), y.data_ptr(), dtype_code(x, "fft_conv_forward_ep"), C, T, k.data_ptr(), K, pad_left,
-                                     pad_right, &ep, stream_of(x)),
-             "fft_conv_forward_ep");
+    check_rc(epa ? tfx_fft_conv_forward_ep(x.data_ptr(), y.data_ptr(), dt, C, T, k.data_ptr(), K, pad_left, pad_right, &ep, stream_of(x))
+                 : tfx_fft_conv_forward(x.data_ptr(), y.data_ptr(), dt, C, T, k.data_ptr(), K, pad_left, pad_right, stream_of(x)),
+             what);
     return {y, stat};
+}
+
+Tensor fft_conv_op(const Tensor &x, const Tensor &kernel, int64_t pad_left, int64_t pad_right)
+{
+    return std::get<0>(fft_conv_impl(x, kernel, pad_left, pad_right, nullptr));
+}
+
+std::tuple<Tensor, Tensor> fft_conv_ep_op(const Tensor &x, const Tensor &kernel, int64_t pad_left, int64_t pad_right, double gain,
+                                          bool clamp, int64_t stat_mode, bool per_row)
+{
+    const EpilogueArgs epa{gain, clamp, stat_mode, per_row};
+    return fft_conv_impl(x, kernel, pad_left, pad_right, &epa);
 }
 
 // zero-state SOS cascade | FFT-mode FIR as one overlap-save pipeline (tfx_sos_fft_conv_forward): y, the statistic of the
@@ -692,7 +695,7 @@ std::tuple<Tensor, Tensor, Tensor> sos_fft_conv_op(const Tensor &x_in, const Ten
     const int64_t tout = T + pad_left + pad_right - taps + 1;
     Tensor y = at::empty({C, tout > 0 ? tout : 0}, x.options()), stat;
     Tensor sec = sections ? at::empty({K, C, T}, x.options().dtype(at::kDouble)) : at::empty({0}, x.options().dtype(at::kDouble));
-    const tfx_epilogue ep = make_epilogue(gain, clamp, stat_mode, per_row, stat, x, C);
+    const tfx_epilogue ep = make_epilogue({gain, clamp, stat_mode, per_row}, stat, x, C);
     c10::hip::HIPGuard guard(x.get_device());
     check_rc(tfx_sos_fft_conv_forward(x.data_ptr<float>(), y.data_ptr<float>(), C, T, sos.data_ptr<double>(), K, k.data_ptr<float>(), taps,
                                       pad_left, pad_right, sections ? sec.data_ptr<double>() : nullptr, (int)force_block, &ep,
@@ -962,94 +965,78 @@ Tensor fft_conv_meta(const Tensor &x, const Tensor &kernel, int64_t pad_left, in
     return at::empty({x.size(0), tout > 0 ? tout : 0}, x.options());
 }
 
-// CPU tensors: an explicit error instead of the dispatcher's "no kernel for backend CPU"
+// No CPU branch, by design: every op of the namespace answers a host tensor with the same error instead of the dispatcher's
+// "no kernel for backend CPU" (one boxed function registered for the CPU key of each op; per-namespace fallbacks are not
+// supported by the dispatcher).
+void no_cpu_boxed(const c10::OperatorHandle &op, c10::DispatchKeySet, torch::jit::Stack *)
+{
+    TORCH_CHECK(false, "torchfx_amd: ", op.schema().name(),
+                ": tensors must live on a ROCm device; this backend has no CPU path -- move them with .to('cuda').");
+}
+
+// One line per op: its schema, `fn` for the CUDA key ("CUDA" is the dispatch key of ROCm device tensors) and the refusal above
+// for the CPU key.  The op's name is the schema up to its "(".
+template <typename F> void reg_op(torch::Library &m, const char *schema, F *fn)
+{
+    const std::string s(schema), name = s.substr(0, s.find('('));
+    m.def(schema);
+    m.impl(name.c_str(), torch::dispatch(c10::DispatchKey::CUDA, fn));
+    m.impl(name.c_str(), torch::dispatch(c10::DispatchKey::CPU, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>()));
+}
 
 }  // namespace
 
 TORCH_LIBRARY(torchfx_hip, m)
 {
-    m.def("sos_forward(Tensor x, Tensor sos_cpu, Tensor? state_x=None, Tensor? state_y=None, *, ScalarType? out_dtype=None, "
-          "int precision=-1) -> (Tensor, Tensor, Tensor)");
-    m.def("sos_forward_sections(Tensor x, Tensor sos_cpu, Tensor? state_x=None, Tensor? state_y=None, *, ScalarType? out_dtype=None, "
-          "int precision=-1) -> (Tensor, Tensor, Tensor, Tensor)");
-    m.def("sos_bank_forward(Tensor x, Tensor sos_banks_cpu, Tensor? state_x=None, Tensor? state_y=None, *, ScalarType? out_dtype=None, "
-          "int precision=-1) -> (Tensor, Tensor, Tensor)");
-    m.def("sos_bank_sum_forward(Tensor x, Tensor sos_banks_cpu, Tensor? state_x=None, Tensor? state_y=None, *, int precision=-1) "
-          "-> (Tensor, Tensor, Tensor)");
-    m.def("biquad_forward(Tensor x, Tensor b, float a1, float a2, Tensor? state_x=None, Tensor? state_y=None, *, "
-          "ScalarType? out_dtype=None, int precision=-1) -> (Tensor, Tensor, Tensor)");
-    m.def("delay_line_forward(Tensor(a) x, int delay_samples, float decay, float mix) -> Tensor(a)");
-    m.def("delay_forward(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong) -> Tensor");
-    m.def("resample_forward(Tensor x, int up, int down, Tensor h) -> Tensor");
-    m.def("sos_filtfilt(Tensor x, Tensor sos_cpu, int padtype=0, int padlen=-1) -> Tensor");
-    m.def("sos_block_energy(Tensor x, Tensor sos_cpu, int num, int den=1) -> Tensor");
-    m.def("true_peak(Tensor x, Tensor taps_cpu, int up) -> Tensor");
-    m.def("limiter_forward(Tensor x, float c, int A, int H, Tensor window_cpu, int up, Tensor? taps_cpu, int channels, "
-          "bool return_gain) -> (Tensor, Tensor)");
-    m.def("limiter_stream_forward(Tensor x, Tensor? hist, int consumed, float c, int A, int H, Tensor window_cpu, int up, "
-          "Tensor? taps_cpu, int channels, bool return_gain, int n_in=-1) -> (Tensor, Tensor, Tensor)");
-    m.def("resample_stream_forward(Tensor x, Tensor h, Tensor? hist, int up, int down, int consumed) -> (Tensor, Tensor)");
-    m.def("delay_forward_ep(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong, float gain, bool clamp, int stat_mode, "
-          "bool per_row) -> (Tensor, Tensor)");
-    m.def("delay_stream_forward(Tensor x, Tensor? hist, int delay_samples, float[] amps, float mix, bool pingpong) -> (Tensor, Tensor)");
-    m.def("delay_line_stream_forward(Tensor x, Tensor? hist, int delay_samples, float decay, float mix) -> (Tensor, Tensor)");
-    m.def("fir_direct_forward(Tensor x, Tensor kernel) -> Tensor");
-    m.def("fft_conv_forward(Tensor x, Tensor kernel, int pad_left, int pad_right) -> Tensor");
-    m.def("fir_stream_forward(Tensor x, Tensor kernel, Tensor? hist, bool direct) -> (Tensor, Tensor)");
-    m.def("chunk_forward(Tensor x, Tensor sos_cpu, Tensor? state_x, Tensor? state_y, Tensor kernel, Tensor? hist, float gain, "
-          "bool scale, bool clamp, int precision=-1) -> (Tensor, Tensor, Tensor, Tensor)");
-    m.def("sos_forward_ep(Tensor x, Tensor sos_cpu, Tensor? state_x, Tensor? state_y, float gain, bool clamp, int stat_mode, "
-          "bool per_row, *, ScalarType? out_dtype=None, int precision=-1) -> (Tensor, Tensor, Tensor, Tensor)");
-    m.def("fft_conv_forward_ep(Tensor x, Tensor kernel, int pad_left, int pad_right, float gain, bool clamp, int stat_mode, "
-          "bool per_row) -> (Tensor, Tensor)");
-    m.def("sos_fft_conv_forward(Tensor x, Tensor sos_cpu, Tensor kernel, int pad_left, int pad_right, bool sections=False, "
-          "int force_block=0, float gain=1.0, bool clamp=False, int stat_mode=-1, bool per_row=False) -> (Tensor, Tensor, Tensor)");
-    m.def("normalize_apply(Tensor x, Tensor stat, float peak, int mode, bool per_row) -> Tensor");
-    m.def("sum_forward(Tensor[] tensors) -> Tensor");
-    m.def("gain_forward(Tensor x, float gain, bool clamp) -> Tensor");
-    m.def("quantile_abs(Tensor x, float q) -> Tensor");
-    m.def("stat_forward(Tensor x, int mode, bool per_row) -> Tensor");
-    m.def("normalize_forward(Tensor x, float peak, int mode, bool per_row) -> Tensor");
-    m.def("deinterleave_forward(Tensor frames, float scale=3.0517578125e-05) -> Tensor");
-    m.def("deinterleave_into(Tensor frames, Tensor(a!) out, int frame_base=0, float scale=3.0517578125e-05) -> ()");
-    m.def("interleave_forward(Tensor x, int frame_base=0, int frames=-1) -> Tensor");
-}
-
-TORCH_LIBRARY_IMPL(torchfx_hip, CUDA, m)          // "CUDA" is the dispatch key of ROCm device tensors
-{
-    m.impl("sos_forward", sos_op);
-    m.impl("sos_forward_sections", sos_sections_op);
-    m.impl("sos_bank_forward", bank_op);
-    m.impl("sos_bank_sum_forward", bank_sum_op);
-    m.impl("biquad_forward", biquad_op);
-    m.impl("delay_line_forward", delay_line_op);
-    m.impl("delay_forward", delay_op);
-    m.impl("resample_forward", resample_op);
-    m.impl("sos_filtfilt", sos_filtfilt_op);
-    m.impl("sos_block_energy", sos_block_energy_op);
-    m.impl("true_peak", true_peak_op);
-    m.impl("limiter_forward", limiter_op);
-    m.impl("limiter_stream_forward", limiter_stream_op);
-    m.impl("resample_stream_forward", resample_stream_op);
-    m.impl("delay_forward_ep", delay_ep_op);
-    m.impl("delay_stream_forward", delay_stream_op);
-    m.impl("delay_line_stream_forward", delay_line_stream_op);
-    m.impl("fir_direct_forward", fir_direct_op);
-    m.impl("fft_conv_forward", fft_conv_op);
-    m.impl("fir_stream_forward", fir_stream_op);
-    m.impl("chunk_forward", chunk_op);
-    m.impl("sos_forward_ep", sos_ep_op);
-    m.impl("fft_conv_forward_ep", fft_conv_ep_op);
-    m.impl("sos_fft_conv_forward", sos_fft_conv_op);
-    m.impl("normalize_apply", normalize_apply_op);
-    m.impl("sum_forward", sum_op);
-    m.impl("gain_forward", gain_op);
-    m.impl("quantile_abs", quantile_abs_op);
-    m.impl("stat_forward", stat_op);
-    m.impl("normalize_forward", normalize_op);
-    m.impl("deinterleave_forward", deinterleave_op);
-    m.impl("deinterleave_into", deinterleave_into_op);
-    m.impl("interleave_forward", interleave_op);
+    reg_op(m, "sos_forward(Tensor x, Tensor sos_cpu, Tensor? state_x=None, Tensor? state_y=None, *, ScalarType? out_dtype=None, "
+              "int precision=-1) -> (Tensor, Tensor, Tensor)", sos_op);
+    reg_op(m, "sos_forward_sections(Tensor x, Tensor sos_cpu, Tensor? state_x=None, Tensor? state_y=None, *, ScalarType? out_dtype=None, "
+              "int precision=-1) -> (Tensor, Tensor, Tensor, Tensor)", sos_sections_op);
+    reg_op(m, "sos_bank_forward(Tensor x, Tensor sos_banks_cpu, Tensor? state_x=None, Tensor? state_y=None, *, ScalarType? out_dtype=None, "
+              "int precision=-1) -> (Tensor, Tensor, Tensor)", bank_op);
+    reg_op(m, "sos_bank_sum_forward(Tensor x, Tensor sos_banks_cpu, Tensor? state_x=None, Tensor? state_y=None, *, int precision=-1) "
+              "-> (Tensor, Tensor, Tensor)", bank_sum_op);
+    reg_op(m, "biquad_forward(Tensor x, Tensor b, float a1, float a2, Tensor? state_x=None, Tensor? state_y=None, *, "
+              "ScalarType? out_dtype=None, int precision=-1) -> (Tensor, Tensor, Tensor)", biquad_op);
+    reg_op(m, "delay_line_forward(Tensor(a) x, int delay_samples, float decay, float mix) -> Tensor(a)", delay_line_op);
+    reg_op(m, "delay_forward(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong) -> Tensor", delay_op);
+    reg_op(m, "resample_forward(Tensor x, int up, int down, Tensor h) -> Tensor", resample_op);
+    reg_op(m, "sos_filtfilt(Tensor x, Tensor sos_cpu, int padtype=0, int padlen=-1) -> Tensor", sos_filtfilt_op);
+    reg_op(m, "sos_block_energy(Tensor x, Tensor sos_cpu, int num, int den=1) -> Tensor", sos_block_energy_op);
+    reg_op(m, "true_peak(Tensor x, Tensor taps_cpu, int up) -> Tensor", true_peak_op);
+    reg_op(m, "limiter_forward(Tensor x, float c, int A, int H, Tensor window_cpu, int up, Tensor? taps_cpu, int channels, "
+              "bool return_gain) -> (Tensor, Tensor)", limiter_op);
+    reg_op(m, "limiter_stream_forward(Tensor x, Tensor? hist, int consumed, float c, int A, int H, Tensor window_cpu, int up, "
+              "Tensor? taps_cpu, int channels, bool return_gain, int n_in=-1) -> (Tensor, Tensor, Tensor)", limiter_stream_op);
+    reg_op(m, "resample_stream_forward(Tensor x, Tensor h, Tensor? hist, int up, int down, int consumed) -> (Tensor, Tensor)",
+           resample_stream_op);
+    reg_op(m, "delay_forward_ep(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong, float gain, bool clamp, int stat_mode, "
+              "bool per_row) -> (Tensor, Tensor)", delay_ep_op);
+    reg_op(m, "delay_stream_forward(Tensor x, Tensor? hist, int delay_samples, float[] amps, float mix, bool pingpong) -> (Tensor, Tensor)",
+           delay_stream_op);
+    reg_op(m, "delay_line_stream_forward(Tensor x, Tensor? hist, int delay_samples, float decay, float mix) -> (Tensor, Tensor)",
+           delay_line_stream_op);
+    reg_op(m, "fir_direct_forward(Tensor x, Tensor kernel) -> Tensor", fir_direct_op);
+    reg_op(m, "fft_conv_forward(Tensor x, Tensor kernel, int pad_left, int pad_right) -> Tensor", fft_conv_op);
+    reg_op(m, "fir_stream_forward(Tensor x, Tensor kernel, Tensor? hist, bool direct) -> (Tensor, Tensor)", fir_stream_op);
+    reg_op(m, "chunk_forward(Tensor x, Tensor sos_cpu, Tensor? state_x, Tensor? state_y, Tensor kernel, Tensor? hist, float gain, "
+              "bool scale, bool clamp, int precision=-1) -> (Tensor, Tensor, Tensor, Tensor)", chunk_op);
+    reg_op(m, "sos_forward_ep(Tensor x, Tensor sos_cpu, Tensor? state_x, Tensor? state_y, float gain, bool clamp, int stat_mode, "
+              "bool per_row, *, ScalarType? out_dtype=None, int precision=-1) -> (Tensor, Tensor, Tensor, Tensor)", sos_ep_op);
+    reg_op(m, "fft_conv_forward_ep(Tensor x, Tensor kernel, int pad_left, int pad_right, float gain, bool clamp, int stat_mode, "
+              "bool per_row) -> (Tensor, Tensor)", fft_conv_ep_op);
+    reg_op(m, "sos_fft_conv_forward(Tensor x, Tensor sos_cpu, Tensor kernel, int pad_left, int pad_right, bool sections=False, "
+              "int force_block=0, float gain=1.0, bool clamp=False, int stat_mode=-1, bool per_row=False) -> (Tensor, Tensor, Tensor)",
+           sos_fft_conv_op);
+    reg_op(m, "normalize_apply(Tensor x, Tensor stat, float peak, int mode, bool per_row) -> Tensor", normalize_apply_op);
+    reg_op(m, "sum_forward(Tensor[] tensors) -> Tensor", sum_op);
+    reg_op(m, "gain_forward(Tensor x, float gain, bool clamp) -> Tensor", gain_op);
+    reg_op(m, "quantile_abs(Tensor x, float q) -> Tensor", quantile_abs_op);
+    reg_op(m, "stat_forward(Tensor x, int mode, bool per_row) -> Tensor", stat_op);
+    reg_op(m, "normalize_forward(Tensor x, float peak, int mode, bool per_row) -> Tensor", normalize_op);
+    reg_op(m, "deinterleave_forward(Tensor frames, float scale=3.0517578125e-05) -> Tensor", deinterleave_op);
+    reg_op(m, "deinterleave_into(Tensor frames, Tensor(a!) out, int frame_base=0, float scale=3.0517578125e-05) -> ()", deinterleave_into_op);
+    reg_op(m, "interleave_forward(Tensor x, int frame_base=0, int frames=-1) -> Tensor", interleave_op);
 }
 
 TORCH_LIBRARY_IMPL(torchfx_hip, Meta, m)
@@ -1077,22 +1064,6 @@ TORCH_LIBRARY_IMPL(torchfx_hip, Meta, m)
     });
     m.impl("gain_forward", [](const Tensor &x, double, bool) { return at::empty_like(x); });
     m.impl("normalize_forward", [](const Tensor &x, double, int64_t, bool) { return at::empty_like(x); });
-}
-
-// No CPU branch, by design: every op of the namespace answers a host tensor with the same error (one boxed function
-// registered for the CPU key of each op; per-namespace fallbacks are not supported by the dispatcher).
-static void no_cpu_boxed(const c10::OperatorHandle &op, c10::DispatchKeySet, torch::jit::Stack *)
-{
-    TORCH_CHECK(false, "torchfx_amd: ", op.schema().name(),
-                ": tensors must live on a ROCm device; this backend has no CPU path -- move them with .to('cuda').");
-}
-TORCH_LIBRARY_IMPL(torchfx_hip, CPU, m)
-{
-    for (const char *name : {"sos_forward", "sos_forward_sections", "sos_bank_forward", "sos_bank_sum_forward", "biquad_forward",
-                             "delay_line_forward", "delay_forward", "delay_forward_ep", "delay_stream_forward", "delay_line_stream_forward", "resample_forward", "sos_filtfilt", "sos_block_energy", "true_peak", "limiter_forward", "limiter_stream_forward", "resample_stream_forward", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep",
-                             "fft_conv_forward_ep", "sos_fft_conv_forward", "normalize_apply", "sum_forward", "gain_forward", "quantile_abs", "stat_forward",
-                             "normalize_forward", "deinterleave_forward", "deinterleave_into", "interleave_forward"})
-        m.impl(name, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>());
 }
 
 // The reference's module surface (binding.cpp:83-96): exactly these three names and argument lists.

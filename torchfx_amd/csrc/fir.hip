@@ -28,7 +28,9 @@
 // float64 signals (the reference computes conv1d in the input dtype) use a plain LDS-tiled
 // vector kernel: rare path, correctness first.
 #include "common.h"
+#include "ols_route.h"
 #include "plan_cache.h"
+#include "timedomain.h"
 #include "../../include/torchfx_hip.h"
 
 #include <cstdlib>
@@ -372,6 +374,25 @@ void fir_direct_forward(const void *x, void *y, int dtype, int64_t C, int64_t T,
         }
         TFX_HIP(hipGetLastError());
     }
+}
+
+// one chunk of a stateful FIR: history and chunk are read from their two buffers (direct form here, overlap-save through
+// ols_route.h), then the new history is written
+void fir_stream_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, const void *kernel_host, int64_t K, int direct,
+                        const void *hist_in, void *hist_out, hipStream_t stream)
+{
+    TFX_CHECK(K >= 1, "fir_stream_forward: empty kernel");
+    TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "fir_stream_forward: bad dtype %d", dtype);
+    TFX_CHECK(C >= 0 && T >= 0 && (C == 0 || (T <= INT64_MAX / 16 / C && K <= INT64_MAX / 16 / C)),
+              "fir_stream_forward: negative size or size overflows");
+    TFX_CHECK(C == 0 || T == 0 || x, "fir_stream_forward: null signal");
+    const int64_t H = K - 1;
+    check_stream_buffers("fir_stream_forward", dtype == TFX_F32 ? 4 : 8, x, C * T, y, C * T, hist_in, hist_out, C * H);
+    if (C > 0 && T > 0) {
+        if (direct) fir_direct_forward(x, y, dtype, C, T, kernel_host, K, stream, H ? hist_in : nullptr, hist_in ? H : 0);
+        else fft_conv_forward(x, y, dtype, C, T, kernel_host, K, H, 0, stream, H ? hist_in : nullptr, hist_in ? H : 0);
+    }
+    if (hist_out && C > 0) fir_hist_update(x, hist_in, hist_out, dtype, C, T, H, stream);
 }
 
 }  // namespace tfx

@@ -7,6 +7,7 @@
 // 16-bit PCM, move half the bytes over PCIe and convert on the GPU (x / 32768, libsndfile's
 // normalisation).  Both directions are pure HBM-bound transposes through a padded LDS tile.
 #include "common.h"
+#include "timedomain.h"
 #include "../../include/torchfx_hip.h"
 
 namespace tfx {

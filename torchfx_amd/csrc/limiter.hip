@@ -33,6 +33,7 @@
 #include "common.h"
 #include "plan_cache.h"
 #include "polyphase.h"
+#include "timedomain.h"
 #include "../../include/torchfx_hip.h"
 
 #include <algorithm>
@@ -410,13 +411,15 @@ static void limiter_check_values(const char *what, int dtype, double c, int64_t 
     }
 }
 
-void limiter_check(const void *x, const void *y, int dtype, int64_t groups, int64_t channels, int64_t T, double c, int64_t A,
-                   int64_t H, const void *window_host, int64_t up, const void *taps_host, int64_t nh)
+// every refusal of limiter_forward (host-only); hands back the plan it built on the way
+static LimiterPlan limiter_check(const void *x, const void *y, int dtype, int64_t groups, int64_t channels, int64_t T, double c,
+                                 int64_t A, int64_t H, const void *window_host, int64_t up, const void *taps_host, int64_t nh)
 {
     const char *what = "limiter_forward";
-    (void)limiter_plan(what, dtype, groups, channels, T, A, H, up, nh);
+    const LimiterPlan pl = limiter_plan(what, dtype, groups, channels, T, A, H, up, nh);
     limiter_check_values(what, dtype, c, A, window_host, up, taps_host);
     TFX_CHECK(groups * T == 0 || (x && y), "%s: null pointer", what);
+    return pl;
 }
 
 void limiter_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh, int dtype,
@@ -504,9 +507,8 @@ void limiter_forward(const void *x, void *y, void *gain, int dtype, int64_t grou
                      int64_t A, int64_t H, const void *window_host, int64_t up, const void *taps_host, int64_t nh,
                      hipStream_t stream)
 {
-    limiter_check(x, y, dtype, groups, channels, T, c, A, H, window_host, up, taps_host, nh);
+    const LimiterPlan pl = limiter_check(x, y, dtype, groups, channels, T, c, A, H, window_host, up, taps_host, nh);
     if (groups * T == 0) return;
-    const LimiterPlan pl = limiter_plan("limiter_forward", dtype, groups, channels, T, A, H, up, nh);
     if (dtype == TFX_F32) limiter_launch<float>(x, y, gain, groups, channels, T, c, A, H, window_host, up, taps_host, nh, pl, stream);
     else limiter_launch<double>(x, y, gain, groups, channels, T, c, A, H, window_host, up, taps_host, nh, pl, stream);
 }
@@ -535,9 +537,11 @@ static LimiterStreamPlan limiter_stream_plan(int dtype, int64_t groups, int64_t 
     return sp;
 }
 
-void limiter_stream_check(const void *x, const void *y, const void *gain, int dtype, int64_t groups, int64_t channels, int64_t T,
-                          int64_t n_in, int64_t consumed, double c, int64_t A, int64_t H, const void *window_host, int64_t up,
-                          const void *taps_host, int64_t nh, const void *hist_in, const void *hist_out)
+// every refusal of limiter_stream_forward (host-only); hands back the plan it built on the way
+static LimiterStreamPlan limiter_stream_check(const void *x, const void *y, const void *gain, int dtype, int64_t groups,
+                                              int64_t channels, int64_t T, int64_t n_in, int64_t consumed, double c, int64_t A,
+                                              int64_t H, const void *window_host, int64_t up, const void *taps_host, int64_t nh,
+                                              const void *hist_in, const void *hist_out)
 {
     const char *what = "limiter_stream_forward";
     const LimiterStreamPlan sp = limiter_stream_plan(dtype, groups, channels, T, A, H, up, nh);
@@ -551,6 +555,7 @@ void limiter_stream_check(const void *x, const void *y, const void *gain, int dt
     check_stream_buffers(what, esz, x, rows * T, y, rows * T, hist_in, hist_out, rows * sp.Hs);
     check_stream_buffers(what, esz, x, rows * T, gain, groups * T, hist_in, hist_out, rows * sp.Hs);
     check_stream_buffers(what, esz, y, rows * T, gain, groups * T, nullptr, nullptr, 0);
+    return sp;
 }
 
 void limiter_stream_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh, int dtype,
@@ -570,9 +575,8 @@ void limiter_stream_forward(const void *x, void *y, void *gain, int dtype, int64
                             int64_t consumed, double c, int64_t A, int64_t H, const void *window_host, int64_t up,
                             const void *taps_host, int64_t nh, const void *hist_in, void *hist_out, hipStream_t stream)
 {
-    limiter_stream_check(x, y, gain, dtype, groups, channels, T, n_in, consumed, c, A, H, window_host, up, taps_host, nh, hist_in,
-                         hist_out);
-    const LimiterStreamPlan sp = limiter_stream_plan(dtype, groups, channels, T, A, H, up, nh);
+    const LimiterStreamPlan sp = limiter_stream_check(x, y, gain, dtype, groups, channels, T, n_in, consumed, c, A, H, window_host, up,
+                                                      taps_host, nh, hist_in, hist_out);
     const int64_t rows = groups * channels;
     if (rows == 0) return;
     if (T == 0) {                                // nothing in, nothing out: the history moves on unchanged

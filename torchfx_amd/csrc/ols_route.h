@@ -7,6 +7,8 @@
 #include "common.h"
 #include "epilogue.h"
 
+#include <vector>
+
 namespace tfx {
 
 enum { OLS_PATH_ROCFFT = 0, OLS_PATH_PASSES = 1, OLS_PATH_LDS = 2 };      // tfx_ols_plan_info2's *path codes
@@ -55,6 +57,7 @@ void olsnative_forward(const float *x, float *y, int64_t C, int64_t Tn, const fl
 void olsnative_prewarm();
 void olsnative_wait_warm();
 void olsnative_clear();
+void host_fft_f64(std::vector<double> &re, std::vector<double> &im);      // in-place host FFT: the spectra olslds.hip and olsnative64.hip upload
 
 // olsnative64.hip: the three-pass pipeline in float64
 bool olsnative64_supported(int64_t K, int64_t L, bool has_hist, int64_t *N_out);

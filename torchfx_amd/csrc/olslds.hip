@@ -38,8 +38,6 @@
 
 namespace tfx {
 
-void host_fft_f64(std::vector<double> &re, std::vector<double> &im);      // olsnative.hip
-
 namespace ldsfft {
 
 using pk::v2f;

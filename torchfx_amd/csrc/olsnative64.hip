@@ -27,8 +27,6 @@
 
 namespace tfx {
 
-void host_fft_f64(std::vector<double> &re, std::vector<double> &im);      // olsnative.hip
-
 namespace ols64 {
 
 using ldsfft::cx;

@@ -17,6 +17,7 @@
 #include "common.h"
 #include "plan_cache.h"
 #include "polyphase.h"
+#include "timedomain.h"
 #include "../../include/torchfx_hip.h"
 
 #include <vector>
@@ -181,8 +182,8 @@ __global__ void __launch_bounds__(RS_THREADS) resample_kernel(const ResampleArgs
     }
 }
 
-void resample_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
-                    const void *taps_host, int64_t nh)
+static void resample_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
+                           const void *taps_host, int64_t nh)
 {
     TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "resample_forward: bad dtype %d", dtype);
     TFX_CHECK(up >= 1 && down >= 1, "resample_forward: up and down must be >= 1, got %lld / %lld", (long long)up, (long long)down);
@@ -348,18 +349,16 @@ static ResampleStreamGeom resample_stream_geometry(int64_t N, int64_t T, int64_t
     return g;
 }
 
-static void resample_stream_plan(int64_t N, int64_t T, int64_t *up, int64_t *down, int64_t nh, int esz, ResampleStreamGeom *g,
-                                 ResampleTiling *t)
-{
-    const int64_t d = gcd64(*up, *down);
-    *up /= d;
-    *down /= d;
-    *g = resample_stream_geometry(N, T, *up, *down, nh);
-    *t = resample_tiling(*up, *down, g->pre_remove, g->Lp, esz);
-}
+struct ResampleStreamPlan {
+    int64_t up, down;                    // reduced
+    ResampleStreamGeom g;
+    ResampleTiling t;
+};
 
-void resample_stream_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
-                           const void *taps_host, int64_t nh, int64_t consumed, const void *hist_in, const void *hist_out)
+// every refusal of resample_stream_forward (host-only); hands back the plan it built on the way
+static ResampleStreamPlan resample_stream_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t up,
+                                                int64_t down, const void *taps_host, int64_t nh, int64_t consumed,
+                                                const void *hist_in, const void *hist_out)
 {
     TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "resample_stream_forward: bad dtype %d", dtype);
     TFX_CHECK(up >= 1 && down >= 1, "resample_stream_forward: up and down must be >= 1, got %lld / %lld", (long long)up,
@@ -370,14 +369,17 @@ void resample_stream_check(const void *x, const void *y, int dtype, int64_t rows
     TFX_CHECK(T <= INT64_MAX / 8 - consumed && consumed + T <= (INT64_MAX / 4) / (up * down),
               "resample_stream_forward: (consumed + T) * up * down overflows");
     const int esz = dtype == TFX_F32 ? 4 : 8;
-    ResampleStreamGeom g;
-    ResampleTiling t;
-    resample_stream_plan(consumed, T, &up, &down, nh, esz, &g, &t);
+    const int64_t d = gcd64(up, down);
+    ResampleStreamPlan pl{up / d, down / d, {}, {}};
+    pl.g = resample_stream_geometry(consumed, T, pl.up, pl.down, nh);
+    pl.t = resample_tiling(pl.up, pl.down, pl.g.pre_remove, pl.g.Lp, esz);
+    const ResampleStreamGeom &g = pl.g;
     const int64_t n_y = g.m_end - g.m_begin;
     TFX_CHECK(rows == 0 || (T <= INT64_MAX / 16 / rows && n_y <= INT64_MAX / 16 / rows && g.H <= INT64_MAX / 16 / rows),
               "resample_stream_forward: size overflows");
     TFX_CHECK((x || rows * T == 0) && (y || rows * n_y == 0) && (hist_out || rows * g.H == 0), "resample_stream_forward: null pointer");
     check_stream_buffers("resample_stream_forward", esz, x, rows * T, y, rows * n_y, hist_in, hist_out, rows * g.H);
+    return pl;
 }
 
 // host-only: what resample_stream_forward does with a chunk of T samples after `consumed` (arguments as resample_stream_check's)
@@ -386,17 +388,14 @@ void resample_stream_plan_info(int64_t consumed, int64_t T, int64_t up, int64_t 
                                int64_t *lds_bytes)
 {
     const int one = 1;
-    resample_stream_check(&one, &one, dtype, 0, T, up, down, &one, nh, consumed, nullptr, nullptr);
-    ResampleStreamGeom g;
-    ResampleTiling t;
-    resample_stream_plan(consumed, T, &up, &down, nh, dtype == TFX_F32 ? 4 : 8, &g, &t);
-    *out_begin = g.m_begin;
-    *out_end = g.m_end;
-    *hist_len = g.H;
-    *pre_remove = g.pre_remove;
-    *Lp = g.Lp;
-    *kernel = t.kernel;
-    *lds_bytes = t.lds;
+    const ResampleStreamPlan pl = resample_stream_check(&one, &one, dtype, 0, T, up, down, &one, nh, consumed, nullptr, nullptr);
+    *out_begin = pl.g.m_begin;
+    *out_end = pl.g.m_end;
+    *hist_len = pl.g.H;
+    *pre_remove = pl.g.pre_remove;
+    *Lp = pl.g.Lp;
+    *kernel = pl.t.kernel;
+    *lds_bytes = pl.t.lds;
 }
 
 constexpr int64_t RS_STREAM_MIN_WG = 256;                // one workgroup per CU
@@ -442,11 +441,12 @@ void resample_stream_forward(const void *x, void *y, int dtype, int64_t rows, in
                              const void *taps_host, int64_t nh, int64_t consumed, const void *hist_in, void *hist_out,
                              hipStream_t stream)
 {
-    resample_stream_check(x, y, dtype, rows, T, up, down, taps_host, nh, consumed, hist_in, hist_out);
+    const ResampleStreamPlan pl = resample_stream_check(x, y, dtype, rows, T, up, down, taps_host, nh, consumed, hist_in, hist_out);
     const int esz = dtype == TFX_F32 ? 4 : 8;
-    ResampleStreamGeom g;
-    ResampleTiling t;
-    resample_stream_plan(consumed, T, &up, &down, nh, esz, &g, &t);
+    const ResampleStreamGeom &g = pl.g;
+    const ResampleTiling &t = pl.t;
+    up = pl.up;
+    down = pl.down;
     if (rows == 0) return;
     if (t.kernel == RS_COPY) {                                  // up == down: y = x, no history
         if (T) TFX_HIP(hipMemcpyAsync(y, x, (size_t)(rows * T * esz), hipMemcpyDeviceToDevice, stream));
@@ -614,13 +614,14 @@ static TruePeakPlan true_peak_plan(int dtype, int64_t rows, int64_t T, int64_t u
     return pl;
 }
 
-void true_peak_check(const void *x, int dtype, const void *peak, int64_t rows, int64_t T, int64_t up, const void *taps_host,
-                     int64_t nh, const void *work)
+// every refusal of true_peak_forward (host-only); hands back the plan it built on the way
+static TruePeakPlan true_peak_check(const void *x, int dtype, const void *peak, int64_t rows, int64_t T, int64_t up,
+                                    const void *taps_host, int64_t nh, const void *work)
 {
     const TruePeakPlan pl = true_peak_plan(dtype, rows, T, up, nh);
     TFX_CHECK(taps_host, "true_peak_forward: no taps");
     TFX_CHECK(rows * T == 0 || (x && peak && work), "true_peak_forward: null pointer");
-    (void)pl;
+    return pl;
 }
 
 void true_peak_plan_info(int64_t rows, int64_t T, int64_t up, int64_t nh, int dtype, int64_t *Lp, int64_t *tile_in, int64_t *tiles,
@@ -665,9 +666,8 @@ static void true_peak_launch(const void *x, void *peak, int64_t rows, int64_t T_
 void true_peak_forward(const void *x, int dtype, void *peak, int64_t rows, int64_t T, int64_t up, const void *taps_host, int64_t nh,
                        void *work, hipStream_t stream)
 {
-    true_peak_check(x, dtype, peak, rows, T, up, taps_host, nh, work);
+    const TruePeakPlan pl = true_peak_check(x, dtype, peak, rows, T, up, taps_host, nh, work);
     if (rows * T == 0) return;                                  // a row of no samples has peak 0: nothing is written
-    const TruePeakPlan pl = true_peak_plan(dtype, rows, T, up, nh);
     if (dtype == TFX_F32) true_peak_launch<float>(x, peak, rows, T, up, taps_host, nh, work, pl, stream);
     else true_peak_launch<double>(x, peak, rows, T, up, taps_host, nh, work, pl, stream);
 }

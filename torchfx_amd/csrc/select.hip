@@ -11,6 +11,7 @@
 // the result equals torch.quantile's wherever torch.quantile runs.  NaN anywhere -> NaN, like torch.
 #include <cstddef>
 #include "common.h"
+#include "timedomain.h"
 #include "../../include/torchfx_hip.h"
 
 namespace tfx {

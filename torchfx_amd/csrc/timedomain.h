@@ -1,0 +1,84 @@
+// timedomain.h -- the host entry points of the time-domain and elementwise ops, one prototype per exported function of fir.hip,
+// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip and layout.hip (the cascade's: sos.h; the overlap-save
+// pipelines': ols_route.h).  Included by the file that defines each function and by capi.hip, so a prototype that drifts from
+// its definition does not compile; default arguments live here and nowhere else.  Every *_forward checks its arguments before
+// anything touches the device; a *_plan_info takes the same checking path without the pointers.
+#pragma once
+#include "common.h"
+
+namespace tfx {
+
+struct Epilogue;                 // epilogue.h
+
+// ---- fir.hip ----
+void fir_direct_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, const void *kernel_host, int64_t K,
+                        hipStream_t stream, const void *hist = nullptr, int64_t H = 0);
+void fir_hist_update(const void *x, const void *hist_in, void *hist_out, int dtype, int64_t C, int64_t T, int64_t H,
+                     hipStream_t stream);
+// one chunk of a stateful FIR (tfx_fir_stream_forward): direct form or overlap-save (ols_route.h), then the new history
+void fir_stream_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, const void *kernel_host, int64_t K, int direct,
+                        const void *hist_in, void *hist_out, hipStream_t stream);
+void fir_clear();
+
+// ---- effects.hip ----
+void gain_forward(const void *x, void *y, int dtype, int64_t n, double gain, int clamp, hipStream_t stream);
+void stat_forward(const void *x, int dtype, int64_t C, int64_t T, int mode, int per_row, double *out_dev, hipStream_t stream);
+void normalize_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int mode, int per_row, double peak,
+                       hipStream_t stream);
+void normalize_apply_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int mode, int per_row, double peak,
+                             const double *stat, hipStream_t stream);
+void sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, hipStream_t stream);
+void delay_line_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int64_t delay, double coeff,
+                        hipStream_t stream);
+void delay_line_stream_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int64_t delay, double coeff,
+                               const void *hist_in, void *hist_out, hipStream_t stream);
+
+// ---- select.hip ----
+void quantile_abs_forward(const float *x, int64_t n, double q, double *out_dev, hipStream_t stream);
+
+// ---- delay.hip ----
+void delay_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
+                   const double *amps_host, double mix, int pingpong, const Epilogue *ep, hipStream_t stream);
+void delay_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
+                          const double *amps_host, double mix, int pingpong, const void *hist_in, void *hist_out, hipStream_t stream);
+int delay_regime(int64_t D, int64_t taps, int esz, int pingpong);
+void delay_clear();
+
+// ---- resample.hip (the polyphase table its users share: polyphase.h) ----
+void resample_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down, const void *taps_host,
+                      int64_t nh, hipStream_t stream);
+void resample_plan_info(int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int64_t *n_out, int64_t *pre_remove,
+                        int64_t *padded, int64_t *Lp, int *kernel, int64_t *lds_bytes);
+void resample_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
+                             const void *taps_host, int64_t nh, int64_t consumed, const void *hist_in, void *hist_out,
+                             hipStream_t stream);
+void resample_stream_plan_info(int64_t consumed, int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int64_t *out_begin,
+                               int64_t *out_end, int64_t *hist_len, int64_t *pre_remove, int64_t *Lp, int *kernel,
+                               int64_t *lds_bytes);
+void true_peak_forward(const void *x, int dtype, void *peak, int64_t rows, int64_t T, int64_t up, const void *taps_host, int64_t nh,
+                       void *work, hipStream_t stream);
+void true_peak_plan_info(int64_t rows, int64_t T, int64_t up, int64_t nh, int dtype, int64_t *Lp, int64_t *tile_in, int64_t *tiles,
+                         int64_t *work_elems);
+void resample_clear();
+
+// ---- limiter.hip ----
+void limiter_forward(const void *x, void *y, void *gain, int dtype, int64_t groups, int64_t channels, int64_t T, double c,
+                     int64_t A, int64_t H, const void *window_host, int64_t up, const void *taps_host, int64_t nh,
+                     hipStream_t stream);
+void limiter_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh, int dtype,
+                       int64_t *tile, int64_t *tiles, int64_t *halo_left, int64_t *halo_right, int64_t *Lp, int64_t *lds_bytes);
+void limiter_stream_forward(const void *x, void *y, void *gain, int dtype, int64_t groups, int64_t channels, int64_t T, int64_t n_in,
+                            int64_t consumed, double c, int64_t A, int64_t H, const void *window_host, int64_t up,
+                            const void *taps_host, int64_t nh, const void *hist_in, void *hist_out, hipStream_t stream);
+void limiter_stream_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh, int dtype,
+                              int64_t *latency, int64_t *history, int64_t *tile, int64_t *tiles, int64_t *positions,
+                              int64_t *lds_bytes);
+void limiter_clear();
+
+// ---- layout.hip ----
+void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, int64_t C, int64_t ld_out, int64_t f_base,
+                          double scale, hipStream_t stream);
+void interleave_forward(const float *in, float *out, int64_t F, int64_t C, int64_t ld_in, int64_t f_base,
+                        hipStream_t stream);
+
+}  // namespace tfx

@@ -72,6 +72,24 @@ def _coeff(t) -> Tensor:
     return torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64))
 
 
+def _dt(dtype: torch.dtype) -> int:
+    """The C ABI's dtype code (``TFX_F32`` / ``TFX_F64``)."""
+    return L.TFX_F64 if dtype == torch.float64 else L.TFX_F32
+
+
+_OUT_KINDS = {"int64": ctypes.c_int64, "int": ctypes.c_int, "double": ctypes.c_double, "double4": ctypes.c_double * 4}
+
+
+def _query(fn, args, outs: str) -> dict:
+    """One host-only planning query of the C ABI: ``fn(*args, *pointers)`` with one output pointer per word of ``outs``
+    (``name``: an int64, or ``name:kind`` with a kind of ``_OUT_KINDS`` -- ``int`` for kernel codes and segment counts),
+    checked with ``L.check``.  Returns ``{name: value}`` in that order."""
+    names = [w.partition(":") for w in outs.split()]
+    vals = [_OUT_KINDS[kind or "int64"]() for _, _, kind in names]
+    L.check(fn(*args, *[v if isinstance(v, ctypes.Array) else ctypes.byref(v) for v in vals]))
+    return {name: (list(v) if isinstance(v, ctypes.Array) else v.value) for (name, _, _), v in zip(names, vals)}
+
+
 def sos_forward(x: Tensor, sos: Tensor | None, sos_cpu: Tensor | None, state_x: Tensor | None,
                 state_y: Tensor | None, *, out_dtype: torch.dtype | None = None,
                 precision=None, return_sections: bool = False, epilogue: Epilogue | None = None):
@@ -166,10 +184,8 @@ def delay_line_stream_forward(x: Tensor, hist: Tensor | None, delay_samples: int
 def delay_regime(delay_samples: int, taps: int, dtype: torch.dtype = torch.float32, pingpong: bool = False) -> str:
     """Which kernel :func:`delay_forward` runs (``tfx_delay_plan_info``; host-only): "span" (the taps' span staged in LDS),
     "lattice" (long delay, residue classes with the last taps in registers) or "gather"."""
-    r = ctypes.c_int(0)
-    L.check(L.load().tfx_delay_plan_info(int(delay_samples), int(taps), L.TFX_F64 if dtype == torch.float64 else L.TFX_F32,
-                                         int(bool(pingpong)), ctypes.byref(r)))
-    return DELAY_REGIMES[r.value]
+    q = _query(L.load().tfx_delay_plan_info, (int(delay_samples), int(taps), _dt(dtype), int(bool(pingpong))), "regime:int")
+    return DELAY_REGIMES[q["regime"]]
 
 
 def resample_forward(x: Tensor, up: int, down: int, h: Tensor) -> Tensor:
@@ -185,12 +201,10 @@ def resample_plan_info(length: int, up: int, down: int, taps: int, dtype: torch.
     """What :func:`resample_forward` does for rows of ``length`` samples and a filter of ``taps`` taps (``tfx_resample_plan_info``;
     host-only): ``n_out``, ``n_pre_remove``, ``padded`` (the filter length with SciPy's zero padding), ``Lp`` (taps per
     phase), ``kernel`` and ``lds_bytes`` per workgroup."""
-    o = [ctypes.c_int64(0) for _ in range(4)]
-    k, lds = ctypes.c_int(0), ctypes.c_int64(0)
-    L.check(L.load().tfx_resample_plan_info(int(length), int(up), int(down), int(taps), L.TFX_F64 if dtype == torch.float64 else L.TFX_F32,
-                                            *[ctypes.byref(v) for v in o], ctypes.byref(k), ctypes.byref(lds)))
-    return {"n_out": o[0].value, "n_pre_remove": o[1].value, "padded": o[2].value, "Lp": o[3].value,
-            "kernel": RESAMPLE_KERNELS[k.value], "lds_bytes": lds.value}
+    q = _query(L.load().tfx_resample_plan_info, (int(length), int(up), int(down), int(taps), _dt(dtype)),
+               "n_out n_pre_remove padded Lp kernel:int lds_bytes")
+    q["kernel"] = RESAMPLE_KERNELS[q["kernel"]]
+    return q
 
 
 def resample_stream_forward(x: Tensor, h: Tensor, hist: Tensor | None, up: int, down: int,
@@ -227,13 +241,9 @@ def sos_filtfilt_plan_info(sos, rows: int, length: int, padtype="odd", padlen: i
     intermediate), ``warmup`` (halo of a time segment, -1 = one segment per row) and the segments per row of the two passes,
     ``nseg_forward`` / ``nseg_reverse``."""
     a = sos_array(sos)
-    o = [ctypes.c_int64(0) for _ in range(4)]
-    nf, nr = ctypes.c_int(0), ctypes.c_int(0)
-    L.check(L.load().tfx_sos_filtfilt_plan_info(int(rows), int(length), a.ctypes.data, a.shape[0], PADTYPES[padtype],
-                                                -1 if padlen is None else int(padlen), *[ctypes.byref(v) for v in o],
-                                                ctypes.byref(nf), ctypes.byref(nr)))
-    return {"default_padlen": o[0].value, "padlen": o[1].value, "work_elems": o[2].value, "warmup": o[3].value,
-            "nseg_forward": nf.value, "nseg_reverse": nr.value}
+    return _query(L.load().tfx_sos_filtfilt_plan_info,
+                  (int(rows), int(length), a.ctypes.data, a.shape[0], PADTYPES[padtype], -1 if padlen is None else int(padlen)),
+                  "default_padlen padlen work_elems warmup nseg_forward:int nseg_reverse:int")
 
 
 def sos_block_energy(x: Tensor, sos, num: int, den: int = 1) -> Tensor:
@@ -249,10 +259,8 @@ def sos_block_energy_plan_info(sos, rows: int, length: int, num: int, den: int =
     host-only, same argument checks): ``nblk`` blocks per row, ``nseg`` time segments per row and ``warm``, the halo of a
     segment (0 with one segment).  The cut depends on ``length``, the cascade and ``num / den`` alone."""
     a = sos_array(sos)
-    nblk, warm, nseg = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0)
-    L.check(L.load().tfx_sos_block_energy_plan_info(int(rows), int(length), a.ctypes.data, a.shape[0], int(num), int(den),
-                                                    ctypes.byref(nblk), ctypes.byref(nseg), ctypes.byref(warm)))
-    return {"nblk": nblk.value, "nseg": nseg.value, "warm": warm.value}
+    return _query(L.load().tfx_sos_block_energy_plan_info, (int(rows), int(length), a.ctypes.data, a.shape[0], int(num), int(den)),
+                  "nblk nseg:int warm")
 
 
 def true_peak(x: Tensor, taps: Tensor, up: int) -> Tensor:
@@ -267,10 +275,8 @@ def true_peak_plan_info(rows: int, length: int, up: int, taps: int, dtype: torch
     """What :func:`true_peak` does for ``rows`` rows of ``length`` samples and a filter of ``taps`` taps
     (``tfx_true_peak_plan_info``; host-only, same argument checks): ``Lp`` (taps per phase), ``tile_in`` (input positions per
     workgroup), ``tiles`` per row and ``work_elems`` (the per-tile maxima).  The tiling does not depend on ``rows``."""
-    o = [ctypes.c_int64(0) for _ in range(4)]
-    L.check(L.load().tfx_true_peak_plan_info(int(rows), int(length), int(up), int(taps),
-                                             L.TFX_F64 if dtype == torch.float64 else L.TFX_F32, *[ctypes.byref(v) for v in o]))
-    return {"Lp": o[0].value, "tile_in": o[1].value, "tiles": o[2].value, "work_elems": o[3].value}
+    return _query(L.load().tfx_true_peak_plan_info, (int(rows), int(length), int(up), int(taps), _dt(dtype)),
+                  "Lp tile_in tiles work_elems")
 
 
 def limiter_forward(x: Tensor, c: float, A: int, H: int, window: Tensor, up: int = 1, taps: Tensor | None = None,
@@ -290,10 +296,9 @@ def limiter_plan_info(length: int, A: int, H: int, up: int = 1, taps: int = 0, d
     checks on the sizes): ``tile`` (outputs per workgroup), ``tiles`` per group, ``halo_left`` / ``halo_right`` (input samples
     a tile reads behind its first and past its last output), ``Lp`` (taps per phase, 0 for ``up == 1``) and ``lds_bytes``.
     The tiling does not depend on ``groups`` or ``channels``."""
-    o = [ctypes.c_int64(0) for _ in range(6)]
-    L.check(L.load().tfx_limiter_plan_info(int(groups), int(channels), int(length), int(A), int(H), int(up), int(taps),
-                                           L.TFX_F64 if dtype == torch.float64 else L.TFX_F32, *[ctypes.byref(v) for v in o]))
-    return dict(zip(("tile", "tiles", "halo_left", "halo_right", "Lp", "lds_bytes"), (v.value for v in o)))
+    return _query(L.load().tfx_limiter_plan_info,
+                  (int(groups), int(channels), int(length), int(A), int(H), int(up), int(taps), _dt(dtype)),
+                  "tile tiles halo_left halo_right Lp lds_bytes")
 
 
 def limiter_stream_forward(x: Tensor, hist: Tensor | None, consumed: int, c: float, A: int, H: int, window: Tensor, up: int = 1,
@@ -317,10 +322,9 @@ def limiter_stream_plan_info(length: int, A: int, H: int, up: int = 1, taps: int
     same checks on the sizes): the stream's ``latency`` (D) and ``history`` (Hs) -- fixed by ``A``, ``H``, ``up`` and ``taps``
     alone --, ``tile`` (outputs per workgroup), ``tiles`` per group, ``positions`` (of the 8192 positions of the detector, the
     division and the sliding minimum, those the first workgroup sweeps) and ``lds_bytes``."""
-    o = [ctypes.c_int64(0) for _ in range(6)]
-    L.check(L.load().tfx_limiter_stream_plan_info(int(groups), int(channels), int(length), int(A), int(H), int(up), int(taps),
-                                                  L.TFX_F64 if dtype == torch.float64 else L.TFX_F32, *[ctypes.byref(v) for v in o]))
-    return dict(zip(("latency", "history", "tile", "tiles", "positions", "lds_bytes"), (v.value for v in o)))
+    return _query(L.load().tfx_limiter_stream_plan_info,
+                  (int(groups), int(channels), int(length), int(A), int(H), int(up), int(taps), _dt(dtype)),
+                  "latency history tile tiles positions lds_bytes")
 
 
 RESAMPLE_STREAM_KERNELS = ("resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel", "copy")
@@ -331,13 +335,10 @@ def resample_stream_plan_info(consumed: int, length: int, up: int, down: int, ta
     """What :func:`resample_stream_forward` does with a chunk of ``length`` samples after ``consumed`` (host-only):
     the outputs ``[out_begin, out_end)`` it emits, ``hist_len`` (H), ``n_pre_remove`` (outputs held back), ``Lp`` (taps per
     phase), ``kernel`` and ``lds_bytes`` per workgroup."""
-    o = [ctypes.c_int64(0) for _ in range(5)]
-    k, lds = ctypes.c_int(0), ctypes.c_int64(0)
-    L.check(L.load().tfx_resample_stream_plan_info(int(consumed), int(length), int(up), int(down), int(taps),
-                                                   L.TFX_F64 if dtype == torch.float64 else L.TFX_F32,
-                                                   *[ctypes.byref(v) for v in o], ctypes.byref(k), ctypes.byref(lds)))
-    return {"out_begin": o[0].value, "out_end": o[1].value, "hist_len": o[2].value, "n_pre_remove": o[3].value,
-            "Lp": o[4].value, "kernel": RESAMPLE_STREAM_KERNELS[k.value], "lds_bytes": lds.value}
+    q = _query(L.load().tfx_resample_stream_plan_info, (int(consumed), int(length), int(up), int(down), int(taps), _dt(dtype)),
+               "out_begin out_end hist_len n_pre_remove Lp kernel:int lds_bytes")
+    q["kernel"] = RESAMPLE_STREAM_KERNELS[q["kernel"]]
+    return q
 
 
 _TAPS_HOST: dict = {}        # (id(base tensor), offset, numel, dtype wanted) -> (weakref to base, version, host tensor)
@@ -390,7 +391,7 @@ def fft_conv_forward(x: Tensor, kernel, padding: tuple[int, int] = (0, 0), epilo
 def sos_fft_conv_supported(T: int, sos, taps: int, padding: tuple[int, int] = (0, 0), force_block: bool = False) -> bool:
     """Whether :func:`sos_fft_conv_forward` serves float32 rows of ``T`` samples with this cascade and tap count
     (``tfx_sos_fft_conv_supported``; host-only, no device needed)."""
-    s = np.ascontiguousarray(_coeff(sos).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 6)
+    s = sos_array(sos)
     return bool(L.load().tfx_sos_fft_conv_supported(
         ctypes.c_int64(int(T)), s.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.c_int64(s.shape[0]),
         ctypes.c_int64(int(taps)), ctypes.c_int64(int(padding[0])), ctypes.c_int64(int(padding[1])), ctypes.c_int(int(force_block))))
@@ -400,7 +401,7 @@ def sos_fft_conv_plan_info(T: int, sos, taps: int, padding: tuple[int, int] = (0
     """Block length ``N``, hop ``S``, frames per row ``F`` and warm-up samples of :func:`sos_fft_conv_forward` for rows of
     ``T`` samples, or None where it does not serve the geometry (``tfx_sos_fft_conv_plan_info2``; host-only).  ``tail_N`` /
     ``tail_S``: block and hop of the row's last frame where it runs at a smaller block than the ``F - 1`` before it, else 0."""
-    s = np.ascontiguousarray(_coeff(sos).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 6)
+    s = sos_array(sos)
     n, h, f, w, tn, ts = (ctypes.c_int64(0) for _ in range(6))
     ok = L.load().tfx_sos_fft_conv_plan_info2(ctypes.c_int64(int(T)), s.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                                              ctypes.c_int64(s.shape[0]), ctypes.c_int64(int(taps)), ctypes.c_int64(int(padding[0])),
@@ -425,7 +426,7 @@ def workspace_bytes() -> int:
 
 def sos_fft_conv_warmup(sos) -> int:
     """Samples a row's recursion starts early (from zero state) inside the column pass of :func:`sos_fft_conv_forward`."""
-    s = np.ascontiguousarray(_coeff(sos).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 6)
+    s = sos_array(sos)
     return int(L.load().tfx_sos_fft_conv_warmup(s.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.c_int64(s.shape[0])))
 
 
@@ -538,19 +539,16 @@ def sos_plan_info(sos, refine: bool = True) -> dict:
     s = np.ascontiguousarray(sos.detach().cpu().numpy() if isinstance(sos, Tensor) else sos, dtype=np.float64)
     if s.ndim != 2 or s.shape[-1] != 6:
         raise RuntimeError(f"expected [K, 6], got shape {tuple(s.shape)}")
-    prec, warm, eb = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_double(0.0)
-    L.check(lib.tfx_sos_plan_info(s.ctypes.data_as(ctypes.c_void_p), s.shape[0],
-                                  ctypes.byref(prec), ctypes.byref(warm), ctypes.byref(eb)))
+    coeffs = (s.ctypes.data_as(ctypes.c_void_p), s.shape[0])
+    q = _query(lib.tfx_sos_plan_info, coeffs, "auto_precision:int warmup f32_error_bound:double")
+    q["auto_precision"] = "f32" if q["auto_precision"] == L.PREC_F32 else "f64"
     if not refine:          # the warm-up and the float32 estimate alone: no replay of the float64 kernel (about 10 ms per plan)
-        return {"auto_precision": "f32" if prec.value == L.PREC_F32 else "f64",
-                "warmup": warm.value, "f32_error_bound": eb.value}
-    unit, r32, r64, errs = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), (ctypes.c_double * 4)()
-    L.check(lib.tfx_sos_refine_info(s.ctypes.data_as(ctypes.c_void_p), s.shape[0], ctypes.byref(unit), ctypes.byref(r32),
-                                    ctypes.byref(r64), errs))
-    return {"auto_precision": "f32" if prec.value == L.PREC_F32 else "f64",
-            "warmup": warm.value, "f32_error_bound": eb.value,
-            "unit_form": bool(unit.value), "refine_f32": bool(r32.value), "refine_f64": bool(r64.value),
-            "blocked_error": (errs[0], errs[2]), "sequential_error": (errs[1], errs[3])}
+        return q
+    r = _query(lib.tfx_sos_refine_info, coeffs, "unit_form:int refine_f32:int refine_f64:int errs:double4")
+    errs = r.pop("errs")
+    q.update({k: bool(v) for k, v in r.items()})
+    q.update(blocked_error=(errs[0], errs[2]), sequential_error=(errs[1], errs[3]))
+    return q
 
 
 def env_reload() -> None:
@@ -573,12 +571,8 @@ def ols_plan_info(K: int, T: int, padding: tuple[int, int] = (0, 0), dtype: torc
     """Block geometry of the overlap-save op for a signal of `dtype` (FFT length N, hop S, blocks per row F) and the
     path that runs: "lds" (one launch, 4096-point transform in LDS), "passes" (three-pass four-step pipeline) or
     "rocfft"; `native` = a hand-written path; `bytes_per_sample` = modelled HBM traffic per output sample."""
-    lib = L.load()
-    n, s_, f, path = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0)
-    code = L.TFX_F64 if dtype == torch.float64 else L.TFX_F32
-    L.check(lib.tfx_ols_plan_info2(int(K), int(T), int(padding[0]), int(padding[1]), code, ctypes.byref(n),
-                                   ctypes.byref(s_), ctypes.byref(f), ctypes.byref(path)))
-    esz = 8 if dtype == torch.float64 else 4
-    bps = {2: esz * n.value / s_.value + esz, 1: (20.0 * n.value / s_.value + 4.0) * esz / 4, 0: 95.0 * esz / 4}[path.value]
-    return {"N": n.value, "S": s_.value, "F": f.value, "native": path.value != 0,
-            "path": ("rocfft", "passes", "lds")[path.value], "bytes_per_sample": bps}
+    q = _query(L.load().tfx_ols_plan_info2, (int(K), int(T), int(padding[0]), int(padding[1]), _dt(dtype)), "N S F path:int")
+    path, esz = q["path"], 8 if dtype == torch.float64 else 4
+    bps = {2: esz * q["N"] / q["S"] + esz, 1: (20.0 * q["N"] / q["S"] + 4.0) * esz / 4, 0: 95.0 * esz / 4}[path]
+    return {"N": q["N"], "S": q["S"], "F": q["F"], "native": path != 0, "path": ("rocfft", "passes", "lds")[path],
+            "bytes_per_sample": bps}
