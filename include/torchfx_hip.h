@@ -568,6 +568,40 @@ int tfx_limiter_stream_plan_info(int64_t groups, int64_t channels, int64_t T, in
                                  int64_t *lds_bytes);
 
 /* ---------------------------------------------------------------------------
+ * tfx_compressor_forward -- feed-forward compressor: log-domain static curve with a soft knee and the smooth decoupled peak
+ * detector of Giannoulis, Massberg & Reiss (JAES 2012).  x is [groups, channels, T]; the `channels` rows of a group share one
+ * gain curve.  The detector runs in float64 for both signal dtypes, for a group and a sample n:
+ *   1. p[n]  = max_ch |x[ch,n]|
+ *   2. o = 20 log10 p[n] - th (p = 0: -inf);  v[n] = 0 where 2o <= -w, s o where 2o >= w, else s (o + w/2)^2 / (2w);
+ *      a non-finite p[n] gives v[n] = NaN
+ *   3. y1[n] = max(v[n], alpha_r y1[n-1] + (1 - alpha_r) v[n]);  yL[n] = alpha_a yL[n-1] + (1 - alpha_a) y1[n];
+ *      (y1[-1], yL[-1]) = state_in[group] or 0; max propagates NaN
+ *   4. g[n] = 10^((makeup_db - yL[n]) / 20);  y[ch,n] = dtype(g[n] x[ch,n]);  gain[n] = dtype(g[n])
+ * th the threshold in dB, s = 1 - 1/ratio in [0, 1], w the knee width in dB (>= 0), alpha_a / alpha_r = exp(-1 / (time * fs)) in
+ * [0, 1] (0 for a time of 0).  x, y DEVICE [groups, channels, T] of dtype (y may alias x); gain DEVICE [groups, T] of dtype or
+ * null; state_in / state_out DEVICE [groups, 2] float64 (y1, yL) or null (silence in / no state out; state_out is the pair at
+ * T - 1 and needs its own buffer).
+ * Both recursions are associative scans, so a group's row is cut into tiles of 2048 samples and the tiles into `segments` runs
+ * (tfx_compressor_plan_info; 0 = chosen from groups and T, any other value is clamped to the tile count).  segments == 1 is
+ * one launch that reads x once and writes y once; otherwise three launches (release summaries, attack summaries, result):
+ * x is read three times and `scratch` -- DEVICE, scratch_bytes of the plan, may be null for one segment -- carries the
+ * summaries across the launch boundaries.  No workgroup waits for another, no atomics.  The association of the scans follows
+ * the tiling: results for different `segments` agree to float64 round-off of the detector (about 1e-13 dB), not bit for bit; a
+ * group whose level never passes th - w/2 comes back bit-identical from a zero state with makeup_db = 0, whatever the tiling.
+ * From the first non-finite sample of a group to the end of its rows every output, the gain and the end state are NaN; earlier
+ * samples and other groups are unaffected.  A group's bits depend on (T, segments) and its own samples alone.  Arguments are
+ * checked before the device is touched.  T == 0 copies state_in to state_out.
+ * ------------------------------------------------------------------------- */
+int tfx_compressor_forward(const void *x, void *y, void *gain_or_null, int dtype, int64_t groups, int64_t channels, int64_t T,
+                           double th, double s, double w, double alpha_a, double alpha_r, double makeup_db, const double *state_in,
+                           double *state_out, int64_t segments, void *scratch, tfx_stream_t stream);
+/* what tfx_compressor_forward does (host-only, same checks on the sizes): samples per tile (2048), tiles per group, the segments
+ * it takes for the request `segments`, the tiles of the longest segment (the first tiles mod segments hold one more than the
+ * rest) and the bytes of `scratch` (0 for one segment) */
+int tfx_compressor_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t segments, int64_t *tile, int64_t *tiles,
+                             int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes);
+
+/* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of
  * ParallelFilterCombination.forward, src/torchfx/filter/__base.py:1019-1026).
  * xs_host: HOST array of n DEVICE pointers, each [numel] of dtype.

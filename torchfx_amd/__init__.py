@@ -6,7 +6,8 @@ Top-level names follow the reference (``src/torchfx/__init__.py:12-23``): ``Wave
 from torchfx_amd import filter  # noqa: A004
 from torchfx_amd._ops import is_native_available
 from torchfx_amd.chain import FilterChain
-from torchfx_amd.effect import FX, Delay, Gain, Limiter, LoudnessNormalize, Normalize, Reverb
+from torchfx_amd.dynamics import compress
+from torchfx_amd.effect import FX, Compressor, Delay, Gain, Limiter, LoudnessNormalize, Normalize, Reverb
 from torchfx_amd.filtfilt import sosfiltfilt
 from torchfx_amd.limiter import limit
 from torchfx_amd.loudness import (block_energy, integrated_loudness, kweighting_sos, loudness_range, momentary_loudness,
@@ -14,7 +15,7 @@ from torchfx_amd.loudness import (block_energy, integrated_loudness, kweighting_
 from torchfx_amd.resample import Resample, resample_poly
 from torchfx_amd.wave import Wave
 
-__all__ = ["FX", "Delay", "FilterChain", "Gain", "Limiter", "LoudnessNormalize", "Normalize", "Resample", "Reverb", "Wave", "block_energy",
-           "filter", "integrated_loudness", "is_native_available", "kweighting_sos", "limit", "loudness_range", "momentary_loudness",
+__all__ = ["FX", "Compressor", "Delay", "FilterChain", "Gain", "Limiter", "LoudnessNormalize", "Normalize", "Resample", "Reverb", "Wave", "block_energy",
+           "compress", "filter", "integrated_loudness", "is_native_available", "kweighting_sos", "limit", "loudness_range", "momentary_loudness",
            "resample_poly", "short_term_loudness", "sosfiltfilt", "true_peak", "true_peak_linear"]
 __version__ = "0.1.0"

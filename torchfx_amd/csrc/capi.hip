@@ -665,6 +665,25 @@ int tfx_limiter_stream_plan_info(int64_t groups, int64_t channels, int64_t T, in
     TFX_API_END
 }
 
+int tfx_compressor_forward(const void *x, void *y, void *gain_or_null, int dtype, int64_t groups, int64_t channels, int64_t T,
+                           double th, double s, double w, double alpha_a, double alpha_r, double makeup_db, const double *state_in,
+                           double *state_out, int64_t segments, void *scratch, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    compressor_forward(x, y, gain_or_null, dtype, groups, channels, T, th, s, w, alpha_a, alpha_r, makeup_db, state_in, state_out,
+                       segments, scratch, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_compressor_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t segments, int64_t *tile, int64_t *tiles,
+                             int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(tile && tiles && segments_out && seg_tiles && scratch_bytes, "compressor_plan_info: null output");
+    compressor_plan_info(groups, channels, T, segments, tile, tiles, segments_out, seg_tiles, scratch_bytes);
+    TFX_API_END
+}
+
 int tfx_sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, tfx_stream_t stream)
 {
     TFX_API_BEGIN

@@ -582,6 +582,37 @@ std::tuple<Tensor, Tensor, Tensor> limiter_stream_op(const Tensor &x_in, const O
     return std::make_tuple(y, gain, hout);
 }
 
+// Feed-forward compressor (tfx_compressor_forward): x [..., T], its rows in groups of `channels` consecutive rows that share one
+// gain curve; th, s, w, alpha_a, alpha_r, makeup_db as the C entry takes them; state [groups, 2] float64 (y1, yL) or None
+// (silence); segments 0 = the plan's choice -> (y like x, gain [groups, T] or an empty tensor, new state [groups, 2] float64).
+// The summaries between the launches live in a tensor from torch's allocator.
+std::tuple<Tensor, Tensor, Tensor> compressor_op(const Tensor &x_in, double th, double s, double w, double alpha_a, double alpha_r,
+                                                 double makeup_db, int64_t channels, const OptTensor &state, bool return_gain,
+                                                 int64_t segments)
+{
+    const char *what = "compressor_forward";
+    need_device(x_in, "x");
+    TORCH_CHECK(x_in.dim() >= 1, what, ": x must have a time dimension");
+    const Tensor x = x_in.contiguous();
+    const int dt = dtype_code(x, what);
+    const int64_t T = x.size(-1), rows = stream_rows(x);
+    TORCH_CHECK(channels >= 1 && rows % channels == 0, what, ": ", rows, " rows do not split into groups of ", channels);
+    const int64_t groups = rows / channels;
+    int64_t info[5];
+    check_rc(tfx_compressor_plan_info(groups, channels, T, segments, info, info + 1, info + 2, info + 3, info + 4), what);
+    Tensor keep;
+    const double *sin = state_ptr(state, {groups, 2}, x, "compressor_forward: state", keep);
+    const auto f64 = x.options().dtype(at::kDouble);
+    Tensor y = at::empty_like(x), sout = at::empty({groups, 2}, f64), scratch = at::empty({info[4] / 8}, f64);
+    Tensor gain = return_gain ? at::empty({groups, T}, x.options()) : at::empty({0}, x.options());
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_compressor_forward(x.data_ptr(), y.data_ptr(), return_gain ? gain.data_ptr() : nullptr, dt, groups, channels, T, th, s,
+                                    w, alpha_a, alpha_r, makeup_db, sin, sout.data_ptr<double>(), segments,
+                                    info[4] ? scratch.data_ptr() : nullptr, stream_of(x)),
+             what);
+    return std::make_tuple(y, gain, sout);
+}
+
 // One chunk of a resampling stream (tfx_resample_stream_forward): x [..., T] after `consumed` samples per row, h as for
 // resample_forward, hist [rows, H] (None = silence) -> (y [..., M(consumed + T) - M(consumed)], new history [rows, H])
 struct ResampleStreamPlan {
@@ -965,6 +996,15 @@ Tensor fft_conv_meta(const Tensor &x, const Tensor &kernel, int64_t pad_left, in
     return at::empty({x.size(0), tout > 0 ? tout : 0}, x.options());
 }
 
+std::tuple<Tensor, Tensor, Tensor> compressor_meta(const Tensor &x, double, double, double, double, double, double, int64_t channels,
+                                                   const OptTensor &, bool return_gain, int64_t)
+{
+    TORCH_CHECK(x.dim() >= 1 && channels >= 1, "compressor_forward: bad shape");
+    const int64_t T = x.size(-1), groups = stream_rows(x) / channels;
+    return {at::empty_like(x), return_gain ? at::empty({groups, T}, x.options()) : at::empty({0}, x.options()),
+            at::empty({groups, 2}, x.options().dtype(at::kDouble))};
+}
+
 // No CPU branch, by design: every op of the namespace answers a host tensor with the same error instead of the dispatcher's
 // "no kernel for backend CPU" (one boxed function registered for the CPU key of each op; per-namespace fallbacks are not
 // supported by the dispatcher).
@@ -1064,6 +1104,19 @@ TORCH_LIBRARY_IMPL(torchfx_hip, Meta, m)
     });
     m.impl("gain_forward", [](const Tensor &x, double, bool) { return at::empty_like(x); });
     m.impl("normalize_forward", [](const Tensor &x, double, int64_t, bool) { return at::empty_like(x); });
+}
+
+// The dynamics processors live in a namespace of their own (torch.ops.torchfx_dynamics), registered the same way: the device
+// kernel for the CUDA key, the "no CPU path" refusal for the CPU key, shape inference for Meta.
+TORCH_LIBRARY(torchfx_dynamics, m)
+{
+    reg_op(m, "compressor_forward(Tensor x, float th, float s, float w, float alpha_a, float alpha_r, float makeup_db, int channels, "
+              "Tensor? state, bool return_gain, int segments=0) -> (Tensor, Tensor, Tensor)", compressor_op);
+}
+
+TORCH_LIBRARY_IMPL(torchfx_dynamics, Meta, m)
+{
+    m.impl("compressor_forward", compressor_meta);
 }
 
 // The reference's module surface (binding.cpp:83-96): exactly these three names and argument lists.

@@ -298,6 +298,65 @@ class Limiter(FX):
                 f"link={self.link}, fs={self.fs}")
 
 
+class Compressor(FX):
+    """Feed-forward compressor: :func:`torchfx_amd.dynamics.compress` with the same parameters -- ``threshold_db``, ``ratio``
+    (``>= 1``, ``inf`` allowed), ``attack`` and ``release`` in seconds, ``knee_db`` (soft-knee width), ``makeup_db`` and ``link``
+    (one gain curve per ``[C, T]`` signal or batch item).  ``wave | LoudnessNormalize(-14) | Compressor(-18, 3) | Limiter(-1.0)``
+    is the mastering chain.
+
+    The level detector is the smooth decoupled peak detector (log domain, float64 for both signal dtypes); the gain is causal
+    with no latency.  ``fs`` comes from the ``Wave`` the effect is piped into when it is None.  Every call starts from silence:
+    the compressor is a step of its own in ``Wave.plan()`` and a chunked stream needs
+    :class:`torchfx_amd.realtime.StatefulCompressor`, which carries the detector's state from chunk to chunk."""
+
+    def __init__(self, threshold_db: float = -20.0, ratio: float = 4.0, attack: float = 5e-3, release: float = 100e-3,
+                 knee_db: float = 6.0, makeup_db: float = 0.0, link: bool = True, fs: int | None = None) -> None:
+        super().__init__()
+        from torchfx_amd.dynamics import CompressorParams
+
+        CompressorParams(48000 if fs is None else fs, torch.float32, threshold_db, ratio, attack, release, knee_db, makeup_db)   # argument errors now
+        self.threshold_db, self.ratio, self.attack, self.release = float(threshold_db), float(ratio), float(attack), float(release)
+        self.knee_db, self.makeup_db, self.link, self.fs = float(knee_db), float(makeup_db), bool(link), fs
+
+    def params(self, dtype: torch.dtype):
+        """The call's :class:`torchfx_amd.dynamics.CompressorParams` for a signal of ``dtype`` at ``self.fs``."""
+        if self.fs is None:
+            raise ValueError("Compressor needs the sample rate: pass fs or pipe a Wave into it (wave | Compressor())")
+        from torchfx_amd.dynamics import CompressorParams
+
+        return CompressorParams(self.fs, dtype, self.threshold_db, self.ratio, self.attack, self.release, self.knee_db, self.makeup_db)
+
+    def route(self, x: Tensor, length: int | None = None) -> str:
+        """``native (...)`` or ``numpy on host -- <reason>`` for ``x`` (rows of ``length`` samples, default x's)."""
+        if not x.is_cuda:
+            return f"numpy on host -- {x.device.type} tensor"
+        try:
+            self.params(x.dtype)
+            from torchfx_amd.limiter import _grouping
+
+            n = int(x.shape[-1]) if length is None else int(length)
+            groups, channels = _grouping(x, self.link)
+            info = _ext().compressor_plan_info(n, groups, channels)
+        except (RuntimeError, ValueError, TypeError) as e:
+            return f"refused -- {e}"
+        launches = "one launch" if info["segments"] == 1 else "three launches"
+        return (f"native (compressor_kernel, log-domain decoupled peak detector, {info['tiles']} tile(s) of {info['tile']} per group "
+                f"in {info['segments']} segment(s); {launches})")
+
+    @torch.no_grad()
+    def forward(self, waveform: Tensor) -> Tensor:
+        if self.fs is None:
+            raise ValueError("Compressor needs the sample rate: pass fs or pipe a Wave into it (wave | Compressor())")
+        from torchfx_amd.dynamics import compress
+
+        return compress(waveform, self.fs, self.threshold_db, self.ratio, self.attack, self.release, self.knee_db, self.makeup_db,
+                        self.link)
+
+    def extra_repr(self) -> str:
+        return (f"threshold_db={self.threshold_db}, ratio={self.ratio}, attack={self.attack}, release={self.release}, "
+                f"knee_db={self.knee_db}, makeup_db={self.makeup_db}, link={self.link}, fs={self.fs}")
+
+
 class Epilogued(FX):
     """Planner product (``Wave.plan()``, ``fuse_epilogue``): a filter followed by ``Gain`` and / or ``Normalize``
     whose elementwise work rides on the filter's own kernel.  ``producer`` is an SOS filter / cascade or an

@@ -63,3 +63,11 @@ def ops():
 
     load()
     return torch.ops.torchfx_hip
+
+
+def dynamics_ops():
+    """``torch.ops.torchfx_dynamics`` (the dynamics processors' namespace, registered by the same module) with the library loaded."""
+    import torch
+
+    load()
+    return torch.ops.torchfx_dynamics

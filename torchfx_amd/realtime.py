@@ -18,7 +18,9 @@ every row, returns the outputs each chunk completes (``tfx_resample_stream_forwa
 ``resample_poly`` on the whole signal.  :class:`StatefulLimiter` is the look-ahead limiter of a stream: it carries the last
 ``D + A + H - 2`` (+ the detector interpolator's reach) inputs of every row, holds the last ``D = A - 1 + i_lo`` outputs back
 (``tfx_limiter_stream_forward``, one launch per chunk), and its chunks plus ``flush()`` are ``limit`` on the whole signal;
-``aligned=False`` gives the constant-latency form a sound card needs.
+``aligned=False`` gives the constant-latency form a sound card needs.  :class:`StatefulCompressor` is the compressor of a
+stream: causal, no latency, it carries the detector's ``(y1, yL)`` per group (``tfx_compressor_forward``'s state), and its chunks
+equal ``compress`` on the whole signal to float64 round-off of the detector (not bit for bit).
 
 Small chunks are launch-bound (a 2 x 4096 step is ~60 us of host + launch overhead for a few us of
 GPU work), so ``StreamProcessor(..., use_graph=True)`` captures one full-size chunk step -- every
@@ -38,7 +40,7 @@ from collections.abc import Generator, Sequence
 import torch
 from torch import Tensor, nn
 
-from torchfx_amd.effect import FX, Delay, Limiter, MonoDelayStrategy, PingPongDelayStrategy, Reverb, _ext
+from torchfx_amd.effect import FX, Compressor, Delay, Limiter, MonoDelayStrategy, PingPongDelayStrategy, Reverb, _ext
 from torchfx_amd.filter._base import AbstractFilter
 from torchfx_amd.filter.fir import FIR
 from torchfx_amd.resample import Resample, design_taps, window_key
@@ -538,6 +540,59 @@ class StatefulLimiter(_RingOut, Limiter):
         return tail
 
 
+class StatefulCompressor(Compressor):
+    """:class:`~torchfx_amd.effect.Compressor` over a continuous stream: the detector's state ``(y1, yL)`` per group goes from
+    chunk to chunk, so the gain curve has no seam.  The compressor is causal with no latency: every chunk returns the chunk's
+    shape and there is nothing to flush.
+
+    The state lives in ``_hist`` (``[groups, 2]`` float64 on the chunks' device) and is rebuilt from silence when the row
+    count, the ``link`` grouping or the device changes; :meth:`reset_state` does the same on request.  A changed parameter
+    applies from the next chunk on.  All chunks together equal :func:`~torchfx_amd.dynamics.compress` on the whole signal to
+    float64 round-off of the detector -- within 1e-10 dB of gain -- and not bit for bit: the scan's association follows the
+    cut.  After a NaN or Inf the state of its group is NaN and stays so until :meth:`reset_state`.  Device float32 / float64
+    chunks run :func:`torchfx_ext.compressor_forward` (one launch for a chunk of up to 2048 samples), CPU chunks the host
+    path."""
+
+    def __init__(self, threshold_db: float = -20.0, ratio: float = 4.0, attack: float = 5e-3, release: float = 100e-3,
+                 knee_db: float = 6.0, makeup_db: float = 0.0, link: bool = True, fs: int | None = None) -> None:
+        super().__init__(threshold_db, ratio, attack, release, knee_db, makeup_db, link, fs)
+        self.reset_state()
+
+    def reset_state(self) -> None:
+        self._hist: Tensor | None = None            # [groups, 2] float64 (y1, yL); None = silence
+        self._key: tuple | None = None              # what the running stream is bound to
+
+    def _capture_key(self) -> tuple:
+        """What a captured HIP graph of this effect bakes in."""
+        return (self.threshold_db, self.ratio, self.attack, self.release, self.knee_db, self.makeup_db, self.link, self.fs)
+
+    def _sync_history(self) -> None:
+        """Nothing to resize: the state's shape follows the rows alone."""
+
+    @torch.no_grad()
+    def forward(self, x: Tensor) -> Tensor:
+        _rows(x)
+        if self.fs is None:
+            raise ValueError("StatefulCompressor needs the sample rate: pass fs or let the processor configure it")
+        from torchfx_amd.dynamics import compress
+
+        key = (tuple(x.shape[:-1]), self.link, x.device)
+        if key != self._key:                        # a new stream: from silence
+            self.reset_state()
+            self._key = key
+        y, self._hist = compress(x, self.fs, self.threshold_db, self.ratio, self.attack, self.release, self.knee_db, self.makeup_db,
+                                 self.link, state=self._hist, return_state=True)
+        return y
+
+
+def _refuse_compressor(e, who: str) -> None:
+    members = list(e.modules() if isinstance(e, nn.Module) else [e])
+    if any(isinstance(m, Compressor) and not isinstance(m, StatefulCompressor) for m in members):
+        raise TypeError(f"Compressor cannot run in {who}: every call starts its level detector from silence, so a chunked stream "
+                        "would drop the envelope at every chunk start; use StatefulCompressor(...) in its place, or compress the "
+                        "whole signal (wave | Compressor(...)) before or after streaming")
+
+
 def _holds_back(e) -> bool:
     """Effects whose chunks may return fewer samples than they take and that hand the rest out in ``flush()``."""
     return isinstance(e, (StatefulResample, StatefulLimiter))
@@ -717,6 +772,7 @@ class StreamProcessor:
             _refuse_zero_phase(e, "StreamProcessor")
             _refuse_loudness(e, "StreamProcessor")
             _refuse_limiter(e, "StreamProcessor")
+            _refuse_compressor(e, "StreamProcessor")
             if not isinstance(e, StatefulResample) and any(isinstance(m, Resample) for m in e.modules()):
                 raise TypeError("Resample cannot run in StreamProcessor: resampling each chunk on its own leaves a seam at "
                                 "every chunk boundary; use StatefulResample as a top-level effect of the chain, or resample "
@@ -1038,6 +1094,7 @@ class RealtimeProcessor:
             _refuse_zero_phase(e, "RealtimeProcessor")
             _refuse_loudness(e, "RealtimeProcessor")
             _refuse_limiter(e, "RealtimeProcessor")
+            _refuse_compressor(e, "RealtimeProcessor")
             if _has_stateful_resample(e):
                 raise TypeError("StatefulResample cannot run in RealtimeProcessor: a sound card's output block has the input "
                                 "block's length and sample rate; resample with StreamProcessor or Wave.resample instead")

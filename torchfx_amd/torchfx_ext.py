@@ -36,7 +36,7 @@ __all__ = [
     "delay_amplitudes", "delay_regime", "delay_stream_forward", "delay_line_stream_forward", "resample_forward",
     "resample_plan_info", "resample_stream_forward", "resample_stream_plan_info", "sos_filtfilt", "sos_filtfilt_plan_info",
     "sos_block_energy", "sos_block_energy_plan_info", "true_peak", "true_peak_plan_info", "limiter_forward", "limiter_plan_info",
-    "limiter_stream_forward", "limiter_stream_plan_info",
+    "limiter_stream_forward", "limiter_stream_plan_info", "compressor_forward", "compressor_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
 ]
@@ -325,6 +325,31 @@ def limiter_stream_plan_info(length: int, A: int, H: int, up: int = 1, taps: int
     return _query(L.load().tfx_limiter_stream_plan_info,
                   (int(groups), int(channels), int(length), int(A), int(H), int(up), int(taps), _dt(dtype)),
                   "latency history tile tiles positions lds_bytes")
+
+
+def compressor_forward(x: Tensor, th: float, s: float, w: float, alpha_a: float, alpha_r: float, makeup_db: float = 0.0,
+                       channels: int = 1, state: Tensor | None = None, return_gain: bool = False,
+                       segments: int = 0) -> tuple[Tensor, Tensor | None, Tensor]:
+    """The feed-forward compressor (``tfx_compressor_forward``; the definition is :func:`torchfx_amd.dynamics.compress`'s) with
+    its parameters already reduced: ``x [..., T]`` on the device (float32 / float64), its rows in groups of ``channels``
+    consecutive rows that share one gain curve; ``th`` the threshold in dB, ``s = 1 - 1 / ratio``, ``w`` the knee width in dB,
+    ``alpha_a`` / ``alpha_r`` the detector's coefficients ``exp(-1 / (time fs))`` (0 for a time of 0), ``state [groups, 2]``
+    float64 ``(y1, yL)`` or None (silence).  ``segments`` cuts a group's row for the scan (0: the plan's choice; clamped to the
+    tile count): one launch for one segment, three otherwise.  Returns ``(y, gain | None, new state [groups, 2] float64)``.
+    The op lives in ``torch.ops.torchfx_dynamics``."""
+    native.ops()                                         # loads the library: both namespaces are registered by the one module
+    y, g, st = native.dynamics_ops().compressor_forward(x.contiguous(), float(th), float(s), float(w), float(alpha_a), float(alpha_r),
+                                                        float(makeup_db), int(channels), state, bool(return_gain), int(segments))
+    return y, (g if return_gain else None), st
+
+
+def compressor_plan_info(length: int, groups: int = 1, channels: int = 1, segments: int = 0) -> dict:
+    """What :func:`compressor_forward` does for ``groups`` rows of ``length`` samples (``tfx_compressor_plan_info``; host-only,
+    same checks on the sizes): ``tile`` (samples per tile), ``tiles`` per group, the ``segments`` it takes for the request
+    (0: chosen from ``groups`` and ``length``, 1 when the groups alone fill the chip), ``seg_tiles`` (tiles of the longest
+    segment) and ``scratch_bytes`` (the summaries between the launches; 0 for one segment)."""
+    return _query(L.load().tfx_compressor_plan_info, (int(groups), int(channels), int(length), int(segments)),
+                  "tile tiles segments seg_tiles scratch_bytes")
 
 
 RESAMPLE_STREAM_KERNELS = ("resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel", "copy")

@@ -210,7 +210,7 @@ def plan_cache_clear() -> None:
 
 
 def _member_key(m: nn.Module, guard: list) -> tuple:
-    from torchfx_amd.effect import Delay, Gain, Limiter, LoudnessNormalize, Normalize
+    from torchfx_amd.effect import Compressor, Delay, Gain, Limiter, LoudnessNormalize, Normalize
     from torchfx_amd.filter.zerophase import ZeroPhase
     from torchfx_amd.resample import Resample, window_key
 
@@ -240,6 +240,8 @@ def _member_key(m: nn.Module, guard: list) -> tuple:
         k += (m.target, m.channel_weights, m.fs)
     elif isinstance(m, Limiter):
         k += (m.ceiling_db, m.lookahead, m.hold, m.detector, m.link, m.oversample, id(m.taps), id(m.window), m.fs)
+    elif isinstance(m, Compressor):
+        k += (m.threshold_db, m.ratio, m.attack, m.release, m.knee_db, m.makeup_db, m.link, m.fs)
     return k
 
 
@@ -330,15 +332,15 @@ class Wave:
         """A ``Resample`` is a barrier: the steps between two of them are planned on their own, at the row length they see,
         and nothing merges, folds or attaches an epilogue across one.  So is a ``ZeroPhase`` (its two passes are one step;
         the row length stays), a ``LoudnessNormalize`` (it measures exactly the signal the steps before it produce) and a
-        ``Limiter`` (its detector reads the samples the steps before it store)."""
-        from torchfx_amd.effect import Limiter, LoudnessNormalize
+        ``Limiter`` or a ``Compressor`` (their detectors read the samples the steps before them store)."""
+        from torchfx_amd.effect import Compressor, Limiter, LoudnessNormalize
         from torchfx_amd.filter.zerophase import ZeroPhase
         from torchfx_amd.resample import Resample
 
         plan: list[nn.Module] = []
         segment: list[nn.Module] = []
         for m in self._pipeline:
-            if isinstance(m, (Resample, ZeroPhase, LoudnessNormalize, Limiter)):
+            if isinstance(m, (Resample, ZeroPhase, LoudnessNormalize, Limiter, Compressor)):
                 plan += self._build_segment(segment, length, dtype)
                 plan.append(m)
                 segment = []
@@ -571,7 +573,7 @@ class Wave:
     def explain(self) -> list[str]:
         """One line per step of :meth:`plan` for THIS tensor: the step, the route it will take (``CascadeFIR``: the fused
         recursion-in-pass-A pipeline or the staged pair of launches) and why."""
-        from torchfx_amd.effect import Delay, Epilogued, Limiter, LoudnessNormalize
+        from torchfx_amd.effect import Compressor, Delay, Epilogued, Limiter, LoudnessNormalize
         from torchfx_amd.filter.fused import CascadeFIR, FusedSOSCascade
         from torchfx_amd.filter.zerophase import ZeroPhase
         from torchfx_amd.realtime import StatefulDelay, _native_stream
@@ -598,7 +600,7 @@ class Wave:
             elif isinstance(inner, Resample):
                 line += ": " + inner.route(self._ys, length)
                 length = inner.output_length(length)
-            elif isinstance(inner, (ZeroPhase, LoudnessNormalize, Limiter)):
+            elif isinstance(inner, (ZeroPhase, LoudnessNormalize, Limiter, Compressor)):
                 line += ": " + inner.route(self._ys, length)
             lines.append(line)
         return lines
