@@ -156,6 +156,24 @@ def test_time_segmentation_geometry_edges(T, monkeypatch):
             close(sy2, sy1.cpu().numpy(), 1e-13, f"T={T} variant={variant} nseg={nseg} state_y")
 
 
+def test_variant_knob_out_of_range_is_rejected(monkeypatch):
+    """TFX_SOS_VARIANT names one of six kernel geometries (0 ... 5); any larger value is refused on the host, before a table
+    is built or a kernel launched, and does not quietly pick a geometry.  Unset again, the same call computes the cascade.
+    The bounds are those of test_random_shapes_vs_oracle: same kind of cascade, same float32 result."""
+    from scipy.signal import butter
+    sos = np.vstack([butter(2, w, output="sos") for w in (0.05, 0.3)])
+    x = rnd((2, 8192), 8192)
+    monkeypatch.setenv("TFX_SOS_VARIANT", "6")
+    with pytest.raises(RuntimeError, match="TFX_SOS_VARIANT"):
+        ext().sos_forward(dev(x), None, torch.from_numpy(sos), None, None)
+    monkeypatch.delenv("TFX_SOS_VARIANT")
+    ey, esx, esy = O.sos_forward(x, sos)
+    y, sx, sy = ext().sos_forward(dev(x), None, torch.from_numpy(sos), None, None)
+    close(y, ey.astype(np.float32), 2.5e-7, "y")
+    close(sx, esx, TOL_STATE, "sx")
+    close(sy, esy, TOL_STATE, "sy")
+
+
 def test_empty_inputs():
     """No rows ([0, T]) or no samples ([C, 0]): empty outputs, the state passes through (iir_cpu.cpp writes back what it
     loaded); the overlap-save op keeps the reference's "kernel size" error for a signal shorter than the taps."""

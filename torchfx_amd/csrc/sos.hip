@@ -78,12 +78,8 @@ struct SosParams {
     int ep_scale, ep_clamp, ep_stat;
     double *ep_partial;  // [C * nseg], one per stream (row-major over (row, segment)), pre-zeroed
     int *nf_flag;        // [C * nseg]: stream ended with a non-finite carried state (nseg > 1 only; every stream writes its slot)
-    const void *ep_host; // host side only: the Epilogue this launch serves
-    int ep_fused;        // host side only: the kernel applies it (else separate passes follow the launch)
     int fair;            // > 0: waves that share a SIMD alternate their issue priority every 2^fair clocks
     int fair_nw;         // waves per SIMD of this launch (the priority levels that rotate): 2 ... 4
-    int unit;            // host side only: `tab` holds the unit-b0 form (UNIT kernels)
-    int refine;          // host side only: the launch takes the kernels that refine the scan's start states (FFR; plan_refine)
     // zero-phase passes (FF kernels, sos_filtfilt_forward): T above is the length of the edge-extended row, ff_T + 2 * ff_pad
     int ff;              // 1 = forward pass over the virtual extension of x, 2 = reverse-time pass over the intermediate
     int ff_padtype;      // TFX_PAD_ODD / EVEN / CONSTANT (NONE arrives as ff_pad = 0)
@@ -176,12 +172,19 @@ template <typename T> struct U16 {               // 16 bytes of T
 // MEAS measuring pass (SosParams::ms_*): the cascade's output is not stored; the stream keeps the sum of its squares over each
 //      block of samples it owns.  Segments start on block edges (their halo in front), so every block has one writer.  Scalar
 //      (!VEC) path only, TOut = TIn (the stage holds the input alone); MEAS = false compiles to the code it was before
+// One compiled instance of the kernel = one value of this struct and a type triple; written with designated initialisers.
+struct SosKernel { int LC = 32; bool VEC = false, TAPS = false, PF = false; int MINW = 2;
+                   bool SUMB = false, EPI = false, UNIT = false; int FF = 0; bool FFR = false, MEAS = false;
+                   bool operator==(const SosKernel &) const = default; };
+
 // The stream body: one wavefront walks stream `sid` = (row, segment) with `stage` as its private LDS (transposition
 // stage + carry).  Shared by the cascade kernel below and by the fused per-chunk kernel (chunk_iir_fir_kernel), whose
 // output pointer is an LDS buffer.
-template <typename TIn, typename TOut, typename TC, int LC, bool VEC, bool TAPS, bool PF, bool SUMB, bool EPI, bool UNIT = false, int FF = 0, bool FFR = false, bool MEAS = false>
+template <typename TIn, typename TOut, typename TC, SosKernel G>
 __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_t sid, char *const stage, const int lane)
 {
+    constexpr int LC = G.LC, FF = G.FF;
+    constexpr bool VEC = G.VEC, TAPS = G.TAPS, PF = G.PF, SUMB = G.SUMB, EPI = G.EPI, UNIT = G.UNIT, FFR = G.FFR, MEAS = G.MEAS;
     static_assert(!(TAPS && SUMB), "section taps are not available in sum mode");
     static_assert(!(UNIT && (TAPS || SUMB)), "the unit-b0 form serves the plain cascade only");
     static_assert(FF == 0 || !(VEC || TAPS || PF || SUMB || EPI || UNIT), "the zero-phase passes run the plain scalar path");
@@ -726,14 +729,14 @@ __host__ __device__ constexpr int sos_wave_lds_bytes(int nbl, int K)
            ((((nbl * K * 4 + 2 * LC) * (int)sizeof(TC)) + 15) & ~15);
 }
 
-template <typename TIn, typename TOut, typename TC, int LC, bool VEC, bool TAPS, bool PF, int MINW, bool SUMB = false, bool EPI = false, bool UNIT = false, int FF = 0, bool FFR = false, bool MEAS = false>
-__global__ void __launch_bounds__(256, MINW) sos_stream_kernel(const SosParams p)
+template <typename TIn, typename TOut, typename TC, SosKernel G>
+__global__ void __launch_bounds__(256, G.MINW) sos_stream_kernel(const SosParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // provably wave-uniform -> SGPR addressing
-    const int per_wave = sos_wave_lds_bytes<TIn, TOut, TC, LC>(SUMB ? p.nsum : 1, p.K);
-    sos_stream_body<TIn, TOut, TC, LC, VEC, TAPS, PF, SUMB, EPI, UNIT, FF, FFR, MEAS>(p, (int64_t)blockIdx.x * 4 + wave, smem + wave * per_wave, lane);
+    const int per_wave = sos_wave_lds_bytes<TIn, TOut, TC, G.LC>(G.SUMB ? p.nsum : 1, p.K);
+    sos_stream_body<TIn, TOut, TC, G>(p, (int64_t)blockIdx.x * 4 + wave, smem + wave * per_wave, lane);
 }
 
 // Non-finite samples and time segmentation.  In the sequential recursion a NaN / Inf never leaves: once the
@@ -1299,17 +1302,18 @@ template <typename TC> static void build_table(SosPlan *pl, int LC, bool unit, S
     }
     t.buf = std::make_unique<DeviceBuffer>(h);          // synchronous copy from a temporary: once per distinct filter
 }
-// The one way to a plan's device tables: sets p.tab / p.nsteps / p.unit for the arithmetic type, the tile size LC (16, 32, 64)
-// and the form, building the table on first use.  Every (type, LC, form) has a table of its own.
-static void table_for(SosParams &p, SosPlan *pl, bool f32, int LC, bool unit = false)
+// The one way to a plan's device tables: sets p.tab / p.nsteps for the arithmetic type and for the kernel that will read them
+// -- its tile size G.LC (16, 32, 64) and its form G.UNIT -- building the table on first use.  Every (type, LC, form) has a
+// table of its own.
+static void table_for(SosParams &p, SosPlan *pl, bool f32, const SosKernel &G)
 {
     std::lock_guard<std::mutex> lk(g_plan_mu);
-    SosPlan::Table &t = pl->tab[f32 ? 0 : 1][LC == 16 ? 0 : (LC == 32 ? 1 : 2)][unit ? 1 : 0];
+    SosPlan::Table &t = pl->tab[f32 ? 0 : 1][lc_index(G.LC)][G.UNIT ? 1 : 0];
     if (!t.buf) {
-        if (f32) build_table<float>(pl, LC, unit, t);
-        else build_table<double>(pl, LC, unit, t);
+        if (f32) build_table<float>(pl, G.LC, G.UNIT, t);
+        else build_table<double>(pl, G.LC, G.UNIT, t);
     }
-    p.tab = t.buf->p; p.nsteps = t.nsteps; p.unit = unit ? 1 : 0;
+    p.tab = t.buf->p; p.nsteps = t.nsteps;
 }
 
 void sos_clear_plans() { g_plans.clear(); }
@@ -1367,6 +1371,9 @@ static void plan_segments(SosParams &p, int64_t plan_warm, int TILE, int residen
 // without a device.  The FF kernels run LC = 32 at two workgroups per CU (launch bounds; 72 KB of LDS each at K = 4) unless
 // the carry of a long cascade leaves room for one only.
 constexpr int FF_LC = 32;
+// the kernel of a pass (1 = forward, 2 = reverse): a float64 result takes the refined start states in both passes; a float32
+// result is 20 times inside its bar without
+constexpr SosKernel ff_kernel(int pass, bool f64_result) { return {.LC = FF_LC, .FF = pass, .FFR = f64_result}; }
 static size_t ff_shmem(int K)
 {
     return 4 * (size_t)sos_wave_lds_bytes<double, double, double, FF_LC>(1, K);      // float32 at either end: the same, the stage holds the wider type
@@ -1375,15 +1382,17 @@ static int ff_blocks_per_cu(int K) { return 2 * ff_shmem(K) <= 160 * 1024 ? 2 : 
 
 // The one launch of the cascade kernel: LDS size, segmentation, flag scratch, the launch and the repair launch behind it.
 // MEAS: the measuring pass arrives with its segmentation decided (block_energy_plan: nseg, warm, ms_bps; fair_nw = 2), so the
-// occupancy query and plan_segments are not for it.
-template <typename TIn, typename TOut, typename TC, int LC, bool VEC, bool TAPS, bool PF, int MINW, bool SUMB = false, bool EPI = false, bool UNIT = false, int FF = 0, bool FFR = false, bool MEAS = false>
-static void launch_one(SosParams p, int64_t plan_warm, hipStream_t stream)
+// occupancy query and plan_segments are not for it.  `ep`: the Epilogue an EPI kernel serves (where its statistic goes).
+template <typename TIn, typename TOut, typename TC, SosKernel G>
+static void launch_one(SosParams p, const Epilogue *ep, int64_t plan_warm, hipStream_t stream)
 {
+    constexpr int LC = G.LC, FF = G.FF;
+    constexpr bool SUMB = G.SUMB, EPI = G.EPI, MEAS = G.MEAS;
     const int nbl = SUMB ? p.nsum : 1;
     const size_t shmem = 4 * (size_t)sos_wave_lds_bytes<TIn, TOut, TC, LC>(nbl, p.K);
     if constexpr (MEAS) TFX_CHECK(shmem <= 160 * 1024, "sos_block_energy: K=%d needs %zu B of LDS (max 163840)", p.K, shmem);
     else TFX_CHECK(shmem <= 160 * 1024, "sos_forward: %d band(s) x K=%d need %zu B of LDS (max 163840)", nbl, p.K, shmem);
-    auto kern = sos_stream_kernel<TIn, TOut, TC, LC, VEC, TAPS, PF, MINW, SUMB, EPI, UNIT, FF, FFR, MEAS>;
+    auto kern = sos_stream_kernel<TIn, TOut, TC, G>;
     if (!EPI) p.ep_stat = -1;                      // the plain instantiation has no epilogue code
     if (shmem > 64 * 1024)
         TFX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
@@ -1440,116 +1449,124 @@ static void launch_one(SosParams p, int64_t plan_warm, hipStream_t stream)
             fix();
         } else fix();
     }
-    if (p.ep_stat >= 0) {
-        const Epilogue *ep = (const Epilogue *)p.ep_host;
+    if (p.ep_stat >= 0)
         stat_finish(p.ep_partial, ep->per_row ? p.C : 1, ep->per_row ? p.nseg : nstreams, p.ep_stat, ep->stat_out, stream);
-    }
 }
 
-// Variants (TFX_SOS_VARIANT): 0 = LC32, 1 = LC16, 2 = LC32 + register prefetch, 3 = LC16 + prefetch.
-// Register budgets (waves/SIMD) were chosen from -Rpass-analysis so that nothing spills.
-template <typename TIn, typename TOut, typename TC>
-static void launch_main(const SosParams &p, bool vec, int variant, int64_t plan_warm, hipStream_t stream)
-{
-    constexpr bool F32 = sizeof(TC) == 4;
-    if constexpr (!F32) {
-        if (p.refine) {
-            // refined start states (plan_refine): the shipping geometry only -- LC = 64 on aligned rows in both forms, with and
-            // without the epilogue, LC = 32 on the dword path, and the two with section taps (sos_forward sends every
-            // refined launch here, whatever TFX_SOS_VARIANT says)
-            if (p.taps) {
-                if (vec) launch_one<TIn, TOut, TC, 64, true, true, false, 2, false, false, false, 0, true>(p, plan_warm, stream);
-                else launch_one<TIn, TOut, TC, 32, false, true, false, 2, false, false, false, 0, true>(p, plan_warm, stream);
-            } else if (!vec) launch_one<TIn, TOut, TC, 32, false, false, false, 2, false, false, false, 0, true>(p, plan_warm, stream);
-            else if (p.unit) {
-                if (p.ep_fused) launch_one<TIn, TOut, TC, 64, true, false, false, 2, false, true, true, 0, true>(p, plan_warm, stream);
-                else launch_one<TIn, TOut, TC, 64, true, false, false, 2, false, false, true, 0, true>(p, plan_warm, stream);
-            } else {
-                if (p.ep_fused) launch_one<TIn, TOut, TC, 64, true, false, false, 2, false, true, false, 0, true>(p, plan_warm, stream);
-                else launch_one<TIn, TOut, TC, 64, true, false, false, 2, false, false, false, 0, true>(p, plan_warm, stream);
-            }
-            return;
-        }
-    }
-    if (p.taps && vec && variant >= 4) {   // the shipping LC = 64 geometry with every section's output tapped (parity tests)
-        launch_one<TIn, TOut, TC, 64, true, true, false, F32 ? 3 : 2>(p, plan_warm, stream);
-        return;
-    }
-    if (p.taps || !vec) {     // debug taps / unaligned rows: plain dword path
-        if (variant & 1) {
-            if (p.taps) launch_one<TIn, TOut, TC, 16, false, true, false, F32 ? 5 : 3>(p, plan_warm, stream);
-            else launch_one<TIn, TOut, TC, 16, false, false, false, F32 ? 5 : 3>(p, plan_warm, stream);
-        } else {
-            if (p.taps) launch_one<TIn, TOut, TC, 32, false, true, false, F32 ? 3 : 2>(p, plan_warm, stream);
-            else launch_one<TIn, TOut, TC, 32, false, false, false, F32 ? 3 : 2>(p, plan_warm, stream);
-        }
-        return;
-    }
-    if constexpr (!F32) {
-        if (p.unit) {          // unit-b0 form of the shipping geometry, plain and with the epilogue (same cascade arithmetic in both)
-            if (p.ep_fused) launch_one<TIn, TOut, TC, 64, true, false, false, 2, false, true, true>(p, plan_warm, stream);
-            else launch_one<TIn, TOut, TC, 64, true, false, false, 2, false, false, true>(p, plan_warm, stream);
-            return;
-        }
-    }
-    if (p.ep_fused) {          // epilogue instantiation: same tile geometry as the plain kernel (bit-identical cascade output)
-        if (variant >= 4) launch_one<TIn, TOut, TC, 64, true, false, false, F32 ? 3 : 2, false, true>(p, plan_warm, stream);
-        else launch_one<TIn, TOut, TC, 32, true, false, true, 2, false, true>(p, plan_warm, stream);
-        return;
-    }
-    switch (variant) {
-    case 1: launch_one<TIn, TOut, TC, 16, true, false, false, F32 ? 8 : 5>(p, plan_warm, stream); break;
-    case 2: launch_one<TIn, TOut, TC, 32, true, false, true, F32 ? 4 : 2>(p, plan_warm, stream); break;
-    case 3: launch_one<TIn, TOut, TC, 16, true, false, true, F32 ? 6 : 4>(p, plan_warm, stream); break;
-    case 4: launch_one<TIn, TOut, TC, 64, true, false, false, F32 ? 3 : 2>(p, plan_warm, stream); break;   // 64 samples per lane: half the scan per sample
-    case 5: launch_one<TIn, TOut, TC, 64, true, false, true, F32 ? 3 : 1>(p, plan_warm, stream); break;
-    default: launch_one<TIn, TOut, TC, 32, true, false, false, F32 ? 5 : 3>(p, plan_warm, stream); break;
-    }
-}
-// rarely used dtype mixes: one configuration only
-template <typename TIn, typename TOut, typename TC>
-static void launch_rare(const SosParams &p, bool vec, int64_t plan_warm, hipStream_t stream)
-{
-    if (p.refine) {           // the same three with refined start states (plan_refine)
-        if (p.taps) launch_one<TIn, TOut, TC, 16, false, true, false, 3, false, false, false, 0, true>(p, plan_warm, stream);
-        else if (vec) launch_one<TIn, TOut, TC, 16, true, false, false, 4, false, false, false, 0, true>(p, plan_warm, stream);
-        else launch_one<TIn, TOut, TC, 16, false, false, false, 3, false, false, false, 0, true>(p, plan_warm, stream);
-        return;
-    }
-    if (p.taps) launch_one<TIn, TOut, TC, 16, false, true, false, 3>(p, plan_warm, stream);
-    else if (vec) launch_one<TIn, TOut, TC, 16, true, false, false, 4>(p, plan_warm, stream);
-    else launch_one<TIn, TOut, TC, 16, false, false, false, 3>(p, plan_warm, stream);
-}
+// Which kernel a forward call runs: sos_choose decides it, the lists behind it compile it, a static_assert holds the two together.
+// The type family of a call: float32 signals with float32 / float64 arithmetic (main), the other dtype mixes (rare), and the
+// sum mode with float32 / float64 arithmetic.
+enum class SosFamily { MainF32, MainF64, Rare, SumF32, SumF64 };
 
-// sum mode: one configuration per dtype mix (LC = 16: the accumulator costs registers)
-template <typename TIn, typename TOut, typename TC>
-static void launch_sum(const SosParams &p, bool vec, int64_t plan_warm, hipStream_t stream)
-{
-    if constexpr (sizeof(TC) == 8) {
-        if (p.refine) {       // refined start states (plan_refine)
-            if (vec) launch_one<TIn, TOut, TC, 16, true, false, false, 3, true, false, false, 0, true>(p, plan_warm, stream);
-            else launch_one<TIn, TOut, TC, 16, false, false, false, 3, true, false, false, 0, true>(p, plan_warm, stream);
-            return;
-        }
-    }
-    if (vec) launch_one<TIn, TOut, TC, 16, true, false, false, 3, true>(p, plan_warm, stream);
-    else launch_one<TIn, TOut, TC, 16, false, false, false, 3, true>(p, plan_warm, stream);
-}
+// Cascades whose lane scan costs the result accuracy (poles next to z = 1 under a rough output; plan_refine, decided per
+// cascade and for the dtype of the result) take the refined kernels.  Those exist for the shipping geometry only: LC = 64
+// on aligned rows, LC = 32 on the dword path; LC = 16 for the rare dtype mixes and the sum mode as before.  The decision
+// is made at the tile size of that geometry -- the one the refined launch runs -- whatever TFX_SOS_VARIANT asks for: a
+// variant with fewer samples per lane is never left unrefined where the shipping one is refined.  Every other cascade runs the kernel, and computes the bits, it did without this rule.
+constexpr int sos_refine_lc(SosFamily fam, bool vec) { return fam == SosFamily::MainF32 || fam == SosFamily::MainF64 ? (vec ? 64 : 32) : 16; }
 
-// The tile variant of a call (the list at launch_main), and with it the tile size LC of kernel and table.  `env` is
-// TFX_SOS_VARIANT (negative = unset), `vec` the aligned 16-byte path, `ep` a requested epilogue (fused where vec holds).
-static int resolve_variant(bool rare, bool sum, int prec, bool vec, bool ep, int env)
+// The kernel of a call.  `vec`: aligned rows (16-byte path); `taps`: section taps asked for; `ep`: an epilogue asked for --
+// the chosen kernel applies it where G.EPI says so, separate passes over y otherwise; `refine`: plan_refine at sos_refine_lc
+// (float64 arithmetic only); `unit_ok`: the plan has a unit-b0 form; `knob`: TFX_SOS_VARIANT, negative = unset.
+// Variants: 0 = LC32, 1 = LC16, 2 = LC32 + register prefetch, 3 = LC16 + prefetch, 4 = LC64, 5 = LC64 + prefetch.
+// Register budgets (MINW, waves/SIMD) were chosen from -Rpass-analysis so that nothing spills.
+constexpr SosKernel sos_choose(SosFamily fam, bool vec, bool taps, bool ep, bool refine, bool unit_ok, int knob)
 {
-    if (rare || sum) return 1;                     // one configuration only (launch_rare, launch_sum)
+    const bool F32 = fam == SosFamily::MainF32;
+    const bool ffr = refine && !F32 && fam != SosFamily::SumF32;
+    // rarely used dtype mixes and the sum mode: one configuration each (LC = 16: the sum's accumulator costs registers)
+    if (fam == SosFamily::Rare) return {.LC = 16, .VEC = vec && !taps, .TAPS = taps, .MINW = vec && !taps ? 4 : 3, .FFR = ffr};
+    if (fam == SosFamily::SumF32 || fam == SosFamily::SumF64) return {.LC = 16, .VEC = vec, .MINW = 3, .SUMB = true, .FFR = ffr};
+    // the epilogue is fused on aligned rows without section taps, into kernels that exist for LC = 32 + prefetch and LC = 64
+    const bool fuse = ep && vec && !taps;
     // float32 arithmetic: LC = 32 + register prefetch (4 waves per SIMD); float64: LC = 64 -- the kernel is bound by VALU
     // issue (1440 instructions per 2048-sample tile, ~100 % busy at 3 waves per SIMD), and 64 samples per lane halve the
     // scan's share per sample (0.352 vs 0.38-0.42 ms at cfg 2 on the same box)
-    int variant = env >= 0 ? env : (prec == TFX_PREC_F32 ? 2 : 4);
+    int variant = knob >= 0 ? knob : (F32 ? 2 : 4);
     if (variant >= 4 && !vec) variant = 2;         // LC = 64 exists for the aligned (16-byte) path only
-    if (variant >= 4 && ep) variant = 4;           // (its epilogue instantiation: no register prefetch)
-    if (variant < 4 && ep && vec) variant = 2;     // the epilogue kernel exists for LC = 32 and LC = 64: table and kernel must agree
-    return variant;
+    if (fuse) variant = variant >= 4 ? 4 : 2;
+    if (ffr) variant = vec ? 4 : 0;                // refined start states: the shipping geometry only (sos_refine_lc)
+    const int LC = variant >= 4 ? 64 : ((variant & 1) ? 16 : 32);
+    if (taps || !vec)                              // debug taps / unaligned rows: plain dword path, but LC = 64 taps its aligned rows
+        return {.LC = LC, .VEC = LC == 64, .TAPS = taps, .MINW = LC == 16 ? (F32 ? 5 : 3) : (F32 ? 3 : 2), .FFR = ffr};
+    // the shipping float32-in / float32-out geometry (float64 arithmetic, LC = 64, aligned rows, no section taps) runs the
+    // unit-b0 form when the cascade has one (unit_form_ok), plain and with the epilogue: same cascade arithmetic in both
+    if (!F32 && variant == 4 && unit_ok) return {.LC = 64, .VEC = true, .MINW = 2, .EPI = fuse, .UNIT = true, .FFR = ffr};
+    if (fuse && LC == 32) return {.LC = 32, .VEC = true, .PF = true, .MINW = 2, .EPI = true};
+    if (fuse) return {.LC = 64, .VEC = true, .MINW = F32 ? 3 : 2, .EPI = true, .FFR = ffr};
+    switch (variant) {
+    case 0: return {.LC = 32, .VEC = true, .MINW = F32 ? 5 : 3};
+    case 1: return {.LC = 16, .VEC = true, .MINW = F32 ? 8 : 5};
+    case 2: return {.LC = 32, .VEC = true, .PF = true, .MINW = F32 ? 4 : 2};
+    case 3: return {.LC = 16, .VEC = true, .PF = true, .MINW = F32 ? 6 : 4};
+    case 4: return {.LC = 64, .VEC = true, .MINW = F32 ? 3 : 2, .FFR = ffr};      // 64 samples per lane: half the scan per sample
+    case 5: return {.LC = 64, .VEC = true, .PF = true, .MINW = F32 ? 3 : 1};
+    default: return {.LC = 0};                     // no such variant (sos_forward rejects the knob): in no list
+    }
 }
+
+// does `f` hold for the kernel of any input of sos_choose in this family (the knob: unset and 0 ... 5)
+template <typename F> constexpr bool sos_any_choice(SosFamily fam, F f)
+{
+    for (int in = 0; in < 32; ++in)
+        for (int knob = -1; knob <= 5; ++knob)
+            if (f(sos_choose(fam, in & 1, in & 2, in & 4, in & 8, in & 16, knob))) return true;
+    return false;
+}
+
+// A list of compiled instances: `launch` takes a runtime SosKernel to the instance equal to it.  `matches`: every kernel
+// sos_choose picks in `fam` is in the list, and every kernel of the list is picked (this file's compile time is its instances).
+template <SosKernel... Gs> struct SosKernels {
+    static constexpr bool has(SosKernel g) { return ((g == Gs) || ...); }
+    static constexpr bool matches(SosFamily fam)
+    {
+        return !sos_any_choice(fam, [](SosKernel g) { return !has(g); }) && (sos_any_choice(fam, [](SosKernel g) { return g == Gs; }) && ...);
+    }
+    template <typename TIn, typename TOut, typename TC>
+    static void launch(SosKernel g, const SosParams &p, const Epilogue *ep, int64_t plan_warm, hipStream_t stream)
+    {
+        const bool found = ((g == Gs && (launch_one<TIn, TOut, TC, Gs>(p, ep, plan_warm, stream), true)) || ...);
+        TFX_CHECK(found, "sos: no kernel instance LC=%d VEC=%d TAPS=%d PF=%d EPI=%d UNIT=%d FFR=%d", g.LC, g.VEC, g.TAPS, g.PF, g.EPI, g.UNIT, g.FFR);
+    }
+};
+
+template <bool F32, SosKernel... More> using SosMainKernels = SosKernels<
+    SosKernel{.LC = 32, .VEC = true, .MINW = F32 ? 5 : 3},                     // aligned rows: variants 0 ... 5
+    SosKernel{.LC = 16, .VEC = true, .MINW = F32 ? 8 : 5},
+    SosKernel{.LC = 32, .VEC = true, .PF = true, .MINW = F32 ? 4 : 2},
+    SosKernel{.LC = 16, .VEC = true, .PF = true, .MINW = F32 ? 6 : 4},
+    SosKernel{.LC = 64, .VEC = true, .MINW = F32 ? 3 : 2},
+    SosKernel{.LC = 64, .VEC = true, .PF = true, .MINW = F32 ? 3 : 1},
+    SosKernel{.LC = 32, .VEC = true, .PF = true, .MINW = 2, .EPI = true},       // ... with the epilogue: same tile geometry as
+    SosKernel{.LC = 64, .VEC = true, .MINW = F32 ? 3 : 2, .EPI = true},         //     the plain kernel (bit-identical cascade output)
+    SosKernel{.LC = 16, .MINW = F32 ? 5 : 3},                                   // unaligned rows
+    SosKernel{.LC = 32, .MINW = F32 ? 3 : 2},
+    SosKernel{.LC = 16, .TAPS = true, .MINW = F32 ? 5 : 3},                     // section taps (parity tests)
+    SosKernel{.LC = 32, .TAPS = true, .MINW = F32 ? 3 : 2},
+    SosKernel{.LC = 64, .VEC = true, .TAPS = true, .MINW = F32 ? 3 : 2},
+    More...>;
+using SosMainF64Kernels = SosMainKernels<false,
+    SosKernel{.LC = 64, .VEC = true, .MINW = 2, .UNIT = true},                  // unit-b0 form
+    SosKernel{.LC = 64, .VEC = true, .MINW = 2, .EPI = true, .UNIT = true},
+    SosKernel{.LC = 64, .VEC = true, .MINW = 2, .FFR = true},                   // refined start states
+    SosKernel{.LC = 64, .VEC = true, .MINW = 2, .EPI = true, .FFR = true},
+    SosKernel{.LC = 64, .VEC = true, .MINW = 2, .UNIT = true, .FFR = true},
+    SosKernel{.LC = 64, .VEC = true, .MINW = 2, .EPI = true, .UNIT = true, .FFR = true},
+    SosKernel{.LC = 32, .MINW = 2, .FFR = true},
+    SosKernel{.LC = 32, .TAPS = true, .MINW = 2, .FFR = true},
+    SosKernel{.LC = 64, .VEC = true, .TAPS = true, .MINW = 2, .FFR = true}>;
+using SosRareKernels = SosKernels<                                              // one list for the three type triples
+    SosKernel{.LC = 16, .VEC = true, .MINW = 4}, SosKernel{.LC = 16, .VEC = true, .MINW = 4, .FFR = true},
+    SosKernel{.LC = 16, .MINW = 3}, SosKernel{.LC = 16, .MINW = 3, .FFR = true},
+    SosKernel{.LC = 16, .TAPS = true, .MINW = 3}, SosKernel{.LC = 16, .TAPS = true, .MINW = 3, .FFR = true}>;
+template <SosKernel... More> using SosSumKernels = SosKernels<
+    SosKernel{.LC = 16, .VEC = true, .MINW = 3, .SUMB = true}, SosKernel{.LC = 16, .MINW = 3, .SUMB = true}, More...>;
+using SosSumF64Kernels = SosSumKernels<
+    SosKernel{.LC = 16, .VEC = true, .MINW = 3, .SUMB = true, .FFR = true}, SosKernel{.LC = 16, .MINW = 3, .SUMB = true, .FFR = true}>;
+
+static_assert(SosMainKernels<true>::matches(SosFamily::MainF32) && SosMainF64Kernels::matches(SosFamily::MainF64) &&
+              SosRareKernels::matches(SosFamily::Rare) && SosSumKernels<>::matches(SosFamily::SumF32) &&
+              SosSumF64Kernels::matches(SosFamily::SumF64), "sos_choose and a kernel list disagree: a chosen kernel is not compiled, or a compiled one is never chosen");
 
 // The coefficient checks every entry point shares: K sections per band in 1 ... 512 (the per-wave carry, 4 values per section,
 // lives in LDS next to the transposition stage), finite values, and -- where the caller's contract says so -- a0 = 1.
@@ -1611,22 +1628,14 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in,
     const bool rare = !(x_dtype == TFX_F32 && y_dtype == TFX_F32);
     const int xsz = x_dtype == TFX_F32 ? 4 : 8, ysz = y_dtype == TFX_F32 ? 4 : 8;
     const bool vec = (((uintptr_t)x & 15) == 0) && (((uintptr_t)y & 15) == 0) && ((T * xsz) % 16 == 0) && ((T * ysz) % 16 == 0);
-    int variant = resolve_variant(rare, sum_bands, prec, vec, ep->any(), (int)env_i64("TFX_SOS_VARIANT", -1));
-    int LC = variant >= 4 ? 64 : ((variant & 1) ? 16 : 32);
-    // Cascades whose lane scan costs the result accuracy (poles next to z = 1 under a rough output; plan_refine, decided per
-    // cascade and for the dtype of the result) take the refined kernels.  Those exist for the shipping geometry only: LC = 64
-    // on aligned rows, LC = 32 on the dword path; LC = 16 for the rare dtype mixes and the sum mode as before.  The decision
-    // is made at the tile size of that geometry -- the one the refined launch runs -- whatever TFX_SOS_VARIANT asks for: a
-    // variant with fewer samples per lane is never left unrefined where the shipping one is refined.  Every other cascade runs the kernel, and computes the bits, it did without this rule.
-    const int lc_rule = (rare || sum_bands) ? LC : (vec ? 64 : 32);
-    const bool refine = !f32 && plan_refine(pl, lc_rule, y_dtype == TFX_F64);
-    if (refine && !rare && !sum_bands) { variant = vec ? 4 : 0; LC = lc_rule; }
-    // fused into the kernel on the main path (float32 I/O, aligned rows, no taps, single cascade); everything
-    // else runs the plain kernel and the same arithmetic as separate passes over y
-    const bool ep_fused = ep->any() && !rare && !sum_bands && !y_sections && vec;
-    // the shipping float32-in / float32-out geometry (float64 arithmetic, LC = 64, aligned rows, no section taps) runs the
-    // unit-b0 form when the cascade has one (unit_form_ok); other cascades run the plain form
-    const bool unit = !f32 && variant == 4 && vec && !y_sections && !sum_bands && !rare && plan_unit_ok(pl);
+    TFX_CHECK(!sum_bands || x_dtype == y_dtype, "sos_forward: sum mode needs equal input and output dtypes");
+    const int64_t knob = env_i64("TFX_SOS_VARIANT", -1);
+    TFX_CHECK(knob <= 5, "sos_forward: TFX_SOS_VARIANT=%lld is outside 0 ... 5 (negative = unset)", (long long)knob);
+    const SosFamily fam = sum_bands ? (f32 ? SosFamily::SumF32 : SosFamily::SumF64)
+                        : rare ? SosFamily::Rare : (f32 ? SosFamily::MainF32 : SosFamily::MainF64);
+    const bool refine = !f32 && plan_refine(pl, sos_refine_lc(fam, vec), y_dtype == TFX_F64);
+    SosKernel G = sos_choose(fam, vec, y_sections != nullptr, ep->any(), refine, true, (int)knob);
+    if (G.UNIT && !plan_unit_ok(pl)) G = sos_choose(fam, vec, y_sections != nullptr, ep->any(), refine, false, (int)knob);
 
     SosParams p{};
     p.x = x; p.y = y; p.taps = y_sections;
@@ -1635,26 +1644,22 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in,
     p.nt = 1;
     p.fair = 15;
     p.nsum = sum_bands ? (int)NB : 0;
-    p.ep_gain = ep->gain; p.ep_scale = ep->scale; p.ep_clamp = ep->clamp; p.ep_stat = ep->stat_mode;
-    p.ep_partial = nullptr; p.ep_host = ep;
-    p.ep_fused = ep_fused ? 1 : 0;
-    if (!ep_fused) { p.ep_scale = p.ep_clamp = 0; p.ep_stat = -1; }
-    p.refine = refine ? 1 : 0;
-    table_for(p, pl, f32, LC, unit);
+    p.ep_stat = -1;
+    // the epilogue runs in the kernels that have it; everything else runs the plain kernel and the same arithmetic as
+    // separate passes over y
+    if (G.EPI) { p.ep_gain = ep->gain; p.ep_scale = ep->scale; p.ep_clamp = ep->clamp; p.ep_stat = ep->stat_mode; }
+    table_for(p, pl, f32, G);
 
     const int64_t warm = pl->warm;         // segmentation is decided per kernel instance (launch_one)
-    if (f32) {
-        if (sum_bands) launch_sum<float, float, float>(p, vec, warm, stream);
-        else launch_main<float, float, float>(p, vec, variant, warm, stream);
-    } else if (sum_bands) {
-        if (x_dtype == TFX_F32 && y_dtype == TFX_F32) launch_sum<float, float, double>(p, vec, warm, stream);
-        else if (x_dtype == TFX_F64 && y_dtype == TFX_F64) launch_sum<double, double, double>(p, vec, warm, stream);
-        else TFX_CHECK(false, "sos_forward: sum mode needs equal input and output dtypes");
-    } else if (!rare) launch_main<float, float, double>(p, vec, variant, warm, stream);
-    else if (x_dtype == TFX_F32) launch_rare<float, double, double>(p, vec, warm, stream);
-    else if (y_dtype == TFX_F32) launch_rare<double, float, double>(p, vec, warm, stream);
-    else launch_rare<double, double, double>(p, vec, warm, stream);
-    if (ep->any() && !ep_fused) epilogue_as_passes(y, y_dtype, C, T, *ep, stream);
+    if (fam == SosFamily::MainF32) SosMainKernels<true>::launch<float, float, float>(G, p, ep, warm, stream);
+    else if (fam == SosFamily::MainF64) SosMainF64Kernels::launch<float, float, double>(G, p, ep, warm, stream);
+    else if (fam == SosFamily::SumF32) SosSumKernels<>::launch<float, float, float>(G, p, ep, warm, stream);
+    else if (fam == SosFamily::SumF64 && x_dtype == TFX_F32) SosSumF64Kernels::launch<float, float, double>(G, p, ep, warm, stream);
+    else if (fam == SosFamily::SumF64) SosSumF64Kernels::launch<double, double, double>(G, p, ep, warm, stream);
+    else if (x_dtype == TFX_F32) SosRareKernels::launch<float, double, double>(G, p, ep, warm, stream);
+    else if (y_dtype == TFX_F32) SosRareKernels::launch<double, float, double>(G, p, ep, warm, stream);
+    else SosRareKernels::launch<double, double, double>(G, p, ep, warm, stream);
+    if (ep->any() && !G.EPI) epilogue_as_passes(y, y_dtype, C, T, *ep, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1731,12 +1736,6 @@ void sos_filtfilt_plan_info(int64_t C, int64_t T, const double *sos_host, int64_
     if (nseg_reverse) *nseg_reverse = p.nseg;
 }
 
-template <typename TIn, typename TOut, int FF, bool FFR>
-static void filtfilt_launch(const SosParams &p, int64_t plan_warm, hipStream_t stream)
-{
-    launch_one<TIn, TOut, double, FF_LC, false, false, false, 2, false, false, false, FF, FFR>(p, plan_warm, stream);
-}
-
 void sos_filtfilt_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C, int64_t T, const double *sos_host, int64_t K,
                           int padtype, int64_t padlen, double *work, hipStream_t stream)
 {
@@ -1754,18 +1753,16 @@ void sos_filtfilt_forward(const void *x, int x_dtype, void *y, int y_dtype, int6
         if (!pl->ff_gain) pl->ff_gain = std::make_unique<DeviceBuffer>(gains);
     }
     SosParams p = filtfilt_params(1, C, T, K, padtype, pad);
-    table_for(p, pl, false, FF_LC);
+    const bool f64_result = y_dtype == TFX_F64;
+    table_for(p, pl, false, ff_kernel(1, f64_result));     // (the two passes read the same table: same LC, same form)
     p.ff_gain = (const double *)pl->ff_gain->p;
     p.x = x; p.y = work;
-    // a float64 result takes the refined start states in both passes; a float32 result is 20 times inside its bar without
-    const bool refine = y_dtype == TFX_F64;
-    if (x_dtype == TFX_F32 && !refine) filtfilt_launch<float, double, 1, false>(p, pl->warm, stream);
-    else if (x_dtype == TFX_F32) filtfilt_launch<float, double, 1, true>(p, pl->warm, stream);
-    else if (!refine) filtfilt_launch<double, double, 1, false>(p, pl->warm, stream);
-    else filtfilt_launch<double, double, 1, true>(p, pl->warm, stream);
+    using Forward = SosKernels<ff_kernel(1, false), ff_kernel(1, true)>;
+    if (x_dtype == TFX_F32) Forward::launch<float, double, double>(ff_kernel(1, f64_result), p, nullptr, pl->warm, stream);
+    else Forward::launch<double, double, double>(ff_kernel(1, f64_result), p, nullptr, pl->warm, stream);
     p.ff = 2; p.x = work; p.y = y; p.x_pitch = p.T;
-    if (y_dtype == TFX_F32) filtfilt_launch<double, float, 2, false>(p, pl->warm, stream);
-    else filtfilt_launch<double, double, 2, true>(p, pl->warm, stream);
+    if (f64_result) launch_one<double, double, double, ff_kernel(2, true)>(p, nullptr, pl->warm, stream);
+    else launch_one<double, float, double, ff_kernel(2, false)>(p, nullptr, pl->warm, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1782,6 +1779,7 @@ void sos_filtfilt_forward(const void *x, int x_dtype, void *y, int y_dtype, int6
 // which fills the part either way, 0.258 / 0.242 / 0.28: 4 x is the shortest that costs the full part nothing.
 // ------------------------------------------------------------------------------------------
 constexpr int MS_LC = 32;
+constexpr SosKernel ms_kernel(bool refine) { return {.LC = MS_LC, .FFR = refine, .MEAS = true}; }
 constexpr int64_t MS_STREAMS = 2048;
 constexpr int64_t MS_SEQ_MAX = (int64_t)1 << 24;       // longest row one wavefront is asked to walk alone
 
@@ -1832,8 +1830,10 @@ void sos_block_energy_forward(const void *x, int x_dtype, double *s, int64_t C, 
     TFX_CHECK(x && s, "sos_block_energy: null signal or result pointer");
     const std::shared_ptr<SosPlan> plan = get_plan(sos_host, K, stream, 1);      // held until the launches are enqueued
     SosPlan *pl = plan.get();
+    // the energies are float64 results: a cascade whose lane scan costs more than the float64 recursion itself refines it
+    const SosKernel G = ms_kernel(plan_refine(pl, MS_LC, true));
     SosParams p{};
-    table_for(p, pl, false, MS_LC);
+    table_for(p, pl, false, G);
     p.x = x; p.y = s;
     p.C = C; p.C_in = C; p.T = T; p.K = (int)K; p.x_pitch = T;
     p.nseg = bp.nseg; p.warm = bp.warm;
@@ -1841,12 +1841,9 @@ void sos_block_energy_forward(const void *x, int x_dtype, double *s, int64_t C, 
     p.ep_stat = -1;
     p.ms_num = num; p.ms_den = den; p.ms_nblk = bp.nblk; p.ms_bps = bp.bps;
     // the segmentation above is final (block_energy_plan): launch_one takes it as it is
-    // the energies are float64 results: a cascade whose lane scan costs more than the float64 recursion itself refines it
-    if (plan_refine(pl, MS_LC, true)) {
-        if (x_dtype == TFX_F32) launch_one<float, float, double, MS_LC, false, false, false, 2, false, false, false, 0, true, true>(p, pl->warm, stream);
-        else launch_one<double, double, double, MS_LC, false, false, false, 2, false, false, false, 0, true, true>(p, pl->warm, stream);
-    } else if (x_dtype == TFX_F32) launch_one<float, float, double, MS_LC, false, false, false, 2, false, false, false, 0, false, true>(p, pl->warm, stream);
-    else launch_one<double, double, double, MS_LC, false, false, false, 2, false, false, false, 0, false, true>(p, pl->warm, stream);
+    using Measuring = SosKernels<ms_kernel(false), ms_kernel(true)>;
+    if (x_dtype == TFX_F32) Measuring::launch<float, float, double>(G, p, nullptr, pl->warm, stream);
+    else Measuring::launch<double, double, double>(G, p, nullptr, pl->warm, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1872,10 +1869,10 @@ struct ChunkParams {
     int scale, clamp;
 };
 
+constexpr SosKernel chunk_kernel(bool vec) { return {.LC = 16, .VEC = vec}; }     // the cascade inside the chunk kernel (body alone)
 template <typename TC, bool VEC>
 __global__ void __launch_bounds__(1024) chunk_iir_fir_kernel(const ChunkParams q)
 {
-    constexpr int LC = 16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, nthr = blockDim.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1901,7 +1898,7 @@ __global__ void __launch_bounds__(1024) chunk_iir_fir_kernel(const ChunkParams q
         SosParams p = q.sos;
         p.y = (void *)(u - c * (int64_t)T);                // the body stores row c at y + c * T
         p.C_in = p.C;
-        sos_stream_body<float, float, TC, LC, VEC, false, false, false, false>(p, c, stage, lane);
+        sos_stream_body<float, float, TC, chunk_kernel(VEC)>(p, c, stage, lane);
     }
     __syncthreads();
     // direct form, float32 FMA in tap order (as fir_direct_simple_kernel): y[n] = sum_k kp[k] * ubuf[n + k].  A thread owns
@@ -1980,7 +1977,7 @@ void chunk_forward(const float *x, int64_t x_pitch, float *y, int64_t C, int64_t
         plan = get_plan(sos_host, K, stream, 1);
         SosPlan *pl = plan.get();
         if (prec == TFX_PREC_AUTO) prec = (plan_err_bound(pl) <= auto_bound()) ? TFX_PREC_F32 : TFX_PREC_F64;
-        table_for(p, pl, prec == TFX_PREC_F32, 16);
+        table_for(p, pl, prec == TFX_PREC_F32, chunk_kernel(false));     // (the table does not depend on VEC)
     }
     const int H = (int)Kf - 1, Hpad = (H + 3) & ~3, Kp = Hpad + 4;
     {   // device taps in the kernel's layout: Hpad - H leading zeros (they meet the zero-filled front of the LDS buffer),
@@ -1995,7 +1992,8 @@ void chunk_forward(const float *x, int64_t x_pitch, float *y, int64_t C, int64_t
     q.gain = (float)gain; q.scale = scale; q.clamp = clamp;
     const bool vec = (((uintptr_t)x & 15) == 0) && (T % 4 == 0) && (x_pitch % 4 == 0);
     const bool f32 = prec == TFX_PREC_F32;
-    const size_t stage_b = K == 0 ? 0 : (size_t)(f32 ? sos_wave_lds_bytes<float, float, float, 16>(1, (int)K) : sos_wave_lds_bytes<float, float, double, 16>(1, (int)K));
+    constexpr int LC = chunk_kernel(false).LC;
+    const size_t stage_b = K == 0 ? 0 : (size_t)(f32 ? sos_wave_lds_bytes<float, float, float, LC>(1, (int)K) : sos_wave_lds_bytes<float, float, double, LC>(1, (int)K));
     const size_t shmem = (size_t)(Hpad + q.Tpad + 8 + Kp) * 4 + stage_b;
     TFX_CHECK(shmem <= 64 * 1024, "chunk_forward: needs %zu B of LDS", shmem);
     // the cascade is one wavefront's work; the FIR phase scales with the threads: 4 outputs each
