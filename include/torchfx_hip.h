@@ -462,6 +462,13 @@ int tfx_resample_forward(const void *x, void *y, int dtype, int64_t rows, int64_
  * taps through the cache, 2 = gather: the window does not fit in LDS, 3 = copy: up == down) and its LDS bytes per workgroup */
 int tfx_resample_plan_info(int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int64_t *n_out, int64_t *n_pre_remove,
                            int64_t *padded, int64_t *Lp, int *kernel, int64_t *lds_bytes);
+/* the workgroup geometry of that launch (host-only, same arguments and checks): the kernel (as above), G phase groups of `up`
+ * threads per workgroup and G_initial, the count before it was halved until the tile's window fit in LDS; E outputs per thread;
+ * tile_out = up * G * E outputs per workgroup (tile k starts at output k * tile_out); span, the input samples of a tile's
+ * window (0 for the gather kernel, which stages none); LP, the taps per phase a thread runs (Lp rounded up to 8, 16, 24, 32,
+ * 48 or 64 with zero taps for kernel 0, else Lp) and tiles = ceil(n_out / tile_out) workgroups per row.  All 0 for the copy. */
+int tfx_resample_tiling_info(int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int *kernel, int64_t *G, int64_t *G_initial,
+                             int64_t *E, int64_t *tile_out, int64_t *span, int64_t *LP, int64_t *tiles);
 /* ---------------------------------------------------------------------------
  * tfx_resample_stream_forward -- one chunk of tfx_resample_forward over a continuous stream, in ONE launch.  The stream fixes
  * (up, down reduced by their gcd) n_pre_pad and n_pre_remove as above and Lp_s = ceil((nh + n_pre_pad) / up) taps per phase.

@@ -100,13 +100,24 @@ def test_misaligned_and_strided_rows(dtype):
 @pytest.mark.parametrize("up,down,dtype,kernel", [
     (160, 147, torch.float32, "resample_stream_reg_kernel"), (997, 1000, torch.float64, "resample_stream_reg_kernel"),
     (1, 6, torch.float32, "resample_stream_lds_kernel"), (1, 480, torch.float32, "resample_stream_lds_kernel"),
-    (1, 480, torch.float64, "resample_stream_gather_kernel"), (1, 8000, torch.float32, "resample_stream_gather_kernel")])
+    (1, 480, torch.float64, "resample_stream_gather_kernel"), (1, 8000, torch.float32, "resample_stream_gather_kernel"),
+    # more than one phase in the gather kernel (most 512-sample chunks complete no output: the history-only launch), G halved
+    # to an odd count in the lds kernel, G halved in the reg kernel (the 41-tap window of tests/test_gpu_resample_edges.py)
+    (3, 4000, torch.float32, "resample_stream_gather_kernel"), (3, 200, torch.float32, "resample_stream_lds_kernel"),
+    (3, 200, torch.float64, "resample_stream_lds_kernel"), (2, 75, torch.float32, "resample_stream_reg_kernel")])
 def test_each_kernel(up, down, dtype, kernel):
-    r = stateful(up, down)
+    kw = {}
+    if (up, down) == (2, 75):
+        from tests.test_gpu_resample_edges import CASES, window_of
+        kw["window"] = window_of(next(c for c in CASES if (c.up, c.down) == (2, 75)))
+        assert len(kw["window"]) == 41
+    r = stateful(up, down, **kw)
     T = 200_000 if down >= 480 else 50_000
     x = signal((2, T), dtype, up + down)
     assert r.route(x, 4096) == f"native ({kernel})"
-    assert torch.equal(chunked(r, x, [512] * 20 + random_sizes(T, 3, 30000)), one_shot(x, up, down))
+    # a stream tile of these short chunks is up * G outputs (E halved down to 1): 3 at 3/4000, at most 129 at 3/200 and 256 at
+    # 2/75, so the rows (150, 750 and 1334 outputs) and the longest chunks span several tiles
+    assert torch.equal(chunked(r, x, [512] * 20 + random_sizes(T, 3, 30000)), one_shot(x, up, down, **kw))
 
 
 def _poisoned(x_len, bad, up, down, h):

@@ -73,6 +73,7 @@ SIGNATURES = {
     "tfx_resample_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
     "tfx_resample_plan_info": (_int, [_i64, _i64, _i64, _i64, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                       ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_int), ctypes.POINTER(_i64)]),
+    "tfx_resample_tiling_info": (_int, [_i64, _i64, _i64, _i64, _int, ctypes.POINTER(_int)] + [ctypes.POINTER(_i64)] * 7),
     "tfx_resample_stream_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     "tfx_resample_stream_plan_info": (_int, [_i64, _i64, _i64, _i64, _i64, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                              ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),

@@ -590,6 +590,15 @@ int tfx_resample_plan_info(int64_t T, int64_t up, int64_t down, int64_t nh, int 
     TFX_API_END
 }
 
+int tfx_resample_tiling_info(int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int *kernel, int64_t *G, int64_t *G_initial,
+                             int64_t *E, int64_t *tile_out, int64_t *span, int64_t *LP, int64_t *tiles)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(kernel && G && G_initial && E && tile_out && span && LP && tiles, "resample_tiling_info: null output");
+    resample_tiling_info(T, up, down, nh, dtype, kernel, G, G_initial, E, tile_out, span, LP, tiles);
+    TFX_API_END
+}
+
 int tfx_resample_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
                                 const void *taps_host, int64_t nh, int64_t consumed, const void *hist_in, void *hist_out,
                                 tfx_stream_t stream)

@@ -33,6 +33,7 @@ enum { RS_REG = 0, RS_LDS = 1, RS_GATHER = 2, RS_COPY = 3 };
 struct ResampleTiling {
     int kernel;
     int64_t G, E, span, tile_out, lds;
+    int64_t G0;                 // G before the halving loop (tfx_resample_tiling_info reports it; no launch reads it)
     int64_t LP;                 // REG: taps held in registers (Lp rounded up to a bucket), else Lp
 };
 
@@ -49,7 +50,7 @@ static ResampleTiling resample_tiling(int64_t up, int64_t down, int64_t pre, int
         return t;
     }
     const int64_t cap = RS_LDS_BYTES / esz;
-    t.G = up >= RS_THREADS ? 1 : RS_THREADS / up;
+    t.G = t.G0 = up >= RS_THREADS ? 1 : RS_THREADS / up;
     t.LP = reg_bucket(Lp) ? reg_bucket(Lp) : Lp;              // the window reaches LP - 1 inputs behind the first output
     while (t.G > 1 && window_span(up, down, pre, t.LP, t.G, 1) > cap) t.G = (t.G + 1) / 2;
     const int64_t s1 = window_span(up, down, pre, t.LP, t.G, 1);
@@ -230,6 +231,26 @@ void resample_plan_info(int64_t T, int64_t up, int64_t down, int64_t nh, int dty
     *Lp = g.Lp;
     *kernel = t.kernel;
     *lds_bytes = t.lds;
+}
+
+// host-only: the workgroup geometry of that launch, from the same resample_plan() call (span is 0 for GATHER, which stages no
+// window; everything is 0 for the copy of up == down)
+void resample_tiling_info(int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int *kernel, int64_t *G, int64_t *G_initial,
+                          int64_t *E, int64_t *tile_out, int64_t *span, int64_t *LP, int64_t *tiles)
+{
+    const int one = 1;
+    resample_check(&one, &one, dtype, 1, T, up, down, &one, nh);
+    ResampleGeom g;
+    ResampleTiling t;
+    resample_plan(T, up, down, nh, dtype == TFX_F32 ? 4 : 8, &g, &t);
+    *kernel = t.kernel;
+    *G = t.G;
+    *G_initial = t.G0;
+    *E = t.E;
+    *tile_out = t.tile_out;
+    *span = t.span;
+    *LP = t.LP;
+    *tiles = t.tile_out ? ceil_div(g.n_out, t.tile_out) : 0;
 }
 
 // polyphase tables by content: the taps' bytes plus (up, down, dtype, n_pre_pad, Lp).  A stream's table has Lp_s taps per phase,

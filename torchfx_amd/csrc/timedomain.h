@@ -49,6 +49,8 @@ void resample_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T
                       int64_t nh, hipStream_t stream);
 void resample_plan_info(int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int64_t *n_out, int64_t *pre_remove,
                         int64_t *padded, int64_t *Lp, int *kernel, int64_t *lds_bytes);
+void resample_tiling_info(int64_t T, int64_t up, int64_t down, int64_t nh, int dtype, int *kernel, int64_t *G, int64_t *G_initial,
+                          int64_t *E, int64_t *tile_out, int64_t *span, int64_t *LP, int64_t *tiles);
 void resample_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
                              const void *taps_host, int64_t nh, int64_t consumed, const void *hist_in, void *hist_out,
                              hipStream_t stream);

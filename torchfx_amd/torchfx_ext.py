@@ -34,7 +34,7 @@ from torchfx_amd import native
 __all__ = [
     "biquad_forward", "sos_forward", "sos_bank_forward", "sos_bank_sum_forward", "delay_line_forward", "delay_forward",
     "delay_amplitudes", "delay_regime", "delay_stream_forward", "delay_line_stream_forward", "resample_forward",
-    "resample_plan_info", "resample_stream_forward", "resample_stream_plan_info", "sos_filtfilt", "sos_filtfilt_plan_info",
+    "resample_plan_info", "resample_tiling_info", "resample_stream_forward", "resample_stream_plan_info", "sos_filtfilt", "sos_filtfilt_plan_info",
     "sos_block_energy", "sos_block_energy_plan_info", "true_peak", "true_peak_plan_info", "limiter_forward", "limiter_plan_info",
     "limiter_stream_forward", "limiter_stream_plan_info", "compressor_forward", "compressor_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
@@ -203,6 +203,17 @@ def resample_plan_info(length: int, up: int, down: int, taps: int, dtype: torch.
     phase), ``kernel`` and ``lds_bytes`` per workgroup."""
     q = _query(L.load().tfx_resample_plan_info, (int(length), int(up), int(down), int(taps), _dt(dtype)),
                "n_out n_pre_remove padded Lp kernel:int lds_bytes")
+    q["kernel"] = RESAMPLE_KERNELS[q["kernel"]]
+    return q
+
+
+def resample_tiling_info(length: int, up: int, down: int, taps: int, dtype: torch.dtype = torch.float32) -> dict:
+    """The workgroup geometry of that launch (``tfx_resample_tiling_info``; host-only, same checks): ``kernel``, ``G`` phase
+    groups of ``up`` threads and ``G_initial`` (before the halving that makes a tile's window fit in LDS), ``E`` outputs per
+    thread, ``tile_out = up * G * E`` outputs per workgroup, ``span`` (inputs in a tile's window; 0 for the gather kernel),
+    ``LP`` (taps per phase a thread runs: ``Lp`` rounded up to a register bucket for the reg kernel) and ``tiles`` per row."""
+    q = _query(L.load().tfx_resample_tiling_info, (int(length), int(up), int(down), int(taps), _dt(dtype)),
+               "kernel:int G G_initial E tile_out span LP tiles")
     q["kernel"] = RESAMPLE_KERNELS[q["kernel"]]
     return q
 
