@@ -443,6 +443,15 @@ int tfx_delay_line_stream_forward(const void *x, void *y, int dtype, int64_t C, 
 /* the kernel tfx_delay_forward picks (host-only): 0 = span (taps*delay + tile staged in LDS), 1 = lattice (long delay,
  * taps <= 8, residue classes with a register ring), 2 = gather (anything else, every tap a global load) */
 int tfx_delay_plan_info(int64_t delay, int64_t taps, int dtype, int pingpong, int *regime);
+/* the workgroup geometry of tfx_delay_forward on [rows, T] (host-only; the size checks of tfx_delay_forward; the launch fills
+ * its kernel arguments from the same plan): the regime (as above); units = rows (gather) or rows / pairs (span, lattice; a
+ * ping-pong pair is one unit); tiles = ceil(L / 1024) output tiles per row, L = T + taps*delay (span, gather), or
+ * ceil(delay / 256) residue blocks of 256 lanes (lattice); kc and nchunks, lattice only (else 0): the ceil(L / delay) steps of a
+ * row are cut into nchunks chunks of kc steps (128, halved down to 16 while the grid has fewer than 4096 workgroups), chunk c
+ * owning outputs [c*kc*delay, (c+1)*kc*delay); groups = workgroups per unit (tiles, or tiles*nchunks) = the first-level
+ * partials of an epilogue statistic per unit; nwg = units*groups (0: nothing to launch); lds_bytes per workgroup (span). */
+int tfx_delay_tiling_info(int64_t rows, int64_t T, int64_t delay, int64_t taps, int dtype, int pingpong, int *regime, int64_t *units,
+                          int64_t *tiles, int64_t *kc, int64_t *nchunks, int64_t *groups, int64_t *nwg, int64_t *lds_bytes);
 
 /* ---------------------------------------------------------------------------
  * tfx_resample_forward -- polyphase rational resampling along each row, scipy.signal.resample_poly(x, up, down, axis=-1,

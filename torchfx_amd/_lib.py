@@ -70,6 +70,7 @@ SIGNATURES = {
     "tfx_delay_stream_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _vp, _dbl, _int, _vp, _vp, _vp]),
     "tfx_delay_line_stream_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _dbl, _dbl, _vp, _vp, _vp]),
     "tfx_delay_plan_info": (_int, [_i64, _i64, _int, _int, ctypes.POINTER(_int)]),
+    "tfx_delay_tiling_info": (_int, [_i64, _i64, _i64, _i64, _int, _int, ctypes.POINTER(_int)] + [ctypes.POINTER(_i64)] * 7),
     "tfx_resample_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
     "tfx_resample_plan_info": (_int, [_i64, _i64, _i64, _i64, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                       ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_int), ctypes.POINTER(_i64)]),

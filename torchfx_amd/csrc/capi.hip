@@ -573,6 +573,15 @@ int tfx_delay_plan_info(int64_t delay, int64_t taps, int dtype, int pingpong, in
     TFX_API_END
 }
 
+int tfx_delay_tiling_info(int64_t rows, int64_t T, int64_t delay, int64_t taps, int dtype, int pingpong, int *regime, int64_t *units,
+                          int64_t *tiles, int64_t *kc, int64_t *nchunks, int64_t *groups, int64_t *nwg, int64_t *lds_bytes)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(regime && units && tiles && kc && nchunks && groups && nwg && lds_bytes, "delay_tiling_info: null output");
+    delay_tiling_info(rows, T, delay, taps, dtype, pingpong, regime, units, tiles, kc, nchunks, groups, nwg, lds_bytes);
+    TFX_API_END
+}
+
 int tfx_resample_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t up, int64_t down,
                          const void *taps_host, int64_t nh, tfx_stream_t stream)
 {

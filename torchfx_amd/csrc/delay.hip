@@ -182,6 +182,8 @@ __global__ void __launch_bounds__(DLY_THREADS) delay_gather_kernel(const DelayAr
             const int64_t over = n - p.T_ + 1;                       // i*D >= over
             if (over > 0) i_lo = (over + p.D - 1) / p.D > 1 ? (over + p.D - 1) / p.D : 1;
         } else if (n >= p.T_) {
+            // unreachable from delay_forward: D = 0 gives taps*D = 0, which delay_regime always sends to SPAN.  Kept so that
+            // the kernel stays correct for any D on its own, and so that its instructions are the ones already measured.
             i_hi = 0;
         }
         T wet = (T)0;
@@ -278,20 +280,60 @@ int delay_regime(int64_t D, int64_t taps, int esz, int pingpong)
     return fits ? DLY_SPAN : DLY_GATHER;
 }
 
+// the checks that need no pointer: delay_forward and the host-only delay_tiling_info share them
+static void delay_check_sizes(const char *who, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps, int pingpong)
+{
+    TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "%s: bad dtype %d", who, dtype);
+    TFX_CHECK(taps >= 1, "%s: taps must be at least 1, got %lld", who, (long long)taps);
+    TFX_CHECK(delay >= 0, "%s: negative delay %lld", who, (long long)delay);
+    TFX_CHECK(rows >= 0 && T >= 0, "%s: negative size", who);
+    TFX_CHECK(!pingpong || rows % 2 == 0, "%s: ping-pong needs an even number of rows, got %lld", who, (long long)rows);
+    TFX_CHECK(delay == 0 || taps <= (INT64_MAX / 2 - T) / delay, "%s: T + taps*delay overflows", who);
+}
+
 static void delay_check(const void *x, const void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
                         const double *amps_host, double mix, int pingpong, const Epilogue *ep)
 {
-    TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "delay_forward: bad dtype %d", dtype);
-    TFX_CHECK(taps >= 1, "delay_forward: taps must be at least 1, got %lld", (long long)taps);
-    TFX_CHECK(delay >= 0, "delay_forward: negative delay %lld", (long long)delay);
-    TFX_CHECK(rows >= 0 && T >= 0, "delay_forward: negative size");
-    TFX_CHECK(!pingpong || rows % 2 == 0, "delay_forward: ping-pong needs an even number of rows, got %lld", (long long)rows);
+    delay_check_sizes("delay_forward", dtype, rows, T, delay, taps, pingpong);
     TFX_CHECK(amps_host, "delay_forward: null amplitudes");
-    TFX_CHECK(delay == 0 || taps <= (INT64_MAX / 2 - T) / delay, "delay_forward: T + taps*delay overflows");
     TFX_CHECK(mix == mix, "delay_forward: NaN mix");
     const int64_t L = T + taps * delay;
     TFX_CHECK((x || rows * T == 0) && (y || rows * L == 0), "delay_forward: null pointer");
     TFX_CHECK(!ep || ep->stat_mode < 0 || ep->stat_out, "delay_forward: statistic requested without an output buffer");
+}
+
+// The geometry of one launch.  LATTICE: `tiles` residue blocks of 256 lanes, the ceil(L / D) steps of a row cut into chunks of
+// kc = 128 steps, halved down to 16 while the grid has fewer than 4096 workgroups.  SPAN / GATHER: tiles of DLY_TILE outputs.
+DelayPlan delay_plan(int64_t rows, int64_t T, int64_t D, int64_t taps, int esz, int pingpong)
+{
+    DelayPlan q{};
+    const int64_t ru = pingpong ? 2 : 1, L = T + taps * D;
+    q.regime = delay_regime(D, taps, esz, pingpong);
+    if (q.regime == DLY_LATTICE) {
+        q.units = rows / ru;
+        q.tiles = ceil_div(D, (int64_t)DLY_THREADS);
+        const int64_t ksteps = ceil_div(L, D);
+        q.kc = 128;
+        while (q.kc > 16 && q.units * q.tiles * ceil_div(ksteps, q.kc) < 4096) q.kc /= 2;
+        q.nchunks = ceil_div(ksteps, q.kc);
+        q.groups = q.tiles * q.nchunks;
+    } else {
+        q.units = q.regime == DLY_SPAN ? rows / ru : rows;
+        q.tiles = ceil_div(L, DLY_TILE);
+        q.groups = q.tiles;
+        if (q.regime == DLY_SPAN) q.lds_bytes = ru * (taps * D + DLY_TILE) * esz;
+    }
+    q.nwg = q.units * q.groups;
+    return q;
+}
+
+void delay_tiling_info(int64_t rows, int64_t T, int64_t delay, int64_t taps, int dtype, int pingpong, int *regime, int64_t *units,
+                       int64_t *tiles, int64_t *kc, int64_t *nchunks, int64_t *groups, int64_t *nwg, int64_t *lds_bytes)
+{
+    delay_check_sizes("delay_tiling_info", dtype, rows, T, delay, taps, pingpong);
+    const DelayPlan q = delay_plan(rows, T, delay, taps, dtype == TFX_F32 ? 4 : 8, pingpong != 0);
+    *regime = q.regime; *units = q.units; *tiles = q.tiles; *kc = q.kc; *nchunks = q.nchunks; *groups = q.groups; *nwg = q.nwg;
+    *lds_bytes = q.lds_bytes;
 }
 
 // amplitude tables beyond the kernel arguments, by content
@@ -314,23 +356,10 @@ static void delay_launch(const void *x, void *y, int64_t rows, int64_t T_, int64
     } else {
         for (int64_t i = 0; i < taps; ++i) p.a[i] = amps_host[i];
     }
-    const int regime = delay_regime(D, taps, esz, pingpong);
-    size_t lds = 0;
-    if (regime == DLY_LATTICE) {
-        p.units = rows / ru;
-        p.tiles = ceil_div(D, (int64_t)DLY_THREADS);
-        const int64_t ksteps = ceil_div(p.L, D);
-        p.kc = 128;
-        while (p.kc > 16 && p.units * p.tiles * ceil_div(ksteps, p.kc) < 4096) p.kc /= 2;
-        p.nchunks = ceil_div(ksteps, p.kc);
-        p.groups = p.tiles * p.nchunks;
-    } else {
-        p.units = regime == DLY_SPAN ? rows / ru : rows;
-        p.tiles = ceil_div(p.L, DLY_TILE);
-        p.groups = p.tiles;
-        if (regime == DLY_SPAN) lds = (size_t)(ru * (taps * D + DLY_TILE) * esz);
-    }
-    p.nwg = p.units * p.groups;
+    const DelayPlan q = delay_plan(rows, T_, D, taps, esz, pingpong);
+    const int regime = q.regime;
+    const size_t lds = (size_t)q.lds_bytes;
+    p.units = q.units; p.tiles = q.tiles; p.kc = q.kc; p.nchunks = q.nchunks; p.groups = q.groups; p.nwg = q.nwg;
     TFX_CHECK(p.nwg < (1ll << 31), "delay_forward: grid too large");
     if (ep.stat_mode >= 0)
         p.partial = (double *)scratch("delay_partial", (size_t)(p.nwg * (ep.per_row ? ru : 1)) * sizeof(double), stream);

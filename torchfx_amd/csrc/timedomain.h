@@ -42,6 +42,19 @@ void delay_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, i
 void delay_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t delay, int64_t taps,
                           const double *amps_host, double mix, int pingpong, const void *hist_in, void *hist_out, hipStream_t stream);
 int delay_regime(int64_t D, int64_t taps, int esz, int pingpong);
+// the geometry of one delay_forward launch (host-only; delay_launch fills its kernel arguments from it)
+struct DelayPlan {
+    int regime;
+    int64_t units;              // rows (GATHER) or rows / pairs (SPAN, LATTICE)
+    int64_t tiles;              // SPAN / GATHER: output tiles per row;  LATTICE: residue blocks per row
+    int64_t kc, nchunks;        // LATTICE: k steps per chunk, chunks per residue block;  0 otherwise
+    int64_t groups;             // workgroups per unit
+    int64_t nwg;                // workgroups in the grid (0: nothing is launched)
+    int64_t lds_bytes;          // SPAN: dynamic LDS per workgroup;  0 otherwise
+};
+DelayPlan delay_plan(int64_t rows, int64_t T, int64_t D, int64_t taps, int esz, int pingpong);
+void delay_tiling_info(int64_t rows, int64_t T, int64_t delay, int64_t taps, int dtype, int pingpong, int *regime, int64_t *units,
+                       int64_t *tiles, int64_t *kc, int64_t *nchunks, int64_t *groups, int64_t *nwg, int64_t *lds_bytes);
 void delay_clear();
 
 // ---- resample.hip (the polyphase table its users share: polyphase.h) ----

@@ -33,7 +33,7 @@ from torchfx_amd import native
 
 __all__ = [
     "biquad_forward", "sos_forward", "sos_bank_forward", "sos_bank_sum_forward", "delay_line_forward", "delay_forward",
-    "delay_amplitudes", "delay_regime", "delay_stream_forward", "delay_line_stream_forward", "resample_forward",
+    "delay_amplitudes", "delay_regime", "delay_tiling_info", "delay_stream_forward", "delay_line_stream_forward", "resample_forward",
     "resample_plan_info", "resample_tiling_info", "resample_stream_forward", "resample_stream_plan_info", "sos_filtfilt", "sos_filtfilt_plan_info",
     "sos_block_energy", "sos_block_energy_plan_info", "true_peak", "true_peak_plan_info", "limiter_forward", "limiter_plan_info",
     "limiter_stream_forward", "limiter_stream_plan_info", "compressor_forward", "compressor_plan_info",
@@ -186,6 +186,19 @@ def delay_regime(delay_samples: int, taps: int, dtype: torch.dtype = torch.float
     "lattice" (long delay, residue classes with the last taps in registers) or "gather"."""
     q = _query(L.load().tfx_delay_plan_info, (int(delay_samples), int(taps), _dt(dtype), int(bool(pingpong))), "regime:int")
     return DELAY_REGIMES[q["regime"]]
+
+
+def delay_tiling_info(rows: int, length: int, delay_samples: int, taps: int, dtype: torch.dtype = torch.float32,
+                      pingpong: bool = False) -> dict:
+    """The workgroup geometry of :func:`delay_forward` on ``[rows, length]`` (``tfx_delay_tiling_info``; host-only, the launch's
+    own plan): ``regime``, ``units`` (rows, or pairs / rows of a span or lattice launch), ``tiles`` (1024-sample output tiles
+    per row; lattice: blocks of 256 residues), ``kc`` steps per chunk and ``nchunks`` chunks (lattice; else 0), ``groups``
+    workgroups per unit, ``nwg`` in the grid and ``lds_bytes`` per workgroup."""
+    q = _query(L.load().tfx_delay_tiling_info,
+               (int(rows), int(length), int(delay_samples), int(taps), _dt(dtype), int(bool(pingpong))),
+               "regime:int units tiles kc nchunks groups nwg lds_bytes")
+    q["regime"] = DELAY_REGIMES[q["regime"]]
+    return q
 
 
 def resample_forward(x: Tensor, up: int, down: int, h: Tensor) -> Tensor:
