@@ -309,8 +309,10 @@ int tfx_normalize_apply(const void *x, void *y, int dtype, int64_t C, int64_t T,
 
 /* ---------------------------------------------------------------------------
  * Stream history -- the contract of every streaming entry point (tfx_fir_stream_forward, tfx_chunk_forward,
- * tfx_delay_stream_forward, tfx_delay_line_stream_forward, tfx_resample_stream_forward, tfx_limiter_stream_forward).  A chunk
- * continues the last H input samples of each of its rows (H is the entry's: K-1, Kf-1, taps*delay, delay, Lp_s-1, Hs):
+ * tfx_delay_stream_forward, tfx_delay_line_stream_forward, tfx_resample_stream_forward, tfx_limiter_stream_forward,
+ * tfx_modulated_delay_stream_forward).  A chunk
+ * continues the last H input samples of each of its rows (H is the entry's: K-1, Kf-1, taps*delay, delay, Lp_s-1, Hs, the
+ * modulated delay's reach):
  *   hist_in  DEVICE [rows, H] of the entry's dtype: the H samples before the chunk, oldest first; NULL = silence (the first
  *            chunk of a stream).
  *   hist_out DEVICE [rows, H]: receives the newest H samples of [hist_in | x] (x: what the entry filters, the cascade output
@@ -616,6 +618,52 @@ int tfx_compressor_forward(const void *x, void *y, void *gain_or_null, int dtype
  * rest) and the bytes of `scratch` (0 for one segment) */
 int tfx_compressor_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t segments, int64_t *tile, int64_t *tiles,
                              int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes);
+
+/* ---------------------------------------------------------------------------
+ * tfx_modulated_delay_forward -- the time-varying delay line behind Chorus, Flanger and Vibrato:
+ *   y[n] = dry x[n] + sum_v g_v x(n - d_v[n]),   the delay d_v moved by a low-frequency oscillator (LFO).
+ * x is [batch, channels, T]; the channel index of a row is c = row mod channels.  voices_host is HOST float64 [V, 5], 1 <= V <= 8,
+ * one row (base, depth, inc, phase, gain) per voice: base and depth in samples, inc = rate / fs in cycles per sample, phase in
+ * cycles.  For the absolute sample n = position + j, voice v and channel c, every intermediate in float64 for both dtypes:
+ *   1. off = frac(phase_v + c * spread), computed on the host
+ *   2. t = double(n) * inc_v -- one IEEE multiplication, never contracted into an FMA;  a = (t - floor(t)) + off
+ *   3. l = sinpi(2 a) (TFX_LFO_SINE) or 1 - 4 |frac(a + 0.25) - 0.5| (TFX_LFO_TRIANGLE)
+ *   4. d = base_v + depth_v * l;  i = floor(d);  f = d - i
+ *   5. TFX_INTERP_LINEAR: xd = x[n-i] + f (x[n-i-1] - x[n-i]);  TFX_INTERP_CUBIC: the 4-point third-order Lagrange interpolant
+ *      through x[n-i+1], x[n-i], x[n-i-1], x[n-i-2] at f, weights -f(f-1)(f-2)/6, (f+1)(f-1)(f-2)/2, -(f+1)f(f-2)/2, (f+1)f(f-1)/6;
+ *      reads before the first sample of the stream give 0 (or the carried history)
+ *   6. y[n] = dtype(dry x[n] + sum_v g_v xd_v), summed in voice order and rounded once
+ * Rules: base_v - depth_v >= 0 (linear) or >= 1 (cubic); floor(base_v + depth_v) + 3 <= 2^24; 0 < inc_v < 0.5; every value
+ * finite; 0 <= position <= 2^52.  x, y DEVICE [batch, channels, T] of dtype, y may not overlap x; the delayed tail past T is
+ * dropped.  One launch: a workgroup owns a tile of 1024 samples of one channel index and applies each (i, f) to up to 4 batch
+ * items (tfx_modulated_delay_plan_info).  Feed-forward: a row's bits depend on its own samples, its channel index and the
+ * position alone -- not on the tiling or the other rows.  At f = 0 both interpolants return x[n-i] exactly.  A non-finite
+ * x[m] reaches no output outside [m, m + floor(max_v(base_v + depth_v)) + 2] of its row.  Arguments are checked before the
+ * device is touched.
+ * ------------------------------------------------------------------------- */
+enum tfx_lfo_shape { TFX_LFO_SINE = 0, TFX_LFO_TRIANGLE = 1 };
+enum tfx_interp { TFX_INTERP_LINEAR = 0, TFX_INTERP_CUBIC = 1 };
+int tfx_modulated_delay_forward(const void *x, void *y, int dtype, int64_t batch, int64_t channels, int64_t T,
+                                const double *voices_host, int64_t V, double spread, double dry, int shape, int interp,
+                                int64_t position, tfx_stream_t stream);
+/* ---------------------------------------------------------------------------
+ * tfx_modulated_delay_stream_forward -- one chunk of tfx_modulated_delay_forward over a continuous stream (StatefulChorus,
+ * StatefulFlanger, StatefulVibrato), one launch: the chunks' outputs are bit-identical to the one-shot call on the whole
+ * signal, whatever the chunk sizes.  History as in "Stream history" with H = max_v floor(base_v + depth_v) + 2 (the plan's
+ * `history`); the kernel reads [hist_in | x] from their two buffers and writes hist_out (chunks shorter than H included).
+ * The position of the chunk's first sample is read on the device: pos_in DEVICE int64 [1] (NULL = 0), and one lane stores
+ * pos_in + T to pos_out (DEVICE int64 [1], its own buffer; NULL = not stored) -- a replayed HIP graph bakes host scalars in,
+ * a device counter moves on with every replay.  T = 0 carries history and position over.
+ * ------------------------------------------------------------------------- */
+int tfx_modulated_delay_stream_forward(const void *x, void *y, int dtype, int64_t batch, int64_t channels, int64_t T,
+                                       const double *voices_host, int64_t V, double spread, double dry, int shape, int interp,
+                                       const void *hist_in, void *hist_out, const int64_t *pos_in, int64_t *pos_out,
+                                       tfx_stream_t stream);
+/* what the two entries above do (host-only, same checks on the sizes and the voice table): samples per tile (1024), tiles per
+ * row, the history H of a stream, the batch items a workgroup applies one (i, f) to (4) and the batch groups of the grid
+ * (ceil(batch / 4)); the grid is tiles * channels * batch_groups workgroups */
+int tfx_modulated_delay_plan_info(int64_t batch, int64_t channels, int64_t T, const double *voices_host, int64_t V, int interp,
+                                  int64_t *tile, int64_t *tiles, int64_t *history, int64_t *batch_items, int64_t *batch_groups);
 
 /* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of

@@ -702,6 +702,35 @@ int tfx_compressor_plan_info(int64_t groups, int64_t channels, int64_t T, int64_
     TFX_API_END
 }
 
+int tfx_modulated_delay_forward(const void *x, void *y, int dtype, int64_t batch, int64_t channels, int64_t T,
+                                const double *voices_host, int64_t V, double spread, double dry, int shape, int interp,
+                                int64_t position, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    modulated_delay_forward(x, y, dtype, batch, channels, T, voices_host, V, spread, dry, shape, interp, position, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_modulated_delay_stream_forward(const void *x, void *y, int dtype, int64_t batch, int64_t channels, int64_t T,
+                                       const double *voices_host, int64_t V, double spread, double dry, int shape, int interp,
+                                       const void *hist_in, void *hist_out, const int64_t *pos_in, int64_t *pos_out,
+                                       tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    modulated_delay_stream_forward(x, y, dtype, batch, channels, T, voices_host, V, spread, dry, shape, interp, hist_in, hist_out,
+                                   pos_in, pos_out, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_modulated_delay_plan_info(int64_t batch, int64_t channels, int64_t T, const double *voices_host, int64_t V, int interp,
+                                  int64_t *tile, int64_t *tiles, int64_t *history, int64_t *batch_items, int64_t *batch_groups)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(tile && tiles && history && batch_items && batch_groups, "modulated_delay_plan_info: null output");
+    modulated_delay_plan_info(batch, channels, T, voices_host, V, interp, tile, tiles, history, batch_items, batch_groups);
+    TFX_API_END
+}
+
 int tfx_sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, tfx_stream_t stream)
 {
     TFX_API_BEGIN
@@ -810,6 +839,7 @@ int tfx_clear_caches(void)
     delay_clear();
     resample_clear();
     limiter_clear();
+    modulation_clear();
     scratch_clear();
     TFX_API_END
 }

@@ -613,6 +613,82 @@ std::tuple<Tensor, Tensor, Tensor> compressor_op(const Tensor &x_in, double th, 
     return std::make_tuple(y, gain, sout);
 }
 
+// The modulated delay line (tfx_modulated_delay_forward): x [T], [C, T] or [B, C, T]; voices a host float64 [V, 5] table of
+// (base, depth, inc, phase, gain) rows; shape 0 sine / 1 triangle, interp 0 linear / 1 cubic.  V, the shape of x and the
+// interpolation are checked here, before anything touches the device.
+struct ModInputs {
+    Tensor x, voices;
+    int dt;
+    int64_t batch, channels, T, V, H;
+};
+
+ModInputs mod_inputs(const Tensor &x_in, const Tensor &voices, int64_t shape, int64_t interp, const char *what)
+{
+    need_device(x_in, "x");
+    TORCH_CHECK(x_in.dim() >= 1 && x_in.dim() <= 3, what, ": x must be [T], [C, T] or [B, C, T], got ", x_in.dim(), " dimensions");
+    TORCH_CHECK(!voices.is_cuda() && voices.dim() == 2 && voices.size(1) == 5 && voices.scalar_type() == at::kDouble, what,
+                ": voices must be a host float64 [V, 5] tensor");
+    TORCH_CHECK(voices.size(0) >= 1 && voices.size(0) <= 8, what, ": the number of voices must be in [1, 8], got ", voices.size(0));
+    TORCH_CHECK(shape == TFX_LFO_SINE || shape == TFX_LFO_TRIANGLE, what, ": bad LFO shape ", shape);
+    TORCH_CHECK(interp == TFX_INTERP_LINEAR || interp == TFX_INTERP_CUBIC, what, ": bad interpolation ", interp);
+    ModInputs in;
+    in.x = x_in.contiguous();
+    in.voices = voices.contiguous();
+    in.dt = dtype_code(in.x, what);
+    in.T = in.x.size(-1);
+    in.channels = in.x.dim() >= 2 ? in.x.size(-2) : 1;
+    in.batch = in.x.dim() == 3 ? in.x.size(0) : 1;
+    in.V = in.voices.size(0);
+    TORCH_CHECK(in.channels >= 1, what, ": x has no channels");
+    int64_t info[5];
+    check_rc(tfx_modulated_delay_plan_info(in.batch, in.channels, in.T, in.voices.data_ptr<double>(), in.V, (int)interp, info, info + 1,
+                                           info + 2, info + 3, info + 4),
+             what);
+    in.H = info[2];
+    return in;
+}
+
+Tensor modulated_delay_op(const Tensor &x_in, const Tensor &voices, double spread, double dry, int64_t shape, int64_t interp,
+                          int64_t position)
+{
+    const char *what = "modulated_delay_forward";
+    const ModInputs in = mod_inputs(x_in, voices, shape, interp, what);
+    Tensor y = at::empty_like(in.x);
+    c10::hip::HIPGuard guard(in.x.get_device());
+    check_rc(tfx_modulated_delay_forward(in.x.data_ptr(), y.data_ptr(), in.dt, in.batch, in.channels, in.T, in.voices.data_ptr<double>(),
+                                         in.V, spread, dry, (int)shape, (int)interp, position, stream_of(in.x)),
+             what);
+    return y;
+}
+
+// one chunk of a modulated-delay stream: hist [rows, H] or None (silence), pos a device int64 [1] or None (0)
+// -> (y like x, new history [rows, H], new position int64 [1]), both fresh tensors (the graph replay of realtime.py copies them
+// into their persistent homes)
+std::tuple<Tensor, Tensor, Tensor> modulated_delay_stream_op(const Tensor &x_in, const OptTensor &hist, const OptTensor &pos,
+                                                             const Tensor &voices, double spread, double dry, int64_t shape,
+                                                             int64_t interp)
+{
+    const char *what = "modulated_delay_stream_forward";
+    const ModInputs in = mod_inputs(x_in, voices, shape, interp, what);
+    const int64_t rows = in.batch * in.channels;
+    const Tensor hin = stream_hist_in(hist, in.x, rows, in.H, what);
+    Tensor pin;
+    if (pos.has_value() && pos->defined()) {
+        TORCH_CHECK(pos->numel() == 1 && pos->scalar_type() == at::kLong, what, ": the position must be an int64 tensor of one element");
+        pin = pos->to(in.x.device()).contiguous();
+    }
+    Tensor y = at::empty_like(in.x), hout = at::empty({rows, in.H}, in.x.options()),
+           pout = at::empty({1}, in.x.options().dtype(at::kLong));
+    c10::hip::HIPGuard guard(in.x.get_device());
+    check_rc(tfx_modulated_delay_stream_forward(in.x.data_ptr(), y.data_ptr(), in.dt, in.batch, in.channels, in.T,
+                                                in.voices.data_ptr<double>(), in.V, spread, dry, (int)shape, (int)interp,
+                                                hin.defined() ? hin.data_ptr() : nullptr, hout.data_ptr(),
+                                                pin.defined() ? pin.data_ptr<int64_t>() : nullptr, pout.data_ptr<int64_t>(),
+                                                stream_of(in.x)),
+             what);
+    return std::make_tuple(y, hout, pout);
+}
+
 // One chunk of a resampling stream (tfx_resample_stream_forward): x [..., T] after `consumed` samples per row, h as for
 // resample_forward, hist [rows, H] (None = silence) -> (y [..., M(consumed + T) - M(consumed)], new history [rows, H])
 struct ResampleStreamPlan {
@@ -1005,6 +1081,22 @@ std::tuple<Tensor, Tensor, Tensor> compressor_meta(const Tensor &x, double, doub
             at::empty({groups, 2}, x.options().dtype(at::kDouble))};
 }
 
+std::tuple<Tensor, Tensor, Tensor> modulated_delay_stream_meta(const Tensor &x, const OptTensor &, const OptTensor &, const Tensor &voices,
+                                                               double, double, int64_t, int64_t)
+{
+    TORCH_CHECK(x.dim() >= 1 && x.dim() <= 3 && voices.dim() == 2 && voices.size(1) == 5 && voices.size(0) >= 1,
+                "modulated_delay_stream_forward: bad shape");
+    // the history's length comes from the table's values: H = max_v floor(base_v + depth_v) + 2 (a host tensor holds them even
+    // when x is a meta tensor)
+    int64_t H = 2;
+    if (!voices.is_meta()) {
+        const Tensor v = voices.to(at::kCPU, at::kDouble).contiguous();
+        for (int64_t i = 0; i < v.size(0); ++i)
+            H = std::max<int64_t>(H, (int64_t)std::floor(v.data_ptr<double>()[5 * i] + v.data_ptr<double>()[5 * i + 1]) + 2);
+    }
+    return {at::empty_like(x), at::empty({stream_rows(x), H}, x.options()), at::empty({1}, x.options().dtype(at::kLong))};
+}
+
 // No CPU branch, by design: every op of the namespace answers a host tensor with the same error instead of the dispatcher's
 // "no kernel for backend CPU" (one boxed function registered for the CPU key of each op; per-namespace fallbacks are not
 // supported by the dispatcher).
@@ -1117,6 +1209,23 @@ TORCH_LIBRARY(torchfx_dynamics, m)
 TORCH_LIBRARY_IMPL(torchfx_dynamics, Meta, m)
 {
     m.impl("compressor_forward", compressor_meta);
+}
+
+// The modulation effects (Chorus, Flanger, Vibrato) likewise: torch.ops.torchfx_modulation.
+TORCH_LIBRARY(torchfx_modulation, m)
+{
+    reg_op(m, "modulated_delay_forward(Tensor x, Tensor voices_cpu, float spread, float dry, int shape, int interp, int position=0) "
+              "-> Tensor", modulated_delay_op);
+    reg_op(m, "modulated_delay_stream_forward(Tensor x, Tensor? hist, Tensor? pos, Tensor voices_cpu, float spread, float dry, "
+              "int shape, int interp) -> (Tensor, Tensor, Tensor)", modulated_delay_stream_op);
+}
+
+TORCH_LIBRARY_IMPL(torchfx_modulation, Meta, m)
+{
+    m.impl("modulated_delay_forward", [](const Tensor &x, const Tensor &, double, double, int64_t, int64_t, int64_t) {
+        return at::empty_like(x);
+    });
+    m.impl("modulated_delay_stream_forward", modulated_delay_stream_meta);
 }
 
 // The reference's module surface (binding.cpp:83-96): exactly these three names and argument lists.

@@ -1,6 +1,6 @@
 // timedomain.h -- the host entry points of the time-domain and elementwise ops, one prototype per exported function of fir.hip,
-// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip, compressor.hip and layout.hip (the cascade's: sos.h; the overlap-save
-// pipelines': ols_route.h).  Included by the file that defines each function and by capi.hip, so a prototype that drifts from
+// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip, compressor.hip, modulation.hip and layout.hip (the cascade's: sos.h; the
+// overlap-save pipelines': ols_route.h).  Included by the file that defines each function and by capi.hip, so a prototype that drifts from
 // its definition does not compile; default arguments live here and nowhere else.  Every *_forward checks its arguments before
 // anything touches the device; a *_plan_info takes the same checking path without the pointers.
 #pragma once
@@ -96,6 +96,16 @@ void compressor_forward(const void *x, void *y, void *gain, int dtype, int64_t g
                         double *state_out, int64_t segments, void *scratch, hipStream_t stream);
 void compressor_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t segments, int64_t *tile, int64_t *tiles,
                           int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes);
+
+// ---- modulation.hip ----
+void modulated_delay_forward(const void *x, void *y, int dtype, int64_t batch, int64_t channels, int64_t T, const double *voices_host,
+                             int64_t V, double spread, double dry, int shape, int interp, int64_t position, hipStream_t stream);
+void modulated_delay_stream_forward(const void *x, void *y, int dtype, int64_t batch, int64_t channels, int64_t T,
+                                    const double *voices_host, int64_t V, double spread, double dry, int shape, int interp,
+                                    const void *hist_in, void *hist_out, const int64_t *pos_in, int64_t *pos_out, hipStream_t stream);
+void modulated_delay_plan_info(int64_t batch, int64_t channels, int64_t T, const double *voices_host, int64_t V, int interp,
+                               int64_t *tile, int64_t *tiles, int64_t *history, int64_t *batch_items, int64_t *batch_groups);
+void modulation_clear();
 
 // ---- layout.hip ----
 void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, int64_t C, int64_t ld_out, int64_t f_base,

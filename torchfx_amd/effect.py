@@ -357,6 +357,120 @@ class Compressor(FX):
                 f"knee_db={self.knee_db}, makeup_db={self.makeup_db}, link={self.link}, fs={self.fs}")
 
 
+class ModulatedDelay(FX):
+    """The modulated delay line as an effect: :func:`torchfx_amd.modulation.modulated_delay` with a voice table given in
+    seconds.  ``voices`` holds 1 to 8 rows ``(delay, depth, rate, phase, gain)``: delay and depth in seconds, rate in Hz, phase
+    in cycles; ``pad`` is added to every voice's delay in samples (the cubic interpolant's one sample of headroom).  ``dry``,
+    ``spread`` (cycles of LFO phase per channel index), ``shape`` ("sine" / "triangle") and ``interpolation`` ("linear" /
+    "cubic") as the function takes them.  :class:`Chorus`, :class:`Flanger` and :class:`Vibrato` only fill the table.
+
+    ``fs`` comes from the ``Wave`` the effect is piped into when it is None.  Every call starts its LFO at position 0 and its
+    delay line from silence: the effect is a step of its own in ``Wave.plan()`` (one launch, ``csrc/modulation.hip``), and a
+    chunked stream needs the stateful classes of :mod:`torchfx_amd.realtime`, which carry the history and the position."""
+
+    def __init__(self, voices, dry: float = 1.0, spread: float = 0.0, shape: str = "sine", interpolation: str = "linear",
+                 fs: int | None = None, pad: float = 0.0) -> None:
+        super().__init__()
+        self.voices = [tuple(float(t) for t in v) for v in voices]
+        self.dry, self.spread, self.shape, self.interpolation, self.fs, self.pad = float(dry), float(spread), shape, interpolation, fs, float(pad)
+        self.params(torch.float32, 48000 if fs is None else fs)          # argument errors now
+
+    def voice_table(self, fs: int) -> list[tuple]:
+        """The voices as :func:`~torchfx_amd.modulation.modulated_delay` takes them at ``fs``: delay and depth in samples."""
+        for v in self.voices:
+            if len(v) != 5:
+                raise ValueError(f"modulated_delay: a voice must be (delay, depth, rate, phase, gain), got {v!r}")
+        return [(d * fs + self.pad, w * fs, r, p, g) for d, w, r, p, g in self.voices]
+
+    def params(self, dtype: torch.dtype, fs: int | None = None):
+        """The call's :class:`torchfx_amd.modulation.ModulationParams` for a signal of ``dtype`` at ``fs`` (default ``self.fs``)."""
+        fs = self.fs if fs is None else fs
+        if fs is None:
+            raise ValueError(f"{type(self).__name__} needs the sample rate: pass fs or pipe a Wave into it (wave | {type(self).__name__}())")
+        from torchfx_amd.modulation import ModulationParams, _check_fs
+
+        return ModulationParams(fs, dtype, self.voice_table(_check_fs(fs)), self.dry, self.spread, self.shape, self.interpolation)
+
+    def route(self, x: Tensor, length: int | None = None) -> str:
+        """``native (...)`` or ``numpy on host -- <reason>`` for ``x`` (rows of ``length`` samples, default x's)."""
+        if not x.is_cuda:
+            return f"numpy on host -- {x.device.type} tensor"
+        try:
+            P = self.params(x.dtype)
+            n = int(x.shape[-1]) if length is None else int(length)
+            info = _ext().modulated_delay_plan_info(n, P.table, int(x.shape[0]) if x.dim() == 3 else 1,
+                                                    int(x.shape[-2]) if x.dim() >= 2 else 1, P.interpolation)
+        except (RuntimeError, ValueError, TypeError) as e:
+            return f"refused -- {e}"
+        return (f"native (modulated_delay_kernel, {len(P.table)} voice(s), {P.shape} LFO, {P.interpolation} interpolation, "
+                f"{info['tiles']} tile(s) of {info['tile']} per row, {info['batch_groups']} batch group(s) of up to "
+                f"{info['batch_items']}; one launch)")
+
+    @torch.no_grad()
+    def forward(self, waveform: Tensor) -> Tensor:
+        from torchfx_amd.modulation import _check_signal, modulate
+
+        _check_signal(waveform, "modulated_delay")
+        return modulate(waveform, self.params(waveform.dtype))
+
+    def extra_repr(self) -> str:
+        return (f"voices={len(self.voices)}, dry={self.dry}, spread={self.spread}, shape={self.shape!r}, "
+                f"interpolation={self.interpolation!r}, fs={self.fs}")
+
+
+def _seconds(name: str, v) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+        raise ValueError(f"modulated_delay: {name} must be a finite time >= 0 in seconds, got {v!r}")
+    return float(v)
+
+
+class Chorus(ModulatedDelay):
+    """Chorus: ``voices`` copies of the signal, each delayed by ``delay`` seconds and swept by ``depth`` seconds at ``rate``
+    Hz, the voices' LFOs spaced evenly over the cycle (voice ``v`` has phase ``v / voices``) and each mixed in with gain
+    ``mix / voices`` next to ``dry = 1 - mix``.  ``spread`` shifts the LFO phase by that many cycles per channel index, which
+    widens a stereo signal.  Feed-forward."""
+
+    def __init__(self, rate: float = 1.5, depth: float = 3e-3, delay: float = 20e-3, voices: int = 3, mix: float = 0.5,
+                 spread: float = 0.25, shape: str = "sine", interpolation: str = "cubic", fs: int | None = None) -> None:
+        if isinstance(voices, bool) or not isinstance(voices, int) or not 1 <= voices <= 8:
+            raise ValueError(f"modulated_delay: the number of voices must be in [1, 8], got {voices!r}")
+        self.rate, self.depth, self.delay, self.mix = float(rate), _seconds("depth", depth), _seconds("delay", delay), float(mix)
+        super().__init__([(self.delay, self.depth, self.rate, v / voices, self.mix / voices) for v in range(voices)],
+                         1.0 - self.mix, spread, shape, interpolation, fs)
+
+    def extra_repr(self) -> str:
+        return f"rate={self.rate}, depth={self.depth}, delay={self.delay}, mix={self.mix}, " + super().extra_repr()
+
+
+class Vibrato(ModulatedDelay):
+    """Vibrato: the signal alone, read through a delay that swings by ``depth`` seconds around ``depth`` (plus one sample for
+    the cubic interpolant) at ``rate`` Hz -- a periodic pitch change.  One voice, no dry part."""
+
+    def __init__(self, rate: float = 5.0, depth: float = 1e-3, shape: str = "sine", interpolation: str = "cubic",
+                 fs: int | None = None) -> None:
+        self.rate, self.depth = float(rate), _seconds("depth", depth)
+        super().__init__([(self.depth, self.depth, self.rate, 0.0, 1.0)], 0.0, 0.0, shape, interpolation, fs,
+                         pad=1.0 if interpolation == "cubic" else 0.0)
+
+    def extra_repr(self) -> str:
+        return f"rate={self.rate}, depth={self.depth}, " + super().extra_repr()
+
+
+class Flanger(ModulatedDelay):
+    """Flanger: the signal plus one short, slowly swept copy of itself (``delay`` +- ``depth`` seconds at ``rate`` Hz) with
+    gain ``mix`` (``-mix`` with ``invert``), which combs the spectrum.  This flanger is **feed-forward**: there is no
+    regeneration path from the output back into the delay line."""
+
+    def __init__(self, rate: float = 0.25, depth: float = 2e-3, delay: float = 3e-3, mix: float = 0.5, invert: bool = False,
+                 spread: float = 0.0, shape: str = "sine", interpolation: str = "cubic", fs: int | None = None) -> None:
+        self.rate, self.depth, self.delay, self.mix, self.invert = float(rate), _seconds("depth", depth), _seconds("delay", delay), float(mix), bool(invert)
+        super().__init__([(self.delay, self.depth, self.rate, 0.0, -self.mix if self.invert else self.mix)], 1.0, spread, shape,
+                         interpolation, fs)
+
+    def extra_repr(self) -> str:
+        return f"rate={self.rate}, depth={self.depth}, delay={self.delay}, mix={self.mix}, invert={self.invert}, " + super().extra_repr()
+
+
 class Epilogued(FX):
     """Planner product (``Wave.plan()``, ``fuse_epilogue``): a filter followed by ``Gain`` and / or ``Normalize``
     whose elementwise work rides on the filter's own kernel.  ``producer`` is an SOS filter / cascade or an

@@ -71,3 +71,11 @@ def dynamics_ops():
 
     load()
     return torch.ops.torchfx_dynamics
+
+
+def modulation_ops():
+    """``torch.ops.torchfx_modulation`` (the modulated delay line's namespace, registered by the same module) with the library loaded."""
+    import torch
+
+    load()
+    return torch.ops.torchfx_modulation

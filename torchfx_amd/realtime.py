@@ -20,7 +20,10 @@ every row, returns the outputs each chunk completes (``tfx_resample_stream_forwa
 (``tfx_limiter_stream_forward``, one launch per chunk), and its chunks plus ``flush()`` are ``limit`` on the whole signal;
 ``aligned=False`` gives the constant-latency form a sound card needs.  :class:`StatefulCompressor` is the compressor of a
 stream: causal, no latency, it carries the detector's ``(y1, yL)`` per group (``tfx_compressor_forward``'s state), and its chunks
-equal ``compress`` on the whole signal to float64 round-off of the detector (not bit for bit).
+equal ``compress`` on the whole signal to float64 round-off of the detector (not bit for bit).  :class:`StatefulChorus`,
+:class:`StatefulFlanger` and :class:`StatefulVibrato` are the modulation effects of a stream: causal, no latency, they carry the
+delay line's reach in ``_hist`` and the LFO's position in ``_pos`` (a device counter, ``tfx_modulated_delay_stream_forward``), and
+their chunks are bit-identical to the one-shot effect on the whole signal.
 
 Small chunks are launch-bound (a 2 x 4096 step is ~60 us of host + launch overhead for a few us of
 GPU work), so ``StreamProcessor(..., use_graph=True)`` captures one full-size chunk step -- every
@@ -40,7 +43,8 @@ from collections.abc import Generator, Sequence
 import torch
 from torch import Tensor, nn
 
-from torchfx_amd.effect import FX, Compressor, Delay, Limiter, MonoDelayStrategy, PingPongDelayStrategy, Reverb, _ext
+from torchfx_amd.effect import (FX, Chorus, Compressor, Delay, Flanger, Limiter, ModulatedDelay, MonoDelayStrategy, PingPongDelayStrategy,
+                                Reverb, Vibrato, _ext)
 from torchfx_amd.filter._base import AbstractFilter
 from torchfx_amd.filter.fir import FIR
 from torchfx_amd.resample import Resample, design_taps, window_key
@@ -593,6 +597,80 @@ def _refuse_compressor(e, who: str) -> None:
                         "whole signal (wave | Compressor(...)) before or after streaming")
 
 
+class _ModulationStream:
+    """A modulated delay line (:class:`~torchfx_amd.effect.ModulatedDelay`) over a continuous stream; mixed in in front of the
+    effect class.  Every row carries its last ``H = max_v floor(delay_v + depth_v) + 2`` input samples in ``_hist``
+    (``[rows, H]``, the stream-history contract, :func:`_carried`) and the stream the absolute position of its next sample in
+    ``_pos`` (int64 ``[1]`` on the chunks' device: a replayed HIP graph bakes host scalars in, a device counter moves on with
+    every replay).  The stream is causal with no latency: every chunk returns the chunk's shape and there is nothing to flush.
+    All chunks together are ``torch.equal`` to the one-shot effect on the whole signal, whatever the chunk sizes.
+
+    The stream restarts from silence and position 0 when the row count, dtype or device changes; :meth:`reset_state` does the
+    same on request.  When a changed parameter changes ``H`` the newest samples are kept.  Device float32 / float64 chunks run
+    one launch each (:func:`torchfx_ext.modulated_delay_stream_forward`), CPU chunks the host path on ``[history | chunk]``
+    with the absolute position."""
+
+    def __init__(self, *args, **kwargs) -> None:
+        super().__init__(*args, **kwargs)
+        self.reset_state()
+
+    def reset_state(self) -> None:
+        self._hist: Tensor | None = None            # [rows, H]; None = silence
+        self._pos: Tensor | None = None             # int64 [1] on the chunks' device; None = 0
+
+    def _capture_key(self) -> tuple:
+        """What a captured HIP graph of this effect bakes in: every parameter of the launch."""
+        return (tuple(self.voices), self.dry, self.spread, self.shape, self.interpolation, self.pad, self.fs)
+
+    def _sync_history(self) -> None:
+        """Bring the carried history to the current ``H`` (newest samples kept) before a capture takes it as a home."""
+        if self._hist is not None and self.fs is not None:
+            self._hist = _carried(self._hist, self._hist.shape[0], self.params(self._hist.dtype).history, self._hist)
+
+    @torch.no_grad()
+    def forward(self, x: Tensor) -> Tensor:
+        rows = _rows(x)
+        if self.fs is None:
+            raise ValueError(f"{type(self).__name__} needs the sample rate: pass fs or let the processor configure it")
+        P = self.params(x.dtype)
+        h = _carried(self._hist, rows, P.history, x)
+        if h is None or self._pos is None or self._pos.device != x.device:      # a new stream: silence, position 0
+            h, self._pos = None, None
+        if _native_stream(x):
+            with torch.cuda.device(x.device):
+                y, self._hist, self._pos = _ext().modulated_delay_stream_forward(x, h, self._pos, P.table, P.spread, P.dry, P.shape,
+                                                                                 P.interpolation)
+            return y
+        from torchfx_amd.modulation import modulate_stream_host
+
+        pos = 0 if self._pos is None else int(self._pos)
+        y, self._hist = modulate_stream_host(x, h, P, pos)
+        self._pos = torch.tensor([pos + x.shape[-1]], dtype=torch.int64, device=x.device)
+        return y
+
+
+class StatefulChorus(_ModulationStream, Chorus):
+    """:class:`~torchfx_amd.effect.Chorus` over a continuous stream (see :class:`_ModulationStream`)."""
+
+
+class StatefulFlanger(_ModulationStream, Flanger):
+    """:class:`~torchfx_amd.effect.Flanger` over a continuous stream (see :class:`_ModulationStream`)."""
+
+
+class StatefulVibrato(_ModulationStream, Vibrato):
+    """:class:`~torchfx_amd.effect.Vibrato` over a continuous stream (see :class:`_ModulationStream`)."""
+
+
+def _refuse_modulation(e, who: str) -> None:
+    for m in (e.modules() if isinstance(e, nn.Module) else [e]):
+        if isinstance(m, ModulatedDelay) and not isinstance(m, _ModulationStream):
+            name = type(m).__name__
+            stateful = f"Stateful{name}(...)" if isinstance(m, (Chorus, Flanger, Vibrato)) else "a stateful class (StatefulChorus, StatefulFlanger, StatefulVibrato)"
+            raise TypeError(f"{name} cannot run in {who}: every call starts its LFO at position 0 and its delay line from silence, "
+                            f"so a chunked stream would restart the sweep and drop the delayed samples at every chunk start; use "
+                            f"{stateful} in its place, or run the whole signal (wave | {name}(...)) before or after streaming")
+
+
 def _holds_back(e) -> bool:
     """Effects whose chunks may return fewer samples than they take and that hand the rest out in ``flush()``."""
     return isinstance(e, (StatefulResample, StatefulLimiter))
@@ -773,6 +851,7 @@ class StreamProcessor:
             _refuse_loudness(e, "StreamProcessor")
             _refuse_limiter(e, "StreamProcessor")
             _refuse_compressor(e, "StreamProcessor")
+            _refuse_modulation(e, "StreamProcessor")
             if not isinstance(e, StatefulResample) and any(isinstance(m, Resample) for m in e.modules()):
                 raise TypeError("Resample cannot run in StreamProcessor: resampling each chunk on its own leaves a seam at "
                                 "every chunk boundary; use StatefulResample as a top-level effect of the chain, or resample "
@@ -827,7 +906,7 @@ class StreamProcessor:
         return fs
 
     # ---- HIP-graph replay of the per-chunk step ------------------------------------------------
-    _STATE_ATTRS = ("_state_x", "_state_y", "_hist")
+    _STATE_ATTRS = ("_state_x", "_state_y", "_hist", "_pos")
 
     def _stateful_slots(self) -> list[tuple[object, str]]:
         """(module, attribute) of every carried-state tensor reachable from the effects."""
@@ -1095,6 +1174,7 @@ class RealtimeProcessor:
             _refuse_loudness(e, "RealtimeProcessor")
             _refuse_limiter(e, "RealtimeProcessor")
             _refuse_compressor(e, "RealtimeProcessor")
+            _refuse_modulation(e, "RealtimeProcessor")
             if _has_stateful_resample(e):
                 raise TypeError("StatefulResample cannot run in RealtimeProcessor: a sound card's output block has the input "
                                 "block's length and sample rate; resample with StreamProcessor or Wave.resample instead")

@@ -37,6 +37,7 @@ __all__ = [
     "resample_plan_info", "resample_tiling_info", "resample_stream_forward", "resample_stream_plan_info", "sos_filtfilt", "sos_filtfilt_plan_info",
     "sos_block_energy", "sos_block_energy_plan_info", "true_peak", "true_peak_plan_info", "limiter_forward", "limiter_plan_info",
     "limiter_stream_forward", "limiter_stream_plan_info", "compressor_forward", "compressor_plan_info",
+    "modulated_delay_forward", "modulated_delay_stream_forward", "modulated_delay_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
 ]
@@ -374,6 +375,51 @@ def compressor_plan_info(length: int, groups: int = 1, channels: int = 1, segmen
     segment) and ``scratch_bytes`` (the summaries between the launches; 0 for one segment)."""
     return _query(L.load().tfx_compressor_plan_info, (int(groups), int(channels), int(length), int(segments)),
                   "tile tiles segments seg_tiles scratch_bytes")
+
+
+LFO_SHAPES = ("sine", "triangle")                        # tfx_lfo_shape
+INTERPOLATIONS = ("linear", "cubic")                     # tfx_interp
+
+
+def _voice_table(voices) -> Tensor:
+    """The host float64 ``[V, 5]`` table of ``(base, depth, inc, phase, gain)`` rows the modulated delay's entries take."""
+    return torch.as_tensor(voices, dtype=torch.float64, device="cpu").reshape(-1, 5).contiguous()
+
+
+def modulated_delay_forward(x: Tensor, voices, spread: float = 0.0, dry: float = 1.0, shape: str = "sine",
+                            interpolation: str = "linear", position: int = 0) -> Tensor:
+    """The modulated delay line (``tfx_modulated_delay_forward``; the definition is
+    :func:`torchfx_amd.modulation.modulated_delay`'s) with its parameters already reduced: ``x [T]``, ``[C, T]`` or
+    ``[B, C, T]`` on the device (float32 / float64), ``voices`` a ``[V, 5]`` table of ``(base, depth, inc, phase, gain)`` rows
+    (delay and depth in samples, ``inc = rate / fs``, phase in cycles), ``position`` the absolute index of the first sample.
+    One launch (``modulated_delay_kernel``).  The op lives in ``torch.ops.torchfx_modulation``."""
+    native.ops()                                         # loads the library: every namespace is registered by the one module
+    return native.modulation_ops().modulated_delay_forward(x.contiguous(), _voice_table(voices), float(spread), float(dry),
+                                                           LFO_SHAPES.index(shape), INTERPOLATIONS.index(interpolation), int(position))
+
+
+def modulated_delay_stream_forward(x: Tensor, hist: Tensor | None, pos: Tensor | None, voices, spread: float = 0.0, dry: float = 1.0,
+                                   shape: str = "sine", interpolation: str = "linear") -> tuple[Tensor, Tensor, Tensor]:
+    """One chunk of :func:`modulated_delay_forward` over a continuous stream, in one launch
+    (``modulated_delay_stream_kernel``): the ``H`` samples of every row before ``x`` come from ``hist [rows, H]`` (None =
+    silence; ``H`` is :func:`modulated_delay_plan_info`'s ``history``) and the position of the chunk's first sample from the
+    device int64 ``pos [1]`` (None = 0).  Returns ``(y like x, new history, new position = pos + T)``; the chunks' outputs are
+    bit-identical to the one-shot call on the whole signal."""
+    native.ops()
+    return native.modulation_ops().modulated_delay_stream_forward(x.contiguous(), hist, pos, _voice_table(voices), float(spread),
+                                                                  float(dry), LFO_SHAPES.index(shape),
+                                                                  INTERPOLATIONS.index(interpolation))
+
+
+def modulated_delay_plan_info(length: int, voices, batch: int = 1, channels: int = 1, interpolation: str = "linear") -> dict:
+    """What the modulated delay's launches do for ``[batch, channels, length]`` (``tfx_modulated_delay_plan_info``; host-only,
+    same checks on the sizes and the voice table): ``tile`` (samples per tile), ``tiles`` per row, ``history`` (``H`` of a
+    stream: ``max_v floor(base_v + depth_v) + 2``), ``batch_items`` (batch items one workgroup applies a delay ``(i, f)`` to)
+    and ``batch_groups`` (the batch split of the grid; the grid is ``tiles * channels * batch_groups`` workgroups)."""
+    t = _voice_table(voices)
+    return _query(L.load().tfx_modulated_delay_plan_info,
+                  (int(batch), int(channels), int(length), ctypes.c_void_p(t.data_ptr()), int(t.shape[0]),
+                   INTERPOLATIONS.index(interpolation)), "tile tiles history batch_items batch_groups")
 
 
 RESAMPLE_STREAM_KERNELS = ("resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel", "copy")

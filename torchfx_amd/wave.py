@@ -210,7 +210,7 @@ def plan_cache_clear() -> None:
 
 
 def _member_key(m: nn.Module, guard: list) -> tuple:
-    from torchfx_amd.effect import Compressor, Delay, Gain, Limiter, LoudnessNormalize, Normalize
+    from torchfx_amd.effect import Compressor, Delay, Gain, Limiter, LoudnessNormalize, ModulatedDelay, Normalize
     from torchfx_amd.filter.zerophase import ZeroPhase
     from torchfx_amd.resample import Resample, window_key
 
@@ -242,6 +242,8 @@ def _member_key(m: nn.Module, guard: list) -> tuple:
         k += (m.ceiling_db, m.lookahead, m.hold, m.detector, m.link, m.oversample, id(m.taps), id(m.window), m.fs)
     elif isinstance(m, Compressor):
         k += (m.threshold_db, m.ratio, m.attack, m.release, m.knee_db, m.makeup_db, m.link, m.fs)
+    elif isinstance(m, ModulatedDelay):
+        k += (tuple(m.voices), m.dry, m.spread, m.shape, m.interpolation, m.pad, m.fs)
     return k
 
 
@@ -573,7 +575,7 @@ class Wave:
     def explain(self) -> list[str]:
         """One line per step of :meth:`plan` for THIS tensor: the step, the route it will take (``CascadeFIR``: the fused
         recursion-in-pass-A pipeline or the staged pair of launches) and why."""
-        from torchfx_amd.effect import Compressor, Delay, Epilogued, Limiter, LoudnessNormalize
+        from torchfx_amd.effect import Compressor, Delay, Epilogued, Limiter, LoudnessNormalize, ModulatedDelay
         from torchfx_amd.filter.fused import CascadeFIR, FusedSOSCascade
         from torchfx_amd.filter.zerophase import ZeroPhase
         from torchfx_amd.realtime import StatefulDelay, _native_stream
@@ -600,7 +602,7 @@ class Wave:
             elif isinstance(inner, Resample):
                 line += ": " + inner.route(self._ys, length)
                 length = inner.output_length(length)
-            elif isinstance(inner, (ZeroPhase, LoudnessNormalize, Limiter, Compressor)):
+            elif isinstance(inner, (ZeroPhase, LoudnessNormalize, Limiter, Compressor, ModulatedDelay)):
                 line += ": " + inner.route(self._ys, length)
             lines.append(line)
         return lines
