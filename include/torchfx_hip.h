@@ -699,6 +699,14 @@ int tfx_stat_forward(const void *x, int dtype, int64_t C, int64_t T, int mode, i
                      double *out_dev, tfx_stream_t stream);
 int tfx_normalize_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int mode, int per_row,
                           double peak, tfx_stream_t stream);
+/* the geometry of the launches above, of tfx_normalize_apply, tfx_sum_forward and the two tfx_delay_line entries for rows of T
+ * samples of `dtype` (host-only, from the launches' own constants): vec = samples per 16-byte vector (4 / 2); tile = samples
+ * one workgroup of an elementwise pass covers (1024 / 512); group = samples one workgroup of the statistics' first stage
+ * reduces to one partial (8 tiles); groups = partials per row of T samples; finish_threads = threads of the second stage's one
+ * workgroup per row (1024: a row with more partials takes strided trips); stream_tile = samples per workgroup of
+ * tfx_delay_line_stream_forward (1024 for both dtypes) */
+int tfx_effects_plan_info(int64_t T, int dtype, int64_t *vec, int64_t *tile, int64_t *group, int64_t *groups,
+                          int64_t *finish_threads, int64_t *stream_tile);
 
 /* ---------------------------------------------------------------------------
  * The data-format edge: decoded audio is INTERLEAVED frames [F, C]; the filter

@@ -20,7 +20,7 @@ def declared_symbols():
 def test_header_declares_the_hot_path():
     syms = declared_symbols()
     for need in ("tfx_sos_forward", "tfx_biquad_forward", "tfx_fir_direct_forward",
-                 "tfx_fft_conv_forward", "tfx_delay_line_forward", "tfx_sum_forward"):
+                 "tfx_fft_conv_forward", "tfx_delay_line_forward", "tfx_sum_forward", "tfx_effects_plan_info"):
         assert need in syms
 
 
@@ -56,6 +56,8 @@ def test_plan_info_runs_without_gpu():
     assert E.sos_plan_info(np.array([[1.0, 0.5, 0.25, 1, 0, 0]]))["warmup"] < 32
     # marginally stable integrator never decays
     assert E.sos_plan_info(np.array([[1.0, 0, 0, 1, -1.0, 0]]))["warmup"] == -1
+    # the elementwise effects' geometry: 16-byte vectors, 256 threads, 8 tiles per reduce workgroup
+    assert E.effects_plan_info(3 * 8192 + 1) == dict(vec=4, tile=1024, group=8192, groups=4, finish_threads=1024, stream_tile=1024)
 
 
 def test_errors_without_device_are_loud():

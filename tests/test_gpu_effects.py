@@ -57,7 +57,8 @@ def test_effect_kernels_ragged_shapes_vs_oracle(C, T, dtype):
         y = e.normalize_forward(xd, 0.9, mode, per_row).cpu().numpy()
         exp = O.normalize(x, 0.9, strat)
         assert np.abs(y - exp).max() <= tol * max(1.0, np.abs(exp).max()), strat
-    # rows that are not 16-byte aligned (a view shifted by one sample) take the scalar path
+    # a view shifted by one sample is not contiguous: the extension makes it contiguous (a fresh, aligned copy) before the
+    # kernel sees it.  Rows that really start misaligned: tests/test_gpu_effects_edges.py (`at_offset`)
     if T > 8:
         xs = dev(x)[:, 1:]
         assert not xs.is_contiguous()
@@ -175,6 +176,95 @@ def test_epilogue_statistics_and_golden_mix(golden):
     close(w.ys, g["mix_y"], TOL_IIR_F32OUT * 2, "reference mixed pipeline, gain as an epilogue")
 
 
+# ---- the abs-max an epilogue leaves, with the maximum planted at the seams of the producer's own geometry ----
+def _planted(rows, T, index, seed=23):
+    """Quiet noise (|x| <= 1e-3) with one impulse of 0.9 at `index` of the last row."""
+    x = rnd((rows, T), seed) * np.float32(1e-3)
+    x[-1, index] = 0.9
+    return dev(x)
+
+
+def _check_planted(what, y_plain, y_ep, ep, per_row, index):
+    """The position first -- arg-max |y| of the un-epilogued output is the planted index of the last row -- then the statistic:
+    exactly max |y| of the output the epilogue call stored, per row or over everything."""
+    rows, T = y_plain.shape
+    assert int(y_plain.abs().argmax()) == (rows - 1) * T + index, f"{what}: arg-max {int(y_plain.abs().argmax())}, planted {(rows - 1) * T + index}"
+    assert int(y_ep.abs().argmax()) == (rows - 1) * T + index, what
+    view = y_ep.double() if per_row else y_ep.double().reshape(1, -1)
+    ref = view.abs().max(dim=1).values
+    assert ep.stat_value.dtype == torch.float64 and torch.equal(ep.stat_value, ref), f"{what}: statistic {ep.stat_value.tolist()} != {ref.tolist()}"
+    assert float(ref[-1]) == float(y_ep[-1, index].abs()) > 0.25
+
+
+PLANT_SOS = np.array([[1.0, 0.05, 0.02, 1.0, -0.1, 0.05], [1.05, -0.08, 0.01, 1.0, 0.12, 0.04]])     # direct tap 1.05, the next ones below 0.06
+
+
+def _cascade_seams(T, plan_warm, nseg):
+    """The first sample each later time segment of the cascade stores, from the warm-up its plan query reports: the halo is
+    that rounded up to 256, segment g starts at g * stride with stride = seg_tiles * tile - halo and stores from g * stride +
+    halo.  The tile is 64 samples per lane chunk of 16, 32 or 64 -- the query does not say which kernel runs, so the seams of
+    all three are returned.  nseg > 0: TFX_SOS_NSEG = nseg; 0: the default plan of a device with room for every segment (one
+    tile per segment, or the 8 halos a segment must be worth)."""
+    halo = (plan_warm + 255) & ~255
+    out = set()
+    for tile in (1024, 2048, 4096):
+        if nseg:
+            seg_tiles = -(-(-(-(T - halo) // nseg) + halo) // tile)
+        else:
+            seg_tiles = max(1, -(-8 * halo // tile))
+        stride = seg_tiles * tile - halo
+        out |= {g * stride + halo for g in range(1, -(-(T - halo) // stride))}
+    return sorted(s for s in out if 0 < s < T)
+
+
+@pytest.mark.parametrize("nseg", [0, 2, 3])
+@pytest.mark.parametrize("T", [3 * 4096 + 1000, 3 * 4096 + 1001], ids=["aligned rows", "odd rows"])
+def test_cascade_epilogue_absmax_planted_at_the_segment_seams(T, nseg, monkeypatch):
+    """A cascade dominated by its direct tap puts the largest output where the impulse is: at 0, T - 1 and both sides of every
+    segment seam.  Rows of a multiple of four samples take the fused epilogue, odd rows the separate passes."""
+    e = ext()
+    sos = torch.from_numpy(PLANT_SOS)
+    warm = e.sos_plan_info(PLANT_SOS, refine=False)["warmup"]
+    assert 0 < warm <= 256
+    seams = _cascade_seams(T, warm, nseg)
+    assert seams and len(seams) <= 24
+    if nseg:
+        monkeypatch.setenv("TFX_SOS_NSEG", str(nseg))
+    for index in sorted({0, T - 1} | {s - 1 for s in seams} | set(seams)):
+        x = _planted(3, T, index)
+        y0, _, _ = e.sos_forward(x, None, sos, None, None)
+        for per_row in (False, True):
+            ep = e.Epilogue(gain=0.5, stat="absmax", per_row=per_row)
+            y, _, _ = e.sos_forward(x, None, sos, None, None, epilogue=ep)
+            assert torch.equal(y, e.gain_forward(y0, 0.5))
+            _check_planted(f"cascade T={T} nseg={nseg} index {index} per_row={per_row}", y0, y, ep, per_row, index)
+
+
+@pytest.mark.parametrize("taps,block", [(301, 4096), (3001, 8192), (6001, 16384)])
+def test_fir_epilogue_absmax_planted_at_the_block_seams(taps, block):
+    """The three one-launch overlap-save kernels on rows of three hops and an odd remainder: a kernel with one tap of 0.97 and
+    the rest below 1e-2 keeps the impulse where it is -- at 0, T - 1 and both sides of the first and the last block seam."""
+    e = ext()
+    S = block - taps + 1
+    T = 3 * S + 37
+    info = e.ols_plan_info(taps, T, (taps - 1, 0))
+    assert (info["N"], info["S"], info["path"]) == (block, S, "lds") and T % 2 == 1
+    k = (rnd((taps,), taps) * np.float32(5e-3))
+    k[-1] = 0.97                                          # the tap that multiplies x[n] with padding (taps - 1, 0)
+    assert np.abs(k[:-1]).max() < 1e-2
+    kt = torch.from_numpy(k)
+    last = (T - 1) // S * S
+    assert last == 3 * S
+    for index in (0, S - 1, S, last - 1, last, T - 1):
+        x = _planted(3, T, index)
+        y0 = e.fft_conv_forward(x, kt, (taps - 1, 0))
+        for per_row in (False, True):
+            ep = e.Epilogue(gain=0.5, stat="absmax", per_row=per_row)
+            y = e.fft_conv_forward(x, kt, (taps - 1, 0), epilogue=ep)
+            assert torch.equal(y, e.gain_forward(y0, 0.5))
+            _check_planted(f"fft conv taps={taps} index {index} per_row={per_row}", y0, y, ep, per_row, index)
+
+
 @pytest.mark.parametrize("n,q", [(1, 0.5), (2, 0.3), (7, 0.99), (1000, 0.97), (4097, 0.5), (100_003, 0.999), (1 << 20, 0.97),
                                  (3_000_001, 0.25), (16_000_000, 0.99), (5, 1.0), (5, 0.0)])
 def test_quantile_abs_equals_torch_quantile(n, q):
@@ -194,7 +284,7 @@ def test_quantile_abs_equals_torch_quantile(n, q):
     got = ext().quantile_abs(x.to(DEV), q).cpu()
     assert got.dtype == torch.float64 and got.shape == (1,)
     assert float(got) == float(ref), (n, q, float(got), float(ref))
-    # unaligned base pointer and a 2-D view
+    # a contiguous slice one element into a buffer: this one does reach the kernel with an unaligned base pointer
     if n > 9:
         xo = torch.zeros(n + 1, device=DEV)
         xo[1:] = x.to(DEV)

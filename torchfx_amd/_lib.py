@@ -97,6 +97,7 @@ SIGNATURES = {
     "tfx_gain_forward": (_int, [_vp, _vp, _int, _i64, _dbl, _int, _vp]),
     "tfx_stat_forward": (_int, [_vp, _int, _i64, _i64, _int, _int, _vp, _vp]),
     "tfx_normalize_forward": (_int, [_vp, _vp, _int, _i64, _i64, _int, _int, _dbl, _vp]),
+    "tfx_effects_plan_info": (_int, [_i64, _int] + [ctypes.POINTER(_i64)] * 6),
     "tfx_deinterleave_forward": (_int, [_vp, _int, _vp, _i64, _i64, _i64, _i64, _dbl, _vp]),
     "tfx_interleave_forward": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "tfx_prof_enable": (_int, [_int]),

@@ -761,6 +761,15 @@ int tfx_normalize_forward(const void *x, void *y, int dtype, int64_t C, int64_t 
     TFX_API_END
 }
 
+int tfx_effects_plan_info(int64_t T, int dtype, int64_t *vec, int64_t *tile, int64_t *group, int64_t *groups,
+                          int64_t *finish_threads, int64_t *stream_tile)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(vec && tile && group && groups && finish_threads && stream_tile, "effects_plan_info: null output");
+    effects_plan_info(T, dtype, vec, tile, group, groups, finish_threads, stream_tile);
+    TFX_API_END
+}
+
 int tfx_deinterleave_forward(const void *in, int in_kind, void *out, int64_t F, int64_t C, int64_t ld_out,
                              int64_t f_base, double scale, tfx_stream_t stream)
 {

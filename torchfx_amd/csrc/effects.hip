@@ -19,6 +19,16 @@ namespace tfx {
 constexpr int EFX_THREADS = 256;
 constexpr int EFX_U = 1;                                   // 16-byte vectors per thread (1: short-lived waves stream best, stream_copy2.hip)
 
+constexpr int EFX_RT = 8;                                  // consecutive tiles one reduce workgroup covers (128 KiB)
+constexpr int EFX_FINISH_THREADS = 1024;                   // reduce_finish_kernel: one workgroup per row
+constexpr int EFX_STR_E = 4;                               // delay_line_stream_kernel: samples per thread
+constexpr int64_t EFX_STR_TILE = (int64_t)EFX_THREADS * EFX_STR_E;
+
+// the geometry every launch below and effects_plan_info take from here (esz = bytes per sample)
+static inline int64_t efx_tile(int esz) { return (int64_t)EFX_U * EFX_THREADS * (16 / esz); }
+static inline int64_t efx_tiles(int64_t T, int esz) { return ceil_div(T, efx_tile(esz)); }
+static inline int64_t efx_groups(int64_t T, int esz) { return ceil_div(efx_tiles(T, esz), (int64_t)EFX_RT); }
+
 template <typename T> struct Vec16;
 template <> struct Vec16<float> { typedef float4 type; static constexpr int N = 4; };
 template <> struct Vec16<double> { typedef double2 type; static constexpr int N = 2; };
@@ -66,7 +76,6 @@ gain_kernel(const T *__restrict__ x, T *__restrict__ y, int64_t n, T g)
 //                          like unsigned integers and NaN sorts above inf, so a NaN anywhere wins,
 //                          like torch.max
 //   MODE 1  sum x^2     -- float64 accumulation
-constexpr int EFX_RT = 8;
 
 template <typename T, int MODE>
 __global__ void __launch_bounds__(EFX_THREADS)
@@ -113,17 +122,17 @@ reduce_kernel(const T *__restrict__ x, int64_t T_, int64_t groups, double *__res
 }
 
 template <int MODE>
-__global__ void __launch_bounds__(1024) reduce_finish_kernel(const double *__restrict__ partial, int64_t groups,
+__global__ void __launch_bounds__(EFX_FINISH_THREADS) reduce_finish_kernel(const double *__restrict__ partial, int64_t groups,
                                                              double *__restrict__ out)
 {
     // one workgroup per row: strided partials, then a fixed tree
-    __shared__ double sh[1024];
+    __shared__ double sh[EFX_FINISH_THREADS];
     const double *p = partial + (int64_t)blockIdx.x * groups;
     double s = red_init<MODE>();
-    for (int64_t i = threadIdx.x; i < groups; i += 1024) s = red_comb<MODE>(s, p[i]);
+    for (int64_t i = threadIdx.x; i < groups; i += EFX_FINISH_THREADS) s = red_comb<MODE>(s, p[i]);
     sh[threadIdx.x] = s;
     __syncthreads();
-    for (int off = 512; off >= 1; off >>= 1) {
+    for (int off = EFX_FINISH_THREADS / 2; off >= 1; off >>= 1) {
         if ((int)threadIdx.x < off) sh[threadIdx.x] = red_comb<MODE>(sh[threadIdx.x], sh[threadIdx.x + off]);
         __syncthreads();
     }
@@ -281,7 +290,7 @@ void delay_line_forward(const void *x, void *y, int dtype, int64_t C, int64_t T,
     if (C == 0 || T == 0) return;
     TFX_CHECK(C > 0 && T > 0 && x && y, "delay_line_forward: null pointer or negative size");
     const int esz = dtype == TFX_F32 ? 4 : 8;
-    const int64_t tiles = ceil_div(T, (int64_t)EFX_U * EFX_THREADS * (16 / esz));
+    const int64_t tiles = efx_tiles(T, esz);
     TFX_CHECK(C * tiles < (1ll << 31), "delay_line_forward: grid too large");
     ProfScope ps("delay_line_kernel", stream);
     if (dtype == TFX_F32)
@@ -299,9 +308,6 @@ void delay_line_forward(const void *x, void *y, int dtype, int64_t C, int64_t T,
 // Same expression as delay_line_kernel, in this file and under the same contraction setting, so a chunk's samples are the
 // one-shot kernel's bits; with hist_in null the first D outputs are copies of x, as the one-shot kernel leaves them.  The
 // workgroups past the output tiles write hist_out (one launch per chunk).  Scalar loads: rows of any alignment.
-constexpr int EFX_STR_E = 4;                               // samples per thread
-constexpr int64_t EFX_STR_TILE = (int64_t)EFX_THREADS * EFX_STR_E;
-
 template <typename T>
 __global__ void __launch_bounds__(EFX_THREADS)
 delay_line_stream_kernel(const T *__restrict__ x, const T *__restrict__ hist_in, T *__restrict__ y, T *__restrict__ hist_out,
@@ -366,7 +372,20 @@ void delay_line_stream_forward(const void *x, void *y, int dtype, int64_t C, int
 }
 
 // ---- host ---------------------------------------------------------------------------------------
-static inline int64_t efx_tiles(int64_t T, int esz) { return ceil_div(T, (int64_t)EFX_U * EFX_THREADS * (16 / esz)); }
+// the geometry of the launches of this file for rows of T samples (host-only): what the edge tests take their shapes from
+void effects_plan_info(int64_t T, int dtype, int64_t *vec, int64_t *tile, int64_t *group, int64_t *groups, int64_t *finish_threads,
+                       int64_t *stream_tile)
+{
+    TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "effects_plan_info: bad dtype %d", dtype);
+    TFX_CHECK(T >= 0, "effects_plan_info: negative length");
+    const int esz = dtype == TFX_F32 ? 4 : 8;
+    *vec = 16 / esz;
+    *tile = efx_tile(esz);
+    *group = EFX_RT * efx_tile(esz);
+    *groups = efx_groups(T, esz);
+    *finish_threads = EFX_FINISH_THREADS;
+    *stream_tile = EFX_STR_TILE;
+}
 
 void gain_forward(const void *x, void *y, int dtype, int64_t n, double gain, int clamp, hipStream_t stream)
 {
@@ -391,7 +410,7 @@ void gain_forward(const void *x, void *y, int dtype, int64_t n, double gain, int
 static void stat_launch(const void *x, int dtype, int64_t rows, int64_t T, int mode, double *stat_dev, hipStream_t stream)
 {
     const int esz = dtype == TFX_F32 ? 4 : 8;
-    const int64_t groups = ceil_div(efx_tiles(T, esz), (int64_t)EFX_RT);
+    const int64_t groups = efx_groups(T, esz);
     TFX_CHECK(rows * groups < (1ll << 31), "stat_forward: grid too large");
     double *partial = (double *)scratch("efx_partial", (size_t)(rows * groups) * sizeof(double), stream);
 #define TFX_RED_LAUNCH(TT, MODE_)                                                                              \
@@ -402,7 +421,7 @@ static void stat_launch(const void *x, int dtype, int64_t rows, int64_t T, int m
                                stream, (const TT *)x, T, groups, partial);                                     \
         }                                                                                                      \
         ProfScope ps("reduce_finish_kernel", stream);                                                          \
-        hipLaunchKernelGGL(reduce_finish_kernel<MODE_>, dim3((unsigned)rows), dim3(1024), 0, stream, partial,  \
+        hipLaunchKernelGGL(reduce_finish_kernel<MODE_>, dim3((unsigned)rows), dim3(EFX_FINISH_THREADS), 0, stream, partial,  \
                            groups, stat_dev);                                                                  \
     }
     if (dtype == TFX_F32) {
@@ -443,8 +462,8 @@ void stat_forward(const void *x, int dtype, int64_t C, int64_t T, int mode, int 
 void stat_finish(const double *partial, int64_t rows, int64_t groups, int mode, double *stat_dev, hipStream_t stream)
 {
     ProfScope ps("reduce_finish_kernel", stream);
-    if (mode == 0) hipLaunchKernelGGL(reduce_finish_kernel<0>, dim3((unsigned)rows), dim3(1024), 0, stream, partial, groups, stat_dev);
-    else hipLaunchKernelGGL(reduce_finish_kernel<1>, dim3((unsigned)rows), dim3(1024), 0, stream, partial, groups, stat_dev);
+    if (mode == 0) hipLaunchKernelGGL(reduce_finish_kernel<0>, dim3((unsigned)rows), dim3(EFX_FINISH_THREADS), 0, stream, partial, groups, stat_dev);
+    else hipLaunchKernelGGL(reduce_finish_kernel<1>, dim3((unsigned)rows), dim3(EFX_FINISH_THREADS), 0, stream, partial, groups, stat_dev);
     TFX_HIP(hipGetLastError());
 }
 

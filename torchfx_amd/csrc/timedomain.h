@@ -32,6 +32,8 @@ void delay_line_forward(const void *x, void *y, int dtype, int64_t C, int64_t T,
                         hipStream_t stream);
 void delay_line_stream_forward(const void *x, void *y, int dtype, int64_t C, int64_t T, int64_t delay, double coeff,
                                const void *hist_in, void *hist_out, hipStream_t stream);
+void effects_plan_info(int64_t T, int dtype, int64_t *vec, int64_t *tile, int64_t *group, int64_t *groups, int64_t *finish_threads,
+                       int64_t *stream_tile);
 
 // ---- select.hip ----
 void quantile_abs_forward(const float *x, int64_t n, double q, double *out_dev, hipStream_t stream);

@@ -39,7 +39,7 @@ __all__ = [
     "limiter_stream_forward", "limiter_stream_plan_info", "compressor_forward", "compressor_plan_info",
     "modulated_delay_forward", "modulated_delay_stream_forward", "modulated_delay_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
-    "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
+    "effects_plan_info", "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
 ]
 
 
@@ -603,6 +603,16 @@ def normalize_forward(x: Tensor, peak: float, mode: int = STAT_ABSMAX, per_row: 
     """``s > 0 ? x / s * peak : x`` with ``s`` = abs-max or RMS, global or per row of the ``[rows, T]`` view
     (``effect.py:696-698,719-721,775-786``); two streaming passes, statistic stays on device."""
     return native.ops().normalize_forward(x, float(peak), int(mode), bool(per_row))
+
+
+def effects_plan_info(length: int, dtype: torch.dtype = torch.float32) -> dict:
+    """The geometry of :func:`gain_forward`, :func:`stat_forward`, :func:`normalize_forward`, :func:`sum_forward` and the two
+    delay-line ops for rows of ``length`` samples (``tfx_effects_plan_info``; host-only, the launches' own constants): ``vec``
+    (samples per 16-byte vector), ``tile`` (samples per workgroup of an elementwise pass), ``group`` (samples one first-stage
+    reduce workgroup turns into one partial), ``groups`` (partials per row), ``finish_threads`` (threads of the second stage's
+    workgroup; more partials than that take strided trips) and ``stream_tile`` (samples per workgroup of
+    :func:`delay_line_stream_forward`)."""
+    return _query(L.load().tfx_effects_plan_info, (int(length), _dt(dtype)), "vec tile group groups finish_threads stream_tile")
 
 
 def deinterleave_forward(frames: Tensor, out: Tensor | None = None, frame_base: int = 0,
