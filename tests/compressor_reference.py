@@ -37,9 +37,11 @@ def detector(v, aA, aR, state=(0.0, 0.0)):
 
 
 def compress_ref(x, fs, threshold_db=-20.0, ratio=4.0, attack=5e-3, release=100e-3, knee_db=6.0, makeup_db=0.0, link=True,
-                 state=None):
+                 state=None, alphas_=None, trace=None):
     """``x`` a NumPy array ``[T]``, ``[C, T]`` or ``[B, C, T]`` (float32 / float64) -> ``(y float64 like x, g float64
-    [groups, T], end state float64 [groups, 2])``; ``y`` is the unrounded float64 product ``g * x``."""
+    [groups, T], end state float64 [groups, 2])``; ``y`` is the unrounded float64 product ``g * x``.  ``alphas_ = (aA, aR)``
+    takes the place of the coefficients of ``attack`` and ``release`` (what the low-level op is given); a dict ``trace``
+    receives the loop's ``v`` and ``y1`` as ``[groups, T]`` arrays."""
     x = np.asarray(x)
     T = x.shape[-1]
     rows = int(np.prod(x.shape[:-1], dtype=np.int64))
@@ -47,8 +49,9 @@ def compress_ref(x, fs, threshold_db=-20.0, ratio=4.0, attack=5e-3, release=100e
     groups = rows // channels
     xg = x.reshape(groups, channels, T).astype(np.float64)
     s = 1.0 - 1.0 / ratio
-    aA, aR = alphas(fs, attack, release)
+    aA, aR = alphas(fs, attack, release) if alphas_ is None else alphas_
     g = np.empty((groups, T))
+    tv, t1 = np.empty((groups, T)), np.empty((groups, T))
     end = np.zeros((groups, 2))
     for k in range(groups):
         with np.errstate(invalid="ignore"):
@@ -59,6 +62,9 @@ def compress_ref(x, fs, threshold_db=-20.0, ratio=4.0, attack=5e-3, release=100e
         y1, yl = detector(v, aA, aR, st)
         g[k] = 10.0 ** ((makeup_db - yl) / 20.0)
         end[k] = (y1[-1], yl[-1]) if T else st
+        tv[k], t1[k] = v, y1
+    if trace is not None:
+        trace["v"], trace["y1"] = tv, t1
     y = (g[:, None, :] * xg).reshape(x.shape)
     return y, g, end
 

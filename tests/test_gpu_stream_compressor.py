@@ -1,7 +1,9 @@
 """StatefulCompressor on the device inside StreamProcessor: chunk sizes 1, 7, 512 and tile + 1, eager and as a replayed HIP
-graph, against compress() on the whole signal; and the chain HiButterworth | StatefulCompressor | StatefulLimiter against the
+graph, against compress() on the whole signal and against the definition (tests/compressor_reference.py); and the chain HiButterworth | StatefulCompressor | StatefulLimiter against the
 staged one-shot chain.  Chunks equal the one-shot call within the accuracy bound of tests/test_gpu_compressor.py, not bit for
 bit: the scan's association follows the cut."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -33,6 +35,17 @@ def chunk_cases():
     return {1: 300, 7: 7 * 60 + 3, 512: 512 * 9 + 100, t + 1: 3 * (t + 1) + 50}
 
 
+def stream_signal(case, dtype):
+    B, n = list(chunk_cases().items())[case]
+    return B, torch.from_numpy(R.bursty(np.random.default_rng(case), (2, n), burst=n // 5, gap=n // 4)).to(dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def definition(case, dtype):
+    """``compress_ref`` (the per-sample float64 loop) on a case's whole signal, computed once for the eager and the graph run."""
+    return R.compress_ref(stream_signal(case, dtype)[1].numpy(), FS, **KW)
+
+
 @pytest.mark.parametrize("use_graph", [False, True], ids=["eager", "graph"])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
 @pytest.mark.parametrize("case", [0, 1, 2, 3], ids=["1", "7", "512", "tile+1"])
@@ -40,8 +53,7 @@ def test_stream_processor_chunks_equal_the_one_shot_call(case, dtype, use_graph)
     from torchfx_amd import compress
     from torchfx_amd.realtime import StatefulCompressor, StreamProcessor
 
-    B, n = list(chunk_cases().items())[case]
-    x = torch.from_numpy(R.bursty(np.random.default_rng(case), (2, n), burst=n // 5, gap=n // 4)).to(dtype)
+    B, x = stream_signal(case, dtype)
     ref, g = compress(x.to(DEV), FS, return_gain=True, **KW)
     assert float(g.min()) < 0.7                                       # the compressor is at work
     comp = StatefulCompressor(**KW)
@@ -51,6 +63,9 @@ def test_stream_processor_chunks_equal_the_one_shot_call(case, dtype, use_graph)
     bound(got, ref, dtype)
     st = compress(x.to(DEV), FS, return_state=True, **KW)[1]
     assert comp._hist.shape == (1, 2) and float((comp._hist - st).abs().max()) <= 1e-10
+    y_def, _, st_def = definition(case, dtype)                        # and with the definition itself, under the same bound
+    bound(got, torch.from_numpy(y_def), dtype)
+    assert float((comp._hist.cpu() - torch.from_numpy(st_def)).abs().max()) <= 1e-10
 
 
 def test_chain_with_filter_and_limiter_equals_the_staged_one_shot_chain():

@@ -151,6 +151,8 @@ def compress(x: Tensor, fs: int, threshold_db: float = -20.0, ratio: float = 4.0
     * **Static curve.**  A constant level ``L`` above the knee settles to the output level ``Th + (L - Th) / ratio``.
     * **Attack.**  After a step of ``v`` from 0 to ``v0``, ``yL[n] = v0 (1 - aA^(n+1))``.
     * **Release.**  After ``v`` drops to 0, ``y1`` decays as ``aR^n``.
+    * **Hold.**  A release so long that ``aR`` rounds to 1 (``release = 1e300``) holds the peak: ``y1`` is the running maximum
+      of ``v``, without any rounding.
     * **Chunks.**  Feeding the returned state into the next call continues the curve: chunks equal the one-shot result to
       float64 round-off of the detector (the scan's association follows the cut), not bit for bit.
     * **Non-finite input.**  From the first NaN / Inf sample of a group to the end of its rows every output, the gain and the
