@@ -666,6 +666,47 @@ int tfx_modulated_delay_plan_info(int64_t batch, int64_t channels, int64_t T, co
                                   int64_t *tile, int64_t *tiles, int64_t *history, int64_t *batch_items, int64_t *batch_groups);
 
 /* ---------------------------------------------------------------------------
+ * tfx_freeverb_forward -- Freeverb (Jezar at Dreampoint, public domain), the Schroeder-Moorer room reverb: per *bank* (one
+ * channel of one batch item) NC parallel feedback combs with a one-pole low-pass in the loop, summed, then NA all-passes in
+ * series.  x is [batch, channels, T], channels 1 or 2; y is [batch, channels, T + tail] (x counts as zero from T on).
+ * comb_delays_host HOST int64 [channels, NC], 1 <= NC <= 8; allpass_delays_host HOST int64 [channels, NA], 0 <= NA <= 4 (may be
+ * null for NA = 0); every delay in [1, 65536] samples.  Everything is float64 for both signal dtypes.  For an item and a sample n:
+ *   feed       u[n] = input_gain (2 / channels) sum_c x_c[n]          ((L + R) gain for stereo, L = R for mono)
+ *   comb k     o_k[n] = w_k[n - D];  f_k[n] = d2 o_k[n] + d1 f_k[n-1];  w_k[n] = u[n] + feedback f_k[n];  d1 = damp, d2 = 1 - d1
+ *   comb sum   s_0[n] = ((o_0[n] + o_1[n]) + o_2[n]) + ...            in this order
+ *   all-pass j b[n] = v_j[n - D];  s_{j+1}[n] = b[n] - s_j[n];  v_j[n] = s_j[n] + allpass_gain b[n]
+ *   mix        y_c[n] = dtype(dry_gain x_c[n] + wet1 r_c[n] + wet2 r_{1-c}[n]),  r_c = s_NA of bank c; for one channel
+ *              dtype(dry_gain x[n] + (wet1 + wet2) r_0[n]); summed left to right, rounded once
+ * |feedback| < 1, 0 <= damp < 1, |allpass_gain| < 1, the four gains finite.  w, f and v are zero before sample 0 unless
+ * state_in is given.
+ * State: DEVICE float64 [batch * channels, state_len], one row per bank: for each comb the last D values of w, oldest first,
+ * then f; then for each all-pass the last D values of v, oldest first; state_len is the longest bank's length and a shorter
+ * bank's row ends in zeros.  Time order, not ring order: the state does not depend on how the stream was cut, and chunks
+ * shorter than a delay work.  state_in null = silence, state_out null = not stored; state_out needs its own buffer.
+ * One workgroup per bank and one wave per comb: blocks of B = min(shortest comb delay, 1024) samples; within a block the
+ * low-pass is an affine scan over the 64 lanes, the all-passes run in parallel over sub-blocks of up to their delay.  The
+ * lines are float64 rings in LDS (TFX_FREEVERB_LINES_LDS) when 8 (line words + 2 B) <= 159 KB, else in `workspace`
+ * (TFX_FREEVERB_LINES_GLOBAL).  One launch when channels == 1 or wet2 == 0; else the banks write r to `workspace` and a
+ * second, elementwise launch mixes.  workspace: DEVICE, workspace_bytes of the plan, may be null when that is 0.  No
+ * workgroup waits for another, no atomics.  The scan's association follows the blocks, and the blocks the start of the call:
+ * chunked calls agree with the one-shot call to float64 round-off, not bit for bit.  A bank's bits depend on its item's
+ * samples, T, tail and the arguments alone -- not on the other items or their number.  Samples before an item's first
+ * non-finite input sample are unaffected by it; other items never are.  x, y DEVICE of dtype, y may not overlap x.  Arguments
+ * are checked before the device is touched.  T + tail == 0 copies state_in to state_out.
+ * ------------------------------------------------------------------------- */
+enum tfx_freeverb_lines { TFX_FREEVERB_LINES_LDS = 0, TFX_FREEVERB_LINES_GLOBAL = 1 };
+int tfx_freeverb_forward(const void *x, void *y, int dtype, int64_t batch, int64_t channels, int64_t T, int64_t tail,
+                         const int64_t *comb_delays_host, int64_t NC, const int64_t *allpass_delays_host, int64_t NA, double feedback,
+                         double damp, double allpass_gain, double input_gain, double dry_gain, double wet1, double wet2,
+                         const double *state_in, double *state_out, void *workspace, tfx_stream_t stream);
+/* what tfx_freeverb_forward does (host-only, same checks on the sizes and the delays): the block size B, where the lines live
+ * (tfx_freeverb_lines), the length of a state row, the launches (1 or 2) and the bytes of `workspace` (the lines of every bank
+ * for the global placement, then [batch * channels, T + tail] float64 for two launches) */
+int tfx_freeverb_plan_info(int64_t batch, int64_t channels, int64_t T, int64_t tail, const int64_t *comb_delays_host, int64_t NC,
+                           const int64_t *allpass_delays_host, int64_t NA, double wet2, int64_t *block, int *placement,
+                           int64_t *state_len, int64_t *launches, int64_t *workspace_bytes);
+
+/* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of
  * ParallelFilterCombination.forward, src/torchfx/filter/__base.py:1019-1026).
  * xs_host: HOST array of n DEVICE pointers, each [numel] of dtype.

@@ -7,7 +7,7 @@ from torchfx_amd import filter  # noqa: A004
 from torchfx_amd._ops import is_native_available
 from torchfx_amd.chain import FilterChain
 from torchfx_amd.dynamics import compress
-from torchfx_amd.effect import (FX, Chorus, Compressor, Delay, Flanger, Gain, Limiter, LoudnessNormalize, ModulatedDelay, Normalize, Reverb,
+from torchfx_amd.effect import (FX, Chorus, Compressor, Delay, Flanger, Freeverb, Gain, Limiter, LoudnessNormalize, ModulatedDelay, Normalize, Reverb,
                                 Vibrato)
 from torchfx_amd.filtfilt import sosfiltfilt
 from torchfx_amd.limiter import limit
@@ -15,9 +15,10 @@ from torchfx_amd.loudness import (block_energy, integrated_loudness, kweighting_
                                   short_term_loudness, true_peak, true_peak_linear)
 from torchfx_amd.modulation import modulated_delay
 from torchfx_amd.resample import Resample, resample_poly
+from torchfx_amd.reverb import freeverb, freeverb_bank
 from torchfx_amd.wave import Wave
 
-__all__ = ["FX", "Chorus", "Compressor", "Delay", "FilterChain", "Flanger", "Gain", "Limiter", "LoudnessNormalize", "ModulatedDelay", "Normalize", "Resample", "Reverb", "Wave", "block_energy",
-           "compress", "filter", "integrated_loudness", "is_native_available", "kweighting_sos", "limit", "loudness_range", "modulated_delay", "momentary_loudness",
+__all__ = ["FX", "Chorus", "Compressor", "Delay", "FilterChain", "Flanger", "Freeverb", "Gain", "Limiter", "LoudnessNormalize", "ModulatedDelay", "Normalize", "Resample", "Reverb", "Wave", "block_energy",
+           "compress", "filter", "freeverb", "freeverb_bank", "integrated_loudness", "is_native_available", "kweighting_sos", "limit", "loudness_range", "modulated_delay", "momentary_loudness",
            "resample_poly", "short_term_loudness", "sosfiltfilt", "true_peak", "true_peak_linear", "Vibrato"]
 __version__ = "0.1.0"

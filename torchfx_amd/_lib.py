@@ -93,6 +93,9 @@ SIGNATURES = {
     "tfx_modulated_delay_stream_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _dbl, _dbl, _int, _int, _vp, _vp, _vp,
                                                   _vp, _vp]),
     "tfx_modulated_delay_plan_info": (_int, [_i64, _i64, _i64, _vp, _i64, _int] + [ctypes.POINTER(_i64)] * 5),
+    "tfx_freeverb_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64] + [_dbl] * 7 + [_vp, _vp, _vp, _vp]),
+    "tfx_freeverb_plan_info": (_int, [_i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _dbl, ctypes.POINTER(_i64), ctypes.POINTER(_int)]
+                               + [ctypes.POINTER(_i64)] * 3),
     "tfx_sum_forward": (_int, [_vp, _int, _vp, _int, _i64, _vp]),
     "tfx_gain_forward": (_int, [_vp, _vp, _int, _i64, _dbl, _int, _vp]),
     "tfx_stat_forward": (_int, [_vp, _int, _i64, _i64, _int, _int, _vp, _vp]),

@@ -731,6 +731,28 @@ int tfx_modulated_delay_plan_info(int64_t batch, int64_t channels, int64_t T, co
     TFX_API_END
 }
 
+int tfx_freeverb_forward(const void *x, void *y, int dtype, int64_t batch, int64_t channels, int64_t T, int64_t tail,
+                         const int64_t *comb_delays_host, int64_t NC, const int64_t *allpass_delays_host, int64_t NA, double feedback,
+                         double damp, double allpass_gain, double input_gain, double dry_gain, double wet1, double wet2,
+                         const double *state_in, double *state_out, void *workspace, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    freeverb_forward(x, y, dtype, batch, channels, T, tail, comb_delays_host, NC, allpass_delays_host, NA, feedback, damp, allpass_gain,
+                     input_gain, dry_gain, wet1, wet2, state_in, state_out, workspace, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_freeverb_plan_info(int64_t batch, int64_t channels, int64_t T, int64_t tail, const int64_t *comb_delays_host, int64_t NC,
+                           const int64_t *allpass_delays_host, int64_t NA, double wet2, int64_t *block, int *placement,
+                           int64_t *state_len, int64_t *launches, int64_t *workspace_bytes)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(block && placement && state_len && launches && workspace_bytes, "freeverb_plan_info: null output");
+    freeverb_plan_info(batch, channels, T, tail, comb_delays_host, NC, allpass_delays_host, NA, wet2, block, placement, state_len,
+                       launches, workspace_bytes);
+    TFX_API_END
+}
+
 int tfx_sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, tfx_stream_t stream)
 {
     TFX_API_BEGIN

@@ -613,6 +613,64 @@ std::tuple<Tensor, Tensor, Tensor> compressor_op(const Tensor &x_in, double th, 
     return std::make_tuple(y, gain, sout);
 }
 
+// Freeverb (tfx_freeverb_forward): x [T], [C, T] or [B, C, T] with C 1 or 2; comb_delays / allpass_delays the flattened
+// [C, NC] / [C, NA] tables in samples; state [B * C, state_len] float64 or None (silence) -> (y [..., T + tail], new state).
+// The shape and the tables are checked here and by the plan, before anything touches the device; the workspace (global lines,
+// the wet signal between two launches) is a tensor from torch's allocator.
+struct FreeverbInputs {
+    Tensor x;
+    std::vector<int64_t> comb, allpass, yshape;
+    int dt, placement;
+    int64_t batch, channels, T, NC, NA, block, state_len, launches, workspace_bytes;
+};
+
+FreeverbInputs freeverb_inputs(const Tensor &x, at::IntArrayRef comb_delays, at::IntArrayRef allpass_delays, double wet2, int64_t tail,
+                               const char *what)
+{
+    TORCH_CHECK(x.dim() >= 1 && x.dim() <= 3, what, ": x must be [T], [C, T] or [B, C, T], got ", x.dim(), " dimensions");
+    TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kDouble, what, ": float32 or float64 only, got ", x.scalar_type());
+    FreeverbInputs in;
+    in.dt = x.scalar_type() == at::kFloat ? TFX_F32 : TFX_F64;
+    in.T = x.size(-1);
+    in.channels = x.dim() >= 2 ? x.size(-2) : 1;
+    in.batch = x.dim() == 3 ? x.size(0) : 1;
+    TORCH_CHECK(in.channels == 1 || in.channels == 2, what, ": channels must be 1 or 2, got ", in.channels);
+    TORCH_CHECK(comb_delays.size() % in.channels == 0 && allpass_delays.size() % in.channels == 0, what,
+                ": the delay tables must hold one row per channel");
+    in.comb.assign(comb_delays.begin(), comb_delays.end());
+    in.allpass.assign(allpass_delays.begin(), allpass_delays.end());
+    in.NC = (int64_t)in.comb.size() / in.channels;
+    in.NA = (int64_t)in.allpass.size() / in.channels;
+    check_rc(tfx_freeverb_plan_info(in.batch, in.channels, in.T, tail, in.comb.data(), in.NC, in.NA ? in.allpass.data() : nullptr, in.NA,
+                                    wet2, &in.block, &in.placement, &in.state_len, &in.launches, &in.workspace_bytes),
+             what);
+    in.yshape.assign(x.sizes().begin(), x.sizes().end());
+    in.yshape.back() = in.T + tail;
+    return in;
+}
+
+std::tuple<Tensor, Tensor> freeverb_op(const Tensor &x_in, at::IntArrayRef comb_delays, at::IntArrayRef allpass_delays, double feedback,
+                                       double damp, double allpass_gain, double input_gain, double dry_gain, double wet1, double wet2,
+                                       int64_t tail, const OptTensor &state)
+{
+    const char *what = "freeverb_forward";
+    need_device(x_in, "x");
+    FreeverbInputs in = freeverb_inputs(x_in, comb_delays, allpass_delays, wet2, tail, what);
+    const Tensor x = x_in.contiguous();
+    const int64_t banks = in.batch * in.channels;
+    Tensor keep;
+    const double *sin = state_ptr(state, {banks, in.state_len}, x, "freeverb_forward: state", keep);
+    const auto f64 = x.options().dtype(at::kDouble);
+    Tensor y = at::empty(in.yshape, x.options()), sout = at::empty({banks, in.state_len}, f64),
+           work = at::empty({in.workspace_bytes / 8}, f64);
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_freeverb_forward(x.data_ptr(), y.data_ptr(), in.dt, in.batch, in.channels, in.T, tail, in.comb.data(), in.NC,
+                                  in.NA ? in.allpass.data() : nullptr, in.NA, feedback, damp, allpass_gain, input_gain, dry_gain, wet1,
+                                  wet2, sin, sout.data_ptr<double>(), in.workspace_bytes ? work.data_ptr() : nullptr, stream_of(x)),
+             what);
+    return std::make_tuple(y, sout);
+}
+
 // The modulated delay line (tfx_modulated_delay_forward): x [T], [C, T] or [B, C, T]; voices a host float64 [V, 5] table of
 // (base, depth, inc, phase, gain) rows; shape 0 sine / 1 triangle, interp 0 linear / 1 cubic.  V, the shape of x and the
 // interpolation are checked here, before anything touches the device.
@@ -1097,6 +1155,13 @@ std::tuple<Tensor, Tensor, Tensor> modulated_delay_stream_meta(const Tensor &x, 
     return {at::empty_like(x), at::empty({stream_rows(x), H}, x.options()), at::empty({1}, x.options().dtype(at::kLong))};
 }
 
+std::tuple<Tensor, Tensor> freeverb_meta(const Tensor &x, at::IntArrayRef comb_delays, at::IntArrayRef allpass_delays, double, double,
+                                         double, double, double, double, double wet2, int64_t tail, const OptTensor &)
+{
+    const FreeverbInputs in = freeverb_inputs(x, comb_delays, allpass_delays, wet2, tail, "freeverb_forward");
+    return {at::empty(in.yshape, x.options()), at::empty({in.batch * in.channels, in.state_len}, x.options().dtype(at::kDouble))};
+}
+
 // No CPU branch, by design: every op of the namespace answers a host tensor with the same error instead of the dispatcher's
 // "no kernel for backend CPU" (one boxed function registered for the CPU key of each op; per-namespace fallbacks are not
 // supported by the dispatcher).
@@ -1226,6 +1291,19 @@ TORCH_LIBRARY_IMPL(torchfx_modulation, Meta, m)
         return at::empty_like(x);
     });
     m.impl("modulated_delay_stream_forward", modulated_delay_stream_meta);
+}
+
+// Freeverb likewise: torch.ops.torchfx_reverb.
+TORCH_LIBRARY(torchfx_reverb, m)
+{
+    reg_op(m, "freeverb_forward(Tensor x, int[] comb_delays, int[] allpass_delays, float feedback, float damp, float allpass_gain, "
+              "float input_gain, float dry_gain, float wet1, float wet2, int tail=0, Tensor? state=None) -> (Tensor, Tensor)",
+           freeverb_op);
+}
+
+TORCH_LIBRARY_IMPL(torchfx_reverb, Meta, m)
+{
+    m.impl("freeverb_forward", freeverb_meta);
 }
 
 // The reference's module surface (binding.cpp:83-96): exactly these three names and argument lists.

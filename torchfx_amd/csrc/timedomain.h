@@ -1,5 +1,5 @@
 // timedomain.h -- the host entry points of the time-domain and elementwise ops, one prototype per exported function of fir.hip,
-// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip, compressor.hip, modulation.hip and layout.hip (the cascade's: sos.h; the
+// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip, compressor.hip, modulation.hip, reverb.hip and layout.hip (the cascade's: sos.h; the
 // overlap-save pipelines': ols_route.h).  Included by the file that defines each function and by capi.hip, so a prototype that drifts from
 // its definition does not compile; default arguments live here and nowhere else.  Every *_forward checks its arguments before
 // anything touches the device; a *_plan_info takes the same checking path without the pointers.
@@ -108,6 +108,15 @@ void modulated_delay_stream_forward(const void *x, void *y, int dtype, int64_t b
 void modulated_delay_plan_info(int64_t batch, int64_t channels, int64_t T, const double *voices_host, int64_t V, int interp,
                                int64_t *tile, int64_t *tiles, int64_t *history, int64_t *batch_items, int64_t *batch_groups);
 void modulation_clear();
+
+// ---- reverb.hip ----
+void freeverb_forward(const void *x, void *y, int dtype, int64_t batch, int64_t channels, int64_t T, int64_t tail,
+                      const int64_t *comb_delays_host, int64_t NC, const int64_t *allpass_delays_host, int64_t NA, double feedback,
+                      double damp, double allpass_gain, double input_gain, double dry_gain, double wet1, double wet2,
+                      const double *state_in, double *state_out, void *workspace, hipStream_t stream);
+void freeverb_plan_info(int64_t batch, int64_t channels, int64_t T, int64_t tail, const int64_t *comb_delays_host, int64_t NC,
+                        const int64_t *allpass_delays_host, int64_t NA, double wet2, int64_t *block, int *placement,
+                        int64_t *state_len, int64_t *launches, int64_t *workspace_bytes);
 
 // ---- layout.hip ----
 void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, int64_t C, int64_t ld_out, int64_t f_base,

@@ -512,6 +512,72 @@ class Epilogued(FX):
         return y
 
 
+class Freeverb(FX):
+    """Freeverb room reverb (Jezar at Dreampoint's Schroeder-Moorer network, public domain):
+    :func:`torchfx_amd.reverb.freeverb` with the same parameters -- ``room_size``, ``damping``, ``wet``, ``dry`` and ``width`` in
+    ``[0, 1]`` and ``tail`` in seconds (``>= 0``: that much ring-out is appended to the signal).  Per channel eight feedback combs
+    with a damping low-pass in the loop, then four all-passes, at Freeverb's tunings scaled from 44.1 kHz to ``fs``; signals
+    of one or two channels, all arithmetic in float64.  ``wet = 0, dry = 0.5`` returns the input bit for bit.
+
+    ``fs`` comes from the ``Wave`` the effect is piped into when it is None.  Every call starts from silent delay lines: the
+    reverb is a step of its own in ``Wave.plan()`` (``csrc/reverb.hip``: one workgroup per channel of a batch item) and a
+    chunked stream needs :class:`torchfx_amd.realtime.StatefulFreeverb`, which carries the lines from chunk to chunk."""
+
+    def __init__(self, room_size: float = 0.5, damping: float = 0.5, wet: float = 1.0 / 3.0, dry: float = 0.5, width: float = 1.0,
+                 tail: float = 0.0, fs: int | None = None) -> None:
+        super().__init__()
+        from torchfx_amd.reverb import FreeverbParams
+
+        FreeverbParams(48000 if fs is None else fs, room_size, damping, wet, dry, width, tail)      # argument errors now
+        self.room_size, self.damping, self.wet, self.dry = float(room_size), float(damping), float(wet), float(dry)
+        self.width, self.tail, self.fs = float(width), float(tail), fs
+
+    def params(self):
+        """The call's :class:`torchfx_amd.reverb.FreeverbParams` at ``self.fs``."""
+        if self.fs is None:
+            raise ValueError(f"{type(self).__name__} needs the sample rate: pass fs or pipe a Wave into it (wave | Freeverb())")
+        from torchfx_amd.reverb import FreeverbParams
+
+        return FreeverbParams(self.fs, self.room_size, self.damping, self.wet, self.dry, self.width, self.tail)
+
+    def output_length(self, length: int) -> int:
+        """Samples per row this effect returns for rows of ``length`` samples: ``length + floor(tail fs + 0.5)``."""
+        return int(length) + (self.params().tail_samples if self.fs is not None else 0)
+
+    def route(self, x: Tensor, length: int | None = None) -> str:
+        """``native (...)`` or ``numpy on host -- <reason>`` for ``x`` (rows of ``length`` samples, default x's)."""
+        if not x.is_cuda:
+            return f"numpy on host -- {x.device.type} tensor"
+        try:
+            from torchfx_amd.reverb import _shape
+
+            F = self.params()
+            batch, channels, T = _shape(x)
+            P = F.bank(channels)
+            info = _ext().freeverb_plan_info(T if length is None else int(length), P.comb, P.allpass, batch, channels, P.wet2,
+                                             self._call_tail(F))
+        except (RuntimeError, ValueError, TypeError) as e:
+            return f"refused -- {e}"
+        where = "LDS" if info["placement"] == "lds" else "a global workspace"
+        launches = "one launch" if info["launches"] == 1 else "two launches (banks, then the cross-channel mix)"
+        return (f"native (freeverb_kernel, one workgroup per bank and one wave per comb, blocks of {info['block']} samples, "
+                f"delay lines in {where}; {launches})")
+
+    def _call_tail(self, F) -> int:
+        return F.tail_samples
+
+    @torch.no_grad()
+    def forward(self, waveform: Tensor) -> Tensor:
+        from torchfx_amd.reverb import freeverb
+
+        self.params()
+        return freeverb(waveform, self.fs, self.room_size, self.damping, self.wet, self.dry, self.width, self.tail)
+
+    def extra_repr(self) -> str:
+        return (f"room_size={self.room_size}, damping={self.damping}, wet={self.wet}, dry={self.dry}, width={self.width}, "
+                f"tail={self.tail}, fs={self.fs}")
+
+
 class Reverb(FX):
     """``y[n] = x[n] + mix * decay * x[n - delay]`` -- the reference's "reverb" is one feed-forward
     tap (``effect.py:789-931`` over ``delay_line_forward``, ``_csrc/cpu/delay_cpu.cpp:17-41``); a

@@ -79,3 +79,11 @@ def modulation_ops():
 
     load()
     return torch.ops.torchfx_modulation
+
+
+def reverb_ops():
+    """``torch.ops.torchfx_reverb`` (Freeverb's namespace, registered by the same module) with the library loaded."""
+    import torch
+
+    load()
+    return torch.ops.torchfx_reverb

@@ -23,7 +23,9 @@ stream: causal, no latency, it carries the detector's ``(y1, yL)`` per group (``
 equal ``compress`` on the whole signal to float64 round-off of the detector (not bit for bit).  :class:`StatefulChorus`,
 :class:`StatefulFlanger` and :class:`StatefulVibrato` are the modulation effects of a stream: causal, no latency, they carry the
 delay line's reach in ``_hist`` and the LFO's position in ``_pos`` (a device counter, ``tfx_modulated_delay_stream_forward``), and
-their chunks are bit-identical to the one-shot effect on the whole signal.
+their chunks are bit-identical to the one-shot effect on the whole signal.  :class:`StatefulFreeverb` is the room reverb of a
+stream: causal, no latency, it carries every delay line in time order (``tfx_freeverb_forward``'s state), its chunks equal
+``freeverb`` on the whole signal to float64 round-off (not bit for bit) and ``flush()`` returns the ring-out.
 
 Small chunks are launch-bound (a 2 x 4096 step is ~60 us of host + launch overhead for a few us of
 GPU work), so ``StreamProcessor(..., use_graph=True)`` captures one full-size chunk step -- every
@@ -43,7 +45,7 @@ from collections.abc import Generator, Sequence
 import torch
 from torch import Tensor, nn
 
-from torchfx_amd.effect import (FX, Chorus, Compressor, Delay, Flanger, Limiter, ModulatedDelay, MonoDelayStrategy, PingPongDelayStrategy,
+from torchfx_amd.effect import (FX, Chorus, Compressor, Delay, Flanger, Freeverb, Limiter, ModulatedDelay, MonoDelayStrategy, PingPongDelayStrategy,
                                 Reverb, Vibrato, _ext)
 from torchfx_amd.filter._base import AbstractFilter
 from torchfx_amd.filter.fir import FIR
@@ -597,6 +599,76 @@ def _refuse_compressor(e, who: str) -> None:
                         "whole signal (wave | Compressor(...)) before or after streaming")
 
 
+class StatefulFreeverb(_RingOut, Freeverb):
+    """:class:`~torchfx_amd.effect.Freeverb` over a continuous stream: the delay lines go from chunk to chunk, so the room's
+    tail has no seam.  The reverb is causal with no latency: every chunk returns the chunk's shape; with ``tail > 0``
+    :meth:`flush` returns the ring-out (``[..., floor(tail fs + 0.5)]``) and resets the state.
+
+    The state lives in ``_hist`` (``[banks, state_len]`` float64 on the chunks' device: per bank every comb's last ``D`` values
+    and its low-pass state, then every all-pass's last ``D`` values, oldest first -- :func:`~torchfx_amd.reverb.freeverb_bank`)
+    and is rebuilt from silence when the leading shape, the device or the sample rate changes; :meth:`reset_state` does the
+    same on request.  ``room_size``, ``damping``, ``wet``, ``dry`` and ``width`` may change between chunks.  The state is in time
+    order, so chunks shorter than a delay work and the state does not depend on the chunk sizes; all chunks together (then
+    ``flush()``) equal :func:`~torchfx_amd.reverb.freeverb` on the whole signal to float64 round-off and not bit for bit: the
+    damping scan's association follows the cut.  After a NaN or Inf the state of its item is not finite and stays so until
+    :meth:`reset_state`.  Device float32 / float64 chunks run :func:`torchfx_ext.freeverb_forward`, CPU chunks the host path."""
+
+    def __init__(self, room_size: float = 0.5, damping: float = 0.5, wet: float = 1.0 / 3.0, dry: float = 0.5, width: float = 1.0,
+                 tail: float = 0.0, fs: int | None = None) -> None:
+        super().__init__(room_size, damping, wet, dry, width, tail, fs)
+        self.reset_state()
+
+    def reset_state(self) -> None:
+        self._hist: Tensor | None = None            # [banks, state_len] float64; None = silence
+        self._key: tuple | None = None              # what the running stream is bound to
+        self._last: tuple | None = None
+
+    def _capture_key(self) -> tuple:
+        """What a captured HIP graph of this effect bakes in."""
+        return (self.room_size, self.damping, self.wet, self.dry, self.width, self.fs)
+
+    def _sync_history(self) -> None:
+        """Nothing to resize: the state's shape follows the rows and the rate alone, and a change of either restarts the stream."""
+
+    def _call_tail(self, F) -> int:
+        return 0                                    # a chunk returns the chunk's shape; the ring-out is flush()'s
+
+    @torch.no_grad()
+    def forward(self, x: Tensor) -> Tensor:
+        _rows(x)
+        if self.fs is None:
+            raise ValueError("StatefulFreeverb needs the sample rate: pass fs or let the processor configure it")
+        from torchfx_amd.reverb import _shape, freeverb_bank
+
+        key = (tuple(x.shape[:-1]), x.device, self.fs)
+        if key != self._key:                        # a new stream: from silence
+            self.reset_state()
+            self._key = key
+        self._note(x)
+        P = self.params().bank(_shape(x)[1])
+        y, self._hist = freeverb_bank(x, P.comb, P.allpass, P.fb, P.d1, P.g, P.input_gain, P.dry, P.wet1, P.wet2, 0, self._hist, True)
+        return y
+
+    @torch.no_grad()
+    def flush(self) -> Tensor:
+        """The ring-out of the stream (the ``floor(tail fs + 0.5)`` samples the one-shot effect appends), shaped like the last
+        chunk; then the state is reset.  Without a chunk since the last reset, or with ``tail = 0``: an empty tensor."""
+        if self._last is None:
+            return torch.zeros(0)
+        n = self.params().tail_samples
+        out = self.forward(self._zeros(n)) if n else self._zeros(0)
+        self.reset_state()
+        return out
+
+
+def _refuse_freeverb(e, who: str) -> None:
+    members = list(e.modules() if isinstance(e, nn.Module) else [e])
+    if any(isinstance(m, Freeverb) and not isinstance(m, StatefulFreeverb) for m in members):
+        raise TypeError(f"Freeverb cannot run in {who}: every call starts from silent delay lines, so a chunked stream would cut "
+                        "the room's tail at every chunk start; use StatefulFreeverb(...) in its place, or run the whole signal "
+                        "(wave | Freeverb(...)) before or after streaming")
+
+
 class _ModulationStream:
     """A modulated delay line (:class:`~torchfx_amd.effect.ModulatedDelay`) over a continuous stream; mixed in in front of the
     effect class.  Every row carries its last ``H = max_v floor(delay_v + depth_v) + 2`` input samples in ``_hist``
@@ -852,6 +924,7 @@ class StreamProcessor:
             _refuse_limiter(e, "StreamProcessor")
             _refuse_compressor(e, "StreamProcessor")
             _refuse_modulation(e, "StreamProcessor")
+            _refuse_freeverb(e, "StreamProcessor")
             if not isinstance(e, StatefulResample) and any(isinstance(m, Resample) for m in e.modules()):
                 raise TypeError("Resample cannot run in StreamProcessor: resampling each chunk on its own leaves a seam at "
                                 "every chunk boundary; use StatefulResample as a top-level effect of the chain, or resample "
@@ -1175,6 +1248,7 @@ class RealtimeProcessor:
             _refuse_limiter(e, "RealtimeProcessor")
             _refuse_compressor(e, "RealtimeProcessor")
             _refuse_modulation(e, "RealtimeProcessor")
+            _refuse_freeverb(e, "RealtimeProcessor")
             if _has_stateful_resample(e):
                 raise TypeError("StatefulResample cannot run in RealtimeProcessor: a sound card's output block has the input "
                                 "block's length and sample rate; resample with StreamProcessor or Wave.resample instead")

@@ -37,7 +37,7 @@ __all__ = [
     "resample_plan_info", "resample_tiling_info", "resample_stream_forward", "resample_stream_plan_info", "sos_filtfilt", "sos_filtfilt_plan_info",
     "sos_block_energy", "sos_block_energy_plan_info", "true_peak", "true_peak_plan_info", "limiter_forward", "limiter_plan_info",
     "limiter_stream_forward", "limiter_stream_plan_info", "compressor_forward", "compressor_plan_info",
-    "modulated_delay_forward", "modulated_delay_stream_forward", "modulated_delay_plan_info",
+    "modulated_delay_forward", "modulated_delay_stream_forward", "modulated_delay_plan_info", "freeverb_forward", "freeverb_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "effects_plan_info", "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
 ]
@@ -420,6 +420,48 @@ def modulated_delay_plan_info(length: int, voices, batch: int = 1, channels: int
     return _query(L.load().tfx_modulated_delay_plan_info,
                   (int(batch), int(channels), int(length), ctypes.c_void_p(t.data_ptr()), int(t.shape[0]),
                    INTERPOLATIONS.index(interpolation)), "tile tiles history batch_items batch_groups")
+
+
+FREEVERB_LINES = ("lds", "global")                       # tfx_freeverb_lines
+
+
+def _delay_table(delays, channels: int, what: str) -> np.ndarray:
+    """A ``[channels, N]`` table of whole-sample delays as a contiguous int64 array (``N`` may be 0)."""
+    a = np.asarray(delays)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"freeverb: {what} must hold integers (samples), got {a.dtype}")
+    return np.ascontiguousarray(a, dtype=np.int64).reshape(int(channels), -1)
+
+
+def freeverb_forward(x: Tensor, comb_delays, allpass_delays, feedback: float, damp: float, allpass_gain: float = 0.5,
+                     input_gain: float = 0.015, dry_gain: float = 1.0, wet1: float = 1.0, wet2: float = 0.0, tail: int = 0,
+                     state: Tensor | None = None) -> tuple[Tensor, Tensor]:
+    """Freeverb (``tfx_freeverb_forward``; the definition is :func:`torchfx_amd.reverb.freeverb_bank`'s): ``x [T]``, ``[C, T]`` or
+    ``[B, C, T]`` on the device (float32 / float64) with ``C`` 1 or 2, ``comb_delays [C, NC]`` and ``allpass_delays [C, NA]`` in
+    samples, ``state [B * C, state_len]`` float64 or None (silence).  One workgroup per bank (``freeverb_kernel``), one launch
+    for ``C = 1`` or ``wet2 = 0``, else a second one mixes (:func:`freeverb_plan_info`).  Returns ``(y [..., T + tail], new
+    state)``.  The op lives in ``torch.ops.torchfx_reverb``."""
+    native.ops()                                         # loads the library: every namespace is registered by the one module
+    C = int(x.shape[-2]) if x.dim() >= 2 else 1
+    return native.reverb_ops().freeverb_forward(x.contiguous(), _delay_table(comb_delays, C, "comb_delays").ravel().tolist(),
+                                                _delay_table(allpass_delays, C, "allpass_delays").ravel().tolist(), float(feedback),
+                                                float(damp), float(allpass_gain), float(input_gain), float(dry_gain), float(wet1),
+                                                float(wet2), int(tail), state)
+
+
+def freeverb_plan_info(length: int, comb_delays, allpass_delays, batch: int = 1, channels: int = 1, wet2: float = 0.0,
+                       tail: int = 0) -> dict:
+    """What :func:`freeverb_forward` does for ``[batch, channels, length]`` (``tfx_freeverb_plan_info``; host-only, same checks
+    on the sizes and the delays): ``block`` (samples per block: the shortest comb delay, at most 1024), ``placement`` (``"lds"``
+    or ``"global"``: where the delay lines live), ``state_len`` (float64 words per bank of the state), ``launches`` (2 when the
+    channels cross-feed: ``channels = 2`` and ``wet2 != 0``) and ``workspace_bytes``."""
+    cd, ad = _delay_table(comb_delays, channels, "comb_delays"), _delay_table(allpass_delays, channels, "allpass_delays")
+    info = _query(L.load().tfx_freeverb_plan_info,
+                  (int(batch), int(channels), int(length), int(tail), ctypes.c_void_p(cd.ctypes.data), int(cd.shape[1]),
+                   ctypes.c_void_p(ad.ctypes.data) if ad.size else None, int(ad.shape[1]), float(wet2)),
+                  "block placement:int state_len launches workspace_bytes")
+    info["placement"] = FREEVERB_LINES[info["placement"]]
+    return info
 
 
 RESAMPLE_STREAM_KERNELS = ("resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel", "copy")

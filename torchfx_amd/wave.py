@@ -210,7 +210,7 @@ def plan_cache_clear() -> None:
 
 
 def _member_key(m: nn.Module, guard: list) -> tuple:
-    from torchfx_amd.effect import Compressor, Delay, Gain, Limiter, LoudnessNormalize, ModulatedDelay, Normalize
+    from torchfx_amd.effect import Compressor, Delay, Freeverb, Gain, Limiter, LoudnessNormalize, ModulatedDelay, Normalize
     from torchfx_amd.filter.zerophase import ZeroPhase
     from torchfx_amd.resample import Resample, window_key
 
@@ -244,6 +244,8 @@ def _member_key(m: nn.Module, guard: list) -> tuple:
         k += (m.threshold_db, m.ratio, m.attack, m.release, m.knee_db, m.makeup_db, m.link, m.fs)
     elif isinstance(m, ModulatedDelay):
         k += (tuple(m.voices), m.dry, m.spread, m.shape, m.interpolation, m.pad, m.fs)
+    elif isinstance(m, Freeverb):
+        k += (m.room_size, m.damping, m.wet, m.dry, m.width, m.tail, m.fs)
     return k
 
 
@@ -334,19 +336,20 @@ class Wave:
         """A ``Resample`` is a barrier: the steps between two of them are planned on their own, at the row length they see,
         and nothing merges, folds or attaches an epilogue across one.  So is a ``ZeroPhase`` (its two passes are one step;
         the row length stays), a ``LoudnessNormalize`` (it measures exactly the signal the steps before it produce) and a
-        ``Limiter`` or a ``Compressor`` (their detectors read the samples the steps before them store)."""
-        from torchfx_amd.effect import Compressor, Limiter, LoudnessNormalize
+        ``Limiter`` or a ``Compressor`` (their detectors read the samples the steps before them store).  A ``Freeverb`` is a step
+        of its own too (its workgroups own whole rows), and its ``tail`` lengthens the rows for the steps after it."""
+        from torchfx_amd.effect import Compressor, Freeverb, Limiter, LoudnessNormalize
         from torchfx_amd.filter.zerophase import ZeroPhase
         from torchfx_amd.resample import Resample
 
         plan: list[nn.Module] = []
         segment: list[nn.Module] = []
         for m in self._pipeline:
-            if isinstance(m, (Resample, ZeroPhase, LoudnessNormalize, Limiter, Compressor)):
+            if isinstance(m, (Resample, ZeroPhase, LoudnessNormalize, Limiter, Compressor, Freeverb)):
                 plan += self._build_segment(segment, length, dtype)
                 plan.append(m)
                 segment = []
-                if isinstance(m, Resample):
+                if isinstance(m, (Resample, Freeverb)):
                     length = m.output_length(length)
             else:
                 segment.append(m)
@@ -575,7 +578,7 @@ class Wave:
     def explain(self) -> list[str]:
         """One line per step of :meth:`plan` for THIS tensor: the step, the route it will take (``CascadeFIR``: the fused
         recursion-in-pass-A pipeline or the staged pair of launches) and why."""
-        from torchfx_amd.effect import Compressor, Delay, Epilogued, Limiter, LoudnessNormalize, ModulatedDelay
+        from torchfx_amd.effect import Compressor, Delay, Epilogued, Freeverb, Limiter, LoudnessNormalize, ModulatedDelay
         from torchfx_amd.filter.fused import CascadeFIR, FusedSOSCascade
         from torchfx_amd.filter.zerophase import ZeroPhase
         from torchfx_amd.realtime import StatefulDelay, _native_stream
@@ -599,7 +602,7 @@ class Wave:
                                 else f"torch composition -- {self._ys.device.type} {self._ys.dtype} signal")
             elif isinstance(inner, Delay):
                 line += ": " + Wave._delay_route(inner, self._ys, self.fs)
-            elif isinstance(inner, Resample):
+            elif isinstance(inner, (Resample, Freeverb)):
                 line += ": " + inner.route(self._ys, length)
                 length = inner.output_length(length)
             elif isinstance(inner, (ZeroPhase, LoudnessNormalize, Limiter, Compressor, ModulatedDelay)):
