@@ -707,6 +707,38 @@ int tfx_freeverb_plan_info(int64_t batch, int64_t channels, int64_t T, int64_t t
                            int64_t *state_len, int64_t *launches, int64_t *workspace_bytes);
 
 /* ---------------------------------------------------------------------------
+ * tfx_waveshaper_forward -- an oversampled memoryless nonlinearity (Waveshaper, Distortion) in ONE launch.  With
+ * L = oversample in {1, 2, 4, 8}, h_up the taps of tfx_resample_forward(x, L, 1) and h_dn those of (1, L):
+ *   u = resample(x, L, 1)            length T*L, zeros outside [0, T)
+ *   v = drive * u + bias             a multiplication, then an addition: two roundings
+ *   w = f(v) - c0                    c0 = f(bias) evaluated in float64 on the host and rounded to dtype
+ *   z = resample(w, 1, L)            length T; w counts as zero outside [0, T*L)
+ *   y = dry * x + wet * z            two multiplications and an addition
+ * all in dtype; L = 1 has no filters (z = w).  f: TFX_SHAPE_HARD min(max(v, -1), 1); TFX_SHAPE_CUBIC 1.5 v - 0.5 v^3 inside
+ * [-1, 1], sign(v) outside; TFX_SHAPE_TANH; TFX_SHAPE_CURVE a table c of curve_n in [2, 4096] points over [-1, 1] read
+ * with WebAudio's rule: pos = (v + 1)(N - 1)/2 clamped to [0, N - 1], i = min(floor(pos), N - 2),
+ * f = c[i] + (pos - i)(c[i+1] - c[i]).  x, y DEVICE [rows, T] of dtype (y may not overlap x); curve_host HOST [curve_n] of
+ * dtype (NULL unless TFX_SHAPE_CURVE); taps_up_host / taps_dn_host HOST arrays of dtype with at most 64 * L taps each (both
+ * ignored when L = 1).  Both stages sum as tfx_resample_forward does (a descending-j fma chain from +0), so a finite signal
+ * through TFX_SHAPE_HARD gives the bits of resample -> multiply -> clamp -> resample.  The oversampled signal lives in LDS only.
+ * A workgroup owns a tile of `tile` outputs of one row (tfx_waveshaper_plan_info); the tiling does not depend on `rows`, and
+ * a row's bits depend on its own samples alone.  Non-finite input: y[m] is NaN exactly when x[m - reach_after .. m +
+ * reach_before] holds a NaN or an Inf (every tap of both zero-padded filters counted; an up-sampled value that is not finite
+ * shapes to NaN); every other output has the bits it has with a zero in that sample's place.  Arguments are checked before
+ * the device is touched; the first call with a new filter or curve uploads it with a blocking copy and caches it by content.
+ * ------------------------------------------------------------------------- */
+enum tfx_shape { TFX_SHAPE_HARD = 0, TFX_SHAPE_CUBIC = 1, TFX_SHAPE_TANH = 2, TFX_SHAPE_CURVE = 3 };
+int tfx_waveshaper_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t oversample, int shape,
+                           const void *curve_host, int64_t curve_n, double drive, double bias, double dry, double wet,
+                           const void *taps_up_host, int64_t nh_up, const void *taps_dn_host, int64_t nh_dn, tfx_stream_t stream);
+/* what tfx_waveshaper_forward does (host-only, same checks on the sizes): outputs per tile, tiles per row, the future and past
+ * input samples an output depends on (reach_before, reach_after; 0 for L = 1), the LDS bytes of a workgroup and the taps per
+ * phase of the up-sampler and of the (single-phase, zero-padded) decimator; the grid is rows * tiles workgroups */
+int tfx_waveshaper_plan_info(int64_t rows, int64_t T, int64_t oversample, int64_t nh_up, int64_t nh_dn, int64_t curve_n, int dtype,
+                             int64_t *tile, int64_t *tiles, int64_t *reach_before, int64_t *reach_after, int64_t *lds_bytes,
+                             int64_t *taps_up, int64_t *taps_dn);
+
+/* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of
  * ParallelFilterCombination.forward, src/torchfx/filter/__base.py:1019-1026).
  * xs_host: HOST array of n DEVICE pointers, each [numel] of dtype.

@@ -753,6 +753,27 @@ int tfx_freeverb_plan_info(int64_t batch, int64_t channels, int64_t T, int64_t t
     TFX_API_END
 }
 
+int tfx_waveshaper_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t oversample, int shape,
+                           const void *curve_host, int64_t curve_n, double drive, double bias, double dry, double wet,
+                           const void *taps_up_host, int64_t nh_up, const void *taps_dn_host, int64_t nh_dn, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    waveshaper_forward(x, y, dtype, rows, T, oversample, shape, curve_host, curve_n, drive, bias, dry, wet, taps_up_host, nh_up,
+                       taps_dn_host, nh_dn, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_waveshaper_plan_info(int64_t rows, int64_t T, int64_t oversample, int64_t nh_up, int64_t nh_dn, int64_t curve_n, int dtype,
+                             int64_t *tile, int64_t *tiles, int64_t *reach_before, int64_t *reach_after, int64_t *lds_bytes,
+                             int64_t *taps_up, int64_t *taps_dn)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(tile && tiles && reach_before && reach_after && lds_bytes && taps_up && taps_dn, "waveshaper_plan_info: null output");
+    waveshaper_plan_info(rows, T, oversample, nh_up, nh_dn, curve_n, dtype, tile, tiles, reach_before, reach_after, lds_bytes, taps_up,
+                         taps_dn);
+    TFX_API_END
+}
+
 int tfx_sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, tfx_stream_t stream)
 {
     TFX_API_BEGIN
@@ -871,6 +892,7 @@ int tfx_clear_caches(void)
     resample_clear();
     limiter_clear();
     modulation_clear();
+    waveshaper_clear();
     scratch_clear();
     TFX_API_END
 }

@@ -747,6 +747,41 @@ std::tuple<Tensor, Tensor, Tensor> modulated_delay_stream_op(const Tensor &x_in,
     return std::make_tuple(y, hout, pout);
 }
 
+// The oversampled waveshaper (tfx_waveshaper_forward): x [..., T], rows independent; curve (shape 3 only) and the two tap vectors
+// (oversample > 1 only) host tensors of x's dtype.  Everything is checked by the plan query before anything touches the device.
+Tensor waveshaper_op(const Tensor &x_in, int64_t oversample, int64_t shape, const OptTensor &curve, double drive, double bias, double dry,
+                     double wet, const OptTensor &taps_up, const OptTensor &taps_dn)
+{
+    const char *what = "waveshaper_forward";
+    need_device(x_in, "x");
+    TORCH_CHECK(x_in.dim() >= 1, what, ": x must have a time dimension");
+    const Tensor x = x_in.contiguous();
+    const int dt = dtype_code(x, what);
+    const bool has_curve = curve.has_value() && curve->defined();
+    TORCH_CHECK(has_curve == (shape == TFX_SHAPE_CURVE), what, ": a curve goes with shape ", (int)TFX_SHAPE_CURVE, " and with no other");
+    Tensor cv, hu, hd;
+    if (has_curve) cv = host_vector(*curve, x, what, "curve");
+    if (oversample != 1) {
+        TORCH_CHECK(taps_up.has_value() && taps_up->defined() && taps_dn.has_value() && taps_dn->defined(), what,
+                    ": oversample > 1 needs the taps of both stages");
+        hu = host_vector(*taps_up, x, what, "taps_up");
+        hd = host_vector(*taps_dn, x, what, "taps_dn");
+    }
+    const int64_t T = x.size(-1), rows = stream_rows(x);
+    int64_t info[7];
+    check_rc(tfx_waveshaper_plan_info(rows, T, oversample, hu.defined() ? hu.numel() : 0, hd.defined() ? hd.numel() : 0,
+                                      has_curve ? cv.numel() : 0, dt, info, info + 1, info + 2, info + 3, info + 4, info + 5, info + 6),
+             what);
+    Tensor y = at::empty_like(x);
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_waveshaper_forward(x.data_ptr(), y.data_ptr(), dt, rows, T, oversample, (int)shape, has_curve ? cv.data_ptr() : nullptr,
+                                    has_curve ? cv.numel() : 0, drive, bias, dry, wet, hu.defined() ? hu.data_ptr() : nullptr,
+                                    hu.defined() ? hu.numel() : 0, hd.defined() ? hd.data_ptr() : nullptr, hd.defined() ? hd.numel() : 0,
+                                    stream_of(x)),
+             what);
+    return y;
+}
+
 // One chunk of a resampling stream (tfx_resample_stream_forward): x [..., T] after `consumed` samples per row, h as for
 // resample_forward, hist [rows, H] (None = silence) -> (y [..., M(consumed + T) - M(consumed)], new history [rows, H])
 struct ResampleStreamPlan {
@@ -1304,6 +1339,19 @@ TORCH_LIBRARY(torchfx_reverb, m)
 TORCH_LIBRARY_IMPL(torchfx_reverb, Meta, m)
 {
     m.impl("freeverb_forward", freeverb_meta);
+}
+
+// The waveshaper likewise: torch.ops.torchfx_shaper.
+TORCH_LIBRARY(torchfx_shaper, m)
+{
+    reg_op(m, "waveshaper_forward(Tensor x, int oversample, int shape, Tensor? curve_cpu, float drive, float bias, float dry, float wet, "
+              "Tensor? taps_up_cpu, Tensor? taps_dn_cpu) -> Tensor", waveshaper_op);
+}
+
+TORCH_LIBRARY_IMPL(torchfx_shaper, Meta, m)
+{
+    m.impl("waveshaper_forward", [](const Tensor &x, int64_t, int64_t, const OptTensor &, double, double, double, double, const OptTensor &,
+                                    const OptTensor &) { return at::empty_like(x); });
 }
 
 // The reference's module surface (binding.cpp:83-96): exactly these three names and argument lists.

@@ -1,5 +1,5 @@
 // timedomain.h -- the host entry points of the time-domain and elementwise ops, one prototype per exported function of fir.hip,
-// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip, compressor.hip, modulation.hip, reverb.hip and layout.hip (the cascade's: sos.h; the
+// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip, compressor.hip, modulation.hip, reverb.hip, waveshaper.hip and layout.hip (the cascade's: sos.h; the
 // overlap-save pipelines': ols_route.h).  Included by the file that defines each function and by capi.hip, so a prototype that drifts from
 // its definition does not compile; default arguments live here and nowhere else.  Every *_forward checks its arguments before
 // anything touches the device; a *_plan_info takes the same checking path without the pointers.
@@ -117,6 +117,15 @@ void freeverb_forward(const void *x, void *y, int dtype, int64_t batch, int64_t 
 void freeverb_plan_info(int64_t batch, int64_t channels, int64_t T, int64_t tail, const int64_t *comb_delays_host, int64_t NC,
                         const int64_t *allpass_delays_host, int64_t NA, double wet2, int64_t *block, int *placement,
                         int64_t *state_len, int64_t *launches, int64_t *workspace_bytes);
+
+// ---- waveshaper.hip ----
+void waveshaper_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t oversample, int shape,
+                        const void *curve_host, int64_t curve_n, double drive, double bias, double dry, double wet,
+                        const void *taps_up_host, int64_t nh_up, const void *taps_dn_host, int64_t nh_dn, hipStream_t stream);
+void waveshaper_plan_info(int64_t rows, int64_t T, int64_t oversample, int64_t nh_up, int64_t nh_dn, int64_t curve_n, int dtype,
+                          int64_t *tile, int64_t *tiles, int64_t *reach_before, int64_t *reach_after, int64_t *lds_bytes,
+                          int64_t *taps_up, int64_t *taps_dn);
+void waveshaper_clear();
 
 // ---- layout.hip ----
 void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, int64_t C, int64_t ld_out, int64_t f_base,

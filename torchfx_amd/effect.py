@@ -578,6 +578,65 @@ class Freeverb(FX):
                 f"tail={self.tail}, fs={self.fs}")
 
 
+class Waveshaper(FX):
+    """Oversampled waveshaping as an effect: :func:`torchfx_amd.waveshaper.waveshape` with the same parameters -- ``shape``
+    ("hard", "cubic", "tanh"; default "tanh") or a ``curve`` table of 2 to 4096 points over ``[-1, 1]`` (WebAudio's
+    ``WaveShaperNode`` rule), ``drive_db``, ``bias``, ``oversample`` (1, 2, 4 or 8), ``mix``, ``output_db`` and the resampling
+    ``window``.  It needs no sample rate.  Every call zero-pads its edges: the effect is a step of its own in ``Wave.plan()``
+    (one launch, ``csrc/waveshaper.hip``), and the stream processors take it with ``oversample=1`` only."""
+
+    def __init__(self, shape: str | None = None, drive_db: float = 0.0, bias: float = 0.0, oversample: int = 4, mix: float = 1.0,
+                 output_db: float = 0.0, curve=None, window=("kaiser", 5.0)) -> None:
+        super().__init__()
+        self.shape, self.drive_db, self.bias, self.oversample, self.mix = shape, drive_db, bias, oversample, mix
+        self.output_db, self.curve, self.window = output_db, curve, window
+        self.params()                                                    # argument errors now
+
+    def params(self):
+        """The call's :class:`torchfx_amd.waveshaper.ShaperParams`."""
+        from torchfx_amd.waveshaper import ShaperParams
+
+        return ShaperParams(self.shape, self.drive_db, self.bias, self.oversample, self.mix, self.output_db, self.curve, self.window)
+
+    def route(self, x: Tensor, length: int | None = None) -> str:
+        """``native (...)`` or ``scipy on host -- <reason>`` for ``x`` (rows of ``length`` samples, default x's)."""
+        if not x.is_cuda:
+            return f"scipy on host -- {x.device.type} tensor"
+        if x.dtype not in (torch.float32, torch.float64):
+            return f"refused -- {x.dtype} signal (float32 / float64 only)"
+        try:
+            P = self.params()
+            up, dn = P.taps(x.dtype)
+            n = int(x.shape[-1]) if length is None else int(length)
+            info = _ext().waveshaper_plan_info(n, P.oversample, 0 if up is None else up.numel(), 0 if dn is None else dn.numel(),
+                                               0 if P.curve is None else P.curve.size, x.dtype)
+        except (RuntimeError, ValueError, TypeError) as e:
+            return f"refused -- {e}"
+        if P.oversample == 1:
+            return f"native (waveshaper_plain_kernel, L = 1, {P.shape}, no filters; one launch)"
+        return (f"native (waveshaper_kernel, L = {P.oversample}, {P.shape}, {info['taps_up']} taps per phase up and {info['taps_dn']} "
+                f"taps down, {info['tiles']} tile(s) of {info['tile']} per row, {info['lds_bytes']} B of LDS; one launch)")
+
+    @torch.no_grad()
+    def forward(self, waveform: Tensor) -> Tensor:
+        from torchfx_amd.waveshaper import shape_signal
+
+        return shape_signal(waveform, self.params())
+
+    def extra_repr(self) -> str:
+        what = f"curve={len(self.curve)} points" if self.curve is not None else f"shape={self.params().shape!r}"
+        return (f"{what}, drive_db={self.drive_db}, bias={self.bias}, oversample={self.oversample}, mix={self.mix}, "
+                f"output_db={self.output_db}")
+
+
+class Distortion(Waveshaper):
+    """Distortion: a :class:`Waveshaper` with 12 dB of drive into ``tanh`` at 4x oversampling unless told otherwise."""
+
+    def __init__(self, drive_db: float = 12.0, shape: str = "tanh", bias: float = 0.0, oversample: int = 4, mix: float = 1.0,
+                 output_db: float = 0.0) -> None:
+        super().__init__(shape, drive_db, bias, oversample, mix, output_db)
+
+
 class Reverb(FX):
     """``y[n] = x[n] + mix * decay * x[n - delay]`` -- the reference's "reverb" is one feed-forward
     tap (``effect.py:789-931`` over ``delay_line_forward``, ``_csrc/cpu/delay_cpu.cpp:17-41``); a

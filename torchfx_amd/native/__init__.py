@@ -87,3 +87,11 @@ def reverb_ops():
 
     load()
     return torch.ops.torchfx_reverb
+
+
+def shaper_ops():
+    """``torch.ops.torchfx_shaper`` (the waveshaper's namespace, registered by the same module) with the library loaded."""
+    import torch
+
+    load()
+    return torch.ops.torchfx_shaper

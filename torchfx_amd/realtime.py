@@ -46,7 +46,7 @@ import torch
 from torch import Tensor, nn
 
 from torchfx_amd.effect import (FX, Chorus, Compressor, Delay, Flanger, Freeverb, Limiter, ModulatedDelay, MonoDelayStrategy, PingPongDelayStrategy,
-                                Reverb, Vibrato, _ext)
+                                Reverb, Vibrato, Waveshaper, _ext)
 from torchfx_amd.filter._base import AbstractFilter
 from torchfx_amd.filter.fir import FIR
 from torchfx_amd.resample import Resample, design_taps, window_key
@@ -669,6 +669,14 @@ def _refuse_freeverb(e, who: str) -> None:
                         "(wave | Freeverb(...)) before or after streaming")
 
 
+def _refuse_waveshaper(e, who: str) -> None:
+    for m in (e.modules() if isinstance(e, nn.Module) else [e]):
+        if isinstance(m, Waveshaper) and m.oversample != 1:
+            raise TypeError(f"{type(m).__name__} with oversample={m.oversample} cannot run in {who}: every call zero-pads the edges "
+                            "of its resampling filters, so a chunked stream would click at every chunk seam; use oversample=1 "
+                            f"(memoryless) here, or run the whole signal (wave | {type(m).__name__}(...)) before or after streaming")
+
+
 class _ModulationStream:
     """A modulated delay line (:class:`~torchfx_amd.effect.ModulatedDelay`) over a continuous stream; mixed in in front of the
     effect class.  Every row carries its last ``H = max_v floor(delay_v + depth_v) + 2`` input samples in ``_hist``
@@ -925,6 +933,7 @@ class StreamProcessor:
             _refuse_compressor(e, "StreamProcessor")
             _refuse_modulation(e, "StreamProcessor")
             _refuse_freeverb(e, "StreamProcessor")
+            _refuse_waveshaper(e, "StreamProcessor")
             if not isinstance(e, StatefulResample) and any(isinstance(m, Resample) for m in e.modules()):
                 raise TypeError("Resample cannot run in StreamProcessor: resampling each chunk on its own leaves a seam at "
                                 "every chunk boundary; use StatefulResample as a top-level effect of the chain, or resample "
@@ -1249,6 +1258,7 @@ class RealtimeProcessor:
             _refuse_compressor(e, "RealtimeProcessor")
             _refuse_modulation(e, "RealtimeProcessor")
             _refuse_freeverb(e, "RealtimeProcessor")
+            _refuse_waveshaper(e, "RealtimeProcessor")
             if _has_stateful_resample(e):
                 raise TypeError("StatefulResample cannot run in RealtimeProcessor: a sound card's output block has the input "
                                 "block's length and sample rate; resample with StreamProcessor or Wave.resample instead")

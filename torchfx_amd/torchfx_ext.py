@@ -464,6 +464,33 @@ def freeverb_plan_info(length: int, comb_delays, allpass_delays, batch: int = 1,
     return info
 
 
+WAVESHAPES = ("hard", "cubic", "tanh", "curve")           # tfx_shape
+
+
+def waveshaper_forward(x: Tensor, oversample: int, shape: str, curve: Tensor | None, drive: float, bias: float, dry: float, wet: float,
+                       taps_up: Tensor | None = None, taps_dn: Tensor | None = None) -> Tensor:
+    """The oversampled waveshaper in one launch (``tfx_waveshaper_forward``; the definition is
+    :func:`torchfx_amd.waveshaper.waveshape`'s) with its parameters already reduced: ``x [..., T]`` on the device (float32 /
+    float64), ``oversample`` 1, 2, 4 or 8, ``shape`` one of ``WAVESHAPES`` (``"curve"`` with ``curve``, a 1-D host tensor of 2
+    to 4096 points in ``x``'s dtype), the linear ``drive``, ``bias``, ``dry`` and ``wet``, and for ``oversample > 1`` the taps of
+    ``resample_poly(x, L, 1)`` and ``(x, 1, L)`` as 1-D host tensors of ``x``'s dtype, at most ``64 * oversample`` each
+    (``waveshaper_kernel``; ``oversample = 1``: ``waveshaper_plain_kernel``).  The op lives in ``torch.ops.torchfx_shaper``."""
+    native.ops()                                         # loads the library: every namespace is registered by the one module
+    return native.shaper_ops().waveshaper_forward(x.contiguous(), int(oversample), WAVESHAPES.index(shape), curve, float(drive),
+                                                  float(bias), float(dry), float(wet), taps_up, taps_dn)
+
+
+def waveshaper_plan_info(length: int, oversample: int, taps_up: int = 0, taps_dn: int = 0, curve: int = 0,
+                         dtype: torch.dtype = torch.float32, rows: int = 1) -> dict:
+    """What :func:`waveshaper_forward` does for rows of ``length`` samples (``tfx_waveshaper_plan_info``; host-only, same checks
+    on the sizes): ``tile`` (outputs per workgroup), ``tiles`` per row, ``reach_before`` / ``reach_after`` (the future / past
+    input samples an output depends on), ``lds_bytes`` per workgroup, and ``taps_up`` / ``taps_dn`` (taps per phase of the
+    up-sampler, taps of the zero-padded decimator).  The tiling does not depend on ``rows``."""
+    return _query(L.load().tfx_waveshaper_plan_info,
+                  (int(rows), int(length), int(oversample), int(taps_up), int(taps_dn), int(curve), _dt(dtype)),
+                  "tile tiles reach_before reach_after lds_bytes taps_up taps_dn")
+
+
 RESAMPLE_STREAM_KERNELS = ("resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel", "copy")
 
 

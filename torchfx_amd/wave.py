@@ -210,7 +210,7 @@ def plan_cache_clear() -> None:
 
 
 def _member_key(m: nn.Module, guard: list) -> tuple:
-    from torchfx_amd.effect import Compressor, Delay, Freeverb, Gain, Limiter, LoudnessNormalize, ModulatedDelay, Normalize
+    from torchfx_amd.effect import Compressor, Delay, Freeverb, Gain, Limiter, LoudnessNormalize, ModulatedDelay, Normalize, Waveshaper
     from torchfx_amd.filter.zerophase import ZeroPhase
     from torchfx_amd.resample import Resample, window_key
 
@@ -246,6 +246,9 @@ def _member_key(m: nn.Module, guard: list) -> tuple:
         k += (tuple(m.voices), m.dry, m.spread, m.shape, m.interpolation, m.pad, m.fs)
     elif isinstance(m, Freeverb):
         k += (m.room_size, m.damping, m.wet, m.dry, m.width, m.tail, m.fs)
+    elif isinstance(m, Waveshaper):
+        k += (m.shape, m.drive_db, m.bias, m.oversample, m.mix, m.output_db, None if m.curve is None else window_key(m.curve),
+              window_key(m.window))
     return k
 
 
@@ -578,7 +581,7 @@ class Wave:
     def explain(self) -> list[str]:
         """One line per step of :meth:`plan` for THIS tensor: the step, the route it will take (``CascadeFIR``: the fused
         recursion-in-pass-A pipeline or the staged pair of launches) and why."""
-        from torchfx_amd.effect import Compressor, Delay, Epilogued, Freeverb, Limiter, LoudnessNormalize, ModulatedDelay
+        from torchfx_amd.effect import Compressor, Delay, Epilogued, Freeverb, Limiter, LoudnessNormalize, ModulatedDelay, Waveshaper
         from torchfx_amd.filter.fused import CascadeFIR, FusedSOSCascade
         from torchfx_amd.filter.zerophase import ZeroPhase
         from torchfx_amd.realtime import StatefulDelay, _native_stream
@@ -605,7 +608,7 @@ class Wave:
             elif isinstance(inner, (Resample, Freeverb)):
                 line += ": " + inner.route(self._ys, length)
                 length = inner.output_length(length)
-            elif isinstance(inner, (ZeroPhase, LoudnessNormalize, Limiter, Compressor, ModulatedDelay)):
+            elif isinstance(inner, (ZeroPhase, LoudnessNormalize, Limiter, Compressor, ModulatedDelay, Waveshaper)):
                 line += ": " + inner.route(self._ys, length)
             lines.append(line)
         return lines
