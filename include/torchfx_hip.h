@@ -310,9 +310,9 @@ int tfx_normalize_apply(const void *x, void *y, int dtype, int64_t C, int64_t T,
 /* ---------------------------------------------------------------------------
  * Stream history -- the contract of every streaming entry point (tfx_fir_stream_forward, tfx_chunk_forward,
  * tfx_delay_stream_forward, tfx_delay_line_stream_forward, tfx_resample_stream_forward, tfx_limiter_stream_forward,
- * tfx_modulated_delay_stream_forward).  A chunk
+ * tfx_modulated_delay_stream_forward, tfx_waveshaper_stream_forward).  A chunk
  * continues the last H input samples of each of its rows (H is the entry's: K-1, Kf-1, taps*delay, delay, Lp_s-1, Hs, the
- * modulated delay's reach):
+ * modulated delay's reach, the waveshaper's Hs):
  *   hist_in  DEVICE [rows, H] of the entry's dtype: the H samples before the chunk, oldest first; NULL = silence (the first
  *            chunk of a stream).
  *   hist_out DEVICE [rows, H]: receives the newest H samples of [hist_in | x] (x: what the entry filters, the cascade output
@@ -737,6 +737,41 @@ int tfx_waveshaper_forward(const void *x, void *y, int dtype, int64_t rows, int6
 int tfx_waveshaper_plan_info(int64_t rows, int64_t T, int64_t oversample, int64_t nh_up, int64_t nh_dn, int64_t curve_n, int dtype,
                              int64_t *tile, int64_t *tiles, int64_t *reach_before, int64_t *reach_after, int64_t *lds_bytes,
                              int64_t *taps_up, int64_t *taps_dn);
+
+/* ---------------------------------------------------------------------------
+ * tfx_waveshaper_stream_forward -- one chunk of tfx_waveshaper_forward over a continuous stream, in ONE launch.  With Y the
+ * one-shot result of the whole stream (past and to come), the chunk of T samples that follows `consumed` = N inputs per row
+ * writes
+ *   y[., t] = Y[N - D + t], 0 where N - D + t < 0
+ * and each sample is final.  (oversample, nh_up, nh_dn) fix the stream's geometry, with reach_before and reach_after as
+ * tfx_waveshaper_plan_info gives them (they do not depend on T):
+ *   latency D  = reach_before: output n needs input n + D and no later one
+ *   history Hs = reach_before + reach_after: the inputs before the chunk its outputs read
+ * and D = Hs = 0 for oversample = 1.  History as in "Stream history" with H = Hs: hist_in holds inputs [N - Hs, N) (zeros
+ * before 0).  The kernel reads [hist_in | x] from the two buffers -- the dry term x[N - D + t] too -- and knows where the stream
+ * began: the shaped signal w is zero before up-sampled index 0 although the up-sampler rings into it.  n_in <= T is the number
+ * of real inputs in x: n_in < T says that the stream ends after them -- x[., n_in:] is never read, the inputs from N + n_in on
+ * are zeros and w counts as zero from up-sampled index (N + n_in) * oversample on, exactly as tfx_waveshaper_forward treats its
+ * end -- and hist_out then receives the newest Hs samples of [hist_in | x[., :n_in]].  The last min(N, D) outputs of a stream
+ * of N inputs are the end of a chunk with T = D, n_in = 0.  `consumed` matters only up to Hs + D and is clamped there.
+ * Every output is tfx_waveshaper_forward's arithmetic (the same source: both fma chains, the transfer function, the mix), so
+ * the chunks' outputs equal the one-shot call on the whole signal bit for bit, whatever the chunk sizes, a NaN's or an Inf's
+ * reach included.  A workgroup computes up to `tile` outputs (the one-shot tiling), and whole waves whose positions no output
+ * of the chunk depends on skip the up-sampler and the transfer function.
+ * x, y DEVICE [rows, T], hist_out DEVICE [rows, Hs] or null (no history out); the other arguments as for
+ * tfx_waveshaper_forward.  T == 0 copies hist_in to hist_out.
+ * ------------------------------------------------------------------------- */
+int tfx_waveshaper_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t n_in, int64_t consumed,
+                                  int64_t oversample, int shape, const void *curve_host, int64_t curve_n, double drive, double bias,
+                                  double dry, double wet, const void *taps_up_host, int64_t nh_up, const void *taps_dn_host,
+                                  int64_t nh_dn, const void *hist_in, void *hist_out, tfx_stream_t stream);
+/* what tfx_waveshaper_stream_forward does with a chunk of T samples (host-only, same checks on the sizes): the stream's latency
+ * D and history length Hs, outputs per workgroup `tile`, tiles per row, the positions whose up-sampled samples the first
+ * workgroup computes and shapes (those its min(T, tile) outputs read, rounded up to whole waves of 512 / 256 positions, of
+ * 2048 for float32 / 1024 for float64; min(T, tile) for oversample = 1) and the LDS bytes per workgroup */
+int tfx_waveshaper_stream_plan_info(int64_t rows, int64_t T, int64_t oversample, int64_t nh_up, int64_t nh_dn, int64_t curve_n,
+                                    int dtype, int64_t *latency, int64_t *history, int64_t *tile, int64_t *tiles,
+                                    int64_t *positions, int64_t *lds_bytes);
 
 /* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of

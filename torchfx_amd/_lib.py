@@ -98,6 +98,9 @@ SIGNATURES = {
                                + [ctypes.POINTER(_i64)] * 3),
     "tfx_waveshaper_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _int, _vp, _i64, _dbl, _dbl, _dbl, _dbl, _vp, _i64, _vp, _i64, _vp]),
     "tfx_waveshaper_plan_info": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _int] + [ctypes.POINTER(_i64)] * 7),
+    "tfx_waveshaper_stream_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _int, _vp, _i64, _dbl, _dbl, _dbl, _dbl, _vp,
+                                             _i64, _vp, _i64, _vp, _vp, _vp]),
+    "tfx_waveshaper_stream_plan_info": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _int] + [ctypes.POINTER(_i64)] * 6),
     "tfx_sum_forward": (_int, [_vp, _int, _vp, _int, _i64, _vp]),
     "tfx_gain_forward": (_int, [_vp, _vp, _int, _i64, _dbl, _int, _vp]),
     "tfx_stat_forward": (_int, [_vp, _int, _i64, _i64, _int, _int, _vp, _vp]),

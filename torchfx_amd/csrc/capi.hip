@@ -774,6 +774,27 @@ int tfx_waveshaper_plan_info(int64_t rows, int64_t T, int64_t oversample, int64_
     TFX_API_END
 }
 
+int tfx_waveshaper_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t n_in, int64_t consumed,
+                                  int64_t oversample, int shape, const void *curve_host, int64_t curve_n, double drive, double bias,
+                                  double dry, double wet, const void *taps_up_host, int64_t nh_up, const void *taps_dn_host,
+                                  int64_t nh_dn, const void *hist_in, void *hist_out, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    waveshaper_stream_forward(x, y, dtype, rows, T, n_in, consumed, oversample, shape, curve_host, curve_n, drive, bias, dry, wet,
+                              taps_up_host, nh_up, taps_dn_host, nh_dn, hist_in, hist_out, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_waveshaper_stream_plan_info(int64_t rows, int64_t T, int64_t oversample, int64_t nh_up, int64_t nh_dn, int64_t curve_n,
+                                    int dtype, int64_t *latency, int64_t *history, int64_t *tile, int64_t *tiles,
+                                    int64_t *positions, int64_t *lds_bytes)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(latency && history && tile && tiles && positions && lds_bytes, "waveshaper_stream_plan_info: null output");
+    waveshaper_stream_plan_info(rows, T, oversample, nh_up, nh_dn, curve_n, dtype, latency, history, tile, tiles, positions, lds_bytes);
+    TFX_API_END
+}
+
 int tfx_sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, tfx_stream_t stream)
 {
     TFX_API_BEGIN

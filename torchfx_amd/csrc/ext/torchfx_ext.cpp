@@ -747,39 +747,85 @@ std::tuple<Tensor, Tensor, Tensor> modulated_delay_stream_op(const Tensor &x_in,
     return std::make_tuple(y, hout, pout);
 }
 
-// The oversampled waveshaper (tfx_waveshaper_forward): x [..., T], rows independent; curve (shape 3 only) and the two tap vectors
-// (oversample > 1 only) host tensors of x's dtype.  Everything is checked by the plan query before anything touches the device.
+// What the waveshaper's two ops take: x [..., T] contiguous, rows independent; curve (shape 3 only) and the two tap vectors
+// (oversample > 1 only) host tensors of x's dtype
+struct ShaperInputs {
+    Tensor x, cv, hu, hd;
+    int64_t T = 0, rows = 0;
+    int dt = 0;
+    int64_t n_curve() const { return cv.defined() ? cv.numel() : 0; }
+    int64_t n_up() const { return hu.defined() ? hu.numel() : 0; }
+    int64_t n_dn() const { return hd.defined() ? hd.numel() : 0; }
+    const void *curve_ptr() const { return cv.defined() ? cv.data_ptr() : nullptr; }
+    const void *up_ptr() const { return hu.defined() ? hu.data_ptr() : nullptr; }
+    const void *dn_ptr() const { return hd.defined() ? hd.data_ptr() : nullptr; }
+};
+
+ShaperInputs shaper_inputs(const char *what, const Tensor &x_in, int64_t oversample, int64_t shape, const OptTensor &curve,
+                           const OptTensor &taps_up, const OptTensor &taps_dn)
+{
+    need_device(x_in, "x");
+    TORCH_CHECK(x_in.dim() >= 1, what, ": x must have a time dimension");
+    ShaperInputs in;
+    in.x = x_in.contiguous();
+    in.dt = dtype_code(in.x, what);
+    const bool has_curve = curve.has_value() && curve->defined();
+    TORCH_CHECK(has_curve == (shape == TFX_SHAPE_CURVE), what, ": a curve goes with shape ", (int)TFX_SHAPE_CURVE, " and with no other");
+    if (has_curve) in.cv = host_vector(*curve, in.x, what, "curve");
+    if (oversample != 1) {
+        TORCH_CHECK(taps_up.has_value() && taps_up->defined() && taps_dn.has_value() && taps_dn->defined(), what,
+                    ": oversample > 1 needs the taps of both stages");
+        in.hu = host_vector(*taps_up, in.x, what, "taps_up");
+        in.hd = host_vector(*taps_dn, in.x, what, "taps_dn");
+    }
+    in.T = in.x.size(-1);
+    in.rows = stream_rows(in.x);
+    return in;
+}
+
+// The oversampled waveshaper (tfx_waveshaper_forward).  Everything is checked by the plan query before anything touches the device.
 Tensor waveshaper_op(const Tensor &x_in, int64_t oversample, int64_t shape, const OptTensor &curve, double drive, double bias, double dry,
                      double wet, const OptTensor &taps_up, const OptTensor &taps_dn)
 {
     const char *what = "waveshaper_forward";
-    need_device(x_in, "x");
-    TORCH_CHECK(x_in.dim() >= 1, what, ": x must have a time dimension");
-    const Tensor x = x_in.contiguous();
-    const int dt = dtype_code(x, what);
-    const bool has_curve = curve.has_value() && curve->defined();
-    TORCH_CHECK(has_curve == (shape == TFX_SHAPE_CURVE), what, ": a curve goes with shape ", (int)TFX_SHAPE_CURVE, " and with no other");
-    Tensor cv, hu, hd;
-    if (has_curve) cv = host_vector(*curve, x, what, "curve");
-    if (oversample != 1) {
-        TORCH_CHECK(taps_up.has_value() && taps_up->defined() && taps_dn.has_value() && taps_dn->defined(), what,
-                    ": oversample > 1 needs the taps of both stages");
-        hu = host_vector(*taps_up, x, what, "taps_up");
-        hd = host_vector(*taps_dn, x, what, "taps_dn");
-    }
-    const int64_t T = x.size(-1), rows = stream_rows(x);
+    const ShaperInputs in = shaper_inputs(what, x_in, oversample, shape, curve, taps_up, taps_dn);
+    const Tensor &x = in.x;
     int64_t info[7];
-    check_rc(tfx_waveshaper_plan_info(rows, T, oversample, hu.defined() ? hu.numel() : 0, hd.defined() ? hd.numel() : 0,
-                                      has_curve ? cv.numel() : 0, dt, info, info + 1, info + 2, info + 3, info + 4, info + 5, info + 6),
+    check_rc(tfx_waveshaper_plan_info(in.rows, in.T, oversample, in.n_up(), in.n_dn(), in.n_curve(), in.dt, info, info + 1, info + 2,
+                                      info + 3, info + 4, info + 5, info + 6),
              what);
     Tensor y = at::empty_like(x);
     c10::hip::HIPGuard guard(x.get_device());
-    check_rc(tfx_waveshaper_forward(x.data_ptr(), y.data_ptr(), dt, rows, T, oversample, (int)shape, has_curve ? cv.data_ptr() : nullptr,
-                                    has_curve ? cv.numel() : 0, drive, bias, dry, wet, hu.defined() ? hu.data_ptr() : nullptr,
-                                    hu.defined() ? hu.numel() : 0, hd.defined() ? hd.data_ptr() : nullptr, hd.defined() ? hd.numel() : 0,
-                                    stream_of(x)),
+    check_rc(tfx_waveshaper_forward(x.data_ptr(), y.data_ptr(), in.dt, in.rows, in.T, oversample, (int)shape, in.curve_ptr(), in.n_curve(),
+                                    drive, bias, dry, wet, in.up_ptr(), in.n_up(), in.dn_ptr(), in.n_dn(), stream_of(x)),
              what);
     return y;
+}
+
+// One chunk of a waveshaper stream (tfx_waveshaper_stream_forward): x [..., T] after `consumed` samples per row, hist [rows, Hs]
+// (None = silence), n_in real inputs in x (-1: all T; fewer: the stream ends after them) -> (y like x: the one-shot result from
+// position consumed - D on, new history [rows, Hs]).  The other arguments as waveshaper_op's.
+std::tuple<Tensor, Tensor> waveshaper_stream_op(const Tensor &x_in, const OptTensor &hist, int64_t consumed, int64_t oversample,
+                                                int64_t shape, const OptTensor &curve, double drive, double bias, double dry, double wet,
+                                                const OptTensor &taps_up, const OptTensor &taps_dn, int64_t n_in)
+{
+    const char *what = "waveshaper_stream_forward";
+    const ShaperInputs in = shaper_inputs(what, x_in, oversample, shape, curve, taps_up, taps_dn);
+    const Tensor &x = in.x;
+    int64_t info[6];
+    check_rc(tfx_waveshaper_stream_plan_info(in.rows, in.T, oversample, in.n_up(), in.n_dn(), in.n_curve(), in.dt, info, info + 1,
+                                             info + 2, info + 3, info + 4, info + 5),
+             what);
+    const int64_t Hs = info[1];
+    const Tensor hin = stream_hist_in(hist, x, in.rows, Hs, what);
+    Tensor y = at::empty_like(x), hout = at::empty({in.rows, Hs}, x.options());
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_waveshaper_stream_forward(x.data_ptr(), y.data_ptr(), in.dt, in.rows, in.T, n_in < 0 ? in.T : n_in, consumed, oversample,
+                                           (int)shape, in.curve_ptr(), in.n_curve(), drive, bias, dry, wet, in.up_ptr(), in.n_up(),
+                                           in.dn_ptr(), in.n_dn(), hin.defined() ? hin.data_ptr() : nullptr,
+                                           Hs ? hout.data_ptr() : nullptr, stream_of(x)),
+             what);
+    return std::make_tuple(y, hout);
 }
 
 // One chunk of a resampling stream (tfx_resample_stream_forward): x [..., T] after `consumed` samples per row, h as for
@@ -1352,6 +1398,31 @@ TORCH_LIBRARY_IMPL(torchfx_shaper, Meta, m)
 {
     m.impl("waveshaper_forward", [](const Tensor &x, int64_t, int64_t, const OptTensor &, double, double, double, double, const OptTensor &,
                                     const OptTensor &) { return at::empty_like(x); });
+}
+
+// Its stream form in a namespace of its own: torch.ops.torchfx_shaper_stream.
+TORCH_LIBRARY(torchfx_shaper_stream, m)
+{
+    reg_op(m, "waveshaper_stream_forward(Tensor x, Tensor? hist, int consumed, int oversample, int shape, Tensor? curve_cpu, float drive, "
+              "float bias, float dry, float wet, Tensor? taps_up_cpu, Tensor? taps_dn_cpu, int n_in=-1) -> (Tensor, Tensor)",
+           waveshaper_stream_op);
+}
+
+TORCH_LIBRARY_IMPL(torchfx_shaper_stream, Meta, m)
+{
+    // the history's length is the plan's (host-only: it reads the sizes alone)
+    m.impl("waveshaper_stream_forward", [](const Tensor &x, const OptTensor &, int64_t, int64_t oversample, int64_t, const OptTensor &curve,
+                                           double, double, double, double, const OptTensor &taps_up, const OptTensor &taps_dn, int64_t) {
+        const char *what = "waveshaper_stream_forward";
+        const auto count = [](const OptTensor &t) { return t.has_value() && t->defined() ? t->numel() : (int64_t)0; };
+        const int64_t rows = stream_rows(x);
+        int64_t info[6];
+        check_rc(tfx_waveshaper_stream_plan_info(rows, x.size(-1), oversample, oversample == 1 ? 0 : count(taps_up),
+                                                 oversample == 1 ? 0 : count(taps_dn), count(curve), dtype_code(x, what), info,
+                                                 info + 1, info + 2, info + 3, info + 4, info + 5),
+                 what);
+        return std::make_tuple(at::empty_like(x), at::empty({rows, info[1]}, x.options()));
+    });
 }
 
 // The reference's module surface (binding.cpp:83-96): exactly these three names and argument lists.

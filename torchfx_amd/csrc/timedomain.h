@@ -125,6 +125,13 @@ void waveshaper_forward(const void *x, void *y, int dtype, int64_t rows, int64_t
 void waveshaper_plan_info(int64_t rows, int64_t T, int64_t oversample, int64_t nh_up, int64_t nh_dn, int64_t curve_n, int dtype,
                           int64_t *tile, int64_t *tiles, int64_t *reach_before, int64_t *reach_after, int64_t *lds_bytes,
                           int64_t *taps_up, int64_t *taps_dn);
+void waveshaper_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t n_in, int64_t consumed,
+                               int64_t oversample, int shape, const void *curve_host, int64_t curve_n, double drive, double bias,
+                               double dry, double wet, const void *taps_up_host, int64_t nh_up, const void *taps_dn_host,
+                               int64_t nh_dn, const void *hist_in, void *hist_out, hipStream_t stream);
+void waveshaper_stream_plan_info(int64_t rows, int64_t T, int64_t oversample, int64_t nh_up, int64_t nh_dn, int64_t curve_n, int dtype,
+                                 int64_t *latency, int64_t *history, int64_t *tile, int64_t *tiles, int64_t *positions,
+                                 int64_t *lds_bytes);
 void waveshaper_clear();
 
 // ---- layout.hip ----

@@ -21,6 +21,13 @@
 // Lp: the extra terms add +-0.  A tile whose window holds a NaN or an Inf sums exactly the Lp terms of the definition from LDS,
 // so the sample poisons exactly the outputs whose windows cover it; the decimator always sums exactly its Lp_dn terms.  Either
 // way an output's bits do not depend on where the tiles fall.  The tiling is fixed: it does not depend on the row count.
+//
+// Stream form (tfx_waveshaper_stream_forward, waveshaper_kernel<T, LP, true>): the same kernel on [hist | x], a row's carried
+// history and its chunk in their two buffers.  A chunk's outputs trail its inputs by the latency D = reach_before; the masks of
+// the shaped signal are the stream's start and its end (or none), not the row's; the dry term comes from the staged window;
+// whole waves whose positions no output of the chunk reads skip `up` and `shape`, and a chunk of at most 512 samples runs two
+// of the decimator's R chains per thread.  Every sum, the transfer function and the mix are the one-shot form's source, so the
+// bits agree.  The launch also writes the next chunk's history (WsStreamPlan below has the geometry).
 #include "common.h"
 #include "plan_cache.h"
 #include "polyphase.h"
@@ -28,6 +35,8 @@
 #include "timedomain.h"
 #include "../../include/torchfx_hip.h"
 
+#include <algorithm>
+#include <cmath>
 #include <vector>
 
 namespace tfx {
@@ -60,6 +69,41 @@ template <typename T> struct WsArgs {
     int CA;                     // absolute column of wbuf's column 0, counted from the tile's first output
     int ncols;                  // columns the decimator reads: N + Q0
     T drive, bias, c0, dry, wet;
+    // stream form only (tfx_waveshaper_stream_forward): a row is [hist | x], T_ = Nc + n_in is where its inputs end so far
+    const T *hist;              // [rows, Hs] or null (silence)
+    T *hist_out;                // [rows, Hs] or null
+    int64_t Tc, Nc, Hs, n_in;   // chunk length (pitch of x and y), inputs before the chunk (clamped), history, real inputs
+    int lat;                    // latency: output t of the chunk is stream position Nc - lat + t
+    int KX;                     // a tile of n outputs reads the up-sampled samples of its positions 0 .. n + KX
+    int ends;                   // n_in < Tc: the stream ends at T_, the shaped signal is cut there
+};
+
+// A row by sample position.  One-shot: x[row] over [0, T_).  Stream: positions [Nc - Hs, Nc) come from hist (zeros when null),
+// [Nc, T_) from x; nothing exists before 0 or from T_ on.
+template <typename T, bool STREAM> struct WsRow {
+    const T *xr, *hr;
+    int64_t N, h0, end;
+    __device__ __forceinline__ WsRow(const WsArgs<T> &p, int64_t row) : xr(nullptr), hr(nullptr), N(0), h0(0), end(p.T_)
+    {
+        if constexpr (STREAM) {
+            xr = p.x + row * p.Tc;
+            hr = p.hist ? p.hist + row * p.Hs : nullptr;
+            N = p.Nc;
+            h0 = p.Nc - p.Hs;
+        } else {
+            xr = p.x + row * p.T_;
+        }
+    }
+    __device__ __forceinline__ T at(int64_t i) const
+    {
+        if constexpr (STREAM) {
+            if (i < 0 || i >= end) return (T)0;
+            if (i >= N) return xr[i - N];
+            return (hr && i >= h0) ? hr[i - h0] : (T)0;
+        } else {
+            return (i >= 0 && i < end) ? xr[i] : (T)0;
+        }
+    }
 };
 
 template <typename T> __device__ __forceinline__ T ws_shape(int shape, T u, const WsArgs<T> &p, const T *curve)
@@ -83,7 +127,33 @@ __device__ __forceinline__ void ws_store(const T (&acc)[ws_r<T>()], const WsArgs
     }
 }
 
-template <typename T, int LP>
+// the decimator's sum for the outputs t + WS_THREADS * e, e < NE, of a thread: per tap one uniform (line, column offset) and NE
+// independent fma chains, descending j from +0
+template <typename T, int NE>
+__device__ __forceinline__ void ws_decimate(T (&acc)[ws_r<T>()], const WsArgs<T> &p, const T *wbuf, int tq)
+{
+    constexpr int WS = ws_wstride<T>();
+    constexpr int ESTEP = WS_THREADS + WS_THREADS / 32;         // ws_col(c + 256 e) - ws_col(c)
+    const tp_const_ptr<T> hd = (tp_const_ptr<T>)p.hdn;
+    auto term = [&](int j) {
+        const int a = j & (p.L - 1), b = j >> p.logL;
+        const int c = tq - b - (a != 0);
+        const T *w = wbuf + ((p.L - a) & (p.L - 1)) * WS + ws_col(c);
+        const T tap = hd[j];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) acc[e] = tp_fma(tap, w[e * ESTEP], acc[e]);
+    };
+    int j = p.Lp_dn - 1;
+    for (; j >= 7; j -= 8) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) term(j - k);
+    }
+    for (; j >= 0; --j) term(j);
+}
+
+// STREAM: one chunk of a stream.  Output o of tile k is chunk sample k * N + o at stream position Nc - lat + k * N + o (0 is
+// written where that is negative).
+template <typename T, int LP, bool STREAM>
 __global__ void __launch_bounds__(WS_THREADS) waveshaper_kernel(const WsArgs<T> p)
 {
     constexpr int R = ws_r<T>(), S = ws_stride<T>(), WS = ws_wstride<T>(), PT = ws_positions<T>();
@@ -94,24 +164,37 @@ __global__ void __launch_bounds__(WS_THREADS) waveshaper_kernel(const WsArgs<T> 
     T *wbuf = win + R * S;                                      // [L][WS]
     T *curve = wbuf + p.L * WS;                                 // [curve_n]
     const int64_t row = blockIdx.x / p.tiles, tile = blockIdx.x % p.tiles;
-    const T *xr = p.x + row * p.T_;
-    T *yr = p.y + row * p.T_;
-    const int64_t m0 = tile * p.N;
+    const WsRow<T, STREAM> xr(p, row);
+    const int64_t pitch = STREAM ? p.Tc : p.T_, y0 = tile * p.N;  // rows of y, the tile's first sample in them
+    T *yr = p.y + row * pitch + y0;
+    const int64_t m0 = y0 - (STREAM ? p.lat - p.Nc : 0);        // position of the tile's first output
+    const int64_t left = pitch - y0;
+    const int mend = (int)(left < p.N ? left : p.N);            // the tile's outputs
+    // the positions whose up-sampled samples they read, in whole waves
+    constexpr int WV = 64 * R;
+    const int npos = STREAM ? min(PT, ((mend + p.KX) / WV + 1) * WV) : PT;
+    const int span = STREAM ? npos + LP - 1 : SPAN;
     const int64_t s0 = m0 + p.I0 - (LP - 1);                    // first input of the window
     const int t = (int)threadIdx.x;
+    if constexpr (STREAM) {
+        if (p.hist_out) {
+            const T *hr = p.hist ? p.hist + row * p.Hs : nullptr;
+            for (int64_t j = tile * WS_THREADS + t; j < p.Hs; j += p.tiles * WS_THREADS)
+                p.hist_out[row * p.Hs + j] = stream_hist_at(p.x + row * p.Tc, hr, p.n_in, p.Hs, j);
+        }
+    }
     bool bad = false;
-    for (int j0 = 0; j0 < SPAN; j0 += WS_THREADS * RS_STAGE_BATCH) {
+    for (int j0 = 0; j0 < span; j0 += WS_THREADS * RS_STAGE_BATCH) {
         T v[RS_STAGE_BATCH];
 #pragma unroll
         for (int u = 0; u < RS_STAGE_BATCH; ++u) {
             const int j = j0 + u * WS_THREADS + t;
-            const int64_t i = s0 + j;
-            v[u] = (j < SPAN && i >= 0 && i < p.T_) ? xr[i] : (T)0;
+            v[u] = j < span ? xr.at(s0 + j) : (T)0;
         }
 #pragma unroll
         for (int u = 0; u < RS_STAGE_BATCH; ++u) {
             const int j = j0 + u * WS_THREADS + t;
-            if (j < SPAN) win[(j % R) * S + j / R] = v[u];
+            if (j < span) win[(j % R) * S + j / R] = v[u];
             bad |= !isfinite(v[u]);
         }
     }
@@ -119,18 +202,22 @@ __global__ void __launch_bounds__(WS_THREADS) waveshaper_kernel(const WsArgs<T> 
         for (int k = t; k < p.curve_n; k += WS_THREADS) curve[k] = p.curve[k];
     const bool finite = !__syncthreads_or(bad);
 
-    // wbuf index `rel` = (n - (m0 + CA) * L) of the up-sampled sample n; the samples of [0, T * L) are the row's
+    // wbuf index `rel` = (n - (m0 + CA) * L) of the up-sampled sample n; the samples of [0, T * L) are the row's (stream: from
+    // the stream's start to its end, if the chunk says that it ends)
     const int64_t colA = m0 + p.CA;
     const int64_t lo64 = -colA * p.L, hi64 = (p.T_ - colA) * p.L, cap = (int64_t)p.ncols * p.L;
-    const int rel_lo = (int)(lo64 < 0 ? 0 : (lo64 > cap ? cap : lo64)), rel_hi = (int)(hi64 < 0 ? 0 : (hi64 > cap ? cap : hi64));
+    const int rel_lo = (int)(lo64 < 0 ? 0 : (lo64 > cap ? cap : lo64));
+    const int rel_hi = (STREAM && !p.ends) ? (int)cap : (int)(hi64 < 0 ? 0 : (hi64 > cap ? cap : hi64));
 
+    // stream: a wave none of whose positions is read skips `up` and `shape` (wave-uniform)
+    const bool active = !STREAM || __builtin_amdgcn_readfirstlane(t >> 6) * WV < npos;
     T xw[NW];
-    if (finite) {
+    if (finite && active) {
 #pragma unroll
         for (int k = 0; k < NW; ++k) xw[k] = win[(k % R) * S + t + k / R];
     }
 #pragma unroll 1
-    for (int ph = 0; ph < p.L; ++ph) {
+    for (int ph = 0; active && ph < p.L; ++ph) {
         T acc[R];
         if (finite) {
             const tp_const_ptr<T> h = (tp_const_ptr<T>)(p.hup + ph * LP);
@@ -167,41 +254,33 @@ __global__ void __launch_bounds__(WS_THREADS) waveshaper_kernel(const WsArgs<T> 
     __syncthreads();
 
     // the decimator: output m0 + t + 256 e reads, for tap j = b L + a, line (L - a) mod L at column t + 256 e + Q0 - b - (a > 0)
-    const int64_t left = p.T_ - m0;
-    const int mend = (int)(left < p.N ? left : p.N);
     T xv[R], acc[R];
 #pragma unroll
     for (int e = 0; e < R; ++e) {
         const int m = t + WS_THREADS * e;
-        xv[e] = m < mend ? xr[m0 + m] : (T)0;
+        if constexpr (STREAM) {                                 // position m0 + m is window index m - I0 + LP - 1
+            const int k = m - p.I0 + LP - 1;
+            xv[e] = m < mend ? win[(k % R) * S + k / R] : (T)0;
+        } else {
+            xv[e] = m < mend ? xr.xr[m0 + m] : (T)0;
+        }
         acc[e] = (T)0;
     }
-    const tp_const_ptr<T> hd = (tp_const_ptr<T>)p.hdn;
-    const int tq = t + p.Q0;
-    constexpr int ESTEP = WS_THREADS + WS_THREADS / 32;         // ws_col(c + 256 e) - ws_col(c)
-    auto term = [&](int j) {
-        const int a = j & (p.L - 1), b = j >> p.logL;
-        const int c = tq - b - (a != 0);
-        const T *w = wbuf + ((p.L - a) & (p.L - 1)) * WS + ws_col(c);
-        const T tap = hd[j];
-#pragma unroll
-        for (int e = 0; e < R; ++e) acc[e] = tp_fma(tap, w[e * ESTEP], acc[e]);
-    };
-    int j = p.Lp_dn - 1;
-    for (; j >= 7; j -= 8) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) term(j - k);
-    }
-    for (; j >= 0; --j) term(j);
+    if (STREAM && mend <= 2 * WS_THREADS) ws_decimate<T, 2>(acc, p, wbuf, t + p.Q0);
+    else ws_decimate<T, R>(acc, p, wbuf, t + p.Q0);
 #pragma unroll
     for (int e = 0; e < R; ++e) {
         const int m = t + WS_THREADS * e;
-        if (m < mend) yr[m0 + m] = shape_fn::add(shape_fn::mul(p.dry, xv[e]), shape_fn::mul(p.wet, acc[e]));
+        if (m < mend) {
+            const T y = shape_fn::add(shape_fn::mul(p.dry, xv[e]), shape_fn::mul(p.wet, acc[e]));
+            yr[m] = (STREAM && m0 + m < 0) ? (T)0 : y;
+        }
     }
 }
 
 // L = 1: no filters, y = dry x + wet (f(drive x + bias) - c0)
-template <typename T> __global__ void __launch_bounds__(WS_THREADS) waveshaper_plain_kernel(const WsArgs<T> p, int64_t n)
+// ENDS (a stream's chunk with n_in < Tc real inputs per row): x[., n_in:] is not read and the outputs there are zeros
+template <typename T, bool ENDS> __global__ void __launch_bounds__(WS_THREADS) waveshaper_plain_kernel(const WsArgs<T> p, int64_t n)
 {
     extern __shared__ __align__(16) unsigned char ws_lds_raw[];
     T *curve = (T *)ws_lds_raw;
@@ -212,15 +291,18 @@ template <typename T> __global__ void __launch_bounds__(WS_THREADS) waveshaper_p
     constexpr int E = 4;
     const int64_t base = (int64_t)blockIdx.x * (WS_THREADS * E) + threadIdx.x;
     T v[E];
+    bool real[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         const int64_t i = base + (int64_t)e * WS_THREADS;
-        v[e] = i < n ? p.x[i] : (T)0;
+        real[e] = i < n && (!ENDS || i % p.Tc < p.n_in);
+        v[e] = real[e] ? p.x[i] : (T)0;
     }
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         const int64_t i = base + (int64_t)e * WS_THREADS;
-        if (i < n) p.y[i] = shape_fn::add(shape_fn::mul(p.dry, v[e]), shape_fn::mul(p.wet, ws_shape<T>(p.shape, v[e], p, curve)));
+        const T y = shape_fn::add(shape_fn::mul(p.dry, v[e]), shape_fn::mul(p.wet, ws_shape<T>(p.shape, v[e], p, curve)));
+        if (i < n) p.y[i] = (ENDS && !real[e]) ? (T)0 : y;
     }
 }
 
@@ -308,23 +390,32 @@ void waveshaper_plan_info(int64_t rows, int64_t T, int64_t oversample, int64_t n
 // curve tables by content (the bytes plus the element size)
 static PlanCache<DeviceBuffer, 1> g_curves(32, "waveshaper_forward");
 
-template <typename T, int LP> static void waveshaper_launch_lp(const WsArgs<T> &p, int64_t rows, size_t lds, hipStream_t stream)
+template <typename T, int LP, bool STREAM>
+static void waveshaper_launch_lp(const WsArgs<T> &p, int64_t rows, size_t lds, hipStream_t stream)
 {
     static size_t attr[TFX_MAX_DEVICES] = {};
     size_t &have = attr[current_device()];
     if (lds > have) {
-        TFX_HIP(hipFuncSetAttribute((const void *)waveshaper_kernel<T, LP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        TFX_HIP(hipFuncSetAttribute((const void *)waveshaper_kernel<T, LP, STREAM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         have = lds;
     }
-    ProfScope ps("waveshaper_kernel", stream);
-    hipLaunchKernelGGL((waveshaper_kernel<T, LP>), dim3((unsigned)(rows * p.tiles)), dim3(WS_THREADS), lds, stream, p);
+    ProfScope ps(STREAM ? "waveshaper_stream_kernel" : "waveshaper_kernel", stream);
+    hipLaunchKernelGGL((waveshaper_kernel<T, LP, STREAM>), dim3((unsigned)(rows * p.tiles)), dim3(WS_THREADS), lds, stream, p);
     TFX_HIP(hipGetLastError());
 }
+
+// the stream form's extra arguments (tfx_waveshaper_stream_forward); N is `consumed` after the clamp
+struct WsStreamArgs {
+    const void *hist_in;
+    void *hist_out;
+    int64_t n_in, N, D, Hs, KX;
+};
 
 template <typename T>
 static void waveshaper_launch(const void *x, void *y, int64_t rows, int64_t T_, int shape, const void *curve_host, int64_t curve_n,
                               double drive, double bias, double dry, double wet, const void *taps_up_host, int64_t nh_up,
-                              const void *taps_dn_host, int64_t nh_dn, const WsPlan &pl, hipStream_t stream)
+                              const void *taps_dn_host, int64_t nh_dn, const WsPlan &pl, hipStream_t stream,
+                              const WsStreamArgs *st = nullptr)
 {
     std::shared_ptr<DeviceBuffer> tup, tdn, tcurve;
     WsArgs<T> p{};
@@ -332,6 +423,11 @@ static void waveshaper_launch(const void *x, void *y, int64_t rows, int64_t T_, 
     p.curve_n = (int)curve_n; p.N = (int)pl.N; p.I0 = (int)pl.I0; p.Lp_up = (int)pl.Lp_up; p.Lp_dn = (int)pl.Lp_dn; p.D = (int)pl.D;
     p.Q0 = (int)pl.Q0; p.CA = (int)pl.CA; p.ncols = (int)pl.ncols;
     p.drive = (T)drive; p.bias = (T)bias; p.dry = (T)dry; p.wet = (T)wet;
+    if (st) {                                   // T_ is the chunk's length; the kernel's T_ is where the stream's inputs end so far
+        p.hist = (const T *)st->hist_in; p.hist_out = (T *)st->hist_out;
+        p.Tc = T_; p.Nc = st->N; p.Hs = st->Hs; p.n_in = st->n_in; p.lat = (int)st->D; p.KX = (int)st->KX; p.ends = st->n_in < T_;
+        p.T_ = st->N + st->n_in;
+    }
     // c0 = f(bias) in float64 (bias and the curve as the signal's dtype holds them), rounded once
     std::vector<double> cd;
     if (shape == TFX_SHAPE_CURVE) {
@@ -345,22 +441,40 @@ static void waveshaper_launch(const void *x, void *y, int64_t rows, int64_t T_, 
     p.c0 = (T)shape_fn::apply<double, double>(shape, (double)p.bias, cd.data(), (int)curve_n);
     if (pl.L == 1) {
         const int64_t n = rows * T_;
-        ProfScope ps("waveshaper_plain_kernel", stream);
-        hipLaunchKernelGGL((waveshaper_plain_kernel<T>), dim3((unsigned)ceil_div(n, pl.N)), dim3(WS_THREADS), (size_t)pl.lds, stream, p, n);
+        const dim3 grid((unsigned)ceil_div(n, pl.N));
+        ProfScope ps(st ? "waveshaper_stream_kernel" : "waveshaper_plain_kernel", stream);
+        if (st && p.ends) hipLaunchKernelGGL((waveshaper_plain_kernel<T, true>), grid, dim3(WS_THREADS), (size_t)pl.lds, stream, p, n);
+        else hipLaunchKernelGGL((waveshaper_plain_kernel<T, false>), grid, dim3(WS_THREADS), (size_t)pl.lds, stream, p, n);
         TFX_HIP(hipGetLastError());
         return;
     }
     p.hup = resample_table<T>(taps_up_host, nh_up, pl.L, 1, pl.gu.pre_pad, pl.LP, stream, &tup);
     p.hdn = resample_table<T>(taps_dn_host, nh_dn, 1, pl.L, pl.gd.pre_pad, pl.Lp_dn, stream, &tdn);
+    const size_t lds = (size_t)pl.lds;
+#define TFX_WS_CASE(LP_) \
+    if (st) waveshaper_launch_lp<T, LP_, true>(p, rows, lds, stream); \
+    else waveshaper_launch_lp<T, LP_, false>(p, rows, lds, stream); \
+    break
     switch (pl.LP) {
-    case 8: waveshaper_launch_lp<T, 8>(p, rows, (size_t)pl.lds, stream); break;
-    case 16: waveshaper_launch_lp<T, 16>(p, rows, (size_t)pl.lds, stream); break;
-    case 24: waveshaper_launch_lp<T, 24>(p, rows, (size_t)pl.lds, stream); break;
-    case 32: waveshaper_launch_lp<T, 32>(p, rows, (size_t)pl.lds, stream); break;
-    case 48: waveshaper_launch_lp<T, 48>(p, rows, (size_t)pl.lds, stream); break;
-    case 64: waveshaper_launch_lp<T, 64>(p, rows, (size_t)pl.lds, stream); break;
-    default: waveshaper_launch_lp<T, (int)TP_LP_MAX>(p, rows, (size_t)pl.lds, stream); break;
+    case 8: TFX_WS_CASE(8);
+    case 16: TFX_WS_CASE(16);
+    case 24: TFX_WS_CASE(24);
+    case 32: TFX_WS_CASE(32);
+    case 48: TFX_WS_CASE(48);
+    case 64: TFX_WS_CASE(64);
+    default: TFX_WS_CASE((int)TP_LP_MAX);
     }
+#undef TFX_WS_CASE
+}
+
+// what both entries refuse about the values (host-only)
+static void waveshaper_check_values(const char *who, int64_t oversample, int shape, const void *curve_host, double drive, double bias,
+                                    double dry, double wet, const void *taps_up_host, const void *taps_dn_host)
+{
+    TFX_CHECK(std::isfinite(drive) && std::isfinite(bias) && std::isfinite(dry) && std::isfinite(wet),
+              "%s: drive, bias, dry and wet must be finite", who);
+    TFX_CHECK(shape != TFX_SHAPE_CURVE || curve_host, "%s: no curve", who);
+    TFX_CHECK(oversample == 1 || (taps_up_host && taps_dn_host), "%s: no taps", who);
 }
 
 void waveshaper_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t oversample, int shape,
@@ -369,10 +483,7 @@ void waveshaper_forward(const void *x, void *y, int dtype, int64_t rows, int64_t
 {
     const char *who = "waveshaper_forward";
     const WsPlan pl = waveshaper_plan(who, dtype, rows, T, oversample, nh_up, nh_dn, shape, curve_n);
-    TFX_CHECK(std::isfinite(drive) && std::isfinite(bias) && std::isfinite(dry) && std::isfinite(wet),
-              "%s: drive, bias, dry and wet must be finite", who);
-    TFX_CHECK(shape != TFX_SHAPE_CURVE || curve_host, "%s: no curve", who);
-    TFX_CHECK(oversample == 1 || (taps_up_host && taps_dn_host), "%s: no taps", who);
+    waveshaper_check_values(who, oversample, shape, curve_host, drive, bias, dry, wet, taps_up_host, taps_dn_host);
     TFX_CHECK(rows * T == 0 || (x && y), "%s: null pointer", who);
     const int64_t esz = dtype == TFX_F32 ? 4 : 8;
     const char *xb = (const char *)x, *yb = (const char *)y;
@@ -386,6 +497,89 @@ void waveshaper_forward(const void *x, void *y, int dtype, int64_t rows, int64_t
                                   nh_dn, pl, stream);
 }
 
+// ---- the stream form ------------------------------------------------------------------------------------------------------
+// Geometry of a stream (oversample, nh_up, nh_dn alone: resample_geometry's pre_remove and Lp do not depend on T, whose terms
+// cancel in both stages).  Output n reads the inputs n - reach_after .. n + reach_before, so it is final once input n + D is
+// in, D = reach_before, and the chunk that starts with output N - D reads back to N - D - reach_after = N - Hs.  Position k of
+// a tile makes the columns k + floor(D_w / L) and, when L does not divide pre_up, the next one of wbuf (D_w: WsPlan::D); the
+// last column the tile's n outputs read is n - 1 + Q0, and only line 0 of it, which the earlier of its two positions makes: they
+// read the positions up to n + KX, KX = Q0 - ceil(D_w / L) - 1 = reach_before - 1 - I0 (a whole tile: all PT of them).
+struct WsStreamPlan {
+    WsPlan pl;
+    int64_t D, Hs, KX, positions;
+};
+
+static WsStreamPlan waveshaper_stream_plan(const char *who, int dtype, int64_t rows, int64_t T, int64_t L, int64_t nh_up,
+                                           int64_t nh_dn, int shape, int64_t curve_n)
+{
+    WsStreamPlan sp{};
+    sp.pl = waveshaper_plan(who, dtype, rows, T, L, nh_up, nh_dn, shape, curve_n);
+    if (L == 1) {
+        sp.positions = std::min(T, sp.pl.N);
+        return sp;
+    }
+    const WsPlan &pl = sp.pl;
+    const int64_t PT = dtype == TFX_F32 ? ws_positions<float>() : ws_positions<double>(), WV = PT / (WS_THREADS / 64);
+    sp.D = pl.reach_before;
+    sp.Hs = pl.reach_before + pl.reach_after;
+    sp.KX = pl.Q0 - ceil_div(pl.D + (1 << 20) * L, L) + (1 << 20) - 1;          // ceil of a D_w that may be negative
+    // the dry sample of output o is position o - I0 of the tile: staged with the positions 0 .. o + KX, at a window index >= 0
+    TFX_CHECK(pl.reach_before >= 1 && pl.reach_after >= 0 && pl.I0 <= pl.LP - 1 && sp.KX == pl.reach_before - 1 - pl.I0 &&
+                  pl.N + sp.KX == PT - 1,
+              "%s: the filters' geometry does not fit the stream", who);
+    sp.positions = T == 0 ? 0 : std::min(PT, ((std::min(T, pl.N) + sp.KX) / WV + 1) * WV);
+    return sp;
+}
+
+void waveshaper_stream_plan_info(int64_t rows, int64_t T, int64_t oversample, int64_t nh_up, int64_t nh_dn, int64_t curve_n, int dtype,
+                                 int64_t *latency, int64_t *history, int64_t *tile, int64_t *tiles, int64_t *positions,
+                                 int64_t *lds_bytes)
+{
+    const WsStreamPlan sp = waveshaper_stream_plan("waveshaper_stream_plan_info", dtype, rows, T, oversample, nh_up, nh_dn,
+                                                   curve_n ? TFX_SHAPE_CURVE : TFX_SHAPE_HARD, curve_n);
+    *latency = sp.D;
+    *history = sp.Hs;
+    *tile = sp.pl.N;
+    *tiles = sp.pl.tiles;
+    *positions = sp.positions;
+    *lds_bytes = sp.pl.lds;
+}
+
+void waveshaper_stream_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t n_in, int64_t consumed,
+                               int64_t oversample, int shape, const void *curve_host, int64_t curve_n, double drive, double bias,
+                               double dry, double wet, const void *taps_up_host, int64_t nh_up, const void *taps_dn_host,
+                               int64_t nh_dn, const void *hist_in, void *hist_out, hipStream_t stream)
+{
+    const char *who = "waveshaper_stream_forward";
+    const WsStreamPlan sp = waveshaper_stream_plan(who, dtype, rows, T, oversample, nh_up, nh_dn, shape, curve_n);
+    waveshaper_check_values(who, oversample, shape, curve_host, drive, bias, dry, wet, taps_up_host, taps_dn_host);
+    TFX_CHECK(n_in >= 0 && n_in <= T, "%s: n_in = %lld is not in [0, T = %lld]", who, (long long)n_in, (long long)T);
+    TFX_CHECK(consumed >= 0, "%s: negative stream position %lld", who, (long long)consumed);
+    TFX_CHECK(rows * T == 0 || y, "%s: null pointer", who);
+    TFX_CHECK(rows * n_in == 0 || x, "%s: null pointer", who);
+    const size_t esz = dtype == TFX_F32 ? 4 : 8;
+    check_stream_buffers(who, esz, x, rows * T, y, rows * T, hist_in, hist_out, rows * sp.Hs);
+    if (rows == 0) return;
+    if (T == 0) {                                // nothing in, nothing out: the history moves on unchanged
+        const size_t bytes = (size_t)(rows * sp.Hs) * esz;
+        if (hist_out && bytes) {
+            if (hist_in) TFX_HIP(hipMemcpyAsync(hist_out, hist_in, bytes, hipMemcpyDeviceToDevice, stream));
+            else TFX_HIP(hipMemsetAsync(hist_out, 0, bytes, stream));
+        }
+        return;
+    }
+    // positions before N - Hs are never read and position 0 matters only while it lies in [N - Hs, N + T): past Hs + D every N
+    // gives the same chunk
+    const WsStreamArgs st{hist_in, hist_out, n_in, std::min(consumed, sp.Hs + sp.D), sp.D, sp.Hs, sp.KX};
+    if (dtype == TFX_F32)
+        waveshaper_launch<float>(x, y, rows, T, shape, curve_host, curve_n, drive, bias, dry, wet, taps_up_host, nh_up, taps_dn_host,
+                                 nh_dn, sp.pl, stream, &st);
+    else
+        waveshaper_launch<double>(x, y, rows, T, shape, curve_host, curve_n, drive, bias, dry, wet, taps_up_host, nh_up, taps_dn_host,
+                                  nh_dn, sp.pl, stream, &st);
+}
+
 void waveshaper_clear() { g_curves.clear(); }
 
 }  // namespace tfx
+

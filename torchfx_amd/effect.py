@@ -583,7 +583,8 @@ class Waveshaper(FX):
     ("hard", "cubic", "tanh"; default "tanh") or a ``curve`` table of 2 to 4096 points over ``[-1, 1]`` (WebAudio's
     ``WaveShaperNode`` rule), ``drive_db``, ``bias``, ``oversample`` (1, 2, 4 or 8), ``mix``, ``output_db`` and the resampling
     ``window``.  It needs no sample rate.  Every call zero-pads its edges: the effect is a step of its own in ``Wave.plan()``
-    (one launch, ``csrc/waveshaper.hip``), and the stream processors take it with ``oversample=1`` only."""
+    (one launch, ``csrc/waveshaper.hip``), and the stream processors take it with ``oversample=1`` only:
+    :class:`torchfx_amd.realtime.StatefulWaveshaper` / ``StatefulDistortion`` are the effects for a chunked stream."""
 
     def __init__(self, shape: str | None = None, drive_db: float = 0.0, bias: float = 0.0, oversample: int = 4, mix: float = 1.0,
                  output_db: float = 0.0, curve=None, window=("kaiser", 5.0)) -> None:

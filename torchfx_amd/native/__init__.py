@@ -95,3 +95,11 @@ def shaper_ops():
 
     load()
     return torch.ops.torchfx_shaper
+
+
+def shaper_stream_ops():
+    """``torch.ops.torchfx_shaper_stream`` (the waveshaper's stream form, registered by the same module) with the library loaded."""
+    import torch
+
+    load()
+    return torch.ops.torchfx_shaper_stream

@@ -26,6 +26,10 @@ delay line's reach in ``_hist`` and the LFO's position in ``_pos`` (a device cou
 their chunks are bit-identical to the one-shot effect on the whole signal.  :class:`StatefulFreeverb` is the room reverb of a
 stream: causal, no latency, it carries every delay line in time order (``tfx_freeverb_forward``'s state), its chunks equal
 ``freeverb`` on the whole signal to float64 round-off (not bit for bit) and ``flush()`` returns the ring-out.
+:class:`StatefulWaveshaper` and :class:`StatefulDistortion` are the oversampled waveshaper of a stream: they carry the last
+``reach_before + reach_after`` inputs of every row, hold the last ``D = reach_before`` outputs back
+(``tfx_waveshaper_stream_forward``, one launch per chunk), and their chunks plus ``flush()`` are bit-identical to ``waveshape`` on
+the whole signal; ``aligned=False`` gives the constant-latency form.
 
 Small chunks are launch-bound (a 2 x 4096 step is ~60 us of host + launch overhead for a few us of
 GPU work), so ``StreamProcessor(..., use_graph=True)`` captures one full-size chunk step -- every
@@ -45,7 +49,7 @@ from collections.abc import Generator, Sequence
 import torch
 from torch import Tensor, nn
 
-from torchfx_amd.effect import (FX, Chorus, Compressor, Delay, Flanger, Freeverb, Limiter, ModulatedDelay, MonoDelayStrategy, PingPongDelayStrategy,
+from torchfx_amd.effect import (FX, Chorus, Compressor, Delay, Distortion, Flanger, Freeverb, Limiter, ModulatedDelay, MonoDelayStrategy, PingPongDelayStrategy,
                                 Reverb, Vibrato, Waveshaper, _ext)
 from torchfx_amd.filter._base import AbstractFilter
 from torchfx_amd.filter.fir import FIR
@@ -669,12 +673,200 @@ def _refuse_freeverb(e, who: str) -> None:
                         "(wave | Freeverb(...)) before or after streaming")
 
 
+class _ShaperStream(_RingOut):
+    """An oversampled waveshaper (:class:`~torchfx_amd.effect.Waveshaper`) over a continuous stream; mixed in in front of the
+    effect class.  An output reads ``latency`` = ``D = reach_before`` samples ahead and ``reach_after`` behind
+    (:func:`torchfx_ext.waveshaper_plan_info`: 21 and 20 for the default window at every ``oversample > 1``), so after ``N``
+    input samples per row the stream has returned the first ``max(0, N - D)`` samples of
+    :func:`~torchfx_amd.waveshaper.waveshape` on the whole signal, each final, and :meth:`flush` returns the remaining
+    ``min(N, D)``, computed with the stream ending at ``N``.  ``oversample=1`` is memoryless: no history, no latency, nothing to
+    flush.
+
+    * ``aligned=True``: a chunk returns the outputs it completes -- ``max(0, N + T - D) - max(0, N - D)`` samples, possibly
+      none.  All chunk outputs followed by ``flush()`` are ``waveshape`` on the whole signal: ``torch.equal``, on the same device
+      and in the same dtype, whatever the chunk sizes, a NaN's or an Inf's reach included.
+    * ``aligned=False`` (constant latency, what a sound card needs): every chunk returns the chunk's shape, the one-shot result
+      delayed by ``D`` samples with zeros first; ``flush()`` still returns the last ``min(N, D)``.
+
+    Every row carries its last ``history_length`` = ``Hs = reach_before + reach_after`` input samples in ``_hist``
+    (``[rows, Hs]``) and the stream one host integer, ``min(N, Hs + D)``: no chunk waits on the device.  Device float32 / float64
+    chunks run one launch each (:func:`torchfx_ext.waveshaper_stream_forward`, which reads the history and the chunk from their
+    two buffers); CPU chunks run the host definition on ``[history | chunk]``.  ``drive_db``, ``bias``, ``mix``, ``output_db``,
+    ``shape`` and ``curve`` may change between chunks without a restart; such a run equals no one-shot call.  The stream restarts
+    from silence -- and what is held back is dropped -- when ``oversample`` or the taps of ``window`` change and when the row count,
+    dtype or device changes.  A ``Wave`` is a whole signal: pipe it through ``Waveshaper`` / ``Distortion`` instead."""
+
+    def __init__(self, *args, aligned: bool = True, **kwargs) -> None:
+        super().__init__(*args, **kwargs)
+        self.aligned = bool(aligned)
+        self._geos: dict = {}
+        self.reset_state()
+
+    def reset_state(self) -> None:
+        self._hist: Tensor | None = None
+        self._pos = 0                               # min(N, Hs + D): input samples per row so far, as far as it matters
+        self._key: tuple | None = None              # what the running stream is bound to (see _stream)
+        self._geo: tuple[int, int] = (0, 0)         # its (D, Hs)
+        self._last: tuple | None = None
+
+    def _geometry(self, L: int, up: Tensor | None, dn: Tensor | None) -> tuple[int, int]:
+        """``(D, Hs)`` of the stream: ``tfx_waveshaper_stream_plan_info``'s latency and history (host-only)."""
+        key = (L, 0 if up is None else int(up.numel()), 0 if dn is None else int(dn.numel()))
+        geo = self._geos.get(key)
+        if geo is None:
+            info = _ext().waveshaper_stream_plan_info(0, *key)
+            geo = self._geos[key] = (info["latency"], info["history"])
+        return geo
+
+    @property
+    def latency(self) -> int:
+        """The samples the stream holds back (``D``): what :meth:`flush` returns at most, and the delay of ``aligned=False``."""
+        P = self.params()
+        return self._geometry(P.oversample, *P.taps(torch.float32))[0]
+
+    @property
+    def history_length(self) -> int:
+        """The input samples every row carries between chunks (``Hs = reach_before + reach_after``)."""
+        P = self.params()
+        return self._geometry(P.oversample, *P.taps(torch.float32))[1]
+
+    def _stream(self, lead: tuple, dtype: torch.dtype, device) -> tuple:
+        """``(P, taps up, taps down, key, (D, Hs))`` for chunks of leading shape ``lead``: a stream lives while ``key`` stays."""
+        if dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{type(self).__name__}: float32 or float64 signals only, got {dtype}")
+        P = self.params()
+        up, dn = P.taps(dtype)
+        taps = None if up is None else (up.numpy().tobytes(), dn.numpy().tobytes())
+        return P, up, dn, (math.prod(lead), dtype, device, P.oversample, taps), self._geometry(P.oversample, up, dn)
+
+    def route(self, x: Tensor, length: int | None = None) -> str:
+        """``native (waveshaper_stream_kernel, ...)`` for the next chunk of ``x``, or the host / refusal route."""
+        if not _native_stream(x):
+            return super().route(x, length)
+        try:
+            P = self.params()
+            up, dn = P.taps(x.dtype)
+            n = int(x.shape[-1]) if length is None else int(length)
+            info = _ext().waveshaper_stream_plan_info(n, P.oversample, 0 if up is None else up.numel(), 0 if dn is None else dn.numel(),
+                                                      0 if P.curve is None else P.curve.size, x.dtype)
+        except (RuntimeError, ValueError, TypeError) as e:
+            return f"refused -- {e}"
+        return (f"native (waveshaper_stream_kernel, L = {P.oversample}, {P.shape}, latency {info['latency']}, history {info['history']}, "
+                f"{info['tiles']} tile(s) of {info['tile']}, {info['positions']} positions up-sampled and shaped; one launch)")
+
+    def _capture_key(self) -> tuple:
+        """What a captured HIP graph of this effect bakes in: every parameter of the launch."""
+        P = self.params()
+        return (P.shape, None if P.curve is None else P.curve.tobytes(), P.drive, P.bias, P.oversample, P.dry, P.wet,
+                window_key(P.window), self.aligned)
+
+    def _sync_history(self) -> None:
+        """Nothing to resize: a parameter that changes the history's length restarts the stream (``_graph_ready``)."""
+
+    def _graph_ready(self, x: Tensor) -> bool:
+        """A replay skips :meth:`forward`: it leaves nothing stale once the position counter has saturated, for the stream
+        that is running."""
+        if self._key is None or self._pos != sum(self._geo):
+            return False
+        return self._stream(tuple(x.shape[:-1]), x.dtype, x.device)[3] == self._key
+
+    def _launch(self, x: Tensor, P, up, dn, n_in: int | None = None) -> Tensor:
+        curve = None if P.curve is None else torch.from_numpy(P.curve).to(x.dtype)
+        with torch.cuda.device(x.device):
+            y, hist = _ext().waveshaper_stream_forward(x, self._hist, self._pos, P.oversample, P.shape, curve, P.drive, P.bias, P.dry,
+                                                       P.wet, up, dn, n_in)
+        if n_in is None:
+            self._hist = hist
+        return y
+
+    @torch.no_grad()
+    def forward(self, x: Tensor) -> Tensor:
+        _rows(x)
+        P, up, dn, key, geo = self._stream(tuple(x.shape[:-1]), x.dtype, x.device)
+        if key != self._key:                        # a new stream: from silence
+            self.reset_state()
+            self._key, self._geo = key, geo
+        self._note(x)
+        (D, Hs), N, T = geo, self._pos, x.shape[-1]
+        if T == 0:
+            return torch.zeros_like(x)
+        y = self._launch(x, P, up, dn) if _native_stream(x) else self._host_chunk(x, P)
+        self._pos = min(N + T, Hs + D)
+        k = min(T, max(0, D - N)) if self.aligned else 0         # outputs in front of position 0
+        return y[..., k:] if k else y
+
+    def _window(self, rows: int, dtype: torch.dtype) -> tuple[Tensor, Tensor]:
+        """``(history [rows, Hs], its valid part)``: the part starts at position 0 while the stream is younger than ``Hs``."""
+        Hs = self._geo[1]
+        hist = self._hist.cpu() if self._hist is not None else torch.zeros(rows, Hs, dtype=dtype)
+        return hist, hist[:, Hs - min(self._pos, Hs):]
+
+    def _host_chunk(self, x: Tensor, P) -> Tensor:
+        """One chunk on the host: the one-shot definition on ``[history | chunk]`` -- its start is position 0 or the sample
+        ``reach_after`` behind the chunk's first output, its end the sample ``reach_before`` past its last one, so no output that
+        is cut out of it reads a truncated edge -- and the chunk's outputs cut from it."""
+        from torchfx_amd.waveshaper import _waveshape_host
+
+        (D, Hs), N, T = self._geo, self._pos, x.shape[-1]
+        rows = math.prod(x.shape[:-1])
+        hist, valid = self._window(rows, x.dtype)
+        xr = x.detach().reshape(rows, T).cpu()
+        v = torch.cat([valid, xr], dim=-1)                   # positions [N - valid, N + T)
+        self._hist = torch.cat([hist, xr], dim=-1)[:, T:].to(x.device)
+        out = torch.zeros(rows, T, dtype=x.dtype)
+        lo = max(0, N - D)
+        n = N + T - D - lo
+        if n > 0:
+            s = lo - (N - valid.shape[-1])
+            out[:, T - n:] = _waveshape_host(v, P)[:, s:s + n]
+        return out.reshape(x.shape).to(x.device)
+
+    @torch.no_grad()
+    def flush(self) -> Tensor:
+        """The outputs still held back (the last ``min(N, latency)`` samples of the one-shot result), computed with the stream
+        ending here and shaped like the last chunk; then the state is reset.  Without a chunk since the last reset, or after a
+        parameter change that restarts the stream: an empty tensor."""
+        if self._last is None:
+            return torch.zeros(0)
+        lead, dtype, device = self._last
+        P, up, dn, key, _ = self._stream(lead, dtype, device)
+        D, N = self._geo[0], self._pos
+        n = min(N, D) if key == self._key else 0
+        if n == 0:
+            tail = self._zeros(0)
+        elif device.type == "cuda":                   # a chunk of D samples with no input in it: the stream ends at N
+            tail = self._launch(self._zeros(D), P, up, dn, 0)[..., D - n:].contiguous()
+        else:
+            from torchfx_amd.waveshaper import _waveshape_host
+
+            v = self._window(math.prod(lead), dtype)[1]
+            tail = _waveshape_host(v, P)[:, v.shape[-1] - n:].reshape(*lead, n).to(device)
+        self.reset_state()
+        return tail
+
+
+class StatefulWaveshaper(_ShaperStream, Waveshaper):
+    """:class:`~torchfx_amd.effect.Waveshaper` over a continuous stream, with its constructor arguments plus ``aligned``
+    (see :class:`_ShaperStream`)."""
+
+
+class StatefulDistortion(_ShaperStream, Distortion):
+    """:class:`~torchfx_amd.effect.Distortion` over a continuous stream, with its constructor arguments plus ``aligned``
+    (see :class:`_ShaperStream`)."""
+
+
 def _refuse_waveshaper(e, who: str) -> None:
-    for m in (e.modules() if isinstance(e, nn.Module) else [e]):
-        if isinstance(m, Waveshaper) and m.oversample != 1:
+    members = list(e.modules() if isinstance(e, nn.Module) else [e])
+    for m in members:
+        if isinstance(m, Waveshaper) and not isinstance(m, _ShaperStream) and m.oversample != 1:
             raise TypeError(f"{type(m).__name__} with oversample={m.oversample} cannot run in {who}: every call zero-pads the edges "
-                            "of its resampling filters, so a chunked stream would click at every chunk seam; use oversample=1 "
-                            f"(memoryless) here, or run the whole signal (wave | {type(m).__name__}(...)) before or after streaming")
+                            "of its resampling filters, so a chunked stream would click at every chunk seam; use "
+                            f"Stateful{type(m).__name__ if type(m) in (Waveshaper, Distortion) else 'Waveshaper'}(...) in its place, "
+                            f"oversample=1 (memoryless), or run the whole signal (wave | {type(m).__name__}(...)) before or after "
+                            "streaming")
+    if not isinstance(e, _ShaperStream) and any(isinstance(m, _ShaperStream) for m in members):
+        raise TypeError(f"StatefulWaveshaper / StatefulDistortion must be a top-level effect of the chain in {who}: the processor "
+                        "flushes what it holds back at the end of the stream")
 
 
 class _ModulationStream:
@@ -753,7 +945,7 @@ def _refuse_modulation(e, who: str) -> None:
 
 def _holds_back(e) -> bool:
     """Effects whose chunks may return fewer samples than they take and that hand the rest out in ``flush()``."""
-    return isinstance(e, (StatefulResample, StatefulLimiter))
+    return isinstance(e, (StatefulResample, StatefulLimiter, _ShaperStream))
 
 
 def _has_stateful_resample(e) -> bool:
@@ -940,8 +1132,9 @@ class StreamProcessor:
                                 "the whole signal (Wave.resample) before or after streaming")
         self._resamplers = [e for e in self._effects if isinstance(e, StatefulResample)]
         self._limiters = [e for e in self._effects if isinstance(e, StatefulLimiter)]
-        if (self._resamplers or self._limiters) and overlap != 0:
-            who = "StatefulResample" if self._resamplers else "StatefulLimiter"
+        shapers = [e for e in self._effects if isinstance(e, _ShaperStream)]
+        if (self._resamplers or self._limiters or shapers) and overlap != 0:
+            who = "StatefulResample" if self._resamplers else ("StatefulLimiter" if self._limiters else type(shapers[0]).__name__)
             raise ValueError(f"A chain with a {who} needs overlap = 0, got {overlap}: the effect holds outputs back, so a chunk's "
                              "dropped overlap samples have no counterpart in its output")
         self._chunk_size, self._overlap, self._device = chunk_size, overlap, device
@@ -1011,7 +1204,7 @@ class StreamProcessor:
 
     def _run(self, w: Tensor, start: int = 0) -> Tensor | None:
         """The chain from segment ``start`` on; None when an effect that holds outputs back (``StatefulResample``,
-        ``StatefulLimiter``) completes no output for this chunk (the effects after it are not called)."""
+        ``StatefulLimiter``, ``StatefulWaveshaper``) completes no output for this chunk (the effects after it are not called)."""
         for e in self._segments[start:]:
             w = e(w)
             if _holds_back(e) and w.shape[-1] == 0:
@@ -1031,8 +1224,12 @@ class StreamProcessor:
 
     def _graphable(self, w: Tensor) -> bool:
         """Whether a replayed step leaves the host side of every effect right: a resampler counts samples per chunk (never),
-        a limiter only until its position counter has saturated (chunks run eagerly until then)."""
-        return not self._resamplers and all(m._graph_ready(w) for m in self._limiters)
+        a limiter or an oversampled waveshaper only until its position counter has saturated (chunks run eagerly until then).
+        Every member that has ``_graph_ready`` is asked."""
+        if self._resamplers:
+            return False
+        members = (m for e in self._effects for m in (e.modules() if isinstance(e, nn.Module) else [e]))
+        return all(m._graph_ready(w) for m in members if hasattr(m, "_graph_ready"))
 
     def _capture_members(self) -> list:
         """Members whose parameters a captured step bakes in and whose carried state can change length (StatefulDelay,
@@ -1267,6 +1464,11 @@ class RealtimeProcessor:
                                 "completes, none for the first blocks, and a sound card's output block has the input block's "
                                 "length; construct it with aligned=False (constant latency: the result delayed by "
                                 "StatefulLimiter.latency samples)")
+            if isinstance(e, _ShaperStream) and e.aligned:
+                raise TypeError(f"{type(e).__name__}(aligned=True) cannot run in RealtimeProcessor: it returns the outputs a block "
+                                "completes, fewer for the first block, and a sound card's output block has the input block's "
+                                "length; construct it with aligned=False (constant latency: the result delayed by its `latency` "
+                                "samples)")
         self._runner = StreamProcessor(modules, chunk_size=config.buffer_size, overlap=0, device=device, use_graph=use_graph)
         self._backend, self._config, self._running = backend, config, False
         self._buffer_capacity = buffer_capacity
@@ -1389,7 +1591,8 @@ class RealtimeProcessor:
 
     @property
     def chain_latency_samples(self) -> int:
-        """The delay the effects add on top of the buffer's: the sum of their ``latency`` (``StatefulLimiter``'s ``D``)."""
+        """The delay the effects add on top of the buffer's: the sum of their ``latency`` (``StatefulLimiter``'s and
+        ``StatefulWaveshaper``'s ``D``)."""
         return sum(int(getattr(e, "latency", 0) or 0) for e in self._runner.effects)
 
     is_running = property(lambda self: self._running)

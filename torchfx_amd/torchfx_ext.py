@@ -38,6 +38,7 @@ __all__ = [
     "sos_block_energy", "sos_block_energy_plan_info", "true_peak", "true_peak_plan_info", "limiter_forward", "limiter_plan_info",
     "limiter_stream_forward", "limiter_stream_plan_info", "compressor_forward", "compressor_plan_info",
     "modulated_delay_forward", "modulated_delay_stream_forward", "modulated_delay_plan_info", "freeverb_forward", "freeverb_plan_info",
+    "waveshaper_stream_forward", "waveshaper_stream_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "effects_plan_info", "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
 ]
@@ -489,6 +490,34 @@ def waveshaper_plan_info(length: int, oversample: int, taps_up: int = 0, taps_dn
     return _query(L.load().tfx_waveshaper_plan_info,
                   (int(rows), int(length), int(oversample), int(taps_up), int(taps_dn), int(curve), _dt(dtype)),
                   "tile tiles reach_before reach_after lds_bytes taps_up taps_dn")
+
+
+def waveshaper_stream_forward(x: Tensor, hist: Tensor | None, consumed: int, oversample: int, shape: str, curve: Tensor | None,
+                              drive: float, bias: float, dry: float, wet: float, taps_up: Tensor | None = None,
+                              taps_dn: Tensor | None = None, n_in: int | None = None) -> tuple[Tensor, Tensor]:
+    """One chunk of a waveshaper stream in one launch (``tfx_waveshaper_stream_forward``): ``x [..., T]`` follows ``consumed``
+    input samples per row, whose last ``Hs`` are ``hist [rows, Hs]`` (None = silence).  Returns ``(y, new history)``:
+    ``y[..., t]`` is sample ``consumed - D + t`` of :func:`waveshaper_forward` on the whole stream (0 where that is negative),
+    bit for bit.  ``n_in`` (default: all ``T``) is the number of real inputs in ``x``; fewer says that the stream ends after them
+    (the tail of a stream: ``T = D``, ``n_in = 0``).  ``D`` and ``Hs`` are :func:`waveshaper_stream_plan_info`'s ``latency`` and
+    ``history`` (both 0 for ``oversample = 1``); the other arguments are :func:`waveshaper_forward`'s
+    (``waveshaper_stream_kernel``).  The op lives in ``torch.ops.torchfx_shaper_stream``."""
+    native.ops()
+    return native.shaper_stream_ops().waveshaper_stream_forward(x.contiguous(), hist, int(consumed), int(oversample),
+                                                                WAVESHAPES.index(shape), curve, float(drive), float(bias), float(dry),
+                                                                float(wet), taps_up, taps_dn, -1 if n_in is None else int(n_in))
+
+
+def waveshaper_stream_plan_info(length: int, oversample: int, taps_up: int = 0, taps_dn: int = 0, curve: int = 0,
+                                dtype: torch.dtype = torch.float32, rows: int = 1) -> dict:
+    """What :func:`waveshaper_stream_forward` does with a chunk of ``length`` samples (``tfx_waveshaper_stream_plan_info``;
+    host-only, same checks on the sizes): the stream's ``latency`` (D = ``reach_before``) and ``history`` (Hs = ``reach_before +
+    reach_after``) -- fixed by ``oversample`` and the tap counts alone --, ``tile`` (outputs per workgroup), ``tiles`` per row,
+    ``positions`` (of a workgroup's 2048 / 1024 positions, those whose up-sampled samples the first workgroup computes: whole
+    waves) and ``lds_bytes``."""
+    return _query(L.load().tfx_waveshaper_stream_plan_info,
+                  (int(rows), int(length), int(oversample), int(taps_up), int(taps_dn), int(curve), _dt(dtype)),
+                  "latency history tile tiles positions lds_bytes")
 
 
 RESAMPLE_STREAM_KERNELS = ("resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel", "copy")

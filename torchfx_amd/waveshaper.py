@@ -185,7 +185,8 @@ def waveshape(x: Tensor, shape: str | None = None, drive_db: float = 0.0, bias: 
       zero-padded filters counts.  An up-sampled value that is not finite shapes to NaN -- the composition's ``tanh`` of an Inf
       would come back finite.  Every other output has the bits it has with a zero in that sample's place.
 
-    Argument errors are ``ValueError`` / ``TypeError`` before any launch.  A stateful streaming form for ``oversample > 1``,
-    shapes with memory, autograd and axes other than the last are not provided."""
+    Argument errors are ``ValueError`` / ``TypeError`` before any launch.  For chunked streams use
+    :class:`torchfx_amd.realtime.StatefulWaveshaper` / ``StatefulDistortion``, whose chunks plus ``flush()`` are ``torch.equal`` to
+    this call on the whole signal.  Shapes with memory, autograd and axes other than the last are not provided."""
     _check_signal(x, "waveshape")
     return shape_signal(x, ShaperParams(shape, drive_db, bias, oversample, mix, output_db, curve, window))
