@@ -58,8 +58,9 @@ struct OlsGeom {
                        // moves left by sh(c) = (sh_base + c * Tn) % 32 samples, so every frame still starts on a 128-byte line of
                        // memory; block output i of frame f is then y[f * S + i - sh(c)]  (sh_base = element offset of x in its line)
     int *nf_flag;      // cascade in pass A: [nframes], 1 = the recursion of this frame met a non-finite value (every slot written)
-    int *nf_pair;      // plain pass A: [C] zeroed per call, or null: row c's first frame shares its transform with row c - 1's last and
-                       // held a non-finite sample (only when a row has an odd number of frames)
+    int *nf_pair;      // plain pass A: [C] zeroed per call, or null: bit 0 = row c's first frame shares its transform with row c - 1's
+                       // last and held a non-finite sample, bit 1 = row c's last frame shares one with row c + 1's first and held
+                       // one (only when a row has an odd number of frames)
     int nt;            // nontemporal hints (the host passes 3): 1 = signal loads of pass A, 2 = signal stores of pass C -- the signal
                        // is read once and written once; chain step 7.98 -> 7.87 ms.  (The same hint on the workspace loads of
                        // passes B and C, their last use, changes nothing.)
@@ -188,17 +189,22 @@ ols_col_fwd16_kernel(const float *__restrict__ x, cpx *__restrict__ T, const cpx
             }
     }
     if (has_b && ca != cb_ && g.nf_pair) {
-        // A pair that straddles two signal rows (the last frame of row ca, the first of row cb): frame b's non-finite samples
-        // enter as zeros and row cb is flagged -- ols_straddle_fix_kernel makes that frame's output NaN, which it would have
-        // been, while row ca keeps its own (rows are independent signals; inside a row a shared transform only widens the
-        // non-finite stretch by a block).  Wave-uniform, at most one pair per row: the other workgroups never get here.
-        bool bad = false;
+        // A pair that straddles two signal rows (the last frame of row ca, the first of row cb): non-finite samples of either
+        // frame enter as zeros and the frame's row is flagged -- bit 0: its first frame, bit 1: its last -- and
+        // ols_straddle_fix_kernel makes that frame's output NaN, which it would have been, while the other frame keeps its own
+        // (rows are independent signals; inside a row a shared transform only widens the non-finite stretch by a block).  A row
+        // can be flagged for its first frame by one workgroup and for its last by another: atomic OR.  Wave-uniform branch, at
+        // most two pairs per row: the other workgroups never get here.
+        bool bad_a = false, bad_b = false;
 #pragma unroll
         for (int i = 0; i < NBF; ++i)
 #pragma unroll
-            for (int t = 0; t < 16; ++t)
-                if (!(__builtin_fabsf(v[i][t].y) <= 3.4028234663852886e38f)) { v[i][t].y = 0.0f; bad = true; }
-        if (bad) g.nf_pair[cb_] = 1;
+            for (int t = 0; t < 16; ++t) {
+                if (!(__builtin_fabsf(v[i][t].x) <= 3.4028234663852886e38f)) { v[i][t].x = 0.0f; bad_a = true; }
+                if (!(__builtin_fabsf(v[i][t].y) <= 3.4028234663852886e38f)) { v[i][t].y = 0.0f; bad_b = true; }
+            }
+        if (bad_a) atomicOr(&g.nf_pair[ca], 2);
+        if (bad_b) atomicOr(&g.nf_pair[cb_], 1);
     }
     __syncthreads();
     col_stages16<false, NBF>(v, lds, tw256, col, q);
@@ -288,15 +294,21 @@ ols_col_inv16_kernel(const cpx *__restrict__ T, float *__restrict__ y, const cpx
     }
 }
 
-// see the straddling-pair branch of ols_col_fwd16_kernel: frame 0 of a flagged row becomes NaN (grid: C x chunks -- rows on x, the
-// dimension without a 65 535 limit)
+// see the straddling-pair branch of ols_col_fwd16_kernel: the first (bit 0) and / or the last (bit 1) frame of a flagged row
+// becomes NaN, and so does that frame's first statistic partial (grid: C x chunks -- rows on x, the dimension without a 65 535 limit)
 __global__ void __launch_bounds__(256) ols_straddle_fix_kernel(float *__restrict__ y, OlsGeom g)
 {
     const int64_t c = blockIdx.x;
-    if (!g.nf_pair[c]) return;
-    if (blockIdx.y == 0 && threadIdx.x == 0 && g.ep_stat >= 0) g.ep_partial[c * g.ep_row] = __builtin_nan("");
-    const int64_t lo = max((int64_t)0, g.t0 - g.out_shift - row_shift(g, c)), hi = min(g.Tout, g.t0 + g.S - g.out_shift - row_shift(g, c));
-    for (int64_t t = lo + (int64_t)blockIdx.y * 256 + threadIdx.x; t < hi; t += (int64_t)gridDim.y * 256) y[c * g.Tout + t] = __builtin_nanf("");
+    const int flag = g.nf_pair[c];
+    if (!flag) return;
+    const int64_t org = g.t0 - g.out_shift - row_shift(g, c);       // where block output 0 of frame 0 lands in the row
+    for (int e = 0; e < 2; ++e) {
+        if (!(flag & (1 << e))) continue;
+        const int64_t f = e ? g.F - 1 : 0;
+        if (blockIdx.y == 0 && threadIdx.x == 0 && g.ep_stat >= 0) g.ep_partial[c * g.ep_row + f * (g.N2 / OLS_CB)] = __builtin_nan("");
+        const int64_t lo = max((int64_t)0, org + f * g.S), hi = min(g.Tout, org + (f + 1) * g.S);
+        for (int64_t t = lo + (int64_t)blockIdx.y * 256 + threadIdx.x; t < hi; t += (int64_t)gridDim.y * 256) y[c * g.Tout + t] = __builtin_nanf("");
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -551,10 +563,12 @@ ols_sos_nonfinite_fix_kernel(float *__restrict__ y, double *__restrict__ section
     double *row = sections + ((int64_t)(blockIdx.z - 1) * (g.nframes / g.F) + c) * g.Tn;
     const int64_t start = max((int64_t)0, g.t0 + first * g.S - g.pad_left - sh - (int64_t)OLS_CB * warm_blocks);
     for (int64_t t0 = start; t0 < g.Tn; t0 += 4096) {         // first non-finite sample of this section, 4096 samples at a time
+        int found = 0;
         for (int64_t t = t0 + tid; t < min(g.Tn, t0 + 4096); t += 256)
-            if (!(__builtin_fabs(row[t]) <= 1.7976931348623157e308)) { atomicMin(&s_n, (long long)t); break; }
-        __syncthreads();
-        if (s_n != 0x7fffffffffffffffll) break;
+            if (!(__builtin_fabs(row[t]) <= 1.7976931348623157e308)) { atomicMin(&s_n, (long long)t); found = 1; break; }
+        // one decision for the whole workgroup, taken on the threads' own finds: no wavefront reads s_n while another, already in
+        // the next stretch, may write it.  The barrier inside also orders the atomics before the read of the minimum below
+        if (__syncthreads_or(found)) break;
     }
     const int64_t n = s_n;
     if (n == 0x7fffffffffffffffll) return;

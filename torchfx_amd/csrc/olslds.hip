@@ -112,26 +112,38 @@ __device__ __forceinline__ void fetch_pair(cx<R> (&v)[VPT], const R *__restrict_
 
 // Two frames share one complex transform, so a non-finite sample of one comes out in both.  Inside a signal row that only widens
 // the non-finite stretch by a block (the reference's blocks are other sizes anyway, _fftconv.py:119-122) -- but a pair that
-// STRADDLES two rows would carry row c's NaN into the tail of row c - 1, and rows are independent signals.  Such pairs (at most
-// one per row, only when a row has an odd number of frames) check frame b on the way in: non-finite samples enter the transform
-// as zeros, and the workgroup -- it owns the pair from load to store -- writes NaN as frame b's output (poison_partner), which is
-// what it would have been.  Returns whether frame b has to be poisoned (workgroup-uniform).
+// STRADDLES two rows would carry row c's NaN into the tail of row c - 1 and row c - 1's into the head of row c, and rows are
+// independent signals.  Such pairs (at most one per row end, only when a row has an odd number of frames; EVERY pair when a row is
+// one frame) check both frames on the way in: non-finite samples enter the transform as zeros, and the workgroup -- it owns the
+// pair from load to store -- writes NaN as the output of each frame that held one (poison_partner), which is what it would have
+// been (the statistic of an epilogue sees those NaNs), while the other frame keeps its own.  Returns which frames have to be
+// poisoned, bit 0 = frame a, bit 1 = frame b (workgroup-uniform).
 template <typename R, int VPT>
-__device__ __forceinline__ bool sanitize_partner(cx<R> (&v)[VPT], const PairAt<R> &p)
+__device__ __forceinline__ int sanitize_partner(cx<R> (&v)[VPT], const PairAt<R> &p)
 {
-    if (!(p.has_b && p.ca != p.cb)) return false;              // workgroup-uniform: the barrier below is reached by all or none
+    if (!(p.has_b && p.ca != p.cb)) return 0;                  // workgroup-uniform: the barriers below are reached by all or none
     int bad = 0;
 #pragma unroll
     for (int t = 0; t < VPT; ++t)
         if (!(__builtin_fabs((double)v[t].y) <= 1.7976931348623157e308)) { v[t].y = (R)0; bad = 1; }
-    return __syncthreads_or(bad) != 0;
+    const bool nan_b = __syncthreads_or(bad) != 0;
+    bad = 0;
+#pragma unroll
+    for (int t = 0; t < VPT; ++t)
+        if (!(__builtin_fabs((double)v[t].x) <= 1.7976931348623157e308)) { v[t].x = (R)0; bad = 1; }
+    const bool nan_a = __syncthreads_or(bad) != 0;
+    return (nan_a ? 1 : 0) | (nan_b ? 2 : 0);
 }
 template <typename R, int VPT>
-__device__ __forceinline__ void poison_partner(cx<R> (&v)[VPT], bool nan_b)
+__device__ __forceinline__ void poison_partner(cx<R> (&v)[VPT], int nan_ab)
 {
-    if (!nan_b) return;
+    if (!nan_ab) return;
+    const R nan_ = (R)__builtin_nan("");
 #pragma unroll
-    for (int t = 0; t < VPT; ++t) v[t].y = (R)__builtin_nan("");
+    for (int t = 0; t < VPT; ++t) {
+        if (nan_ab & 1) v[t].x = nan_;
+        if (nan_ab & 2) v[t].y = nan_;
+    }
 }
 
 // the valid part of the block, n < S: real part -> frame a's hop, imaginary part -> frame b's
@@ -257,9 +269,9 @@ ols_lds4096_kernel(const R *__restrict__ x, R *__restrict__ y, const cx<R> *__re
     cx<R> v[16];
     const PairAt<R> p(pair, g);
     fetch_pair<R>(v, x, g, p, j);
-    const bool nan_b = sanitize_partner<R, 16>(v, p);
+    const int nan_ab = sanitize_partner<R, 16>(v, p);
     transform_pair<R>(v, lds, twB, twA, Hs, j);
-    poison_partner<R, 16>(v, nan_b);
+    poison_partner<R, 16>(v, nan_ab);
     store_pair<R>(v, y, g, p, j, smem);
 }
 
@@ -370,12 +382,12 @@ ols_lds8192_kernel(const R *__restrict__ x, R *__restrict__ y, const cx<R> *__re
     cx<R> v[32];
     const PairAt<R> p(pair, g);
     fetch_pair<R, LDS8K, 32>(v, x, g, p, j);
-    const bool nan_b = sanitize_partner<R, 32>(v, p);
+    const int nan_ab = sanitize_partner<R, 32>(v, p);
     if constexpr (sizeof(R) == 4)
         transform_pair8k(v, lds, twB, twA, (const v4f *)Hs, __builtin_bit_cast(v2f, wj), j);
     else
         transform_pair8k_plain<R>(v, lds, twB, twA, Hs, wj, j);
-    poison_partner<R, 32>(v, nan_b);
+    poison_partner<R, 32>(v, nan_ab);
     store_pair<R, LDS8K, 32>(v, y, g, p, j, smem);
 }
 
@@ -520,9 +532,9 @@ ols_lds16k_w8_kernel(const float *__restrict__ x, float *__restrict__ y, const v
     cx<float> v[32];
     const PairAt<float> p(pair, g);
     fetch_pair<float, 16384, 32>(v, x, g, p, j);
-    const bool nan_b = sanitize_partner<float, 32>(v, p);
+    const int nan_ab = sanitize_partner<float, 32>(v, p);
     transform_pair16k_w8(v, (v2f *)lbuf, twB, twA, Hq, w16kg, j);
-    poison_partner<float, 32>(v, nan_b);
+    poison_partner<float, 32>(v, nan_ab);
     store_pair<float, 16384, 32>(v, y, g, p, j, smem);
 }
 
@@ -577,9 +589,9 @@ ols_lds16k_kernel(const float *__restrict__ x, float *__restrict__ y, const v4f 
         cx<float> v[16];
         const PairAt<float> p(pair, g);
         fetch_pair<float, LDS16K>(v, x, g, p, j);
-        const bool nan_b = sanitize_partner<float, 16>(v, p);
+        const int nan_ab = sanitize_partner<float, 16>(v, p);
         transform_pair16k(v, L, tb, Hq, j);
-        poison_partner<float, 16>(v, nan_b);
+        poison_partner<float, 16>(v, nan_ab);
         store_pair<float, LDS16K>(v, y, g, p, j, smem);
         __syncthreads();                         // the statistic's scratch is the transform buffer
     }

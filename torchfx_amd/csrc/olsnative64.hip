@@ -41,7 +41,8 @@ constexpr int64_t NPTS = (int64_t)N1 * N2;
 struct Geom {
     int64_t Tn, Tout, F, S, pad_left, nframes;
     int sh_on, sh_base;                              // rows that are not whole 128-byte lines: see row_shift (olsnative.hip)
-    int *nf_pair;                                    // [C] zeroed per call, or null: see the straddling-pair branch of ols_col_fwd16_kernel (ols_kernels.h)
+    int *nf_pair;                                    // [C] zeroed per call, or null: bit 0 / 1 = the row's first / last frame held a non-finite sample
+                                                     // in a pair that straddles rows: see that branch of ols_col_fwd16_kernel (ols_kernels.h)
 };
 __device__ __forceinline__ int row_shift(const Geom &g, int64_t c) { return g.sh_on ? (int)(((int64_t)g.sh_base + c * g.Tn) & 15) : 0; }
 
@@ -98,12 +99,15 @@ ols64_col_fwd_kernel(const double *__restrict__ x, cpd *__restrict__ T, const cp
             v[t] = mk<double>((ia >= 0 && ia < g.Tn) ? xa[ia] : 0.0, (has_b && ib >= 0 && ib < g.Tn) ? xb[ib] : 0.0);
         }
     }
-    if (has_b && ca != cb_ && g.nf_pair) {           // a pair that straddles two signal rows: row cb's non-finite samples must not reach row ca
-        bool bad = false;
+    if (has_b && ca != cb_ && g.nf_pair) {           // a pair that straddles two signal rows: neither row's non-finite samples may reach the other
+        bool bad_a = false, bad_b = false;
 #pragma unroll
-        for (int t = 0; t < 16; ++t)
-            if (!(__builtin_fabs(v[t].y) <= 1.7976931348623157e308)) { v[t].y = 0.0; bad = true; }
-        if (bad) g.nf_pair[cb_] = 1;
+        for (int t = 0; t < 16; ++t) {
+            if (!(__builtin_fabs(v[t].x) <= 1.7976931348623157e308)) { v[t].x = 0.0; bad_a = true; }
+            if (!(__builtin_fabs(v[t].y) <= 1.7976931348623157e308)) { v[t].y = 0.0; bad_b = true; }
+        }
+        if (bad_a) atomicOr(&g.nf_pair[ca], 2);      // row ca's last frame; another workgroup may flag the same row for its first
+        if (bad_b) atomicOr(&g.nf_pair[cb_], 1);     // row cb's first frame
     }
     __syncthreads();
     col_fft256<false>(v, lds, tw256, col, j);
@@ -149,9 +153,14 @@ ols64_col_inv_kernel(const cpd *__restrict__ T, double *__restrict__ y, const cp
 __global__ void __launch_bounds__(256) ols64_straddle_fix_kernel(double *__restrict__ y, Geom g)
 {
     const int64_t c = blockIdx.x;                                    // rows on x: no 65 535 limit
-    if (!g.nf_pair[c]) return;
-    const int64_t hi = min(g.Tout, g.S - row_shift(g, c));          // frame 0 of row c
-    for (int64_t t = (int64_t)blockIdx.y * 256 + threadIdx.x; t < hi; t += (int64_t)gridDim.y * 256) y[c * g.Tout + t] = __builtin_nan("");
+    const int flag = g.nf_pair[c];                                   // bit 0: the row's first frame becomes NaN, bit 1: its last
+    if (!flag) return;
+    for (int e = 0; e < 2; ++e) {
+        if (!(flag & (1 << e))) continue;
+        const int64_t f = e ? g.F - 1 : 0;
+        const int64_t lo = max((int64_t)0, f * g.S - row_shift(g, c)), hi = min(g.Tout, (f + 1) * g.S - row_shift(g, c));
+        for (int64_t t = lo + (int64_t)blockIdx.y * 256 + threadIdx.x; t < hi; t += (int64_t)gridDim.y * 256) y[c * g.Tout + t] = __builtin_nan("");
+    }
 }
 
 // Row pass: one workgroup per row k1 of a frame pair; thread j holds T[k1][j + 256 t].
