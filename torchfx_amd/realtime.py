@@ -29,7 +29,8 @@ stream: causal, no latency, it carries every delay line in time order (``tfx_fre
 :class:`StatefulWaveshaper` and :class:`StatefulDistortion` are the oversampled waveshaper of a stream: they carry the last
 ``reach_before + reach_after`` inputs of every row, hold the last ``D = reach_before`` outputs back
 (``tfx_waveshaper_stream_forward``, one launch per chunk), and their chunks plus ``flush()`` are bit-identical to ``waveshape`` on
-the whole signal; ``aligned=False`` gives the constant-latency form.
+the whole signal; ``aligned=False`` gives the constant-latency form.  The limiter and the waveshapers share their state machine,
+:class:`_HoldBackStream`; the effects that cannot run chunk by chunk at all are one table, ``_REFUSALS``.
 
 Small chunks are launch-bound (a 2 x 4096 step is ~60 us of host + launch overhead for a few us of
 GPU work), so ``StreamProcessor(..., use_graph=True)`` captures one full-size chunk step -- every
@@ -44,15 +45,17 @@ import enum
 import math
 import os
 import threading
+import typing as tp
 from collections.abc import Generator, Sequence
 
 import torch
 from torch import Tensor, nn
 
-from torchfx_amd.effect import (FX, Chorus, Compressor, Delay, Distortion, Flanger, Freeverb, Limiter, ModulatedDelay, MonoDelayStrategy, PingPongDelayStrategy,
-                                Reverb, Vibrato, Waveshaper, _ext)
+from torchfx_amd.effect import (FX, Chorus, Compressor, Delay, Distortion, Flanger, Freeverb, Limiter, LoudnessNormalize, ModulatedDelay,
+                                MonoDelayStrategy, PingPongDelayStrategy, Reverb, Vibrato, Waveshaper, _ext)
 from torchfx_amd.filter._base import AbstractFilter
 from torchfx_amd.filter.fir import FIR
+from torchfx_amd.filter.zerophase import ZeroPhase
 from torchfx_amd.resample import Resample, design_taps, window_key
 
 
@@ -250,6 +253,11 @@ class StatefulResample(_RingOut, Resample):
     changes between chunks -- the outputs still held back are then dropped.  A ``Wave`` is a whole signal: pipe it through
     ``Resample`` or use ``Wave.resample`` instead."""
 
+    holds_back = True                               # chunks may return fewer samples than they take; flush() hands out the rest
+    _hold_rank = 0                                  # see _held_back
+    _wave_refusal = ("StatefulResample is for chunked streams (StreamProcessor): a Wave is a whole signal, and a stream's forward "
+                     "holds back its last outputs; pipe it through Resample or call Wave.resample instead")
+
     def __init__(self, new_fs: int, fs: int | None = None, window=("kaiser", 5.0)) -> None:
         super().__init__(new_fs, fs, window)
         self.reset_state()
@@ -296,6 +304,10 @@ class StatefulResample(_RingOut, Resample):
 
     def _emit_count(self, n: int, up: int, down: int, pre: int) -> int:
         return max(0, -(-n * up // down) - pre)
+
+    def _graph_ready(self, x: Tensor) -> bool:
+        """Never: a replay skips :meth:`forward`, which counts the samples of every chunk."""
+        return False
 
     @torch.no_grad()
     def forward(self, x: Tensor) -> Tensor:
@@ -374,7 +386,130 @@ class StatefulResample(_RingOut, Resample):
         return tail
 
 
-class StatefulLimiter(_RingOut, Limiter):
+class _HoldBackStream(_RingOut):
+    """The state machine of a stream whose outputs read ``D`` input samples ahead (:class:`StatefulLimiter`,
+    :class:`_ShaperStream`); mixed in in front of the effect class.  After ``N`` input samples per row the stream has returned the
+    first ``max(0, N - D)`` samples of the one-shot result, and :meth:`flush` returns the remaining ``min(N, D)``.  Every row
+    carries its last ``Hs`` input samples in ``_hist`` (``[rows, Hs]``) and the stream one host integer, ``_pos = min(N, Hs + D)``;
+    ``aligned`` chooses between the outputs a chunk completes and the chunk's shape, delayed by ``D``.  A subclass says what its
+    stream is made of in three hooks:
+
+    * ``_stream(lead, dtype, device) -> (ctx, key, (D, Hs))`` for chunks of leading shape ``lead``: ``ctx`` is what the other two
+      hooks need, a stream lives while ``key`` stays, and ``(D, Hs)`` comes from :meth:`_geometry`;
+    * ``_launch(x, ctx, n_in=None) -> y``: one native launch on the chunk ``x`` behind ``_hist`` at position ``_pos``; it stores
+      the new history unless ``n_in`` (the number of real inputs in ``x``) is given;
+    * ``_one_shot_host(v, ctx) -> [rows, n]``: the effect's host definition on the whole signal ``v [rows, n]``."""
+
+    holds_back = True                               # chunks may return fewer samples than they take; flush() hands out the rest
+    _aligned_refusal = ("{name}(aligned=True) cannot run in RealtimeProcessor: it returns the outputs a block completes, fewer for "
+                        "the first block, and a sound card's output block has the input block's length; construct it with "
+                        "aligned=False (constant latency: the result delayed by its `latency` samples)")
+
+    def __init__(self, *args, aligned: bool = True, **kwargs) -> None:
+        super().__init__(*args, **kwargs)
+        self.aligned = bool(aligned)
+        self._geos: dict = {}
+        self.reset_state()
+
+    def reset_state(self) -> None:
+        self._hist: Tensor | None = None
+        self._pos = 0                               # min(N, Hs + D): input samples per row so far, as far as it matters
+        self._key: tuple | None = None              # what the running stream is bound to (see _stream)
+        self._geo: tuple[int, int] = (0, 0)         # its (D, Hs)
+        self._last: tuple | None = None
+
+    def _geometry(self, query: str, *key) -> tuple[int, int]:
+        """``(D, Hs)`` of the stream: the latency and history that the effect's stream plan query (``torchfx_ext.<query>``,
+        host-only) gives for ``key``, the sizes they depend on; asked once per key."""
+        geo = self._geos.get(key)
+        if geo is None:
+            info = getattr(_ext(), query)(0, *key)
+            geo = self._geos[key] = (info["latency"], info["history"])
+        return geo
+
+    @property
+    def latency(self) -> int:
+        """The samples the stream holds back (``D``): what :meth:`flush` returns at most, and the delay of ``aligned=False``."""
+        return self._stream((), torch.float32, None)[2][0]
+
+    @property
+    def history_length(self) -> int:
+        """The input samples every row carries between chunks (``Hs``; the class says what it is made of)."""
+        return self._stream((), torch.float32, None)[2][1]
+
+    def _sync_history(self) -> None:
+        """Nothing to resize: a parameter that changes the history's length restarts the stream (``_graph_ready``)."""
+
+    def _graph_ready(self, x: Tensor) -> bool:
+        """A replay skips :meth:`forward`: it leaves nothing stale once the position counter has saturated, for the stream
+        that is running."""
+        if self._key is None or self._pos != sum(self._geo):
+            return False
+        return self._stream(tuple(x.shape[:-1]), x.dtype, x.device)[1] == self._key
+
+    @torch.no_grad()
+    def forward(self, x: Tensor) -> Tensor:
+        _rows(x)
+        ctx, key, geo = self._stream(tuple(x.shape[:-1]), x.dtype, x.device)
+        if key != self._key:                        # a new stream: from silence
+            self.reset_state()
+            self._key, self._geo = key, geo
+        self._note(x)
+        (D, Hs), N, T = geo, self._pos, x.shape[-1]
+        if T == 0:
+            return torch.zeros_like(x)
+        y = self._launch(x, ctx) if _native_stream(x) else self._host_chunk(x, ctx)
+        self._pos = min(N + T, Hs + D)
+        k = min(T, max(0, D - N)) if self.aligned else 0         # outputs in front of position 0
+        return y[..., k:] if k else y
+
+    def _window(self, rows: int, dtype: torch.dtype) -> tuple[Tensor, Tensor]:
+        """``(history [rows, Hs], its valid part)``: the part starts at position 0 while the stream is younger than ``Hs``."""
+        Hs = self._geo[1]
+        hist = self._hist.cpu() if self._hist is not None else torch.zeros(rows, Hs, dtype=dtype)
+        return hist, hist[:, Hs - min(self._pos, Hs):]
+
+    def _host_chunk(self, x: Tensor, ctx) -> Tensor:
+        """One chunk on the host: the one-shot definition on ``[history | chunk]`` -- its start is position 0 or a sample no
+        output of the chunk reads behind, its end a sample none reads past, so no output that is cut out of it reads a truncated
+        edge -- and the chunk's outputs cut from it."""
+        (D, Hs), N, T = self._geo, self._pos, x.shape[-1]
+        rows = math.prod(x.shape[:-1])
+        hist, valid = self._window(rows, x.dtype)
+        xr = x.detach().reshape(rows, T).cpu()
+        v = torch.cat([valid, xr], dim=-1)                   # positions [N - valid, N + T)
+        self._hist = torch.cat([hist, xr], dim=-1)[:, T:].to(x.device)
+        out = torch.zeros(rows, T, dtype=x.dtype)
+        lo = max(0, N - D)
+        n = N + T - D - lo
+        if n > 0:
+            s = lo - (N - valid.shape[-1])
+            out[:, T - n:] = self._one_shot_host(v, ctx)[:, s:s + n]
+        return out.reshape(x.shape).to(x.device)
+
+    @torch.no_grad()
+    def flush(self) -> Tensor:
+        """The outputs still held back (the last ``min(N, latency)`` samples of the one-shot result), computed with the stream
+        ending here and shaped like the last chunk; then the state is reset.  Without a chunk since the last reset, or after a
+        parameter change that restarts the stream: an empty tensor."""
+        if self._last is None:
+            return torch.zeros(0)
+        lead, dtype, device = self._last
+        ctx, key, _ = self._stream(lead, dtype, device)
+        D, N = self._geo[0], self._pos
+        n = min(N, D) if key == self._key else 0
+        if n == 0:
+            tail = self._zeros(0)
+        elif device.type == "cuda":                   # a chunk of D samples with no input in it: the stream ends at N
+            tail = self._launch(self._zeros(D), ctx, 0)[..., D - n:].contiguous()
+        else:
+            v = self._window(math.prod(lead), dtype)[1]
+            tail = self._one_shot_host(v, ctx)[:, v.shape[-1] - n:].reshape(*lead, n).to(device)
+        self.reset_state()
+        return tail
+
+
+class StatefulLimiter(_HoldBackStream, Limiter):
     """:class:`~torchfx_amd.effect.Limiter` over a continuous stream: chunks go in, the limited signal comes out with no seam.
     The gain at a sample reads ``latency`` = ``D = A - 1 + i_lo`` samples ahead (``A`` the look-ahead in samples, ``i_lo`` the
     detector interpolator's forward reach: 0 for ``detector="sample"``, 10 for the library's filters), so after ``N`` input
@@ -397,21 +532,18 @@ class StatefulLimiter(_RingOut, Limiter):
     the outputs of the chunks whose ``[history | chunk]`` still holds it NaN (all channels of the group); after that the stream
     is the clean stream's again, bit for bit.  A ``Wave`` is a whole signal: pipe it through ``Limiter`` instead."""
 
+    _hold_rank = 1                                  # see _held_back
+    _wave_refusal = ("StatefulLimiter is for chunked streams (StreamProcessor, RealtimeProcessor): a Wave is a whole signal, and a "
+                     "stream's forward holds back its last outputs; pipe it through Limiter instead")
+    _aligned_refusal = ("{name}(aligned=True) cannot run in RealtimeProcessor: it returns the outputs a block completes, none for "
+                        "the first blocks, and a sound card's output block has the input block's length; construct it with "
+                        "aligned=False (constant latency: the result delayed by {name}.latency samples)")
+
     def __init__(self, ceiling_db: float = -1.0, lookahead: float = 1.5e-3, hold: float = 10e-3, detector: str = "true_peak",
                  link: bool = True, oversample: int | None = None, taps=None, window=None, fs: int | None = None,
                  aligned: bool = True) -> None:
-        super().__init__(ceiling_db, lookahead, hold, detector, link, oversample, taps, window, fs)
-        self.aligned = bool(aligned)
+        super().__init__(ceiling_db, lookahead, hold, detector, link, oversample, taps, window, fs, aligned=aligned)
         self._pcache: tuple | None = None
-        self._geos: dict = {}
-        self.reset_state()
-
-    def reset_state(self) -> None:
-        self._hist: Tensor | None = None
-        self._pos = 0                               # min(N, Hs + D): input samples per row so far, as far as it matters
-        self._key: tuple | None = None              # what the running stream is bound to (see _stream)
-        self._geo: tuple[int, int] = (0, 0)         # its (D, Hs)
-        self._last: tuple | None = None
 
     def _params(self, dtype: torch.dtype):
         """``self.params(dtype)``, kept while the attributes it is made from stay what they were."""
@@ -421,32 +553,29 @@ class StatefulLimiter(_RingOut, Limiter):
             self._pcache = (key, self.params(dtype), (self.taps, self.window))
         return self._pcache[1]
 
-    def _geometry(self, P) -> tuple[int, int]:
-        """``(D, Hs)`` of the stream: ``tfx_limiter_stream_plan_info``'s latency and history (host-only)."""
-        key = (P.A, P.H, P.up, 0 if P.taps is None else int(P.taps.numel()))
-        geo = self._geos.get(key)
-        if geo is None:
-            info = _ext().limiter_stream_plan_info(0, *key)
-            geo = self._geos[key] = (info["latency"], info["history"])
-        return geo
-
-    @property
-    def latency(self) -> int:
-        """The samples the stream holds back (``D``): what :meth:`flush` returns at most, and the delay of ``aligned=False``."""
-        return self._geometry(self._params(torch.float32))[0]
-
-    @property
-    def history_length(self) -> int:
-        """The input samples every row carries between chunks (``Hs = D + A + H - 2`` plus the interpolator's backward reach)."""
-        return self._geometry(self._params(torch.float32))[1]
-
     def _stream(self, lead: tuple, dtype: torch.dtype, device) -> tuple:
-        """``(P, groups, channels, key, (D, Hs))`` for chunks of leading shape ``lead``: a stream lives while ``key`` stays."""
+        """``((P, groups, channels), key, (D, Hs))`` for chunks of leading shape ``lead``: a stream lives while ``key`` stays.
+        ``Hs = D + A + H - 2`` plus the interpolator's backward reach (``tfx_limiter_stream_plan_info``)."""
         P = self._params(dtype)
         channels = int(lead[-1]) if (self.link and lead) else 1        # limiter._grouping, from the leading shape
         groups = math.prod(lead) // channels if channels else 0
+        ntaps = 0 if P.taps is None else int(P.taps.numel())
         key = (groups, channels, dtype, device, P.A, P.H, P.up, None if P.taps is None else P.taps.numpy().tobytes())
-        return P, groups, channels, key, self._geometry(P)
+        return (P, groups, channels), key, self._geometry("limiter_stream_plan_info", P.A, P.H, P.up, ntaps)
+
+    def _launch(self, x: Tensor, ctx, n_in: int | None = None) -> Tensor:
+        P, _, channels = ctx
+        with torch.cuda.device(x.device):
+            y, _, hist = _ext().limiter_stream_forward(x, self._hist, self._pos, P.c, P.A, P.H, torch.from_numpy(P.w), P.up, P.taps,
+                                                       channels, False, n_in)
+        if n_in is None:
+            self._hist = hist
+        return y
+
+    def _one_shot_host(self, v: Tensor, ctx) -> Tensor:
+        from torchfx_amd.limiter import _limit_host
+
+        return _limit_host(v, *ctx)[0]
 
     def route(self, x: Tensor, length: int | None = None) -> str:
         """``native (limiter_stream_kernel, ...)`` for the next chunk of ``x``, or the host / refusal route."""
@@ -466,88 +595,6 @@ class StatefulLimiter(_RingOut, Limiter):
         """What a captured HIP graph of this effect bakes in (the ceiling and the window among it)."""
         dtype = self._last[1] if self._last is not None else torch.float32
         return self._params(dtype).key(), self.link, self.aligned
-
-    def _sync_history(self) -> None:
-        """Nothing to resize: a parameter that changes the history's length restarts the stream (``_graph_ready``)."""
-
-    def _graph_ready(self, x: Tensor) -> bool:
-        """A replay skips :meth:`forward`: it leaves nothing stale once the position counter has saturated, for the stream
-        that is running."""
-        if self._key is None or self._pos != sum(self._geo):
-            return False
-        return self._stream(tuple(x.shape[:-1]), x.dtype, x.device)[3] == self._key
-
-    @torch.no_grad()
-    def forward(self, x: Tensor) -> Tensor:
-        _rows(x)
-        P, groups, channels, key, geo = self._stream(tuple(x.shape[:-1]), x.dtype, x.device)
-        if key != self._key:                        # a new stream: from silence
-            self.reset_state()
-            self._key, self._geo = key, geo
-        self._note(x)
-        (D, Hs), N, T = geo, self._pos, x.shape[-1]
-        if T == 0:
-            return torch.zeros_like(x)
-        if _native_stream(x):
-            with torch.cuda.device(x.device):
-                y, _, self._hist = _ext().limiter_stream_forward(x, self._hist, N, P.c, P.A, P.H, torch.from_numpy(P.w), P.up,
-                                                                 P.taps, channels, False)
-        else:
-            y = self._host_chunk(x, P, groups, channels)
-        self._pos = min(N + T, Hs + D)
-        k = min(T, max(0, D - N)) if self.aligned else 0         # outputs in front of position 0
-        return y[..., k:] if k else y
-
-    def _window(self, rows: int, dtype: torch.dtype) -> tuple[Tensor, Tensor]:
-        """``(history [rows, Hs], its valid part)``: the part starts at position 0 while the stream is younger than ``Hs``."""
-        Hs = self._geo[1]
-        hist = self._hist.cpu() if self._hist is not None else torch.zeros(rows, Hs, dtype=dtype)
-        return hist, hist[:, Hs - min(self._pos, Hs):]
-
-    def _host_chunk(self, x: Tensor, P, groups: int, channels: int) -> Tensor:
-        """One chunk on the host: the one-shot definition on ``[history | chunk]`` -- its start is position 0 or a sample no
-        output of the chunk reads behind, its end a sample none reads past -- and the chunk's outputs cut from it."""
-        from torchfx_amd.limiter import _limit_host
-
-        (D, Hs), N, T = self._geo, self._pos, x.shape[-1]
-        rows = groups * channels
-        hist, valid = self._window(rows, x.dtype)
-        xr = x.detach().reshape(rows, T).cpu()
-        v = torch.cat([valid, xr], dim=-1)                   # positions [N - valid, N + T)
-        self._hist = torch.cat([hist, xr], dim=-1)[:, T:].to(x.device)
-        out = torch.zeros(rows, T, dtype=x.dtype)
-        lo = max(0, N - D)
-        n = N + T - D - lo
-        if n > 0:
-            s = lo - (N - valid.shape[-1])
-            out[:, T - n:] = _limit_host(v, P, groups, channels)[0][:, s:s + n]
-        return out.reshape(x.shape).to(x.device)
-
-    @torch.no_grad()
-    def flush(self) -> Tensor:
-        """The outputs still held back (the last ``min(N, latency)`` samples of the one-shot result), computed with the stream
-        ending here and shaped like the last chunk; then the state is reset.  Without a chunk since the last reset, or after a
-        parameter change that restarts the stream: an empty tensor."""
-        if self._last is None:
-            return torch.zeros(0)
-        lead, dtype, device = self._last
-        P, groups, channels, key, _ = self._stream(lead, dtype, device)
-        D, N = self._geo[0], self._pos
-        n = min(N, D) if key == self._key else 0
-        if n == 0:
-            tail = self._zeros(0)
-        elif device.type == "cuda":
-            with torch.cuda.device(device):           # a chunk of D samples with no input in it: the stream ends at N
-                y = _ext().limiter_stream_forward(self._zeros(D), self._hist, N, P.c, P.A, P.H, torch.from_numpy(P.w), P.up,
-                                                  P.taps, channels, False, 0)[0]
-            tail = y[..., D - n:].contiguous()
-        else:
-            from torchfx_amd.limiter import _limit_host
-
-            v = self._window(groups * channels, dtype)[1]
-            tail = _limit_host(v, P, groups, channels)[0][:, v.shape[-1] - n:].reshape(*lead, n).to(device)
-        self.reset_state()
-        return tail
 
 
 class StatefulCompressor(Compressor):
@@ -593,14 +640,6 @@ class StatefulCompressor(Compressor):
         y, self._hist = compress(x, self.fs, self.threshold_db, self.ratio, self.attack, self.release, self.knee_db, self.makeup_db,
                                  self.link, state=self._hist, return_state=True)
         return y
-
-
-def _refuse_compressor(e, who: str) -> None:
-    members = list(e.modules() if isinstance(e, nn.Module) else [e])
-    if any(isinstance(m, Compressor) and not isinstance(m, StatefulCompressor) for m in members):
-        raise TypeError(f"Compressor cannot run in {who}: every call starts its level detector from silence, so a chunked stream "
-                        "would drop the envelope at every chunk start; use StatefulCompressor(...) in its place, or compress the "
-                        "whole signal (wave | Compressor(...)) before or after streaming")
 
 
 class StatefulFreeverb(_RingOut, Freeverb):
@@ -665,15 +704,7 @@ class StatefulFreeverb(_RingOut, Freeverb):
         return out
 
 
-def _refuse_freeverb(e, who: str) -> None:
-    members = list(e.modules() if isinstance(e, nn.Module) else [e])
-    if any(isinstance(m, Freeverb) and not isinstance(m, StatefulFreeverb) for m in members):
-        raise TypeError(f"Freeverb cannot run in {who}: every call starts from silent delay lines, so a chunked stream would cut "
-                        "the room's tail at every chunk start; use StatefulFreeverb(...) in its place, or run the whole signal "
-                        "(wave | Freeverb(...)) before or after streaming")
-
-
-class _ShaperStream(_RingOut):
+class _ShaperStream(_HoldBackStream):
     """An oversampled waveshaper (:class:`~torchfx_amd.effect.Waveshaper`) over a continuous stream; mixed in in front of the
     effect class.  An output reads ``latency`` = ``D = reach_before`` samples ahead and ``reach_after`` behind
     (:func:`torchfx_ext.waveshaper_plan_info`: 21 and 20 for the default window at every ``oversample > 1``), so after ``N``
@@ -696,48 +727,37 @@ class _ShaperStream(_RingOut):
     from silence -- and what is held back is dropped -- when ``oversample`` or the taps of ``window`` change and when the row count,
     dtype or device changes.  A ``Wave`` is a whole signal: pipe it through ``Waveshaper`` / ``Distortion`` instead."""
 
-    def __init__(self, *args, aligned: bool = True, **kwargs) -> None:
-        super().__init__(*args, **kwargs)
-        self.aligned = bool(aligned)
-        self._geos: dict = {}
-        self.reset_state()
-
-    def reset_state(self) -> None:
-        self._hist: Tensor | None = None
-        self._pos = 0                               # min(N, Hs + D): input samples per row so far, as far as it matters
-        self._key: tuple | None = None              # what the running stream is bound to (see _stream)
-        self._geo: tuple[int, int] = (0, 0)         # its (D, Hs)
-        self._last: tuple | None = None
-
-    def _geometry(self, L: int, up: Tensor | None, dn: Tensor | None) -> tuple[int, int]:
-        """``(D, Hs)`` of the stream: ``tfx_waveshaper_stream_plan_info``'s latency and history (host-only)."""
-        key = (L, 0 if up is None else int(up.numel()), 0 if dn is None else int(dn.numel()))
-        geo = self._geos.get(key)
-        if geo is None:
-            info = _ext().waveshaper_stream_plan_info(0, *key)
-            geo = self._geos[key] = (info["latency"], info["history"])
-        return geo
-
-    @property
-    def latency(self) -> int:
-        """The samples the stream holds back (``D``): what :meth:`flush` returns at most, and the delay of ``aligned=False``."""
-        P = self.params()
-        return self._geometry(P.oversample, *P.taps(torch.float32))[0]
-
-    @property
-    def history_length(self) -> int:
-        """The input samples every row carries between chunks (``Hs = reach_before + reach_after``)."""
-        P = self.params()
-        return self._geometry(P.oversample, *P.taps(torch.float32))[1]
+    _hold_rank = 2                                  # see _held_back
+    _wave_refusal = ("StatefulWaveshaper / StatefulDistortion are for chunked streams (StreamProcessor, RealtimeProcessor): a Wave is "
+                     "a whole signal, and a stream's forward holds back its last outputs; pipe it through Waveshaper or Distortion "
+                     "instead")
 
     def _stream(self, lead: tuple, dtype: torch.dtype, device) -> tuple:
-        """``(P, taps up, taps down, key, (D, Hs))`` for chunks of leading shape ``lead``: a stream lives while ``key`` stays."""
+        """``((P, taps up, taps down), key, (D, Hs))`` for chunks of leading shape ``lead``: a stream lives while ``key`` stays.
+        ``Hs = reach_before + reach_after`` (``tfx_waveshaper_stream_plan_info``)."""
         if dtype not in (torch.float32, torch.float64):
             raise TypeError(f"{type(self).__name__}: float32 or float64 signals only, got {dtype}")
         P = self.params()
         up, dn = P.taps(dtype)
         taps = None if up is None else (up.numpy().tobytes(), dn.numpy().tobytes())
-        return P, up, dn, (math.prod(lead), dtype, device, P.oversample, taps), self._geometry(P.oversample, up, dn)
+        geo = self._geometry("waveshaper_stream_plan_info", P.oversample, 0 if up is None else int(up.numel()),
+                             0 if dn is None else int(dn.numel()))
+        return (P, up, dn), (math.prod(lead), dtype, device, P.oversample, taps), geo
+
+    def _launch(self, x: Tensor, ctx, n_in: int | None = None) -> Tensor:
+        P, up, dn = ctx
+        curve = None if P.curve is None else torch.from_numpy(P.curve).to(x.dtype)
+        with torch.cuda.device(x.device):
+            y, hist = _ext().waveshaper_stream_forward(x, self._hist, self._pos, P.oversample, P.shape, curve, P.drive, P.bias, P.dry,
+                                                       P.wet, up, dn, n_in)
+        if n_in is None:
+            self._hist = hist
+        return y
+
+    def _one_shot_host(self, v: Tensor, ctx) -> Tensor:
+        from torchfx_amd.waveshaper import _waveshape_host
+
+        return _waveshape_host(v, ctx[0])
 
     def route(self, x: Tensor, length: int | None = None) -> str:
         """``native (waveshaper_stream_kernel, ...)`` for the next chunk of ``x``, or the host / refusal route."""
@@ -760,90 +780,6 @@ class _ShaperStream(_RingOut):
         return (P.shape, None if P.curve is None else P.curve.tobytes(), P.drive, P.bias, P.oversample, P.dry, P.wet,
                 window_key(P.window), self.aligned)
 
-    def _sync_history(self) -> None:
-        """Nothing to resize: a parameter that changes the history's length restarts the stream (``_graph_ready``)."""
-
-    def _graph_ready(self, x: Tensor) -> bool:
-        """A replay skips :meth:`forward`: it leaves nothing stale once the position counter has saturated, for the stream
-        that is running."""
-        if self._key is None or self._pos != sum(self._geo):
-            return False
-        return self._stream(tuple(x.shape[:-1]), x.dtype, x.device)[3] == self._key
-
-    def _launch(self, x: Tensor, P, up, dn, n_in: int | None = None) -> Tensor:
-        curve = None if P.curve is None else torch.from_numpy(P.curve).to(x.dtype)
-        with torch.cuda.device(x.device):
-            y, hist = _ext().waveshaper_stream_forward(x, self._hist, self._pos, P.oversample, P.shape, curve, P.drive, P.bias, P.dry,
-                                                       P.wet, up, dn, n_in)
-        if n_in is None:
-            self._hist = hist
-        return y
-
-    @torch.no_grad()
-    def forward(self, x: Tensor) -> Tensor:
-        _rows(x)
-        P, up, dn, key, geo = self._stream(tuple(x.shape[:-1]), x.dtype, x.device)
-        if key != self._key:                        # a new stream: from silence
-            self.reset_state()
-            self._key, self._geo = key, geo
-        self._note(x)
-        (D, Hs), N, T = geo, self._pos, x.shape[-1]
-        if T == 0:
-            return torch.zeros_like(x)
-        y = self._launch(x, P, up, dn) if _native_stream(x) else self._host_chunk(x, P)
-        self._pos = min(N + T, Hs + D)
-        k = min(T, max(0, D - N)) if self.aligned else 0         # outputs in front of position 0
-        return y[..., k:] if k else y
-
-    def _window(self, rows: int, dtype: torch.dtype) -> tuple[Tensor, Tensor]:
-        """``(history [rows, Hs], its valid part)``: the part starts at position 0 while the stream is younger than ``Hs``."""
-        Hs = self._geo[1]
-        hist = self._hist.cpu() if self._hist is not None else torch.zeros(rows, Hs, dtype=dtype)
-        return hist, hist[:, Hs - min(self._pos, Hs):]
-
-    def _host_chunk(self, x: Tensor, P) -> Tensor:
-        """One chunk on the host: the one-shot definition on ``[history | chunk]`` -- its start is position 0 or the sample
-        ``reach_after`` behind the chunk's first output, its end the sample ``reach_before`` past its last one, so no output that
-        is cut out of it reads a truncated edge -- and the chunk's outputs cut from it."""
-        from torchfx_amd.waveshaper import _waveshape_host
-
-        (D, Hs), N, T = self._geo, self._pos, x.shape[-1]
-        rows = math.prod(x.shape[:-1])
-        hist, valid = self._window(rows, x.dtype)
-        xr = x.detach().reshape(rows, T).cpu()
-        v = torch.cat([valid, xr], dim=-1)                   # positions [N - valid, N + T)
-        self._hist = torch.cat([hist, xr], dim=-1)[:, T:].to(x.device)
-        out = torch.zeros(rows, T, dtype=x.dtype)
-        lo = max(0, N - D)
-        n = N + T - D - lo
-        if n > 0:
-            s = lo - (N - valid.shape[-1])
-            out[:, T - n:] = _waveshape_host(v, P)[:, s:s + n]
-        return out.reshape(x.shape).to(x.device)
-
-    @torch.no_grad()
-    def flush(self) -> Tensor:
-        """The outputs still held back (the last ``min(N, latency)`` samples of the one-shot result), computed with the stream
-        ending here and shaped like the last chunk; then the state is reset.  Without a chunk since the last reset, or after a
-        parameter change that restarts the stream: an empty tensor."""
-        if self._last is None:
-            return torch.zeros(0)
-        lead, dtype, device = self._last
-        P, up, dn, key, _ = self._stream(lead, dtype, device)
-        D, N = self._geo[0], self._pos
-        n = min(N, D) if key == self._key else 0
-        if n == 0:
-            tail = self._zeros(0)
-        elif device.type == "cuda":                   # a chunk of D samples with no input in it: the stream ends at N
-            tail = self._launch(self._zeros(D), P, up, dn, 0)[..., D - n:].contiguous()
-        else:
-            from torchfx_amd.waveshaper import _waveshape_host
-
-            v = self._window(math.prod(lead), dtype)[1]
-            tail = _waveshape_host(v, P)[:, v.shape[-1] - n:].reshape(*lead, n).to(device)
-        self.reset_state()
-        return tail
-
 
 class StatefulWaveshaper(_ShaperStream, Waveshaper):
     """:class:`~torchfx_amd.effect.Waveshaper` over a continuous stream, with its constructor arguments plus ``aligned``
@@ -853,20 +789,6 @@ class StatefulWaveshaper(_ShaperStream, Waveshaper):
 class StatefulDistortion(_ShaperStream, Distortion):
     """:class:`~torchfx_amd.effect.Distortion` over a continuous stream, with its constructor arguments plus ``aligned``
     (see :class:`_ShaperStream`)."""
-
-
-def _refuse_waveshaper(e, who: str) -> None:
-    members = list(e.modules() if isinstance(e, nn.Module) else [e])
-    for m in members:
-        if isinstance(m, Waveshaper) and not isinstance(m, _ShaperStream) and m.oversample != 1:
-            raise TypeError(f"{type(m).__name__} with oversample={m.oversample} cannot run in {who}: every call zero-pads the edges "
-                            "of its resampling filters, so a chunked stream would click at every chunk seam; use "
-                            f"Stateful{type(m).__name__ if type(m) in (Waveshaper, Distortion) else 'Waveshaper'}(...) in its place, "
-                            f"oversample=1 (memoryless), or run the whole signal (wave | {type(m).__name__}(...)) before or after "
-                            "streaming")
-    if not isinstance(e, _ShaperStream) and any(isinstance(m, _ShaperStream) for m in members):
-        raise TypeError(f"StatefulWaveshaper / StatefulDistortion must be a top-level effect of the chain in {who}: the processor "
-                        "flushes what it holds back at the end of the stream")
 
 
 class _ModulationStream:
@@ -933,53 +855,94 @@ class StatefulVibrato(_ModulationStream, Vibrato):
     """:class:`~torchfx_amd.effect.Vibrato` over a continuous stream (see :class:`_ModulationStream`)."""
 
 
-def _refuse_modulation(e, who: str) -> None:
-    for m in (e.modules() if isinstance(e, nn.Module) else [e]):
-        if isinstance(m, ModulatedDelay) and not isinstance(m, _ModulationStream):
-            name = type(m).__name__
-            stateful = f"Stateful{name}(...)" if isinstance(m, (Chorus, Flanger, Vibrato)) else "a stateful class (StatefulChorus, StatefulFlanger, StatefulVibrato)"
-            raise TypeError(f"{name} cannot run in {who}: every call starts its LFO at position 0 and its delay line from silence, "
-                            f"so a chunked stream would restart the sweep and drop the delayed samples at every chunk start; use "
-                            f"{stateful} in its place, or run the whole signal (wave | {name}(...)) before or after streaming")
+def _members(e) -> list:
+    """``e`` and every module inside it."""
+    return list(e.modules() if isinstance(e, nn.Module) else [e])
 
 
 def _holds_back(e) -> bool:
-    """Effects whose chunks may return fewer samples than they take and that hand the rest out in ``flush()``."""
-    return isinstance(e, (StatefulResample, StatefulLimiter, _ShaperStream))
+    """Effects whose chunks may return fewer samples than they take and that hand the rest out in ``flush()``: their class says
+    ``holds_back = True``."""
+    return getattr(type(e), "holds_back", False)
 
 
-def _has_stateful_resample(e) -> bool:
-    return any(isinstance(m, StatefulResample) for m in (e.modules() if isinstance(e, nn.Module) else [e]))
+def _held_back(members):
+    """The member that holds outputs back, or None.  Of several, the one a message names: a resampler before a limiter before a
+    shaper (``_hold_rank``), the first of its kind."""
+    return min((m for m in members if _holds_back(m)), key=lambda m: m._hold_rank, default=None)
 
 
-def _refuse_zero_phase(e, who: str) -> None:
-    from torchfx_amd.filter.zerophase import ZeroPhase
-
-    if any(isinstance(m, ZeroPhase) for m in (e.modules() if isinstance(e, nn.Module) else [e])):
-        raise TypeError(f"ZeroPhase cannot run in {who}: zero-phase filtering is non-causal -- its backward pass starts at the "
-                        "end of the signal, which a chunked stream has not seen yet; filter the whole signal "
-                        "(wave | ZeroPhase(...) or sosfiltfilt) before or after streaming")
-
-
-def _refuse_loudness(e, who: str) -> None:
-    from torchfx_amd.effect import LoudnessNormalize
-
-    if any(isinstance(m, LoudnessNormalize) for m in (e.modules() if isinstance(e, nn.Module) else [e])):
-        raise TypeError(f"LoudnessNormalize cannot run in {who}: integrated loudness is a measurement of the whole signal "
-                        "(its relative gate depends on every block), which a chunked stream has not seen yet; normalise the "
-                        "whole signal (wave | LoudnessNormalize(...)) before or after streaming")
+class _Refusal(tp.NamedTuple):
+    """One family of effects that cannot run chunk by chunk.  A member that is a ``plain`` but no ``stream`` instance (and meets
+    ``when``) raises ``text``, with ``{who}``, ``{name}`` (the member's class), ``{m}`` (the member) and ``{stateful}``
+    (``stateful(m)``) filled in; where ``stream`` holds outputs back, an instance of it below the top level raises ``nested``.
+    ``who`` names the one processor that makes the check (None: both)."""
+    plain: type
+    stream: type | tuple
+    text: str
+    when: tp.Callable | None = None
+    stateful: tp.Callable | None = None
+    nested: str | None = None
+    who: str | None = None
 
 
-def _refuse_limiter(e, who: str) -> None:
-    members = list(e.modules() if isinstance(e, nn.Module) else [e])
-    if any(isinstance(m, Limiter) and not isinstance(m, StatefulLimiter) for m in members):
-        raise TypeError(f"Limiter cannot run in {who}: its gain looks A - 1 samples ahead (the look-ahead), which a chunked stream "
-                        "has not seen yet; a streaming limiter that carries that history is not provided by Limiter itself -- use "
-                        "StatefulLimiter(...) in its place, or limit the whole signal (wave | Limiter(...)) before or after "
-                        "streaming")
-    if not isinstance(e, StatefulLimiter) and any(isinstance(m, StatefulLimiter) for m in members):
-        raise TypeError(f"StatefulLimiter must be a top-level effect of the chain in {who}: the processor flushes what it holds "
-                        "back at the end of the stream")
+_TOP_LEVEL = "{} must be a top-level effect of the chain in {{who}}: the processor flushes what it holds back at the end of the stream"
+_NO_RESAMPLE = ("Resample cannot run in StreamProcessor: resampling each chunk on its own leaves a seam at every chunk boundary; use "
+                "StatefulResample as a top-level effect of the chain, or resample the whole signal (Wave.resample) before or after "
+                "streaming")
+# in the order the refusals fire for an effect that would meet several of them
+_REFUSALS = (
+    _Refusal(ZeroPhase, (),
+             "ZeroPhase cannot run in {who}: zero-phase filtering is non-causal -- its backward pass starts at the end of the signal, "
+             "which a chunked stream has not seen yet; filter the whole signal (wave | ZeroPhase(...) or sosfiltfilt) before or after "
+             "streaming"),
+    _Refusal(LoudnessNormalize, (),
+             "LoudnessNormalize cannot run in {who}: integrated loudness is a measurement of the whole signal (its relative gate "
+             "depends on every block), which a chunked stream has not seen yet; normalise the whole signal "
+             "(wave | LoudnessNormalize(...)) before or after streaming"),
+    _Refusal(Limiter, StatefulLimiter,
+             "Limiter cannot run in {who}: its gain looks A - 1 samples ahead (the look-ahead), which a chunked stream has not seen "
+             "yet; a streaming limiter that carries that history is not provided by Limiter itself -- use StatefulLimiter(...) in its "
+             "place, or limit the whole signal (wave | Limiter(...)) before or after streaming",
+             nested=_TOP_LEVEL.format("StatefulLimiter")),
+    _Refusal(Compressor, StatefulCompressor,
+             "Compressor cannot run in {who}: every call starts its level detector from silence, so a chunked stream would drop the "
+             "envelope at every chunk start; use StatefulCompressor(...) in its place, or compress the whole signal "
+             "(wave | Compressor(...)) before or after streaming"),
+    _Refusal(ModulatedDelay, _ModulationStream,
+             "{name} cannot run in {who}: every call starts its LFO at position 0 and its delay line from silence, so a chunked stream "
+             "would restart the sweep and drop the delayed samples at every chunk start; use {stateful} in its place, or run the "
+             "whole signal (wave | {name}(...)) before or after streaming",
+             stateful=lambda m: (f"Stateful{type(m).__name__}(...)" if isinstance(m, (Chorus, Flanger, Vibrato))
+                                 else "a stateful class (StatefulChorus, StatefulFlanger, StatefulVibrato)")),
+    _Refusal(Freeverb, StatefulFreeverb,
+             "Freeverb cannot run in {who}: every call starts from silent delay lines, so a chunked stream would cut the room's tail "
+             "at every chunk start; use StatefulFreeverb(...) in its place, or run the whole signal (wave | Freeverb(...)) before or "
+             "after streaming"),
+    _Refusal(Waveshaper, _ShaperStream,
+             "{name} with oversample={m.oversample} cannot run in {who}: every call zero-pads the edges of its resampling filters, so "
+             "a chunked stream would click at every chunk seam; use {stateful}(...) in its place, oversample=1 (memoryless), or run "
+             "the whole signal (wave | {name}(...)) before or after streaming",
+             when=lambda m: m.oversample != 1,
+             stateful=lambda m: f"Stateful{type(m).__name__ if type(m) in (Waveshaper, Distortion) else 'Waveshaper'}",
+             nested=_TOP_LEVEL.format("StatefulWaveshaper / StatefulDistortion")),
+    # RealtimeProcessor has no text of its own for a plain Resample: it meets this one in the StreamProcessor it runs its blocks through
+    _Refusal(Resample, StatefulResample, _NO_RESAMPLE, nested=_NO_RESAMPLE, who="StreamProcessor"),
+)
+
+
+def _check_streamable(e, who: str) -> None:
+    """Raise the TypeError of the first family in ``_REFUSALS`` that ``e``, a top-level effect of ``who``'s chain, or a module
+    inside it belongs to."""
+    members = _members(e)
+    for r in _REFUSALS:
+        if r.who not in (None, who):
+            continue
+        for m in members:
+            if isinstance(m, r.plain) and not isinstance(m, r.stream) and (r.when is None or r.when(m)):
+                raise TypeError(r.text.format(who=who, name=type(m).__name__, m=m, stateful=r.stateful and r.stateful(m)))
+        if getattr(r.stream, "holds_back", False) and not isinstance(e, r.stream) and any(isinstance(m, r.stream) for m in members):
+            raise TypeError(r.nested.format(who=who))
 
 
 class _ChunkRun:
@@ -1119,24 +1082,12 @@ class StreamProcessor:
         for e in self._effects:
             if not isinstance(e, FX):
                 raise TypeError("All effects must inherit from FX when used in StreamProcessor")
-            _refuse_zero_phase(e, "StreamProcessor")
-            _refuse_loudness(e, "StreamProcessor")
-            _refuse_limiter(e, "StreamProcessor")
-            _refuse_compressor(e, "StreamProcessor")
-            _refuse_modulation(e, "StreamProcessor")
-            _refuse_freeverb(e, "StreamProcessor")
-            _refuse_waveshaper(e, "StreamProcessor")
-            if not isinstance(e, StatefulResample) and any(isinstance(m, Resample) for m in e.modules()):
-                raise TypeError("Resample cannot run in StreamProcessor: resampling each chunk on its own leaves a seam at "
-                                "every chunk boundary; use StatefulResample as a top-level effect of the chain, or resample "
-                                "the whole signal (Wave.resample) before or after streaming")
+            _check_streamable(e, "StreamProcessor")
         self._resamplers = [e for e in self._effects if isinstance(e, StatefulResample)]
-        self._limiters = [e for e in self._effects if isinstance(e, StatefulLimiter)]
-        shapers = [e for e in self._effects if isinstance(e, _ShaperStream)]
-        if (self._resamplers or self._limiters or shapers) and overlap != 0:
-            who = "StatefulResample" if self._resamplers else ("StatefulLimiter" if self._limiters else type(shapers[0]).__name__)
-            raise ValueError(f"A chain with a {who} needs overlap = 0, got {overlap}: the effect holds outputs back, so a chunk's "
-                             "dropped overlap samples have no counterpart in its output")
+        held = _held_back(self._effects)
+        if held is not None and overlap != 0:
+            raise ValueError(f"A chain with a {type(held).__name__} needs overlap = 0, got {overlap}: the effect holds outputs back, so "
+                             "a chunk's dropped overlap samples have no counterpart in its output")
         self._chunk_size, self._overlap, self._device = chunk_size, overlap, device
         self._use_graph = use_graph
         self._graph = None            # (CUDAGraph, static in, static out, stream, signature, state slots, homes)
@@ -1187,7 +1138,7 @@ class StreamProcessor:
         """(module, attribute) of every carried-state tensor reachable from the effects."""
         slots = []
         for e in self._effects:
-            for m in (e.modules() if isinstance(e, nn.Module) else [e]):
+            for m in _members(e):
                 for a in self._STATE_ATTRS:
                     if isinstance(getattr(m, a, None), Tensor):
                         slots.append((m, a))
@@ -1203,8 +1154,8 @@ class StreamProcessor:
         return len(self._segments) == 1 and isinstance(self._segments[0], _ChunkRun) and self._segments[0].fuses(w)
 
     def _run(self, w: Tensor, start: int = 0) -> Tensor | None:
-        """The chain from segment ``start`` on; None when an effect that holds outputs back (``StatefulResample``,
-        ``StatefulLimiter``, ``StatefulWaveshaper``) completes no output for this chunk (the effects after it are not called)."""
+        """The chain from segment ``start`` on; None when an effect that holds outputs back (``holds_back``) completes no output
+        for this chunk (the effects after it are not called)."""
         for e in self._segments[start:]:
             w = e(w)
             if _holds_back(e) and w.shape[-1] == 0:
@@ -1226,15 +1177,12 @@ class StreamProcessor:
         """Whether a replayed step leaves the host side of every effect right: a resampler counts samples per chunk (never),
         a limiter or an oversampled waveshaper only until its position counter has saturated (chunks run eagerly until then).
         Every member that has ``_graph_ready`` is asked."""
-        if self._resamplers:
-            return False
-        members = (m for e in self._effects for m in (e.modules() if isinstance(e, nn.Module) else [e]))
-        return all(m._graph_ready(w) for m in members if hasattr(m, "_graph_ready"))
+        return all(m._graph_ready(w) for e in self._effects for m in _members(e) if hasattr(m, "_graph_ready"))
 
     def _capture_members(self) -> list:
         """Members whose parameters a captured step bakes in and whose carried state can change length (StatefulDelay,
         StatefulReverb): they name their parameters in ``_capture_key`` and resize their history in ``_sync_history``."""
-        return [m for e in self._effects for m in (e.modules() if isinstance(e, nn.Module) else [e]) if hasattr(m, "_capture_key")]
+        return [m for e in self._effects for m in _members(e) if hasattr(m, "_capture_key")]
 
     def _graph_step(self, w: Tensor) -> Tensor:
         """Replay the captured step on ``w`` (capturing it first; the carried states must exist)."""
@@ -1449,26 +1397,12 @@ class RealtimeProcessor:
         for e in modules:
             if not isinstance(e, FX):
                 raise TypeError("All effects must inherit from FX when used in RealtimeProcessor")
-            _refuse_zero_phase(e, "RealtimeProcessor")
-            _refuse_loudness(e, "RealtimeProcessor")
-            _refuse_limiter(e, "RealtimeProcessor")
-            _refuse_compressor(e, "RealtimeProcessor")
-            _refuse_modulation(e, "RealtimeProcessor")
-            _refuse_freeverb(e, "RealtimeProcessor")
-            _refuse_waveshaper(e, "RealtimeProcessor")
-            if _has_stateful_resample(e):
+            _check_streamable(e, "RealtimeProcessor")
+            if any(isinstance(m, StatefulResample) for m in _members(e)):
                 raise TypeError("StatefulResample cannot run in RealtimeProcessor: a sound card's output block has the input "
                                 "block's length and sample rate; resample with StreamProcessor or Wave.resample instead")
-            if isinstance(e, StatefulLimiter) and e.aligned:
-                raise TypeError("StatefulLimiter(aligned=True) cannot run in RealtimeProcessor: it returns the outputs a block "
-                                "completes, none for the first blocks, and a sound card's output block has the input block's "
-                                "length; construct it with aligned=False (constant latency: the result delayed by "
-                                "StatefulLimiter.latency samples)")
-            if isinstance(e, _ShaperStream) and e.aligned:
-                raise TypeError(f"{type(e).__name__}(aligned=True) cannot run in RealtimeProcessor: it returns the outputs a block "
-                                "completes, fewer for the first block, and a sound card's output block has the input block's "
-                                "length; construct it with aligned=False (constant latency: the result delayed by its `latency` "
-                                "samples)")
+            if _holds_back(e) and e.aligned:
+                raise TypeError(e._aligned_refusal.format(name=type(e).__name__))
         self._runner = StreamProcessor(modules, chunk_size=config.buffer_size, overlap=0, device=device, use_graph=use_graph)
         self._backend, self._config, self._running = backend, config, False
         self._buffer_capacity = buffer_capacity

@@ -667,18 +667,11 @@ class Wave:
     def __or__(self, f: nn.Module) -> "Wave":
         if not isinstance(f, nn.Module):
             raise TypeError(f"Expected nn.Module, but got {type(f).__name__} instead.")
-        from torchfx_amd.realtime import StatefulLimiter, StatefulResample, _ShaperStream
+        from torchfx_amd.realtime import _held_back
 
-        if any(isinstance(m, StatefulResample) for m in f.modules()):
-            raise TypeError("StatefulResample is for chunked streams (StreamProcessor): a Wave is a whole signal, and a stream's "
-                            "forward holds back its last outputs; pipe it through Resample or call Wave.resample instead")
-        if any(isinstance(m, StatefulLimiter) for m in f.modules()):
-            raise TypeError("StatefulLimiter is for chunked streams (StreamProcessor, RealtimeProcessor): a Wave is a whole "
-                            "signal, and a stream's forward holds back its last outputs; pipe it through Limiter instead")
-        if any(isinstance(m, _ShaperStream) for m in f.modules()):
-            raise TypeError("StatefulWaveshaper / StatefulDistortion are for chunked streams (StreamProcessor, RealtimeProcessor): a "
-                            "Wave is a whole signal, and a stream's forward holds back its last outputs; pipe it through Waveshaper "
-                            "or Distortion instead")
+        held = _held_back(f.modules())              # an effect that holds outputs back says itself why a Wave cannot take it
+        if held is not None:
+            raise TypeError(held._wave_refusal)
         fs = Wave._bind_fs(f, self.fs)
         steps = list(f.children()) if isinstance(f, nn.Sequential) else [f]
         return Wave._deferred(self._ys, fs, self._device, self.metadata,
