@@ -774,6 +774,42 @@ int tfx_waveshaper_stream_plan_info(int64_t rows, int64_t T, int64_t oversample,
                                     int64_t *positions, int64_t *lds_bytes);
 
 /* ---------------------------------------------------------------------------
+ * tfx_phaser_forward -- the phaser: `stages` = N first-order all-pass sections in series whose one coefficient an LFO sweeps
+ * every sample.  x is [rows, T] with rows = batch * channels; the channel index of a row is c = row mod channels.  For the
+ * absolute sample n = position + j (position: the host scalar, or *pos_in when pos_in is given), every intermediate in float64
+ * for both dtypes:
+ *   1. off = frac(phase + c * spread)
+ *   2. t = double(n) * (rate / fs) -- one IEEE multiplication, never contracted into an FMA;  a_ = (t - floor(t)) + off
+ *   3. l = sinpi(2 a_) (TFX_LFO_SINE) or 1 - 4 |frac(a_ + 0.25) - 0.5| (TFX_LFO_TRIANGLE)   [1 to 3: tfx_modulated_delay_forward's]
+ *   4. fc = min_freq * exp(Lg * (0.5 + 0.5 l)),  Lg = ln(max_freq / min_freq) computed on the host as a double (an exponential
+ *      sweep; min_freq == max_freq gives a constant filter)
+ *   5. g = tan(w * fc),  w = pi / fs computed on the host as a double;  a[n] = (g - 1) / (g + 1): |a| < 1 under the rules, negative below fs / 4
+ *   6. x_0 = double(x);  for k = 1..N:  x_k[n] = a[n] x_{k-1}[n] + x_{k-1}[n-1] - a[n] x_k[n-1]   (every section uses a[n])
+ *   7. y[n] = dtype(dry x_0[n] + wet x_N[n]), rounded once
+ * State: DEVICE float64 [rows, N + 1] = (x_0[-1], x_1[-1], .., x_N[-1]); state_in NULL = silence; state_out (its own buffer, or
+ * NULL) receives the state after the last sample.  pos_out (DEVICE int64 [1], its own buffer, or NULL) receives the position + T:
+ * a replayed HIP graph bakes host scalars in, a device counter moves on with every replay.  coef_or_null: DEVICE float64
+ * [channels, T] -- [1, T] when spread == 0 or channels == 1 -- receives a[n] as the kernel computed it.
+ * Rules: 1 <= stages <= 12; 10 Hz <= min_freq <= max_freq <= 0.45 fs; 0 < rate < fs / 2; 0 <= position <= 2^52; dry, wet,
+ * phase and spread finite.  x, y DEVICE [rows, T] of dtype, y may not overlap x.
+ * Launches: a row is cut into tiles of 2048 samples and the tiles into `segments` runs of whole tiles (0 = the plan's choice: 1
+ * when the rows alone fill the chip; clamped to the tile count).  One segment is one launch; otherwise two, the first storing
+ * per segment how it maps the incoming state (s -> M s + v, M lower-triangular Toeplitz: 2 N doubles) into `scratch`
+ * (scratch_bytes of tfx_phaser_plan_info; may be NULL for one segment).  The coefficient track does not depend on the cut, the
+ * segments or the other rows, bit for bit; the outputs depend on the cut only through the association of the scan (float64
+ * round-off).  A sample's bits do not depend on values after it.  From a NaN / Inf x[m] on, every output of that row is
+ * non-finite.  T == 0 hands the state and the position on.  Arguments are checked before the device is touched.
+ * ------------------------------------------------------------------------- */
+int tfx_phaser_forward(const void *x, void *y, double *coef_or_null, int dtype, int64_t rows, int64_t channels, int64_t T,
+                       int64_t stages, double fs, double rate, double min_freq, double max_freq, double phase, double spread, double dry,
+                       double wet, int shape, int64_t position, const int64_t *pos_in, int64_t *pos_out, const double *state_in,
+                       double *state_out, int64_t segments, void *scratch, tfx_stream_t stream);
+/* what tfx_phaser_forward does (host-only, same checks on the sizes): samples per tile (2048), tiles per row, the segments it
+ * takes for the request, the tiles of the longest segment and the bytes of `scratch` (0 for one segment) */
+int tfx_phaser_plan_info(int64_t rows, int64_t channels, int64_t T, int64_t stages, int64_t segments, int64_t *tile, int64_t *tiles,
+                         int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes);
+
+/* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of
  * ParallelFilterCombination.forward, src/torchfx/filter/__base.py:1019-1026).
  * xs_host: HOST array of n DEVICE pointers, each [numel] of dtype.

@@ -795,6 +795,26 @@ int tfx_waveshaper_stream_plan_info(int64_t rows, int64_t T, int64_t oversample,
     TFX_API_END
 }
 
+int tfx_phaser_forward(const void *x, void *y, double *coef_or_null, int dtype, int64_t rows, int64_t channels, int64_t T,
+                       int64_t stages, double fs, double rate, double min_freq, double max_freq, double phase, double spread, double dry,
+                       double wet, int shape, int64_t position, const int64_t *pos_in, int64_t *pos_out, const double *state_in,
+                       double *state_out, int64_t segments, void *scratch, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    phaser_forward(x, y, coef_or_null, dtype, rows, channels, T, stages, fs, rate, min_freq, max_freq, phase, spread, dry, wet, shape,
+                   position, pos_in, pos_out, state_in, state_out, segments, scratch, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_phaser_plan_info(int64_t rows, int64_t channels, int64_t T, int64_t stages, int64_t segments, int64_t *tile, int64_t *tiles,
+                         int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(tile && tiles && segments_out && seg_tiles && scratch_bytes, "phaser_plan_info: null output");
+    phaser_plan_info(rows, channels, T, stages, segments, tile, tiles, segments_out, seg_tiles, scratch_bytes);
+    TFX_API_END
+}
+
 int tfx_sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, tfx_stream_t stream)
 {
     TFX_API_BEGIN

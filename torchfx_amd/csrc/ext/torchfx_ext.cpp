@@ -747,6 +747,58 @@ std::tuple<Tensor, Tensor, Tensor> modulated_delay_stream_op(const Tensor &x_in,
     return std::make_tuple(y, hout, pout);
 }
 
+// The phaser (tfx_phaser_forward): x [T], [C, T] or [B, C, T]; the parameters as the C entry takes them; pos a device int64 [1]
+// (a stream's position; None = the host scalar `position`), state [rows, stages + 1] float64 or None (silence); segments 0 = the
+// plan's choice -> (y like x, coef [C or 1, T] float64 or an empty tensor, new state [rows, stages + 1] float64, pos + T as a
+// fresh int64 [1] or an empty tensor without pos).  The summaries between the launches live in a tensor from torch's allocator.
+int64_t phaser_coef_rows(int64_t channels, double spread) { return (spread == 0.0 || channels == 1) ? 1 : channels; }
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> phaser_op(const Tensor &x_in, int64_t stages, double fs, double rate, double min_freq,
+                                                     double max_freq, double phase, double spread, double dry, double wet, int64_t shape,
+                                                     int64_t position, const OptTensor &pos, const OptTensor &state, bool return_coef,
+                                                     int64_t segments)
+{
+    const char *what = "phaser_forward";
+    need_device(x_in, "x");
+    TORCH_CHECK(x_in.dim() >= 1 && x_in.dim() <= 3, what, ": x must be [T], [C, T] or [B, C, T], got ", x_in.dim(), " dimensions");
+    TORCH_CHECK(shape == TFX_LFO_SINE || shape == TFX_LFO_TRIANGLE, what, ": bad LFO shape ", shape);
+    const Tensor x = x_in.contiguous();
+    const int dt = dtype_code(x, what);
+    const int64_t T = x.size(-1), rows = stream_rows(x), channels = x.dim() >= 2 ? x.size(-2) : 1;
+    TORCH_CHECK(channels >= 1, what, ": x has no channels");
+    int64_t info[5];
+    check_rc(tfx_phaser_plan_info(rows, channels, T, stages, segments, info, info + 1, info + 2, info + 3, info + 4), what);
+    Tensor keep, pin;
+    const double *sin = state_ptr(state, {rows, stages + 1}, x, "phaser_forward: state", keep);
+    if (pos.has_value() && pos->defined()) {
+        TORCH_CHECK(pos->numel() == 1 && pos->scalar_type() == at::kLong, what, ": the position must be an int64 tensor of one element");
+        pin = pos->to(x.device()).contiguous();
+    }
+    const auto f64 = x.options().dtype(at::kDouble), i64 = x.options().dtype(at::kLong);
+    Tensor y = at::empty_like(x), sout = at::empty({rows, stages + 1}, f64), scratch = at::empty({info[4] / 8}, f64);
+    Tensor coef = return_coef ? at::empty({phaser_coef_rows(channels, spread), T}, f64) : at::empty({0}, f64);
+    Tensor pout = at::empty({pin.defined() ? 1 : 0}, i64);
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_phaser_forward(x.data_ptr(), y.data_ptr(), return_coef ? coef.data_ptr<double>() : nullptr, dt, rows, channels, T, stages,
+                                fs, rate, min_freq, max_freq, phase, spread, dry, wet, (int)shape, position,
+                                pin.defined() ? pin.data_ptr<int64_t>() : nullptr, pin.defined() ? pout.data_ptr<int64_t>() : nullptr, sin,
+                                sout.data_ptr<double>(), segments, info[4] ? scratch.data_ptr() : nullptr, stream_of(x)),
+             what);
+    return std::make_tuple(y, coef, sout, pout);
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> phaser_meta(const Tensor &x, int64_t stages, double, double, double, double, double,
+                                                       double spread, double, double, int64_t, int64_t, const OptTensor &pos,
+                                                       const OptTensor &, bool return_coef, int64_t)
+{
+    TORCH_CHECK(x.dim() >= 1 && x.dim() <= 3 && stages >= 1, "phaser_forward: bad shape");
+    const int64_t T = x.size(-1), channels = x.dim() >= 2 ? x.size(-2) : 1;
+    const auto f64 = x.options().dtype(at::kDouble);
+    return {at::empty_like(x), return_coef ? at::empty({phaser_coef_rows(channels, spread), T}, f64) : at::empty({0}, f64),
+            at::empty({stream_rows(x), stages + 1}, f64),
+            at::empty({pos.has_value() && pos->defined() ? 1 : 0}, x.options().dtype(at::kLong))};
+}
+
 // What the waveshaper's two ops take: x [..., T] contiguous, rows independent; curve (shape 3 only) and the two tap vectors
 // (oversample > 1 only) host tensors of x's dtype
 struct ShaperInputs {
@@ -1385,6 +1437,19 @@ TORCH_LIBRARY(torchfx_reverb, m)
 TORCH_LIBRARY_IMPL(torchfx_reverb, Meta, m)
 {
     m.impl("freeverb_forward", freeverb_meta);
+}
+
+// The phaser likewise: torch.ops.torchfx_phaser.
+TORCH_LIBRARY(torchfx_phaser, m)
+{
+    reg_op(m, "phaser_forward(Tensor x, int stages, float fs, float rate, float min_freq, float max_freq, float phase, float spread, "
+              "float dry, float wet, int shape, int position=0, Tensor? pos=None, Tensor? state=None, bool return_coef=False, "
+              "int segments=0) -> (Tensor, Tensor, Tensor, Tensor)", phaser_op);
+}
+
+TORCH_LIBRARY_IMPL(torchfx_phaser, Meta, m)
+{
+    m.impl("phaser_forward", phaser_meta);
 }
 
 // The waveshaper likewise: torch.ops.torchfx_shaper.

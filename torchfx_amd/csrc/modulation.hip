@@ -18,6 +18,7 @@
 // samples of delay at n = 2^40), and with it off every expression below rounds exactly as written, on the device and the host.
 // Plain vector stores only; nothing crosses between workgroups.
 #include "common.h"
+#include "lfo.h"
 #include "plan_cache.h"
 #include "timedomain.h"
 #include "../../include/torchfx_hip.h"
@@ -59,15 +60,7 @@ template <typename T> struct ModArgs {
 template <bool TRI>
 __device__ __forceinline__ void mod_delay_at(int64_t n, const ModVoice &vc, double off, int64_t &i, double &f)
 {
-    const double t = __dmul_rn((double)n, vc.inc);
-    const double a = (t - floor(t)) + off;                  // in [0, 2]
-    double l;
-    if (TRI) {
-        const double z = a + 0.25;
-        l = 1.0 - 4.0 * fabs((z - floor(z)) - 0.5);
-    } else {
-        l = sinpi(2.0 * a);
-    }
+    const double l = lfo_at<TRI>(n, vc.inc, off);           // lfo.h: shared with the phaser
     const double d = vc.base + vc.depth * l;
     const double fl = floor(d);
     i = (int64_t)fl;

@@ -1,5 +1,5 @@
 // timedomain.h -- the host entry points of the time-domain and elementwise ops, one prototype per exported function of fir.hip,
-// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip, compressor.hip, modulation.hip, reverb.hip, waveshaper.hip and layout.hip (the cascade's: sos.h; the
+// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip, compressor.hip, modulation.hip, reverb.hip, waveshaper.hip, phaser.hip and layout.hip (the cascade's: sos.h; the
 // overlap-save pipelines': ols_route.h).  Included by the file that defines each function and by capi.hip, so a prototype that drifts from
 // its definition does not compile; default arguments live here and nowhere else.  Every *_forward checks its arguments before
 // anything touches the device; a *_plan_info takes the same checking path without the pointers.
@@ -133,6 +133,14 @@ void waveshaper_stream_plan_info(int64_t rows, int64_t T, int64_t oversample, in
                                  int64_t *latency, int64_t *history, int64_t *tile, int64_t *tiles, int64_t *positions,
                                  int64_t *lds_bytes);
 void waveshaper_clear();
+
+// ---- phaser.hip ----
+void phaser_forward(const void *x, void *y, double *coef, int dtype, int64_t rows, int64_t channels, int64_t T, int64_t stages, double fs,
+                    double rate, double min_freq, double max_freq, double phase, double spread, double dry, double wet, int shape,
+                    int64_t position, const int64_t *pos_in, int64_t *pos_out, const double *state_in, double *state_out,
+                    int64_t segments, void *scratch, hipStream_t stream);
+void phaser_plan_info(int64_t rows, int64_t channels, int64_t T, int64_t stages, int64_t segments, int64_t *tile, int64_t *tiles,
+                      int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes);
 
 // ---- layout.hip ----
 void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, int64_t C, int64_t ld_out, int64_t f_base,

@@ -471,6 +471,61 @@ class Flanger(ModulatedDelay):
         return f"rate={self.rate}, depth={self.depth}, delay={self.delay}, mix={self.mix}, invert={self.invert}, " + super().extra_repr()
 
 
+class Phaser(FX):
+    """Phaser: :func:`torchfx_amd.phaser.phase_shift` as an effect -- ``stages`` first-order all-pass sections in series whose
+    corner frequency an LFO sweeps exponentially between ``min_freq`` and ``max_freq`` Hz at ``rate`` Hz, mixed with the signal:
+    ``dry = 1 - mix`` and ``wet = mix`` (``-mix`` with ``invert``, which moves the notches to where the peaks were).  ``spread``
+    shifts the LFO phase by that many cycles per channel index; ``shape`` is "sine" or "triangle".  There is no feedback
+    (regeneration) path around the chain.
+
+    ``fs`` comes from the ``Wave`` the effect is piped into when it is None.  Every call starts its sweep at position 0 and its
+    sections from silence: the effect is a step of its own in ``Wave.plan()`` (``csrc/phaser.hip``), and a chunked stream needs
+    :class:`torchfx_amd.realtime.StatefulPhaser`, which carries the sections' states and the position."""
+
+    def __init__(self, rate: float = 0.5, min_freq: float = 200.0, max_freq: float = 2000.0, stages: int = 4, mix: float = 0.5,
+                 invert: bool = False, spread: float = 0.0, shape: str = "sine", fs: int | None = None) -> None:
+        super().__init__()
+        self.rate, self.min_freq, self.max_freq, self.stages = rate, min_freq, max_freq, stages
+        self.mix, self.invert, self.spread, self.shape, self.fs = mix, bool(invert), spread, shape, fs
+        self.params(torch.float32, 48000 if fs is None else fs)         # argument errors now
+
+    def params(self, dtype: torch.dtype, fs: int | None = None):
+        """The call's :class:`torchfx_amd.phaser.PhaserParams` for a signal of ``dtype`` at ``fs`` (default ``self.fs``)."""
+        fs = self.fs if fs is None else fs
+        if fs is None:
+            raise ValueError(f"{type(self).__name__} needs the sample rate: pass fs or pipe a Wave into it (wave | {type(self).__name__}())")
+        from torchfx_amd.phaser import PhaserParams, _real
+
+        mix = _real("mix", self.mix)
+        return PhaserParams(fs, dtype, self.stages, self.min_freq, self.max_freq, self.rate, 0.0, 1.0 - mix, -mix if self.invert else mix,
+                            self.spread, self.shape)
+
+    def route(self, x: Tensor, length: int | None = None) -> str:
+        """``native (...)`` or ``numpy on host -- <reason>`` for ``x`` (rows of ``length`` samples, default x's)."""
+        if not x.is_cuda:
+            return f"numpy on host -- {x.device.type} tensor"
+        try:
+            P = self.params(x.dtype)
+            n = int(x.shape[-1]) if length is None else int(length)
+            info = _ext().phaser_plan_info(n, max(1, math.prod(x.shape[:-1])), int(x.shape[-2]) if x.dim() >= 2 else 1, P.stages)
+        except (RuntimeError, ValueError, TypeError) as e:
+            return f"refused -- {e}"
+        launches = "one launch" if info["segments"] == 1 else "two launches"
+        return (f"native (phaser_kernel, {P.stages} stage(s), {P.shape} LFO, {info['tiles']} tile(s) of {info['tile']} per row in "
+                f"{info['segments']} segment(s); {launches})")
+
+    @torch.no_grad()
+    def forward(self, waveform: Tensor) -> Tensor:
+        from torchfx_amd.phaser import _check_signal, phase_shift_run
+
+        _check_signal(waveform, "phase_shift")
+        return phase_shift_run(waveform, self.params(waveform.dtype))[0]
+
+    def extra_repr(self) -> str:
+        return (f"rate={self.rate}, min_freq={self.min_freq}, max_freq={self.max_freq}, stages={self.stages}, mix={self.mix}, "
+                f"invert={self.invert}, spread={self.spread}, shape={self.shape!r}, fs={self.fs}")
+
+
 class Epilogued(FX):
     """Planner product (``Wave.plan()``, ``fuse_epilogue``): a filter followed by ``Gain`` and / or ``Normalize``
     whose elementwise work rides on the filter's own kernel.  ``producer`` is an SOS filter / cascade or an

@@ -103,3 +103,11 @@ def shaper_stream_ops():
 
     load()
     return torch.ops.torchfx_shaper_stream
+
+
+def phaser_ops():
+    """``torch.ops.torchfx_phaser`` (the phaser's namespace, registered by the same module) with the library loaded."""
+    import torch
+
+    load()
+    return torch.ops.torchfx_phaser

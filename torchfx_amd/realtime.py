@@ -23,7 +23,10 @@ stream: causal, no latency, it carries the detector's ``(y1, yL)`` per group (``
 equal ``compress`` on the whole signal to float64 round-off of the detector (not bit for bit).  :class:`StatefulChorus`,
 :class:`StatefulFlanger` and :class:`StatefulVibrato` are the modulation effects of a stream: causal, no latency, they carry the
 delay line's reach in ``_hist`` and the LFO's position in ``_pos`` (a device counter, ``tfx_modulated_delay_stream_forward``), and
-their chunks are bit-identical to the one-shot effect on the whole signal.  :class:`StatefulFreeverb` is the room reverb of a
+their chunks are bit-identical to the one-shot effect on the whole signal.  :class:`StatefulPhaser` is the phaser of a stream:
+causal, no latency, it carries the all-pass sections' states in ``_hist`` and the sweep's position in ``_pos``
+(``tfx_phaser_forward``'s state and device counter); its coefficient track is bit-identical to the one-shot call's and its chunks
+equal it to float64 round-off (not bit for bit).  :class:`StatefulFreeverb` is the room reverb of a
 stream: causal, no latency, it carries every delay line in time order (``tfx_freeverb_forward``'s state), its chunks equal
 ``freeverb`` on the whole signal to float64 round-off (not bit for bit) and ``flush()`` returns the ring-out.
 :class:`StatefulWaveshaper` and :class:`StatefulDistortion` are the oversampled waveshaper of a stream: they carry the last
@@ -52,7 +55,7 @@ import torch
 from torch import Tensor, nn
 
 from torchfx_amd.effect import (FX, Chorus, Compressor, Delay, Distortion, Flanger, Freeverb, Limiter, LoudnessNormalize, ModulatedDelay,
-                                MonoDelayStrategy, PingPongDelayStrategy, Reverb, Vibrato, Waveshaper, _ext)
+                                MonoDelayStrategy, Phaser, PingPongDelayStrategy, Reverb, Vibrato, Waveshaper, _ext)
 from torchfx_amd.filter._base import AbstractFilter
 from torchfx_amd.filter.fir import FIR
 from torchfx_amd.filter.zerophase import ZeroPhase
@@ -855,6 +858,51 @@ class StatefulVibrato(_ModulationStream, Vibrato):
     """:class:`~torchfx_amd.effect.Vibrato` over a continuous stream (see :class:`_ModulationStream`)."""
 
 
+class StatefulPhaser(Phaser):
+    """:class:`~torchfx_amd.effect.Phaser` over a continuous stream: every row carries ``(x_0[-1], .., x_N[-1])``, the last
+    sample of the input and of each all-pass section, in ``_hist`` (``[rows, stages + 1]`` float64) and the stream the absolute
+    position of its next sample in ``_pos`` (int64 ``[1]`` on the chunks' device: a replayed HIP graph bakes host scalars in, a
+    device counter moves on with every replay).  The phaser is causal with no latency: every chunk returns the chunk's shape
+    and there is nothing to flush.
+
+    The stream restarts from silence and position 0 when the row count, ``stages`` or the device changes; :meth:`reset_state`
+    does the same on request.  Any other parameter applies from the next chunk on.  The coefficient track of the chunks is
+    bit-identical to the one-shot call's; the outputs equal :func:`~torchfx_amd.phaser.phase_shift` on the whole signal to
+    float64 round-off and not bit for bit: the scan's association follows the cut.  After a NaN or Inf the state of its row is
+    non-finite and stays so until :meth:`reset_state`.  Device float32 / float64 chunks run :func:`torchfx_ext.phaser_forward`
+    (one launch for a chunk of up to 2048 samples), CPU chunks the host path."""
+
+    def __init__(self, *args, **kwargs) -> None:
+        super().__init__(*args, **kwargs)
+        self.reset_state()
+
+    def reset_state(self) -> None:
+        self._hist: Tensor | None = None            # [rows, stages + 1] float64; None = silence
+        self._pos: Tensor | None = None             # int64 [1] on the chunks' device; None = 0
+
+    def _capture_key(self) -> tuple:
+        """What a captured HIP graph of this effect bakes in: every parameter of the launch."""
+        return (self.rate, self.min_freq, self.max_freq, self.stages, self.mix, self.invert, self.spread, self.shape, self.fs)
+
+    def _sync_history(self) -> None:
+        """Nothing to resize: a changed ``stages`` restarts the stream in :meth:`forward`."""
+
+    @torch.no_grad()
+    def forward(self, x: Tensor) -> Tensor:
+        rows = _rows(x)
+        if self.fs is None:
+            raise ValueError(f"{type(self).__name__} needs the sample rate: pass fs or let the processor configure it")
+        from torchfx_amd.phaser import phase_shift_run
+
+        P = self.params(x.dtype)
+        h = self._hist
+        if (h is None or self._pos is None or tuple(h.shape) != (rows, P.stages + 1) or h.device != x.device
+                or self._pos.device != x.device):                   # a new stream: silence, position 0
+            h, self._pos = None, torch.zeros(1, dtype=torch.int64, device=x.device)
+        y, _, self._hist, self._pos = phase_shift_run(x, P, 0, h, False, self._pos)
+        return y
+
+
 def _members(e) -> list:
     """``e`` and every module inside it."""
     return list(e.modules() if isinstance(e, nn.Module) else [e])
@@ -928,6 +976,10 @@ _REFUSALS = (
              nested=_TOP_LEVEL.format("StatefulWaveshaper / StatefulDistortion")),
     # RealtimeProcessor has no text of its own for a plain Resample: it meets this one in the StreamProcessor it runs its blocks through
     _Refusal(Resample, StatefulResample, _NO_RESAMPLE, nested=_NO_RESAMPLE, who="StreamProcessor"),
+    _Refusal(Phaser, StatefulPhaser,
+             "Phaser cannot run in {who}: every call starts its sweep at position 0 and its all-pass sections from silence, so a "
+             "chunked stream would restart the sweep and the filter states at every chunk start; use StatefulPhaser(...) in its "
+             "place, or run the whole signal (wave | Phaser(...)) before or after streaming"),
 )
 
 

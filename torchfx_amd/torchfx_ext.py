@@ -38,7 +38,7 @@ __all__ = [
     "sos_block_energy", "sos_block_energy_plan_info", "true_peak", "true_peak_plan_info", "limiter_forward", "limiter_plan_info",
     "limiter_stream_forward", "limiter_stream_plan_info", "compressor_forward", "compressor_plan_info",
     "modulated_delay_forward", "modulated_delay_stream_forward", "modulated_delay_plan_info", "freeverb_forward", "freeverb_plan_info",
-    "waveshaper_stream_forward", "waveshaper_stream_plan_info",
+    "waveshaper_stream_forward", "waveshaper_stream_plan_info", "phaser_forward", "phaser_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "effects_plan_info", "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
 ]
@@ -518,6 +518,35 @@ def waveshaper_stream_plan_info(length: int, oversample: int, taps_up: int = 0, 
     return _query(L.load().tfx_waveshaper_stream_plan_info,
                   (int(rows), int(length), int(oversample), int(taps_up), int(taps_dn), int(curve), _dt(dtype)),
                   "latency history tile tiles positions lds_bytes")
+
+
+def phaser_forward(x: Tensor, stages: int, fs: float, rate: float, min_freq: float, max_freq: float, phase: float = 0.0,
+                   spread: float = 0.0, dry: float = 0.5, wet: float = 0.5, shape: str = "sine", position: int = 0,
+                   pos: Tensor | None = None, state: Tensor | None = None, return_coef: bool = False,
+                   segments: int = 0) -> tuple[Tensor, Tensor | None, Tensor, Tensor | None]:
+    """The phaser (``tfx_phaser_forward``; the definition is :func:`torchfx_amd.phaser.phase_shift`'s): ``x [T]``, ``[C, T]`` or
+    ``[B, C, T]`` on the device (float32 / float64), ``stages`` all-pass sections swept between ``min_freq`` and ``max_freq`` Hz
+    at ``rate`` Hz.  The position of the first sample is the host scalar ``position``, or the device int64 ``pos [1]`` of a
+    stream; ``state [rows, stages + 1]`` float64 ``(x_0[-1], .., x_N[-1])`` or None (silence).  ``segments`` cuts a row for the
+    scan (0: the plan's choice; clamped to the tile count): one launch for one segment, two otherwise.  Returns ``(y, coef |
+    None, new state, pos + T | None)``: ``coef`` is ``a[n]`` as the kernel computed it, float64 ``[C, T]`` (``[1, T]`` when
+    ``spread == 0`` or ``C == 1``); the new position is a fresh device tensor when ``pos`` was given.  The op lives in
+    ``torch.ops.torchfx_phaser``."""
+    native.ops()                                         # loads the library: every namespace is registered by the one module
+    y, coef, st, pout = native.phaser_ops().phaser_forward(x.contiguous(), int(stages), float(fs), float(rate), float(min_freq),
+                                                           float(max_freq), float(phase), float(spread), float(dry), float(wet),
+                                                           LFO_SHAPES.index(shape), int(position), pos, state, bool(return_coef),
+                                                           int(segments))
+    return y, (coef if return_coef else None), st, (pout if pos is not None else None)
+
+
+def phaser_plan_info(length: int, rows: int = 1, channels: int = 1, stages: int = 4, segments: int = 0) -> dict:
+    """What :func:`phaser_forward` does for ``rows`` rows of ``length`` samples (``tfx_phaser_plan_info``; host-only, same checks
+    on the sizes): ``tile`` (samples per tile), ``tiles`` per row, the ``segments`` it takes for the request (0: chosen from
+    ``rows`` and ``length``, 1 when the rows alone fill the chip), ``seg_tiles`` (tiles of the longest segment) and
+    ``scratch_bytes`` (the summaries between the launches; 0 for one segment)."""
+    return _query(L.load().tfx_phaser_plan_info, (int(rows), int(channels), int(length), int(stages), int(segments)),
+                  "tile tiles segments seg_tiles scratch_bytes")
 
 
 RESAMPLE_STREAM_KERNELS = ("resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel", "copy")

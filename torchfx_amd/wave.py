@@ -210,7 +210,7 @@ def plan_cache_clear() -> None:
 
 
 def _member_key(m: nn.Module, guard: list) -> tuple:
-    from torchfx_amd.effect import Compressor, Delay, Freeverb, Gain, Limiter, LoudnessNormalize, ModulatedDelay, Normalize, Waveshaper
+    from torchfx_amd.effect import Compressor, Delay, Freeverb, Gain, Limiter, LoudnessNormalize, ModulatedDelay, Normalize, Phaser, Waveshaper
     from torchfx_amd.filter.zerophase import ZeroPhase
     from torchfx_amd.resample import Resample, window_key
 
@@ -244,6 +244,8 @@ def _member_key(m: nn.Module, guard: list) -> tuple:
         k += (m.threshold_db, m.ratio, m.attack, m.release, m.knee_db, m.makeup_db, m.link, m.fs)
     elif isinstance(m, ModulatedDelay):
         k += (tuple(m.voices), m.dry, m.spread, m.shape, m.interpolation, m.pad, m.fs)
+    elif isinstance(m, Phaser):
+        k += (m.rate, m.min_freq, m.max_freq, m.stages, m.mix, m.invert, m.spread, m.shape, m.fs)
     elif isinstance(m, Freeverb):
         k += (m.room_size, m.damping, m.wet, m.dry, m.width, m.tail, m.fs)
     elif isinstance(m, Waveshaper):
@@ -581,7 +583,7 @@ class Wave:
     def explain(self) -> list[str]:
         """One line per step of :meth:`plan` for THIS tensor: the step, the route it will take (``CascadeFIR``: the fused
         recursion-in-pass-A pipeline or the staged pair of launches) and why."""
-        from torchfx_amd.effect import Compressor, Delay, Epilogued, Freeverb, Limiter, LoudnessNormalize, ModulatedDelay, Waveshaper
+        from torchfx_amd.effect import Compressor, Delay, Epilogued, Freeverb, Limiter, LoudnessNormalize, ModulatedDelay, Phaser, Waveshaper
         from torchfx_amd.filter.fused import CascadeFIR, FusedSOSCascade
         from torchfx_amd.filter.zerophase import ZeroPhase
         from torchfx_amd.realtime import StatefulDelay, _native_stream
@@ -608,7 +610,7 @@ class Wave:
             elif isinstance(inner, (Resample, Freeverb)):
                 line += ": " + inner.route(self._ys, length)
                 length = inner.output_length(length)
-            elif isinstance(inner, (ZeroPhase, LoudnessNormalize, Limiter, Compressor, ModulatedDelay, Waveshaper)):
+            elif isinstance(inner, (ZeroPhase, LoudnessNormalize, Limiter, Compressor, ModulatedDelay, Waveshaper, Phaser)):
                 line += ": " + inner.route(self._ys, length)
             lines.append(line)
         return lines
