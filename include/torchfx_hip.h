@@ -133,6 +133,23 @@ int tfx_sos_plan_info(const double *sos_host, int64_t K,
 int tfx_sos_refine_info(const double *sos_host, int64_t K,
                         int *unit_form, int *refine_f32, int *refine_f64, double *errs);
 
+/* How tfx_sos_forward cuts [C,T] rows into time segments for this cascade, dtypes and precision (host only when wave_slots
+ * > 0; same argument checks and the same code path as the call; any output may be NULL).  *route:
+ *   TFX_SOS_ROUTE_SEQUENTIAL  one wavefront per row;
+ *   TFX_SOS_ROUTE_HALO        segments after the first start *warmup samples early from zero state (short-memory cascades);
+ *   TFX_SOS_ROUTE_HANDOFF     every segment starts at its own first sample from the exact state, for any pole radius: end-state
+ *                             passes over the segments, a scan of the end states with the segment's transition matrix, one
+ *                             refinement of both where the cascade's lane scan is refined too, then the ordinary kernel.
+ * *nseg segments per row, *seg_len samples between the starts of consecutive segments (segment g stores from
+ * g * seg_len + warmup), *warmup the halo in force (0 unless HALO), *passes reads of the signal (1; hand-off: 2, or 3 with
+ * the refinement), *bytes_per_sample the signal traffic that makes.  sections != 0: section taps are asked for.
+ * wave_slots: wavefronts the device is taken to hold at once (MI355X: 2048 for the float64 kernels); 0 = ask the current
+ * device as the launch does.  The environment (TFX_SOS_NSEG, TFX_SOS_HANDOFF) acts on the query as on the call. */
+enum tfx_sos_route { TFX_SOS_ROUTE_SEQUENTIAL = 0, TFX_SOS_ROUTE_HALO = 1, TFX_SOS_ROUTE_HANDOFF = 2 };
+int tfx_sos_route_info(int64_t C, int64_t T, const double *sos_host, int64_t K, int x_dtype, int y_dtype, int precision,
+                       int sections, int64_t wave_slots, int *route, int64_t *nseg, int64_t *seg_len, int64_t *warmup,
+                       int *passes, double *bytes_per_sample);
+
 /* ---------------------------------------------------------------------------
  * tfx_sos_filtfilt_forward -- zero-phase (forward-backward) filtering along each row with the semantics of
  * scipy.signal.sosfiltfilt(sos, x, axis=-1, padtype, padlen) (SciPy 1.15); the reference has no counterpart.

@@ -37,6 +37,8 @@ SIGNATURES = {
     "tfx_sos_bank_sum_forward": (_int, [_vp, _int, _vp, _int, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _int, _vp]),
     "tfx_sos_plan_info": (_int, [_vp, _i64, ctypes.POINTER(_int), ctypes.POINTER(_i64), ctypes.POINTER(_dbl)]),
     "tfx_sos_refine_info": (_int, [_vp, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_dbl)]),
+    "tfx_sos_route_info": (_int, [_i64, _i64, _vp, _i64, _int, _int, _int, _int, _i64, ctypes.POINTER(_int), ctypes.POINTER(_i64),
+                                  ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_int), ctypes.POINTER(_dbl)]),
     "tfx_sos_filtfilt_forward": (_int, [_vp, _int, _vp, _int, _i64, _i64, _vp, _i64, _int, _i64, _vp, _vp]),
     "tfx_sos_filtfilt_plan_info": (_int, [_i64, _i64, _vp, _i64, _int, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                           ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_int), ctypes.POINTER(_int)]),

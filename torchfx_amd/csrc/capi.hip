@@ -423,6 +423,17 @@ int tfx_sos_refine_info(const double *sos_host, int64_t K, int *unit_form, int *
     TFX_API_END
 }
 
+int tfx_sos_route_info(int64_t C, int64_t T, const double *sos_host, int64_t K, int x_dtype, int y_dtype, int precision,
+                       int sections, int64_t wave_slots, int *route, int64_t *nseg, int64_t *seg_len, int64_t *warmup,
+                       int *passes, double *bytes_per_sample)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(sos_host && K >= 1 && K <= 512, "sos_route_info: null coefficients or bad section count %lld", (long long)K);
+    sos_route_info(C, T, sos_host, K, x_dtype, y_dtype, precision, sections, wave_slots, route, nseg, seg_len, warmup, passes,
+                   bytes_per_sample);
+    TFX_API_END
+}
+
 int tfx_biquad_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C, int64_t T,
                        const double *b_host, double a1, double a2, const double *state_x_in,
                        const double *state_y_in, double *state_x_out, double *state_y_out, int precision,

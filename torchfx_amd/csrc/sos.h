@@ -14,6 +14,8 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C, in
                  bool sum_bands = false, const Epilogue *ep = nullptr);
 void sos_plan_info(const double *sos_host, int64_t K, int *precision, int64_t *warmup, double *err_bound);
 void sos_refine_info(const double *sos_host, int64_t K, int *unit_form, int *refine_f32, int *refine_f64, double *errs);
+void sos_route_info(int64_t C, int64_t T, const double *sos_host, int64_t K, int x_dtype, int y_dtype, int precision, int sections,
+                    int64_t wave_slots, int *route, int64_t *nseg, int64_t *seg_len, int64_t *warm, int *passes, double *bytes_per_sample);
 void sos_clear_plans();
 
 // zero-phase filtering (scipy.signal.sosfiltfilt along each row)

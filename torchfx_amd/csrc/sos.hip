@@ -30,6 +30,7 @@
 #include "epilogue.h"
 #include "plan_cache.h"
 #include "sos.h"
+#include "sos_route.h"
 #include "../../include/torchfx_hip.h"
 
 #include <cmath>
@@ -89,6 +90,10 @@ struct SosParams {
     // measuring pass (MEAS kernels, sos_block_energy_forward): y is the float64 [C, ms_nblk] array of block energies; block i
     // holds the samples [e_i, e_(i+1)), e_i = (i * ms_num) / ms_den, and segment g owns the blocks [g * ms_bps, (g + 1) * ms_bps)
     int64_t ms_num, ms_den, ms_nblk, ms_bps;
+    // hand-off route (sos_route.h): D = 2 K + 2 doubles per stream, [x1 x2 | y1 y2 of section 0 | ... of section K - 1] in the
+    // true scale (cascade_step's vector; a section's input history is the output history of the one before it)
+    const double *ho_state;  // [C * nseg, D] or null: the streams g > 0 start from their slot instead of zeros
+    double *ho_end;          // ENDS kernels: [C * nseg, D], stream (row, g) leaves its end state in its slot
 };
 
 // Sample i of the row x[0 .. T) extended by `pad` samples at each end (scipy.signal's odd_ext / even_ext / const_ext), i counted
@@ -172,9 +177,12 @@ template <typename T> struct U16 {               // 16 bytes of T
 // MEAS measuring pass (SosParams::ms_*): the cascade's output is not stored; the stream keeps the sum of its squares over each
 //      block of samples it owns.  Segments start on block edges (their halo in front), so every block has one writer.  Scalar
 //      (!VEC) path only, TOut = TIn (the stage holds the input alone); MEAS = false compiles to the code it was before
+// ENDS end-state pass of the hand-off route (SosParams::ho_*): the streams g < nseg - 1 walk their whole-tile segments with the
+//      same arithmetic and store nothing but the cascade's state after their last sample.  Scalar (!VEC) path only, TOut = TIn,
+//      float64 arithmetic; ENDS = false compiles to the code it was before
 // One compiled instance of the kernel = one value of this struct and a type triple; written with designated initialisers.
 struct SosKernel { int LC = 32; bool VEC = false, TAPS = false, PF = false; int MINW = 2;
-                   bool SUMB = false, EPI = false, UNIT = false; int FF = 0; bool FFR = false, MEAS = false;
+                   bool SUMB = false, EPI = false, UNIT = false; int FF = 0; bool FFR = false, MEAS = false, ENDS = false;
                    bool operator==(const SosKernel &) const = default; };
 
 // The stream body: one wavefront walks stream `sid` = (row, segment) with `stage` as its private LDS (transposition
@@ -184,12 +192,14 @@ template <typename TIn, typename TOut, typename TC, SosKernel G>
 __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_t sid, char *const stage, const int lane)
 {
     constexpr int LC = G.LC, FF = G.FF;
-    constexpr bool VEC = G.VEC, TAPS = G.TAPS, PF = G.PF, SUMB = G.SUMB, EPI = G.EPI, UNIT = G.UNIT, FFR = G.FFR, MEAS = G.MEAS;
+    constexpr bool VEC = G.VEC, TAPS = G.TAPS, PF = G.PF, SUMB = G.SUMB, EPI = G.EPI, UNIT = G.UNIT, FFR = G.FFR, MEAS = G.MEAS, ENDS = G.ENDS;
     static_assert(!(TAPS && SUMB), "section taps are not available in sum mode");
     static_assert(!(UNIT && (TAPS || SUMB)), "the unit-b0 form serves the plain cascade only");
     static_assert(FF == 0 || !(VEC || TAPS || PF || SUMB || EPI || UNIT), "the zero-phase passes run the plain scalar path");
     static_assert(!MEAS || !(VEC || TAPS || PF || SUMB || EPI || UNIT || FF != 0), "the measuring pass runs the plain scalar path");
     static_assert(!MEAS || (std::is_same<TC, double>::value && LC <= 64), "block energies: float64 sums, at most one block edge per lane");
+    static_assert(!ENDS || !(VEC || TAPS || PF || SUMB || EPI || UNIT || FF != 0 || MEAS), "the end-state pass runs the plain scalar path");
+    static_assert(!ENDS || std::is_same<TC, double>::value, "end states are float64");
     // what the LDS stage holds on the way in: the odd extension 2 x[0] - x[i] of a float32 row is not a float32 value
     typedef typename std::conditional<FF == 1, TC, TIn>::type TSt;
     constexpr int IOB = sizeof(TIn) > sizeof(TOut) ? sizeof(TIn) : sizeof(TOut);
@@ -236,6 +246,7 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
         out_begin = ms_kb * p.ms_num / p.ms_den;           // e_kb >= warm for g > 0 (block_energy_plan)
         start = g ? out_begin - p.warm : 0;
     }
+    if constexpr (ENDS) { if (g == p.nseg - 1) return; }      // the last segment hands nothing on
     if (out_begin >= T) {
         if (p.nf_flag && lane == 0) p.nf_flag[sid] = 0;
         return;
@@ -243,7 +254,7 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
     int64_t out_end = start + p.seg_len + p.warm;
     if (out_end > T || g == p.nseg - 1) out_end = T;
     if constexpr (MEAS) out_end = ms_ke * p.ms_num / p.ms_den;      // e_ke <= T: samples from e_nblk on belong to no block
-    const bool last_seg = !MEAS && (out_end == T);         // (the measuring pass returns no state)
+    const bool last_seg = !MEAS && !ENDS && (out_end == T);     // (the measuring and end-state passes return no state)
 
     // ---- initial carry: the caller's state for the stream that starts at n = 0, zeros for a
     //      warm-up start.  Layout of state tensors: [K, C, 2] (iir_cpu.cpp:125-130).
@@ -251,7 +262,11 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
         const int b = i / (K * 4), rem = i - b * K * 4;
         const int s = rem >> 2, f = rem & 3;
         TC v = (TC)0;
-        if (start == 0) {
+        if (FF == 0 && !MEAS && g > 0 && p.ho_state) {
+            // hand-off: the exact state at the segment's first sample (the scan's), into the section's scale like the caller's
+            v = (TC)p.ho_state[sid * (2 * K + 2) + (f < 2 ? 2 * s + f : 2 + 2 * s + (f & 1))];
+            if (UNIT) v *= ((const TC *)p.tab)[(band * K + s) * TS + (f < 2 ? 160 : 161)];
+        } else if (start == 0) {
             if constexpr (FF != 0) {
                 // steady state of the cascade for a constant input v0 = the first sample of the pass: section s has seen
                 // v0 G_(s-1) for ever and answered v0 G_s
@@ -606,7 +621,7 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
         }
 
         // ---- store (skipped entirely while still inside the warm-up halo)
-        if (!MEAS && ts + TILE > out_begin) {
+        if (!MEAS && !ENDS && ts + TILE > out_begin) {
             const int64_t lo64 = out_begin - ts, hi64 = out_end - ts;
             const bool full = (lo64 <= 0) && (hi64 >= TILE);
             if constexpr (UNIT) {                       // the product of all b0, once, on the way out
@@ -700,6 +715,11 @@ __device__ __forceinline__ void sos_stream_body(const SosParams &p, const int64_
         // tile runs on into the next segment's samples.
         const int anyb = __any(ms_bad) ? 1 : 0;
         if (p.nf_flag && lane == 0) p.nf_flag[sid] = anyb;
+        return;
+    }
+    if constexpr (ENDS) {
+        // the carry after a whole number of full tiles is the cascade's state after the segment's last sample
+        for (int i = lane; i < 2 * K + 2; i += 64) p.ho_end[sid * (2 * K + 2) + i] = (double)carry[i < 2 ? i : 4 * ((i - 2) >> 1) + 2 + (i & 1)];
         return;
     }
     if (p.nf_flag) {
@@ -804,6 +824,52 @@ __global__ void __launch_bounds__(256) sos_block_energy_fix_kernel(const SosPara
     for (int64_t b = (int64_t)(g0 + 1) * p.ms_bps + tid; b < p.ms_nblk; b += nthr) s[b] = __builtin_nan("");
 }
 
+// Hand-off scan: the start states of a row's segments from the end states the ENDS pass left.  With v_j the input of segment
+// boundary j = 1 ... nseg - 1 and P the transition over a segment, S_j = v_j + P S_(j-1) (S_0 = 0) -- a Kogge-Stone scan over the
+// boundaries with the host's powers P^(2^k) (pw [nlev][D][D]), like the lane scan of the stream kernel one level up:
+// ceil(log2(nseg - 1)) levels of independent D x D mat-vecs instead of nseg - 1 dependent ones.  One workgroup per row; the
+// two buffers of a row (work [C][2][nseg][D]) and the barrier between levels stay inside the workgroup.
+//   refine == 0:  v_j = ends[j - 1]                  state[j] = S_j        (ends[0] is the TRUE end of segment 0: it ran from the
+//                                                                           caller's state, so the states are the true ones)
+//   refine == 1:  v_j = ends[j - 1] - state[j]       state[j] += S_j       (ends = where the segments really end when started
+//                 from `state`: the residual of the first scan, scanned the same way -- the FFR step of the lane scan)
+// A non-finite end state makes every later state of its row non-finite in every component (each mat-vec adds all D products).
+// state[0] is never read or written: segment 0 starts from the caller's state.
+constexpr int SOS_HANDOFF_MAXD = 2 * SOS_HANDOFF_MAXK + 2;
+__global__ void __launch_bounds__(256) sos_handoff_scan_kernel(const double *__restrict__ ends, double *__restrict__ state,
+                                                               const double *__restrict__ pw, double *__restrict__ work,
+                                                               int nseg, int D, int nlev, int refine)
+{
+    __shared__ double Pk[SOS_HANDOFF_MAXD * SOS_HANDOFF_MAXD];
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int64_t row = blockIdx.x;
+    const int n = (nseg - 1) * D;                              // element (j, i) of the boundaries 1 ... nseg - 1 at (j - 1) * D + i
+    const double *e = ends + row * (int64_t)nseg * D;
+    double *st = state + row * (int64_t)nseg * D + D;          // boundary 1 first
+    double *a = work + row * 2 * (int64_t)nseg * D, *b = a + (int64_t)nseg * D;
+    for (int q = tid; q < n; q += nthr) a[q] = refine ? e[q] - st[q] : e[q];
+    for (int k = 0; k < nlev; ++k) {
+        __syncthreads();
+        for (int q = tid; q < D * D; q += nthr) Pk[q] = pw[(int64_t)k * D * D + q];
+        __syncthreads();
+        const int off = (1 << k) * D;
+        for (int q = tid; q < n; q += nthr) {
+            double v = a[q];
+            if (q >= off) {
+                const int i = q % D;
+                const double *src = a + (q - i - off), *pr = Pk + i * D;
+                double acc = 0.0;
+                for (int m = 0; m < D; ++m) acc = fma(pr[m], src[m], acc);
+                v += acc;
+            }
+            b[q] = v;
+        }
+        double *t = a; a = b; b = t;
+    }
+    __syncthreads();
+    for (int q = tid; q < n; q += nthr) st[q] = refine ? st[q] + a[q] : a[q];
+}
+
 // ------------------------------------------------------------------------------------------
 // Host side: tables and plan cache
 // ------------------------------------------------------------------------------------------
@@ -820,6 +886,14 @@ struct SosPlan {
     int unit_ok = -1;                    // the cascade has a unit-b0 form (lazy)
     int blocked_known[3] = {0, 0, 0};    // per LC = 16 / 32 / 64: the measured error of the unrefined float64 kernel and of the
     double blocked[3][3] = {};           // sequential float64 recursion, shares of the output scale (plan_blocked_error, lazy)
+    // hand-off route: P^(2^k), k < nlev, for P = A^L, the zero-input transition of the cascade over a segment of L samples --
+    // computed in long double, rounded to float64, [nlev][D][D] row-major; ok = every entry finite and below SOS_HANDOFF_PMAX.
+    // The device copy is made by the first launch that needs it (the route query needs none).  Lazy, per L (handoff_powers).
+    struct Handoff {
+        int nlev = 0; bool ok = false; std::vector<double> pw; std::unique_ptr<DeviceBuffer> buf;
+        int nlev_for(int64_t nseg) const { int n = 0; while (((int64_t)1 << n) < nseg - 1) ++n; return n; }      // <= nlev (handoff_powers)
+    };
+    std::map<int64_t, std::shared_ptr<Handoff>> handoff;
     std::vector<double> sos;
 };
 
@@ -897,6 +971,33 @@ static int64_t warmup_length(const std::vector<double> &sos, int K, int bits = 6
     int64_t W = n + 1;
     W += W / 8 + 8;                    // margin: the norm is not strictly monotone
     return W;
+}
+
+// Hand-off route: the powers P^(2^k), k < nlev, of P = A^L (L samples of zero input), in long double, rounded to float64 at
+// the end.  `ok` is false when an entry of any of them is not finite or reaches SOS_HANDOFF_PMAX: a cascade that is truly
+// unstable keeps today's plan.  Poles ON the unit circle are fine (an integrator's P is bounded, a double one's grows like L).
+static void handoff_power_table(const std::vector<double> &sos, int K, int64_t L, int nlev, std::vector<double> &out, bool &ok)
+{
+    const int D = 2 * K + 2;
+    std::vector<ld> A((size_t)D * D, 0.0L);
+    for (int j = 0; j < D; ++j) {
+        std::vector<ld> w(D, 0.0L);
+        w[j] = 1.0L;
+        cascade_step(sos, K, w);
+        for (int i = 0; i < D; ++i) A[(size_t)i * D + j] = w[i];
+    }
+    std::vector<ld> P;                       // A^L by squaring
+    for (std::vector<ld> sq = A; L > 0; L >>= 1) {
+        if (L & 1) P = P.empty() ? sq : matmul(P, sq, D);
+        if (L > 1) sq = matmul(sq, sq, D);
+    }
+    out.assign((size_t)nlev * D * D, 0.0);
+    ok = !P.empty();
+    for (int k = 0; k < nlev && ok; ++k) {
+        if (!(maxabs(P) < (ld)SOS_HANDOFF_PMAX)) { ok = false; break; }      // NaN-propagating
+        for (size_t i = 0; i < (size_t)D * D; ++i) out[(size_t)k * D * D + i] = (double)P[i];
+        if (k + 1 < nlev) P = matmul(P, P, D);
+    }
 }
 
 // Whether the cascade can run in the unit-b0 form: every b0 non-zero, not dwarfed by its section's other numerator
@@ -1336,35 +1437,9 @@ static int device_cus()
 // kernel actually launched.  Segments shorter than 8 x warm-up are not worth their halo.
 static void plan_segments(SosParams &p, int64_t plan_warm, int TILE, int resident_waves_per_cu)
 {
-    const int64_t tiles_total = ceil_div(p.T, TILE);
-    int64_t nseg = 1, seg_len = tiles_total * TILE, warm = 0;
-    const int force_nseg = (int)env_i64("TFX_SOS_NSEG", 0);
-    if (plan_warm >= 0) {
-        // halo rounded to 1 KB of float32: streams start on cache-line boundaries; 256 measured 1.5-4 % faster
-        // than 32 on the float64 kernel (64 x 2.88 M / 10 M / 28.8 M), no difference beyond
-        warm = (plan_warm + 255) & ~(int64_t)255;
-        const int64_t capacity = (int64_t)device_cus() * resident_waves_per_cu;
-        int64_t nseg_target = force_nseg > 0 ? force_nseg : capacity / p.C;      // floor: one round
-        if (nseg_target < 1) nseg_target = 1;
-        if (nseg_target > 1 && p.T > warm) {
-            // Every stream walks seg_tiles FULL tiles: stream g starts at g * stride, stride = seg_tiles * TILE - warm,
-            // and its first `warm` samples (g > 0) are the halo -- the halo is absorbed into the tile grid instead of
-            // costing every stream an extra, mostly discarded tile (+4 % at 64 x 2.88 M with 4096-sample tiles).
-            int64_t seg_tiles = ceil_div(ceil_div(p.T - warm, nseg_target) + warm, TILE);
-            if (force_nseg <= 0) {
-                const int64_t min_tiles = ceil_div(8 * warm, TILE);
-                if (seg_tiles < min_tiles) seg_tiles = min_tiles;
-            }
-            if (seg_tiles < 1) seg_tiles = 1;
-            const int64_t stride = seg_tiles * TILE - warm;
-            if (stride > 0) {
-                nseg = ceil_div(p.T - warm, stride);
-                seg_len = stride;
-            }
-        }
-        if (nseg <= 1) { nseg = 1; warm = 0; seg_len = tiles_total * TILE; }
-    }
-    p.nseg = (int)nseg; p.seg_len = seg_len; p.warm = warm;
+    const int64_t capacity = plan_warm >= 0 ? (int64_t)device_cus() * resident_waves_per_cu : 0;
+    const SosRoute r = sos_halo_plan(p.C, p.T, plan_warm, TILE, capacity, env_i64("TFX_SOS_NSEG", 0));      // the formula: sos_route.h
+    p.nseg = (int)r.nseg; p.seg_len = r.seg_len; p.warm = r.warm;
 }
 
 // Zero-phase passes: the segmentation must not depend on an occupancy query, because tfx_sos_filtfilt_plan_info reports it
@@ -1380,11 +1455,99 @@ static size_t ff_shmem(int K)
 }
 static int ff_blocks_per_cu(int K) { return 2 * ff_shmem(K) <= 160 * 1024 ? 2 : 1; }
 
+// ------------------------------------------------------------------------------------------
+// Hand-off route (sos_route.h): what runs in front of the result launch.
+// ------------------------------------------------------------------------------------------
+constexpr int HO_LC = 32;
+static_assert(64 * HO_LC == SOS_HANDOFF_QUANTUM, "hand-off segments are whole tiles of the end-state kernel");
+// the end-state kernel: refined lane scan exactly where the result kernel's is (an end state is a float64 result of the cascade)
+constexpr SosKernel ends_kernel(bool refine) { return {.LC = HO_LC, .FFR = refine, .ENDS = true}; }
+
+// what a forward call hands to launch_one for the route decision, and what it gets back
+struct SosRouting {
+    SosPlan *pl = nullptr;
+    bool eligible = false;        // the call may take the hand-off route (sos_forward_impl)
+    bool refine = false;          // plan_refine for the call's kernel geometry and result dtype
+    int64_t wave_slots = 0;       // > 0: given (the route query); 0: the device's, from the occupancy of the kernel launched
+    bool query = false;           // decide only: nothing is allocated or launched
+    SosRoute route;               // out
+};
+
+// P^(2^k) of the plan for segments of L samples, enough levels for nseg segments (lazy, a few L per plan)
+static std::shared_ptr<SosPlan::Handoff> handoff_powers(SosPlan *pl, int64_t L, int64_t nseg)
+{
+    int nlev = 0;
+    while (((int64_t)1 << nlev) < nseg - 1) ++nlev;
+    {
+        std::lock_guard<std::mutex> lk(g_plan_mu);
+        auto it = pl->handoff.find(L);
+        if (it != pl->handoff.end() && (it->second->nlev >= nlev || !it->second->ok)) return it->second;
+    }
+    // outside the lock, like the replays of plan_blocked_error: the coefficients never change, racing threads compute the same
+    auto h = std::make_shared<SosPlan::Handoff>();
+    h->nlev = nlev;
+    handoff_power_table(pl->sos, pl->K, L, nlev, h->pw, h->ok);
+    std::lock_guard<std::mutex> lk(g_plan_mu);
+    if (pl->handoff.size() >= 8) pl->handoff.clear();
+    pl->handoff[L] = h;
+    return h;
+}
+
+// The launches in front of the result pass; returns the per-stream start states [C * nseg, D] (slot 0 of a row is unused).
+// Everything goes to the caller's stream with scratch() buffers: no host synchronisation.
+template <typename TIn>
+static const double *handoff_states(const SosParams &p, SosPlan *pl, SosPlan::Handoff *ho, bool refine, hipStream_t stream)
+{
+    const int D = 2 * p.K + 2;
+    const int64_t nstreams = p.C * p.nseg;
+    TFX_CHECK(nstreams * D < ((int64_t)1 << 30) && p.C <= INT32_MAX, "sos_forward: %lld segments are too many for the hand-off route", (long long)nstreams);
+    {
+        std::lock_guard<std::mutex> lk(g_plan_mu);
+        if (!ho->buf && !ho->pw.empty()) ho->buf = std::make_unique<DeviceBuffer>(ho->pw);
+    }
+    const double *pw = ho->buf ? (const double *)ho->buf->p : nullptr;
+    const size_t bytes = (size_t)nstreams * D * sizeof(double);
+    double *ends = (double *)scratch("sos_ho_end", bytes, stream);
+    double *state = (double *)scratch("sos_ho_state", bytes, stream);
+    double *work = (double *)scratch("sos_ho_work", 2 * bytes, stream);
+    SosParams e = p;
+    e.y = nullptr; e.taps = nullptr; e.sx_out = nullptr; e.sy_out = nullptr;
+    e.ep_stat = -1; e.ep_partial = nullptr; e.nf_flag = nullptr; e.fair = 0; e.nt = 0;
+    e.ho_end = ends; e.ho_state = nullptr;
+    const size_t shmem = 4 * (size_t)sos_wave_lds_bytes<TIn, TIn, double, HO_LC>(1, p.K);
+    TFX_CHECK(shmem <= 160 * 1024, "sos_forward: K=%d needs %zu B of LDS on the hand-off route (max 163840)", p.K, shmem);
+    const auto ends_pass = [&](const char *name) {
+        const auto go = [&](auto kern) {
+            if (shmem > 64 * 1024) TFX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+            ProfScope ps(name, stream);
+            hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(nstreams, 4)), dim3(256), shmem, stream, e);
+            TFX_HIP(hipGetLastError());
+        };
+        table_for(e, pl, false, ends_kernel(refine));
+        if (refine) go(sos_stream_kernel<TIn, TIn, double, ends_kernel(true)>);
+        else go(sos_stream_kernel<TIn, TIn, double, ends_kernel(false)>);
+    };
+    const auto scan = [&](const char *name, int second) {
+        ProfScope ps(name, stream);
+        hipLaunchKernelGGL(sos_handoff_scan_kernel, dim3((unsigned)p.C), dim3(256), 0, stream, ends, state, pw, work, p.nseg, D, ho->nlev_for(p.nseg), second);
+        TFX_HIP(hipGetLastError());
+    };
+    ends_pass("sos_handoff_ends_kernel");
+    scan("sos_handoff_scan_kernel", 0);
+    if (refine) {
+        e.ho_state = state;
+        ends_pass("sos_handoff_refine_ends_kernel");
+        scan("sos_handoff_refine_scan_kernel", 1);
+    }
+    return state;
+}
+
 // The one launch of the cascade kernel: LDS size, segmentation, flag scratch, the launch and the repair launch behind it.
 // MEAS: the measuring pass arrives with its segmentation decided (block_energy_plan: nseg, warm, ms_bps; fair_nw = 2), so the
 // occupancy query and plan_segments are not for it.  `ep`: the Epilogue an EPI kernel serves (where its statistic goes).
+// `rt`: a forward call's routing (sos_route): the zero-phase passes have none and keep the halo plan.
 template <typename TIn, typename TOut, typename TC, SosKernel G>
-static void launch_one(SosParams p, const Epilogue *ep, int64_t plan_warm, hipStream_t stream)
+static void launch_one(SosParams p, const Epilogue *ep, int64_t plan_warm, hipStream_t stream, SosRouting *rt = nullptr)
 {
     constexpr int LC = G.LC, FF = G.FF;
     constexpr bool SUMB = G.SUMB, EPI = G.EPI, MEAS = G.MEAS;
@@ -1394,7 +1557,8 @@ static void launch_one(SosParams p, const Epilogue *ep, int64_t plan_warm, hipSt
     else TFX_CHECK(shmem <= 160 * 1024, "sos_forward: %d band(s) x K=%d need %zu B of LDS (max 163840)", nbl, p.K, shmem);
     auto kern = sos_stream_kernel<TIn, TOut, TC, G>;
     if (!EPI) p.ep_stat = -1;                      // the plain instantiation has no epilogue code
-    if (shmem > 64 * 1024)
+    const bool query = rt && rt->query;
+    if (shmem > 64 * 1024 && !query)
         TFX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     if constexpr (!MEAS) {
         static int blocks_per_cu_tab[TFX_MAX_DEVICES] = {0};     // per template instance and device
@@ -1412,13 +1576,31 @@ static void launch_one(SosParams p, const Epilogue *ep, int64_t plan_warm, hipSt
                 blocks_shmem = shmem;
             }
             blocks_per_cu = ff_blocks_per_cu(p.K);
-        } else if (!blocks_per_cu || blocks_shmem != shmem) {
+        } else if (!(rt && rt->wave_slots > 0) && (!blocks_per_cu || blocks_shmem != shmem)) {
             int nb = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, 256, shmem) != hipSuccess || nb < 1) nb = 1;
             blocks_per_cu = nb;
             blocks_shmem = shmem;
         }
-        plan_segments(p, plan_warm, 64 * LC, blocks_per_cu * 4);
+        if constexpr (FF != 0) plan_segments(p, plan_warm, 64 * LC, blocks_per_cu * 4);
+        else {
+            SosRouteQuery q;
+            q.C = p.C; q.T = p.T; q.plan_warm = plan_warm; q.K = p.K; q.tile = 64 * LC;
+            q.wave_slots = rt && rt->wave_slots > 0 ? rt->wave_slots : (int64_t)device_cus() * blocks_per_cu * 4;
+            q.force_nseg = env_i64("TFX_SOS_NSEG", 0);
+            q.handoff = (int)env_i64("TFX_SOS_HANDOFF", -1);
+            q.eligible = rt && rt->eligible; q.refine = rt && rt->refine;
+            SosRoute r = sos_route(q);
+            std::shared_ptr<SosPlan::Handoff> ho;
+            if (r.route == SOS_ROUTE_HANDOFF) {
+                ho = handoff_powers(rt->pl, r.seg_len, r.nseg);
+                if (!ho->ok) { q.eligible = false; r = sos_route(q); }      // P overflows: a truly unstable cascade keeps today's plan
+            }
+            p.nseg = (int)r.nseg; p.seg_len = r.seg_len; p.warm = r.warm;
+            if (rt) rt->route = r;
+            if (query) return;
+            if (r.route == SOS_ROUTE_HANDOFF) p.ho_state = handoff_states<TIn>(p, rt->pl, ho.get(), rt->refine, stream);
+        }
         p.fair_nw = blocks_per_cu < 2 ? 1 : (blocks_per_cu > 4 ? 4 : blocks_per_cu);      // one wave of every resident workgroup per SIMD
         if (p.fair_nw < 2) p.fair = 0;
     }
@@ -1523,9 +1705,9 @@ template <SosKernel... Gs> struct SosKernels {
         return !sos_any_choice(fam, [](SosKernel g) { return !has(g); }) && (sos_any_choice(fam, [](SosKernel g) { return g == Gs; }) && ...);
     }
     template <typename TIn, typename TOut, typename TC>
-    static void launch(SosKernel g, const SosParams &p, const Epilogue *ep, int64_t plan_warm, hipStream_t stream)
+    static void launch(SosKernel g, const SosParams &p, const Epilogue *ep, int64_t plan_warm, hipStream_t stream, SosRouting *rt = nullptr)
     {
-        const bool found = ((g == Gs && (launch_one<TIn, TOut, TC, Gs>(p, ep, plan_warm, stream), true)) || ...);
+        const bool found = ((g == Gs && (launch_one<TIn, TOut, TC, Gs>(p, ep, plan_warm, stream, rt), true)) || ...);
         TFX_CHECK(found, "sos: no kernel instance LC=%d VEC=%d TAPS=%d PF=%d EPI=%d UNIT=%d FFR=%d", g.LC, g.VEC, g.TAPS, g.PF, g.EPI, g.UNIT, g.FFR);
     }
 };
@@ -1582,10 +1764,13 @@ static void check_sos(const char *op, const double *sos_host, int64_t K, bool re
 // rows; output rows (and state rows) are band-major: row = band * C_in + c.  C is the number of
 // INPUT rows.  sum_bands: the bands' outputs are accumulated into C_in output rows (`+`); the state
 // tensors keep the band-major [K, NB * C_in, 2] layout.
-void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in, int64_t T,
-                 const double *sos_host, int64_t K,
-                 const double *sx_in, const double *sy_in, double *sx_out, double *sy_out,
-                 void *y_sections, int precision, hipStream_t stream, int64_t NB, bool sum_bands, const Epilogue *ep)
+// `rq`: the route query (sos_route_info) -- the same checks and decisions, then launch_one decides the route and returns
+// before anything is allocated or launched; x and y are not looked at beyond their alignment (null = aligned).
+static void sos_forward_impl(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in, int64_t T,
+                             const double *sos_host, int64_t K,
+                             const double *sx_in, const double *sy_in, double *sx_out, double *sy_out,
+                             void *y_sections, int precision, hipStream_t stream, int64_t NB, bool sum_bands, const Epilogue *ep,
+                             SosRouting *rq)
 {
     Epilogue none;
     if (!ep) ep = &none;
@@ -1600,7 +1785,8 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in,
     TFX_CHECK(x_dtype == TFX_F32 || x_dtype == TFX_F64, "sos_forward: bad x dtype %d", x_dtype);
     TFX_CHECK(y_dtype == TFX_F32 || y_dtype == TFX_F64, "sos_forward: bad y dtype %d", y_dtype);
     if (C == 0) return;
-    TFX_CHECK((T == 0 || (x && y)) && (K == 0 || sos_host), "sos_forward: null signal or coefficient pointer");   // an empty tensor has no storage
+    if (rq && (T == 0 || K == 0)) return;          // nothing to segment: the query's default, one sequential pass
+    TFX_CHECK((T == 0 || (x && y) || rq) && (K == 0 || sos_host), "sos_forward: null signal or coefficient pointer");   // an empty tensor has no storage
     const size_t st_bytes = (size_t)K * C_in * NB * 2 * sizeof(double);   // [K, NB * C_in, 2] in every mode
     TFX_CHECK(!(sum_bands && K == 0), "sos_forward: sum mode needs at least one section");
     if (T == 0 || K == 0) {
@@ -1648,18 +1834,60 @@ void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in,
     // the epilogue runs in the kernels that have it; everything else runs the plain kernel and the same arithmetic as
     // separate passes over y
     if (G.EPI) { p.ep_gain = ep->gain; p.ep_scale = ep->scale; p.ep_clamp = ep->clamp; p.ep_stat = ep->stat_mode; }
-    table_for(p, pl, f32, G);
+    if (!rq) table_for(p, pl, f32, G);
 
-    const int64_t warm = pl->warm;         // segmentation is decided per kernel instance (launch_one)
-    if (fam == SosFamily::MainF32) SosMainKernels<true>::launch<float, float, float>(G, p, ep, warm, stream);
-    else if (fam == SosFamily::MainF64) SosMainF64Kernels::launch<float, float, double>(G, p, ep, warm, stream);
-    else if (fam == SosFamily::SumF32) SosSumKernels<>::launch<float, float, float>(G, p, ep, warm, stream);
-    else if (fam == SosFamily::SumF64 && x_dtype == TFX_F32) SosSumF64Kernels::launch<float, float, double>(G, p, ep, warm, stream);
-    else if (fam == SosFamily::SumF64) SosSumF64Kernels::launch<double, double, double>(G, p, ep, warm, stream);
-    else if (x_dtype == TFX_F32) SosRareKernels::launch<float, double, double>(G, p, ep, warm, stream);
-    else if (y_dtype == TFX_F32) SosRareKernels::launch<double, float, double>(G, p, ep, warm, stream);
-    else SosRareKernels::launch<double, double, double>(G, p, ep, warm, stream);
+    // The route (sos_route.h) is decided per kernel instance, in launch_one.  Hand-off serves the float64 arithmetic of one
+    // cascade of up to SOS_HANDOFF_MAXK sections, main and rare dtype families; float32 arithmetic, banks and the sum mode keep
+    // the halo plan (DESIGN.md 4.1.1 names them as follow-ups).
+    SosRouting own;
+    SosRouting *rt = rq ? rq : &own;
+    rt->pl = pl;
+    rt->eligible = !f32 && NB == 1 && !sum_bands && K <= SOS_HANDOFF_MAXK && (fam == SosFamily::MainF64 || fam == SosFamily::Rare);
+    rt->refine = refine;
+    const int64_t warm = pl->warm;
+    if (fam == SosFamily::MainF32) SosMainKernels<true>::launch<float, float, float>(G, p, ep, warm, stream, rt);
+    else if (fam == SosFamily::MainF64) SosMainF64Kernels::launch<float, float, double>(G, p, ep, warm, stream, rt);
+    else if (fam == SosFamily::SumF32) SosSumKernels<>::launch<float, float, float>(G, p, ep, warm, stream, rt);
+    else if (fam == SosFamily::SumF64 && x_dtype == TFX_F32) SosSumF64Kernels::launch<float, float, double>(G, p, ep, warm, stream, rt);
+    else if (fam == SosFamily::SumF64) SosSumF64Kernels::launch<double, double, double>(G, p, ep, warm, stream, rt);
+    else if (x_dtype == TFX_F32) SosRareKernels::launch<float, double, double>(G, p, ep, warm, stream, rt);
+    else if (y_dtype == TFX_F32) SosRareKernels::launch<double, float, double>(G, p, ep, warm, stream, rt);
+    else SosRareKernels::launch<double, double, double>(G, p, ep, warm, stream, rt);
+    if (rq) return;
     if (ep->any() && !G.EPI) epilogue_as_passes(y, y_dtype, C, T, *ep, stream);
+}
+
+void sos_forward(const void *x, int x_dtype, void *y, int y_dtype, int64_t C_in, int64_t T,
+                 const double *sos_host, int64_t K,
+                 const double *sx_in, const double *sy_in, double *sx_out, double *sy_out,
+                 void *y_sections, int precision, hipStream_t stream, int64_t NB, bool sum_bands, const Epilogue *ep)
+{
+    sos_forward_impl(x, x_dtype, y, y_dtype, C_in, T, sos_host, K, sx_in, sy_in, sx_out, sy_out, y_sections, precision, stream, NB,
+                     sum_bands, ep, nullptr);
+}
+
+// The route a forward call of [C, T] takes (sos_route.h), decided by the call's own code path.  `sections`: section taps are
+// asked for (they change the kernel, and with it the tile).  wave_slots > 0: the wavefronts the device is taken to hold -- no
+// device is asked anything; 0: the current device's, as the launch counts them.  Rows are taken as 16-byte aligned.
+// bytes_per_sample: signal traffic, one read per pass and one store (plus the section taps).
+void sos_route_info(int64_t C, int64_t T, const double *sos_host, int64_t K, int x_dtype, int y_dtype, int precision, int sections,
+                    int64_t wave_slots, int *route, int64_t *nseg, int64_t *seg_len, int64_t *warm, int *passes, double *bytes_per_sample)
+{
+    TFX_CHECK(wave_slots >= 0, "sos_route_info: negative wave_slots");
+    SosRouting rq;
+    rq.query = true;
+    rq.wave_slots = wave_slots;
+    rq.route.seg_len = T;
+    sos_forward_impl(nullptr, x_dtype, nullptr, y_dtype, C, T, sos_host, K, nullptr, nullptr, nullptr, nullptr,
+                     sections ? (void *)(uintptr_t)16 : nullptr /* asked for or not: never dereferenced */, precision, nullptr, 1, false, nullptr, &rq);
+    const SosRoute &r = rq.route;
+    if (route) *route = r.route;
+    if (nseg) *nseg = r.nseg;
+    if (seg_len) *seg_len = r.seg_len;
+    if (warm) *warm = r.warm;
+    if (passes) *passes = r.passes;
+    const int xsz = x_dtype == TFX_F64 ? 8 : 4, ysz = y_dtype == TFX_F64 ? 8 : 4;
+    if (bytes_per_sample) *bytes_per_sample = (double)r.passes * xsz + (double)ysz * (1 + (sections ? K : 0));
 }
 
 // ------------------------------------------------------------------------------------------

@@ -40,7 +40,7 @@ __all__ = [
     "modulated_delay_forward", "modulated_delay_stream_forward", "modulated_delay_plan_info", "freeverb_forward", "freeverb_plan_info",
     "waveshaper_stream_forward", "waveshaper_stream_plan_info", "phaser_forward", "phaser_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
-    "effects_plan_info", "deinterleave_forward", "interleave_forward", "sos_plan_info", "ols_plan_info", "prewarm",
+    "effects_plan_info", "deinterleave_forward", "interleave_forward", "sos_plan_info", "sos_route_info", "ols_plan_info", "prewarm",
 ]
 
 
@@ -780,6 +780,26 @@ def sos_plan_info(sos, refine: bool = True) -> dict:
     errs = r.pop("errs")
     q.update({k: bool(v) for k, v in r.items()})
     q.update(blocked_error=(errs[0], errs[2]), sequential_error=(errs[1], errs[3]))
+    return q
+
+
+SOS_ROUTES = ("sequential", "halo", "handoff")          # enum tfx_sos_route
+
+
+def sos_route_info(sos, rows: int, length: int, dtype: torch.dtype = torch.float32, out_dtype: torch.dtype | None = None,
+                   precision=None, sections: bool = False, wave_slots: int = 0) -> dict:
+    """How :func:`sos_forward` cuts ``rows`` rows of ``length`` samples into time segments (``tfx_sos_route_info``; the call's own
+    decision, host-only when ``wave_slots`` is given): ``route`` ("sequential", "halo" or "handoff" -- exact segment starts for
+    cascades whose memory is too long for a halo), ``nseg`` segments per row, ``seg_len`` samples between segment starts,
+    ``warmup`` (the halo in force; 0 unless "halo"), ``passes`` (reads of the signal) and ``bytes_per_sample``.
+    ``wave_slots``: the wavefronts the device is taken to hold (2048 on MI355X for the float64 kernels); 0 asks the current
+    device.  ``TFX_SOS_NSEG`` / ``TFX_SOS_HANDOFF`` act on the query as on the call."""
+    a = sos_array(sos)
+    q = _query(L.load().tfx_sos_route_info,
+               (int(rows), int(length), a.ctypes.data, a.shape[0], _dt(dtype), _dt(dtype if out_dtype is None else out_dtype),
+                L.precision_code(precision), int(bool(sections)), int(wave_slots)),
+               "route:int nseg seg_len warmup passes:int bytes_per_sample:double")
+    q["route"] = SOS_ROUTES[q["route"]]
     return q
 
 

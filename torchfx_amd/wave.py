@@ -584,7 +584,9 @@ class Wave:
         """One line per step of :meth:`plan` for THIS tensor: the step, the route it will take (``CascadeFIR``: the fused
         recursion-in-pass-A pipeline or the staged pair of launches) and why."""
         from torchfx_amd.effect import Compressor, Delay, Epilogued, Freeverb, Limiter, LoudnessNormalize, ModulatedDelay, Phaser, Waveshaper
+        from torchfx_amd.filter.biquad import Biquad
         from torchfx_amd.filter.fused import CascadeFIR, FusedSOSCascade
+        from torchfx_amd.filter.iir import IIR
         from torchfx_amd.filter.zerophase import ZeroPhase
         from torchfx_amd.realtime import StatefulDelay, _native_stream
         from torchfx_amd.resample import Resample
@@ -612,8 +614,29 @@ class Wave:
                 length = inner.output_length(length)
             elif isinstance(inner, (ZeroPhase, LoudnessNormalize, Limiter, Compressor, ModulatedDelay, Waveshaper, Phaser)):
                 line += ": " + inner.route(self._ys, length)
+            if isinstance(inner, (FusedSOSCascade, IIR, Biquad)):
+                route = Wave._cascade_route(inner, self._ys, length)
+                line += ((";" if ": " in line else ":") + route) if route else ""
             lines.append(line)
         return lines
+
+    @staticmethod
+    def _cascade_route(m, x: Tensor, length: int) -> str:
+        """How the cascade kernel cuts the rows of a device tensor into time segments for an IIR step (``sos_route_info``):
+        sequential, halo, or hand-off -- exact segment starts for filters whose memory is too long for a halo."""
+        from torchfx_amd import torchfx_ext
+        from torchfx_amd.filter._sos import CascadeTable
+
+        if not x.is_cuda or x.dtype not in (torch.float32, torch.float64) or length < 1 or x.dim() < 1:
+            return ""
+        try:
+            sos = CascadeTable.of(m)
+        except (TypeError, ValueError):       # not designed yet and no sample rate to design it for
+            return ""
+        with torch.cuda.device(x.device):
+            r = torchfx_ext.sos_route_info(sos, max(1, x.numel() // length), length, x.dtype)
+        cut = "one wavefront per row" if r["nseg"] == 1 else f"{r['nseg']} segments of {r['seg_len']} samples per row"
+        return f" cascade {r['route']} ({cut}, {r['passes']} pass{'es' if r['passes'] > 1 else ''} over the signal)"
 
     @staticmethod
     def _delay_route(d, x: Tensor, fs) -> str:
