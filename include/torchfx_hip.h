@@ -827,6 +827,44 @@ int tfx_phaser_plan_info(int64_t rows, int64_t channels, int64_t T, int64_t stag
                          int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes);
 
 /* ---------------------------------------------------------------------------
+ * tfx_gate_forward -- noise gate with hysteresis, hold and range.  x is [groups, channels, T]; the `channels` rows of a group
+ * share one gain curve.  All levels are linear and come from the caller, so that every implementation compares against the
+ * same doubles: p_open = 10^(threshold_db / 20), p_close = 10^((threshold_db - hysteresis_db) / 20) <= p_open, range = r =
+ * 10^(-range_db / 20) in [0, 1] (0 for an infinite range), hold = H = floor(hold_seconds * fs + 0.5) samples in [0, 2^31),
+ * alpha_a / alpha_r = exp(-1 / (time * fs)) in [0, 1] (0 for a time of 0); the kernel takes bA = 1 - alpha_a and
+ * bR = (1 - alpha_r) * r.  The detector runs in float64 for both signal dtypes, for a group and a sample n:
+ *   1. p[n] = max_ch |x[ch,n]|; the max propagates NaN
+ *   2. the state (open, c) starts from state_in[group] or (closed, 0):
+ *        if p >= p_open: open = 1, c = 0;  else if open and p >= p_close: c = 0;
+ *        else if open: c += 1, and if c > H then open = 0, c = 0;  else: stays closed.   open[n] is the value after sample n
+ *   3. g[n] = alpha_a g[n-1] + bA where open[n], else alpha_r g[n-1] + bR;  g[-1] = state_in[group][0] or r
+ *   4. y[ch,n] = dtype(g[n] x[ch,n]);  gain[n] = dtype(g[n])
+ *   5. a non-finite p[n] (NaN or Inf) poisons its group: from that sample to the end of its rows y, gain and the end state are
+ *      NaN and open is 0; earlier samples and other groups are untouched.  A non-finite state_in poisons from sample 0.
+ * x, y DEVICE [groups, channels, T] of dtype (y may alias x); gain DEVICE [groups, T] of dtype or null; open DEVICE [groups, T]
+ * bytes (0 / 1) or null; state_in / state_out DEVICE [groups, 3] float64 (g, open, c) or null (start state in / no state out);
+ * state_out is the triple at T - 1, with c = 0 whenever closed, and needs its own buffer.
+ * Both recursions are associative scans (the decision over summaries (S0, S1, L, allquiet) of a run, the gain over affine maps
+ * with the coefficient product carried), so a group's row is cut into tiles of 2048 samples and the tiles into `segments` runs
+ * (tfx_gate_plan_info; 0 = chosen from groups and T, any other value is clamped to the tile count).  segments == 1 is one
+ * launch that reads x once and writes y once; otherwise three launches (decision summaries, gain summaries, result): x is read
+ * three times and `scratch` -- DEVICE, scratch_bytes of the plan, may be null for one segment -- carries the summaries across
+ * the launch boundaries.  No workgroup waits for another, no atomics.  The open track and the (open, c) of the end state are
+ * the per-sample loop's bit for bit under any tiling and any `segments`; the gain follows the association of the scan: results
+ * for different `segments` agree to float64 round-off, within 8 * 2^-53 * min(T, 1 / (1 - max(alpha_a, alpha_r))) of the
+ * exact recursion.  With alpha_a = alpha_r = 0 the gain is exactly 1 or r.  A group's bits depend on (T, segments) and its own
+ * samples alone.  Arguments are checked before the device is touched.  T == 0 copies state_in (or the start state) to state_out.
+ * ------------------------------------------------------------------------- */
+int tfx_gate_forward(const void *x, void *y, void *gain_or_null, unsigned char *open_or_null, int dtype, int64_t groups,
+                     int64_t channels, int64_t T, double p_open, double p_close, double range, int64_t hold, double alpha_a,
+                     double alpha_r, const double *state_in, double *state_out, int64_t segments, void *scratch, tfx_stream_t stream);
+/* what tfx_gate_forward does (host-only, same checks on the sizes): samples per tile (2048), tiles per group, the segments it
+ * takes for the request `segments`, the tiles of the longest segment (the first tiles mod segments hold one more than the rest)
+ * and the bytes of `scratch` (0 for one segment) */
+int tfx_gate_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t segments, int64_t *tile, int64_t *tiles,
+                       int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes);
+
+/* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of
  * ParallelFilterCombination.forward, src/torchfx/filter/__base.py:1019-1026).
  * xs_host: HOST array of n DEVICE pointers, each [numel] of dtype.

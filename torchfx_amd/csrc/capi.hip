@@ -826,6 +826,25 @@ int tfx_phaser_plan_info(int64_t rows, int64_t channels, int64_t T, int64_t stag
     TFX_API_END
 }
 
+int tfx_gate_forward(const void *x, void *y, void *gain_or_null, unsigned char *open_or_null, int dtype, int64_t groups,
+                     int64_t channels, int64_t T, double p_open, double p_close, double range, int64_t hold, double alpha_a,
+                     double alpha_r, const double *state_in, double *state_out, int64_t segments, void *scratch, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    gate_forward(x, y, gain_or_null, open_or_null, dtype, groups, channels, T, p_open, p_close, range, hold, alpha_a, alpha_r, state_in,
+                 state_out, segments, scratch, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_gate_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t segments, int64_t *tile, int64_t *tiles,
+                       int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(tile && tiles && segments_out && seg_tiles && scratch_bytes, "gate_plan_info: null output");
+    gate_plan_info(groups, channels, T, segments, tile, tiles, segments_out, seg_tiles, scratch_bytes);
+    TFX_API_END
+}
+
 int tfx_sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, tfx_stream_t stream)
 {
     TFX_API_BEGIN

@@ -613,6 +613,40 @@ std::tuple<Tensor, Tensor, Tensor> compressor_op(const Tensor &x_in, double th, 
     return std::make_tuple(y, gain, sout);
 }
 
+// Noise gate (tfx_gate_forward): x [..., T], its rows in groups of `channels` consecutive rows that share one gain curve; p_open,
+// p_close, range (linear), hold (samples), alpha_a, alpha_r as the C entry takes them; state [groups, 3] float64 (g, open, c) or
+// None (closed, g = range); segments 0 = the plan's choice -> (y like x, gain [groups, T] or an empty tensor, open [groups, T]
+// uint8 or an empty tensor, new state [groups, 3] float64).  The summaries between the launches live in a tensor from torch's
+// allocator.
+std::tuple<Tensor, Tensor, Tensor, Tensor> gate_op(const Tensor &x_in, double p_open, double p_close, double range, int64_t hold,
+                                                   double alpha_a, double alpha_r, int64_t channels, const OptTensor &state,
+                                                   bool return_gain, bool return_open, int64_t segments)
+{
+    const char *what = "gate_forward";
+    need_device(x_in, "x");
+    TORCH_CHECK(x_in.dim() >= 1, what, ": x must have a time dimension");
+    const Tensor x = x_in.contiguous();
+    const int dt = dtype_code(x, what);
+    const int64_t T = x.size(-1), rows = stream_rows(x);
+    TORCH_CHECK(channels >= 1 && rows % channels == 0, what, ": ", rows, " rows do not split into groups of ", channels);
+    const int64_t groups = rows / channels;
+    int64_t info[5];
+    check_rc(tfx_gate_plan_info(groups, channels, T, segments, info, info + 1, info + 2, info + 3, info + 4), what);
+    Tensor keep;
+    const double *sin = state_ptr(state, {groups, 3}, x, "gate_forward: state", keep);
+    const auto f64 = x.options().dtype(at::kDouble), u8 = x.options().dtype(at::kByte);
+    Tensor y = at::empty_like(x), sout = at::empty({groups, 3}, f64), scratch = at::empty({info[4] / 8}, f64);
+    Tensor gain = return_gain ? at::empty({groups, T}, x.options()) : at::empty({0}, x.options());
+    Tensor open = return_open ? at::empty({groups, T}, u8) : at::empty({0}, u8);
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_gate_forward(x.data_ptr(), y.data_ptr(), return_gain ? gain.data_ptr() : nullptr,
+                              return_open ? open.data_ptr<uint8_t>() : nullptr, dt, groups, channels, T, p_open, p_close, range, hold,
+                              alpha_a, alpha_r, sin, sout.data_ptr<double>(), segments, info[4] ? scratch.data_ptr() : nullptr,
+                              stream_of(x)),
+             what);
+    return std::make_tuple(y, gain, open, sout);
+}
+
 // Freeverb (tfx_freeverb_forward): x [T], [C, T] or [B, C, T] with C 1 or 2; comb_delays / allpass_delays the flattened
 // [C, NC] / [C, NA] tables in samples; state [B * C, state_len] float64 or None (silence) -> (y [..., T + tail], new state).
 // The shape and the tables are checked here and by the plan, before anything touches the device; the workspace (global lines,
@@ -1272,6 +1306,16 @@ std::tuple<Tensor, Tensor, Tensor> compressor_meta(const Tensor &x, double, doub
             at::empty({groups, 2}, x.options().dtype(at::kDouble))};
 }
 
+std::tuple<Tensor, Tensor, Tensor, Tensor> gate_meta(const Tensor &x, double, double, double, int64_t, double, double, int64_t channels,
+                                                     const OptTensor &, bool return_gain, bool return_open, int64_t)
+{
+    TORCH_CHECK(x.dim() >= 1 && channels >= 1, "gate_forward: bad shape");
+    const int64_t T = x.size(-1), groups = stream_rows(x) / channels;
+    const auto u8 = x.options().dtype(at::kByte);
+    return {at::empty_like(x), return_gain ? at::empty({groups, T}, x.options()) : at::empty({0}, x.options()),
+            return_open ? at::empty({groups, T}, u8) : at::empty({0}, u8), at::empty({groups, 3}, x.options().dtype(at::kDouble))};
+}
+
 std::tuple<Tensor, Tensor, Tensor> modulated_delay_stream_meta(const Tensor &x, const OptTensor &, const OptTensor &, const Tensor &voices,
                                                                double, double, int64_t, int64_t)
 {
@@ -1450,6 +1494,18 @@ TORCH_LIBRARY(torchfx_phaser, m)
 TORCH_LIBRARY_IMPL(torchfx_phaser, Meta, m)
 {
     m.impl("phaser_forward", phaser_meta);
+}
+
+// The gate likewise: torch.ops.torchfx_gate.
+TORCH_LIBRARY(torchfx_gate, m)
+{
+    reg_op(m, "gate_forward(Tensor x, float p_open, float p_close, float range, int hold, float alpha_a, float alpha_r, int channels, "
+              "Tensor? state, bool return_gain, bool return_open, int segments=0) -> (Tensor, Tensor, Tensor, Tensor)", gate_op);
+}
+
+TORCH_LIBRARY_IMPL(torchfx_gate, Meta, m)
+{
+    m.impl("gate_forward", gate_meta);
 }
 
 // The waveshaper likewise: torch.ops.torchfx_shaper.

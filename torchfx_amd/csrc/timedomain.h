@@ -1,5 +1,5 @@
 // timedomain.h -- the host entry points of the time-domain and elementwise ops, one prototype per exported function of fir.hip,
-// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip, compressor.hip, modulation.hip, reverb.hip, waveshaper.hip, phaser.hip and layout.hip (the cascade's: sos.h; the
+// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip, compressor.hip, modulation.hip, reverb.hip, waveshaper.hip, phaser.hip, gate.hip and layout.hip (the cascade's: sos.h; the
 // overlap-save pipelines': ols_route.h).  Included by the file that defines each function and by capi.hip, so a prototype that drifts from
 // its definition does not compile; default arguments live here and nowhere else.  Every *_forward checks its arguments before
 // anything touches the device; a *_plan_info takes the same checking path without the pointers.
@@ -141,6 +141,13 @@ void phaser_forward(const void *x, void *y, double *coef, int dtype, int64_t row
                     int64_t segments, void *scratch, hipStream_t stream);
 void phaser_plan_info(int64_t rows, int64_t channels, int64_t T, int64_t stages, int64_t segments, int64_t *tile, int64_t *tiles,
                       int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes);
+
+// ---- gate.hip ----
+void gate_forward(const void *x, void *y, void *gain, unsigned char *open, int dtype, int64_t groups, int64_t channels, int64_t T,
+                  double p_open, double p_close, double range, int64_t hold, double alpha_a, double alpha_r, const double *state_in,
+                  double *state_out, int64_t segments, void *scratch, hipStream_t stream);
+void gate_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t segments, int64_t *tile, int64_t *tiles,
+                    int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes);
 
 // ---- layout.hip ----
 void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, int64_t C, int64_t ld_out, int64_t f_base,

@@ -158,8 +158,8 @@ def compress(x: Tensor, fs: int, threshold_db: float = -20.0, ratio: float = 4.0
     * **Non-finite input.**  From the first NaN / Inf sample of a group to the end of its rows every output, the gain and the
       end state of that group are NaN; earlier samples and other groups are unaffected.
 
-    RMS, feedback and branching detectors, a side-chain input, automatic make-up gain, look-ahead, expansion and gating,
-    autograd and axes other than the last are not provided.  An empty ``T`` returns an empty tensor and the state unchanged.
+    RMS, feedback and branching detectors, a side-chain input, automatic make-up gain, look-ahead, downward expansion (gating
+    is :func:`torchfx_amd.gate.gate`), autograd and axes other than the last are not provided.  An empty ``T`` returns an empty tensor and the state unchanged.
     ``ValueError`` / ``TypeError`` for ``ratio < 1`` or NaN, a negative or non-finite time, ``knee_db < 0``, a non-finite level,
     a non-float dtype and a state of the wrong shape."""
     _check_signal(x, "compress")

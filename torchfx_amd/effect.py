@@ -357,6 +357,66 @@ class Compressor(FX):
                 f"knee_db={self.knee_db}, makeup_db={self.makeup_db}, link={self.link}, fs={self.fs}")
 
 
+class Gate(FX):
+    """Noise gate: :func:`torchfx_amd.gate.gate` with the same parameters -- ``threshold_db`` (the gate opens at or above it),
+    ``hysteresis_db`` (it closes that far below), ``range_db`` (the closed gate's attenuation, ``inf`` for silence), ``attack``,
+    ``hold`` and ``release`` in seconds and ``link`` (one gain curve per ``[C, T]`` signal or batch item).
+    ``wave | Gate(-45) | Compressor(-18, 3) | Limiter(-1.0)`` is the practical chain: the gate goes first, so that no make-up
+    gain lifts what lies between the phrases.
+
+    The detector is the sample peak in float64 for both signal dtypes; the gain is causal with no latency.  ``fs`` comes from
+    the ``Wave`` the effect is piped into when it is None.  Every call starts closed with its hold counter at zero: the gate is
+    a step of its own in ``Wave.plan()`` and a chunked stream needs :class:`torchfx_amd.realtime.StatefulGate`, which carries
+    the gain, the decision and the counter from chunk to chunk."""
+
+    def __init__(self, threshold_db: float = -40.0, hysteresis_db: float = 6.0, range_db: float = math.inf, attack: float = 1e-3,
+                 hold: float = 50e-3, release: float = 100e-3, link: bool = True, fs: int | None = None) -> None:
+        super().__init__()
+        from torchfx_amd.gate import GateParams
+
+        GateParams(48000 if fs is None else fs, torch.float32, threshold_db, hysteresis_db, range_db, attack, hold, release)   # argument errors now
+        self.threshold_db, self.hysteresis_db, self.range_db = float(threshold_db), float(hysteresis_db), float(range_db)
+        self.attack, self.hold, self.release, self.link, self.fs = float(attack), float(hold), float(release), bool(link), fs
+
+    def params(self, dtype: torch.dtype):
+        """The call's :class:`torchfx_amd.gate.GateParams` for a signal of ``dtype`` at ``self.fs``."""
+        if self.fs is None:
+            raise ValueError("Gate needs the sample rate: pass fs or pipe a Wave into it (wave | Gate())")
+        from torchfx_amd.gate import GateParams
+
+        return GateParams(self.fs, dtype, self.threshold_db, self.hysteresis_db, self.range_db, self.attack, self.hold, self.release)
+
+    def route(self, x: Tensor, length: int | None = None) -> str:
+        """``native (...)`` or ``numpy on host -- <reason>`` for ``x`` (rows of ``length`` samples, default x's)."""
+        if not x.is_cuda:
+            return f"numpy on host -- {x.device.type} tensor"
+        try:
+            P = self.params(x.dtype)
+            from torchfx_amd.limiter import _grouping
+
+            n = int(x.shape[-1]) if length is None else int(length)
+            groups, channels = _grouping(x, self.link)
+            info = _ext().gate_plan_info(n, groups, channels)
+        except (RuntimeError, ValueError, TypeError) as e:
+            return f"refused -- {e}"
+        launches = "one launch" if info["segments"] == 1 else "three launches"
+        return (f"native (gate_kernel, hysteresis decision and gain smoother as scans, hold H = {P.H} samples, {info['tiles']} tile(s) "
+                f"of {info['tile']} per group in {info['segments']} segment(s); {launches})")
+
+    @torch.no_grad()
+    def forward(self, waveform: Tensor) -> Tensor:
+        if self.fs is None:
+            raise ValueError("Gate needs the sample rate: pass fs or pipe a Wave into it (wave | Gate())")
+        from torchfx_amd.gate import gate
+
+        return gate(waveform, self.fs, self.threshold_db, self.hysteresis_db, self.range_db, self.attack, self.hold, self.release,
+                    self.link)
+
+    def extra_repr(self) -> str:
+        return (f"threshold_db={self.threshold_db}, hysteresis_db={self.hysteresis_db}, range_db={self.range_db}, "
+                f"attack={self.attack}, hold={self.hold}, release={self.release}, link={self.link}, fs={self.fs}")
+
+
 class ModulatedDelay(FX):
     """The modulated delay line as an effect: :func:`torchfx_amd.modulation.modulated_delay` with a voice table given in
     seconds.  ``voices`` holds 1 to 8 rows ``(delay, depth, rate, phase, gain)``: delay and depth in seconds, rate in Hz, phase

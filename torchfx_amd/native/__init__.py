@@ -111,3 +111,11 @@ def phaser_ops():
 
     load()
     return torch.ops.torchfx_phaser
+
+
+def gate_ops():
+    """``torch.ops.torchfx_gate`` (the gate's namespace, registered by the same module) with the library loaded."""
+    import torch
+
+    load()
+    return torch.ops.torchfx_gate

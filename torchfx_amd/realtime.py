@@ -20,7 +20,9 @@ every row, returns the outputs each chunk completes (``tfx_resample_stream_forwa
 (``tfx_limiter_stream_forward``, one launch per chunk), and its chunks plus ``flush()`` are ``limit`` on the whole signal;
 ``aligned=False`` gives the constant-latency form a sound card needs.  :class:`StatefulCompressor` is the compressor of a
 stream: causal, no latency, it carries the detector's ``(y1, yL)`` per group (``tfx_compressor_forward``'s state), and its chunks
-equal ``compress`` on the whole signal to float64 round-off of the detector (not bit for bit).  :class:`StatefulChorus`,
+equal ``compress`` on the whole signal to float64 round-off of the detector (not bit for bit).  :class:`StatefulGate` is the noise
+gate of a stream: causal, no latency, it carries ``(g, open, c)`` per group (``tfx_gate_forward``'s state); its decision is the
+one-shot call's bit for bit and its gain equals it to float64 round-off.  :class:`StatefulChorus`,
 :class:`StatefulFlanger` and :class:`StatefulVibrato` are the modulation effects of a stream: causal, no latency, they carry the
 delay line's reach in ``_hist`` and the LFO's position in ``_pos`` (a device counter, ``tfx_modulated_delay_stream_forward``), and
 their chunks are bit-identical to the one-shot effect on the whole signal.  :class:`StatefulPhaser` is the phaser of a stream:
@@ -54,7 +56,7 @@ from collections.abc import Generator, Sequence
 import torch
 from torch import Tensor, nn
 
-from torchfx_amd.effect import (FX, Chorus, Compressor, Delay, Distortion, Flanger, Freeverb, Limiter, LoudnessNormalize, ModulatedDelay,
+from torchfx_amd.effect import (FX, Chorus, Compressor, Delay, Distortion, Flanger, Freeverb, Gate, Limiter, LoudnessNormalize, ModulatedDelay,
                                 MonoDelayStrategy, Phaser, PingPongDelayStrategy, Reverb, Vibrato, Waveshaper, _ext)
 from torchfx_amd.filter._base import AbstractFilter
 from torchfx_amd.filter.fir import FIR
@@ -645,6 +647,50 @@ class StatefulCompressor(Compressor):
         return y
 
 
+class StatefulGate(Gate):
+    """:class:`~torchfx_amd.effect.Gate` over a continuous stream: the state ``(g, open, c)`` per group -- the smoothed gain, the
+    decision and the hold counter -- goes from chunk to chunk, so neither the gain curve nor the hold has a seam.  The gate is
+    causal with no latency: every chunk returns the chunk's shape and there is nothing to flush.
+
+    The state lives in ``_hist`` (``[groups, 3]`` float64 on the chunks' device) and is rebuilt from the closed gate when the
+    row count, the ``link`` grouping or the device changes; :meth:`reset_state` does the same on request.  A changed parameter
+    applies from the next chunk on.  The decision of all chunks together is :func:`~torchfx_amd.gate.gate`'s on the whole
+    signal bit for bit; the gain equals it to float64 round-off (the scan's association follows the cut).  After a NaN or Inf
+    the state of its group is NaN and stays so until :meth:`reset_state`.  Device float32 / float64 chunks run
+    :func:`torchfx_ext.gate_forward` (one launch for a chunk of up to 2048 samples), CPU chunks the host path."""
+
+    def __init__(self, threshold_db: float = -40.0, hysteresis_db: float = 6.0, range_db: float = math.inf, attack: float = 1e-3,
+                 hold: float = 50e-3, release: float = 100e-3, link: bool = True, fs: int | None = None) -> None:
+        super().__init__(threshold_db, hysteresis_db, range_db, attack, hold, release, link, fs)
+        self.reset_state()
+
+    def reset_state(self) -> None:
+        self._hist: Tensor | None = None            # [groups, 3] float64 (g, open, c); None = closed, g = r
+        self._key: tuple | None = None              # what the running stream is bound to
+
+    def _capture_key(self) -> tuple:
+        """What a captured HIP graph of this effect bakes in."""
+        return (self.threshold_db, self.hysteresis_db, self.range_db, self.attack, self.hold, self.release, self.link, self.fs)
+
+    def _sync_history(self) -> None:
+        """Nothing to resize: the state's shape follows the rows alone."""
+
+    @torch.no_grad()
+    def forward(self, x: Tensor) -> Tensor:
+        _rows(x)
+        if self.fs is None:
+            raise ValueError("StatefulGate needs the sample rate: pass fs or let the processor configure it")
+        from torchfx_amd.gate import gate
+
+        key = (tuple(x.shape[:-1]), self.link, x.device)
+        if key != self._key:                        # a new stream: from the closed gate
+            self.reset_state()
+            self._key = key
+        y, self._hist = gate(x, self.fs, self.threshold_db, self.hysteresis_db, self.range_db, self.attack, self.hold, self.release,
+                             self.link, state=self._hist, return_state=True)
+        return y
+
+
 class StatefulFreeverb(_RingOut, Freeverb):
     """:class:`~torchfx_amd.effect.Freeverb` over a continuous stream: the delay lines go from chunk to chunk, so the room's
     tail has no seam.  The reverb is causal with no latency: every chunk returns the chunk's shape; with ``tail > 0``
@@ -976,6 +1022,11 @@ _REFUSALS = (
              nested=_TOP_LEVEL.format("StatefulWaveshaper / StatefulDistortion")),
     # RealtimeProcessor has no text of its own for a plain Resample: it meets this one in the StreamProcessor it runs its blocks through
     _Refusal(Resample, StatefulResample, _NO_RESAMPLE, nested=_NO_RESAMPLE, who="StreamProcessor"),
+    # new families go in here, in front of the phaser, which stays the table's last entry (tests/test_stream_phaser_host.py)
+    _Refusal(Gate, StatefulGate,
+             "Gate cannot run in {who}: every call starts closed with its hold counter at zero, so a chunked stream would shut the "
+             "gate at every chunk start; use StatefulGate(...) in its place, or gate the whole signal (wave | Gate(...)) before or "
+             "after streaming"),
     _Refusal(Phaser, StatefulPhaser,
              "Phaser cannot run in {who}: every call starts its sweep at position 0 and its all-pass sections from silence, so a "
              "chunked stream would restart the sweep and the filter states at every chunk start; use StatefulPhaser(...) in its "

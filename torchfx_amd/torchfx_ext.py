@@ -38,7 +38,7 @@ __all__ = [
     "sos_block_energy", "sos_block_energy_plan_info", "true_peak", "true_peak_plan_info", "limiter_forward", "limiter_plan_info",
     "limiter_stream_forward", "limiter_stream_plan_info", "compressor_forward", "compressor_plan_info",
     "modulated_delay_forward", "modulated_delay_stream_forward", "modulated_delay_plan_info", "freeverb_forward", "freeverb_plan_info",
-    "waveshaper_stream_forward", "waveshaper_stream_plan_info", "phaser_forward", "phaser_plan_info",
+    "waveshaper_stream_forward", "waveshaper_stream_plan_info", "phaser_forward", "phaser_plan_info", "gate_forward", "gate_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "effects_plan_info", "deinterleave_forward", "interleave_forward", "sos_plan_info", "sos_route_info", "ols_plan_info", "prewarm",
 ]
@@ -546,6 +546,32 @@ def phaser_plan_info(length: int, rows: int = 1, channels: int = 1, stages: int 
     ``rows`` and ``length``, 1 when the rows alone fill the chip), ``seg_tiles`` (tiles of the longest segment) and
     ``scratch_bytes`` (the summaries between the launches; 0 for one segment)."""
     return _query(L.load().tfx_phaser_plan_info, (int(rows), int(channels), int(length), int(stages), int(segments)),
+                  "tile tiles segments seg_tiles scratch_bytes")
+
+
+def gate_forward(x: Tensor, p_open: float, p_close: float, r: float, hold: int, alpha_a: float, alpha_r: float, channels: int = 1,
+                 state: Tensor | None = None, return_gain: bool = False, return_open: bool = False,
+                 segments: int = 0) -> tuple[Tensor, Tensor | None, Tensor | None, Tensor]:
+    """The noise gate (``tfx_gate_forward``; the definition is :func:`torchfx_amd.gate.gate`'s) with its parameters already
+    reduced: ``x [..., T]`` on the device (float32 / float64), its rows in groups of ``channels`` consecutive rows that share one
+    gain curve; ``p_open`` / ``p_close`` the linear opening and closing levels, ``r`` the linear gain of the closed gate,
+    ``hold`` in samples, ``alpha_a`` / ``alpha_r`` the smoother's coefficients ``exp(-1 / (time fs))`` (0 for a time of 0),
+    ``state [groups, 3]`` float64 ``(g, open, c)`` or None (closed, ``g = r``).  ``segments`` cuts a group's row for the scans
+    (0: the plan's choice; clamped to the tile count): one launch for one segment, three otherwise.  Returns ``(y, gain | None,
+    open | None, new state [groups, 3] float64)``.  The op lives in ``torch.ops.torchfx_gate``."""
+    native.ops()                                         # loads the library: every namespace is registered by the one module
+    y, g, o, st = native.gate_ops().gate_forward(x.contiguous(), float(p_open), float(p_close), float(r), int(hold), float(alpha_a),
+                                                 float(alpha_r), int(channels), state, bool(return_gain), bool(return_open),
+                                                 int(segments))
+    return y, (g if return_gain else None), (o if return_open else None), st
+
+
+def gate_plan_info(length: int, groups: int = 1, channels: int = 1, segments: int = 0) -> dict:
+    """What :func:`gate_forward` does for ``groups`` rows of ``length`` samples (``tfx_gate_plan_info``; host-only, same checks
+    on the sizes): ``tile`` (samples per tile), ``tiles`` per group, the ``segments`` it takes for the request (0: chosen from
+    ``groups`` and ``length``, 1 when the groups alone fill the chip), ``seg_tiles`` (tiles of the longest segment) and
+    ``scratch_bytes`` (the summaries between the launches; 0 for one segment)."""
+    return _query(L.load().tfx_gate_plan_info, (int(groups), int(channels), int(length), int(segments)),
                   "tile tiles segments seg_tiles scratch_bytes")
 
 

@@ -210,7 +210,7 @@ def plan_cache_clear() -> None:
 
 
 def _member_key(m: nn.Module, guard: list) -> tuple:
-    from torchfx_amd.effect import Compressor, Delay, Freeverb, Gain, Limiter, LoudnessNormalize, ModulatedDelay, Normalize, Phaser, Waveshaper
+    from torchfx_amd.effect import Compressor, Delay, Freeverb, Gain, Gate, Limiter, LoudnessNormalize, ModulatedDelay, Normalize, Phaser, Waveshaper
     from torchfx_amd.filter.zerophase import ZeroPhase
     from torchfx_amd.resample import Resample, window_key
 
@@ -242,6 +242,8 @@ def _member_key(m: nn.Module, guard: list) -> tuple:
         k += (m.ceiling_db, m.lookahead, m.hold, m.detector, m.link, m.oversample, id(m.taps), id(m.window), m.fs)
     elif isinstance(m, Compressor):
         k += (m.threshold_db, m.ratio, m.attack, m.release, m.knee_db, m.makeup_db, m.link, m.fs)
+    elif isinstance(m, Gate):
+        k += (m.threshold_db, m.hysteresis_db, m.range_db, m.attack, m.hold, m.release, m.link, m.fs)
     elif isinstance(m, ModulatedDelay):
         k += (tuple(m.voices), m.dry, m.spread, m.shape, m.interpolation, m.pad, m.fs)
     elif isinstance(m, Phaser):
@@ -341,16 +343,16 @@ class Wave:
         """A ``Resample`` is a barrier: the steps between two of them are planned on their own, at the row length they see,
         and nothing merges, folds or attaches an epilogue across one.  So is a ``ZeroPhase`` (its two passes are one step;
         the row length stays), a ``LoudnessNormalize`` (it measures exactly the signal the steps before it produce) and a
-        ``Limiter`` or a ``Compressor`` (their detectors read the samples the steps before them store).  A ``Freeverb`` is a step
+        ``Limiter``, a ``Compressor`` or a ``Gate`` (their detectors read the samples the steps before them store).  A ``Freeverb`` is a step
         of its own too (its workgroups own whole rows), and its ``tail`` lengthens the rows for the steps after it."""
-        from torchfx_amd.effect import Compressor, Freeverb, Limiter, LoudnessNormalize
+        from torchfx_amd.effect import Compressor, Freeverb, Gate, Limiter, LoudnessNormalize
         from torchfx_amd.filter.zerophase import ZeroPhase
         from torchfx_amd.resample import Resample
 
         plan: list[nn.Module] = []
         segment: list[nn.Module] = []
         for m in self._pipeline:
-            if isinstance(m, (Resample, ZeroPhase, LoudnessNormalize, Limiter, Compressor, Freeverb)):
+            if isinstance(m, (Resample, ZeroPhase, LoudnessNormalize, Limiter, Compressor, Gate, Freeverb)):
                 plan += self._build_segment(segment, length, dtype)
                 plan.append(m)
                 segment = []
@@ -583,7 +585,7 @@ class Wave:
     def explain(self) -> list[str]:
         """One line per step of :meth:`plan` for THIS tensor: the step, the route it will take (``CascadeFIR``: the fused
         recursion-in-pass-A pipeline or the staged pair of launches) and why."""
-        from torchfx_amd.effect import Compressor, Delay, Epilogued, Freeverb, Limiter, LoudnessNormalize, ModulatedDelay, Phaser, Waveshaper
+        from torchfx_amd.effect import Compressor, Delay, Epilogued, Freeverb, Gate, Limiter, LoudnessNormalize, ModulatedDelay, Phaser, Waveshaper
         from torchfx_amd.filter.biquad import Biquad
         from torchfx_amd.filter.fused import CascadeFIR, FusedSOSCascade
         from torchfx_amd.filter.iir import IIR
@@ -612,7 +614,7 @@ class Wave:
             elif isinstance(inner, (Resample, Freeverb)):
                 line += ": " + inner.route(self._ys, length)
                 length = inner.output_length(length)
-            elif isinstance(inner, (ZeroPhase, LoudnessNormalize, Limiter, Compressor, ModulatedDelay, Waveshaper, Phaser)):
+            elif isinstance(inner, (ZeroPhase, LoudnessNormalize, Limiter, Compressor, Gate, ModulatedDelay, Waveshaper, Phaser)):
                 line += ": " + inner.route(self._ys, length)
             if isinstance(inner, (FusedSOSCascade, IIR, Biquad)):
                 route = Wave._cascade_route(inner, self._ys, length)
