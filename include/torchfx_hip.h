@@ -865,6 +865,40 @@ int tfx_gate_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t segm
                        int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes);
 
 /* ---------------------------------------------------------------------------
+ * tfx_stft_forward -- short-time Fourier transform of every row of x [rows, T] (torch.stft's onesided result).  With
+ * M = n_fft / 2, frames = 1 + (T + 2 pad - n_fft) / hop and xp the row extended by `pad` samples at each end (reflected:
+ * xp[-i] = x[i], xp[T - 1 + i] = x[T - 1 - i], needs pad < T; or zeros), frame f and bin k <= M:
+ *   1. s[i] = dtype(w[i] * xp[f hop + i - pad]), i < n_fft: ONE rounded product per sample, in the signal's dtype; w is `window`
+ *      [win_length] centred in zeros ((n_fft - win_length) / 2 on the left), ones when window is null.  The product is always
+ *      formed, so a non-finite sample under a zero of the window is NaN, as in torch.
+ *   2. X[f, k] = sum_i s[i] exp(-2 pi i k i / n_fft), times n_fft^-1/2 when `normalized` (one more rounding per component)
+ *   3. out[row, f, k] = X (power 0: complex, interleaved re / im of dtype), |X| (power 1) or |X|^2 (power 2), of dtype, formed
+ *      in registers from the complex value: re * re + im * im, and its correctly rounded square root.
+ * x, window DEVICE; out DEVICE [rows, frames, M + 1], contiguous (torch.stft returns the transpose of the last two axes as a
+ * view of just this buffer).  One launch, x read once, nothing but out written: a workgroup stages the span of its
+ * frames_per_workgroup consecutive frames in LDS, the padding being part of that load's addressing.  Each frame is transformed
+ * on its own by threads_per_frame threads (an M-point complex transform of the even / odd samples and the real-input
+ * post-twiddle; all twiddles are tables computed in double and rounded once), so a frame's bits depend on its n_fft samples and
+ * the window alone: not on its index, its row, hop, its place in the workgroup or the batch.  A NaN sample makes exactly the
+ * frames that hold it (through the reflected edge too) non-finite in every bin; so does an Inf, and it turns into NaN on the way
+ * (Inf - Inf, Inf * 0).  Error: ||Xhat - X||_2 over a frame's bins <= 8 u (log2 n_fft + 2) sqrt(n_fft) ||s||_2, u = 2^-24 /
+ * 2^-53, X being the exact transform of the rounded s.
+ * Served: n_fft in {256, 512, 1024, 2048, 4096}, pad_mode constant or reflect (any pad_mode when pad == 0), 0 <= pad <= n_fft,
+ * hop >= 1, 1 <= win_length <= n_fft; anything else is refused (tfx_stft_plan_info says route 0: the caller takes torch.stft).
+ * Arguments are checked before the device is touched.
+ * ------------------------------------------------------------------------- */
+enum tfx_stft_pad { TFX_STFT_PAD_CONSTANT = 0, TFX_STFT_PAD_REFLECT = 1, TFX_STFT_PAD_REPLICATE = 2, TFX_STFT_PAD_CIRCULAR = 3 };
+int tfx_stft_forward(const void *x, const void *window_or_null, void *out, int dtype, int64_t rows, int64_t T, int64_t n_fft,
+                     int64_t hop, int64_t win_length, int64_t pad, int pad_mode, int power, int normalized, tfx_stream_t stream);
+/* what an STFT of this geometry does (host-only, same checks on the sizes; pad = n_fft / 2 when `center`): route (1: the LDS
+ * kernel, 0: not served -- another n_fft, a two-sided result, another pad_mode), frames per row and, for route 1, the frames
+ * and threads per frame of a workgroup, its LDS bytes and the workgroups of the launch (rows * ceil(frames / frames per
+ * workgroup); 0 for route 0) */
+int tfx_stft_plan_info(int64_t n_fft, int64_t hop, int64_t win_length, int64_t T, int64_t rows, int dtype, int center, int pad_mode,
+                       int onesided, int *route, int64_t *frames, int64_t *frames_per_workgroup, int64_t *threads_per_frame,
+                       int64_t *lds_bytes, int64_t *workgroups);
+
+/* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of
  * ParallelFilterCombination.forward, src/torchfx/filter/__base.py:1019-1026).
  * xs_host: HOST array of n DEVICE pointers, each [numel] of dtype.

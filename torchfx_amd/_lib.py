@@ -107,6 +107,8 @@ SIGNATURES = {
     "tfx_phaser_plan_info": (_int, [_i64, _i64, _i64, _i64, _i64] + [ctypes.POINTER(_i64)] * 5),
     "tfx_gate_forward": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _dbl, _dbl, _dbl, _i64, _dbl, _dbl, _vp, _vp, _i64, _vp, _vp]),
     "tfx_gate_plan_info": (_int, [_i64, _i64, _i64, _i64] + [ctypes.POINTER(_i64)] * 5),
+    "tfx_stft_forward": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _vp]),
+    "tfx_stft_plan_info": (_int, [_i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, ctypes.POINTER(_int)] + [ctypes.POINTER(_i64)] * 5),
     "tfx_sum_forward": (_int, [_vp, _int, _vp, _int, _i64, _vp]),
     "tfx_gain_forward": (_int, [_vp, _vp, _int, _i64, _dbl, _int, _vp]),
     "tfx_stat_forward": (_int, [_vp, _int, _i64, _i64, _int, _int, _vp, _vp]),

@@ -845,6 +845,25 @@ int tfx_gate_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t segm
     TFX_API_END
 }
 
+int tfx_stft_forward(const void *x, const void *window_or_null, void *out, int dtype, int64_t rows, int64_t T, int64_t n_fft,
+                     int64_t hop, int64_t win_length, int64_t pad, int pad_mode, int power, int normalized, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    stft_forward(x, window_or_null, out, dtype, rows, T, n_fft, hop, win_length, pad, pad_mode, power, normalized, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_stft_plan_info(int64_t n_fft, int64_t hop, int64_t win_length, int64_t T, int64_t rows, int dtype, int center, int pad_mode,
+                       int onesided, int *route, int64_t *frames, int64_t *frames_per_workgroup, int64_t *threads_per_frame,
+                       int64_t *lds_bytes, int64_t *workgroups)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(route && frames && frames_per_workgroup && threads_per_frame && lds_bytes && workgroups, "stft_plan_info: null output");
+    stft_plan_info(n_fft, hop, win_length, T, rows, dtype, center, pad_mode, onesided, route, frames, frames_per_workgroup,
+                   threads_per_frame, lds_bytes, workgroups);
+    TFX_API_END
+}
+
 int tfx_sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, tfx_stream_t stream)
 {
     TFX_API_BEGIN
@@ -964,6 +983,7 @@ int tfx_clear_caches(void)
     limiter_clear();
     modulation_clear();
     waveshaper_clear();
+    stft_clear();
     scratch_clear();
     TFX_API_END
 }

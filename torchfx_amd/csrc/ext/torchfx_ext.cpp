@@ -647,6 +647,55 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> gate_op(const Tensor &x_in, double p_
     return std::make_tuple(y, gain, open, sout);
 }
 
+// Short-time Fourier transform (tfx_stft_forward): x [..., T]; window a 1-D device tensor of x's dtype with 1 <= numel <= n_fft
+// (centred in zeros) or None (ones over n_fft); pad samples at each end, pad_mode a tfx_stft_pad; power 0 (complex), 1 or 2 ->
+// [..., n_fft / 2 + 1, frames], the transposed view of a contiguous [..., frames, n_fft / 2 + 1] buffer, as torch.stft returns it.
+struct StftShape {
+    std::vector<int64_t> sizes;     // [..., frames, bins]
+    at::ScalarType dtype;
+    int64_t win_length;
+};
+
+StftShape stft_shape(const Tensor &x, const OptTensor &window, int64_t n_fft, int64_t hop, int64_t pad, int64_t power, const char *what)
+{
+    TORCH_CHECK(x.dim() >= 1 && x.size(-1) >= 1, what, ": x must have a non-empty time dimension");
+    TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kDouble, what, ": expected a float32 or float64 tensor, got ",
+                x.scalar_type());
+    TORCH_CHECK(n_fft >= 2 && hop >= 1 && pad >= 0 && x.size(-1) + 2 * pad >= n_fft, what, ": bad geometry (n_fft ", n_fft, ", hop ", hop,
+                ", pad ", pad, ", T ", x.size(-1), ")");
+    TORCH_CHECK(power >= 0 && power <= 2, what, ": power must be 0 (complex), 1 or 2");
+    StftShape s;
+    s.win_length = n_fft;
+    if (window.has_value() && window->defined()) {
+        TORCH_CHECK(window->dim() == 1 && window->numel() >= 1 && window->numel() <= n_fft, what, ": window must be 1-D with 1 to n_fft values");
+        TORCH_CHECK(window->scalar_type() == x.scalar_type() && window->device() == x.device(), what, ": window must have x's dtype and device");
+        s.win_length = window->numel();
+    }
+    s.sizes.assign(x.sizes().begin(), x.sizes().end() - 1);
+    s.sizes.push_back(1 + (x.size(-1) + 2 * pad - n_fft) / hop);
+    s.sizes.push_back(n_fft / 2 + 1);
+    s.dtype = power != 0 ? x.scalar_type() : (x.scalar_type() == at::kFloat ? at::kComplexFloat : at::kComplexDouble);
+    return s;
+}
+
+Tensor stft_op(const Tensor &x_in, const OptTensor &window, int64_t n_fft, int64_t hop, int64_t pad, int64_t pad_mode, int64_t power,
+               bool normalized)
+{
+    const char *what = "stft_forward";
+    need_device(x_in, "x");
+    const StftShape s = stft_shape(x_in, window, n_fft, hop, pad, power, what);
+    const Tensor x = x_in.contiguous();
+    Tensor w;
+    if (window.has_value() && window->defined()) w = window->contiguous();
+    const int64_t T = x.size(-1), rows = stream_rows(x);
+    Tensor out = at::empty(s.sizes, x.options().dtype(s.dtype));
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_stft_forward(x.data_ptr(), w.defined() ? w.data_ptr() : nullptr, out.data_ptr(), dtype_code(x, what), rows, T, n_fft, hop,
+                              s.win_length, pad, (int)pad_mode, (int)power, normalized ? 1 : 0, stream_of(x)),
+             what);
+    return out.transpose(-1, -2);
+}
+
 // Freeverb (tfx_freeverb_forward): x [T], [C, T] or [B, C, T] with C 1 or 2; comb_delays / allpass_delays the flattened
 // [C, NC] / [C, NA] tables in samples; state [B * C, state_len] float64 or None (silence) -> (y [..., T + tail], new state).
 // The shape and the tables are checked here and by the plan, before anything touches the device; the workspace (global lines,
@@ -1316,6 +1365,12 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> gate_meta(const Tensor &x, double, do
             return_open ? at::empty({groups, T}, u8) : at::empty({0}, u8), at::empty({groups, 3}, x.options().dtype(at::kDouble))};
 }
 
+Tensor stft_meta(const Tensor &x, const OptTensor &window, int64_t n_fft, int64_t hop, int64_t pad, int64_t, int64_t power, bool)
+{
+    const StftShape s = stft_shape(x, window, n_fft, hop, pad, power, "stft_forward");
+    return at::empty(s.sizes, x.options().dtype(s.dtype)).transpose(-1, -2);
+}
+
 std::tuple<Tensor, Tensor, Tensor> modulated_delay_stream_meta(const Tensor &x, const OptTensor &, const OptTensor &, const Tensor &voices,
                                                                double, double, int64_t, int64_t)
 {
@@ -1506,6 +1561,18 @@ TORCH_LIBRARY(torchfx_gate, m)
 TORCH_LIBRARY_IMPL(torchfx_gate, Meta, m)
 {
     m.impl("gate_forward", gate_meta);
+}
+
+// The short-time Fourier transform likewise: torch.ops.torchfx_spectral.
+TORCH_LIBRARY(torchfx_spectral, m)
+{
+    reg_op(m, "stft_forward(Tensor x, Tensor? window, int n_fft, int hop, int pad, int pad_mode, int power, bool normalized) -> Tensor",
+           stft_op);
+}
+
+TORCH_LIBRARY_IMPL(torchfx_spectral, Meta, m)
+{
+    m.impl("stft_forward", stft_meta);
 }
 
 // The waveshaper likewise: torch.ops.torchfx_shaper.

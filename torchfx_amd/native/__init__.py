@@ -119,3 +119,11 @@ def gate_ops():
 
     load()
     return torch.ops.torchfx_gate
+
+
+def spectral_ops():
+    """``torch.ops.torchfx_spectral`` (the short-time Fourier transform's namespace, registered by the same module) with the library loaded."""
+    import torch
+
+    load()
+    return torch.ops.torchfx_spectral

@@ -39,6 +39,7 @@ __all__ = [
     "limiter_stream_forward", "limiter_stream_plan_info", "compressor_forward", "compressor_plan_info",
     "modulated_delay_forward", "modulated_delay_stream_forward", "modulated_delay_plan_info", "freeverb_forward", "freeverb_plan_info",
     "waveshaper_stream_forward", "waveshaper_stream_plan_info", "phaser_forward", "phaser_plan_info", "gate_forward", "gate_plan_info",
+    "stft_forward", "stft_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "effects_plan_info", "deinterleave_forward", "interleave_forward", "sos_plan_info", "sos_route_info", "ols_plan_info", "prewarm",
 ]
@@ -573,6 +574,42 @@ def gate_plan_info(length: int, groups: int = 1, channels: int = 1, segments: in
     ``scratch_bytes`` (the summaries between the launches; 0 for one segment)."""
     return _query(L.load().tfx_gate_plan_info, (int(groups), int(channels), int(length), int(segments)),
                   "tile tiles segments seg_tiles scratch_bytes")
+
+
+STFT_PAD_MODES = {"constant": 0, "reflect": 1, "replicate": 2, "circular": 3}      # enum tfx_stft_pad
+STFT_POWERS = {None: 0, 1.0: 1, 2.0: 2}                                            # complex, |X|, |X|^2
+
+
+def stft_forward(x: Tensor, window: Tensor | None, n_fft: int, hop: int, pad: int, pad_mode: str = "reflect",
+                 power: float | None = None, normalized: bool = False) -> Tensor:
+    """The short-time Fourier transform of the LDS route (``tfx_stft_forward``; the definition is
+    :func:`torchfx_amd.spectral.stft`'s): ``x [..., T]`` on the device (float32 / float64), ``window`` a 1-D device tensor of
+    ``x``'s dtype with 1 to ``n_fft`` values (centred in zeros) or None (ones), ``pad`` samples added at each end
+    (``n_fft // 2`` for ``center=True``, 0 without) by ``pad_mode`` ("reflect" / "constant"), ``power`` None (complex), 1.0 or 2.0.
+    Returns ``[..., n_fft // 2 + 1, frames]``, a transposed view of a contiguous ``[..., frames, bins]`` buffer.  A geometry
+    off the route (:func:`stft_plan_info`) is an error here, not a fall-back.  The op lives in ``torch.ops.torchfx_spectral``."""
+    native.ops()                                         # loads the library: every namespace is registered by the one module
+    if pad_mode not in STFT_PAD_MODES:
+        raise ValueError(f"stft_forward: pad_mode must be one of {sorted(STFT_PAD_MODES)}, got {pad_mode!r}")
+    if power not in STFT_POWERS:
+        raise ValueError(f"stft_forward: power must be None, 1.0 or 2.0, got {power!r}")
+    return native.spectral_ops().stft_forward(x, window, int(n_fft), int(hop), int(pad), STFT_PAD_MODES[pad_mode], STFT_POWERS[power],
+                                              bool(normalized))
+
+
+def stft_plan_info(n_fft: int, hop: int, win_length: int, length: int, rows: int = 1, dtype: torch.dtype = torch.float32,
+                   center: bool = True, pad_mode: str = "reflect", onesided: bool = True) -> dict:
+    """What an STFT of this geometry does (``tfx_stft_plan_info``; host-only, same checks on the sizes): ``route`` ("lds": the
+    one-launch kernel, "torch": ``torch.stft`` on the tensor's device), ``frames`` per row and, for the LDS route,
+    ``frames_per_workgroup``, ``threads_per_frame``, ``lds_bytes`` and ``workgroups`` (``rows * ceil(frames /
+    frames_per_workgroup)``; zeros on the torch route)."""
+    if pad_mode not in STFT_PAD_MODES:
+        raise ValueError(f"stft_plan_info: pad_mode must be one of {sorted(STFT_PAD_MODES)}, got {pad_mode!r}")
+    info = _query(L.load().tfx_stft_plan_info, (int(n_fft), int(hop), int(win_length), int(length), int(rows), _dt(dtype), int(bool(center)),
+                                                STFT_PAD_MODES[pad_mode], int(bool(onesided))),
+                  "route:int frames frames_per_workgroup threads_per_frame lds_bytes workgroups")
+    info["route"] = "lds" if info["route"] == 1 else "torch"
+    return info
 
 
 RESAMPLE_STREAM_KERNELS = ("resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel", "copy")

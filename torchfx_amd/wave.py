@@ -748,6 +748,23 @@ class Wave:
 
         return float(loudness_range(self.ys, self.fs, channel_weights))
 
+    def stft(self, n_fft: int, hop_length: int | None = None, win_length: int | None = None, window=None, center: bool = True,
+             pad_mode: str = "reflect", normalized: bool = False, onesided: bool = True) -> Tensor:
+        """Short-time Fourier transform of the (materialised) signal along time: a complex tensor ``[channels, bins, frames]``
+        with ``torch.stft``'s semantics (:func:`torchfx_amd.spectral.stft`).  An analysis, not an effect: the result is a
+        tensor, not a ``Wave``."""
+        from torchfx_amd.spectral import stft
+
+        return stft(self.ys, n_fft, hop_length, win_length, window, center, pad_mode, normalized, onesided)
+
+    def spectrogram(self, n_fft: int = 1024, hop_length: int | None = None, win_length: int | None = None, window="hann",
+                    power: float | None = 2.0, center: bool = True, pad_mode: str = "reflect", normalized: bool = False) -> Tensor:
+        """Spectrogram of the (materialised) signal, ``[channels, n_fft // 2 + 1, frames]``: power (``power=2.0``), magnitude
+        (``1.0``) or the complex STFT (``None``) (:func:`torchfx_amd.spectral.spectrogram`)."""
+        from torchfx_amd.spectral import spectrogram
+
+        return spectrogram(self.ys, n_fft, hop_length, win_length, window, power, center, pad_mode, normalized)
+
     def resample(self, new_fs: int, window=("kaiser", 5.0)) -> "Wave":
         """``self | Resample(new_fs, window=window)``: the signal at ``new_fs`` (``scipy.signal.resample_poly`` semantics)."""
         from torchfx_amd.resample import Resample
