@@ -582,6 +582,37 @@ std::tuple<Tensor, Tensor, Tensor> limiter_stream_op(const Tensor &x_in, const O
     return std::make_tuple(y, gain, hout);
 }
 
+// What the scan-parallel ops (compressor, gate, phaser) do between their shape checks and the C entry: the contiguous x and its
+// dtype code, the rows split into units of `per_unit` rows, the plan query (plan_info(units, T, info) -> rc; info[4] the scratch
+// bytes), the state [units, width] float64 or None, and the tensors for the new state and for the summaries between the launches.
+struct ScanInputs {
+    Tensor x, state, sout, scratch;      // x contiguous; state the given one on x's device, or undefined
+    int64_t T, units;
+    int dt;
+    const double *sin;                   // null without a state
+    void *scratch_ptr;                   // null when the plan needs none
+};
+
+template <typename PlanInfo>
+ScanInputs scan_inputs(const char *what, const Tensor &x_in, int64_t per_unit, int64_t width, const OptTensor &state, PlanInfo plan_info)
+{
+    ScanInputs in;
+    in.x = x_in.contiguous();
+    in.dt = dtype_code(in.x, what);
+    in.T = in.x.size(-1);
+    const int64_t rows = stream_rows(in.x);
+    TORCH_CHECK(per_unit >= 1 && rows % per_unit == 0, what, ": ", rows, " rows do not split into groups of ", per_unit);
+    in.units = rows / per_unit;             // the phaser's units are its rows (per_unit 1): the check above is the dynamics effects'
+    int64_t info[5];
+    check_rc(plan_info(in.units, in.T, info), what);
+    in.sin = state_ptr(state, {in.units, width}, in.x, (std::string(what) + ": state").c_str(), in.state);
+    const auto f64 = in.x.options().dtype(at::kDouble);
+    in.sout = at::empty({in.units, width}, f64);
+    in.scratch = at::empty({info[4] / 8}, f64);
+    in.scratch_ptr = info[4] ? in.scratch.data_ptr() : nullptr;
+    return in;
+}
+
 // Feed-forward compressor (tfx_compressor_forward): x [..., T], its rows in groups of `channels` consecutive rows that share one
 // gain curve; th, s, w, alpha_a, alpha_r, makeup_db as the C entry takes them; state [groups, 2] float64 (y1, yL) or None
 // (silence); segments 0 = the plan's choice -> (y like x, gain [groups, T] or an empty tensor, new state [groups, 2] float64).
@@ -593,24 +624,18 @@ std::tuple<Tensor, Tensor, Tensor> compressor_op(const Tensor &x_in, double th, 
     const char *what = "compressor_forward";
     need_device(x_in, "x");
     TORCH_CHECK(x_in.dim() >= 1, what, ": x must have a time dimension");
-    const Tensor x = x_in.contiguous();
-    const int dt = dtype_code(x, what);
-    const int64_t T = x.size(-1), rows = stream_rows(x);
-    TORCH_CHECK(channels >= 1 && rows % channels == 0, what, ": ", rows, " rows do not split into groups of ", channels);
-    const int64_t groups = rows / channels;
-    int64_t info[5];
-    check_rc(tfx_compressor_plan_info(groups, channels, T, segments, info, info + 1, info + 2, info + 3, info + 4), what);
-    Tensor keep;
-    const double *sin = state_ptr(state, {groups, 2}, x, "compressor_forward: state", keep);
-    const auto f64 = x.options().dtype(at::kDouble);
-    Tensor y = at::empty_like(x), sout = at::empty({groups, 2}, f64), scratch = at::empty({info[4] / 8}, f64);
-    Tensor gain = return_gain ? at::empty({groups, T}, x.options()) : at::empty({0}, x.options());
+    const ScanInputs in = scan_inputs(what, x_in, channels, 2, state, [&](int64_t groups, int64_t T, int64_t *info) {
+        return tfx_compressor_plan_info(groups, channels, T, segments, info, info + 1, info + 2, info + 3, info + 4);
+    });
+    const Tensor &x = in.x;
+    Tensor y = at::empty_like(x);
+    Tensor gain = return_gain ? at::empty({in.units, in.T}, x.options()) : at::empty({0}, x.options());
     c10::hip::HIPGuard guard(x.get_device());
-    check_rc(tfx_compressor_forward(x.data_ptr(), y.data_ptr(), return_gain ? gain.data_ptr() : nullptr, dt, groups, channels, T, th, s,
-                                    w, alpha_a, alpha_r, makeup_db, sin, sout.data_ptr<double>(), segments,
-                                    info[4] ? scratch.data_ptr() : nullptr, stream_of(x)),
+    check_rc(tfx_compressor_forward(x.data_ptr(), y.data_ptr(), return_gain ? gain.data_ptr() : nullptr, in.dt, in.units, channels, in.T,
+                                    th, s, w, alpha_a, alpha_r, makeup_db, in.sin, in.sout.data_ptr<double>(), segments, in.scratch_ptr,
+                                    stream_of(x)),
              what);
-    return std::make_tuple(y, gain, sout);
+    return std::make_tuple(y, gain, in.sout);
 }
 
 // Noise gate (tfx_gate_forward): x [..., T], its rows in groups of `channels` consecutive rows that share one gain curve; p_open,
@@ -625,26 +650,20 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> gate_op(const Tensor &x_in, double p_
     const char *what = "gate_forward";
     need_device(x_in, "x");
     TORCH_CHECK(x_in.dim() >= 1, what, ": x must have a time dimension");
-    const Tensor x = x_in.contiguous();
-    const int dt = dtype_code(x, what);
-    const int64_t T = x.size(-1), rows = stream_rows(x);
-    TORCH_CHECK(channels >= 1 && rows % channels == 0, what, ": ", rows, " rows do not split into groups of ", channels);
-    const int64_t groups = rows / channels;
-    int64_t info[5];
-    check_rc(tfx_gate_plan_info(groups, channels, T, segments, info, info + 1, info + 2, info + 3, info + 4), what);
-    Tensor keep;
-    const double *sin = state_ptr(state, {groups, 3}, x, "gate_forward: state", keep);
-    const auto f64 = x.options().dtype(at::kDouble), u8 = x.options().dtype(at::kByte);
-    Tensor y = at::empty_like(x), sout = at::empty({groups, 3}, f64), scratch = at::empty({info[4] / 8}, f64);
-    Tensor gain = return_gain ? at::empty({groups, T}, x.options()) : at::empty({0}, x.options());
-    Tensor open = return_open ? at::empty({groups, T}, u8) : at::empty({0}, u8);
+    const ScanInputs in = scan_inputs(what, x_in, channels, 3, state, [&](int64_t groups, int64_t T, int64_t *info) {
+        return tfx_gate_plan_info(groups, channels, T, segments, info, info + 1, info + 2, info + 3, info + 4);
+    });
+    const Tensor &x = in.x;
+    const auto u8 = x.options().dtype(at::kByte);
+    Tensor y = at::empty_like(x);
+    Tensor gain = return_gain ? at::empty({in.units, in.T}, x.options()) : at::empty({0}, x.options());
+    Tensor open = return_open ? at::empty({in.units, in.T}, u8) : at::empty({0}, u8);
     c10::hip::HIPGuard guard(x.get_device());
     check_rc(tfx_gate_forward(x.data_ptr(), y.data_ptr(), return_gain ? gain.data_ptr() : nullptr,
-                              return_open ? open.data_ptr<uint8_t>() : nullptr, dt, groups, channels, T, p_open, p_close, range, hold,
-                              alpha_a, alpha_r, sin, sout.data_ptr<double>(), segments, info[4] ? scratch.data_ptr() : nullptr,
-                              stream_of(x)),
+                              return_open ? open.data_ptr<uint8_t>() : nullptr, in.dt, in.units, channels, in.T, p_open, p_close, range,
+                              hold, alpha_a, alpha_r, in.sin, in.sout.data_ptr<double>(), segments, in.scratch_ptr, stream_of(x)),
              what);
-    return std::make_tuple(y, gain, open, sout);
+    return std::make_tuple(y, gain, open, in.sout);
 }
 
 // Short-time Fourier transform (tfx_stft_forward): x [..., T]; window a 1-D device tensor of x's dtype with 1 <= numel <= n_fft
@@ -845,29 +864,29 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> phaser_op(const Tensor &x_in, int64_t
     need_device(x_in, "x");
     TORCH_CHECK(x_in.dim() >= 1 && x_in.dim() <= 3, what, ": x must be [T], [C, T] or [B, C, T], got ", x_in.dim(), " dimensions");
     TORCH_CHECK(shape == TFX_LFO_SINE || shape == TFX_LFO_TRIANGLE, what, ": bad LFO shape ", shape);
-    const Tensor x = x_in.contiguous();
-    const int dt = dtype_code(x, what);
-    const int64_t T = x.size(-1), rows = stream_rows(x), channels = x.dim() >= 2 ? x.size(-2) : 1;
-    TORCH_CHECK(channels >= 1, what, ": x has no channels");
-    int64_t info[5];
-    check_rc(tfx_phaser_plan_info(rows, channels, T, stages, segments, info, info + 1, info + 2, info + 3, info + 4), what);
-    Tensor keep, pin;
-    const double *sin = state_ptr(state, {rows, stages + 1}, x, "phaser_forward: state", keep);
+    const int64_t channels = x_in.dim() >= 2 ? x_in.size(-2) : 1;
+    const ScanInputs in = scan_inputs(what, x_in, 1, stages + 1, state, [&](int64_t rows, int64_t T, int64_t *info) {
+        TORCH_CHECK(channels >= 1, what, ": x has no channels");    // here, not in front: callers meet it after the dtype check, as ever
+        return tfx_phaser_plan_info(rows, channels, T, stages, segments, info, info + 1, info + 2, info + 3, info + 4);
+    });
+    const Tensor &x = in.x;
+    const int64_t T = in.T;
+    Tensor pin;
     if (pos.has_value() && pos->defined()) {
         TORCH_CHECK(pos->numel() == 1 && pos->scalar_type() == at::kLong, what, ": the position must be an int64 tensor of one element");
         pin = pos->to(x.device()).contiguous();
     }
     const auto f64 = x.options().dtype(at::kDouble), i64 = x.options().dtype(at::kLong);
-    Tensor y = at::empty_like(x), sout = at::empty({rows, stages + 1}, f64), scratch = at::empty({info[4] / 8}, f64);
+    Tensor y = at::empty_like(x);
     Tensor coef = return_coef ? at::empty({phaser_coef_rows(channels, spread), T}, f64) : at::empty({0}, f64);
     Tensor pout = at::empty({pin.defined() ? 1 : 0}, i64);
     c10::hip::HIPGuard guard(x.get_device());
-    check_rc(tfx_phaser_forward(x.data_ptr(), y.data_ptr(), return_coef ? coef.data_ptr<double>() : nullptr, dt, rows, channels, T, stages,
+    check_rc(tfx_phaser_forward(x.data_ptr(), y.data_ptr(), return_coef ? coef.data_ptr<double>() : nullptr, in.dt, in.units, channels, T, stages,
                                 fs, rate, min_freq, max_freq, phase, spread, dry, wet, (int)shape, position,
-                                pin.defined() ? pin.data_ptr<int64_t>() : nullptr, pin.defined() ? pout.data_ptr<int64_t>() : nullptr, sin,
-                                sout.data_ptr<double>(), segments, info[4] ? scratch.data_ptr() : nullptr, stream_of(x)),
+                                pin.defined() ? pin.data_ptr<int64_t>() : nullptr, pin.defined() ? pout.data_ptr<int64_t>() : nullptr, in.sin,
+                                in.sout.data_ptr<double>(), segments, in.scratch_ptr, stream_of(x)),
              what);
-    return std::make_tuple(y, coef, sout, pout);
+    return std::make_tuple(y, coef, in.sout, pout);
 }
 
 std::tuple<Tensor, Tensor, Tensor, Tensor> phaser_meta(const Tensor &x, int64_t stages, double, double, double, double, double,

@@ -18,20 +18,16 @@
 // on (0 * NaN is NaN, so aA = aR = 0 carries it too): the open track is forced to 0 wherever g is NaN and the end state is NaN.
 // The decision scan itself runs over such samples as the comparisons fall; its result there is masked.
 //
-// Work unit (compressor.hip's).  A group's row is cut into tiles of GT_TILE = 2048 samples (256 threads x 8 consecutive samples)
-// and the tiles into `segments` runs of whole tiles; a workgroup owns one (group, segment) and walks its tiles in order with
-// both carries in registers.  A tile: stage p through LDS with coalesced loads; every lane runs its 8 samples from both start
-// states for the lane's summary; Kogge-Stone scan of the summaries over the wave (shuffles), the 4 wave totals through LDS;
-// second run from the true start.  Then the same for the gain, whose coefficients the decision has just fixed.
-//
-// segments == 1: one launch (pass C).  Otherwise three, and nothing crosses between workgroups but at a launch boundary:
+// Work unit: scan_tile.h's, a unit being a group; both carries stay in registers.  The decision's lane summary runs the lane's 8
+// samples from both start states; the gain's scan follows it, its coefficients fixed by the decision just made.
+// segments == 1: one launch (pass C).  Otherwise three:
 //   A  every segment but the last: its decision summary                                               reads x
 //   B  every segment but the last: composes the decision summaries in front of it (a short loop), runs the decision for real
 //      and stores its gain summary (A, S)                                                             reads x
 //   C  every segment: composes both carries, runs both scans, applies the gain                        reads x, writes y
-// The three passes compute p and the decision with the same code, so the carries B and C compose are the same words.  No
-// atomics, no flags.
+// The three passes compute p and the decision with the same code, so the carries B and C compose are the same words.
 #include "common.h"
+#include "scan_tile.h"
 #include "timedomain.h"
 #include "../../include/torchfx_hip.h"
 
@@ -40,9 +36,6 @@
 
 namespace tfx {
 
-constexpr int GT_THREADS = 256, GT_E = 8, GT_WAVES = GT_THREADS / 64;
-constexpr int GT_TILE = GT_THREADS * GT_E;
-constexpr int GT_PAD = GT_TILE + GT_TILE / GT_E;          // p, then g, at a + a/8: a lane's 8 words and a strided sweep both spread over the banks
 constexpr int64_t GT_AUTO_BLOCKS = 1024, GT_AUTO_GROUPS = 512;
 constexpr int GT_SCRATCH_WORDS = 4;                       // per (group, segment): the decision summary's two words, then A and S
 constexpr unsigned GT_CLOSED = 0x80000000u;               // the closed state; an open one is its hold counter c <= H < 2^31
@@ -56,22 +49,21 @@ struct GtSum {
 };
 
 template <typename T> struct GateArgs {
-    const T *x;                 // [groups, channels, T_]
-    T *y;                       // [groups, channels, T_]
-    T *gain;                    // [groups, T_] or null
+    ScanGainIO<T> io;
     unsigned char *open;        // [groups, T_] or null
     const double *state_in;     // [groups, 3] (g, open, c) or null (closed, g = r)
     double *state_out;          // [groups, 3] or null
     gt_u64 *scratch;            // [groups, segments, GT_SCRATCH_WORDS]; unused for segments == 1
-    int64_t T_, tiles, q;       // q = tiles / segments; the first r = tiles % segments segments hold one tile more
-    int channels, segments, r;
+    ScanCut cut;
     unsigned H;
     double p_open, p_close, range;
     double aA, bA, aR, bR;
 };
 
-// NaN-propagating maximum
-__device__ __forceinline__ double gt_max(double a, double b) { return (a > b || a != a) ? a : b; }
+// a run of samples of the gain stage: g -> A g + S
+struct GtGain {
+    double A, S;
+};
 
 // one sample of the automaton: cls 2 = at or above P_open, 1 = at or above P_close, 0 = below both (NaN falls here)
 __device__ __forceinline__ unsigned gt_step(unsigned s, unsigned cls, unsigned H)
@@ -106,14 +98,6 @@ __device__ __forceinline__ GtSum gt_compose(const GtSum &x, const GtSum &y, unsi
     return o;
 }
 
-__device__ __forceinline__ GtSum gt_shfl_up(const GtSum &m, int d)
-{
-    GtSum o;
-    o.s = __shfl_up(m.s, d);
-    o.l = __shfl_up(m.l, d);
-    return o;
-}
-
 // (g, open, c) -> the state word; anything that is not a clean state is closed (the gain's NaN marks the poisoned group)
 __device__ __forceinline__ unsigned gt_state_word(double op, double c, unsigned H)
 {
@@ -124,18 +108,16 @@ __device__ __forceinline__ unsigned gt_state_word(double op, double c, unsigned 
 
 // PASS 0 = A, 1 = B, 2 = C
 template <typename T, int PASS>
-__global__ void __launch_bounds__(GT_THREADS, 4) gate_kernel(const GateArgs<T> p)      // 4 waves per SIMD: pass C fits 128 VGPRs
+__global__ void __launch_bounds__(ST_THREADS, 4) gate_kernel(const GateArgs<T> p)      // 4 waves per SIMD: pass C fits 128 VGPRs
 {
-    __shared__ double slot[GT_PAD];
-    __shared__ gt_u64 wDs[GT_WAVES], wDl[GT_WAVES];
-    __shared__ double wA[GT_WAVES], wS[GT_WAVES];
-    __shared__ gt_u64 obits[GT_THREADS];                               // the open track, a lane's 8 samples as 8 bytes
+    __shared__ double slot[ST_PAD];
+    __shared__ gt_u64 wDs[ST_WAVES], wDl[ST_WAVES];
+    __shared__ double wA[ST_WAVES], wS[ST_WAVES];
+    __shared__ gt_u64 obits[ST_THREADS];                               // the open track, a lane's 8 samples as 8 bytes
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int nseg = PASS == 2 ? p.segments : p.segments - 1;
-    const int64_t grp = blockIdx.x / nseg;
-    const int seg = (int)(blockIdx.x % nseg);
-    const int64_t tile0 = (int64_t)seg * p.q + (seg < p.r ? seg : p.r);
-    const int64_t ntile = p.q + (seg < p.r ? 1 : 0);
+    const ScanSeg sg = scan_segment(p.cut, PASS == 2 ? p.cut.segments : p.cut.segments - 1);
+    const int64_t grp = sg.unit, T_ = p.cut.T_;
+    const int seg = sg.seg;
     const unsigned H = p.H;
 
     // the carries at the segment's start: the state, then the summaries of the segments in front
@@ -147,7 +129,7 @@ __global__ void __launch_bounds__(GT_THREADS, 4) gate_kernel(const GateArgs<T> p
             cs = gt_state_word(o0, c0, H);
             cg = (fabs(g0) <= 1.7976931348623157e308 && o0 == o0 && c0 == c0) ? g0 : (double)NAN;
         }
-        const gt_u64 *sc = p.scratch + grp * p.segments * GT_SCRATCH_WORDS;
+        const gt_u64 *sc = p.scratch + grp * p.cut.segments * GT_SCRATCH_WORDS;
         for (int k = 0; k < seg; ++k) {
             GtSum m;
             m.s = sc[k * GT_SCRATCH_WORDS], m.l = sc[k * GT_SCRATCH_WORDS + 1];
@@ -160,34 +142,15 @@ __global__ void __launch_bounds__(GT_THREADS, 4) gate_kernel(const GateArgs<T> p
     GtSum sD{};                                                        // the segment's summaries (passes A and B)
     double sA = 1.0, sS = 0.0;
 
-    for (int64_t it = 0; it < ntile; ++it) {
-        const int64_t n0 = (tile0 + it) * GT_TILE;
-        // p = max_ch |x|, coalesced, into the slots
-        {
-            double pm[GT_E];
-#pragma unroll
-            for (int k = 0; k < GT_E; ++k) pm[k] = 0.0;
-            for (int ch = 0; ch < p.channels; ++ch) {
-                const T *xr = p.x + (grp * p.channels + ch) * p.T_;
-#pragma unroll
-                for (int k = 0; k < GT_E; ++k) {
-                    const int64_t n = n0 + k * GT_THREADS + t;
-                    const double v = n < p.T_ ? fabs((double)xr[n]) : 0.0;
-                    pm[k] = gt_max(v, pm[k]);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < GT_E; ++k) {
-                const int a = k * GT_THREADS + t;
-                slot[a + (a >> 3)] = pm[k];
-            }
-        }
+    for (int64_t it = 0; it < sg.ntile; ++it) {
+        const int64_t n0 = (sg.tile0 + it) * ST_TILE;
+        scan_stage_peak(slot, p.io, T_, grp, n0);
         __syncthreads();
         // the lane's 8 samples: class (2 bits each) and non-finite mark (1 bit each)
         unsigned cls = 0u, bad = 0u;
 #pragma unroll
-        for (int e = 0; e < GT_E; ++e) {
-            const double pv = slot[t * (GT_E + 1) + e];
+        for (int e = 0; e < ST_E; ++e) {
+            const double pv = slot[st_own(t, e)];
             cls |= (pv >= p.p_open ? 2u : pv >= p.p_close ? 1u : 0u) << (2 * e);
             bad |= (pv <= 1.7976931348623157e308 ? 0u : 1u) << e;
         }
@@ -198,7 +161,7 @@ __global__ void __launch_bounds__(GT_THREADS, 4) gate_kernel(const GateArgs<T> p
             unsigned s0 = GT_CLOSED, s1 = 0u, L = 0u;
             bool quiet = true;
 #pragma unroll
-            for (int e = 0; e < GT_E; ++e) {
+            for (int e = 0; e < ST_E; ++e) {
                 const unsigned c = (cls >> (2 * e)) & 3u;
                 s0 = gt_step(s0, c, H);
                 s1 = gt_step(s1, c, H);
@@ -209,12 +172,8 @@ __global__ void __launch_bounds__(GT_THREADS, 4) gate_kernel(const GateArgs<T> p
             D.s = (gt_u64)s0 | ((gt_u64)s1 << 32);
             D.l = (gt_u64)L | ((gt_u64)(quiet ? 1u : 0u) << 32);
         }
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            const GtSum Dp = gt_shfl_up(D, 1 << j);
-            if (lane >= (1 << j)) D = gt_compose(Dp, D, H);
-        }
-        const GtSum Dex = gt_shfl_up(D, 1);                            // the lanes in front of this one (lane 0: unused)
+        scan_wave(D, lane, [&](const GtSum &Dp, const GtSum &Dc, int) { return gt_compose(Dp, Dc, H); });
+        const GtSum Dex = scan_shfl_up(D, 1);                          // the lanes in front of this one (lane 0: unused)
         if (lane == 63) wDs[wave] = D.s, wDl[wave] = D.l;
         __syncthreads();
 
@@ -222,7 +181,7 @@ __global__ void __launch_bounds__(GT_THREADS, 4) gate_kernel(const GateArgs<T> p
             GtSum Dt;
             Dt.s = wDs[0], Dt.l = wDl[0];
 #pragma unroll
-            for (int k = 1; k < GT_WAVES; ++k) {
+            for (int k = 1; k < ST_WAVES; ++k) {
                 GtSum w;
                 w.s = wDs[k], w.l = wDl[k];
                 Dt = gt_compose(Dt, w, H);
@@ -234,48 +193,45 @@ __global__ void __launch_bounds__(GT_THREADS, 4) gate_kernel(const GateArgs<T> p
             // second run from the true start
             unsigned s = cs;
 #pragma unroll
-            for (int k = 0; k < GT_WAVES; ++k) {
+            for (int k = 0; k < ST_WAVES; ++k) {
                 GtSum w;
                 w.s = wDs[k], w.l = wDl[k];
                 if (k < wave) s = gt_apply(w, s, H);
                 cs = gt_apply(w, cs, H);
             }
             if (lane > 0) s = gt_apply(Dex, s, H);
-            const int64_t nl = n0 + (int64_t)t * GT_E;               // the lane's first sample
+            const int64_t nl = n0 + (int64_t)t * ST_E;               // the lane's first sample
             unsigned op = 0u, slast = GT_CLOSED;                     // open[e] at bit e; the state after sample T - 1
 #pragma unroll
-            for (int e = 0; e < GT_E; ++e) {
+            for (int e = 0; e < ST_E; ++e) {
                 s = gt_step(s, (cls >> (2 * e)) & 3u, H);
                 op |= (s != GT_CLOSED ? 1u : 0u) << e;
-                if (nl + e == p.T_ - 1) slast = s;
+                if (nl + e == T_ - 1) slast = s;
             }
 
             // ---- gain: the coefficients follow the decision; a non-finite sample's addend is NaN
-            double A = 1.0, S = 0.0;
+            GtGain G{1.0, 0.0};
 #pragma unroll
-            for (int e = 0; e < GT_E; ++e) {
+            for (int e = 0; e < ST_E; ++e) {
                 const bool o = (op >> e) & 1u;
                 const double a = o ? p.aA : p.aR;
                 const double b = ((bad >> e) & 1u) ? (double)NAN : (o ? p.bA : p.bR);
-                S = a * S + b;
-                A = a * A;
+                G.S = a * G.S + b;
+                G.A = a * G.A;
             }
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const double Ap = __shfl_up(A, 1 << j), Sp = __shfl_up(S, 1 << j);
-                if (lane >= (1 << j)) {
-                    S = A * Sp + S;
-                    A = A * Ap;
-                }
-            }
-            const double Aex = __shfl_up(A, 1), Sex = __shfl_up(S, 1);
-            if (lane == 63) wA[wave] = A, wS[wave] = S;
+            scan_wave(G, lane, [](const GtGain &f, GtGain c, int) {
+                c.S = c.A * f.S + c.S;
+                c.A = c.A * f.A;
+                return c;
+            });
+            const GtGain Gex = scan_shfl_up(G, 1);
+            if (lane == 63) wA[wave] = G.A, wS[wave] = G.S;
             __syncthreads();
 
             if constexpr (PASS == 1) {
                 double At = wA[0], St = wS[0];
 #pragma unroll
-                for (int k = 1; k < GT_WAVES; ++k) {
+                for (int k = 1; k < ST_WAVES; ++k) {
                     St = wA[k] * St + wS[k];
                     At = wA[k] * At;
                 }
@@ -290,19 +246,19 @@ __global__ void __launch_bounds__(GT_THREADS, 4) gate_kernel(const GateArgs<T> p
             } else {
                 double g = cg;
 #pragma unroll
-                for (int k = 0; k < GT_WAVES; ++k) {
+                for (int k = 0; k < ST_WAVES; ++k) {
                     if (k < wave) g = wA[k] * g + wS[k];
                     cg = wA[k] * cg + wS[k];
                 }
-                if (lane > 0) g = Aex * g + Sex;
+                if (lane > 0) g = Gex.A * g + Gex.S;
                 gt_u64 ob = 0ull;
 #pragma unroll
-                for (int e = 0; e < GT_E; ++e) {
+                for (int e = 0; e < ST_E; ++e) {
                     const bool o = (op >> e) & 1u;
                     g = (o ? p.aA : p.aR) * g + (((bad >> e) & 1u) ? (double)NAN : (o ? p.bA : p.bR));
-                    slot[t * (GT_E + 1) + e] = g;
+                    slot[st_own(t, e)] = g;
                     ob |= (gt_u64)((o && g == g) ? 1u : 0u) << (8 * e);
-                    if (p.state_out && nl + e == p.T_ - 1) {
+                    if (p.state_out && nl + e == T_ - 1) {
                         const bool ok = g == g, so = slast != GT_CLOSED;
                         p.state_out[grp * 3] = g;
                         p.state_out[grp * 3 + 1] = ok ? (so ? 1.0 : 0.0) : (double)NAN;
@@ -311,32 +267,14 @@ __global__ void __launch_bounds__(GT_THREADS, 4) gate_kernel(const GateArgs<T> p
                 }
                 if (p.open) obits[t] = ob;
                 __syncthreads();
-                // apply: coalesced, the tile's re-read comes from cache
-                for (int ch = 0; ch < p.channels; ++ch) {
-                    const T *xr = p.x + (grp * p.channels + ch) * p.T_;
-                    T *yr = p.y + (grp * p.channels + ch) * p.T_;
-#pragma unroll
-                    for (int k = 0; k < GT_E; ++k) {
-                        const int a = k * GT_THREADS + t;
-                        const int64_t n = n0 + a;
-                        if (n < p.T_) yr[n] = (T)(slot[a + (a >> 3)] * (double)xr[n]);
-                    }
-                }
-                if (p.gain) {
-#pragma unroll
-                    for (int k = 0; k < GT_E; ++k) {
-                        const int a = k * GT_THREADS + t;
-                        const int64_t n = n0 + a;
-                        if (n < p.T_) p.gain[grp * p.T_ + n] = (T)slot[a + (a >> 3)];
-                    }
-                }
+                scan_apply_gain(slot, p.io, T_, grp, n0);
                 if (p.open) {
                     const unsigned char *ob8 = (const unsigned char *)obits;
 #pragma unroll
-                    for (int k = 0; k < GT_E; ++k) {
-                        const int a = k * GT_THREADS + t;
+                    for (int k = 0; k < ST_E; ++k) {
+                        const int a = k * ST_THREADS + t;
                         const int64_t n = n0 + a;
-                        if (n < p.T_) p.open[grp * p.T_ + n] = ob8[a];
+                        if (n < T_) p.open[grp * T_ + n] = ob8[a];
                     }
                 }
                 __syncthreads();                                     // the slots are free again
@@ -345,13 +283,13 @@ __global__ void __launch_bounds__(GT_THREADS, 4) gate_kernel(const GateArgs<T> p
     }
     if constexpr (PASS == 0) {
         if (t == 0) {
-            gt_u64 *sc = p.scratch + (grp * p.segments + seg) * GT_SCRATCH_WORDS;
+            gt_u64 *sc = p.scratch + (grp * p.cut.segments + seg) * GT_SCRATCH_WORDS;
             sc[0] = sD.s, sc[1] = sD.l;
         }
     }
     if constexpr (PASS == 1) {
         if (t == 0) {
-            gt_u64 *sc = p.scratch + (grp * p.segments + seg) * GT_SCRATCH_WORDS;
+            gt_u64 *sc = p.scratch + (grp * p.cut.segments + seg) * GT_SCRATCH_WORDS;
             sc[2] = (gt_u64)__double_as_longlong(sA), sc[3] = (gt_u64)__double_as_longlong(sS);
         }
     }
@@ -364,69 +302,16 @@ __global__ void gate_start_state_kernel(double *state_out, int64_t groups, doubl
     if (i < groups) state_out[i * 3] = range, state_out[i * 3 + 1] = 0.0, state_out[i * 3 + 2] = 0.0;
 }
 
-struct GatePlan {
-    int64_t tiles, segments, q, r, scratch_bytes;
-};
-
-// sizes alone (host-only); the segment choice is compressor_plan's
-static GatePlan gate_plan(const char *what, int64_t groups, int64_t channels, int64_t T, int64_t segments)
+// sizes alone (host-only)
+static ScanPlan gate_plan(const char *what, int64_t groups, int64_t channels, int64_t T, int64_t segments)
 {
-    TFX_CHECK(groups >= 0 && T >= 0, "%s: negative size", what);
-    TFX_CHECK(channels >= 1 && channels <= (1 << 20), "%s: channels must be in [1, 2^20], got %lld", what, (long long)channels);
-    TFX_CHECK(segments >= 0, "%s: segments must be >= 0 (0 = chosen by the plan), got %lld", what, (long long)segments);
-    TFX_CHECK(groups == 0 || T <= INT64_MAX / 16 / groups / channels, "%s: size overflows", what);
-    GatePlan pl{};
-    pl.tiles = ceil_div(T, GT_TILE);
-    int64_t s = segments;
-    if (s == 0) s = (groups == 0 || groups >= GT_AUTO_GROUPS) ? 1 : ceil_div(GT_AUTO_BLOCKS, groups);
-    s = std::max<int64_t>(1, std::min(s, pl.tiles));
-    pl.segments = s;
-    pl.q = pl.tiles / s;
-    pl.r = pl.tiles % s;
-    pl.scratch_bytes = s > 1 ? groups * s * GT_SCRATCH_WORDS * (int64_t)sizeof(gt_u64) : 0;
-    TFX_CHECK(groups == 0 || s < (1ll << 31) / groups, "%s: size overflows", what);
-    return pl;
+    return scan_plan(what, groups, channels, T, segments, GT_AUTO_BLOCKS, GT_AUTO_GROUPS, GT_SCRATCH_WORDS * (int64_t)sizeof(gt_u64));
 }
 
 void gate_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t segments, int64_t *tile, int64_t *tiles,
                     int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes)
 {
-    const GatePlan pl = gate_plan("gate_plan_info", groups, channels, T, segments);
-    *tile = GT_TILE;
-    *tiles = pl.tiles;
-    *segments_out = pl.segments;
-    *seg_tiles = pl.q + (pl.r ? 1 : 0);
-    *scratch_bytes = pl.scratch_bytes;
-}
-
-template <typename T>
-static void gate_launch(const void *x, void *y, void *gain, unsigned char *open, int64_t groups, int64_t channels, int64_t T_,
-                        double p_open, double p_close, double range, int64_t hold, double alpha_a, double alpha_r,
-                        const double *state_in, double *state_out, void *scratch, const GatePlan &pl, hipStream_t stream)
-{
-    GateArgs<T> p{};
-    p.x = (const T *)x; p.y = (T *)y; p.gain = (T *)gain; p.open = open; p.state_in = state_in; p.state_out = state_out;
-    p.scratch = (gt_u64 *)scratch;
-    p.T_ = T_; p.tiles = pl.tiles; p.q = pl.q; p.r = (int)pl.r; p.channels = (int)channels; p.segments = (int)pl.segments;
-    p.H = (unsigned)hold; p.p_open = p_open; p.p_close = p_close; p.range = range;
-    p.aA = alpha_a; p.bA = 1.0 - alpha_a;
-    p.aR = alpha_r; p.bR = (1.0 - alpha_r) * range;
-    if (pl.segments > 1) {
-        const unsigned grid = (unsigned)(groups * (pl.segments - 1));
-        {
-            ProfScope ps("gate_pass_a", stream);
-            hipLaunchKernelGGL((gate_kernel<T, 0>), dim3(grid), dim3(GT_THREADS), 0, stream, p);
-            TFX_HIP(hipGetLastError());
-        }
-        {
-            ProfScope ps("gate_pass_b", stream);
-            hipLaunchKernelGGL((gate_kernel<T, 1>), dim3(grid), dim3(GT_THREADS), 0, stream, p);
-            TFX_HIP(hipGetLastError());
-        }
-    }
-    ProfScope ps("gate_pass_c", stream);
-    hipLaunchKernelGGL((gate_kernel<T, 2>), dim3((unsigned)(groups * pl.segments)), dim3(GT_THREADS), 0, stream, p);
-    TFX_HIP(hipGetLastError());
+    scan_plan_info(gate_plan("gate_plan_info", groups, channels, T, segments), tile, tiles, segments_out, seg_tiles, scratch_bytes);
 }
 
 void gate_forward(const void *x, void *y, void *gain, unsigned char *open, int dtype, int64_t groups, int64_t channels, int64_t T,
@@ -435,7 +320,7 @@ void gate_forward(const void *x, void *y, void *gain, unsigned char *open, int d
 {
     const char *what = "gate_forward";
     TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "%s: bad dtype %d", what, dtype);
-    const GatePlan pl = gate_plan(what, groups, channels, T, segments);
+    const ScanPlan pl = gate_plan(what, groups, channels, T, segments);
     TFX_CHECK(std::isfinite(p_open) && p_open > 0.0, "%s: the opening level must be a finite linear level > 0, got %g", what, p_open);
     TFX_CHECK(p_close >= 0.0 && p_close <= p_open, "%s: the closing level must be in [0, the opening level %g], got %g", what, p_open,
               p_close);
@@ -443,29 +328,28 @@ void gate_forward(const void *x, void *y, void *gain, unsigned char *open, int d
     TFX_CHECK(hold >= 0 && hold < (1ll << 31), "%s: the hold must be in [0, 2^31) samples, got %lld", what, (long long)hold);
     TFX_CHECK(alpha_a >= 0.0 && alpha_a <= 1.0, "%s: alpha_a must be in [0, 1], got %g", what, alpha_a);
     TFX_CHECK(alpha_r >= 0.0 && alpha_r <= 1.0, "%s: alpha_r must be in [0, 1], got %g", what, alpha_r);
-    TFX_CHECK(groups * T == 0 || (x && y), "%s: null pointer", what);
-    TFX_CHECK(groups * T == 0 || pl.segments == 1 || scratch, "%s: %lld segments need a scratch buffer of %lld bytes", what,
-              (long long)pl.segments, (long long)pl.scratch_bytes);
-    TFX_CHECK(!state_out || state_out != state_in, "%s: the new state needs its own buffer", what);
-    if (groups == 0) return;
-    if (T == 0) {                                // nothing in, nothing out: the state moves on unchanged
-        if (state_out) {
-            if (state_in) {
-                TFX_HIP(hipMemcpyAsync(state_out, state_in, (size_t)groups * 3 * sizeof(double), hipMemcpyDeviceToDevice, stream));
-            } else {
-                hipLaunchKernelGGL(gate_start_state_kernel, dim3((unsigned)ceil_div(groups, 256)), dim3(256), 0, stream, state_out,
-                                   groups, range);
-                TFX_HIP(hipGetLastError());
-            }
-        }
-        return;
-    }
-    if (dtype == TFX_F32)
-        gate_launch<float>(x, y, gain, open, groups, channels, T, p_open, p_close, range, hold, alpha_a, alpha_r, state_in, state_out,
-                           scratch, pl, stream);
-    else
-        gate_launch<double>(x, y, gain, open, groups, channels, T, p_open, p_close, range, hold, alpha_a, alpha_r, state_in, state_out,
-                            scratch, pl, stream);
+    scan_check_buffers(what, pl, T, x, y, scratch, state_in, state_out);
+    if (groups * T == 0)
+        return scan_empty_chunk(groups, 3, state_in, state_out, stream, [&](size_t) {
+            hipLaunchKernelGGL(gate_start_state_kernel, dim3((unsigned)ceil_div(groups, 256)), dim3(256), 0, stream, state_out, groups,
+                               range);
+            TFX_HIP(hipGetLastError());
+        });
+    auto run = [&](auto tag) {
+        using E = decltype(tag);
+        GateArgs<E> p{};
+        p.io = {(const E *)x, (E *)y, (E *)gain, (int)channels};
+        p.open = open; p.state_in = state_in; p.state_out = state_out; p.scratch = (gt_u64 *)scratch;
+        p.cut = scan_cut(pl, T);
+        p.H = (unsigned)hold; p.p_open = p_open; p.p_close = p_close; p.range = range;
+        p.aA = alpha_a; p.bA = 1.0 - alpha_a;
+        p.aR = alpha_r; p.bR = (1.0 - alpha_r) * range;
+        const ScanPass<GateArgs<E>> ladder[] = {{gate_kernel<E, 0>, "gate_pass_a"}, {gate_kernel<E, 1>, "gate_pass_b"},
+                                                {gate_kernel<E, 2>, "gate_pass_c"}};
+        scan_launch(ladder, p, pl, stream);
+    };
+    if (dtype == TFX_F32) run(float{});
+    else run(double{});
 }
 
 }  // namespace tfx

@@ -7,8 +7,7 @@
 // of samples acts on the incoming y as y -> C y + B with C the product of its c's: a scan.  Every stage has the same c[n], so the
 // products the scan strides need are computed once per tile and serve all N stages.
 //
-// Work unit.  A row is cut into tiles of PH_TILE = 2048 samples (256 threads x 8 consecutive samples) and the tiles into `segments`
-// runs of whole tiles; a workgroup owns one (row, segment) and walks its tiles in order.  The N + 1 carries x_k[tile start - 1] are
+// Work unit: scan_tile.h's, a unit being a row.  The N + 1 carries x_k[tile start - 1] are
 // the values the last thread of the previous tile computed; they sit in 2 x 13 doubles of LDS (read as broadcasts), because a
 // register array indexed by the stage counter would live in scratch memory.  A tile: x_0 through LDS with coalesced loads; a[n]
 // once; the lane products of c and their Kogge-Stone prefix products over the wave; then per stage: b from the input and the sample
@@ -16,15 +15,16 @@
 // scan of B over the wave, the 4 wave totals through LDS, a second run from the true start.  Combines are ordered by position
 // alone and read only what lies in front, so a sample's bits do not depend on values after it.
 //
-// segments == 1: one launch (pass C).  Otherwise two, and nothing crosses between workgroups but at the launch boundary:
+// segments == 1: one launch (pass C).  Otherwise two:
 //   A  every segment but the last: the segment acts on the incoming (x_1[-1] .. x_N[-1]) as s -> M s + v.  M depends on the
 //      coefficients alone and is lower-triangular Toeplitz (every stage is the same operator, and a state enters stage k exactly as
 //      it enters stage 1).  The pass runs the segment twice in lockstep on one coefficient track: the real signal from a zero state
 //      gives v, the zero signal from x_1[-1] = 1 gives the N distinct entries of M.  x_0[-1] is read from the signal itself.
 //   C  every segment: composes the summaries in front of it (a short loop of triangular products), runs the stages, writes y.
-// Both passes compute a[n] with the same code, so the numbers they compose are the same numbers.  No atomics, no flags.
+// Both passes compute a[n] with the same code, so the numbers they compose are the same numbers.
 #include "common.h"
 #include "lfo.h"
+#include "scan_tile.h"
 #include "timedomain.h"
 #include "../../include/torchfx_hip.h"
 
@@ -35,9 +35,6 @@
 
 namespace tfx {
 
-constexpr int PH_THREADS = 256, PH_E = 8, PH_WAVES = PH_THREADS / 64;
-constexpr int PH_TILE = PH_THREADS * PH_E;
-constexpr int PH_PAD = PH_TILE + PH_TILE / PH_E;          // x_0, then y, at a + a/8: a lane's 8 words and a strided sweep both spread over the banks
 constexpr int PH_MAXN = 12;
 constexpr int64_t PH_AUTO_BLOCKS = 512, PH_AUTO_ROWS = 256;   // two workgroups per CU; the rows alone fill the chip
 
@@ -51,8 +48,8 @@ template <typename T> struct PhaserArgs {
     const int64_t *pos_in;      // DEVICE position of sample 0, null = pos
     int64_t *pos_out;           // receives the position + T_, or null
     int64_t pos;
-    int64_t T_, q;              // q = tiles / segments; the first r = tiles % segments segments hold one tile more
-    int channels, coef_rows, N, segments, r;
+    int channels, coef_rows, N;
+    ScanCut cut;                // behind the ints: in front of them the float64 pass C reserves a stack slot for a scalar spill
     double inc, phase, spread, fmin, lg, w, dry, wet;
 };
 
@@ -67,34 +64,32 @@ template <bool TRI> __device__ __forceinline__ double ph_coef(int64_t n, double 
 
 // PASS 0 = A (two runs in lockstep: r = 0 the real signal from a zero state, r = 1 the zero signal from x_1[-1] = 1), 1 = C
 template <typename T, bool TRI, int PASS>
-__global__ void __launch_bounds__(PH_THREADS) phaser_kernel(const PhaserArgs<T> p)
+__global__ void __launch_bounds__(ST_THREADS) phaser_kernel(const PhaserArgs<T> p)
 {
     constexpr int R = PASS == 0 ? 2 : 1;
-    __shared__ double slot[PH_PAD];
-    __shared__ double wC[PH_WAVES], wB[R][PH_WAVES], wU[R][PH_WAVES];
+    __shared__ double slot[ST_PAD];
+    __shared__ double wC[ST_WAVES], wB[R][ST_WAVES], wU[R][ST_WAVES];
     __shared__ double sC[2][R][PH_MAXN + 1];                         // the carries x_k[tile start - 1], by tile parity
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
     const int N = p.N;
-    const int nseg = PASS == 1 ? p.segments : p.segments - 1;
-    const int64_t row = blockIdx.x / nseg;
-    const int seg = (int)(blockIdx.x % nseg);
-    const int64_t tile0 = (int64_t)seg * p.q + (seg < p.r ? seg : p.r);
-    const int64_t ntile = p.q + (seg < p.r ? 1 : 0);
+    const ScanSeg sg = scan_segment(p.cut, PASS == 1 ? p.cut.segments : p.cut.segments - 1);
+    const int64_t row = sg.unit, tile0 = sg.tile0, ntile = sg.ntile, T_ = p.cut.T_;
+    const int seg = sg.seg;
     const int64_t pos = p.pos_in ? *p.pos_in : p.pos;
-    const T *xr = p.x + row * p.T_;
+    const T *xr = p.x + row * T_;
     const double z = p.phase + (double)(row % p.channels) * p.spread;
     const double off = z - floor(z);
-    if (PASS == 1 && blockIdx.x == 0 && t == 0 && p.pos_out) *p.pos_out = pos + p.T_;
+    if (PASS == 1 && blockIdx.x == 0 && t == 0 && p.pos_out) *p.pos_out = pos + T_;
 
     // the carries at the segment's start
     {
         double s[PH_MAXN + 1];
-        s[0] = tile0 == 0 ? (p.state_in ? p.state_in[row * (N + 1)] : 0.0) : (double)xr[tile0 * PH_TILE - 1];
+        s[0] = tile0 == 0 ? (p.state_in ? p.state_in[row * (N + 1)] : 0.0) : (double)xr[tile0 * ST_TILE - 1];
 #pragma unroll
         for (int k = 1; k <= PH_MAXN; ++k) s[k] = (PASS == 1 && p.state_in && k <= N) ? p.state_in[row * (N + 1) + k] : 0.0;
         if constexpr (PASS == 1) {
             // the state through the summaries of the segments in front: s <- M s + v, M[k][j] = m[k - j]
-            const double *sc = p.scratch + row * p.segments * 2 * N;
+            const double *sc = p.scratch + row * p.cut.segments * 2 * N;
             for (int g = 0; g < seg; ++g) {
                 const double *sv = sc + (int64_t)g * 2 * N, *sm = sv + N;
                 double m[PH_MAXN];
@@ -122,59 +117,57 @@ __global__ void __launch_bounds__(PH_THREADS) phaser_kernel(const PhaserArgs<T> 
 
     for (int64_t it = 0; it < ntile; ++it) {
         const int cur = (int)(it & 1), nxt = cur ^ 1;
-        const int64_t n0 = (tile0 + it) * PH_TILE;
+        const int64_t n0 = (tile0 + it) * ST_TILE;
         // x_0, coalesced, into the slots
 #pragma unroll
-        for (int k = 0; k < PH_E; ++k) {
-            const int a = k * PH_THREADS + t;
+        for (int k = 0; k < ST_E; ++k) {
+            const int a = k * ST_THREADS + t;
             const int64_t n = n0 + a;
-            slot[a + (a >> 3)] = n < p.T_ ? (double)xr[n] : 0.0;
+            slot[st_sweep(a)] = n < T_ ? (double)xr[n] : 0.0;
         }
         // the coefficient of the lane's 8 samples, and what the scan of every stage needs of it: P[j] = the product of c = -a over
         // the 2^j lanes that end at this one, Pinc over the lanes 0 .. this one, Pex over the lanes in front
-        const int64_t nl = n0 + (int64_t)t * PH_E;                   // the lane's first sample
-        double a[PH_E];
+        const int64_t nl = n0 + (int64_t)t * ST_E;                   // the lane's first sample
+        double a[ST_E];
 #pragma unroll
-        for (int e = 0; e < PH_E; ++e) a[e] = ph_coef<TRI>(pos + nl + e, off, p.inc, p.fmin, p.lg, p.w);
+        for (int e = 0; e < ST_E; ++e) a[e] = ph_coef<TRI>(pos + nl + e, off, p.inc, p.fmin, p.lg, p.w);
         if constexpr (PASS == 1) {
             if (p.coef && row < p.coef_rows) {
 #pragma unroll
-                for (int e = 0; e < PH_E; ++e)
-                    if (nl + e < p.T_) p.coef[row * p.T_ + nl + e] = a[e];
+                for (int e = 0; e < ST_E; ++e)
+                    if (nl + e < T_) p.coef[row * T_ + nl + e] = a[e];
             }
         }
         double P[6], Pinc = -a[0];
 #pragma unroll
-        for (int e = 1; e < PH_E; ++e) Pinc = Pinc * -a[e];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            P[j] = Pinc;
-            const double up = __shfl_up(Pinc, 1 << j);
-            if (lane >= (1 << j)) Pinc = Pinc * up;
-        }
-        const double Pex = __shfl_up(Pinc, 1);                       // lane 0: unused
+        for (int e = 1; e < ST_E; ++e) Pinc = Pinc * -a[e];
+        scan_wave(Pinc, lane, [&](double up, double Pc, int j) {
+            P[j] = Pc;
+            return Pc * up;
+        });
+        const double Pex = scan_shfl_up(Pinc, 1);                    // lane 0: unused
         __syncthreads();                                             // the slots are full; the last tile's reads of wC, wU are over
 
-        double u[R][PH_E];
+        double u[R][ST_E];
 #pragma unroll
-        for (int e = 0; e < PH_E; ++e) {
-            u[0][e] = slot[t * (PH_E + 1) + e];
+        for (int e = 0; e < ST_E; ++e) {
+            u[0][e] = slot[st_own(t, e)];
             if (R == 2) u[R - 1][e] = 0.0;
         }
-        const bool last = PASS == 1 && p.state_out && n0 + PH_TILE >= p.T_;      // this tile holds the row's last sample
+        const bool last = PASS == 1 && p.state_out && n0 + ST_TILE >= T_;      // this tile holds the row's last sample
         if (last) {
 #pragma unroll
-            for (int e = 0; e < PH_E; ++e)
-                if (nl + e == p.T_ - 1) p.state_out[row * (N + 1)] = u[0][e];
+            for (int e = 0; e < ST_E; ++e)
+                if (nl + e == T_ - 1) p.state_out[row * (N + 1)] = u[0][e];
         }
         if (lane == 63) {
             wC[wave] = Pinc;
 #pragma unroll
-            for (int r = 0; r < R; ++r) wU[r][wave] = u[r][PH_E - 1];
+            for (int r = 0; r < R; ++r) wU[r][wave] = u[r][ST_E - 1];
         }
-        if (t == PH_THREADS - 1) {
+        if (t == ST_THREADS - 1) {
 #pragma unroll
-            for (int r = 0; r < R; ++r) sC[nxt][r][0] = u[r][PH_E - 1];
+            for (int r = 0; r < R; ++r) sC[nxt][r][0] = u[r][ST_E - 1];
         }
 
         for (int k = 1; k <= N; ++k) {
@@ -183,21 +176,17 @@ __global__ void __launch_bounds__(PH_THREADS) phaser_kernel(const PhaserArgs<T> 
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 // b[n] = a[n] u[n] + u[n-1], in place of u from the back
-                double up = __shfl_up(u[r][PH_E - 1], 1);
+                double up = __shfl_up(u[r][ST_E - 1], 1);
                 if (lane == 0) up = wave == 0 ? sC[cur][r][k - 1] : wU[r][wave - 1];
 #pragma unroll
-                for (int e = PH_E - 1; e >= 1; --e) u[r][e] = fma(a[e], u[r][e], u[r][e - 1]);
+                for (int e = ST_E - 1; e >= 1; --e) u[r][e] = fma(a[e], u[r][e], u[r][e - 1]);
                 u[r][0] = fma(a[0], u[r][0], up);
                 // the lane's 8 samples from nothing, then the lanes in front by strides
                 double B = u[r][0];
 #pragma unroll
-                for (int e = 1; e < PH_E; ++e) B = fma(-a[e], B, u[r][e]);
-#pragma unroll
-                for (int j = 0; j < 6; ++j) {
-                    const double Bp = __shfl_up(B, 1 << j);
-                    if (lane >= (1 << j)) B = fma(P[j], Bp, B);
-                }
-                Bex[r] = __shfl_up(B, 1);
+                for (int e = 1; e < ST_E; ++e) B = fma(-a[e], B, u[r][e]);
+                scan_wave(B, lane, [&](double Bp, double Bc, int j) { return fma(P[j], Bp, Bc); });
+                Bex[r] = scan_shfl_up(B, 1);
                 if (lane == 63) wB[r][wave] = B;
             }
             __syncthreads();
@@ -206,37 +195,37 @@ __global__ void __launch_bounds__(PH_THREADS) phaser_kernel(const PhaserArgs<T> 
                 // second run from the true start
                 double yv = sC[cur][r][k];
 #pragma unroll
-                for (int w = 0; w < PH_WAVES - 1; ++w)
+                for (int w = 0; w < ST_WAVES - 1; ++w)
                     if (w < wave) yv = fma(wC[w], yv, wB[r][w]);
                 if (lane > 0) yv = fma(Pex, yv, Bex[r]);
 #pragma unroll
-                for (int e = 0; e < PH_E; ++e) {
+                for (int e = 0; e < ST_E; ++e) {
                     yv = fma(-a[e], yv, u[r][e]);
                     u[r][e] = yv;
                 }
                 if (lane == 63) wU[r][wave] = yv;
-                if (t == PH_THREADS - 1) sC[nxt][r][k] = yv;
+                if (t == ST_THREADS - 1) sC[nxt][r][k] = yv;
             }
             if (last) {
 #pragma unroll
-                for (int e = 0; e < PH_E; ++e)
-                    if (nl + e == p.T_ - 1) p.state_out[row * (N + 1) + k] = u[0][e];
+                for (int e = 0; e < ST_E; ++e)
+                    if (nl + e == T_ - 1) p.state_out[row * (N + 1) + k] = u[0][e];
             }
         }
 
         if constexpr (PASS == 1) {
 #pragma unroll
-            for (int e = 0; e < PH_E; ++e) {
-                const int i = t * (PH_E + 1) + e;
+            for (int e = 0; e < ST_E; ++e) {
+                const int i = st_own(t, e);
                 slot[i] = p.dry * slot[i] + p.wet * u[0][e];
             }
             __syncthreads();
-            T *yr = p.y + row * p.T_;
+            T *yr = p.y + row * T_;
 #pragma unroll
-            for (int k = 0; k < PH_E; ++k) {
-                const int i = k * PH_THREADS + t;
+            for (int k = 0; k < ST_E; ++k) {
+                const int i = k * ST_THREADS + t;
                 const int64_t n = n0 + i;
-                if (n < p.T_) yr[n] = (T)slot[i + (i >> 3)];
+                if (n < T_) yr[n] = (T)slot[st_sweep(i)];
             }
             __syncthreads();                                         // the slots are free again
         }
@@ -245,7 +234,7 @@ __global__ void __launch_bounds__(PH_THREADS) phaser_kernel(const PhaserArgs<T> 
     if constexpr (PASS == 0) {
         __syncthreads();
         const int fin = (int)(ntile & 1);
-        double *sc = p.scratch + (row * p.segments + seg) * 2 * N;
+        double *sc = p.scratch + (row * p.cut.segments + seg) * 2 * N;
         if (t < N) sc[t] = sC[fin][0][t + 1];
         else if (t < 2 * N) sc[t] = sC[fin][1][t - N + 1];
     }
@@ -254,69 +243,20 @@ __global__ void __launch_bounds__(PH_THREADS) phaser_kernel(const PhaserArgs<T> 
 // an empty chunk still hands its position on
 __global__ void phaser_position_kernel(const int64_t *pos_in, int64_t pos, int64_t *pos_out) { *pos_out = pos_in ? *pos_in : pos; }
 
-struct PhaserPlan {
-    int64_t rows, tiles, segments, q, r, scratch_bytes;
-};
-
-// sizes alone (host-only)
-static PhaserPlan phaser_plan(const char *what, int64_t rows, int64_t channels, int64_t T, int64_t stages, int64_t segments)
+// sizes alone (host-only); the two checks that are the phaser's own sit where callers have always met them, after the size checks
+static ScanPlan phaser_plan(const char *what, int64_t rows, int64_t channels, int64_t T, int64_t stages, int64_t segments)
 {
-    TFX_CHECK(rows >= 0 && T >= 0, "%s: negative size", what);
-    TFX_CHECK(channels >= 1 && channels <= (1 << 20), "%s: channels must be in [1, 2^20], got %lld", what, (long long)channels);
+    scan_check_sizes(what, rows, channels, T);
     TFX_CHECK(rows % channels == 0, "%s: %lld rows do not split into items of %lld channels", what, (long long)rows, (long long)channels);
     TFX_CHECK(stages >= 1 && stages <= PH_MAXN, "%s: stages must be in [1, %d], got %lld", what, PH_MAXN, (long long)stages);
-    TFX_CHECK(segments >= 0, "%s: segments must be >= 0 (0 = chosen by the plan), got %lld", what, (long long)segments);
-    TFX_CHECK(rows == 0 || T <= INT64_MAX / 16 / rows, "%s: size overflows", what);
-    PhaserPlan pl{};
-    pl.rows = rows;
-    pl.tiles = ceil_div(T, PH_TILE);
-    int64_t s = segments;
-    if (s == 0) s = (rows == 0 || rows >= PH_AUTO_ROWS) ? 1 : ceil_div(PH_AUTO_BLOCKS, rows);
-    s = std::max<int64_t>(1, std::min(s, pl.tiles));
-    pl.segments = s;
-    pl.q = pl.tiles / s;
-    pl.r = pl.tiles % s;
-    pl.scratch_bytes = s > 1 ? rows * s * 2 * stages * (int64_t)sizeof(double) : 0;
-    TFX_CHECK(rows == 0 || s < (1ll << 31) / rows, "%s: size overflows", what);
-    return pl;
+    return scan_plan(what, rows, 1, T, segments, PH_AUTO_BLOCKS, PH_AUTO_ROWS, 2 * stages * (int64_t)sizeof(double));
 }
 
 void phaser_plan_info(int64_t rows, int64_t channels, int64_t T, int64_t stages, int64_t segments, int64_t *tile, int64_t *tiles,
                       int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes)
 {
-    const PhaserPlan pl = phaser_plan("phaser_plan_info", rows, channels, T, stages, segments);
-    *tile = PH_TILE;
-    *tiles = pl.tiles;
-    *segments_out = pl.segments;
-    *seg_tiles = pl.q + (pl.r ? 1 : 0);
-    *scratch_bytes = pl.scratch_bytes;
-}
-
-template <typename T, bool TRI> static void phaser_launch(const PhaserArgs<T> &p, const PhaserPlan &pl, hipStream_t stream)
-{
-    if (pl.segments > 1) {
-        ProfScope ps("phaser_pass_a", stream);
-        hipLaunchKernelGGL((phaser_kernel<T, TRI, 0>), dim3((unsigned)(pl.rows * (pl.segments - 1))), dim3(PH_THREADS), 0, stream, p);
-        TFX_HIP(hipGetLastError());
-    }
-    ProfScope ps("phaser_pass_c", stream);
-    hipLaunchKernelGGL((phaser_kernel<T, TRI, 1>), dim3((unsigned)(pl.rows * pl.segments)), dim3(PH_THREADS), 0, stream, p);
-    TFX_HIP(hipGetLastError());
-}
-
-template <typename T>
-static void phaser_run(const void *x, void *y, double *coef, int64_t coef_rows, int64_t channels, int64_t T_, int64_t stages,
-                       const double *par, int shape, int64_t position, const int64_t *pos_in, int64_t *pos_out, const double *state_in,
-                       double *state_out, void *scratch, const PhaserPlan &pl, hipStream_t stream)
-{
-    PhaserArgs<T> p{};
-    p.x = (const T *)x; p.y = (T *)y; p.coef = coef; p.state_in = state_in; p.state_out = state_out; p.scratch = (double *)scratch;
-    p.pos_in = pos_in; p.pos_out = pos_out; p.pos = position;
-    p.T_ = T_; p.q = pl.q; p.r = (int)pl.r; p.channels = (int)channels; p.coef_rows = (int)coef_rows; p.N = (int)stages;
-    p.segments = (int)pl.segments;
-    p.inc = par[0]; p.phase = par[1]; p.spread = par[2]; p.fmin = par[3]; p.lg = par[4]; p.w = par[5]; p.dry = par[6]; p.wet = par[7];
-    if (shape == TFX_LFO_TRIANGLE) phaser_launch<T, true>(p, pl, stream);
-    else phaser_launch<T, false>(p, pl, stream);
+    scan_plan_info(phaser_plan("phaser_plan_info", rows, channels, T, stages, segments), tile, tiles, segments_out, seg_tiles,
+                   scratch_bytes);
 }
 
 void phaser_forward(const void *x, void *y, double *coef, int dtype, int64_t rows, int64_t channels, int64_t T, int64_t stages, double fs,
@@ -326,7 +266,7 @@ void phaser_forward(const void *x, void *y, double *coef, int dtype, int64_t row
 {
     const char *what = "phaser_forward";
     TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "%s: bad dtype %d", what, dtype);
-    const PhaserPlan pl = phaser_plan(what, rows, channels, T, stages, segments);
+    const ScanPlan pl = phaser_plan(what, rows, channels, T, stages, segments);
     TFX_CHECK(shape == TFX_LFO_SINE || shape == TFX_LFO_TRIANGLE, "%s: bad LFO shape %d", what, shape);
     TFX_CHECK(std::isfinite(fs) && fs > 0.0, "%s: the sample rate must be finite and > 0, got %g", what, fs);
     TFX_CHECK(min_freq >= 10.0 && min_freq <= max_freq && max_freq <= 0.45 * fs,
@@ -337,18 +277,11 @@ void phaser_forward(const void *x, void *y, double *coef, int dtype, int64_t row
     TFX_CHECK(std::isfinite(dry), "%s: dry must be finite, got %g", what, dry);
     TFX_CHECK(std::isfinite(wet), "%s: wet must be finite, got %g", what, wet);
     TFX_CHECK(position >= 0 && position <= (1ll << 52), "%s: the position must be in [0, 2^52], got %lld", what, (long long)position);
-    TFX_CHECK(rows * T == 0 || (x && y), "%s: null pointer", what);
-    TFX_CHECK(rows * T == 0 || pl.segments == 1 || scratch, "%s: %lld segments need a scratch buffer of %lld bytes", what,
-              (long long)pl.segments, (long long)pl.scratch_bytes);
-    TFX_CHECK(!state_out || state_out != state_in, "%s: the new state needs its own buffer", what);
+    scan_check_buffers(what, pl, T, x, y, scratch, state_in, state_out);
     TFX_CHECK(!pos_out || pos_out != pos_in, "%s: the new position needs its own buffer", what);
     check_stream_buffers(what, dtype == TFX_F32 ? 4 : 8, x, rows * T, y, rows * T, nullptr, nullptr, 0);
     if (rows * T == 0) {                         // nothing in, nothing out: the state and the position move on unchanged
-        const size_t bytes = (size_t)rows * (size_t)(stages + 1) * sizeof(double);
-        if (state_out && bytes) {
-            if (state_in) TFX_HIP(hipMemcpyAsync(state_out, state_in, bytes, hipMemcpyDeviceToDevice, stream));
-            else TFX_HIP(hipMemsetAsync(state_out, 0, bytes, stream));
-        }
+        scan_empty_chunk(rows, stages + 1, state_in, state_out, stream);
         if (pos_out) {
             hipLaunchKernelGGL(phaser_position_kernel, dim3(1), dim3(1), 0, stream, pos_in, position, pos_out);
             TFX_HIP(hipGetLastError());
@@ -357,13 +290,20 @@ void phaser_forward(const void *x, void *y, double *coef, int dtype, int64_t row
     }
     // the reduced parameters, as doubles on the host: inc = rate / fs, Lg = ln(max_freq / min_freq), w = pi / fs
     const double par[8] = {rate / fs, phase, spread, min_freq, std::log(max_freq / min_freq), M_PI / fs, dry, wet};
-    const int64_t coef_rows = (spread == 0.0 || channels == 1) ? 1 : channels;
-    if (dtype == TFX_F32)
-        phaser_run<float>(x, y, coef, coef_rows, channels, T, stages, par, shape, position, pos_in, pos_out, state_in, state_out, scratch,
-                          pl, stream);
-    else
-        phaser_run<double>(x, y, coef, coef_rows, channels, T, stages, par, shape, position, pos_in, pos_out, state_in, state_out, scratch,
-                           pl, stream);
+    auto run = [&](auto tag, auto tri) {
+        using E = decltype(tag);
+        PhaserArgs<E> p{};
+        p.x = (const E *)x; p.y = (E *)y; p.coef = coef; p.state_in = state_in; p.state_out = state_out; p.scratch = (double *)scratch;
+        p.pos_in = pos_in; p.pos_out = pos_out; p.pos = position;
+        p.cut = scan_cut(pl, T);
+        p.channels = (int)channels; p.coef_rows = (int)((spread == 0.0 || channels == 1) ? 1 : channels); p.N = (int)stages;
+        p.inc = par[0]; p.phase = par[1]; p.spread = par[2]; p.fmin = par[3]; p.lg = par[4]; p.w = par[5]; p.dry = par[6]; p.wet = par[7];
+        const ScanPass<PhaserArgs<E>> ladder[] = {{phaser_kernel<E, tri(), 0>, "phaser_pass_a"}, {phaser_kernel<E, tri(), 1>, "phaser_pass_c"}};
+        scan_launch(ladder, p, pl, stream);
+    };
+    const bool tri = shape == TFX_LFO_TRIANGLE;
+    if (dtype == TFX_F32) tri ? run(float{}, std::true_type{}) : run(float{}, std::false_type{});
+    else tri ? run(double{}, std::true_type{}) : run(double{}, std::false_type{});
 }
 
 }  // namespace tfx
