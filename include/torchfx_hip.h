@@ -741,8 +741,10 @@ int tfx_freeverb_plan_info(int64_t batch, int64_t channels, int64_t T, int64_t t
  * A workgroup owns a tile of `tile` outputs of one row (tfx_waveshaper_plan_info); the tiling does not depend on `rows`, and
  * a row's bits depend on its own samples alone.  Non-finite input: y[m] is NaN exactly when x[m - reach_after .. m +
  * reach_before] holds a NaN or an Inf (every tap of both zero-padded filters counted; an up-sampled value that is not finite
- * shapes to NaN); every other output has the bits it has with a zero in that sample's place.  Arguments are checked before
- * the device is touched; the first call with a new filter or curve uploads it with a blocking copy and caches it by content.
+ * shapes to NaN); every other output has the bits it has with a zero in that sample's place.  drive, bias, dry and wet must be
+ * finite after rounding to dtype, which is how the kernel holds them: 1e39 is refused for TFX_F32 (it would arrive as Inf, and
+ * silence would shape to 0 * Inf = NaN) and accepted for TFX_F64; tfx_waveshaper_stream_forward refuses the same.  Arguments are
+ * checked before the device is touched; the first call with a new filter or curve uploads it with a blocking copy and caches it by content.
  * ------------------------------------------------------------------------- */
 enum tfx_shape { TFX_SHAPE_HARD = 0, TFX_SHAPE_CUBIC = 1, TFX_SHAPE_TANH = 2, TFX_SHAPE_CURVE = 3 };
 int tfx_waveshaper_forward(const void *x, void *y, int dtype, int64_t rows, int64_t T, int64_t oversample, int shape,

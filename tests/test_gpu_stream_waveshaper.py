@@ -3,7 +3,10 @@ flush() are torch.equal to the one-shot device call for every oversampling facto
 latency, the history and the tile; the concatenated stream also meets the per-sample bound of tests/waveshaper_reference.py and,
 for the hard clipper, has the bits of the device composition resample -> multiply -> clamp -> resample; one-sample chunks,
 layouts, planted NaNs and Infs at chunk seams and in the history, batch independence, one launch per chunk, graph replay and the
-real-time callback.  The tile, the latency and the history come from the plan query."""
+real-time callback.  The tile, the latency and the history come from the plan query.
+
+All of it at the default window (waveshaper_kernel<T, 24, true>).  The stream form of every other register bucket and of stages of
+unequal length, whose dry sample sits elsewhere in the staged window, is section B of tests/test_gpu_waveshaper_edges.py."""
 import functools
 import json
 

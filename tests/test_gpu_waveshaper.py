@@ -1,7 +1,12 @@
 """The waveshaper on the device (csrc/waveshaper.hip): torch.equal to the device composition resample -> multiply -> clamp ->
 resample for the hard clipper at every length class of the tiling, the per-sample bound of tests/waveshaper_reference.py for
 tanh, cubic and three curves under a bias and a partial mix, planted impulses and NaNs at every tile seam, batch independence,
-transparency at mix = 0, the effect in a Wave and tap-array windows.  The tile and the reach come from the plan query."""
+transparency at mix = 0, the effect in a Wave and tap-array windows.  The tile and the reach come from the plan query.
+
+These tests run the default window (LP = 24) and three symmetric tap arrays (LP = 16 and 72) with stages of equal length.  Every
+register bucket of waveshaper_kernel, stages of unequal length (a tile origin I0 != 0), asymmetric taps read back exactly, the
+extremes of the non-finite reach and the transfer functions' edges are tests/test_gpu_waveshaper_edges.py, over the cases of
+tests/waveshaper_cases.py (checked without a device by tests/test_waveshaper_cases_host.py)."""
 import functools
 
 import numpy as np

@@ -1,7 +1,8 @@
 """StatefulWaveshaper / StatefulDistortion on the host: chunk outputs plus flush() are torch.equal to waveshape() on the whole
 signal for every oversampling factor, shape, dtype, window and chunking; the geometry is the plan query's and does not depend
 on the chunk length; the constant-latency form, restarts, the two processors and Wave, the op's namespace, and what the C
-entry points refuse before they touch a device."""
+entry points refuse before they touch a device.  Both stages have one length here; the stream plan at stages of unequal length, and
+the refusal of gains that are not finite in the signal's dtype, are tests/test_waveshaper_cases_host.py."""
 import ctypes
 
 import numpy as np

@@ -1,7 +1,9 @@
 """The waveshaper without a GPU: the CPU path of torchfx_amd.waveshaper against the float64 definition of
 tests/waveshaper_reference.py within its bound (hard: exact against numpy's clip of the SciPy composition), argument refusals,
 the effects in a Wave and in the stream processors, the op namespace, the host-only plan query against a NaN probe of the CPU
-path, the transfer functions' measured error (tools/shape_sweep.cpp, compiled here) and the alias figures of the design note."""
+path, the transfer functions' measured error (tools/shape_sweep.cpp, compiled here) and the alias figures of the design note.
+The plan at every register bucket and at stages of unequal length, the exact tap probes' own checks and the refusal of gains that
+are not finite in the signal's dtype are tests/test_waveshaper_cases_host.py."""
 import ctypes
 import os
 import re

@@ -468,11 +468,13 @@ static void waveshaper_launch(const void *x, void *y, int64_t rows, int64_t T_, 
 }
 
 // what both entries refuse about the values (host-only)
-static void waveshaper_check_values(const char *who, int64_t oversample, int shape, const void *curve_host, double drive, double bias,
-                                    double dry, double wet, const void *taps_up_host, const void *taps_dn_host)
+static void waveshaper_check_values(const char *who, int dtype, int64_t oversample, int shape, const void *curve_host, double drive,
+                                    double bias, double dry, double wet, const void *taps_up_host, const void *taps_dn_host)
 {
-    TFX_CHECK(std::isfinite(drive) && std::isfinite(bias) && std::isfinite(dry) && std::isfinite(wet),
-              "%s: drive, bias, dry and wet must be finite", who);
+    // as the kernel holds them: a double beyond float32's range rounds to Inf, and silence would shape to 0 * Inf = NaN
+    auto finite = [dtype](double v) { return dtype == TFX_F32 ? std::isfinite((float)v) : std::isfinite(v); };
+    TFX_CHECK(finite(drive) && finite(bias) && finite(dry) && finite(wet), "%s: drive, bias, dry and wet must be finite in %s", who,
+              dtype == TFX_F32 ? "float32" : "float64");
     TFX_CHECK(shape != TFX_SHAPE_CURVE || curve_host, "%s: no curve", who);
     TFX_CHECK(oversample == 1 || (taps_up_host && taps_dn_host), "%s: no taps", who);
 }
@@ -483,7 +485,7 @@ void waveshaper_forward(const void *x, void *y, int dtype, int64_t rows, int64_t
 {
     const char *who = "waveshaper_forward";
     const WsPlan pl = waveshaper_plan(who, dtype, rows, T, oversample, nh_up, nh_dn, shape, curve_n);
-    waveshaper_check_values(who, oversample, shape, curve_host, drive, bias, dry, wet, taps_up_host, taps_dn_host);
+    waveshaper_check_values(who, dtype, oversample, shape, curve_host, drive, bias, dry, wet, taps_up_host, taps_dn_host);
     TFX_CHECK(rows * T == 0 || (x && y), "%s: null pointer", who);
     const int64_t esz = dtype == TFX_F32 ? 4 : 8;
     const char *xb = (const char *)x, *yb = (const char *)y;
@@ -552,7 +554,7 @@ void waveshaper_stream_forward(const void *x, void *y, int dtype, int64_t rows, 
 {
     const char *who = "waveshaper_stream_forward";
     const WsStreamPlan sp = waveshaper_stream_plan(who, dtype, rows, T, oversample, nh_up, nh_dn, shape, curve_n);
-    waveshaper_check_values(who, oversample, shape, curve_host, drive, bias, dry, wet, taps_up_host, taps_dn_host);
+    waveshaper_check_values(who, dtype, oversample, shape, curve_host, drive, bias, dry, wet, taps_up_host, taps_dn_host);
     TFX_CHECK(n_in >= 0 && n_in <= T, "%s: n_in = %lld is not in [0, T = %lld]", who, (long long)n_in, (long long)T);
     TFX_CHECK(consumed >= 0, "%s: negative stream position %lld", who, (long long)consumed);
     TFX_CHECK(rows * T == 0 || y, "%s: null pointer", who);

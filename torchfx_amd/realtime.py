@@ -786,7 +786,10 @@ class _ShaperStream(_HoldBackStream):
         ``Hs = reach_before + reach_after`` (``tfx_waveshaper_stream_plan_info``)."""
         if dtype not in (torch.float32, torch.float64):
             raise TypeError(f"{type(self).__name__}: float32 or float64 signals only, got {dtype}")
+        from torchfx_amd.waveshaper import check_gains
+
         P = self.params()
+        check_gains(P, dtype)
         up, dn = P.taps(dtype)
         taps = None if up is None else (up.numpy().tobytes(), dn.numpy().tobytes())
         geo = self._geometry("waveshaper_stream_plan_info", P.oversample, 0 if up is None else int(up.numel()),

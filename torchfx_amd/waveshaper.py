@@ -136,12 +136,24 @@ def _waveshape_host(x: Tensor, P: ShaperParams) -> Tensor:
     return torch.from_numpy(np.ascontiguousarray(y.astype(u.dtype, copy=False)))
 
 
+def check_gains(P: ShaperParams, dtype: torch.dtype) -> None:
+    """Refuse gains that are finite as Python floats but not in the signal's dtype, which is how both paths hold them: a float32
+    drive of 10^40 is Inf, and silence would shape to ``0 * Inf = NaN``."""
+    if dtype != torch.float32:
+        return
+    with np.errstate(over="ignore"):
+        bad = [n for n in ("drive", "bias", "dry", "wet") if not np.isfinite(np.float32(getattr(P, n)))]
+    if bad:
+        raise ValueError(f"waveshape: {', '.join(bad)} must be finite in the signal's dtype {dtype}")
+
+
 @torch.no_grad()
 def shape_signal(x: Tensor, P: ShaperParams) -> Tensor:
     """:func:`waveshape` with the parameters already checked and reduced (the effects' entry)."""
     _check_signal(x, "waveshape")
     if x.dtype not in (torch.float32, torch.float64):
         raise TypeError(f"waveshape: float32 or float64 signals only, got {x.dtype}")
+    check_gains(P, x.dtype)
     up, dn = P.taps(x.dtype)
     if x.shape[-1] == 0 or x.numel() == 0:
         return torch.empty_like(x)
@@ -185,7 +197,8 @@ def waveshape(x: Tensor, shape: str | None = None, drive_db: float = 0.0, bias: 
       zero-padded filters counts.  An up-sampled value that is not finite shapes to NaN -- the composition's ``tanh`` of an Inf
       would come back finite.  Every other output has the bits it has with a zero in that sample's place.
 
-    Argument errors are ``ValueError`` / ``TypeError`` before any launch.  For chunked streams use
+    Argument errors are ``ValueError`` / ``TypeError`` before any launch; that includes gains that are finite numbers but not in
+    the signal's dtype (``drive_db=800`` on a float32 signal: the drive would be Inf and silence would shape to NaN).  For chunked streams use
     :class:`torchfx_amd.realtime.StatefulWaveshaper` / ``StatefulDistortion``, whose chunks plus ``flush()`` are ``torch.equal`` to
     this call on the whole signal.  Shapes with memory, autograd and axes other than the last are not provided."""
     _check_signal(x, "waveshape")
