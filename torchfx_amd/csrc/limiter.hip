@@ -12,11 +12,12 @@
 // Work unit.  A workgroup of 256 threads is one tile of `tile` = LM_NR + 1 - 2A - H consecutive outputs of one group, and owns
 // LM_NR = 8192 consecutive positions of p / r: the tile, A+H-2 behind, A-1 ahead and one spare at either end.
 //   detect   channel by channel, in two passes of TP_TILE = 4096 positions: the pass's input window is staged transposed in
-//            LDS and every thread runs true_peak_kernel's chain on 16 consecutive positions (taps of a phase as scalar loads,
-//            v_fmac_f32 by hand).  Table phase ph' of position i is output m = i*up + ph' - rem (rem = n_pre_remove mod up):
-//            phases below rem belong to sample i-1 (lo), the others to i (hi).  p[i] = max(|x_i|, hi[i], lo[i+1], hi[i-1],
-//            lo[i]) is accumulated in LDS over the channels; the two terms from a neighbouring thread's positions are added
-//            in a second, barrier-separated step, each LDS word written by one thread per step.  No atomics.
+//            LDS and every thread runs the interpolator chain of polyphase.h on 16 consecutive positions (taps of a phase as
+//            scalar loads, v_fmac_f32 by hand; written out below, not through tp_stage / tp_window / tp_phase).  Table phase ph' of position i is output
+//            m = i*up + ph' - rem (rem = n_pre_remove mod up): phases below rem belong to sample i-1 (lo), the others to i
+//            (hi).  p[i] = max(|x_i|, hi[i], lo[i+1], hi[i-1], lo[i]) is accumulated in LDS over the channels; the two terms
+//            from a neighbouring thread's positions are added in a second, barrier-separated step, each LDS word written by
+//            one thread per step.  No atomics.
 //   r        one correctly rounded division per position
 //   m        exact sliding minimum by log-step doubling in LDS (min over 2^k, then two overlapping windows), staged through
 //            registers so it runs in place
@@ -55,10 +56,10 @@ template <typename T> struct LimiterArgs {
     const T *x;                 // [groups, channels, T_]
     T *y;                       // [groups, channels, T_]
     T *gain;                    // [groups, T_] or null
-    const T *hp;                // [up, LP] (true_peak_kernel's table); unused for up = 1
+    const T *hp;                // [up, LP]: resample_table's layout with LP >= Lp taps per phase; unused for up = 1
     const T *w;                 // [Apad]: the smoothing weights, zeros past A
     int64_t T_, tiles, up;
-    int64_t i_lo, n_lo, n_hi;   // as TruePeakArgs
+    int64_t i_lo, n_lo, n_hi;   // interp_plan's i_lo; n = i*up + phase is an output for n in [n_lo, n_hi)
     int channels, A, Apad, H, tile;
     int rem;                    // n_pre_remove mod up
     int xoff;                   // LP - 1 - i_lo: window offset of a position's own sample
@@ -70,48 +71,15 @@ template <typename T> struct LimiterArgs {
     int D;                      // latency: output t of the chunk is stream position N - D + t
 };
 
-// A row by sample position.  One-shot: x[row] over [0, T_).  Stream: positions [N - Hs, N) come from hist (zeros when null),
-// [N, T_) from x; nothing exists before 0 or from T_ on.
-template <typename T, bool STREAM> struct LmRow {
-    const T *xr, *hr;
-    int64_t N, h0, end;
-    __device__ __forceinline__ LmRow(const LimiterArgs<T> &p, int64_t row) : xr(nullptr), hr(nullptr), N(0), h0(0), end(p.T_)
-    {
-        if constexpr (STREAM) {
-            xr = p.x + row * p.Tc;
-            hr = p.hist ? p.hist + row * p.Hs : nullptr;
-            N = p.N;
-            h0 = p.N - p.Hs;
-        } else {
-            xr = p.x + row * p.T_;
-        }
-    }
-    __device__ __forceinline__ T at(int64_t i) const
-    {
-        if constexpr (STREAM) {
-            if (i < 0 || i >= end) return (T)0;
-            if (i >= N) return xr[i - N];
-            return (hr && i >= h0) ? hr[i - h0] : (T)0;
-        } else {
-            return (i >= 0 && i < end) ? xr[i] : (T)0;
-        }
-    }
-};
+// a row by sample position: x[row] over [0, T_), or the stream's [hist | x]
+template <typename T, bool STREAM> __device__ __forceinline__ StreamRow<T, STREAM> lm_row(const LimiterArgs<T> &p, int64_t row)
+{
+    return StreamRow<T, STREAM>(p.x, STREAM ? p.Tc : p.T_, p.hist, p.Hs, p.N, p.T_, row);
+}
 
 __device__ __forceinline__ int lm_idx(int a) { return a + (a >> 4); }
 template <typename T> __device__ __forceinline__ T lm_max(T a, T b) { return b > a ? b : a; }
 template <typename T> __device__ __forceinline__ T lm_min(T a, T b) { return b < a ? b : a; }
-// the chain's fma with the tap as a scalar operand: the long filters (LP >= 64) have no vector registers left for their taps
-template <bool SCALAR> __device__ __forceinline__ float lm_fma(float tap, float x, float acc)
-{
-    if constexpr (SCALAR) {
-        asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "s"(tap), "v"(x));
-        return acc;
-    } else {
-        return tp_fma(tap, x, acc);
-    }
-}
-template <bool SCALAR> __device__ __forceinline__ double lm_fma(double tap, double x, double acc) { return fma(tap, x, acc); }
 __device__ __forceinline__ float lm_div(float a, float b) { return __fdiv_rn(a, b); }
 __device__ __forceinline__ double lm_div(double a, double b) { return a / b; }
 
@@ -137,12 +105,9 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
     const int np = STREAM ? nout + 2 * p.A + p.H - 2 : LM_NR;    // positions of p / r they depend on (a = 0 is spare)
     if constexpr (STREAM) {
         if (p.hist_out)
-            for (int ch = 0; ch < p.channels; ++ch) {
-                const int64_t row = grp * p.channels + ch;
-                const T *hr = p.hist ? p.hist + row * p.Hs : nullptr;
-                for (int64_t j = tile * LM_THREADS + t; j < p.Hs; j += p.tiles * LM_THREADS)
-                    p.hist_out[row * p.Hs + j] = stream_hist_at(p.x + row * p.Tc, hr, p.n_in, p.Hs, j);
-            }
+            for (int ch = 0; ch < p.channels; ++ch)
+                stream_hist_copy(p.hist_out, p.x, p.Tc, p.hist, p.n_in, p.Hs, grp * p.channels + ch, tile * LM_THREADS + t,
+                                 p.tiles * LM_THREADS);
     }
     {
         const int nz = (STREAM && np + 2 * TP_R < LM_NR) ? np + 2 * TP_R : LM_NR;
@@ -151,7 +116,7 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
     bool bad = false;
     if constexpr (LP == 0) {
         for (int ch = 0; ch < p.channels; ++ch) {
-            const LmRow<T, STREAM> xr(p, grp * p.channels + ch);
+            const auto xr = lm_row<T, STREAM>(p, grp * p.channels + ch);
             for (int a = t; a < np; a += LM_THREADS) {           // a thread's own words only: no barrier
                 const T v = xr.at(rb + a);
                 bad |= !isfinite(v);
@@ -163,12 +128,16 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
         // positions 0 .. np feed p[a], a < np (p[a] takes a term from a + 1): the passes and the threads of a pass that hold one
         const int passes = (STREAM && np < (int)TP_TILE) ? 1 : LM_NR / (int)TP_TILE;
         for (int ch = 0; ch < p.channels; ++ch) {
-            const LmRow<T, STREAM> xr(p, grp * p.channels + ch);
+            const auto xr = lm_row<T, STREAM>(p, grp * p.channels + ch);
             for (int ps = 0; ps < passes; ++ps) {
                 const int a0 = ps * (int)TP_TILE + t * TP_R;     // the thread's first position
                 const bool live = !STREAM || a0 <= np;
                 const int span = STREAM ? min(SPAN, (np - ps * (int)TP_TILE) / TP_R * TP_R + NW) : SPAN;
                 const int64_t s0 = p.i_lo + rb + ps * TP_TILE - (LP - 1);       // first input of the window
+                // What follows is polyphase.h's tp_stage, tp_window, tp_phase (scalar-operand fma for LP >= 64) and tp_phase_at,
+                // written out over tp_win_at and tp_fma.  Through the four helpers this kernel's registers are allocated
+                // differently and a single workgroup's full sweep measured 0.4 to 0.8 % slower; written out, every kernel
+                // has the instruction count it had before polyphase.h held the chain (profiles/interp_chain_refactor.txt).
                 for (int j0 = 0; j0 < span; j0 += LM_THREADS * RS_STAGE_BATCH) {
                     T v[RS_STAGE_BATCH];
 #pragma unroll
@@ -179,7 +148,7 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
 #pragma unroll
                     for (int u = 0; u < RS_STAGE_BATCH; ++u) {
                         const int j = j0 + u * LM_THREADS + t;
-                        if (j < span) reg[(j % TP_R) * S + j / TP_R] = v[u];
+                        if (j < span) tp_win_at<TP_R, S>(reg, 0, j) = v[u];
                         bad |= !isfinite(v[u]);
                     }
                 }
@@ -193,20 +162,20 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
                 } else if (nf >= p.n_lo && nf + (int64_t)TP_R * up <= p.n_hi) {
                     T xw[NW];
 #pragma unroll
-                    for (int k = 0; k < NW; ++k) xw[k] = reg[(k % TP_R) * S + t + k / TP_R];
+                    for (int k = 0; k < NW; ++k) xw[k] = tp_win_at<TP_R, S>(reg, t, k);
 #pragma unroll 1
                     for (int ph = 0; ph < up; ++ph) {
                         const tp_const_ptr<T> h = (tp_const_ptr<T>)(p.hp + ph * LP);
                         T tap[LP > 0 ? LP : 1];
 #pragma unroll
                         for (int j = 0; j < LP; ++j) tap[j] = h[j];
-                        T acc[TP_R];
+                        T acc[TP_R];                             // LP >= 64: no vector registers left for taps, scalar operands
 #pragma unroll
-                        for (int r = 0; r < TP_R; ++r) acc[r] = LP >= 64 ? lm_fma<true>(tap[LP - 1], xw[r], (T)0) : tp_fma0(tap[LP - 1], xw[r]);
+                        for (int r = 0; r < TP_R; ++r) acc[r] = LP >= 64 ? tp_fma<true>(tap[LP - 1], xw[r], (T)0) : tp_fma0(tap[LP - 1], xw[r]);
 #pragma unroll
                         for (int j = LP - 2; j >= 0; --j)
 #pragma unroll
-                            for (int r = 0; r < TP_R; ++r) acc[r] = lm_fma<(LP >= 64)>(tap[j], xw[r + LP - 1 - j], acc[r]);
+                            for (int r = 0; r < TP_R; ++r) acc[r] = tp_fma<(LP >= 64)>(tap[j], xw[r + LP - 1 - j], acc[r]);
                         if (ph < p.rem) {
 #pragma unroll
                             for (int r = 0; r < TP_R; ++r) lo[r] = lm_max(lo[r], (T)fabs(acc[r]));
@@ -224,10 +193,7 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
                             if (n < p.n_lo || n >= p.n_hi) continue;
                             const T *h = p.hp + ph * LP;
                             T acc = (T)0;
-                            for (int j = LP - 1; j >= 0; --j) {
-                                const int k = r + LP - 1 - j;
-                                acc = fma(h[j], reg[(k % TP_R) * S + t + k / TP_R], acc);
-                            }
+                            for (int j = LP - 1; j >= 0; --j) acc = fma(h[j], tp_win_at<TP_R, S>(reg, t, r + LP - 1 - j), acc);
                             if (ph < p.rem) l_ = lm_max(l_, (T)fabs(acc));
                             else h_ = lm_max(h_, (T)fabs(acc));
                         }
@@ -239,8 +205,7 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
                 // step 1: a thread's own 16 positions
 #pragma unroll
                 for (int r = 0; r < TP_R && live; ++r) {
-                    const int k = r + p.xoff;
-                    T v = lm_max(lm_max(hi[r], lo[r]), (T)fabs(reg[(k % TP_R) * S + t + k / TP_R]));
+                    T v = lm_max(lm_max(hi[r], lo[r]), (T)fabs(tp_win_at<TP_R, S>(reg, t, r + p.xoff)));
                     if (r + 1 < TP_R) v = lm_max(v, lo[r + 1 < TP_R ? r + 1 : r]);
                     if (r > 0) v = lm_max(v, hi[r > 0 ? r - 1 : 0]);
                     const int ix = lm_idx(a0 + r);
@@ -310,7 +275,7 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
         for (int e = 0; e < LM_DE; ++e) {
             if (STREAM && e * LM_THREADS >= nd) break;
             const int dl = e * LM_THREADS + t;
-            reg[(dl % TP_R) * LM_SD + dl / TP_R] = d[e];
+            tp_win_at<TP_R, LM_SD>(reg, 0, dl) = d[e];
         }
         __syncthreads();
     }
@@ -326,8 +291,7 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
                 // weights j = jb + jj; output e reads d at o0 + cb + e + 15 - jj, cb = Apad - 16 - jb
                 const int col = t + sw * LM_THREADS + (p.Apad - TP_R - jb) / TP_R;
                 T dv[2 * TP_R - 1], wt[TP_R];
-#pragma unroll
-                for (int u = 0; u < 2 * TP_R - 1; ++u) dv[u] = reg[(u % TP_R) * LM_SD + col + u / TP_R];
+                tp_window<TP_R, LM_SD>(dv, reg, col);
                 const tp_const_ptr<T> wp = (tp_const_ptr<T>)(p.w + jb);
 #pragma unroll
                 for (int jj = 0; jj < TP_R; ++jj) wt[jj] = wp[jj];
@@ -349,7 +313,7 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
     }
     __syncthreads();
     for (int ch = 0; ch < p.channels; ++ch) {
-        const LmRow<T, STREAM> xr(p, grp * p.channels + ch);
+        const auto xr = lm_row<T, STREAM>(p, grp * p.channels + ch);
         T *yr = p.y + (grp * p.channels + ch) * pitch + y0;
         for (int o = t; o < nout; o += LM_THREADS) {
             if constexpr (STREAM) yr[o] = n0 + o < 0 ? (T)0 : rr[lm_idx(o + p.A + p.H - 1)] * xr.at(n0 + o);
@@ -361,9 +325,8 @@ __global__ void __launch_bounds__(LM_THREADS) limiter_kernel(const LimiterArgs<T
             p.gain[grp * pitch + y0 + o] = (STREAM && n0 + o < 0) ? (T)1 : rr[lm_idx(o + p.A + p.H - 1)];
 }
 
-struct LimiterPlan {
-    ResampleGeom g;
-    int64_t LP, i_lo, tile, tiles, halo_left, halo_right, lds;
+struct LimiterPlan : InterpPlan {                 // zeros for up = 1
+    int64_t tile, tiles, halo_left, halo_right, lds;
 };
 
 // everything but the pointers and the values of c and the window (host-only)
@@ -379,16 +342,7 @@ static LimiterPlan limiter_plan(const char *what, int dtype, int64_t groups, int
               (long long)LM_H_MAX);
     TFX_CHECK(T <= (INT64_MAX / 64) / up, "%s: T * up overflows", what);
     LimiterPlan pl{};
-    if (up > 1) {
-        TFX_CHECK(nh >= 1, "%s: no taps", what);
-        TFX_CHECK(nh <= 64 * up, "%s: %lld taps, at most 64 * up = %lld are held in registers", what, (long long)nh,
-                  (long long)(64 * up));
-        pl.g = resample_geometry(T, up, 1, nh);
-        TFX_CHECK(pl.g.Lp <= TP_LP_MAX, "%s: %lld taps per phase", what, (long long)pl.g.Lp);
-        pl.LP = tp_bucket(pl.g.Lp);
-        pl.i_lo = pl.g.pre_remove / up;
-        TFX_CHECK(pl.i_lo <= pl.LP - 1, "%s: the filter's delay exceeds its taps per phase", what);
-    }
+    if (up > 1) static_cast<InterpPlan &>(pl) = interp_plan(what, up, nh, T);
     pl.tile = LM_NR + 1 - 2 * A - H;
     pl.tiles = ceil_div(T, pl.tile);
     pl.halo_left = A + H - 1 + (up > 1 ? pl.LP - 1 - pl.i_lo : 0);
@@ -437,31 +391,10 @@ void limiter_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, i
 // the smoothing weights zero padded to a multiple of 16, by content
 static PlanCache<DeviceBuffer, 2> g_windows(32, "limiter_forward");
 
-template <typename T, int LP, bool STREAM>
-static void limiter_launch_lp(const LimiterArgs<T> &p, int64_t groups, size_t lds, hipStream_t stream)
-{
-    static bool attr_done[TFX_MAX_DEVICES] = {};
-    bool &done = attr_done[current_device()];
-    if (!done) {
-        TFX_HIP(hipFuncSetAttribute((const void *)limiter_kernel<T, LP, STREAM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        done = true;
-    }
-    ProfScope ps(STREAM ? "limiter_stream_kernel" : "limiter_kernel", stream);
-    hipLaunchKernelGGL((limiter_kernel<T, LP, STREAM>), dim3((unsigned)(groups * p.tiles)), dim3(LM_THREADS), lds, stream, p);
-    TFX_HIP(hipGetLastError());
-}
-
-// the stream form's extra arguments (tfx_limiter_stream_forward); N is `consumed` after the clamp
-struct LimiterStreamArgs {
-    const void *hist_in;
-    void *hist_out;
-    int64_t n_in, N, D, Hs;
-};
-
 template <typename T>
 static void limiter_launch(const void *x, void *y, void *gain, int64_t groups, int64_t channels, int64_t T_, double c, int64_t A,
                            int64_t H, const void *window_host, int64_t up, const void *taps_host, int64_t nh,
-                           const LimiterPlan &pl, hipStream_t stream, const LimiterStreamArgs *st = nullptr)
+                           const LimiterPlan &pl, hipStream_t stream, const StreamArgs *st = nullptr)
 {
     std::shared_ptr<DeviceBuffer> table, window;
     LimiterArgs<T> p{};
@@ -485,22 +418,14 @@ static void limiter_launch(const void *x, void *y, void *gain, int64_t groups, i
         p.i_lo = pl.i_lo; p.n_lo = pl.g.pre_remove; p.n_hi = pl.g.pre_remove + T_ * up;
         p.rem = (int)(pl.g.pre_remove % up); p.xoff = (int)(pl.LP - 1 - pl.i_lo);
     }
-    const size_t lds = (size_t)pl.lds;
-#define TFX_LM_CASE(LP_) \
-    if (st) limiter_launch_lp<T, LP_, true>(p, groups, lds, stream); \
-    else limiter_launch_lp<T, LP_, false>(p, groups, lds, stream); \
-    break
-    switch (up > 1 ? pl.LP : 0) {
-    case 0: TFX_LM_CASE(0);
-    case 8: TFX_LM_CASE(8);
-    case 16: TFX_LM_CASE(16);
-    case 24: TFX_LM_CASE(24);
-    case 32: TFX_LM_CASE(32);
-    case 48: TFX_LM_CASE(48);
-    case 64: TFX_LM_CASE(64);
-    default: TFX_LM_CASE((int)TP_LP_MAX);
-    }
-#undef TFX_LM_CASE
+    const auto launch = [&](auto lp) {
+        const int64_t grid = groups * p.tiles;
+        const size_t lds = (size_t)pl.lds;
+        if (st) launch_dynamic_lds<limiter_kernel<T, lp(), true>>("limiter_stream_kernel", grid, LM_THREADS, lds, stream, p);
+        else launch_dynamic_lds<limiter_kernel<T, lp(), false>>("limiter_kernel", grid, LM_THREADS, lds, stream, p);
+    };
+    if (up > 1) tp_dispatch(pl.LP, launch);
+    else launch(std::integral_constant<int, 0>{});         // the sample peak
 }
 
 void limiter_forward(const void *x, void *y, void *gain, int dtype, int64_t groups, int64_t channels, int64_t T, double c,
@@ -537,27 +462,6 @@ static LimiterStreamPlan limiter_stream_plan(int dtype, int64_t groups, int64_t 
     return sp;
 }
 
-// every refusal of limiter_stream_forward (host-only); hands back the plan it built on the way
-static LimiterStreamPlan limiter_stream_check(const void *x, const void *y, const void *gain, int dtype, int64_t groups,
-                                              int64_t channels, int64_t T, int64_t n_in, int64_t consumed, double c, int64_t A,
-                                              int64_t H, const void *window_host, int64_t up, const void *taps_host, int64_t nh,
-                                              const void *hist_in, const void *hist_out)
-{
-    const char *what = "limiter_stream_forward";
-    const LimiterStreamPlan sp = limiter_stream_plan(dtype, groups, channels, T, A, H, up, nh);
-    limiter_check_values(what, dtype, c, A, window_host, up, taps_host);
-    TFX_CHECK(n_in >= 0 && n_in <= T, "%s: n_in = %lld is not in [0, T = %lld]", what, (long long)n_in, (long long)T);
-    TFX_CHECK(consumed >= 0, "%s: negative stream position %lld", what, (long long)consumed);
-    const int64_t rows = groups * channels;
-    TFX_CHECK(rows * T == 0 || y, "%s: null pointer", what);
-    TFX_CHECK(rows * n_in == 0 || x, "%s: null pointer", what);
-    const size_t esz = dtype == TFX_F32 ? 4 : 8;
-    check_stream_buffers(what, esz, x, rows * T, y, rows * T, hist_in, hist_out, rows * sp.Hs);
-    check_stream_buffers(what, esz, x, rows * T, gain, groups * T, hist_in, hist_out, rows * sp.Hs);
-    check_stream_buffers(what, esz, y, rows * T, gain, groups * T, nullptr, nullptr, 0);
-    return sp;
-}
-
 void limiter_stream_plan_info(int64_t groups, int64_t channels, int64_t T, int64_t A, int64_t H, int64_t up, int64_t nh, int dtype,
                               int64_t *latency, int64_t *history, int64_t *tile, int64_t *tiles, int64_t *positions,
                               int64_t *lds_bytes)
@@ -575,21 +479,16 @@ void limiter_stream_forward(const void *x, void *y, void *gain, int dtype, int64
                             int64_t consumed, double c, int64_t A, int64_t H, const void *window_host, int64_t up,
                             const void *taps_host, int64_t nh, const void *hist_in, void *hist_out, hipStream_t stream)
 {
-    const LimiterStreamPlan sp = limiter_stream_check(x, y, gain, dtype, groups, channels, T, n_in, consumed, c, A, H, window_host, up,
-                                                      taps_host, nh, hist_in, hist_out);
+    const char *what = "limiter_stream_forward";
+    const LimiterStreamPlan sp = limiter_stream_plan(dtype, groups, channels, T, A, H, up, nh);
+    limiter_check_values(what, dtype, c, A, window_host, up, taps_host);
     const int64_t rows = groups * channels;
-    if (rows == 0) return;
-    if (T == 0) {                                // nothing in, nothing out: the history moves on unchanged
-        const size_t bytes = (size_t)(rows * sp.Hs) * (dtype == TFX_F32 ? 4 : 8);
-        if (hist_out && bytes) {
-            if (hist_in) TFX_HIP(hipMemcpyAsync(hist_out, hist_in, bytes, hipMemcpyDeviceToDevice, stream));
-            else TFX_HIP(hipMemsetAsync(hist_out, 0, bytes, stream));
-        }
-        return;
-    }
-    // positions before N - Hs are never read and position 0 matters only while it lies in [N - Hs, N + T): past Hs + D every N
-    // gives the same chunk
-    const LimiterStreamArgs st{hist_in, hist_out, n_in, std::min(consumed, sp.Hs + sp.D), sp.D, sp.Hs};
+    const size_t esz = dtype == TFX_F32 ? 4 : 8;
+    StreamArgs st;
+    if (!stream_enter(&st, what, esz, x, y, rows, T, n_in, consumed, sp.D, sp.Hs, hist_in, hist_out, stream)) return;
+    // the gain track against the other buffers (an empty chunk has none)
+    check_stream_buffers(what, esz, x, rows * T, gain, groups * T, hist_in, hist_out, rows * sp.Hs);
+    check_stream_buffers(what, esz, y, rows * T, gain, groups * T, nullptr, nullptr, 0);
     if (dtype == TFX_F32)
         limiter_launch<float>(x, y, gain, groups, channels, T, c, A, H, window_host, up, taps_host, nh, sp.pl, stream, &st);
     else

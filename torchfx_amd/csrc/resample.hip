@@ -98,6 +98,12 @@ __device__ __forceinline__ T rs_load(const ResampleArgs<T> &p, const T *xr, cons
     if (k >= 0) return k < p.T_ ? xr[k] : (T)0;
     return (hr && k >= -p.H) ? hr[k + p.H] : (T)0;
 }
+// rs_load as tp_stage's row
+template <typename T, bool STREAM> struct RsRow {
+    const ResampleArgs<T> &p;
+    const T *xr, *hr;
+    __device__ __forceinline__ T at(int64_t i) const { return rs_load<T, STREAM>(p, xr, hr, i); }
+};
 
 template <typename T, int LP, bool STAGE, bool STREAM>
 __global__ void __launch_bounds__(RS_THREADS) resample_kernel(const ResampleArgs<T> p)
@@ -120,22 +126,7 @@ __global__ void __launch_bounds__(RS_THREADS) resample_kernel(const ResampleArgs
     const int64_t s0 = (m0 / p.up) * p.down + p.pre_div - p.halo;    // first input of the window
     bool finite = true;
     if (STAGE) {
-        const int span = (int)p.span;
-        bool bad = false;
-        for (int j0 = 0; j0 < span; j0 += RS_THREADS * RS_STAGE_BATCH) {
-            T v[RS_STAGE_BATCH];
-#pragma unroll
-            for (int u = 0; u < RS_STAGE_BATCH; ++u) {
-                const int j = j0 + u * RS_THREADS + (int)threadIdx.x;
-                v[u] = j < span ? rs_load<T, STREAM>(p, xr, hr, s0 + j) : (T)0;
-            }
-#pragma unroll
-            for (int u = 0; u < RS_STAGE_BATCH; ++u) {
-                const int j = j0 + u * RS_THREADS + (int)threadIdx.x;
-                if (j < span) win[j] = v[u];
-                bad |= !isfinite(v[u]);
-            }
-        }
+        const bool bad = tp_stage<1, 0, RS_THREADS>(win, RsRow<T, STREAM>{p, xr, hr}, s0, (int)p.span, (int)threadIdx.x);
         finite = !__syncthreads_or(bad);
     }
     const int64_t nq = p.up * p.G, step = p.up * p.G;
@@ -485,12 +476,10 @@ void resample_stream_forward(const void *x, void *y, int dtype, int64_t rows, in
 // positions, holds their TP_R + LP - 1 inputs in registers and runs phase after phase over them.  The taps of a phase are the
 // same for every lane (scalar loads, one move each into a vector register per phase), so a term costs one fma and nothing
 // else; the LDS window is read once per thread, (TP_R + LP - 1) / TP_R reads per position instead of up * Lp.
-//   tile      TP_THREADS * TP_R positions of one row; its window (LP - 1 inputs of halo in front) is staged in LDS as
-//             win[(w % TP_R) * S + w / TP_R]: lane t reads window index t*TP_R + k at column t + k / TP_R of line k % TP_R, so
-//             the lanes of one read are consecutive dwords, and S is chosen so that the 32 (f64: 16) consecutive w of a
-//             staging store fall into distinct banks too
+//   tile      TP_THREADS * TP_R positions of one row; its window (LP - 1 inputs of halo in front) is staged in LDS transposed
+//             (tp_stage, polyphase.h); the chain is tp_phase, this kernel's part is what it does with a phase's sums
 //   edges     only the row's first and last positions have phases that are no output (n outside [pre, pre + T*up)); the two
-//             threads that own them take a plain loop over the window with the bounds test, everyone else the unrolled one
+//             threads that own them take tp_phase_at over the window with the bounds test, everyone else the unrolled chain
 //   reduce    running NaN-propagating max per thread, lane shuffles, LDS across the four waves, ONE writer of work[row, tile];
 //             true_peak_fold_kernel (one workgroup per row) folds work[row, :] into peak[row].  No atomics.
 //   non-finite  a tile whose window holds a NaN or an Inf writes NaN (the row's reading is NaN; other rows are untouched)
@@ -524,27 +513,11 @@ __global__ void __launch_bounds__(TP_THREADS) true_peak_kernel(const TruePeakArg
     __shared__ T part[TP_THREADS / 64];
     T *win = (T *)rs_lds_raw;
     const int64_t row = blockIdx.x / p.tiles, tile = blockIdx.x % p.tiles;
-    const T *xr = p.x + row * p.T_;
+    const StreamRow<T, false> xr(p.x, p.T_, nullptr, 0, 0, p.T_, row);
     const int64_t P0 = tile * TP_TILE;                           // the tile's first position, counted from i_lo
     const int64_t s0 = p.i_lo + P0 - (LP - 1);                   // first input of the window
     const int t = (int)threadIdx.x;
-    bool bad = false;
-    for (int j0 = 0; j0 < SPAN; j0 += TP_THREADS * RS_STAGE_BATCH) {
-        T v[RS_STAGE_BATCH];
-#pragma unroll
-        for (int u = 0; u < RS_STAGE_BATCH; ++u) {
-            const int j = j0 + u * TP_THREADS + t;
-            const int64_t i = s0 + j;
-            v[u] = (j < SPAN && i >= 0 && i < p.T_) ? xr[i] : (T)0;
-        }
-#pragma unroll
-        for (int u = 0; u < RS_STAGE_BATCH; ++u) {
-            const int j = j0 + u * TP_THREADS + t;
-            if (j < SPAN) win[(j % TP_R) * S + j / TP_R] = v[u];
-            bad |= !isfinite(v[u]);
-        }
-    }
-    if (__syncthreads_or(bad)) {
+    if (__syncthreads_or(tp_stage<TP_R, S, TP_THREADS>(win, xr, s0, SPAN, t))) {
         if (t == 0) p.work[blockIdx.x] = (T)NAN;
         return;
     }
@@ -553,24 +526,12 @@ __global__ void __launch_bounds__(TP_THREADS) true_peak_kernel(const TruePeakArg
     T m = (T)0;
     if (nf >= p.n_lo && nf + (int64_t)TP_R * up <= p.n_hi) {
         T xw[NW];
-#pragma unroll
-        for (int k = 0; k < NW; ++k) xw[k] = win[(k % TP_R) * S + t + k / TP_R];
+        tp_window<TP_R, S>(xw, win, t);
         unsigned mb = 0;                                         // f32: |acc| compared as bits, NaN above Inf
 #pragma unroll 1
         for (int ph = 0; ph < up; ++ph) {
-            // the table is read-only for the whole launch: through the constant address space its taps, the same for every
-            // lane, are scalar loads (a global load per lane and tap otherwise)
-            const tp_const_ptr<T> h = (tp_const_ptr<T>)(p.hp + ph * LP);
-            T tap[LP];
-#pragma unroll
-            for (int j = 0; j < LP; ++j) tap[j] = h[j];
             T acc[TP_R];
-#pragma unroll
-            for (int r = 0; r < TP_R; ++r) acc[r] = tp_fma0(tap[LP - 1], xw[r]);
-#pragma unroll
-            for (int j = LP - 2; j >= 0; --j)
-#pragma unroll
-                for (int r = 0; r < TP_R; ++r) acc[r] = tp_fma(tap[j], xw[r + LP - 1 - j], acc[r]);
+            tp_phase<LP>(acc, p.hp + ph * LP, xw);
 #pragma unroll
             for (int r = 0; r < TP_R; ++r) {
                 if constexpr (sizeof(T) == 4) {
@@ -587,13 +548,7 @@ __global__ void __launch_bounds__(TP_THREADS) true_peak_kernel(const TruePeakArg
             for (int ph = 0; ph < up; ++ph) {
                 const int64_t n = nf + (int64_t)r * up + ph;
                 if (n < p.n_lo || n >= p.n_hi) continue;
-                const T *h = p.hp + ph * LP;
-                T acc = (T)0;
-                for (int j = LP - 1; j >= 0; --j) {
-                    const int k = r + LP - 1 - j;
-                    acc = fma(h[j], win[(k % TP_R) * S + t + k / TP_R], acc);
-                }
-                m = tp_max(m, (T)fabs(acc));
+                m = tp_max(m, (T)fabs(tp_phase_at<TP_R, S>(p.hp + ph * LP, LP, LP, win, t, r)));
             }
     }
     m = tp_block_max(m, part);
@@ -610,9 +565,8 @@ template <typename T> __global__ void __launch_bounds__(TP_THREADS) true_peak_fo
     if (threadIdx.x == 0) peak[blockIdx.x] = m;
 }
 
-struct TruePeakPlan {
-    ResampleGeom g;
-    int64_t LP, i_lo, tiles;
+struct TruePeakPlan : InterpPlan {
+    int64_t tiles;
 };
 
 // everything but the pointers (host-only)
@@ -621,15 +575,7 @@ static TruePeakPlan true_peak_plan(int dtype, int64_t rows, int64_t T, int64_t u
     TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "true_peak_forward: bad dtype %d", dtype);
     TFX_CHECK(up == 2 || up == 4 || up == 8, "true_peak_forward: up must be 2, 4 or 8, got %lld", (long long)up);
     TFX_CHECK(rows >= 0 && T >= 0, "true_peak_forward: negative size");
-    TFX_CHECK(nh >= 1, "true_peak_forward: no taps");
-    TFX_CHECK(nh <= 64 * up, "true_peak_forward: %lld taps, at most 64 * up = %lld are held in registers", (long long)nh,
-              (long long)(64 * up));
-    TFX_CHECK(T <= (INT64_MAX / 64) / up, "true_peak_forward: T * up overflows");
-    TruePeakPlan pl{};
-    pl.g = resample_geometry(T, up, 1, nh);
-    TFX_CHECK(pl.g.Lp <= TP_LP_MAX, "true_peak_forward: %lld taps per phase", (long long)pl.g.Lp);
-    pl.LP = tp_bucket(pl.g.Lp);
-    pl.i_lo = pl.g.pre_remove / up;
+    TruePeakPlan pl{interp_plan("true_peak_forward", up, nh, T), 0};
     pl.tiles = T ? ceil_div((pl.g.pre_remove + T * up - 1) / up - pl.i_lo + 1, TP_TILE) : 0;
     TFX_CHECK(rows == 0 || (T <= INT64_MAX / 16 / rows && pl.tiles < (1ll << 31) / rows), "true_peak_forward: size overflows");
     return pl;
@@ -668,15 +614,7 @@ static void true_peak_launch(const void *x, void *peak, int64_t rows, int64_t T_
     const size_t lds = (size_t)TP_R * tp_stride<T>() * sizeof(T);
     {
         ProfScope ps("true_peak_kernel", stream);
-        switch (pl.LP) {
-        case 8: hipLaunchKernelGGL((true_peak_kernel<T, 8>), grid, block, lds, stream, p); break;
-        case 16: hipLaunchKernelGGL((true_peak_kernel<T, 16>), grid, block, lds, stream, p); break;
-        case 24: hipLaunchKernelGGL((true_peak_kernel<T, 24>), grid, block, lds, stream, p); break;
-        case 32: hipLaunchKernelGGL((true_peak_kernel<T, 32>), grid, block, lds, stream, p); break;
-        case 48: hipLaunchKernelGGL((true_peak_kernel<T, 48>), grid, block, lds, stream, p); break;
-        case 64: hipLaunchKernelGGL((true_peak_kernel<T, 64>), grid, block, lds, stream, p); break;
-        default: hipLaunchKernelGGL((true_peak_kernel<T, (int)TP_LP_MAX>), grid, block, lds, stream, p); break;
-        }
+        tp_dispatch(pl.LP, [&](auto lp) { hipLaunchKernelGGL((true_peak_kernel<T, lp()>), grid, block, lds, stream, p); });
         TFX_HIP(hipGetLastError());
     }
     ProfScope ps("true_peak_fold_kernel", stream);

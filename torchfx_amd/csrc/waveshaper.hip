@@ -4,11 +4,11 @@
 // (include/torchfx_hip.h has the definition).  Both FIR stages are recursion-free, so a tile with halos is exact: a workgroup
 // owns WS_THREADS * R input positions of one row, N = WS_THREADS * R - Ku of them outputs and Ku of them the halo the decimator
 // needs, reads each sample once, keeps the oversampled signal in LDS only and writes each output once.
-//   stage   the positions' window (LP - 1 inputs of halo in front, zeros outside [0, T)) goes to LDS as true_peak_kernel's:
-//           win[(k % R) * S + k / R], so a thread reads its R + LP - 1 consecutive inputs at consecutive addresses across lanes
-//   up      thread t owns R consecutive positions and runs phase after phase over the inputs it holds in registers: the
-//           per-output sum is resample_forward's (a descending-j fma chain from +0 over hp[phase][j]; the taps of a phase are
-//           wave-uniform scalar loads through the constant address space)
+//   stage   the positions' window (LP - 1 inputs of halo in front, zeros outside [0, T)) goes to LDS transposed (tp_stage,
+//           polyphase.h), so a thread reads its R + LP - 1 consecutive inputs at consecutive addresses across lanes
+//   up      thread t owns R consecutive positions and runs phase after phase over the inputs it holds in registers (tp_phase):
+//           the per-output sum is resample_forward's (a descending-j fma chain from +0 over hp[phase][j]; the taps of a phase
+//           are wave-uniform scalar loads through the constant address space)
 //   shape   drive, bias, f, - c0 in registers; an up-sampled value that is not finite shapes to NaN; values outside [0, T*L)
 //           are zeros.  The shaped sample n goes to wbuf[n mod L][n div L]: one line per phase of the decimator.  A thread's R
 //           columns are consecutive, so a line's columns are spread with one pad per 32 (ws_col): the R-strided stores of a
@@ -78,34 +78,6 @@ template <typename T> struct WsArgs {
     int ends;                   // n_in < Tc: the stream ends at T_, the shaped signal is cut there
 };
 
-// A row by sample position.  One-shot: x[row] over [0, T_).  Stream: positions [Nc - Hs, Nc) come from hist (zeros when null),
-// [Nc, T_) from x; nothing exists before 0 or from T_ on.
-template <typename T, bool STREAM> struct WsRow {
-    const T *xr, *hr;
-    int64_t N, h0, end;
-    __device__ __forceinline__ WsRow(const WsArgs<T> &p, int64_t row) : xr(nullptr), hr(nullptr), N(0), h0(0), end(p.T_)
-    {
-        if constexpr (STREAM) {
-            xr = p.x + row * p.Tc;
-            hr = p.hist ? p.hist + row * p.Hs : nullptr;
-            N = p.Nc;
-            h0 = p.Nc - p.Hs;
-        } else {
-            xr = p.x + row * p.T_;
-        }
-    }
-    __device__ __forceinline__ T at(int64_t i) const
-    {
-        if constexpr (STREAM) {
-            if (i < 0 || i >= end) return (T)0;
-            if (i >= N) return xr[i - N];
-            return (hr && i >= h0) ? hr[i - h0] : (T)0;
-        } else {
-            return (i >= 0 && i < end) ? xr[i] : (T)0;
-        }
-    }
-};
-
 template <typename T> __device__ __forceinline__ T ws_shape(int shape, T u, const WsArgs<T> &p, const T *curve)
 {
     const T v = shape_fn::add(shape_fn::mul(p.drive, u), p.bias);
@@ -164,8 +136,8 @@ __global__ void __launch_bounds__(WS_THREADS) waveshaper_kernel(const WsArgs<T> 
     T *wbuf = win + R * S;                                      // [L][WS]
     T *curve = wbuf + p.L * WS;                                 // [curve_n]
     const int64_t row = blockIdx.x / p.tiles, tile = blockIdx.x % p.tiles;
-    const WsRow<T, STREAM> xr(p, row);
-    const int64_t pitch = STREAM ? p.Tc : p.T_, y0 = tile * p.N;  // rows of y, the tile's first sample in them
+    const int64_t pitch = STREAM ? p.Tc : p.T_, y0 = tile * p.N;  // rows of x and y, the tile's first sample in them
+    const StreamRow<T, STREAM> xr(p.x, pitch, p.hist, p.Hs, p.Nc, p.T_, row);
     T *yr = p.y + row * pitch + y0;
     const int64_t m0 = y0 - (STREAM ? p.lat - p.Nc : 0);        // position of the tile's first output
     const int64_t left = pitch - y0;
@@ -177,27 +149,10 @@ __global__ void __launch_bounds__(WS_THREADS) waveshaper_kernel(const WsArgs<T> 
     const int64_t s0 = m0 + p.I0 - (LP - 1);                    // first input of the window
     const int t = (int)threadIdx.x;
     if constexpr (STREAM) {
-        if (p.hist_out) {
-            const T *hr = p.hist ? p.hist + row * p.Hs : nullptr;
-            for (int64_t j = tile * WS_THREADS + t; j < p.Hs; j += p.tiles * WS_THREADS)
-                p.hist_out[row * p.Hs + j] = stream_hist_at(p.x + row * p.Tc, hr, p.n_in, p.Hs, j);
-        }
+        if (p.hist_out)
+            stream_hist_copy(p.hist_out, p.x, p.Tc, p.hist, p.n_in, p.Hs, row, tile * WS_THREADS + t, p.tiles * WS_THREADS);
     }
-    bool bad = false;
-    for (int j0 = 0; j0 < span; j0 += WS_THREADS * RS_STAGE_BATCH) {
-        T v[RS_STAGE_BATCH];
-#pragma unroll
-        for (int u = 0; u < RS_STAGE_BATCH; ++u) {
-            const int j = j0 + u * WS_THREADS + t;
-            v[u] = j < span ? xr.at(s0 + j) : (T)0;
-        }
-#pragma unroll
-        for (int u = 0; u < RS_STAGE_BATCH; ++u) {
-            const int j = j0 + u * WS_THREADS + t;
-            if (j < span) win[(j % R) * S + j / R] = v[u];
-            bad |= !isfinite(v[u]);
-        }
-    }
+    const bool bad = tp_stage<R, S, WS_THREADS>(win, xr, s0, span, t);
     if (p.shape == shape_fn::CURVE)
         for (int k = t; k < p.curve_n; k += WS_THREADS) curve[k] = p.curve[k];
     const bool finite = !__syncthreads_or(bad);
@@ -212,35 +167,15 @@ __global__ void __launch_bounds__(WS_THREADS) waveshaper_kernel(const WsArgs<T> 
     // stream: a wave none of whose positions is read skips `up` and `shape` (wave-uniform)
     const bool active = !STREAM || __builtin_amdgcn_readfirstlane(t >> 6) * WV < npos;
     T xw[NW];
-    if (finite && active) {
-#pragma unroll
-        for (int k = 0; k < NW; ++k) xw[k] = win[(k % R) * S + t + k / R];
-    }
+    if (finite && active) tp_window<R, S>(xw, win, t);
 #pragma unroll 1
     for (int ph = 0; active && ph < p.L; ++ph) {
         T acc[R];
         if (finite) {
-            const tp_const_ptr<T> h = (tp_const_ptr<T>)(p.hup + ph * LP);
-            T tap[LP];
-#pragma unroll
-            for (int j = 0; j < LP; ++j) tap[j] = h[j];
-#pragma unroll
-            for (int r = 0; r < R; ++r) acc[r] = tp_fma0(tap[LP - 1], xw[r]);
-#pragma unroll
-            for (int j = LP - 2; j >= 0; --j)
-#pragma unroll
-                for (int r = 0; r < R; ++r) acc[r] = tp_fma(tap[j], xw[r + LP - 1 - j], acc[r]);
+            tp_phase<LP>(acc, p.hup + ph * LP, xw);
         } else {
-            const T *h = p.hup + ph * LP;
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                T a = (T)0;
-                for (int j = p.Lp_up - 1; j >= 0; --j) {
-                    const int k = r + LP - 1 - j;
-                    a = fma(h[j], win[(k % R) * S + t + k / R], a);
-                }
-                acc[r] = a;
-            }
+            for (int r = 0; r < R; ++r) acc[r] = tp_phase_at<R, S>(p.hup + ph * LP, p.Lp_up, LP, win, t, r);
         }
         const int sh = ph + p.D, line = sh & (p.L - 1), col0 = t * R + (sh >> p.logL);
         T *wline = wbuf + line * WS;
@@ -259,8 +194,7 @@ __global__ void __launch_bounds__(WS_THREADS) waveshaper_kernel(const WsArgs<T> 
     for (int e = 0; e < R; ++e) {
         const int m = t + WS_THREADS * e;
         if constexpr (STREAM) {                                 // position m0 + m is window index m - I0 + LP - 1
-            const int k = m - p.I0 + LP - 1;
-            xv[e] = m < mend ? win[(k % R) * S + k / R] : (T)0;
+            xv[e] = m < mend ? tp_win_at<R, S>(win, 0, m - p.I0 + LP - 1) : (T)0;
         } else {
             xv[e] = m < mend ? xr.xr[m0 + m] : (T)0;
         }
@@ -308,6 +242,7 @@ template <typename T, bool ENDS> __global__ void __launch_bounds__(WS_THREADS) w
 
 struct WsPlan {
     int64_t L, logL, Lp_up, Lp_dn, LP, N, tiles, I0, D, Q0, CA, ncols, reach_before, reach_after, lds;
+    int64_t KX;                 // a stream's (waveshaper_stream_plan), else 0
     ResampleGeom gu, gd;
 };
 
@@ -341,12 +276,14 @@ static WsPlan waveshaper_plan(const char *who, int dtype, int64_t rows, int64_t 
     TFX_CHECK(nh_up <= 64 * L && nh_dn <= 64 * L, "%s: %lld and %lld taps, each stage takes at most 64 * oversample = %lld", who,
               (long long)nh_up, (long long)nh_dn, (long long)(64 * L));
     pl.logL = L == 2 ? 1 : (L == 4 ? 2 : 3);
-    pl.gu = resample_geometry(T, L, 1, nh_up);
+    // none of interp_plan's refusals can fire here: nh_up and T are checked above, nh_up <= 64 L gives Lp <= 65, and with
+    // down = 1 i_lo = ((nh_up - 1) / 2 + 1) / L <= Lp - 1
+    const InterpPlan ip = interp_plan(who, L, nh_up, T);
+    pl.gu = ip.g;
     pl.gd = resample_geometry(T * L, 1, L, nh_dn);
     pl.Lp_up = pl.gu.Lp;
     pl.Lp_dn = pl.gd.Lp;
-    TFX_CHECK(pl.Lp_up <= TP_LP_MAX, "%s: %lld taps per phase", who, (long long)pl.Lp_up);
-    pl.LP = tp_bucket(pl.Lp_up);
+    pl.LP = ip.LP;
     const int64_t PT = dtype == TFX_F32 ? ws_positions<float>() : ws_positions<double>();
     const int64_t WS = dtype == TFX_F32 ? ws_wstride<float>() : ws_wstride<double>();
     const int64_t RS = dtype == TFX_F32 ? ws_r<float>() * ws_stride<float>() : ws_r<double>() * ws_stride<double>();
@@ -390,32 +327,11 @@ void waveshaper_plan_info(int64_t rows, int64_t T, int64_t oversample, int64_t n
 // curve tables by content (the bytes plus the element size)
 static PlanCache<DeviceBuffer, 1> g_curves(32, "waveshaper_forward");
 
-template <typename T, int LP, bool STREAM>
-static void waveshaper_launch_lp(const WsArgs<T> &p, int64_t rows, size_t lds, hipStream_t stream)
-{
-    static size_t attr[TFX_MAX_DEVICES] = {};
-    size_t &have = attr[current_device()];
-    if (lds > have) {
-        TFX_HIP(hipFuncSetAttribute((const void *)waveshaper_kernel<T, LP, STREAM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        have = lds;
-    }
-    ProfScope ps(STREAM ? "waveshaper_stream_kernel" : "waveshaper_kernel", stream);
-    hipLaunchKernelGGL((waveshaper_kernel<T, LP, STREAM>), dim3((unsigned)(rows * p.tiles)), dim3(WS_THREADS), lds, stream, p);
-    TFX_HIP(hipGetLastError());
-}
-
-// the stream form's extra arguments (tfx_waveshaper_stream_forward); N is `consumed` after the clamp
-struct WsStreamArgs {
-    const void *hist_in;
-    void *hist_out;
-    int64_t n_in, N, D, Hs, KX;
-};
-
 template <typename T>
 static void waveshaper_launch(const void *x, void *y, int64_t rows, int64_t T_, int shape, const void *curve_host, int64_t curve_n,
                               double drive, double bias, double dry, double wet, const void *taps_up_host, int64_t nh_up,
                               const void *taps_dn_host, int64_t nh_dn, const WsPlan &pl, hipStream_t stream,
-                              const WsStreamArgs *st = nullptr)
+                              const StreamArgs *st = nullptr)
 {
     std::shared_ptr<DeviceBuffer> tup, tdn, tcurve;
     WsArgs<T> p{};
@@ -425,7 +341,7 @@ static void waveshaper_launch(const void *x, void *y, int64_t rows, int64_t T_, 
     p.drive = (T)drive; p.bias = (T)bias; p.dry = (T)dry; p.wet = (T)wet;
     if (st) {                                   // T_ is the chunk's length; the kernel's T_ is where the stream's inputs end so far
         p.hist = (const T *)st->hist_in; p.hist_out = (T *)st->hist_out;
-        p.Tc = T_; p.Nc = st->N; p.Hs = st->Hs; p.n_in = st->n_in; p.lat = (int)st->D; p.KX = (int)st->KX; p.ends = st->n_in < T_;
+        p.Tc = T_; p.Nc = st->N; p.Hs = st->Hs; p.n_in = st->n_in; p.lat = (int)st->D; p.KX = (int)pl.KX; p.ends = st->n_in < T_;
         p.T_ = st->N + st->n_in;
     }
     // c0 = f(bias) in float64 (bias and the curve as the signal's dtype holds them), rounded once
@@ -450,21 +366,12 @@ static void waveshaper_launch(const void *x, void *y, int64_t rows, int64_t T_, 
     }
     p.hup = resample_table<T>(taps_up_host, nh_up, pl.L, 1, pl.gu.pre_pad, pl.LP, stream, &tup);
     p.hdn = resample_table<T>(taps_dn_host, nh_dn, 1, pl.L, pl.gd.pre_pad, pl.Lp_dn, stream, &tdn);
-    const size_t lds = (size_t)pl.lds;
-#define TFX_WS_CASE(LP_) \
-    if (st) waveshaper_launch_lp<T, LP_, true>(p, rows, lds, stream); \
-    else waveshaper_launch_lp<T, LP_, false>(p, rows, lds, stream); \
-    break
-    switch (pl.LP) {
-    case 8: TFX_WS_CASE(8);
-    case 16: TFX_WS_CASE(16);
-    case 24: TFX_WS_CASE(24);
-    case 32: TFX_WS_CASE(32);
-    case 48: TFX_WS_CASE(48);
-    case 64: TFX_WS_CASE(64);
-    default: TFX_WS_CASE((int)TP_LP_MAX);
-    }
-#undef TFX_WS_CASE
+    tp_dispatch(pl.LP, [&](auto lp) {
+        const int64_t grid = rows * p.tiles;
+        const size_t lds = (size_t)pl.lds;
+        if (st) launch_dynamic_lds<waveshaper_kernel<T, lp(), true>>("waveshaper_stream_kernel", grid, WS_THREADS, lds, stream, p);
+        else launch_dynamic_lds<waveshaper_kernel<T, lp(), false>>("waveshaper_kernel", grid, WS_THREADS, lds, stream, p);
+    });
 }
 
 // what both entries refuse about the values (host-only)
@@ -508,7 +415,7 @@ void waveshaper_forward(const void *x, void *y, int dtype, int64_t rows, int64_t
 // read the positions up to n + KX, KX = Q0 - ceil(D_w / L) - 1 = reach_before - 1 - I0 (a whole tile: all PT of them).
 struct WsStreamPlan {
     WsPlan pl;
-    int64_t D, Hs, KX, positions;
+    int64_t D, Hs, positions;
 };
 
 static WsStreamPlan waveshaper_stream_plan(const char *who, int dtype, int64_t rows, int64_t T, int64_t L, int64_t nh_up,
@@ -520,16 +427,16 @@ static WsStreamPlan waveshaper_stream_plan(const char *who, int dtype, int64_t r
         sp.positions = std::min(T, sp.pl.N);
         return sp;
     }
-    const WsPlan &pl = sp.pl;
+    WsPlan &pl = sp.pl;
     const int64_t PT = dtype == TFX_F32 ? ws_positions<float>() : ws_positions<double>(), WV = PT / (WS_THREADS / 64);
     sp.D = pl.reach_before;
     sp.Hs = pl.reach_before + pl.reach_after;
-    sp.KX = pl.Q0 - ceil_div(pl.D + (1 << 20) * L, L) + (1 << 20) - 1;          // ceil of a D_w that may be negative
+    pl.KX = pl.Q0 - ceil_div(pl.D + (1 << 20) * L, L) + (1 << 20) - 1;          // ceil of a D_w that may be negative
     // the dry sample of output o is position o - I0 of the tile: staged with the positions 0 .. o + KX, at a window index >= 0
-    TFX_CHECK(pl.reach_before >= 1 && pl.reach_after >= 0 && pl.I0 <= pl.LP - 1 && sp.KX == pl.reach_before - 1 - pl.I0 &&
-                  pl.N + sp.KX == PT - 1,
+    TFX_CHECK(pl.reach_before >= 1 && pl.reach_after >= 0 && pl.I0 <= pl.LP - 1 && pl.KX == pl.reach_before - 1 - pl.I0 &&
+                  pl.N + pl.KX == PT - 1,
               "%s: the filters' geometry does not fit the stream", who);
-    sp.positions = T == 0 ? 0 : std::min(PT, ((std::min(T, pl.N) + sp.KX) / WV + 1) * WV);
+    sp.positions = T == 0 ? 0 : std::min(PT, ((std::min(T, pl.N) + pl.KX) / WV + 1) * WV);
     return sp;
 }
 
@@ -555,24 +462,9 @@ void waveshaper_stream_forward(const void *x, void *y, int dtype, int64_t rows, 
     const char *who = "waveshaper_stream_forward";
     const WsStreamPlan sp = waveshaper_stream_plan(who, dtype, rows, T, oversample, nh_up, nh_dn, shape, curve_n);
     waveshaper_check_values(who, dtype, oversample, shape, curve_host, drive, bias, dry, wet, taps_up_host, taps_dn_host);
-    TFX_CHECK(n_in >= 0 && n_in <= T, "%s: n_in = %lld is not in [0, T = %lld]", who, (long long)n_in, (long long)T);
-    TFX_CHECK(consumed >= 0, "%s: negative stream position %lld", who, (long long)consumed);
-    TFX_CHECK(rows * T == 0 || y, "%s: null pointer", who);
-    TFX_CHECK(rows * n_in == 0 || x, "%s: null pointer", who);
+    StreamArgs st;
     const size_t esz = dtype == TFX_F32 ? 4 : 8;
-    check_stream_buffers(who, esz, x, rows * T, y, rows * T, hist_in, hist_out, rows * sp.Hs);
-    if (rows == 0) return;
-    if (T == 0) {                                // nothing in, nothing out: the history moves on unchanged
-        const size_t bytes = (size_t)(rows * sp.Hs) * esz;
-        if (hist_out && bytes) {
-            if (hist_in) TFX_HIP(hipMemcpyAsync(hist_out, hist_in, bytes, hipMemcpyDeviceToDevice, stream));
-            else TFX_HIP(hipMemsetAsync(hist_out, 0, bytes, stream));
-        }
-        return;
-    }
-    // positions before N - Hs are never read and position 0 matters only while it lies in [N - Hs, N + T): past Hs + D every N
-    // gives the same chunk
-    const WsStreamArgs st{hist_in, hist_out, n_in, std::min(consumed, sp.Hs + sp.D), sp.D, sp.Hs, sp.KX};
+    if (!stream_enter(&st, who, esz, x, y, rows, T, n_in, consumed, sp.D, sp.Hs, hist_in, hist_out, stream)) return;
     if (dtype == TFX_F32)
         waveshaper_launch<float>(x, y, rows, T, shape, curve_host, curve_n, drive, bias, dry, wet, taps_up_host, nh_up, taps_dn_host,
                                  nh_dn, sp.pl, stream, &st);
