@@ -901,6 +901,38 @@ int tfx_stft_plan_info(int64_t n_fft, int64_t hop, int64_t win_length, int64_t T
                        int64_t *lds_bytes, int64_t *workgroups);
 
 /* ---------------------------------------------------------------------------
+ * tfx_istft_forward -- inverse short-time Fourier transform of every row of spec [rows, frames, M + 1] (M = n_fft / 2; complex,
+ * interleaved re / im of dtype; the buffer tfx_stft_forward writes), torch.istft's onesided semantics:
+ *   1. s_f = irfft(spec[row, f, :], n_fft), scaled once by 1 / n_fft (n_fft^-1/2 when `normalized`); the imaginary parts of
+ *      bins 0 and M are not read.
+ *   2. num[t] = sum_f dtype(w[t - f hop] * s_f[t - f hop]),  env[t] = sum_f dtype(w[t - f hop]^2): over the frames that cover t,
+ *      in ascending frame order, starting from zero, in dtype; w is `window` [win_length] centred in n_fft zeros, ones when
+ *      window is null.  Both products are always formed, so a non-finite frame reaches every sample it covers, also under a
+ *      zero of the window.
+ *   3. out[row, t - pad] = num[t] / env[t] for 0 <= t - pad < length; positions past the last frame ((frames - 1) hop + n_fft)
+ *      read 0.  length = -1 is the natural length (frames - 1) hop + n_fft - 2 pad.
+ * spec, window, out [rows, length] and flag (one int) DEVICE.  *flag is cleared on the stream, then set to 1 by every thread
+ * that meets !(|env[t]| > 1e-11) on a returned position under a frame (torch's "window overlap add min" condition): the caller
+ * reads it when it may synchronise.  One launch: a workgroup owns `tile` consecutive output samples of one row, transforms the
+ * frames that cover them (frames_per_batch at a time, threads_per_frame threads each, the forward transform's stages and
+ * tables run on the conjugate) and adds them in frame order in registers: no atomics, nothing but out and flag written.  A
+ * frame that straddles two tiles is transformed by both, to the same bits, so a sample's bits depend on the frames that cover
+ * it and the window alone -- not on the tile, the row, the batch or the frame count.
+ * Served: n_fft in {256, 512, 1024, 2048, 4096}, 1 <= hop <= win_length <= n_fft, 0 <= pad <= n_fft; anything else is refused
+ * (tfx_istft_plan_info says route 0: the caller takes torch.istft).  Arguments are checked before the device is touched.
+ * ------------------------------------------------------------------------- */
+int tfx_istft_forward(const void *spec, const void *window_or_null, void *out, int *flag, int dtype, int64_t rows, int64_t frames,
+                      int64_t n_fft, int64_t hop, int64_t win_length, int64_t pad, int64_t length, int normalized, tfx_stream_t stream);
+/* what an ISTFT of this geometry does (host-only, same checks on the sizes; pad = n_fft / 2 when `center`, length -1 = natural):
+ * route (1: the LDS kernel, 0: not served -- another n_fft, a two-sided spectrum), the output length and, for route 1, the
+ * samples of a tile, the frames of a batch, the threads per frame, the LDS bytes of a workgroup, the workgroups of the launch
+ * (rows * ceil(length / tile); 0 for route 0) and the share of the transforms that a neighbouring tile runs too:
+ * e / (tile / hop + e), e = ceil(n_fft / hop) - 1 */
+int tfx_istft_plan_info(int64_t n_fft, int64_t hop, int64_t win_length, int64_t frames, int64_t rows, int dtype, int center,
+                        int64_t length, int onesided, int *route, int64_t *out_length, int64_t *tile, int64_t *frames_per_batch,
+                        int64_t *threads_per_frame, int64_t *lds_bytes, int64_t *workgroups, double *redundant_share);
+
+/* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of
  * ParallelFilterCombination.forward, src/torchfx/filter/__base.py:1019-1026).
  * xs_host: HOST array of n DEVICE pointers, each [numel] of dtype.

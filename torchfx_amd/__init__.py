@@ -18,11 +18,11 @@ from torchfx_amd.modulation import modulated_delay
 from torchfx_amd.phaser import phase_shift
 from torchfx_amd.resample import Resample, resample_poly
 from torchfx_amd.reverb import freeverb, freeverb_bank
-from torchfx_amd.spectral import spectrogram, stft
+from torchfx_amd.spectral import istft, spectrogram, stft
 from torchfx_amd.wave import Wave
 from torchfx_amd.waveshaper import waveshape
 
 __all__ = ["FX", "Chorus", "Compressor", "Delay", "Distortion", "FilterChain", "Flanger", "Freeverb", "Gain", "Gate", "Limiter", "LoudnessNormalize", "ModulatedDelay", "Normalize", "Phaser", "Resample", "Reverb", "Wave", "block_energy",
-           "compress", "filter", "freeverb", "freeverb_bank", "gate", "integrated_loudness", "is_native_available", "kweighting_sos", "limit", "loudness_range", "modulated_delay", "momentary_loudness",
+           "compress", "filter", "freeverb", "freeverb_bank", "gate", "integrated_loudness", "is_native_available", "istft", "kweighting_sos", "limit", "loudness_range", "modulated_delay", "momentary_loudness",
            "phase_shift", "resample_poly", "short_term_loudness", "sosfiltfilt", "spectrogram", "stft", "true_peak", "true_peak_linear", "Vibrato", "Waveshaper", "waveshape"]
 __version__ = "0.1.0"

@@ -109,6 +109,9 @@ SIGNATURES = {
     "tfx_gate_plan_info": (_int, [_i64, _i64, _i64, _i64] + [ctypes.POINTER(_i64)] * 5),
     "tfx_stft_forward": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _vp]),
     "tfx_stft_plan_info": (_int, [_i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, ctypes.POINTER(_int)] + [ctypes.POINTER(_i64)] * 5),
+    "tfx_istft_forward": (_int, [_vp, _vp, _vp, ctypes.POINTER(_int), _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp]),
+    "tfx_istft_plan_info": (_int, [_i64, _i64, _i64, _i64, _i64, _int, _int, _i64, _int, ctypes.POINTER(_int)] + [ctypes.POINTER(_i64)] * 6
+                            + [ctypes.POINTER(ctypes.c_double)]),
     "tfx_sum_forward": (_int, [_vp, _int, _vp, _int, _i64, _vp]),
     "tfx_gain_forward": (_int, [_vp, _vp, _int, _i64, _dbl, _int, _vp]),
     "tfx_stat_forward": (_int, [_vp, _int, _i64, _i64, _int, _int, _vp, _vp]),

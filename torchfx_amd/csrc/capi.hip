@@ -864,6 +864,26 @@ int tfx_stft_plan_info(int64_t n_fft, int64_t hop, int64_t win_length, int64_t T
     TFX_API_END
 }
 
+int tfx_istft_forward(const void *spec, const void *window_or_null, void *out, int *flag, int dtype, int64_t rows, int64_t frames,
+                      int64_t n_fft, int64_t hop, int64_t win_length, int64_t pad, int64_t length, int normalized, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    istft_forward(spec, window_or_null, out, flag, dtype, rows, frames, n_fft, hop, win_length, pad, length, normalized, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_istft_plan_info(int64_t n_fft, int64_t hop, int64_t win_length, int64_t frames, int64_t rows, int dtype, int center,
+                        int64_t length, int onesided, int *route, int64_t *out_length, int64_t *tile, int64_t *frames_per_batch,
+                        int64_t *threads_per_frame, int64_t *lds_bytes, int64_t *workgroups, double *redundant_share)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(route && out_length && tile && frames_per_batch && threads_per_frame && lds_bytes && workgroups && redundant_share,
+              "istft_plan_info: null output");
+    istft_plan_info(n_fft, hop, win_length, frames, rows, dtype, center, length, onesided, route, out_length, tile, frames_per_batch,
+                    threads_per_frame, lds_bytes, workgroups, redundant_share);
+    TFX_API_END
+}
+
 int tfx_sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, tfx_stream_t stream)
 {
     TFX_API_BEGIN

@@ -715,6 +715,66 @@ Tensor stft_op(const Tensor &x_in, const OptTensor &window, int64_t n_fft, int64
     return out.transpose(-1, -2);
 }
 
+// Inverse short-time Fourier transform (tfx_istft_forward): spec [bins, frames], [C, bins, frames] or [B, C, bins, frames],
+// complex64 / complex128 with bins = n_fft / 2 + 1; window a 1-D device tensor of the matching real dtype with hop <= numel <=
+// n_fft (centred in zeros) or None (ones over n_fft); pad samples cut from each end; length -1 = natural -> (y [..., T] of the
+// real dtype, flag [1] int32: 1 where the window envelope vanishes, which the caller reads when it may synchronise).  The kernel
+// reads the buffer stft_forward writes -- the transpose of a contiguous [..., frames, bins] -- in place; any other layout is
+// copied into it first.
+struct IstftShape {
+    std::vector<int64_t> sizes;     // [..., T]
+    at::ScalarType dtype;
+    int64_t win_length, frames;
+};
+
+IstftShape istft_shape(const Tensor &spec, const OptTensor &window, int64_t n_fft, int64_t hop, int64_t pad, int64_t length, const char *what)
+{
+    TORCH_CHECK(spec.dim() >= 2 && spec.dim() <= 4, what, ": spec must be [bins, frames], [C, bins, frames] or [B, C, bins, frames], got ",
+                spec.dim(), " dimensions");
+    TORCH_CHECK(spec.scalar_type() == at::kComplexFloat || spec.scalar_type() == at::kComplexDouble, what,
+                ": expected a complex64 or complex128 tensor, got ", spec.scalar_type());
+    TORCH_CHECK(n_fft >= 2 && spec.size(-2) == n_fft / 2 + 1, what, ": expected the frequency dimension (2nd to the last) to be n_fft / 2 + 1 = ",
+                n_fft / 2 + 1, ", got ", spec.size(-2));
+    TORCH_CHECK(spec.size(-1) >= 1 && hop >= 1 && pad >= 0 && (length == -1 || length >= 1), what, ": bad geometry (frames ", spec.size(-1),
+                ", hop ", hop, ", pad ", pad, ", length ", length, ")");
+    IstftShape s;
+    s.dtype = spec.scalar_type() == at::kComplexFloat ? at::kFloat : at::kDouble;
+    s.win_length = n_fft;
+    s.frames = spec.size(-1);
+    if (window.has_value() && window->defined()) {
+        TORCH_CHECK(window->dim() == 1 && window->numel() >= 1 && window->numel() <= n_fft, what, ": window must be 1-D with 1 to n_fft values");
+        TORCH_CHECK(window->scalar_type() == s.dtype && window->device() == spec.device(), what,
+                    ": window must have spec's real dtype and device");
+        s.win_length = window->numel();
+    }
+    TORCH_CHECK(hop <= s.win_length, what, ": expected 0 < hop <= win_length, got hop ", hop, " and win_length ", s.win_length);
+    const int64_t T = length == -1 ? (s.frames - 1) * hop + n_fft - 2 * pad : length;
+    TORCH_CHECK(T >= 1, what, ": ", s.frames, " frames leave no sample after ", pad, " are cut from each end");
+    s.sizes.assign(spec.sizes().begin(), spec.sizes().end() - 2);
+    s.sizes.push_back(T);
+    return s;
+}
+
+std::tuple<Tensor, Tensor> istft_op(const Tensor &spec_in, const OptTensor &window, int64_t n_fft, int64_t hop, int64_t pad, int64_t length,
+                                    bool normalized)
+{
+    const char *what = "istft_forward";
+    need_device(spec_in, "spec");
+    const IstftShape s = istft_shape(spec_in, window, n_fft, hop, pad, length, what);
+    const Tensor spec = spec_in.transpose(-1, -2).contiguous();         // [..., frames, bins]: no copy for stft_forward's layout
+    Tensor w;
+    if (window.has_value() && window->defined()) w = window->contiguous();
+    const int64_t rows = c10::multiply_integers(s.sizes.begin(), s.sizes.end() - 1);
+    Tensor out = at::empty(s.sizes, spec.options().dtype(s.dtype));
+    Tensor flag = at::empty({1}, spec.options().dtype(at::kInt));
+    c10::hip::HIPGuard guard(spec.get_device());
+    check_rc(tfx_istft_forward(spec.data_ptr(), w.defined() ? w.data_ptr() : nullptr, out.data_ptr(), flag.data_ptr<int>(),
+                               s.dtype == at::kFloat ? TFX_F32 : TFX_F64, rows, s.frames, n_fft, hop, s.win_length, pad, length,
+                               normalized ? 1 : 0, stream_of(spec)),
+             what);
+    return std::make_tuple(out, flag);
+}
+
 // Freeverb (tfx_freeverb_forward): x [T], [C, T] or [B, C, T] with C 1 or 2; comb_delays / allpass_delays the flattened
 // [C, NC] / [C, NA] tables in samples; state [B * C, state_len] float64 or None (silence) -> (y [..., T + tail], new state).
 // The shape and the tables are checked here and by the plan, before anything touches the device; the workspace (global lines,
@@ -1390,6 +1450,12 @@ Tensor stft_meta(const Tensor &x, const OptTensor &window, int64_t n_fft, int64_
     return at::empty(s.sizes, x.options().dtype(s.dtype)).transpose(-1, -2);
 }
 
+std::tuple<Tensor, Tensor> istft_meta(const Tensor &spec, const OptTensor &window, int64_t n_fft, int64_t hop, int64_t pad, int64_t length, bool)
+{
+    const IstftShape s = istft_shape(spec, window, n_fft, hop, pad, length, "istft_forward");
+    return {at::empty(s.sizes, spec.options().dtype(s.dtype)), at::empty({1}, spec.options().dtype(at::kInt))};
+}
+
 std::tuple<Tensor, Tensor, Tensor> modulated_delay_stream_meta(const Tensor &x, const OptTensor &, const OptTensor &, const Tensor &voices,
                                                                double, double, int64_t, int64_t)
 {
@@ -1592,6 +1658,18 @@ TORCH_LIBRARY(torchfx_spectral, m)
 TORCH_LIBRARY_IMPL(torchfx_spectral, Meta, m)
 {
     m.impl("stft_forward", stft_meta);
+}
+
+// Its inverse in a namespace of its own: torch.ops.torchfx_spectral_inverse.
+TORCH_LIBRARY(torchfx_spectral_inverse, m)
+{
+    reg_op(m, "istft_forward(Tensor spec, Tensor? window, int n_fft, int hop, int pad, int length, bool normalized) -> (Tensor, Tensor)",
+           istft_op);
+}
+
+TORCH_LIBRARY_IMPL(torchfx_spectral_inverse, Meta, m)
+{
+    m.impl("istft_forward", istft_meta);
 }
 
 // The waveshaper likewise: torch.ops.torchfx_shaper.

@@ -1,5 +1,5 @@
 // timedomain.h -- the host entry points of the time-domain and elementwise ops, one prototype per exported function of fir.hip,
-// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip, compressor.hip, modulation.hip, reverb.hip, waveshaper.hip, phaser.hip, gate.hip, stft.hip and layout.hip (the cascade's: sos.h; the
+// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip, compressor.hip, modulation.hip, reverb.hip, waveshaper.hip, phaser.hip, gate.hip, stft.hip, istft.hip and layout.hip (the cascade's: sos.h; the
 // overlap-save pipelines': ols_route.h).  Included by the file that defines each function and by capi.hip, so a prototype that drifts from
 // its definition does not compile; default arguments live here and nowhere else.  Every *_forward checks its arguments before
 // anything touches the device; a *_plan_info takes the same checking path without the pointers.
@@ -156,6 +156,13 @@ void stft_plan_info(int64_t n_fft, int64_t hop, int64_t win_length, int64_t T, i
                     int onesided, int *route, int64_t *frames, int64_t *frames_per_workgroup, int64_t *threads_per_frame,
                     int64_t *lds_bytes, int64_t *workgroups);
 void stft_clear();
+
+// ---- istft.hip ----
+void istft_forward(const void *spec, const void *window, void *out, int *flag, int dtype, int64_t rows, int64_t frames, int64_t n_fft,
+                   int64_t hop, int64_t win_length, int64_t pad, int64_t length, int normalized, hipStream_t stream);
+void istft_plan_info(int64_t n_fft, int64_t hop, int64_t win_length, int64_t frames, int64_t rows, int dtype, int center, int64_t length,
+                     int onesided, int *route, int64_t *out_length, int64_t *tile, int64_t *frames_per_batch, int64_t *threads_per_frame,
+                     int64_t *lds_bytes, int64_t *workgroups, double *redundant_share);
 
 // ---- layout.hip ----
 void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, int64_t C, int64_t ld_out, int64_t f_base,

@@ -127,3 +127,11 @@ def spectral_ops():
 
     load()
     return torch.ops.torchfx_spectral
+
+
+def spectral_inverse_ops():
+    """``torch.ops.torchfx_spectral_inverse`` (the inverse short-time Fourier transform's namespace, registered by the same module) with the library loaded."""
+    import torch
+
+    load()
+    return torch.ops.torchfx_spectral_inverse

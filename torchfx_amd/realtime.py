@@ -47,6 +47,7 @@ from __future__ import annotations
 import abc
 import dataclasses
 import enum
+import gc
 import math
 import os
 import threading
@@ -1319,13 +1320,24 @@ class StreamProcessor:
                     h.copy_(s0)
                 rehome()
                 graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, stream=side):
-                    static_out = self._run(static_in)
-                    for (m, a), h in zip(slots, homes):
-                        new = getattr(m, a)
-                        if new is not h:
-                            h.copy_(new)
-                    rehome()
+                # No cyclic collection may fall into the capture: a dead cycle can hold an earlier processor's CUDAGraph and
+                # its pool (a RealtimeProcessor and its backend refer to each other), and destroying those while a stream
+                # captures aborts the process.  torch.cuda.graph no longer collects on entry, so collect here, then hold the
+                # collector off until the capture has ended.
+                gc.collect()
+                gc_was_on = gc.isenabled()
+                gc.disable()
+                try:
+                    with torch.cuda.graph(graph, stream=side):
+                        static_out = self._run(static_in)
+                        for (m, a), h in zip(slots, homes):
+                            new = getattr(m, a)
+                            if new is not h:
+                                h.copy_(new)
+                        rehome()
+                finally:
+                    if gc_was_on:
+                        gc.enable()
             torch.cuda.current_stream(dev).wait_stream(side)
             self._graph = (graph, static_in, static_out, side, sig, slots, homes)
         graph, static_in, static_out, _, _, slots, homes = self._graph

@@ -1,8 +1,9 @@
-"""Looking at a signal in frequency: the short-time Fourier transform and the spectrogram.
+"""Looking at a signal in frequency, and coming back: the short-time Fourier transform, the spectrogram and the inverse.
 
 :func:`stft` is ``torch.stft(..., return_complex=True)`` along the last axis -- same defaults, errors, result shape and result
-strides -- and :func:`spectrogram` its magnitude or power with a named window.  These are analyses: they return tensors, there is
-no ``FX`` class, nothing in the planner and nothing in the stream processors.
+strides -- and :func:`spectrogram` its magnitude or power with a named window.  :func:`istft` is ``torch.istft`` over the last two
+axes, so that ``istft(stft(x) * mask)`` is a round trip through the library.  These are analyses and a synthesis: they return
+tensors, there is no ``FX`` class, nothing in the planner and nothing in the stream processors.
 
 On a ROCm device the transform is one launch of ``torchfx_amd/csrc/stft.hip`` (``torchfx_ext.stft_forward``) that reads the signal
 once and writes only the result: the centre padding is part of the kernel's addressing, the frames are formed in LDS and each is
@@ -11,7 +12,15 @@ transformed on its own, so a frame's bits depend on its ``n_fft`` samples and th
 geometry, and every CPU tensor, takes ``torch.stft`` on the tensor's own device, so the functions are total.
 ``torchfx_ext.stft_plan_info`` says which route a geometry takes.
 
-Not here: the inverse (ISTFT), mel / log scaling, a streaming form, autograd, axes other than the last.
+The inverse is one launch of ``torchfx_amd/csrc/istft.hip`` (``torchfx_ext.istft_forward``) that reads the spectrum once, in the
+layout :func:`stft` returns, and writes only the signal: a workgroup owns a tile of output samples, transforms the frames that
+cover it with the forward kernel's stages and tables, and adds them in ascending frame order in registers -- no frame matrix, no
+envelope array, no atomics -- so a sample's bits depend on the frames that cover it and the window alone.  That route serves the
+same ``n_fft``, one-sided spectra and ``return_complex=False``; everything else takes ``torch.istft`` on the tensor's own device
+(``torchfx_ext.istft_plan_info``).
+
+Not here: ``onesided=False`` and ``return_complex=True`` on the device route, mel / log scaling, streaming forms, autograd, axes
+other than the last, round-trip effect classes.
 """
 from __future__ import annotations
 
@@ -23,7 +32,7 @@ from torch import Tensor
 
 from torchfx_amd import torchfx_ext as E
 
-__all__ = ["stft", "spectrogram", "named_window"]
+__all__ = ["stft", "spectrogram", "istft", "named_window"]
 
 _NAMED = {"hann": torch.hann_window, "hamming": torch.hamming_window, "rect": torch.ones}
 
@@ -127,3 +136,97 @@ def spectrogram(x: Tensor, n_fft: int = 1024, hop_length: int | None = None, win
             raise TypeError(f"spectrogram: expected a tensor, got {type(x).__name__}")
         window = named_window(window, wl, x.dtype if x.dtype.is_floating_point else torch.float32, x.device)
     return _stft(x, n_fft, hop_length, win_length, window, center, pad_mode, normalized, True, power)
+
+
+def _torch_istft(X: Tensor, n_fft, hop_length, win_length, window, center, normalized, onesided, length, return_complex) -> Tensor:
+    """``torch.istft`` itself; the one thing added is a ``[B, C, bins, frames]`` input, whose leading axes it takes as rows."""
+    lead = None
+    if isinstance(X, Tensor) and X.dim() == 4:
+        lead, X = X.shape[:2], X.reshape((-1,) + tuple(X.shape[-2:]))
+    y = torch.istft(X, n_fft, hop_length, win_length, window, center, normalized, onesided, length, return_complex)
+    return y if lead is None else y.unflatten(0, tuple(lead))
+
+
+def _check_istft(X: Tensor, n_fft, hop_length, win_length, window, center, normalized, onesided, length, return_complex):
+    """The argument checks of ``torch.istft``, in its order, with its exception types and the telling part of its messages.
+    ``torch.istft`` cannot be asked on tensors without storage (its envelope check reads a value), so the device route checks
+    for itself.  Returns ``(hop, win_length, onesided, output length)`` as torch resolves the defaults."""
+    if not X.is_complex():
+        raise RuntimeError("istft requires a complex-valued input tensor matching the output from stft with return_complex=True.")
+    if window is not None and window.is_complex() and not return_complex:
+        raise RuntimeError("Complex windows are incompatible with return_complex=False")
+    n_fft = int(n_fft)
+    hop = int(hop_length) if hop_length is not None else n_fft >> 2
+    wl = int(win_length) if win_length is not None else n_fft
+    if X.dim() < 2:
+        raise IndexError(f"Dimension out of range (expected to be in range of [{-(X.dim() + 1)}, {X.dim()}], but got -3)")
+    one = bool(onesided) if onesided is not None else X.shape[-2] != n_fft
+    if return_complex and one:
+        raise RuntimeError("Cannot have onesided output if window or input is complex")
+    what = (f"istft({tuple(X.shape)}, n_fft={n_fft}, hop_length={hop}, win_length={wl}, window={None if window is None else tuple(window.shape)}, "
+            f"center={int(bool(center))}, normalized={int(bool(normalized))}, onesided={onesided}, length={length}, "
+            f"return_complex={int(bool(return_complex))})")
+    if X.numel() == 0:
+        raise RuntimeError(f"{what} : input tensor cannot be empty.")
+    if X.dim() > 4:
+        raise RuntimeError(f"{what} : expected a tensor with 3 or 4 dimensions, but got {X.dim() + 1}")
+    if X.shape[-2] != (n_fft // 2 + 1 if one else n_fft):
+        raise RuntimeError(f"{what} : expected the frequency dimension (3rd to the last) of the input tensor to match "
+                           f"{'n_fft / 2 + 1 when onesided=True' if one else 'n_fft when onesided=False'}, but got {X.shape[-2]}")
+    if not 0 < hop <= wl:
+        raise RuntimeError(f"{what} : expected 0 < hop_length <= win_length")
+    if not 0 < wl <= n_fft:
+        raise RuntimeError(f"{what} : expected 0 < win_length <= n_fft")
+    if window is not None and (window.dim() != 1 or window.shape[0] != wl):
+        raise RuntimeError(f"{what} : Invalid window shape. window has to be 1D and length of `win_length`")
+    T = int(length) if length is not None else (X.shape[-1] - 1) * hop + n_fft - (2 * (n_fft // 2) if center else 0)
+    if T <= 0:      # torch fails here too, inside its envelope check
+        raise RuntimeError(f"{what} : no output sample is left (min(): Expected reduction dim to be specified for input.numel() == 0)")
+    return hop, wl, one, T
+
+
+def _on_istft_route(X: Tensor, n_fft: int, hop: int, wl: int, window: Tensor | None, center: bool, onesided: bool, length,
+                    return_complex: bool) -> bool:
+    if not X.is_cuda or X.dtype not in (torch.complex64, torch.complex128) or return_complex or not onesided:
+        return False
+    real = torch.float32 if X.dtype == torch.complex64 else torch.float64
+    if window is not None and (window.dtype != real or window.device != X.device):
+        return False
+    rows = X.numel() // (X.shape[-1] * X.shape[-2])
+    return E.istft_plan_info(n_fft, hop, wl, X.shape[-1], rows, real, center, length, True)["route"] == "lds"
+
+
+def istft(X: Tensor, n_fft: int, hop_length: int | None = None, win_length: int | None = None, window: Tensor | None = None,
+          center: bool = True, normalized: bool = False, onesided: bool | None = None, length: int | None = None,
+          return_complex: bool = False) -> Tensor:
+    """``torch.istft(X, n_fft, hop_length, win_length, window, center, normalized, onesided, length, return_complex)`` over the
+    last two axes of ``X [bins, frames]``, ``[C, bins, frames]`` or ``[B, C, bins, frames]`` (complex64 -> float32, complex128 ->
+    float64): ``[..., T]`` with ``T = length`` or ``(frames - 1) hop + n_fft - 2 pad`` (``pad = n_fft // 2`` when centred).
+
+    Frame ``f`` is ``s_f = irfft(X[..., :, f], n_fft)`` (scaled by ``1 / n_fft``, ``n_fft ** -0.5`` when ``normalized``; the
+    imaginary parts of bins 0 and ``n_fft / 2`` are not read), ``w`` the window centred in ``n_fft`` zeros (None: ones), and
+    ``y[t - pad] = sum_f fl(w s_f)[t - f hop] / sum_f fl(w w)[t - f hop]``, both sums over the frames that cover ``t`` in ascending
+    frame order, in the signal's dtype.  Positions past the last frame read 0.  Where the envelope does not exceed ``1e-11`` in
+    the returned range the call raises ``RuntimeError`` ("window overlap add min"), as torch does; like torch it synchronises
+    once to know (``torchfx_ext.istft_forward`` returns the flag unread).
+
+    On the device route the kernel reads the layout :func:`stft` returns (which ``X * mask`` keeps) in place; any other layout
+    costs one copy into it first.  A non-finite bin makes exactly the samples its frame covers non-finite -- also under a zero of
+    the window -- and leaves every other sample's bits alone.  ``onesided=False``, ``return_complex=True``, other ``n_fft`` and
+    CPU tensors take ``torch.istft`` on the tensor's own device."""
+    if not isinstance(X, Tensor):
+        raise TypeError(f"istft: expected a tensor, got {type(X).__name__}")
+    if not X.is_cuda:
+        return _torch_istft(X, n_fft, hop_length, win_length, window, center, normalized, onesided, length, return_complex)
+    hop, wl, one, _ = _check_istft(X, n_fft, hop_length, win_length, window, center, normalized, onesided, length, return_complex)
+    if _on_istft_route(X, int(n_fft), hop, wl, window, bool(center), one, length, bool(return_complex)):
+        w = window
+        if w is None and wl < n_fft:
+            w = torch.ones(wl, dtype=torch.float32 if X.dtype == torch.complex64 else torch.float64, device=X.device)
+        with torch.cuda.device(X.device):
+            y, flag = E.istft_forward(X, w, int(n_fft), hop, int(n_fft) // 2 if center else 0, length, bool(normalized))
+            if int(flag.item()):
+                raise RuntimeError(f"istft({tuple(X.shape)}, n_fft={int(n_fft)}, hop_length={hop}, win_length={wl}, center={int(bool(center))}, "
+                                   f"length={length}) window overlap add min: 1")
+        return y
+    return _torch_istft(X, n_fft, hop_length, win_length, window, center, normalized, onesided, length, return_complex)

@@ -39,7 +39,7 @@ __all__ = [
     "limiter_stream_forward", "limiter_stream_plan_info", "compressor_forward", "compressor_plan_info",
     "modulated_delay_forward", "modulated_delay_stream_forward", "modulated_delay_plan_info", "freeverb_forward", "freeverb_plan_info",
     "waveshaper_stream_forward", "waveshaper_stream_plan_info", "phaser_forward", "phaser_plan_info", "gate_forward", "gate_plan_info",
-    "stft_forward", "stft_plan_info",
+    "stft_forward", "stft_plan_info", "istft_forward", "istft_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "effects_plan_info", "deinterleave_forward", "interleave_forward", "sos_plan_info", "sos_route_info", "ols_plan_info", "prewarm",
 ]
@@ -608,6 +608,38 @@ def stft_plan_info(n_fft: int, hop: int, win_length: int, length: int, rows: int
     info = _query(L.load().tfx_stft_plan_info, (int(n_fft), int(hop), int(win_length), int(length), int(rows), _dt(dtype), int(bool(center)),
                                                 STFT_PAD_MODES[pad_mode], int(bool(onesided))),
                   "route:int frames frames_per_workgroup threads_per_frame lds_bytes workgroups")
+    info["route"] = "lds" if info["route"] == 1 else "torch"
+    return info
+
+
+def istft_forward(spec: Tensor, window: Tensor | None, n_fft: int, hop: int, pad: int, length: int | None = None,
+                  normalized: bool = False) -> tuple[Tensor, Tensor]:
+    """The inverse short-time Fourier transform of the LDS route (``tfx_istft_forward``; the definition is
+    :func:`torchfx_amd.spectral.istft`'s): ``spec [bins, frames]``, ``[C, bins, frames]`` or ``[B, C, bins, frames]`` on the device
+    (complex64 / complex128, ``bins = n_fft // 2 + 1``), ``window`` a 1-D device tensor of the matching real dtype with ``hop`` to
+    ``n_fft`` values (centred in zeros) or None (ones), ``pad`` samples cut from each end (``n_fft // 2`` for ``center=True``),
+    ``length`` None for the natural length.  Returns ``(y [..., T], flag)``: ``flag`` is a one-element int32 device tensor, 1
+    when the window's overlap-add envelope vanishes somewhere in the returned range (torch's "window overlap add min" error).
+    It is not read here, so the call does not synchronise.  The kernel reads the layout :func:`stft_forward` returns (the
+    transpose of a contiguous ``[..., frames, bins]`` buffer) in place; any other layout costs one copy into it first.  A
+    geometry off the route (:func:`istft_plan_info`) is an error here, not a fall-back.  The op lives in
+    ``torch.ops.torchfx_spectral_inverse``."""
+    native.ops()                                         # loads the library: every namespace is registered by the one module
+    return native.spectral_inverse_ops().istft_forward(spec, window, int(n_fft), int(hop), int(pad), -1 if length is None else int(length),
+                                                       bool(normalized))
+
+
+def istft_plan_info(n_fft: int, hop: int, win_length: int, frames: int, rows: int = 1, dtype: torch.dtype = torch.float32,
+                    center: bool = True, length: int | None = None, onesided: bool = True) -> dict:
+    """What an ISTFT of this geometry does (``tfx_istft_plan_info``; host-only, same checks on the sizes): ``route`` ("lds": the
+    one-launch kernel, "torch": ``torch.istft`` on the tensor's device), the output ``length`` and, for the LDS route, ``tile``
+    (output samples a workgroup owns), ``frames_per_batch``, ``threads_per_frame``, ``lds_bytes``, ``workgroups`` (``rows *
+    ceil(length / tile)``) and ``redundant_share``: ``e / (tile / hop + e)`` with ``e = ceil(n_fft / hop) - 1``, the share of a
+    tile's transforms that its neighbour runs too (zeros on the torch route).  ``dtype`` is the real or the complex one."""
+    dtype = {torch.complex64: torch.float32, torch.complex128: torch.float64}.get(dtype, dtype)
+    info = _query(L.load().tfx_istft_plan_info, (int(n_fft), int(hop), int(win_length), int(frames), int(rows), _dt(dtype), int(bool(center)),
+                                                 -1 if length is None else int(length), int(bool(onesided))),
+                  "route:int length tile frames_per_batch threads_per_frame lds_bytes workgroups redundant_share:double")
     info["route"] = "lds" if info["route"] == 1 else "torch"
     return info
 

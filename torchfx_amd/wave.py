@@ -765,6 +765,15 @@ class Wave:
 
         return spectrogram(self.ys, n_fft, hop_length, win_length, window, power, center, pad_mode, normalized)
 
+    @classmethod
+    def from_stft(cls, spec: Tensor, fs: int, n_fft: int, hop_length: int | None = None, win_length: int | None = None, window=None,
+                  center: bool = True, normalized: bool = False, onesided: bool | None = None, length: int | None = None) -> "Wave":
+        """The counterpart of :meth:`stft`: a ``Wave`` at ``fs`` on ``spec``'s device from the inverse short-time Fourier
+        transform of ``spec [channels, bins, frames]`` (``torch.istft``'s semantics, :func:`torchfx_amd.spectral.istft`)."""
+        from torchfx_amd.spectral import istft
+
+        return cls(istft(spec, n_fft, hop_length, win_length, window, center, normalized, onesided, length), fs, device=spec.device)
+
     def resample(self, new_fs: int, window=("kaiser", 5.0)) -> "Wave":
         """``self | Resample(new_fs, window=window)``: the signal at ``new_fs`` (``scipy.signal.resample_poly`` semantics)."""
         from torchfx_amd.resample import Resample
