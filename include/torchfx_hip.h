@@ -933,6 +933,36 @@ int tfx_istft_plan_info(int64_t n_fft, int64_t hop, int64_t win_length, int64_t 
                         int64_t *threads_per_frame, int64_t *lds_bytes, int64_t *workgroups, double *redundant_share);
 
 /* ---------------------------------------------------------------------------
+ * tfx_mel_forward -- mel (or any banded filterbank) spectrogram of every row of x [rows, T]: tfx_stft_forward's steps 1 and 2
+ * with power 1 or 2, P[f, k] = |X[f, k]| or |X[f, k]|^2 with exactly its bits, then for filter m < n_filters
+ *   4. v[f, m] = sum_i w_m[i] P[f, lo_m + i], i < len_m, in dtype: a group of S lanes (lanes_per_filter, a power of two that
+ *      depends on n_fft, n_filters and dtype alone) each runs acc = fma(w_m[i], P, acc) over i = j, j + S, ... in ascending
+ *      order from zero, and the S sums combine pairwise at lane distance 1, 2, ... S / 2.  len_m = 0 reads exactly 0.
+ *   5. out[row, f, m] = v (TFX_MEL_LOG_NONE), or with v' = v < amin ? amin : v (a NaN passes): c log10(v') with c = 10 (power 2) or
+ *      20 (power 1) for TFX_MEL_LOG_DB, log10(v') for TFX_MEL_LOG_LOG10, ln(v') for TFX_MEL_LOG_LN; amin > 0 in dtype.
+ * The filterbank arrives as a band table in HOST memory, table_bytes long: int32 lo[n_filters] (first bin), int32
+ * len[n_filters] (first to last non-zero weight; 0 for an all-zero filter), int32 off[n_filters] (the band's first weight: the
+ * bands are packed one after another, off[0] = 0), zero padding to a multiple of 8 bytes, then the weights in dtype.  It is
+ * checked (0 <= lo, lo + len <= M + 1, packing, size) and its device copy cached by its bytes (tfx_clear_caches drops it).
+ * x, window DEVICE; out DEVICE [rows, frames, n_filters], contiguous.  One launch, x read once, nothing but out written: the
+ * power spectrum lives in the workgroup's LDS only.  A frame's bits depend on its n_fft samples, the window and the table alone;
+ * a non-finite sample makes exactly the frames that hold it non-finite in every filter with len > 0.
+ * Served: what tfx_stft_forward serves, with 1 <= n_filters <= 256 and a table of at most 2 n_fft values of dtype in bytes that
+ * fits a workgroup's LDS beside the frames; anything else is refused (tfx_mel_plan_info says route 0: the caller composes
+ * tfx_stft_forward with a matrix product).  Arguments are checked before the device is touched.
+ * ------------------------------------------------------------------------- */
+enum tfx_mel_log { TFX_MEL_LOG_NONE = 0, TFX_MEL_LOG_DB = 1, TFX_MEL_LOG_LOG10 = 2, TFX_MEL_LOG_LN = 3 };
+int tfx_mel_forward(const void *x, const void *window_or_null, const void *table_host, int64_t table_bytes, int64_t n_filters, void *out,
+                    int dtype, int64_t rows, int64_t T, int64_t n_fft, int64_t hop, int64_t win_length, int64_t pad, int pad_mode,
+                    int power, int normalized, int log_mode, double amin, tfx_stream_t stream);
+/* what a mel spectrogram of this geometry and table size does (host-only, same checks on the sizes; total_band = sum of len):
+ * route (1: the LDS kernel, 0: not served), frames per row and, for route 1, the frames of a workgroup, the lanes per
+ * (frame, filter) sum, the LDS bytes of a workgroup and the workgroups of the launch (0 for route 0) */
+int tfx_mel_plan_info(int64_t n_fft, int64_t hop, int64_t win_length, int64_t T, int64_t rows, int dtype, int center, int pad_mode,
+                      int64_t n_filters, int64_t total_band, int *route, int64_t *frames, int64_t *frames_per_workgroup,
+                      int64_t *lanes_per_filter, int64_t *lds_bytes, int64_t *workgroups);
+
+/* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of
  * ParallelFilterCombination.forward, src/torchfx/filter/__base.py:1019-1026).
  * xs_host: HOST array of n DEVICE pointers, each [numel] of dtype.

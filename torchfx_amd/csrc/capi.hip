@@ -884,6 +884,27 @@ int tfx_istft_plan_info(int64_t n_fft, int64_t hop, int64_t win_length, int64_t 
     TFX_API_END
 }
 
+int tfx_mel_forward(const void *x, const void *window_or_null, const void *table_host, int64_t table_bytes, int64_t n_filters, void *out,
+                    int dtype, int64_t rows, int64_t T, int64_t n_fft, int64_t hop, int64_t win_length, int64_t pad, int pad_mode,
+                    int power, int normalized, int log_mode, double amin, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    mel_forward(x, window_or_null, table_host, table_bytes, n_filters, out, dtype, rows, T, n_fft, hop, win_length, pad, pad_mode, power,
+                normalized, log_mode, amin, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_mel_plan_info(int64_t n_fft, int64_t hop, int64_t win_length, int64_t T, int64_t rows, int dtype, int center, int pad_mode,
+                      int64_t n_filters, int64_t total_band, int *route, int64_t *frames, int64_t *frames_per_workgroup,
+                      int64_t *lanes_per_filter, int64_t *lds_bytes, int64_t *workgroups)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(route && frames && frames_per_workgroup && lanes_per_filter && lds_bytes && workgroups, "mel_plan_info: null output");
+    mel_plan_info(n_fft, hop, win_length, T, rows, dtype, center, pad_mode, n_filters, total_band, route, frames, frames_per_workgroup,
+                  lanes_per_filter, lds_bytes, workgroups);
+    TFX_API_END
+}
+
 int tfx_sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, tfx_stream_t stream)
 {
     TFX_API_BEGIN
@@ -1004,6 +1025,7 @@ int tfx_clear_caches(void)
     modulation_clear();
     waveshaper_clear();
     stft_clear();
+    mel_clear();
     scratch_clear();
     TFX_API_END
 }

@@ -715,6 +715,40 @@ Tensor stft_op(const Tensor &x_in, const OptTensor &window, int64_t n_fft, int64
     return out.transpose(-1, -2);
 }
 
+// Mel spectrogram (tfx_mel_forward): x, window, n_fft, hop, pad, pad_mode, normalized as for stft_forward; power 1 or 2; table_cpu a
+// 1-D uint8 HOST tensor, the band table of n_filters filters in the layout of include/torchfx_hip.h; log a tfx_mel_log ->
+// [..., n_filters, frames], the transposed view of a contiguous [..., frames, n_filters] buffer.
+StftShape mel_shape(const Tensor &x, const OptTensor &window, const Tensor &table_cpu, int64_t n_filters, int64_t n_fft, int64_t hop,
+                    int64_t pad, int64_t power, const char *what)
+{
+    TORCH_CHECK(power == 1 || power == 2, what, ": power must be 1 or 2");
+    TORCH_CHECK(n_filters >= 1 && table_cpu.dim() == 1 && table_cpu.scalar_type() == at::kByte && table_cpu.numel() >= 12 * n_filters, what,
+                ": table_cpu must be a 1-D uint8 tensor holding ", n_filters, " bands");
+    StftShape s = stft_shape(x, window, n_fft, hop, pad, power, what);
+    s.sizes.back() = n_filters;
+    return s;
+}
+
+Tensor mel_op(const Tensor &x_in, const OptTensor &window, const Tensor &table_cpu, int64_t n_filters, int64_t n_fft, int64_t hop,
+              int64_t pad, int64_t pad_mode, int64_t power, bool normalized, int64_t log, double amin)
+{
+    const char *what = "mel_forward";
+    need_device(x_in, "x");
+    TORCH_CHECK(table_cpu.is_cpu(), what, ": table_cpu must be a host tensor");
+    const StftShape s = mel_shape(x_in, window, table_cpu, n_filters, n_fft, hop, pad, power, what);
+    const Tensor x = x_in.contiguous(), table = table_cpu.contiguous();
+    Tensor w;
+    if (window.has_value() && window->defined()) w = window->contiguous();
+    const int64_t T = x.size(-1), rows = stream_rows(x);
+    Tensor out = at::empty(s.sizes, x.options());
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_mel_forward(x.data_ptr(), w.defined() ? w.data_ptr() : nullptr, table.data_ptr(), table.numel(), n_filters, out.data_ptr(),
+                             dtype_code(x, what), rows, T, n_fft, hop, s.win_length, pad, (int)pad_mode, (int)power, normalized ? 1 : 0,
+                             (int)log, amin, stream_of(x)),
+             what);
+    return out.transpose(-1, -2);
+}
+
 // Inverse short-time Fourier transform (tfx_istft_forward): spec [bins, frames], [C, bins, frames] or [B, C, bins, frames],
 // complex64 / complex128 with bins = n_fft / 2 + 1; window a 1-D device tensor of the matching real dtype with hop <= numel <=
 // n_fft (centred in zeros) or None (ones over n_fft); pad samples cut from each end; length -1 = natural -> (y [..., T] of the
@@ -1450,6 +1484,13 @@ Tensor stft_meta(const Tensor &x, const OptTensor &window, int64_t n_fft, int64_
     return at::empty(s.sizes, x.options().dtype(s.dtype)).transpose(-1, -2);
 }
 
+Tensor mel_meta(const Tensor &x, const OptTensor &window, const Tensor &table_cpu, int64_t n_filters, int64_t n_fft, int64_t hop, int64_t pad,
+                int64_t, int64_t power, bool, int64_t, double)
+{
+    const StftShape s = mel_shape(x, window, table_cpu, n_filters, n_fft, hop, pad, power, "mel_forward");
+    return at::empty(s.sizes, x.options()).transpose(-1, -2);
+}
+
 std::tuple<Tensor, Tensor> istft_meta(const Tensor &spec, const OptTensor &window, int64_t n_fft, int64_t hop, int64_t pad, int64_t length, bool)
 {
     const IstftShape s = istft_shape(spec, window, n_fft, hop, pad, length, "istft_forward");
@@ -1670,6 +1711,18 @@ TORCH_LIBRARY(torchfx_spectral_inverse, m)
 TORCH_LIBRARY_IMPL(torchfx_spectral_inverse, Meta, m)
 {
     m.impl("istft_forward", istft_meta);
+}
+
+// The mel spectrogram in a namespace of its own: torch.ops.torchfx_mel.
+TORCH_LIBRARY(torchfx_mel, m)
+{
+    reg_op(m, "mel_forward(Tensor x, Tensor? window, Tensor table_cpu, int n_filters, int n_fft, int hop, int pad, int pad_mode, int power, "
+              "bool normalized, int log, float amin) -> Tensor", mel_op);
+}
+
+TORCH_LIBRARY_IMPL(torchfx_mel, Meta, m)
+{
+    m.impl("mel_forward", mel_meta);
 }
 
 // The waveshaper likewise: torch.ops.torchfx_shaper.

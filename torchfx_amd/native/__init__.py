@@ -129,6 +129,14 @@ def spectral_ops():
     return torch.ops.torchfx_spectral
 
 
+def mel_ops():
+    """``torch.ops.torchfx_mel`` (the mel spectrogram's namespace, registered by the same module) with the library loaded."""
+    import torch
+
+    load()
+    return torch.ops.torchfx_mel
+
+
 def spectral_inverse_ops():
     """``torch.ops.torchfx_spectral_inverse`` (the inverse short-time Fourier transform's namespace, registered by the same module) with the library loaded."""
     import torch

@@ -19,20 +19,29 @@ envelope array, no atomics -- so a sample's bits depend on the frames that cover
 same ``n_fft``, one-sided spectra and ``return_complex=False``; everything else takes ``torch.istft`` on the tensor's own device
 (``torchfx_ext.istft_plan_info``).
 
-Not here: ``onesided=False`` and ``return_complex=True`` on the device route, mel / log scaling, streaming forms, autograd, axes
-other than the last, round-trip effect classes.
+The mel spectrogram (:func:`mel_spectrogram`, :class:`MelSpectrogram`, :func:`mel_filterbank`) is one launch of
+``torchfx_amd/csrc/mel.hip`` (``torchfx_ext.mel_forward``): the STFT kernel's front, then the filterbank -- as a table of bands --
+and the logarithm applied to the power spectrum while it lies in the workgroup's LDS, so that only ``[..., frames, n_mels]`` is
+written.  It serves what the STFT's route serves with up to 256 filters whose bands fit LDS; everything else (CPU tensors, other
+``n_fft``, dense banks) is the composition spectrogram, ``matmul``, logarithm on the tensor's own device
+(``torchfx_ext.mel_plan_info``).
+
+Not here: ``onesided=False`` and ``return_complex=True`` on the device route, MFCC / DCT, the inverse mel transform, streaming
+forms, autograd, axes other than the last, round-trip effect classes.
 """
 from __future__ import annotations
 
+import math
 import re
 import warnings
 
+import numpy as np
 import torch
 from torch import Tensor
 
 from torchfx_amd import torchfx_ext as E
 
-__all__ = ["stft", "spectrogram", "istft", "named_window"]
+__all__ = ["stft", "spectrogram", "istft", "named_window", "mel_filterbank", "mel_spectrogram", "MelSpectrogram"]
 
 _NAMED = {"hann": torch.hann_window, "hamming": torch.hamming_window, "rect": torch.ones}
 
@@ -230,3 +239,190 @@ def istft(X: Tensor, n_fft: int, hop_length: int | None = None, win_length: int 
                                    f"length={length}) window overlap add min: 1")
         return y
     return _torch_istft(X, n_fft, hop_length, win_length, window, center, normalized, onesided, length, return_complex)
+
+
+def _hz_to_mel(f, mel_scale: str):
+    f = np.asarray(f, dtype=np.float64)
+    if mel_scale == "htk":
+        return 2595.0 * np.log10(1.0 + f / 700.0)
+    return np.where(f < 1000.0, 3.0 * f / 200.0, 15.0 + 27.0 * np.log(np.maximum(f, 1000.0) / 1000.0) / math.log(6.4))
+
+
+def _mel_to_hz(m, mel_scale: str):
+    m = np.asarray(m, dtype=np.float64)
+    if mel_scale == "htk":
+        return 700.0 * (10.0 ** (m / 2595.0) - 1.0)
+    return np.where(m < 15.0, 200.0 * m / 3.0, 1000.0 * np.exp(math.log(6.4) * (np.maximum(m, 15.0) - 15.0) / 27.0))
+
+
+def _mel_design(n_freqs, sample_rate, n_mels, f_min, f_max, norm, mel_scale) -> np.ndarray:
+    """The mel filterbank ``[n_freqs, n_mels]`` in float64, after the argument checks."""
+    if int(n_mels) < 1:
+        raise ValueError(f"n_mels must be at least 1, got {n_mels!r}")
+    nyquist = float(sample_rate) / 2.0
+    f_max = nyquist if f_max is None else float(f_max)
+    if not 0.0 <= float(f_min) < f_max:
+        raise ValueError(f"f_min must satisfy 0 <= f_min < f_max, got f_min {f_min!r} and f_max {f_max!r}")
+    if f_max > nyquist:
+        raise ValueError(f"f_max must not exceed sample_rate / 2 = {nyquist}, got {f_max!r}")
+    if norm not in (None, "slaney"):
+        raise ValueError(f"norm must be None or 'slaney', got {norm!r}")
+    if mel_scale not in ("htk", "slaney"):
+        raise ValueError(f"mel_scale must be 'htk' or 'slaney', got {mel_scale!r}")
+    all_freqs = np.linspace(0.0, nyquist, int(n_freqs))
+    f_pts = _mel_to_hz(np.linspace(_hz_to_mel(float(f_min), mel_scale), _hz_to_mel(f_max, mel_scale), int(n_mels) + 2), mel_scale)
+    down = (all_freqs[:, None] - f_pts[None, :-2]) / (f_pts[1:-1] - f_pts[:-2])
+    up = (f_pts[None, 2:] - all_freqs[:, None]) / (f_pts[2:] - f_pts[1:-1])
+    fb = np.maximum(0.0, np.minimum(down, up))
+    if norm == "slaney":
+        fb = fb * (2.0 / (f_pts[2:] - f_pts[:-2]))
+    return fb
+
+
+def mel_filterbank(n_freqs: int, sample_rate: float, n_mels: int = 128, f_min: float = 0.0, f_max: float | None = None,
+                   norm: str | None = None, mel_scale: str = "htk", dtype: torch.dtype = torch.float32, device=None) -> Tensor:
+    """The triangular mel filterbank ``[n_freqs, n_mels]`` (``torchaudio.functional.melscale_fbanks`` for even integer rates),
+    built in float64 on the host and rounded once to ``dtype``.  With ``all_freqs = linspace(0, sample_rate / 2, n_freqs)`` and
+    ``f_pts = mel_to_hz(linspace(hz_to_mel(f_min), hz_to_mel(f_max), n_mels + 2))`` (``f_max=None``: ``sample_rate / 2``) column
+    ``m`` is ``max(0, min((f - f_pts[m]) / (f_pts[m+1] - f_pts[m]), (f_pts[m+2] - f) / (f_pts[m+2] - f_pts[m+1])))``, times
+    ``2 / (f_pts[m+2] - f_pts[m])`` for ``norm="slaney"``.  ``mel_scale`` "htk": ``mel = 2595 log10(1 + f / 700)``; "slaney":
+    ``3 f / 200`` below 1000 Hz and ``15 + 27 ln(f / 1000) / ln 6.4`` from there.  A filter narrower than the bin spacing can be
+    an all-zero column."""
+    return torch.from_numpy(_mel_design(n_freqs, sample_rate, n_mels, f_min, f_max, norm, mel_scale)).to(dtype=dtype, device=device)
+
+
+class _Bank:
+    """A filterbank prepared for both routes: the float64 design (or the caller's tensor), its dense form per dtype and device
+    and its host band table per dtype, each built on first use."""
+
+    def __init__(self, design: np.ndarray | None = None, tensor: Tensor | None = None) -> None:
+        self.design, self.tensor = design, tensor
+        self.n_filters = int(design.shape[1] if design is not None else tensor.shape[1])
+        self._dense: dict = {}
+        self._tables: dict = {}
+
+    def dense(self, dtype: torch.dtype, device) -> Tensor:
+        key = (dtype, torch.device(device))
+        if key not in self._dense:
+            src = torch.from_numpy(self.design) if self.design is not None else self.tensor
+            self._dense[key] = src.to(dtype=dtype, device=device)
+        return self._dense[key]
+
+    def fits(self, x: Tensor) -> bool:
+        """The route's condition on a caller's tensor: the signal's dtype and device (the design is rounded to any dtype)."""
+        return self.design is not None or (self.tensor.dtype == x.dtype and self.tensor.device == x.device)
+
+    def table(self, dtype: torch.dtype) -> tuple[Tensor, int]:
+        """``torchfx_ext.mel_band_table`` of the bank rounded to ``dtype``; a caller's device tensor costs one device-to-host copy."""
+        if dtype not in self._tables:
+            host = self.design if self.design is not None else self.tensor.detach().cpu().numpy()
+            self._tables[dtype] = E.mel_band_table(host.astype(np.float32 if dtype == torch.float32 else np.float64))
+        return self._tables[dtype]
+
+
+def _mel_log(v: Tensor, log: str, power: float, amin: float) -> Tensor:
+    v = torch.where(v < amin, torch.full_like(v, amin), v)              # not clamp: a NaN stays
+    if log == "ln":
+        return v.log()
+    return v.log10() * (10.0 if power == 2.0 else 20.0) if log == "db" else v.log10()
+
+
+class MelSpectrogram:
+    """:func:`mel_spectrogram` with everything but the signal fixed: the filterbank and its band table are built once, with the
+    object (a ``filterbank=`` tensor on the device costs one device-to-host copy, at the first call on the device route), and
+    ``MelSpectrogram(sample_rate, ...)(x)`` has the function's bits.  Not an ``FX``: it returns a tensor."""
+
+    def __init__(self, sample_rate: float, n_fft: int = 1024, hop_length: int | None = None, win_length: int | None = None,
+                 window: Tensor | str = "hann", n_mels: int = 128, f_min: float = 0.0, f_max: float | None = None,
+                 norm: str | None = None, mel_scale: str = "htk", power: float = 2.0, center: bool = True, pad_mode: str = "reflect",
+                 normalized: bool = False, log: str | None = None, amin: float = 1e-10, top_db: float | None = None,
+                 filterbank: Tensor | None = None) -> None:
+        n_freqs = int(n_fft) // 2 + 1
+        design = (n_freqs, float(sample_rate), int(n_mels), float(f_min), None if f_max is None else float(f_max), norm, mel_scale)
+        if filterbank is None and design not in E._MEL_BANKS:
+            fb = _mel_design(*design)
+        if isinstance(power, bool) or not isinstance(power, (int, float)) or float(power) not in (1.0, 2.0):
+            raise ValueError(f"power must be 1.0 or 2.0, got {power!r}")
+        if log not in E.MEL_LOGS:
+            raise ValueError(f"log must be None, 'db', 'log10' or 'ln', got {log!r}")
+        if not float(amin) > 0.0:
+            raise ValueError(f"amin must be positive, got {amin!r}")
+        if top_db is not None and not float(top_db) >= 0.0:
+            raise ValueError(f"top_db must not be negative, got {top_db!r}")
+        if filterbank is not None:
+            if not isinstance(filterbank, Tensor) or filterbank.dim() != 2 or filterbank.shape[0] != n_freqs or filterbank.shape[1] < 1 \
+                    or not filterbank.dtype.is_floating_point:
+                raise ValueError(f"filterbank must be a real [n_fft / 2 + 1 = {n_freqs}, n_filters] tensor, got "
+                                 f"{tuple(filterbank.shape) if isinstance(filterbank, Tensor) else type(filterbank).__name__}")
+            self.bank = _Bank(tensor=filterbank)
+        else:
+            if design not in E._MEL_BANKS:
+                if len(E._MEL_BANKS) >= 64:
+                    E._MEL_BANKS.clear()
+                E._MEL_BANKS[design] = _Bank(design=fb)
+            self.bank = E._MEL_BANKS[design]
+        self.n_fft, self.hop_length, self.win_length, self.window = int(n_fft), hop_length, win_length, window
+        self.power, self.center, self.pad_mode, self.normalized = float(power), bool(center), pad_mode, bool(normalized)
+        self.log, self.amin, self.top_db = log, float(amin), None if top_db is None else float(top_db)
+
+    def __call__(self, x: Tensor) -> Tensor:
+        if not isinstance(x, Tensor):
+            raise TypeError(f"mel_spectrogram: expected a tensor, got {type(x).__name__}")
+        n_fft, bank = self.n_fft, self.bank
+        hop = int(self.hop_length) if self.hop_length is not None else n_fft // 4
+        wl = int(self.win_length) if self.win_length is not None else n_fft
+        window = self.window
+        if isinstance(window, str):
+            window = named_window(window, wl, x.dtype if x.dtype.is_floating_point else torch.float32, x.device)
+        y = None
+        if x.is_cuda and bank.fits(x):
+            _check_as_torch(x, n_fft, hop, wl, window, self.center, self.pad_mode, self.normalized, True)
+            if _on_lds_route(x, n_fft, hop, wl, window, self.center, self.pad_mode, True):
+                table, total = bank.table(x.dtype)
+                rows = x.numel() // x.shape[-1]
+                info = E.mel_plan_info(n_fft, hop, wl, x.shape[-1], rows, x.dtype, self.center, self.pad_mode, bank.n_filters, total)
+                if info["route"] == "lds":
+                    w = window
+                    if w is None and wl < n_fft:
+                        w = torch.ones(wl, dtype=x.dtype, device=x.device)
+                    with torch.cuda.device(x.device):
+                        y = E.mel_forward(x, w, table, bank.n_filters, n_fft, hop, n_fft // 2 if self.center else 0, self.pad_mode,
+                                          self.power, self.normalized, self.log, self.amin)
+        if y is None:
+            P = spectrogram(x, n_fft, self.hop_length, self.win_length, window, self.power, self.center, self.pad_mode, self.normalized)
+            y = torch.matmul(P.transpose(-1, -2), bank.dense(P.dtype, P.device)).transpose(-1, -2)
+            if self.log is not None:
+                y = _mel_log(y, self.log, self.power, self.amin)
+        if self.log == "db" and self.top_db is not None:
+            item = y if y.dim() <= 3 else y.flatten(1)
+            peak = item.amax() if y.dim() <= 3 else item.amax(dim=1).view(-1, 1, 1, 1)
+            y = torch.maximum(y, peak - self.top_db)
+        return y
+
+
+def mel_spectrogram(x: Tensor, sample_rate: float, n_fft: int = 1024, hop_length: int | None = None, win_length: int | None = None,
+                    window: Tensor | str = "hann", n_mels: int = 128, f_min: float = 0.0, f_max: float | None = None,
+                    norm: str | None = None, mel_scale: str = "htk", power: float = 2.0, center: bool = True, pad_mode: str = "reflect",
+                    normalized: bool = False, log: str | None = None, amin: float = 1e-10, top_db: float | None = None,
+                    filterbank: Tensor | None = None) -> Tensor:
+    """The mel spectrogram ``[..., n_mels, frames]`` of ``x [T]``, ``[C, T]`` or ``[B, C, T]`` (float32 / float64, the result's
+    dtype), the transposed view of a contiguous ``[..., frames, n_mels]`` buffer.  With ``P = spectrogram(x, n_fft, hop_length,
+    win_length, window, power, center, pad_mode, normalized)`` (``power`` 1.0 or 2.0) and ``fb = mel_filterbank(n_fft // 2 + 1,
+    sample_rate, n_mels, f_min, f_max, norm, mel_scale, x.dtype)``: ``mel[f, m] = sum_k fb[k, m] P[f, k]`` over the filter's band,
+    in the signal's dtype.  ``log`` "db" gives ``c log10(v')`` with ``c`` 10 (``power=2``) or 20 (``power=1``), "log10"
+    ``log10(v')`` and "ln" ``ln(v')``, where ``v' = v < amin ? amin : v`` (a NaN passes the floor).  ``top_db`` with ``log="db"``
+    raises everything to ``y.amax() - top_db``, the maximum taken over each ``[C, T]`` signal or batch item (two torch ops on
+    the small result, no host synchronisation).  ``filterbank=`` takes any real ``[n_fft // 2 + 1, n_filters]`` tensor in place
+    of the mel design (negative weights allowed); ``ValueError`` names a bad argument.
+
+    On a ROCm device one launch reads the signal once and writes only the result; the power spectrum has :func:`spectrogram`'s
+    bits and never reaches global memory.  The mel design's band table is cached by its parameters
+    (``torchfx_ext.clear_caches`` drops it); a ``filterbank=`` tensor builds its table per call, which on the device costs one
+    device-to-host copy -- :class:`MelSpectrogram` pays it once.  A frame's bits depend on its ``n_fft`` samples, the window and
+    the filterbank alone (the same with and without ``log``); a non-finite sample makes exactly the frames that hold it non-finite
+    in every filter with a non-empty band; an all-zero filter reads exactly 0, the ``amin`` floor with ``log``.  Served:
+    :func:`stft`'s device geometries with at most 256 filters whose bands fit LDS and a ``filterbank`` of the signal's dtype and
+    device; everything else (CPU tensors, ``n_fft=400``, dense banks) is ``spectrogram``, ``matmul(P.transpose(-1, -2),
+    fb).transpose(-1, -2)`` and the logarithm in torch ops on the tensor's own device."""
+    return MelSpectrogram(sample_rate, n_fft, hop_length, win_length, window, n_mels, f_min, f_max, norm, mel_scale, power, center,
+                          pad_mode, normalized, log, amin, top_db, filterbank)(x)

@@ -39,7 +39,7 @@ __all__ = [
     "limiter_stream_forward", "limiter_stream_plan_info", "compressor_forward", "compressor_plan_info",
     "modulated_delay_forward", "modulated_delay_stream_forward", "modulated_delay_plan_info", "freeverb_forward", "freeverb_plan_info",
     "waveshaper_stream_forward", "waveshaper_stream_plan_info", "phaser_forward", "phaser_plan_info", "gate_forward", "gate_plan_info",
-    "stft_forward", "stft_plan_info", "istft_forward", "istft_plan_info",
+    "stft_forward", "stft_plan_info", "istft_forward", "istft_plan_info", "mel_forward", "mel_plan_info", "mel_band_table",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "effects_plan_info", "deinterleave_forward", "interleave_forward", "sos_plan_info", "sos_route_info", "ols_plan_info", "prewarm",
 ]
@@ -612,6 +612,66 @@ def stft_plan_info(n_fft: int, hop: int, win_length: int, length: int, rows: int
     return info
 
 
+MEL_LOGS = {None: 0, "db": 1, "log10": 2, "ln": 3}                                 # enum tfx_mel_log
+_MEL_BANKS: dict = {}        # design parameters -> the mel design's prepared bank (torchfx_amd.spectral); :func:`clear_caches` empties it
+
+
+def mel_band_table(fb) -> tuple[Tensor, int]:
+    """The band table ``tfx_mel_forward`` takes, from a filterbank ``fb [n_freqs, n_filters]`` (a float32 or float64 host array,
+    already rounded to the signal's dtype): for each filter its first bin, its length from the first to the last non-zero weight
+    (0 for an all-zero column) and the offset of its weights, as three int32 rows, zero padding to 8 bytes, then the bands'
+    weights packed one after another.  Returns ``(table, total_band)``: a 1-D uint8 host tensor and the number of weights."""
+    w = np.ascontiguousarray(fb)
+    if w.ndim != 2 or w.dtype not in (np.float32, np.float64) or w.shape[1] < 1:
+        raise ValueError(f"mel_band_table: expected a float32 / float64 [n_freqs, n_filters] array, got {w.dtype} {w.shape}")
+    nz = w != 0                                          # a NaN weight belongs to its band
+    some = nz.any(axis=0)
+    lo = np.where(some, nz.argmax(axis=0), 0)
+    length = np.where(some, w.shape[0] - nz[::-1].argmax(axis=0) - lo, 0)
+    off = np.concatenate(([0], np.cumsum(length)[:-1]))
+    head = np.concatenate((lo, length, off)).astype(np.int32).tobytes()
+    bands = [w[a:a + n, m] for m, (a, n) in enumerate(zip(lo, length))]
+    blob = head + b"\0" * (-len(head) % 8) + np.concatenate(bands).astype(w.dtype).tobytes()
+    return torch.frombuffer(bytearray(blob), dtype=torch.uint8), int(length.sum())
+
+
+def mel_forward(x: Tensor, window: Tensor | None, table: Tensor, n_filters: int, n_fft: int, hop: int, pad: int,
+                pad_mode: str = "reflect", power: float = 2.0, normalized: bool = False, log: str | None = None,
+                amin: float = 1e-10) -> Tensor:
+    """The mel spectrogram of the LDS route (``tfx_mel_forward``; the definition is :func:`torchfx_amd.spectral.mel_spectrogram`'s):
+    ``x``, ``window``, ``n_fft``, ``hop``, ``pad``, ``pad_mode`` and ``normalized`` as for :func:`stft_forward`, ``power`` 1.0 or
+    2.0, ``table`` the host band table of ``n_filters`` filters (:func:`mel_band_table`, in ``x``'s dtype), ``log`` None, "db",
+    "log10" or "ln" with the floor ``amin``.  Returns ``[..., n_filters, frames]``, a transposed view of a contiguous
+    ``[..., frames, n_filters]`` buffer.  A geometry or table off the route (:func:`mel_plan_info`) is an error here, not a
+    fall-back.  The op lives in ``torch.ops.torchfx_mel``."""
+    native.ops()                                         # loads the library: every namespace is registered by the one module
+    if pad_mode not in STFT_PAD_MODES:
+        raise ValueError(f"mel_forward: pad_mode must be one of {sorted(STFT_PAD_MODES)}, got {pad_mode!r}")
+    if power not in (1.0, 2.0):
+        raise ValueError(f"mel_forward: power must be 1.0 or 2.0, got {power!r}")
+    if log not in MEL_LOGS:
+        raise ValueError(f"mel_forward: log must be None, 'db', 'log10' or 'ln', got {log!r}")
+    return native.mel_ops().mel_forward(x, window, table, int(n_filters), int(n_fft), int(hop), int(pad), STFT_PAD_MODES[pad_mode],
+                                        STFT_POWERS[float(power)], bool(normalized), MEL_LOGS[log], float(amin))
+
+
+def mel_plan_info(n_fft: int, hop: int, win_length: int, length: int, rows: int = 1, dtype: torch.dtype = torch.float32,
+                  center: bool = True, pad_mode: str = "reflect", n_filters: int = 128, total_band: int = 0) -> dict:
+    """What a mel spectrogram of this geometry and band table does (``tfx_mel_plan_info``; host-only, same checks on the sizes):
+    ``route`` ("lds": the one-launch kernel, "composition": spectrogram, matrix product and logarithm on the tensor's device),
+    ``frames`` per row, ``total_band`` as given (the weights of the table, :func:`mel_band_table`) and, for the LDS route,
+    ``frames_per_workgroup``, ``lanes_per_filter`` (the lanes that share one (frame, filter) sum), ``lds_bytes`` and ``workgroups``
+    (zeros on the composition)."""
+    if pad_mode not in STFT_PAD_MODES:
+        raise ValueError(f"mel_plan_info: pad_mode must be one of {sorted(STFT_PAD_MODES)}, got {pad_mode!r}")
+    info = _query(L.load().tfx_mel_plan_info, (int(n_fft), int(hop), int(win_length), int(length), int(rows), _dt(dtype), int(bool(center)),
+                                               STFT_PAD_MODES[pad_mode], int(n_filters), int(total_band)),
+                  "route:int frames frames_per_workgroup lanes_per_filter lds_bytes workgroups")
+    info["route"] = "lds" if info["route"] == 1 else "composition"
+    info["total_band"] = int(total_band)
+    return info
+
+
 def istft_forward(spec: Tensor, window: Tensor | None, n_fft: int, hop: int, pad: int, length: int | None = None,
                   normalized: bool = False) -> tuple[Tensor, Tensor]:
     """The inverse short-time Fourier transform of the LDS route (``tfx_istft_forward``; the definition is
@@ -732,6 +792,7 @@ def clear_caches() -> None:
     """Drop every cached plan and hand all device workspaces back to their allocator (``tfx_clear_caches``): PyTorch's caching
     allocator under this module, so ``torch.cuda.empty_cache()`` afterwards returns them to the driver."""
     L.check(L.load().tfx_clear_caches())
+    _MEL_BANKS.clear()
 
 
 def workspace_bytes() -> int:

@@ -765,6 +765,14 @@ class Wave:
 
         return spectrogram(self.ys, n_fft, hop_length, win_length, window, power, center, pad_mode, normalized)
 
+    def mel_spectrogram(self, n_fft: int = 1024, hop_length: int | None = None, win_length: int | None = None, window="hann",
+                        n_mels: int = 128, **kwargs) -> Tensor:
+        """Mel spectrogram of the (materialised) signal at its own rate, ``[channels, n_mels, frames]``
+        (:func:`torchfx_amd.spectral.mel_spectrogram`, which takes the further keywords)."""
+        from torchfx_amd.spectral import mel_spectrogram
+
+        return mel_spectrogram(self.ys, self.fs, n_fft, hop_length, win_length, window, n_mels, **kwargs)
+
     @classmethod
     def from_stft(cls, spec: Tensor, fs: int, n_fft: int, hop_length: int | None = None, win_length: int | None = None, window=None,
                   center: bool = True, normalized: bool = False, onesided: bool | None = None, length: int | None = None) -> "Wave":
