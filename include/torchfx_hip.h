@@ -963,6 +963,37 @@ int tfx_mel_plan_info(int64_t n_fft, int64_t hop, int64_t win_length, int64_t T,
                       int64_t *lanes_per_filter, int64_t *lds_bytes, int64_t *workgroups);
 
 /* ---------------------------------------------------------------------------
+ * tfx_phase_vocoder_forward -- phase vocoder over every row of spec [rows, frames, bins] (complex, interleaved re / im of dtype;
+ * the buffer tfx_stft_forward writes and tfx_istft_forward reads), the meaning of torchaudio.functional.phase_vocoder:
+ *   1. Fo = ceil(frames / rate) in double.  Output frame t < Fo stands at p = fl(t rate) (double): i = floor(p),
+ *      alpha = dtype(p - i).  X[j] is input frame j; frames `frames` and `frames + 1` are zeros.
+ *   2. mag[t] = alpha |X[i+1]| + (1 - alpha) |X[i]| in dtype.
+ *   3. A[j] = rint(atan2(im, re) / 2 pi * 2^64) in double, as a 64-bit integer (2^64 = one turn; 0 for the zero bin), and
+ *      phase[t] = A[0] + sum_{s<t} (A[i_s + 1] - A[i_s]) in wrapping unsigned arithmetic.  torchaudio's increment
+ *      wrap(d - pa) + pa differs from d by whole turns, so the expected phase advance pa is no argument here.
+ *   4. out[row, t, bin] = dtype(mag (cos, sin)(2 pi phase 2^-64)), formed in double and rounded once.
+ *   5. A bin with a NaN or Inf component has no angle: from the first output frame that reads it (as X[i] or X[i+1]) every
+ *      later frame of that (row, bin) is NaN in both parts; earlier frames, other bins and other rows are untouched.
+ * spec, out [rows, Fo, bins] DEVICE, contiguous.  Lanes own neighbouring bins; a workgroup owns one (row, bin tile, time
+ * segment) and walks its output frames in order with the phase and the two frames it stands between in registers, so an input
+ * frame's angle is computed once and a frame that no output stands on is never read.  `segments` cuts a row's Fo frames
+ * (tfx_phase_vocoder_plan_info; 0 = chosen from the sizes): one segment is one launch; otherwise two, a summary pass that leaves
+ * each segment's increment sum and poison flag in `scratch` (DEVICE, scratch_bytes of the plan, may be null for one segment)
+ * and the pass that writes.  No atomics, no workgroup waits for another.  The sums are integers: a value's bits depend on its
+ * own (row, bin) track up to its frame alone -- not on `segments`, the bin tile or the other rows -- and at rate 1 the phase is
+ * A[t] exactly.  Arguments are checked before the device is touched; rows * bins * frames == 0 launches nothing.
+ * ------------------------------------------------------------------------- */
+int tfx_phase_vocoder_forward(const void *spec, void *out, int dtype, int64_t rows, int64_t frames, int64_t bins, double rate,
+                              int64_t segments, void *scratch, tfx_stream_t stream);
+/* what tfx_phase_vocoder_forward does (host-only, same checks on the sizes): the output frames Fo, the bins of a workgroup
+ * (64, 128 or 256: the fewest idle lanes), the segments it takes for the request `segments`, the output frames of a segment
+ * (the last may hold fewer), the launches (1 or 2), the workgroups of the writing launch (rows * bin tiles * segments) and
+ * the bytes of `scratch` (0 for one segment).  Empty work reports 0 segments and 0 launches. */
+int tfx_phase_vocoder_plan_info(int64_t rows, int64_t frames, int64_t bins, double rate, int dtype, int64_t segments,
+                                int64_t *out_frames, int64_t *bin_tile, int64_t *segments_out, int64_t *seg_frames, int64_t *launches,
+                                int64_t *workgroups, int64_t *scratch_bytes);
+
+/* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of
  * ParallelFilterCombination.forward, src/torchfx/filter/__base.py:1019-1026).
  * xs_host: HOST array of n DEVICE pointers, each [numel] of dtype.

@@ -18,11 +18,12 @@ from torchfx_amd.modulation import modulated_delay
 from torchfx_amd.phaser import phase_shift
 from torchfx_amd.resample import Resample, resample_poly
 from torchfx_amd.reverb import freeverb, freeverb_bank
-from torchfx_amd.spectral import MelSpectrogram, istft, mel_filterbank, mel_spectrogram, spectrogram, stft
+from torchfx_amd.spectral import (MelSpectrogram, PitchShift, TimeStretch, istft, mel_filterbank, mel_spectrogram, phase_vocoder, pitch_shift,
+                                  spectrogram, stft, time_stretch)
 from torchfx_amd.wave import Wave
 from torchfx_amd.waveshaper import waveshape
 
 __all__ = ["FX", "Chorus", "Compressor", "Delay", "Distortion", "FilterChain", "Flanger", "Freeverb", "Gain", "Gate", "Limiter", "LoudnessNormalize", "MelSpectrogram", "ModulatedDelay", "Normalize", "Phaser", "Resample", "Reverb", "Wave", "block_energy",
            "compress", "filter", "freeverb", "freeverb_bank", "gate", "integrated_loudness", "is_native_available", "istft", "kweighting_sos", "limit", "loudness_range", "mel_filterbank", "mel_spectrogram", "modulated_delay", "momentary_loudness",
-           "phase_shift", "resample_poly", "short_term_loudness", "sosfiltfilt", "spectrogram", "stft", "true_peak", "true_peak_linear", "Vibrato", "Waveshaper", "waveshape"]
+           "phase_shift", "phase_vocoder", "pitch_shift", "PitchShift", "resample_poly", "time_stretch", "TimeStretch", "short_term_loudness", "sosfiltfilt", "spectrogram", "stft", "true_peak", "true_peak_linear", "Vibrato", "Waveshaper", "waveshape"]
 __version__ = "0.1.0"

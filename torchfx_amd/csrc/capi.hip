@@ -905,6 +905,26 @@ int tfx_mel_plan_info(int64_t n_fft, int64_t hop, int64_t win_length, int64_t T,
     TFX_API_END
 }
 
+int tfx_phase_vocoder_forward(const void *spec, void *out, int dtype, int64_t rows, int64_t frames, int64_t bins, double rate,
+                              int64_t segments, void *scratch, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    phase_vocoder_forward(spec, out, dtype, rows, frames, bins, rate, segments, scratch, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_phase_vocoder_plan_info(int64_t rows, int64_t frames, int64_t bins, double rate, int dtype, int64_t segments,
+                                int64_t *out_frames, int64_t *bin_tile, int64_t *segments_out, int64_t *seg_frames, int64_t *launches,
+                                int64_t *workgroups, int64_t *scratch_bytes)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(out_frames && bin_tile && segments_out && seg_frames && launches && workgroups && scratch_bytes,
+              "phase_vocoder_plan_info: null output");
+    phase_vocoder_plan_info(rows, frames, bins, rate, dtype, segments, out_frames, bin_tile, segments_out, seg_frames, launches, workgroups,
+                            scratch_bytes);
+    TFX_API_END
+}
+
 int tfx_sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, tfx_stream_t stream)
 {
     TFX_API_BEGIN

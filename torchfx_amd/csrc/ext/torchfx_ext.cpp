@@ -809,6 +809,53 @@ std::tuple<Tensor, Tensor> istft_op(const Tensor &spec_in, const OptTensor &wind
     return std::make_tuple(out, flag);
 }
 
+// Phase vocoder (tfx_phase_vocoder_forward): spec [bins, frames], [C, bins, frames] or [B, C, bins, frames], complex64 /
+// complex128; rate > 0; segments 0 = the plan's choice -> [..., bins, Fo], the transposed view of a contiguous [..., Fo, bins]
+// buffer: stft_forward's layout in and out, so istft_forward reads the result in place.  Any other input layout is copied into
+// it first.  The summaries between the two launches live in a tensor from torch's allocator.
+struct VocoderShape {
+    std::vector<int64_t> sizes;     // [..., Fo, bins]
+    int dt;
+    int64_t rows, frames, bins, scratch_bytes;
+};
+
+VocoderShape vocoder_shape(const Tensor &spec, double rate, int64_t segments, const char *what)
+{
+    TORCH_CHECK(spec.dim() >= 2 && spec.dim() <= 4, what, ": spec must be [bins, frames], [C, bins, frames] or [B, C, bins, frames], got ",
+                spec.dim(), " dimensions");
+    TORCH_CHECK(spec.scalar_type() == at::kComplexFloat || spec.scalar_type() == at::kComplexDouble, what,
+                ": expected a complex64 or complex128 tensor, got ", spec.scalar_type());
+    VocoderShape s;
+    s.dt = spec.scalar_type() == at::kComplexFloat ? TFX_F32 : TFX_F64;
+    s.bins = spec.size(-2);
+    s.frames = spec.size(-1);
+    s.rows = c10::multiply_integers(spec.sizes().begin(), spec.sizes().end() - 2);
+    int64_t info[7];
+    check_rc(tfx_phase_vocoder_plan_info(s.rows, s.frames, s.bins, rate, s.dt, segments, info, info + 1, info + 2, info + 3, info + 4,
+                                         info + 5, info + 6),
+             what);
+    s.scratch_bytes = info[6];
+    s.sizes.assign(spec.sizes().begin(), spec.sizes().end() - 2);
+    s.sizes.push_back(info[0]);
+    s.sizes.push_back(s.bins);
+    return s;
+}
+
+Tensor phase_vocoder_op(const Tensor &spec_in, double rate, int64_t segments)
+{
+    const char *what = "phase_vocoder_forward";
+    need_device(spec_in, "spec");
+    const VocoderShape s = vocoder_shape(spec_in, rate, segments, what);
+    const Tensor spec = spec_in.transpose(-1, -2).contiguous();         // [..., frames, bins]: no copy for stft_forward's layout
+    Tensor out = at::empty(s.sizes, spec.options());
+    Tensor scratch = at::empty({s.scratch_bytes / 4}, spec.options().dtype(at::kInt));
+    c10::hip::HIPGuard guard(spec.get_device());
+    check_rc(tfx_phase_vocoder_forward(spec.data_ptr(), out.data_ptr(), s.dt, s.rows, s.frames, s.bins, rate, segments,
+                                       s.scratch_bytes ? scratch.data_ptr() : nullptr, stream_of(spec)),
+             what);
+    return out.transpose(-1, -2);
+}
+
 // Freeverb (tfx_freeverb_forward): x [T], [C, T] or [B, C, T] with C 1 or 2; comb_delays / allpass_delays the flattened
 // [C, NC] / [C, NA] tables in samples; state [B * C, state_len] float64 or None (silence) -> (y [..., T + tail], new state).
 // The shape and the tables are checked here and by the plan, before anything touches the device; the workspace (global lines,
@@ -1711,6 +1758,20 @@ TORCH_LIBRARY(torchfx_spectral_inverse, m)
 TORCH_LIBRARY_IMPL(torchfx_spectral_inverse, Meta, m)
 {
     m.impl("istft_forward", istft_meta);
+}
+
+// The phase vocoder between the two: torch.ops.torchfx_vocoder.
+TORCH_LIBRARY(torchfx_vocoder, m)
+{
+    reg_op(m, "phase_vocoder_forward(Tensor spec, float rate, int segments=0) -> Tensor", phase_vocoder_op);
+}
+
+TORCH_LIBRARY_IMPL(torchfx_vocoder, Meta, m)
+{
+    m.impl("phase_vocoder_forward", [](const Tensor &spec, double rate, int64_t segments) {
+        const VocoderShape s = vocoder_shape(spec, rate, segments, "phase_vocoder_forward");
+        return at::empty(s.sizes, spec.options()).transpose(-1, -2);
+    });
 }
 
 // The mel spectrogram in a namespace of its own: torch.ops.torchfx_mel.

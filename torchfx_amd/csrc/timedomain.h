@@ -1,5 +1,5 @@
 // timedomain.h -- the host entry points of the time-domain and elementwise ops, one prototype per exported function of fir.hip,
-// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip, compressor.hip, modulation.hip, reverb.hip, waveshaper.hip, phaser.hip, gate.hip, stft.hip, istft.hip, mel.hip and layout.hip (the cascade's: sos.h; the
+// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip, compressor.hip, modulation.hip, reverb.hip, waveshaper.hip, phaser.hip, gate.hip, stft.hip, istft.hip, mel.hip, phasevocoder.hip and layout.hip (the cascade's: sos.h; the
 // overlap-save pipelines': ols_route.h).  Included by the file that defines each function and by capi.hip, so a prototype that drifts from
 // its definition does not compile; default arguments live here and nowhere else.  Every *_forward checks its arguments before
 // anything touches the device; a *_plan_info takes the same checking path without the pointers.
@@ -172,6 +172,13 @@ void mel_plan_info(int64_t n_fft, int64_t hop, int64_t win_length, int64_t T, in
                    int64_t n_filters, int64_t total_band, int *route, int64_t *frames, int64_t *frames_per_workgroup,
                    int64_t *lanes_per_filter, int64_t *lds_bytes, int64_t *workgroups);
 void mel_clear();
+
+// ---- phasevocoder.hip ----
+void phase_vocoder_forward(const void *spec, void *out, int dtype, int64_t rows, int64_t frames, int64_t bins, double rate,
+                           int64_t segments, void *scratch, hipStream_t stream);
+void phase_vocoder_plan_info(int64_t rows, int64_t frames, int64_t bins, double rate, int dtype, int64_t segments, int64_t *out_frames,
+                             int64_t *bin_tile, int64_t *segments_out, int64_t *seg_frames, int64_t *launches, int64_t *workgroups,
+                             int64_t *scratch_bytes);
 
 // ---- layout.hip ----
 void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, int64_t C, int64_t ld_out, int64_t f_base,

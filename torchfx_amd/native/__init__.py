@@ -137,6 +137,14 @@ def mel_ops():
     return torch.ops.torchfx_mel
 
 
+def vocoder_ops():
+    """``torch.ops.torchfx_vocoder`` (the phase vocoder's namespace, registered by the same module) with the library loaded."""
+    import torch
+
+    load()
+    return torch.ops.torchfx_vocoder
+
+
 def spectral_inverse_ops():
     """``torch.ops.torchfx_spectral_inverse`` (the inverse short-time Fourier transform's namespace, registered by the same module) with the library loaded."""
     import torch

@@ -63,6 +63,7 @@ from torchfx_amd.filter._base import AbstractFilter
 from torchfx_amd.filter.fir import FIR
 from torchfx_amd.filter.zerophase import ZeroPhase
 from torchfx_amd.resample import Resample, design_taps, window_key
+from torchfx_amd.spectral import TimeStretch
 
 
 def _rows(x: Tensor) -> int:
@@ -1037,12 +1038,21 @@ _REFUSALS = (
              "place, or run the whole signal (wave | Phaser(...)) before or after streaming"),
 )
 
+# The round trips through the spectrum (PitchShift is a TimeStretch): families of their own behind the table above, whose
+# membership and order its tests pin.
+_SPECTRAL_REFUSALS = (
+    _Refusal(TimeStretch, (),
+             "{name} cannot run in {who}: the phase vocoder is a transform of the whole signal -- its frames overlap every chunk "
+             "boundary and its phase runs from the first frame on, and a chunk stretched on its own would not keep its length; "
+             "run the whole signal (wave | {name}(...)) before or after streaming"),
+)
+
 
 def _check_streamable(e, who: str) -> None:
     """Raise the TypeError of the first family in ``_REFUSALS`` that ``e``, a top-level effect of ``who``'s chain, or a module
     inside it belongs to."""
     members = _members(e)
-    for r in _REFUSALS:
+    for r in _REFUSALS + _SPECTRAL_REFUSALS:
         if r.who not in (None, who):
             continue
         for m in members:

@@ -27,10 +27,19 @@ written.  It serves what the STFT's route serves with up to 256 filters whose ba
 (``torchfx_ext.mel_plan_info``).
 
 Not here: ``onesided=False`` and ``return_complex=True`` on the device route, MFCC / DCT, the inverse mel transform, streaming
-forms, autograd, axes other than the last, round-trip effect classes.
+forms, autograd, axes other than the last.
+
+Between the two transforms stands the phase vocoder (:func:`phase_vocoder`, ``torchaudio.functional.phase_vocoder``'s meaning):
+one or two launches of ``torchfx_amd/csrc/phasevocoder.hip`` (``torchfx_ext.phase_vocoder_forward``) that read the spectrum once,
+in the layout :func:`stft` returns, and write the stretched one once, in the layout :func:`istft` reads, with the running phase
+kept exactly as a 64-bit integer.  On it rest :func:`time_stretch` / :class:`TimeStretch` (tempo without pitch) and
+:func:`pitch_shift` / :class:`PitchShift` (pitch without tempo; the last step is :func:`torchfx_amd.resample_poly`).  Not
+provided: phase locking (identity or scaled), transient preservation, formant correction, a streaming vocoder, autograd, axes
+other than the last two, a time-varying ``rate``.
 """
 from __future__ import annotations
 
+import fractions
 import math
 import re
 import warnings
@@ -40,8 +49,10 @@ import torch
 from torch import Tensor
 
 from torchfx_amd import torchfx_ext as E
+from torchfx_amd.effect import FX
 
-__all__ = ["stft", "spectrogram", "istft", "named_window", "mel_filterbank", "mel_spectrogram", "MelSpectrogram"]
+__all__ = ["stft", "spectrogram", "istft", "named_window", "mel_filterbank", "mel_spectrogram", "MelSpectrogram", "phase_vocoder",
+           "time_stretch", "pitch_shift", "TimeStretch", "PitchShift"]
 
 _NAMED = {"hann": torch.hann_window, "hamming": torch.hamming_window, "rect": torch.ones}
 
@@ -426,3 +437,225 @@ def mel_spectrogram(x: Tensor, sample_rate: float, n_fft: int = 1024, hop_length
     fb).transpose(-1, -2)`` and the logarithm in torch ops on the tensor's own device."""
     return MelSpectrogram(sample_rate, n_fft, hop_length, win_length, window, n_mels, f_min, f_max, norm, mel_scale, power, center,
                           pad_mode, normalized, log, amin, top_db, filterbank)(x)
+
+
+def _vocoder_rate(rate, what: str = "phase_vocoder") -> float:
+    if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not math.isfinite(rate) or not rate > 0:
+        raise ValueError(f"{what}: rate must be a finite number > 0, got {rate!r}")
+    return float(rate)
+
+
+def _vocoder_host(X: np.ndarray, rate: float) -> np.ndarray:
+    """The definition of :func:`phase_vocoder` on a host array ``[..., bins, F]``, with the device's fixed-point phase."""
+    real = np.float32 if X.dtype == np.complex64 else np.float64
+    F = X.shape[-1]
+    Fo = int(math.ceil(F / rate))
+    pos = np.arange(Fo, dtype=np.float64) * rate
+    i = np.floor(pos).astype(np.int64)
+    alpha = (pos - i).astype(real)
+    Xp = np.concatenate([X, np.zeros(X.shape[:-1] + (2,), dtype=X.dtype)], axis=-1)          # frames F and F + 1 are zeros
+    re, im = Xp.real.astype(np.float64), Xp.imag.astype(np.float64)
+    finite = np.isfinite(re) & np.isfinite(im)
+    with np.errstate(invalid="ignore", over="ignore"):
+        turns = np.where(finite & ((re != 0) | (im != 0)), np.arctan2(im, re) * 0.15915494309189535, 0.0)
+        w = np.rint(turns * 2.0 ** 64)
+        A = np.where(w >= 2.0 ** 63, w - 2.0 ** 64, w).astype(np.int64).view(np.uint64)      # 2^64 = one turn
+        inc = A[..., i + 1] - A[..., i]                                                      # wraps, as the sum does
+        P = A[..., :1] + np.concatenate([np.zeros_like(inc[..., :1]), np.cumsum(inc, axis=-1, dtype=np.uint64)[..., :-1]], axis=-1)
+        ang = P.view(np.int64).astype(np.float64) * (math.pi * 2.0 ** -63)                   # [-pi, pi]
+        M = np.abs(Xp).astype(real)
+        mag = (alpha * M[..., i + 1] + (real(1) - alpha) * M[..., i]).astype(np.float64)
+        Y = (mag * np.cos(ang) + 1j * (mag * np.sin(ang))).astype(X.dtype)
+    bad = np.logical_or.accumulate(~(finite[..., i] & finite[..., i + 1]), axis=-1)
+    Y[bad] = complex(np.nan, np.nan)
+    return Y
+
+
+@torch.no_grad()
+def phase_vocoder(X: Tensor, rate: float, phase_advance: Tensor | None = None) -> Tensor:
+    """``torchaudio.functional.phase_vocoder(X, rate, phase_advance)``: the spectrum ``X [bins, F]``, ``[C, bins, F]`` or
+    ``[B, C, bins, F]`` (complex64 / complex128) sped up by ``rate > 0`` (a Python float) without a change of pitch:
+    ``[..., bins, Fo]`` with ``Fo = ceil(F / rate)``, computed in double as ``torch.arange(0, F, rate)`` sizes itself.
+
+    Output frame ``t`` stands at ``p = t rate`` (double), ``i = floor(p)``, ``alpha = p - i`` rounded once to the real dtype;
+    input frames ``F`` and ``F + 1`` are zeros (torchaudio's padding).  ``mag[t] = alpha |X[i+1]| + (1 - alpha) |X[i]|`` in the
+    real dtype, ``phase[t] = angle(X[0]) + sum_{s<t} (angle(X[i_s + 1]) - angle(X[i_s]))`` and ``Y[t] = polar(mag[t], phase[t])``,
+    formed in double and rounded once.  torchaudio adds ``wrap(d - pa) + pa`` per step, with ``pa`` the expected advance
+    ``phase_advance``: that differs from ``d`` by whole turns and only ``phase mod 2 pi`` reaches ``Y``, so **``phase_advance``
+    drops out of the result**.  It is accepted for compatibility (torchaudio's default is ``linspace(0, pi hop, bins)[..., None]``),
+    checked to be a real ``[bins, 1]`` tensor when given, and changes nothing.
+
+    The phase is kept in turns as 64-bit fixed point: each bin's angle once, ``A = rint(atan2(im, re) / 2 pi * 2^64)`` in
+    float64 (0 for the zero bin), and the sum in wrapping integers -- exact however long the signal, equal to ``A[t]`` at
+    ``rate=1``, and the same bits whatever the segment count, the other rows or the batch.  From the first output frame that
+    reads a bin with a NaN or Inf component every later frame of that (row, bin) is NaN in both parts; earlier frames, other
+    bins and other rows keep their bits.
+
+    Device tensors take ``torchfx_amd/csrc/phasevocoder.hip`` (``torchfx_ext.phase_vocoder_forward``), which reads the layout
+    :func:`stft` returns in place and writes the one :func:`istft` reads; CPU tensors run the same definition in NumPy with the
+    same integer phase.  There is no other route.  ``ValueError`` names a bad argument."""
+    if not isinstance(X, Tensor) or X.dtype not in (torch.complex64, torch.complex128) or X.dim() not in (2, 3, 4):
+        got = f"{X.dtype} {tuple(X.shape)}" if isinstance(X, Tensor) else type(X).__name__
+        raise ValueError(f"phase_vocoder: X must be a complex64 / complex128 tensor [bins, F], [C, bins, F] or [B, C, bins, F], got {got}")
+    rate = _vocoder_rate(rate)
+    if phase_advance is not None:
+        if not isinstance(phase_advance, Tensor) or phase_advance.is_complex() or not phase_advance.dtype.is_floating_point \
+                or tuple(phase_advance.shape) != (X.shape[-2], 1):
+            got = tuple(phase_advance.shape) if isinstance(phase_advance, Tensor) else type(phase_advance).__name__
+            raise ValueError(f"phase_vocoder: phase_advance must be a real [bins, 1] = [{X.shape[-2]}, 1] tensor, got {got}")
+    if X.is_cuda:
+        with torch.cuda.device(X.device):
+            return E.phase_vocoder_forward(X, rate)
+    return torch.from_numpy(_vocoder_host(X.detach().numpy(), rate))
+
+
+def _stretch_geometry(what: str, x: Tensor, n_fft, hop_length, win_length, window, length: int | None = None):
+    """The checks of a stretch of ``x`` (rows of ``length`` samples, default x's) and its resolved ``(n_fft, hop, win_length,
+    window)``."""
+    if not isinstance(x, Tensor) or x.dtype not in (torch.float32, torch.float64) or x.dim() not in (1, 2, 3) or x.shape[-1] < 1:
+        got = f"{x.dtype} {tuple(x.shape)}" if isinstance(x, Tensor) else type(x).__name__
+        raise ValueError(f"{what}: x must be a float32 / float64 tensor [T], [C, T] or [B, C, T] with T >= 1, got {got}")
+    n_fft = int(n_fft)
+    hop = int(hop_length) if hop_length is not None else n_fft // 4
+    wl = int(win_length) if win_length is not None else n_fft
+    if n_fft < 2 or not 0 < wl <= n_fft or not 0 < hop <= wl:
+        raise ValueError(f"{what}: need n_fft >= 2 and 0 < hop_length <= win_length <= n_fft, got n_fft {n_fft}, hop_length {hop}, "
+                         f"win_length {wl}")
+    T = int(x.shape[-1]) if length is None else int(length)
+    if T <= n_fft // 2:
+        raise ValueError(f"{what}: x must be longer than n_fft / 2 = {n_fft // 2} samples (the reflected edge), got {T}")
+    if isinstance(window, str):
+        window = named_window(window, wl, x.dtype, x.device)
+    elif not isinstance(window, Tensor) or tuple(window.shape) != (wl,) or window.dtype != x.dtype or window.device != x.device:
+        got = f"{window.dtype} {tuple(window.shape)} on {window.device}" if isinstance(window, Tensor) else type(window).__name__
+        raise ValueError(f"{what}: window must be a name or a [win_length = {wl}] tensor of x's dtype and device ({x.dtype} on "
+                         f"{x.device}), got {got}")
+    return n_fft, hop, wl, window
+
+
+@torch.no_grad()
+def time_stretch(x: Tensor, rate: float, n_fft: int = 2048, hop_length: int | None = None, win_length: int | None = None,
+                 window: Tensor | str = "hann") -> Tensor:
+    """Change the tempo of ``x [T]``, ``[C, T]`` or ``[B, C, T]`` by ``rate`` and keep its pitch: ``istft(phase_vocoder(stft(x),
+    rate), length=round(T / rate))`` with a centred, reflected :func:`stft` (``hop_length`` defaults to ``n_fft // 4``,
+    ``window`` is a tensor or a name of :func:`named_window`).  ``rate > 1`` is faster and shorter.  On a ROCm device with
+    ``n_fft`` in 256 ... 4096 that is three kernels and no copy between them: the vocoder reads the buffer the transform wrote
+    and the inverse reads the buffer the vocoder wrote."""
+    rate = _vocoder_rate(rate, "time_stretch")
+    n_fft, hop, wl, window = _stretch_geometry("time_stretch", x, n_fft, hop_length, win_length, window)
+    Y = phase_vocoder(stft(x, n_fft, hop, wl, window), rate)
+    return istft(Y, n_fft, hop, wl, window, length=int(round(x.shape[-1] / rate)))
+
+
+def _pitch_ratio(n_steps, bins_per_octave) -> tuple[float, int, int]:
+    """``(r, up, down)``: the stretch rate ``r = 2 ** (-n_steps / bins_per_octave)`` and, with ``down / up`` the rational
+    approximation of ``1 / r`` (``Fraction(1 / r).limit_denominator(1000)``), the ``resample_poly(up, down)`` that brings the
+    stretched ``T / r`` samples back to ``T``."""
+    if isinstance(n_steps, bool) or not isinstance(n_steps, (int, float)) or not math.isfinite(n_steps):
+        raise ValueError(f"pitch_shift: n_steps must be a finite number, got {n_steps!r}")
+    if isinstance(bins_per_octave, bool) or not isinstance(bins_per_octave, int) or bins_per_octave < 1:
+        raise ValueError(f"pitch_shift: bins_per_octave must be an integer >= 1, got {bins_per_octave!r}")
+    r = 2.0 ** (-float(n_steps) / bins_per_octave)
+    q = fractions.Fraction(1.0 / r).limit_denominator(1000)
+    if q <= 0:
+        raise ValueError(f"pitch_shift: n_steps {n_steps!r} is out of range")
+    return r, q.denominator, q.numerator
+
+
+@torch.no_grad()
+def pitch_shift(x: Tensor, n_steps: float, bins_per_octave: int = 12, n_fft: int = 2048, hop_length: int | None = None,
+                win_length: int | None = None, window: Tensor | str = "hann") -> Tensor:
+    """Shift the pitch of ``x [T]``, ``[C, T]`` or ``[B, C, T]`` by ``n_steps`` steps of ``bins_per_octave`` to the octave
+    (12: semitones) and keep length and rate: with ``r = 2 ** (-n_steps / bins_per_octave)``, :func:`time_stretch` by ``r``,
+    then ``resample_poly(up, down)`` with ``down / up`` the rational approximation of ``1 / r``
+    (``fractions.Fraction(1 / r).limit_denominator(1000)``: that many input samples per output sample, so ``T / r`` samples
+    come back to ``T``), then the result is trimmed or zero-padded to ``T``."""
+    r, up, down = _pitch_ratio(n_steps, bins_per_octave)
+    from torchfx_amd.resample import resample_poly
+
+    T = x.shape[-1] if isinstance(x, Tensor) and x.dim() else 0
+    y = resample_poly(time_stretch(x, r, n_fft, hop_length, win_length, window), up, down)
+    if y.shape[-1] >= T:
+        return y[..., :T].contiguous()
+    return torch.nn.functional.pad(y, (0, T - y.shape[-1]))
+
+
+class TimeStretch(FX):
+    """:func:`time_stretch` as an effect: ``wave | TimeStretch(0.8)`` is a ``Wave`` of ``round(T / rate)`` samples at the same
+    ``fs``.  A whole-signal effect that changes the length: the planner keeps it as a step of its own, and
+    ``StreamProcessor`` and ``RealtimeProcessor`` refuse it."""
+
+    def __init__(self, rate: float, n_fft: int = 2048, hop_length: int | None = None, win_length: int | None = None,
+                 window: Tensor | str = "hann") -> None:
+        super().__init__()
+        self.rate = _vocoder_rate(rate, type(self).__name__)
+        self.n_fft, self.hop_length, self.win_length = int(n_fft), hop_length, win_length
+        if isinstance(window, Tensor):
+            self.register_buffer("window", window, persistent=False)    # moves with the effect (.to)
+        else:
+            self.window = window
+
+    def _stretch(self) -> float:
+        return self.rate
+
+    def output_length(self, length: int) -> int:
+        return int(round(int(length) / self.rate))
+
+    def route(self, x: Tensor, length: int | None = None) -> str:
+        """``native (<kernels>, <the vocoder's plan>)`` or ``numpy on host -- <reason>`` for ``x`` (rows of ``length`` samples,
+        default x's)."""
+        n = int(x.shape[-1]) if length is None else int(length)
+        try:
+            n_fft, hop, wl, _ = _stretch_geometry(type(self).__name__, x, self.n_fft, self.hop_length, self.win_length, self.window, n)
+        except ValueError as e:
+            return f"refused -- {e}"
+        if not x.is_cuda:
+            return f"torch.stft, phase vocoder in numpy, torch.istft on host -- {x.device.type} tensor"
+        rows, rate = max(1, x.numel() // max(1, int(x.shape[-1]))), self._stretch()
+        fwd = E.stft_plan_info(n_fft, hop, wl, n, rows, x.dtype)
+        pv = E.phase_vocoder_plan_info(fwd["frames"], n_fft // 2 + 1, rate, rows, x.dtype)
+        inv = E.istft_plan_info(n_fft, hop, wl, pv["out_frames"], rows, x.dtype, True, int(round(n / rate)))
+        cut = "one launch" if pv["launches"] == 1 else f"summary pass + final pass over {pv['segments']} segments of {pv['seg_frames']} frames"
+        steps = ["stft_kernel" if fwd["route"] == "lds" else "torch.stft",
+                 f"phase_vocoder_kernel ({fwd['frames']} -> {pv['out_frames']} frames, {cut}, bin tile {pv['bin_tile']})",
+                 "istft_kernel" if inv["route"] == "lds" else "torch.istft"]
+        copies = "no layout copy between them" if fwd["route"] == inv["route"] == "lds" else "torch's transforms own their layouts"
+        return f"native ({' + '.join(steps + self._last_step(x, int(round(n / rate))))}; {copies})"
+
+    def _last_step(self, x: Tensor, length: int) -> list[str]:
+        return []
+
+    def forward(self, x: Tensor) -> Tensor:
+        return time_stretch(x, self.rate, self.n_fft, self.hop_length, self.win_length, self.window)
+
+    def extra_repr(self) -> str:
+        return f"rate={self.rate}, n_fft={self.n_fft}, hop_length={self.hop_length}, win_length={self.win_length}"
+
+
+class PitchShift(TimeStretch):
+    """:func:`pitch_shift` as an effect: ``wave | PitchShift(3)`` is the signal three semitones up, at the same length and
+    ``fs``.  A whole-signal effect: the planner keeps it as a step of its own, and ``StreamProcessor`` and
+    ``RealtimeProcessor`` refuse it."""
+
+    def __init__(self, n_steps: float, bins_per_octave: int = 12, n_fft: int = 2048, hop_length: int | None = None,
+                 win_length: int | None = None, window: Tensor | str = "hann") -> None:
+        r, self.up, self.down = _pitch_ratio(n_steps, bins_per_octave)
+        super().__init__(r, n_fft, hop_length, win_length, window)
+        self.n_steps, self.bins_per_octave = n_steps, bins_per_octave
+
+    def output_length(self, length: int) -> int:
+        return int(length)
+
+    def _last_step(self, x: Tensor, length: int) -> list[str]:
+        from torchfx_amd.resample import design_taps
+
+        if self.up == self.down:
+            return []
+        taps = int(design_taps(self.up, self.down, ("kaiser", 5.0), x.dtype).numel())
+        return [f"{E.resample_plan_info(length, self.up, self.down, taps, x.dtype)['kernel']} ({self.up} / {self.down})"]
+
+    def forward(self, x: Tensor) -> Tensor:
+        return pitch_shift(x, self.n_steps, self.bins_per_octave, self.n_fft, self.hop_length, self.win_length, self.window)
+
+    def extra_repr(self) -> str:
+        return f"n_steps={self.n_steps}, bins_per_octave={self.bins_per_octave}, n_fft={self.n_fft}, hop_length={self.hop_length}"

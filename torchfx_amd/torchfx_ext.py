@@ -40,6 +40,7 @@ __all__ = [
     "modulated_delay_forward", "modulated_delay_stream_forward", "modulated_delay_plan_info", "freeverb_forward", "freeverb_plan_info",
     "waveshaper_stream_forward", "waveshaper_stream_plan_info", "phaser_forward", "phaser_plan_info", "gate_forward", "gate_plan_info",
     "stft_forward", "stft_plan_info", "istft_forward", "istft_plan_info", "mel_forward", "mel_plan_info", "mel_band_table",
+    "phase_vocoder_forward", "phase_vocoder_plan_info",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "effects_plan_info", "deinterleave_forward", "interleave_forward", "sos_plan_info", "sos_route_info", "ols_plan_info", "prewarm",
 ]
@@ -702,6 +703,31 @@ def istft_plan_info(n_fft: int, hop: int, win_length: int, frames: int, rows: in
                   "route:int length tile frames_per_batch threads_per_frame lds_bytes workgroups redundant_share:double")
     info["route"] = "lds" if info["route"] == 1 else "torch"
     return info
+
+
+def phase_vocoder_forward(spec: Tensor, rate: float, segments: int = 0) -> Tensor:
+    """The phase vocoder (``tfx_phase_vocoder_forward``; the definition is :func:`torchfx_amd.spectral.phase_vocoder`'s):
+    ``spec [bins, frames]``, ``[C, bins, frames]`` or ``[B, C, bins, frames]`` on the device (complex64 / complex128), ``rate > 0``.
+    Returns ``[..., bins, ceil(frames / rate)]``, a transposed view of a contiguous ``[..., Fo, bins]`` buffer: the layout
+    :func:`stft_forward` returns, which the kernel also reads in place (any other layout costs one copy into it first), so
+    :func:`istft_forward` takes the result without a copy.  ``segments`` cuts each row's output frames (0: the plan's choice,
+    :func:`phase_vocoder_plan_info`): one launch for one segment, two otherwise, to the same bits.  The op lives in
+    ``torch.ops.torchfx_vocoder``."""
+    native.ops()                                         # loads the library: every namespace is registered by the one module
+    return native.vocoder_ops().phase_vocoder_forward(spec, float(rate), int(segments))
+
+
+def phase_vocoder_plan_info(frames: int, bins: int, rate: float, rows: int = 1, dtype: torch.dtype = torch.float32,
+                            segments: int = 0) -> dict:
+    """What :func:`phase_vocoder_forward` does for ``rows`` spectra of ``frames`` frames of ``bins`` bins
+    (``tfx_phase_vocoder_plan_info``; host-only, same checks on the sizes): ``out_frames`` (``ceil(frames / rate)``), ``bin_tile``
+    (the bins of a workgroup, one lane each), the ``segments`` it takes for the request (0: chosen from the sizes, 1 when rows and
+    bin tiles alone fill the chip), ``seg_frames`` (output frames per segment; the last may hold fewer), ``launches`` (1 or 2),
+    ``workgroups`` of the writing launch and ``scratch_bytes`` (the summaries between the launches; 0 for one segment).
+    ``dtype`` is the real or the complex one."""
+    dtype = {torch.complex64: torch.float32, torch.complex128: torch.float64}.get(dtype, dtype)
+    return _query(L.load().tfx_phase_vocoder_plan_info, (int(rows), int(frames), int(bins), float(rate), _dt(dtype), int(segments)),
+                  "out_frames bin_tile segments seg_frames launches workgroups scratch_bytes")
 
 
 RESAMPLE_STREAM_KERNELS = ("resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel", "copy")

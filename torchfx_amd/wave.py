@@ -213,6 +213,7 @@ def _member_key(m: nn.Module, guard: list) -> tuple:
     from torchfx_amd.effect import Compressor, Delay, Freeverb, Gain, Gate, Limiter, LoudnessNormalize, ModulatedDelay, Normalize, Phaser, Waveshaper
     from torchfx_amd.filter.zerophase import ZeroPhase
     from torchfx_amd.resample import Resample, window_key
+    from torchfx_amd.spectral import PitchShift, TimeStretch
 
     guard.append(m)
     k: tuple = (id(m),)
@@ -236,6 +237,9 @@ def _member_key(m: nn.Module, guard: list) -> tuple:
         k += (m.new_fs, m.fs, window_key(m.window))
     elif isinstance(m, ZeroPhase):
         k += (m.padtype, m.padlen)
+    elif isinstance(m, TimeStretch):
+        k += (m.rate, getattr(m, "up", 0), getattr(m, "down", 0), m.n_fft, m.hop_length, m.win_length,
+              window_key(m.window) if isinstance(m.window, Tensor) else m.window)
     elif isinstance(m, LoudnessNormalize):
         k += (m.target, m.channel_weights, m.fs)
     elif isinstance(m, Limiter):
@@ -344,19 +348,22 @@ class Wave:
         and nothing merges, folds or attaches an epilogue across one.  So is a ``ZeroPhase`` (its two passes are one step;
         the row length stays), a ``LoudnessNormalize`` (it measures exactly the signal the steps before it produce) and a
         ``Limiter``, a ``Compressor`` or a ``Gate`` (their detectors read the samples the steps before them store).  A ``Freeverb`` is a step
-        of its own too (its workgroups own whole rows), and its ``tail`` lengthens the rows for the steps after it."""
+        of its own too (its workgroups own whole rows), and its ``tail`` lengthens the rows for the steps after it.  A
+        ``TimeStretch`` or ``PitchShift`` is a round trip through the spectrum of the whole signal: a step of its own, after
+        which the rows have the step's ``output_length``."""
         from torchfx_amd.effect import Compressor, Freeverb, Gate, Limiter, LoudnessNormalize
         from torchfx_amd.filter.zerophase import ZeroPhase
         from torchfx_amd.resample import Resample
+        from torchfx_amd.spectral import TimeStretch
 
         plan: list[nn.Module] = []
         segment: list[nn.Module] = []
         for m in self._pipeline:
-            if isinstance(m, (Resample, ZeroPhase, LoudnessNormalize, Limiter, Compressor, Gate, Freeverb)):
+            if isinstance(m, (Resample, ZeroPhase, LoudnessNormalize, Limiter, Compressor, Gate, Freeverb, TimeStretch)):
                 plan += self._build_segment(segment, length, dtype)
                 plan.append(m)
                 segment = []
-                if isinstance(m, (Resample, Freeverb)):
+                if isinstance(m, (Resample, Freeverb, TimeStretch)):
                     length = m.output_length(length)
             else:
                 segment.append(m)
@@ -592,6 +599,7 @@ class Wave:
         from torchfx_amd.filter.zerophase import ZeroPhase
         from torchfx_amd.realtime import StatefulDelay, _native_stream
         from torchfx_amd.resample import Resample
+        from torchfx_amd.spectral import TimeStretch
 
         lines = []
         length = int(self._ys.shape[-1]) if self._ys.dim() else 0
@@ -611,7 +619,7 @@ class Wave:
                                 else f"torch composition -- {self._ys.device.type} {self._ys.dtype} signal")
             elif isinstance(inner, Delay):
                 line += ": " + Wave._delay_route(inner, self._ys, self.fs)
-            elif isinstance(inner, (Resample, Freeverb)):
+            elif isinstance(inner, (Resample, Freeverb, TimeStretch)):
                 line += ": " + inner.route(self._ys, length)
                 length = inner.output_length(length)
             elif isinstance(inner, (ZeroPhase, LoudnessNormalize, Limiter, Compressor, Gate, ModulatedDelay, Waveshaper, Phaser)):
@@ -787,6 +795,22 @@ class Wave:
         from torchfx_amd.resample import Resample
 
         return self | Resample(new_fs, window=window)
+
+    def time_stretch(self, rate: float, n_fft: int = 2048, hop_length: int | None = None, win_length: int | None = None,
+                     window="hann") -> "Wave":
+        """``self | TimeStretch(rate, ...)``: the signal ``rate`` times as fast at the same pitch and ``fs``, ``round(T / rate)``
+        samples long (:func:`torchfx_amd.spectral.time_stretch`)."""
+        from torchfx_amd.spectral import TimeStretch
+
+        return self | TimeStretch(rate, n_fft, hop_length, win_length, window)
+
+    def pitch_shift(self, n_steps: float, bins_per_octave: int = 12, n_fft: int = 2048, hop_length: int | None = None,
+                    win_length: int | None = None, window="hann") -> "Wave":
+        """``self | PitchShift(n_steps, ...)``: the signal ``n_steps`` steps higher at the same length and ``fs``
+        (:func:`torchfx_amd.spectral.pitch_shift`)."""
+        from torchfx_amd.spectral import PitchShift
+
+        return self | PitchShift(n_steps, bins_per_octave, n_fft, hop_length, win_length, window)
 
     # ------------------------------------------------------------------ files
     _SUBTYPE_BY_ENCODING = {"PCM_S": lambda b: f"PCM_{b}", "PCM_U": lambda b: "PCM_U8" if b == 8 else f"PCM_{b}",
