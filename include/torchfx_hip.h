@@ -994,6 +994,39 @@ int tfx_phase_vocoder_plan_info(int64_t rows, int64_t frames, int64_t bins, doub
                                 int64_t *workgroups, int64_t *scratch_bytes);
 
 /* ---------------------------------------------------------------------------
+ * tfx_yin_forward -- YIN pitch detection (de Cheveigne & Kawahara, JASA 2002, steps 2 to 5) over every row of x [rows, T], in
+ * dtype.  frames = 1 + (T + 2 pad - frame_length) / hop; frame f starts at s = f hop - pad (samples outside the row are zeros,
+ * or one reflection for TFX_STFT_PAD_REFLECT, by addressing) and reads its first win_length + Lmax samples, Lmax = tau_max + 1:
+ *   1. d(tau) = sum_{j < win_length} (x[s + j] - x[s + j + tau])^2 for tau = 0 .. Lmax: squares only, nothing cancels.
+ *   2. S(tau) = sum_{k = 1 .. tau} d(k);  d'(0) = 1, d'(tau) = tau d(tau) / S(tau), and 1 where S(tau) = 0.
+ *   3. tau = the smallest lag in [tau_min, tau_max] with d' < threshold, advanced while tau < tau_max and d'(tau + 1) < d'(tau);
+ *      with none, the first arg-min of d' over [tau_min, tau_max].
+ *   4. a, b, c = d'(tau - 1), d'(tau), d'(tau + 1);  delta = 0.5 (a - c) / (a - 2 b + c) when a - 2 b + c > 0, b <= a and b <= c,
+ *      else 0;  f0 = fs / (tau + delta), aper = b.
+ *   5. A frame whose win_length + Lmax samples hold a NaN or an Inf stores NaN in f0, aper and its row of cmndf; every other
+ *      frame keeps its bits.
+ * x, f0 [rows, frames], aper [rows, frames] DEVICE; cmndf DEVICE [rows, frames, Lmax + 1] or NULL (then d' never leaves the
+ * chip).  One launch, no atomics, no scratch: a workgroup stages the span of its consecutive frames in LDS once, computes the
+ * partial difference function of each block of `block` samples once -- frames that overlap share them -- and finishes its frames
+ * (block sums, prefix sum over the lags, d', pick, parabola) in LDS and registers.  `block` 0 = the plan's choice
+ * (gcd(win_length, hop) when hop < win_length, that is at least 16 and the plan's cost model favours it, else win_length:
+ * nothing shared); win_length or that gcd force a route.  The choice reads win_length, hop, Lmax and dtype, never the number
+ * of frames, so a frame's bits depend on its own samples, win_length, hop, Lmax, threshold and fs alone.
+ * frame_length <= 8192 (TFX_F32) / 4096 (TFX_F64) and win_length + Lmax <= frame_length; arguments are checked before the
+ * device is touched; rows == 0 launches nothing.
+ * ------------------------------------------------------------------------- */
+int tfx_yin_forward(const void *x, void *f0, void *aper, void *cmndf, int dtype, int64_t rows, int64_t T, double fs,
+                    int64_t frame_length, int64_t win_length, int64_t hop, int64_t tau_min, int64_t tau_max, double threshold,
+                    int64_t pad, int pad_mode, int64_t block, tfx_stream_t stream);
+/* what tfx_yin_forward does (host-only, same checks on the sizes): the frames per row, the lags Lmax + 1, the block, the blocks
+ * of a frame (1: nothing shared), the frames of a workgroup, the neighbouring lags a thread keeps in registers, the bytes of
+ * LDS and the workgroups (rows * ceil(frames / frames_per_workgroup)). */
+int tfx_yin_plan_info(int64_t rows, int64_t T, int64_t frame_length, int64_t win_length, int64_t hop, int64_t tau_min,
+                      int64_t tau_max, int dtype, int64_t pad, int pad_mode, int64_t block, int64_t *frames, int64_t *lags,
+                      int64_t *block_out, int64_t *blocks_per_frame, int64_t *frames_per_workgroup, int64_t *lags_per_thread,
+                      int64_t *lds_bytes, int64_t *workgroups);
+
+/* ---------------------------------------------------------------------------
  * tfx_sum_forward -- y = sum_i xs[i]  (the accumulate of
  * ParallelFilterCombination.forward, src/torchfx/filter/__base.py:1019-1026).
  * xs_host: HOST array of n DEVICE pointers, each [numel] of dtype.

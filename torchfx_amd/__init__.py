@@ -16,6 +16,7 @@ from torchfx_amd.loudness import (block_energy, integrated_loudness, kweighting_
                                   short_term_loudness, true_peak, true_peak_linear)
 from torchfx_amd.modulation import modulated_delay
 from torchfx_amd.phaser import phase_shift
+from torchfx_amd.pitch import yin
 from torchfx_amd.resample import Resample, resample_poly
 from torchfx_amd.reverb import freeverb, freeverb_bank
 from torchfx_amd.spectral import (MelSpectrogram, PitchShift, TimeStretch, istft, mel_filterbank, mel_spectrogram, phase_vocoder, pitch_shift,
@@ -25,5 +26,5 @@ from torchfx_amd.waveshaper import waveshape
 
 __all__ = ["FX", "Chorus", "Compressor", "Delay", "Distortion", "FilterChain", "Flanger", "Freeverb", "Gain", "Gate", "Limiter", "LoudnessNormalize", "MelSpectrogram", "ModulatedDelay", "Normalize", "Phaser", "Resample", "Reverb", "Wave", "block_energy",
            "compress", "filter", "freeverb", "freeverb_bank", "gate", "integrated_loudness", "is_native_available", "istft", "kweighting_sos", "limit", "loudness_range", "mel_filterbank", "mel_spectrogram", "modulated_delay", "momentary_loudness",
-           "phase_shift", "phase_vocoder", "pitch_shift", "PitchShift", "resample_poly", "time_stretch", "TimeStretch", "short_term_loudness", "sosfiltfilt", "spectrogram", "stft", "true_peak", "true_peak_linear", "Vibrato", "Waveshaper", "waveshape"]
+           "phase_shift", "phase_vocoder", "pitch_shift", "PitchShift", "resample_poly", "time_stretch", "TimeStretch", "short_term_loudness", "sosfiltfilt", "spectrogram", "stft", "true_peak", "true_peak_linear", "Vibrato", "Waveshaper", "waveshape", "yin"]
 __version__ = "0.1.0"

@@ -925,6 +925,29 @@ int tfx_phase_vocoder_plan_info(int64_t rows, int64_t frames, int64_t bins, doub
     TFX_API_END
 }
 
+int tfx_yin_forward(const void *x, void *f0, void *aper, void *cmndf, int dtype, int64_t rows, int64_t T, double fs,
+                    int64_t frame_length, int64_t win_length, int64_t hop, int64_t tau_min, int64_t tau_max, double threshold,
+                    int64_t pad, int pad_mode, int64_t block, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    yin_forward(x, f0, aper, cmndf, dtype, rows, T, fs, frame_length, win_length, hop, tau_min, tau_max, threshold, pad, pad_mode, block,
+                (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_yin_plan_info(int64_t rows, int64_t T, int64_t frame_length, int64_t win_length, int64_t hop, int64_t tau_min,
+                      int64_t tau_max, int dtype, int64_t pad, int pad_mode, int64_t block, int64_t *frames, int64_t *lags,
+                      int64_t *block_out, int64_t *blocks_per_frame, int64_t *frames_per_workgroup, int64_t *lags_per_thread,
+                      int64_t *lds_bytes, int64_t *workgroups)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(frames && lags && block_out && blocks_per_frame && frames_per_workgroup && lags_per_thread && lds_bytes && workgroups,
+              "yin_plan_info: null output");
+    yin_plan_info(rows, T, frame_length, win_length, hop, tau_min, tau_max, dtype, pad, pad_mode, block, frames, lags, block_out,
+                  blocks_per_frame, frames_per_workgroup, lags_per_thread, lds_bytes, workgroups);
+    TFX_API_END
+}
+
 int tfx_sum_forward(const void *const *xs_host, int n, void *y, int dtype, int64_t numel, tfx_stream_t stream)
 {
     TFX_API_BEGIN

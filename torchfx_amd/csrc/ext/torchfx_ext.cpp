@@ -856,6 +856,58 @@ Tensor phase_vocoder_op(const Tensor &spec_in, double rate, int64_t segments)
     return out.transpose(-1, -2);
 }
 
+// YIN pitch detection (tfx_yin_forward): x [T], [C, T] or [B, C, T], float32 / float64; lags [tau_min, tau_max]; pad samples at
+// each end by pad_mode (0 constant, 1 reflect); block 0 = the plan's choice -> (f0 [..., frames], aperiodicity [..., frames],
+// cmndf [..., frames, tau_max + 2] or an empty tensor without return_cmndf).
+struct YinShape {
+    std::vector<int64_t> sizes;     // [..., frames]
+    int dt;
+    int64_t rows, T, lags;
+};
+
+YinShape yin_shape(const Tensor &x, int64_t frame_length, int64_t win_length, int64_t hop, int64_t tau_min, int64_t tau_max, int64_t pad,
+                   int64_t pad_mode, int64_t block, const char *what)
+{
+    TORCH_CHECK(x.dim() >= 1 && x.dim() <= 3, what, ": x must be [T], [C, T] or [B, C, T], got ", x.dim(), " dimensions");
+    YinShape s;
+    s.dt = dtype_code(x, what);
+    s.T = x.size(-1);
+    s.rows = stream_rows(x);
+    int64_t info[8];
+    check_rc(tfx_yin_plan_info(s.rows, s.T, frame_length, win_length, hop, tau_min, tau_max, s.dt, pad, (int)pad_mode, block, info, info + 1,
+                               info + 2, info + 3, info + 4, info + 5, info + 6, info + 7),
+             what);
+    s.lags = info[1];
+    s.sizes.assign(x.sizes().begin(), x.sizes().end() - 1);
+    s.sizes.push_back(info[0]);
+    return s;
+}
+
+std::vector<int64_t> yin_cmndf_sizes(const YinShape &s, bool return_cmndf)
+{
+    if (!return_cmndf) return {0};
+    std::vector<int64_t> sizes = s.sizes;
+    sizes.push_back(s.lags);
+    return sizes;
+}
+
+std::tuple<Tensor, Tensor, Tensor> yin_op(const Tensor &x_in, double fs, int64_t frame_length, int64_t win_length, int64_t hop,
+                                          int64_t tau_min, int64_t tau_max, double threshold, int64_t pad, int64_t pad_mode,
+                                          bool return_cmndf, int64_t block)
+{
+    const char *what = "yin_forward";
+    need_device(x_in, "x");
+    const YinShape s = yin_shape(x_in, frame_length, win_length, hop, tau_min, tau_max, pad, pad_mode, block, what);
+    const Tensor x = x_in.contiguous();
+    Tensor f0 = at::empty(s.sizes, x.options()), aper = at::empty(s.sizes, x.options());
+    Tensor cmndf = at::empty(yin_cmndf_sizes(s, return_cmndf), x.options());
+    c10::hip::HIPGuard guard(x.get_device());
+    check_rc(tfx_yin_forward(x.data_ptr(), f0.data_ptr(), aper.data_ptr(), return_cmndf ? cmndf.data_ptr() : nullptr, s.dt, s.rows, s.T, fs,
+                             frame_length, win_length, hop, tau_min, tau_max, threshold, pad, (int)pad_mode, block, stream_of(x)),
+             what);
+    return std::make_tuple(f0, aper, cmndf);
+}
+
 // Freeverb (tfx_freeverb_forward): x [T], [C, T] or [B, C, T] with C 1 or 2; comb_delays / allpass_delays the flattened
 // [C, NC] / [C, NA] tables in samples; state [B * C, state_len] float64 or None (silence) -> (y [..., T + tail], new state).
 // The shape and the tables are checked here and by the plan, before anything touches the device; the workspace (global lines,
@@ -1771,6 +1823,23 @@ TORCH_LIBRARY_IMPL(torchfx_vocoder, Meta, m)
     m.impl("phase_vocoder_forward", [](const Tensor &spec, double rate, int64_t segments) {
         const VocoderShape s = vocoder_shape(spec, rate, segments, "phase_vocoder_forward");
         return at::empty(s.sizes, spec.options()).transpose(-1, -2);
+    });
+}
+
+// Pitch detection in a namespace of its own: torch.ops.torchfx_pitch.
+TORCH_LIBRARY(torchfx_pitch, m)
+{
+    reg_op(m, "yin_forward(Tensor x, float fs, int frame_length, int win_length, int hop, int tau_min, int tau_max, float threshold, int pad, "
+              "int pad_mode, bool return_cmndf, int block=0) -> (Tensor, Tensor, Tensor)", yin_op);
+}
+
+TORCH_LIBRARY_IMPL(torchfx_pitch, Meta, m)
+{
+    m.impl("yin_forward", [](const Tensor &x, double, int64_t frame_length, int64_t win_length, int64_t hop, int64_t tau_min, int64_t tau_max,
+                             double, int64_t pad, int64_t pad_mode, bool return_cmndf, int64_t block) {
+        const YinShape s = yin_shape(x, frame_length, win_length, hop, tau_min, tau_max, pad, pad_mode, block, "yin_forward");
+        return std::make_tuple(at::empty(s.sizes, x.options()), at::empty(s.sizes, x.options()),
+                               at::empty(yin_cmndf_sizes(s, return_cmndf), x.options()));
     });
 }
 

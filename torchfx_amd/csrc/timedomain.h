@@ -1,5 +1,5 @@
 // timedomain.h -- the host entry points of the time-domain and elementwise ops, one prototype per exported function of fir.hip,
-// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip, compressor.hip, modulation.hip, reverb.hip, waveshaper.hip, phaser.hip, gate.hip, stft.hip, istft.hip, mel.hip, phasevocoder.hip and layout.hip (the cascade's: sos.h; the
+// effects.hip, select.hip, delay.hip, resample.hip, limiter.hip, compressor.hip, modulation.hip, reverb.hip, waveshaper.hip, phaser.hip, gate.hip, stft.hip, istft.hip, mel.hip, phasevocoder.hip, yin.hip and layout.hip (the cascade's: sos.h; the
 // overlap-save pipelines': ols_route.h).  Included by the file that defines each function and by capi.hip, so a prototype that drifts from
 // its definition does not compile; default arguments live here and nowhere else.  Every *_forward checks its arguments before
 // anything touches the device; a *_plan_info takes the same checking path without the pointers.
@@ -179,6 +179,14 @@ void phase_vocoder_forward(const void *spec, void *out, int dtype, int64_t rows,
 void phase_vocoder_plan_info(int64_t rows, int64_t frames, int64_t bins, double rate, int dtype, int64_t segments, int64_t *out_frames,
                              int64_t *bin_tile, int64_t *segments_out, int64_t *seg_frames, int64_t *launches, int64_t *workgroups,
                              int64_t *scratch_bytes);
+
+// ---- yin.hip ----
+void yin_forward(const void *x, void *f0, void *aper, void *cmndf, int dtype, int64_t rows, int64_t T, double fs, int64_t frame_length,
+                 int64_t win_length, int64_t hop, int64_t tau_min, int64_t tau_max, double threshold, int64_t pad, int pad_mode,
+                 int64_t block, hipStream_t stream);
+void yin_plan_info(int64_t rows, int64_t T, int64_t frame_length, int64_t win_length, int64_t hop, int64_t tau_min, int64_t tau_max,
+                   int dtype, int64_t pad, int pad_mode, int64_t block, int64_t *frames, int64_t *lags, int64_t *block_out,
+                   int64_t *blocks_per_frame, int64_t *frames_per_workgroup, int64_t *lags_per_thread, int64_t *lds_bytes, int64_t *workgroups);
 
 // ---- layout.hip ----
 void deinterleave_forward(const void *in, int in_kind, float *out, int64_t F, int64_t C, int64_t ld_out, int64_t f_base,

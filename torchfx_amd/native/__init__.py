@@ -145,6 +145,14 @@ def vocoder_ops():
     return torch.ops.torchfx_vocoder
 
 
+def pitch_ops():
+    """``torch.ops.torchfx_pitch`` (pitch detection's namespace, registered by the same module) with the library loaded."""
+    import torch
+
+    load()
+    return torch.ops.torchfx_pitch
+
+
 def spectral_inverse_ops():
     """``torch.ops.torchfx_spectral_inverse`` (the inverse short-time Fourier transform's namespace, registered by the same module) with the library loaded."""
     import torch

@@ -22,6 +22,7 @@ Differences a caller can observe, all deliberate:
 from __future__ import annotations
 
 import ctypes
+import math
 import weakref
 
 import numpy as np
@@ -40,7 +41,7 @@ __all__ = [
     "modulated_delay_forward", "modulated_delay_stream_forward", "modulated_delay_plan_info", "freeverb_forward", "freeverb_plan_info",
     "waveshaper_stream_forward", "waveshaper_stream_plan_info", "phaser_forward", "phaser_plan_info", "gate_forward", "gate_plan_info",
     "stft_forward", "stft_plan_info", "istft_forward", "istft_plan_info", "mel_forward", "mel_plan_info", "mel_band_table",
-    "phase_vocoder_forward", "phase_vocoder_plan_info",
+    "phase_vocoder_forward", "phase_vocoder_plan_info", "yin_forward", "yin_plan_info", "yin_lags",
     "fir_direct_forward", "fft_conv_forward", "sos_fft_conv_forward", "sos_fft_conv_supported", "sos_fft_conv_warmup", "sos_fft_conv_plan_info", "workspace_bytes", "clear_caches", "env_reload", "fir_stream_forward", "chunk_forward", "chunk_supported", "normalize_apply", "Epilogue", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
     "effects_plan_info", "deinterleave_forward", "interleave_forward", "sos_plan_info", "sos_route_info", "ols_plan_info", "prewarm",
 ]
@@ -728,6 +729,44 @@ def phase_vocoder_plan_info(frames: int, bins: int, rate: float, rows: int = 1, 
     dtype = {torch.complex64: torch.float32, torch.complex128: torch.float64}.get(dtype, dtype)
     return _query(L.load().tfx_phase_vocoder_plan_info, (int(rows), int(frames), int(bins), float(rate), _dt(dtype), int(segments)),
                   "out_frames bin_tile segments seg_frames launches workgroups scratch_bytes")
+
+
+def yin_lags(fs: float, fmin: float, fmax: float) -> tuple[int, int]:
+    """The lag range of a pitch search: ``tau_min = max(1, floor(fs / fmax))``, ``tau_max = ceil(fs / fmin)``."""
+    return max(1, int(math.floor(fs / fmax))), int(math.ceil(fs / fmin))
+
+
+def yin_forward(x: Tensor, fs: float, frame_length: int, win_length: int, hop: int, tau_min: int, tau_max: int, threshold: float = 0.1,
+                pad: int = 0, pad_mode: str = "constant", return_cmndf: bool = False, block: int = 0) -> tuple[Tensor, Tensor, Tensor]:
+    """YIN pitch detection (``tfx_yin_forward``; the definition is :func:`torchfx_amd.pitch.yin`'s): ``x [T]``, ``[C, T]`` or
+    ``[B, C, T]`` on the device (float32 / float64), the lags ``[tau_min, tau_max]`` (:func:`yin_lags`), ``pad`` samples added at
+    each end (``frame_length // 2`` for ``center=True``) by ``pad_mode`` ("constant" / "reflect").  Returns ``(f0, aperiodicity,
+    cmndf)``: ``[..., frames]`` twice and ``[..., frames, tau_max + 2]``, empty without ``return_cmndf`` (the difference function
+    then never leaves the chip).  ``block`` 0 is the plan's choice (:func:`yin_plan_info`), ``win_length`` forces the route that
+    shares nothing.  The op lives in ``torch.ops.torchfx_pitch``."""
+    native.ops()                                         # loads the library: every namespace is registered by the one module
+    if pad_mode not in ("constant", "reflect"):
+        raise ValueError(f"yin_forward: pad_mode must be 'constant' or 'reflect', got {pad_mode!r}")
+    return native.pitch_ops().yin_forward(x, float(fs), int(frame_length), int(win_length), int(hop), int(tau_min), int(tau_max),
+                                          float(threshold), int(pad), STFT_PAD_MODES[pad_mode], bool(return_cmndf), int(block))
+
+
+def yin_plan_info(length: int, fs: float, fmin: float = 65.0, fmax: float = 2093.0, frame_length: int = 2048, win_length: int | None = None,
+                  hop_length: int | None = None, rows: int = 1, dtype: torch.dtype = torch.float32, center: bool = True,
+                  pad_mode: str = "constant", block: int = 0) -> dict:
+    """What :func:`yin_forward` does for ``rows`` signals of ``length`` samples (``tfx_yin_plan_info``; host-only, same checks on
+    the sizes): ``tau_min``, ``tau_max``, ``frames`` per row, ``lags`` (``tau_max + 2``: the lags 0 ... ``tau_max + 1`` of the
+    difference function), ``block`` (the samples whose partial sums overlapping frames share; ``win_length``: nothing shared),
+    ``blocks_per_frame``, ``frames_per_workgroup``, ``lags_per_thread``, ``lds_bytes`` and ``workgroups``."""
+    if pad_mode not in ("constant", "reflect"):
+        raise ValueError(f"yin_plan_info: pad_mode must be 'constant' or 'reflect', got {pad_mode!r}")
+    wl = int(win_length) if win_length is not None else int(frame_length) // 2
+    hop = int(hop_length) if hop_length is not None else int(frame_length) // 4
+    tau_min, tau_max = yin_lags(fs, fmin, fmax)
+    info = _query(L.load().tfx_yin_plan_info, (int(rows), int(length), int(frame_length), wl, hop, tau_min, tau_max, _dt(dtype),
+                                               int(frame_length) // 2 if center else 0, STFT_PAD_MODES[pad_mode], int(block)),
+                  "frames lags block blocks_per_frame frames_per_workgroup lags_per_thread lds_bytes workgroups")
+    return dict(tau_min=tau_min, tau_max=tau_max, **info)
 
 
 RESAMPLE_STREAM_KERNELS = ("resample_stream_reg_kernel", "resample_stream_lds_kernel", "resample_stream_gather_kernel", "copy")

@@ -781,6 +781,14 @@ class Wave:
 
         return mel_spectrogram(self.ys, self.fs, n_fft, hop_length, win_length, window, n_mels, **kwargs)
 
+    def pitch(self, **kwargs):
+        """Fundamental frequency of the (materialised) signal at its own rate by YIN, ``[channels, frames]`` in Hz
+        (:func:`torchfx_amd.pitch.yin`, which takes the keywords and, with ``return_aperiodicity`` / ``return_cmndf``, returns a
+        tuple).  An analysis, not an effect: the result is a tensor, not a ``Wave``."""
+        from torchfx_amd.pitch import yin
+
+        return yin(self.ys, self.fs, **kwargs)
+
     @classmethod
     def from_stft(cls, spec: Tensor, fs: int, n_fft: int, hop_length: int | None = None, win_length: int | None = None, window=None,
                   center: bool = True, normalized: bool = False, onesided: bool | None = None, length: int | None = None) -> "Wave":
