@@ -90,18 +90,33 @@ TORCH_OPS = {
     "limiter_stream_forward", "resample_stream_forward", "delay_forward_ep", "delay_stream_forward", "delay_line_stream_forward",
     "fir_direct_forward", "fft_conv_forward", "fir_stream_forward", "chunk_forward", "sos_forward_ep", "fft_conv_forward_ep",
     "sos_fft_conv_forward", "normalize_apply", "sum_forward", "gain_forward", "quantile_abs", "stat_forward", "normalize_forward",
-    "deinterleave_forward", "deinterleave_into", "interleave_forward",
+    "deinterleave_forward", "deinterleave_into", "interleave_forward", "compressor_forward", "modulated_delay_forward",
+    "modulated_delay_stream_forward", "freeverb_forward", "phaser_forward", "gate_forward", "stft_forward", "istft_forward",
+    "phase_vocoder_forward", "yin_forward", "mel_forward", "waveshaper_forward", "waveshaper_stream_forward",
+}
+
+# the ops with shape inference (a kernel for the Meta key); the others have none and must not gain one unnoticed
+META_OPS = {
+    "sos_forward", "sos_forward_sections", "sos_bank_forward", "sos_bank_sum_forward", "biquad_forward", "delay_forward",
+    "resample_forward", "sos_filtfilt", "sos_block_energy", "true_peak", "resample_stream_forward", "delay_forward_ep",
+    "delay_stream_forward", "delay_line_stream_forward", "fir_direct_forward", "fft_conv_forward", "fir_stream_forward",
+    "gain_forward", "normalize_forward", "compressor_forward", "modulated_delay_forward", "modulated_delay_stream_forward",
+    "freeverb_forward", "phaser_forward", "gate_forward", "stft_forward", "istft_forward", "phase_vocoder_forward", "yin_forward",
+    "mel_forward", "waveshaper_forward", "waveshaper_stream_forward",
 }
 
 
 def test_every_op_of_the_namespace_has_a_device_kernel_and_a_cpu_refusal():
-    """The 33 ops of ``torchfx_hip`` and nothing else; each one is registered for the CUDA key (its kernel) and for the CPU key
-    (the "no CPU path" error), so no op can be defined without either."""
+    """The 46 ops of ``torchfx_hip`` and nothing else, in no other ``torchfx_*`` namespace either; each one is registered for the
+    CUDA key (its kernel) and for the CPU key (the "no CPU path" error), so no op can be defined without either, and exactly the
+    32 of ``META_OPS`` for the Meta key."""
     import torch
     import torchfx_amd.ops  # noqa: F401
-    names = {s.name for s in torch._C._jit_get_all_schemas() if s.name.startswith("torchfx_hip::")}
-    assert len(TORCH_OPS) == 33
+    names = {s.name for s in torch._C._jit_get_all_schemas() if s.name.startswith("torchfx_")}
+    assert len(TORCH_OPS) == 46
     assert names == {"torchfx_hip::" + n for n in TORCH_OPS}
+    assert len(META_OPS) == 32 and META_OPS <= TORCH_OPS
+    assert {n for n in names if torch._C._dispatch_has_kernel_for_dispatch_key(n, "Meta")} == {"torchfx_hip::" + n for n in META_OPS}
     for name in sorted(names):
         assert torch._C._dispatch_has_kernel_for_dispatch_key(name, "CUDA"), name
         assert torch._C._dispatch_has_kernel_for_dispatch_key(name, "CPU"), name

@@ -158,7 +158,7 @@ def test_geometries_off_the_route_say_torch_and_bad_sizes_are_errors():
 def test_meta_op_has_the_result_shapes_dtypes_and_the_flag():
     from torchfx_amd import native
     native.load()
-    op = torch.ops.torchfx_spectral_inverse.istft_forward
+    op = torch.ops.torchfx_hip.istft_forward
     for lead in ((), (3,), (2, 3)):
         for cdt, dt in ((torch.complex64, torch.float32), (torch.complex128, torch.float64)):
             X = torch.empty(lead + (513, 20), dtype=cdt, device="meta")
@@ -183,10 +183,10 @@ def test_the_namespace_holds_the_one_op_with_a_device_kernel_and_a_cpu_refusal()
     import torchfx_amd
     from torchfx_amd import native
     native.load()
-    names = {s.name for s in torch._C._jit_get_all_schemas() if s.name.startswith("torchfx_spectral_inverse::")}
-    assert names == {"torchfx_spectral_inverse::istft_forward"}
-    assert native.spectral_inverse_ops() is torch.ops.torchfx_spectral_inverse
-    assert torch._C._dispatch_has_kernel_for_dispatch_key("torchfx_spectral_inverse::istft_forward", "CUDA")
+    # tests/test_capi_exports.py pins the exact contents of torchfx_hip; here: the op is in it
+    assert "torchfx_hip::istft_forward" in {s.name for s in torch._C._jit_get_all_schemas()}
+    assert native.ops() is torch.ops.torchfx_hip
+    assert torch._C._dispatch_has_kernel_for_dispatch_key("torchfx_hip::istft_forward", "CUDA")
     with pytest.raises(RuntimeError, match="no CPU path"):
         ext().istft_forward(X3, None, 256, 64, 128)
     assert {"istft_forward", "istft_plan_info"} <= set(ext().__all__) and "istft" in torchfx_amd.__all__ and "istft" in sp().__all__

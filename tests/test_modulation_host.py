@@ -1,6 +1,6 @@
 """The modulated delay line without a device: the NumPy host path of torchfx_amd.modulation.modulated_delay against the
 per-sample loop of tests/modulation_reference.py within the derived bound, the exact cases of the definition, argument errors,
-the plan query and the C ABI's refusals, Chorus / Flanger / Vibrato in a Wave, the planner, the torchfx_modulation namespace and
+the plan query and the C ABI's refusals, Chorus / Flanger / Vibrato in a Wave, the planner, the dispatcher ops and
 the stateful classes over CPU chunks."""
 import ctypes
 import math
@@ -232,13 +232,14 @@ def test_c_abi_refuses_bad_arguments_before_the_device():
 
 
 def test_modulation_namespace_census():
-    """Exactly the two ops of ``torchfx_modulation``, each with a device kernel, the CPU refusal and shape inference."""
+    """The two modulation ops are in ``torchfx_hip`` (tests/test_capi_exports.py pins the namespace's exact contents), each with a
+    device kernel, the CPU refusal and shape inference."""
     from torchfx_amd import native
     from torchfx_amd import torchfx_ext as E
 
-    ns = native.modulation_ops()
-    names = {s.name for s in torch._C._jit_get_all_schemas() if s.name.startswith("torchfx_modulation::")}
-    assert names == {"torchfx_modulation::modulated_delay_forward", "torchfx_modulation::modulated_delay_stream_forward"}
+    ns = native.ops()
+    names = {"torchfx_hip::modulated_delay_forward", "torchfx_hip::modulated_delay_stream_forward"}
+    assert names <= {s.name for s in torch._C._jit_get_all_schemas()}
     for name in names:
         assert torch._C._dispatch_has_kernel_for_dispatch_key(name, "CUDA"), name
         assert torch._C._dispatch_has_kernel_for_dispatch_key(name, "CPU"), name

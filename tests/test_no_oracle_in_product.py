@@ -42,14 +42,23 @@ def test_no_cpu_fallback_branches():
     for fn in ops:
         assert "native.ops()" in ast.unparse(fn), fn.name
     cpp = open(os.path.join(ROOT, "torchfx_amd", "csrc", "ext", "torchfx_ext.cpp")).read()
-    # one reg_op line per op: its schema and the function registered for the CUDA key (the CPU key gets the refusal)
-    ops_block = cpp[cpp.index("TORCH_LIBRARY(torchfx_hip, m)"):cpp.index("TORCH_LIBRARY_IMPL(torchfx_hip, Meta, m)")]
-    impls = re.findall(r'reg_op\(m,\s*"(\w+)\(.*?,\s*(\w+)\);', ops_block, re.S)
-    assert len(impls) == ops_block.count("reg_op(") == 33 and "m.impl(" not in ops_block and "m.def(" not in ops_block
-    for name, fn in impls:
+    # one reg_op call per op in the one library block: its schema (adjacent string literals), then the function registered for
+    # the CUDA key (the CPU key gets the refusal; a Meta kernel may follow as the last argument)
+    assert cpp.count("\nTORCH_LIBRARY(") == 1 and "TORCH_LIBRARY_IMPL" not in cpp
+    ops_block = cpp[cpp.index("TORCH_LIBRARY(torchfx_hip, m)"):cpp.index("PYBIND11_MODULE(")]
+    impls = re.findall(r'reg_op\(m,\s*"(\w+)\([^"]*"(?:\s*"[^"]*")*\s*,\s*(\w+)\s*[,)]', ops_block)
+    assert len(impls) == ops_block.count("reg_op(") == 46 and "m.impl(" not in ops_block and "m.def(" not in ops_block
+    assert len({name for name, _ in impls}) == 46 and all(fn.endswith("_op") for _, fn in impls)
+    def body_of(fn):
         body = cpp[cpp.index(" " + fn + "("):]
-        body = body[:body.index("\n}\n")]
-        assert "need_device(" in body or "_impl(" in body or "deinterleave_into_op(" in body, (name, fn)
+        return body[:body.index("\n}\n")]
+
+    # the check is in the op's own function or in the helper (`*_impl`, `*_inputs`) it hands its tensors to first
+    for name, fn in impls:
+        body = body_of(fn)
+        helpers = re.findall(r"\b(\w+_(?:impl|inputs))\(", body)
+        assert ("need_device(" in body or any("need_device(" in body_of(h) for h in helpers)
+                or "deinterleave_into_op(" in body), (name, fn)
     assert cpp.count("need_device(") >= 12
 
 

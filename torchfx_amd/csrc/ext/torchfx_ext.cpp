@@ -3,17 +3,18 @@
 // The reference binds its native kernels through a pybind11 torch extension named `torchfx_ext`
 // (src/torchfx/_csrc/binding.cpp:83-96, imported as `from torchfx import torchfx_ext`).  This file is
 // that module for MI355X: the same three entry points with the same signatures on at::Tensor
-// (biquad_forward, sos_forward, delay_line_forward), launched on PyTorch's current HIP stream, plus a
-// TORCH_LIBRARY(torchfx_hip) registration of every op of the backend so that Python reaches the kernels
-// through the dispatcher (torch.ops.torchfx_hip.*) -- no ctypes on the tensor path.  It is a thin,
-// host-only translation unit (compiled with g++): tensors are checked, outputs allocated, and the
-// extern "C" ABI of libtorchfx_hip.so (include/torchfx_hip.h) is called -- the C ABI stays the one
-// boundary non-torch hosts and this module share.
+// (biquad_forward, sos_forward, delay_line_forward), launched on PyTorch's current HIP stream, plus the
+// one TORCH_LIBRARY(torchfx_hip) block near the bottom, which registers every op of the backend so that
+// Python reaches the kernels through the dispatcher (torch.ops.torchfx_hip.*) -- no ctypes on the tensor
+// path.  It is a thin, host-only translation unit (compiled with g++): tensors are checked, outputs
+// allocated, and the extern "C" ABI of libtorchfx_hip.so (include/torchfx_hip.h) is called -- the C ABI
+// stays the one boundary non-torch hosts and this module share.
 //
 // Host tensors: the reference's module dispatches on x.is_cuda() (binding.cpp:30-81), so the three pybind entry points
 // at the bottom do too -- their host branch is host_branch.h (this module's own Direct Form I loop).  Everything else is
-// device-only: the dispatcher ops are registered for the CUDA key (= ROCm device tensors in a ROCm build of PyTorch) and
-// for Meta (shape inference), and a CPU tensor gets an explicit error there.
+// device-only.  Each op is one reg_op call in that block: its schema, its kernel for the CUDA key (= ROCm device tensors in
+// a ROCm build of PyTorch), the explicit error a CPU tensor gets and, as the call's last argument where the op has one, its
+// Meta kernel (shape inference).  There is no other namespace and no separate block of Meta kernels.
 #include <torch/extension.h>
 #include <torch/library.h>
 
@@ -1628,14 +1629,22 @@ void no_cpu_boxed(const c10::OperatorHandle &op, c10::DispatchKeySet, torch::jit
                 ": tensors must live on a ROCm device; this backend has no CPU path -- move them with .to('cuda').");
 }
 
-// One line per op: its schema, `fn` for the CUDA key ("CUDA" is the dispatch key of ROCm device tensors) and the refusal above
-// for the CPU key.  The op's name is the schema up to its "(".
-template <typename F> void reg_op(torch::Library &m, const char *schema, F *fn)
+// One call per op.  Three arguments: its schema, `fn` for the CUDA key ("CUDA" is the dispatch key of ROCm device tensors) and
+// the refusal above for the CPU key -- an op registered this way has no shape inference.  A fourth argument is its Meta kernel
+// (shape inference), a function or a lambda.  The op's name, which the three-argument form returns, is the schema up to its "(".
+template <typename F> std::string reg_op(torch::Library &m, const char *schema, F *fn)
 {
     const std::string s(schema), name = s.substr(0, s.find('('));
     m.def(schema);
     m.impl(name.c_str(), torch::dispatch(c10::DispatchKey::CUDA, fn));
     m.impl(name.c_str(), torch::dispatch(c10::DispatchKey::CPU, torch::CppFunction::makeFromBoxedFunction<&no_cpu_boxed>()));
+    return name;
+}
+
+template <typename F, typename M> void reg_op(torch::Library &m, const char *schema, F *fn, M meta)
+{
+    const std::string name = reg_op(m, schema, fn);
+    m.impl(name.c_str(), torch::dispatch(c10::DispatchKey::Meta, std::move(meta)));
 }
 
 }  // namespace
@@ -1643,36 +1652,45 @@ template <typename F> void reg_op(torch::Library &m, const char *schema, F *fn)
 TORCH_LIBRARY(torchfx_hip, m)
 {
     reg_op(m, "sos_forward(Tensor x, Tensor sos_cpu, Tensor? state_x=None, Tensor? state_y=None, *, ScalarType? out_dtype=None, "
-              "int precision=-1) -> (Tensor, Tensor, Tensor)", sos_op);
+              "int precision=-1) -> (Tensor, Tensor, Tensor)", sos_op, sos_meta);
     reg_op(m, "sos_forward_sections(Tensor x, Tensor sos_cpu, Tensor? state_x=None, Tensor? state_y=None, *, ScalarType? out_dtype=None, "
-              "int precision=-1) -> (Tensor, Tensor, Tensor, Tensor)", sos_sections_op);
+              "int precision=-1) -> (Tensor, Tensor, Tensor, Tensor)", sos_sections_op, sos_sections_meta);
     reg_op(m, "sos_bank_forward(Tensor x, Tensor sos_banks_cpu, Tensor? state_x=None, Tensor? state_y=None, *, ScalarType? out_dtype=None, "
-              "int precision=-1) -> (Tensor, Tensor, Tensor)", bank_op);
+              "int precision=-1) -> (Tensor, Tensor, Tensor)", bank_op, bank_meta);
     reg_op(m, "sos_bank_sum_forward(Tensor x, Tensor sos_banks_cpu, Tensor? state_x=None, Tensor? state_y=None, *, int precision=-1) "
-              "-> (Tensor, Tensor, Tensor)", bank_sum_op);
+              "-> (Tensor, Tensor, Tensor)", bank_sum_op, bank_sum_meta);
     reg_op(m, "biquad_forward(Tensor x, Tensor b, float a1, float a2, Tensor? state_x=None, Tensor? state_y=None, *, "
-              "ScalarType? out_dtype=None, int precision=-1) -> (Tensor, Tensor, Tensor)", biquad_op);
+              "ScalarType? out_dtype=None, int precision=-1) -> (Tensor, Tensor, Tensor)", biquad_op, biquad_meta);
     reg_op(m, "delay_line_forward(Tensor(a) x, int delay_samples, float decay, float mix) -> Tensor(a)", delay_line_op);
-    reg_op(m, "delay_forward(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong) -> Tensor", delay_op);
-    reg_op(m, "resample_forward(Tensor x, int up, int down, Tensor h) -> Tensor", resample_op);
-    reg_op(m, "sos_filtfilt(Tensor x, Tensor sos_cpu, int padtype=0, int padlen=-1) -> Tensor", sos_filtfilt_op);
-    reg_op(m, "sos_block_energy(Tensor x, Tensor sos_cpu, int num, int den=1) -> Tensor", sos_block_energy_op);
-    reg_op(m, "true_peak(Tensor x, Tensor taps_cpu, int up) -> Tensor", true_peak_op);
+    reg_op(m, "delay_forward(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong) -> Tensor", delay_op, delay_meta);
+    reg_op(m, "resample_forward(Tensor x, int up, int down, Tensor h) -> Tensor", resample_op, resample_meta);
+    reg_op(m, "sos_filtfilt(Tensor x, Tensor sos_cpu, int padtype=0, int padlen=-1) -> Tensor", sos_filtfilt_op,
+           [](const Tensor &x, const Tensor &, int64_t, int64_t) { return at::empty_like(x); });
+    reg_op(m, "sos_block_energy(Tensor x, Tensor sos_cpu, int num, int den=1) -> Tensor", sos_block_energy_op,
+           [](const Tensor &x, const Tensor &sos, int64_t num, int64_t den) {
+               return at::empty(sos_block_energy_shape(x, sos, num, den), x.options().dtype(at::kDouble));
+           });
+    reg_op(m, "true_peak(Tensor x, Tensor taps_cpu, int up) -> Tensor", true_peak_op,
+           [](const Tensor &x, const Tensor &, int64_t) { return at::empty(true_peak_shape(x), x.options()); });
     reg_op(m, "limiter_forward(Tensor x, float c, int A, int H, Tensor window_cpu, int up, Tensor? taps_cpu, int channels, "
               "bool return_gain) -> (Tensor, Tensor)", limiter_op);
     reg_op(m, "limiter_stream_forward(Tensor x, Tensor? hist, int consumed, float c, int A, int H, Tensor window_cpu, int up, "
               "Tensor? taps_cpu, int channels, bool return_gain, int n_in=-1) -> (Tensor, Tensor, Tensor)", limiter_stream_op);
     reg_op(m, "resample_stream_forward(Tensor x, Tensor h, Tensor? hist, int up, int down, int consumed) -> (Tensor, Tensor)",
-           resample_stream_op);
+           resample_stream_op, resample_stream_meta);
     reg_op(m, "delay_forward_ep(Tensor x, int delay_samples, float[] amps, float mix, bool pingpong, float gain, bool clamp, int stat_mode, "
-              "bool per_row) -> (Tensor, Tensor)", delay_ep_op);
+              "bool per_row) -> (Tensor, Tensor)", delay_ep_op, delay_ep_meta);
     reg_op(m, "delay_stream_forward(Tensor x, Tensor? hist, int delay_samples, float[] amps, float mix, bool pingpong) -> (Tensor, Tensor)",
-           delay_stream_op);
+           delay_stream_op, delay_stream_meta);
     reg_op(m, "delay_line_stream_forward(Tensor x, Tensor? hist, int delay_samples, float decay, float mix) -> (Tensor, Tensor)",
-           delay_line_stream_op);
-    reg_op(m, "fir_direct_forward(Tensor x, Tensor kernel) -> Tensor", fir_direct_op);
-    reg_op(m, "fft_conv_forward(Tensor x, Tensor kernel, int pad_left, int pad_right) -> Tensor", fft_conv_op);
-    reg_op(m, "fir_stream_forward(Tensor x, Tensor kernel, Tensor? hist, bool direct) -> (Tensor, Tensor)", fir_stream_op);
+           delay_line_stream_op, delay_line_stream_meta);
+    reg_op(m, "fir_direct_forward(Tensor x, Tensor kernel) -> Tensor", fir_direct_op,
+           [](const Tensor &x, const Tensor &) { return at::empty_like(x); });
+    reg_op(m, "fft_conv_forward(Tensor x, Tensor kernel, int pad_left, int pad_right) -> Tensor", fft_conv_op, fft_conv_meta);
+    reg_op(m, "fir_stream_forward(Tensor x, Tensor kernel, Tensor? hist, bool direct) -> (Tensor, Tensor)", fir_stream_op,
+           [](const Tensor &x, const Tensor &kernel, const OptTensor &, bool) {
+               return std::make_tuple(at::empty_like(x), at::empty({x.size(0), kernel.numel() - 1}, x.options()));
+           });
     reg_op(m, "chunk_forward(Tensor x, Tensor sos_cpu, Tensor? state_x, Tensor? state_y, Tensor kernel, Tensor? hist, float gain, "
               "bool scale, bool clamp, int precision=-1) -> (Tensor, Tensor, Tensor, Tensor)", chunk_op);
     reg_op(m, "sos_forward_ep(Tensor x, Tensor sos_cpu, Tensor? state_x, Tensor? state_y, float gain, bool clamp, int stat_mode, "
@@ -1684,214 +1702,72 @@ TORCH_LIBRARY(torchfx_hip, m)
            sos_fft_conv_op);
     reg_op(m, "normalize_apply(Tensor x, Tensor stat, float peak, int mode, bool per_row) -> Tensor", normalize_apply_op);
     reg_op(m, "sum_forward(Tensor[] tensors) -> Tensor", sum_op);
-    reg_op(m, "gain_forward(Tensor x, float gain, bool clamp) -> Tensor", gain_op);
+    reg_op(m, "gain_forward(Tensor x, float gain, bool clamp) -> Tensor", gain_op,
+           [](const Tensor &x, double, bool) { return at::empty_like(x); });
     reg_op(m, "quantile_abs(Tensor x, float q) -> Tensor", quantile_abs_op);
     reg_op(m, "stat_forward(Tensor x, int mode, bool per_row) -> Tensor", stat_op);
-    reg_op(m, "normalize_forward(Tensor x, float peak, int mode, bool per_row) -> Tensor", normalize_op);
+    reg_op(m, "normalize_forward(Tensor x, float peak, int mode, bool per_row) -> Tensor", normalize_op,
+           [](const Tensor &x, double, int64_t, bool) { return at::empty_like(x); });
     reg_op(m, "deinterleave_forward(Tensor frames, float scale=3.0517578125e-05) -> Tensor", deinterleave_op);
     reg_op(m, "deinterleave_into(Tensor frames, Tensor(a!) out, int frame_base=0, float scale=3.0517578125e-05) -> ()", deinterleave_into_op);
     reg_op(m, "interleave_forward(Tensor x, int frame_base=0, int frames=-1) -> Tensor", interleave_op);
-}
-
-TORCH_LIBRARY_IMPL(torchfx_hip, Meta, m)
-{
-    m.impl("sos_forward", sos_meta);
-    m.impl("sos_forward_sections", sos_sections_meta);
-    m.impl("sos_bank_forward", bank_meta);
-    m.impl("sos_bank_sum_forward", bank_sum_meta);
-    m.impl("biquad_forward", biquad_meta);
-    m.impl("fir_direct_forward", [](const Tensor &x, const Tensor &) { return at::empty_like(x); });
-    m.impl("fft_conv_forward", fft_conv_meta);
-    m.impl("delay_forward", delay_meta);
-    m.impl("resample_forward", resample_meta);
-    m.impl("sos_filtfilt", [](const Tensor &x, const Tensor &, int64_t, int64_t) { return at::empty_like(x); });
-    m.impl("sos_block_energy", [](const Tensor &x, const Tensor &sos, int64_t num, int64_t den) {
-        return at::empty(sos_block_energy_shape(x, sos, num, den), x.options().dtype(at::kDouble));
-    });
-    m.impl("true_peak", [](const Tensor &x, const Tensor &, int64_t) { return at::empty(true_peak_shape(x), x.options()); });
-    m.impl("resample_stream_forward", resample_stream_meta);
-    m.impl("delay_forward_ep", delay_ep_meta);
-    m.impl("delay_stream_forward", delay_stream_meta);
-    m.impl("delay_line_stream_forward", delay_line_stream_meta);
-    m.impl("fir_stream_forward", [](const Tensor &x, const Tensor &kernel, const OptTensor &, bool) {
-        return std::make_tuple(at::empty_like(x), at::empty({x.size(0), kernel.numel() - 1}, x.options()));
-    });
-    m.impl("gain_forward", [](const Tensor &x, double, bool) { return at::empty_like(x); });
-    m.impl("normalize_forward", [](const Tensor &x, double, int64_t, bool) { return at::empty_like(x); });
-}
-
-// The dynamics processors live in a namespace of their own (torch.ops.torchfx_dynamics), registered the same way: the device
-// kernel for the CUDA key, the "no CPU path" refusal for the CPU key, shape inference for Meta.
-TORCH_LIBRARY(torchfx_dynamics, m)
-{
     reg_op(m, "compressor_forward(Tensor x, float th, float s, float w, float alpha_a, float alpha_r, float makeup_db, int channels, "
-              "Tensor? state, bool return_gain, int segments=0) -> (Tensor, Tensor, Tensor)", compressor_op);
-}
-
-TORCH_LIBRARY_IMPL(torchfx_dynamics, Meta, m)
-{
-    m.impl("compressor_forward", compressor_meta);
-}
-
-// The modulation effects (Chorus, Flanger, Vibrato) likewise: torch.ops.torchfx_modulation.
-TORCH_LIBRARY(torchfx_modulation, m)
-{
+              "Tensor? state, bool return_gain, int segments=0) -> (Tensor, Tensor, Tensor)", compressor_op, compressor_meta);
     reg_op(m, "modulated_delay_forward(Tensor x, Tensor voices_cpu, float spread, float dry, int shape, int interp, int position=0) "
-              "-> Tensor", modulated_delay_op);
+              "-> Tensor", modulated_delay_op,
+           [](const Tensor &x, const Tensor &, double, double, int64_t, int64_t, int64_t) { return at::empty_like(x); });
     reg_op(m, "modulated_delay_stream_forward(Tensor x, Tensor? hist, Tensor? pos, Tensor voices_cpu, float spread, float dry, "
-              "int shape, int interp) -> (Tensor, Tensor, Tensor)", modulated_delay_stream_op);
-}
-
-TORCH_LIBRARY_IMPL(torchfx_modulation, Meta, m)
-{
-    m.impl("modulated_delay_forward", [](const Tensor &x, const Tensor &, double, double, int64_t, int64_t, int64_t) {
-        return at::empty_like(x);
-    });
-    m.impl("modulated_delay_stream_forward", modulated_delay_stream_meta);
-}
-
-// Freeverb likewise: torch.ops.torchfx_reverb.
-TORCH_LIBRARY(torchfx_reverb, m)
-{
+              "int shape, int interp) -> (Tensor, Tensor, Tensor)", modulated_delay_stream_op, modulated_delay_stream_meta);
     reg_op(m, "freeverb_forward(Tensor x, int[] comb_delays, int[] allpass_delays, float feedback, float damp, float allpass_gain, "
               "float input_gain, float dry_gain, float wet1, float wet2, int tail=0, Tensor? state=None) -> (Tensor, Tensor)",
-           freeverb_op);
-}
-
-TORCH_LIBRARY_IMPL(torchfx_reverb, Meta, m)
-{
-    m.impl("freeverb_forward", freeverb_meta);
-}
-
-// The phaser likewise: torch.ops.torchfx_phaser.
-TORCH_LIBRARY(torchfx_phaser, m)
-{
+           freeverb_op, freeverb_meta);
     reg_op(m, "phaser_forward(Tensor x, int stages, float fs, float rate, float min_freq, float max_freq, float phase, float spread, "
               "float dry, float wet, int shape, int position=0, Tensor? pos=None, Tensor? state=None, bool return_coef=False, "
-              "int segments=0) -> (Tensor, Tensor, Tensor, Tensor)", phaser_op);
-}
-
-TORCH_LIBRARY_IMPL(torchfx_phaser, Meta, m)
-{
-    m.impl("phaser_forward", phaser_meta);
-}
-
-// The gate likewise: torch.ops.torchfx_gate.
-TORCH_LIBRARY(torchfx_gate, m)
-{
+              "int segments=0) -> (Tensor, Tensor, Tensor, Tensor)", phaser_op, phaser_meta);
     reg_op(m, "gate_forward(Tensor x, float p_open, float p_close, float range, int hold, float alpha_a, float alpha_r, int channels, "
-              "Tensor? state, bool return_gain, bool return_open, int segments=0) -> (Tensor, Tensor, Tensor, Tensor)", gate_op);
-}
-
-TORCH_LIBRARY_IMPL(torchfx_gate, Meta, m)
-{
-    m.impl("gate_forward", gate_meta);
-}
-
-// The short-time Fourier transform likewise: torch.ops.torchfx_spectral.
-TORCH_LIBRARY(torchfx_spectral, m)
-{
+              "Tensor? state, bool return_gain, bool return_open, int segments=0) -> (Tensor, Tensor, Tensor, Tensor)", gate_op, gate_meta);
     reg_op(m, "stft_forward(Tensor x, Tensor? window, int n_fft, int hop, int pad, int pad_mode, int power, bool normalized) -> Tensor",
-           stft_op);
-}
-
-TORCH_LIBRARY_IMPL(torchfx_spectral, Meta, m)
-{
-    m.impl("stft_forward", stft_meta);
-}
-
-// Its inverse in a namespace of its own: torch.ops.torchfx_spectral_inverse.
-TORCH_LIBRARY(torchfx_spectral_inverse, m)
-{
+           stft_op, stft_meta);
     reg_op(m, "istft_forward(Tensor spec, Tensor? window, int n_fft, int hop, int pad, int length, bool normalized) -> (Tensor, Tensor)",
-           istft_op);
-}
-
-TORCH_LIBRARY_IMPL(torchfx_spectral_inverse, Meta, m)
-{
-    m.impl("istft_forward", istft_meta);
-}
-
-// The phase vocoder between the two: torch.ops.torchfx_vocoder.
-TORCH_LIBRARY(torchfx_vocoder, m)
-{
-    reg_op(m, "phase_vocoder_forward(Tensor spec, float rate, int segments=0) -> Tensor", phase_vocoder_op);
-}
-
-TORCH_LIBRARY_IMPL(torchfx_vocoder, Meta, m)
-{
-    m.impl("phase_vocoder_forward", [](const Tensor &spec, double rate, int64_t segments) {
-        const VocoderShape s = vocoder_shape(spec, rate, segments, "phase_vocoder_forward");
-        return at::empty(s.sizes, spec.options()).transpose(-1, -2);
-    });
-}
-
-// Pitch detection in a namespace of its own: torch.ops.torchfx_pitch.
-TORCH_LIBRARY(torchfx_pitch, m)
-{
+           istft_op, istft_meta);
+    reg_op(m, "phase_vocoder_forward(Tensor spec, float rate, int segments=0) -> Tensor", phase_vocoder_op,
+           [](const Tensor &spec, double rate, int64_t segments) {
+               const VocoderShape s = vocoder_shape(spec, rate, segments, "phase_vocoder_forward");
+               return at::empty(s.sizes, spec.options()).transpose(-1, -2);
+           });
     reg_op(m, "yin_forward(Tensor x, float fs, int frame_length, int win_length, int hop, int tau_min, int tau_max, float threshold, int pad, "
-              "int pad_mode, bool return_cmndf, int block=0) -> (Tensor, Tensor, Tensor)", yin_op);
-}
-
-TORCH_LIBRARY_IMPL(torchfx_pitch, Meta, m)
-{
-    m.impl("yin_forward", [](const Tensor &x, double, int64_t frame_length, int64_t win_length, int64_t hop, int64_t tau_min, int64_t tau_max,
-                             double, int64_t pad, int64_t pad_mode, bool return_cmndf, int64_t block) {
-        const YinShape s = yin_shape(x, frame_length, win_length, hop, tau_min, tau_max, pad, pad_mode, block, "yin_forward");
-        return std::make_tuple(at::empty(s.sizes, x.options()), at::empty(s.sizes, x.options()),
-                               at::empty(yin_cmndf_sizes(s, return_cmndf), x.options()));
-    });
-}
-
-// The mel spectrogram in a namespace of its own: torch.ops.torchfx_mel.
-TORCH_LIBRARY(torchfx_mel, m)
-{
+              "int pad_mode, bool return_cmndf, int block=0) -> (Tensor, Tensor, Tensor)", yin_op,
+           [](const Tensor &x, double, int64_t frame_length, int64_t win_length, int64_t hop, int64_t tau_min, int64_t tau_max, double,
+              int64_t pad, int64_t pad_mode, bool return_cmndf, int64_t block) {
+               const YinShape s = yin_shape(x, frame_length, win_length, hop, tau_min, tau_max, pad, pad_mode, block, "yin_forward");
+               return std::make_tuple(at::empty(s.sizes, x.options()), at::empty(s.sizes, x.options()),
+                                      at::empty(yin_cmndf_sizes(s, return_cmndf), x.options()));
+           });
     reg_op(m, "mel_forward(Tensor x, Tensor? window, Tensor table_cpu, int n_filters, int n_fft, int hop, int pad, int pad_mode, int power, "
-              "bool normalized, int log, float amin) -> Tensor", mel_op);
-}
-
-TORCH_LIBRARY_IMPL(torchfx_mel, Meta, m)
-{
-    m.impl("mel_forward", mel_meta);
-}
-
-// The waveshaper likewise: torch.ops.torchfx_shaper.
-TORCH_LIBRARY(torchfx_shaper, m)
-{
+              "bool normalized, int log, float amin) -> Tensor", mel_op, mel_meta);
     reg_op(m, "waveshaper_forward(Tensor x, int oversample, int shape, Tensor? curve_cpu, float drive, float bias, float dry, float wet, "
-              "Tensor? taps_up_cpu, Tensor? taps_dn_cpu) -> Tensor", waveshaper_op);
-}
-
-TORCH_LIBRARY_IMPL(torchfx_shaper, Meta, m)
-{
-    m.impl("waveshaper_forward", [](const Tensor &x, int64_t, int64_t, const OptTensor &, double, double, double, double, const OptTensor &,
-                                    const OptTensor &) { return at::empty_like(x); });
-}
-
-// Its stream form in a namespace of its own: torch.ops.torchfx_shaper_stream.
-TORCH_LIBRARY(torchfx_shaper_stream, m)
-{
+              "Tensor? taps_up_cpu, Tensor? taps_dn_cpu) -> Tensor", waveshaper_op,
+           [](const Tensor &x, int64_t, int64_t, const OptTensor &, double, double, double, double, const OptTensor &, const OptTensor &) {
+               return at::empty_like(x);
+           });
+    // the history's length is the plan's (host-only: it reads the sizes alone)
     reg_op(m, "waveshaper_stream_forward(Tensor x, Tensor? hist, int consumed, int oversample, int shape, Tensor? curve_cpu, float drive, "
               "float bias, float dry, float wet, Tensor? taps_up_cpu, Tensor? taps_dn_cpu, int n_in=-1) -> (Tensor, Tensor)",
-           waveshaper_stream_op);
+           waveshaper_stream_op,
+           [](const Tensor &x, const OptTensor &, int64_t, int64_t oversample, int64_t, const OptTensor &curve, double, double, double, double,
+              const OptTensor &taps_up, const OptTensor &taps_dn, int64_t) {
+               const char *what = "waveshaper_stream_forward";
+               const auto count = [](const OptTensor &t) { return t.has_value() && t->defined() ? t->numel() : (int64_t)0; };
+               const int64_t rows = stream_rows(x);
+               int64_t info[6];
+               check_rc(tfx_waveshaper_stream_plan_info(rows, x.size(-1), oversample, oversample == 1 ? 0 : count(taps_up),
+                                                        oversample == 1 ? 0 : count(taps_dn), count(curve), dtype_code(x, what), info,
+                                                        info + 1, info + 2, info + 3, info + 4, info + 5),
+                        what);
+               return std::make_tuple(at::empty_like(x), at::empty({rows, info[1]}, x.options()));
+           });
 }
 
-TORCH_LIBRARY_IMPL(torchfx_shaper_stream, Meta, m)
-{
-    // the history's length is the plan's (host-only: it reads the sizes alone)
-    m.impl("waveshaper_stream_forward", [](const Tensor &x, const OptTensor &, int64_t, int64_t oversample, int64_t, const OptTensor &curve,
-                                           double, double, double, double, const OptTensor &taps_up, const OptTensor &taps_dn, int64_t) {
-        const char *what = "waveshaper_stream_forward";
-        const auto count = [](const OptTensor &t) { return t.has_value() && t->defined() ? t->numel() : (int64_t)0; };
-        const int64_t rows = stream_rows(x);
-        int64_t info[6];
-        check_rc(tfx_waveshaper_stream_plan_info(rows, x.size(-1), oversample, oversample == 1 ? 0 : count(taps_up),
-                                                 oversample == 1 ? 0 : count(taps_dn), count(curve), dtype_code(x, what), info,
-                                                 info + 1, info + 2, info + 3, info + 4, info + 5),
-                 what);
-        return std::make_tuple(at::empty_like(x), at::empty({rows, info[1]}, x.options()));
-    });
-}
 
 // The reference's module surface (binding.cpp:83-96): exactly these three names and argument lists.
 PYBIND11_MODULE(torchfx_ext, m)

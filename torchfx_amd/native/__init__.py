@@ -63,99 +63,3 @@ def ops():
 
     load()
     return torch.ops.torchfx_hip
-
-
-def dynamics_ops():
-    """``torch.ops.torchfx_dynamics`` (the dynamics processors' namespace, registered by the same module) with the library loaded."""
-    import torch
-
-    load()
-    return torch.ops.torchfx_dynamics
-
-
-def modulation_ops():
-    """``torch.ops.torchfx_modulation`` (the modulated delay line's namespace, registered by the same module) with the library loaded."""
-    import torch
-
-    load()
-    return torch.ops.torchfx_modulation
-
-
-def reverb_ops():
-    """``torch.ops.torchfx_reverb`` (Freeverb's namespace, registered by the same module) with the library loaded."""
-    import torch
-
-    load()
-    return torch.ops.torchfx_reverb
-
-
-def shaper_ops():
-    """``torch.ops.torchfx_shaper`` (the waveshaper's namespace, registered by the same module) with the library loaded."""
-    import torch
-
-    load()
-    return torch.ops.torchfx_shaper
-
-
-def shaper_stream_ops():
-    """``torch.ops.torchfx_shaper_stream`` (the waveshaper's stream form, registered by the same module) with the library loaded."""
-    import torch
-
-    load()
-    return torch.ops.torchfx_shaper_stream
-
-
-def phaser_ops():
-    """``torch.ops.torchfx_phaser`` (the phaser's namespace, registered by the same module) with the library loaded."""
-    import torch
-
-    load()
-    return torch.ops.torchfx_phaser
-
-
-def gate_ops():
-    """``torch.ops.torchfx_gate`` (the gate's namespace, registered by the same module) with the library loaded."""
-    import torch
-
-    load()
-    return torch.ops.torchfx_gate
-
-
-def spectral_ops():
-    """``torch.ops.torchfx_spectral`` (the short-time Fourier transform's namespace, registered by the same module) with the library loaded."""
-    import torch
-
-    load()
-    return torch.ops.torchfx_spectral
-
-
-def mel_ops():
-    """``torch.ops.torchfx_mel`` (the mel spectrogram's namespace, registered by the same module) with the library loaded."""
-    import torch
-
-    load()
-    return torch.ops.torchfx_mel
-
-
-def vocoder_ops():
-    """``torch.ops.torchfx_vocoder`` (the phase vocoder's namespace, registered by the same module) with the library loaded."""
-    import torch
-
-    load()
-    return torch.ops.torchfx_vocoder
-
-
-def pitch_ops():
-    """``torch.ops.torchfx_pitch`` (pitch detection's namespace, registered by the same module) with the library loaded."""
-    import torch
-
-    load()
-    return torch.ops.torchfx_pitch
-
-
-def spectral_inverse_ops():
-    """``torch.ops.torchfx_spectral_inverse`` (the inverse short-time Fourier transform's namespace, registered by the same module) with the library loaded."""
-    import torch
-
-    load()
-    return torch.ops.torchfx_spectral_inverse

@@ -364,11 +364,9 @@ def compressor_forward(x: Tensor, th: float, s: float, w: float, alpha_a: float,
     consecutive rows that share one gain curve; ``th`` the threshold in dB, ``s = 1 - 1 / ratio``, ``w`` the knee width in dB,
     ``alpha_a`` / ``alpha_r`` the detector's coefficients ``exp(-1 / (time fs))`` (0 for a time of 0), ``state [groups, 2]``
     float64 ``(y1, yL)`` or None (silence).  ``segments`` cuts a group's row for the scan (0: the plan's choice; clamped to the
-    tile count): one launch for one segment, three otherwise.  Returns ``(y, gain | None, new state [groups, 2] float64)``.
-    The op lives in ``torch.ops.torchfx_dynamics``."""
-    native.ops()                                         # loads the library: both namespaces are registered by the one module
-    y, g, st = native.dynamics_ops().compressor_forward(x.contiguous(), float(th), float(s), float(w), float(alpha_a), float(alpha_r),
-                                                        float(makeup_db), int(channels), state, bool(return_gain), int(segments))
+    tile count): one launch for one segment, three otherwise.  Returns ``(y, gain | None, new state [groups, 2] float64)``."""
+    y, g, st = native.ops().compressor_forward(x.contiguous(), float(th), float(s), float(w), float(alpha_a), float(alpha_r),
+                                               float(makeup_db), int(channels), state, bool(return_gain), int(segments))
     return y, (g if return_gain else None), st
 
 
@@ -396,10 +394,9 @@ def modulated_delay_forward(x: Tensor, voices, spread: float = 0.0, dry: float =
     :func:`torchfx_amd.modulation.modulated_delay`'s) with its parameters already reduced: ``x [T]``, ``[C, T]`` or
     ``[B, C, T]`` on the device (float32 / float64), ``voices`` a ``[V, 5]`` table of ``(base, depth, inc, phase, gain)`` rows
     (delay and depth in samples, ``inc = rate / fs``, phase in cycles), ``position`` the absolute index of the first sample.
-    One launch (``modulated_delay_kernel``).  The op lives in ``torch.ops.torchfx_modulation``."""
-    native.ops()                                         # loads the library: every namespace is registered by the one module
-    return native.modulation_ops().modulated_delay_forward(x.contiguous(), _voice_table(voices), float(spread), float(dry),
-                                                           LFO_SHAPES.index(shape), INTERPOLATIONS.index(interpolation), int(position))
+    One launch (``modulated_delay_kernel``)."""
+    return native.ops().modulated_delay_forward(x.contiguous(), _voice_table(voices), float(spread), float(dry),
+                                                LFO_SHAPES.index(shape), INTERPOLATIONS.index(interpolation), int(position))
 
 
 def modulated_delay_stream_forward(x: Tensor, hist: Tensor | None, pos: Tensor | None, voices, spread: float = 0.0, dry: float = 1.0,
@@ -409,10 +406,9 @@ def modulated_delay_stream_forward(x: Tensor, hist: Tensor | None, pos: Tensor |
     silence; ``H`` is :func:`modulated_delay_plan_info`'s ``history``) and the position of the chunk's first sample from the
     device int64 ``pos [1]`` (None = 0).  Returns ``(y like x, new history, new position = pos + T)``; the chunks' outputs are
     bit-identical to the one-shot call on the whole signal."""
-    native.ops()
-    return native.modulation_ops().modulated_delay_stream_forward(x.contiguous(), hist, pos, _voice_table(voices), float(spread),
-                                                                  float(dry), LFO_SHAPES.index(shape),
-                                                                  INTERPOLATIONS.index(interpolation))
+    return native.ops().modulated_delay_stream_forward(x.contiguous(), hist, pos, _voice_table(voices), float(spread),
+                                                       float(dry), LFO_SHAPES.index(shape),
+                                                       INTERPOLATIONS.index(interpolation))
 
 
 def modulated_delay_plan_info(length: int, voices, batch: int = 1, channels: int = 1, interpolation: str = "linear") -> dict:
@@ -444,13 +440,12 @@ def freeverb_forward(x: Tensor, comb_delays, allpass_delays, feedback: float, da
     ``[B, C, T]`` on the device (float32 / float64) with ``C`` 1 or 2, ``comb_delays [C, NC]`` and ``allpass_delays [C, NA]`` in
     samples, ``state [B * C, state_len]`` float64 or None (silence).  One workgroup per bank (``freeverb_kernel``), one launch
     for ``C = 1`` or ``wet2 = 0``, else a second one mixes (:func:`freeverb_plan_info`).  Returns ``(y [..., T + tail], new
-    state)``.  The op lives in ``torch.ops.torchfx_reverb``."""
-    native.ops()                                         # loads the library: every namespace is registered by the one module
+    state)``."""
     C = int(x.shape[-2]) if x.dim() >= 2 else 1
-    return native.reverb_ops().freeverb_forward(x.contiguous(), _delay_table(comb_delays, C, "comb_delays").ravel().tolist(),
-                                                _delay_table(allpass_delays, C, "allpass_delays").ravel().tolist(), float(feedback),
-                                                float(damp), float(allpass_gain), float(input_gain), float(dry_gain), float(wet1),
-                                                float(wet2), int(tail), state)
+    return native.ops().freeverb_forward(x.contiguous(), _delay_table(comb_delays, C, "comb_delays").ravel().tolist(),
+                                         _delay_table(allpass_delays, C, "allpass_delays").ravel().tolist(), float(feedback),
+                                         float(damp), float(allpass_gain), float(input_gain), float(dry_gain), float(wet1),
+                                         float(wet2), int(tail), state)
 
 
 def freeverb_plan_info(length: int, comb_delays, allpass_delays, batch: int = 1, channels: int = 1, wet2: float = 0.0,
@@ -478,10 +473,9 @@ def waveshaper_forward(x: Tensor, oversample: int, shape: str, curve: Tensor | N
     float64), ``oversample`` 1, 2, 4 or 8, ``shape`` one of ``WAVESHAPES`` (``"curve"`` with ``curve``, a 1-D host tensor of 2
     to 4096 points in ``x``'s dtype), the linear ``drive``, ``bias``, ``dry`` and ``wet``, and for ``oversample > 1`` the taps of
     ``resample_poly(x, L, 1)`` and ``(x, 1, L)`` as 1-D host tensors of ``x``'s dtype, at most ``64 * oversample`` each
-    (``waveshaper_kernel``; ``oversample = 1``: ``waveshaper_plain_kernel``).  The op lives in ``torch.ops.torchfx_shaper``."""
-    native.ops()                                         # loads the library: every namespace is registered by the one module
-    return native.shaper_ops().waveshaper_forward(x.contiguous(), int(oversample), WAVESHAPES.index(shape), curve, float(drive),
-                                                  float(bias), float(dry), float(wet), taps_up, taps_dn)
+    (``waveshaper_kernel``; ``oversample = 1``: ``waveshaper_plain_kernel``)."""
+    return native.ops().waveshaper_forward(x.contiguous(), int(oversample), WAVESHAPES.index(shape), curve, float(drive),
+                                           float(bias), float(dry), float(wet), taps_up, taps_dn)
 
 
 def waveshaper_plan_info(length: int, oversample: int, taps_up: int = 0, taps_dn: int = 0, curve: int = 0,
@@ -504,11 +498,10 @@ def waveshaper_stream_forward(x: Tensor, hist: Tensor | None, consumed: int, ove
     bit for bit.  ``n_in`` (default: all ``T``) is the number of real inputs in ``x``; fewer says that the stream ends after them
     (the tail of a stream: ``T = D``, ``n_in = 0``).  ``D`` and ``Hs`` are :func:`waveshaper_stream_plan_info`'s ``latency`` and
     ``history`` (both 0 for ``oversample = 1``); the other arguments are :func:`waveshaper_forward`'s
-    (``waveshaper_stream_kernel``).  The op lives in ``torch.ops.torchfx_shaper_stream``."""
-    native.ops()
-    return native.shaper_stream_ops().waveshaper_stream_forward(x.contiguous(), hist, int(consumed), int(oversample),
-                                                                WAVESHAPES.index(shape), curve, float(drive), float(bias), float(dry),
-                                                                float(wet), taps_up, taps_dn, -1 if n_in is None else int(n_in))
+    (``waveshaper_stream_kernel``)."""
+    return native.ops().waveshaper_stream_forward(x.contiguous(), hist, int(consumed), int(oversample),
+                                                  WAVESHAPES.index(shape), curve, float(drive), float(bias), float(dry),
+                                                  float(wet), taps_up, taps_dn, -1 if n_in is None else int(n_in))
 
 
 def waveshaper_stream_plan_info(length: int, oversample: int, taps_up: int = 0, taps_dn: int = 0, curve: int = 0,
@@ -533,13 +526,11 @@ def phaser_forward(x: Tensor, stages: int, fs: float, rate: float, min_freq: flo
     stream; ``state [rows, stages + 1]`` float64 ``(x_0[-1], .., x_N[-1])`` or None (silence).  ``segments`` cuts a row for the
     scan (0: the plan's choice; clamped to the tile count): one launch for one segment, two otherwise.  Returns ``(y, coef |
     None, new state, pos + T | None)``: ``coef`` is ``a[n]`` as the kernel computed it, float64 ``[C, T]`` (``[1, T]`` when
-    ``spread == 0`` or ``C == 1``); the new position is a fresh device tensor when ``pos`` was given.  The op lives in
-    ``torch.ops.torchfx_phaser``."""
-    native.ops()                                         # loads the library: every namespace is registered by the one module
-    y, coef, st, pout = native.phaser_ops().phaser_forward(x.contiguous(), int(stages), float(fs), float(rate), float(min_freq),
-                                                           float(max_freq), float(phase), float(spread), float(dry), float(wet),
-                                                           LFO_SHAPES.index(shape), int(position), pos, state, bool(return_coef),
-                                                           int(segments))
+    ``spread == 0`` or ``C == 1``); the new position is a fresh device tensor when ``pos`` was given."""
+    y, coef, st, pout = native.ops().phaser_forward(x.contiguous(), int(stages), float(fs), float(rate), float(min_freq),
+                                                    float(max_freq), float(phase), float(spread), float(dry), float(wet),
+                                                    LFO_SHAPES.index(shape), int(position), pos, state, bool(return_coef),
+                                                    int(segments))
     return y, (coef if return_coef else None), st, (pout if pos is not None else None)
 
 
@@ -561,11 +552,10 @@ def gate_forward(x: Tensor, p_open: float, p_close: float, r: float, hold: int, 
     ``hold`` in samples, ``alpha_a`` / ``alpha_r`` the smoother's coefficients ``exp(-1 / (time fs))`` (0 for a time of 0),
     ``state [groups, 3]`` float64 ``(g, open, c)`` or None (closed, ``g = r``).  ``segments`` cuts a group's row for the scans
     (0: the plan's choice; clamped to the tile count): one launch for one segment, three otherwise.  Returns ``(y, gain | None,
-    open | None, new state [groups, 3] float64)``.  The op lives in ``torch.ops.torchfx_gate``."""
-    native.ops()                                         # loads the library: every namespace is registered by the one module
-    y, g, o, st = native.gate_ops().gate_forward(x.contiguous(), float(p_open), float(p_close), float(r), int(hold), float(alpha_a),
-                                                 float(alpha_r), int(channels), state, bool(return_gain), bool(return_open),
-                                                 int(segments))
+    open | None, new state [groups, 3] float64)``."""
+    y, g, o, st = native.ops().gate_forward(x.contiguous(), float(p_open), float(p_close), float(r), int(hold), float(alpha_a),
+                                            float(alpha_r), int(channels), state, bool(return_gain), bool(return_open),
+                                            int(segments))
     return y, (g if return_gain else None), (o if return_open else None), st
 
 
@@ -589,14 +579,13 @@ def stft_forward(x: Tensor, window: Tensor | None, n_fft: int, hop: int, pad: in
     ``x``'s dtype with 1 to ``n_fft`` values (centred in zeros) or None (ones), ``pad`` samples added at each end
     (``n_fft // 2`` for ``center=True``, 0 without) by ``pad_mode`` ("reflect" / "constant"), ``power`` None (complex), 1.0 or 2.0.
     Returns ``[..., n_fft // 2 + 1, frames]``, a transposed view of a contiguous ``[..., frames, bins]`` buffer.  A geometry
-    off the route (:func:`stft_plan_info`) is an error here, not a fall-back.  The op lives in ``torch.ops.torchfx_spectral``."""
-    native.ops()                                         # loads the library: every namespace is registered by the one module
+    off the route (:func:`stft_plan_info`) is an error here, not a fall-back."""
     if pad_mode not in STFT_PAD_MODES:
         raise ValueError(f"stft_forward: pad_mode must be one of {sorted(STFT_PAD_MODES)}, got {pad_mode!r}")
     if power not in STFT_POWERS:
         raise ValueError(f"stft_forward: power must be None, 1.0 or 2.0, got {power!r}")
-    return native.spectral_ops().stft_forward(x, window, int(n_fft), int(hop), int(pad), STFT_PAD_MODES[pad_mode], STFT_POWERS[power],
-                                              bool(normalized))
+    return native.ops().stft_forward(x, window, int(n_fft), int(hop), int(pad), STFT_PAD_MODES[pad_mode], STFT_POWERS[power],
+                                     bool(normalized))
 
 
 def stft_plan_info(n_fft: int, hop: int, win_length: int, length: int, rows: int = 1, dtype: torch.dtype = torch.float32,
@@ -645,16 +634,15 @@ def mel_forward(x: Tensor, window: Tensor | None, table: Tensor, n_filters: int,
     2.0, ``table`` the host band table of ``n_filters`` filters (:func:`mel_band_table`, in ``x``'s dtype), ``log`` None, "db",
     "log10" or "ln" with the floor ``amin``.  Returns ``[..., n_filters, frames]``, a transposed view of a contiguous
     ``[..., frames, n_filters]`` buffer.  A geometry or table off the route (:func:`mel_plan_info`) is an error here, not a
-    fall-back.  The op lives in ``torch.ops.torchfx_mel``."""
-    native.ops()                                         # loads the library: every namespace is registered by the one module
+    fall-back."""
     if pad_mode not in STFT_PAD_MODES:
         raise ValueError(f"mel_forward: pad_mode must be one of {sorted(STFT_PAD_MODES)}, got {pad_mode!r}")
     if power not in (1.0, 2.0):
         raise ValueError(f"mel_forward: power must be 1.0 or 2.0, got {power!r}")
     if log not in MEL_LOGS:
         raise ValueError(f"mel_forward: log must be None, 'db', 'log10' or 'ln', got {log!r}")
-    return native.mel_ops().mel_forward(x, window, table, int(n_filters), int(n_fft), int(hop), int(pad), STFT_PAD_MODES[pad_mode],
-                                        STFT_POWERS[float(power)], bool(normalized), MEL_LOGS[log], float(amin))
+    return native.ops().mel_forward(x, window, table, int(n_filters), int(n_fft), int(hop), int(pad), STFT_PAD_MODES[pad_mode],
+                                    STFT_POWERS[float(power)], bool(normalized), MEL_LOGS[log], float(amin))
 
 
 def mel_plan_info(n_fft: int, hop: int, win_length: int, length: int, rows: int = 1, dtype: torch.dtype = torch.float32,
@@ -684,11 +672,9 @@ def istft_forward(spec: Tensor, window: Tensor | None, n_fft: int, hop: int, pad
     when the window's overlap-add envelope vanishes somewhere in the returned range (torch's "window overlap add min" error).
     It is not read here, so the call does not synchronise.  The kernel reads the layout :func:`stft_forward` returns (the
     transpose of a contiguous ``[..., frames, bins]`` buffer) in place; any other layout costs one copy into it first.  A
-    geometry off the route (:func:`istft_plan_info`) is an error here, not a fall-back.  The op lives in
-    ``torch.ops.torchfx_spectral_inverse``."""
-    native.ops()                                         # loads the library: every namespace is registered by the one module
-    return native.spectral_inverse_ops().istft_forward(spec, window, int(n_fft), int(hop), int(pad), -1 if length is None else int(length),
-                                                       bool(normalized))
+    geometry off the route (:func:`istft_plan_info`) is an error here, not a fall-back."""
+    return native.ops().istft_forward(spec, window, int(n_fft), int(hop), int(pad), -1 if length is None else int(length),
+                                      bool(normalized))
 
 
 def istft_plan_info(n_fft: int, hop: int, win_length: int, frames: int, rows: int = 1, dtype: torch.dtype = torch.float32,
@@ -712,10 +698,8 @@ def phase_vocoder_forward(spec: Tensor, rate: float, segments: int = 0) -> Tenso
     Returns ``[..., bins, ceil(frames / rate)]``, a transposed view of a contiguous ``[..., Fo, bins]`` buffer: the layout
     :func:`stft_forward` returns, which the kernel also reads in place (any other layout costs one copy into it first), so
     :func:`istft_forward` takes the result without a copy.  ``segments`` cuts each row's output frames (0: the plan's choice,
-    :func:`phase_vocoder_plan_info`): one launch for one segment, two otherwise, to the same bits.  The op lives in
-    ``torch.ops.torchfx_vocoder``."""
-    native.ops()                                         # loads the library: every namespace is registered by the one module
-    return native.vocoder_ops().phase_vocoder_forward(spec, float(rate), int(segments))
+    :func:`phase_vocoder_plan_info`): one launch for one segment, two otherwise, to the same bits."""
+    return native.ops().phase_vocoder_forward(spec, float(rate), int(segments))
 
 
 def phase_vocoder_plan_info(frames: int, bins: int, rate: float, rows: int = 1, dtype: torch.dtype = torch.float32,
@@ -743,12 +727,11 @@ def yin_forward(x: Tensor, fs: float, frame_length: int, win_length: int, hop: i
     each end (``frame_length // 2`` for ``center=True``) by ``pad_mode`` ("constant" / "reflect").  Returns ``(f0, aperiodicity,
     cmndf)``: ``[..., frames]`` twice and ``[..., frames, tau_max + 2]``, empty without ``return_cmndf`` (the difference function
     then never leaves the chip).  ``block`` 0 is the plan's choice (:func:`yin_plan_info`), ``win_length`` forces the route that
-    shares nothing.  The op lives in ``torch.ops.torchfx_pitch``."""
-    native.ops()                                         # loads the library: every namespace is registered by the one module
+    shares nothing."""
     if pad_mode not in ("constant", "reflect"):
         raise ValueError(f"yin_forward: pad_mode must be 'constant' or 'reflect', got {pad_mode!r}")
-    return native.pitch_ops().yin_forward(x, float(fs), int(frame_length), int(win_length), int(hop), int(tau_min), int(tau_max),
-                                          float(threshold), int(pad), STFT_PAD_MODES[pad_mode], bool(return_cmndf), int(block))
+    return native.ops().yin_forward(x, float(fs), int(frame_length), int(win_length), int(hop), int(tau_min), int(tau_max),
+                                    float(threshold), int(pad), STFT_PAD_MODES[pad_mode], bool(return_cmndf), int(block))
 
 
 def yin_plan_info(length: int, fs: float, fmin: float = 65.0, fmax: float = 2093.0, frame_length: int = 2048, win_length: int | None = None,
