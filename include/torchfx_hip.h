@@ -994,6 +994,32 @@ int tfx_phase_vocoder_plan_info(int64_t rows, int64_t frames, int64_t bins, doub
                                 int64_t *workgroups, int64_t *scratch_bytes);
 
 /* ---------------------------------------------------------------------------
+ * tfx_phase_vocoder_locked_forward -- the phase vocoder above with identity phase locking (Laroche & Dolson 1999, III-C).  Steps
+ * 1, 2 and 4 and the angles A of step 3 are tfx_phase_vocoder_forward's; the phase is
+ *   3'. U[0,k] = A[0,k]; U[t,k] = phi[t-1,k] + (A[i_{t-1}+1,k] - A[i_{t-1},k]), the plain update.  Bin k is a peak of frame t iff
+ *       mag[t,k] > mag[t,j] for every in-range j in {k-2, k-1, k+1, k+2} (a comparison with a NaN is false; a single bin is a
+ *       peak).  P(k) is the peak nearest to k, the lower one at equal distance.  A frame without a peak has phi[t,k] = U[t,k];
+ *       otherwise phi[t,k] = U[t,P(k)] + (A[i_t,k] - A[i_t,P(k)]), in wrapping 64-bit integers.
+ *   5'. The paths couple a row's bins: from the first output frame that reads a NaN or Inf bin every bin of every later frame
+ *       of that row is NaN, that frame included; earlier frames and other rows are untouched.
+ * At rate 1 phi[t,k] = A[t,k], and a spectrum without peaks takes the plain update everywhere: both are bit-identical to
+ * tfx_phase_vocoder_forward.  One workgroup owns all bins of one (row, time segment), several bins a lane, the frame's moduli,
+ * phases and peak mask in LDS (two barriers a frame).  `segments` as above: one launch for one segment; otherwise a summary
+ * pass leaves, per (row, segment, bin), the bin of the segment's entry state its phase descends from and the integer sum along
+ * that path, and per (row, segment) the poison flag, in `scratch`; the writing pass composes them.  The same bits either way,
+ * whatever the other rows.  Served: bins <= 4097 (n_fft 8192); more is refused.  Arguments are checked before the device is touched.
+ * ------------------------------------------------------------------------- */
+int tfx_phase_vocoder_locked_forward(const void *spec, void *out, int dtype, int64_t rows, int64_t frames, int64_t bins, double rate,
+                                     int64_t segments, void *scratch, tfx_stream_t stream);
+/* what tfx_phase_vocoder_locked_forward does (host-only, same checks): the output frames Fo, the lanes of a workgroup, the bins
+ * of a lane, the LDS bytes of a workgroup (the larger of the two passes), the segments it takes, the output frames of a segment,
+ * the launches (1 or 2), the workgroups of the writing launch (rows * segments) and the bytes of `scratch` (0 for one segment). */
+int tfx_phase_vocoder_locked_plan_info(int64_t rows, int64_t frames, int64_t bins, double rate, int dtype, int64_t segments,
+                                       int64_t *out_frames, int64_t *threads, int64_t *bins_per_thread, int64_t *lds_bytes,
+                                       int64_t *segments_out, int64_t *seg_frames, int64_t *launches, int64_t *workgroups,
+                                       int64_t *scratch_bytes);
+
+/* ---------------------------------------------------------------------------
  * tfx_yin_forward -- YIN pitch detection (de Cheveigne & Kawahara, JASA 2002, steps 2 to 5) over every row of x [rows, T], in
  * dtype.  frames = 1 + (T + 2 pad - frame_length) / hop; frame f starts at s = f hop - pad (samples outside the row are zeros,
  * or one reflection for TFX_STFT_PAD_REFLECT, by addressing) and reads its first win_length + Lmax samples, Lmax = tau_max + 1:

@@ -13,7 +13,12 @@ Times are device events around one call; min / median / max of --repeats are all
 is gated.  The byte model of (a) is the input once (rate > 1: the frames an output stands on, at most two per output) plus the
 output once; beside it stands what (e)'s rate would make of those bytes -- the rest is float64 atan2 and sincospi.
 
+With --lock it times instead, on the same eight cases and tensors: (a) the identity phase-locked kernel, (b) the plain kernel,
+(c) ``time_stretch(..., phase_lock="identity")`` whole, (d) ``time_stretch`` whole; --plain times the plain kernel alone (what a
+build without the locked route can run, for the same-session comparison of the untouched code).
+
     python tools/phasevocoder_bench.py --out profiles/phasevocoder_bench.txt
+    python tools/phasevocoder_bench.py --lock --out profiles/phasevocoder_lock_bench.txt
 """
 from __future__ import annotations
 
@@ -70,13 +75,57 @@ def time_alternating(fns, repeats):
     return [(min(t), statistics.median(t), max(t)) for t in ts]
 
 
+def lock_report(repeats: int, plain_only: bool) -> list[str]:
+    """The locked route beside the plain one (or, ``plain_only``, the plain kernel alone)."""
+    from torchfx_amd import phase_vocoder, stft, time_stretch, torchfx_ext as E
+    from torchfx_amd.spectral import named_window
+
+    lines = [f"phase vocoder, {'plain kernel alone' if plain_only else 'identity phase locking beside the plain kernel'}, float32 on "
+             f"{torch.cuda.get_device_name(0)}; device events around one call, min / median / max of {repeats} alternating repeats, ms"]
+    fmt = lambda t: f"{t[0]:.3f} / {t[1]:.3f} / {t[2]:.3f}"          # noqa: E731
+    for rows, T in SHAPES:
+        for n_fft, hop in GEOMETRIES:
+            x = torch.randn(rows, T, generator=torch.Generator(device="cuda").manual_seed(1), device="cuda", dtype=torch.float32) * 0.25
+            w = named_window("hann", n_fft, torch.float32, x.device)
+            X = stft(x, n_fft, hop, window=w)
+            bins, frames = X.shape[-2:]
+            for rate in RATES:
+                case = f"{rows} x {T}, n_fft {n_fft} hop {hop}, rate {rate}"
+                if plain_only:
+                    b, = time_alternating([lambda: phase_vocoder(X, rate)], repeats)
+                    lines.append(f"{case}: plain kernel {fmt(b)}")
+                    continue
+                p = E.phase_vocoder_plan_info(frames, bins, rate, rows, torch.float32, 0, 1)
+                a, b, c, d = time_alternating([lambda: phase_vocoder(X, rate, phase_lock="identity"), lambda: phase_vocoder(X, rate),
+                                               lambda: time_stretch(x, rate, n_fft, hop, window=w, phase_lock="identity"),
+                                               lambda: time_stretch(x, rate, n_fft, hop, window=w)], repeats)
+                lines.append(json.dumps(dict(rows=rows, samples=T, n_fft=n_fft, hop=hop, rate=rate, frames=frames, plan=p, locked_ms=a,
+                                             plain_ms=b, time_stretch_locked_ms=c, time_stretch_ms=d, locked_over_plain=a[0] / b[0])))
+                lines.append(f"{case} ({frames} -> {p['out_frames']} frames; {p['threads']} lanes x {p['bins_per_thread']} bins, "
+                             f"{p['lds_bytes']} B LDS, {p['segments']} segments of {p['seg_frames']}, {p['workgroups']} workgroups): "
+                             f"(a) locked {fmt(a)}   (b) plain {fmt(b)}   a/b {a[0] / b[0]:.2f}x   (c) time_stretch locked {fmt(c)}   "
+                             f"(d) time_stretch {fmt(d)}   c/d {c[0] / d[0]:.2f}x")
+            del X, x
+            torch.cuda.empty_cache()
+    return lines
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the report here")
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--lock", action="store_true", help="the locked route beside the plain one")
+    ap.add_argument("--plain", action="store_true", help="the plain kernel alone")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("phasevocoder_bench needs a ROCm device")
+    if args.lock or args.plain:
+        text = "\n".join(lock_report(args.repeats, args.plain))
+        print(text, flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     from torchfx_amd import phase_vocoder, stft, time_stretch, torchfx_ext as E
     from torchfx_amd.spectral import named_window
 

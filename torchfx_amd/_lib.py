@@ -116,6 +116,8 @@ SIGNATURES = {
                             + [ctypes.POINTER(ctypes.c_double)]),
     "tfx_phase_vocoder_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _dbl, _i64, _vp, _vp]),
     "tfx_phase_vocoder_plan_info": (_int, [_i64, _i64, _i64, _dbl, _int, _i64] + [ctypes.POINTER(_i64)] * 7),
+    "tfx_phase_vocoder_locked_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _dbl, _i64, _vp, _vp]),
+    "tfx_phase_vocoder_locked_plan_info": (_int, [_i64, _i64, _i64, _dbl, _int, _i64] + [ctypes.POINTER(_i64)] * 9),
     "tfx_yin_forward": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _dbl, _i64, _i64, _i64, _i64, _i64, _dbl, _i64, _int, _i64, _vp]),
     "tfx_yin_plan_info": (_int, [_i64] * 7 + [_int, _i64, _int, _i64] + [ctypes.POINTER(_i64)] * 8),
     "tfx_sum_forward": (_int, [_vp, _int, _vp, _int, _i64, _vp]),

@@ -925,6 +925,27 @@ int tfx_phase_vocoder_plan_info(int64_t rows, int64_t frames, int64_t bins, doub
     TFX_API_END
 }
 
+int tfx_phase_vocoder_locked_forward(const void *spec, void *out, int dtype, int64_t rows, int64_t frames, int64_t bins, double rate,
+                                     int64_t segments, void *scratch, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    phase_vocoder_locked_forward(spec, out, dtype, rows, frames, bins, rate, segments, scratch, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_phase_vocoder_locked_plan_info(int64_t rows, int64_t frames, int64_t bins, double rate, int dtype, int64_t segments,
+                                       int64_t *out_frames, int64_t *threads, int64_t *bins_per_thread, int64_t *lds_bytes,
+                                       int64_t *segments_out, int64_t *seg_frames, int64_t *launches, int64_t *workgroups,
+                                       int64_t *scratch_bytes)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(out_frames && threads && bins_per_thread && lds_bytes && segments_out && seg_frames && launches && workgroups && scratch_bytes,
+              "phase_vocoder_locked_plan_info: null output");
+    phase_vocoder_locked_plan_info(rows, frames, bins, rate, dtype, segments, out_frames, threads, bins_per_thread, lds_bytes, segments_out,
+                                   seg_frames, launches, workgroups, scratch_bytes);
+    TFX_API_END
+}
+
 int tfx_yin_forward(const void *x, void *f0, void *aper, void *cmndf, int dtype, int64_t rows, int64_t T, double fs,
                     int64_t frame_length, int64_t win_length, int64_t hop, int64_t tau_min, int64_t tau_max, double threshold,
                     int64_t pad, int pad_mode, int64_t block, tfx_stream_t stream)

@@ -811,7 +811,8 @@ std::tuple<Tensor, Tensor> istft_op(const Tensor &spec_in, const OptTensor &wind
 }
 
 // Phase vocoder (tfx_phase_vocoder_forward): spec [bins, frames], [C, bins, frames] or [B, C, bins, frames], complex64 /
-// complex128; rate > 0; segments 0 = the plan's choice -> [..., bins, Fo], the transposed view of a contiguous [..., Fo, bins]
+// complex128; rate > 0; segments 0 = the plan's choice; lock 0 none, 1 identity phase locking
+// (tfx_phase_vocoder_locked_forward) -> [..., bins, Fo], the transposed view of a contiguous [..., Fo, bins]
 // buffer: stft_forward's layout in and out, so istft_forward reads the result in place.  Any other input layout is copied into
 // it first.  The summaries between the two launches live in a tensor from torch's allocator.
 struct VocoderShape {
@@ -820,8 +821,9 @@ struct VocoderShape {
     int64_t rows, frames, bins, scratch_bytes;
 };
 
-VocoderShape vocoder_shape(const Tensor &spec, double rate, int64_t segments, const char *what)
+VocoderShape vocoder_shape(const Tensor &spec, double rate, int64_t segments, int64_t lock, const char *what)
 {
+    TORCH_CHECK(lock == 0 || lock == 1, what, ": lock must be 0 (none) or 1 (identity phase locking), got ", lock);
     TORCH_CHECK(spec.dim() >= 2 && spec.dim() <= 4, what, ": spec must be [bins, frames], [C, bins, frames] or [B, C, bins, frames], got ",
                 spec.dim(), " dimensions");
     TORCH_CHECK(spec.scalar_type() == at::kComplexFloat || spec.scalar_type() == at::kComplexDouble, what,
@@ -831,28 +833,34 @@ VocoderShape vocoder_shape(const Tensor &spec, double rate, int64_t segments, co
     s.bins = spec.size(-2);
     s.frames = spec.size(-1);
     s.rows = c10::multiply_integers(spec.sizes().begin(), spec.sizes().end() - 2);
-    int64_t info[7];
-    check_rc(tfx_phase_vocoder_plan_info(s.rows, s.frames, s.bins, rate, s.dt, segments, info, info + 1, info + 2, info + 3, info + 4,
-                                         info + 5, info + 6),
-             what);
-    s.scratch_bytes = info[6];
+    int64_t info[9];
+    if (lock)
+        check_rc(tfx_phase_vocoder_locked_plan_info(s.rows, s.frames, s.bins, rate, s.dt, segments, info, info + 1, info + 2, info + 3,
+                                                    info + 4, info + 5, info + 6, info + 7, info + 8),
+                 what);
+    else
+        check_rc(tfx_phase_vocoder_plan_info(s.rows, s.frames, s.bins, rate, s.dt, segments, info, info + 1, info + 2, info + 3, info + 4,
+                                             info + 5, info + 6),
+                 what);
+    s.scratch_bytes = info[lock ? 8 : 6];
     s.sizes.assign(spec.sizes().begin(), spec.sizes().end() - 2);
     s.sizes.push_back(info[0]);
     s.sizes.push_back(s.bins);
     return s;
 }
 
-Tensor phase_vocoder_op(const Tensor &spec_in, double rate, int64_t segments)
+Tensor phase_vocoder_op(const Tensor &spec_in, double rate, int64_t segments, int64_t lock)
 {
     const char *what = "phase_vocoder_forward";
     need_device(spec_in, "spec");
-    const VocoderShape s = vocoder_shape(spec_in, rate, segments, what);
+    const VocoderShape s = vocoder_shape(spec_in, rate, segments, lock, what);
     const Tensor spec = spec_in.transpose(-1, -2).contiguous();         // [..., frames, bins]: no copy for stft_forward's layout
     Tensor out = at::empty(s.sizes, spec.options());
     Tensor scratch = at::empty({s.scratch_bytes / 4}, spec.options().dtype(at::kInt));
     c10::hip::HIPGuard guard(spec.get_device());
-    check_rc(tfx_phase_vocoder_forward(spec.data_ptr(), out.data_ptr(), s.dt, s.rows, s.frames, s.bins, rate, segments,
-                                       s.scratch_bytes ? scratch.data_ptr() : nullptr, stream_of(spec)),
+    check_rc((lock ? tfx_phase_vocoder_locked_forward : tfx_phase_vocoder_forward)(
+                 spec.data_ptr(), out.data_ptr(), s.dt, s.rows, s.frames, s.bins, rate, segments,
+                 s.scratch_bytes ? scratch.data_ptr() : nullptr, stream_of(spec)),
              what);
     return out.transpose(-1, -2);
 }
@@ -1730,9 +1738,9 @@ TORCH_LIBRARY(torchfx_hip, m)
            stft_op, stft_meta);
     reg_op(m, "istft_forward(Tensor spec, Tensor? window, int n_fft, int hop, int pad, int length, bool normalized) -> (Tensor, Tensor)",
            istft_op, istft_meta);
-    reg_op(m, "phase_vocoder_forward(Tensor spec, float rate, int segments=0) -> Tensor", phase_vocoder_op,
-           [](const Tensor &spec, double rate, int64_t segments) {
-               const VocoderShape s = vocoder_shape(spec, rate, segments, "phase_vocoder_forward");
+    reg_op(m, "phase_vocoder_forward(Tensor spec, float rate, int segments=0, int lock=0) -> Tensor", phase_vocoder_op,
+           [](const Tensor &spec, double rate, int64_t segments, int64_t lock) {
+               const VocoderShape s = vocoder_shape(spec, rate, segments, lock, "phase_vocoder_forward");
                return at::empty(s.sizes, spec.options()).transpose(-1, -2);
            });
     reg_op(m, "yin_forward(Tensor x, float fs, int frame_length, int win_length, int hop, int tau_min, int tau_max, float threshold, int pad, "

@@ -179,6 +179,12 @@ void phase_vocoder_forward(const void *spec, void *out, int dtype, int64_t rows,
 void phase_vocoder_plan_info(int64_t rows, int64_t frames, int64_t bins, double rate, int dtype, int64_t segments, int64_t *out_frames,
                              int64_t *bin_tile, int64_t *segments_out, int64_t *seg_frames, int64_t *launches, int64_t *workgroups,
                              int64_t *scratch_bytes);
+void phase_vocoder_locked_forward(const void *spec, void *out, int dtype, int64_t rows, int64_t frames, int64_t bins, double rate,
+                                  int64_t segments, void *scratch, hipStream_t stream);
+void phase_vocoder_locked_plan_info(int64_t rows, int64_t frames, int64_t bins, double rate, int dtype, int64_t segments,
+                                    int64_t *out_frames, int64_t *threads, int64_t *bins_per_thread, int64_t *lds_bytes,
+                                    int64_t *segments_out, int64_t *seg_frames, int64_t *launches, int64_t *workgroups,
+                                    int64_t *scratch_bytes);
 
 // ---- yin.hip ----
 void yin_forward(const void *x, void *f0, void *aper, void *cmndf, int dtype, int64_t rows, int64_t T, double fs, int64_t frame_length,

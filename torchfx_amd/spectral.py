@@ -33,8 +33,10 @@ Between the two transforms stands the phase vocoder (:func:`phase_vocoder`, ``to
 one or two launches of ``torchfx_amd/csrc/phasevocoder.hip`` (``torchfx_ext.phase_vocoder_forward``) that read the spectrum once,
 in the layout :func:`stft` returns, and write the stretched one once, in the layout :func:`istft` reads, with the running phase
 kept exactly as a 64-bit integer.  On it rest :func:`time_stretch` / :class:`TimeStretch` (tempo without pitch) and
-:func:`pitch_shift` / :class:`PitchShift` (pitch without tempo; the last step is :func:`torchfx_amd.resample_poly`).  Not
-provided: phase locking (identity or scaled), transient preservation, formant correction, a streaming vocoder, autograd, axes
+:func:`pitch_shift` / :class:`PitchShift` (pitch without tempo; the last step is :func:`torchfx_amd.resample_poly`).
+``phase_lock="identity"`` on any of them locks every bin's phase to its nearest spectral peak (Laroche & Dolson 1999): a kernel
+of its own in the same file, one workgroup per (row, time segment) with the frame's moduli, phases and peak mask in LDS.  Not
+provided: scaled phase locking, transient preservation, formant correction, a streaming vocoder, autograd, axes
 other than the last two, a time-varying ``rate``.
 """
 from __future__ import annotations
@@ -445,7 +447,46 @@ def _vocoder_rate(rate, what: str = "phase_vocoder") -> float:
     return float(rate)
 
 
-def _vocoder_host(X: np.ndarray, rate: float) -> np.ndarray:
+def _lock_served(what: str, bins: int, dtype: torch.dtype) -> None:
+    """``ValueError`` where the device's locked route does not serve ``bins``: the plan's own answer, asked before any launch."""
+    try:
+        E.phase_vocoder_plan_info(1, bins, 1.0, 1, dtype, 0, 1)
+    except RuntimeError as e:
+        raise ValueError(f"{what}: {e}") from None
+
+
+def _vocoder_lock(phase_lock, what: str = "phase_vocoder") -> int:
+    """``phase_lock`` as the native ``lock`` code: ``None`` 0, ``"identity"`` 1."""
+    if phase_lock is None:
+        return 0
+    if phase_lock != "identity":
+        raise ValueError(f'{what}: phase_lock must be None or "identity", got {phase_lock!r}')
+    return 1
+
+
+def _locked_phase(A: np.ndarray, mag: np.ndarray, i: np.ndarray) -> np.ndarray:
+    """Identity phase locking, frame by frame: ``A [..., bins, F + 2]`` (uint64 turns), ``mag [..., bins, Fo]`` in the real dtype
+    -> ``phi [..., bins, Fo]`` (uint64)."""
+    bins = A.shape[-2]
+    k = np.arange(bins)
+    phi = np.empty(mag.shape, np.uint64)
+    U = A[..., 0].copy()                                                 # the plain update of the frame to come
+    for t in range(len(i)):
+        m = mag[..., t]
+        peak = np.ones(m.shape, bool)
+        for s in (1, 2):                                                 # strictly above every in-range neighbour; a NaN compares false
+            peak[..., s:] &= m[..., s:] > m[..., :-s]
+            peak[..., :-s] &= m[..., :-s] > m[..., s:]
+        lo = np.maximum.accumulate(np.where(peak, k, -1), axis=-1)       # the nearest peak at or below, -1: none
+        hi = np.minimum.accumulate(np.where(peak, k, bins)[..., ::-1], axis=-1)[..., ::-1]      # at or above, bins: none
+        near = np.where(lo < 0, np.where(hi == bins, k, hi), np.where((hi == bins) | (k - lo <= hi - k), lo, hi))
+        A0 = A[..., i[t]]
+        phi[..., t] = np.take_along_axis(U - A0, near, axis=-1) + A0     # U[P] + (A[i, k] - A[i, P]); no peak: U[k]
+        U = phi[..., t] + (A[..., i[t] + 1] - A0)
+    return phi
+
+
+def _vocoder_host(X: np.ndarray, rate: float, lock: int = 0) -> np.ndarray:
     """The definition of :func:`phase_vocoder` on a host array ``[..., bins, F]``, with the device's fixed-point phase."""
     real = np.float32 if X.dtype == np.complex64 else np.float64
     F = X.shape[-1]
@@ -461,18 +502,24 @@ def _vocoder_host(X: np.ndarray, rate: float) -> np.ndarray:
         w = np.rint(turns * 2.0 ** 64)
         A = np.where(w >= 2.0 ** 63, w - 2.0 ** 64, w).astype(np.int64).view(np.uint64)      # 2^64 = one turn
         inc = A[..., i + 1] - A[..., i]                                                      # wraps, as the sum does
-        P = A[..., :1] + np.concatenate([np.zeros_like(inc[..., :1]), np.cumsum(inc, axis=-1, dtype=np.uint64)[..., :-1]], axis=-1)
-        ang = P.view(np.int64).astype(np.float64) * (math.pi * 2.0 ** -63)                   # [-pi, pi]
         M = np.abs(Xp).astype(real)
-        mag = (alpha * M[..., i + 1] + (real(1) - alpha) * M[..., i]).astype(np.float64)
+        mag = alpha * M[..., i + 1] + (real(1) - alpha) * M[..., i]
+        if lock:
+            P = _locked_phase(A, mag, i)
+        else:
+            P = A[..., :1] + np.concatenate([np.zeros_like(inc[..., :1]), np.cumsum(inc, axis=-1, dtype=np.uint64)[..., :-1]], axis=-1)
+        ang = P.view(np.int64).astype(np.float64) * (math.pi * 2.0 ** -63)                   # [-pi, pi]
+        mag = mag.astype(np.float64)
         Y = (mag * np.cos(ang) + 1j * (mag * np.sin(ang))).astype(X.dtype)
     bad = np.logical_or.accumulate(~(finite[..., i] & finite[..., i + 1]), axis=-1)
+    if lock:                                                             # the paths couple the bins: the poison is the row's
+        bad = np.broadcast_to(bad.any(axis=-2, keepdims=True), bad.shape)
     Y[bad] = complex(np.nan, np.nan)
     return Y
 
 
 @torch.no_grad()
-def phase_vocoder(X: Tensor, rate: float, phase_advance: Tensor | None = None) -> Tensor:
+def phase_vocoder(X: Tensor, rate: float, phase_advance: Tensor | None = None, phase_lock: str | None = None) -> Tensor:
     """``torchaudio.functional.phase_vocoder(X, rate, phase_advance)``: the spectrum ``X [bins, F]``, ``[C, bins, F]`` or
     ``[B, C, bins, F]`` (complex64 / complex128) sped up by ``rate > 0`` (a Python float) without a change of pitch:
     ``[..., bins, Fo]`` with ``Fo = ceil(F / rate)``, computed in double as ``torch.arange(0, F, rate)`` sizes itself.
@@ -491,6 +538,18 @@ def phase_vocoder(X: Tensor, rate: float, phase_advance: Tensor | None = None) -
     reads a bin with a NaN or Inf component every later frame of that (row, bin) is NaN in both parts; earlier frames, other
     bins and other rows keep their bits.
 
+    ``phase_lock="identity"`` locks the phases around each spectral peak (Laroche & Dolson 1999, identity phase locking), which
+    takes the plain vocoder's smeared, reverberant colour away.  With ``U[t,k] = phase[t-1,k] + (A[i_{t-1}+1,k] - A[i_{t-1},k])``
+    the plain update (``U[0] = A[0]``), bin ``k`` is a peak of frame ``t`` iff ``mag[t,k] > mag[t,j]``, strictly, for every
+    in-range ``j`` in ``{k-2, k-1, k+1, k+2}`` (a comparison with a NaN is false; a single bin is a peak), ``P(k)`` is the peak
+    nearest to ``k`` (the lower one at equal distance), and ``phase[t,k] = U[t,P(k)] + (A[i_t,k] - A[i_t,P(k)])``: a peak keeps its
+    own update, every other bin the analysis frame's phase relation to its peak.  A frame without a peak (silence, a flat frame)
+    keeps ``U``.  The same integer phase: at ``rate=1`` the result is bit-identical to the plain one, and so is a spectrum without
+    peaks at any rate; the bits do not depend on the segment count, the other rows or the batch.  The paths couple a row's bins,
+    so from the first output frame that reads a NaN or Inf bin **every bin** of every later frame of that row is NaN, that frame
+    included.  The device serves up to 4097 bins (``n_fft=8192``) this way; more raise ``ValueError``.  Any other value of
+    ``phase_lock`` raises ``ValueError``; scaled locking is not provided.
+
     Device tensors take ``torchfx_amd/csrc/phasevocoder.hip`` (``torchfx_ext.phase_vocoder_forward``), which reads the layout
     :func:`stft` returns in place and writes the one :func:`istft` reads; CPU tensors run the same definition in NumPy with the
     same integer phase.  There is no other route.  ``ValueError`` names a bad argument."""
@@ -498,15 +557,18 @@ def phase_vocoder(X: Tensor, rate: float, phase_advance: Tensor | None = None) -
         got = f"{X.dtype} {tuple(X.shape)}" if isinstance(X, Tensor) else type(X).__name__
         raise ValueError(f"phase_vocoder: X must be a complex64 / complex128 tensor [bins, F], [C, bins, F] or [B, C, bins, F], got {got}")
     rate = _vocoder_rate(rate)
+    lock = _vocoder_lock(phase_lock)
     if phase_advance is not None:
         if not isinstance(phase_advance, Tensor) or phase_advance.is_complex() or not phase_advance.dtype.is_floating_point \
                 or tuple(phase_advance.shape) != (X.shape[-2], 1):
             got = tuple(phase_advance.shape) if isinstance(phase_advance, Tensor) else type(phase_advance).__name__
             raise ValueError(f"phase_vocoder: phase_advance must be a real [bins, 1] = [{X.shape[-2]}, 1] tensor, got {got}")
     if X.is_cuda:
+        if lock:
+            _lock_served("phase_vocoder", X.shape[-2], X.dtype)
         with torch.cuda.device(X.device):
-            return E.phase_vocoder_forward(X, rate)
-    return torch.from_numpy(_vocoder_host(X.detach().numpy(), rate))
+            return E.phase_vocoder_forward(X, rate, 0, lock)
+    return torch.from_numpy(_vocoder_host(X.detach().numpy(), rate, lock))
 
 
 def _stretch_geometry(what: str, x: Tensor, n_fft, hop_length, win_length, window, length: int | None = None):
@@ -535,15 +597,19 @@ def _stretch_geometry(what: str, x: Tensor, n_fft, hop_length, win_length, windo
 
 @torch.no_grad()
 def time_stretch(x: Tensor, rate: float, n_fft: int = 2048, hop_length: int | None = None, win_length: int | None = None,
-                 window: Tensor | str = "hann") -> Tensor:
+                 window: Tensor | str = "hann", phase_lock: str | None = None) -> Tensor:
     """Change the tempo of ``x [T]``, ``[C, T]`` or ``[B, C, T]`` by ``rate`` and keep its pitch: ``istft(phase_vocoder(stft(x),
     rate), length=round(T / rate))`` with a centred, reflected :func:`stft` (``hop_length`` defaults to ``n_fft // 4``,
     ``window`` is a tensor or a name of :func:`named_window`).  ``rate > 1`` is faster and shorter.  On a ROCm device with
     ``n_fft`` in 256 ... 4096 that is three kernels and no copy between them: the vocoder reads the buffer the transform wrote
-    and the inverse reads the buffer the vocoder wrote."""
+    and the inverse reads the buffer the vocoder wrote.  ``phase_lock="identity"`` is :func:`phase_vocoder`'s: phases locked to the
+    spectral peaks, the same three kernels with the locked vocoder in the middle."""
     rate = _vocoder_rate(rate, "time_stretch")
+    lock = _vocoder_lock(phase_lock, "time_stretch")
     n_fft, hop, wl, window = _stretch_geometry("time_stretch", x, n_fft, hop_length, win_length, window)
-    Y = phase_vocoder(stft(x, n_fft, hop, wl, window), rate)
+    if lock and x.is_cuda:
+        _lock_served("time_stretch", n_fft // 2 + 1, x.dtype)             # before the transform runs
+    Y = phase_vocoder(stft(x, n_fft, hop, wl, window), rate, phase_lock=phase_lock)
     return istft(Y, n_fft, hop, wl, window, length=int(round(x.shape[-1] / rate)))
 
 
@@ -564,17 +630,18 @@ def _pitch_ratio(n_steps, bins_per_octave) -> tuple[float, int, int]:
 
 @torch.no_grad()
 def pitch_shift(x: Tensor, n_steps: float, bins_per_octave: int = 12, n_fft: int = 2048, hop_length: int | None = None,
-                win_length: int | None = None, window: Tensor | str = "hann") -> Tensor:
+                win_length: int | None = None, window: Tensor | str = "hann", phase_lock: str | None = None) -> Tensor:
     """Shift the pitch of ``x [T]``, ``[C, T]`` or ``[B, C, T]`` by ``n_steps`` steps of ``bins_per_octave`` to the octave
     (12: semitones) and keep length and rate: with ``r = 2 ** (-n_steps / bins_per_octave)``, :func:`time_stretch` by ``r``,
     then ``resample_poly(up, down)`` with ``down / up`` the rational approximation of ``1 / r``
     (``fractions.Fraction(1 / r).limit_denominator(1000)``: that many input samples per output sample, so ``T / r`` samples
-    come back to ``T``), then the result is trimmed or zero-padded to ``T``."""
+    come back to ``T``), then the result is trimmed or zero-padded to ``T``.  ``phase_lock`` is :func:`time_stretch`'s."""
     r, up, down = _pitch_ratio(n_steps, bins_per_octave)
+    _vocoder_lock(phase_lock, "pitch_shift")
     from torchfx_amd.resample import resample_poly
 
     T = x.shape[-1] if isinstance(x, Tensor) and x.dim() else 0
-    y = resample_poly(time_stretch(x, r, n_fft, hop_length, win_length, window), up, down)
+    y = resample_poly(time_stretch(x, r, n_fft, hop_length, win_length, window, phase_lock), up, down)
     if y.shape[-1] >= T:
         return y[..., :T].contiguous()
     return torch.nn.functional.pad(y, (0, T - y.shape[-1]))
@@ -583,12 +650,15 @@ def pitch_shift(x: Tensor, n_steps: float, bins_per_octave: int = 12, n_fft: int
 class TimeStretch(FX):
     """:func:`time_stretch` as an effect: ``wave | TimeStretch(0.8)`` is a ``Wave`` of ``round(T / rate)`` samples at the same
     ``fs``.  A whole-signal effect that changes the length: the planner keeps it as a step of its own, and
-    ``StreamProcessor`` and ``RealtimeProcessor`` refuse it."""
+    ``StreamProcessor`` and ``RealtimeProcessor`` refuse it.  ``phase_lock="identity"`` locks the phases to the spectral peaks
+    (:func:`phase_vocoder`)."""
 
     def __init__(self, rate: float, n_fft: int = 2048, hop_length: int | None = None, win_length: int | None = None,
-                 window: Tensor | str = "hann") -> None:
+                 window: Tensor | str = "hann", phase_lock: str | None = None) -> None:
         super().__init__()
         self.rate = _vocoder_rate(rate, type(self).__name__)
+        _vocoder_lock(phase_lock, type(self).__name__)
+        self.phase_lock = phase_lock
         self.n_fft, self.hop_length, self.win_length = int(n_fft), hop_length, win_length
         if isinstance(window, Tensor):
             self.register_buffer("window", window, persistent=False)    # moves with the effect (.to)
@@ -613,11 +683,19 @@ class TimeStretch(FX):
             return f"torch.stft, phase vocoder in numpy, torch.istft on host -- {x.device.type} tensor"
         rows, rate = max(1, x.numel() // max(1, int(x.shape[-1]))), self._stretch()
         fwd = E.stft_plan_info(n_fft, hop, wl, n, rows, x.dtype)
-        pv = E.phase_vocoder_plan_info(fwd["frames"], n_fft // 2 + 1, rate, rows, x.dtype)
+        lock = _vocoder_lock(self.phase_lock)
+        try:
+            pv = E.phase_vocoder_plan_info(fwd["frames"], n_fft // 2 + 1, rate, rows, x.dtype, 0, lock)
+        except RuntimeError as e:                                        # more bins than the locked route serves
+            return f"refused -- {e}"
         inv = E.istft_plan_info(n_fft, hop, wl, pv["out_frames"], rows, x.dtype, True, int(round(n / rate)))
         cut = "one launch" if pv["launches"] == 1 else f"summary pass + final pass over {pv['segments']} segments of {pv['seg_frames']} frames"
-        steps = ["stft_kernel" if fwd["route"] == "lds" else "torch.stft",
-                 f"phase_vocoder_kernel ({fwd['frames']} -> {pv['out_frames']} frames, {cut}, bin tile {pv['bin_tile']})",
+        if lock:
+            vocoder = (f"phase_lock_kernel (identity phase locking, {fwd['frames']} -> {pv['out_frames']} frames, {cut}, {pv['threads']} lanes x "
+                       f"{pv['bins_per_thread']} bins, {pv['lds_bytes']} B LDS)")
+        else:
+            vocoder = f"phase_vocoder_kernel ({fwd['frames']} -> {pv['out_frames']} frames, {cut}, bin tile {pv['bin_tile']})"
+        steps = ["stft_kernel" if fwd["route"] == "lds" else "torch.stft", vocoder,
                  "istft_kernel" if inv["route"] == "lds" else "torch.istft"]
         copies = "no layout copy between them" if fwd["route"] == inv["route"] == "lds" else "torch's transforms own their layouts"
         return f"native ({' + '.join(steps + self._last_step(x, int(round(n / rate))))}; {copies})"
@@ -626,10 +704,11 @@ class TimeStretch(FX):
         return []
 
     def forward(self, x: Tensor) -> Tensor:
-        return time_stretch(x, self.rate, self.n_fft, self.hop_length, self.win_length, self.window)
+        return time_stretch(x, self.rate, self.n_fft, self.hop_length, self.win_length, self.window, self.phase_lock)
 
     def extra_repr(self) -> str:
-        return f"rate={self.rate}, n_fft={self.n_fft}, hop_length={self.hop_length}, win_length={self.win_length}"
+        lock = f", phase_lock={self.phase_lock!r}" if self.phase_lock is not None else ""
+        return f"rate={self.rate}, n_fft={self.n_fft}, hop_length={self.hop_length}, win_length={self.win_length}{lock}"
 
 
 class PitchShift(TimeStretch):
@@ -638,9 +717,9 @@ class PitchShift(TimeStretch):
     ``RealtimeProcessor`` refuse it."""
 
     def __init__(self, n_steps: float, bins_per_octave: int = 12, n_fft: int = 2048, hop_length: int | None = None,
-                 win_length: int | None = None, window: Tensor | str = "hann") -> None:
+                 win_length: int | None = None, window: Tensor | str = "hann", phase_lock: str | None = None) -> None:
         r, self.up, self.down = _pitch_ratio(n_steps, bins_per_octave)
-        super().__init__(r, n_fft, hop_length, win_length, window)
+        super().__init__(r, n_fft, hop_length, win_length, window, phase_lock)
         self.n_steps, self.bins_per_octave = n_steps, bins_per_octave
 
     def output_length(self, length: int) -> int:
@@ -655,7 +734,8 @@ class PitchShift(TimeStretch):
         return [f"{E.resample_plan_info(length, self.up, self.down, taps, x.dtype)['kernel']} ({self.up} / {self.down})"]
 
     def forward(self, x: Tensor) -> Tensor:
-        return pitch_shift(x, self.n_steps, self.bins_per_octave, self.n_fft, self.hop_length, self.win_length, self.window)
+        return pitch_shift(x, self.n_steps, self.bins_per_octave, self.n_fft, self.hop_length, self.win_length, self.window, self.phase_lock)
 
     def extra_repr(self) -> str:
-        return f"n_steps={self.n_steps}, bins_per_octave={self.bins_per_octave}, n_fft={self.n_fft}, hop_length={self.hop_length}"
+        lock = f", phase_lock={self.phase_lock!r}" if self.phase_lock is not None else ""
+        return f"n_steps={self.n_steps}, bins_per_octave={self.bins_per_octave}, n_fft={self.n_fft}, hop_length={self.hop_length}{lock}"

@@ -692,25 +692,33 @@ def istft_plan_info(n_fft: int, hop: int, win_length: int, frames: int, rows: in
     return info
 
 
-def phase_vocoder_forward(spec: Tensor, rate: float, segments: int = 0) -> Tensor:
+def phase_vocoder_forward(spec: Tensor, rate: float, segments: int = 0, lock: int = 0) -> Tensor:
     """The phase vocoder (``tfx_phase_vocoder_forward``; the definition is :func:`torchfx_amd.spectral.phase_vocoder`'s):
     ``spec [bins, frames]``, ``[C, bins, frames]`` or ``[B, C, bins, frames]`` on the device (complex64 / complex128), ``rate > 0``.
     Returns ``[..., bins, ceil(frames / rate)]``, a transposed view of a contiguous ``[..., Fo, bins]`` buffer: the layout
     :func:`stft_forward` returns, which the kernel also reads in place (any other layout costs one copy into it first), so
     :func:`istft_forward` takes the result without a copy.  ``segments`` cuts each row's output frames (0: the plan's choice,
-    :func:`phase_vocoder_plan_info`): one launch for one segment, two otherwise, to the same bits."""
-    return native.ops().phase_vocoder_forward(spec, float(rate), int(segments))
+    :func:`phase_vocoder_plan_info`): one launch for one segment, two otherwise, to the same bits.  ``lock=1`` takes the identity
+    phase-locked route (``tfx_phase_vocoder_locked_forward``; at most 4097 bins), ``lock=0`` the plain one."""
+    return native.ops().phase_vocoder_forward(spec, float(rate), int(segments), int(lock))
 
 
 def phase_vocoder_plan_info(frames: int, bins: int, rate: float, rows: int = 1, dtype: torch.dtype = torch.float32,
-                            segments: int = 0) -> dict:
+                            segments: int = 0, lock: int = 0) -> dict:
     """What :func:`phase_vocoder_forward` does for ``rows`` spectra of ``frames`` frames of ``bins`` bins
     (``tfx_phase_vocoder_plan_info``; host-only, same checks on the sizes): ``out_frames`` (``ceil(frames / rate)``), ``bin_tile``
     (the bins of a workgroup, one lane each), the ``segments`` it takes for the request (0: chosen from the sizes, 1 when rows and
     bin tiles alone fill the chip), ``seg_frames`` (output frames per segment; the last may hold fewer), ``launches`` (1 or 2),
     ``workgroups`` of the writing launch and ``scratch_bytes`` (the summaries between the launches; 0 for one segment).
-    ``dtype`` is the real or the complex one."""
+    ``dtype`` is the real or the complex one.  With ``lock=1`` (``tfx_phase_vocoder_locked_plan_info``) a workgroup owns all bins
+    of a (row, segment) and the answer is ``out_frames``, ``threads``, ``bins_per_thread``, ``lds_bytes`` (of a workgroup),
+    ``segments``, ``seg_frames``, ``launches``, ``workgroups`` (``rows * segments``) and ``scratch_bytes``."""
     dtype = {torch.complex64: torch.float32, torch.complex128: torch.float64}.get(dtype, dtype)
+    if lock not in (0, 1):
+        raise ValueError(f"phase_vocoder_plan_info: lock must be 0 or 1, got {lock!r}")
+    if lock:
+        return _query(L.load().tfx_phase_vocoder_locked_plan_info, (int(rows), int(frames), int(bins), float(rate), _dt(dtype), int(segments)),
+                      "out_frames threads bins_per_thread lds_bytes segments seg_frames launches workgroups scratch_bytes")
     return _query(L.load().tfx_phase_vocoder_plan_info, (int(rows), int(frames), int(bins), float(rate), _dt(dtype), int(segments)),
                   "out_frames bin_tile segments seg_frames launches workgroups scratch_bytes")
 

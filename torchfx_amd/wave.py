@@ -238,7 +238,7 @@ def _member_key(m: nn.Module, guard: list) -> tuple:
     elif isinstance(m, ZeroPhase):
         k += (m.padtype, m.padlen)
     elif isinstance(m, TimeStretch):
-        k += (m.rate, getattr(m, "up", 0), getattr(m, "down", 0), m.n_fft, m.hop_length, m.win_length,
+        k += (m.rate, getattr(m, "up", 0), getattr(m, "down", 0), m.n_fft, m.hop_length, m.win_length, m.phase_lock,
               window_key(m.window) if isinstance(m.window, Tensor) else m.window)
     elif isinstance(m, LoudnessNormalize):
         k += (m.target, m.channel_weights, m.fs)
@@ -805,20 +805,20 @@ class Wave:
         return self | Resample(new_fs, window=window)
 
     def time_stretch(self, rate: float, n_fft: int = 2048, hop_length: int | None = None, win_length: int | None = None,
-                     window="hann") -> "Wave":
+                     window="hann", phase_lock: str | None = None) -> "Wave":
         """``self | TimeStretch(rate, ...)``: the signal ``rate`` times as fast at the same pitch and ``fs``, ``round(T / rate)``
-        samples long (:func:`torchfx_amd.spectral.time_stretch`)."""
+        samples long (:func:`torchfx_amd.spectral.time_stretch`; ``phase_lock="identity"`` locks each bin's phase to its peak)."""
         from torchfx_amd.spectral import TimeStretch
 
-        return self | TimeStretch(rate, n_fft, hop_length, win_length, window)
+        return self | TimeStretch(rate, n_fft, hop_length, win_length, window, phase_lock)
 
     def pitch_shift(self, n_steps: float, bins_per_octave: int = 12, n_fft: int = 2048, hop_length: int | None = None,
-                    win_length: int | None = None, window="hann") -> "Wave":
+                    win_length: int | None = None, window="hann", phase_lock: str | None = None) -> "Wave":
         """``self | PitchShift(n_steps, ...)``: the signal ``n_steps`` steps higher at the same length and ``fs``
-        (:func:`torchfx_amd.spectral.pitch_shift`)."""
+        (:func:`torchfx_amd.spectral.pitch_shift`; ``phase_lock="identity"`` locks each bin's phase to its peak)."""
         from torchfx_amd.spectral import PitchShift
 
-        return self | PitchShift(n_steps, bins_per_octave, n_fft, hop_length, win_length, window)
+        return self | PitchShift(n_steps, bins_per_octave, n_fft, hop_length, win_length, window, phase_lock)
 
     # ------------------------------------------------------------------ files
     _SUBTYPE_BY_ENCODING = {"PCM_S": lambda b: f"PCM_{b}", "PCM_U": lambda b: "PCM_U8" if b == 8 else f"PCM_{b}",
