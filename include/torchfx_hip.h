@@ -681,6 +681,37 @@ int tfx_modulated_delay_stream_forward(const void *x, void *y, int dtype, int64_
  * (ceil(batch / 4)); the grid is tiles * channels * batch_groups workgroups */
 int tfx_modulated_delay_plan_info(int64_t batch, int64_t channels, int64_t T, const double *voices_host, int64_t V, int interp,
                                   int64_t *tile, int64_t *tiles, int64_t *history, int64_t *batch_items, int64_t *batch_groups);
+/* ---------------------------------------------------------------------------
+ * tfx_modulated_delay_feedback_forward -- the same line with feedback (regeneration), the recursive form of Flanger and Chorus:
+ * the voices read the line w, not the signal, and their sum is fed back into it.  Arguments, steps 1 to 4 (off, a, l, d = i + f)
+ * and the interpolation weights are tfx_modulated_delay_forward's; every intermediate in float64 for both dtypes:
+ *   5. wd_v = the interpolant of step 5 through w[n-i+1], w[n-i], w[n-i-1], w[n-i-2] (linear: w[n-i], w[n-i-1]); w[m] = 0 for m < 0
+ *   6. r[n] = sum_v g_v wd_v, summed in voice order
+ *   7. w[n] = x[n] + feedback r[n]  -- the line, float64, never rounded to dtype
+ *   8. y[n] = dtype(dry x[n] + r[n])
+ * feedback = 0 is tfx_modulated_delay_forward itself (w = x), bit for bit.  Rules in addition to that entry's, for feedback != 0:
+ *   - feedback finite, and |feedback| * sum_v |g_v| * L < 1 with L = 1 (linear) or 1.25 (cubic, the interpolant's Lebesgue
+ *     constant): the sufficient condition for a bounded line;
+ *   - B = floor(min_v(base_v - depth_v)) - c >= 1, c = 1 (cubic) or 0 (linear): the newest line sample an output reads is older
+ *     than the output;
+ *   - H + min(B, 64) <= 8192 with H = max_v floor(base_v + depth_v) + 2: the line is a ring in LDS of 64 KiB at most (two
+ *     workgroups stay resident in a gfx950 CU's 160 KiB).  A longer line with feedback is refused.
+ * One launch: the B outputs of a block [k B, (k + 1) B) depend only on samples before the block, so they are computed in
+ * parallel and a row is a chain of ceil(T / B) steps.  A workgroup is one wave that owns its rows from start to end (nothing
+ * crosses between workgroups); B <= 32 packs floor(64 / B) batch items of one channel index into the wave, B > 64 sweeps the
+ * block in sub-blocks of 64.  B, the packing and the batch only schedule the work: a row's bits depend on its own samples, its
+ * channel index and the position alone.  At f = 0 the interpolants return w[n-i] exactly.  A non-finite x[m] stays in its own
+ * row, reaches no output before m and may stay in the line from there on.  There is no stream entry: the history of the recursive line is its own output.
+ * ------------------------------------------------------------------------- */
+int tfx_modulated_delay_feedback_forward(const void *x, void *y, int dtype, int64_t batch, int64_t channels, int64_t T,
+                                         const double *voices_host, int64_t V, double spread, double dry, int shape, int interp,
+                                         int64_t position, double feedback, tfx_stream_t stream);
+/* what the entry above does (host-only, same checks, feedback != 0): the block B, the rows (batch items) a wave owns, the ring's
+ * samples per row, the LDS bytes of a workgroup, the workgroups of the launch (channels * ceil(batch / rows_per_wave)) and the
+ * dependent steps per row (ceil(T / B)) */
+int tfx_modulated_delay_feedback_plan_info(int64_t batch, int64_t channels, int64_t T, const double *voices_host, int64_t V, int interp,
+                                           double feedback, int64_t *block, int64_t *rows_per_wave, int64_t *ring, int64_t *lds_bytes,
+                                           int64_t *workgroups, int64_t *steps);
 
 /* ---------------------------------------------------------------------------
  * tfx_freeverb_forward -- Freeverb (Jezar at Dreampoint, public domain), the Schroeder-Moorer room reverb: per *bank* (one

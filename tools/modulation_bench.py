@@ -17,6 +17,14 @@ Gate: (a) agrees with (c) within the bound of tests/modulation_reference.py (flo
 and the slowest repeat of (a) is faster than the fastest of (c).  (a) / (b) is recorded, not gated.
 
     python tools/modulation_bench.py --out profiles/modulation_bench.txt
+
+``--feedback`` times the recursive line instead (modulated_delay_feedback_kernel): ``Flanger(feedback=0.7)`` and
+``Chorus(feedback=0.4)`` next to the plain effects, one ``gain_forward`` pass and ``Freeverb()`` on [32, 2, 2 880 000] and
+[1, 2, 28 800 000] float32, device events around one call, minimum of 7.  Nothing is gated: the time of a recursion follows the
+dependent steps per row (``ceil(T / B)``), not the bytes, and the report gives the time per step and per item (a block or, for
+B > 64, a sub-block of 64) so that it can be set against the LFO arithmetic, the LDS round trip and the stores.
+
+    python tools/modulation_bench.py --feedback --out profiles/modulation_feedback_bench.txt
 """
 from __future__ import annotations
 
@@ -100,13 +108,58 @@ def excess_over_bound(got, ref, x, P):
     return worst, dev
 
 
+def write(lines, out) -> None:
+    text = "\n".join(lines)
+    print(text, flush=True)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(text + "\n")
+
+
+def feedback_main(args) -> None:
+    from torchfx_amd import Chorus, Flanger, Freeverb, torchfx_ext as E
+
+    repeats = 7
+    effects = [("Flanger(feedback=0.7)", Flanger(fs=FS, feedback=0.7), Flanger(fs=FS)),
+               ("Chorus(feedback=0.4)", Chorus(fs=FS, feedback=0.4), Chorus(fs=FS))]
+    lines = [f"Feedback (regeneration) at {FS} Hz, float32 on {torch.cuda.get_device_name(0)}; device events around one call, min / "
+             f"median / max of {repeats} alternating repeats, ms.  No time is required of the recursive line."]
+    fmt = lambda t: f"{t[0]:.3f} / {t[1]:.3f} / {t[2]:.3f}"          # noqa: E731
+    for B, C, T in SHAPES[:2]:
+        x = signal(B, C, T)
+        rev = Freeverb(fs=FS)
+        g, r = time_alternating([lambda: E.gain_forward(x, 0.5), lambda: rev(x)], repeats)
+        lines.append(f"{B} x {C} x {T}: gain_forward {fmt(g)}   Freeverb() {fmt(r)}")
+        for name, fb, plain in effects:
+            P = fb.params(torch.float32)
+            info = E.modulated_delay_feedback_plan_info(T, P.table, P.feedback, B, C, P.interpolation)
+            a, b = time_alternating([lambda: fb(x), lambda: plain(x)], repeats)
+            items = info["steps"] * math.ceil(info["block"] / 64)
+            row = dict(effect=name, batch=B, channels=C, length=T, voices=len(P.table), **info, feedback_ms=a, plain_ms=b, gain_ms=g,
+                       freeverb_ms=r, us_per_step=a[0] * 1e3 / info["steps"], us_per_item=a[0] * 1e3 / items,
+                       ns_per_item_and_voice=a[0] * 1e6 / items / len(P.table))
+            lines.append(json.dumps(row))
+            lines.append(f"  {name}: block {info['block']}, {info['rows_per_wave']} row(s) per wave, ring {info['ring']}, "
+                         f"{info['workgroups']} workgroup(s) of {info['steps']} step(s): {fmt(a)}   plain {fmt(b)}   "
+                         f"{a[0] * 1e3 / info['steps']:.3f} us per step, {a[0] * 1e3 / items:.3f} us per item of <= 64 samples, "
+                         f"{a[0] * 1e6 / items / len(P.table):.0f} ns per item and voice   over plain {a[0] / b[0]:.1f}x, over "
+                         f"gain_forward {a[0] / g[0]:.1f}x, over Freeverb() {a[0] / r[0]:.2f}x")
+        del x
+        torch.cuda.empty_cache()
+    write(lines, args.out)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the report here")
     ap.add_argument("--repeats", type=int, default=15)
+    ap.add_argument("--feedback", action="store_true", help="time the recursive line (Flanger / Chorus with feedback) instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("modulation_bench needs a ROCm device")
+    if args.feedback:
+        return feedback_main(args)
     from torchfx_amd import Chorus, torchfx_ext as E
 
     eff = Chorus(fs=FS)
@@ -147,12 +200,7 @@ def main() -> None:
         torch.cuda.empty_cache()
     lines.append("GATE: " + ("PASS" if ok else "FAIL") + " -- (a) agrees with (c) within the bound and the slowest repeat of (a) is faster "
                  "than the fastest of (c), on every shape")
-    text = "\n".join(lines)
-    print(text, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    write(lines, args.out)
     if not ok:
         raise SystemExit(1)
 

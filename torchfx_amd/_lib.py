@@ -95,6 +95,8 @@ SIGNATURES = {
     "tfx_modulated_delay_stream_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _dbl, _dbl, _int, _int, _vp, _vp, _vp,
                                                   _vp, _vp]),
     "tfx_modulated_delay_plan_info": (_int, [_i64, _i64, _i64, _vp, _i64, _int] + [ctypes.POINTER(_i64)] * 5),
+    "tfx_modulated_delay_feedback_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _dbl, _dbl, _int, _int, _i64, _dbl, _vp]),
+    "tfx_modulated_delay_feedback_plan_info": (_int, [_i64, _i64, _i64, _vp, _i64, _int, _dbl] + [ctypes.POINTER(_i64)] * 6),
     "tfx_freeverb_forward": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64] + [_dbl] * 7 + [_vp, _vp, _vp, _vp]),
     "tfx_freeverb_plan_info": (_int, [_i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _dbl, ctypes.POINTER(_i64), ctypes.POINTER(_int)]
                                + [ctypes.POINTER(_i64)] * 3),

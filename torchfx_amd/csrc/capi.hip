@@ -742,6 +742,27 @@ int tfx_modulated_delay_plan_info(int64_t batch, int64_t channels, int64_t T, co
     TFX_API_END
 }
 
+int tfx_modulated_delay_feedback_forward(const void *x, void *y, int dtype, int64_t batch, int64_t channels, int64_t T,
+                                         const double *voices_host, int64_t V, double spread, double dry, int shape, int interp,
+                                         int64_t position, double feedback, tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    modulated_delay_feedback_forward(x, y, dtype, batch, channels, T, voices_host, V, spread, dry, shape, interp, position, feedback,
+                                     (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_modulated_delay_feedback_plan_info(int64_t batch, int64_t channels, int64_t T, const double *voices_host, int64_t V, int interp,
+                                           double feedback, int64_t *block, int64_t *rows_per_wave, int64_t *ring, int64_t *lds_bytes,
+                                           int64_t *workgroups, int64_t *steps)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(block && rows_per_wave && ring && lds_bytes && workgroups && steps, "modulated_delay_feedback_plan_info: null output");
+    modulated_delay_feedback_plan_info(batch, channels, T, voices_host, V, interp, feedback, block, rows_per_wave, ring, lds_bytes,
+                                       workgroups, steps);
+    TFX_API_END
+}
+
 int tfx_freeverb_forward(const void *x, void *y, int dtype, int64_t batch, int64_t channels, int64_t T, int64_t tail,
                          const int64_t *comb_delays_host, int64_t NC, const int64_t *allpass_delays_host, int64_t NA, double feedback,
                          double damp, double allpass_gain, double input_gain, double dry_gain, double wet1, double wet2,

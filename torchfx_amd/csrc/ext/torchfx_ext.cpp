@@ -1010,16 +1010,31 @@ ModInputs mod_inputs(const Tensor &x_in, const Tensor &voices, int64_t shape, in
     return in;
 }
 
+// feedback == 0: the feed-forward entry; anything else the recursive line (tfx_modulated_delay_feedback_forward), whose rules are
+// checked by its plan before the output is allocated
 Tensor modulated_delay_op(const Tensor &x_in, const Tensor &voices, double spread, double dry, int64_t shape, int64_t interp,
-                          int64_t position)
+                          int64_t position, double feedback)
 {
     const char *what = "modulated_delay_forward";
     const ModInputs in = mod_inputs(x_in, voices, shape, interp, what);
+    if (feedback != 0.0) {
+        int64_t info[6];
+        check_rc(tfx_modulated_delay_feedback_plan_info(in.batch, in.channels, in.T, in.voices.data_ptr<double>(), in.V, (int)interp,
+                                                        feedback, info, info + 1, info + 2, info + 3, info + 4, info + 5),
+                 what);
+    }
     Tensor y = at::empty_like(in.x);
     c10::hip::HIPGuard guard(in.x.get_device());
-    check_rc(tfx_modulated_delay_forward(in.x.data_ptr(), y.data_ptr(), in.dt, in.batch, in.channels, in.T, in.voices.data_ptr<double>(),
-                                         in.V, spread, dry, (int)shape, (int)interp, position, stream_of(in.x)),
-             what);
+    if (feedback == 0.0)
+        check_rc(tfx_modulated_delay_forward(in.x.data_ptr(), y.data_ptr(), in.dt, in.batch, in.channels, in.T,
+                                             in.voices.data_ptr<double>(), in.V, spread, dry, (int)shape, (int)interp, position,
+                                             stream_of(in.x)),
+                 what);
+    else
+        check_rc(tfx_modulated_delay_feedback_forward(in.x.data_ptr(), y.data_ptr(), in.dt, in.batch, in.channels, in.T,
+                                                      in.voices.data_ptr<double>(), in.V, spread, dry, (int)shape, (int)interp, position,
+                                                      feedback, stream_of(in.x)),
+                 what);
     return y;
 }
 
@@ -1721,9 +1736,9 @@ TORCH_LIBRARY(torchfx_hip, m)
     reg_op(m, "interleave_forward(Tensor x, int frame_base=0, int frames=-1) -> Tensor", interleave_op);
     reg_op(m, "compressor_forward(Tensor x, float th, float s, float w, float alpha_a, float alpha_r, float makeup_db, int channels, "
               "Tensor? state, bool return_gain, int segments=0) -> (Tensor, Tensor, Tensor)", compressor_op, compressor_meta);
-    reg_op(m, "modulated_delay_forward(Tensor x, Tensor voices_cpu, float spread, float dry, int shape, int interp, int position=0) "
-              "-> Tensor", modulated_delay_op,
-           [](const Tensor &x, const Tensor &, double, double, int64_t, int64_t, int64_t) { return at::empty_like(x); });
+    reg_op(m, "modulated_delay_forward(Tensor x, Tensor voices_cpu, float spread, float dry, int shape, int interp, int position=0, "
+              "float feedback=0.0) -> Tensor", modulated_delay_op,
+           [](const Tensor &x, const Tensor &, double, double, int64_t, int64_t, int64_t, double) { return at::empty_like(x); });
     reg_op(m, "modulated_delay_stream_forward(Tensor x, Tensor? hist, Tensor? pos, Tensor voices_cpu, float spread, float dry, "
               "int shape, int interp) -> (Tensor, Tensor, Tensor)", modulated_delay_stream_op, modulated_delay_stream_meta);
     reg_op(m, "freeverb_forward(Tensor x, int[] comb_delays, int[] allpass_delays, float feedback, float damp, float allpass_gain, "

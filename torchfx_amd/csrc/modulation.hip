@@ -17,6 +17,12 @@
 // file: t = double(n) * inc must stay one IEEE multiplication (a fused n * inc - floor(t) moves the LFO phase by up to 2e-5
 // samples of delay at n = 2^40), and with it off every expression below rounds exactly as written, on the device and the host.
 // Plain vector stores only; nothing crosses between workgroups.
+//
+// With feedback (regeneration) the voices read the line w[n] = x[n] + feedback * r[n] instead of the signal, which makes the
+// effect a recursion whose memory is the moving delay.  That is a kernel of its own further down
+// (modulated_delay_feedback_kernel: one wave per row, the line as a ring in LDS, blocks of B = floor(min(base - depth)) - c samples
+// in parallel and in order); it shares mod_delay_at, mod_weights and mod_tap with the feed-forward kernels, and feedback == 0
+// never reaches it.
 #include "common.h"
 #include "lfo.h"
 #include "plan_cache.h"
@@ -91,13 +97,21 @@ template <bool CUBIC> __device__ __forceinline__ void mod_weights(double f, doub
     }
 }
 
+// the interpolant over w(m+1), w(m), w(m-1), w(m-2) with mod_weights' weights (linear reads x0 and x1 alone); the one text of the
+// tap for the feed-forward kernels, which read the signal, and the feedback kernel, which reads its line
+template <bool CUBIC> __device__ __forceinline__ double mod_tap(double xm, double x0, double x1, double x2, const double (&w)[4])
+{
+    if (!CUBIC) return x0 + w[2] * (x1 - x0);
+    return w[0] * xm + w[1] * x0 + w[2] * x1 + w[3] * x2;
+}
+
 template <typename T, bool CUBIC>
-__device__ __forceinline__ double mod_tap(const T *xr, const T *hr, int64_t T_, int64_t H, int64_t m, const double (&w)[4])
+__device__ __forceinline__ double mod_tap_signal(const T *xr, const T *hr, int64_t T_, int64_t H, int64_t m, const double (&w)[4])
 {
     const double x0 = mod_read(xr, hr, T_, H, m), x1 = mod_read(xr, hr, T_, H, m - 1);
-    if (!CUBIC) return x0 + w[2] * (x1 - x0);
+    if (!CUBIC) return mod_tap<false>(0.0, x0, x1, 0.0, w);
     const double xm = mod_read(xr, hr, T_, H, m + 1), x2 = mod_read(xr, hr, T_, H, m - 2);
-    return w[0] * xm + w[1] * x0 + w[2] * x1 + w[3] * x2;
+    return mod_tap<true>(xm, x0, x1, x2, w);
 }
 
 // output workgroup `lid` of the launch: (tile, channel index, batch group), pos = the absolute position of sample 0
@@ -128,7 +142,7 @@ __device__ __forceinline__ void mod_tile(const ModArgs<T> &p, int64_t lid, int64
                 if (b < nb) {
                     const int64_t row = row0 + b * p.channels;
                     const T *hr = p.hist_in ? p.hist_in + row * p.H : nullptr;
-                    acc[b] = acc[b] + g * mod_tap<T, CUBIC>(p.x + row * p.T_, hr, p.T_, p.H, j - i, w);
+                    acc[b] = acc[b] + g * mod_tap_signal<T, CUBIC>(p.x + row * p.T_, hr, p.T_, p.H, j - i, w);
                 }
             }
         }
@@ -168,9 +182,177 @@ __global__ void __launch_bounds__(MD_THREADS) modulated_delay_stream_kernel(cons
     }
 }
 
+// ---- feedback (regeneration): the line holds w[n] = x[n] + feedback * r[n], r[n] = sum_v g_v * w(n - d_v[n]) -----------------
+// y[n] = dtype(dry * x[n] + r[n]).  Output n reads the line no later than n - i_min + c (i_min = floor(min_v(base_v - depth_v)),
+// c = 1 for the cubic interpolant's w[m+1], else 0), so the B = i_min - c samples of a *block* [k B, (k + 1) B) depend only on
+// samples before the block: they are computed in parallel and the blocks run in order, ceil(T / B) dependent steps per row.
+//
+// Ownership: a workgroup is ONE wave and owns its rows from the first sample to the last; a row's line is a float64 ring in LDS
+// of R = 2^k >= H + min(B, 64) samples.  No barrier, no atomics, nothing crosses between workgroups; LDS operations of one wave
+// execute in order, so the write of a block is seen by the reads of the next (wave_sync only keeps the compiler from moving
+// them).  The ring starts as zeros and needs no bounds check: a read of m < 0 (m >= n - H) lands on the slot of m + R >=
+// n + min(B, 64), which no item up to and including the current one has written, and a slot written at m is overwritten at m + R
+// only, past every reader of m.
+// Lanes: a row takes min(B, 64) lanes.  B <= 32 packs floor(64 / B) rows of one channel index (consecutive batch items) into the
+// wave, lane = slot * B + sample, so the serial small-B case does not idle the wave; the rows' rings are R + B apart, which puts
+// lane l of a step on LDS bank pair l.  B > 64 sweeps the block in sub-blocks of 64 with no dependency between them.  One *item*
+// of the loop below is one (block, sub-block).
+// Off the chain: the loop is software-pipelined by hand.  Phase 1 of an item only issues its LDS reads (2 or 4 per voice); phase
+// 2 computes the NEXT item's LFO (the float64 sinpi is the bulk of the arithmetic), (i, f), weights and ring slot and issues the
+// global load of x for the item MDF_AHEAD ahead; phase 3 waits for the reads and is all that depends on the line: the
+// multiply-adds of mod_tap, w = x + feedback * r, one LDS write, and the store of y.  The three phases are three runs of
+// per-voice basic blocks in that order, which the compiler does not reorder.  The loop is unrolled MDF_AHEAD times so that the
+// x queue and the two prep sets are indexed statically (a register copy of a load in flight would wait for it).
+// Bits: B, the packing and the batch only schedule the work; a sample's expressions are mod_delay_at, mod_weights and mod_tap at
+// its own (n, v, c) whatever they are.
+constexpr int MDF_LANES = 64;
+constexpr int MDF_AHEAD = 4;                               // items the x loads run ahead of the line
+static_assert(MDF_AHEAD % 2 == 0, "the two prep sets alternate over the unrolled loop");
+constexpr int64_t MDF_MAX_LDS = 64 << 10;                  // bytes per workgroup: two workgroups stay resident in gfx950's 160 KiB
+constexpr int64_t MDF_MAX_RING = MDF_MAX_LDS / 8;          // 8192 samples: the longest ring, H + min(B, 64) <= 8192
+
+template <typename T> struct ModFbArgs {
+    const T *x;
+    T *y;
+    int64_t pos, T_, batch, channels;
+    int B, lanes, rpw;          // block; lanes per row = min(B, 64); rows per wave
+    int mask, stride;           // R - 1; doubles between the rings of a wave's rows
+    int lds_doubles;
+    int V;
+    double dry, fb;
+    const ModVoice *voice;      // DEVICE [V]
+    const double *off;          // DEVICE [channels, V]
+};
+
+struct ModFbPrep {
+    int m;                      // (n - i) & mask: the ring slot of w[n - i]
+    double w[4];
+};
+
+struct ModFbItem {              // a (block, sub-block): the samples n0 + s0 + [0, 64) below n0 + B
+    int64_t n0;
+    int s0;
+};
+
+__device__ __forceinline__ void mod_fb_advance(ModFbItem &it, int B, int64_t T_)
+{
+    it.s0 += MDF_LANES;
+    if (it.s0 >= B || it.n0 + it.s0 >= T_) {
+        it.n0 += B;
+        it.s0 = 0;
+    }
+}
+
+__device__ __forceinline__ void mod_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <typename T, bool CUBIC, bool TRI>
+__global__ void __launch_bounds__(MDF_LANES) modulated_delay_feedback_kernel(const ModFbArgs<T> p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char mdf_lds_raw[];
+    double *lds = reinterpret_cast<double *>(mdf_lds_raw);
+    const int lane = threadIdx.x;
+    const int q = lane / p.lanes, k = lane - q * p.lanes;                 // row slot of the wave, sample of the (sub-)block
+    const int64_t c = (int64_t)blockIdx.x % p.channels, b = ((int64_t)blockIdx.x / p.channels) * p.rpw + q;
+    const bool row_ok = q < p.rpw && b < p.batch;                         // idle lanes touch no memory
+    const int64_t row = row_ok ? b * p.channels + c : 0;
+    const T *__restrict__ xr = p.x + row * p.T_;
+    T *__restrict__ yr = p.y + row * p.T_;
+    double *ring = lds + (row_ok ? q : 0) * p.stride;
+    const int mask = p.mask, B = p.B, V = p.V;
+    const int64_t T_ = p.T_;
+    const double dry = p.dry, fb = p.fb;
+
+    for (int s = lane; s < p.lds_doubles; s += MDF_LANES) lds[s] = 0.0;
+    ModVoice vc[MD_MAXV];
+    double off[MD_MAXV];
+#pragma unroll
+    for (int v = 0; v < MD_MAXV; ++v) {
+        vc[v] = p.voice[v < V ? v : 0];
+        off[v] = p.off[c * V + (v < V ? v : 0)];
+    }
+    mod_wave_sync();
+
+    ModFbItem cur{0, 0}, xit{0, 0};
+    T xq[MDF_AHEAD];
+    ModFbPrep P[2][MD_MAXV];
+    // the next item's (i, f, weights) per voice; lanes past the block or the row compute on a harmless n and are not used
+    auto prep = [&](const ModFbItem &it, ModFbPrep (&o)[MD_MAXV]) __attribute__((always_inline)) {
+        const int64_t n = it.n0 + it.s0 + k;
+#pragma unroll
+        for (int v = 0; v < MD_MAXV; ++v) {
+            if (v < V) {
+                int64_t i;
+                double f;
+                mod_delay_at<TRI>(p.pos + n, vc[v], off[v], i, f);
+                mod_weights<CUBIC>(f, o[v].w);
+                o[v].m = (int)((n - i) & (int64_t)mask);
+            }
+        }
+    };
+    auto active = [&](const ModFbItem &it) __attribute__((always_inline)) { return row_ok && it.s0 + k < B && it.n0 + it.s0 + k < T_; };
+    auto fetch = [&](ModFbItem &it) __attribute__((always_inline)) {
+        const T v = (it.n0 < T_ && active(it)) ? xr[it.n0 + it.s0 + k] : (T)0;
+        mod_fb_advance(it, B, T_);
+        return v;
+    };
+#pragma unroll
+    for (int j = 0; j < MDF_AHEAD; ++j) xq[j] = fetch(xit);
+    prep(cur, P[0]);
+
+    for (;;) {
+#pragma unroll
+        for (int j = 0; j < MDF_AHEAD; ++j) {
+            if (cur.n0 >= T_) return;
+            const ModFbPrep(&pc)[MD_MAXV] = P[j & 1];
+            const bool act = active(cur);
+            const int64_t n = cur.n0 + cur.s0 + k;
+            // phase 1: the line's reads of this item
+            double wm[MD_MAXV], w0[MD_MAXV], w1[MD_MAXV], w2[MD_MAXV];
+#pragma unroll
+            for (int v = 0; v < MD_MAXV; ++v) {
+                if (v < V) {
+                    w0[v] = ring[pc[v].m];
+                    w1[v] = ring[(pc[v].m - 1) & mask];
+                    if (CUBIC) {
+                        wm[v] = ring[(pc[v].m + 1) & mask];
+                        w2[v] = ring[(pc[v].m - 2) & mask];
+                    } else {
+                        wm[v] = w2[v] = 0.0;
+                    }
+                }
+            }
+            // phase 2: off the chain -- the next item's delays and weights, the x load MDF_AHEAD items ahead
+            const double xn = (double)xq[j];
+            ModFbItem nxt = cur;
+            mod_fb_advance(nxt, B, T_);
+            prep(nxt, P[(j + 1) & 1]);
+            xq[j] = fetch(xit);
+            // phase 3: the chain
+            double r = 0.0;
+#pragma unroll
+            for (int v = 0; v < MD_MAXV; ++v) {
+                if (v < V) {
+                    const double t = vc[v].gain * mod_tap<CUBIC>(wm[v], w0[v], w1[v], w2[v], pc[v].w);
+                    r = v == 0 ? t : r + t;
+                }
+            }
+            if (act) ring[(int)(n & (int64_t)mask)] = xn + fb * r;
+            mod_wave_sync();
+            if (act) yr[n] = (T)(dry * xn + r);
+            cur = nxt;
+        }
+    }
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------------
 struct ModPlan {
     int64_t rows, tiles, bgroups, n_out, H;
+    double i_min, gain_abs;     // floor(min_v(base_v - depth_v)); sum_v |gain_v|
 };
 
 // sizes and the voice table (host-only): every argument error of both entries that does not need a pointer
@@ -189,6 +371,7 @@ static ModPlan mod_plan(const char *what, int dtype, int64_t batch, int64_t chan
     TFX_CHECK(std::isfinite(dry), "%s: dry must be finite, got %g", what, dry);
     const double lowest = interp == TFX_INTERP_CUBIC ? 1.0 : 0.0;
     ModPlan pl{};
+    pl.i_min = (double)MD_MAX_REACH;
     for (int64_t v = 0; v < V; ++v) {
         const double base = voices[5 * v], depth = voices[5 * v + 1], inc = voices[5 * v + 2], phase = voices[5 * v + 3],
                      gain = voices[5 * v + 4];
@@ -204,6 +387,8 @@ static ModPlan mod_plan(const char *what, int dtype, int64_t batch, int64_t chan
         TFX_CHECK(std::isfinite(phase), "%s: voice %lld: the phase must be finite, got %g", what, (long long)v, phase);
         TFX_CHECK(std::isfinite(gain), "%s: voice %lld: the gain must be finite, got %g", what, (long long)v, gain);
         pl.H = std::max(pl.H, (int64_t)std::floor(base + depth) + 2);
+        pl.i_min = std::min(pl.i_min, std::floor(base - depth));
+        pl.gain_abs += std::fabs(gain);
     }
     pl.rows = batch * channels;
     pl.tiles = ceil_div(T, MD_TILE);
@@ -327,6 +512,104 @@ void modulated_delay_stream_forward(const void *x, void *y, int dtype, int64_t b
     else
         mod_stream<double>(x, y, pl, batch, channels, T, voices_host, V, spread, dry, shape, interp, hist_in, hist_out, pos_in, pos_out,
                            stream);
+}
+
+// ---- feedback, host side ---------------------------------------------------------------------------------------------------
+struct ModFbPlan {
+    int64_t B, rpw, ring, lds, wgs, steps;
+    int lanes, stride;
+};
+
+// the rules feedback adds to mod_plan's, and the geometry of modulated_delay_feedback_kernel
+static ModFbPlan mod_fb_plan(const char *what, const ModPlan &pl, int64_t batch, int64_t channels, int64_t T, int interp, double feedback)
+{
+    const bool cubic = interp == TFX_INTERP_CUBIC;
+    TFX_CHECK(std::isfinite(feedback), "%s: feedback must be finite, got %g", what, feedback);
+    TFX_CHECK(feedback != 0.0, "%s: feedback must not be 0 here (the feed-forward line is modulated_delay_forward's)", what);
+    const double lebesgue = cubic ? 1.25 : 1.0, rho = std::fabs(feedback) * pl.gain_abs * lebesgue;
+    TFX_CHECK(rho < 1.0, "%s: feedback: the loop is not stable, |feedback| * sum |gain| * %g = %g must be < 1 (%s interpolation)", what,
+              lebesgue, rho, cubic ? "cubic" : "linear");
+    const double block = pl.i_min - (cubic ? 1.0 : 0.0);
+    TFX_CHECK(block >= 1.0,
+              "%s: with feedback floor(delay - depth) must be >= %d sample(s) for %s interpolation (the line is read at least one "
+              "sample back), got %g",
+              what, cubic ? 2 : 1, cubic ? "cubic" : "linear", pl.i_min);
+    ModFbPlan f{};
+    f.B = (int64_t)block;
+    f.lanes = (int)std::min<int64_t>(f.B, MDF_LANES);
+    TFX_CHECK(pl.H + f.lanes <= MDF_MAX_RING,
+              "%s: with feedback the line must fit the LDS ring: floor(delay + depth) + 2 + min(block, 64) = %lld samples, at most %lld",
+              what, (long long)(pl.H + f.lanes), (long long)MDF_MAX_RING);
+    f.ring = 1;
+    while (f.ring < pl.H + f.lanes) f.ring *= 2;
+    const int64_t packed = f.B <= MDF_LANES / 2 ? MDF_LANES / f.B : 1;
+    f.stride = (int)(packed > 1 ? f.ring + f.B : f.ring);                // rings B apart in banks: lane l of a step on bank pair l
+    f.rpw = std::max<int64_t>(1, std::min(packed, MDF_MAX_RING / f.stride));
+    if (f.rpw == 1) f.stride = (int)f.ring;
+    f.lds = f.rpw * f.stride * 8;
+    f.wgs = channels * ceil_div(batch, f.rpw);
+    TFX_CHECK(f.wgs < (1ll << 31), "%s: grid too large", what);
+    f.steps = ceil_div(T, f.B);
+    return f;
+}
+
+void modulated_delay_feedback_plan_info(int64_t batch, int64_t channels, int64_t T, const double *voices_host, int64_t V, int interp,
+                                        double feedback, int64_t *block, int64_t *rows_per_wave, int64_t *ring, int64_t *lds_bytes,
+                                        int64_t *workgroups, int64_t *steps)
+{
+    const char *what = "modulated_delay_feedback_plan_info";
+    const ModPlan pl = mod_plan(what, TFX_F32, batch, channels, T, voices_host, V, 0.0, 0.0, TFX_LFO_SINE, interp);
+    const ModFbPlan f = mod_fb_plan(what, pl, batch, channels, T, interp, feedback);
+    *block = f.B;
+    *rows_per_wave = f.rpw;
+    *ring = f.ring;
+    *lds_bytes = f.lds;
+    *workgroups = f.wgs;
+    *steps = f.steps;
+}
+
+template <typename T>
+static void mod_fb_forward(const void *x, void *y, const ModPlan &pl, const ModFbPlan &f, int64_t batch, int64_t channels, int64_t T_,
+                           const double *voices, int64_t V, double spread, double dry, int shape, int interp, int64_t position,
+                           double feedback, hipStream_t stream)
+{
+    ModArgs<T> t{};
+    const std::shared_ptr<DeviceBuffer> keep = mod_fill(t, pl, batch, channels, T_, voices, V, spread, dry, stream);
+    ModFbArgs<T> p{};
+    p.x = (const T *)x; p.y = (T *)y; p.pos = position; p.T_ = T_; p.batch = batch; p.channels = channels;
+    p.B = (int)f.B; p.lanes = f.lanes; p.rpw = (int)f.rpw; p.mask = (int)f.ring - 1; p.stride = f.stride;
+    p.lds_doubles = (int)(f.lds / 8); p.V = (int)V; p.dry = dry; p.fb = feedback; p.voice = t.voice; p.off = t.off;
+    ProfScope ps("modulated_delay_feedback_kernel", stream);
+    const dim3 grid((unsigned)f.wgs), block(MDF_LANES);
+#define MDF_GO(CUBIC, TRI) hipLaunchKernelGGL((modulated_delay_feedback_kernel<T, CUBIC, TRI>), grid, block, (size_t)f.lds, stream, p)
+    const bool cubic = interp == TFX_INTERP_CUBIC, tri = shape == TFX_LFO_TRIANGLE;
+    if (cubic && tri) MDF_GO(true, true);
+    else if (cubic) MDF_GO(true, false);
+    else if (tri) MDF_GO(false, true);
+    else MDF_GO(false, false);
+#undef MDF_GO
+    TFX_HIP(hipGetLastError());
+}
+
+void modulated_delay_feedback_forward(const void *x, void *y, int dtype, int64_t batch, int64_t channels, int64_t T,
+                                      const double *voices_host, int64_t V, double spread, double dry, int shape, int interp,
+                                      int64_t position, double feedback, hipStream_t stream)
+{
+    const char *what = "modulated_delay_feedback_forward";
+    if (feedback == 0.0) {                                   // w = x: the feed-forward kernel, bit for bit
+        modulated_delay_forward(x, y, dtype, batch, channels, T, voices_host, V, spread, dry, shape, interp, position, stream);
+        return;
+    }
+    const ModPlan pl = mod_plan(what, dtype, batch, channels, T, voices_host, V, spread, dry, shape, interp);
+    const ModFbPlan f = mod_fb_plan(what, pl, batch, channels, T, interp, feedback);
+    TFX_CHECK(position >= 0 && position <= (1ll << 52), "%s: the position must be in [0, 2^52], got %lld", what, (long long)position);
+    TFX_CHECK(pl.rows * T == 0 || (x && y), "%s: null pointer", what);
+    check_stream_buffers(what, dtype == TFX_F32 ? 4 : 8, x, pl.rows * T, y, pl.rows * T, nullptr, nullptr, 0);
+    if (pl.rows * T == 0) return;
+    if (dtype == TFX_F32)
+        mod_fb_forward<float>(x, y, pl, f, batch, channels, T, voices_host, V, spread, dry, shape, interp, position, feedback, stream);
+    else
+        mod_fb_forward<double>(x, y, pl, f, batch, channels, T, voices_host, V, spread, dry, shape, interp, position, feedback, stream);
 }
 
 void modulation_clear() { g_tables.clear(); }

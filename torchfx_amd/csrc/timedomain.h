@@ -107,6 +107,12 @@ void modulated_delay_stream_forward(const void *x, void *y, int dtype, int64_t b
                                     const void *hist_in, void *hist_out, const int64_t *pos_in, int64_t *pos_out, hipStream_t stream);
 void modulated_delay_plan_info(int64_t batch, int64_t channels, int64_t T, const double *voices_host, int64_t V, int interp,
                                int64_t *tile, int64_t *tiles, int64_t *history, int64_t *batch_items, int64_t *batch_groups);
+void modulated_delay_feedback_forward(const void *x, void *y, int dtype, int64_t batch, int64_t channels, int64_t T,
+                                      const double *voices_host, int64_t V, double spread, double dry, int shape, int interp,
+                                      int64_t position, double feedback, hipStream_t stream);
+void modulated_delay_feedback_plan_info(int64_t batch, int64_t channels, int64_t T, const double *voices_host, int64_t V, int interp,
+                                        double feedback, int64_t *block, int64_t *rows_per_wave, int64_t *ring, int64_t *lds_bytes,
+                                        int64_t *workgroups, int64_t *steps);
 void modulation_clear();
 
 // ---- reverb.hip ----

@@ -422,17 +422,19 @@ class ModulatedDelay(FX):
     seconds.  ``voices`` holds 1 to 8 rows ``(delay, depth, rate, phase, gain)``: delay and depth in seconds, rate in Hz, phase
     in cycles; ``pad`` is added to every voice's delay in samples (the cubic interpolant's one sample of headroom).  ``dry``,
     ``spread`` (cycles of LFO phase per channel index), ``shape`` ("sine" / "triangle") and ``interpolation`` ("linear" /
-    "cubic") as the function takes them.  :class:`Chorus`, :class:`Flanger` and :class:`Vibrato` only fill the table.
+    "cubic") and ``feedback`` (the raw factor of the recursive line, ``w[n] = x[n] + feedback r[n]``; 0 = feed-forward) as the
+    function takes them.  :class:`Chorus`, :class:`Flanger` and :class:`Vibrato` only fill the table.
 
     ``fs`` comes from the ``Wave`` the effect is piped into when it is None.  Every call starts its LFO at position 0 and its
     delay line from silence: the effect is a step of its own in ``Wave.plan()`` (one launch, ``csrc/modulation.hip``), and a
     chunked stream needs the stateful classes of :mod:`torchfx_amd.realtime`, which carry the history and the position."""
 
     def __init__(self, voices, dry: float = 1.0, spread: float = 0.0, shape: str = "sine", interpolation: str = "linear",
-                 fs: int | None = None, pad: float = 0.0) -> None:
+                 fs: int | None = None, pad: float = 0.0, feedback: float = 0.0) -> None:
         super().__init__()
         self.voices = [tuple(float(t) for t in v) for v in voices]
         self.dry, self.spread, self.shape, self.interpolation, self.fs, self.pad = float(dry), float(spread), shape, interpolation, fs, float(pad)
+        self.feedback = feedback
         self.params(torch.float32, 48000 if fs is None else fs)          # argument errors now
 
     def voice_table(self, fs: int) -> list[tuple]:
@@ -449,7 +451,8 @@ class ModulatedDelay(FX):
             raise ValueError(f"{type(self).__name__} needs the sample rate: pass fs or pipe a Wave into it (wave | {type(self).__name__}())")
         from torchfx_amd.modulation import ModulationParams, _check_fs
 
-        return ModulationParams(fs, dtype, self.voice_table(_check_fs(fs)), self.dry, self.spread, self.shape, self.interpolation)
+        return ModulationParams(fs, dtype, self.voice_table(_check_fs(fs)), self.dry, self.spread, self.shape, self.interpolation,
+                                self.feedback)
 
     def route(self, x: Tensor, length: int | None = None) -> str:
         """``native (...)`` or ``numpy on host -- <reason>`` for ``x`` (rows of ``length`` samples, default x's)."""
@@ -458,8 +461,13 @@ class ModulatedDelay(FX):
         try:
             P = self.params(x.dtype)
             n = int(x.shape[-1]) if length is None else int(length)
-            info = _ext().modulated_delay_plan_info(n, P.table, int(x.shape[0]) if x.dim() == 3 else 1,
-                                                    int(x.shape[-2]) if x.dim() >= 2 else 1, P.interpolation)
+            batch, channels = int(x.shape[0]) if x.dim() == 3 else 1, int(x.shape[-2]) if x.dim() >= 2 else 1
+            if P.feedback != 0.0:
+                fb = _ext().modulated_delay_feedback_plan_info(n, P.table, P.feedback, batch, channels, P.interpolation)
+                return (f"native (modulated_delay_feedback_kernel, {len(P.table)} voice(s), {P.shape} LFO, {P.interpolation} "
+                        f"interpolation, feedback {P.feedback:g}: block {fb['block']}, {fb['rows_per_wave']} row(s) per wave, ring "
+                        f"{fb['ring']}, {fb['workgroups']} workgroup(s) of {fb['steps']} step(s); one launch)")
+            info = _ext().modulated_delay_plan_info(n, P.table, batch, channels, P.interpolation)
         except (RuntimeError, ValueError, TypeError) as e:
             return f"refused -- {e}"
         return (f"native (modulated_delay_kernel, {len(P.table)} voice(s), {P.shape} LFO, {P.interpolation} interpolation, "
@@ -475,7 +483,19 @@ class ModulatedDelay(FX):
 
     def extra_repr(self) -> str:
         return (f"voices={len(self.voices)}, dry={self.dry}, spread={self.spread}, shape={self.shape!r}, "
-                f"interpolation={self.interpolation!r}, fs={self.fs}")
+                f"interpolation={self.interpolation!r}, fs={self.fs}" + (f", feedback={self.feedback}" if self.feedback else ""))
+
+
+def _loop_feedback(feedback, mix: float, wet_sum: float) -> float:
+    """The raw factor that gives Chorus / Flanger the loop gain ``feedback`` whatever ``mix`` and ``invert`` are:
+    ``feedback / sum_v g_v``."""
+    if isinstance(feedback, bool) or not isinstance(feedback, (int, float)) or not math.isfinite(feedback):
+        raise ValueError(f"modulated_delay: feedback must be a finite number, got {feedback!r}")
+    if feedback == 0:
+        return 0.0
+    if mix == 0:
+        raise ValueError("modulated_delay: mix must not be 0 with feedback: the loop runs through the wet voices")
+    return float(feedback) / wet_sum
 
 
 def _seconds(name: str, v) -> float:
@@ -488,15 +508,18 @@ class Chorus(ModulatedDelay):
     """Chorus: ``voices`` copies of the signal, each delayed by ``delay`` seconds and swept by ``depth`` seconds at ``rate``
     Hz, the voices' LFOs spaced evenly over the cycle (voice ``v`` has phase ``v / voices``) and each mixed in with gain
     ``mix / voices`` next to ``dry = 1 - mix``.  ``spread`` shifts the LFO phase by that many cycles per channel index, which
-    widens a stereo signal.  Feed-forward."""
+    widens a stereo signal.  Feed-forward with ``feedback = 0``; otherwise ``feedback`` is the *loop gain* ``F`` of the
+    regeneration path (the voices' sum is fed back into the line with the factor ``F / mix``, so that the loop gain is ``F``
+    whatever ``mix`` is): ``|F| L < 1`` with ``L = 1.25`` for cubic and ``1`` for linear interpolation, and ``mix != 0``."""
 
     def __init__(self, rate: float = 1.5, depth: float = 3e-3, delay: float = 20e-3, voices: int = 3, mix: float = 0.5,
-                 spread: float = 0.25, shape: str = "sine", interpolation: str = "cubic", fs: int | None = None) -> None:
+                 spread: float = 0.25, shape: str = "sine", interpolation: str = "cubic", fs: int | None = None,
+                 feedback: float = 0.0) -> None:
         if isinstance(voices, bool) or not isinstance(voices, int) or not 1 <= voices <= 8:
             raise ValueError(f"modulated_delay: the number of voices must be in [1, 8], got {voices!r}")
         self.rate, self.depth, self.delay, self.mix = float(rate), _seconds("depth", depth), _seconds("delay", delay), float(mix)
         super().__init__([(self.delay, self.depth, self.rate, v / voices, self.mix / voices) for v in range(voices)],
-                         1.0 - self.mix, spread, shape, interpolation, fs)
+                         1.0 - self.mix, spread, shape, interpolation, fs, feedback=_loop_feedback(feedback, self.mix, self.mix))
 
     def extra_repr(self) -> str:
         return f"rate={self.rate}, depth={self.depth}, delay={self.delay}, mix={self.mix}, " + super().extra_repr()
@@ -518,14 +541,18 @@ class Vibrato(ModulatedDelay):
 
 class Flanger(ModulatedDelay):
     """Flanger: the signal plus one short, slowly swept copy of itself (``delay`` +- ``depth`` seconds at ``rate`` Hz) with
-    gain ``mix`` (``-mix`` with ``invert``), which combs the spectrum.  This flanger is **feed-forward**: there is no
-    regeneration path from the output back into the delay line."""
+    gain ``mix`` (``-mix`` with ``invert``), which combs the spectrum.  With ``feedback = 0`` the flanger is feed-forward: a
+    single swept comb.  ``feedback`` is the *loop gain* ``F`` of the regeneration path from the swept copy back into the delay
+    line (the raw factor is ``F / (+-mix)``, so that the loop gain is ``F`` whatever ``mix`` and ``invert`` are), which sharpens
+    the comb into the resonant sweep: ``|F| L < 1`` with ``L = 1.25`` for cubic and ``1`` for linear interpolation, ``mix != 0``."""
 
     def __init__(self, rate: float = 0.25, depth: float = 2e-3, delay: float = 3e-3, mix: float = 0.5, invert: bool = False,
-                 spread: float = 0.0, shape: str = "sine", interpolation: str = "cubic", fs: int | None = None) -> None:
+                 spread: float = 0.0, shape: str = "sine", interpolation: str = "cubic", fs: int | None = None,
+                 feedback: float = 0.0) -> None:
         self.rate, self.depth, self.delay, self.mix, self.invert = float(rate), _seconds("depth", depth), _seconds("delay", delay), float(mix), bool(invert)
-        super().__init__([(self.delay, self.depth, self.rate, 0.0, -self.mix if self.invert else self.mix)], 1.0, spread, shape,
-                         interpolation, fs)
+        wet = -self.mix if self.invert else self.mix
+        super().__init__([(self.delay, self.depth, self.rate, 0.0, wet)], 1.0, spread, shape, interpolation, fs,
+                         feedback=_loop_feedback(feedback, self.mix, wet))
 
     def extra_repr(self) -> str:
         return f"rate={self.rate}, depth={self.depth}, delay={self.delay}, mix={self.mix}, invert={self.invert}, " + super().extra_repr()

@@ -6,6 +6,11 @@ position that a low-frequency oscillator (LFO) moves.  It is feed-forward, so ti
 exact: on ROCm device float32 / float64 tensors one launch of ``csrc/modulation.hip``
 (:func:`torchfx_ext.modulated_delay_forward`), on CPU tensors the same expressions over NumPy arrays.  Every intermediate is
 float64 for both signal dtypes.
+
+With ``feedback != 0`` (regeneration) the voices read the line ``w[n] = x[n] + feedback r[n]``, ``r[n] = sum_v g_v w(n - d_v[n])``,
+and ``y[n] = dry x[n] + r[n]``: a recursion whose memory is the moving delay.  The ``B = floor(min_v(delay_v - depth_v)) - c``
+samples of a block depend only on samples before it, so the device kernel (``modulated_delay_feedback_kernel``) and the host path
+compute a block in parallel and the blocks in order.
 """
 from __future__ import annotations
 
@@ -38,11 +43,14 @@ class ModulationParams:
     ``interpolation`` and ``history`` (``H = max_v floor(base_v + depth_v) + 2``, what a stream carries per row).
 
     ``voices`` is a sequence of ``(delay, depth, rate, phase, gain)`` rows with delay and depth in samples (need not be
-    integers) and rate in Hz."""
+    integers) and rate in Hz.  ``feedback != 0`` adds the rules of the recursive line, which are the native plan's own answer
+    (:func:`torchfx_ext.modulated_delay_feedback_plan_info`, host-only) for CPU and device tensors alike, and ``block``, the
+    plan's ``B`` (0 without feedback)."""
 
-    __slots__ = ("table", "dry", "spread", "shape", "interpolation", "history")
+    __slots__ = ("table", "dry", "spread", "shape", "interpolation", "history", "feedback", "block")
 
-    def __init__(self, fs, dtype: torch.dtype, voices, dry=1.0, spread=0.0, shape="sine", interpolation="linear") -> None:
+    def __init__(self, fs, dtype: torch.dtype, voices, dry=1.0, spread=0.0, shape="sine", interpolation="linear",
+                 feedback=0.0) -> None:
         fs = _check_fs(fs)
         if dtype not in (torch.float32, torch.float64):
             raise TypeError(f"modulated_delay: float32 or float64 signals only, got {dtype}")
@@ -81,6 +89,14 @@ class ModulationParams:
         self.spread = _real("spread", spread, "a finite phase in cycles per channel")
         self.shape, self.interpolation = shape, interpolation
         self.history = int(np.floor(table[:, 0] + table[:, 1]).max()) + 2
+        self.feedback, self.block = _real("feedback", feedback), 0
+        if self.feedback != 0.0:
+            from torchfx_amd import torchfx_ext
+
+            try:
+                self.block = torchfx_ext.modulated_delay_feedback_plan_info(0, table, self.feedback, interpolation=interpolation)["block"]
+            except RuntimeError as e:
+                raise ValueError(f"modulated_delay: {str(e).split(': ', 1)[-1]}") from None
 
 
 def _check_position(position) -> int:
@@ -139,6 +155,43 @@ def _modulate_host(xh: np.ndarray, H: int, P: ModulationParams, channels: int, p
     return y.reshape(rows, T)
 
 
+def _modulate_feedback_host(x: np.ndarray, P: ModulationParams, channels: int, position: int) -> np.ndarray:
+    """``x [rows, T]`` -> ``[rows, T]`` in ``x``'s dtype with feedback: the line ``w`` is float64 ``[batch, T]`` per channel
+    index, and a block of ``P.block`` samples (which reads nothing newer than the block before it) is one vectorised step over
+    the block and the batch."""
+    rows, T = x.shape
+    xb = x.reshape(rows // channels, channels, T)
+    y = np.empty_like(xb)
+    cubic, B = P.interpolation == "cubic", P.block
+    with np.errstate(invalid="ignore", over="ignore"):
+        for c in range(channels):
+            xc = xb[:, c, :].astype(np.float64)
+            w = np.zeros_like(xc)
+            delays = []
+            for voice in P.table:                                    # the delays do not depend on the line: whole rows at once
+                z = voice[3] + float(c) * P.spread
+                delays.append(lfo_delay(position + np.arange(T, dtype=np.int64), voice, z - math.floor(z), P.shape))
+            for n0 in range(0, T, B):
+                j = np.arange(n0, min(T, n0 + B), dtype=np.int64)
+                r = 0.0
+                for voice, (i, f) in zip(P.table, delays):
+                    m, fj = j - i[j], f[j]
+
+                    def at(k):
+                        return np.where(k >= 0, w[:, np.maximum(k, 0)], 0.0)
+
+                    w0, w1 = at(m), at(m - 1)
+                    if cubic:
+                        wd = ((-fj * (fj - 1.0) * (fj - 2.0) / 6.0) * at(m + 1) + ((fj + 1.0) * (fj - 1.0) * (fj - 2.0) / 2.0) * w0
+                              + (-(fj + 1.0) * fj * (fj - 2.0) / 2.0) * w1 + ((fj + 1.0) * fj * (fj - 1.0) / 6.0) * at(m - 2))
+                    else:
+                        wd = w0 + fj * (w1 - w0)
+                    r = r + voice[4] * wd
+                w[:, j] = xc[:, j] + P.feedback * r
+                y[:, c, j] = (P.dry * xc[:, j] + r).astype(x.dtype)
+    return y.reshape(rows, T)
+
+
 def _channels(x: Tensor) -> int:
     return int(x.shape[-2]) if x.dim() >= 2 else 1
 
@@ -156,7 +209,7 @@ def modulate_stream_host(x: Tensor, hist: Tensor | None, P: ModulationParams, po
 
 @torch.no_grad()
 def modulated_delay(x: Tensor, fs: int, voices, dry: float = 1.0, spread: float = 0.0, shape: str = "sine",
-                    interpolation: str = "linear", position: int = 0) -> Tensor:
+                    interpolation: str = "linear", position: int = 0, feedback: float = 0.0) -> Tensor:
     """Modulated delay line: ``x [T]``, ``[C, T]`` or ``[B, C, T]`` (float32 / float64) -> the same shape, dtype and device,
     ``y[n] = dry x[n] + sum_v g_v x(n - d_v[n])`` along the last axis.  The delayed tail past the end is dropped.
 
@@ -184,10 +237,23 @@ def modulated_delay(x: Tensor, fs: int, voices, dry: float = 1.0, spread: float 
     * **Non-finite input.**  A NaN / Inf ``x[m]`` reaches no output outside ``[m, m + H]`` of its own row.
 
     Rules: ``delay_v - depth_v >= 0`` (linear) or ``>= 1`` (cubic, which reads ``x[n-i+1]``); ``floor(delay_v + depth_v) + 3 <=
-    2^24``; ``0 < rate_v < fs / 2``; ``0 <= position <= 2^52``.  ``ValueError`` / ``TypeError`` otherwise.  Feedback
-    (regeneration), autograd and axes other than the last are not provided."""
+    2^24``; ``0 < rate_v < fs / 2``; ``0 <= position <= 2^52``.  ``ValueError`` / ``TypeError`` otherwise.
+
+    **Feedback (regeneration).**  With ``feedback != 0`` the voices read the line ``w`` in place of ``x`` in step 5 (``w[m] = 0``
+    for ``m < 0``), ``r[n] = sum_v g_v wd_v`` in voice order, ``w[n] = x[n] + feedback r[n]`` (float64, never rounded to the
+    signal's dtype) and ``y[n] = dtype(dry x[n] + r[n])``.  ``feedback = 0`` is the formula above, bit for bit.  Rules, each a
+    ``ValueError``: ``feedback`` finite; ``|feedback| sum_v |g_v| L < 1`` with ``L = 1`` (linear) or ``1.25`` (cubic), the
+    sufficient condition for a bounded line; ``B = floor(min_v(delay_v - depth_v)) - c >= 1`` with ``c = 1`` (cubic) or ``0``
+    (linear), so that an output reads only older line samples; ``H + min(B, 64) <= 8192``, the ring the device kernel keeps a
+    row's line in (``csrc/modulation.hip``, ``modulated_delay_feedback_kernel``: one wave owns a row, the ``B`` samples of a
+    block are computed in parallel, ``ceil(T / B)`` dependent steps).  A row's bits depend on its own samples, its channel index
+    and ``position`` alone, as without feedback; a non-finite ``x[m]`` stays in its row, reaches nothing before ``m`` and may stay
+    in the line from there on.
+
+    Not provided: a streaming feedback line (its history is its own output), lines longer than the ring with feedback,
+    time-segmenting a row of the recursion, autograd and axes other than the last."""
     _check_signal(x, "modulated_delay")
-    return modulate(x, ModulationParams(fs, x.dtype, voices, dry, spread, shape, interpolation), position)
+    return modulate(x, ModulationParams(fs, x.dtype, voices, dry, spread, shape, interpolation, feedback), position)
 
 
 @torch.no_grad()
@@ -201,7 +267,9 @@ def modulate(x: Tensor, P: ModulationParams, position: int = 0) -> Tensor:
         from torchfx_amd import torchfx_ext
 
         with torch.cuda.device(x.device):
-            return torchfx_ext.modulated_delay_forward(x, P.table, P.spread, P.dry, P.shape, P.interpolation, position)
+            return torchfx_ext.modulated_delay_forward(x, P.table, P.spread, P.dry, P.shape, P.interpolation, position, P.feedback)
     a = x.detach().contiguous().numpy()
     rows = max(1, math.prod(x.shape[:-1]))
+    if P.feedback != 0.0:
+        return torch.from_numpy(_modulate_feedback_host(a.reshape(rows, -1), P, _channels(x), position).reshape(a.shape))
     return torch.from_numpy(_modulate_host(a.reshape(rows, -1), 0, P, _channels(x), position).reshape(a.shape))

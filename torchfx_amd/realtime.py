@@ -860,7 +860,14 @@ class _ModulationStream:
 
     def __init__(self, *args, **kwargs) -> None:
         super().__init__(*args, **kwargs)
+        self._refuse_feedback()
         self.reset_state()
+
+    def _refuse_feedback(self) -> None:
+        """The carried history is the input's; the recursive line's history is its own output, which no stream carries."""
+        if self.feedback != 0:
+            raise ValueError(f"{type(self).__name__}: feedback must be 0, got {self.feedback!r}: a stream of the recursive line is "
+                             f"not provided (its history is its own output); the one-shot effect takes feedback")
 
     def reset_state(self) -> None:
         self._hist: Tensor | None = None            # [rows, H]; None = silence
@@ -880,6 +887,7 @@ class _ModulationStream:
         rows = _rows(x)
         if self.fs is None:
             raise ValueError(f"{type(self).__name__} needs the sample rate: pass fs or let the processor configure it")
+        self._refuse_feedback()
         P = self.params(x.dtype)
         h = _carried(self._hist, rows, P.history, x)
         if h is None or self._pos is None or self._pos.device != x.device:      # a new stream: silence, position 0

@@ -38,7 +38,7 @@ __all__ = [
     "resample_plan_info", "resample_tiling_info", "resample_stream_forward", "resample_stream_plan_info", "sos_filtfilt", "sos_filtfilt_plan_info",
     "sos_block_energy", "sos_block_energy_plan_info", "true_peak", "true_peak_plan_info", "limiter_forward", "limiter_plan_info",
     "limiter_stream_forward", "limiter_stream_plan_info", "compressor_forward", "compressor_plan_info",
-    "modulated_delay_forward", "modulated_delay_stream_forward", "modulated_delay_plan_info", "freeverb_forward", "freeverb_plan_info",
+    "modulated_delay_forward", "modulated_delay_stream_forward", "modulated_delay_plan_info", "modulated_delay_feedback_plan_info", "freeverb_forward", "freeverb_plan_info",
     "waveshaper_stream_forward", "waveshaper_stream_plan_info", "phaser_forward", "phaser_plan_info", "gate_forward", "gate_plan_info",
     "stft_forward", "stft_plan_info", "istft_forward", "istft_plan_info", "mel_forward", "mel_plan_info", "mel_band_table",
     "phase_vocoder_forward", "phase_vocoder_plan_info", "yin_forward", "yin_plan_info", "yin_lags",
@@ -389,14 +389,17 @@ def _voice_table(voices) -> Tensor:
 
 
 def modulated_delay_forward(x: Tensor, voices, spread: float = 0.0, dry: float = 1.0, shape: str = "sine",
-                            interpolation: str = "linear", position: int = 0) -> Tensor:
+                            interpolation: str = "linear", position: int = 0, feedback: float = 0.0) -> Tensor:
     """The modulated delay line (``tfx_modulated_delay_forward``; the definition is
     :func:`torchfx_amd.modulation.modulated_delay`'s) with its parameters already reduced: ``x [T]``, ``[C, T]`` or
     ``[B, C, T]`` on the device (float32 / float64), ``voices`` a ``[V, 5]`` table of ``(base, depth, inc, phase, gain)`` rows
     (delay and depth in samples, ``inc = rate / fs``, phase in cycles), ``position`` the absolute index of the first sample.
-    One launch (``modulated_delay_kernel``)."""
+    One launch: ``modulated_delay_kernel``, or with ``feedback != 0`` the recursive line of
+    ``tfx_modulated_delay_feedback_forward`` (``modulated_delay_feedback_kernel``; :func:`modulated_delay_feedback_plan_info`
+    holds its rules and its geometry)."""
     return native.ops().modulated_delay_forward(x.contiguous(), _voice_table(voices), float(spread), float(dry),
-                                                LFO_SHAPES.index(shape), INTERPOLATIONS.index(interpolation), int(position))
+                                                LFO_SHAPES.index(shape), INTERPOLATIONS.index(interpolation), int(position),
+                                                float(feedback))
 
 
 def modulated_delay_stream_forward(x: Tensor, hist: Tensor | None, pos: Tensor | None, voices, spread: float = 0.0, dry: float = 1.0,
@@ -420,6 +423,20 @@ def modulated_delay_plan_info(length: int, voices, batch: int = 1, channels: int
     return _query(L.load().tfx_modulated_delay_plan_info,
                   (int(batch), int(channels), int(length), ctypes.c_void_p(t.data_ptr()), int(t.shape[0]),
                    INTERPOLATIONS.index(interpolation)), "tile tiles history batch_items batch_groups")
+
+
+def modulated_delay_feedback_plan_info(length: int, voices, feedback: float, batch: int = 1, channels: int = 1,
+                                       interpolation: str = "linear") -> dict:
+    """What the modulated delay with ``feedback != 0`` does for ``[batch, channels, length]``
+    (``tfx_modulated_delay_feedback_plan_info``; host-only, and the one place the rules feedback adds are checked: a stable
+    loop, a delay of at least one sample, a line that fits the LDS ring): ``block`` (``B``, the samples of a row computed in
+    parallel), ``rows_per_wave`` (batch items of one channel index a wave owns; more than 1 for ``B <= 32``), ``ring`` (samples
+    of a row's ring), ``lds_bytes`` per workgroup, ``workgroups`` and ``steps`` (``ceil(length / B)``, the dependent steps of a
+    row)."""
+    t = _voice_table(voices)
+    return _query(L.load().tfx_modulated_delay_feedback_plan_info,
+                  (int(batch), int(channels), int(length), ctypes.c_void_p(t.data_ptr()), int(t.shape[0]),
+                   INTERPOLATIONS.index(interpolation), float(feedback)), "block rows_per_wave ring lds_bytes workgroups steps")
 
 
 FREEVERB_LINES = ("lds", "global")                       # tfx_freeverb_lines
