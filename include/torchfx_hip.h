@@ -860,6 +860,38 @@ int tfx_phaser_plan_info(int64_t rows, int64_t channels, int64_t T, int64_t stag
                          int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes);
 
 /* ---------------------------------------------------------------------------
+ * tfx_phaser_feedback_forward -- tfx_phaser_forward with feedback (resonance) around the chain: the last section's previous
+ * output, scaled, is added to the input of the first.  Steps 1 to 5 (the coefficient track a[n]) are tfx_phaser_forward's, the
+ * same code and the same bits; then, every intermediate in float64 for both dtypes:
+ *   6. u[n]   = x[n] + feedback * x_N[n-1]                                   (one fma)
+ *      x_0[n] = u[n]
+ *      x_k[n] = a[n] x_{k-1}[n] + x_{k-1}[n-1] - a[n] x_k[n-1],  k = 1..N    (two fmas: fma(-a, x_k[n-1], fma(a, x_{k-1}[n], x_{k-1}[n-1])))
+ *   7. y[n]   = dtype(dry x[n] + wet x_N[n]), rounded once: dry multiplies the input, not u
+ * State: DEVICE float64 [rows, N + 1] = (x_0[-1], .., x_N[-1]) as for tfx_phaser_forward, but x_0[-1] = u[-1] is the loop's own
+ * value here, not the input's last sample.  Rules: tfx_phaser_forward's, and feedback finite with |feedback| < 1 (every section
+ * has unit gain, so the loop decays); feedback == 0 runs tfx_phaser_forward and returns its bits.
+ * Launches: rows, tiles of 2048 samples and `segments` as for tfx_phaser_forward.  The loop is one sample long, so the tile is not
+ * scanned stage by stage: a run of samples acts on the incoming state as s -> M s + v with M (N+1) x (N+1) dense.  A tile is cut
+ * into chunks of L = 32, 64 or 128 samples (N + 2 <= 4, 8, 16); each of a chunk's N + 2 runs (the signal from a zero state, the
+ * zero signal from each unit state) belongs to one lane; the chunks' summaries are chained in order by matrix-vector steps, and
+ * one lane per chunk runs it once more from its true start state.  One segment is one launch; otherwise two, the first storing
+ * every segment's (v | M), (N + 1)(N + 2) doubles, into `scratch` (scratch_bytes of tfx_phaser_feedback_plan_info).  The
+ * properties of tfx_phaser_forward hold: the track does not depend on the cut, a sample's bits do not depend on values after
+ * it, rows are independent, and from a NaN / Inf x[m] on every output of the row and its end state are non-finite.
+ * ------------------------------------------------------------------------- */
+int tfx_phaser_feedback_forward(const void *x, void *y, double *coef_or_null, int dtype, int64_t rows, int64_t channels, int64_t T,
+                                int64_t stages, double fs, double rate, double min_freq, double max_freq, double phase, double spread,
+                                double dry, double wet, double feedback, int shape, int64_t position, const int64_t *pos_in,
+                                int64_t *pos_out, const double *state_in, double *state_out, int64_t segments, void *scratch,
+                                tfx_stream_t stream);
+/* what tfx_phaser_feedback_forward does (host-only; the one place the rule on feedback is checked, with the checks on the sizes):
+ * the samples of a lane's run L, samples per tile (2048), the segments it takes for the request, the launches (1 or 2), the LDS
+ * bytes of a workgroup, the workgroups of the writing launch and the bytes of `scratch` (0 for one segment) */
+int tfx_phaser_feedback_plan_info(int64_t rows, int64_t channels, int64_t T, int64_t stages, int64_t segments, double feedback,
+                                  int64_t *run, int64_t *tile, int64_t *segments_out, int64_t *launches, int64_t *lds_bytes,
+                                  int64_t *workgroups, int64_t *scratch_bytes);
+
+/* ---------------------------------------------------------------------------
  * tfx_gate_forward -- noise gate with hysteresis, hold and range.  x is [groups, channels, T]; the `channels` rows of a group
  * share one gain curve.  All levels are linear and come from the caller, so that every implementation compares against the
  * same doubles: p_open = 10^(threshold_db / 20), p_close = 10^((threshold_db - hysteresis_db) / 20) <= p_open, range = r =

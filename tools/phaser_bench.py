@@ -10,6 +10,11 @@ and, once, (e) the NumPy host path on a CPU copy of one row.  Times are device e
 cost of a stage ((b) - (a)) / 8 and what is left of (a) without its stages, a[n] and the products of the scan.
 
     python tools/phaser_bench.py --out profiles/phaser_bench.txt
+
+With --feedback it times instead ``Phaser(feedback=0.7)`` at 4 and 12 stages (``phaser_feedback_kernel``) against ``Phaser()`` at
+both and ``Flanger(feedback=0.7)`` on the same tensors, and reports the ratio to the feedback-free kernel and the cost of a stage.
+
+    python tools/phaser_bench.py --feedback --out profiles/phaser_feedback_bench.txt
 """
 from __future__ import annotations
 
@@ -51,14 +56,53 @@ def signal(B, C, T):
     return torch.randn(B, C, T, generator=g, device="cuda", dtype=torch.float32) * 0.25
 
 
+def feedback_report(repeats: int) -> list[str]:
+    """--feedback: Phaser(feedback=0.7) at 4 and 12 stages against Phaser() and Flanger(feedback=0.7) on the same tensors."""
+    from torchfx_amd import Flanger, Phaser, torchfx_ext as E
+
+    lines = [f"Phaser feedback at {FS} Hz, rate 0.5 Hz, 200-2000 Hz, sine, float32 on {torch.cuda.get_device_name(0)}; device events "
+             f"around one call, min / median / max of {repeats} alternating repeats, ms"]
+    fmt = lambda t: f"{t[0]:.3f} / {t[1]:.3f} / {t[2]:.3f}"          # noqa: E731
+    effects = [Phaser(stages=4, fs=FS, feedback=0.7), Phaser(stages=12, fs=FS, feedback=0.7), Phaser(stages=4, fs=FS), Phaser(stages=12, fs=FS),
+               Flanger(fs=FS, feedback=0.7)]
+    for B, C, T in SHAPES:
+        x = signal(B, C, T)
+        info = E.phaser_feedback_plan_info(T, 0.7, B * C, C, 4)
+        f4, f12, p4, p12, fl = time_alternating([lambda e=e: e(x) for e in effects], repeats)
+        n = B * C * T
+        row = dict(batch=B, channels=C, length=T, plan4=info, plan12_run=E.phaser_feedback_plan_info(T, 0.7, B * C, C, 12)["run"],
+                   feedback4_ms=f4, feedback12_ms=f12, phaser4_ms=p4, phaser12_ms=p12, flanger_feedback_ms=fl,
+                   feedback4_over_phaser4=f4[0] / p4[0], feedback12_over_phaser12=f12[0] / p12[0], feedback4_over_flanger=f4[0] / fl[0],
+                   ms_per_stage=(f12[0] - f4[0]) / 8.0, feedback4_samples_per_us=n / f4[0] * 1e-3)
+        lines.append(json.dumps(row))
+        lines.append(f"{B} x {C} x {T} ({B * C} rows, {info['segments']} segment(s), {info['launches']} launch(es), "
+                     f"{info['workgroups']} workgroups): Phaser(stages=4, feedback=0.7) {fmt(f4)}   Phaser(stages=12, feedback=0.7) "
+                     f"{fmt(f12)}   Phaser(stages=4) {fmt(p4)}   Phaser(stages=12) {fmt(p12)}   Flanger(feedback=0.7) {fmt(fl)}   "
+                     f"ratio to the feedback-free kernel {f4[0] / p4[0]:.2f}x (4 stages) {f12[0] / p12[0]:.2f}x (12 stages); "
+                     f"to the flanger {f4[0] / fl[0]:.2f}x; a stage costs {(f12[0] - f4[0]) / 8.0:.3f} ms")
+        del x
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the report here")
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--feedback", action="store_true", help="time Phaser(feedback=0.7) against Phaser() and Flanger(feedback=0.7) instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("phaser_bench needs a ROCm device")
     from torchfx_amd import Freeverb, Phaser, torchfx_ext as E
+
+    if args.feedback:
+        text = "\n".join(feedback_report(args.repeats))
+        print(text, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
 
     lines = [f"Phaser at {FS} Hz, rate 0.5 Hz, 200-2000 Hz, sine, float32 on {torch.cuda.get_device_name(0)}; device events around one "
              f"call, min / median / max of {args.repeats} alternating repeats, ms"]

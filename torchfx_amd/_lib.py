@@ -107,6 +107,9 @@ SIGNATURES = {
     "tfx_waveshaper_stream_plan_info": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _int] + [ctypes.POINTER(_i64)] * 6),
     "tfx_phaser_forward": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64] + [_dbl] * 8 + [_int, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "tfx_phaser_plan_info": (_int, [_i64, _i64, _i64, _i64, _i64] + [ctypes.POINTER(_i64)] * 5),
+    "tfx_phaser_feedback_forward": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64] + [_dbl] * 9
+                                    + [_int, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "tfx_phaser_feedback_plan_info": (_int, [_i64, _i64, _i64, _i64, _i64, _dbl] + [ctypes.POINTER(_i64)] * 7),
     "tfx_gate_forward": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _dbl, _dbl, _dbl, _i64, _dbl, _dbl, _vp, _vp, _i64, _vp, _vp]),
     "tfx_gate_plan_info": (_int, [_i64, _i64, _i64, _i64] + [ctypes.POINTER(_i64)] * 5),
     "tfx_stft_forward": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _vp]),

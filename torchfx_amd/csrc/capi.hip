@@ -847,6 +847,29 @@ int tfx_phaser_plan_info(int64_t rows, int64_t channels, int64_t T, int64_t stag
     TFX_API_END
 }
 
+int tfx_phaser_feedback_forward(const void *x, void *y, double *coef_or_null, int dtype, int64_t rows, int64_t channels, int64_t T,
+                                int64_t stages, double fs, double rate, double min_freq, double max_freq, double phase, double spread,
+                                double dry, double wet, double feedback, int shape, int64_t position, const int64_t *pos_in,
+                                int64_t *pos_out, const double *state_in, double *state_out, int64_t segments, void *scratch,
+                                tfx_stream_t stream)
+{
+    TFX_API_BEGIN
+    phaser_feedback_forward(x, y, coef_or_null, dtype, rows, channels, T, stages, fs, rate, min_freq, max_freq, phase, spread, dry, wet,
+                            feedback, shape, position, pos_in, pos_out, state_in, state_out, segments, scratch, (hipStream_t)stream);
+    TFX_API_END
+}
+
+int tfx_phaser_feedback_plan_info(int64_t rows, int64_t channels, int64_t T, int64_t stages, int64_t segments, double feedback,
+                                  int64_t *run, int64_t *tile, int64_t *segments_out, int64_t *launches, int64_t *lds_bytes,
+                                  int64_t *workgroups, int64_t *scratch_bytes)
+{
+    TFX_API_BEGIN
+    TFX_CHECK(run && tile && segments_out && launches && lds_bytes && workgroups && scratch_bytes, "phaser_feedback_plan_info: null output");
+    phaser_feedback_plan_info(rows, channels, T, stages, segments, feedback, run, tile, segments_out, launches, lds_bytes, workgroups,
+                              scratch_bytes);
+    TFX_API_END
+}
+
 int tfx_gate_forward(const void *x, void *y, void *gain_or_null, unsigned char *open_or_null, int dtype, int64_t groups,
                      int64_t channels, int64_t T, double p_open, double p_close, double range, int64_t hold, double alpha_a,
                      double alpha_r, const double *state_in, double *state_out, int64_t segments, void *scratch, tfx_stream_t stream)

@@ -1070,12 +1070,13 @@ std::tuple<Tensor, Tensor, Tensor> modulated_delay_stream_op(const Tensor &x_in,
 // (a stream's position; None = the host scalar `position`), state [rows, stages + 1] float64 or None (silence); segments 0 = the
 // plan's choice -> (y like x, coef [C or 1, T] float64 or an empty tensor, new state [rows, stages + 1] float64, pos + T as a
 // fresh int64 [1] or an empty tensor without pos).  The summaries between the launches live in a tensor from torch's allocator.
+// feedback != 0 takes tfx_phaser_feedback_forward, whose plan holds the rule on feedback and sizes the summaries.
 int64_t phaser_coef_rows(int64_t channels, double spread) { return (spread == 0.0 || channels == 1) ? 1 : channels; }
 
 std::tuple<Tensor, Tensor, Tensor, Tensor> phaser_op(const Tensor &x_in, int64_t stages, double fs, double rate, double min_freq,
                                                      double max_freq, double phase, double spread, double dry, double wet, int64_t shape,
                                                      int64_t position, const OptTensor &pos, const OptTensor &state, bool return_coef,
-                                                     int64_t segments)
+                                                     int64_t segments, double feedback)
 {
     const char *what = "phaser_forward";
     need_device(x_in, "x");
@@ -1084,7 +1085,12 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> phaser_op(const Tensor &x_in, int64_t
     const int64_t channels = x_in.dim() >= 2 ? x_in.size(-2) : 1;
     const ScanInputs in = scan_inputs(what, x_in, 1, stages + 1, state, [&](int64_t rows, int64_t T, int64_t *info) {
         TORCH_CHECK(channels >= 1, what, ": x has no channels");    // here, not in front: callers meet it after the dtype check, as ever
-        return tfx_phaser_plan_info(rows, channels, T, stages, segments, info, info + 1, info + 2, info + 3, info + 4);
+        if (feedback == 0.0) return tfx_phaser_plan_info(rows, channels, T, stages, segments, info, info + 1, info + 2, info + 3, info + 4);
+        int64_t fb[7];                      // the feedback plan's own answer: its rule on feedback, its scratch bytes
+        const int rc = tfx_phaser_feedback_plan_info(rows, channels, T, stages, segments, feedback, fb, fb + 1, fb + 2, fb + 3, fb + 4, fb + 5,
+                                                     fb + 6);
+        info[4] = fb[6];
+        return rc;
     });
     const Tensor &x = in.x;
     const int64_t T = in.T;
@@ -1098,17 +1104,25 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> phaser_op(const Tensor &x_in, int64_t
     Tensor coef = return_coef ? at::empty({phaser_coef_rows(channels, spread), T}, f64) : at::empty({0}, f64);
     Tensor pout = at::empty({pin.defined() ? 1 : 0}, i64);
     c10::hip::HIPGuard guard(x.get_device());
-    check_rc(tfx_phaser_forward(x.data_ptr(), y.data_ptr(), return_coef ? coef.data_ptr<double>() : nullptr, in.dt, in.units, channels, T, stages,
-                                fs, rate, min_freq, max_freq, phase, spread, dry, wet, (int)shape, position,
-                                pin.defined() ? pin.data_ptr<int64_t>() : nullptr, pin.defined() ? pout.data_ptr<int64_t>() : nullptr, in.sin,
-                                in.sout.data_ptr<double>(), segments, in.scratch_ptr, stream_of(x)),
-             what);
+    double *cp = return_coef ? coef.data_ptr<double>() : nullptr;
+    const int64_t *pi = pin.defined() ? pin.data_ptr<int64_t>() : nullptr;
+    int64_t *po = pin.defined() ? pout.data_ptr<int64_t>() : nullptr;
+    if (feedback == 0.0)
+        check_rc(tfx_phaser_forward(x.data_ptr(), y.data_ptr(), cp, in.dt, in.units, channels, T, stages, fs, rate, min_freq, max_freq, phase,
+                                    spread, dry, wet, (int)shape, position, pi, po, in.sin, in.sout.data_ptr<double>(), segments,
+                                    in.scratch_ptr, stream_of(x)),
+                 what);
+    else
+        check_rc(tfx_phaser_feedback_forward(x.data_ptr(), y.data_ptr(), cp, in.dt, in.units, channels, T, stages, fs, rate, min_freq,
+                                             max_freq, phase, spread, dry, wet, feedback, (int)shape, position, pi, po, in.sin,
+                                             in.sout.data_ptr<double>(), segments, in.scratch_ptr, stream_of(x)),
+                 what);
     return std::make_tuple(y, coef, in.sout, pout);
 }
 
 std::tuple<Tensor, Tensor, Tensor, Tensor> phaser_meta(const Tensor &x, int64_t stages, double, double, double, double, double,
                                                        double spread, double, double, int64_t, int64_t, const OptTensor &pos,
-                                                       const OptTensor &, bool return_coef, int64_t)
+                                                       const OptTensor &, bool return_coef, int64_t, double)
 {
     TORCH_CHECK(x.dim() >= 1 && x.dim() <= 3 && stages >= 1, "phaser_forward: bad shape");
     const int64_t T = x.size(-1), channels = x.dim() >= 2 ? x.size(-2) : 1;
@@ -1746,7 +1760,7 @@ TORCH_LIBRARY(torchfx_hip, m)
            freeverb_op, freeverb_meta);
     reg_op(m, "phaser_forward(Tensor x, int stages, float fs, float rate, float min_freq, float max_freq, float phase, float spread, "
               "float dry, float wet, int shape, int position=0, Tensor? pos=None, Tensor? state=None, bool return_coef=False, "
-              "int segments=0) -> (Tensor, Tensor, Tensor, Tensor)", phaser_op, phaser_meta);
+              "int segments=0, float feedback=0.0) -> (Tensor, Tensor, Tensor, Tensor)", phaser_op, phaser_meta);
     reg_op(m, "gate_forward(Tensor x, float p_open, float p_close, float range, int hold, float alpha_a, float alpha_r, int channels, "
               "Tensor? state, bool return_gain, bool return_open, int segments=0) -> (Tensor, Tensor, Tensor, Tensor)", gate_op, gate_meta);
     reg_op(m, "stft_forward(Tensor x, Tensor? window, int n_fft, int hop, int pad, int pad_mode, int power, bool normalized) -> Tensor",

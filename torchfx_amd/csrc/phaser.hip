@@ -22,6 +22,9 @@
 //      gives v, the zero signal from x_1[-1] = 1 gives the N distinct entries of M.  x_0[-1] is read from the signal itself.
 //   C  every segment: composes the summaries in front of it (a short loop of triangular products), runs the stages, writes y.
 // Both passes compute a[n] with the same code, so the numbers they compose are the same numbers.
+//
+// With feedback around the chain (tfx_phaser_feedback_forward) nothing can be scanned stage by stage; phaser_feedback_kernel
+// below has a work split of its own and shares ph_coef, the tiles, the segments and the launch ladder.
 #include "common.h"
 #include "lfo.h"
 #include "scan_tile.h"
@@ -259,14 +262,10 @@ void phaser_plan_info(int64_t rows, int64_t channels, int64_t T, int64_t stages,
                    scratch_bytes);
 }
 
-void phaser_forward(const void *x, void *y, double *coef, int dtype, int64_t rows, int64_t channels, int64_t T, int64_t stages, double fs,
-                    double rate, double min_freq, double max_freq, double phase, double spread, double dry, double wet, int shape,
-                    int64_t position, const int64_t *pos_in, int64_t *pos_out, const double *state_in, double *state_out,
-                    int64_t segments, void *scratch, hipStream_t stream)
+// the sweep's rules, in the order callers have always met them
+static void phaser_check_sweep(const char *what, double fs, double rate, double min_freq, double max_freq, double phase, double spread,
+                               double dry, double wet, int shape, int64_t position)
 {
-    const char *what = "phaser_forward";
-    TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "%s: bad dtype %d", what, dtype);
-    const ScanPlan pl = phaser_plan(what, rows, channels, T, stages, segments);
     TFX_CHECK(shape == TFX_LFO_SINE || shape == TFX_LFO_TRIANGLE, "%s: bad LFO shape %d", what, shape);
     TFX_CHECK(std::isfinite(fs) && fs > 0.0, "%s: the sample rate must be finite and > 0, got %g", what, fs);
     TFX_CHECK(min_freq >= 10.0 && min_freq <= max_freq && max_freq <= 0.45 * fs,
@@ -277,6 +276,32 @@ void phaser_forward(const void *x, void *y, double *coef, int dtype, int64_t row
     TFX_CHECK(std::isfinite(dry), "%s: dry must be finite, got %g", what, dry);
     TFX_CHECK(std::isfinite(wet), "%s: wet must be finite, got %g", what, wet);
     TFX_CHECK(position >= 0 && position <= (1ll << 52), "%s: the position must be in [0, 2^52], got %lld", what, (long long)position);
+}
+
+// the launch's arguments; the reduced parameters as doubles on the host: inc = rate / fs, Lg = ln(max_freq / min_freq), w = pi / fs
+template <typename E>
+static void phaser_fill(PhaserArgs<E> &p, const ScanPlan &pl, const void *x, void *y, double *coef, int64_t channels, int64_t T,
+                        int64_t stages, double fs, double rate, double min_freq, double max_freq, double phase, double spread, double dry,
+                        double wet, int64_t position, const int64_t *pos_in, int64_t *pos_out, const double *state_in, double *state_out,
+                        void *scratch)
+{
+    p.x = (const E *)x; p.y = (E *)y; p.coef = coef; p.state_in = state_in; p.state_out = state_out; p.scratch = (double *)scratch;
+    p.pos_in = pos_in; p.pos_out = pos_out; p.pos = position;
+    p.cut = scan_cut(pl, T);
+    p.channels = (int)channels; p.coef_rows = (int)((spread == 0.0 || channels == 1) ? 1 : channels); p.N = (int)stages;
+    p.inc = rate / fs; p.phase = phase; p.spread = spread; p.fmin = min_freq; p.lg = std::log(max_freq / min_freq); p.w = M_PI / fs;
+    p.dry = dry; p.wet = wet;
+}
+
+void phaser_forward(const void *x, void *y, double *coef, int dtype, int64_t rows, int64_t channels, int64_t T, int64_t stages, double fs,
+                    double rate, double min_freq, double max_freq, double phase, double spread, double dry, double wet, int shape,
+                    int64_t position, const int64_t *pos_in, int64_t *pos_out, const double *state_in, double *state_out,
+                    int64_t segments, void *scratch, hipStream_t stream)
+{
+    const char *what = "phaser_forward";
+    TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "%s: bad dtype %d", what, dtype);
+    const ScanPlan pl = phaser_plan(what, rows, channels, T, stages, segments);
+    phaser_check_sweep(what, fs, rate, min_freq, max_freq, phase, spread, dry, wet, shape, position);
     scan_check_buffers(what, pl, T, x, y, scratch, state_in, state_out);
     TFX_CHECK(!pos_out || pos_out != pos_in, "%s: the new position needs its own buffer", what);
     check_stream_buffers(what, dtype == TFX_F32 ? 4 : 8, x, rows * T, y, rows * T, nullptr, nullptr, 0);
@@ -288,17 +313,260 @@ void phaser_forward(const void *x, void *y, double *coef, int dtype, int64_t row
         }
         return;
     }
-    // the reduced parameters, as doubles on the host: inc = rate / fs, Lg = ln(max_freq / min_freq), w = pi / fs
-    const double par[8] = {rate / fs, phase, spread, min_freq, std::log(max_freq / min_freq), M_PI / fs, dry, wet};
     auto run = [&](auto tag, auto tri) {
         using E = decltype(tag);
         PhaserArgs<E> p{};
-        p.x = (const E *)x; p.y = (E *)y; p.coef = coef; p.state_in = state_in; p.state_out = state_out; p.scratch = (double *)scratch;
-        p.pos_in = pos_in; p.pos_out = pos_out; p.pos = position;
-        p.cut = scan_cut(pl, T);
-        p.channels = (int)channels; p.coef_rows = (int)((spread == 0.0 || channels == 1) ? 1 : channels); p.N = (int)stages;
-        p.inc = par[0]; p.phase = par[1]; p.spread = par[2]; p.fmin = par[3]; p.lg = par[4]; p.w = par[5]; p.dry = par[6]; p.wet = par[7];
+        phaser_fill(p, pl, x, y, coef, channels, T, stages, fs, rate, min_freq, max_freq, phase, spread, dry, wet, position, pos_in, pos_out,
+                    state_in, state_out, scratch);
         const ScanPass<PhaserArgs<E>> ladder[] = {{phaser_kernel<E, tri(), 0>, "phaser_pass_a"}, {phaser_kernel<E, tri(), 1>, "phaser_pass_c"}};
+        scan_launch(ladder, p, pl, stream);
+    };
+    const bool tri = shape == TFX_LFO_TRIANGLE;
+    if (dtype == TFX_F32) tri ? run(float{}, std::true_type{}) : run(float{}, std::false_type{});
+    else tri ? run(double{}, std::true_type{}) : run(double{}, std::false_type{});
+}
+
+// ---- feedback (resonance): tfx_phaser_feedback_forward ----
+// u[n] = x[n] + feedback x_N[n-1] feeds stage 1, and every section has a direct feed-through, so the loop is one sample long and no
+// stage can run ahead of the next.  The chain's map per sample on the N + 1 delayed values s = (x_0 .. x_N)[n-1] is still affine:
+// a run of samples acts as s -> M s + v with M (N+1) x (N+1) dense (coefficients and feedback alone) and v from the signal.
+//
+// Work unit: scan_tile.h's (row, segment) of tiles of ST_TILE samples.  A tile is cut into chunks of L = 8 RL consecutive samples
+// and a chunk belongs to RL = 4, 8 or 16 neighbouring lanes (the power of two that holds the N + 2 runs), so that a summary is
+// never one lane's: lane r of a chunk runs ONE of the chunk's N + 2 runs over its L samples with its N + 1 states in registers
+// (every stage loop is unrolled to PH_MAXN behind the uniform test k <= N, so no register is indexed by a runtime value):
+//   r = 0        the real signal from a zero state: v
+//   r = 1..N+1   the zero signal from the unit state e_{r-1}: column r - 1 of M
+// All of them read the one coefficient track a[n] (computed once per sample, coalesced, into LDS) and the signal from LDS by
+// broadcast; the slots are padded by one word per 32 so that the chunks of a wave sit on different banks.  The summaries go to LDS
+// as rows (v_k, M_k0 .. M_kN).  Then the chunks are chained in order, s_{c+1} = M_c s_c + v_c, one thread per row and a fixed
+// j = 0..N fma chain, which leaves every chunk's true start state in LDS, and lane 0 of every chunk runs its L samples once
+// more from that state and writes dry x + wet x_N over the signal's slot; coalesced stores.  The end state is taken where the
+// run passes sample T - 1 (the tile is zero-padded behind it).
+//
+// segments == 1: one launch (pass C).  Otherwise pass A chains N + 2 columns instead of one -- the real signal from zero and the
+// N + 1 unit states, thread (k, q) of (N+1)(N+2) -- so a segment's (v | M) is built by matrix-vector steps alone, never a
+// matrix product of summaries, and is stored in scratch; pass C composes the summaries in front of its segment with the same
+// step.  Combines are ordered by position and read only what lies in front; M never reads the signal, so a non-finite v travels
+// forward only.
+constexpr int PF_PADDED = ST_TILE + ST_TILE / 32;
+constexpr int PF_SUM_MAX = 16 * (PH_MAXN + 1) * (PH_MAXN + 2);      // doubles of a tile's summaries: RL = 16 is the largest
+constexpr int PF_CHAIN = 2 * (PH_MAXN + 1) * (PH_MAXN + 2);         // pass A: two buffers of (N+1)(N+2); pass C: (chunks + 1)(N + 1)
+constexpr int64_t PF_LDS_BYTES = (2 * PF_PADDED + PF_SUM_MAX + PF_CHAIN) * (int64_t)sizeof(double);
+
+__host__ __device__ inline int pf_shift(int N) { return N + 2 <= 4 ? 2 : N + 2 <= 8 ? 3 : 4; }       // log2 RL
+__device__ __forceinline__ int pf_slot(int a) { return a + (a >> 5); }
+
+template <typename T> struct PhaserFbArgs : PhaserArgs<T> {          // scratch: [rows, segments, (N + 1)(N + 2)], rows (v_k | M_k.)
+    double fb;
+};
+
+// One chain step on Q columns: out[i][q] = (q == 0 ? sum[i][0] : 0) + sum_j sum[i][1 + j] in[j][q] for thread (i, q) = (t / Q, t % Q)
+// of the first (N + 1) Q threads; `sum` is a summary in LDS or in scratch.  The caller's barrier follows.
+__device__ __forceinline__ void pf_chain_step(const double *sum, const double *in, double *out, int N, int Q, int i, int q, bool mine)
+{
+    if (!mine) return;
+    const double *row = sum + i * (N + 2);
+    double acc = q == 0 ? row[0] : 0.0;
+#pragma unroll
+    for (int j = 0; j <= PH_MAXN; ++j)
+        if (j <= N) acc = fma(row[1 + j], in[j * Q + q], acc);
+    out[i * Q + q] = acc;
+}
+
+// PASS 0 = A (a segment's summary to scratch), 1 = C (writes y)
+template <typename T, bool TRI, int PASS>
+__global__ void __launch_bounds__(ST_THREADS) phaser_feedback_kernel(const PhaserFbArgs<T> p)
+{
+    __shared__ double sX[PF_PADDED], sA[PF_PADDED];                  // the tile's signal (then its result) and coefficients
+    __shared__ double sM[PF_SUM_MAX];                                // the chunks' summaries
+    __shared__ double sS[PF_CHAIN];                                  // the chained states
+    const int t = (int)threadIdx.x;
+    const int N = p.N, sh = pf_shift(N), RL = 1 << sh, L = ST_E * RL, chunks = ST_THREADS >> sh, SZ = (N + 1) * (N + 2);
+    const int c = t >> sh, r = t & (RL - 1);
+    const ScanSeg sg = scan_segment(p.cut, PASS == 1 ? p.cut.segments : p.cut.segments - 1);
+    const int64_t row = sg.unit, tile0 = sg.tile0, ntile = sg.ntile, T_ = p.cut.T_;
+    const int seg = sg.seg;
+    const int64_t pos = p.pos_in ? *p.pos_in : p.pos;
+    const T *xr = p.x + row * T_;
+    const double z = p.phase + (double)(row % p.channels) * p.spread;
+    const double off = z - floor(z);
+    const double fb = p.fb;
+    if (PASS == 1 && blockIdx.x == 0 && t == 0 && p.pos_out) *p.pos_out = pos + T_;
+
+    // the chain's columns: pass A (N + 2): the signal's run from zero and the unit states; pass C (1): the true state
+    const int Q = PASS == 0 ? N + 2 : 1, ST = PASS == 0 ? SZ : N + 1;        // ST: the stride between the chain's buffers
+    const int ci = t / Q, cq = t - ci * Q;
+    const bool mine = t < (N + 1) * Q;
+    if (mine) {
+        if (PASS == 0) sS[t] = (cq >= 1 && ci == cq - 1) ? 1.0 : 0.0;
+        else sS[t] = p.state_in ? p.state_in[row * (N + 1) + t] : 0.0;
+    }
+    __syncthreads();
+    if constexpr (PASS == 1) {
+        // the state through the summaries of the segments in front
+        const double *sc = p.scratch + row * p.cut.segments * SZ;
+        for (int g = 0; g < seg; ++g) {
+            pf_chain_step(sc + (int64_t)g * SZ, sS + (g & 1) * ST, sS + ((g + 1) & 1) * ST, N, 1, ci, 0, mine);
+            __syncthreads();
+        }
+        if ((seg & 1) && mine) sS[t] = sS[ST + t];
+        __syncthreads();
+    }
+
+    for (int64_t it = 0; it < ntile; ++it) {
+        const int64_t n0 = (tile0 + it) * ST_TILE;
+        // x_0 and a[n], coalesced, into the slots
+#pragma unroll
+        for (int k = 0; k < ST_E; ++k) {
+            const int a = k * ST_THREADS + t;
+            const int64_t n = n0 + a;
+            const double av = ph_coef<TRI>(pos + n, off, p.inc, p.fmin, p.lg, p.w);
+            sX[pf_slot(a)] = n < T_ ? (double)xr[n] : 0.0;
+            sA[pf_slot(a)] = av;
+            if (PASS == 1 && p.coef && row < p.coef_rows && n < T_) p.coef[row * T_ + n] = av;
+        }
+        __syncthreads();
+
+        // the chunk's N + 2 runs, one per lane
+        if (r <= N + 1) {
+            double s[PH_MAXN + 1];
+#pragma unroll
+            for (int k = 0; k <= PH_MAXN; ++k) s[k] = k == r - 1 ? 1.0 : 0.0;
+            double xn = r - 1 == N ? 1.0 : 0.0;                              // x_N[n-1]
+            const int base = c * L;
+            for (int i = 0; i < L; ++i) {
+                const int sl = pf_slot(base + i);
+                const double a = sA[sl];
+                double cur = fma(fb, xn, r == 0 ? sX[sl] : 0.0), prev = s[0];
+                s[0] = cur;
+#pragma unroll
+                for (int k = 1; k <= PH_MAXN; ++k) {
+                    if (k <= N) {
+                        const double v = fma(-a, s[k], fma(a, cur, prev));
+                        prev = s[k];
+                        s[k] = v;
+                        cur = v;
+                    }
+                }
+                xn = cur;
+            }
+            double *sm = sM + c * SZ + r;
+#pragma unroll
+            for (int k = 0; k <= PH_MAXN; ++k)
+                if (k <= N) sm[k * (N + 2)] = s[k];
+        }
+        __syncthreads();
+
+        // the chunks in order: s_{c+1} = M_c s_c + v_c
+        for (int cc = 0; cc < chunks; ++cc) {
+            const int from = PASS == 0 ? (cc & 1) : cc, to = PASS == 0 ? (from ^ 1) : cc + 1;
+            pf_chain_step(sM + cc * SZ, sS + from * ST, sS + to * ST, N, Q, ci, cq, mine);
+            __syncthreads();
+        }
+
+        if constexpr (PASS == 1) {
+            // once more from the true start, the chunk's lane 0
+            if (r == 0) {
+                const bool last = p.state_out && n0 + ST_TILE >= T_;         // this tile holds the row's last sample
+                const double *s0 = sS + c * ST;
+                double s[PH_MAXN + 1];
+#pragma unroll
+                for (int k = 0; k <= PH_MAXN; ++k) s[k] = k <= N ? s0[k] : 0.0;
+                double xn = s0[N];
+                const int base = c * L;
+                for (int i = 0; i < L; ++i) {
+                    const int sl = pf_slot(base + i);
+                    const double a = sA[sl], x0 = sX[sl];
+                    double cur = fma(fb, xn, x0), prev = s[0];
+                    s[0] = cur;
+#pragma unroll
+                    for (int k = 1; k <= PH_MAXN; ++k) {
+                        if (k <= N) {
+                            const double v = fma(-a, s[k], fma(a, cur, prev));
+                            prev = s[k];
+                            s[k] = v;
+                            cur = v;
+                        }
+                    }
+                    xn = cur;
+                    sX[sl] = p.dry * x0 + p.wet * cur;
+                    if (last && n0 + base + i == T_ - 1) {
+#pragma unroll
+                        for (int k = 0; k <= PH_MAXN; ++k)
+                            if (k <= N) p.state_out[row * (N + 1) + k] = s[k];
+                    }
+                }
+            }
+            __syncthreads();
+            if (mine) sS[t] = sS[chunks * ST + t];                           // the next tile's start; nobody reads these two now
+            T *yr = p.y + row * T_;
+#pragma unroll
+            for (int k = 0; k < ST_E; ++k) {
+                const int a = k * ST_THREADS + t;
+                const int64_t n = n0 + a;
+                if (n < T_) yr[n] = (T)sX[pf_slot(a)];
+            }
+            __syncthreads();                                                 // the slots are free again
+        }
+    }
+
+    if constexpr (PASS == 0) {
+        // chunks is even, so the chain ends in buffer 0: rows (v_k | M_k.), the layout of a summary
+        if (mine) p.scratch[(row * p.cut.segments + seg) * SZ + t] = sS[t];
+    }
+}
+
+static ScanPlan phaser_feedback_plan(const char *what, int64_t rows, int64_t channels, int64_t T, int64_t stages, int64_t segments,
+                                     double feedback)
+{
+    scan_check_sizes(what, rows, channels, T);
+    TFX_CHECK(rows % channels == 0, "%s: %lld rows do not split into items of %lld channels", what, (long long)rows, (long long)channels);
+    TFX_CHECK(stages >= 1 && stages <= PH_MAXN, "%s: stages must be in [1, %d], got %lld", what, PH_MAXN, (long long)stages);
+    TFX_CHECK(std::isfinite(feedback) && std::fabs(feedback) < 1.0, "%s: feedback must be finite with |feedback| < 1 (the loop decays), got %g",
+              what, feedback);
+    return scan_plan(what, rows, 1, T, segments, PH_AUTO_BLOCKS, PH_AUTO_ROWS, (stages + 1) * (stages + 2) * (int64_t)sizeof(double));
+}
+
+void phaser_feedback_plan_info(int64_t rows, int64_t channels, int64_t T, int64_t stages, int64_t segments, double feedback, int64_t *run,
+                               int64_t *tile, int64_t *segments_out, int64_t *launches, int64_t *lds_bytes, int64_t *workgroups,
+                               int64_t *scratch_bytes)
+{
+    const ScanPlan pl = phaser_feedback_plan("phaser_feedback_plan_info", rows, channels, T, stages, segments, feedback);
+    *run = ST_E << pf_shift((int)stages);
+    *tile = ST_TILE;
+    *segments_out = pl.segments;
+    *launches = pl.segments > 1 ? 2 : 1;
+    *lds_bytes = PF_LDS_BYTES;
+    *workgroups = pl.units * pl.segments;
+    *scratch_bytes = pl.scratch_bytes;
+}
+
+void phaser_feedback_forward(const void *x, void *y, double *coef, int dtype, int64_t rows, int64_t channels, int64_t T, int64_t stages,
+                             double fs, double rate, double min_freq, double max_freq, double phase, double spread, double dry, double wet,
+                             double feedback, int shape, int64_t position, const int64_t *pos_in, int64_t *pos_out,
+                             const double *state_in, double *state_out, int64_t segments, void *scratch, hipStream_t stream)
+{
+    const char *what = "phaser_feedback_forward";
+    TFX_CHECK(dtype == TFX_F32 || dtype == TFX_F64, "%s: bad dtype %d", what, dtype);
+    const ScanPlan pl = phaser_feedback_plan(what, rows, channels, T, stages, segments, feedback);
+    if (feedback == 0.0 || rows * T == 0) {      // no loop: the feed-forward kernel and its bits; an empty chunk hands on alike
+        phaser_forward(x, y, coef, dtype, rows, channels, T, stages, fs, rate, min_freq, max_freq, phase, spread, dry, wet, shape, position,
+                       pos_in, pos_out, state_in, state_out, segments, scratch, stream);
+        return;
+    }
+    phaser_check_sweep(what, fs, rate, min_freq, max_freq, phase, spread, dry, wet, shape, position);
+    scan_check_buffers(what, pl, T, x, y, scratch, state_in, state_out);
+    TFX_CHECK(!pos_out || pos_out != pos_in, "%s: the new position needs its own buffer", what);
+    check_stream_buffers(what, dtype == TFX_F32 ? 4 : 8, x, rows * T, y, rows * T, nullptr, nullptr, 0);
+    auto run = [&](auto tag, auto tri) {
+        using E = decltype(tag);
+        PhaserFbArgs<E> p{};
+        phaser_fill<E>(p, pl, x, y, coef, channels, T, stages, fs, rate, min_freq, max_freq, phase, spread, dry, wet, position, pos_in,
+                       pos_out, state_in, state_out, scratch);
+        p.fb = feedback;
+        const ScanPass<PhaserFbArgs<E>> ladder[] = {{phaser_feedback_kernel<E, tri(), 0>, "phaser_feedback_pass_a"},
+                                                    {phaser_feedback_kernel<E, tri(), 1>, "phaser_feedback_pass_c"}};
         scan_launch(ladder, p, pl, stream);
     };
     const bool tri = shape == TFX_LFO_TRIANGLE;

@@ -147,6 +147,13 @@ void phaser_forward(const void *x, void *y, double *coef, int dtype, int64_t row
                     int64_t segments, void *scratch, hipStream_t stream);
 void phaser_plan_info(int64_t rows, int64_t channels, int64_t T, int64_t stages, int64_t segments, int64_t *tile, int64_t *tiles,
                       int64_t *segments_out, int64_t *seg_tiles, int64_t *scratch_bytes);
+void phaser_feedback_forward(const void *x, void *y, double *coef, int dtype, int64_t rows, int64_t channels, int64_t T, int64_t stages,
+                             double fs, double rate, double min_freq, double max_freq, double phase, double spread, double dry, double wet,
+                             double feedback, int shape, int64_t position, const int64_t *pos_in, int64_t *pos_out,
+                             const double *state_in, double *state_out, int64_t segments, void *scratch, hipStream_t stream);
+void phaser_feedback_plan_info(int64_t rows, int64_t channels, int64_t T, int64_t stages, int64_t segments, double feedback, int64_t *run,
+                               int64_t *tile, int64_t *segments_out, int64_t *launches, int64_t *lds_bytes, int64_t *workgroups,
+                               int64_t *scratch_bytes);
 
 // ---- gate.hip ----
 void gate_forward(const void *x, void *y, void *gain, unsigned char *open, int dtype, int64_t groups, int64_t channels, int64_t T,

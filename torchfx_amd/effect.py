@@ -562,18 +562,20 @@ class Phaser(FX):
     """Phaser: :func:`torchfx_amd.phaser.phase_shift` as an effect -- ``stages`` first-order all-pass sections in series whose
     corner frequency an LFO sweeps exponentially between ``min_freq`` and ``max_freq`` Hz at ``rate`` Hz, mixed with the signal:
     ``dry = 1 - mix`` and ``wet = mix`` (``-mix`` with ``invert``, which moves the notches to where the peaks were).  ``spread``
-    shifts the LFO phase by that many cycles per channel index; ``shape`` is "sine" or "triangle".  There is no feedback
-    (regeneration) path around the chain.
+    shifts the LFO phase by that many cycles per channel index; ``shape`` is "sine" or "triangle".  ``feedback`` (resonance,
+    ``|feedback| < 1``) adds the last section's previous output to the first section's input, which deepens the notches; 0 is
+    the feed-forward chain, bit for bit.
 
     ``fs`` comes from the ``Wave`` the effect is piped into when it is None.  Every call starts its sweep at position 0 and its
     sections from silence: the effect is a step of its own in ``Wave.plan()`` (``csrc/phaser.hip``), and a chunked stream needs
     :class:`torchfx_amd.realtime.StatefulPhaser`, which carries the sections' states and the position."""
 
     def __init__(self, rate: float = 0.5, min_freq: float = 200.0, max_freq: float = 2000.0, stages: int = 4, mix: float = 0.5,
-                 invert: bool = False, spread: float = 0.0, shape: str = "sine", fs: int | None = None) -> None:
+                 invert: bool = False, spread: float = 0.0, shape: str = "sine", fs: int | None = None, feedback: float = 0.0) -> None:
         super().__init__()
         self.rate, self.min_freq, self.max_freq, self.stages = rate, min_freq, max_freq, stages
         self.mix, self.invert, self.spread, self.shape, self.fs = mix, bool(invert), spread, shape, fs
+        self.feedback = feedback
         self.params(torch.float32, 48000 if fs is None else fs)         # argument errors now
 
     def params(self, dtype: torch.dtype, fs: int | None = None):
@@ -585,7 +587,7 @@ class Phaser(FX):
 
         mix = _real("mix", self.mix)
         return PhaserParams(fs, dtype, self.stages, self.min_freq, self.max_freq, self.rate, 0.0, 1.0 - mix, -mix if self.invert else mix,
-                            self.spread, self.shape)
+                            self.spread, self.shape, self.feedback)
 
     def route(self, x: Tensor, length: int | None = None) -> str:
         """``native (...)`` or ``numpy on host -- <reason>`` for ``x`` (rows of ``length`` samples, default x's)."""
@@ -594,7 +596,13 @@ class Phaser(FX):
         try:
             P = self.params(x.dtype)
             n = int(x.shape[-1]) if length is None else int(length)
-            info = _ext().phaser_plan_info(n, max(1, math.prod(x.shape[:-1])), int(x.shape[-2]) if x.dim() >= 2 else 1, P.stages)
+            rows, channels = max(1, math.prod(x.shape[:-1])), int(x.shape[-2]) if x.dim() >= 2 else 1
+            if P.feedback != 0.0:
+                fb = _ext().phaser_feedback_plan_info(n, P.feedback, rows, channels, P.stages)
+                return (f"native (phaser_feedback_kernel, {P.stages} stage(s), {P.shape} LFO, feedback {P.feedback:g}: runs of "
+                        f"{fb['run']} in tiles of {fb['tile']}, {fb['segments']} segment(s), {fb['workgroups']} workgroup(s), "
+                        f"{fb['lds_bytes']} B of LDS; " + ("one launch)" if fb["launches"] == 1 else "two launches)"))
+            info = _ext().phaser_plan_info(n, rows, channels, P.stages)
         except (RuntimeError, ValueError, TypeError) as e:
             return f"refused -- {e}"
         launches = "one launch" if info["segments"] == 1 else "two launches"
@@ -610,7 +618,8 @@ class Phaser(FX):
 
     def extra_repr(self) -> str:
         return (f"rate={self.rate}, min_freq={self.min_freq}, max_freq={self.max_freq}, stages={self.stages}, mix={self.mix}, "
-                f"invert={self.invert}, spread={self.spread}, shape={self.shape!r}, fs={self.fs}")
+                f"invert={self.invert}, spread={self.spread}, shape={self.shape!r}, fs={self.fs}"
+                + (f", feedback={self.feedback}" if self.feedback else ""))
 
 
 class Epilogued(FX):

@@ -34,12 +34,16 @@ def _real(name: str, v, what: str = "a finite number") -> float:
 class PhaserParams:
     """What a phaser call works with, checked and reduced: ``fs``, ``stages``, ``min_freq``, ``max_freq``, ``rate``, ``phase``,
     ``dry``, ``wet``, ``spread``, ``shape`` as given, and the three numbers the coefficient track is built from, each computed
-    once as a float64: ``inc = rate / fs`` (cycles per sample), ``lg = ln(max_freq / min_freq)`` and ``w = pi / fs``."""
+    once as a float64: ``inc = rate / fs`` (cycles per sample), ``lg = ln(max_freq / min_freq)`` and ``w = pi / fs``.
+    ``feedback != 0`` adds the resonance path; its rule (finite, ``|feedback| < 1``) is the native plan's own answer
+    (:func:`torchfx_ext.phaser_feedback_plan_info`, host-only) for CPU and device tensors alike, and ``run`` is that plan's
+    ``L``, the samples the host path runs in lockstep as a lane of the device does (0 without feedback)."""
 
-    __slots__ = ("fs", "stages", "min_freq", "max_freq", "rate", "phase", "dry", "wet", "spread", "shape", "inc", "lg", "w")
+    __slots__ = ("fs", "stages", "min_freq", "max_freq", "rate", "phase", "dry", "wet", "spread", "shape", "inc", "lg", "w",
+                 "feedback", "run")
 
     def __init__(self, fs, dtype: torch.dtype, stages=4, min_freq=200.0, max_freq=2000.0, rate=0.5, phase=0.0, dry=0.5, wet=0.5,
-                 spread=0.0, shape="sine") -> None:
+                 spread=0.0, shape="sine", feedback=0.0) -> None:
         fs = _check_fs(fs)
         if dtype not in (torch.float32, torch.float64):
             raise TypeError(f"phase_shift: float32 or float64 signals only, got {dtype}")
@@ -61,6 +65,16 @@ class PhaserParams:
         self.spread = _real("spread", spread, "a finite phase in cycles per channel")
         self.shape = shape
         self.inc, self.lg, self.w = rate / fs, math.log(hi / lo), math.pi / fs
+        if isinstance(feedback, bool) or not isinstance(feedback, numbers.Real):
+            raise ValueError(f"phase_shift: feedback must be a finite number with |feedback| < 1, got {feedback!r}")
+        self.feedback, self.run = float(feedback), 0
+        if self.feedback != 0.0:
+            from torchfx_amd import torchfx_ext
+
+            try:
+                self.run = torchfx_ext.phaser_feedback_plan_info(0, self.feedback, stages=self.stages)["run"]
+            except RuntimeError as e:
+                raise ValueError(f"phase_shift: {str(e).split(': ', 1)[-1]}") from None
 
 
 def _check_position(position) -> int:
@@ -154,6 +168,76 @@ def _phase_shift_host(xr: np.ndarray, P: PhaserParams, channels: int, position: 
     return y.reshape(rows, T), coef, st.reshape(rows, N + 1)
 
 
+def _feedback_step(s: np.ndarray, a: np.ndarray, xin, fb: float, N: int) -> np.ndarray:
+    """One sample of the chain with feedback on the states ``s [..., N + 1]`` in place; returns ``x_N[n]``."""
+    cur = xin + fb * s[..., N]
+    prev = s[..., 0].copy()
+    s[..., 0] = cur
+    for k in range(1, N + 1):
+        v = (a * cur + prev) - a * s[..., k]
+        prev = s[..., k].copy()
+        s[..., k] = v
+        cur = v
+    return cur
+
+
+def _feedback_chunks(x0: np.ndarray, a: np.ndarray, s: np.ndarray, fb: float, N: int, L: int) -> tuple[np.ndarray, np.ndarray]:
+    """``x0 [B, n]`` with ``n`` a multiple of ``L``, ``a [n]``, the start states ``s [B, N + 1]`` -> ``(x_N [B, n], end states)``,
+    blocked as the device is: every chunk of ``L`` samples runs the signal from a zero state (``v``) and the zero signal from
+    the unit states (the columns of ``M``) in lockstep, the chunks are chained in order (``s <- M s + v``), and every chunk runs
+    once more from its true start."""
+    B, n = x0.shape
+    nch = n // L
+    xc, ac = x0.reshape(B, nch, L), a.reshape(nch, L)
+    sv = np.zeros((B, nch, N + 1))
+    sm = np.broadcast_to(np.eye(N + 1), (nch, N + 1, N + 1)).copy()          # [chunk, unit state j, component i]
+    for i in range(L):
+        _feedback_step(sv, ac[:, i], xc[:, :, i], fb, N)
+        _feedback_step(sm, ac[:, i, None], 0.0, fb, N)
+    start = np.empty((B, nch, N + 1))
+    for c in range(nch):
+        start[:, c] = s
+        s = sv[:, c] + s @ sm[c]
+    out = np.empty((B, nch, L))
+    for i in range(L):
+        out[:, :, i] = _feedback_step(start, ac[:, i], xc[:, :, i], fb, N)
+    return out.reshape(B, n), s
+
+
+def _phase_shift_feedback_host(xr: np.ndarray, P: PhaserParams, channels: int, position: int, state: np.ndarray,
+                               want_coef: bool) -> tuple[np.ndarray, np.ndarray | None, np.ndarray]:
+    """:func:`_phase_shift_host` with ``P.feedback != 0``: the loop is one sample long, so a block is not scanned stage by stage
+    but in chunks of ``P.run`` samples (:func:`_feedback_chunks`); a block's last, shorter chunk runs on its own."""
+    rows, T = xr.shape
+    N, fb, L = P.stages, P.feedback, P.run
+    xb = xr.reshape(rows // channels, channels, T)
+    st = state.reshape(rows // channels, channels, N + 1).copy()
+    y = np.empty_like(xb)
+    crow = coef_rows(channels, P.spread)
+    coef = np.empty((crow, T), np.float64) if want_coef else None
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        for n0 in range(0, T, _HOST_BLOCK):
+            n1 = min(T, n0 + _HOST_BLOCK)
+            n = position + np.arange(n0, n1, dtype=np.int64)
+            a = None
+            for c in range(channels):
+                if a is None or crow > 1:
+                    a = coefficient_track(n, P, c)
+                if coef is not None and c < crow:
+                    coef[c, n0:n1] = a
+                x0 = xb[:, c, n0:n1].astype(np.float64)
+                full = (n1 - n0) // L * L
+                xn = np.empty_like(x0)
+                s = st[:, c]
+                if full:
+                    xn[:, :full], s = _feedback_chunks(x0[:, :full], a[:full], s, fb, N, L)
+                if full < n1 - n0:
+                    xn[:, full:], s = _feedback_chunks(x0[:, full:], a[full:], s, fb, N, n1 - n0 - full)
+                st[:, c] = s
+                y[:, c, n0:n1] = (P.dry * x0 + P.wet * xn).astype(xr.dtype)
+    return y.reshape(rows, T), coef, st.reshape(rows, N + 1)
+
+
 def _check_state(state, rows: int, stages: int, device) -> Tensor | None:
     if state is None:
         return None
@@ -185,12 +269,12 @@ def phase_shift_run(x: Tensor, P: PhaserParams, position: int = 0, state: Tensor
 
         with torch.cuda.device(x.device):
             return torchfx_ext.phaser_forward(x, P.stages, P.fs, P.rate, P.min_freq, P.max_freq, P.phase, P.spread, P.dry, P.wet, P.shape,
-                                              position, pos, st, want_coef, segments)
+                                              position, pos, st, want_coef, segments, P.feedback)
     if pos is not None:
         position = _check_position(int(pos))
     a = x.detach().contiguous().numpy()
-    y, coef, new = _phase_shift_host(a.reshape(rows, T), P, channels, position,
-                                     np.zeros((rows, P.stages + 1)) if st is None else st.numpy(), want_coef)
+    host = _phase_shift_feedback_host if P.feedback != 0.0 else _phase_shift_host
+    y, coef, new = host(a.reshape(rows, T), P, channels, position, np.zeros((rows, P.stages + 1)) if st is None else st.numpy(), want_coef)
     return (torch.from_numpy(y.reshape(a.shape)), None if coef is None else torch.from_numpy(coef), torch.from_numpy(new),
             None if pos is None else torch.tensor([position + T], dtype=torch.int64))
 
@@ -198,7 +282,7 @@ def phase_shift_run(x: Tensor, P: PhaserParams, position: int = 0, state: Tensor
 @torch.no_grad()
 def phase_shift(x: Tensor, fs: int, stages: int = 4, min_freq: float = 200.0, max_freq: float = 2000.0, rate: float = 0.5,
                 phase: float = 0.0, dry: float = 0.5, wet: float = 0.5, spread: float = 0.0, shape: str = "sine", position: int = 0,
-                state: Tensor | None = None, return_state: bool = False, return_coef: bool = False):
+                state: Tensor | None = None, return_state: bool = False, return_coef: bool = False, feedback: float = 0.0):
     """Phaser: ``x [T]``, ``[C, T]`` or ``[B, C, T]`` (float32 / float64) -> the same shape, dtype and device, computed along
     the last axis; with ``return_coef`` also the coefficient track ``a[n]`` (float64 ``[C, T]``, or ``[1, T]`` when ``spread ==
     0`` or ``C == 1``), with ``return_state`` also the end state (float64 ``[rows, stages + 1]``), in that order.
@@ -230,11 +314,20 @@ def phase_shift(x: Tensor, fs: int, stages: int = 4, min_freq: float = 200.0, ma
       are unaffected.
 
     Rules: ``1 <= stages <= 12``; ``10 Hz <= min_freq <= max_freq <= 0.45 fs``; ``0 < rate < fs / 2``; ``0 <= position <= 2^52``;
-    finite ``dry``, ``wet``, ``phase`` and ``spread``.  ``ValueError`` / ``TypeError`` otherwise.  Feedback (regeneration) around
-    the chain, per-stage sweeps, an externally supplied coefficient track, tempo-synced rates, autograd and axes other than the
-    last are not provided."""
+    finite ``dry``, ``wet``, ``phase`` and ``spread``.  ``ValueError`` / ``TypeError`` otherwise.
+
+    **Feedback (resonance).**  With ``feedback != 0`` the last section's previous output is added to the first section's input:
+    ``u[n] = x[n] + feedback x_N[n-1]``, ``x_0[n] = u[n]``, the sections as above, and ``y[n] = dtype(dry x[n] + wet x_N[n])``
+    -- ``dry`` multiplies the input, not ``u``.  The coefficient track is the same code and the same bits; ``state[:, 0]`` is
+    then ``u[-1]``, the loop's own value.  ``feedback`` must be finite with ``|feedback| < 1`` (every section has unit gain, so
+    the loop decays), a ``ValueError`` from the native plan otherwise; ``feedback = 0`` is the formula above, bit for bit.  The
+    loop is one sample long, so a row is a scan over dense ``(N + 1) x (N + 1)`` maps ``s -> M s + v`` (``csrc/phaser.hip``,
+    ``phaser_feedback_kernel``; the host path blocks its rows the same way).  Everything under "what follows" holds as stated.
+
+    Per-stage sweeps, an externally supplied coefficient track, tempo-synced rates, autograd and axes other than the last are not
+    provided."""
     _check_signal(x, "phase_shift")
-    P = PhaserParams(fs, x.dtype, stages, min_freq, max_freq, rate, phase, dry, wet, spread, shape)
+    P = PhaserParams(fs, x.dtype, stages, min_freq, max_freq, rate, phase, dry, wet, spread, shape, feedback)
     y, coef, st, _ = phase_shift_run(x, P, position, state, bool(return_coef))
     out = (y,) + ((coef,) if return_coef else ()) + ((st,) if return_state else ())
     return out if len(out) > 1 else y

@@ -929,7 +929,8 @@ class StatefulPhaser(Phaser):
     bit-identical to the one-shot call's; the outputs equal :func:`~torchfx_amd.phaser.phase_shift` on the whole signal to
     float64 round-off and not bit for bit: the scan's association follows the cut.  After a NaN or Inf the state of its row is
     non-finite and stays so until :meth:`reset_state`.  Device float32 / float64 chunks run :func:`torchfx_ext.phaser_forward`
-    (one launch for a chunk of up to 2048 samples), CPU chunks the host path."""
+    (one launch for a chunk of up to 2048 samples), CPU chunks the host path.  With ``feedback`` the carried state has the same
+    shape -- ``x_0[-1]`` is then the loop's own ``u[-1]`` -- so the stream passes the argument down and nothing else changes."""
 
     def __init__(self, *args, **kwargs) -> None:
         super().__init__(*args, **kwargs)
@@ -941,7 +942,8 @@ class StatefulPhaser(Phaser):
 
     def _capture_key(self) -> tuple:
         """What a captured HIP graph of this effect bakes in: every parameter of the launch."""
-        return (self.rate, self.min_freq, self.max_freq, self.stages, self.mix, self.invert, self.spread, self.shape, self.fs)
+        return (self.rate, self.min_freq, self.max_freq, self.stages, self.mix, self.invert, self.spread, self.shape, self.fs,
+                self.feedback)
 
     def _sync_history(self) -> None:
         """Nothing to resize: a changed ``stages`` restarts the stream in :meth:`forward`."""

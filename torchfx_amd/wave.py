@@ -251,7 +251,7 @@ def _member_key(m: nn.Module, guard: list) -> tuple:
     elif isinstance(m, ModulatedDelay):
         k += (tuple(m.voices), m.dry, m.spread, m.shape, m.interpolation, m.pad, m.fs)
     elif isinstance(m, Phaser):
-        k += (m.rate, m.min_freq, m.max_freq, m.stages, m.mix, m.invert, m.spread, m.shape, m.fs)
+        k += (m.rate, m.min_freq, m.max_freq, m.stages, m.mix, m.invert, m.spread, m.shape, m.fs, m.feedback)
     elif isinstance(m, Freeverb):
         k += (m.room_size, m.damping, m.wet, m.dry, m.width, m.tail, m.fs)
     elif isinstance(m, Waveshaper):
