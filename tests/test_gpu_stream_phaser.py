@@ -1,7 +1,8 @@
 """StatefulPhaser on the device: chunkings of sizes 1, 8, 513 and ragged over (2, 3 tile + 17) against the one-shot call -- the
 coefficient track bit for bit, the outputs within 16 E_REF of the long-double loop fed that track (tests/phaser_reference.py), not
 bit for bit: the scan's association follows the cut --, StreamProcessor eager and as a replayed HIP graph, a parameter change
-mid-stream and a row-count change, which restarts the stream."""
+mid-stream and a row-count change, which restarts the stream; StatefulPhaser(feedback=0.7) over chunks 300, 1, 2049, 7, none and
+the rest against the loop with feedback (tests/phaser_feedback_reference.py), the device position and the state after every chunk."""
 import numpy as np
 import pytest
 import torch
@@ -133,6 +134,33 @@ def test_a_row_count_or_stage_change_restarts_the_stream():
     rest = eff(a[:, 300:].contiguous())
     whole = Phaser(fs=FS, **dict(KW, stages=6))(a)
     assert torch.allclose(torch.cat([first, rest], -1), whole, rtol=0, atol=2e-7)
+
+
+@pytest.mark.parametrize("dt", list(DTYPES))
+def test_feedback_chunks_carry_the_state_and_the_device_position(dt):
+    """StatefulPhaser(feedback=0.7) on the device (phaser_feedback_kernel with pos_in / pos_out): chunks of 300, 1, 2049, 7, none
+    and the rest against the long-double loop with feedback fed the one-shot call's track; the position and the state's shape after
+    every chunk; the empty chunk moves neither."""
+    from tests import phaser_feedback_reference as F
+    from torchfx_amd.effect import Phaser
+    from torchfx_amd.phaser import phase_shift_run
+    from torchfx_amd.realtime import StatefulPhaser
+
+    kw = dict(rate=30.0, stages=4, spread=0.25, fs=FS, feedback=0.7, mix=0.5)
+    x = signal((2, 4000), 20, DTYPES[dt]).to(DEV)
+    y1, coef, st1, _ = phase_shift_run(x, Phaser(**kw).params(DTYPES[dt]), 0, None, True)
+    ref = F.reference(x.double().cpu().numpy(), coef.cpu().numpy(), 4, 0.5, 0.5, 0.7, 2)
+    F.check(y1.cpu().numpy(), ref.y, ref.e_ref, f"Phaser(feedback=0.7) one-shot {dt}")
+    eff, edges, ys = StatefulPhaser(**kw), np.cumsum([0, 300, 1, 2049, 7, 0, 1643]), []
+    for a, b in zip(edges[:-1], edges[1:]):
+        before = None if eff._hist is None else (eff._hist.clone(), eff._pos.clone())
+        ys.append(eff(x[:, a:b].contiguous()))
+        assert ys[-1].shape == (2, b - a) and int(eff._pos) == b and eff._pos.is_cuda
+        assert eff._hist.shape == (2, 5) and eff._hist.dtype == torch.float64
+        if a == b:
+            assert torch.equal(eff._hist, before[0]) and torch.equal(eff._pos, before[1])
+        F.check_state(eff._hist.cpu().numpy(), ref.states[:, b - 1], ref.e_ref_s, f"feedback stream {dt}: state after {b}", f"stream {dt}")
+    F.check(torch.cat(ys, -1).cpu().numpy(), ref.y, ref.e_ref, f"StatefulPhaser(feedback=0.7) chunks {dt}")
 
 
 def test_zz_report():

@@ -1,5 +1,7 @@
 """Feedback (regeneration) of the modulated delay line without a device: the NumPy host path against the per-sample loop of
-tests/modulation_feedback_reference.py within its derived bound, every argument rule feedback adds, the plan query, the routes."""
+tests/modulation_feedback_reference.py within its derived bound -- every case of its tables, so that host and device are held
+to one reference --, the plan each case was built for (packing, packing cut by LDS, the rpw == 1 fallback, the lane seams 32 / 33,
+64, 128 / 129, eight voices), every argument rule feedback adds, the plan query, the routes."""
 import math
 
 import numpy as np
@@ -14,12 +16,42 @@ from tests import modulation_feedback_reference as F
 @pytest.mark.parametrize("interpolation,lfo,dtype", [("linear", "sine", torch.float32), ("cubic", "triangle", torch.float64),
                                                       ("cubic", "sine", torch.float32), ("linear", "triangle", torch.float64)])
 def test_host_path_against_the_definition(interpolation, lfo, dtype, name):
+    F.assert_plan(name, interpolation)
     x = torch.from_numpy(np.array(F.case(name, interpolation, lfo)[0])).to(dtype)
     kw = dict(dry=F.DRY, spread=F.SPREAD, shape=lfo, interpolation=interpolation, position=F.POSITION, feedback=F.TABLES[name][1])
     B = F.TABLES[name][2]
     for n in (F.T, 0, 1, B - 1, B, B + 1):                             # the reference is causal: a prefix is the shorter call
         y = f.modulated_delay(x[..., :n].contiguous(), F.FS, F.voices(name, interpolation), **kw)
         F.check(y.numpy(), name, interpolation, lfo, f"host {name} {interpolation} {lfo} T = {n}", length=n)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_host_path_on_the_longest_ring(dtype):
+    """B1long: block 1 with a ring of 8192 samples that wraps -- rows_per_wave falls back to 1 and the launch takes 64 KiB."""
+    interpolation, lfo = F.LONG_PAIR
+    assert F.assert_plan("B1long", interpolation)["steps"] == F.shape_of("B1long")[1]
+    x = torch.from_numpy(np.array(F.case("B1long", interpolation, lfo)[0])).to(dtype)
+    y = f.modulated_delay(x, F.FS, F.voices("B1long", interpolation), dry=F.DRY, spread=F.SPREAD, shape=lfo, interpolation=interpolation,
+                          position=F.POSITION, feedback=F.table("B1long")[1])
+    F.check(y.numpy(), "B1long", interpolation, lfo, f"host B1long {interpolation} {lfo} {dtype}")
+
+
+@pytest.mark.parametrize("interpolation", ["linear", "cubic"])
+def test_the_plans_the_cases_were_built_for(interpolation):
+    """Every row of the case table reports the geometry it was chosen to reach, and the geometry follows the batch."""
+    for name in list(F.TABLES) + list(F.LONG_TABLES):
+        q = F.assert_plan(name, interpolation)
+        batch, n = F.shape_of(name)
+        assert q["steps"] == -(-n // q["block"]) and q["workgroups"] == 2 * -(-batch // q["rows_per_wave"])
+        assert q["lds_bytes"] <= 65536 and q["ring"] & (q["ring"] - 1) == 0
+    # the stride between a wave's rings: ring + B when packed, the ring alone when the wave holds one row
+    assert F.plan("B16", interpolation)["lds_bytes"] == 4 * (64 + 16) * 8
+    assert F.plan("B5long", interpolation)["lds_bytes"] == 7 * (1024 + 5) * 8
+    assert F.plan("B1long", interpolation)["lds_bytes"] == 8192 * 8               # not (8192 + 1) * 8: that would not fit
+    assert F.plan("B33", interpolation)["lds_bytes"] == F.plan("B33", interpolation)["ring"] * 8
+    # waves: B16 4 + 1, B32 2 + 2 + 1, B5long 7 + 2; a batch of rows_per_wave + 1 opens the second wave
+    for name, rpw in (("B16", 4), ("B32", 2), ("B5long", 7), ("V8", 8)):
+        assert F.plan(name, interpolation, batch=rpw)["workgroups"] == 2 and F.plan(name, interpolation, batch=rpw + 1)["workgroups"] == 4
 
 
 def test_feedback_zero_is_the_call_without_it_and_the_effects_carry_the_loop_gain():

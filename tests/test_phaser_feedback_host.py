@@ -1,5 +1,6 @@
 """Phaser feedback (resonance) without a device: the argument rule, the C entries, the plan query, feedback = 0, the NumPy host
-path against the per-sample loop of tests/phaser_feedback_reference.py within 16 E_REF, and StatefulPhaser's chunks."""
+path against the per-sample loop of tests/phaser_feedback_reference.py within 16 E_REF and its end state within 16 E_REF_S -- at
+1, 4 and 12 stages, at the lane-bucket edges 2, 3, 6 and 7 and with the triangle LFO --, and StatefulPhaser's chunks."""
 import ctypes
 import math
 
@@ -62,19 +63,33 @@ def test_feedback_zero_is_the_call_without_it():
     assert torch.equal(f.Phaser(fs=FS, feedback=0.0)(x), f.Phaser(fs=FS)(x))
 
 
-@pytest.mark.parametrize("stages,feedback,dtype", [(1, 0.7, torch.float32), (4, -0.9, torch.float64), (12, 0.7, torch.float64)])
-def test_host_path_against_the_definition(stages, feedback, dtype):
+def host_against_the_definition(stages, feedback, dtype, shape="sine"):
     x = signal((2, 2, 1117), 10 + stages)                               # 1117: whole runs of 32, 64 and 128 and a shorter last one
     state = np.random.default_rng(3).uniform(-1.0, 1.0, (4, stages + 1))
     y, coef, st = f.phase_shift(x.to(dtype), FS, stages, feedback=feedback, state=torch.from_numpy(state), return_coef=True,
-                                return_state=True, **KW)
-    F.check_coef(coef.numpy(), FS, 200.0, 2000.0, KW["rate"], KW["phase"], KW["spread"])
-    yld, sld, e_ref = F.reference(x.numpy().reshape(4, -1), coef.numpy(), stages, KW["dry"], KW["wet"], feedback, 2, state)
-    F.check(y.numpy().reshape(yld.shape), yld, e_ref, f"host N={stages} fb={feedback}")
-    assert st.shape == (4, stages + 1) and np.allclose(st.numpy(), sld.astype(np.float64), rtol=0, atol=1e-6)      # the bound is the outputs'
-    plain = f.phase_shift(x.to(dtype), FS, stages, state=torch.from_numpy(state), **KW)
+                                return_state=True, shape=shape, **KW)
+    F.check_coef(coef.numpy(), FS, 200.0, 2000.0, KW["rate"], KW["phase"], KW["spread"], shape)
+    ref = F.reference(x.numpy().reshape(4, -1), coef.numpy(), stages, KW["dry"], KW["wet"], feedback, 2, state)
+    yld, e_ref = ref.y, ref.e_ref
+    F.check(y.numpy().reshape(yld.shape), yld, e_ref, f"host N={stages} fb={feedback} {shape}")
+    assert st.shape == (4, stages + 1) and np.allclose(st.numpy(), ref.state.astype(np.float64), rtol=0, atol=1e-6)
+    F.check_state(st.numpy(), ref.state, ref.e_ref_s, f"host N={stages} fb={feedback} {shape}", "host")   # the state's own bound
+    plain = f.phase_shift(x.to(dtype), FS, stages, state=torch.from_numpy(state), shape=shape, **KW)
     gap = np.abs(plain.numpy().astype(np.float64) - yld.reshape(x.shape).astype(np.float64)).max(-1)
     assert (gap > 100.0 * (16.0 * e_ref + 2.0 ** -24 * np.abs(yld).max())).all(), "feedback is not at work"
+
+
+@pytest.mark.parametrize("stages,feedback,dtype", [(1, 0.7, torch.float32), (4, -0.9, torch.float64), (12, 0.7, torch.float64)])
+def test_host_path_against_the_definition(stages, feedback, dtype):
+    host_against_the_definition(stages, feedback, dtype)
+
+
+@pytest.mark.parametrize("stages,feedback,dtype,shape", [
+    (2, 0.7, torch.float64, "sine"), (3, -0.9, torch.float32, "sine"), (6, 0.7, torch.float64, "sine"), (7, -0.9, torch.float64, "sine"),
+    (7, 0.7, torch.float64, "triangle")])
+def test_host_path_at_the_bucket_edges_and_with_the_triangle(stages, feedback, dtype, shape):
+    """N + 2 = 4 and 8 fill a chunk's lanes, 3 and 7 open the next bucket; the NumPy path has the same run and chunk structure."""
+    host_against_the_definition(stages, feedback, dtype, shape)
 
 
 def test_stateful_phaser_chunks_equal_the_one_shot_call():
@@ -85,6 +100,6 @@ def test_stateful_phaser_chunks_equal_the_one_shot_call():
     cuts = np.cumsum([0, 300, 1, 2049, 7, 1643])
     y = torch.cat([eff(x[:, a:b].contiguous()) for a, b in zip(cuts[:-1], cuts[1:])], -1)
     _, coef = f.phase_shift(x, FS, rate=30.0, spread=0.25, feedback=0.7, return_coef=True)
-    yld, _, e_ref = F.reference(x.numpy(), coef.numpy(), 4, 0.5, 0.5, 0.7, 2)
+    yld, _, e_ref, *_ = F.reference(x.numpy(), coef.numpy(), 4, 0.5, 0.5, 0.7, 2)
     F.check(y.numpy(), yld, e_ref, "StatefulPhaser(feedback=0.7) chunks")
     F.check(f.Phaser(rate=30.0, stages=4, spread=0.25, fs=FS, feedback=0.7)(x).numpy(), yld, e_ref, "Phaser(feedback=0.7)")
